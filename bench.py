@@ -10,15 +10,24 @@ log-assignment, match filtering and the ragged match lists).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: bench.py spawns the same N ranks itself on a free loopback port)
+    python bench.py ... --full          (everything beyond the headline, see below)
+    python bench.py ... --dump-outputs DIR
 
 N > 1: one process per GPU, every rank matches its own 32 pairs (weak scaling, no data-path
 collective) and the match indices are all-gathered over RCCL each step (lightglue_amd.parallel).
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 with the
+driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step, the workload).
+--full adds what takes instrumentation or runs of its own:
   roofline     — dominant kernel class, measured with HIP events on the launch stream over the timed
                  region (engine-side events, include/lightglue_amd.h lg_engine_profile_*)
+  calibration  — dense-MFMA spin, board power, shader clock inside the tail kernel
+  probes       — synchronous forward, world-of-one result gather, PCIe-inclusive feed (one GPU), RCCL block (N > 1)
+  parity       — the timed batch against the reference's fixture
   cpu_baseline — the port of the reference's CPU path (oracle/, on torch's CPU kernels) timed on this host's
                  cores on a bounded sample of the same workload (N=1, rank 0 only)
+--dump-outputs DIR writes the step output of the last timed step (rank 0: what forward() hands back)
+to DIR/<name>.npy in float32 / float64, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -198,6 +207,53 @@ def parity_block(gpu_out, refs, n, m, source, tol=1e-3, filter_threshold=0.1):
             "max_dscore": maxd, "score_tolerance": tol, "source": source}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: forward()'s dict of the last timed step as DIR/<name>.npy.  Float tensors are written as float32 (float64 stays), integer
+    ones (match indices, stop layers) as float64, which holds them exactly.  The ragged per-pair lists are concatenated: `matches` as rows
+    (pair, index0, index1), `scores` as one vector in the same order.  Above `limit` bytes a fixed, seeded sample of whole pairs is written."""
+    def dense(v):
+        a = v.detach().cpu().numpy()
+        return a.astype(np.float32 if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else np.float64)
+
+    tensors = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    lists = {k: v for k, v in out.items() if isinstance(v, list) and all(torch.is_tensor(t) for t in v)}
+    scalars = {k: v for k, v in out.items() if isinstance(v, (int, float)) and not isinstance(v, bool)}   # `stop` of a one-pair batch
+    batch = out["matches0"].shape[0]
+    pairs = np.arange(batch)
+
+    def build(pairs):
+        arrays = {k: np.asarray([v], np.float64) for k, v in scalars.items()}
+        for k, v in tensors.items():
+            arrays[k] = dense(v[torch.as_tensor(pairs, device=v.device)] if v.dim() and v.shape[0] == batch else v)
+        for k, v in lists.items():
+            parts = [dense(v[b]).reshape(v[b].shape[0], int(np.prod(v[b].shape[1:]))) for b in pairs]
+            if k == "matches":
+                parts = [np.concatenate([np.full((len(p), 1), b, np.float64), p], axis=1) for b, p in zip(pairs, parts)]
+            arrays[k] = np.concatenate(parts) if parts else np.zeros((0, 3 if k == "matches" else 1))
+            if k != "matches":
+                arrays[k] = arrays[k].reshape(-1)
+        return arrays
+
+    arrays = build(pairs)
+    size = lambda arrays: sum(a.nbytes for a in arrays.values())
+    total = size(arrays)
+    if total > limit:
+        order = np.random.default_rng(seed).permutation(batch)   # the sample is a prefix of one seeded permutation
+        keep = batch
+        while size(arrays) > limit and keep > 1:
+            keep = max(1, min(keep - 1, int(keep * limit / size(arrays))))
+            pairs = np.sort(order[:keep])
+            arrays = build(pairs)
+        print(f"bench: --dump-outputs wrote a seeded sample of {keep} of {batch} pairs ({total / 2**20:.1f} MB in all)", file=sys.stderr)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    return sorted(arrays)
+
+
 def batch_kwargs(recipe):
     """make_batch keywords of a recipe: "D" = trained-model statistics (descriptor norms in [0.5, 3], noisier copies)."""
     return dict(synthetic.RECIPE_D_DATA) if recipe == "D" else {}
@@ -268,7 +324,12 @@ def main():
     ap.add_argument("--no-calibration", action="store_true", help="skip the 25 ms dense-MFMA spin that measures what the box sustains (profiling runs)")
     ap.add_argument("--no-fuse-next", action="store_true", help="run the q/k/v projections as their own kernels instead of inside the previous block's tail kernel")
     ap.add_argument("--unfused", action="store_true", help="use the per-op kernels instead of the fused block tail")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel-class events and rooflines, MFMA / power / clock calibration, "
+                    "the synchronous-forward, gather and PCIe probes, the RCCL block, parity and the CPU baseline (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the output of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N` (no launcher): spawn the N ranks ourselves — one process per GPU through
@@ -394,12 +455,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # Per-class kernel times (HIP events around every launch) are taken over the WARM-UP steps; in the timed region only
+    # --full: per-class kernel times (HIP events around every launch) are taken over the WARM-UP steps; in the timed region only
     # the dominant class keeps its events (the roofline leg needs exactly that kernel's launch duration, live), so the
     # headline is not taxed by ~90 event records per step.  With --warmup < 2 everything is timed in the timed region.
+    # A plain run records no events at all.
     warm_prof = {}
     dom_class = None
-    if args.warmup >= 2:
+    out = None
+    if args.full and args.warmup >= 2:
         out = step()
         model.profile(True, dev)
         for _ in range(args.warmup - 1):
@@ -423,8 +486,9 @@ def main():
             _cabi.check(_cabi.load().lg_debug_mfma_sustained(C.byref(tf), C.byref(mhz), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return round(tf.value, 1), round(mhz.value, 1)
 
-    sustained_tflops, sustained_mhz = (None, None) if args.no_calibration else mfma_sustained()
-    model.profile(True, dev, only=dom_class)
+    sustained_tflops, sustained_mhz = mfma_sustained() if (args.full and not args.no_calibration) else (None, None)
+    if args.full:
+        model.profile(True, dev, only=dom_class)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -433,8 +497,17 @@ def main():
     out = last if last is not None else out
     barrier()
     dt = time.perf_counter() - t0
-    prof = model.profile_read(dev)
-    model.profile(False, dev)
+    prof = {}
+    if args.full:
+        prof = model.profile_read(dev)
+        model.profile(False, dev)
+    if world > 1:
+        import torch.distributed as dist
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
     def tail_clock_mhz():
         # the shader clock the chip gives the fused tail INSIDE a forward (power management): shader cycles between a workgroup's first and last stamp /
@@ -492,15 +565,13 @@ def main():
         except Exception as exc:
             return {"error": repr(exc)[:200]}
 
-    power = power_probe() if (rank == 0 and world == 1 and not args.no_calibration) else None
-    kernel_clock = tail_clock_mhz() if (rank == 0 and not args.no_calibration and args.precision == "f16x3" and not adaptive) else None   # (every tile live: no stale stamps)
+    calibrate = args.full and not args.no_calibration
+    power = power_probe() if (rank == 0 and world == 1 and calibrate) else None
+    kernel_clock = tail_clock_mhz() if (rank == 0 and calibrate and args.precision == "f16x3" and not adaptive) else None   # (every tile live: no stale stamps)
     rccl = None
     sync_value = None
-    if world > 1:
+    if args.full and world > 1:
         import torch.distributed as dist
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
         # what the collective looked like from inside the job (SCALE_r*.json then shows that RCCL saw N ranks): the result gather of
         # one step timed ALONE with events on this rank's stream (in the timed loop it runs on a side stream under the next forward)
         width = 3 * n + 3 * m + 2   # LG_WIRE_WIDTH: matches0 | scores0 | matches1 | scores1 | stop | status | prune0 | prune1
@@ -527,7 +598,7 @@ def main():
                 "gather_ms_alone": e0.elapsed_time(e1) / 20, "gather_overlap": "gather, unpack kernel and the copy of the [3][B] host block run on a side stream behind an event, under step i+1's forward",
                 "rank0_cpu_affinity": rank_affinity,
                 "step_output_note": "the N > 1 step returns the same dict as the N = 1 step (see step_output): every rank rebuilds it for the WHOLE batch from the gathered rows"}
-    elif not args.no_pipeline:
+    elif args.full and world == 1 and not args.no_pipeline:
         # the reference's forward() is synchronous; the headline loop defers each step's host sync by one step.  The same K
         # steps once more with a synchronous forward per step, reported beside it
         torch.cuda.synchronize(dev)
@@ -538,7 +609,7 @@ def main():
         sync_value = B * args.steps / (time.perf_counter() - ts)
         del out_sync
     gather_probe = None
-    if world == 1 and not args.no_gather_probe:
+    if args.full and world == 1 and not args.no_gather_probe:
         # what the pair-sharded path's result gather costs a step when it runs beside the next forward: the same K steps through
         # PairShardedMatcher in a world of ONE over RCCL — engine-packed wire rows, all_gather_into_tensor on the side stream behind an event, unpack
         # kernel — against the plain pipelined loop above.  At N > 1 the collective is the same call with N - 1 more peers on the xGMI ring.
@@ -570,7 +641,7 @@ def main():
             gather_probe = {"error": repr(exc)[:300]}
 
     pcie_probe = None
-    if world == 1 and not args.no_gather_probe and lanes is None and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_gather_probe and lanes is None and not args.no_pipeline:
         # PCIe-inclusive rate (never `value`: the reference's contract, and this boundary's, is tensors already in HBM): the same K pipelined steps with every batch
         # starting in PINNED HOST memory, (a) copied on the compute stream in front of its forward (what `batch_to_device` + forward does, ref utils.py:63-69),
         # (b) through lightglue_amd.prefetch_to_device: two batches ahead on a copy stream, i.e. under the previous forward
@@ -600,33 +671,6 @@ def main():
     if rank == 0:
         total_pairs = B * world * args.steps
         value = total_pairs / dt
-        fl = flops_per_launch(B, n, m)
-        timed = {k: v for k, v in prof.items() if v[1] > 0}
-        classes_seen = set(timed) | set(warm_prof)
-        fused_next = "fused_tail" in classes_seen and "gemm_qkv_cross" not in classes_seen
-        if fused_next:
-            # the tail kernel also runs the NEXT block's q/k/v projection (L cross + L-1 self projections over 2L tail
-            # launches per forward): charge their algorithmic FLOPs to the launches that execute them
-            fl["fused_tail"] += (L * fl["gemm_qkv_cross"] + (L - 1) * fl["gemm_qkv_self"]) / (2 * L)
-            if "gemm_final_proj" not in classes_seen:   # fixed depth: the LAST tail launch also runs the final projection of the log assignment
-                fl["fused_tail"] += fl["gemm_final_proj"] / (2 * L)
-        dom = max((k for k in timed if k in fl), key=lambda k: timed[k][0])
-        dom_ms = timed[dom][0] / timed[dom][1]
-        achieved = fl[dom] / (dom_ms * 1e-3) / 1e12
-        peak = 157.3 if args.precision == "fp32" else 2500.0  # dense MFMA peak, MI355X_MICROARCH.md
-        tkey = f"{args.precision}/{args.attention or args.precision}/B{B}/N{n}/"
-        traffic_dom = pmc_traffic(tkey + dom + ("+next" if fused_next and dom == "fused_tail" else ""))
-        traffic_assign = pmc_traffic(tkey + "assign_sweeps")
-        if warm_prof:   # per-class table from the warm-up steps; the dominant class from the timed region
-            kernel_ms = {k: round(v[0], 4) for k, v in warm_prof.items()}
-            kernel_ms[dom] = round(timed[dom][0] / args.steps, 4)
-            timed = {**{k: (v[0] * args.steps, v[1] * args.steps) for k, v in warm_prof.items()}, dom: timed[dom]}
-        else:
-            kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in timed.items()}
-        # MFMAs issued per algorithmic MAC: linear layers 3 in f16x3 (the projection's x operand is one plane in the fast opt-in: its
-        # share of the tail's MACs runs 2), attention 3 with split operands, 1 otherwise
-        mfma_per_mac_attn = 3 if (args.precision == "f16x3" and not args.attention) else 1
-        mfma_per_mac_linear = (3 if not args.attention else round((3 * 393216 + 2 * 163840) / 557056, 3)) if args.precision == "f16x3" else 1
         res = {
             "metric": ("image-pairs/s at N=M=1024, 9 layers; match-index parity vs ref" if args.config == 2 else
                        f"image-pairs/s at N={n} M={m}, 9 layers ({'adaptive depth/width' if adaptive else 'pruning off'}, {dim}-d descriptors); match-index parity vs ref"),
@@ -655,61 +699,91 @@ def main():
                                            f"{args.inflight} whole batches in flight (lightglue_amd.InflightMatcher: step i on lane i % {args.inflight}, one engine + one HIP stream per lane); a step's full output dict is built when its lane is used next, all K inside the timed region; "
                                            "event-timed launches (roofline legs) overlap the other lanes' kernels and read longer than alone" if lanes is not None else
                                            "output assembly (the forward's one host sync) of step i overlaps the forward of step i+1; all K outputs are built inside the timed region")},
-            "roofline": {"bound": "mfma", "kernel": dom + (" (+ next block's q/k/v projection)" if fused_next and dom == "fused_tail" else ""), "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "traffic": traffic_dom[0], "traffic_source": traffic_dom[1],
-                         "avg_launch_ms": dom_ms, "algorithmic_flops_per_launch": fl[dom],
-                         "sustained_peak": sustained_tflops, "frac_of_sustained": (achieved / sustained_tflops if sustained_tflops else None),
-                         # matrix-core work actually ISSUED per second: the split-f16 products cost 3 MFMAs per algorithmic MAC
-                         "mfma_per_mac": mfma_per_mac_linear, "issued_tflops": achieved * mfma_per_mac_linear,
-                         "note": ("ADAPTIVE config: pairs stop early and rows are pruned during the forward, so the FLOPs of the full N x M shape charged to every launch are an UPPER bound (achieved / frac overstate).  " if adaptive else "")
-                                 + "algorithmic FLOPs (2/MAC) of one launch / HIP-event launch duration; split f16 issues 3 MFMAs per algorithmic MAC.  "
-                                 "peak = nominal dense bf16 / f16 (2.4 GHz); sustained_peak = what a dense bf16 MFMA spin "
-                                 "reaches on THIS box right before the timed region (power-managed clock, see effective_mfma_clock_mhz)"},
-            # the HBM-bound stage of the path: dual log-softmax + argmax sweeps over the similarity matrix
-            "roofline_hbm": ({"bound": "hbm", "kernel": "assign (lse_sweep + argmax_sweep + merges + finalize)",
-                              "achieved": hbm_bytes_assign(B, n, m) / (timed["assign"][0] / timed["assign"][1] * 1e-3) / 1e9,
-                              "peak": 8000.0, "unit": "GB/s",
-                              "frac": hbm_bytes_assign(B, n, m) / (timed["assign"][0] / timed["assign"][1] * 1e-3) / 1e9 / 8000.0,
-                              "algorithmic_bytes_per_launch": hbm_bytes_assign(B, n, m),
-                              "traffic": traffic_assign[0], "traffic_source": traffic_assign[1]} if "assign" in timed else None),
-            # the attention GEMMs against the same peak (north_star asks for it): algorithmic FLOPs of one self-attention launch (QK^T + PV
-            # over both images) / its average launch time from the per-class events; the split attention issues 3 MFMAs per MAC
-            "roofline_attention": ({"bound": "mfma", "kernel": "attn_self", "achieved": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
-                                    "frac": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12 / peak, "avg_launch_ms": kernel_ms["attn_self"] / L,
-                                    "algorithmic_flops_per_launch": fl["attn_self"], "mfma_per_mac": mfma_per_mac_attn, "issued_tflops": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12 * mfma_per_mac_attn,
-                                    "traffic": pmc_traffic(tkey + "attention")[0]} if "attn_self" in kernel_ms else None),
-            "kernel_ms_per_step": kernel_ms,
-            "kernel_ms_per_step_source": ("HIP events around every launch during the warm-up steps; the roofline kernel's entry and "
-                                          "avg_launch_ms come from events inside the timed region") if warm_prof else "HIP events inside the timed region",
-            #  class attribution under fusion: what each event class brackets in the product configuration
-            "kernel_ms_class_notes": {"prep": "input_dim 256 (fused_prep): only the bounding-box / state kernels — normalisation, rotary rows, index set and the descriptor copy run inside the FIRST gemm_qkv_self launch (proj_first_kernel), whose time and bytes (1 KB read + 1.3 KB write per keypoint) are in gemm_qkv_self",
-                                      "fused_tail": "tail + the next block's q/k/v projection (+ the final projection in the last launch at fixed depth)",
-                                      "gemm_qkv_self": "the first projection only (later ones run inside fused_tail) unless pruning forces standalone projections"},
-            "gpu_ms_per_step_sum": round(sum(kernel_ms.values()), 3),
-            "gpu_ms_per_step_sum_note": "sum of the per-class event times of the WARM-UP steps (each launch bracketed by its own event pair, ~90 pairs per step): an upper bound that is not additive with ms_per_step, which is the un-instrumented timed region",
-            "algorithmic_tflops": value * flops_per_pair(n, m) / 1e12,
-            # shader clock this box sustains under a matrix-core-dense load, measured right before the timed region: the pool's
-            # boxes differ by up to ~20 % for one binary, and most of it is this clock
-            "effective_mfma_clock_mhz": sustained_mhz, "sustained_dense_bf16_tflops": sustained_tflops,
-            # the board's power limit is what bounds the two big kernels: the clock the fused tail actually ran at inside a forward, of 2 400 MHz nominal
-            "shader_clock_mhz_inside_tail_kernel": kernel_clock,
-            "power": power,
-            "matches_per_pair": float((out["matches0"].cpu().numpy() > -1).sum(axis=1).mean()) if "matches0" in out else None,   # (one copy: no framework kernels behind the timed region either)
-            "value_synchronous_forward": sync_value,   # pairs/s with model(data) per step (host sync inside every forward), N = 1 only
-            "rccl": rccl,
-            "gather_probe_one_gpu": gather_probe,
-            "pcie_inclusive": pcie_probe,
             # what one step hands back: the same dict at every N — LightGlue.forward's keys / dtypes (ref :619-629), built inside the timed
             # region with ONE deferred host synchronisation per step (N = 1: forward_deferred; N > 1: PairShardedMatcher.issue_local -> Pending.wait)
             "step_output": {k: (str(v.dtype).replace("torch.", "") if torch.is_tensor(v) else f"list[{len(v)}] of {str(v[0].dtype).replace('torch.', '')}" if isinstance(v, list) and v else type(v).__name__)
                             for k, v in sorted((out or {}).items())},
         }
-        # match-index parity of the batch that was just timed (rank 0's pairs): against the reference's own fixture for the
-        # first 4 pairs and against the oracle on the pairs the CPU leg runs anyway
-        default_weights = args.precision in ("f16x3", "fp32") and not args.checkpoint
-        res["parity"] = golden_parity(out, n, B, args.recipe, args.config, m) if (default_weights and os.environ.get("LG_BENCH_ABLATION") != "1") else None
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"], res["parity_oracle"] = cpu_baseline(sd, n, m, gpu_out=out, recipe=args.recipe, conf_kw={k: v for k, v in conf_kw.items() if k != "input_dim"}, dim=dim, wseed=cfg["wseed"], checkpoint=args.checkpoint)
+        if args.full:
+            fl = flops_per_launch(B, n, m)
+            timed = {k: v for k, v in prof.items() if v[1] > 0}
+            classes_seen = set(timed) | set(warm_prof)
+            fused_next = "fused_tail" in classes_seen and "gemm_qkv_cross" not in classes_seen
+            if fused_next:
+                # the tail kernel also runs the NEXT block's q/k/v projection (L cross + L-1 self projections over 2L tail
+                # launches per forward): charge their algorithmic FLOPs to the launches that execute them
+                fl["fused_tail"] += (L * fl["gemm_qkv_cross"] + (L - 1) * fl["gemm_qkv_self"]) / (2 * L)
+                if "gemm_final_proj" not in classes_seen:   # fixed depth: the LAST tail launch also runs the final projection of the log assignment
+                    fl["fused_tail"] += fl["gemm_final_proj"] / (2 * L)
+            dom = max((k for k in timed if k in fl), key=lambda k: timed[k][0])
+            dom_ms = timed[dom][0] / timed[dom][1]
+            achieved = fl[dom] / (dom_ms * 1e-3) / 1e12
+            peak = 157.3 if args.precision == "fp32" else 2500.0  # nominal dense MFMA peak of the MI355X (fp32 / bf16-f16 at 2.4 GHz)
+            tkey = f"{args.precision}/{args.attention or args.precision}/B{B}/N{n}/"
+            traffic_dom = pmc_traffic(tkey + dom + ("+next" if fused_next and dom == "fused_tail" else ""))
+            traffic_assign = pmc_traffic(tkey + "assign_sweeps")
+            if warm_prof:   # per-class table from the warm-up steps; the dominant class from the timed region
+                kernel_ms = {k: round(v[0], 4) for k, v in warm_prof.items()}
+                kernel_ms[dom] = round(timed[dom][0] / args.steps, 4)
+                timed = {**{k: (v[0] * args.steps, v[1] * args.steps) for k, v in warm_prof.items()}, dom: timed[dom]}
+            else:
+                kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in timed.items()}
+            # MFMAs issued per algorithmic MAC: linear layers 3 in f16x3 (the projection's x operand is one plane in the fast opt-in: its
+            # share of the tail's MACs runs 2), attention 3 with split operands, 1 otherwise
+            mfma_per_mac_attn = 3 if (args.precision == "f16x3" and not args.attention) else 1
+            mfma_per_mac_linear = (3 if not args.attention else round((3 * 393216 + 2 * 163840) / 557056, 3)) if args.precision == "f16x3" else 1
+            res.update({
+                "roofline": {"bound": "mfma", "kernel": dom + (" (+ next block's q/k/v projection)" if fused_next and dom == "fused_tail" else ""), "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                             "traffic": traffic_dom[0], "traffic_source": traffic_dom[1],
+                             "avg_launch_ms": dom_ms, "algorithmic_flops_per_launch": fl[dom],
+                             "sustained_peak": sustained_tflops, "frac_of_sustained": (achieved / sustained_tflops if sustained_tflops else None),
+                             # matrix-core work actually ISSUED per second: the split-f16 products cost 3 MFMAs per algorithmic MAC
+                             "mfma_per_mac": mfma_per_mac_linear, "issued_tflops": achieved * mfma_per_mac_linear,
+                             "note": ("ADAPTIVE config: pairs stop early and rows are pruned during the forward, so the FLOPs of the full N x M shape charged to every launch are an UPPER bound (achieved / frac overstate).  " if adaptive else "")
+                                     + "algorithmic FLOPs (2/MAC) of one launch / HIP-event launch duration; split f16 issues 3 MFMAs per algorithmic MAC.  "
+                                     "peak = nominal dense bf16 / f16 (2.4 GHz); sustained_peak = what a dense bf16 MFMA spin "
+                                     "reaches on THIS box right before the timed region (power-managed clock, see effective_mfma_clock_mhz)"},
+                # the HBM-bound stage of the path: dual log-softmax + argmax sweeps over the similarity matrix
+                "roofline_hbm": ({"bound": "hbm", "kernel": "assign (lse_sweep + argmax_sweep + merges + finalize)",
+                                  "achieved": hbm_bytes_assign(B, n, m) / (timed["assign"][0] / timed["assign"][1] * 1e-3) / 1e9,
+                                  "peak": 8000.0, "unit": "GB/s",
+                                  "frac": hbm_bytes_assign(B, n, m) / (timed["assign"][0] / timed["assign"][1] * 1e-3) / 1e9 / 8000.0,
+                                  "algorithmic_bytes_per_launch": hbm_bytes_assign(B, n, m),
+                                  "traffic": traffic_assign[0], "traffic_source": traffic_assign[1]} if "assign" in timed else None),
+                # the attention GEMMs against the same peak (north_star asks for it): algorithmic FLOPs of one self-attention launch (QK^T + PV
+                # over both images) / its average launch time from the per-class events; the split attention issues 3 MFMAs per MAC
+                "roofline_attention": ({"bound": "mfma", "kernel": "attn_self", "achieved": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                                        "frac": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12 / peak, "avg_launch_ms": kernel_ms["attn_self"] / L,
+                                        "algorithmic_flops_per_launch": fl["attn_self"], "mfma_per_mac": mfma_per_mac_attn, "issued_tflops": fl["attn_self"] / (kernel_ms["attn_self"] / L * 1e-3) / 1e12 * mfma_per_mac_attn,
+                                        "traffic": pmc_traffic(tkey + "attention")[0]} if "attn_self" in kernel_ms else None),
+                "kernel_ms_per_step": kernel_ms,
+                "kernel_ms_per_step_source": ("HIP events around every launch during the warm-up steps; the roofline kernel's entry and "
+                                              "avg_launch_ms come from events inside the timed region") if warm_prof else "HIP events inside the timed region",
+                #  class attribution under fusion: what each event class brackets in the product configuration
+                "kernel_ms_class_notes": {"prep": "input_dim 256 (fused_prep): only the bounding-box / state kernels — normalisation, rotary rows, index set and the descriptor copy run inside the FIRST gemm_qkv_self launch (proj_first_kernel), whose time and bytes (1 KB read + 1.3 KB write per keypoint) are in gemm_qkv_self",
+                                          "fused_tail": "tail + the next block's q/k/v projection (+ the final projection in the last launch at fixed depth)",
+                                          "gemm_qkv_self": "the first projection only (later ones run inside fused_tail) unless pruning forces standalone projections"},
+                "gpu_ms_per_step_sum": round(sum(kernel_ms.values()), 3),
+                "gpu_ms_per_step_sum_note": "sum of the per-class event times of the WARM-UP steps (each launch bracketed by its own event pair, ~90 pairs per step): an upper bound that is not additive with ms_per_step, which is the un-instrumented timed region",
+                "algorithmic_tflops": value * flops_per_pair(n, m) / 1e12,
+                # shader clock this box sustains under a matrix-core-dense load, measured right before the timed region: the pool's
+                # boxes differ by up to ~20 % for one binary, and most of it is this clock
+                "effective_mfma_clock_mhz": sustained_mhz, "sustained_dense_bf16_tflops": sustained_tflops,
+                # the board's power limit is what bounds the two big kernels: the clock the fused tail actually ran at inside a forward, of 2 400 MHz nominal
+                "shader_clock_mhz_inside_tail_kernel": kernel_clock,
+                "power": power,
+                "matches_per_pair": float((out["matches0"].cpu().numpy() > -1).sum(axis=1).mean()) if "matches0" in out else None,   # (one copy: no framework kernels behind the timed region either)
+                "value_synchronous_forward": sync_value,   # pairs/s with model(data) per step (host sync inside every forward), N = 1 only
+                "rccl": rccl,
+                "gather_probe_one_gpu": gather_probe,
+                "pcie_inclusive": pcie_probe,
+            })
+            # match-index parity of the batch that was just timed (rank 0's pairs): against the reference's own fixture for the
+            # first 4 pairs and against the oracle on the pairs the CPU leg runs anyway
+            default_weights = args.precision in ("f16x3", "fp32") and not args.checkpoint
+            res["parity"] = golden_parity(out, n, B, args.recipe, args.config, m) if (default_weights and os.environ.get("LG_BENCH_ABLATION") != "1") else None
+            if world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"], res["parity_oracle"] = cpu_baseline(sd, n, m, gpu_out=out, recipe=args.recipe, conf_kw={k: v for k, v in conf_kw.items() if k != "input_dim"}, dim=dim, wseed=cfg["wseed"], checkpoint=args.checkpoint)
         json_out.write(json.dumps(res) + "\n")
         json_out.flush()
     if world > 1:

@@ -25,15 +25,20 @@ def test_state_dict_names_and_shapes_match_reference_contract():
     assert tuple(m128.state_dict()["posenc.Wr.weight"].shape) == (32, 4)
 
 
-@pytest.mark.skipif(not make_golden.REF.exists(), reason="reference tree not mounted")
 def test_state_dict_interchangeable_with_reference_module():
-    lg = make_golden.load_reference()
-    ref = lg.LightGlue(features=None, input_dim=128)
+    """The reference module's state dict — names in order, shapes and dtypes of LightGlue(features=None, input_dim=128), recorded in
+    tests/golden/reference_lightglue_state_dict_128.json — loads strictly into this class and reads back unchanged."""
+    import json
+    from pathlib import Path
+    layout = json.loads((Path(__file__).resolve().parent / "golden" / "reference_lightglue_state_dict_128.json").read_text())["tensors"]
+    g = torch.Generator().manual_seed(0)
+    ref_sd = {name: torch.randn(shape, generator=g).to(getattr(torch, dtype)) for name, shape, dtype in layout}
     ours = LightGlue(features=None, input_dim=128)
-    assert list(ref.state_dict().keys()) == list(ours.state_dict().keys())
-    res = ours.load_state_dict(ref.state_dict(), strict=True)
+    assert list(ref_sd.keys()) == list(ours.state_dict().keys())
+    assert all(ours.state_dict()[k].shape == v.shape and ours.state_dict()[k].dtype == v.dtype for k, v in ref_sd.items())
+    res = ours.load_state_dict(ref_sd, strict=True)
     assert not res.missing_keys and not res.unexpected_keys
-    for k, v in ref.state_dict().items():
+    for k, v in ref_sd.items():
         assert torch.equal(v, ours.state_dict()[k])
 
 
@@ -152,7 +157,7 @@ def test_extracted_to_image_frame_matches_reference_formula():
 
 def test_cm_prune_colours_the_prune_output_like_the_reference():
     """ref viz2d.py:33-39 (cm_prune) over :22-31 (cm_BlRdGn): survivors blue, dropped points red -> green by layer.
-    Compared live against the reference function when /root/reference (and matplotlib, which its module imports) is there."""
+    Compared against the reference function's own output for three prune vectors (tests/golden/cm_prune_reference.json)."""
     import numpy as np
     from lightglue_amd import cm_prune
     prune = torch.tensor([1, 2, 5, 9, 10, 10, 3])
@@ -161,12 +166,11 @@ def test_cm_prune_colours_the_prune_output_like_the_reference():
     assert np.allclose(c[4], [0.0, 0.2, 1.0, 1.0]) and np.allclose(c[5], c[4])            # alive to the end
     assert np.allclose(c[0], [1.0, 0.0, 0.0, 1.0])                                          # dropped after the first layer: red
     assert np.allclose(c[2], [1.0, 8.0 / 9.0, 0.0, 1.0]) and np.allclose(c[3], [2.0 / 9.0, 1.0, 0.0, 1.0])
-    import importlib.util, pathlib
-    ref = pathlib.Path("/root/reference/lightglue/viz2d.py")
-    if ref.exists() and importlib.util.find_spec("matplotlib") is not None:
-        spec = importlib.util.spec_from_file_location("ref_viz2d", ref); mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-        for p in (prune, torch.tensor([0, 1, 4, 4]), torch.tensor([3, 3, 3])):
-            assert np.allclose(cm_prune(p), mod.cm_prune(p)), p
+    import json, pathlib
+    ref = json.loads((pathlib.Path(__file__).resolve().parent / "golden" / "cm_prune_reference.json").read_text())
+    assert [c["prune"] for c in ref["cases"]] == [prune.tolist(), [0, 1, 4, 4], [3, 3, 3]]
+    for case in ref["cases"]:
+        assert np.allclose(cm_prune(torch.tensor(case["prune"])), np.asarray(case["rgba"])), case["prune"]
 
 
 def test_deferred_handle_synchronises_once_and_caches():
@@ -259,6 +263,39 @@ def test_bench_spawns_its_own_ranks_without_a_launcher(monkeypatch):
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in cmd and "127.0.0.1" in cmd
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_writes_the_step_dict(tmp_path):
+    """bench.py --dump-outputs: forward()'s dict as <name>.npy in float32 / float64 with the values unchanged, the ragged lists as (pair, index0, index1)
+    rows, and above the size limit the same seeded sample of whole pairs on every call."""
+    import sys
+    from pathlib import Path
+    import numpy as np
+    sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+    import bench
+    g = torch.Generator().manual_seed(3)
+    B, N = 6, 50
+    m0 = torch.randint(-1, N, (B, N), generator=g)
+    counts = [0, 7, 3, 50, 1, 20]
+    out = {"matches0": m0, "matches1": m0.flip(1), "matching_scores0": torch.rand(B, N, generator=g), "matching_scores1": torch.rand(B, N, generator=g),
+           "stop": torch.full((B,), 9, dtype=torch.int64), "prune0": torch.rand(B, N, generator=g), "prune1": torch.rand(B, N, generator=g),
+           "matches": [torch.randint(0, N, (c, 2), generator=g) for c in counts], "scores": [torch.rand(c, generator=g) for c in counts]}
+    names = bench.dump_outputs(out, str(tmp_path / "all"))
+    a = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in names}
+    assert set(a) == set(out) and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    for k in ("matches0", "matches1", "stop"):
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], out[k].numpy()), k
+    for k in ("matching_scores0", "matching_scores1", "prune0", "prune1"):
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], out[k].numpy()), k
+    assert np.array_equal(a["matches"][:, 0], np.repeat(np.arange(B), counts)) and np.array_equal(a["matches"][:, 1:], torch.cat(out["matches"]).numpy())
+    assert np.array_equal(a["scores"], torch.cat(out["scores"]).numpy())
+    limit = sum(v.nbytes for v in a.values()) // 2
+    s1, s2 = (bench.dump_outputs(out, str(tmp_path / d), limit=limit) for d in ("s1", "s2"))
+    b1 = {k: np.load(tmp_path / "s1" / f"{k}.npy") for k in s1}
+    assert 0 < sum(v.nbytes for v in b1.values()) <= limit and b1["matches0"].shape[0] < B
+    assert all(np.array_equal(b1[k], np.load(tmp_path / "s2" / f"{k}.npy")) for k in s2)
+    pairs = [int(np.where((m0.numpy() == row).all(1))[0][0]) for row in b1["matches0"]]
+    assert np.array_equal(b1["stop"], out["stop"].numpy()[pairs]) and set(np.unique(b1["matches"][:, 0]).astype(int)) <= set(pairs)
 
 
 def test_prefetch_to_device_refuses_a_cpu_target():

@@ -11,7 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import gpu_util
-from conftest import require_gpu
+from conftest import SCORE_TOL, require_gpu
 from lightglue_amd import PairShardedMatcher
 from lightglue_amd import synthetic as synth
 
@@ -178,7 +178,7 @@ def test_plain_bench_command_launches_its_own_ranks():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LG_BENCH_ONE_GPU="1", LG_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -205,7 +205,7 @@ def test_bench_config_4_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LG_BENCH_ONE_GPU="1", LG_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--config", "4", "--kpts", "512", "--pairs", "4", "--steps", "2", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -224,7 +224,7 @@ def test_bench_default_is_config_2_and_reports_the_gather_probe():
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
     assert d["metric"] == "image-pairs/s at N=M=1024, 9 layers; match-index parity vs ref" and d["config"]["pairs_per_gpu"] == 32 and d["config"]["keypoints"] == 1024
@@ -236,3 +236,38 @@ def test_bench_default_is_config_2_and_reports_the_gather_probe():
     g = d["gather_probe_one_gpu"]
     assert "error" not in g, g
     assert g["matches_equal_plain_loop"] is True and g["ms_per_step_with_world1_gather"] > 0
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) prints the contract line without the --full blocks, and --dump-outputs writes what the last timed
+    step handed back as float32 / float64 arrays: its first four pairs are the reference's own fixture (tests/golden/nonadaptive_1024_b4)."""
+    require_gpu()
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "2", "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "image-pairs/s at N=M=1024, 9 layers; match-index parity vs ref" and d["unit"] == "image-pairs/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f16" and d["steps"] == 3 and d["warmup"] == 2
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert not {"roofline", "kernel_ms_per_step", "power", "parity", "cpu_baseline", "gather_probe_one_gpu", "pcie_inclusive"} & set(d), sorted(d)
+    a = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    assert set(a) == {"matches0", "matches1", "matching_scores0", "matching_scores1", "stop", "prune0", "prune1", "matches", "scores"}, sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["matches0"].shape == (32, 1024) and a["matching_scores0"].dtype == np.float32
+    z = np.load(root / "tests" / "golden" / "nonadaptive_1024_b4.npz")
+    for k in ("matches0", "matches1"):
+        assert np.array_equal(a[k][:4], z[k]), k
+    for k in ("matching_scores0", "matching_scores1"):
+        assert np.abs(a[k][:4] - z[k]).max() <= SCORE_TOL, k
+    # the ragged lists: rows (pair, index0, index1) in pair order, the same matches as the dense indices
+    m, m0 = a["matches"].astype(np.int64), a["matches0"].astype(np.int64)
+    assert len(m) == len(a["scores"]) == int((m0 > -1).sum())
+    assert np.array_equal(m0[m[:, 0], m[:, 1]], m[:, 2]) and np.all(np.diff(m[:, 0]) >= 0)

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import argparse
 import importlib.util
+import os
 import re
 import sys
 from pathlib import Path
@@ -52,8 +53,8 @@ def load_checkpoint(path):
 
 def find_reference(hint):
     for cand in ([Path(hint)] if hint else []) + [Path("/root/reference")]:
-        f = cand / "lightglue" / "lightglue.py" if cand.is_dir() else cand
-        if f.exists():
+        f = cand / "lightglue" / "lightglue.py" if os.path.isdir(cand) else cand
+        if os.access(f, os.R_OK):   # a checkout this user cannot read counts as absent
             spec = importlib.util.spec_from_file_location("lg_ref", str(f))
             mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
             return mod, str(f)
