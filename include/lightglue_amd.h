@@ -267,6 +267,40 @@ int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32
                  void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts,
                  int32_t* totals, void* hip_stream);
 
+/* ---- ALIKED extractor (aliked-n16 / n16rot / n32; lightglue/aliked.py:612-760) ----
+ * Exact fp32 arithmetic throughout.  `n_pos` selects the model: 16 (aliked-n16, aliked-n16rot) or 32 (aliked-n32); anything else is
+ * refused.  Images: h, w >= 8 and a padded size (h, w rounded up to multiples of 32) below 2^25 pixels.  Device pointers, caller's stream.
+ * lg_aliked_pack_weights: the 68 fp32 state tensors of the module in the order
+ *     block1: conv1.weight, bn1.{weight, bias, running_mean, running_var}, conv2.weight, bn2.{...}
+ *     block2: conv1.weight, bn1.{...}, conv2.weight, bn2.{...}, downsample.{weight, bias}
+ *     block3, block4: conv1.offset_conv.{weight, bias}, conv1.regular_conv.weight, bn1.{...}, conv2.offset_conv.{weight, bias},
+ *                     conv2.regular_conv.weight, bn2.{...}, downsample.{weight, bias}
+ *     conv1 .. conv4 .weight, score_head.{0, 2, 4, 6}.weight,
+ *     desc_head: offset_conv.0.{weight, bias}, offset_conv.2.{weight, bias}, sf_conv.weight, agg_weights
+ *   -> one packed buffer of lg_aliked_packed_bytes(n_pos) bytes (BatchNorm folded into weights and biases, eps 1e-5).
+ * lg_aliked_encode: image [batch][channels = 1 | 3][h][w] -> scores [batch][h][w] (sigmoid score map, unpadded) and the four 32-channel
+ *   level maps of x1234 (levels: lg_aliked_levels_bytes bytes, read by lg_aliked_describe); workspace: lg_aliked_workspace_bytes.
+ * lg_aliked_detect: DKD (sub-pixel) on the score map.  top_k > 0: the top_k best positive NMS maxima, sorted by score (fewer when the map has
+ *   fewer); else threshold mode: scores > scores_th, or > the image's mean score if no pixel of the batch passes (or scores_th <= 0), the
+ *   n_limit best sorted by score when more pass, raster order otherwise.  top_k, n_limit <= 20000, capacity >= top_k / n_limit.
+ *   image_size [batch][2] (w, h) or NULL.  keypoints [batch][capacity][2] pixel (x, y), kp_scores [batch][capacity], kp_norm [batch][capacity][2]
+ *   (the (-1, 1) frame lg_aliked_describe reads), counts [batch]; rows >= counts[b] are zero.  workspace: lg_aliked_detect_workspace_bytes.
+ * lg_aliked_describe: SDDH descriptors [batch][n][128] for kp_norm [batch][n][2] (rows >= counts[b] give zero rows); n <= 20000;
+ *   workspace: lg_aliked_describe_workspace_bytes(batch * n, n_pos). */
+int64_t lg_aliked_packed_bytes(int32_t n_pos);
+int lg_aliked_pack_weights(int32_t n_pos, const float* const* tensors, int32_t n_tensors, void* packed, int64_t packed_bytes, void* hip_stream);
+int64_t lg_aliked_levels_bytes(int32_t batch, int32_t h, int32_t w);
+int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n_pos);
+int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
+                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream);
+int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity);
+int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th,
+                     int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
+                     float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream);
+int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos);
+int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
+                       const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ EXPORTED_SYMBOLS = (
     "lg_profile_num_classes", "lg_profile_class_name", "lg_engine_profile_enable", "lg_engine_profile_read",
     "lg_sp_sample_descriptors", "lg_sp_detect_workspace_bytes", "lg_sp_detect",
     "lg_sp_pack_conv_weight", "lg_sp_encode_workspace_bytes", "lg_sp_encode", "lg_sp_pack_conv_weight_split", "lg_sp_encode_split", "lg_debug_mfma_sustained",
+    "lg_aliked_packed_bytes", "lg_aliked_pack_weights", "lg_aliked_levels_bytes", "lg_aliked_workspace_bytes", "lg_aliked_encode",
+    "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
 )
 
 
@@ -126,6 +128,21 @@ def load() -> C.CDLL:
     lib.lg_sp_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lg_sp_pack_conv_weight_split.argtypes = lib.lg_sp_pack_conv_weight.argtypes
     lib.lg_sp_encode_split.argtypes = lib.lg_sp_encode.argtypes
+    lib.lg_aliked_packed_bytes.argtypes = [C.c_int32]
+    lib.lg_aliked_packed_bytes.restype = C.c_int64
+    lib.lg_aliked_pack_weights.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.lg_aliked_levels_bytes.argtypes = [C.c_int32] * 3
+    lib.lg_aliked_levels_bytes.restype = C.c_int64
+    lib.lg_aliked_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.lg_aliked_workspace_bytes.restype = C.c_int64
+    lib.lg_aliked_encode.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]
+    lib.lg_aliked_detect_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.lg_aliked_detect_workspace_bytes.restype = C.c_int64
+    lib.lg_aliked_detect.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_float] + [C.c_int32] * 3
+                                     + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
+    lib.lg_aliked_describe_workspace_bytes.argtypes = [C.c_int32] * 2
+    lib.lg_aliked_describe_workspace_bytes.restype = C.c_int64
+    lib.lg_aliked_describe.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

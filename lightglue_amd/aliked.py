@@ -1,0 +1,248 @@
+"""ALIKED on the MI355X: the extractor upstream LightGlue recommends with `LightGlue(features="aliked")`.
+
+Same module tree / parameter names as the reference class (`lightglue/aliked.py:612-694`), built from `nn.Conv2d` /
+`nn.BatchNorm2d` only (no torchvision, no kornia), so a released `aliked-n16.pth` / `aliked-n32.pth` loads with
+`load_state_dict(strict=True)`, and the same `forward({"image"[, "image_size"]})` contract (`:740-760`).  Everything runs in
+`lightglue_amd/csrc/lg_aliked.hip` behind the `lg_aliked_*` C entry points: the encoder, aggregation and score head
+(`lg_aliked_encode`), DKD (`lg_aliked_detect`) and SDDH (`lg_aliked_describe`), all exact fp32.  No CPU fallback.  As for
+SuperPoint, image resizing (`ImagePreprocessor`) is out of scope: `extract()` takes an already sized image."""
+from __future__ import annotations
+
+import ctypes as C
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import _cabi
+
+
+class DeformableConv2d(nn.Module):
+    """Parameter holder of the reference's DeformableConv2d (aliked.py:282-336; mask=False, bias=False)."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.offset_conv = nn.Conv2d(cin, 18, 3, 1, 1, bias=True)
+        self.regular_conv = nn.Conv2d(cin, cout, 3, 1, 1, bias=False)
+
+
+def _conv(cin, cout, conv_type):
+    return nn.Conv2d(cin, cout, 3, 1, 1, bias=False) if conv_type == "conv" else DeformableConv2d(cin, cout)
+
+
+class ConvBlock(nn.Module):
+    def __init__(self, cin, cout, conv_type="conv"):
+        super().__init__()
+        self.conv1 = _conv(cin, cout, conv_type)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.conv2 = _conv(cout, cout, conv_type)
+        self.bn2 = nn.BatchNorm2d(cout)
+
+
+class ResBlock(ConvBlock):
+    def __init__(self, cin, cout, conv_type="conv"):
+        super().__init__(cin, cout, conv_type)
+        self.downsample = nn.Conv2d(cin, cout, 1)
+
+
+class SDDH(nn.Module):
+    def __init__(self, dims: int, n_pos: int):
+        super().__init__()
+        self.offset_conv = nn.Sequential(nn.Conv2d(dims, 2 * n_pos, 3, 1, 0, bias=True), nn.SELU(inplace=True),
+                                         nn.Conv2d(2 * n_pos, 2 * n_pos, 1, 1, 0, bias=True))
+        self.sf_conv = nn.Conv2d(dims, dims, 1, 1, 0, bias=False)
+        self.register_parameter("agg_weights", nn.Parameter(torch.rand(n_pos, dims, dims)))
+
+
+def _abi_names():
+    """State-dict names in the order lg_aliked_pack_weights takes them (include/lightglue_amd.h)."""
+    bn = lambda p: [f"{p}.weight", f"{p}.bias", f"{p}.running_mean", f"{p}.running_var"]  # noqa: E731
+    names = ["block1.conv1.weight", *bn("block1.bn1"), "block1.conv2.weight", *bn("block1.bn2")]
+    names += ["block2.conv1.weight", *bn("block2.bn1"), "block2.conv2.weight", *bn("block2.bn2"), "block2.downsample.weight", "block2.downsample.bias"]
+    for b in ("block3", "block4"):
+        names += [f"{b}.conv1.offset_conv.weight", f"{b}.conv1.offset_conv.bias", f"{b}.conv1.regular_conv.weight", *bn(f"{b}.bn1"),
+                  f"{b}.conv2.offset_conv.weight", f"{b}.conv2.offset_conv.bias", f"{b}.conv2.regular_conv.weight", *bn(f"{b}.bn2"),
+                  f"{b}.downsample.weight", f"{b}.downsample.bias"]
+    names += [f"conv{i}.weight" for i in range(1, 5)] + [f"score_head.{i}.weight" for i in (0, 2, 4, 6)]
+    names += ["desc_head.offset_conv.0.weight", "desc_head.offset_conv.0.bias", "desc_head.offset_conv.2.weight", "desc_head.offset_conv.2.bias",
+              "desc_head.sf_conv.weight", "desc_head.agg_weights"]
+    return names
+
+
+_ABI_NAMES = _abi_names()
+
+
+class ALIKED(nn.Module):
+    default_conf = {"model_name": "aliked-n16", "max_num_keypoints": -1, "detection_threshold": 0.2, "nms_radius": 2}   # ref :613-618
+    # c1, c2, c3, c4, dim, K, M  (ref :624-630)
+    cfgs = {
+        "aliked-t16": [8, 16, 32, 64, 64, 3, 16],
+        "aliked-n16": [16, 32, 64, 128, 128, 3, 16],
+        "aliked-n16rot": [16, 32, 64, 128, 128, 3, 16],
+        "aliked-n32": [16, 32, 64, 128, 128, 3, 32],
+    }
+    n_limit_max = 20000
+    required_data_keys = ["image"]
+
+    def __init__(self, weights: Optional[dict] = None, **conf):
+        """`weights`: a state dict with the reference's names (e.g. torch.load('aliked-n16.pth')), loaded with strict=True; None = PyTorch's
+        default init (the released files come from the network, which this class never touches)."""
+        super().__init__()
+        self.conf = SimpleNamespace(**{**self.default_conf, **conf})
+        name = self.conf.model_name
+        if name == "aliked-t16":
+            raise ValueError("aliked-t16 is not built (8-channel layers, 64-d descriptors; LightGlue has no weights for it)")
+        if name not in self.cfgs:
+            raise ValueError(f"unknown ALIKED model {name!r}; built: aliked-n16, aliked-n16rot, aliked-n32")
+        if self.conf.nms_radius < 1 or self.conf.nms_radius > 8:
+            raise ValueError("nms_radius must be in [1, 8]")
+        if self.conf.max_num_keypoints is not None and self.conf.max_num_keypoints > self.n_limit_max:
+            raise ValueError(f"max_num_keypoints must be at most {self.n_limit_max}")
+        c1, c2, c3, c4, dim, K, M = self.cfgs[name]
+        self.n_pos = M
+        # module tree of the reference (registration order included: state_dict keys come out in the same order)
+        self.block1 = ConvBlock(3, c1, "conv")
+        self.block2 = ResBlock(c1, c2, "conv")
+        self.block3 = ResBlock(c2, c3, "dcn")
+        self.block4 = ResBlock(c3, c4, "dcn")
+        self.conv1 = nn.Conv2d(c1, dim // 4, 1, bias=False)
+        self.conv2 = nn.Conv2d(c2, dim // 4, 1, bias=False)
+        self.conv3 = nn.Conv2d(c3, dim // 4, 1, bias=False)
+        self.conv4 = nn.Conv2d(dim, dim // 4, 1, bias=False)
+        self.score_head = nn.Sequential(nn.Conv2d(dim, 8, 1, bias=False), nn.SELU(inplace=True), nn.Conv2d(8, 4, 3, 1, 1, bias=False), nn.SELU(inplace=True),
+                                        nn.Conv2d(4, 4, 3, 1, 1, bias=False), nn.SELU(inplace=True), nn.Conv2d(4, 1, 3, 1, 1, bias=False))
+        self.desc_head = SDDH(dim, M)
+        if weights is not None:
+            self.load_state_dict(weights, strict=True)
+        self._packed = None   # (signature, packed device buffer)
+
+    # ------------------------------------------------------------------ detector settings of the reference's DKD (ref :680-689)
+    def _dkd(self):
+        c = self.conf
+        mnk = c.max_num_keypoints if c.max_num_keypoints is not None else -1
+        top_k = -1 if c.detection_threshold > 0 else mnk
+        n_limit = mnk if mnk > 0 else self.n_limit_max
+        return top_k, float(c.detection_threshold), n_limit
+
+    # ------------------------------------------------------------------ weights -> kernel layout (BatchNorm folded)
+    def _params(self, device):
+        sd = self.state_dict(keep_vars=True)
+        sig = (str(device),) + tuple((sd[n]._version, sd[n].data_ptr()) for n in _ABI_NAMES)
+        if self._packed is not None and self._packed[0] == sig:
+            return self._packed[1]
+        lib = _cabi.load()
+        with torch.cuda.device(device):
+            tensors = [sd[n].detach().to(device=device, dtype=torch.float32).contiguous() for n in _ABI_NAMES]
+            nbytes = lib.lg_aliked_packed_bytes(self.n_pos)
+            packed = torch.empty((nbytes,), device=device, dtype=torch.uint8)
+            arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+            stream = torch.cuda.current_stream(device)
+            _cabi.check(lib.lg_aliked_pack_weights(self.n_pos, arr, len(tensors), packed.data_ptr(), nbytes, C.c_void_p(stream.cuda_stream)))
+            stream.synchronize()   # the temporaries may be freed after this
+        self._packed = (sig, packed)
+        return packed
+
+    @staticmethod
+    def _check_image(image):
+        if image.device.type != "cuda":
+            raise RuntimeError("lightglue_amd.ALIKED runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
+                               f"Got an image on {image.device}.")
+        assert image.dim() == 4 and image.shape[1] in (1, 3), "image must be [B, 1|3, H, W]"
+
+    # ------------------------------------------------------------------ encoder + score head
+    @torch.no_grad()
+    def encode(self, image: torch.Tensor):
+        """image [B, 1|3, H, W] -> (scores [B, H, W], level maps): ref extract_dense_map (:696-738) without the dense feature map, which
+        lg_aliked_describe recomputes per keypoint from the four 32-channel level maps."""
+        self._check_image(image)
+        device = image.device
+        image = image.detach().to(dtype=torch.float32).contiguous()
+        bsz, ch, h, w = image.shape
+        lib = _cabi.load()
+        packed = self._params(device)
+        nlev = lib.lg_aliked_levels_bytes(bsz, h, w)
+        nws = lib.lg_aliked_workspace_bytes(bsz, h, w, self.n_pos)
+        if nlev <= 0 or nws <= 0:   # refused sizes: let the encode call report why
+            nlev, nws = max(nlev, 1), max(nws, 1)
+        levels = torch.empty((nlev,), device=device, dtype=torch.uint8)
+        work = torch.empty((nws,), device=device, dtype=torch.uint8)
+        scores = torch.empty((bsz, h, w), device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _cabi.check(lib.lg_aliked_encode(image.data_ptr(), bsz, ch, h, w, self.n_pos, packed.data_ptr(), levels.data_ptr(), work.data_ptr(), nws,
+                                             scores.data_ptr(), C.c_void_p(stream)))
+        return scores, levels
+
+    @torch.no_grad()
+    def detect(self, scores: torch.Tensor, image_size: Optional[torch.Tensor] = None):
+        """DKD (ref :94-262) on a score map [B, H, W] -> keypoints [B, cap, 2] (pixels), scores [B, cap], normalised keypoints [B, cap, 2], counts [B]."""
+        bsz, h, w = scores.shape
+        device = scores.device
+        top_k, th, n_limit = self._dkd()
+        cap = top_k if top_k > 0 else n_limit
+        lib = _cabi.load()
+        nws = max(lib.lg_aliked_detect_workspace_bytes(bsz, h, w, cap), 1)
+        work = torch.empty((nws,), device=device, dtype=torch.uint8)
+        kpts = torch.empty((bsz, cap, 2), device=device, dtype=torch.float32)
+        kscores = torch.empty((bsz, cap), device=device, dtype=torch.float32)
+        knorm = torch.empty((bsz, cap, 2), device=device, dtype=torch.float32)
+        counts = torch.empty((bsz,), device=device, dtype=torch.int32)
+        size_ptr = None
+        if image_size is not None:
+            image_size = image_size.to(device=device, dtype=torch.float32).reshape(bsz, 2).contiguous()
+            size_ptr = image_size.data_ptr()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _cabi.check(lib.lg_aliked_detect(scores.data_ptr(), bsz, h, w, size_ptr, int(self.conf.nms_radius), th, top_k, n_limit, cap,
+                                             work.data_ptr(), nws, kpts.data_ptr(), kscores.data_ptr(), knorm.data_ptr(), counts.data_ptr(), C.c_void_p(stream)))
+        return kpts, kscores, knorm, counts
+
+    @torch.no_grad()
+    def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor):
+        """SDDH (ref :479-609): descriptors [B, N, 128] of the normalised keypoints knorm [B, N, 2]; rows >= counts[b] are zero."""
+        bsz, h, w = shape
+        n = knorm.shape[1]
+        device = knorm.device
+        out = torch.empty((bsz, n, 128), device=device, dtype=torch.float32)   # every row is written (padding rows with zeros)
+        if n == 0:
+            return out
+        lib = _cabi.load()
+        packed = self._params(device)
+        knorm = knorm.contiguous()
+        nws = max(lib.lg_aliked_describe_workspace_bytes(bsz * n, self.n_pos), 1)
+        work = torch.empty((nws,), device=device, dtype=torch.uint8)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _cabi.check(lib.lg_aliked_describe(levels.data_ptr(), bsz, h, w, self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n,
+                                               work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream)))
+        return out
+
+    # ------------------------------------------------------------------ the reference's forward
+    @torch.no_grad()
+    def forward(self, data: dict) -> dict:
+        """ref :740-760.  Returns keypoints [B, N, 2] (pixel frame), keypoint_scores [B, N], descriptors [B, N, 128] and — extension for ragged
+        batches — num_keypoints [B]; rows beyond an image's count are zero (the reference's torch.stack only handles equal counts)."""
+        for key in self.required_data_keys:
+            assert key in data, f"Missing key {key} in data"
+        image = data["image"]
+        self._check_image(image)
+        bsz, _, h, w = image.shape
+        scores, levels = self.encode(image)
+        kpts, kscores, knorm, counts = self.detect(scores, data.get("image_size"))
+        nmax = int(counts.cpu().max()) if counts.numel() else 0   # (a copy, not a reduction kernel)
+        kpts, kscores, knorm = kpts[:, :nmax].contiguous(), kscores[:, :nmax].contiguous(), knorm[:, :nmax].contiguous()
+        desc = self.describe(levels, (bsz, h, w), knorm, counts)
+        return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}
+
+    @torch.no_grad()
+    def extract(self, img: torch.Tensor, **conf) -> dict:
+        """ref utils.py:136-147 WITHOUT the resize step (as SuperPoint.extract): the image is used at its own size, keypoints are in its pixel
+        frame, and `image_size` = (w, h) is attached for the matcher."""
+        if img.dim() == 3:
+            img = img[None]
+        assert img.dim() == 4 and img.shape[0] == 1
+        feats = self.forward({"image": img})
+        h, w = img.shape[-2:]
+        feats["image_size"] = torch.tensor([[w, h]], dtype=torch.float32, device=img.device)
+        return feats

@@ -1,0 +1,988 @@
+// lightglue_amd — the ALIKED extractor (aliked-n16 / n16rot / n32) on the MI355X: encoder, aggregation, score head, DKD and SDDH of
+// the reference's ALIKED.forward (lightglue/aliked.py:612-760), every arithmetic step in the kernels below.
+//
+// Arithmetic is EXACT fp32 (v_mfma_f32_16x16x4_f32 / VALU): DKD thresholds and NMS-compares the scores, so they must agree with an fp32
+// convolution to round-off.  Layouts are NHWC throughout.  The stages:
+//   * convolutions: implicit GEMMs in the scheme of lg_sp_encoder.hip (16-channel chunks, lane (lr, g) supplies pixel / cout lr and the
+//     4 consecutive channels 4g .. 4g + 3, one 16-byte load per fragment, zero padding = clamped address + select), with an output tile
+//     width of 16 / 32 / 64 channels chosen from cout, so the 16-channel block1 layers do not run 48 dead output columns.  BatchNorm
+//     (eval: running statistics) is folded into weights and bias at pack time; the ResBlock's 1 x 1 downsample (with bias) is extra K of
+//     conv2's GEMM, read at the centre pixel of the block input; SELU is the epilogue.
+//   * block1.conv1 (cin = 3, K = 27) is VALU; it reads the image through clamped addresses, which is InputPadder's replicate padding to a
+//     multiple of 32, and broadcasts a 1-channel image to 3 channels (kornia grayscale_to_rgb).
+//   * deformable convs (blocks 3 and 4, torchvision deform_conv2d without mask): offset conv (3 x 3, bias, 18 channels) on the MFMA path,
+//     offsets clamped to +-max(h, w) / 4, bilinear sampling into a [pixel][tap * cin] buffer, then the MFMA GEMM with regular_conv.weight.
+//   * aggregation + score head: conv1 .. conv4 (1 x 1, SELU) write 32-channel level maps at their own resolution; one per-pixel kernel
+//     builds the 128 channels of x1234 on the fly (x1 at the pixel, x2 / x3 / x4 upsampled bilinearly, align_corners=True) and applies
+//     score_head.0 + SELU; three small VALU 3 x 3 convs (SELU, SELU, sigmoid) finish, the last one crops the padding.  The full-resolution
+//     128-channel map is never written.
+//   * DKD (aliked.py:94-262, sub_pixel): simple_nms, zeroed borders, threshold (whole-batch mean fallback) / top-k selection, soft-argmax
+//     over the (2r+1)^2 window, bilinear score.
+//   * SDDH (aliked.py:479-609): per keypoint the normalised x1234 vectors at the 3 x 3 patch and at the n_pos sample positions are
+//     recomputed from the level maps; the 3 x 3 offset conv, sf_conv and the agg_weights contraction are MFMA GEMMs over all keypoints.
+#include <string>
+
+#include "lg_kernels.h"
+#include "../../include/lightglue_amd.h"
+
+namespace lg {
+int set_error(int code, const char* msg);   // lg_engine.hip: the message lg_last_error() returns
+}
+
+namespace lg {
+namespace {
+
+constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.0507009873554804934193349852946f;
+__device__ __forceinline__ float selu(float x) { return SELU_SCALE * (x > 0.f ? x : SELU_ALPHA * expm1f(x)); }
+
+// ==================================================================================================== convolutions (MFMA)
+struct AkConv {
+    const float* in; const float* w; const float* bias;   // w: [taps][Cout][Cin]; bias may be null
+    const float* in2; const float* w2;                    // optional extra K at the centre pixel: in2 [pixel][Cin2], w2 [Cout][Cin2]
+    float* out;
+    int B, H, W, Cin, Cin2, Cout, taps, act;              // taps 9 (3 x 3, zero pad 1) or 1; act 1 = SELU
+};
+
+// acc[mt][nt] += the wave's 2 rows x 32 pixels x 16 NT channels of one operand pair
+template <int NT>
+__device__ __forceinline__ void ak_accum(f32x4 (&acc)[4][NT], const float* inb, const float* wt, int H, int W, int Cin, int Cout, int taps,
+                                         int n0, int x0, int y0, int lr, int g) {
+    const int nchunk = Cin >> 4;
+    for (int tap = 0; tap < taps; ++tap) {
+        const int dy = taps == 9 ? tap / 3 - 1 : 0, dx = taps == 9 ? tap % 3 - 1 : 0;
+        long long poff[4]; bool ok[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int yy = y0 + (mt >> 1) + dy, xx = x0 + (mt & 1) * 16 + lr + dx;
+            ok[mt] = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
+            poff[mt] = ((long long)yc * W + xc) * Cin + 4 * g;
+        }
+        long long wrow[NT]; bool live[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int co = n0 + nt * 16 + lr;
+            live[nt] = co < Cout;
+            wrow[nt] = ((long long)tap * Cout + min(co, Cout - 1)) * Cin + 4 * g;
+        }
+        for (int c = 0; c < nchunk; ++c) {
+            u32x4 af[4], bf[NT];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const u32x4 v = *reinterpret_cast<const u32x4*>(inb + poff[mt] + c * 16);
+                af[mt] = ok[mt] ? v : u32x4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const u32x4 v = *reinterpret_cast<const u32x4*>(wt + wrow[nt] + c * 16);
+                bf[nt] = live[nt] ? v : u32x4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) mma_chunk<TagF32>(acc[mt][nt], af[mt], bf[nt]);
+        }
+    }
+}
+
+// wave = 2 rows x 32 pixels x 16 NT output channels, workgroup = 4 waves = 8 rows.  grid (W / 32, H / 8, B * cout groups)
+template <int NT>
+__global__ __launch_bounds__(256) void ak_conv_kernel(AkConv a) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
+    constexpr int NW = 16 * NT;
+    const int ngroups = (a.Cout + NW - 1) / NW;
+    const int b = blockIdx.z / ngroups, n0 = (blockIdx.z - b * ngroups) * NW;
+    const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 8 + wv * 2;
+    if (y0 >= a.H) return;
+    f32x4 acc[4][NT];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const long long img = (long long)b * a.H * a.W;
+    ak_accum<NT>(acc, a.in + img * a.Cin, a.w, a.H, a.W, a.Cin, a.Cout, a.taps, n0, x0, y0, lr, g);
+    if (a.in2) ak_accum<NT>(acc, a.in2 + img * a.Cin2, a.w2, a.H, a.W, a.Cin2, a.Cout, 1, n0, x0, y0, lr, g);
+    // acc[mt][nt][r] = out[pixel (y0 + mt / 2, x0 + (mt & 1) * 16 + 4g + r)][cout n0 + nt * 16 + lr]
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int co = n0 + nt * 16 + lr;
+        if (co >= a.Cout) continue;
+        const float bv = a.bias ? a.bias[co] : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int y = y0 + (mt >> 1), xb = x0 + (mt & 1) * 16 + 4 * g;
+            if (y >= a.H) continue;
+            float* o = a.out + (img + (long long)y * a.W + xb) * a.Cout + co;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (xb + r >= a.W) continue;
+                const float v = acc[mt][nt][r] + bv;
+                o[(long long)r * a.Cout] = a.act ? selu(v) : v;
+            }
+        }
+    }
+}
+
+void conv(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout, int taps, int act, hipStream_t s,
+          const float* in2 = nullptr, const float* w2 = nullptr, int Cin2 = 0) {
+    AkConv a{in, w, bias, in2, w2, out, B, H, W, Cin, Cin2, Cout, taps, act};
+    const int NT = Cout <= 16 ? 1 : (Cout <= 32 ? 2 : 4);
+    const dim3 grid((W + 31) / 32, (H + 7) / 8, B * ((Cout + 16 * NT - 1) / (16 * NT)));
+    if (NT == 1) hipLaunchKernelGGL(ak_conv_kernel<1>, grid, dim3(256), 0, s, a);
+    else if (NT == 2) hipLaunchKernelGGL(ak_conv_kernel<2>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ak_conv_kernel<4>, grid, dim3(256), 0, s, a);
+}
+
+// a [rows][K] x [Cout][K] GEMM as a 1 x 1 convolution over a 32-pixel-wide "image" (rows % 32 == 0)
+void gemm(const float* in, const float* w, const float* bias, float* out, int rows, int K, int Cout, int act, hipStream_t s) {
+    conv(in, w, bias, out, 1, rows / 32, 32, K, Cout, 1, act, s);
+}
+
+// ==================================================================================================== encoder helpers (VALU)
+// block1.conv1: image [B][C][H][W] (C = 1 or 3) -> padded [B][Hp][Wp][16], BN folded, SELU.  w: [9 taps][3 cin][16 cout].
+// thread = (padded pixel, 4 output channels)
+__global__ __launch_bounds__(256) void ak_conv_first_kernel(const float* img, int C, int H, int W, int Hp, int Wp, int pt, int pl, const float* w,
+                                                            const float* bias, float* out, int B) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * Hp * Wp * 4;
+    if (idx >= total) return;
+    const int c4 = (int)(idx & 3);
+    const long long pix = idx >> 2;
+    const int xp = (int)(pix % Wp), yp = (int)((pix / Wp) % Hp), b = (int)(pix / ((long long)Wp * Hp));
+    f32x4 s = *reinterpret_cast<const f32x4*>(bias + c4 * 4);
+    for (int t = 0; t < 9; ++t) {
+        const int yy = yp + t / 3 - 1, xx = xp + t % 3 - 1;
+        if (yy < 0 || yy >= Hp || xx < 0 || xx >= Wp) continue;                  // the conv's own zero padding of the padded image
+        const int sy = min(max(yy - pt, 0), H - 1), sx = min(max(xx - pl, 0), W - 1);   // replicate padding (InputPadder)
+#pragma unroll
+        for (int ci = 0; ci < 3; ++ci) {
+            const float p = img[(((long long)b * C + (C == 1 ? 0 : ci)) * H + sy) * W + sx];
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (t * 3 + ci) * 16 + c4 * 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[r] = __builtin_fmaf(p, wv[r], s[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] = selu(s[r]);
+    *reinterpret_cast<f32x4*>(out + pix * 16 + c4 * 4) = s;
+}
+
+// f x f average pooling (nn.AvgPool2d, stride f), NHWC, C % 4 == 0.  thread = (output pixel, 4 channels)
+__global__ __launch_bounds__(256) void ak_pool_kernel(const float* in, float* out, int B, int H, int W, int C, int f) {
+    const int Ho = H / f, Wo = W / f, C4 = C >> 2;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * Ho * Wo * C4;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % C4);
+    const long long pix = idx / C4;
+    const int xo = (int)(pix % Wo), yo = (int)((pix / Wo) % Ho), b = (int)(pix / ((long long)Wo * Ho));
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < f; ++i)
+        for (int j = 0; j < f; ++j) s += *reinterpret_cast<const f32x4*>(in + (((long long)b * H + yo * f + i) * W + xo * f + j) * C + c4 * 4);
+    const float inv = (float)(f * f);
+    *reinterpret_cast<f32x4*>(out + pix * C + c4 * 4) = f32x4{s[0] / inv, s[1] / inv, s[2] / inv, s[3] / inv};
+}
+
+// torchvision deform_conv2d sampling (3 x 3, pad 1, stride 1, one offset group, no mask): in [B][h][w][cin], off [B][h][w][18]
+// (tap k = 3i + j: dy = channel 2k, dx = channel 2k + 1, clamped to +-max_off) -> cols [B][h][w][9][cin].  thread = (pixel, tap, 4 channels)
+__global__ __launch_bounds__(256) void ak_deform_gather_kernel(const float* in, const float* off, float* cols, int B, int h, int w, int cin, float max_off) {
+    const int C4 = cin >> 2;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * h * w * 9 * C4;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % C4);
+    const long long rest = idx / C4;
+    const int k = (int)(rest % 9);
+    const long long pix = rest / 9;
+    const int x = (int)(pix % w), y = (int)((pix / w) % h), b = (int)(pix / ((long long)w * h));
+    const float dy = fminf(fmaxf(off[pix * 18 + 2 * k], -max_off), max_off), dx = fminf(fmaxf(off[pix * 18 + 2 * k + 1], -max_off), max_off);
+    const float py = (float)(y - 1 + k / 3) + dy, px = (float)(x - 1 + k % 3) + dx;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (!(py <= -1.f || py >= (float)h || px <= -1.f || px >= (float)w)) {
+        const int hl = (int)floorf(py), wl = (int)floorf(px), hh = hl + 1, wh = wl + 1;
+        const float lh = py - (float)hl, lw = px - (float)wl, uh = 1.f - lh, uw = 1.f - lw;
+        const float* base = in + (long long)b * h * w * cin + c4 * 4;
+        auto at = [&](int yy, int xx) { return *reinterpret_cast<const f32x4*>(base + ((long long)yy * w + xx) * cin); };
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 v1 = (hl >= 0 && wl >= 0) ? at(hl, wl) : z;
+        const f32x4 v2 = (hl >= 0 && wh <= w - 1) ? at(hl, wh) : z;
+        const f32x4 v3 = (hh <= h - 1 && wl >= 0) ? at(hh, wl) : z;
+        const f32x4 v4 = (hh <= h - 1 && wh <= w - 1) ? at(hh, wh) : z;
+        const float w1 = uh * uw, w2 = uh * lw, w3 = lh * uw, w4 = lh * lw;
+        v = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
+    }
+    *reinterpret_cast<f32x4*>(cols + (pix * 9 + k) * cin + c4 * 4) = v;
+}
+
+// bilinear upsampling coordinate (nn.Upsample, align_corners=True): source rows i0 / i1 and their weights for output row `dst`
+struct Up { int i0, i1; float l0, l1; };
+__device__ __forceinline__ Up up_coord(int dst, int in, int out) {
+    if (in == out) return Up{dst, dst, 1.f, 0.f};
+    const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+    const float src = scale * (float)dst;
+    const int i0 = min((int)floorf(src), in - 1);
+    const float l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+    return Up{i0, i0 + (i0 < in - 1 ? 1 : 0), 1.f - l1, l1};
+}
+
+// the four 32-channel level maps of x1234 (after conv1 .. conv4 + SELU); level l has (Hp >> sh[l]) x (Wp >> sh[l]) pixels, sh = 0, 1, 3, 5
+struct AkLevels { const float* x[4]; int B, Hp, Wp; };
+__device__ __forceinline__ int lvl_shift(int l) { return l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); }
+
+// score_head.0 (128 -> 8, no bias) + SELU on x1234 built per padded pixel.  w0: [8][128].  out [B][Hp][Wp][8].  thread = padded pixel
+__global__ __launch_bounds__(256) void ak_score_head0_kernel(AkLevels L, const float* w0, float* out) {
+    __shared__ float sw[8 * 128];
+    for (int i = threadIdx.x; i < 8 * 128; i += 256) sw[i] = w0[i];
+    __syncthreads();
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= (long long)L.B * L.Hp * L.Wp) return;
+    const int xp = (int)(pix % L.Wp), yp = (int)((pix / L.Wp) % L.Hp), b = (int)(pix / ((long long)L.Wp * L.Hp));
+    float acc[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) acc[o] = 0.f;
+    for (int l = 0; l < 4; ++l) {
+        const int sh = lvl_shift(l), h = L.Hp >> sh, w = L.Wp >> sh;
+        const Up uy = up_coord(yp, h, L.Hp), ux = up_coord(xp, w, L.Wp);
+        const float* m = L.x[l] + (long long)b * h * w * 32;
+        const float* p00 = m + ((long long)uy.i0 * w + ux.i0) * 32; const float* p01 = m + ((long long)uy.i0 * w + ux.i1) * 32;
+        const float* p10 = m + ((long long)uy.i1 * w + ux.i0) * 32; const float* p11 = m + ((long long)uy.i1 * w + ux.i1) * 32;
+        for (int c4 = 0; c4 < 8; ++c4) {
+            f32x4 v;
+            if (l == 0) v = *reinterpret_cast<const f32x4*>(p00 + c4 * 4);
+            else {
+                const f32x4 a00 = *reinterpret_cast<const f32x4*>(p00 + c4 * 4), a01 = *reinterpret_cast<const f32x4*>(p01 + c4 * 4);
+                const f32x4 a10 = *reinterpret_cast<const f32x4*>(p10 + c4 * 4), a11 = *reinterpret_cast<const f32x4*>(p11 + c4 * 4);
+                v = uy.l0 * (ux.l0 * a00 + ux.l1 * a01) + uy.l1 * (ux.l0 * a10 + ux.l1 * a11);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = l * 32 + c4 * 4 + r;
+#pragma unroll
+                for (int o = 0; o < 8; ++o) acc[o] = __builtin_fmaf(sw[o * 128 + c], v[r], acc[o]);
+            }
+        }
+    }
+    f32x4 r0 = {selu(acc[0]), selu(acc[1]), selu(acc[2]), selu(acc[3])}, r1 = {selu(acc[4]), selu(acc[5]), selu(acc[6]), selu(acc[7])};
+    *reinterpret_cast<f32x4*>(out + pix * 8) = r0;
+    *reinterpret_cast<f32x4*>(out + pix * 8 + 4) = r1;
+}
+
+// score_head.2 / .4 / .6: 3 x 3, zero pad, no bias, raw weights [COUT][CIN][3][3].  Not FINAL: SELU, [B][Hp][Wp][COUT].  FINAL (COUT = 1): sigmoid
+// and the unpad crop, scores [B][H][W].  thread = output pixel
+template <int CIN, int COUT, bool FINAL>
+__global__ __launch_bounds__(256) void ak_small_conv_kernel(const float* in, const float* w, float* out, int B, int Hp, int Wp, int H, int W, int pt, int pl) {
+    const int OH = FINAL ? H : Hp, OW = FINAL ? W : Wp;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= (long long)B * OH * OW) return;
+    const int xo = (int)(pix % OW), yo = (int)((pix / OW) % OH), b = (int)(pix / ((long long)OW * OH));
+    const int yp = FINAL ? yo + pt : yo, xp = FINAL ? xo + pl : xo;
+    float acc[COUT];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
+    for (int t = 0; t < 9; ++t) {
+        const int yy = yp + t / 3 - 1, xx = xp + t % 3 - 1;
+        if (yy < 0 || yy >= Hp || xx < 0 || xx >= Wp) continue;
+        const float* p = in + (((long long)b * Hp + yy) * Wp + xx) * CIN;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) {
+            const float v = p[ci];
+#pragma unroll
+            for (int o = 0; o < COUT; ++o) acc[o] = __builtin_fmaf(w[(o * CIN + ci) * 9 + t], v, acc[o]);
+        }
+    }
+    if constexpr (FINAL) {
+        out[pix] = 1.f / (1.f + expf(-acc[0]));
+    } else {
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) out[pix * COUT + o] = selu(acc[o]);
+    }
+}
+
+// ==================================================================================================== weight packing
+enum : int { PK_TAP_CO_CI = 0, PK_CO_TAP_CI = 1, PK_TAP_CI_CO = 2, PK_COPY = 3, PK_AGG = 4 };
+// dst weight = s[co] * src (layout by mode), s = gamma / sqrt(var + eps) with BN, else 1; bias_dst[co] = s (cbias - mean) + beta (+ extra)
+__global__ __launch_bounds__(256) void ak_fold_kernel(const float* src, float* dst, float* bias_dst, int Cout, int Cin, int kk, int mode, const float* gamma,
+                                                      const float* beta, const float* mean, const float* var, const float* cbias, const float* extra) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)Cout * Cin * kk;
+    if (i >= total) return;
+    int co, ci, t;
+    if (mode == PK_AGG) {    // src [n_pos][128][128] = (p, c, d) -> dst [d][p * 128 + c]; Cin = n_pos * 128
+        co = (int)(i % Cout); ci = (int)(i / Cout); t = 0;
+    } else {
+        t = (int)(i % kk); ci = (int)((i / kk) % Cin); co = (int)(i / ((long long)kk * Cin));
+    }
+    const float s = gamma ? gamma[co] / sqrtf(var[co] + 1e-5f) : 1.f;
+    const float v = s * src[i];
+    long long o;
+    switch (mode) {
+        case PK_TAP_CO_CI: o = ((long long)t * Cout + co) * Cin + ci; break;
+        case PK_CO_TAP_CI: o = ((long long)co * kk + t) * Cin + ci; break;
+        case PK_TAP_CI_CO: o = ((long long)t * Cin + ci) * Cout + co; break;
+        case PK_AGG: o = (long long)co * Cin + ci; break;
+        default: o = i;
+    }
+    dst[o] = v;
+    if (bias_dst && ci == 0 && t == 0) {
+        float bv = cbias ? cbias[co] : 0.f;
+        if (gamma) bv = s * (bv - mean[co]) + beta[co];
+        if (extra) bv += extra[co];
+        bias_dst[co] = bv;
+    }
+}
+
+// ==================================================================================================== DKD
+struct AkDetect {
+    const float* S;            // [B][H][W] scores
+    int B, H, W, r;
+    const float* image_size;   // [B][2] (w, h) or null
+    unsigned char *m0, *m1, *supp; float* ss; float* nms;
+    int* rowcnt; double* rowsum; float* th;
+    int* cand_idx; float* cand_score; int* cand_total;
+    int cap; int* sel; unsigned* selkey; int* nsel; int* sorted;
+    float scores_th; int topk; int n_limit;
+    float* kpts; float* kscores; float* knorm; int* counts;
+};
+
+// mode 0: m_out = S == maxpool(S); 1: supp = maxpool(m_in) > 0, ss = supp ? 0 : S; 2: m_out = m_in | (ss == maxpool(ss) & ~supp)
+__global__ __launch_bounds__(256) void ak_nms_kernel(AkDetect a, int mode, const unsigned char* m_in, unsigned char* m_out) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long long)a.B * a.H * a.W) return;
+    const int x = (int)(p % a.W), y = (int)((p / a.W) % a.H);
+    const long long base = p - ((long long)y * a.W + x);
+    const int r = a.r;
+    if (mode == 0 || mode == 2) {
+        const float* src = mode == 0 ? a.S : a.ss;
+        float m = -INFINITY;
+        for (int dy = -r; dy <= r; ++dy)
+            for (int dx = -r; dx <= r; ++dx) {
+                const int yy = y + dy, xx = x + dx;
+                if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) m = fmaxf(m, src[base + (long long)yy * a.W + xx]);
+            }
+        if (mode == 0) m_out[p] = a.S[p] == m;
+        else m_out[p] = m_in[p] || (a.ss[p] == m && !a.supp[p]);
+    } else {
+        unsigned char v = 0;
+        for (int dy = -r; dy <= r; ++dy)
+            for (int dx = -r; dx <= r; ++dx) {
+                const int yy = y + dy, xx = x + dx;
+                if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) v |= m_in[base + (long long)yy * a.W + xx];
+            }
+        a.supp[p] = v;
+        a.ss[p] = v ? 0.f : a.S[p];
+    }
+}
+
+// nms = mask ? S : 0, borders of r pixels set to 0 (the far ones from image_size when given)
+__global__ __launch_bounds__(256) void ak_nms_final_kernel(AkDetect a, const unsigned char* mask) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long long)a.B * a.H * a.W) return;
+    const int x = (int)(p % a.W), y = (int)((p / a.W) % a.H), b = (int)(p / ((long long)a.W * a.H));
+    int hl = a.H, wl = a.W;
+    if (a.image_size) { wl = (int)a.image_size[2 * b]; hl = (int)a.image_size[2 * b + 1]; }   // .long(): truncation
+    const bool border = y < a.r || x < a.r || y >= hl - a.r || x >= wl - a.r;
+    a.nms[p] = (mask[p] && !border) ? a.S[p] : 0.f;
+}
+
+__device__ __forceinline__ int block_sum_int(int v, int* sh) {   // 256 threads
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// per row: number of nms > threshold (th[b] when `th` is set, else scores_th) and the row sum of S (for the mean).  grid (H, B)
+__global__ __launch_bounds__(256) void ak_row_stats_kernel(AkDetect a, const float* th) {
+    const int y = blockIdx.x, b = blockIdx.y;
+    const long long row = ((long long)b * a.H + y) * a.W;
+    const float t = th ? th[b] : a.scores_th;
+    int cnt = 0; double sum = 0.0;
+    for (int x = threadIdx.x; x < a.W; x += 256) { cnt += a.nms[row + x] > t; sum += (double)a.S[row + x]; }
+    __shared__ int sh[4];
+    __shared__ double shd[256];
+    cnt = block_sum_int(cnt, sh);
+    shd[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) shd[threadIdx.x] += shd[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) { a.rowcnt[b * a.H + y] = cnt; if (!th) a.rowsum[b * a.H + y] = shd[0]; }
+}
+
+// the threshold of each image (aliked.py:183-193): top-k mode: > 0 (the positive NMS maxima are the candidates); threshold mode: scores_th,
+// unless no pixel of the WHOLE batch passes it (or scores_th <= 0): the image's mean score.  grid (B), 256 threads
+__global__ __launch_bounds__(256) void ak_decide_kernel(AkDetect a) {
+    const int b = blockIdx.x;
+    __shared__ int sh[4];
+    __shared__ double shd[256];
+    int any = 0;
+    for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.rowcnt[i];
+    any = block_sum_int(any, sh);
+    double s = 0.0;
+    for (int y = threadIdx.x; y < a.H; y += 256) s += a.rowsum[b * a.H + y];
+    shd[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) shd[threadIdx.x] += shd[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) {
+        const float mean = (float)(shd[0] / ((double)a.H * a.W));
+        a.th[b] = a.topk > 0 ? 0.f : ((a.scores_th > 0.f && any > 0) ? a.scores_th : mean);
+    }
+}
+
+// raster-order compaction (the order of nonzero()): grid (H, B)
+__global__ __launch_bounds__(256) void ak_compact_kernel(AkDetect a) {
+    const int y = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float t = a.th[b];
+    __shared__ int sh[4];
+    int pre = 0;
+    for (int yy = tid; yy < y; yy += 256) pre += a.rowcnt[b * a.H + yy];
+    int running = block_sum_int(pre, sh);
+    const long long row = ((long long)b * a.H + y) * a.W;
+    const long long cbase = (long long)b * a.H * a.W;
+    for (int x0 = 0; x0 < a.W; x0 += 256) {
+        const int x = x0 + tid;
+        const float v = x < a.W ? a.nms[row + x] : 0.f;
+        const bool hit = x < a.W && v > t;
+        const unsigned long long bal = __ballot(hit);
+        __syncthreads();
+        if (lane == 0) sh[wave] = __popcll(bal);
+        __syncthreads();
+        int off = running;
+        for (int w = 0; w < wave; ++w) off += sh[w];
+        off += __popcll(bal & ((1ull << lane) - 1ull));
+        if (hit) { a.cand_idx[cbase + off] = y * a.W + x; a.cand_score[cbase + off] = a.S[row + x]; }
+        running += sh[0] + sh[1] + sh[2] + sh[3];
+    }
+    if (y == a.H - 1 && tid == 0) a.cand_total[b] = running;
+}
+
+__device__ __forceinline__ unsigned fkey(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+
+// per image: the candidates that survive the limit, in raster order (sel), with their keys; sorted[b] = the output is ordered by score
+// (top-k mode, or more candidates than n_limit).  Radix select of the K-th largest key as in lg_superpoint.hip.  grid (B), 1024 threads
+__global__ __launch_bounds__(1024) void ak_select_kernel(AkDetect a) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int total = a.cand_total[b];
+    const float* csc = a.cand_score + (long long)b * a.H * a.W;
+    int* sel = a.sel + (long long)b * a.cap;
+    unsigned* skey = a.selkey + (long long)b * a.cap;
+    const int K = a.topk > 0 ? a.topk : a.n_limit;
+    const bool limit = total > K;
+    __shared__ unsigned hist[256];
+    __shared__ unsigned prefix_sh, need_sh;
+    __shared__ int wsum[16];
+    unsigned prefix = 0, need = 0xFFFFFFFFu;
+    if (limit) {
+        need = (unsigned)K;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            const unsigned fixed_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+            for (int i = tid; i < total; i += 1024) {
+                const unsigned k = fkey(csc[i]);
+                if ((k & fixed_mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned acc = 0; int d = 255;
+                for (; d > 0; --d) { if (acc + hist[d] >= need) break; acc += hist[d]; }
+                prefix_sh = prefix | ((unsigned)d << shift); need_sh = need - acc;
+            }
+            __syncthreads();
+            prefix = prefix_sh; need = need_sh;
+            __syncthreads();
+        }
+    }
+    // keep key > prefix, and the first `need` keys == prefix in raster order (everything when not limited)
+    int taken = 0, eq_taken = 0;
+    for (int i0 = 0; i0 < total; i0 += 1024) {
+        const int i = i0 + tid;
+        const unsigned k = i < total ? fkey(csc[i]) : 0u;
+        const bool eq = limit && i < total && k == prefix;
+        const unsigned long long beq = __ballot(eq);
+        __syncthreads();
+        if (lane == 0) wsum[wave] = __popcll(beq);
+        __syncthreads();
+        int eoff = eq_taken;
+        for (int w = 0; w < wave; ++w) eoff += wsum[w];
+        eoff += __popcll(beq & ((1ull << lane) - 1ull));
+        int eall = 0;
+        for (int w = 0; w < 16; ++w) eall += wsum[w];
+        const bool keep = i < total && (!limit || k > prefix || (eq && eoff < (int)need));
+        const unsigned long long bk = __ballot(keep);
+        __syncthreads();
+        if (lane == 0) wsum[wave] = __popcll(bk);
+        __syncthreads();
+        int off = taken;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        off += __popcll(bk & ((1ull << lane) - 1ull));
+        if (keep && off < a.cap) { sel[off] = i; skey[off] = k; }
+        int all = 0;
+        for (int w = 0; w < 16; ++w) all += wsum[w];
+        taken += all; eq_taken += eall;
+    }
+    if (tid == 0) { a.nsel[b] = min(taken, a.cap); a.sorted[b] = (a.topk > 0 || limit) ? 1 : 0; }
+}
+
+// per output slot: rank (score descending, raster order among equals, when sorted), soft-argmax refinement and the bilinear score
+// (aliked.py:212-247).  Rows >= the image's count are zero-filled.  grid (cap / 256, B)
+__global__ __launch_bounds__(256) void ak_refine_kernel(AkDetect a) {
+    const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.cap) return;
+    const int n = a.nsel[b];
+    const long long ob = (long long)b * a.cap;
+    if (j == 0) a.counts[b] = n;
+    if (j >= n) {   // padding rows (written by their own slot j: ranks are a permutation of [0, n))
+        a.kpts[2 * (ob + j)] = 0.f; a.kpts[2 * (ob + j) + 1] = 0.f; a.kscores[ob + j] = 0.f;
+        a.knorm[2 * (ob + j)] = 0.f; a.knorm[2 * (ob + j) + 1] = 0.f;
+        return;
+    }
+    const unsigned* skey = a.selkey + ob;
+    int rank = j;
+    if (a.sorted[b]) {
+        const unsigned k = skey[j];
+        rank = 0;
+        for (int i = 0; i < n; ++i) { const unsigned q = skey[i]; rank += (q > k) || (q == k && i < j); }
+    }
+    const int p = a.cand_idx[(long long)b * a.H * a.W + a.sel[ob + j]];
+    const int y = p / a.W, x = p - y * a.W, r = a.r;
+    const float* S = a.S + (long long)b * a.H * a.W;
+    auto sv = [&](int yy, int xx) { return (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? S[(long long)yy * a.W + xx] : 0.f; };   // unfold: zero padding
+    float mx = -INFINITY;
+    for (int dy = -r; dy <= r; ++dy)
+        for (int dx = -r; dx <= r; ++dx) mx = fmaxf(mx, sv(y + dy, x + dx));
+    float se = 0.f, sx = 0.f, sy = 0.f;
+    for (int dy = -r; dy <= r; ++dy)
+        for (int dx = -r; dx <= r; ++dx) {
+            const float e = expf(__fdiv_rn(sv(y + dy, x + dx) - mx, 0.1f));
+            se += e; sx = __builtin_fmaf(e, (float)dx, sx); sy = __builtin_fmaf(e, (float)dy, sy);
+        }
+    const float rx = __fdiv_rn(sx, se), ry = __fdiv_rn(sy, se);
+    const float wm1 = (float)(a.W - 1), hm1 = (float)(a.H - 1);
+    // (xy_nms + residual) / wh * 2 - 1, each step rounded like the reference's tensor ops (no contraction)
+    const float kx = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)x, rx), wm1), 2.f), 1.f);
+    const float ky = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)y, ry), hm1), 2.f), 1.f);
+    // grid_sample(bilinear, align_corners=True, zeros)
+    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(kx, 1.f), 2.f), wm1), iy = __fmul_rn(__fdiv_rn(__fadd_rn(ky, 1.f), 2.f), hm1);
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float ex = fx + 1.f, ey = fy + 1.f;
+    const float score = sv(y0, x0) * ((ex - ix) * (ey - iy)) + sv(y0, x0 + 1) * ((ix - fx) * (ey - iy)) + sv(y0 + 1, x0) * ((ex - ix) * (iy - fy)) +
+                        sv(y0 + 1, x0 + 1) * ((ix - fx) * (iy - fy));
+    const long long o = ob + rank;
+    a.kpts[2 * o] = __fdiv_rn(__fmul_rn(wm1, __fadd_rn(kx, 1.f)), 2.f);       // wh * (k + 1) / 2 (aliked.py:756)
+    a.kpts[2 * o + 1] = __fdiv_rn(__fmul_rn(hm1, __fadd_rn(ky, 1.f)), 2.f);
+    a.kscores[o] = score;
+    a.knorm[2 * o] = kx; a.knorm[2 * o + 1] = ky;
+}
+
+// ==================================================================================================== SDDH
+// one lane = 2 channels of x1234 at padded pixel (yp, xp): lanes 0-15 x1, 16-31 x2 (upsampled), 32-47 x3, 48-63 x4; L2-normalised over the wave
+__device__ __forceinline__ f32x2 x1234_norm(const AkLevels& L, int b, int yp, int xp, int lane) {
+    const int l = lane >> 4, c = (lane & 15) * 2, sh = lvl_shift(l), h = L.Hp >> sh, w = L.Wp >> sh;
+    const float* m = L.x[l] + (long long)b * h * w * 32 + c;
+    f32x2 v;
+    if (l == 0) v = *reinterpret_cast<const f32x2*>(m + ((long long)yp * w + xp) * 32);
+    else {
+        const Up uy = up_coord(yp, h, L.Hp), ux = up_coord(xp, w, L.Wp);
+        const f32x2 a00 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i0 * w + ux.i0) * 32), a01 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i0 * w + ux.i1) * 32);
+        const f32x2 a10 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i1 * w + ux.i0) * 32), a11 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i1 * w + ux.i1) * 32);
+        v = uy.l0 * (ux.l0 * a00 + ux.l1 * a01) + uy.l1 * (ux.l0 * a10 + ux.l1 * a11);
+    }
+    const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1]));
+    const float d = fmaxf(nrm, 1e-12f);
+    return f32x2{v[0] / d, v[1] / d};
+}
+
+struct AkDescribe {
+    AkLevels L; int H, W, pt, pl, N, np;   // unpadded size, padding offsets, keypoint rows per image, n_pos
+    const float* knorm;                    // [B][N][2] normalised keypoints (DKD)
+    float* patch; float* off1; float* spos; float* feat; float* sf; float* draw;
+    const float* w_off2; const float* b_off2;
+    const int* counts; float* out;
+};
+
+__device__ __forceinline__ void kp_pixel(const AkDescribe& d, int row, float& kw, float& kh) {   // (kpts / 2 + 0.5) * wh  (aliked.py:542)
+    const float* k = d.knorm + 2LL * row;
+    kw = __fmul_rn(__fadd_rn(__fdiv_rn(k[0], 2.f), 0.5f), (float)(d.W - 1));
+    kh = __fmul_rn(__fadd_rn(__fdiv_rn(k[1], 2.f), 0.5f), (float)(d.H - 1));
+}
+
+// get_patches (aliked.py:48-64) of the normalised x1234 map: patch [row][tap = 3 dy + dx][128].  grid (rows), 4 waves: wave w takes taps w, w + 4, w + 8
+__global__ __launch_bounds__(256) void ak_patch_kernel(AkDescribe d) {
+    const int row = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, b = row / d.N;
+    float kw, kh;
+    kp_pixel(d, row, kw, kh);
+    const long long lw = (long long)kw, lh = (long long)kh;                      // .long()
+    int cx = (int)(long long)((float)lw - 1.5f + 1.f), cy = (int)(long long)((float)lh - 1.5f + 1.f);
+    cx = min(max(cx, 0), d.W - 1 - 3); cy = min(max(cy, 0), d.H - 1 - 3);
+    for (int t = wv; t < 9; t += 4) {
+        const f32x2 v = x1234_norm(d.L, b, cy + t / 3 + d.pt, cx + t % 3 + d.pl, lane);
+        *reinterpret_cast<f32x2*>(d.patch + ((long long)row * 9 + t) * 128 + lane * 2) = v;
+    }
+}
+
+// offset_conv.2 (1 x 1, bias) on the SELU'd first conv, clamp, sample positions in map pixels (grid_sample's un-normalisation).  thread = keypoint row
+__global__ __launch_bounds__(256) void ak_offsets_kernel(AkDescribe d, int rows) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const int C2 = 2 * d.np;
+    const float* o1 = d.off1 + (long long)row * C2;
+    const float mo = (float)max(d.H, d.W) / 4.f;
+    float kw, kh;
+    kp_pixel(d, row, kw, kh);
+    const float wm1 = (float)(d.W - 1), hm1 = (float)(d.H - 1);
+    for (int p = 0; p < d.np; ++p) {
+        float ox = d.b_off2[p], oy = d.b_off2[d.np + p];
+        for (int i = 0; i < C2; ++i) {
+            ox = __builtin_fmaf(d.w_off2[p * C2 + i], o1[i], ox);
+            oy = __builtin_fmaf(d.w_off2[(d.np + p) * C2 + i], o1[i], oy);
+        }
+        ox = fminf(fmaxf(ox, -mo), mo); oy = fminf(fmaxf(oy, -mo), mo);
+        const float gx = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fadd_rn(kw, ox)), wm1), 1.f);   // 2 pos / wh - 1
+        const float gy = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fadd_rn(kh, oy)), hm1), 1.f);
+        d.spos[((long long)row * d.np + p) * 2] = __fmul_rn(__fdiv_rn(__fadd_rn(gx, 1.f), 2.f), wm1);
+        d.spos[((long long)row * d.np + p) * 2 + 1] = __fmul_rn(__fdiv_rn(__fadd_rn(gy, 1.f), 2.f), hm1);
+    }
+}
+
+// bilinear sample (align_corners=True, zeros outside the unpadded map) of the normalised x1234 at every position: feat [row * np + p][128].  wave = one sample
+__global__ __launch_bounds__(256) void ak_sample_kernel(AkDescribe d, int samples) {
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= samples) return;
+    const int b = (s / d.np) / d.N;
+    const float ix = d.spos[2LL * s], iy = d.spos[2LL * s + 1];
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float ex = fx + 1.f, ey = fy + 1.f;
+    const float wgt[4] = {(ex - ix) * (ey - iy), (ix - fx) * (ey - iy), (ex - ix) * (iy - fy), (ix - fx) * (iy - fy)};   // nw ne sw se
+    f32x2 acc = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        if (x >= 0 && x < d.W && y >= 0 && y < d.H) {      // wave-uniform
+            const f32x2 v = x1234_norm(d.L, b, y + d.pt, x + d.pl, lane);
+            acc += wgt[k] * v;
+        }
+    }
+    *reinterpret_cast<f32x2*>(d.feat + (long long)s * 128 + lane * 2) = acc;
+}
+
+// F.normalize of the aggregated descriptors -> out [B][N][128]; rows >= count are zero.  wave = one row
+__global__ __launch_bounds__(256) void ak_desc_norm_kernel(AkDescribe d, int rows) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int b = row / d.N, i = row - b * d.N;
+    f32x2 v = *reinterpret_cast<const f32x2*>(d.draw + (long long)row * 128 + lane * 2);
+    const float nrm = fmaxf(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
+    v = i < d.counts[b] ? f32x2{v[0] / nrm, v[1] / nrm} : f32x2{0.f, 0.f};
+    *reinterpret_cast<f32x2*>(d.out + (long long)row * 128 + lane * 2) = v;
+}
+
+// ==================================================================================================== host-side layouts
+struct Bump {
+    long long used = 0;
+    long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
+};
+
+// packed weights (float offsets)
+struct PackLayout {
+    long long b1c1_w, b1c1_b, b1c2_w, b1c2_b;
+    long long b2c1_w, b2c1_b, b2c2_w, b2c2_b, b2ds_w;
+    struct Dcn { long long off1_w, off1_b, reg1_w, reg1_b, off2_w, off2_b, reg2_w, reg2_b, ds_w; } b3, b4;
+    long long cv[4], sh0, sh2, sh4, sh6, so0_w, so0_b, so2_w, so2_b, sf, agg;
+    long long total;
+};
+PackLayout pack_layout(int np) {
+    PackLayout P{};
+    long long n = 0;
+    auto t = [&](long long f) { const long long o = n; n += (f + 63) / 64 * 64; return o; };
+    P.b1c1_w = t(9 * 3 * 16); P.b1c1_b = t(16); P.b1c2_w = t(9 * 16 * 16); P.b1c2_b = t(16);
+    P.b2c1_w = t(9 * 32 * 16); P.b2c1_b = t(32); P.b2c2_w = t(9 * 32 * 32); P.b2c2_b = t(32); P.b2ds_w = t(32 * 16);
+    auto dcn = [&](PackLayout::Dcn& D, int ci, int co) {
+        D.off1_w = t(9 * 18 * ci); D.off1_b = t(18); D.reg1_w = t((long long)co * 9 * ci); D.reg1_b = t(co);
+        D.off2_w = t(9 * 18 * co); D.off2_b = t(18); D.reg2_w = t((long long)co * 9 * co); D.reg2_b = t(co); D.ds_w = t((long long)co * ci);
+    };
+    dcn(P.b3, 32, 64); dcn(P.b4, 64, 128);
+    const int cin[4] = {16, 32, 64, 128};
+    for (int i = 0; i < 4; ++i) P.cv[i] = t(32 * cin[i]);
+    P.sh0 = t(8 * 128); P.sh2 = t(4 * 8 * 9); P.sh4 = t(4 * 4 * 9); P.sh6 = t(4 * 9);
+    P.so0_w = t((long long)2 * np * 9 * 128); P.so0_b = t(2 * np); P.so2_w = t(4LL * np * np); P.so2_b = t(2 * np);
+    P.sf = t(128 * 128); P.agg = t((long long)np * 128 * 128);
+    P.total = n;
+    return P;
+}
+
+struct Dims { int Hp, Wp, pt, pl; };
+Dims dims_of(int h, int w) {
+    const int ph = ((h / 32 + 1) * 32 - h) % 32, pw = ((w / 32 + 1) * 32 - w) % 32;   // InputPadder(divis_by = 32)
+    return Dims{h + ph, w + pw, ph / 2, pw / 2};
+}
+
+// level maps x1 .. x4 (32 channels each), one buffer
+struct LevelLayout { long long x[4]; long long total; };
+LevelLayout level_layout(int B, int h, int w) {
+    const Dims D = dims_of(h, w);
+    Bump bp; LevelLayout L{};
+    for (int l = 0; l < 4; ++l) { const int s = l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); L.x[l] = bp.take((long long)B * (D.Hp >> s) * (D.Wp >> s) * 32 * 4); }
+    L.total = bp.used;
+    return L;
+}
+
+struct EncodeLayout { long long full_a, full_b, p2, q2, r2, p3, off, cols, t3, r3, p4, t4, r4; long long total; };
+EncodeLayout encode_layout(int B, int h, int w) {
+    const Dims D = dims_of(h, w);
+    const long long f = (long long)B * D.Hp * D.Wp, f2 = f / 4, f8 = f / 64, f32 = f / 1024;
+    Bump bp; EncodeLayout E{};
+    E.full_a = bp.take(f * 16 * 4); E.full_b = bp.take(f * 16 * 4);   // block1 (later: score head 8 + 4 channels, and 4 channels)
+    E.p2 = bp.take(f2 * 16 * 4); E.q2 = bp.take(f2 * 32 * 4); E.r2 = bp.take(f2 * 32 * 4);
+    E.p3 = bp.take(f8 * 32 * 4); E.off = bp.take(f8 * 18 * 4); E.cols = bp.take(f8 * 9 * 64 * 4); E.t3 = bp.take(f8 * 64 * 4); E.r3 = bp.take(f8 * 64 * 4);
+    E.p4 = bp.take(f32 * 64 * 4); E.t4 = bp.take(f32 * 128 * 4); E.r4 = bp.take(f32 * 128 * 4);
+    E.total = bp.used;
+    return E;
+}
+
+struct DetectLayout { long long m0, m1, supp, ss, nms, rowcnt, rowsum, th, cidx, cscore, ctotal, sel, selkey, nsel, sorted; long long total; };
+DetectLayout detect_layout(int B, int h, int w, int cap) {
+    const long long px = (long long)B * h * w;
+    Bump bp; DetectLayout L{};
+    L.m0 = bp.take(px); L.m1 = bp.take(px); L.supp = bp.take(px); L.ss = bp.take(px * 4); L.nms = bp.take(px * 4);
+    L.rowcnt = bp.take((long long)B * h * 4); L.rowsum = bp.take((long long)B * h * 8); L.th = bp.take(B * 4);
+    L.cidx = bp.take(px * 4); L.cscore = bp.take(px * 4); L.ctotal = bp.take(B * 4);
+    L.sel = bp.take((long long)B * cap * 4); L.selkey = bp.take((long long)B * cap * 4); L.nsel = bp.take(B * 4); L.sorted = bp.take(B * 4);
+    L.total = bp.used;
+    return L;
+}
+
+struct DescribeLayout { long long patch, off1, spos, feat, sf, draw; long long total; int rows_pad; };
+DescribeLayout describe_layout(int rows, int np) {
+    const int rp = (rows + 31) / 32 * 32;
+    Bump bp; DescribeLayout L{};
+    L.rows_pad = rp;
+    L.patch = bp.take((long long)rp * 9 * 128 * 4); L.off1 = bp.take((long long)rp * 2 * np * 4); L.spos = bp.take((long long)rp * np * 2 * 4);
+    L.feat = bp.take((long long)rp * np * 128 * 4); L.sf = bp.take((long long)rp * np * 128 * 4); L.draw = bp.take((long long)rp * 128 * 4);
+    L.total = bp.used;
+    return L;
+}
+
+inline unsigned blocks(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+constexpr int kTensors = 68;
+constexpr long long kMaxPixels = 1LL << 25;
+
+int fold(const float* src, float* dst, float* bias_dst, int cout, int cin, int kk, int mode, const float* const* bn, const float* cbias, const float* extra,
+         hipStream_t s) {
+    const long long total = (long long)cout * cin * kk;
+    hipLaunchKernelGGL(ak_fold_kernel, dim3(blocks(total)), dim3(256), 0, s, src, dst, bias_dst, cout, cin, kk, mode, bn ? bn[0] : nullptr, bn ? bn[1] : nullptr,
+                       bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, cbias, extra);
+    return hipGetLastError() == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, "ALIKED weight packing launch failed");
+}
+
+int check_model(int np) { return (np == 16 || np == 32) ? LG_OK : set_error(LG_ERR_INVALID, "unknown ALIKED model: n_pos must be 16 (aliked-n16, -n16rot) or 32 (aliked-n32)"); }
+int check_size(int B, int h, int w) {
+    if (B < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "ALIKED: batch >= 1 and images of at least 8 x 8 pixels");
+    const Dims D = dims_of(h, w);
+    if ((long long)D.Hp * D.Wp >= kMaxPixels) return set_error(LG_ERR_INVALID, "ALIKED: the padded image must stay below 2^25 pixels (32-bit pixel indices)");
+    return LG_OK;
+}
+
+}  // namespace
+}  // namespace lg
+
+using namespace lg;
+
+extern "C" {
+
+int64_t lg_aliked_packed_bytes(int32_t n_pos) { return check_model(n_pos) == LG_OK ? pack_layout(n_pos).total * 4 : 0; }
+
+int lg_aliked_pack_weights(int32_t n_pos, const float* const* t, int32_t n_tensors, void* packed, int64_t packed_bytes, void* hip_stream) {
+    if (int rc = check_model(n_pos)) return rc;
+    if (!t || !packed || n_tensors != kTensors) return set_error(LG_ERR_INVALID, "lg_aliked_pack_weights: 68 state tensors (state-dict order, without num_batches_tracked)");
+    for (int i = 0; i < kTensors; ++i) if (!t[i]) return set_error(LG_ERR_INVALID, "lg_aliked_pack_weights: null tensor");
+    const PackLayout P = pack_layout(n_pos);
+    if (packed_bytes < P.total * 4) return set_error(LG_ERR_INVALID, "lg_aliked_pack_weights: buffer smaller than lg_aliked_packed_bytes");
+    float* o = static_cast<float*>(packed);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    int rc = LG_OK;
+    auto F = [&](int i, long long w, long long b, int co, int ci, int kk, int mode, int bn, int cbias, int extra) {
+        if (rc) return;
+        rc = fold(t[i], o + w, b >= 0 ? o + b : nullptr, co, ci, kk, mode, bn >= 0 ? t + bn : nullptr, cbias >= 0 ? t[cbias] : nullptr, extra >= 0 ? t[extra] : nullptr, s);
+    };
+    // state-dict order: block1 0-9, block2 10-21, block3 22-37, block4 38-53, conv1-4 54-57, score_head 58-61, desc_head 62-67
+    F(0, P.b1c1_w, P.b1c1_b, 16, 3, 9, PK_TAP_CI_CO, 1, -1, -1);
+    F(5, P.b1c2_w, P.b1c2_b, 16, 16, 9, PK_TAP_CO_CI, 6, -1, -1);
+    F(10, P.b2c1_w, P.b2c1_b, 32, 16, 9, PK_TAP_CO_CI, 11, -1, -1);
+    F(15, P.b2c2_w, P.b2c2_b, 32, 32, 9, PK_TAP_CO_CI, 16, -1, 21);    // + downsample bias
+    F(20, P.b2ds_w, -1, 32, 16, 1, PK_TAP_CO_CI, -1, -1, -1);
+    auto dcn = [&](int i0, const PackLayout::Dcn& D, int ci, int co) {
+        F(i0, D.off1_w, D.off1_b, 18, ci, 9, PK_TAP_CO_CI, -1, i0 + 1, -1);
+        F(i0 + 2, D.reg1_w, D.reg1_b, co, ci, 9, PK_CO_TAP_CI, i0 + 3, -1, -1);
+        F(i0 + 7, D.off2_w, D.off2_b, 18, co, 9, PK_TAP_CO_CI, -1, i0 + 8, -1);
+        F(i0 + 9, D.reg2_w, D.reg2_b, co, co, 9, PK_CO_TAP_CI, i0 + 10, -1, i0 + 15);
+        F(i0 + 14, D.ds_w, -1, co, ci, 1, PK_TAP_CO_CI, -1, -1, -1);
+    };
+    dcn(22, P.b3, 32, 64);
+    dcn(38, P.b4, 64, 128);
+    const int cin[4] = {16, 32, 64, 128};
+    for (int i = 0; i < 4; ++i) F(54 + i, P.cv[i], -1, 32, cin[i], 1, PK_TAP_CO_CI, -1, -1, -1);
+    F(58, P.sh0, -1, 8, 128, 1, PK_COPY, -1, -1, -1);
+    F(59, P.sh2, -1, 4, 8, 9, PK_COPY, -1, -1, -1);
+    F(60, P.sh4, -1, 4, 4, 9, PK_COPY, -1, -1, -1);
+    F(61, P.sh6, -1, 1, 4, 9, PK_COPY, -1, -1, -1);
+    F(62, P.so0_w, P.so0_b, 2 * n_pos, 128, 9, PK_CO_TAP_CI, -1, 63, -1);
+    F(64, P.so2_w, P.so2_b, 2 * n_pos, 2 * n_pos, 1, PK_COPY, -1, 65, -1);
+    F(66, P.sf, -1, 128, 128, 1, PK_TAP_CO_CI, -1, -1, -1);
+    F(67, P.agg, -1, 128, n_pos * 128, 1, PK_AGG, -1, -1, -1);
+    return rc;
+}
+
+int64_t lg_aliked_levels_bytes(int32_t batch, int32_t h, int32_t w) { return check_size(batch, h, w) == LG_OK ? level_layout(batch, h, w).total : 0; }
+int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n_pos) {
+    if (check_model(n_pos) != LG_OK || check_size(batch, h, w) != LG_OK) return 0;
+    return encode_layout(batch, h, w).total;
+}
+
+int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
+                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+    if (int rc = check_model(n_pos)) return rc;
+    if (int rc = check_size(batch, h, w)) return rc;
+    if (channels != 1 && channels != 3) return set_error(LG_ERR_INVALID, "ALIKED: images of 1 or 3 channels");
+    if (!image || !packed || !levels || !workspace || !scores) return set_error(LG_ERR_INVALID, "null pointer");
+    if (workspace_bytes < encode_layout(batch, h, w).total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_workspace_bytes)");
+    const PackLayout P = pack_layout(n_pos);
+    const EncodeLayout E = encode_layout(batch, h, w);
+    const LevelLayout LL = level_layout(batch, h, w);
+    const Dims D = dims_of(h, w);
+    const int B = batch, Hp = D.Hp, Wp = D.Wp, H2 = Hp / 2, W2 = Wp / 2, H8 = Hp / 8, W8 = Wp / 8, H32 = Hp / 32, W32 = Wp / 32;
+    const float* p = static_cast<const float*>(packed);
+    char* ws = static_cast<char*>(workspace);
+    char* lv = static_cast<char*>(levels);
+    auto W_ = [&](long long off) { return reinterpret_cast<float*>(ws + off); };
+    float* x[4];
+    for (int l = 0; l < 4; ++l) x[l] = reinterpret_cast<float*>(lv + LL.x[l]);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const long long f = (long long)B * Hp * Wp;
+    // ---- block1 (ConvBlock) at full resolution
+    hipLaunchKernelGGL(ak_conv_first_kernel, dim3(blocks(f * 4)), dim3(256), 0, s, image, channels, h, w, Hp, Wp, D.pt, D.pl, p + P.b1c1_w, p + P.b1c1_b, W_(E.full_a), B);
+    conv(W_(E.full_a), p + P.b1c2_w, p + P.b1c2_b, W_(E.full_b), B, Hp, Wp, 16, 16, 9, 1, s);
+    conv(W_(E.full_b), p + P.cv[0], nullptr, x[0], B, Hp, Wp, 16, 32, 1, 1, s);                  // conv1 + SELU -> x1
+    // ---- block2 (ResBlock) at 1/2
+    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 4 * 4)), dim3(256), 0, s, W_(E.full_b), W_(E.p2), B, Hp, Wp, 16, 2);
+    conv(W_(E.p2), p + P.b2c1_w, p + P.b2c1_b, W_(E.q2), B, H2, W2, 16, 32, 9, 1, s);
+    conv(W_(E.q2), p + P.b2c2_w, p + P.b2c2_b, W_(E.r2), B, H2, W2, 32, 32, 9, 1, s, W_(E.p2), p + P.b2ds_w, 16);
+    conv(W_(E.r2), p + P.cv[1], nullptr, x[1], B, H2, W2, 32, 32, 1, 1, s);                      // conv2 -> x2
+    // ---- blocks 3 and 4 (deformable ResBlocks) at 1/8 and 1/32
+    auto dcn_block = [&](const PackLayout::Dcn& Dc, const float* in, float* t, float* out, int hh, int ww, int ci, int co) {
+        const float mo = (float)max(hh, ww) / 4.f;
+        const long long px = (long long)B * hh * ww;
+        conv(in, p + Dc.off1_w, p + Dc.off1_b, W_(E.off), B, hh, ww, ci, 18, 9, 0, s);
+        hipLaunchKernelGGL(ak_deform_gather_kernel, dim3(blocks(px * 9 * (ci / 4))), dim3(256), 0, s, in, W_(E.off), W_(E.cols), B, hh, ww, ci, mo);
+        conv(W_(E.cols), p + Dc.reg1_w, p + Dc.reg1_b, t, B, hh, ww, 9 * ci, co, 1, 1, s);
+        conv(t, p + Dc.off2_w, p + Dc.off2_b, W_(E.off), B, hh, ww, co, 18, 9, 0, s);
+        hipLaunchKernelGGL(ak_deform_gather_kernel, dim3(blocks(px * 9 * (co / 4))), dim3(256), 0, s, t, W_(E.off), W_(E.cols), B, hh, ww, co, mo);
+        conv(W_(E.cols), p + Dc.reg2_w, p + Dc.reg2_b, out, B, hh, ww, 9 * co, co, 1, 1, s, in, p + Dc.ds_w, ci);
+    };
+    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 64 * 8)), dim3(256), 0, s, W_(E.r2), W_(E.p3), B, H2, W2, 32, 4);
+    dcn_block(P.b3, W_(E.p3), W_(E.t3), W_(E.r3), H8, W8, 32, 64);
+    conv(W_(E.r3), p + P.cv[2], nullptr, x[2], B, H8, W8, 64, 32, 1, 1, s);                      // conv3 -> x3
+    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 1024 * 16)), dim3(256), 0, s, W_(E.r3), W_(E.p4), B, H8, W8, 64, 4);
+    dcn_block(P.b4, W_(E.p4), W_(E.t4), W_(E.r4), H32, W32, 64, 128);
+    conv(W_(E.r4), p + P.cv[3], nullptr, x[3], B, H32, W32, 128, 32, 1, 1, s);                  // conv4 -> x4
+    // ---- score head on x1234 (never materialised) -> scores [B][h][w]
+    AkLevels L{{x[0], x[1], x[2], x[3]}, B, Hp, Wp};
+    float* s8 = W_(E.full_a);                  // [f][8]
+    float* s4a = W_(E.full_b);                 // [f][4]
+    float* s4b = W_(E.full_a) + f * 8;         // [f][4]
+    hipLaunchKernelGGL(ak_score_head0_kernel, dim3(blocks(f)), dim3(256), 0, s, L, p + P.sh0, s8);
+    hipLaunchKernelGGL((ak_small_conv_kernel<8, 4, false>), dim3(blocks(f)), dim3(256), 0, s, s8, p + P.sh2, s4a, B, Hp, Wp, h, w, D.pt, D.pl);
+    hipLaunchKernelGGL((ak_small_conv_kernel<4, 4, false>), dim3(blocks(f)), dim3(256), 0, s, s4a, p + P.sh4, s4b, B, Hp, Wp, h, w, D.pt, D.pl);
+    hipLaunchKernelGGL((ak_small_conv_kernel<4, 1, true>), dim3(blocks((long long)B * h * w)), dim3(256), 0, s, s4b, p + P.sh6, scores, B, Hp, Wp, h, w, D.pt, D.pl);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
+}
+
+int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity) {
+    if (check_size(batch, h, w) != LG_OK || capacity < 1) return 0;
+    return detect_layout(batch, h, w, capacity).total;
+}
+
+int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th, int32_t top_k,
+                     int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, float* kp_norm,
+                     int32_t* counts, void* hip_stream) {
+    if (int rc = check_size(batch, h, w)) return rc;
+    if (nms_radius < 1 || nms_radius > 8) return set_error(LG_ERR_INVALID, "ALIKED: nms_radius must be in [1, 8]");
+    if (n_limit > 20000 || top_k > 20000) return set_error(LG_ERR_INVALID, "ALIKED: n_limit / top_k above 20000 (ALIKED.n_limit_max)");
+    if (top_k <= 0 && n_limit < 1) return set_error(LG_ERR_INVALID, "ALIKED: threshold mode needs n_limit >= 1");
+    const int K = top_k > 0 ? top_k : n_limit;
+    if (capacity < K) return set_error(LG_ERR_INVALID, "ALIKED: capacity must be at least top_k / n_limit");
+    if (!scores || !workspace || !keypoints || !kp_scores || !kp_norm || !counts) return set_error(LG_ERR_INVALID, "null pointer");
+    const DetectLayout DL = detect_layout(batch, h, w, capacity);
+    if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_detect_workspace_bytes)");
+    char* ws = static_cast<char*>(workspace);
+    AkDetect a{};
+    a.S = scores; a.B = batch; a.H = h; a.W = w; a.r = nms_radius; a.image_size = image_size;
+    a.m0 = reinterpret_cast<unsigned char*>(ws + DL.m0); a.m1 = reinterpret_cast<unsigned char*>(ws + DL.m1); a.supp = reinterpret_cast<unsigned char*>(ws + DL.supp);
+    a.ss = reinterpret_cast<float*>(ws + DL.ss); a.nms = reinterpret_cast<float*>(ws + DL.nms);
+    a.rowcnt = reinterpret_cast<int*>(ws + DL.rowcnt); a.rowsum = reinterpret_cast<double*>(ws + DL.rowsum); a.th = reinterpret_cast<float*>(ws + DL.th);
+    a.cand_idx = reinterpret_cast<int*>(ws + DL.cidx); a.cand_score = reinterpret_cast<float*>(ws + DL.cscore); a.cand_total = reinterpret_cast<int*>(ws + DL.ctotal);
+    a.cap = capacity; a.sel = reinterpret_cast<int*>(ws + DL.sel); a.selkey = reinterpret_cast<unsigned*>(ws + DL.selkey);
+    a.nsel = reinterpret_cast<int*>(ws + DL.nsel); a.sorted = reinterpret_cast<int*>(ws + DL.sorted);
+    a.scores_th = scores_th; a.topk = top_k; a.n_limit = n_limit;
+    a.kpts = keypoints; a.kscores = kp_scores; a.knorm = kp_norm; a.counts = counts;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const long long px = (long long)batch * h * w;
+    // simple_nms (aliked.py:69-91): max mask, then two suppression rounds
+    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 0, (const unsigned char*)nullptr, a.m0);
+    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 1, (const unsigned char*)a.m0, (unsigned char*)nullptr);
+    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 2, (const unsigned char*)a.m0, a.m1);
+    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 1, (const unsigned char*)a.m1, (unsigned char*)nullptr);
+    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 2, (const unsigned char*)a.m1, a.m0);
+    hipLaunchKernelGGL(ak_nms_final_kernel, dim3(blocks(px)), dim3(256), 0, s, a, (const unsigned char*)a.m0);
+    hipLaunchKernelGGL(ak_row_stats_kernel, dim3(h, batch), dim3(256), 0, s, a, (const float*)nullptr);
+    hipLaunchKernelGGL(ak_decide_kernel, dim3(batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ak_row_stats_kernel, dim3(h, batch), dim3(256), 0, s, a, (const float*)a.th);
+    hipLaunchKernelGGL(ak_compact_kernel, dim3(h, batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ak_select_kernel, dim3(batch), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(ak_refine_kernel, dim3(blocks(capacity), batch), dim3(256), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
+}
+
+int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos) {
+    if (check_model(n_pos) != LG_OK || rows < 1) return 0;
+    return describe_layout(rows, n_pos).total;
+}
+
+int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
+                       int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
+    if (int rc = check_model(n_pos)) return rc;
+    if (int rc = check_size(batch, h, w)) return rc;
+    if (n < 1) return LG_OK;
+    if (n > 20000) return set_error(LG_ERR_INVALID, "ALIKED: more than 20000 keypoints per image");
+    if (!levels || !packed || !kp_norm || !counts || !workspace || !descriptors) return set_error(LG_ERR_INVALID, "null pointer");
+    const int rows = batch * n;
+    const DescribeLayout DL = describe_layout(rows, n_pos);
+    if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_describe_workspace_bytes)");
+    const PackLayout P = pack_layout(n_pos);
+    const LevelLayout LL = level_layout(batch, h, w);
+    const Dims D = dims_of(h, w);
+    const float* p = static_cast<const float*>(packed);
+    const char* lv = static_cast<const char*>(levels);
+    char* ws = static_cast<char*>(workspace);
+    AkDescribe d{};
+    for (int l = 0; l < 4; ++l) d.L.x[l] = reinterpret_cast<const float*>(lv + LL.x[l]);
+    d.L.B = batch; d.L.Hp = D.Hp; d.L.Wp = D.Wp;
+    d.H = h; d.W = w; d.pt = D.pt; d.pl = D.pl; d.N = n; d.np = n_pos; d.knorm = kp_norm;
+    d.patch = reinterpret_cast<float*>(ws + DL.patch); d.off1 = reinterpret_cast<float*>(ws + DL.off1); d.spos = reinterpret_cast<float*>(ws + DL.spos);
+    d.feat = reinterpret_cast<float*>(ws + DL.feat); d.sf = reinterpret_cast<float*>(ws + DL.sf); d.draw = reinterpret_cast<float*>(ws + DL.draw);
+    d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = counts; d.out = descriptors;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int rp = DL.rows_pad;
+    hipLaunchKernelGGL(ak_patch_kernel, dim3(rows), dim3(256), 0, s, d);
+    if (rp > rows) (void)hipMemsetAsync(d.patch + (long long)rows * 9 * 128, 0, (size_t)(rp - rows) * 9 * 128 * 4, s);   // GEMM pad rows: keep them finite
+    gemm(d.patch, p + P.so0_w, p + P.so0_b, d.off1, rp, 9 * 128, 2 * n_pos, 1, s);            // offset_conv.0 + SELU
+    hipLaunchKernelGGL(ak_offsets_kernel, dim3(blocks(rows)), dim3(256), 0, s, d, rows);
+    hipLaunchKernelGGL(ak_sample_kernel, dim3(blocks((long long)rows * n_pos, 4)), dim3(256), 0, s, d, rows * n_pos);
+    if (rp > rows) (void)hipMemsetAsync(d.feat + (long long)rows * n_pos * 128, 0, (size_t)(rp - rows) * n_pos * 128 * 4, s);
+    gemm(d.feat, p + P.sf, nullptr, d.sf, rp * n_pos, 128, 128, 1, s);                        // sf_conv + SELU
+    gemm(d.sf, p + P.agg, nullptr, d.draw, rp, n_pos * 128, 128, 0, s);                      // einsum("ncp,pcd->nd")
+    hipLaunchKernelGGL(ak_desc_norm_kernel, dim3(blocks(rows, 4)), dim3(256), 0, s, d, rows);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
+}
+
+}  // extern "C"

@@ -438,6 +438,11 @@ int prof_collect(lg_engine* e) {
 
 }  // namespace
 
+// error hook for the C entry points defined in other files (lg_aliked.hip): the message lg_last_error() returns
+namespace lg {
+int set_error(int code, const char* msg) { g_err = msg; return code; }
+}  // namespace lg
+
 extern "C" {
 
 int32_t lg_profile_num_classes(void) { return LG_PROF_NCLS; }
