@@ -3,11 +3,9 @@
 //
 // Arithmetic is EXACT fp32 (v_mfma_f32_16x16x4_f32 / VALU): DKD thresholds and NMS-compares the scores, so they must agree with an fp32
 // convolution to round-off.  Layouts are NHWC throughout.  The stages:
-//   * convolutions: implicit GEMMs in the scheme of lg_sp_encoder.hip (16-channel chunks, lane (lr, g) supplies pixel / cout lr and the
-//     4 consecutive channels 4g .. 4g + 3, one 16-byte load per fragment, zero padding = clamped address + select), with an output tile
-//     width of 16 / 32 / 64 channels chosen from cout, so the 16-channel block1 layers do not run 48 dead output columns.  BatchNorm
-//     (eval: running statistics) is folded into weights and bias at pack time; the ResBlock's 1 x 1 downsample (with bias) is extra K of
-//     conv2's GEMM, read at the centre pixel of the block input; SELU is the epilogue.
+//   * convolutions: the implicit GEMM SuperPoint's fp32 stack runs (launch_conv, lg_extract.hip), with an output tile width of 16 / 32 / 64
+//     channels chosen from cout.  BatchNorm (eval: running statistics) is folded into weights and bias at pack time (launch_fold); the
+//     ResBlock's 1 x 1 downsample (with bias) is extra K of conv2's GEMM, read at the centre pixel of the block input; SELU is the epilogue.
 //   * block1.conv1 (cin = 3, K = 27) is VALU; it reads the image through clamped addresses, which is InputPadder's replicate padding to a
 //     multiple of 32, and broadcasts a 1-channel image to 3 channels (kornia grayscale_to_rgb).
 //   * deformable convs (blocks 3 and 4, torchvision deform_conv2d without mask): offset conv (3 x 3, bias, 18 channels) on the MFMA path,
@@ -16,121 +14,24 @@
 //     builds the 128 channels of x1234 on the fly (x1 at the pixel, x2 / x3 / x4 upsampled bilinearly, align_corners=True) and applies
 //     score_head.0 + SELU; three small VALU 3 x 3 convs (SELU, SELU, sigmoid) finish, the last one crops the padding.  The full-resolution
 //     128-channel map is never written.
-//   * DKD (aliked.py:94-262, sub_pixel): simple_nms, zeroed borders, threshold (whole-batch mean fallback) / top-k selection, soft-argmax
-//     over the (2r+1)^2 window, bilinear score.
+//   * DKD (aliked.py:94-262, sub_pixel): simple_nms, zeroed borders, threshold and top-k selection on SuperPoint's detection kernels
+//     (lg_extract.hip); here the threshold of each image (whole-batch mean fallback), the soft-argmax over the (2r+1)^2 window and the
+//     bilinear score.
 //   * SDDH (aliked.py:479-609): per keypoint the normalised x1234 vectors at the 3 x 3 patch and at the n_pos sample positions are
 //     recomputed from the level maps; the 3 x 3 offset conv, sf_conv and the agg_weights contraction are MFMA GEMMs over all keypoints.
 #include <string>
 
-#include "lg_kernels.h"
+#include "lg_extract.h"
 #include "../../include/lightglue_amd.h"
-
-namespace lg {
-int set_error(int code, const char* msg);   // lg_engine.hip: the message lg_last_error() returns
-}
 
 namespace lg {
 namespace {
 
-constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.0507009873554804934193349852946f;
-__device__ __forceinline__ float selu(float x) { return SELU_SCALE * (x > 0.f ? x : SELU_ALPHA * expm1f(x)); }
-
 // ==================================================================================================== convolutions (MFMA)
-struct AkConv {
-    const float* in; const float* w; const float* bias;   // w: [taps][Cout][Cin]; bias may be null
-    const float* in2; const float* w2;                    // optional extra K at the centre pixel: in2 [pixel][Cin2], w2 [Cout][Cin2]
-    float* out;
-    int B, H, W, Cin, Cin2, Cout, taps, act;              // taps 9 (3 x 3, zero pad 1) or 1; act 1 = SELU
-};
-
-// acc[mt][nt] += the wave's 2 rows x 32 pixels x 16 NT channels of one operand pair
-template <int NT>
-__device__ __forceinline__ void ak_accum(f32x4 (&acc)[4][NT], const float* inb, const float* wt, int H, int W, int Cin, int Cout, int taps,
-                                         int n0, int x0, int y0, int lr, int g) {
-    const int nchunk = Cin >> 4;
-    for (int tap = 0; tap < taps; ++tap) {
-        const int dy = taps == 9 ? tap / 3 - 1 : 0, dx = taps == 9 ? tap % 3 - 1 : 0;
-        long long poff[4]; bool ok[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const int yy = y0 + (mt >> 1) + dy, xx = x0 + (mt & 1) * 16 + lr + dx;
-            ok[mt] = yy >= 0 && yy < H && xx >= 0 && xx < W;
-            const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
-            poff[mt] = ((long long)yc * W + xc) * Cin + 4 * g;
-        }
-        long long wrow[NT]; bool live[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int co = n0 + nt * 16 + lr;
-            live[nt] = co < Cout;
-            wrow[nt] = ((long long)tap * Cout + min(co, Cout - 1)) * Cin + 4 * g;
-        }
-        for (int c = 0; c < nchunk; ++c) {
-            u32x4 af[4], bf[NT];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(inb + poff[mt] + c * 16);
-                af[mt] = ok[mt] ? v : u32x4{0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(wt + wrow[nt] + c * 16);
-                bf[nt] = live[nt] ? v : u32x4{0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) mma_chunk<TagF32>(acc[mt][nt], af[mt], bf[nt]);
-        }
-    }
-}
-
-// wave = 2 rows x 32 pixels x 16 NT output channels, workgroup = 4 waves = 8 rows.  grid (W / 32, H / 8, B * cout groups)
-template <int NT>
-__global__ __launch_bounds__(256) void ak_conv_kernel(AkConv a) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
-    constexpr int NW = 16 * NT;
-    const int ngroups = (a.Cout + NW - 1) / NW;
-    const int b = blockIdx.z / ngroups, n0 = (blockIdx.z - b * ngroups) * NW;
-    const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 8 + wv * 2;
-    if (y0 >= a.H) return;
-    f32x4 acc[4][NT];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const long long img = (long long)b * a.H * a.W;
-    ak_accum<NT>(acc, a.in + img * a.Cin, a.w, a.H, a.W, a.Cin, a.Cout, a.taps, n0, x0, y0, lr, g);
-    if (a.in2) ak_accum<NT>(acc, a.in2 + img * a.Cin2, a.w2, a.H, a.W, a.Cin2, a.Cout, 1, n0, x0, y0, lr, g);
-    // acc[mt][nt][r] = out[pixel (y0 + mt / 2, x0 + (mt & 1) * 16 + 4g + r)][cout n0 + nt * 16 + lr]
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = n0 + nt * 16 + lr;
-        if (co >= a.Cout) continue;
-        const float bv = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const int y = y0 + (mt >> 1), xb = x0 + (mt & 1) * 16 + 4 * g;
-            if (y >= a.H) continue;
-            float* o = a.out + (img + (long long)y * a.W + xb) * a.Cout + co;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (xb + r >= a.W) continue;
-                const float v = acc[mt][nt][r] + bv;
-                o[(long long)r * a.Cout] = a.act ? selu(v) : v;
-            }
-        }
-    }
-}
-
-void conv(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout, int taps, int act, hipStream_t s,
+// act_selu: SELU epilogue; in2 / w2 / Cin2: extra K at the centre pixel
+void conv(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout, int taps, int act_selu, hipStream_t s,
           const float* in2 = nullptr, const float* w2 = nullptr, int Cin2 = 0) {
-    AkConv a{in, w, bias, in2, w2, out, B, H, W, Cin, Cin2, Cout, taps, act};
-    const int NT = Cout <= 16 ? 1 : (Cout <= 32 ? 2 : 4);
-    const dim3 grid((W + 31) / 32, (H + 7) / 8, B * ((Cout + 16 * NT - 1) / (16 * NT)));
-    if (NT == 1) hipLaunchKernelGGL(ak_conv_kernel<1>, grid, dim3(256), 0, s, a);
-    else if (NT == 2) hipLaunchKernelGGL(ak_conv_kernel<2>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(ak_conv_kernel<4>, grid, dim3(256), 0, s, a);
+    launch_conv(ConvArgs{in, w, bias, in2, w2, out, B, H, W, Cin, Cin2, Cout, taps, act_selu ? ACT_SELU : ACT_NONE, 0, 0}, s);
 }
 
 // a [rows][K] x [Cout][K] GEMM as a 1 x 1 convolution over a 32-pixel-wide "image" (rows % 32 == 0)
@@ -295,252 +196,45 @@ __global__ __launch_bounds__(256) void ak_small_conv_kernel(const float* in, con
     }
 }
 
-// ==================================================================================================== weight packing
-enum : int { PK_TAP_CO_CI = 0, PK_CO_TAP_CI = 1, PK_TAP_CI_CO = 2, PK_COPY = 3, PK_AGG = 4 };
-// dst weight = s[co] * src (layout by mode), s = gamma / sqrt(var + eps) with BN, else 1; bias_dst[co] = s (cbias - mean) + beta (+ extra)
-__global__ __launch_bounds__(256) void ak_fold_kernel(const float* src, float* dst, float* bias_dst, int Cout, int Cin, int kk, int mode, const float* gamma,
-                                                      const float* beta, const float* mean, const float* var, const float* cbias, const float* extra) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)Cout * Cin * kk;
-    if (i >= total) return;
-    int co, ci, t;
-    if (mode == PK_AGG) {    // src [n_pos][128][128] = (p, c, d) -> dst [d][p * 128 + c]; Cin = n_pos * 128
-        co = (int)(i % Cout); ci = (int)(i / Cout); t = 0;
-    } else {
-        t = (int)(i % kk); ci = (int)((i / kk) % Cin); co = (int)(i / ((long long)kk * Cin));
-    }
-    const float s = gamma ? gamma[co] / sqrtf(var[co] + 1e-5f) : 1.f;
-    const float v = s * src[i];
-    long long o;
-    switch (mode) {
-        case PK_TAP_CO_CI: o = ((long long)t * Cout + co) * Cin + ci; break;
-        case PK_CO_TAP_CI: o = ((long long)co * kk + t) * Cin + ci; break;
-        case PK_TAP_CI_CO: o = ((long long)t * Cin + ci) * Cout + co; break;
-        case PK_AGG: o = (long long)co * Cin + ci; break;
-        default: o = i;
-    }
-    dst[o] = v;
-    if (bias_dst && ci == 0 && t == 0) {
-        float bv = cbias ? cbias[co] : 0.f;
-        if (gamma) bv = s * (bv - mean[co]) + beta[co];
-        if (extra) bv += extra[co];
-        bias_dst[co] = bv;
-    }
-}
-
 // ==================================================================================================== DKD
-struct AkDetect {
-    const float* S;            // [B][H][W] scores
-    int B, H, W, r;
-    const float* image_size;   // [B][2] (w, h) or null
-    unsigned char *m0, *m1, *supp; float* ss; float* nms;
-    int* rowcnt; double* rowsum; float* th;
-    int* cand_idx; float* cand_score; int* cand_total;
-    int cap; int* sel; unsigned* selkey; int* nsel; int* sorted;
-    float scores_th; int topk; int n_limit;
-    float* kpts; float* kscores; float* knorm; int* counts;
-};
-
-// mode 0: m_out = S == maxpool(S); 1: supp = maxpool(m_in) > 0, ss = supp ? 0 : S; 2: m_out = m_in | (ss == maxpool(ss) & ~supp)
-__global__ __launch_bounds__(256) void ak_nms_kernel(AkDetect a, int mode, const unsigned char* m_in, unsigned char* m_out) {
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= (long long)a.B * a.H * a.W) return;
-    const int x = (int)(p % a.W), y = (int)((p / a.W) % a.H);
-    const long long base = p - ((long long)y * a.W + x);
-    const int r = a.r;
-    if (mode == 0 || mode == 2) {
-        const float* src = mode == 0 ? a.S : a.ss;
-        float m = -INFINITY;
-        for (int dy = -r; dy <= r; ++dy)
-            for (int dx = -r; dx <= r; ++dx) {
-                const int yy = y + dy, xx = x + dx;
-                if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) m = fmaxf(m, src[base + (long long)yy * a.W + xx]);
-            }
-        if (mode == 0) m_out[p] = a.S[p] == m;
-        else m_out[p] = m_in[p] || (a.ss[p] == m && !a.supp[p]);
-    } else {
-        unsigned char v = 0;
-        for (int dy = -r; dy <= r; ++dy)
-            for (int dx = -r; dx <= r; ++dx) {
-                const int yy = y + dy, xx = x + dx;
-                if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) v |= m_in[base + (long long)yy * a.W + xx];
-            }
-        a.supp[p] = v;
-        a.ss[p] = v ? 0.f : a.S[p];
-    }
-}
-
-// nms = mask ? S : 0, borders of r pixels set to 0 (the far ones from image_size when given)
-__global__ __launch_bounds__(256) void ak_nms_final_kernel(AkDetect a, const unsigned char* mask) {
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= (long long)a.B * a.H * a.W) return;
-    const int x = (int)(p % a.W), y = (int)((p / a.W) % a.H), b = (int)(p / ((long long)a.W * a.H));
-    int hl = a.H, wl = a.W;
-    if (a.image_size) { wl = (int)a.image_size[2 * b]; hl = (int)a.image_size[2 * b + 1]; }   // .long(): truncation
-    const bool border = y < a.r || x < a.r || y >= hl - a.r || x >= wl - a.r;
-    a.nms[p] = (mask[p] && !border) ? a.S[p] : 0.f;
-}
-
-__device__ __forceinline__ int block_sum_int(int v, int* sh) {   // 256 threads
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// per row: number of nms > threshold (th[b] when `th` is set, else scores_th) and the row sum of S (for the mean).  grid (H, B)
-__global__ __launch_bounds__(256) void ak_row_stats_kernel(AkDetect a, const float* th) {
-    const int y = blockIdx.x, b = blockIdx.y;
-    const long long row = ((long long)b * a.H + y) * a.W;
-    const float t = th ? th[b] : a.scores_th;
-    int cnt = 0; double sum = 0.0;
-    for (int x = threadIdx.x; x < a.W; x += 256) { cnt += a.nms[row + x] > t; sum += (double)a.S[row + x]; }
-    __shared__ int sh[4];
-    __shared__ double shd[256];
-    cnt = block_sum_int(cnt, sh);
-    shd[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) shd[threadIdx.x] += shd[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) { a.rowcnt[b * a.H + y] = cnt; if (!th) a.rowsum[b * a.H + y] = shd[0]; }
-}
-
 // the threshold of each image (aliked.py:183-193): top-k mode: > 0 (the positive NMS maxima are the candidates); threshold mode: scores_th,
-// unless no pixel of the WHOLE batch passes it (or scores_th <= 0): the image's mean score.  grid (B), 256 threads
-__global__ __launch_bounds__(256) void ak_decide_kernel(AkDetect a) {
+// unless no pixel of the WHOLE batch passes it (or scores_th <= 0): the image's mean score.  Row counts of a.threshold = scores_th.  grid (B), 256 threads
+__global__ __launch_bounds__(256) void ak_decide_kernel(DetectArgs a, int topk, const double* rowsum, float* th) {
     const int b = blockIdx.x;
     __shared__ int sh[4];
     __shared__ double shd[256];
     int any = 0;
-    for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.rowcnt[i];
+    for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.row_counts[i];
     any = block_sum_int(any, sh);
     double s = 0.0;
-    for (int y = threadIdx.x; y < a.H; y += 256) s += a.rowsum[b * a.H + y];
+    for (int y = threadIdx.x; y < a.H; y += 256) s += rowsum[b * a.H + y];
     shd[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) shd[threadIdx.x] += shd[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) {
         const float mean = (float)(shd[0] / ((double)a.H * a.W));
-        a.th[b] = a.topk > 0 ? 0.f : ((a.scores_th > 0.f && any > 0) ? a.scores_th : mean);
+        th[b] = topk > 0 ? 0.f : ((a.threshold > 0.f && any > 0) ? a.threshold : mean);
     }
 }
 
-// raster-order compaction (the order of nonzero()): grid (H, B)
-__global__ __launch_bounds__(256) void ak_compact_kernel(AkDetect a) {
-    const int y = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float t = a.th[b];
-    __shared__ int sh[4];
-    int pre = 0;
-    for (int yy = tid; yy < y; yy += 256) pre += a.rowcnt[b * a.H + yy];
-    int running = block_sum_int(pre, sh);
-    const long long row = ((long long)b * a.H + y) * a.W;
-    const long long cbase = (long long)b * a.H * a.W;
-    for (int x0 = 0; x0 < a.W; x0 += 256) {
-        const int x = x0 + tid;
-        const float v = x < a.W ? a.nms[row + x] : 0.f;
-        const bool hit = x < a.W && v > t;
-        const unsigned long long bal = __ballot(hit);
-        __syncthreads();
-        if (lane == 0) sh[wave] = __popcll(bal);
-        __syncthreads();
-        int off = running;
-        for (int w = 0; w < wave; ++w) off += sh[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        if (hit) { a.cand_idx[cbase + off] = y * a.W + x; a.cand_score[cbase + off] = a.S[row + x]; }
-        running += sh[0] + sh[1] + sh[2] + sh[3];
-    }
-    if (y == a.H - 1 && tid == 0) a.cand_total[b] = running;
-}
+struct AkKeypoints { float* kpts; float* kscores; float* knorm; int* counts; };   // [B][cap][2], [B][cap], [B][cap][2], [B]; cap = a.sel_cap
 
-__device__ __forceinline__ unsigned fkey(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-
-// per image: the candidates that survive the limit, in raster order (sel), with their keys; sorted[b] = the output is ordered by score
-// (top-k mode, or more candidates than n_limit).  Radix select of the K-th largest key as in lg_superpoint.hip.  grid (B), 1024 threads
-__global__ __launch_bounds__(1024) void ak_select_kernel(AkDetect a) {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int total = a.cand_total[b];
-    const float* csc = a.cand_score + (long long)b * a.H * a.W;
-    int* sel = a.sel + (long long)b * a.cap;
-    unsigned* skey = a.selkey + (long long)b * a.cap;
-    const int K = a.topk > 0 ? a.topk : a.n_limit;
-    const bool limit = total > K;
-    __shared__ unsigned hist[256];
-    __shared__ unsigned prefix_sh, need_sh;
-    __shared__ int wsum[16];
-    unsigned prefix = 0, need = 0xFFFFFFFFu;
-    if (limit) {
-        need = (unsigned)K;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const unsigned fixed_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-            for (int i = tid; i < total; i += 1024) {
-                const unsigned k = fkey(csc[i]);
-                if ((k & fixed_mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned acc = 0; int d = 255;
-                for (; d > 0; --d) { if (acc + hist[d] >= need) break; acc += hist[d]; }
-                prefix_sh = prefix | ((unsigned)d << shift); need_sh = need - acc;
-            }
-            __syncthreads();
-            prefix = prefix_sh; need = need_sh;
-            __syncthreads();
-        }
-    }
-    // keep key > prefix, and the first `need` keys == prefix in raster order (everything when not limited)
-    int taken = 0, eq_taken = 0;
-    for (int i0 = 0; i0 < total; i0 += 1024) {
-        const int i = i0 + tid;
-        const unsigned k = i < total ? fkey(csc[i]) : 0u;
-        const bool eq = limit && i < total && k == prefix;
-        const unsigned long long beq = __ballot(eq);
-        __syncthreads();
-        if (lane == 0) wsum[wave] = __popcll(beq);
-        __syncthreads();
-        int eoff = eq_taken;
-        for (int w = 0; w < wave; ++w) eoff += wsum[w];
-        eoff += __popcll(beq & ((1ull << lane) - 1ull));
-        int eall = 0;
-        for (int w = 0; w < 16; ++w) eall += wsum[w];
-        const bool keep = i < total && (!limit || k > prefix || (eq && eoff < (int)need));
-        const unsigned long long bk = __ballot(keep);
-        __syncthreads();
-        if (lane == 0) wsum[wave] = __popcll(bk);
-        __syncthreads();
-        int off = taken;
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        off += __popcll(bk & ((1ull << lane) - 1ull));
-        if (keep && off < a.cap) { sel[off] = i; skey[off] = k; }
-        int all = 0;
-        for (int w = 0; w < 16; ++w) all += wsum[w];
-        taken += all; eq_taken += eall;
-    }
-    if (tid == 0) { a.nsel[b] = min(taken, a.cap); a.sorted[b] = (a.topk > 0 || limit) ? 1 : 0; }
-}
-
-// per output slot: rank (score descending, raster order among equals, when sorted), soft-argmax refinement and the bilinear score
-// (aliked.py:212-247).  Rows >= the image's count are zero-filled.  grid (cap / 256, B)
-__global__ __launch_bounds__(256) void ak_refine_kernel(AkDetect a) {
+// per output slot: rank (selected_rank when sorted), soft-argmax refinement and the bilinear score (aliked.py:212-247).  Rows >= the image's
+// count are zero-filled.  grid (cap / 256, B)
+__global__ __launch_bounds__(256) void ak_refine_kernel(DetectArgs a, AkKeypoints k) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= a.cap) return;
-    const int n = a.nsel[b];
-    const long long ob = (long long)b * a.cap;
-    if (j == 0) a.counts[b] = n;
+    const int n = selected_count(a, b);
+    const long long ob = (long long)b * a.sel_cap;
+    const int rank = selection_sorted(a, b) && (int)blockIdx.x * 256 < n ? selected_rank(a.sel_key + ob, n, j) : j;   // (block-uniform)
+    if (j >= a.sel_cap) return;
+    if (j == 0) k.counts[b] = n;
     if (j >= n) {   // padding rows (written by their own slot j: ranks are a permutation of [0, n))
-        a.kpts[2 * (ob + j)] = 0.f; a.kpts[2 * (ob + j) + 1] = 0.f; a.kscores[ob + j] = 0.f;
-        a.knorm[2 * (ob + j)] = 0.f; a.knorm[2 * (ob + j) + 1] = 0.f;
+        k.kpts[2 * (ob + j)] = 0.f; k.kpts[2 * (ob + j) + 1] = 0.f; k.kscores[ob + j] = 0.f;
+        k.knorm[2 * (ob + j)] = 0.f; k.knorm[2 * (ob + j) + 1] = 0.f;
         return;
     }
-    const unsigned* skey = a.selkey + ob;
-    int rank = j;
-    if (a.sorted[b]) {
-        const unsigned k = skey[j];
-        rank = 0;
-        for (int i = 0; i < n; ++i) { const unsigned q = skey[i]; rank += (q > k) || (q == k && i < j); }
-    }
-    const int p = a.cand_idx[(long long)b * a.H * a.W + a.sel[ob + j]];
-    const int y = p / a.W, x = p - y * a.W, r = a.r;
+    const int p = a.cand_idx[(long long)b * a.max_candidates + a.sel[ob + j]];
+    const int y = p / a.W, x = p - y * a.W, r = a.radius;
     const float* S = a.S + (long long)b * a.H * a.W;
     auto sv = [&](int yy, int xx) { return (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? S[(long long)yy * a.W + xx] : 0.f; };   // unfold: zero padding
     float mx = -INFINITY;
@@ -565,10 +259,10 @@ __global__ __launch_bounds__(256) void ak_refine_kernel(AkDetect a) {
     const float score = sv(y0, x0) * ((ex - ix) * (ey - iy)) + sv(y0, x0 + 1) * ((ix - fx) * (ey - iy)) + sv(y0 + 1, x0) * ((ex - ix) * (iy - fy)) +
                         sv(y0 + 1, x0 + 1) * ((ix - fx) * (iy - fy));
     const long long o = ob + rank;
-    a.kpts[2 * o] = __fdiv_rn(__fmul_rn(wm1, __fadd_rn(kx, 1.f)), 2.f);       // wh * (k + 1) / 2 (aliked.py:756)
-    a.kpts[2 * o + 1] = __fdiv_rn(__fmul_rn(hm1, __fadd_rn(ky, 1.f)), 2.f);
-    a.kscores[o] = score;
-    a.knorm[2 * o] = kx; a.knorm[2 * o + 1] = ky;
+    k.kpts[2 * o] = __fdiv_rn(__fmul_rn(wm1, __fadd_rn(kx, 1.f)), 2.f);       // wh * (k + 1) / 2 (aliked.py:756)
+    k.kpts[2 * o + 1] = __fdiv_rn(__fmul_rn(hm1, __fadd_rn(ky, 1.f)), 2.f);
+    k.kscores[o] = score;
+    k.knorm[2 * o] = kx; k.knorm[2 * o + 1] = ky;
 }
 
 // ==================================================================================================== SDDH
@@ -675,11 +369,6 @@ __global__ __launch_bounds__(256) void ak_desc_norm_kernel(AkDescribe d, int row
 }
 
 // ==================================================================================================== host-side layouts
-struct Bump {
-    long long used = 0;
-    long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
-};
-
 // packed weights (float offsets)
 struct PackLayout {
     long long b1c1_w, b1c1_b, b1c2_w, b1c2_b;
@@ -737,18 +426,6 @@ EncodeLayout encode_layout(int B, int h, int w) {
     return E;
 }
 
-struct DetectLayout { long long m0, m1, supp, ss, nms, rowcnt, rowsum, th, cidx, cscore, ctotal, sel, selkey, nsel, sorted; long long total; };
-DetectLayout detect_layout(int B, int h, int w, int cap) {
-    const long long px = (long long)B * h * w;
-    Bump bp; DetectLayout L{};
-    L.m0 = bp.take(px); L.m1 = bp.take(px); L.supp = bp.take(px); L.ss = bp.take(px * 4); L.nms = bp.take(px * 4);
-    L.rowcnt = bp.take((long long)B * h * 4); L.rowsum = bp.take((long long)B * h * 8); L.th = bp.take(B * 4);
-    L.cidx = bp.take(px * 4); L.cscore = bp.take(px * 4); L.ctotal = bp.take(B * 4);
-    L.sel = bp.take((long long)B * cap * 4); L.selkey = bp.take((long long)B * cap * 4); L.nsel = bp.take(B * 4); L.sorted = bp.take(B * 4);
-    L.total = bp.used;
-    return L;
-}
-
 struct DescribeLayout { long long patch, off1, spos, feat, sf, draw; long long total; int rows_pad; };
 DescribeLayout describe_layout(int rows, int np) {
     const int rp = (rows + 31) / 32 * 32;
@@ -760,16 +437,12 @@ DescribeLayout describe_layout(int rows, int np) {
     return L;
 }
 
-inline unsigned blocks(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 constexpr int kTensors = 68;
 constexpr long long kMaxPixels = 1LL << 25;
 
 int fold(const float* src, float* dst, float* bias_dst, int cout, int cin, int kk, int mode, const float* const* bn, const float* cbias, const float* extra,
          hipStream_t s) {
-    const long long total = (long long)cout * cin * kk;
-    hipLaunchKernelGGL(ak_fold_kernel, dim3(blocks(total)), dim3(256), 0, s, src, dst, bias_dst, cout, cin, kk, mode, bn ? bn[0] : nullptr, bn ? bn[1] : nullptr,
-                       bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, cbias, extra);
-    return hipGetLastError() == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, "ALIKED weight packing launch failed");
+    return launch_fold(src, dst, bias_dst, cout, cin, kk, mode, bn, cbias, extra, s) == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, "ALIKED weight packing launch failed");
 }
 
 int check_model(int np) { return (np == 16 || np == 32) ? LG_OK : set_error(LG_ERR_INVALID, "unknown ALIKED model: n_pos must be 16 (aliked-n16, -n16rot) or 32 (aliked-n32)"); }
@@ -897,7 +570,7 @@ int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_
 
 int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity) {
     if (check_size(batch, h, w) != LG_OK || capacity < 1) return 0;
-    return detect_layout(batch, h, w, capacity).total;
+    return detect_layout(batch, h, w, h * w, capacity, true).total;
 }
 
 int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th, int32_t top_k,
@@ -910,34 +583,23 @@ int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, c
     const int K = top_k > 0 ? top_k : n_limit;
     if (capacity < K) return set_error(LG_ERR_INVALID, "ALIKED: capacity must be at least top_k / n_limit");
     if (!scores || !workspace || !keypoints || !kp_scores || !kp_norm || !counts) return set_error(LG_ERR_INVALID, "null pointer");
-    const DetectLayout DL = detect_layout(batch, h, w, capacity);
+    const DetectLayout DL = detect_layout(batch, h, w, h * w, capacity, true);
     if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_detect_workspace_bytes)");
-    char* ws = static_cast<char*>(workspace);
-    AkDetect a{};
-    a.S = scores; a.B = batch; a.H = h; a.W = w; a.r = nms_radius; a.image_size = image_size;
-    a.m0 = reinterpret_cast<unsigned char*>(ws + DL.m0); a.m1 = reinterpret_cast<unsigned char*>(ws + DL.m1); a.supp = reinterpret_cast<unsigned char*>(ws + DL.supp);
-    a.ss = reinterpret_cast<float*>(ws + DL.ss); a.nms = reinterpret_cast<float*>(ws + DL.nms);
-    a.rowcnt = reinterpret_cast<int*>(ws + DL.rowcnt); a.rowsum = reinterpret_cast<double*>(ws + DL.rowsum); a.th = reinterpret_cast<float*>(ws + DL.th);
-    a.cand_idx = reinterpret_cast<int*>(ws + DL.cidx); a.cand_score = reinterpret_cast<float*>(ws + DL.cscore); a.cand_total = reinterpret_cast<int*>(ws + DL.ctotal);
-    a.cap = capacity; a.sel = reinterpret_cast<int*>(ws + DL.sel); a.selkey = reinterpret_cast<unsigned*>(ws + DL.selkey);
-    a.nsel = reinterpret_cast<int*>(ws + DL.nsel); a.sorted = reinterpret_cast<int*>(ws + DL.sorted);
-    a.scores_th = scores_th; a.topk = top_k; a.n_limit = n_limit;
-    a.kpts = keypoints; a.kscores = kp_scores; a.knorm = kp_norm; a.counts = counts;
+    DetectArgs a{};
+    detect_bind(a, DL, workspace);
+    a.S = scores; a.B = batch; a.H = h; a.W = w; a.radius = nms_radius;
+    a.border = nms_radius; a.image_size = image_size; a.border_value = 0.f; a.threshold = scores_th;
+    a.max_candidates = h * w; a.K = K; a.sort_always = top_k > 0; a.sel_cap = capacity;
+    double* rowsum = reinterpret_cast<double*>(static_cast<char*>(workspace) + DL.rowsum);
+    float* th = reinterpret_cast<float*>(static_cast<char*>(workspace) + DL.th);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const long long px = (long long)batch * h * w;
-    // simple_nms (aliked.py:69-91): max mask, then two suppression rounds
-    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 0, (const unsigned char*)nullptr, a.m0);
-    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 1, (const unsigned char*)a.m0, (unsigned char*)nullptr);
-    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 2, (const unsigned char*)a.m0, a.m1);
-    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 1, (const unsigned char*)a.m1, (unsigned char*)nullptr);
-    hipLaunchKernelGGL(ak_nms_kernel, dim3(blocks(px)), dim3(256), 0, s, a, 2, (const unsigned char*)a.m1, a.m0);
-    hipLaunchKernelGGL(ak_nms_final_kernel, dim3(blocks(px)), dim3(256), 0, s, a, (const unsigned char*)a.m0);
-    hipLaunchKernelGGL(ak_row_stats_kernel, dim3(h, batch), dim3(256), 0, s, a, (const float*)nullptr);
-    hipLaunchKernelGGL(ak_decide_kernel, dim3(batch), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ak_row_stats_kernel, dim3(h, batch), dim3(256), 0, s, a, (const float*)a.th);
-    hipLaunchKernelGGL(ak_compact_kernel, dim3(h, batch), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ak_select_kernel, dim3(batch), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(ak_refine_kernel, dim3(blocks(capacity), batch), dim3(256), 0, s, a);
+    launch_nms(a, s);                               // simple_nms (aliked.py:69-91)
+    launch_row_count(a, nullptr, rowsum, s);        // against scores_th, and the row sums for the mean
+    hipLaunchKernelGGL(ak_decide_kernel, dim3(batch), dim3(256), 0, s, a, top_k, (const double*)rowsum, th);
+    launch_row_count(a, th, nullptr, s);
+    launch_compact(a, th, s);
+    launch_select(a, s);
+    hipLaunchKernelGGL(ak_refine_kernel, dim3(blocks(capacity), batch), dim3(256), 0, s, a, AkKeypoints{keypoints, kp_scores, kp_norm, counts});
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
 }

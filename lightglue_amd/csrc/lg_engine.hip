@@ -25,13 +25,6 @@ static const char* const kProfNames[LG_PROF_NCLS] = {"prep", "gemm_qkv_self", "a
 namespace {
 
 thread_local std::string g_err = "";
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return fail(LG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
-    } while (0)
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -401,7 +394,7 @@ int ensure_workspace(lg_engine* e, int B, int n0, int n1) {
     e->X2 = (float*)take("X2", R * 256 * 4); e->COS2 = (float*)take("COS2", R * 32 * 4); e->SIN2 = (float*)take("SIN2", R * 32 * 4);
     e->CFLAGS = (int*)take("CFLAGS", (size_t)2 * B * ((c0 > c1 ? c0 : c1) / compact_chunk_rows()) * 4 + 256); e->cflags_clean = false;
     e->TAILDBG = (long long*)take("TAILDBG", R * 16); e->TAILDBG2 = (long long*)take("TAILDBG2", R * 16);
-    if (ar.used > e->ws_bytes) return fail(LG_ERR_STATE, "workspace carve overflow");
+    if (ar.used > e->ws_bytes) return set_error(LG_ERR_STATE, "workspace carve overflow");
     return LG_OK;
 }
 
@@ -438,9 +431,8 @@ int prof_collect(lg_engine* e) {
 
 }  // namespace
 
-// error hook for the C entry points defined in other files (lg_aliked.hip): the message lg_last_error() returns
 namespace lg {
-int set_error(int code, const char* msg) { g_err = msg; return code; }
+int set_error(int code, const std::string& msg) { g_err = msg; return code; }
 }  // namespace lg
 
 extern "C" {
@@ -448,13 +440,13 @@ extern "C" {
 int32_t lg_profile_num_classes(void) { return LG_PROF_NCLS; }
 const char* lg_profile_class_name(int32_t cls) { return (cls >= 0 && cls < LG_PROF_NCLS) ? kProfNames[cls] : ""; }
 int lg_engine_profile_enable(lg_engine* e, int32_t on) {
-    if (!e) return fail(LG_ERR_INVALID, "null engine");
+    if (!e) return set_error(LG_ERR_INVALID, "null engine");
     if (!on && e->profiling) { int rc = prof_collect(e); if (rc != LG_OK) return rc; }
     e->profiling = on != 0;
     return LG_OK;
 }
 int lg_engine_profile_read(lg_engine* e, double* ms, int64_t* count, int32_t n) {
-    if (!e || !ms || !count || n < LG_PROF_NCLS) return fail(LG_ERR_INVALID, "bad argument");
+    if (!e || !ms || !count || n < LG_PROF_NCLS) return set_error(LG_ERR_INVALID, "bad argument");
     int rc = prof_collect(e);
     if (rc != LG_OK) return rc;
     for (int i = 0; i < LG_PROF_NCLS; ++i) { ms[i] = e->prof_ms[i]; count[i] = e->prof_cnt[i]; e->prof_ms[i] = 0; e->prof_cnt[i] = 0; }
@@ -465,17 +457,17 @@ const char* lg_last_error(void) { return g_err.c_str(); }
 const char* lg_version(void) { return "lightglue_amd 0.4 (gfx950)"; }
 
 int lg_engine_create(const lg_config* cfg, lg_engine** out) {
-    if (!cfg || !out) return fail(LG_ERR_INVALID, "null argument");
-    if (cfg->descriptor_dim != 256 || cfg->num_heads != 4) return fail(LG_ERR_INVALID, "only descriptor_dim=256, num_heads=4 (head_dim 64) are built");
-    if (cfg->n_layers < 1 || cfg->n_layers > 64) return fail(LG_ERR_INVALID, "bad n_layers");
-    if (cfg->input_dim <= 0 || cfg->input_dim % 64) return fail(LG_ERR_INVALID, "input_dim must be a positive multiple of 64");
-    if (cfg->precision != LG_PREC_F32 && cfg->precision != LG_PREC_BF16 && cfg->precision != LG_PREC_F16 && cfg->precision != LG_PREC_F16X3) return fail(LG_ERR_INVALID, "bad precision");
+    if (!cfg || !out) return set_error(LG_ERR_INVALID, "null argument");
+    if (cfg->descriptor_dim != 256 || cfg->num_heads != 4) return set_error(LG_ERR_INVALID, "only descriptor_dim=256, num_heads=4 (head_dim 64) are built");
+    if (cfg->n_layers < 1 || cfg->n_layers > 64) return set_error(LG_ERR_INVALID, "bad n_layers");
+    if (cfg->input_dim <= 0 || cfg->input_dim % 64) return set_error(LG_ERR_INVALID, "input_dim must be a positive multiple of 64");
+    if (cfg->precision != LG_PREC_F32 && cfg->precision != LG_PREC_BF16 && cfg->precision != LG_PREC_F16 && cfg->precision != LG_PREC_F16X3) return set_error(LG_ERR_INVALID, "bad precision");
     auto* e = new lg_engine();
     e->cfg = *cfg;
     int ap = cfg->attn_precision;
     if (ap < 0) ap = cfg->precision;   // f16x3 -> split attention; every other precision -> its own element type
     // pairs with a q/k/v projection kernel (lg_proj.hip): a precision with itself, or f16x3 with one f16 plane (the fast opt-in)
-    if (!(ap == cfg->precision || (cfg->precision == PREC_F16X3 && ap == PREC_F16))) { delete e; return fail(LG_ERR_INVALID, "bad attn_precision: must equal `precision`, or LG_PREC_F16 with LG_PREC_F16X3"); }
+    if (!(ap == cfg->precision || (cfg->precision == PREC_F16X3 && ap == PREC_F16))) { delete e; return set_error(LG_ERR_INVALID, "bad attn_precision: must equal `precision`, or LG_PREC_F16 with LG_PREC_F16X3"); }
     e->attn_prec = ap;
     *out = e;
     return LG_OK;
@@ -490,7 +482,7 @@ void lg_engine_destroy(lg_engine* e) {
 }
 
 int lg_engine_set_weight(lg_engine* e, const char* name, const float* host_data, const int64_t* shape, int32_t ndim) {
-    if (!e || !name || !host_data || ndim < 0 || ndim > 4) return fail(LG_ERR_INVALID, "bad argument");
+    if (!e || !name || !host_data || ndim < 0 || ndim > 4) return set_error(LG_ERR_INVALID, "bad argument");
     HostTensor t;
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
@@ -501,7 +493,7 @@ int lg_engine_set_weight(lg_engine* e, const char* name, const float* host_data,
 }
 
 int lg_engine_finalize_weights(lg_engine* e) {
-    if (!e) return fail(LG_ERR_INVALID, "null engine");
+    if (!e) return set_error(LG_ERR_INVALID, "null engine");
     const int L = e->cfg.n_layers, D = 256, Din = e->cfg.input_dim, prec = e->cfg.precision;
     const int pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
     const size_t es = elem_size(prec);
@@ -546,11 +538,11 @@ int lg_engine_finalize_weights(lg_engine* e) {
     e->sqkv_layer_bytes = sqkv_layer; e->cqkv_layer_bytes = cqkv_layer;
     e->w_sqkv_p = static_cast<char*>(ar.take(L * sqkv_layer)); e->w_cqkv_p = static_cast<char*>(ar.take(L * cqkv_layer));
     e->final_layer_bytes = final_layer; e->w_final_p = static_cast<char*>(ar.take(L * final_layer));
-    if (ar.used > total) return fail(LG_ERR_STATE, "weight arena carve overflow");
+    if (ar.used > total) return set_error(LG_ERR_STATE, "weight arena carve overflow");
 
     std::string err;
     auto up_f32 = [&](float* dst, const float* src, size_t n) -> int { HIPCHK(hipMemcpy(dst, src, n * 4, hipMemcpyHostToDevice)); return LG_OK; };
-#define NEED(var, name, ...) const HostTensor* var = find(e, name, {__VA_ARGS__}, err); if (!var) return fail(LG_ERR_INVALID, err)
+#define NEED(var, name, ...) const HostTensor* var = find(e, name, {__VA_ARGS__}, err); if (!var) return set_error(LG_ERR_INVALID, err)
 #define TRY(x) do { int _rc = (x); if (_rc != LG_OK) return _rc; } while (0)
     {
         NEED(wr, "posenc.Wr.weight", 32, pos_dim);
@@ -656,48 +648,37 @@ int lg_engine_finalize_weights(lg_engine* e) {
 static int check_envelope(long long B, long long n0, long long n1) {
     const long long c0 = (n0 + 127) / 128 * 128, c1 = (n1 + 127) / 128 * 128;
     if (n0 > LG_MAX_KEYPOINTS || n1 > LG_MAX_KEYPOINTS)
-        return fail(LG_ERR_INVALID, "more than LG_MAX_KEYPOINTS (8192) keypoints in one image");
+        return set_error(LG_ERR_INVALID, "more than LG_MAX_KEYPOINTS (8192) keypoints in one image");
     if (B * (c0 + c1) > LG_MAX_ROWS)
-        return fail(LG_ERR_INVALID, "batch * (cap0 + cap1) exceeds LG_MAX_ROWS (2^21 keypoint rows per forward): split the batch across calls");
+        return set_error(LG_ERR_INVALID, "batch * (cap0 + cap1) exceeds LG_MAX_ROWS (2^21 keypoint rows per forward): split the batch across calls");
     if (B * c0 * c1 > LG_MAX_SIM_ELEMS)
-        return fail(LG_ERR_INVALID, "batch * cap0 * cap1 exceeds LG_MAX_SIM_ELEMS (2^31 - 1 similarity entries per forward): split the batch across calls");
+        return set_error(LG_ERR_INVALID, "batch * cap0 * cap1 exceeds LG_MAX_SIM_ELEMS (2^31 - 1 similarity entries per forward): split the batch across calls");
     return LG_OK;
 }
 
 int lg_engine_reserve(lg_engine* e, int32_t max_batch, int32_t max_n0, int32_t max_n1) {
-    if (!e || max_batch < 1 || max_n0 < 0 || max_n1 < 0) return fail(LG_ERR_INVALID, "bad argument");
+    if (!e || max_batch < 1 || max_n0 < 0 || max_n1 < 0) return set_error(LG_ERR_INVALID, "bad argument");
     TRY(check_envelope(max_batch, max_n0, max_n1));
     return ensure_workspace(e, max_batch, max_n0, max_n1);
 }
 
 int lg_engine_set_option(lg_engine* e, const char* key, int32_t value) {
-    if (!e || !key) return fail(LG_ERR_INVALID, "null argument");
+    if (!e || !key) return set_error(LG_ERR_INVALID, "null argument");
     if (std::strcmp(key, "fused_tail") == 0) { e->fused_tail = value != 0; return LG_OK; }
     if (std::strcmp(key, "fused_next") == 0) { e->fused_next = value != 0; return LG_OK; }
     if (std::strcmp(key, "fused_prep") == 0) { e->fused_prep = value != 0; return LG_OK; }
     if (std::strcmp(key, "attn_dma") == 0) { e->attn_dma = value != 0; return LG_OK; }
     if (std::strcmp(key, "adapt_gather") == 0) { e->adapt_gather = value != 0; return LG_OK; }
     if (std::strcmp(key, "sim_planes") == 0) { e->sim_planes = value != 0; return LG_OK; }
-    if (std::strcmp(key, "sim_chunk") == 0) { if (value < 0 || value % 64) return fail(LG_ERR_INVALID, "sim_chunk: 0 or a multiple of 64"); e->sim_chunk = value; return LG_OK; }
-    if (std::strcmp(key, "attn_rows") == 0) { if (value != 16 && value != 32 && value != 64) return fail(LG_ERR_INVALID, "attn_rows must be 16, 32 or 64"); e->attn_rows = value; e->attn_auto_rows = false; return LG_OK; }
-    if (std::strcmp(key, "tail_row_tiles") == 0) { if (value != 0 && value != 1 && value != 2 && value != 4) return fail(LG_ERR_INVALID, "tail_row_tiles must be 0 (automatic), 1, 2 or 4"); e->tail_row_tiles = value; return LG_OK; }
+    if (std::strcmp(key, "sim_chunk") == 0) { if (value < 0 || value % 64) return set_error(LG_ERR_INVALID, "sim_chunk: 0 or a multiple of 64"); e->sim_chunk = value; return LG_OK; }
+    if (std::strcmp(key, "attn_rows") == 0) { if (value != 16 && value != 32 && value != 64) return set_error(LG_ERR_INVALID, "attn_rows must be 16, 32 or 64"); e->attn_rows = value; e->attn_auto_rows = false; return LG_OK; }
+    if (std::strcmp(key, "tail_row_tiles") == 0) { if (value != 0 && value != 1 && value != 2 && value != 4) return set_error(LG_ERR_INVALID, "tail_row_tiles must be 0 (automatic), 1, 2 or 4"); e->tail_row_tiles = value; return LG_OK; }
     if (std::strcmp(key, "profile_only") == 0) { e->prof_only = value; return LG_OK; }   // kernel class index, -1 = all classes
     if (std::strcmp(key, "tail_timing") == 0) { e->tail_timing = value; return LG_OK; }   // 1: tail kernel, 2: self projection, 3: self attention (LG_ATTN_TIMING builds), 4: assign sweeps, 5 / 6: layer 0's CrossBlock / SelfBlock tail WITH its fused next projection (stamps of the projection in TAILDBG2)
-    return fail(LG_ERR_INVALID, std::string("unknown option '") + key + "'");
+    return set_error(LG_ERR_INVALID, std::string("unknown option '") + key + "'");
 }
 
-int lg_engine_debug_stop_after(lg_engine* e, int32_t step) { if (!e) return fail(LG_ERR_INVALID, "null engine"); e->debug_stop = step; return LG_OK; }
-
-int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
-                             const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out,
-                             void* hip_stream) {
-    if (channels != 256) return fail(LG_ERR_INVALID, "descriptor map must have 256 channels");
-    if (batch < 1 || h < 1 || w < 1 || n < 0 || cell < 1) return fail(LG_ERR_INVALID, "bad descriptor map / keypoint sizes");
-    if (!desc_map || !workspace || (n && (!keypoints || !out))) return fail(LG_ERR_INVALID, "null pointer");
-    SpArgs a{desc_map, workspace, keypoints, num, out, batch, h, w, n, cell, normalize_dense ? 1 : 0};
-    HIPCHK(launch_sp_sample(a, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
+int lg_engine_debug_stop_after(lg_engine* e, int32_t step) { if (!e) return set_error(LG_ERR_INVALID, "null engine"); e->debug_stop = step; return LG_OK; }
 
 namespace {
 // Fused tail: 16-row tiles per workgroup by grid fill.  A 64-row workgroup costs ~114k cycles (matrix-bound), a 32- / 16-row
@@ -712,82 +693,7 @@ int tail_row_tiles_for(int R) {
     }
     return best;
 }
-struct SpLayout { size_t mask_a, mask_b, nms, rows, cxy, csc, ctot, total; };
-SpLayout sp_layout(int B, int h, int w, int maxc) {
-    SpLayout l{}; size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
-    const size_t px = (size_t)B * h * w;
-    l.mask_a = take(px); l.mask_b = take(px); l.nms = take(px * 4); l.rows = take((size_t)B * h * 4);
-    l.cxy = take((size_t)B * maxc * 4); l.csc = take((size_t)B * maxc * 4); l.ctot = take((size_t)B * 4); l.total = off;
-    return l;
-}
 }  // namespace
-
-int lg_sp_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t k, float* dst, void* hip_stream) {
-    if (!src || !dst || cout < 1 || cin < 1 || (k != 1 && k != 3)) return fail(LG_ERR_INVALID, "bad conv weight");
-    HIPCHK(launch_sp_pack_weight(src, dst, cout, cin, k, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
-int64_t lg_sp_encode_workspace_bytes(int32_t batch, int32_t h, int32_t w) {
-    if (batch < 1 || h < 8 || w < 8) return 0;
-    return (int64_t)2 * batch * h * w * 64 * 4;
-}
-
-int lg_sp_encode(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                 int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
-    if (batch < 1 || h < 8 || w < 8) return fail(LG_ERR_INVALID, "image height / width must be at least 8");
-    if (!image || !params || !workspace || !scores || !desc_map) return fail(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return fail(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
-    for (int i = 0; i < 24; ++i) if (!params[i]) return fail(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 0, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
-int lg_sp_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t k, void* dst, void* hip_stream) {
-    if (!src || !dst || cout < 1 || cin < 32 || cin % 32 || (k != 1 && k != 3) || (k == 3 && cout % 64)) return fail(LG_ERR_INVALID, "bad conv weight (split form: cin a multiple of 32; 3 x 3 layers: cout a multiple of 64)");
-    HIPCHK(launch_sp_pack_weight_split(src, dst, cout, cin, k, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
-int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                       int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
-    if (batch < 1 || h < 8 || w < 8) return fail(LG_ERR_INVALID, "image height / width must be at least 8");
-    // sp_conv3x3_split_kernel addresses the pixels of ONE image with 32-bit element offsets (h w 64 channels at full resolution)
-    if ((int64_t)h * w * 64 >= (int64_t)1 << 31) return fail(LG_ERR_INVALID, "split-f16 conv stack: h * w must stay below 2^25 pixels (use conv_precision = fp32 for larger images)");
-    if (!image || !params || !workspace || !scores || !desc_map) return fail(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return fail(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
-    for (int i = 0; i < 24; ++i) if (!params[i]) return fail(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 1, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
-int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t max_candidates) {
-    if (batch < 1 || h < 1 || w < 1 || max_candidates < 1) return 0;
-    return (int64_t)sp_layout(batch, h, w, max_candidates).total;
-}
-
-int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32_t nms_radius, int32_t remove_borders,
-                 float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
-                 int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
-    if (batch < 1 || h < 1 || w < 1 || h >= 32768 || w >= 32768) return fail(LG_ERR_INVALID, "bad score map size");
-    if (nms_radius < 0 || nms_radius > 4) return fail(LG_ERR_INVALID, "nms_radius must be in [0, 4]");
-    if (max_keypoints > SP_TOPK_MAX) return fail(LG_ERR_INVALID, "max_keypoints above 4096");
-    if (capacity < 1 || max_candidates < 1 || (max_keypoints > 0 && capacity < max_keypoints)) return fail(LG_ERR_INVALID, "bad capacity / max_candidates");
-    if (!scores || !workspace || !keypoints || !kp_scores || !counts) return fail(LG_ERR_INVALID, "null pointer");
-    const SpLayout l = sp_layout(batch, h, w, max_candidates);
-    if (workspace_bytes < (int64_t)l.total) return fail(LG_ERR_INVALID, "workspace too small (lg_sp_detect_workspace_bytes)");
-    char* ws = static_cast<char*>(workspace);
-    SpDetectArgs a{};
-    a.scores = scores; a.B = batch; a.H = h; a.W = w; a.radius = nms_radius; a.border = remove_borders; a.threshold = detection_threshold;
-    a.max_keypoints = max_keypoints; a.capacity = capacity; a.max_candidates = max_candidates;
-    a.mask_a = reinterpret_cast<unsigned char*>(ws + l.mask_a); a.mask_b = reinterpret_cast<unsigned char*>(ws + l.mask_b);
-    a.nms = reinterpret_cast<float*>(ws + l.nms); a.row_counts = reinterpret_cast<int*>(ws + l.rows);
-    a.cand_xy = reinterpret_cast<int*>(ws + l.cxy); a.cand_score = reinterpret_cast<float*>(ws + l.csc); a.cand_total = reinterpret_cast<int*>(ws + l.ctot);
-    a.keypoints = keypoints; a.kp_scores = kp_scores; a.counts = counts; a.totals = totals;
-    HIPCHK(launch_sp_detect(a, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
 
 namespace {
 // matrix-core-dense spin: 2 waves per SIMD, 8 independent accumulators per wave (the pipe never waits), operands with
@@ -819,7 +725,7 @@ __global__ __launch_bounds__(512) void mfma_spin_kernel(long long* cycles, int i
  * the power management to settle).  tflops = achieved dense bf16 rate (the nominal 2.5 PFLOP/s assumes 2.4 GHz; under this load
  * the boxes of the pool hold 1.8 - 2.1 GHz), mhz = shader clock during the spin (s_memtime span of one wave / HIP-event time). */
 int lg_debug_mfma_sustained(double* tflops, double* mhz, void* hip_stream) {
-    if (!tflops || !mhz) return fail(LG_ERR_INVALID, "null pointer");
+    if (!tflops || !mhz) return set_error(LG_ERR_INVALID, "null pointer");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     long long* d = nullptr;
     HIPCHK(hipMalloc(&d, 16));
@@ -842,15 +748,15 @@ int lg_debug_mfma_sustained(double* tflops, double* mhz, void* hip_stream) {
 }
 
 int lg_engine_debug_caps(lg_engine* e, int32_t* cap0, int32_t* cap1) {
-    if (!e || !cap0 || !cap1) return fail(LG_ERR_INVALID, "null argument");
+    if (!e || !cap0 || !cap1) return set_error(LG_ERR_INVALID, "null argument");
     *cap0 = e->cur_cap0; *cap1 = e->cur_cap1;
     return LG_OK;
 }
 
 int lg_engine_debug_read(lg_engine* e, const char* name, void* host_dst, int64_t max_bytes, int64_t* nbytes_out) {
-    if (!e || !name) return fail(LG_ERR_INVALID, "null argument");
+    if (!e || !name) return set_error(LG_ERR_INVALID, "null argument");
     auto it = e->bufs.find(name);
-    if (it == e->bufs.end()) return fail(LG_ERR_INVALID, std::string("unknown buffer '") + name + "'");
+    if (it == e->bufs.end()) return set_error(LG_ERR_INVALID, std::string("unknown buffer '") + name + "'");
     if (nbytes_out) *nbytes_out = (int64_t)it->second.second;
     HIPCHK(hipDeviceSynchronize());
     if (host_dst && max_bytes > 0) {
@@ -861,27 +767,27 @@ int lg_engine_debug_read(lg_engine* e, const char* name, void* host_dst, int64_t
 }
 
 int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
-    if (!e || !io) return fail(LG_ERR_INVALID, "null argument");
-    if (!e->weights_ready) return fail(LG_ERR_STATE, "weights not finalised");
+    if (!e || !io) return set_error(LG_ERR_INVALID, "null argument");
+    if (!e->weights_ready) return set_error(LG_ERR_STATE, "weights not finalised");
     const int B = io->batch, n0 = io->n0, n1 = io->n1, L = e->cfg.n_layers, D = 256;
-    if (B < 1 || n0 < 0 || n1 < 0) return fail(LG_ERR_INVALID, "bad batch / keypoint counts");
+    if (B < 1 || n0 < 0 || n1 < 0) return set_error(LG_ERR_INVALID, "bad batch / keypoint counts");
     TRY(check_envelope(B, n0, n1));
-    if (!io->stop || !io->n_matches) return fail(LG_ERR_INVALID, "null output pointer");
-    if ((n0 && (!io->matches0 || !io->scores0)) || (n1 && (!io->matches1 || !io->scores1))) return fail(LG_ERR_INVALID, "null output pointer");
-    if (n0 && n1 && (!io->matches || !io->match_scores)) return fail(LG_ERR_INVALID, "null match-list pointer");
-    if (n0 && n1 && (!io->kpts0 || !io->kpts1 || !io->desc0 || !io->desc1)) return fail(LG_ERR_INVALID, "null input pointer");
+    if (!io->stop || !io->n_matches) return set_error(LG_ERR_INVALID, "null output pointer");
+    if ((n0 && (!io->matches0 || !io->scores0)) || (n1 && (!io->matches1 || !io->scores1))) return set_error(LG_ERR_INVALID, "null output pointer");
+    if (n0 && n1 && (!io->matches || !io->match_scores)) return set_error(LG_ERR_INVALID, "null match-list pointer");
+    if (n0 && n1 && (!io->kpts0 || !io->kpts1 || !io->desc0 || !io->desc1)) return set_error(LG_ERR_INVALID, "null input pointer");
     const bool do_stop = e->cfg.depth_confidence > 0;
     const bool do_prune = e->cfg.width_confidence > 0 && !(io->flags & LG_FLAG_NO_PRUNING);
-    if (do_prune && ((n0 && !io->prune0) || (n1 && !io->prune1))) return fail(LG_ERR_INVALID, "prune0/prune1 required when width_confidence > 0");
-    if (e->cfg.add_scale_ori && (!io->scales0 || !io->oris0 || !io->scales1 || !io->oris1)) return fail(LG_ERR_INVALID, "scales/oris required");
+    if (do_prune && ((n0 && !io->prune0) || (n1 && !io->prune1))) return set_error(LG_ERR_INVALID, "prune0/prune1 required when width_confidence > 0");
+    if (e->cfg.add_scale_ori && (!io->scales0 || !io->oris0 || !io->scales1 || !io->oris1)) return set_error(LG_ERR_INVALID, "scales/oris required");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int max_matches = n0 < n1 ? n0 : n1;
     const bool ext = (io->flags & LG_FLAG_EXT) != 0;            // round-5 extension fields present
     const bool check_finite = ext && (io->flags & LG_FLAG_CHECK_FINITE) != 0;
-    if ((io->flags & LG_FLAG_CHECK_FINITE) && (!ext || !io->status)) return fail(LG_ERR_INVALID, "LG_FLAG_CHECK_FINITE needs LG_FLAG_EXT and a status array");
-    if (ext && io->wire && io->wire_stride < LG_WIRE_WIDTH(n0, n1)) return fail(LG_ERR_INVALID, "wire_stride < LG_WIRE_WIDTH(n0, n1) = 3 n0 + 3 n1 + 2");
-    if (ext && do_prune && ((io->prune0_f32 || io->prune1_f32))) return fail(LG_ERR_INVALID, "prune0_f32 / prune1_f32 are the outputs of a forward WITHOUT pruning");
-    if (ext && !do_prune && ((io->prune0_i64 || io->prune1_i64))) return fail(LG_ERR_INVALID, "prune0_i64 / prune1_i64 are the outputs of a forward WITH pruning");
+    if ((io->flags & LG_FLAG_CHECK_FINITE) && (!ext || !io->status)) return set_error(LG_ERR_INVALID, "LG_FLAG_CHECK_FINITE needs LG_FLAG_EXT and a status array");
+    if (ext && io->wire && io->wire_stride < LG_WIRE_WIDTH(n0, n1)) return set_error(LG_ERR_INVALID, "wire_stride < LG_WIRE_WIDTH(n0, n1) = 3 n0 + 3 n1 + 2");
+    if (ext && do_prune && ((io->prune0_f32 || io->prune1_f32))) return set_error(LG_ERR_INVALID, "prune0_f32 / prune1_f32 are the outputs of a forward WITHOUT pruning");
+    if (ext && !do_prune && ((io->prune0_i64 || io->prune1_i64))) return set_error(LG_ERR_INVALID, "prune0_i64 / prune1_i64 are the outputs of a forward WITH pruning");
     auto write_outputs = [&](const int* final_layer, int stop_const, const int* range_flag, const int* device_err) -> hipError_t {
         OutArgs o{};
         o.B = B; o.n0 = n0; o.n1 = n1; o.L = L; o.kmax = max_matches; o.final_layer = final_layer; o.stop_const = stop_const; o.stop = io->stop;
@@ -1177,10 +1083,10 @@ int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
 }
 
 int lg_unpack_wire(const lg_unpack_io* io, void* hip_stream) {
-    if (!io || io->rows < 0 || io->n0 < 0 || io->n1 < 0 || io->pairs_out < 0) return fail(LG_ERR_INVALID, "lg_unpack_wire: bad argument");
+    if (!io || io->rows < 0 || io->n0 < 0 || io->n1 < 0 || io->pairs_out < 0) return set_error(LG_ERR_INVALID, "lg_unpack_wire: bad argument");
     if (io->rows == 0 || io->pairs_out == 0) return LG_OK;    // an empty gather (world of one, empty batch) is a no-op
-    if (!io->wire || io->wire_stride < LG_WIRE_WIDTH(io->n0, io->n1)) return fail(LG_ERR_INVALID, "lg_unpack_wire: null wire or wire_stride < LG_WIRE_WIDTH(n0, n1)");
-    if (io->n0 > LG_MAX_KEYPOINTS || io->n1 > LG_MAX_KEYPOINTS) return fail(LG_ERR_INVALID, "lg_unpack_wire: more than LG_MAX_KEYPOINTS keypoints");
+    if (!io->wire || io->wire_stride < LG_WIRE_WIDTH(io->n0, io->n1)) return set_error(LG_ERR_INVALID, "lg_unpack_wire: null wire or wire_stride < LG_WIRE_WIDTH(n0, n1)");
+    if (io->n0 > LG_MAX_KEYPOINTS || io->n1 > LG_MAX_KEYPOINTS) return set_error(LG_ERR_INVALID, "lg_unpack_wire: more than LG_MAX_KEYPOINTS keypoints");
     UnpackArgs a{};
     a.wire = io->wire; a.stride = io->wire_stride; a.n0 = io->n0; a.n1 = io->n1; a.with_prune = io->with_prune; a.pairs_out = io->pairs_out;
     a.kmax = io->n0 < io->n1 ? io->n0 : io->n1; a.order = io->order;

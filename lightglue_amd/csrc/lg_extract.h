@@ -1,0 +1,157 @@
+// lightglue_amd — the algorithms both keypoint extractors run (SuperPoint: lg_sp_encoder.hip, lg_superpoint.hip; ALIKED: lg_aliked.hip),
+// implemented once in lg_extract.hip: the exact-fp32 implicit-GEMM convolution, the weight repack, simple_nms, threshold + raster-order
+// compaction and the top-K selection.
+#pragma once
+#include "lg_kernels.h"
+
+namespace lg {
+
+// ---------------------------------------------------------------- convolution
+// Implicit GEMM on NHWC activations, C[pixel][cout] = sum_{tap, cin} A[pixel + tap][cin] W[tap][cout][cin] (exact fp32, v_mfma_f32_16x16x4_f32):
+//   * one MFMA "chunk" = 16 input channels: lane (lr, g) supplies pixel lr / cout lr and the 4 consecutive channels 4g .. 4g + 3 -> ONE 16-byte
+//     load per fragment for both operands (weights are repacked [tap][cout][cin] once, launch_fold);
+//   * wave = 2 image rows x 32 pixels x 16 NT output channels (NT = 1, 2, 4 from Cout: the 16-channel layers of ALIKED do not run 48 dead
+//     output columns), workgroup = 4 waves = 8 rows: the 9 taps re-read the same input lines from L1 / L2, nothing is staged through LDS;
+//   * zero padding = clamped address + select; bias / activation / the 2x2 max-pool run on the accumulators (a lane holds 4 horizontally
+//     consecutive pixels of one channel and both rows of the pool window).
+// The split-f16 kernels of lg_sp_encoder.hip take the same arguments (w then holds their packing) and end in the same epilogue.
+enum : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SELU = 2 };
+struct ConvArgs {
+    const float* in; const void* w; const float* bias;   // in [B][H][W][Cin]; w [taps][Cout][Cin] fp32; bias [Cout] or null
+    const float* in2; const float* w2;                   // optional extra K at the centre pixel (ResBlock downsample): in2 [B][H][W][Cin2], w2 [Cout][Cin2]
+    float* out;                                          // [B][H][W][Cout]; pool: [B][H/2][W/2][Cout]; out_nchw: [B][Cout][H][W]
+    int B, H, W, Cin, Cin2, Cout, taps;                  // taps 9 (3 x 3, zero pad 1) or 1
+    int act, pool, out_nchw;
+};
+void launch_conv(const ConvArgs& a, hipStream_t s);      // exact fp32; Cin % 16 == 0
+
+constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.0507009873554804934193349852946f;
+__device__ __forceinline__ float selu(float x) { return SELU_SCALE * (x > 0.f ? x : SELU_ALPHA * expm1f(x)); }
+
+// bias / activation / 2x2 max-pool / stores of one wave's 2 rows x 32 pixels x 16 NT output channels, straight from the accumulators:
+// acc[mt][nt][r] = out[pixel (y0 + mt / 2, x0 + (mt & 1) * 16 + 4g + r)][cout n0 + nt * 16 + lr]
+template <int NT>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][NT], int b, int n0, int x0, int y0, int lr, int g) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int co = n0 + nt * 16 + lr;
+        if (co >= a.Cout) continue;
+        const float bv = a.bias ? a.bias[co] : 0.f;
+        f32x4 v[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            v[mt] = acc[mt][nt] + bv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[mt][r] = a.act == ACT_RELU ? fmaxf(v[mt][r], 0.f) : (a.act == ACT_SELU ? selu(v[mt][r]) : v[mt][r]);
+        }
+        if (a.pool) {        // 2x2 max-pool (SuperPoint): rows y0, y0 + 1; columns (4g, 4g + 1), (4g + 2, 4g + 3)
+            const int H2 = a.H >> 1, W2 = a.W >> 1, yo = y0 >> 1;
+            if (yo < H2) {
+#pragma unroll
+                for (int xt = 0; xt < 2; ++xt) {
+                    const float p0 = fmaxf(fmaxf(v[xt][0], v[xt][1]), fmaxf(v[2 + xt][0], v[2 + xt][1]));
+                    const float p1 = fmaxf(fmaxf(v[xt][2], v[xt][3]), fmaxf(v[2 + xt][2], v[2 + xt][3]));
+                    const int xo = (x0 + xt * 16 + 4 * g) >> 1;
+                    float* o = a.out + (((long long)b * H2 + yo) * W2 + xo) * a.Cout + co;
+                    if (xo < W2) o[0] = p0;
+                    if (xo + 1 < W2) o[a.Cout] = p1;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const int y = y0 + (mt >> 1), x = x0 + (mt & 1) * 16 + 4 * g;
+                if (y >= a.H) continue;
+                if (a.out_nchw) {    // 4 consecutive pixels of one channel: one 16-byte store when the row allows it
+                    float* o = a.out + (((long long)b * a.Cout + co) * a.H + y) * a.W + x;
+                    if (x + 3 < a.W && (a.W & 3) == 0) *reinterpret_cast<f32x4*>(o) = v[mt];
+                    else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) if (x + r < a.W) o[r] = v[mt][r];
+                    }
+                } else {
+                    float* o = a.out + (((long long)b * a.H + y) * a.W + x) * a.Cout + co;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) if (x + r < a.W) o[(long long)r * a.Cout] = v[mt][r];
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- weight repack
+// dst = s[co] * src in the layout of `mode`, s = gamma / sqrt(var + 1e-5) with BatchNorm (bn = {gamma, beta, mean, var}, eval), else 1;
+// bias_dst[co] = s (cbias - mean) + beta (+ extra) when bias_dst is set.  src [Cout][Cin][kk]; PK_AGG: [n_pos][128][128] -> [128][n_pos * 128]
+enum : int { PK_TAP_CO_CI = 0, PK_CO_TAP_CI = 1, PK_TAP_CI_CO = 2, PK_COPY = 3, PK_AGG = 4 };
+hipError_t launch_fold(const float* src, float* dst, float* bias_dst, int Cout, int Cin, int kk, int mode, const float* const* bn, const float* cbias,
+                       const float* extra, hipStream_t s);
+
+// ---------------------------------------------------------------- keypoint detection on a dense score map
+// simple_nms (superpoint.py / aliked.py: three rounds of (2r+1)^2 max-pooling with equality tests), border, threshold, raster-order compaction
+// (the order of torch.where / nonzero) and the selection of the K best.  All comparisons are exact.
+struct DetectArgs {
+    const float* S;                    // [B][H][W] scores
+    int B, H, W, radius;               // NMS radius <= 8
+    unsigned char* mask_a; unsigned char* mask_b;   // [B][H][W] workspace
+    float* nms;                        // [B][H][W]: S at the NMS maxima, 0 elsewhere
+    // the thresholded value: border_value within `border` pixels of the top / left edges and of the far ones (image_size [B][2] (w, h),
+    // truncated like .long(), else H / W), nms elsewhere
+    int border; const float* image_size; float border_value;
+    float threshold;                   // a per-image array th[b] replaces it where the kernels are given one
+    int* row_counts;                   // [B][H] pixels above the threshold
+    int max_candidates;                // candidate rows per image (hits beyond are dropped; cand_total keeps counting)
+    int* cand_idx; float* cand_score; int* cand_total;   // [B][max_candidates] raster index y W + x and value, [B] hits
+    int K, sort_always;                // keep the K best (K <= 0: all); ordered by score when that limited the set, or always
+    int sel_cap; int* sel; unsigned* sel_key;        // [B][sel_cap] kept candidates in raster order and their keys
+};
+
+// the workspace of one detection, carved from one buffer; rowsum / th only with `stats` (ALIKED's mean fallback)
+struct DetectLayout { long long mask_a, mask_b, nms, rows, rowsum, th, cidx, cscore, ctotal, sel, selkey, total; };
+DetectLayout detect_layout(int B, int H, int W, int max_candidates, int sel_cap, bool stats);
+void detect_bind(DetectArgs& a, const DetectLayout& L, void* ws);   // the workspace pointers of `a`
+
+void launch_nms(const DetectArgs& a, hipStream_t s);                                         // S -> nms (mask_a, mask_b as scratch)
+void launch_row_count(const DetectArgs& a, const float* th, double* rowsum, hipStream_t s);  // rowsum (optional): [B][H] row sums of S
+void launch_compact(const DetectArgs& a, const float* th, hipStream_t s);
+void launch_select(const DetectArgs& a, hipStream_t s);
+
+// entries the selection kept for image b, and whether their output order is by score
+__device__ __forceinline__ int selected_count(const DetectArgs& a, int b) {
+    const int total = min(a.cand_total[b], a.max_candidates);
+    return min(a.K > 0 ? min(total, a.K) : total, a.sel_cap);
+}
+__device__ __forceinline__ bool selection_sorted(const DetectArgs& a, int b) {
+    return a.sort_always || (a.K > 0 && min(a.cand_total[b], a.max_candidates) > a.K);
+}
+// output slot of kept entry j among n: score descending, the lower raster index first among equal keys.  The block streams the key list
+// through LDS together (every thread reads each key as a broadcast), so every thread of the block calls it; slots j >= n get no rank.
+__device__ __forceinline__ int selected_rank(const unsigned* key, int n, int j) {
+    __shared__ unsigned tile[1024];
+    const unsigned k = j < n ? key[j] : 0u;
+    int rank = 0;
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int m = min(1024, n - i0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < m; t += blockDim.x) tile[t] = key[i0 + t];
+        __syncthreads();
+        for (int t = 0; t < m; ++t) { const unsigned q = tile[t]; rank += (q > k) || (q == k && i0 + t < j); }
+    }
+    return rank;
+}
+
+__device__ __forceinline__ int block_sum_int(int v, int* sh) {   // 256 threads
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// host: workspace carving, 256-byte aligned offsets
+struct Bump {
+    long long used = 0;
+    long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
+};
+inline unsigned blocks(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+}  // namespace lg

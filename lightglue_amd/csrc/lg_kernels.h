@@ -1,9 +1,20 @@
 // lightglue_amd — kernel argument structs and host-side launchers (internal C++ interface;
 // the public C-ABI is include/lightglue_amd.h).
 #pragma once
+#include <string>
+
 #include "lg_common.h"
 
 namespace lg {
+
+// the error every C entry point reports: sets the message lg_last_error() returns (lg_engine.hip) and returns `code`
+int set_error(int code, const std::string& msg);
+#define HIPCHK(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess)                                                                     \
+            return lg::set_error(LG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
 
 // ---------------------------------------------------------------- GEMM  (lg_gemm.hip)
 // Y[row, n] = sum_k A[row, k] * W[n, k] (+ bias[n]);  A is fp32 in HBM and converted to the operand
@@ -216,40 +227,5 @@ struct AssignArgs {
     int all_rows_live; // 1: len == n for every segment (no pruning ever, no ragged counts): the -1 / 0 pre-fill of m/s is skipped
 };
 hipError_t launch_assign(const AssignArgs& a, hipStream_t s);
-
-// ---------------------------------------------------------------- SuperPoint descriptor head (lg_superpoint.hip)
-struct SpArgs {
-    const float* desc_map;     // [B][256][h][w] dense descriptor map (NCHW, as the conv stack leaves it)
-    float* nhwc;               // [B][h][w][256] workspace: (normalised) location-major copy
-    const float* keypoints;    // [B][N][2] pixel (x, y)
-    const int* num;            // [B] live keypoints per image or nullptr
-    float* out;                // [B][N][256]
-    int B, h, w, N, s, normalize_dense;
-};
-hipError_t launch_sp_sample(const SpArgs& a, hipStream_t s);
-
-// keypoint extraction from the dense score map (ref superpoint.py:52-70 simple_nms, :186-214)
-struct SpDetectArgs {
-    const float* scores;       // [B][H][W]
-    int B, H, W, radius, border; float threshold;
-    int max_keypoints;         // top-k (<= 0: keep all, ref :200-208), at most SP_TOPK_MAX
-    int capacity;              // rows of the outputs per image
-    int max_candidates;        // rows of the candidate buffers per image
-    // workspace pieces
-    unsigned char* mask_a; unsigned char* mask_b;   // [B][H][W]
-    float* nms;                // [B][H][W] scores after non-maximum suppression (0 elsewhere)
-    int* row_counts;           // [B][H]
-    int* cand_xy; float* cand_score; int* cand_total;   // [B][max_candidates] packed (y << 16 | x), [B][max_candidates], [B]
-    // outputs
-    float* keypoints; float* kp_scores; int* counts;    // [B][capacity][2] (x, y), [B][capacity], [B]
-    int* totals;               // optional [B]: pixels above the threshold before top-k / capacity clipping
-};
-constexpr int SP_TOPK_MAX = 4096;
-// SuperPoint conv stack (lg_sp_encoder.hip): image [B][1][H][W] (any H, W >= 8; floor pooling) -> scores [B][H/8*8][W/8*8], raw descriptor map
-// [B][256][H/8][W/8]; P = 24 device pointers (packed weight, bias) x 12 layers; ws = 2 * B*H*W*64 floats
-hipError_t launch_sp_encode(const float* image, int B, int H, int W, const float* const* P, float* ws, float* scores, float* desc_map, int split, hipStream_t s);
-hipError_t launch_sp_pack_weight_split(const float* src, void* dst, int Cout, int Cin, int k, hipStream_t s);
-hipError_t launch_sp_pack_weight(const float* src, float* dst, int Cout, int Cin, int k, hipStream_t s);
-hipError_t launch_sp_detect(const SpDetectArgs& a, hipStream_t s);
 
 }  // namespace lg

@@ -5,81 +5,24 @@
 // Arithmetic is EXACT fp32 (v_mfma_f32_16x16x4_f32): the detector thresholds / NMS-compares the scores, so they must
 // agree with an fp32 convolution to round-off; the f32 MFMA rate (157 TFLOP/s) is not the limiter of this stage.
 //
-// Convolutions are implicit GEMMs on NHWC activations, C[pixel][cout] = sum_{tap, cin} A[pixel + tap][cin] W[tap][cout][cin]:
-//   * one MFMA "chunk" = 16 input channels: lane (lr, g) supplies pixel lr / cout lr and the 4 consecutive channels
-//     4g..4g+3 -> ONE 16-byte load per fragment for both operands (weights are repacked [tap][cout][cin] once);
-//   * wave = 2 image rows x 32 pixels x 64 output channels (4 x 4 tiles, 64 accumulator registers), workgroup = 4 waves =
-//     8 rows: the 9 taps re-read the same input lines from L1/L2, nothing is staged through LDS;
-//   * zero padding = clamped address + select; bias / ReLU / the 2x2 max-pool run on the accumulators (a lane holds 4
-//     horizontally consecutive pixels of one channel and both rows of the pool window).
-#include "lg_kernels.h"
+// The fp32 convolutions run launch_conv (lg_extract.hip, shared with ALIKED); this file holds the split-f16 forms, which end in the same
+// epilogue (conv_epilogue, lg_extract.h).
+#include <string>
+
+#include "lg_extract.h"
+#include "../../include/lightglue_amd.h"
 
 namespace lg {
 
-struct ConvArgs {
-    const float* in; float* out; const void* w; const float* bias;
-    int B, H, W, Cin, Cout, taps;    // taps = 9 (3x3, pad 1) or 1 (1x1)
-    int relu, pool, out_nchw;
-};
-
-// bias / ReLU / 2x2 max-pool / stores of one wave's 2 rows x 32 pixels x 64 output channels, straight from the accumulators (shared by the conv kernels)
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][4], int b, int n0, int ntl, int x0, int y0, int lr, int g) {
-    // ---- epilogue: acc[mt][nt][r] = out[pixel (y0 + mt/2, x0 + (mt&1)*16 + 4g + r)][cout n0 + nt*16 + lr]
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int co = n0 + nt * 16 + lr;
-        if (nt >= ntl || co >= a.Cout) continue;
-        const float bv = a.bias[co];
-        f32x4 v[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            v[mt] = acc[mt][nt] + bv;
-            if (a.relu) { v[mt][0] = fmaxf(v[mt][0], 0.f); v[mt][1] = fmaxf(v[mt][1], 0.f); v[mt][2] = fmaxf(v[mt][2], 0.f); v[mt][3] = fmaxf(v[mt][3], 0.f); }
-        }
-        if (a.pool) {        // 2x2 max-pool (ref :161-169): rows y0, y0+1; columns (4g, 4g+1), (4g+2, 4g+3)
-            const int H2 = a.H >> 1, W2 = a.W >> 1, yo = y0 >> 1;
-            if (yo < H2) {
-#pragma unroll
-                for (int xt = 0; xt < 2; ++xt) {
-                    const float p0 = fmaxf(fmaxf(v[xt][0], v[xt][1]), fmaxf(v[2 + xt][0], v[2 + xt][1]));
-                    const float p1 = fmaxf(fmaxf(v[xt][2], v[xt][3]), fmaxf(v[2 + xt][2], v[2 + xt][3]));
-                    const int xo = (x0 + xt * 16 + 4 * g) >> 1;
-                    float* o = a.out + (((long long)b * H2 + yo) * W2 + xo) * a.Cout + co;
-                    if (xo < W2) o[0] = p0;
-                    if (xo + 1 < W2) o[a.Cout] = p1;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const int y = y0 + (mt >> 1), x = x0 + (mt & 1) * 16 + 4 * g;
-                if (y >= a.H) continue;
-                if (a.out_nchw) {    // 4 consecutive pixels of one channel: one 16-byte store when the row allows it
-                    float* o = a.out + (((long long)b * a.Cout + co) * a.H + y) * a.W + x;
-                    if (x + 3 < a.W && (a.W & 3) == 0) *reinterpret_cast<f32x4*>(o) = v[mt];
-                    else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) if (x + r < a.W) o[r] = v[mt][r];
-                    }
-                } else {
-                    float* o = a.out + (((long long)b * a.H + y) * a.W + x) * a.Cout + co;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (x + r < a.W) o[(long long)r * a.Cout] = v[mt][r];
-                }
-            }
-        }
-    }
-}
-
-// SPLIT (conv_precision "f16x3", opt-in): the same implicit GEMM on split-f16 operands — activations split into hi + lo f16 planes in registers (x = hi + lo, 22 bits),
-// weights pre-split by lg_sp_pack_conv_weight_split ([2 planes][tap][cout][cin] f16, the bytes of the fp32 array), three v_mfma_f32_16x16x32_f16 per product with fp32
-// accumulation (hi lo + lo hi + hi hi; the dropped lo lo term is 2^-24-class, below the fp32 convolution's own summation-order noise over K = 576 ... 1152).  One MFMA
-// chunk = 32 input channels: lane (lr, g) supplies pixel lr / cout lr and the 8 consecutive channels 8g .. 8g + 7 (two 16-byte fp32 loads per activation fragment,
-// one 16-byte load per weight plane).  Same tiles, loop order, epilogue and layouts as the fp32 form.  Measured (profiles/r06sp_*): 1.2 x the fp32 form, not the 5 x of
-// the MFMA rates — with 16 KB of operand loads per 48 MFMAs and no LDS staging the kernel is bound by its loads and their address / split arithmetic, whatever the matrix
-// instruction costs (a one-step-ahead register prefetch at one wave per SIMD: slower; chunk-outer loop order: the same).
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void sp_conv_kernel(ConvArgs a) {
+// The 1 x 1 layers of the split-f16 form (conv_precision "f16x3", opt-in: convPb, convDb): the implicit GEMM of launch_conv on split-f16 operands —
+// activations split into hi + lo f16 planes in registers (x = hi + lo, 22 bits), weights pre-split by lg_sp_pack_conv_weight_split ([2 planes][cout][cin]
+// f16, the bytes of the fp32 array), three v_mfma_f32_16x16x32_f16 per product with fp32 accumulation (hi lo + lo hi + hi hi; the dropped lo lo term is
+// 2^-24-class, below the fp32 convolution's own summation-order noise over K = 576 ... 1152).  One MFMA chunk = 32 input channels: lane (lr, g) supplies
+// pixel lr / cout lr and the 8 consecutive channels 8g .. 8g + 7 (two 16-byte fp32 loads per activation fragment, one 16-byte load per weight plane).
+// Same tiles (64 output channels per wave), epilogue and layouts as the fp32 form.  Measured on the 3 x 3 layers before they moved to the LDS-staged
+// kernel below (profiles/r06sp_*): 1.2 x the fp32 form, not the 5 x of the MFMA rates — with 16 KB of operand loads per 48 MFMAs and no LDS staging the
+// kernel is bound by its loads and their address / split arithmetic, whatever the matrix instruction costs.
+__global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     const int ngroups = (a.Cout + 63) >> 6;
     const int b = blockIdx.z / ngroups, n0 = (blockIdx.z - b * ngroups) << 6;
@@ -91,78 +34,52 @@ __global__ __launch_bounds__(256) void sp_conv_kernel(ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* inb = a.in + (long long)b * a.H * a.W * a.Cin;
-    constexpr int CPL = SPLIT ? 8 : 4;                        // input channels per lane and chunk
-    const int nchunk = a.Cin / (4 * CPL);
-    const long long wplane = (long long)a.taps * a.Cout * a.Cin;   // SPLIT: f16 elements from the hi to the lo weight plane
+    const int nchunk = a.Cin >> 5;
+    const long long wplane = (long long)a.Cout * a.Cin;        // f16 elements from the hi to the lo weight plane
     const int ntl = min(4, (a.Cout - n0 + 15) >> 4);          // live n-tiles of this channel group (wave-uniform)
-    for (int tap = 0; tap < a.taps; ++tap) {
-        const int dy = a.taps == 9 ? tap / 3 - 1 : 0, dx = a.taps == 9 ? tap % 3 - 1 : 0;
-        // source pixel of every m-tile for this tap (clamped; `ok` = inside the image)
-        long long poff[4]; bool ok[4];
+    // pixel of every m-tile (clamped; `ok` = inside the image)
+    long long poff[4]; bool ok[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const int yy = y0 + (mt >> 1), xx = x0 + (mt & 1) * 16 + lr;
+        ok[mt] = yy < a.H && xx < a.W;
+        const int yc = min(yy, a.H - 1), xc = min(xx, a.W - 1);
+        poff[mt] = ((long long)yc * a.W + xc) * a.Cin + 8 * g;
+    }
+    long long wrow[4];   // weight row of every n-tile, in elements (clamped into the matrix; dead lanes are zeroed after the load)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) wrow[nt] = (long long)min(n0 + nt * 16 + lr, a.Cout - 1) * a.Cin + 8 * g;
+    const f16_t* wh = static_cast<const f16_t*>(a.w);
+    for (int c = 0; c < nchunk; ++c) {
+        u32x4 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            const int yy = y0 + (mt >> 1) + dy, xx = x0 + (mt & 1) * 16 + lr + dx;
-            ok[mt] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-            const int yc = min(max(yy, 0), a.H - 1), xc = min(max(xx, 0), a.W - 1);
-            poff[mt] = ((long long)yc * a.W + xc) * a.Cin + CPL * g;
+            const float* src = inb + poff[mt] + c * 32;
+            f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+            if (!ok[mt]) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
+            split8<TagF16>(v0, v1, ah[mt], al[mt]);
         }
-        long long wrow[4];   // weight row of every n-tile, in elements (clamped into the matrix; dead lanes are zeroed after the load)
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wrow[nt] = ((long long)tap * a.Cout + min(n0 + nt * 16 + lr, a.Cout - 1)) * a.Cin + CPL * g;
-        if constexpr (SPLIT) {
-            const f16_t* wh = static_cast<const f16_t*>(a.w);
-            for (int c = 0; c < nchunk; ++c) {
-                u32x4 ah[4], al[4], bh[4], bl[4];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const float* src = inb + poff[mt] + c * 32;
-                    f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-                    if (!ok[mt]) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
-                    split8<TagF16>(v0, v1, ah[mt], al[mt]);
-                }
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const bool live = nt < ntl && n0 + nt * 16 + lr < a.Cout;
-                    const u32x4 h = *reinterpret_cast<const u32x4*>(wh + wrow[nt] + c * 32), l = *reinterpret_cast<const u32x4*>(wh + wplane + wrow[nt] + c * 32);
-                    bh[nt] = live ? h : u32x4{0u, 0u, 0u, 0u};
-                    bl[nt] = live ? l : u32x4{0u, 0u, 0u, 0u};
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) {
-                        mma_chunk<TagF16>(acc[mt][nt], ah[mt], bl[nt]);
-                        mma_chunk<TagF16>(acc[mt][nt], al[mt], bh[nt]);
-                        mma_chunk<TagF16>(acc[mt][nt], ah[mt], bh[nt]);
-                    }
-            }
-        } else {
-            const float* wf = static_cast<const float*>(a.w);
-            for (int c = 0; c < nchunk; ++c) {
-                u32x4 af[4], bf[4];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const u32x4 v = *reinterpret_cast<const u32x4*>(inb + poff[mt] + c * 16);
-                    af[mt] = ok[mt] ? v : u32x4{0u, 0u, 0u, 0u};
-                }
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const bool live = nt < ntl && n0 + nt * 16 + lr < a.Cout;
-                    const u32x4 v = *reinterpret_cast<const u32x4*>(wf + wrow[nt] + c * 16);
-                    bf[nt] = live ? v : u32x4{0u, 0u, 0u, 0u};
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) mma_chunk<TagF32>(acc[mt][nt], af[mt], bf[nt]);
-            }
+        for (int nt = 0; nt < 4; ++nt) {
+            const bool live = nt < ntl && n0 + nt * 16 + lr < a.Cout;
+            const u32x4 h = *reinterpret_cast<const u32x4*>(wh + wrow[nt] + c * 32), l = *reinterpret_cast<const u32x4*>(wh + wplane + wrow[nt] + c * 32);
+            bh[nt] = live ? h : u32x4{0u, 0u, 0u, 0u};
+            bl[nt] = live ? l : u32x4{0u, 0u, 0u, 0u};
         }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                mma_chunk<TagF16>(acc[mt][nt], ah[mt], bl[nt]);
+                mma_chunk<TagF16>(acc[mt][nt], al[mt], bh[nt]);
+                mma_chunk<TagF16>(acc[mt][nt], ah[mt], bh[nt]);
+            }
     }
-    conv_epilogue(a, acc, b, n0, ntl, x0, y0, lr, g);
+    conv_epilogue<4>(a, acc, b, n0, x0, y0, lr, g);
 }
 
 // ---- 3 x 3 convolutions of the split-f16 form, LDS-staged (conv_precision "f16x3": conv1b ... convPa / convDa; cin % 32 == 0, cout % 64 == 0).
-// The register-only form above is bound by its operand loads (PMC: matrix pipe 17 % busy at 1.7 waves per SIMD: every tap re-fetches its pixels from L2 and splits them
+// The register-only form is bound by its operand loads (PMC: matrix pipe 17 % busy at 1.7 waves per SIMD: every tap re-fetches its pixels from L2 and splits them
 // again).  Here a workgroup (4 waves = 8 rows x 32 pixels x 64 output channels, as above) stages the (8 + 2) x (32 + 2) pixel halo tile of ONE 32-channel chunk in LDS —
 // fetched once, split once into hi / lo f16 planes (43.5 KB), zero padding applied at staging — and the nine taps read their activation fragments from it (slot XOR pixel
 // bits 1..2: two-way, the minimum for a 16-byte read); the next chunk's pixels are requested into registers before the taps run.  Weights arrive as in the matcher's tail
@@ -266,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void sp_conv3x3_split_kernel(ConvArgs a) { 
             __syncthreads();                                   // every wave is past its last read of the tile
         }
     }
-    conv_epilogue(a, acc, b, n0, 4, x0, y0, lr, g);
+    conv_epilogue<4>(a, acc, b, n0, x0, y0, lr, g);
 }
 
 // conv1a (ref :127, :159): 1 -> 64 channels, 3x3, pad 1, ReLU, image [B][1][H][W] -> NHWC.  K = 9: plain VALU.
@@ -305,15 +222,7 @@ __global__ __launch_bounds__(256) void sp_scores_kernel(const float* logits, flo
     scores[((long long)b * h * 8 + i * 8 + (lane >> 3)) * (w * 8) + j * 8 + (lane & 7)] = e / sum;
 }
 
-// repack a conv weight [Cout][Cin][k][k] -> [k*k][Cout][Cin] (conv1a: [9][64])
-__global__ __launch_bounds__(256) void sp_pack_weight_kernel(const float* src, float* dst, int Cout, int Cin, int kk) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)Cout * Cin * kk;
-    if (i >= total) return;
-    const int t = (int)(i % kk), ci = (int)((i / kk) % Cin), co = (int)(i / ((long long)kk * Cin));
-    dst[((long long)t * Cout + co) * Cin + ci] = src[i];
-}
-
-// SPLIT form, hi = f16(w), lo = f16(w - hi).  1 x 1 layers: [2 planes][Cout][Cin] f16 (sp_conv_kernel<true>).  3 x 3 layers: MFMA-fragment order for
+// SPLIT form, hi = f16(w), lo = f16(w - hi).  1 x 1 layers: [2 planes][Cout][Cin] f16 (sp_conv1x1_split_kernel).  3 x 3 layers: MFMA-fragment order for
 // sp_conv3x3_split_kernel, [cout group of 64][32-channel chunk][tap][n-tile][plane][lane = 16 g + lr][8 f16]: lane (lr, g) of n-tile nt holds cout 64 grp + 16 nt + lr,
 // channels 32 c + 8 g .. + 7 — 1 KB per fragment, 8 KB per (chunk, tap) step.
 __global__ __launch_bounds__(256) void sp_pack_weight_split_kernel(const float* src, f16_t* dst, int Cout, int Cin, int kk) {
@@ -334,31 +243,31 @@ __global__ __launch_bounds__(256) void sp_pack_weight_split_kernel(const float* 
     }
 }
 
-hipError_t launch_sp_pack_weight_split(const float* src, void* dst, int Cout, int Cin, int k, hipStream_t s) {
+static hipError_t launch_sp_pack_weight_split(const float* src, void* dst, int Cout, int Cin, int k, hipStream_t s) {
     const long long total = (long long)Cout * Cin * k * k;
     hipLaunchKernelGGL(sp_pack_weight_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, static_cast<f16_t*>(dst), Cout, Cin, k * k);
     return hipGetLastError();
 }
 
-hipError_t launch_sp_pack_weight(const float* src, float* dst, int Cout, int Cin, int k, hipStream_t s) {
-    const long long total = (long long)Cout * Cin * k * k;
-    hipLaunchKernelGGL(sp_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, Cout, Cin, k * k);
-    return hipGetLastError();
+// repack a conv weight [Cout][Cin][k][k] -> [k*k][Cout][Cin] (conv1a: [9][64])
+static hipError_t launch_sp_pack_weight(const float* src, float* dst, int Cout, int Cin, int k, hipStream_t s) {
+    return launch_fold(src, dst, nullptr, Cout, Cin, k * k, PK_TAP_CO_CI, nullptr, nullptr, nullptr, s);
 }
 
 static void conv(bool split, const float* in, float* out, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, int taps, int relu, int pool,
                  int nchw, hipStream_t s) {
-    ConvArgs a{in, out, w, bias, B, H, W, Cin, Cout, taps, relu, pool, nchw};
+    const ConvArgs a{in, w, bias, nullptr, nullptr, out, B, H, W, Cin, 0, Cout, taps, relu ? ACT_RELU : ACT_NONE, pool, nchw};
     const dim3 grid((W + 31) / 32, (H + 7) / 8, B * ((Cout + 63) / 64));
-    if (split && taps == 9) hipLaunchKernelGGL(sp_conv3x3_split_kernel, grid, dim3(256), 0, s, a);      // (every 3 x 3 layer of the stack has cin % 32 == 0 and cout % 64 == 0)
-    else if (split) hipLaunchKernelGGL(sp_conv_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(sp_conv_kernel<false>, grid, dim3(256), 0, s, a);
+    if (!split) launch_conv(a, s);     // (every layer of the stack has cout >= 64: the 64-channel tile)
+    else if (taps == 9) hipLaunchKernelGGL(sp_conv3x3_split_kernel, grid, dim3(256), 0, s, a);      // (every 3 x 3 layer of the stack has cin % 32 == 0 and cout % 64 == 0)
+    else hipLaunchKernelGGL(sp_conv1x1_split_kernel, grid, dim3(256), 0, s, a);
 }
 
 // params: packed weight / bias pointers in layer order conv1a, conv1b, conv2a, conv2b, conv3a, conv3b, conv4a, conv4b, convPa, convPb,
 // convDa, convDb (24 device pointers).  ws: two ping-pong buffers of B*H*W*64 floats each.
 // split != 0: every MFMA convolution on split-f16 operands (weights packed by launch_sp_pack_weight_split; conv1a — K = 9, VALU — stays fp32 with its fp32 packing)
-hipError_t launch_sp_encode(const float* image, int B, int H, int W, const float* const* P, float* ws, float* scores, float* desc_map, int split_flag, hipStream_t s) {
+static hipError_t launch_sp_encode(const float* image, int B, int H, int W, const float* const* P, float* ws, float* scores, float* desc_map, int split_flag,
+                                   hipStream_t s) {
     const bool split = split_flag != 0;
     const long long half = (long long)B * H * W * 64;
     float* A = ws; float* Bf = ws + half;
@@ -385,3 +294,48 @@ hipError_t launch_sp_encode(const float* image, int B, int H, int W, const float
 }
 
 }  // namespace lg
+
+using namespace lg;
+
+extern "C" {
+
+int lg_sp_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t k, float* dst, void* hip_stream) {
+    if (!src || !dst || cout < 1 || cin < 1 || (k != 1 && k != 3)) return set_error(LG_ERR_INVALID, "bad conv weight");
+    HIPCHK(launch_sp_pack_weight(src, dst, cout, cin, k, static_cast<hipStream_t>(hip_stream)));
+    return LG_OK;
+}
+
+int64_t lg_sp_encode_workspace_bytes(int32_t batch, int32_t h, int32_t w) {
+    if (batch < 1 || h < 8 || w < 8) return 0;
+    return (int64_t)2 * batch * h * w * 64 * 4;
+}
+
+int lg_sp_encode(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
+                 int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
+    if (batch < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "image height / width must be at least 8");
+    if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
+    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
+    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
+    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 0, static_cast<hipStream_t>(hip_stream)));
+    return LG_OK;
+}
+
+int lg_sp_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t k, void* dst, void* hip_stream) {
+    if (!src || !dst || cout < 1 || cin < 32 || cin % 32 || (k != 1 && k != 3) || (k == 3 && cout % 64)) return set_error(LG_ERR_INVALID, "bad conv weight (split form: cin a multiple of 32; 3 x 3 layers: cout a multiple of 64)");
+    HIPCHK(launch_sp_pack_weight_split(src, dst, cout, cin, k, static_cast<hipStream_t>(hip_stream)));
+    return LG_OK;
+}
+
+int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
+                       int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
+    if (batch < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "image height / width must be at least 8");
+    // sp_conv3x3_split_kernel addresses the pixels of ONE image with 32-bit element offsets (h w 64 channels at full resolution)
+    if ((int64_t)h * w * 64 >= (int64_t)1 << 31) return set_error(LG_ERR_INVALID, "split-f16 conv stack: h * w must stay below 2^25 pixels (use conv_precision = fp32 for larger images)");
+    if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
+    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
+    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
+    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 1, static_cast<hipStream_t>(hip_stream)));
+    return LG_OK;
+}
+
+}  // extern "C"

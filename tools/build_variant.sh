@@ -9,8 +9,8 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$ROOT/build_variants/obj_$NAME"
 cd "${LG_VARIANT_SRC:-$ROOT/lightglue_amd/csrc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize"
-for f in lg_gemm lg_sim lg_tail lg_proj lg_attention lg_pointwise lg_adaptive lg_assign lg_superpoint lg_sp_encoder lg_engine; do
-  hipcc $FLAGS "$@" -c $f.hip -o "$ROOT/build_variants/obj_$NAME/$f.o" &
+for f in lg_*.hip; do
+  hipcc $FLAGS "$@" -c $f -o "$ROOT/build_variants/obj_$NAME/${f%.hip}.o" &
 done
 wait
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/build_variants/liblightglue_amd_$NAME.so" "$ROOT"/build_variants/obj_$NAME/*.o

@@ -38,6 +38,7 @@ CASES = {
     "n16_rgb_b2_64x96_top60": ("aliked-n16", 2, 2, 2, 3, 64, 96, {"detection_threshold": -1, "max_num_keypoints": 60}),
     "n16_gray_b1_96x128_fallback": ("aliked-n16", 3, 3, 1, 1, 96, 128, {"detection_threshold": 0.9999}),
     "n32_rgb_b1_240x320_limit300": ("aliked-n32", 4, 4, 1, 3, 240, 320, {"detection_threshold": 0.3, "max_num_keypoints": 300}),
+    "n16_rgb_b1_96x128_r6": ("aliked-n16", 8, 8, 1, 3, 96, 128, {"detection_threshold": 0.3, "nms_radius": 6}),
 }
 # ragged pair: two images of one size, each run by the reference on its own (its torch.stack needs equal counts), batched on the GPU
 RAGGED = {"n16_rgb_ragged_2x80x104": ("aliked-n16", 5, (6, 7), 3, 80, 104, {"detection_threshold": 0.45})}
