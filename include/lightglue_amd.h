@@ -301,6 +301,42 @@ int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos);
 int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
                        const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
 
+/* ---- ImagePreprocessor (lightglue/utils.py:12-38): the resize in front of the extractors, one fused kernel (lg_preprocess.hip) ----
+ * What the reference computes through kornia.geometry.transform.resize (always bilinear: `interpolation` is not forwarded):
+ *   target size   `resize` = one edge length s + side, with ar = w / h in double: VERT (s, int(s ar)); HORZ (int(s / ar), s); LONG / SHORT:
+ *                 (s, int(s ar)) if (side == SHORT) ^ (ar < 1) else (int(s / ar), s) — or an explicit (h, w) pair.  Target == input: identity.
+ *   antialias     only if requested and max(h / h_out, w / w_out) > 1: per axis sigma = max((factor - 1) / 2, 0.001), ks = int(max(4 sigma, 3))
+ *                 made odd, normalised Gaussian taps, separable blur x then y on the image reflect-padded by ks / 2
+ *   bilinear      ATen's float rule: scale = float(in) / out (align_corners: (in - 1) / (out - 1)); src = max(scale (dst + 0.5f) - 0.5f, 0);
+ *                 i0 = int(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1 — in fp32, the coordinate expression not contracted
+ * lg_preprocess_plan is host-only arithmetic (no GPU, no HIP call): it fills the plan or refuses.  resize_w = LG_RESIZE_EDGE: resize_h is the
+ *   edge length and `side` applies; otherwise (resize_h, resize_w) is the target and `side` is ignored (it must still be a valid value).
+ * lg_preprocess_resize: src [batch][channels][h][w] addressed through four ELEMENT strides (a channels-last view or a crop is read in place),
+ *   float32 or uint8 (converted as float(v) / 255.0f, a true division: the reference's numpy_image_to_torch bit for bit) ->
+ *   dst [batch][channels][h_out][w_out] float32 contiguous.  An identity plan is a strided copy / conversion.  Asynchronous on `hip_stream`,
+ *   no allocation, no workspace.
+ * Envelope — anything outside returns LG_ERR_INVALID with a message before the GPU is touched:
+ *   channels 1 or 3; batch <= 65535; every side (input and target) in [1, LG_PREPROCESS_MAX_SIDE];
+ *   ks <= LG_PREPROCESS_MAX_TAPS per axis (antialiased downscale factors up to ~17; without antialias any factor);
+ *   ks / 2 < the axis length (torch's reflect-pad rule);  strides >= 0 and one image spanning fewer than 2^31 elements (32-bit offsets). */
+#define LG_PREPROCESS_MAX_TAPS 33
+#define LG_PREPROCESS_MAX_SIDE 8388608   /* 2^23: dst + 0.5f is exact in fp32 below it */
+#define LG_RESIZE_EDGE (-1)
+enum { LG_SIDE_LONG = 0, LG_SIDE_SHORT = 1, LG_SIDE_VERT = 2, LG_SIDE_HORZ = 3 };
+enum { LG_DTYPE_F32 = 0, LG_DTYPE_U8 = 1 };
+typedef struct lg_resize_plan {
+    int32_t h_in, w_in, h_out, w_out;
+    int32_t ks_y, ks_x;          /* blur taps per axis, odd; 1 = no blur                                   */
+    int32_t align_corners;
+    int32_t identity;            /* target == input size (the reference returns its input)                 */
+    double sigma_y, sigma_x;     /* 0 where ks = 1                                                         */
+    double scale_x, scale_y;     /* w_out / w_in, h_out / h_in: the `scale` ImagePreprocessor returns      */
+} lg_resize_plan;
+int lg_preprocess_plan(int32_t h, int32_t w, int32_t resize_h, int32_t resize_w, int32_t side, int32_t antialias, int32_t align_corners,
+                       lg_resize_plan* plan);
+int lg_preprocess_resize(const void* src, int32_t dtype, int32_t batch, int32_t channels, int32_t h, int32_t w, int64_t stride_b,
+                         int64_t stride_c, int64_t stride_y, int64_t stride_x, const lg_resize_plan* plan, float* dst, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

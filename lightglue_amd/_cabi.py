@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "lg_sp_pack_conv_weight", "lg_sp_encode_workspace_bytes", "lg_sp_encode", "lg_sp_pack_conv_weight_split", "lg_sp_encode_split", "lg_debug_mfma_sustained",
     "lg_aliked_packed_bytes", "lg_aliked_pack_weights", "lg_aliked_levels_bytes", "lg_aliked_workspace_bytes", "lg_aliked_encode",
     "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
+    "lg_preprocess_plan", "lg_preprocess_resize",
 )
 
 
@@ -69,6 +70,21 @@ class LgUnpackIO(C.Structure):
         ("prune0_i64", _fp), ("prune1_i64", _fp), ("prune0_f32", _fp), ("prune1_f32", _fp),
         ("matches", _fp), ("match_scores", _fp),
         ("info", _fp),
+    ]
+
+
+# lg_preprocess_plan / lg_preprocess_resize (include/lightglue_amd.h)
+LG_PREPROCESS_MAX_TAPS, LG_PREPROCESS_MAX_SIDE, LG_RESIZE_EDGE = 33, 2 ** 23, -1
+LG_SIDE = {"long": 0, "short": 1, "vert": 2, "horz": 3}
+LG_DTYPE_F32, LG_DTYPE_U8 = 0, 1
+
+
+class LgResizePlan(C.Structure):
+    """lg_resize_plan (include/lightglue_amd.h)"""
+    _fields_ = [
+        ("h_in", C.c_int32), ("w_in", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
+        ("ks_y", C.c_int32), ("ks_x", C.c_int32), ("align_corners", C.c_int32), ("identity", C.c_int32),
+        ("sigma_y", C.c_double), ("sigma_x", C.c_double), ("scale_x", C.c_double), ("scale_y", C.c_double),
     ]
 
 
@@ -143,6 +159,8 @@ def load() -> C.CDLL:
     lib.lg_aliked_describe_workspace_bytes.argtypes = [C.c_int32] * 2
     lib.lg_aliked_describe_workspace_bytes.restype = C.c_int64
     lib.lg_aliked_describe.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.lg_preprocess_plan.argtypes = [C.c_int32] * 7 + [C.POINTER(LgResizePlan)]
+    lib.lg_preprocess_resize.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_int64] * 4 + [C.POINTER(LgResizePlan), C.c_void_p, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

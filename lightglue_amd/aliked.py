@@ -5,7 +5,7 @@ Same module tree / parameter names as the reference class (`lightglue/aliked.py:
 `load_state_dict(strict=True)`, and the same `forward({"image"[, "image_size"]})` contract (`:740-760`).  Everything runs in
 `lightglue_amd/csrc/lg_aliked.hip` behind the `lg_aliked_*` C entry points: the encoder, aggregation and score head
 (`lg_aliked_encode`), DKD (`lg_aliked_detect`) and SDDH (`lg_aliked_describe`), all exact fp32.  No CPU fallback.  As for
-SuperPoint, image resizing (`ImagePreprocessor`) is out of scope: `extract()` takes an already sized image."""
+SuperPoint, `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`) and maps the keypoints back."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +16,8 @@ import torch
 from torch import nn
 
 from . import _cabi
+from .glue import extracted_to_image_frame
+from .preprocess import ImagePreprocessor
 
 
 class DeformableConv2d(nn.Module):
@@ -235,14 +237,22 @@ class ALIKED(nn.Module):
         desc = self.describe(levels, (bsz, h, w), knorm, counts)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}
 
+    preprocess_conf = {"resize": None}   # NOT the reference's 1024 (aliked.py:631-633): see extract()
+
     @torch.no_grad()
     def extract(self, img: torch.Tensor, **conf) -> dict:
-        """ref utils.py:136-147 WITHOUT the resize step (as SuperPoint.extract): the image is used at its own size, keypoints are in its pixel
-        frame, and `image_size` = (w, h) is attached for the matcher."""
+        """Perform extraction with online resizing (ref utils.py:136-147): ImagePreprocessor(**{**self.preprocess_conf, **conf}) on the device
+        (lightglue_amd/preprocess.py: one HIP kernel), forward on the resized image, keypoints mapped back to the original image's pixel frame,
+        `(k + 0.5) / scale - 0.5`, and `image_size` = the ORIGINAL (w, h).  Deliberate difference: `preprocess_conf["resize"]` is None here, not the
+        reference's 1024, so `extract(img)` keeps using the image at its own size (and returns exactly what it did before resizing existed);
+        the upstream behaviour is one keyword away: `extract(img, resize=1024)`, `match_pair(..., resize=1024)`."""
         if img.dim() == 3:
             img = img[None]
         assert img.dim() == 4 and img.shape[0] == 1
-        feats = self.forward({"image": img})
         h, w = img.shape[-2:]
+        resized, scales = ImagePreprocessor(**{**self.preprocess_conf, **conf})(img)
+        feats = self.forward({"image": resized})
+        if tuple(resized.shape[-2:]) != (h, w):
+            return extracted_to_image_frame(feats, (h, w), scales)
         feats["image_size"] = torch.tensor([[w, h]], dtype=torch.float32, device=img.device)
         return feats

@@ -1,7 +1,9 @@
 """Extractor -> matcher plumbing: behaviour of the reference's `rbd`, `batch_to_device` and
-`match_pair` helpers (reference `lightglue/utils.py:55-69, 150-165`), written for this package.  Image IO, resizing
-and extractor classes are out of scope; `match_pair` accepts any object with the reference's
-`extract(image, **preprocess) -> dict` contract (`lightglue/utils.py:136-147`)."""
+`match_pair` helpers (reference `lightglue/utils.py:55-69, 150-165`), written for this package.  `match_pair` accepts any object
+with the reference's `extract(image, **preprocess) -> dict` contract (`lightglue/utils.py:136-147`); this package's extractors honour
+`**preprocess` (`resize=`, `side=`, `antialias=`, `align_corners=`) through `preprocess.ImagePreprocessor` on the device.  Image file
+I/O is out of scope.  `extracted_to_image_frame` is the keypoint / image_size step of `extract` on its own, for callers who resized by
+other means."""
 from __future__ import annotations
 
 from typing import Any, Callable, Dict

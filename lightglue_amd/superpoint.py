@@ -4,8 +4,8 @@ Same module tree / parameter names as the reference class (`lightglue/superpoint
 released `superpoint_v1.pth` loads with `load_state_dict` unchanged, and the same `forward({"image": ...})` contract
 (`:147-232`).  Everything runs in `lightglue_amd/csrc/`: the conv stack as exact-fp32 MFMA implicit GEMMs
 (`lg_sp_encoder.hip`, `lg_sp_encode`), keypoint extraction (`lg_sp_detect`: NMS, borders, threshold, top-k) and the
-descriptor head (`lg_sp_sample_descriptors`).  No CPU fallback.  Image IO / resizing (`ImagePreprocessor`, kornia) stay out of
-scope: `extract()` takes an already sized image; `glue.extracted_to_image_frame` maps keypoints back if the caller resized."""
+descriptor head (`lg_sp_sample_descriptors`).  No CPU fallback.  `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`,
+`lg_preprocess.hip`) and maps the keypoints back like the reference's `Extractor.extract`; image FILE I/O (cv2) stays out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +16,8 @@ import torch
 from torch import nn
 
 from . import _cabi
+from .glue import extracted_to_image_frame
+from .preprocess import ImagePreprocessor
 from .superpoint_head import descriptor_head, detect_keypoints
 
 _LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
@@ -122,16 +124,22 @@ class SuperPoint(nn.Module):
         desc = descriptor_head(kpts, dense, 8, counts)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}   # counts: consumed by LightGlue.forward
 
+    preprocess_conf = {"resize": None}   # NOT the reference's 1024 (superpoint.py:115-117): see extract()
+
     @torch.no_grad()
     def extract(self, img: torch.Tensor, **conf) -> dict:
-        """ref utils.py:136-147 WITHOUT the resize step: the reference's Extractor.extract first resizes the long side to 1024
-        (ImagePreprocessor, kornia — out of scope here); this method uses the image at its own size, so on the same file it
-        detects at a different scale than the reference unless the caller resizes first.  scales = 1, the keypoints already live
-        in the image's pixel frame; `image_size` = (w, h) is attached for the matcher."""
+        """Perform extraction with online resizing (ref utils.py:136-147): ImagePreprocessor(**{**self.preprocess_conf, **conf}) on the device
+        (lightglue_amd/preprocess.py: one HIP kernel), forward on the resized image, keypoints mapped back to the original image's pixel frame,
+        `(k + 0.5) / scale - 0.5`, and `image_size` = the ORIGINAL (w, h).  Deliberate difference: `preprocess_conf["resize"]` is None here, not the
+        reference's 1024, so `extract(img)` keeps using the image at its own size (and returns exactly what it did before resizing existed);
+        the upstream behaviour is one keyword away: `extract(img, resize=1024)`, `match_pair(..., resize=1024)`."""
         if img.dim() == 3:
             img = img[None]
         assert img.dim() == 4 and img.shape[0] == 1
-        feats = self.forward({"image": img})
         h, w = img.shape[-2:]
+        resized, scales = ImagePreprocessor(**{**self.preprocess_conf, **conf})(img)
+        feats = self.forward({"image": resized})
+        if tuple(resized.shape[-2:]) != (h, w):
+            return extracted_to_image_frame(feats, (h, w), scales)
         feats["image_size"] = torch.tensor([[w, h]], dtype=torch.float32, device=img.device)
         return feats
