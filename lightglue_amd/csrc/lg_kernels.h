@@ -7,7 +7,7 @@
 
 namespace lg {
 
-// the error every C entry point reports: sets the message lg_last_error() returns (lg_engine.hip) and returns `code`
+// the error every C entry point reports: sets the message lg_last_error() returns (lg_api.hip) and returns `code`
 int set_error(int code, const std::string& msg);
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -227,5 +227,34 @@ struct AssignArgs {
     int all_rows_live; // 1: len == n for every segment (no pruning ever, no ragged counts): the -1 / 0 pre-fill of m/s is skipped
 };
 hipError_t launch_assign(const AssignArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- forward state and outputs (lg_outputs.hip)
+// The first kernel of every forward: per-pair lengths (num0 / num1 clamped to [0, n]; nullptr = n), live flags, the layer each pair ends at, the prune
+// counters (1 per keypoint, 0 on padding rows), and the zeroed range / gather-set / device-error words.  Any output pointer may be nullptr (len == nullptr
+// skips the whole per-pair state: the empty-image result).
+struct InitStateArgs {
+    int B, n0, n1, L;
+    const int* num0; const int* num1;
+    int* len; int* len_orig; int* len_old; int* active; int* final_layer;
+    int* prune0; int* prune1;
+    int* range_flag; int* device_err; int* xsel;
+};
+hipError_t launch_init_state(const InitStateArgs& a, hipStream_t s);
+// The last kernel of every forward: `stop` (ref :604 / :575), and — round-5 extension of lg_forward_io — the outputs in the reference's own dtypes
+// (int64 indices ref :619-629, float prune0/1 without pruning ref :616-617), the packed wire row of the pair-sharded path, and the per-pair status.
+// Replaces the framework kernels the Python shim ran behind the forward (one `.long()` over the int32 block, `torch.full`, the ragged masks) and the
+// five slice copies of parallel.py's pack.  grid (ceil(span / 256), B), span = max(n0, n1, 2 * min(n0, n1)).
+struct OutArgs {
+    int B, n0, n1, L, kmax;
+    const int* final_layer; int stop_const;   // final_layer == nullptr: every pair's stop is stop_const (an empty image: 1)
+    int* stop;
+    const int* m0; const int* m1; const float* s0; const float* s1; const int* matches; const int* n_matches;
+    const int* prune0; const int* prune1; const int* num0; const int* num1;
+    long long* m0_64; long long* m1_64; long long* matches_64; long long* stop_64; long long* prune0_64; long long* prune1_64;
+    float* prune0_f; float* prune1_f;
+    int* wire; long long wire_stride; int wire_prune;   // wire_prune: the row's prune block carries the int counters (else the float fill's bits)
+    int* status; const int* range_flag; const int* device_err;
+};
+hipError_t launch_write_outputs(const OutArgs& a, hipStream_t s);
 
 }  // namespace lg

@@ -57,7 +57,7 @@ template <int PREC> struct PJL {   // LDS geometry of the activation tile
 // Which n-tile of the packed weights slot j of pass `pass` is for wave w, and of which kind.  Self (768 columns = q | k | v groups of
 // 16 n-tiles, NTP = 3): pass p = the wave's PAIR of adjacent tiles of group p (q, then k) + one v tile; cross (512 columns = qk | v,
 // NTP = 2): pass 0 = the qk pair, pass 1 = two v tiles.  A q / k pair is the two tiles 2w, 2w + 1 of its group = 32 consecutive head
-// channels, and the host packs their 32 weight rows so that MFMA row 4g + r of tile e holds channel 8g + 4e + r (lg_engine.hip
+// channels, and the host packs their 32 weight rows so that MFMA row 4g + r of tile e holds channel 8g + 4e + r (lg_weights.hip
 // proj_row_permutation): in the transposed form lane (lr, g) then ends with 8 CONSECUTIVE channels 8g .. 8g + 7 of keypoint row lr —
 // one 16-byte store per plane instead of two 8-byte ones (the projection epilogues were store-issue bound: 48 dwordx2 stores per wave).
 // Keypoint ROWS are dealt the same way between pairs of 16-row tiles (MT >= 2): MFMA row slot i of m-tile 2q + e is keypoint row
