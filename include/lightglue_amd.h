@@ -40,6 +40,8 @@ enum {
 #define LG_ERR_RANGE 4     /* LG_FLAG_CHECK_FINITE: a value of this pair's residual stream or of its q / k / v left the f16 operand range
                               (|x| >= 65504, inf or NaN: the input domain of LG_PREC_F16X3 / _F16 / _BF16); its scores are not to be trusted */
 #define LG_ERR_DEVICE 5    /* an internal device-side wait expired (adaptive compaction): results of this forward are invalid */
+#define LG_ERR_INDEX 6     /* LG_FLAG_INDEXED: index0[b] or index1[b] of this pair lies outside [0, images): nothing was read through it and the pair came
+                              back as an empty pair (stop 1, matches -1, scores 0).  Reported before LG_ERR_RANGE; LG_ERR_DEVICE stays on top */
 
 /* Envelope of one lg_engine_forward / lg_engine_reserve call (round 6).  Inside it every index of every kernel fits the integer type it is
  * computed in, and the largest shapes are covered by GPU tests (N = M = 8192, B = 1; N = M = 4096, B = 32); a call outside it returns
@@ -83,6 +85,9 @@ typedef struct lg_engine lg_engine;
 #define LG_FLAG_CHECK_FINITE 4u /* range guard (needs LG_FLAG_EXT and `status`): every fused tail and q/k/v projection also tests the
                                  values it is about to split into f16 planes — one compare per value — and flags the pair           */
 
+#define LG_FLAG_INDEXED 8u    /* the inputs are feature STORES and `index0` / `index1` (the last fields of the struct) say which image of them each pair
+                                 reads: see there.  Needs LG_FLAG_EXT and `status`                                      */
+
 typedef struct lg_forward_io {
     int32_t batch, n0, n1;
     uint32_t flags;                        /* LG_FLAG_*                                           */
@@ -101,7 +106,7 @@ typedef struct lg_forward_io {
      * lightglue.py:46-55, :512-520): optional per-pair keypoint counts, num0[b] <= n0, num1[b] <= n1.
      * Rows >= num of the dense inputs are never read; their outputs are -1 / 0 (prune counters 0).
      * Each pair behaves exactly as a separate B=1 call on its first num rows.  NULL = all rows live. */
-    const int32_t *num0, *num1;            /* [B] or NULL                                         */
+    const int32_t *num0, *num1;            /* [B] or NULL (LG_FLAG_INDEXED: [images])             */
     /* Optional side output: the full log-assignment matrix of
      * sigmoid_log_double_softmax (lightglue.py:265-277) INCLUDING the dustbin row / column, in ORIGINAL
      * keypoint index space: [B][n0+1][n1+1] fp32.  Rows / columns of keypoints that were pruned (or are
@@ -124,7 +129,16 @@ typedef struct lg_forward_io {
      * prune0/1 are the int32 counters when this forward prunes, else the bit patterns of the reference's float fill (n_layers, lightglue.py:616-617; 0 on
      * the padding rows of a ragged batch).  Row stride wire_stride >= LG_WIRE_WIDTH(n0, n1) elements.  lg_unpack_wire() is the inverse on the receiving side. */
     int32_t *wire; int64_t wire_stride;
-    int32_t *status;                       /* [B] LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE per pair                       */
+    int32_t *status;                       /* [B] LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE / LG_ERR_INDEX per pair        */
+    /* ---- indexed inputs: read only when flags & LG_FLAG_INDEXED (together with LG_FLAG_EXT; callers built against the header without them keep working) ----
+     * A pair list over feature stores, matched in place.  With the flag set, kpts0 / desc0 / scales0 / oris0 are [images0][n0][..], size0 is [images0][2] and num0 is
+     * [images0]: per IMAGE, not per pair, and pair b reads image index0[b] of them; side 1 likewise through index1 / images1 (both sides may point at the same
+     * store).  `batch` stays the number of PAIRS of the call and the envelope above applies to batch, n0, n1 as before; offsets into a store are 64-bit, so the
+     * number of images is not limited.  Every output stays per pair.  The engine checks 0 <= index < images on the device before it reads through an index: a pair
+     * that fails on either side is an empty pair with status LG_ERR_INDEX, so no index value can make the engine read outside a store.  The forward is bit-identical
+     * to one on the gathered [batch][n][..] tensors. */
+    const int32_t *index0, *index1;        /* [B] image of the store that pair b reads on side 0 / side 1             */
+    int32_t images0, images1;              /* images in the store of side 0 / side 1, >= 1                            */
 } lg_forward_io;
 
 /* Last error message of the calling thread (never NULL). */

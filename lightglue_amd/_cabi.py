@@ -15,8 +15,9 @@ from pathlib import Path
 _LIB_PATH = Path(os.environ.get("LIGHTGLUE_AMD_LIB") or Path(__file__).resolve().parent / "liblightglue_amd.so")
 
 LG_PREC = {"fp32": 0, "bf16": 1, "fp16": 2, "f16x3": 4}   # include/lightglue_amd.h LG_PREC_* (3 was split-bf16, removed in round 3)
-LG_OK, LG_ERR_INVALID, LG_ERR_HIP, LG_ERR_STATE, LG_ERR_RANGE, LG_ERR_DEVICE = 0, 1, 2, 3, 4, 5
-LG_FLAG_NO_PRUNING, LG_FLAG_EXT, LG_FLAG_CHECK_FINITE = 1, 2, 4
+LG_OK, LG_ERR_INVALID, LG_ERR_HIP, LG_ERR_STATE, LG_ERR_RANGE, LG_ERR_DEVICE, LG_ERR_INDEX = 0, 1, 2, 3, 4, 5, 6
+LG_FLAG_NO_PRUNING, LG_FLAG_EXT, LG_FLAG_CHECK_FINITE, LG_FLAG_INDEXED = 1, 2, 4, 8
+LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
 # every symbol include/lightglue_amd.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -56,6 +57,8 @@ class LgForwardIO(C.Structure):
         ("matches0_i64", _fp), ("matches1_i64", _fp), ("matches_i64", _fp), ("stop_i64", _fp),
         ("prune0_i64", _fp), ("prune1_i64", _fp), ("prune0_f32", _fp), ("prune1_f32", _fp),
         ("wire", _fp), ("wire_stride", C.c_int64), ("status", _fp),
+        # indexed inputs (read only when flags & LG_FLAG_INDEXED)
+        ("index0", _fp), ("index1", _fp), ("images0", C.c_int32), ("images1", C.c_int32),
     ]
 
 

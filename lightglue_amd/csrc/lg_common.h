@@ -191,6 +191,18 @@ __device__ __forceinline__ int seg_row_base(const RowSpace& rs, int seg) {
     return (seg >> 1) * (rs.cap0 + rs.cap1) + (seg & 1) * rs.cap0;
 }
 
+// ---- source images of a pair (LG_FLAG_INDEXED): the inputs of the forward are per-IMAGE arrays (a feature store) and pair b reads image index0[b] /
+// index1[b] of them.  All zero = not indexed: pair b reads image b of either side.
+struct PairIndex { const int* index0; const int* index1; int images0, images1; };
+// The image `pair` reads on side `image`, or -1 when the index of EITHER side lies outside its store: such a pair is empty (init_state_kernel gives both of
+// its segments length 0), so no kernel forms an input address from it.  Uniform per workgroup wherever it is used: one or two scalar loads.
+__device__ __forceinline__ int source_image(const PairIndex& px, int pair, int image) {
+    if (!px.index0) return pair;
+    const int s0 = px.index0[pair], s1 = px.index1[pair];
+    if ((unsigned)s0 >= (unsigned)px.images0 || (unsigned)s1 >= (unsigned)px.images1) return -1;
+    return image ? s1 : s0;
+}
+
 // Workgroup id runs on XCD id % 8 (round-robin dispatch; tools/tail_wall.py: 1024 of 1024).  For a kernel whose tiles share nothing (the
 // fused tail) the identity map hands XCD x every tile = x (mod 8), i.e. one fixed residue of the address bits above the 64 KB tile size,
 // for the whole launch — and when the live tiles of a ragged / pruned / partly stopped batch have a period that is a multiple of 8 tiles

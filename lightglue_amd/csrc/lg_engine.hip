@@ -152,6 +152,9 @@ int tail_row_tiles_for(int R) {
 }
 
 bool pruning_on(const lg_engine* e, const lg_forward_io* io) { return e->cfg.width_confidence > 0 && !(io->flags & LG_FLAG_NO_PRUNING); }
+// LG_FLAG_INDEXED: the index fields sit behind the round-5 extension, so they are read only when both flags are set (check_forward_io refuses one without the other)
+bool indexed(const lg_forward_io* io) { return (io->flags & LG_FLAG_EXT) && (io->flags & LG_FLAG_INDEXED); }
+PairIndex pair_index(const lg_forward_io* io) { return indexed(io) ? PairIndex{io->index0, io->index1, io->images0, io->images1} : PairIndex{}; }
 
 int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if (!e || !io) return set_error(LG_ERR_INVALID, "null argument");
@@ -168,6 +171,11 @@ int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if (e->cfg.add_scale_ori && (!io->scales0 || !io->oris0 || !io->scales1 || !io->oris1)) return set_error(LG_ERR_INVALID, "scales/oris required");
     const bool ext = (io->flags & LG_FLAG_EXT) != 0;            // round-5 extension fields present
     if ((io->flags & LG_FLAG_CHECK_FINITE) && (!ext || !io->status)) return set_error(LG_ERR_INVALID, "LG_FLAG_CHECK_FINITE needs LG_FLAG_EXT and a status array");
+    if (io->flags & LG_FLAG_INDEXED) {
+        if (!ext || !io->status) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED needs LG_FLAG_EXT and a status array");
+        if (!io->index0 || !io->index1) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED: null index0 / index1");
+        if (io->images0 < 1 || io->images1 < 1) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED: images0 and images1 must be at least 1");
+    }
     if (ext && io->wire && io->wire_stride < LG_WIRE_WIDTH(n0, n1)) return set_error(LG_ERR_INVALID, "wire_stride < LG_WIRE_WIDTH(n0, n1) = 3 n0 + 3 n1 + 2");
     if (ext && do_prune && ((io->prune0_f32 || io->prune1_f32))) return set_error(LG_ERR_INVALID, "prune0_f32 / prune1_f32 are the outputs of a forward WITHOUT pruning");
     if (ext && !do_prune && ((io->prune0_i64 || io->prune1_i64))) return set_error(LG_ERR_INVALID, "prune0_i64 / prune1_i64 are the outputs of a forward WITH pruning");
@@ -185,6 +193,7 @@ hipError_t write_outputs(const lg_engine* e, const lg_forward_io* io, const int*
         o.m0_64 = (long long*)io->matches0_i64; o.m1_64 = (long long*)io->matches1_i64; o.matches_64 = (long long*)io->matches_i64; o.stop_64 = (long long*)io->stop_i64;
         o.prune0_64 = (long long*)io->prune0_i64; o.prune1_64 = (long long*)io->prune1_i64; o.prune0_f = io->prune0_f32; o.prune1_f = io->prune1_f32;
         o.wire = io->wire; o.wire_stride = io->wire_stride; o.wire_prune = pruning_on(e, io) ? 1 : 0; o.status = io->status; o.range_flag = range_flag; o.device_err = device_err;
+        o.px = pair_index(io);
     }
     return launch_write_outputs(o, s);
 }
@@ -196,7 +205,7 @@ int forward_empty(const lg_engine* e, const lg_forward_io* io, hipStream_t s) {
     if (n1) { HIPCHK(hipMemsetAsync(io->matches1, 0xFF, sizeof(int) * (size_t)B * n1, s)); HIPCHK(hipMemsetAsync(io->scores1, 0, 4 * (size_t)B * n1, s)); }
     HIPCHK(hipMemsetAsync(io->n_matches, 0, sizeof(int) * (size_t)B, s));
     InitStateArgs is{};   // the prune counters alone
-    is.B = B; is.n0 = n0; is.n1 = n1; is.L = e->cfg.n_layers;
+    is.B = B; is.n0 = n0; is.n1 = n1; is.L = e->cfg.n_layers; is.px = pair_index(io);
     if (pruning_on(e, io)) { is.prune0 = n0 ? io->prune0 : nullptr; is.prune1 = n1 ? io->prune1 : nullptr; }
     HIPCHK(launch_init_state(is, s));
     HIPCHK(write_outputs(e, io, nullptr, 1, nullptr, nullptr, s));   // stop = 1 for every pair (+ the extension outputs of an empty result)
@@ -224,13 +233,13 @@ int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
 
     int* const device_err = e->CFLAGS + (size_t)2 * B * compact_chunks(c0, c1);   // error word + compaction ticket behind the chunk flags (lg_adaptive.hip)
     const InitStateArgs is{B, n0, n1, L, io->num0, io->num1, e->LEN, e->LEN_ORIG, e->LEN_OLD, e->ACTIVE, e->FINAL_LAYER,
-                           do_prune ? io->prune0 : nullptr, do_prune ? io->prune1 : nullptr, e->RANGEF, device_err, e->XSEL};
+                           do_prune ? io->prune0 : nullptr, do_prune ? io->prune1 : nullptr, e->RANGEF, device_err, e->XSEL, pair_index(io)};
     HIPCHK(launch_init_state(is, s));
     int* const range_flag = check_finite ? e->RANGEF : nullptr;
     // prep (+ descriptor copy) as its own launch, or — input_dim == 256, no debug stop — inside the first projection launch (lg_proj.hip proj_first_kernel)
     const bool fuse_prep = e->fused_prep && e->cfg.input_dim == D && e->debug_stop < 0 && e->tail_timing != 2;
     PrepArgs p{};
-    p.rs = rs_all; p.n0 = n0; p.n1 = n1; p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
+    p.rs = rs_all; p.n0 = n0; p.n1 = n1; p.px = pair_index(io); p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
     p.scales0 = io->scales0; p.oris0 = io->oris0; p.scales1 = io->scales1; p.oris1 = io->oris1;
     p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
     p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim;
@@ -442,7 +451,7 @@ int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
         as.matches = io->matches; as.mscores = io->match_scores; as.n_matches = io->n_matches; as.max_matches = max_matches;
         as.log_assignment = io->log_assignment; as.lsneg = e->LSNEG;
         as.dbg = e->tail_timing == 4 ? e->TAILDBG : nullptr;
-        as.all_rows_live = (!do_prune && !io->num0 && !io->num1) ? 1 : 0;
+        as.all_rows_live = (!do_prune && !io->num0 && !io->num1 && !indexed(io)) ? 1 : 0;   // indexed: a pair whose index is out of range has no live row
         PROFILED(PC_ASSIGN, launch_assign(as, s));
         HIPCHK(write_outputs(e, io, e->FINAL_LAYER, 0, range_flag, device_err, s));
     }

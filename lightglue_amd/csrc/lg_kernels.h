@@ -147,6 +147,7 @@ hipError_t launch_attention(int attn_prec, const AttnArgs& a, hipStream_t s);
 struct PrepArgs {
     RowSpace rs;
     int n0, n1;                    // dense input row counts per image (input tensors are [B][n][..])
+    PairIndex px;                  // indexed inputs: every input array below is per IMAGE of a store and pair b reads image source_image(px, b, side)
     const float* kpts0; const float* kpts1;      // [B][n][2] pixels
     const float* size0; const float* size1;      // [B][2] (w,h) or nullptr -> bbox
     const float* scales0; const float* oris0; const float* scales1; const float* oris1;  // [B][n] or nullptr
@@ -238,6 +239,7 @@ struct InitStateArgs {
     int* len; int* len_orig; int* len_old; int* active; int* final_layer;
     int* prune0; int* prune1;
     int* range_flag; int* device_err; int* xsel;
+    PairIndex px;             // indexed inputs: num0 / num1 are per image; a pair whose index is out of range starts (and ends) with both lengths 0
 };
 hipError_t launch_init_state(const InitStateArgs& a, hipStream_t s);
 // The last kernel of every forward: `stop` (ref :604 / :575), and — round-5 extension of lg_forward_io — the outputs in the reference's own dtypes
@@ -254,6 +256,7 @@ struct OutArgs {
     float* prune0_f; float* prune1_f;
     int* wire; long long wire_stride; int wire_prune;   // wire_prune: the row's prune block carries the int counters (else the float fill's bits)
     int* status; const int* range_flag; const int* device_err;
+    PairIndex px;             // indexed inputs: num0 / num1 are per image; an index out of range is the pair's status LG_ERR_INDEX
 };
 hipError_t launch_write_outputs(const OutArgs& a, hipStream_t s);
 

@@ -8,6 +8,11 @@ namespace {
 
 // keypoints of image `pair` of a ragged batch: num[pair] clamped to [0, n]; num == nullptr: n
 __device__ __forceinline__ int count(const int* num, int pair, int n) { int v = num ? num[pair] : n; return v < 0 ? 0 : (v > n ? n : v); }
+// the same through the pair's source image (indexed inputs: num is per image); 0 on both sides for a pair whose index is out of range
+__device__ __forceinline__ int count(const int* num, const PairIndex& px, int pair, int image, int n) {
+    const int src = source_image(px, pair, image);
+    return src < 0 ? 0 : count(num, src, n);
+}
 
 __global__ void init_state_kernel(InitStateArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, B = a.B, n0 = a.n0, n1 = a.n1;
@@ -15,7 +20,7 @@ __global__ void init_state_kernel(InitStateArgs a) {
     if (a.xsel && i < B) a.xsel[i] = 0;
     if (a.device_err && i == 0) *a.device_err = 0;
     if (a.len && i < B) {
-        const int l0 = count(a.num0, i, n0), l1 = count(a.num1, i, n1);
+        const int l0 = count(a.num0, a.px, i, 0, n0), l1 = count(a.num1, a.px, i, 1, n1);
         a.len[2 * i] = l0; a.len[2 * i + 1] = l1; a.len_orig[2 * i] = l0; a.len_orig[2 * i + 1] = l1;
         a.len_old[2 * i] = -1; a.len_old[2 * i + 1] = -1;
         // a pair with an empty image never enters the layer loop: stop = 1, empty result (ref :539-540, :568-588)
@@ -23,8 +28,8 @@ __global__ void init_state_kernel(InitStateArgs a) {
         a.active[i] = live; a.final_layer[i] = live ? a.L - 1 : 0;
     }
     // prune counters start at 1 for every keypoint (ref :535-536); padding rows of a ragged batch get 0
-    if (a.prune0) for (long long k = i; k < (long long)B * n0; k += (long long)gridDim.x * blockDim.x) a.prune0[k] = (int)(k % n0) < count(a.num0, (int)(k / n0), n0);
-    if (a.prune1) for (long long k = i; k < (long long)B * n1; k += (long long)gridDim.x * blockDim.x) a.prune1[k] = (int)(k % n1) < count(a.num1, (int)(k / n1), n1);
+    if (a.prune0) for (long long k = i; k < (long long)B * n0; k += (long long)gridDim.x * blockDim.x) a.prune0[k] = (int)(k % n0) < count(a.num0, a.px, (int)(k / n0), 0, n0);
+    if (a.prune1) for (long long k = i; k < (long long)B * n1; k += (long long)gridDim.x * blockDim.x) a.prune1[k] = (int)(k % n1) < count(a.num1, a.px, (int)(k / n1), 1, n1);
 }
 __global__ __launch_bounds__(256) void write_outputs_kernel(OutArgs a) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
@@ -32,7 +37,8 @@ __global__ __launch_bounds__(256) void write_outputs_kernel(OutArgs a) {
     int* wrow = a.wire ? a.wire + (long long)b * a.wire_stride : nullptr;
     const int wp = 2 * a.n0 + 2 * a.n1 + 2;   // first element of the wire row's prune block
     if (i == 0) {
-        const int status = (a.device_err && *a.device_err) ? LG_ERR_DEVICE : ((a.range_flag && a.range_flag[b]) ? LG_ERR_RANGE : LG_OK);
+        const int status = (a.device_err && *a.device_err) ? LG_ERR_DEVICE : source_image(a.px, b, 0) < 0 ? LG_ERR_INDEX
+                           : ((a.range_flag && a.range_flag[b]) ? LG_ERR_RANGE : LG_OK);
         a.stop[b] = stop;
         if (a.stop_64) a.stop_64[b] = stop;
         if (wrow) { wrow[wp - 2] = stop; wrow[wp - 1] = status; }
@@ -41,7 +47,7 @@ __global__ __launch_bounds__(256) void write_outputs_kernel(OutArgs a) {
     if (i < a.n0) {
         const long long k = (long long)b * a.n0 + i;
         const int m = a.m0[k];
-        const float fill = i < count(a.num0, b, a.n0) ? (float)a.L : 0.f;
+        const float fill = i < count(a.num0, a.px, b, 0, a.n0) ? (float)a.L : 0.f;
         if (a.m0_64) a.m0_64[k] = m;
         if (a.prune0_64) a.prune0_64[k] = a.prune0[k];
         if (a.prune0_f) a.prune0_f[k] = fill;
@@ -50,7 +56,7 @@ __global__ __launch_bounds__(256) void write_outputs_kernel(OutArgs a) {
     if (i < a.n1) {
         const long long k = (long long)b * a.n1 + i;
         const int m = a.m1[k];
-        const float fill = i < count(a.num1, b, a.n1) ? (float)a.L : 0.f;
+        const float fill = i < count(a.num1, a.px, b, 1, a.n1) ? (float)a.L : 0.f;
         if (a.m1_64) a.m1_64[k] = m;
         if (a.prune1_64) a.prune1_64[k] = a.prune1[k];
         if (a.prune1_f) a.prune1_f[k] = fill;

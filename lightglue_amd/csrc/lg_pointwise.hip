@@ -11,8 +11,8 @@ namespace lg {
 __global__ __launch_bounds__(256) void bbox_kernel(PrepArgs a) {
     const int seg = blockIdx.x, image = seg & 1, pair = seg >> 1;
     const int n = image ? a.n1 : a.n0;
-    const float* kp = (image ? a.kpts1 : a.kpts0) + (long long)pair * n * 2;
-    const int live = a.rs.len[seg];   // ragged batch: only the pair's own keypoints define its bounding box
+    const int live = a.rs.len[seg];   // ragged batch: only the pair's own keypoints define its bounding box (0 for a pair whose index is out of range)
+    const float* kp = (image ? a.kpts1 : a.kpts0) + (long long)source_image(a.px, pair, image) * n * 2;
     float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
     for (int i = threadIdx.x; i < live; i += 256) {
         const float x = kp[2 * i], y = kp[2 * i + 1];
@@ -38,18 +38,19 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int r = blockIdx.x * 4 + wave;
     if (r >= a.rs.len[seg]) return;   // len <= n: rows past a pair's own count are padding (never read)
     const long long grow = seg_row_base(a.rs, seg) + r;
-    const float* kp = (image ? a.kpts1 : a.kpts0) + ((long long)pair * n + r) * 2;
+    const long long src = source_image(a.px, pair, image);   // the image whose rows this segment reads: the pair itself unless the inputs are indexed
+    const float* kp = (image ? a.kpts1 : a.kpts0) + (src * n + r) * 2;
     const float* szp = image ? a.size1 : a.size0;
     float sx, sy;
-    if (szp) { sx = szp[pair * 2]; sy = szp[pair * 2 + 1]; }
+    if (szp) { sx = szp[src * 2]; sy = szp[src * 2 + 1]; }
     else { const float* bb = a.bbox + seg * 4; sx = 1.f + bb[2] - bb[0]; sy = 1.f + bb[3] - bb[1]; }
     const float scale = fmaxf(sx, sy) / 2.f;          // ref :41
     float kn[4];
     kn[0] = (kp[0] - sx / 2.f) / scale;               // ref :40, :42
     kn[1] = (kp[1] - sy / 2.f) / scale;
     if (a.pos_dim == 4) {                             // ref :495-501
-        kn[2] = (image ? a.scales1 : a.scales0)[(long long)pair * n + r];
-        kn[3] = (image ? a.oris1 : a.oris0)[(long long)pair * n + r];
+        kn[2] = (image ? a.scales1 : a.scales0)[src * n + r];
+        kn[3] = (image ? a.oris1 : a.oris0)[src * n + r];
     }
     if (lane < 32) {                                  // ref :78-79 (32 frequencies, shared by all heads)
         float p = 0.f;
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     }
     if (lane == 0) a.ind[grow] = r;
     // descriptors -> residual stream (ref :502-503, :521-522 identity case) or input-projection staging
-    const float* d = (image ? a.desc1 : a.desc0) + ((long long)pair * n + r) * a.input_dim;
+    const float* d = (image ? a.desc1 : a.desc0) + (src * n + r) * a.input_dim;
     float* dst = (a.input_dim == 256) ? a.X + grow * 256 : a.Xin + grow * a.input_dim;
     for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(d + c);
 }

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(PTHREADS) void proj_first_kernel(ProjArgs a, PrepAr
     const int image = t.seg & 1, n = image ? pa.n1 : pa.n0;
     const int srow = tid >> 3, sslot = tid & 7;
     const int r = t.r0 + srow, rc = r < len ? r : len - 1;             // rows past the segment's count: a finite copy of its last row (never stored)
-    const long long in_row = (long long)t.pair * n + rc;
+    const long long simg = source_image(pa.px, t.pair, image);          // the image whose rows this tile reads: the pair itself unless the inputs are indexed
+    const long long in_row = simg * n + rc;
     // ---- descriptor rows (the x tile) requested first: cold, in flight under the table arithmetic
     const float* src = (image ? pa.desc1 : pa.desc0) + in_row * 256 + sslot * EPC;
     f32x4 hreg[STAGES][NV];
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(PTHREADS) void proj_first_kernel(ProjArgs a, PrepAr
         const float* kp = (image ? pa.kpts1 : pa.kpts0) + in_row * 2;
         const float* szp = image ? pa.size1 : pa.size0;
         float sx, sy;
-        if (szp) { sx = szp[t.pair * 2]; sy = szp[t.pair * 2 + 1]; }
+        if (szp) { sx = szp[simg * 2]; sy = szp[simg * 2 + 1]; }
         else { const float* bb = pa.bbox + t.seg * 4; sx = 1.f + bb[2] - bb[0]; sy = 1.f + bb[3] - bb[1]; }
         const float scale = fmaxf(sx, sy) / 2.f;
         float kn[4];

@@ -164,6 +164,34 @@ def match_batch(matcher, feats0: list, feats1: list) -> list:
     return out
 
 
+def match_pairs(matcher, feats, pairs, feats1=None) -> list:
+    """Match a pair list over extracted images: pair (i, j) matches image i of `feats` against image j of `feats1` (None: of `feats` too).  `feats` / `feats1`:
+    a feature store (the output of an extractor on an image batch, or of `collate_features`) or a list of per-image dicts, which is collated ONCE — the
+    matcher then reads every pair's rows in the store (`LightGlue.match_pairs`: nothing is stacked per pair, and the list may be longer than one engine
+    call).  Returns one `rbd`-style result dict per pair, trimmed to that pair's own keypoint counts, as `match_batch` does."""
+    store0 = collate_features(feats) if isinstance(feats, (list, tuple)) else feats
+    store1 = None if feats1 is None or feats1 is feats else (collate_features(feats1) if isinstance(feats1, (list, tuple)) else feats1)
+    res = matcher.match_pairs(store0, pairs, store1)
+    def counts(store):
+        num = store.get("num_keypoints")
+        return [int(store["keypoints"].shape[1])] * int(store["keypoints"].shape[0]) if num is None else torch.as_tensor(num).tolist()
+    c0 = counts(store0)
+    c1 = c0 if store1 is None else counts(store1)
+    stop = res["stop"]
+    stops = stop.tolist() if torch.is_tensor(stop) else [stop]
+    out = []
+    for b, (i, j) in enumerate(torch.as_tensor(pairs).reshape(-1, 2).tolist()):
+        n0, n1 = c0[i], c1[j]
+        out.append({
+            "matches0": res["matches0"][b, :n0], "matches1": res["matches1"][b, :n1],
+            "matching_scores0": res["matching_scores0"][b, :n0], "matching_scores1": res["matching_scores1"][b, :n1],
+            "matches": res["matches"][b], "scores": res["scores"][b],
+            "prune0": res["prune0"][b, :n0], "prune1": res["prune1"][b, :n1],
+            "stop": int(stops[b]),
+        })
+    return out
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output

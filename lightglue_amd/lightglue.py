@@ -79,6 +79,34 @@ class DeferredMatches:
         return self._out
 
 
+def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS, max_sim_elems: int = _cabi.LG_MAX_SIM_ELEMS) -> list:
+    """Cut a list of P pairs of n0 x n1 keypoints into the FEWEST contiguous chunks [(start, stop), ...] that each fit one engine call
+    (include/lightglue_amd.h: pairs * (cap0 + cap1) <= max_rows and pairs * cap0 * cap1 <= max_sim_elems, cap = n rounded up to 128).  Chunk sizes differ
+    by at most one, larger chunks first: the first chunk is the largest call, so the engine's workspace grows at most once.  Pure host arithmetic."""
+    P, n0, n1 = int(P), int(n0), int(n1)
+    if n0 > _cabi.LG_MAX_KEYPOINTS or n1 > _cabi.LG_MAX_KEYPOINTS:    # what lg_engine_forward answers (AssertionError through _cabi.check): no chunking helps
+        raise AssertionError("more than LG_MAX_KEYPOINTS (8192) keypoints in one image")
+    if P <= 0:
+        return []
+    c0, c1 = (n0 + 127) // 128 * 128, (n1 + 127) // 128 * 128
+    per_call = P
+    if c0 + c1:
+        per_call = min(per_call, int(max_rows) // (c0 + c1))
+    if c0 * c1:
+        per_call = min(per_call, int(max_sim_elems) // (c0 * c1))
+    if per_call < 1:
+        raise ValueError(f"one pair of {n0} x {n1} keypoints needs {c0 + c1} rows and {c0 * c1} similarity entries: "
+                         f"more than max_rows = {max_rows} / max_sim_elems = {max_sim_elems} allow")
+    chunks = -(-P // per_call)
+    size, larger = divmod(P, chunks)
+    out, start = [], 0
+    for i in range(chunks):
+        stop = start + size + (1 if i < larger else 0)
+        out.append((start, stop))
+        start = stop
+    return out
+
+
 class LightGlue(nn.Module):
     default_conf = {
         "name": "lightglue",
@@ -177,6 +205,11 @@ class LightGlue(nn.Module):
         self.check_finite = "first"
         self._guard_pending = True
         self.track_inplace_weight_edits = True     # see _sync_weights
+        # match_pairs: the per-call limits its chunks are planned for.  None = the engine's envelope (LG_MAX_ROWS / LG_MAX_SIM_ELEMS); lower values cap the
+        # engine's workspace (about 14 KB per keypoint row of a call + 4 bytes per similarity entry); higher ones are refused.  `last_pair_chunks`: the plan of the last call
+        self.max_rows_per_call = None
+        self.max_sim_elems_per_call = None
+        self.last_pair_chunks = None
         self._engine = None  # (handle, device_index, config signature)
         self._weights_sig = None
         self._plist = None
@@ -369,7 +402,8 @@ class LightGlue(nn.Module):
         bad = [(i, int(c)) for i, c in enumerate(status) if int(c) != _cabi.LG_OK]
         if bad:
             what = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
-                    _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)"}
+                    _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
+                    _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched"}
             raise _cabi.LightGlueAmdError("; ".join(f"pair {i}: {what.get(c, c)}" for i, c in bad[:8]))
 
     def forward_deferred(self, data: dict) -> "DeferredMatches":
@@ -440,41 +474,10 @@ class LightGlue(nn.Module):
         do_early_stop = conf.depth_confidence > 0
         do_point_pruning = self.will_prune(m, n)
 
-        # ---- outputs: ONE int32, ONE int64 and ONE fp32 allocation, carved into the tensors of the C ABI (16-byte aligned pieces).  The engine's
-        # last kernel writes the reference's dtypes itself (int64 indices / stop / prune counters, float prune0/1 without pruning, ref :616-629;
-        # round-5 extension of lg_forward_io): no framework kernel runs between or behind the engine's launches.
-        kmax = min(m, n)
-        plan = self._carve_plan(b, m, n, kmax, do_point_pruning)      # offsets of the pieces (cached per shape: the host path of a B = 1 forward is ~0.3 ms, and this was a tenth of it)
-        isz, ioff, fsz, foff, lsz, loff = plan
-        ibuf = torch.empty((ioff[-1],), device=device, dtype=torch.int32)
-
-        def ipiece(buf, off, sz, k, *shape):
-            return buf[off[k]: off[k] + sz[k]].view(shape)
-        m0, m1, mlist = ipiece(ibuf, ioff, isz, 0, b, m), ipiece(ibuf, ioff, isz, 1, b, n), ipiece(ibuf, ioff, isz, 2, b, kmax, 2)
-        prune0_i32 = ipiece(ibuf, ioff, isz, 3, b, m) if do_point_pruning else None
-        prune1_i32 = ipiece(ibuf, ioff, isz, 4, b, n) if do_point_pruning else None
-        stop_nm = ipiece(ibuf, ioff, isz, 5, 3, b)              # [0] = stop, [1] = n_matches, [2] = status (LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE)
-        fbuf = torch.empty((foff[-1],), device=device, dtype=torch.float32)
-        ms0, ms1 = ipiece(fbuf, foff, fsz, 0, b, m), ipiece(fbuf, foff, fsz, 1, b, n)
-        mscore_list = ipiece(fbuf, foff, fsz, 2, b, kmax)
-        raw_mode = _raw is not False
-        m0_64 = m1_64 = mlist64 = stop64 = prune0 = prune1 = lbuf = None
-        if not raw_mode:
-            lbuf = torch.empty((loff[-1],), device=device, dtype=torch.int64)
-            m0_64, m1_64 = ipiece(lbuf, loff, lsz, 0, b, m), ipiece(lbuf, loff, lsz, 1, b, n)
-            mlist64, stop64 = ipiece(lbuf, loff, lsz, 2, b, kmax, 2), ipiece(lbuf, loff, lsz, 3, b)
-            if do_point_pruning:
-                prune0, prune1 = ipiece(lbuf, loff, lsz, 4, b, m), ipiece(lbuf, loff, lsz, 5, b, n)
-            else:   # ref :616-617 (padding rows of a ragged batch: 0)
-                prune0, prune1 = ipiece(fbuf, foff, fsz, 3, b, m), ipiece(fbuf, foff, fsz, 4, b, n)
+        o = self._alloc_outputs(b, m, n, device, do_point_pruning, _raw is not False)
         wire = _raw if torch.is_tensor(_raw) else None          # PairShardedMatcher: [pairs >= b][>= 3m + 3n + 2] int32 rows the engine packs itself
-
-        log_assignment = None
-        if self.return_log_assignment and m > 0 and n > 0:
-            log_assignment = torch.empty((b, m + 1, n + 1), device=device, dtype=torch.float32)
         handle = self._get_engine(device)
         self._sync_weights(handle, device)
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
         self._guard_pending = False
         if wire is not None:   # the engine's last kernel writes b rows of 3m + 3n + 2 int32 into it: a short or mistyped buffer would be an out-of-bounds device write
@@ -483,16 +486,7 @@ class LightGlue(nn.Module):
                 raise ValueError(f"wire must be an int32 [>= {b}, >= {_cabi.wire_width(m, n)}] tensor on {device} with unit column stride, got "
                                  f"{wire.dtype} {tuple(wire.shape)} stride {tuple(wire.stride())} on {wire.device}")
         flags = _cabi.LG_FLAG_EXT | (0 if do_point_pruning or conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING) | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
-        io = _cabi.LgForwardIO(
-            b, m, n, flags,
-            ptr(k0), ptr(k1), ptr(desc0), ptr(desc1), ptr(size0), ptr(size1),
-            ptr(extra[0]), ptr(extra[1]), ptr(extra[2]), ptr(extra[3]),
-            ptr(m0), ptr(m1), ptr(ms0), ptr(ms1), stop_nm[0].data_ptr(), ptr(prune0_i32), ptr(prune1_i32),
-            ptr(mlist), ptr(mscore_list), stop_nm[1].data_ptr(), ptr(num0), ptr(num1), ptr(log_assignment),
-            ptr(m0_64), ptr(m1_64), ptr(mlist64), ptr(stop64),
-            ptr(prune0) if (do_point_pruning and not raw_mode) else None, ptr(prune1) if (do_point_pruning and not raw_mode) else None,
-            None if (do_point_pruning or raw_mode) else ptr(prune0), None if (do_point_pruning or raw_mode) else ptr(prune1),
-            ptr(wire), 0 if wire is None else wire.stride(0), stop_nm[2].data_ptr())
+        io = self._forward_io(o, 0, b, flags, (k0, k1, desc0, desc1, size0, size1, *extra, num0, num1), wire)
         with torch.cuda.device(device):
             cur_stream = torch.cuda.current_stream(device)
             _cabi.check(_cabi.load().lg_engine_forward(handle, C.byref(io), C.c_void_p(cur_stream.cuda_stream)))
@@ -500,38 +494,211 @@ class LightGlue(nn.Module):
         if getattr(self, "_debug_step", -1) >= 0:  # test tap: the pipeline stopped early, outputs are not written
             torch.cuda.synchronize(device)
             return None
-        if raw_mode:
-            return {"matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1, "stop": stop_nm[0], "status": stop_nm[2],
+        if o.raw_mode:
+            return {"matches0": o.m0, "matches1": o.m1, "matching_scores0": o.ms0, "matching_scores1": o.ms1, "stop": o.stop_nm[0], "status": o.stop_nm[2],
                     "pruning": do_point_pruning}   # "pruning": the wire row's prune block holds int counters (else the float fill's bits)
-        # ---- output assembly (ref :593-629): the engine has written every fixed-shape tensor; only the ragged lists need the host.
+        return self._finish(o, cur_stream, _defer)
+
+    # ------------------------------------------------------------------ pair lists over feature stores
+    def _call_limits(self):
+        limits = []
+        for name, top in (("max_rows_per_call", _cabi.LG_MAX_ROWS), ("max_sim_elems_per_call", _cabi.LG_MAX_SIM_ELEMS)):
+            v = getattr(self, name)
+            v = top if v is None else int(v)
+            if not 1 <= v <= top:
+                raise ValueError(f"{name} must lie in [1, {top}] (the envelope of one engine call, include/lightglue_amd.h), got {v}")
+            limits.append(v)
+        return limits
+
+    def _store(self, feats: dict, device) -> SimpleNamespace:
+        """A feature store as the engine reads it: contiguous fp32 / int32 tensors on `device` (tensors that already qualify pass through untouched)."""
+        conf = self.conf
+        def f32(t):
+            if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+                return t
+            return t.detach().to(device=device, dtype=torch.float32).contiguous()
+        kpts, desc = feats["keypoints"], feats["descriptors"]
+        assert kpts.dim() == 3 and kpts.shape[-1] == 2, "a feature store holds keypoints [K, N, 2]"
+        K, N = kpts.shape[:2]
+        assert tuple(desc.shape) == (K, N, conf.input_dim), f"a feature store holds descriptors [K, N, {conf.input_dim}]"
+        st = SimpleNamespace(K=K, N=N, kpts=f32(kpts), desc=f32(desc), size=None, scales=None, oris=None, num=None)
+        size = feats.get("image_size")
+        if size is not None:
+            if not isinstance(size, torch.Tensor):
+                size = torch.tensor(size, dtype=torch.float32)
+            size = f32(size).reshape(-1, 2)
+            assert size.shape[0] in (1, K), f"image_size must have shape [2], [1, 2] or [{K}, 2]"
+            st.size = size if size.shape[0] == K else size.expand(K, 2).contiguous()
+        if conf.add_scale_ori:
+            st.scales, st.oris = f32(feats["scales"]), f32(feats["oris"])
+            assert tuple(st.scales.shape) == (K, N) and tuple(st.oris.shape) == (K, N), "scales / oris must have shape [K, N]"
+        num = feats.get("num_keypoints")
+        if num is not None:
+            num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
+            assert num.shape == (K,), f"num_keypoints must have shape [{K}]"
+            st.num = num.clamp(0, N)
+        return st
+
+    @torch.no_grad()
+    def match_pairs(self, feats0: dict, pairs, feats1: Optional[dict] = None, *, deferred: bool = False, validate: bool = True):
+        """Match a pair list over feature stores: pair p = (i, j) matches image i of `feats0` against image j of `feats1` (None: of `feats0` too).
+
+        A store is what an extractor returns for a K-image batch, or `glue.collate_features` builds: {keypoints [K,N,2], descriptors [K,N,D],
+        num_keypoints [K] (optional), image_size [K,2] | [1,2] | [2] (optional), scales / oris [K,N] iff add_scale_ori}; other keys are ignored.
+        `pairs`: [P, 2] integers (sequence, CPU or device tensor).  Returns the dict of `forward` for a batch of P pairs — bit-identical to `forward` on the
+        stacked tensors {k: v[index]} — but the engine reads every pair's rows IN the store (LG_FLAG_INDEXED): nothing is stacked, and P is not bound by the
+        envelope of one engine call.  The list is cut into the fewest contiguous chunks that fit `max_rows_per_call` / `max_sim_elems_per_call`
+        (`plan_pair_chunks`; the plan used is left in `last_pair_chunks`), each chunk is one engine call on the current stream writing its slice of
+        outputs allocated once for all P pairs, and ONE host synchronisation follows the last call — none with `deferred=True`, which returns a
+        `DeferredMatches`.  The range guard (`check_finite`) covers every chunk of the call it is armed for; a raised status names pairs by their
+        position in `pairs`.
+
+        validate=True checks `pairs` on the host (shape, integer dtype, range; a device tensor is copied to the host once) and raises ValueError before
+        anything is launched.  validate=False uses a device tensor as given, without a host copy: the engine's own check of every index then is the
+        safety net — a pair with an index outside its store is not matched and raises LG_ERR_INDEX."""
+        max_rows, max_sim = self._call_limits()
+        same = feats1 is None or feats1 is feats0
+        K0 = int(feats0["keypoints"].shape[0])
+        K1 = K0 if same else int(feats1["keypoints"].shape[0])
+        # ---- the pair list: [P, 2] integers
+        as_given = torch.is_tensor(pairs)
+        pt = pairs if as_given else torch.as_tensor(pairs)
+        if not as_given and pt.numel() == 0:
+            pt = pt.reshape(0, 2).to(torch.int64)
+        if pt.dim() != 2 or pt.shape[1] != 2:
+            raise ValueError(f"pairs must have shape [P, 2], got {tuple(pt.shape)}")
+        if pt.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"pairs must hold integers, got {pt.dtype}")
+        P = int(pt.shape[0])
+        if validate and P:
+            host = pt.cpu()
+            lo, hi0, hi1 = int(host.min()), int(host[:, 0].max()), int(host[:, 1].max())
+            if lo < 0 or hi0 >= K0 or hi1 >= K1:
+                bad = ((host < 0) | (host >= torch.tensor([K0, K1]))).any(1).nonzero().flatten().tolist()
+                raise ValueError(f"pairs {bad[:8]} index outside the feature stores of {K0} and {K1} images")
+        device = feats0["keypoints"].device
+        if device.type != "cuda":
+            raise RuntimeError("lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
+                               f"Got keypoints on {device}.")
+        s0 = self._store(feats0, device)              # converted at most once per call, never per chunk
+        s1 = s0 if same else self._store(feats1, device)
+        m, n = s0.N, s1.N
+        chunks = plan_pair_chunks(P, m, n, max_rows, max_sim)
+        self.last_pair_chunks = chunks
+        pruning = self.will_prune(m, n)
+        o = self._alloc_outputs(P, m, n, device, pruning, False)
+        debug = getattr(self, "_debug_step", -1) >= 0
+        assert not debug or len(chunks) == 1, "debug taps (debug_stop_after) read the workspace of ONE engine call: match_pairs supports them for a single chunk only"
+        with torch.cuda.device(device):
+            cur_stream = torch.cuda.current_stream(device)
+            if P:
+                index = pt.to(device=device, dtype=torch.int32).t().contiguous()     # [2, P]: index0 | index1, a chunk is an offset into both
+                handle = self._get_engine(device)
+                self._sync_weights(handle, device)
+                guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
+                self._guard_pending = False
+                flags = (_cabi.LG_FLAG_EXT | _cabi.LG_FLAG_INDEXED | (0 if pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
+                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0))
+                inputs = (s0.kpts, s1.kpts, s0.desc, s1.desc, s0.size, s1.size, s0.scales, s0.oris, s1.scales, s1.oris, s0.num, s1.num)
+                lib, stream_ptr = _cabi.load(), C.c_void_p(cur_stream.cuda_stream)
+                for start, stop in chunks:
+                    io = self._forward_io(o, start, stop - start, flags, inputs, None, (index[0], index[1], s0.K, s1.K))
+                    _cabi.check(lib.lg_engine_forward(handle, C.byref(io), stream_ptr))
+            if debug:   # test tap: the pipeline stopped early, outputs are not written
+                torch.cuda.synchronize(device)
+                return None
+            return self._finish(o, cur_stream, deferred)
+
+    # ------------------------------------------------------------------ outputs (shared by forward and match_pairs)
+    def _alloc_outputs(self, b, m, n, device, pruning, raw_mode):
+        """The outputs of `b` pairs: ONE int32, ONE int64 and ONE fp32 allocation, carved into the tensors of the C ABI (16-byte aligned pieces).  The engine's
+        last kernel writes the reference's dtypes itself (int64 indices / stop / prune counters, float prune0/1 without pruning, ref :616-629; round-5 extension
+        of lg_forward_io): no framework kernel runs between or behind the engine's launches.  Every piece is contiguous with the pair as its leading
+        dimension, so the outputs of pairs [start, stop) are the same pieces at a pointer offset (`_forward_io`)."""
+        kmax = min(m, n)
+        isz, ioff, fsz, foff, lsz, loff = self._carve_plan(b, m, n, kmax, pruning)      # offsets of the pieces (cached per shape: the host path of a B = 1 forward is ~0.3 ms, and this was a tenth of it)
+        o = SimpleNamespace(b=b, m=m, n=n, pruning=pruning, raw_mode=raw_mode)
+        ibuf = o.ibuf = torch.empty((ioff[-1],), device=device, dtype=torch.int32)
+
+        def ipiece(buf, off, sz, k, *shape):
+            return buf[off[k]: off[k] + sz[k]].view(shape)
+        o.m0, o.m1, o.mlist = ipiece(ibuf, ioff, isz, 0, b, m), ipiece(ibuf, ioff, isz, 1, b, n), ipiece(ibuf, ioff, isz, 2, b, kmax, 2)
+        o.prune0_i32 = ipiece(ibuf, ioff, isz, 3, b, m) if pruning else None
+        o.prune1_i32 = ipiece(ibuf, ioff, isz, 4, b, n) if pruning else None
+        o.stop_nm = ipiece(ibuf, ioff, isz, 5, 3, b)              # [0] = stop, [1] = n_matches, [2] = status (LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE / LG_ERR_INDEX)
+        fbuf = o.fbuf = torch.empty((foff[-1],), device=device, dtype=torch.float32)
+        o.ms0, o.ms1 = ipiece(fbuf, foff, fsz, 0, b, m), ipiece(fbuf, foff, fsz, 1, b, n)
+        o.mscore_list = ipiece(fbuf, foff, fsz, 2, b, kmax)
+        o.m0_64 = o.m1_64 = o.mlist64 = o.stop64 = o.prune0 = o.prune1 = o.lbuf = None
+        if not raw_mode:
+            lbuf = o.lbuf = torch.empty((loff[-1],), device=device, dtype=torch.int64)
+            o.m0_64, o.m1_64 = ipiece(lbuf, loff, lsz, 0, b, m), ipiece(lbuf, loff, lsz, 1, b, n)
+            o.mlist64, o.stop64 = ipiece(lbuf, loff, lsz, 2, b, kmax, 2), ipiece(lbuf, loff, lsz, 3, b)
+            if pruning:
+                o.prune0, o.prune1 = ipiece(lbuf, loff, lsz, 4, b, m), ipiece(lbuf, loff, lsz, 5, b, n)
+            else:   # ref :616-617 (padding rows of a ragged batch: 0)
+                o.prune0, o.prune1 = ipiece(fbuf, foff, fsz, 3, b, m), ipiece(fbuf, foff, fsz, 4, b, n)
+        o.log_assignment = None
+        if self.return_log_assignment and m > 0 and n > 0:
+            o.log_assignment = torch.empty((b, m + 1, n + 1), device=device, dtype=torch.float32)
+        return o
+
+    @staticmethod
+    def _forward_io(o, start, count, flags, inputs, wire=None, index=None):
+        """lg_forward_io of one engine call that writes pairs [start, start + count) of the outputs `o`.  `inputs`: kpts0, kpts1, desc0, desc1, size0, size1,
+        scales0, oris0, scales1, oris1, num0, num1 (tensors or None), passed whole; `index`: (index0, index1, images0, images1) of an LG_FLAG_INDEXED call,
+        the two int32 [P] tensors offset like the outputs."""
+        whole = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        def at(t):     # the piece's rows from pair `start` on ([pairs, ...] contiguous)
+            return None if t is None or t.numel() == 0 else t.data_ptr() + start * t.stride(0) * t.element_size()
+        row = lambda k: o.stop_nm.data_ptr() + (k * o.b + start) * 4
+        k0, k1, desc0, desc1, size0, size1, sc0, or0, sc1, or1, num0, num1 = inputs
+        with_i64, prune = not o.raw_mode, o.pruning
+        io = _cabi.LgForwardIO(
+            count, o.m, o.n, flags,
+            whole(k0), whole(k1), whole(desc0), whole(desc1), whole(size0), whole(size1), whole(sc0), whole(or0), whole(sc1), whole(or1),
+            at(o.m0), at(o.m1), at(o.ms0), at(o.ms1), row(0), at(o.prune0_i32), at(o.prune1_i32),
+            at(o.mlist), at(o.mscore_list), row(1), whole(num0), whole(num1), at(o.log_assignment),
+            at(o.m0_64), at(o.m1_64), at(o.mlist64), at(o.stop64),
+            at(o.prune0) if (prune and with_i64) else None, at(o.prune1) if (prune and with_i64) else None,
+            None if (prune or not with_i64) else at(o.prune0), None if (prune or not with_i64) else at(o.prune1),
+            whole(wire), 0 if wire is None else wire.stride(0), row(2))
+        if index is not None:
+            io.index0, io.index1 = index[0].data_ptr() + 4 * start, index[1].data_ptr() + 4 * start
+            io.images0, io.images1 = index[2], index[3]
+        return io
+
+    def _finish(self, o, stream, defer):
+        """Output assembly (ref :593-629) behind the last engine call: the engine has written every fixed-shape tensor; only the ragged lists need the host."""
+        b = o.b
 
         def assemble(host):   # host = [[stop per pair], [matches per pair], [status per pair]]
             self._raise_on_status(host[2])
             counts = host[1]
-            matches = [row[:c] for row, c in zip(mlist64.unbind(0), counts)]
-            mscores = [row[:c] for row, c in zip(mscore_list.unbind(0), counts)]
-            stop_out = int(host[0][0]) if b == 1 else stop64
-            extra_out = {} if log_assignment is None else {"log_assignment": log_assignment}
+            matches = [row[:c] for row, c in zip(o.mlist64.unbind(0), counts)]
+            mscores = [row[:c] for row, c in zip(o.mscore_list.unbind(0), counts)]
+            stop_out = int(host[0][0]) if b == 1 else o.stop64
+            extra_out = {} if o.log_assignment is None else {"log_assignment": o.log_assignment}
             return {
                 **extra_out,
-                "matches0": m0_64,
-                "matches1": m1_64,
-                "matching_scores0": ms0,
-                "matching_scores1": ms1,
+                "matches0": o.m0_64,
+                "matches1": o.m1_64,
+                "matching_scores0": o.ms0,
+                "matching_scores1": o.ms1,
                 "stop": stop_out,
                 "matches": matches,
                 "scores": mscores,
-                "prune0": prune0,
-                "prune1": prune1,
+                "prune0": o.prune0,
+                "prune1": o.prune1,
             }
 
-        if _defer:   # the sizes travel to pinned host memory behind an event; nothing waits here
+        if defer:   # the sizes travel to pinned host memory behind an event; nothing waits here
             hbuf = torch.empty((3, b), dtype=torch.int32, pin_memory=True)
-            hbuf.copy_(stop_nm, non_blocking=True)
+            hbuf.copy_(o.stop_nm, non_blocking=True)
             done = torch.cuda.Event()
-            done.record(cur_stream)
-            return DeferredMatches(done, hbuf, assemble, tuple(t for t in (ibuf, fbuf, lbuf, log_assignment) if t is not None))
-        return assemble(stop_nm.tolist())  # THE host sync of the forward: the ragged lists need their sizes (and B = 1 its `stop`)
+            done.record(stream)
+            return DeferredMatches(done, hbuf, assemble, tuple(t for t in (o.ibuf, o.fbuf, o.lbuf, o.log_assignment) if t is not None))
+        return assemble(o.stop_nm.tolist())  # THE host sync of the call: the ragged lists need their sizes (and B = 1 its `stop`)
 
     def set_option(self, key: str, value: int, device="cuda"):
         """Engine options (include/lightglue_amd.h lg_engine_set_option), e.g. ("fused_tail", 0)."""
