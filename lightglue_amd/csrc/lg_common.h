@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 // This library is written for ONE target.  Hard-wired below and in the kernels: the gfx9 buffer-descriptor word 0x00020000 (weight_rsrc, compact_rsrc),
-// the gfx9 s_waitcnt immediate layout (0x0F70 = vmcnt(0) only; lg_attention.hip, lg_tail.hip), v_mfma_f32_16x16x32_{f16,bf16}, v_permlane{16,32}_swap,
+// the gfx9 s_waitcnt immediate layout (wait_vmcnt0), v_mfma_f32_16x16x32_{f16,bf16}, v_permlane{16,32}_swap,
 // global_load_lds_dwordx4, and dynamic LDS up to 132 KB per workgroup (160 KB per CU).  Any other --offload-arch would miscompile or fail at launch
 // (ADVICE r04): refuse it here instead.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -126,8 +126,11 @@ template <> __device__ __forceinline__ void split8<TagF16>(const f32x4& a, const
 // slot index within a row is XOR-swizzled with a function of the row so that the 16-lane groups of
 // ds_read_b128 / the 32-lane halves of ds_read_b64 hit distinct banks (guide §2 / T2):
 //   ROWB = 128: slot ^= (row >> 1) & 7      ROWB = 256: slot ^= row & 15
+// An LDS-DMA lands lane l's 16 bytes at physical slot l & 7 of its row, so its SOURCE is swizzled instead: the XOR term is its own inverse, and
+// lds_off<128> and the DMA source offsets (lg_attention.hip, dma_lanes) both take it from lds_swz128 — they cannot change apart.
+__device__ __forceinline__ int lds_swz128(int row) { return (row >> 1) & 7; }
 template <int ROWB> __device__ __forceinline__ int lds_off(int row, int slot16) {
-    if constexpr (ROWB == 128) return row * 128 + ((slot16 ^ ((row >> 1) & 7)) << 4);
+    if constexpr (ROWB == 128) return row * 128 + ((slot16 ^ lds_swz128(row)) << 4);
     else return row * 256 + ((slot16 ^ (row & 15)) << 4);
 }
 
@@ -139,7 +142,7 @@ template <int ROWB> __device__ __forceinline__ int lds_off(int row, int slot16) 
 // barrier that publishes the tile), and a compiler-issued vmcnt wait can only over-wait because of it, never under-wait.
 // `lds` must be wave-uniform (it travels in M0); one wait state between the M0 write and the DMA instruction.
 // INVARIANTS a caller keeps (checked on the compiled ISA by tools/check_isa.py, tests/test_isa_invariants.py):
-//   * every barrier that publishes a DMA'd tile is preceded by a vmcnt(0) wait, written as __builtin_amdgcn_s_waitcnt (NOT inline asm: the
+//   * every barrier that publishes a DMA'd tile is preceded by a vmcnt(0) wait, written as wait_vmcnt0() = __builtin_amdgcn_s_waitcnt (NOT inline asm: the
 //     waitcnt pass must see it, or it keeps waiting for older compiler-visible loads later — and, the counter being in order, for the DMAs
 //     issued in between: "over-wait" = an exposed DMA round trip, found in the peeled first tile of the attention kernels in round 4);
 //   * no VMEM store sits between a DMA and its wait, and all waits for DMAs are vmcnt(0) (the in-order argument needs nothing else then).
@@ -156,6 +159,10 @@ __device__ __forceinline__ void lds_dma16_s(const void* sbase, uint32_t voff, vo
     const uint64_t sb = ((uint64_t)bhi << 32) | blo;
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(dst), "v"(voff), "s"(sb) : "memory", "m0");
 }
+
+// vmcnt(0) in the gfx9 immediate layout, expcnt / lgkmcnt untouched: "my DMA pieces (and every older load of mine) have landed".  The builtin, for the
+// reason given at lds_dma16; an inline-asm wait is right only where nothing compiler-visible is in flight (the drain behind a tile loop).
+__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 // ---- weight fragments by buffer load: the fragment-packed weight arrays are read as base descriptor (SGPRs) + one per-lane VGPR offset (16 lane,
 // constant for the kernel) + a SCALAR byte offset per fragment.  As plain global loads hipcc built a 64-bit VGPR address per load (v_lshl_add_u64 +

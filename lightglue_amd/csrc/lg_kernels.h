@@ -137,7 +137,7 @@ struct AttnArgs {
     long long plane;  // PREC_F16X3: element distance from the hi to the lo plane of q / k / vt
     float* ctx;       // [R][256] fp32, column = head*64 + d
     int R; int cross; // cross: segment s attends to segment s^1 (q and k both read from `q`)
-    long long* dbg;   // profiling builds (-DLG_ATTN_TIMING) only: [blocks][4 waves][8] phase clock sums
+    long long* dbg;   // profiling builds (-DLG_ATTN_TIMING / -DLG_ATTN_WALL) only: [blocks][waves of the kernel's workgroup][8] words (lg_attention.hip, profiling taps)
     int rows_per_wave;   // 16, 32 or 64 query rows per wave (see launch_attention)
     int dma;             // 16-bit, 32 rows per wave: the LDS-DMA kernel (attn_dma_kernel)
 };

@@ -109,14 +109,14 @@ __global__ __launch_bounds__(STHREADS, 4) void sim_planes_kernel(SimPlanesArgs a
     };
     for (int T = 0; T < nst; ++T) {
         // ---- tile 2 T (half 0).  The BUILTIN wait: hipcc's waitcnt pass must see it (lg_common.h, lds_dma16)
-        __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): my pieces of this tile have landed (first time round: my A fragments too)
+        wait_vmcnt0();                                          // vmcnt(0): my pieces of this tile have landed (first time round: my A fragments too)
         asm volatile("" ::: "memory");
         __syncthreads();                                         // ... and everybody's; every wave is through with half 1
         dma_tile(2 * T + 1);
         __builtin_amdgcn_sched_barrier(0);
         compute_half(0);
         // ---- tile 2 T + 1 (half 1)
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        wait_vmcnt0();
         asm volatile("" ::: "memory");
         __syncthreads();
         dma_tile(T + 1 < nst ? 2 * T + 2 : 2 * T);               // never branched around; past the end: a harmless re-fetch of a live tile into the idle half
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(STHREADS, 4) void sim_planes_kernel(SimPlanesArgs a
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                          // no DMA may land in LDS that has been released
+    wait_vmcnt0();                                              // no DMA may land in LDS that has been released
     (void)ntile;
 }
 

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
     run_half(std::integral_constant<int, 0>{});
     if constexpr (CTX_DMA) {
         static_assert(!CTX_DMA || HC == 8, "one ctx piece per chunk of the x half");
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's pieces have landed (the last one was issued a chunk ago, behind the fragments of chunk 8)
+        wait_vmcnt0();   // vmcnt(0): this wave's pieces have landed (the last one was issued a chunk ago, behind the fragments of chunk 8)
         __builtin_amdgcn_sched_barrier(0);
         ctx_convert_in_place();
     } else {

@@ -59,11 +59,9 @@ def err(a, b):
     return float(d), float(d / (rms + 1e-30))
 
 
-def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False):
-    """Run the pipeline up to every step of `layer` and compare the step's output buffer with the
-    oracle.  Returns {stage name: (max abs err, err / rms)}."""
-    B, n0 = data["image0"]["keypoints"].shape[:2]
-    n1 = data["image1"]["keypoints"].shape[1]
+def oracle_traces(sd, data, conf_kw, layer=0):
+    """The oracle's intermediate tensors of `layer`, one trace dict per pair of the batch."""
+    B = data["image0"]["keypoints"].shape[0]
     conf = O.make_conf(**{**conf_kw, "pruning_min_kpts": conf_kw.get("pruning_min_kpts", -1) if conf_kw.get("pruning_min_kpts") is not None else -1})
     traces = []
     for b in range(B):
@@ -73,8 +71,21 @@ def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False):
         O.forward_pair(sd, conf, g(d0, "keypoints"), g(d1, "keypoints"), g(d0, "descriptors"), g(d1, "descriptors"),
                        g(d0, "image_size"), g(d1, "image_size"), g(d0, "scales"), g(d0, "oris"), g(d1, "scales"), g(d1, "oris"), trace=tr)
         traces.append(tr)
+    return traces
+
+
+def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False, options=None, traces=None):
+    """Run the pipeline up to every step of `layer` and compare the step's output buffer with the
+    oracle.  Returns {stage name: (max abs err, err / rms)}.  `options`: engine options applied with
+    set_option after the model is made; `traces`: oracle_traces(...) of the same inputs, when the caller shares them."""
+    B, n0 = data["image0"]["keypoints"].shape[:2]
+    n1 = data["image1"]["keypoints"].shape[1]
+    if traces is None:
+        traces = oracle_traces(sd, data, conf_kw, layer)
     model = make_model(sd, precision, **conf_kw)
     model.set_option("fused_tail", int(fused))   # unfused: every intermediate buffer of the chain exists
+    for key, value in (options or {}).items():
+        model.set_option(key, value)
     tdata = to_torch(data)
     res = {}
     L = layer

@@ -517,6 +517,48 @@ def test_attention_lds_dma_kernel_is_bit_identical(precision):
         assert torch.isfinite(dma["matching_scores0"]).all() and (dma["matches0"] > -1).any(), (n0, n1)
 
 
+_EDGE_SHAPES = ((1, 65), (63, 64), (129, 17))
+_EDGE_CONF = dict(depth_confidence=-1, width_confidence=-1)
+_edge_cases = {}
+
+
+def _edge_case(shape):
+    """state dict, batch and oracle traces of one tile-edge shape: computed once, shared by every kernel form"""
+    if shape not in _edge_cases:
+        sd = synth.make_state_dict(0, recipe="A")
+        data = synth.make_batch(7, 2, *shape)
+        _edge_cases[shape] = (sd, data, gpu_util.oracle_traces(sd, data, _EDGE_CONF))
+    return _edge_cases[shape]
+
+
+@pytest.mark.parametrize("precision,options,tol", [
+    ("f16x3", {"attn_rows": 32}, 5e-4),                      # attn_split_kernel<1, 8>: 128-row workgroups
+    ("f16x3", {"attn_rows": 16}, 5e-4),                      # attn_split_kernel<1, 4>: 64-row workgroups
+    ("f16x3/fp16", {"attn_rows": 32}, 3e-3),                 # attn_dma_kernel (attn_rows pinned: a grid this small would pick 16 rows, which has no DMA form)
+    ("f16x3/fp16", {"attn_rows": 32, "attn_dma": 0}, 3e-3),  # attn_kernel<f16, 2>
+    ("f16x3/fp16", {"attn_rows": 16}, 3e-3),                 # attn_kernel<f16, 1>
+    ("bf16", {"attn_rows": 64}, 1e-1),                       # attn_kernel<bf16, 4>: 256-row workgroups laid out per segment
+    ("fp32", {}, 2e-5),                                      # attn_kernel<f32, 2>
+], ids=["split-128", "split-64", "dma", "staged-32", "staged-16", "bf16-64", "fp32"])
+def test_attention_context_at_tile_edges(precision, options, tol):
+    """Layer 0's self and cross attention context against the oracle at the sizes where the steps every attention kernel shares
+    (workgroup set-up, dead-key masking, row maximum, first-tile re-base, DMA lane offsets, epilogue) can go wrong: (n0, n1) =
+    (1, 65), (63, 64), (129, 17) give key counts of a single key, a tile minus one, an exact tile, a tile plus one and two tiles
+    plus one, and query counts that end inside a 16-row tile and inside a 128-row workgroup.  With one key the context is v
+    itself, so nothing averages out: the bound (err / rms, as test_pipeline_stages_layer0) is the larger of that test's stage
+    tolerance and its q / k / v operand tolerance for the precision."""
+    require_gpu()
+    bad = {}
+    for shape in _EDGE_SHAPES:
+        sd, data, traces = _edge_case(shape)
+        res = gpu_util.stage_errors(sd, data, precision, _EDGE_CONF, options=options, traces=traces)
+        for stage in ("self.attn_ctx", "cross.attn_ctx"):
+            print(f"tile-edge {precision} {options} {shape} {stage}: max abs {res[stage][0]:.3e}  err/rms {res[stage][1]:.3e}  (bound {tol:g})")
+            if not res[stage][1] <= tol:
+                bad[(shape, stage)] = res[stage]
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("precision", ["f16x3", "f16x3/fp16", "bf16", "fp16"])
 def test_tail_row_tile_shapes_are_bit_identical(precision):
     """The fused tail runs 64-row workgroups when they fill the chip and 32- / 16-row ones for small grids (engine option
