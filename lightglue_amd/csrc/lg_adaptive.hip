@@ -55,7 +55,7 @@ __global__ __launch_bounds__(DNT) void adapt_decide_kernel(AdaptArgs a) {
             return;
         }
     }
-    if (a.gather && tid == 0) a.xsel[pair] = a.xnext;   // the pair continues: proj_gather_kernel moves its rows to the other buffer set
+    if (a.gather && tid == 0) a.xsel[pair] = a.xnext;   // the pair continues: proj_rows_kernel<GatherRows> moves its rows to the other buffer set
     for (int image = 0; image < 2; ++image) {
         const int seg = 2 * pair + image;
         const int L = image ? len1 : len0;
@@ -209,7 +209,7 @@ int compact_chunk_rows() { return CROWS; }
 
 hipError_t launch_adapt(const AdaptArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(adapt_decide_kernel, dim3(a.rs.B), dim3(DNT), 0, s, a);
-    if (a.do_prune && !a.gather) {   // gather mode: the next SelfBlock projection moves the rows (proj_gather_kernel)
+    if (a.do_prune && !a.gather) {   // gather mode: the next SelfBlock projection moves the rows (proj_rows_kernel<GatherRows>)
         const int items = 2 * a.rs.B * a.compact_chunks;   // dealt by ticket: the grid size is a throughput choice only (one workgroup per CU of an MI355X)
         hipLaunchKernelGGL(adapt_compact_kernel, dim3(items < 256 ? items : 256), dim3(256), 0, s, a);
     }

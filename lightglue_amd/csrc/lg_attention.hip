@@ -742,12 +742,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attn_split_kernel(AttnArgs a)
 
 template <int QT, int NW> static hipError_t launch_attn_split(const AttnArgs& a, hipStream_t s) {
     if (a.plane <= 0) return hipErrorInvalidValue;
-    constexpr int smem = 2 * 4 * 64 * 128;
-    auto kern = attn_split_kernel<QT, NW>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(attention_tiles(a.rs, 16 * QT * NW) * 4), dim3(NW * 64), smem, s, a);
-    return hipGetLastError();
+    return launch_with_lds(attn_split_kernel<QT, NW>, dim3(attention_tiles(a.rs, 16 * QT * NW) * 4), dim3(NW * 64), 2 * 4 * 64 * 128, s, a);
 }
 
 template <class Tag> static hipError_t launch_attn_dma(const AttnArgs& a, hipStream_t s) {

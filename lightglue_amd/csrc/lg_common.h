@@ -122,6 +122,14 @@ __device__ __forceinline__ void split8_f16(const f32x4& a, const f32x4& b, u32x4
 template <class Tag> __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo);
 template <> __device__ __forceinline__ void split8<TagF16>(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) { split8_f16<false>(a, b, hi, lo); }
 
+// ---- range guard (LG_FLAG_CHECK_FINITE): 1 for whatever an f16 plane cannot hold, inf and NaN included (int: the callers combine them with | and &)
+__device__ __forceinline__ int out_of_f16_range(float x) { return !(fabsf(x) < 65504.f); }
+__device__ __forceinline__ int out_of_f16_range(const f32x4& v) {
+    return out_of_f16_range(v[0]) | out_of_f16_range(v[1]) | out_of_f16_range(v[2]) | out_of_f16_range(v[3]);
+}
+// ---- profiling tap (dbg == nullptr in production): word `slot` of wave w of this workgroup in [blocks][8 waves][8]
+__device__ __forceinline__ long long& dbg_slot(long long* dbg, int w, int slot) { return dbg[((long long)blockIdx.x * 8 + w) * 8 + slot]; }
+
 // ---- LDS tile addressing.  A tile is [rows][ROWB bytes] with ROWB = 128 or 256; the 16-byte
 // slot index within a row is XOR-swizzled with a function of the row so that the 16-lane groups of
 // ds_read_b128 / the 32-lane halves of ds_read_b64 hit distinct banks (guide §2 / T2):

@@ -16,6 +16,15 @@ int set_error(int code, const std::string& msg);
             return lg::set_error(LG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
     } while (0)
 
+// launch of a kernel whose dynamic LDS may exceed the 64 KB a kernel gets without asking
+template <class... KArgs, class... Args>
+hipError_t launch_with_lds(void (*kern)(KArgs...), dim3 grid, dim3 threads, int smem, hipStream_t s, const Args&... args) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, threads, smem, s, args...);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- GEMM  (lg_gemm.hip)
 // Y[row, n] = sum_k A[row, k] * W[n, k] (+ bias[n]);  A is fp32 in HBM and converted to the operand
 // precision while it is staged into LDS; W is pre-packed in the operand precision ([Nout][K], K
@@ -199,7 +208,7 @@ struct AdaptArgs {
     int* compact_err;       // set to 1 if a bounded flag wait expired (never expected): the chunk's stores are SKIPPED and the forward reports LG_ERR_DEVICE in io->status
     int* compact_ticket;    // work-item counter of adapt_compact_kernel (reset by adapt_decide_kernel of the same launch_adapt)
     // gather mode (round 6; the product path): no compaction launch — adapt_decide_kernel writes the inverse map `src` (new row -> old row), compacts the index
-    // set in place, bumps the prune counters (ref :555-558) and records in xsel[pair] which buffer set a continuing pair's rows move to (proj_gather_kernel)
+    // set in place, bumps the prune counters (ref :555-558) and records in xsel[pair] which buffer set a continuing pair's rows move to (proj_rows_kernel<GatherRows>)
     int gather; int* src; int* xsel; int xnext;
 };
 hipError_t launch_adapt(const AdaptArgs& a, hipStream_t s);

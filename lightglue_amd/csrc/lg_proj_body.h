@@ -5,6 +5,8 @@
 // XOR-swizzled with pj_tile_off) and NO barrier has been executed since those writes (proj_compute issues its weight
 // prefetch first and then synchronises).
 #pragma once
+#include <type_traits>
+
 #include "lg_kernels.h"
 
 namespace lg {
@@ -29,6 +31,18 @@ template <> struct PJ<PREC_BF16> { typedef TagBF16 Tag; static constexpr int NPA
 template <> struct PJ<PREC_F16> { typedef TagF16 Tag; static constexpr int NPART = 1, APART = 1, OPART = 1; };
 template <> struct PJ<PREC_F16X3> { typedef TagF16 Tag; static constexpr int NPART = 2, APART = 2, OPART = 2; };
 template <> struct PJ<PREC_QKV_F16W2> { typedef TagF16 Tag; static constexpr int NPART = 2, APART = 1, OPART = 1; };
+
+// (linear precision, attention precision) pairs the engine runs: every single-plane precision with its own element type,
+// f16x3 with split q / k / v (default; `plane` = their hi -> lo distance) or with one f16 plane (attention_precision fp16).
+// f(PREC as integral_constant, TA()) launches the instantiation.
+template <class F> hipError_t dispatch_qkv_prec(int prec, int attn_prec, long long plane, F f) {
+    if (prec == PREC_F32 && attn_prec == PREC_F32) return f(std::integral_constant<int, PREC_F32>{}, float());
+    if (prec == PREC_BF16 && attn_prec == PREC_BF16) return f(std::integral_constant<int, PREC_BF16>{}, bf16_t());
+    if (prec == PREC_F16 && attn_prec == PREC_F16) return f(std::integral_constant<int, PREC_F16>{}, f16_t());
+    if (prec == PREC_F16X3 && attn_prec == PREC_F16X3) return plane > 0 ? f(std::integral_constant<int, PREC_F16X3>{}, f16_t()) : hipErrorInvalidValue;
+    if (prec == PREC_F16X3 && attn_prec == PREC_F16) return f(std::integral_constant<int, PREC_QKV_F16W2>{}, f16_t());
+    return hipErrorInvalidValue;
+}
 
 // acc += product of one weight fragment set (NPART planes) and one activation fragment set (APART planes).  TRANSPOSED: the
 // weights are the A operand.  split x split: hi*lo + lo*hi + hi*hi; split weights x single activation: lo*x + hi*x.
@@ -75,6 +89,36 @@ template <int NTP> __device__ __forceinline__ int pj_tile(int w, int pass, int j
     if constexpr (NTP == 3) return j < 2 ? 16 * pass + 2 * w + j : 32 + w + 8 * pass;
     else return pass == 0 ? 2 * w + j : 16 + w + 8 * j;
 }
+// ---- steps shared by the projections and the fused tail (lg_tail.hip)
+// Fragment-packed weights (TailArgs, lg_kernels.h): plane p (plane_bytes apart), n-tile nt, k-chunk kc of NKC -> 64 lanes x 16 B contiguous.  By BUFFER load:
+// descriptor + constant per-lane offset (lane16 = 16 lane) + scalar byte offset (lg_common.h weight_rsrc) — no VALU address arithmetic between MFMA runs.
+template <int NKC> __device__ __forceinline__ u32x4 packed_weight_frag(__amdgpu_buffer_rsrc_t rsrc, int lane16, int p, int plane_bytes, int nt, int kc) {
+    return weight_frag(rsrc, lane16, (p ? plane_bytes : 0) + (nt * NKC + kc) * 1024);
+}
+// hi -> lo plane distance of a projection's weights.  A function, evaluated at each use: held in a local it moved registers in the fused tails.
+template <class Tag> __device__ __forceinline__ int proj_plane_bytes(const ProjArgs& a) { return a.Nout * 256 * (int)sizeof(typename Tag::elem); }
+// 8 values of q / k / v^T -> 16 bytes per plane: hi + lo planes (f16 of the residual, exact subtraction in fp32), one 16-bit plane, or fp32
+template <int PREC, class TA>
+__device__ __forceinline__ void store8_qkv(TA* dst, long long plane, const f32x4& v0, const f32x4& v1) {
+    if constexpr (PJ<PREC>::OPART == 2) {
+        u32x4 hi, lo;
+        split8_f16<true>(v0, v1, hi, lo);
+        *reinterpret_cast<u32x4*>(dst) = hi;
+        *reinterpret_cast<u32x4*>(dst + plane) = lo;
+    } else if constexpr (sizeof(TA) == 2) {
+        *reinterpret_cast<u32x4*>(dst) = pack8<typename PJ<PREC>::Tag>(v0, v1);
+    } else {
+        *reinterpret_cast<f32x4*>(dst) = v0; *reinterpret_cast<f32x4*>(dst + 4) = v1;
+    }
+}
+// 4 values -> 8 bytes of the hi plane at dst and of the lo plane `plane` elements of T on
+template <class T> __device__ __forceinline__ void store4_split(T* dst, long long plane, const f32x4& v) {
+    uint32_t h01, l01, h23, l23;
+    split2_f16(v[0], v[1], h01, l01); split2_f16(v[2], v[3], h23, l23);
+    *reinterpret_cast<u32x2*>(dst) = u32x2{h01, h23};
+    *reinterpret_cast<u32x2*>(dst + plane) = u32x2{l01, l23};
+}
+
 // One pass of the projection.  The kind of a tile decides the FORM of its MFMAs:
 //   q / k tiles: TRANSPOSED, C^T = W x^T (weights as the A operand): lane (lr, g) ends with keypoint row lr of the 16-row tile
 //     and 4 consecutive head channels per tile -> bias as float4s, the rotary pair (2j, 2j+1) sits in one lane (no cross-lane
@@ -110,18 +154,15 @@ __device__ __forceinline__ void proj_pass(const ProjArgs& a, const TileLoc& t, c
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     const long long R = a.R;
     auto stamp = [&](int slot) {   // profiling tap (a.dbg == nullptr in production)
-        if (a.dbg && lane == 0) a.dbg[((long long)blockIdx.x * 8 + w) * 8 + stamp_base + slot] = clock64();
+        if (a.dbg && lane == 0) dbg_slot(a.dbg, w, stamp_base + slot) = clock64();
     };
     const __amdgpu_buffer_rsrc_t wrs = weight_rsrc(a.W);
     const int lane16 = lane * 16;
-    auto wfrag = [&](int p, int nt, int kc) -> u32x4 {
-        return weight_frag(wrs, lane16, (p ? a.Nout * 256 * (int)sizeof(typename Tag::elem) : 0) + (nt * NKC + kc) * 1024);
-    };
     auto load_b = [&](u32x4 (&dst)[NTP][NPART], int pass, int kc) {
 #pragma unroll
         for (int j = 0; j < NTP; ++j)
 #pragma unroll
-            for (int p = 0; p < NPART; ++p) dst[j][p] = wfrag(p, pj_tile<NTP>(w, pass, j), kc);
+            for (int p = 0; p < NPART; ++p) dst[j][p] = packed_weight_frag<NKC>(wrs, lane16, p, proj_plane_bytes<Tag>(a), pj_tile<NTP>(w, pass, j), kc);
     };
     constexpr bool HAS_PAIR = !pj_is_v<NTP>(PASS, 0);          // slots 0, 1 = a q / k pair
     constexpr bool ROPE = NTP == 3;                            // SelfBlock: rotary on q and k (ref :58-65)
@@ -189,7 +230,6 @@ __device__ __forceinline__ void proj_pass(const ProjArgs& a, const TileLoc& t, c
     const bool range_on = a.range_flag != nullptr;
     const int live_rows = range_on ? a.rs.len[t.seg] - t.r0 : 0;
     bool out_of_range = false;
-    auto bad4 = [](const f32x4& v) { return !(fabsf(v[0]) < 65504.f) | !(fabsf(v[1]) < 65504.f) | !(fabsf(v[2]) < 65504.f) | !(fabsf(v[3]) < 65504.f); };
     constexpr int OPART = PJ<PREC>::OPART;
     static_assert(OPART == 1 || sizeof(TA) == 2, "split q / k / v planes are f16");
     if constexpr (HAS_PAIR) {                                  // q / k (or qk) pair: 8 consecutive channels per lane and keypoint row
@@ -208,18 +248,9 @@ __device__ __forceinline__ void proj_pass(const ProjArgs& a, const TileLoc& t, c
                 v1[2] = u1[2] * c[3] - u1[3] * sn[3]; v1[3] = u1[3] * c[3] + u1[2] * sn[3];
             }
             v0 *= QK_PRESCALE; v1 *= QK_PRESCALE;
-            if (range_on && pj_row<MT>(mt, lr) < live_rows) out_of_range |= bad4(v0) | bad4(v1);
+            if (range_on && pj_row<MT>(mt, lr) < live_rows) out_of_range |= out_of_f16_range(v0) | out_of_f16_range(v1);
             TA* dst = base + ((long long)head * R + row) * 64 + d0 + 8 * g;
-            if constexpr (OPART == 2) {                        // hi plane + lo plane (f16 of the residual, exact subtraction in fp32)
-                u32x4 hi, lo;
-                split8_f16<true>(v0, v1, hi, lo);
-                *reinterpret_cast<u32x4*>(dst) = hi;
-                *reinterpret_cast<u32x4*>(dst + a.plane) = lo;
-            } else if constexpr (sizeof(TA) == 2) {
-                *reinterpret_cast<u32x4*>(dst) = pack8<Tag>(v0, v1);
-            } else {
-                *reinterpret_cast<f32x4*>(dst) = v0; *reinterpret_cast<f32x4*>(dst + 4) = v1;
-            }
+            store8_qkv<PREC>(dst, a.plane, v0, v1);
         }
     }
 #pragma unroll
@@ -236,33 +267,21 @@ __device__ __forceinline__ void proj_pass(const ProjArgs& a, const TileLoc& t, c
                 if (range_on) {   // rows 32 q + 8 g + 0..3 (v0) and + 4..7 (v1)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        out_of_range |= (32 * q + 8 * g + r < live_rows) & !(fabsf(v0[r]) < 65504.f);
-                        out_of_range |= (32 * q + 8 * g + 4 + r < live_rows) & !(fabsf(v1[r]) < 65504.f);
+                        out_of_range |= (32 * q + 8 * g + r < live_rows) & out_of_f16_range(v0[r]);
+                        out_of_range |= (32 * q + 8 * g + 4 + r < live_rows) & out_of_f16_range(v1[r]);
                     }
                 }
-                if constexpr (OPART == 2) {
-                    u32x4 hi, lo;
-                    split8_f16<true>(v0, v1, hi, lo);
-                    *reinterpret_cast<u32x4*>(dst) = hi;
-                    *reinterpret_cast<u32x4*>(dst + a.plane) = lo;
-                } else if constexpr (sizeof(TA) == 2) {
-                    *reinterpret_cast<u32x4*>(dst) = pack8<Tag>(v0, v1);
-                } else {
-                    *reinterpret_cast<f32x4*>(dst) = v0; *reinterpret_cast<f32x4*>(dst + 4) = v1;
-                }
+                store8_qkv<PREC>(dst, a.plane, v0, v1);
             }
         } else {
             const f32x4 v = acc[0][j] + bv[j];
             TA* dst = vrow + 4 * g;
             if (range_on) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) out_of_range |= (4 * g + r < live_rows) & !(fabsf(v[r]) < 65504.f);
+                for (int r = 0; r < 4; ++r) out_of_range |= (4 * g + r < live_rows) & out_of_f16_range(v[r]);
             }
             if constexpr (OPART == 2) {
-                uint32_t h01, l01, h23, l23;
-                split2_f16(v[0], v[1], h01, l01); split2_f16(v[2], v[3], h23, l23);
-                *reinterpret_cast<u32x2*>(dst) = u32x2{h01, h23};
-                *reinterpret_cast<u32x2*>(dst + a.plane) = u32x2{l01, l23};
+                store4_split(dst, a.plane, v);
             } else {
                 ta4 o = {pj_cvt<TA>(v[0]), pj_cvt<TA>(v[1]), pj_cvt<TA>(v[2]), pj_cvt<TA>(v[3])};
                 *reinterpret_cast<ta4*>(dst) = o;
@@ -289,16 +308,14 @@ __device__ __forceinline__ void proj_compute(const ProjArgs& a, const TileLoc& t
 #pragma unroll
         for (int j = 0; j < NTP; ++j)
 #pragma unroll
-            for (int p = 0; p < NPART; ++p) {
-                bf[i][j][p] = weight_frag(weight_rsrc(a.W), lane * 16, (p ? a.Nout * 256 * (int)sizeof(typename Tag::elem) : 0) + (pj_tile<NTP>(w, 0, j) * NKC + i) * 1024);
-            }
+            for (int p = 0; p < NPART; ++p) bf[i][j][p] = packed_weight_frag<NKC>(weight_rsrc(a.W), lane * 16, p, proj_plane_bytes<Tag>(a), pj_tile<NTP>(w, 0, j), i);
     // the rotary rows are fetched ONCE (the q pass and the k pass rotate by the same rows) and AHEAD of the MFMA loops, behind the first weight
     // fragments in the in-order load queue; the standalone kernel requests them before its x tile (both cold, in flight together), the fused tail
     // has touched them into L2 a GELU step earlier.  Round 3 fetched them at the head of each pass's epilogue: two exposed round trips.
     RopeRows<MT> rr;
     if constexpr (NTP == 3) { if (preloaded) rr = *preloaded; else proj_rope_load<MT>(a, t, rr); }
     __syncthreads();   // the activation tile is complete
-    if (a.dbg && lane == 0) a.dbg[((long long)blockIdx.x * 8 + w) * 8 + stamp_base + 1] = clock64();
+    if (a.dbg && lane == 0) dbg_slot(a.dbg, w, stamp_base + 1) = clock64();
     proj_pass<PREC, TA, NTP, NPASS, 0, A_PLANE, MT, AHEAD>(a, t, smA, bf, stamp_base, rr);
     proj_pass<PREC, TA, NTP, NPASS, 1, A_PLANE, MT, AHEAD>(a, t, smA, bf, stamp_base, rr);
 }
@@ -319,14 +336,12 @@ __device__ __forceinline__ void final_compute(const FinalArgs& a, const TileLoc&
     const __amdgpu_buffer_rsrc_t wrs = weight_rsrc(static_cast<const char*>(a.W) + (long long)layer * a.w_layer_bytes);
     const float* bias = a.bias + (long long)layer * 256;
     const int lane16 = lane * 16;
-    auto wfrag = [&](int p, int nt, int kc) -> u32x4 {
-        return weight_frag(wrs, lane16, (p ? 256 * 256 * (int)sizeof(typename Tag::elem) : 0) + (nt * NKC + kc) * 1024);
-    };
+    constexpr int plane_bytes = 256 * 256 * (int)sizeof(typename Tag::elem);
     auto load_b = [&](u32x4 (&dst)[2][NPART], int kc) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int p = 0; p < NPART; ++p) dst[j][p] = wfrag(p, 2 * w + j, kc);
+            for (int p = 0; p < NPART; ++p) dst[j][p] = packed_weight_frag<NKC>(wrs, lane16, p, plane_bytes, 2 * w + j, kc);
     };
     u32x4 bf[NBUF][2][NPART];
 #pragma unroll
@@ -370,10 +385,7 @@ __device__ __forceinline__ void final_compute(const FinalArgs& a, const TileLoc&
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const f32x4 v = (acc[mt][j] + b4[j]) * a.scale;
-                    uint32_t h01, l01, h23, l23;
-                    split2_f16(v[0], v[1], h01, l01); split2_f16(v[2], v[3], h23, l23);
-                    *reinterpret_cast<u32x2*>(dst + 16 * j) = u32x2{h01, h23};
-                    *reinterpret_cast<u32x2*>(dst + 16 * j + plane) = u32x2{l01, l23};
+                    store4_split(dst + 16 * j, plane, v);
                 }
             }
             return;

@@ -51,19 +51,17 @@ constexpr int TTHREADS = 512;
 #define LG_TAIL_CTX_DMA 1   // ctx half of the activation tile by piecewise LDS-DMA under the x half's MFMAs (A/B switch; 0 = the round-4 register path)
 #endif
 
-template <int PREC> struct TT;
-template <> struct TT<PREC_F32> { typedef TagF32 Tag; static constexpr int KE = 32, NPART = 1; };
-template <> struct TT<PREC_BF16> { typedef TagBF16 Tag; static constexpr int KE = 64, NPART = 1; };
-template <> struct TT<PREC_F16> { typedef TagF16 Tag; static constexpr int KE = 64, NPART = 1; };
-template <> struct TT<PREC_F16X3> { typedef TagF16 Tag; static constexpr int KE = 64, NPART = 2; };
+// Operand scheme, element tag and K elements per 128-byte stage row of a precision: PJ<PREC> / PJL<PREC>::KE (lg_proj_body.h); activations and weights have
+// the same number of planes here (NPART).  Every product is pj_mma<PREC, true>: C^T tile += w x^T for one k-chunk, split-f16 as
+// (w_hi x_lo) + (w_lo x_hi) + (w_hi x_hi).
 
 // LDS map (bytes):  [0, G_BYTES) g tiles  — aliased during phase A by the two staging buffers
 //                   [G_BYTES, +RED_BYTES) cross-wave reduction scratch
 template <int PREC, int MT = 4> struct TL {
-    static constexpr int STAGES = 512 / TT<PREC>::KE;               // K stages of the 512-long contractions
+    static constexpr int STAGES = 512 / PJL<PREC>::KE;              // K stages of the 512-long contractions
     static constexpr int TILE = MT * 16 * 128;                      // one plane of one stage: MT*16 rows x 128 B
     static constexpr int G_PLANE = STAGES * TILE;                   // 64 KB (16-bit) / 128 KB (f32)
-    static constexpr int G_BYTES = TT<PREC>::NPART * G_PLANE;
+    static constexpr int G_BYTES = PJ<PREC>::NPART * G_PLANE;
     static constexpr int RED_BYTES = 8 * MT * 16 * 8;               // (mean, M2) per row per wave
     static constexpr int TOTAL = G_BYTES + RED_BYTES;
 };
@@ -89,19 +87,13 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 u) {
     const f32x2 half_u = u * 0.5f;
     return a * wgt + half_u;
 }
-__device__ __forceinline__ f32x2 gelu_pair(f32x2 u) { return gelu_fast2(u); }
-
-// acc (C^T tile) += w x^T for one k-chunk; split-f16: (w_hi x_lo) + (w_lo x_hi) + (w_hi x_hi)
-template <int PREC>
-__device__ __forceinline__ void tail_mma(f32x4& acc, const u32x4* wf, const u32x4* xf) {
-    typedef typename TT<PREC>::Tag Tag;
-    if constexpr (TT<PREC>::NPART == 2) {
-        mma_chunk<Tag>(acc, wf[0], xf[1]);   // hi * lo
-        mma_chunk<Tag>(acc, wf[1], xf[0]);   // lo * hi
-        mma_chunk<Tag>(acc, wf[0], xf[0]);   // hi * hi
-    } else {
-        mma_chunk<Tag>(acc, wf[0], xf[0]);
-    }
+// ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)) over the eight per-wave partials of a row, which lie in LDS as (even, odd) pairs = four float4s.  The
+// order is part of the result: the LayerNorm statistics and the heads are bit-compared between kernel shapes.
+__device__ __forceinline__ float sum8_even(const f32x4& p0, const f32x4& p1, const f32x4& p2, const f32x4& p3) {
+    return ((p0[0] + p0[2]) + (p1[0] + p1[2])) + ((p2[0] + p2[2]) + (p3[0] + p3[2]));
+}
+__device__ __forceinline__ float sum8_odd(const f32x4& p0, const f32x4& p1, const f32x4& p2, const f32x4& p3) {
+    return ((p0[1] + p0[3]) + (p1[1] + p1[3])) + ((p2[1] + p2[3]) + (p3[1] + p3[3]));
 }
 
 // NEXT: 0 = plain tail, 1 = + SelfBlock projection of the next layer (768 columns, rotary), 2 = + CrossBlock
@@ -115,8 +107,8 @@ __device__ __forceinline__ void tail_mma(f32x4& acc, const u32x4* wf, const u32x
 template <int PREC, int NEXT, class TA, int MT, bool ASPLIT>
 __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
     constexpr int TBM = 16 * MT;
-    typedef typename TT<PREC>::Tag Tag;
-    constexpr int EPC = Tag::EPC, KE = TT<PREC>::KE, NPART = TT<PREC>::NPART;
+    typedef typename PJ<PREC>::Tag Tag;
+    constexpr int EPC = Tag::EPC, KE = PJL<PREC>::KE, NPART = PJ<PREC>::NPART;
     constexpr int STAGES = TL<PREC, MT>::STAGES, TILE = TL<PREC, MT>::TILE, G_PLANE = TL<PREC, MT>::G_PLANE;
     constexpr int NKC = 2 * STAGES;          // 16-byte k-chunks per row (16 for 16-bit, 32 for f32)
     constexpr int NV = EPC / 4;              // float4 loads per staged chunk
@@ -131,10 +123,10 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     // optional per-phase shader-clock stamps (profiling tap; a.dbg == nullptr in production)
     auto stamp = [&](int slot) {
-        if (a.dbg && lane == 0) a.dbg[((long long)blockIdx.x * 8 + w) * 8 + slot] = clock64();
+        if (a.dbg && lane == 0) dbg_slot(a.dbg, w, slot) = clock64();
     };
     stamp(0);
-    if (a.dbg && lane == 0) a.dbg[((long long)blockIdx.x * 8 + w) * 8 + 6] = wall_clock64();   // 100 MHz wall clock: occupancy timeline (tools/tail_wall.py)
+    if (a.dbg && lane == 0) dbg_slot(a.dbg, w, 6) = wall_clock64();   // 100 MHz wall clock: occupancy timeline (tools/tail_wall.py)
     // guide T5, static form: the second-dispatched half of an 8-wave workgroup loses issue arbitration to the older half on
     // every phase; one priority bump for it, no per-cluster flips (measured: tail -0.2 ... -1.3 %)
     if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
@@ -150,13 +142,10 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
         for (int i = 0; i < MT; ++i) acc[i][j] = b4;
     }
 
-    // weight fragment: plane p, n-tile nt, k-chunk kc -> 64 lanes x 16 B contiguous
-    // by BUFFER load (lg_common.h weight_rsrc): descriptor + constant per-lane offset + scalar byte offset — no VALU address arithmetic between MFMA runs
+    // weight fragments by BUFFER load (lg_proj_body.h packed_weight_frag)
     const __amdgpu_buffer_rsrc_t Wc = weight_rsrc(a.Wcat), W2 = weight_rsrc(a.W2);
     const int lane16 = lane * 16;
-    auto wfrag = [&](__amdgpu_buffer_rsrc_t base, int p, long long plane_elems, int nt, int kc) -> u32x4 {
-        return weight_frag(base, lane16, (p ? (int)(plane_elems * (long long)sizeof(typename Tag::elem)) : 0) + (nt * NKC + kc) * 1024);
-    };
+    constexpr int ESZ = (int)sizeof(typename Tag::elem);
 
     // ---- activation tile -> LDS.  Half hf (0: x, 1: ctx) = TBM rows x 256 floats = STAGES/2 K-stage tiles.
     // A stage tile is TBM rows x 8 chunks of 16 bytes = 128 MT threads' worth, so the 512 threads cover 4 / MT stage tiles
@@ -199,9 +188,9 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-            for (int p = 0; p < NPART; ++p) dst[nt][p] = wfrag(Wc, p, 512LL * 512, w + 8 * nt, kc);
+            for (int p = 0; p < NPART; ++p) dst[nt][p] = packed_weight_frag<NKC>(Wc, lane16, p, 512 * 512 * ESZ, w + 8 * nt, kc);
     };
-    // activation fragments of one k-chunk (4 row tiles x planes) from the LDS-resident tile
+    // activation fragments of one k-chunk (4 row tiles x planes) from the LDS-resident tile: the [x ; ctx] tile in phase A, the g tile in phase B
     auto read_af = [&](u32x4 (&af)[MT][NPART], int kc) {
         const char* tile = smem + (kc >> 1) * TILE;
 #pragma unroll
@@ -214,7 +203,7 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
 #pragma unroll
         for (int mt = mt0; mt < mt1; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt) tail_mma<PREC>(acc[mt][nt], b[nt], af[mt]);
+            for (int nt = 0; nt < 4; ++nt) pj_mma<PREC, true>(acc[mt][nt], b[nt], af[mt]);
     };
     auto mma_A = [&](const u32x4 (&af)[MT][NPART], const u32x4 (&b)[4][NPART]) { mma_A_rows(af, b, 0, MT); };
     load_half(0);
@@ -338,8 +327,8 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
             // merge the 8 (count 64, mean, M2) triples of the row: mean = avg(mean_w), M2 = sum M2_w + 64 sum (mean_w - mean)^2
             const f32x4* pr = reinterpret_cast<const f32x4*>(red2 + (mt * 16 + lr) * 8);
             const f32x4 p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3];
-            const float mean = (((p0[0] + p0[2]) + (p1[0] + p1[2])) + ((p2[0] + p2[2]) + (p3[0] + p3[2]))) * 0.125f;
-            float m2 = ((p0[1] + p0[3]) + (p1[1] + p1[3])) + ((p2[1] + p2[3]) + (p3[1] + p3[3]));
+            const float mean = sum8_even(p0, p1, p2, p3) * 0.125f;
+            float m2 = sum8_odd(p0, p1, p2, p3);
             float dm = 0.f;
             { float d;
               d = p0[0] - mean; dm += d * d; d = p0[2] - mean; dm += d * d; d = p1[0] - mean; dm += d * d; d = p1[2] - mean; dm += d * d;
@@ -359,16 +348,13 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
     auto gelu_store = [&](int j, int mt0 = 0, int mt1 = MT) {
 #pragma unroll
         for (int mt = mt0; mt < mt1; ++mt) {
-            const f32x2 v01 = gelu_pair(f32x2{acc[mt][j][0], acc[mt][j][1]});
-            const f32x2 v23 = gelu_pair(f32x2{acc[mt][j][2], acc[mt][j][3]});
+            const f32x2 v01 = gelu_fast2(f32x2{acc[mt][j][0], acc[mt][j][1]});
+            const f32x2 v23 = gelu_fast2(f32x2{acc[mt][j][2], acc[mt][j][3]});
             const int row = mt * 16 + lr;
             if constexpr (EPC == 8) {
                 char* dst = smem + (2 * j + (w >> 2)) * TILE + lds_off<128>(row, (w & 3) * 2 + (g >> 1)) + (g & 1) * 8;
                 if constexpr (PREC == PREC_F16X3) {
-                    uint32_t h01, l01, h23, l23;
-                    split2_f16(v01[0], v01[1], h01, l01); split2_f16(v23[0], v23[1], h23, l23);
-                    *reinterpret_cast<u32x2*>(dst) = u32x2{h01, h23};
-                    *reinterpret_cast<u32x2*>(dst + G_PLANE) = u32x2{l01, l23};
+                    store4_split(dst, G_PLANE, f32x4{v01[0], v01[1], v23[0], v23[1]});
                 } else {
                     *reinterpret_cast<u32x2*>(dst) = u32x2{pack2<Tag>(v01[0], v01[1]), pack2<Tag>(v23[0], v23[1])};
                 }
@@ -387,25 +373,17 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int p = 0; p < NPART; ++p) dst[nt][p] = wfrag(W2, p, 256LL * 512, w * 2 + nt, kc);
+            for (int p = 0; p < NPART; ++p) dst[nt][p] = packed_weight_frag<NKC>(W2, lane16, p, 256 * 512 * ESZ, w * 2 + nt, kc);
     };
     // activation (g) fragments of one k-chunk, read one chunk AHEAD of their MFMAs inside a step (two register sets, as in phase A; round-4 ISA: read
     // right in front of the MFMAs they cost every chunk an exposed LDS round trip).  A step's first chunk reads its own: the tile it needs is
     // published by the barrier in front of it.
     u32x4 afB[2][MT][NPART];
-    auto read_afB = [&](u32x4 (&af)[MT][NPART], int kc) {
-        const char* tile = smem + (kc >> 1) * TILE;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int p = 0; p < NPART; ++p)
-                af[mt][p] = *reinterpret_cast<const u32x4*>(tile + p * G_PLANE + lds_off<128>(mt * 16 + lr, (kc & 1) * 4 + g));
-    };
     auto mma_B = [&](const u32x4 (&af)[MT][NPART], const u32x4 (&b)[2][NPART]) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) tail_mma<PREC>(acc2[mt][nt], b[nt], af[mt]);
+            for (int nt = 0; nt < 2; ++nt) pj_mma<PREC, true>(acc2[mt][nt], b[nt], af[mt]);
     };
     load_b_B(b2f[0], 0); load_b_B(b2f[1], 1); load_b_B(b2f[2], 2);
     // The fused SelfBlock projection rotates q and k by the rotary rows of this tile (64 rows x 128 B per table, cold).  Touch every line now — behind
@@ -453,10 +431,10 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
             // MFMAs) ahead of their MFMAs instead of 3 (tools/isa_wait_distance.py); sched_barrier masks that let the GELU arithmetic float did
             // not hold the loads (the MFMAs moved instead), so the windows are closed and the GELU of the next n-tile is dealt to them by hand:
             // row tile i of n-tile j + 1 with chunk i.  cfg #2 +0.7 %, cfg #5' +2 % (profiles/r04e_*, r04f_*).
-            if (i == 0) read_afB(afB[0], kc);
+            if (i == 0) read_af(afB[0], kc);
             __builtin_amdgcn_sched_barrier(0);
             if (kc + 3 < NKC) load_b_B(b2f[(kc + 3) & 3], kc + 3);
-            if (i + 1 < CPS) read_afB(afB[(i + 1) & 1], kc + 1);
+            if (i + 1 < CPS) read_af(afB[(i + 1) & 1], kc + 1);
             __builtin_amdgcn_sched_barrier(0);
             // the chunk's GELU piece as ONE block in FRONT of its MFMA run (round 4, call p: left in the same window hipcc sprinkles 3 - 5 VALU between every
             // two MFMAs; as a block behind the run +-0, in front of it tail -1.1 %: a wave's VALU block then meets its partner's MFMA run)
@@ -486,7 +464,7 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
             const f32x4 xn = xres[mt][nt] + (acc2[mt][nt] + b2);
             if (t.r0 + row < qlen) {
                 *reinterpret_cast<f32x4*>(a.X + (long long)(t.grow0 + row) * 256 + col) = xn;
-                if (range_on) out_of_range |= !(fabsf(xn[0]) < 65504.f) | !(fabsf(xn[1]) < 65504.f) | !(fabsf(xn[2]) < 65504.f) | !(fabsf(xn[3]) < 65504.f);
+                if (range_on) out_of_range |= out_of_f16_range(xn);
             }
             if (heads) {
                 hp0[mt] += (xn[0] * hw0[nt][0] + xn[1] * hw0[nt][1]) + (xn[2] * hw0[nt][2] + xn[3] * hw0[nt][3]);
@@ -496,10 +474,7 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
                 static_assert(EPC == 8, "fused next projection: 16-bit operands only");
                 char* dst = smem + (col >> 6) * TILE + pj_tile_off(row, (col & 63) >> 3) + (col & 7) * 2;   // the projection's own swizzle (lg_proj_body.h)
                 if constexpr (NPART == 2 && (ASPLIT || NEXT == 3)) {   // hi + lo planes of the new x tile (the final projection always takes both) (lo at G_PLANE: K-stages 0..3 of the lo g plane are just as dead)
-                    uint32_t h01, l01, h23, l23;
-                    split2_f16(xn[0], xn[1], h01, l01); split2_f16(xn[2], xn[3], h23, l23);
-                    *reinterpret_cast<u32x2*>(dst) = u32x2{h01, h23};
-                    *reinterpret_cast<u32x2*>(dst + G_PLANE) = u32x2{l01, l23};
+                    store4_split(dst, G_PLANE, xn);
                 } else if constexpr (NPART == 2) {      // the projection takes ONE f16 plane (PREC_QKV_F16W2, lg_proj_body.h)
                     *reinterpret_cast<u32x2*>(dst) = u32x2{pack2_f16(xn[0], xn[1]), pack2_f16(xn[2], xn[3])};
                 } else {
@@ -529,8 +504,8 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
                     if (lsneg) lsneg[t.grow0 + tid] = fminf(-z, 0.f) - sp;
                 }
             };
-            emit((((p0[0] + p0[2]) + (p1[0] + p1[2])) + ((p2[0] + p2[2]) + (p3[0] + p3[2]))) + a.head_b0[0], a.head_out0, a.head_ls0, a.head_lsneg0);
-            if (a.head_w1) emit((((p0[1] + p0[3]) + (p1[1] + p1[3])) + ((p2[1] + p2[3]) + (p3[1] + p3[3]))) + a.head_b1[0], a.head_out1, a.head_ls1, a.head_lsneg1);
+            emit(sum8_even(p0, p1, p2, p3) + a.head_b0[0], a.head_out0, a.head_ls0, a.head_lsneg0);
+            if (a.head_w1) emit(sum8_odd(p0, p1, p2, p3) + a.head_b1[0], a.head_out1, a.head_ls1, a.head_lsneg1);
         }
     }
     stamp(5);
@@ -538,17 +513,12 @@ __global__ __launch_bounds__(TTHREADS) void tail_kernel(TailArgs a) {
     if constexpr (NEXT == 3) final_compute<PREC, G_PLANE, MT>(a.fin, t, smem);
     else if constexpr (NEXT != 0) proj_compute<(prec_is_split(PREC) ? (ASPLIT ? PREC_F16X3 : PREC_QKV_F16W2) : PREC), TA, NEXT == 1 ? 3 : 2, 2, G_PLANE, MT, true>(a.next, t, smem, 0);
     if (a.dbg && lane == 0)   // wall clock at the end + where the workgroup ran (HW_ID, XCC_ID)
-        a.dbg[((long long)blockIdx.x * 8 + w) * 8 + 7] = (wall_clock64() & ((1LL << 44) - 1)) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFF00) << 40) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 44);
+        dbg_slot(a.dbg, w, 7) = (wall_clock64() & ((1LL << 44) - 1)) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFF00) << 40) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 44);
 }
 
 template <int PREC, int NEXT, class TA, int MT, bool ASPLIT> static hipError_t launch_tail_m(const TailArgs& a, hipStream_t s) {
     const int R = a.rs.B * (a.rs.cap0 + a.rs.cap1);
-    auto kern = tail_kernel<PREC, NEXT, TA, MT, ASPLIT>;
-    constexpr int smem = TL<PREC, MT>::TOTAL;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(R / (16 * MT)), dim3(TTHREADS), smem, s, a);
-    return hipGetLastError();
+    return launch_with_lds(tail_kernel<PREC, NEXT, TA, MT, ASPLIT>, dim3(R / (16 * MT)), dim3(TTHREADS), TL<PREC, MT>::TOTAL, s, a);
 }
 template <int PREC, int NEXT, class TA, bool ASPLIT> static hipError_t launch_tail_t(const TailArgs& a, hipStream_t s) {
     if constexpr (PREC == PREC_F32) return launch_tail_m<PREC, NEXT, TA, 4, false>(a, s);   // (the exact mode keeps one shape)

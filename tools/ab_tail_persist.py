@@ -4,6 +4,7 @@ ragged fixed-depth batches (incl. NaN-poisoned padding and tile counts that are 
 the per-class kernel times, alternating the two forms inside one process (same box, same clock state).
 
 The kernel form lives in tools/experiments/tail_persist.patch (apply to lightglue_amd/csrc, `make`): measured +-0 and not adopted (LAB_NOTES.md round 6, call pa - pc).
+The patch applies at commit e4037d6, not to the tree (the projection and tail kernels' shared steps were written once after it; it was not ported).
 
 usage: ab_tail_persist.py [--check-only] [--rounds 3] [--steps 40]"""
 import argparse
