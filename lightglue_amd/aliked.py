@@ -176,6 +176,24 @@ class ALIKED(nn.Module):
                                              scores.data_ptr(), C.c_void_p(stream)))
         return scores, levels
 
+    @staticmethod
+    def level_maps(levels: torch.Tensor, shape):
+        """The four level maps x1 .. x4 inside the opaque `levels` buffer of `encode` / `describe` for images of `shape` = (B, H, W): float32
+        views [B, Hp >> s, Wp >> s, 32] for s = 0, 1, 3, 5 (NHWC, after conv1 .. conv4 + SELU) that share its memory, so a caller can read
+        the encoder's levels or write its own.  Restates the layout of lg_aliked.hip: Hp, Wp from InputPadder(divis_by=32) (`dims_of`), each
+        level's size rounded up to 256 bytes (`level_layout`); the total is checked against lg_aliked_levels_bytes."""
+        bsz, h, w = shape
+        hp, wp = h + ((h // 32 + 1) * 32 - h) % 32, w + ((w // 32 + 1) * 32 - w) % 32
+        dims = [(bsz, hp >> s, wp >> s, 32) for s in (0, 1, 3, 5)]
+        offsets, used = [], 0
+        for d in dims:
+            offsets.append(used)
+            used += (4 * d[0] * d[1] * d[2] * d[3] + 255) // 256 * 256
+        total = _cabi.load().lg_aliked_levels_bytes(bsz, h, w)
+        assert used == total and levels.dtype == torch.uint8 and levels.dim() == 1 and levels.numel() >= total, \
+            f"level layout: {used} bytes restated here, lg_aliked_levels_bytes says {total}, the buffer has {levels.numel()}"
+        return [levels[o:o + 4 * d[0] * d[1] * d[2] * d[3]].view(torch.float32).view(d) for o, d in zip(offsets, dims)]
+
     @torch.no_grad()
     def detect(self, scores: torch.Tensor, image_size: Optional[torch.Tensor] = None):
         """DKD (ref :94-262) on a score map [B, H, W] -> keypoints [B, cap, 2] (pixels), scores [B, cap], normalised keypoints [B, cap, 2], counts [B]."""

@@ -93,3 +93,23 @@ def test_cabi_refusals_without_gpu():
     # encode workspace + level maps of a 1024 x 768 image: far below the 128-channel dense map (which is never written)
     b, h, w = 1, 768, 1024
     assert lib.lg_aliked_workspace_bytes(b, h, w, 16) + lib.lg_aliked_levels_bytes(b, h, w) < b * h * w * 128 * 4
+
+
+@pytest.mark.parametrize("shape", [(1, 8, 8), (2, 31, 33), (3, 40, 56), (1, 40, 300), (2, 64, 96)])
+def test_level_maps_views_tile_the_buffer(shape):
+    """ALIKED.level_maps restates lg_aliked.hip's level layout: its total is lg_aliked_levels_bytes (asserted inside), the views are
+    [B, Hp >> s, Wp >> s, 32] at 256-byte aligned offsets, they share the buffer's memory and do not overlap."""
+    from lightglue_amd import ALIKED, _cabi
+    b, h, w = shape
+    buf = torch.zeros(_cabi.load().lg_aliked_levels_bytes(b, h, w), dtype=torch.uint8)
+    maps = ALIKED.level_maps(buf, shape)
+    hp, wp = (h + 31) // 32 * 32, (w + 31) // 32 * 32
+    assert [tuple(m.shape) for m in maps] == [(b, hp >> s, wp >> s, 32) for s in (0, 1, 3, 5)]
+    for i, m in enumerate(maps):
+        assert m.dtype == torch.float32 and m.is_contiguous() and (m.data_ptr() - buf.data_ptr()) % 256 == 0
+        m.fill_(float(i + 1))
+    for i, m in enumerate(maps):
+        assert (m == float(i + 1)).all()
+        assert i == 0 or m.data_ptr() >= maps[i - 1].data_ptr() + 4 * maps[i - 1].numel()
+    with pytest.raises(AssertionError, match="level layout"):
+        ALIKED.level_maps(buf[:-256], shape)

@@ -12,7 +12,13 @@ none of which exist here, so the module is executed standalone with stand-ins fo
     tests/test_aliked_cpu.py checks it against F.conv2d at zero offset and against a grid_sample construction at other offsets.
 The fixtures store the unpadded score map and the outputs; weights and images are regenerated from seeds by `aliked_state_dict` /
 `aliked_image`, which never touch the reference (the GPU tests import them).
-    python tools/make_golden_aliked.py
+
+`--stages` writes tests/golden/aliked_stages/*.npz instead: the reference's own DKD and SDDH modules on the seeded crafted inputs of the
+"stage inputs" section below (score maps, level maps, keypoints; plain functions that never touch the reference either).  Those fixtures hold
+the reference's outputs and the case parameters only; they pin oracle/aliked_oracle.py (tests/test_aliked_oracle_cpu.py), which the GPU stage
+tests then compare the kernels with.
+    python tools/make_golden_aliked.py [NAME ...] # whole-model fixtures (all, or the named cases)
+    python tools/make_golden_aliked.py --stages   # stage fixtures
 """
 from __future__ import annotations
 
@@ -31,6 +37,9 @@ REF = Path("/root/reference/lightglue/aliked.py")
 GOLD = ROOT / "tests" / "golden" / "aliked"
 SCORE_GAIN = 2.5   # score_head.6 weight scale of the seeded networks: sigmoid scores spread over ~(0.01, 0.9), no ties at 1.0
 
+# (weight seed, image seed) of the small-image cases
+SEED_8X8, SEED_8X8_ZERO, SEED_31X33, SEED_40X300 = (10, 10), (9, 9), (52, 52), (65, 65)
+
 # name -> (model, weight seed, image seed, B, C, H, W, conf)
 CASES = {
     "n16_rgb_b1_120x160_th": ("aliked-n16", 0, 0, 1, 3, 120, 160, {"detection_threshold": 0.5}),
@@ -39,6 +48,11 @@ CASES = {
     "n16_gray_b1_96x128_fallback": ("aliked-n16", 3, 3, 1, 1, 96, 128, {"detection_threshold": 0.9999}),
     "n32_rgb_b1_240x320_limit300": ("aliked-n32", 4, 4, 1, 3, 240, 320, {"detection_threshold": 0.3, "max_num_keypoints": 300}),
     "n16_rgb_b1_96x128_r6": ("aliked-n16", 8, 8, 1, 3, 96, 128, {"detection_threshold": 0.3, "nms_radius": 6}),
+    # images that pad to ONE 32-pixel tile row / column (a 1 x 1, 1 x 2, 2 x 10 fourth level); seeds chosen for margins >= 1e-4
+    "n16_rgb_b1_8x8_min": ("aliked-n16", SEED_8X8[0], SEED_8X8[1], 1, 3, 8, 8, {"detection_threshold": 0.2}),
+    "n16_rgb_b1_8x8_zero": ("aliked-n16", SEED_8X8_ZERO[0], SEED_8X8_ZERO[1], 1, 3, 8, 8, {"detection_threshold": 0.2}),   # no keypoint: forward with nmax == 0
+    "n16_gray_b2_31x33_top20": ("aliked-n16", SEED_31X33[0], SEED_31X33[1], 2, 1, 31, 33, {"detection_threshold": -1, "max_num_keypoints": 20}),
+    "n32_rgb_b1_40x300_th": ("aliked-n32", SEED_40X300[0], SEED_40X300[1], 1, 3, 40, 300, {"detection_threshold": 0.2}),
 }
 # ragged pair: two images of one size, each run by the reference on its own (its torch.stack needs equal counts), batched on the GPU
 RAGGED = {"n16_rgb_ragged_2x80x104": ("aliked-n16", 5, (6, 7), 3, 80, 104, {"detection_threshold": 0.45})}
@@ -90,6 +104,158 @@ def aliked_image(seed: int, b: int, h: int, w: int, c: int = 3) -> torch.Tensor:
         t += 0.15 * rng.standard_normal((c, h, w)).astype(np.float32)
         img[i] = np.clip(t, 0.0, 1.0)
     return torch.from_numpy(img)
+
+
+# ---------------------------------------------------------------------------------------------------- stage inputs
+def score_maps(seed: int, b: int, h: int, w: int) -> np.ndarray:
+    """[b, h, w] fp32, independent uniform(0.05, 0.95) pixels: about one NMS maximum per (2r+1)^2 pixels, all above ALIKED's 0.2 rarely tied"""
+    rng = np.random.Generator(np.random.PCG64(500 + seed))
+    return rng.uniform(0.05, 0.95, (b, h, w)).astype(np.float32)
+
+
+def quantised_maps(seed: int, b: int, h: int, w: int) -> np.ndarray:
+    """score_maps rounded to 1/16: a dozen distinct values, so NMS plateaus and large tie groups at every cut"""
+    return (np.round(score_maps(seed, b, h, w) * 16) / 16).astype(np.float32)
+
+
+def plateau_maps(h: int = 48, w: int = 80) -> np.ndarray:
+    """[3, h, w]: constant 0.5 (every pixel an NMS maximum, all tied); 0.75 in the top half, 0.5 below; 0.75 in the top quarter, 0.5 below"""
+    m = np.full((3, h, w), 0.5, np.float32)
+    m[1, : h // 2] = 0.75
+    m[2, : h // 4] = 0.75
+    return m
+
+
+def ulp_ladder_map(seed: int, h: int, w: int, r: int):
+    """([1, h, w] map, number of peaks): isolated peaks every 2r + 1 pixels from (r, r) on a 0.01 background, valued by the consecutive fp32 bit
+    patterns 0x3F000001, 0x3F000002, ... (fewer than 256: they agree in their top 24 bits) in shuffled order"""
+    m = np.full((1, h, w), 0.01, np.float32)
+    ys, xs = np.arange(r, h - r, 2 * r + 1), np.arange(r, w - r, 2 * r + 1)
+    n = len(ys) * len(xs)
+    assert n < 256
+    bits = (np.uint32(0x3F000001) + np.random.Generator(np.random.PCG64(600 + seed)).permutation(n).astype(np.uint32)).astype(np.uint32)
+    m[0][np.ix_(ys, xs)] = bits.view(np.float32).reshape(len(ys), len(xs))
+    return m, n
+
+
+def padded_dims(h: int, w: int):
+    """InputPadder(divis_by=32): (Hp, Wp, top, left)"""
+    ph, pw = ((h // 32 + 1) * 32 - h) % 32, ((w // 32 + 1) * 32 - w) % 32
+    return h + ph, w + pw, ph // 2, pw // 2
+
+
+def crafted_levels(seed: int, b: int, h: int, w: int) -> list:
+    """the four level maps x1 .. x4 of an h x w image, [b, Hp >> s, Wp >> s, 32] fp32 for s = 0, 1, 3, 5: independent normal values (the
+    sharpest dense map the upsampling can produce), each level at its own scale"""
+    rng = np.random.Generator(np.random.PCG64(700 + seed))
+    hp, wp, _, _ = padded_dims(h, w)
+    return [(rng.standard_normal((b, hp >> s, wp >> s, 32)) * g).astype(np.float32) for s, g in ((0, 1.0), (1, 0.7), (3, 1.3), (5, 0.9))]
+
+
+def crafted_knorm(seed: int, n: int, h: int, w: int) -> np.ndarray:
+    """[n, 2] fp32 normalised keypoints (x, y): the four corners, the four edge midpoints, then exact pixel centres (every third one, from
+    both ends), then random positions at least 1e-3 px away from an integer pixel coordinate (the .long() of SDDH is discontinuous there, and
+    no test should hang on which side a round-off falls)."""
+    rng = np.random.Generator(np.random.PCG64(800 + seed))
+    pts = [(-1, -1), (1, -1), (-1, 1), (1, 1), (0, -1), (0, 1), (-1, 0), (1, 0)]
+    wm1, hm1 = np.float32(w - 1), np.float32(h - 1)
+    for i in range(6):
+        x, y = (3 * i + 1) % w, (h - 2 - 3 * i) % h
+        pts.append((np.float32(x) / wm1 * np.float32(2) - np.float32(1), np.float32(y) / hm1 * np.float32(2) - np.float32(1)))
+    while len(pts) < n:
+        p = rng.uniform(0, 1, 2) * (w - 1, h - 1)
+        k = (p / (w - 1, h - 1) * 2 - 1).astype(np.float32)
+        back = (k / np.float32(2) + np.float32(0.5)) * np.array([wm1, hm1])
+        if (np.abs(back - np.round(back)) >= 1e-3).all():
+            pts.append((k[0], k[1]))
+    return np.array(pts[:n], np.float32)
+
+
+def scaled_offset_weights(sd: dict, gain: float) -> dict:
+    """`sd` with desc_head.offset_conv.2 (weight and bias) times `gain`: the sample offsets grow until most hit SDDH's +-max(h, w) / 4 clamp
+    and many sample positions leave the map"""
+    out = dict(sd)
+    for k in ("desc_head.offset_conv.2.weight", "desc_head.offset_conv.2.bias"):
+        out[k] = sd[k] * gain
+    return out
+
+
+STAGES = ROOT / "tests" / "golden" / "aliked_stages"
+OFFSET_GAIN = 40.0
+# DKD on crafted score maps.  name -> (map generator, its arguments, radius, top_k, scores_th, n_limit, image_size or None).  Only cases the
+# reference defines: image_size absent or equal to the map, and in top-k mode at least top_k positive maxima.
+DKD_STAGES = {
+    "dkd_tall_b2_300x40_r2_th": ("score_maps", (1, 2, 300, 40), 2, -1, 0.2, 20000, None),
+    "dkd_wide_b2_24x600_r2_limit500": ("score_maps", (2, 2, 24, 600), 2, -1, 0.2, 500, None),
+    "dkd_many_b1_272x96_r1_top1500": ("score_maps", (3, 1, 272, 96), 1, 1500, -1.0, 20000, None),
+    "dkd_many_b1_272x96_r1_limit1025": ("score_maps", (3, 1, 272, 96), 1, -1, 0.04, 1025, None),
+    "dkd_quantised_b1_272x96_r1_limit1500": ("quantised_maps", (3, 1, 272, 96), 1, -1, 0.04, 1500, None),
+    "dkd_radius5_b2_70x130": ("score_maps", (4, 2, 70, 130), 5, -1, 0.2, 20000, None),
+    "dkd_radius8_b2_70x130": ("score_maps", (4, 2, 70, 130), 8, -1, 0.2, 20000, None),
+    "dkd_fallback_b3_40x56_r2": ("score_maps", (5, 3, 40, 56), 2, -1, 0.99, 20000, None),       # nothing passes: per-image means
+    "dkd_mean_b2_40x56_r2": ("score_maps", (6, 2, 40, 56), 2, -1, -1.0, 20000, None),           # scores_th <= 0: the mean mode
+    "dkd_image_size_b2_40x56_r3": ("score_maps", (7, 2, 40, 56), 3, -1, 0.2, 20000, [[56, 40], [56, 40]]),
+}
+# SDDH on crafted level maps.  name -> (model, weight seed, offset gain, level seed, B, H, W, N, keypoint seed)
+SDDH_STAGES = {
+    "sddh_n16_b2_40x56_n33": ("aliked-n16", 20, 1.0, 1, 2, 40, 56, 33, 1),
+    "sddh_n32_b2_40x56_n33": ("aliked-n32", 21, 1.0, 2, 2, 40, 56, 33, 2),
+    "sddh_n16_b2_40x56_n33_clamped": ("aliked-n16", 20, OFFSET_GAIN, 1, 2, 40, 56, 33, 1),
+    "sddh_n32_b2_40x56_n33_clamped": ("aliked-n32", 21, OFFSET_GAIN, 2, 2, 40, 56, 33, 2),
+    "sddh_n16_b1_8x8_n20": ("aliked-n16", 22, 1.0, 3, 1, 8, 8, 20, 3),
+    "sddh_n32_b1_8x8_n20_clamped": ("aliked-n32", 23, OFFSET_GAIN, 4, 1, 8, 8, 20, 4),
+}
+
+
+def stage_knorm(kseed: int, b: int, n: int, h: int, w: int) -> np.ndarray:
+    """[b, n, 2]: crafted_knorm per image (the special points in every image, other random ones)"""
+    return np.stack([crafted_knorm(10 * kseed + i, n, h, w) for i in range(b)])
+
+
+def torch_dense_map(levels: list, h: int, w: int) -> torch.Tensor:
+    """x1234 as extract_dense_map forms it from the level maps, in torch fp32: [B, 128, H, W]"""
+    hp, wp, pt, pl = padded_dims(h, w)
+    ups = [F.interpolate(torch.from_numpy(l).permute(0, 3, 1, 2), size=(hp, wp), mode="bilinear", align_corners=True) for l in levels]
+    x = F.normalize(torch.cat(ups, dim=1), p=2, dim=1)
+    return x[..., pt:pt + h, pl:pl + w].contiguous()
+
+
+def make_stages(mod):
+    STAGES.mkdir(parents=True, exist_ok=True)
+    gens = {"score_maps": score_maps, "quantised_maps": quantised_maps}
+    for name, (gen, args, radius, top_k, th, n_limit, image_size) in DKD_STAGES.items():
+        smap = gens[gen](*args)
+        b, h, w = smap.shape
+        dkd = mod.DKD(radius=radius, top_k=top_k, scores_th=th, n_limit=n_limit)
+        isz = None if image_size is None else torch.tensor(image_size, dtype=torch.float32)
+        with torch.no_grad():
+            s = torch.from_numpy(smap)[:, None]
+            kn, ks, _ = dkd(s.clone(), sub_pixel=True, image_size=isz)
+            k0, _, _ = dkd(s.clone(), sub_pixel=False, image_size=isz)      # the unrefined positions: the raster indices
+        wh = torch.tensor([w - 1, h - 1])
+        idx = [((k + 1) / 2 * wh).round().long() for k in k0]
+        idx = [(i[:, 1] * w + i[:, 0]).numpy().astype(np.int32) for i in idx]
+        pix = [(wh * (k + 1) / 2.0).numpy() for k in kn]                     # aliked.py:757
+        counts = np.array([len(i) for i in idx], np.int32)
+        if top_k > 0:
+            assert all((smap[i].reshape(-1)[idx[i]] > 0).all() for i in range(b)), "top-k beyond the positive maxima: the reference is undefined there"
+        meta = {"gen": gen, "args": list(args), "radius": radius, "top_k": top_k, "scores_th": th, "n_limit": n_limit, "image_size": image_size}
+        np.savez_compressed(STAGES / f"{name}.npz", meta=json.dumps(meta), counts=counts, indices=np.concatenate(idx),
+                            knorm=np.concatenate([k.numpy() for k in kn]), keypoints=np.concatenate(pix), keypoint_scores=np.concatenate([k.numpy() for k in ks]))
+        print(f"{name}: counts {counts.tolist()}")
+    for name, (model, wseed, gain, lseed, b, h, w, n, kseed) in SDDH_STAGES.items():
+        sd = scaled_offset_weights(aliked_state_dict(wseed, model), gain)
+        n_pos = 32 if model.endswith("32") else 16
+        head = mod.SDDH(128, 3, n_pos, gate=torch.nn.SELU(inplace=True), conv2D=False, mask=False)
+        head.load_state_dict({k[len("desc_head."):]: v for k, v in sd.items() if k.startswith("desc_head.")}, strict=True)
+        x = torch_dense_map(crafted_levels(lseed, b, h, w), h, w)
+        kn = stage_knorm(kseed, b, n, h, w)
+        with torch.no_grad():
+            desc, offsets = head(x, [torch.from_numpy(k) for k in kn])
+        clamped = float(np.mean([(o.abs() >= max(h, w) / 4.0).float().mean().item() for o in offsets]))
+        meta = {"model": model, "wseed": wseed, "gain": gain, "lseed": lseed, "b": b, "h": h, "w": w, "n": n, "kseed": kseed}
+        np.savez_compressed(STAGES / f"{name}.npz", meta=json.dumps(meta), descriptors=np.stack([d.numpy() for d in desc]))
+        print(f"{name}: {clamped:.0%} of the offsets at the clamp")
 
 
 # ---------------------------------------------------------------------------------------------------- deform_conv2d restatement
@@ -208,8 +374,11 @@ def run_reference(mod, model, wseed, image, conf):
 
 
 def main():
-    GOLD.mkdir(parents=True, exist_ok=True)
     mod = load_reference(lambda name: None)
+    if "--stages" in sys.argv[1:]:
+        make_stages(mod)
+        return
+    GOLD.mkdir(parents=True, exist_ok=True)
     tree = {}   # names / shapes of the reference's module tree
     for model in ("aliked-n16", "aliked-n32"):
         mod.torch.hub.load_state_dict_from_url = lambda url, map_location=None, _m=model: aliked_state_dict(0, _m)
@@ -232,7 +401,10 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", meta=json.dumps(meta), scores=smap, keypoints=K, keypoint_scores=S, descriptors=D, counts=counts)
         print(f"{name}: counts {counts.tolist()} score range [{smap.min():.3f}, {smap.max():.3f}] th {ths} margins {meta['threshold_margin']:.2e} / {meta['nms_tie_margin']:.2e}")
 
+    only = [a for a in sys.argv[1:] if not a.startswith("-")]
     for name, (model, wseed, iseed, b, c, h, w, conf) in CASES.items():
+        if only and name not in only:
+            continue
         img = aliked_image(iseed, b, h, w, c)
         sd, sm, out, th = None, None, None, None
         mod.torch.hub.load_state_dict_from_url = lambda url, map_location=None, _m=model, _s=wseed: aliked_state_dict(_s, _m)
@@ -242,6 +414,8 @@ def main():
             outs.append((None, sm[i:i + 1], {k: v[i:i + 1] for k, v in out.items()}, th[i] if isinstance(th, list) else th))
         record(name, model, wseed, [iseed], b, c, h, w, conf, outs)
     for name, (model, wseed, iseeds, c, h, w, conf) in RAGGED.items():
+        if only and name not in only:
+            continue
         mod.torch.hub.load_state_dict_from_url = lambda url, map_location=None, _m=model, _s=wseed: aliked_state_dict(_s, _m)
         outs = []
         for s in iseeds:
