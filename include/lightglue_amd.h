@@ -88,11 +88,20 @@ typedef struct lg_engine lg_engine;
 #define LG_FLAG_INDEXED 8u    /* the inputs are feature STORES and `index0` / `index1` (the last fields of the struct) say which image of them each pair
                                  reads: see there.  Needs LG_FLAG_EXT and `status`                                      */
 
+/* Descriptors STORED as IEEE binary16 (the format hloc and most SfM tooling write feature files in): with a flag set, desc0 / desc1 point to binary16 rows
+ * [B or images][n][input_dim] instead of fp32 ones, read in place and widened exactly (every binary16 value, subnormals included) where the descriptors enter the
+ * engine — the forward is bit-identical to one on the same values converted to fp32 by the caller, in every mode (LG_FLAG_INDEXED, ragged num0 / num1,
+ * LG_FLAG_CHECK_FINITE, every precision).  Per side: a pair list may join an f16 store and an fp32 one.  Each flag needs LG_FLAG_EXT, and its pointer must be
+ * 16-byte aligned; otherwise the call returns LG_ERR_INVALID before the GPU is touched.  Rounding descriptors to binary16 is the CALLER's choice of storage format,
+ * not a precision mode of the engine: the 1e-3 score bar is stated for fp32 descriptors only (README: measured drift of f16-stored descriptors). */
+#define LG_FLAG_DESC0_F16 16u
+#define LG_FLAG_DESC1_F16 32u
+
 typedef struct lg_forward_io {
     int32_t batch, n0, n1;
     uint32_t flags;                        /* LG_FLAG_*                                           */
     const float *kpts0, *kpts1;            /* [B][n][2] pixel (x, y)                              */
-    const float *desc0, *desc1;            /* [B][n][input_dim]                                   */
+    const float *desc0, *desc1;            /* [B][n][input_dim]; binary16 rows behind the same pointer with LG_FLAG_DESC0_F16 / _DESC1_F16 */
     const float *size0, *size1;            /* [B][2] (w, h) or NULL -> bounding-box normalisation */
     const float *scales0, *oris0, *scales1, *oris1; /* [B][n] iff add_scale_ori, else NULL        */
     int32_t *matches0, *matches1;          /* [B][n0], [B][n1]; -1 = unmatched                    */
@@ -241,6 +250,11 @@ int lg_engine_profile_read(lg_engine* e, double* ms, int64_t* count, int32_t n_c
 int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w,
                              const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
                              int32_t normalize_dense, float* workspace, float* out, void* hip_stream);
+/* The same with `out` [B][N][256] as IEEE binary16: the last kernel rounds its fp32 result once, to nearest even, on store — bit-identical to converting the fp32
+ * output, zero padding rows included, at half the bytes written (and read by the matcher: LG_FLAG_DESC0_F16 / _DESC1_F16). */
+int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w,
+                                 const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
+                                 int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream);
 
 /* ---- SuperPoint conv stack (replaces superpoint.py:127-141 layers and :159-184, :213-214 of forward) ----
  * lg_sp_pack_conv_weight: repack one nn.Conv2d weight [cout][cin][k][k] (device fp32) into the layout the kernels read,
@@ -314,6 +328,10 @@ int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, c
 int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos);
 int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
                        const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
+/* lg_aliked_describe with `descriptors` [batch][n][128] as IEEE binary16: the fp32 result rounded once, to nearest even, by the last kernel's store (bit-identical
+ * to converting the fp32 output; rows >= counts[b] are zero). */
+int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
+                           const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream);
 
 /* ---- ImagePreprocessor (lightglue/utils.py:12-38): the resize in front of the extractors, one fused kernel (lg_preprocess.hip) ----
  * What the reference computes through kornia.geometry.transform.resize (always bilinear: `interpolation` is not forwarded):

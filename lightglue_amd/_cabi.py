@@ -17,6 +17,7 @@ _LIB_PATH = Path(os.environ.get("LIGHTGLUE_AMD_LIB") or Path(__file__).resolve()
 LG_PREC = {"fp32": 0, "bf16": 1, "fp16": 2, "f16x3": 4}   # include/lightglue_amd.h LG_PREC_* (3 was split-bf16, removed in round 3)
 LG_OK, LG_ERR_INVALID, LG_ERR_HIP, LG_ERR_STATE, LG_ERR_RANGE, LG_ERR_DEVICE, LG_ERR_INDEX = 0, 1, 2, 3, 4, 5, 6
 LG_FLAG_NO_PRUNING, LG_FLAG_EXT, LG_FLAG_CHECK_FINITE, LG_FLAG_INDEXED = 1, 2, 4, 8
+LG_FLAG_DESC0_F16, LG_FLAG_DESC1_F16 = 16, 32   # desc0 / desc1 are binary16 rows, read in place
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
 # every symbol include/lightglue_amd.h declares (tests check the library exports all of them)
@@ -30,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "lg_aliked_packed_bytes", "lg_aliked_pack_weights", "lg_aliked_levels_bytes", "lg_aliked_workspace_bytes", "lg_aliked_encode",
     "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
     "lg_preprocess_plan", "lg_preprocess_resize",
+    "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
 )
 
 
@@ -138,6 +140,7 @@ def load() -> C.CDLL:
     lib.lg_engine_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
     lib.lg_sp_sample_descriptors.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lg_sp_sample_descriptors_half.argtypes = lib.lg_sp_sample_descriptors.argtypes
     lib.lg_sp_detect_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lg_sp_detect_workspace_bytes.restype = C.c_int64
     lib.lg_sp_detect.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_float] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
@@ -162,6 +165,7 @@ def load() -> C.CDLL:
     lib.lg_aliked_describe_workspace_bytes.argtypes = [C.c_int32] * 2
     lib.lg_aliked_describe_workspace_bytes.restype = C.c_int64
     lib.lg_aliked_describe.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.lg_aliked_describe_half.argtypes = lib.lg_aliked_describe.argtypes
     lib.lg_preprocess_plan.argtypes = [C.c_int32] * 7 + [C.POINTER(LgResizePlan)]
     lib.lg_preprocess_resize.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_int64] * 4 + [C.POINTER(LgResizePlan), C.c_void_p, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

@@ -18,6 +18,7 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
+from .superpoint_head import check_descriptor_dtype
 
 
 class DeformableConv2d(nn.Module):
@@ -76,7 +77,10 @@ _ABI_NAMES = _abi_names()
 
 
 class ALIKED(nn.Module):
-    default_conf = {"model_name": "aliked-n16", "max_num_keypoints": -1, "detection_threshold": 0.2, "nms_radius": 2}   # ref :613-618
+    default_conf = {"model_name": "aliked-n16", "max_num_keypoints": -1, "detection_threshold": 0.2, "nms_radius": 2,   # ref :613-618
+                    # extension: element type of the returned descriptors.  torch.float16 = the fp32 descriptors rounded once, on store, by SDDH's last kernel
+                    # (half the bytes of a feature store; LightGlue reads them in place).  A storage format, opt-in: outside the matcher's 1e-3 score bar (README)
+                    "descriptor_dtype": torch.float32}
     # c1, c2, c3, c4, dim, K, M  (ref :624-630)
     cfgs = {
         "aliked-t16": [8, 16, 32, 64, 64, 3, 16],
@@ -101,6 +105,7 @@ class ALIKED(nn.Module):
             raise ValueError("nms_radius must be in [1, 8]")
         if self.conf.max_num_keypoints is not None and self.conf.max_num_keypoints > self.n_limit_max:
             raise ValueError(f"max_num_keypoints must be at most {self.n_limit_max}")
+        check_descriptor_dtype(self.conf.descriptor_dtype)
         c1, c2, c3, c4, dim, K, M = self.cfgs[name]
         self.n_pos = M
         # module tree of the reference (registration order included: state_dict keys come out in the same order)
@@ -219,12 +224,14 @@ class ALIKED(nn.Module):
         return kpts, kscores, knorm, counts
 
     @torch.no_grad()
-    def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor):
-        """SDDH (ref :479-609): descriptors [B, N, 128] of the normalised keypoints knorm [B, N, 2]; rows >= counts[b] are zero."""
+    def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor, dtype: Optional[torch.dtype] = None):
+        """SDDH (ref :479-609): descriptors [B, N, 128] of the normalised keypoints knorm [B, N, 2]; rows >= counts[b] are zero.  `dtype`: torch.float32, or
+        torch.float16 = the same values rounded once on store (`lg_aliked_describe_half`); None = conf.descriptor_dtype."""
+        dtype = check_descriptor_dtype(self.conf.descriptor_dtype if dtype is None else dtype)
         bsz, h, w = shape
         n = knorm.shape[1]
         device = knorm.device
-        out = torch.empty((bsz, n, 128), device=device, dtype=torch.float32)   # every row is written (padding rows with zeros)
+        out = torch.empty((bsz, n, 128), device=device, dtype=dtype)   # every row is written (padding rows with zeros)
         if n == 0:
             return out
         lib = _cabi.load()
@@ -234,8 +241,9 @@ class ALIKED(nn.Module):
         work = torch.empty((nws,), device=device, dtype=torch.uint8)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            _cabi.check(lib.lg_aliked_describe(levels.data_ptr(), bsz, h, w, self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n,
-                                               work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream)))
+            describe = lib.lg_aliked_describe_half if dtype is torch.float16 else lib.lg_aliked_describe
+            _cabi.check(describe(levels.data_ptr(), bsz, h, w, self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n,
+                                 work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream)))
         return out
 
     # ------------------------------------------------------------------ the reference's forward

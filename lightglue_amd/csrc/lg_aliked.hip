@@ -289,6 +289,7 @@ struct AkDescribe {
     float* patch; float* off1; float* spos; float* feat; float* sf; float* draw;
     const float* w_off2; const float* b_off2;
     const int* counts; float* out;
+    int out_f16;                           // != 0: `out` holds binary16 rows (lg_aliked_describe_half): the fp32 result rounded once, to nearest even, on store
 };
 
 __device__ __forceinline__ void kp_pixel(const AkDescribe& d, int row, float& kw, float& kh) {   // (kpts / 2 + 0.5) * wh  (aliked.py:542)
@@ -357,7 +358,7 @@ __global__ __launch_bounds__(256) void ak_sample_kernel(AkDescribe d, int sample
     *reinterpret_cast<f32x2*>(d.feat + (long long)s * 128 + lane * 2) = acc;
 }
 
-// F.normalize of the aggregated descriptors -> out [B][N][128]; rows >= count are zero.  wave = one row
+// F.normalize of the aggregated descriptors -> out [B][N][128] (fp32, or the same values as binary16); rows >= count are zero.  wave = one row
 __global__ __launch_bounds__(256) void ak_desc_norm_kernel(AkDescribe d, int rows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -365,7 +366,12 @@ __global__ __launch_bounds__(256) void ak_desc_norm_kernel(AkDescribe d, int row
     f32x2 v = *reinterpret_cast<const f32x2*>(d.draw + (long long)row * 128 + lane * 2);
     const float nrm = fmaxf(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
     v = i < d.counts[b] ? f32x2{v[0] / nrm, v[1] / nrm} : f32x2{0.f, 0.f};
-    *reinterpret_cast<f32x2*>(d.out + (long long)row * 128 + lane * 2) = v;
+    if (d.out_f16) {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        *reinterpret_cast<f16x2*>(reinterpret_cast<f16_t*>(d.out) + (long long)row * 128 + lane * 2) = f16x2{(f16_t)v[0], (f16_t)v[1]};
+    } else {
+        *reinterpret_cast<f32x2*>(d.out + (long long)row * 128 + lane * 2) = v;
+    }
 }
 
 // ==================================================================================================== host-side layouts
@@ -609,8 +615,9 @@ int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos) {
     return describe_layout(rows, n_pos).total;
 }
 
-int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
-                       int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
+// lg_aliked_describe / lg_aliked_describe_half: one path, the element type of `descriptors` decided at the last kernel's store
+static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
+                           int32_t n, void* workspace, int64_t workspace_bytes, void* descriptors, bool out_f16, void* hip_stream) {
     if (int rc = check_model(n_pos)) return rc;
     if (int rc = check_size(batch, h, w)) return rc;
     if (n < 1) return LG_OK;
@@ -631,7 +638,7 @@ int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, 
     d.H = h; d.W = w; d.pt = D.pt; d.pl = D.pl; d.N = n; d.np = n_pos; d.knorm = kp_norm;
     d.patch = reinterpret_cast<float*>(ws + DL.patch); d.off1 = reinterpret_cast<float*>(ws + DL.off1); d.spos = reinterpret_cast<float*>(ws + DL.spos);
     d.feat = reinterpret_cast<float*>(ws + DL.feat); d.sf = reinterpret_cast<float*>(ws + DL.sf); d.draw = reinterpret_cast<float*>(ws + DL.draw);
-    d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = counts; d.out = descriptors;
+    d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = counts; d.out = static_cast<float*>(descriptors); d.out_f16 = out_f16 ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int rp = DL.rows_pad;
     hipLaunchKernelGGL(ak_patch_kernel, dim3(rows), dim3(256), 0, s, d);
@@ -645,6 +652,14 @@ int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, 
     hipLaunchKernelGGL(ak_desc_norm_kernel, dim3(blocks(rows, 4)), dim3(256), 0, s, d, rows);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
+}
+int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
+                       int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
+    return aliked_describe(levels, batch, h, w, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
+}
+int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
+                           int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream) {
+    return aliked_describe(levels, batch, h, w, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
 }
 
 }  // extern "C"

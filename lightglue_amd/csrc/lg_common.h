@@ -122,6 +122,10 @@ __device__ __forceinline__ void split8_f16(const f32x4& a, const f32x4& b, u32x4
 template <class Tag> __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo);
 template <> __device__ __forceinline__ void split8<TagF16>(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) { split8_f16<false>(a, b, hi, lo); }
 
+// ---- f16 -> fp32 of descriptors that are STORED as binary16 (LG_FLAG_DESC0_F16 / _DESC1_F16): v_cvt_f32_f16, exact for every binary16 value (+-0, subnormals,
+// 65504, +-inf; NaN stays NaN) — the kernels run in the default float mode, which keeps f16 (and f32) denormals
+__device__ __forceinline__ f32x4 widen4_f16(const f16x4& h) { return __builtin_convertvector(h, f32x4); }
+
 // ---- range guard (LG_FLAG_CHECK_FINITE): 1 for whatever an f16 plane cannot hold, inf and NaN included (int: the callers combine them with | and &)
 __device__ __forceinline__ int out_of_f16_range(float x) { return !(fabsf(x) < 65504.f); }
 __device__ __forceinline__ int out_of_f16_range(const f32x4& v) {

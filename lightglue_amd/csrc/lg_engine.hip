@@ -154,10 +154,19 @@ int tail_row_tiles_for(int R) {
 bool pruning_on(const lg_engine* e, const lg_forward_io* io) { return e->cfg.width_confidence > 0 && !(io->flags & LG_FLAG_NO_PRUNING); }
 // LG_FLAG_INDEXED: the index fields sit behind the round-5 extension, so they are read only when both flags are set (check_forward_io refuses one without the other)
 bool indexed(const lg_forward_io* io) { return (io->flags & LG_FLAG_EXT) && (io->flags & LG_FLAG_INDEXED); }
+// bit `side` set: desc0 / desc1 hold binary16 rows (LG_FLAG_DESC0_F16 / _DESC1_F16; check_forward_io refuses them without LG_FLAG_EXT)
+int desc_f16_sides(const lg_forward_io* io) { return ((io->flags & LG_FLAG_DESC0_F16) ? 1 : 0) | ((io->flags & LG_FLAG_DESC1_F16) ? 2 : 0); }
 PairIndex pair_index(const lg_forward_io* io) { return indexed(io) ? PairIndex{io->index0, io->index1, io->images0, io->images1} : PairIndex{}; }
 
 int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if (!e || !io) return set_error(LG_ERR_INVALID, "null argument");
+    if (io->flags & (LG_FLAG_DESC0_F16 | LG_FLAG_DESC1_F16)) {   // pure argument checks, ahead of the engine's state: refused on any engine
+        if (!(io->flags & LG_FLAG_EXT)) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16 need LG_FLAG_EXT");
+        // the kernels read a binary16 row in 16-byte pieces: rows are input_dim * 2 bytes (a multiple of 128), so the base decides
+        if (((io->flags & LG_FLAG_DESC0_F16) && (reinterpret_cast<uintptr_t>(io->desc0) & 15)) ||
+            ((io->flags & LG_FLAG_DESC1_F16) && (reinterpret_cast<uintptr_t>(io->desc1) & 15)))
+            return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16: the descriptor pointer must be 16-byte aligned");
+    }
     if (!e->weights_ready) return set_error(LG_ERR_STATE, "weights not finalised");
     const int B = io->batch, n0 = io->n0, n1 = io->n1;
     if (B < 1 || n0 < 0 || n1 < 0) return set_error(LG_ERR_INVALID, "bad batch / keypoint counts");
@@ -242,7 +251,7 @@ int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
     p.rs = rs_all; p.n0 = n0; p.n1 = n1; p.px = pair_index(io); p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
     p.scales0 = io->scales0; p.oris0 = io->oris0; p.scales1 = io->scales1; p.oris1 = io->oris1;
     p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
-    p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim;
+    p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim; p.desc_f16 = desc_f16_sides(io);
     p.X = e->X; p.Xin = e->XIN; p.cosb = e->COS; p.sinb = e->SIN; p.ind = e->IND; p.bbox = e->BBOX;
     TRY(prof_begin(e, PC_PREP, s));
     if (fuse_prep) HIPCHK(launch_prep_bbox(p, s)); else HIPCHK(launch_prep(p, s));

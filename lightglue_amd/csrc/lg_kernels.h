@@ -162,6 +162,7 @@ struct PrepArgs {
     const float* scales0; const float* oris0; const float* scales1; const float* oris1;  // [B][n] or nullptr
     const float* Wr; int pos_dim;  // [32][pos_dim], pos_dim = 2 or 4
     const float* desc0; const float* desc1; int input_dim;  // [B][n][input_dim]
+    int desc_f16;                  // bit `side` set (LG_FLAG_DESC0_F16 / _DESC1_F16): that side's descriptors are IEEE binary16 rows behind the same pointer, widened exactly on load
     float* X;                      // [R][256]  (written only when input_dim == 256; else see Xin)
     float* Xin;                    // [R][input_dim] staging for the input projection GEMM
     float* cosb; float* sinb;      // [R][32]

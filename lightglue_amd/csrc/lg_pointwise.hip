@@ -60,9 +60,15 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     }
     if (lane == 0) a.ind[grow] = r;
     // descriptors -> residual stream (ref :502-503, :521-522 identity case) or input-projection staging
-    const float* d = (image ? a.desc1 : a.desc0) + (src * n + r) * a.input_dim;
+    const float* d0 = image ? a.desc1 : a.desc0;
     float* dst = (a.input_dim == 256) ? a.X + grow * 256 : a.Xin + grow * a.input_dim;
-    for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(d + c);
+    if ((a.desc_f16 >> image) & 1) {                  // binary16 rows: 8-byte loads of 4 halves, widened exactly
+        const f16_t* d = reinterpret_cast<const f16_t*>(d0) + (src * n + r) * a.input_dim;
+        for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = widen4_f16(*reinterpret_cast<const f16x4*>(d + c));
+    } else {
+        const float* d = d0 + (src * n + r) * a.input_dim;
+        for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(d + c);
+    }
 }
 
 hipError_t launch_prep_bbox(const PrepArgs& a, hipStream_t s) {

@@ -24,7 +24,7 @@ __device__ __forceinline__ bool proj_tile(const RowSpace& rs, TileLoc& t, int& l
 __device__ __forceinline__ bool proj_tile(const RowSpace& rs, TileLoc& t) { int len; return proj_tile(rs, t, len); }
 
 // A thread's share of the 64 x 256 activation tile: 16-byte chunk slot tid & 7 of row tid >> 3 in every 128-byte stage row.
-// load: HBM -> registers (`src` = the row's first float of the slot).  store: registers -> operand precision -> LDS (once); copy_out: the fp32 values are
+// load / load_f16: HBM -> registers (`src` = the row's first element of the slot; fp32 or binary16 rows).  store: registers -> operand precision -> LDS (once); copy_out: the fp32 values are
 // first stored at xdst (the residual row of a keypoint that is new at this kernel).  No barrier (proj_compute / final_compute synchronise).
 template <int PREC> struct TileRegs {
     static constexpr int NV = PJ<PREC>::Tag::EPC / 4, KE = PJL<PREC>::KE, STAGES = PJL<PREC>::STAGES;
@@ -34,6 +34,19 @@ template <int PREC> struct TileRegs {
         for (int st = 0; st < STAGES; ++st)
 #pragma unroll
             for (int j = 0; j < NV; ++j) v[st][j] = *reinterpret_cast<const f32x4*>(src + st * KE + 4 * j);
+    }
+    // the same elements of a row stored as binary16: one 16-byte load of 8 halves per stage (8 bytes of 4 with fp32 operands), widened exactly into the same registers
+    __device__ __forceinline__ void load_f16(const f16_t* src) {
+#pragma unroll
+        for (int st = 0; st < STAGES; ++st) {
+            if constexpr (NV == 2) {
+                const f16x8 h = *reinterpret_cast<const f16x8*>(src + st * KE);
+                v[st][0] = widen4_f16(h.lo); v[st][1] = widen4_f16(h.hi);
+            } else {
+                static_assert(NV == 1, "4 or 8 elements per chunk");
+                v[st][0] = widen4_f16(*reinterpret_cast<const f16x4*>(src + st * KE));
+            }
+        }
     }
     __device__ __forceinline__ void store(char* smA, int srow, int sslot, bool copy_out, float* xdst) const {
         const int off = pj_tile_off(srow, sslot);
@@ -97,7 +110,12 @@ struct FirstRows {
         simg = source_image(pa.px, t.pair, image);          // the image whose rows this tile reads: the pair itself unless the inputs are indexed
         in_row = simg * (image ? pa.n1 : pa.n0) + rc;
     }
-    __device__ __forceinline__ const float* x_row() const { return (image ? pa.desc1 : pa.desc0) + in_row * 256; }   // descriptor rows (the x tile)
+    // descriptor rows (the x tile), fp32 or binary16 per side: uniform per workgroup
+    template <int PREC> __device__ __forceinline__ void load_x(TileRegs<PREC>& h, int col) const {
+        const float* d = image ? pa.desc1 : pa.desc0;
+        if ((pa.desc_f16 >> image) & 1) h.load_f16(reinterpret_cast<const f16_t*>(d) + in_row * 256 + col);
+        else h.load(d + in_row * 256 + col);
+    }
     // rotary rows: thread -> keypoint srow, frequencies 4 sslot .. 4 sslot + 3 (prep_kernel's expressions)
     __device__ __forceinline__ void rotary(int sslot, f32x4& c4, f32x4& s4) const {
         const float* kp = (image ? pa.kpts1 : pa.kpts0) + in_row * 2;
@@ -135,7 +153,7 @@ struct GatherRows {
         const int sr = ga.len_old[t.seg] >= 0 ? ga.src[base + rc] : rc;
         in_row = base + sr;
     }
-    __device__ __forceinline__ const float* x_row() const { return ga.Xold + in_row * 256; }
+    template <int PREC> __device__ __forceinline__ void load_x(TileRegs<PREC>& h, int col) const { h.load(ga.Xold + in_row * 256 + col); }
     __device__ __forceinline__ void rotary(int sslot, f32x4& c4, f32x4& s4) const {
         c4 = *reinterpret_cast<const f32x4*>(ga.cos_old + in_row * 32 + sslot * 4);
         s4 = *reinterpret_cast<const f32x4*>(ga.sin_old + in_row * 32 + sslot * 4);
@@ -162,7 +180,7 @@ __global__ __launch_bounds__(PTHREADS) void proj_rows_kernel(ProjArgs a, typenam
     const RowDest dst = rows.dest();
     // ---- the x tile requested first: cold, in flight under the rotary rows' arithmetic
     TileRegs<PREC> h;
-    h.load(rows.x_row() + sslot * EPC);
+    rows.load_x(h, sslot * EPC);
     {
         f32x4 c4, s4;
         rows.rotary(sslot, c4, s4);

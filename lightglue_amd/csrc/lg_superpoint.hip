@@ -9,7 +9,7 @@
 //   sp_sample_kernel  one wave per keypoint: bilinear interpolation of the 4 neighbouring locations
 //                     (align_corners=True, zero padding: ref :85-91 + grid_sample), each a contiguous
 //                     1 KB row of the NHWC map, then the final L2 normalisation (ref :92-94); writes
-//                     [B][N][C] directly (the layout ref :228 transposes to).
+//                     [B][N][C] directly (the layout ref :228 transposes to), as fp32 or as binary16.
 //                     Algorithmic bytes per keypoint: 4 * 1 KB read + 1 KB written.
 #include <string>
 
@@ -25,6 +25,7 @@ struct SpArgs {
     const int* num;            // [B] live keypoints per image or nullptr
     float* out;                // [B][N][256]
     int B, h, w, N, s, normalize_dense;
+    int out_f16;               // != 0: `out` holds binary16 rows (lg_sp_sample_descriptors_half): the fp32 result rounded once, to nearest even, on store
 };
 
 constexpr int SPC = 256;   // descriptor_dim of SuperPoint (ref superpoint.py:107)
@@ -64,8 +65,12 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(SpArgs a) {
     const int i = blockIdx.x * 4 + wave;
     const int n = a.num ? min(max(a.num[b], 0), a.N) : a.N;
     if (i >= a.N) return;
-    float* out = a.out + ((long long)b * a.N + i) * SPC + lane * 4;
-    if (i >= n) { *reinterpret_cast<f32x4*>(out) = f32x4{0.f, 0.f, 0.f, 0.f}; return; }   // padding row of a ragged batch
+    const long long o = ((long long)b * a.N + i) * SPC + lane * 4;
+    auto store = [&](const f32x4& v) {
+        if (a.out_f16) *reinterpret_cast<f16x4*>(reinterpret_cast<f16_t*>(a.out) + o) = f16x4{(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
+        else *reinterpret_cast<f32x4*>(a.out + o) = v;
+    };
+    if (i >= n) { store(f32x4{0.f, 0.f, 0.f, 0.f}); return; }   // padding row of a ragged batch
     const float* kp = a.keypoints + ((long long)b * a.N + i) * 2;
     const float s = (float)a.s;
     // ref :83-90: (k - s/2 + 0.5) / (w*s - s/2 - 0.5) in [0,1], *2-1, then align_corners=True un-normalisation
@@ -90,7 +95,7 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(SpArgs a) {
     }
     const float nrm = sqrtf(wave_sum(acc[0] * acc[0] + acc[1] * acc[1] + acc[2] * acc[2] + acc[3] * acc[3]));
     const float inv = 1.f / fmaxf(nrm, 1e-12f);          // ref :92-94
-    *reinterpret_cast<f32x4*>(out) = f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+    store(f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv});
 }
 
 static hipError_t launch_sp_sample(const SpArgs& a, hipStream_t s) {
@@ -150,15 +155,26 @@ using namespace lg;
 
 extern "C" {
 
-int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
-                             const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out,
-                             void* hip_stream) {
+// lg_sp_sample_descriptors / lg_sp_sample_descriptors_half: one path, the element type of `out` decided at the last kernel's store
+static int sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
+                                 const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, void* out, bool out_f16,
+                                 void* hip_stream) {
     if (channels != 256) return set_error(LG_ERR_INVALID, "descriptor map must have 256 channels");
     if (batch < 1 || h < 1 || w < 1 || n < 0 || cell < 1) return set_error(LG_ERR_INVALID, "bad descriptor map / keypoint sizes");
     if (!desc_map || !workspace || (n && (!keypoints || !out))) return set_error(LG_ERR_INVALID, "null pointer");
-    SpArgs a{desc_map, workspace, keypoints, num, out, batch, h, w, n, cell, normalize_dense ? 1 : 0};
+    SpArgs a{desc_map, workspace, keypoints, num, static_cast<float*>(out), batch, h, w, n, cell, normalize_dense ? 1 : 0, out_f16 ? 1 : 0};
     HIPCHK(launch_sp_sample(a, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
+}
+int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
+                             const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out,
+                             void* hip_stream) {
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, hip_stream);
+}
+int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
+                                 const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, uint16_t* out,
+                                 void* hip_stream) {
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, hip_stream);
 }
 
 int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t max_candidates) {

@@ -134,7 +134,10 @@ def collate_features(feats: list) -> Dict[str, Any]:
         if not all(key in f for f in items):
             continue
         first = items[0][key]
-        buf = first.new_zeros((len(items), nmax) + tuple(first.shape[1:]))
+        dtype = first.dtype
+        if key == "descriptors" and dtype is torch.float16 and not all(f[key].dtype is torch.float16 for f in items):
+            dtype = torch.float32   # float16 only when EVERY item stores float16: a float16 first item must not round the fp32 ones behind it
+        buf = first.new_zeros((len(items), nmax) + tuple(first.shape[1:]), dtype=dtype)
         for b, f in enumerate(items):
             buf[b, : counts[b]] = f[key]
         out[key] = buf

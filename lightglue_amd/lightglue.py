@@ -18,7 +18,9 @@ Extensions over the reference (documented in DESIGN.md):
   * ``attention_precision`` conf key: None (= ``precision``) or "fp16" together with precision "f16x3": q / k / v as ONE f16
     plane (what the reference's GPU path feeds its fp16 SDPA, ref :119) — ~25 % faster, within the bar only while attention
     is diffuse (it fails the trained-statistics fixtures by 20x, tests/test_gpu_parity.py);
-  * ``pruning_min_kpts`` conf key overrides the device-keyed class dict (ref :339-344).
+  * ``pruning_min_kpts`` conf key overrides the device-keyed class dict (ref :339-344);
+  * float16 descriptors (how feature stores are usually written) are read in place, per side — no fp32 copy, bit-identical to the same call on ``descriptors.float()``;
+    a storage format chosen by the caller, outside the 1e-3 score bar (README).
 """
 from __future__ import annotations
 
@@ -105,6 +107,21 @@ def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS
         out.append((start, stop))
         start = stop
     return out
+
+
+def _engine_descriptors(t: torch.Tensor, device) -> tuple:
+    """Descriptors as the engine reads them -> (tensor, stored as float16).  A float16 tensor is read IN PLACE (LG_FLAG_DESC0_F16 / _DESC1_F16: the engine widens
+    every value exactly where the descriptors enter it, so the forward is bit-identical to one on `t.float()`) — untouched when it is on the device, contiguous
+    and 16-byte aligned, otherwise through one float16 copy; every other dtype becomes contiguous fp32, as before."""
+    if t.dtype is torch.float16:
+        if t.device != device or not t.is_contiguous():
+            t = t.detach().to(device=device).contiguous()
+        if t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
+            t = t.clone()
+        return t, True
+    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+        return t, False
+    return t.detach().to(device=device, dtype=torch.float32).contiguous(), False
 
 
 class LightGlue(nn.Module):
@@ -417,7 +434,8 @@ class LightGlue(nn.Module):
     def forward(self, data: dict, _raw: bool = False, _defer: bool = False) -> dict:
         """Match keypoints and descriptors between two images (same dict contract as ref :456-481).
 
-        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D], image_size [B,2] (optional),
+        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D] (float16 descriptors are read in place, per side: see _engine_descriptors),
+                                       image_size [B,2] (optional),
                                        scales/oris [B,N] iff add_scale_ori,
                                        num_keypoints [B] int (optional, extension: ragged batch — pair b uses only
                                        its first num_keypoints[b] rows and behaves exactly like a separate B=1
@@ -442,7 +460,7 @@ class LightGlue(nn.Module):
             return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
         k0, k1 = f32(kpts0), f32(kpts1)
-        desc0, desc1 = f32(d0["descriptors"]), f32(d1["descriptors"])
+        (desc0, half0), (desc1, half1) = _engine_descriptors(d0["descriptors"], device), _engine_descriptors(d1["descriptors"], device)
         assert desc0.shape[-1] == conf.input_dim
         assert desc1.shape[-1] == conf.input_dim
         size0, size1 = d0.get("image_size"), d1.get("image_size")
@@ -485,7 +503,8 @@ class LightGlue(nn.Module):
                     and wire.shape[1] >= _cabi.wire_width(m, n) and (wire.shape[1] == 1 or wire.stride(1) == 1)):
                 raise ValueError(f"wire must be an int32 [>= {b}, >= {_cabi.wire_width(m, n)}] tensor on {device} with unit column stride, got "
                                  f"{wire.dtype} {tuple(wire.shape)} stride {tuple(wire.stride())} on {wire.device}")
-        flags = _cabi.LG_FLAG_EXT | (0 if do_point_pruning or conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING) | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
+        flags = (_cabi.LG_FLAG_EXT | (0 if do_point_pruning or conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING) | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
+                 | (_cabi.LG_FLAG_DESC0_F16 if half0 else 0) | (_cabi.LG_FLAG_DESC1_F16 if half1 else 0))
         io = self._forward_io(o, 0, b, flags, (k0, k1, desc0, desc1, size0, size1, *extra, num0, num1), wire)
         with torch.cuda.device(device):
             cur_stream = torch.cuda.current_stream(device)
@@ -511,7 +530,8 @@ class LightGlue(nn.Module):
         return limits
 
     def _store(self, feats: dict, device) -> SimpleNamespace:
-        """A feature store as the engine reads it: contiguous fp32 / int32 tensors on `device` (tensors that already qualify pass through untouched)."""
+        """A feature store as the engine reads it: contiguous fp32 / int32 tensors on `device`, descriptors fp32 or float16 (`desc_f16`; tensors that already
+        qualify pass through untouched)."""
         conf = self.conf
         def f32(t):
             if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
@@ -521,7 +541,8 @@ class LightGlue(nn.Module):
         assert kpts.dim() == 3 and kpts.shape[-1] == 2, "a feature store holds keypoints [K, N, 2]"
         K, N = kpts.shape[:2]
         assert tuple(desc.shape) == (K, N, conf.input_dim), f"a feature store holds descriptors [K, N, {conf.input_dim}]"
-        st = SimpleNamespace(K=K, N=N, kpts=f32(kpts), desc=f32(desc), size=None, scales=None, oris=None, num=None)
+        desc, desc_f16 = _engine_descriptors(desc, device)
+        st = SimpleNamespace(K=K, N=N, kpts=f32(kpts), desc=desc, desc_f16=desc_f16, size=None, scales=None, oris=None, num=None)
         size = feats.get("image_size")
         if size is not None:
             if not isinstance(size, torch.Tensor):
@@ -543,7 +564,8 @@ class LightGlue(nn.Module):
     def match_pairs(self, feats0: dict, pairs, feats1: Optional[dict] = None, *, deferred: bool = False, validate: bool = True):
         """Match a pair list over feature stores: pair p = (i, j) matches image i of `feats0` against image j of `feats1` (None: of `feats0` too).
 
-        A store is what an extractor returns for a K-image batch, or `glue.collate_features` builds: {keypoints [K,N,2], descriptors [K,N,D],
+        A store is what an extractor returns for a K-image batch, or `glue.collate_features` builds: {keypoints [K,N,2], descriptors [K,N,D] (fp32, or
+        float16 — read in place, no fp32 copy of the store is made; the two stores may differ),
         num_keypoints [K] (optional), image_size [K,2] | [1,2] | [2] (optional), scales / oris [K,N] iff add_scale_ori}; other keys are ignored.
         `pairs`: [P, 2] integers (sequence, CPU or device tensor).  Returns the dict of `forward` for a batch of P pairs — bit-identical to `forward` on the
         stacked tensors {k: v[index]} — but the engine reads every pair's rows IN the store (LG_FLAG_INDEXED): nothing is stacked, and P is not bound by the
@@ -598,7 +620,8 @@ class LightGlue(nn.Module):
                 guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
                 self._guard_pending = False
                 flags = (_cabi.LG_FLAG_EXT | _cabi.LG_FLAG_INDEXED | (0 if pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
-                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0))
+                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
+                         | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0))
                 inputs = (s0.kpts, s1.kpts, s0.desc, s1.desc, s0.size, s1.size, s0.scales, s0.oris, s1.scales, s1.oris, s0.num, s1.num)
                 lib, stream_ptr = _cabi.load(), C.c_void_p(cur_stream.cuda_stream)
                 for start, stop in chunks:

@@ -18,7 +18,7 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
-from .superpoint_head import descriptor_head, detect_keypoints
+from .superpoint_head import check_descriptor_dtype, descriptor_head, detect_keypoints
 
 _LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
 
@@ -28,7 +28,10 @@ class SuperPoint(nn.Module):
                     "remove_borders": 4,   # ref :108-114
                     # extension: "fp32" = exact f32 MFMA convolutions (default); "f16x3" = split-f16 operands, three f16 MFMAs per product, fp32 accumulation (22 operand bits:
                     # below an fp32 convolution's summation-order noise, cf. the reference's own GPU default of TF32 convolutions) at several times the f32 MFMA rate
-                    "conv_precision": "fp32"}
+                    "conv_precision": "fp32",
+                    # extension: element type of the returned descriptors.  torch.float16 = the fp32 descriptors rounded once, on store, by the head's last kernel
+                    # (half the bytes of a feature store; LightGlue reads them in place).  A storage format, opt-in: outside the matcher's 1e-3 score bar (README)
+                    "descriptor_dtype": torch.float32}
     required_data_keys = ["image"]
 
     def __init__(self, weights: Optional[dict] = None, **conf):
@@ -49,6 +52,7 @@ class SuperPoint(nn.Module):
             raise ValueError("conv_precision must be 'fp32' or 'f16x3'")
         if self.conf.max_num_keypoints is not None and self.conf.max_num_keypoints <= 0:
             raise ValueError("max_num_keypoints must be positive or None")   # ref :146-147
+        check_descriptor_dtype(self.conf.descriptor_dtype)
         if weights is not None:
             self.load_state_dict(weights)
         self._packed = None   # (signature, [24 device tensors])
@@ -108,7 +112,7 @@ class SuperPoint(nn.Module):
     # ------------------------------------------------------------------ the reference's forward
     @torch.no_grad()
     def forward(self, data: dict) -> dict:
-        """ref :147-232.  Returns keypoints [B, N, 2] (x, y), keypoint_scores [B, N], descriptors [B, N, 256] and — extension for
+        """ref :147-232.  Returns keypoints [B, N, 2] (x, y), keypoint_scores [B, N], descriptors [B, N, 256] (conf.descriptor_dtype) and — extension for
         ragged batches — num_keypoints [B] (rows beyond an image's count are padding; with max_num_keypoints and enough
         detections every image has exactly that many, as the reference's torch.stack requires)."""
         for key in self.required_data_keys:
@@ -121,7 +125,7 @@ class SuperPoint(nn.Module):
         if bool((counts < nmax).any()):   # ragged batch: rows beyond an image's count are padding — zero them (descriptor_head does the same)
             live = torch.arange(nmax, device=counts.device)[None, :] < counts[:, None]
             kpts = kpts * live[..., None]; kscores = kscores * live
-        desc = descriptor_head(kpts, dense, 8, counts)
+        desc = descriptor_head(kpts, dense, 8, counts, dtype=c.descriptor_dtype)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}   # counts: consumed by LightGlue.forward
 
     preprocess_conf = {"resize": None}   # NOT the reference's 1024 (superpoint.py:115-117): see extract()

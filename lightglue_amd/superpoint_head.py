@@ -13,8 +13,16 @@ import torch
 from . import _cabi
 
 
+def check_descriptor_dtype(dtype) -> torch.dtype:
+    """The element types an extractor writes its descriptors in: float32 (default) or float16 (rounded once, on store, by the last kernel)."""
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"descriptor_dtype must be torch.float32 or torch.float16, got {dtype}")
+    return dtype
+
+
 def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: bool,
-         num_keypoints: Optional[torch.Tensor]) -> torch.Tensor:
+         num_keypoints: Optional[torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    check_descriptor_dtype(dtype)
     if dense.device.type != "cuda":
         raise RuntimeError("lightglue_amd.superpoint_head runs on MI355X (ROCm device type 'cuda') only; there is no "
                            f"CPU fallback. Got a descriptor map on {dense.device}.")
@@ -28,30 +36,33 @@ def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: 
     if num_keypoints is not None:
         num = torch.as_tensor(num_keypoints).to(device=device, dtype=torch.int32).contiguous()
         assert num.shape == (b,)
-    out = torch.empty((b, n, c), device=device, dtype=torch.float32)
+    out = torch.empty((b, n, c), device=device, dtype=dtype)
     work = torch.empty((b, h, w, c), device=device, dtype=torch.float32)
     ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        _cabi.check(_cabi.load().lg_sp_sample_descriptors(
+        lib = _cabi.load()
+        sample = lib.lg_sp_sample_descriptors_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors
+        _cabi.check(sample(
             ptr(dense), b, c, h, w, ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
             C.c_void_p(stream)))
     return out
 
 
-def sample_descriptors(keypoints: torch.Tensor, descriptors: torch.Tensor, s: int = 8) -> torch.Tensor:
+def sample_descriptors(keypoints: torch.Tensor, descriptors: torch.Tensor, s: int = 8, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Same contract as the reference function (superpoint.py:80-95): `keypoints [b, N, 2]` pixel (x, y),
     `descriptors [b, c, h, w]` -> L2-normalised bilinear samples `[b, c, N]` (a transposed view of the kernel's
-    matcher-ready `[b, N, c]` output).  Unlike the reference, `keypoints` is not modified in place."""
-    return _run(keypoints, descriptors, s, False, None).transpose(1, 2)
+    matcher-ready `[b, N, c]` output).  Unlike the reference, `keypoints` is not modified in place.  `dtype=torch.float16`: the fp32 result
+    rounded once on store (`lg_sp_sample_descriptors_half`), bit-identical to `.half()` of the fp32 output."""
+    return _run(keypoints, descriptors, s, False, None, dtype).transpose(1, 2)
 
 
 def descriptor_head(keypoints: torch.Tensor, dense_descriptors: torch.Tensor, s: int = 8,
-                    num_keypoints: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    num_keypoints: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Descriptor tail of SuperPoint.forward (superpoint.py:216-228) for a whole (ragged) batch: dense L2
     normalisation over channels, sampling at the keypoints, final normalisation, `[B, N, 256]` layout.
-    `dense_descriptors` is the raw `convDb` output `[B, 256, H/8, W/8]`; rows >= num_keypoints[b] come back zero."""
-    return _run(keypoints, dense_descriptors, s, True, num_keypoints)
+    `dense_descriptors` is the raw `convDb` output `[B, 256, H/8, W/8]`; rows >= num_keypoints[b] come back zero.  `dtype` as for `sample_descriptors`."""
+    return _run(keypoints, dense_descriptors, s, True, num_keypoints, dtype)
 
 
 def detect_keypoints(scores: torch.Tensor, nms_radius: int = 4, remove_borders: int = 4, detection_threshold: float = 0.0005,

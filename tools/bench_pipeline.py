@@ -4,7 +4,7 @@ pair through ONE extractor forward (2B images, top-k keypoints, ragged counts ca
 (seeded; the released checkpoints are network-only) and random images: the numbers are the pipeline's cost, not its matching quality.  Reports ms per step and image
 pairs/s for the extractor alone, the matcher alone on the extractor's output, and both.
 
-usage: bench_pipeline.py [--pairs 8] [--kpts 1024] [--sizes 480x640,768x1024] [--steps 20] [--conv-precision fp32|f16x3]"""
+usage: bench_pipeline.py [--pairs 8] [--kpts 1024] [--sizes 480x640,768x1024] [--steps 20] [--conv-precision fp32|f16x3] [--descriptor-dtype f32|f16]"""
 import argparse
 import sys
 import time
@@ -37,8 +37,10 @@ def main():
     ap.add_argument("--sizes", default="480x640,768x1024")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "f16x3"], help="the extractor's convolution arithmetic (lightglue_amd.SuperPoint conv_precision)")
+    ap.add_argument("--descriptor-dtype", default="f32", choices=["f32", "f16"], help="element type the extractor writes its descriptors in (SuperPoint descriptor_dtype); the matcher reads float16 in place")
     a = ap.parse_args()
-    ext = SuperPoint(weights=G.encoder_state_dict(0), max_num_keypoints=a.kpts, conv_precision=a.conv_precision).cuda().eval()
+    ext = SuperPoint(weights=G.encoder_state_dict(0), max_num_keypoints=a.kpts, conv_precision=a.conv_precision,
+                     descriptor_dtype=torch.float16 if a.descriptor_dtype == "f16" else torch.float32).cuda().eval()
     matcher = gpu_util.make_model(synth.make_state_dict(0, recipe="A"), "f16x3", depth_confidence=-1, width_confidence=-1)
     B = a.pairs
     for size in a.sizes.split(","):
@@ -75,7 +77,7 @@ def main():
         overlapped(3); torch.cuda.synchronize(); t0 = time.perf_counter(); out2 = overlapped(a.steps); torch.cuda.synchronize(); t_o = (time.perf_counter() - t0) / a.steps
         same = all(torch.equal(x, y) for x, y in zip(out["matches"], out2["matches"]))
         n = data["image0"]["num_keypoints"].float().mean().item()
-        print(f"[{a.conv_precision}] {h}x{w}, {B} pairs per step, {n:.0f} keypoints per image on average (cap {a.kpts}): extractor {t_e * 1e3:6.2f} ms ({2 * B / t_e:6.0f} images/s), "
+        print(f"[{a.conv_precision}, {a.descriptor_dtype} descriptors] {h}x{w}, {B} pairs per step, {n:.0f} keypoints per image on average (cap {a.kpts}): extractor {t_e * 1e3:6.2f} ms ({2 * B / t_e:6.0f} images/s), "
               f"matcher {t_m * 1e3:6.2f} ms ({B / t_m:6.0f} pairs/s), images -> matches {t_b * 1e3:6.2f} ms = {B / t_b:6.0f} image pairs/s; the two stages on two streams {t_o * 1e3:6.2f} ms = {B / t_o:6.0f} image pairs/s (same matches: {same}); matches per pair {sum(len(x) for x in out['matches']) / B:.0f}", flush=True)
 
 
