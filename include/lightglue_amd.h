@@ -295,6 +295,34 @@ int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32
                  void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts,
                  int32_t* totals, void* hip_stream);
 
+/* ---- SuperPoint on a ragged batch: images of different sizes in ONE call ----
+ * The batch is a canvas [batch][1][hc][wc]; image b is its top-left h_b x w_b corner, 8 <= h_b <= hc, 8 <= w_b <= wc, and `sizes` is a device array
+ * int32 [batch][2] = (w_b, h_b).  Rule of every kernel: addresses and strides come from the canvas, every bound (zero padding, stores, pooling, NMS padding,
+ * borders, grid normalisation) from the image, so nothing outside an image is read — the canvas padding may hold anything, NaN included — and for every image the
+ * outputs are BIT-IDENTICAL to the batch-1 call on its h_b x w_b crop.  Extents: pyramid level k (h_b >> k, w_b >> k) inside the canvas (hc >> k, wc >> k); score map
+ * ((h_b >> 3) << 3, (w_b >> 3) << 3); descriptor map (h_b >> 3, w_b >> 3).  The kernels clamp `sizes` into the canvas (a bad value cannot address outside a
+ * buffer); validating them is the caller's job, who has them as host integers.  Null pointers, batch < 1 and a canvas below 8 x 8 are refused before the GPU is touched.
+ * lg_sp_encode_ragged: lg_sp_encode (split == 0) / lg_sp_encode_split (split != 0: the canvas hc * wc < 2^25 pixels) on the canvas; workspace
+ *   lg_sp_encode_workspace_bytes(batch, hc, wc).  scores [batch][hc/8*8][wc/8*8]: 0 outside an image's score map; desc_map [batch][256][hc/8][wc/8]: unspecified outside
+ *   an image's map (and never read by lg_sp_sample_descriptors_ragged).
+ * lg_sp_detect_ragged: lg_sp_detect on a score canvas [batch][h][w]; here `sizes` holds the (w, h) of the SCORE maps (after lg_sp_encode_ragged: whole cells,
+ *   (w_b >> 3) << 3).  Pixels outside a map are max_pool2d's -inf padding — not zeros, which would be maxima of their own and suppress real maxima next to the far
+ *   border — and never pass the threshold; the far borders are the map's.  Keypoints are (x, y) in the image's own frame (the corner is the origin).
+ * lg_sp_sample_descriptors_ragged(_half): lg_sp_sample_descriptors(_half) on a descriptor canvas [batch][256][h][w]; `sizes` holds the IMAGES' (w_b, h_b): the map
+ *   of image b is (h_b / cell, w_b / cell). */
+int lg_sp_encode_ragged(const float* image, int32_t batch, int32_t hc, int32_t wc, const int32_t* sizes, const float* const* params, void* workspace,
+                        int64_t workspace_bytes, float* scores, float* desc_map, int32_t split, void* hip_stream);
+int lg_sp_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
+                        float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates,
+                        void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts,
+                        int32_t* totals, void* hip_stream);
+int lg_sp_sample_descriptors_ragged(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes,
+                                    const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
+                                    int32_t normalize_dense, float* workspace, float* out, void* hip_stream);
+int lg_sp_sample_descriptors_ragged_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes,
+                                         const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
+                                         int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream);
+
 /* ---- ALIKED extractor (aliked-n16 / n16rot / n32; lightglue/aliked.py:612-760) ----
  * Exact fp32 arithmetic throughout.  `n_pos` selects the model: 16 (aliked-n16, aliked-n16rot) or 32 (aliked-n32); anything else is
  * refused.  Images: h, w >= 8 and a padded size (h, w rounded up to multiples of 32) below 2^25 pixels.  Device pointers, caller's stream.

@@ -7,7 +7,7 @@ SURVEY.md §8 f3: the SuperPoint extractor (conv stack, keypoint extraction, des
 (``lightglue_amd.SuperPoint``), and so does ALIKED (``lightglue_amd.ALIKED``, aliked-n16 / n32).  The resize in front of them (the reference's ``ImagePreprocessor``) is ``lightglue_amd.ImagePreprocessor``, one HIP kernel.  Other extractors, image file I/O and visualisation are out of scope.
 """
 from .lightglue import LightGlue  # noqa: F401
-from .superpoint import SuperPoint  # noqa: F401
+from .superpoint import SuperPoint, plan_image_batches  # noqa: F401
 from .aliked import ALIKED  # noqa: F401
 from .preprocess import ImagePreprocessor, numpy_image_to_torch  # noqa: F401
 from .parallel import PairShardedMatcher, shard_range  # noqa: F401
@@ -15,5 +15,5 @@ from .inflight import InflightMatcher  # noqa: F401
 from .glue import batch_to_device, cm_prune, collate_features, extracted_to_image_frame, match_batch, match_pair, match_pairs, prefetch_to_device, rbd  # noqa: F401
 
 __all__ = ["LightGlue", "SuperPoint", "ALIKED", "ImagePreprocessor", "numpy_image_to_torch", "PairShardedMatcher", "InflightMatcher", "shard_range", "match_pair", "match_batch", "match_pairs", "collate_features", "extracted_to_image_frame", "rbd", "cm_prune",
-           "batch_to_device", "prefetch_to_device"]
+           "batch_to_device", "prefetch_to_device", "plan_image_batches"]
 __version__ = "0.2.0"

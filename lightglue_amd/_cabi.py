@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
     "lg_preprocess_plan", "lg_preprocess_resize",
     "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
+    "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
 )
 
 
@@ -150,6 +151,13 @@ def load() -> C.CDLL:
     lib.lg_sp_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lg_sp_pack_conv_weight_split.argtypes = lib.lg_sp_pack_conv_weight.argtypes
     lib.lg_sp_encode_split.argtypes = lib.lg_sp_encode.argtypes
+    # the ragged forms: `sizes` (int32 [B][2] (w, h), device) follows the map / canvas size
+    lib.lg_sp_encode_ragged.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p])
+    lib.lg_sp_detect_ragged.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_float] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+    lib.lg_sp_sample_descriptors_ragged.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lg_sp_sample_descriptors_ragged_half.argtypes = lib.lg_sp_sample_descriptors_ragged.argtypes
     lib.lg_aliked_packed_bytes.argtypes = [C.c_int32]
     lib.lg_aliked_packed_bytes.restype = C.c_int64
     lib.lg_aliked_pack_weights.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

@@ -25,13 +25,35 @@ struct ConvArgs {
 };
 void launch_conv(const ConvArgs& a, hipStream_t s);      // exact fp32; Cin % 16 == 0
 
+// Ragged batch: H, W are the CANVAS of this pyramid level and give every address and stride; image b occupies its top-left
+// (sizes[2b + 1] >> size_shift) x (sizes[2b] >> size_shift) corner and gives every bound (padding select, stores, pool).  A struct of its own, taken by the RAGGED
+// instances of the convolution kernels only: the uniform instances keep ConvArgs as their kernel argument and compile to the code they were (a larger
+// argument block alone changes how the compiler groups their scalar loads).
+struct RaggedConvArgs : ConvArgs {
+    const int* sizes; int size_shift;                    // [B][2] (w, h) at full resolution; the level's repeated floor halving
+};
+void launch_conv(const RaggedConvArgs& a, hipStream_t s);
+template <class A> inline constexpr bool is_ragged = false;
+template <> inline constexpr bool is_ragged<RaggedConvArgs> = true;
+
+// The extent (rows, columns) the bounds of image b are taken from: a.H / a.W read where they always were (uniform), or the image's, clamped to [1, canvas] —
+// a bad size cannot address outside a buffer (validation proper is the caller's, who has the sizes as host integers).
+struct ConvExtent { int h, w; };
+template <class A> __device__ __forceinline__ ConvExtent conv_extent(const A& a, int b) {
+    if constexpr (is_ragged<A>) return {min(max(a.sizes[2 * b + 1] >> a.size_shift, 1), a.H), min(max(a.sizes[2 * b] >> a.size_shift, 1), a.W)};
+    else return {0, 0};      // (never read)
+}
+template <bool RAGGED> __device__ __forceinline__ int ext_h(const ConvArgs& a, const ConvExtent& e) { if constexpr (RAGGED) return e.h; else return a.H; }
+template <bool RAGGED> __device__ __forceinline__ int ext_w(const ConvArgs& a, const ConvExtent& e) { if constexpr (RAGGED) return e.w; else return a.W; }
+
 constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.0507009873554804934193349852946f;
 __device__ __forceinline__ float selu(float x) { return SELU_SCALE * (x > 0.f ? x : SELU_ALPHA * expm1f(x)); }
 
 // bias / activation / 2x2 max-pool / stores of one wave's 2 rows x 32 pixels x 16 NT output channels, straight from the accumulators:
 // acc[mt][nt][r] = out[pixel (y0 + mt / 2, x0 + (mt & 1) * 16 + 4g + r)][cout n0 + nt * 16 + lr]
-template <int NT>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][NT], int b, int n0, int x0, int y0, int lr, int g) {
+// Strides come from a.H / a.W (the canvas), bounds from the image extent `e` (RAGGED) — the same a.H / a.W otherwise.
+template <int NT, bool RAGGED = false>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][NT], int b, int n0, int x0, int y0, int lr, int g, const ConvExtent& e = ConvExtent{0, 0}) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int co = n0 + nt * 16 + lr;
@@ -46,33 +68,34 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4]
         }
         if (a.pool) {        // 2x2 max-pool (SuperPoint): rows y0, y0 + 1; columns (4g, 4g + 1), (4g + 2, 4g + 3)
             const int H2 = a.H >> 1, W2 = a.W >> 1, yo = y0 >> 1;
-            if (yo < H2) {
+            const int H2i = ext_h<RAGGED>(a, e) >> 1, W2i = ext_w<RAGGED>(a, e) >> 1;       // pooled bounds: the image's; pooled strides: the canvas's
+            if (yo < H2i) {
 #pragma unroll
                 for (int xt = 0; xt < 2; ++xt) {
                     const float p0 = fmaxf(fmaxf(v[xt][0], v[xt][1]), fmaxf(v[2 + xt][0], v[2 + xt][1]));
                     const float p1 = fmaxf(fmaxf(v[xt][2], v[xt][3]), fmaxf(v[2 + xt][2], v[2 + xt][3]));
                     const int xo = (x0 + xt * 16 + 4 * g) >> 1;
                     float* o = a.out + (((long long)b * H2 + yo) * W2 + xo) * a.Cout + co;
-                    if (xo < W2) o[0] = p0;
-                    if (xo + 1 < W2) o[a.Cout] = p1;
+                    if (xo < W2i) o[0] = p0;
+                    if (xo + 1 < W2i) o[a.Cout] = p1;
                 }
             }
         } else {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 const int y = y0 + (mt >> 1), x = x0 + (mt & 1) * 16 + 4 * g;
-                if (y >= a.H) continue;
-                if (a.out_nchw) {    // 4 consecutive pixels of one channel: one 16-byte store when the row allows it
+                if (y >= ext_h<RAGGED>(a, e)) continue;
+                if (a.out_nchw) {    // 4 consecutive pixels of one channel: one 16-byte store when the row allows it (alignment: the canvas width)
                     float* o = a.out + (((long long)b * a.Cout + co) * a.H + y) * a.W + x;
-                    if (x + 3 < a.W && (a.W & 3) == 0) *reinterpret_cast<f32x4*>(o) = v[mt];
+                    if (x + 3 < ext_w<RAGGED>(a, e) && (a.W & 3) == 0) *reinterpret_cast<f32x4*>(o) = v[mt];
                     else {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) if (x + r < a.W) o[r] = v[mt][r];
+                        for (int r = 0; r < 4; ++r) if (x + r < ext_w<RAGGED>(a, e)) o[r] = v[mt][r];
                     }
                 } else {
                     float* o = a.out + (((long long)b * a.H + y) * a.W + x) * a.Cout + co;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) if (x + r < a.W) o[(long long)r * a.Cout] = v[mt][r];
+                    for (int r = 0; r < 4; ++r) if (x + r < ext_w<RAGGED>(a, e)) o[(long long)r * a.Cout] = v[mt][r];
                 }
             }
         }
@@ -103,7 +126,18 @@ struct DetectArgs {
     int* cand_idx; float* cand_score; int* cand_total;   // [B][max_candidates] raster index y W + x and value, [B] hits
     int K, sort_always;                // keep the K best (K <= 0: all); ordered by score when that limited the set, or always
     int sel_cap; int* sel; unsigned* sel_key;        // [B][sel_cap] kept candidates in raster order and their keys
+    // ragged batch (null: every map fills H x W): H, W are the CANVAS (addresses, strides, the raster index y W + x); the score map of image b is its top-left
+    // sizes[2b + 1] x sizes[2b] corner ([B][2] (w, h) of the SCORE maps: SuperPoint passes whole 8 x 8 cells, (h_b >> 3) << 3).  Outside it a pixel is max_pool2d's
+    // -inf padding: never a maximum, never in supp_mask, never above the threshold; the far borders are that corner's.
+    const int* sizes;
 };
+
+// rows / columns of image b's score map: the bound of every detection kernel (clamped into the canvas; H x W when the batch is uniform)
+struct DetectExtent { int h, w; };
+__device__ __forceinline__ DetectExtent detect_extent(const DetectArgs& a, int b) {
+    if (!a.sizes) return {a.H, a.W};
+    return {min(max(a.sizes[2 * b + 1], 0), a.H), min(max(a.sizes[2 * b], 0), a.W)};
+}
 
 // the workspace of one detection, carved from one buffer; rowsum / th only with `stats` (ALIKED's mean fallback)
 struct DetectLayout { long long mask_a, mask_b, nms, rows, rowsum, th, cidx, cscore, ctotal, sel, selkey, total; };

@@ -7,9 +7,10 @@ namespace lg {
 // ==================================================================================================== convolution
 // acc[mt][nt] += the wave's 2 rows x 32 pixels x 16 NT channels of one operand pair (in [pixel][Cin] of one image, w [taps][Cout][Cin]).
 // H, W and Cout are read from `a` where they are used (kernel arguments): passed as values, the NT = 4 instance needs 141 VGPRs instead of 126.
-template <int NT>
+// Addresses and strides: a.H / a.W (the canvas); the padding select and the address clamp: the image extent `e` when RAGGED (conv_extent), so nothing outside an image is read.
+template <int NT, bool RAGGED>
 __device__ __forceinline__ void conv_accum(f32x4 (&acc)[4][NT], const ConvArgs& a, const float* inb, const float* wf, int Cin, int taps, int n0, int x0,
-                                           int y0, int lr, int g) {
+                                           int y0, int lr, int g, const ConvExtent& e) {
     const int nchunk = Cin >> 4;
     const int ntl = min(NT, (a.Cout - n0 + 15) >> 4);        // live n-tiles of this channel group (wave-uniform)
     for (int tap = 0; tap < taps; ++tap) {
@@ -19,8 +20,8 @@ __device__ __forceinline__ void conv_accum(f32x4 (&acc)[4][NT], const ConvArgs& 
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const int yy = y0 + (mt >> 1) + dy, xx = x0 + (mt & 1) * 16 + lr + dx;
-            ok[mt] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-            const int yc = min(max(yy, 0), a.H - 1), xc = min(max(xx, 0), a.W - 1);
+            ok[mt] = yy >= 0 && yy < ext_h<RAGGED>(a, e) && xx >= 0 && xx < ext_w<RAGGED>(a, e);
+            const int yc = min(max(yy, 0), ext_h<RAGGED>(a, e) - 1), xc = min(max(xx, 0), ext_w<RAGGED>(a, e) - 1);
             poff[mt] = ((long long)yc * a.W + xc) * Cin + 4 * g;
         }
         long long wrow[NT];   // weight row of every n-tile, in elements (clamped into the matrix; dead lanes are zeroed after the load)
@@ -47,36 +48,41 @@ __device__ __forceinline__ void conv_accum(f32x4 (&acc)[4][NT], const ConvArgs& 
     }
 }
 
-// grid (W / 32, H / 8, B * cout groups of 16 NT)
-template <int NT, bool EXTRA>
-__global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
+// grid (W / 32, H / 8, B * cout groups of 16 NT).  RAGGED: a tile whose origin lies outside its image has nothing to do
+template <int NT, bool EXTRA, class A>
+__global__ __launch_bounds__(256) void conv_kernel(A a) {
+    constexpr bool RAGGED = is_ragged<A>;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     const int ngroups = (a.Cout + 16 * NT - 1) / (16 * NT);
     const int b = blockIdx.z / ngroups, n0 = (blockIdx.z - b * ngroups) * 16 * NT;
     const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 8 + wv * 2;
-    if (y0 >= a.H) return;
+    const ConvExtent e = conv_extent(a, b);
+    if (y0 >= ext_h<RAGGED>(a, e)) return;
+    if constexpr (RAGGED) { if (x0 >= e.w) return; }
     f32x4 acc[4][NT];   // [mt = ry * 2 + xt][nt]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const long long img = (long long)b * a.H * a.W;
-    conv_accum<NT>(acc, a, a.in + img * a.Cin, static_cast<const float*>(a.w), a.Cin, a.taps, n0, x0, y0, lr, g);
-    if constexpr (EXTRA) conv_accum<NT>(acc, a, a.in2 + img * a.Cin2, a.w2, a.Cin2, 1, n0, x0, y0, lr, g);
-    conv_epilogue<NT>(a, acc, b, n0, x0, y0, lr, g);
+    conv_accum<NT, RAGGED>(acc, a, a.in + img * a.Cin, static_cast<const float*>(a.w), a.Cin, a.taps, n0, x0, y0, lr, g, e);
+    if constexpr (EXTRA) conv_accum<NT, RAGGED>(acc, a, a.in2 + img * a.Cin2, a.w2, a.Cin2, 1, n0, x0, y0, lr, g, e);
+    conv_epilogue<NT, RAGGED>(a, acc, b, n0, x0, y0, lr, g, e);
 }
 
-template <int NT> static void conv_nt(const ConvArgs& a, hipStream_t s) {
+template <int NT, class A> static void conv_nt(const A& a, hipStream_t s) {
     const dim3 grid((a.W + 31) / 32, (a.H + 7) / 8, a.B * ((a.Cout + 16 * NT - 1) / (16 * NT)));
-    if (a.in2) hipLaunchKernelGGL((conv_kernel<NT, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv_kernel<NT, false>), grid, dim3(256), 0, s, a);
+    if (a.in2) hipLaunchKernelGGL((conv_kernel<NT, true, A>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv_kernel<NT, false, A>), grid, dim3(256), 0, s, a);
 }
 
-void launch_conv(const ConvArgs& a, hipStream_t s) {
+template <class A> static void conv_any(const A& a, hipStream_t s) {
     if (a.Cout <= 16) conv_nt<1>(a, s);
     else if (a.Cout <= 32) conv_nt<2>(a, s);
     else conv_nt<4>(a, s);
 }
+void launch_conv(const ConvArgs& a, hipStream_t s) { conv_any(a, s); }
+void launch_conv(const RaggedConvArgs& a, hipStream_t s) { conv_any(a, s); }
 
 // ==================================================================================================== weight repack
 __global__ __launch_bounds__(256) void fold_kernel(const float* src, float* dst, float* bias_dst, int Cout, int Cin, int kk, int mode, const float* gamma,
@@ -137,7 +143,11 @@ __global__ __launch_bounds__(256) void nms_kernel(DetectArgs a, int mode, const 
     __shared__ unsigned char sM[NLH][NLW], sHM[NLH][NLW], sSupp[NLH][NLW];
     const int b = blockIdx.z, ty0 = blockIdx.y * NTY, tx0 = blockIdx.x * NTX, r = a.radius, O = 2 * NR;   // O: local origin offset
     const long long img = (long long)b * a.H * a.W;
-    auto inside = [&](int ly, int lx) { const int y = ty0 + ly - O, x = tx0 + lx - O; return y >= 0 && y < a.H && x >= 0 && x < a.W; };
+    // the bound is image b's score extent, the strides are the canvas's.  A pixel outside the extent is padding (-inf, mask 0), NOT a zero score: 0 == maxpool(0) would make it
+    // a maximum, and the first suppression round would then remove real maxima within r of the far border
+    const DetectExtent e = detect_extent(a, b);
+    if (ty0 >= e.h || tx0 >= e.w) return;       // tile outside the image (workgroup-uniform, before the first barrier): nothing to write, and nobody reads there
+    auto inside = [&](int ly, int lx) { const int y = ty0 + ly - O, x = tx0 + lx - O; return y >= 0 && y < e.h && x >= 0 && x < e.w; };
     // ---- load S (and the mask) for tile +- 2r; outside the image: -inf / 0 (max_pool2d pads with -inf)
     for_region(O - 2 * r, O + NTY + 2 * r, O - 2 * r, O + NTX + 2 * r, [&](int ly, int lx) {
         const bool in = inside(ly, lx);
@@ -206,9 +216,11 @@ void launch_nms(const DetectArgs& a, hipStream_t s) {
 }
 
 // ==================================================================================================== threshold + compaction
-__device__ __forceinline__ float detect_value(const DetectArgs& a, int b, int y, int x) {
-    int hl = a.H, wl = a.W;
+// far edges: image_size (truncated like .long()) where given, else the image's score extent; outside that extent: -inf, which no threshold lets pass (also with border == 0)
+__device__ __forceinline__ float detect_value(const DetectArgs& a, const DetectExtent& e, int b, int y, int x) {
+    int hl = e.h, wl = e.w;
     if (a.image_size) { wl = (int)a.image_size[2 * b]; hl = (int)a.image_size[2 * b + 1]; }   // .long(): truncation
+    if (y >= e.h || x >= e.w) return -INFINITY;
     const bool border = a.border > 0 && (y < a.border || x < a.border || y >= hl - a.border || x >= wl - a.border);
     return border ? a.border_value : a.nms[((long long)b * a.H + y) * a.W + x];
 }
@@ -218,9 +230,10 @@ __global__ __launch_bounds__(256) void row_count_kernel(DetectArgs a, const floa
     const int y = blockIdx.x, b = blockIdx.y;
     const long long row = ((long long)b * a.H + y) * a.W;
     const float t = th ? th[b] : a.threshold;
+    const DetectExtent e = detect_extent(a, b);
     int cnt = 0; double sum = 0.0;
     for (int x = threadIdx.x; x < a.W; x += 256) {
-        cnt += detect_value(a, b, y, x) > t;
+        cnt += detect_value(a, e, b, y, x) > t;
         if (rowsum) sum += (double)a.S[row + x];
     }
     __shared__ int sh[4];
@@ -239,6 +252,7 @@ __global__ __launch_bounds__(256) void row_count_kernel(DetectArgs a, const floa
 __global__ __launch_bounds__(256) void compact_kernel(DetectArgs a, const float* th) {
     const int y = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float t = th ? th[b] : a.threshold;
+    const DetectExtent e = detect_extent(a, b);
     __shared__ int sh[4];
     int pre = 0;
     for (int yy = tid; yy < y; yy += 256) pre += a.row_counts[b * a.H + yy];
@@ -246,7 +260,7 @@ __global__ __launch_bounds__(256) void compact_kernel(DetectArgs a, const float*
     const long long cb = (long long)b * a.max_candidates;
     for (int x0 = 0; x0 < a.W; x0 += 256) {
         const int x = x0 + tid;
-        const float v = x < a.W ? detect_value(a, b, y, x) : 0.f;
+        const float v = x < a.W ? detect_value(a, e, b, y, x) : 0.f;
         const bool hit = x < a.W && v > t;
         const unsigned long long bal = __ballot(hit);
         __syncthreads();

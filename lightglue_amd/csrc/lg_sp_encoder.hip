@@ -22,12 +22,17 @@ namespace lg {
 // Same tiles (64 output channels per wave), epilogue and layouts as the fp32 form.  Measured on the 3 x 3 layers before they moved to the LDS-staged
 // kernel below (profiles/r06sp_*): 1.2 x the fp32 form, not the 5 x of the MFMA rates — with 16 KB of operand loads per 48 MFMAs and no LDS staging the
 // kernel is bound by its loads and their address / split arithmetic, whatever the matrix instruction costs.
-__global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(ConvArgs a) {
+// A = RaggedConvArgs (both split kernels, as in conv_kernel): strides from the canvas a.H / a.W, every bound from the image extent; the uniform instances are the code they were.
+template <class A>
+__global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(A a) {
+    constexpr bool RAGGED = is_ragged<A>;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     const int ngroups = (a.Cout + 63) >> 6;
     const int b = blockIdx.z / ngroups, n0 = (blockIdx.z - b * ngroups) << 6;
     const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 8 + wv * 2;
-    if (y0 >= a.H) return;
+    const ConvExtent e = conv_extent(a, b);
+    if (y0 >= ext_h<RAGGED>(a, e)) return;
+    if constexpr (RAGGED) { if (x0 >= e.w) return; }
     f32x4 acc[4][4];   // [mt = ry*2 + xt][nt]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -42,8 +47,8 @@ __global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(ConvArgs a) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         const int yy = y0 + (mt >> 1), xx = x0 + (mt & 1) * 16 + lr;
-        ok[mt] = yy < a.H && xx < a.W;
-        const int yc = min(yy, a.H - 1), xc = min(xx, a.W - 1);
+        ok[mt] = yy < ext_h<RAGGED>(a, e) && xx < ext_w<RAGGED>(a, e);
+        const int yc = min(yy, ext_h<RAGGED>(a, e) - 1), xc = min(xx, ext_w<RAGGED>(a, e) - 1);
         poff[mt] = ((long long)yc * a.W + xc) * a.Cin + 8 * g;
     }
     long long wrow[4];   // weight row of every n-tile, in elements (clamped into the matrix; dead lanes are zeroed after the load)
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(ConvArgs a) {
                 mma_chunk<TagF16>(acc[mt][nt], ah[mt], bh[nt]);
             }
     }
-    conv_epilogue<4>(a, acc, b, n0, x0, y0, lr, g);
+    conv_epilogue<4, RAGGED>(a, acc, b, n0, x0, y0, lr, g, e);
 }
 
 // ---- 3 x 3 convolutions of the split-f16 form, LDS-staged (conv_precision "f16x3": conv1b ... convPa / convDa; cin % 32 == 0, cout % 64 == 0).
@@ -88,12 +93,16 @@ __global__ __launch_bounds__(256) void sp_conv1x1_split_kernel(ConvArgs a) {
 constexpr int C3_HW = 34, C3_HH = 10, C3_NPX = C3_HW * C3_HH, C3_PLANE = C3_NPX * 64, C3_ITEMS = C3_NPX * 4, C3_ROUNDS = (C3_ITEMS + 255) / 256;
 __device__ __forceinline__ int c3_off(int q, int slot) { return q * 64 + ((slot ^ ((q >> 1) & 3)) << 4); }
 
-__global__ __launch_bounds__(256, 2) void sp_conv3x3_split_kernel(ConvArgs a) {     // two workgroups per CU (<= 256 VGPRs, 43.5 KB of LDS each): at one wave per SIMD the launch is 20 % slower
+template <class A>
+__global__ __launch_bounds__(256, 2) void sp_conv3x3_split_kernel(A a) {     // two workgroups per CU (<= 256 VGPRs, 43.5 KB of LDS each): at one wave per SIMD the launch is 20 % slower
     __shared__ __attribute__((aligned(16))) char smA[2 * C3_PLANE];
+    constexpr bool RAGGED = is_ragged<A>;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, g = lane >> 4;
     const int ngroups = a.Cout >> 6;
     const int b = blockIdx.z / ngroups, grp = blockIdx.z - b * ngroups, n0 = grp << 6;
     const int x0 = blockIdx.x * 32, yt = blockIdx.y * 8, y0 = yt + wv * 2;
+    const ConvExtent e = conv_extent(a, b);
+    if constexpr (RAGGED) { if (yt >= e.h || x0 >= e.w) return; }     // tile origin outside the image: workgroup-uniform, before the first barrier
     f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -109,8 +118,8 @@ __global__ __launch_bounds__(256, 2) void sp_conv3x3_split_kernel(ConvArgs a) { 
         const int item = min(tid + 256 * r, C3_ITEMS - 1);
         q = item >> 2; slot = item & 3;
         const int ry = q / C3_HW, rx = q - ry * C3_HW, yy = yt + ry - 1, xx = x0 + rx - 1;
-        inside = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-        src_off = (min(max(yy, 0), a.H - 1) * a.W + min(max(xx, 0), a.W - 1)) * a.Cin + 8 * slot;      // (element offset inside one image: H W cin < 2^31 in the extractor's envelope)
+        inside = yy >= 0 && yy < ext_h<RAGGED>(a, e) && xx >= 0 && xx < ext_w<RAGGED>(a, e);
+        src_off = (min(max(yy, 0), ext_h<RAGGED>(a, e) - 1) * a.W + min(max(xx, 0), ext_w<RAGGED>(a, e) - 1)) * a.Cin + 8 * slot;      // (element offset inside one image: H W cin < 2^31 in the extractor's envelope)
     };
     f32x4 raw[C3_ROUNDS][2];
     auto stage_load = [&](int c) {
@@ -183,23 +192,27 @@ __global__ __launch_bounds__(256, 2) void sp_conv3x3_split_kernel(ConvArgs a) { 
             __syncthreads();                                   // every wave is past its last read of the tile
         }
     }
-    conv_epilogue<4>(a, acc, b, n0, x0, y0, lr, g);
+    conv_epilogue<4, RAGGED>(a, acc, b, n0, x0, y0, lr, g, e);
 }
 
 // conv1a (ref :127, :159): 1 -> 64 channels, 3x3, pad 1, ReLU, image [B][1][H][W] -> NHWC.  K = 9: plain VALU.
 // thread = (pixel, 4 output channels); weights packed [9][64] (tap-major) and read as float4.
-__global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* img, const float* w9x64, const float* bias, float* out, int B, int H, int W) {
+// RAGGED: sizes [B][2] (w, h); H, W are then the canvas (strides), the image's h x w bounds the taps and the stores.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* img, const float* w9x64, const float* bias, float* out, int B, int H, int W, const int* sizes) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)B * H * W * 16;
     if (idx >= total) return;
     const int c4 = (int)(idx & 15);
     const long long pix = idx >> 4;
     const int x = (int)(pix % W), y = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+    int hi = H, wi = W;
+    if constexpr (RAGGED) { wi = min(max(sizes[2 * b], 1), W); hi = min(max(sizes[2 * b + 1], 1), H); if (y >= hi || x >= wi) return; }
     f32x4 s = *reinterpret_cast<const f32x4*>(bias + c4 * 4);
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        const float p = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? img[((long long)b * H + yy) * W + xx] : 0.f;
+        const float p = (yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? img[((long long)b * H + yy) * W + xx] : 0.f;
         const f32x4 wv = *reinterpret_cast<const f32x4*>(w9x64 + t * 64 + c4 * 4);
         s[0] = __builtin_fmaf(p, wv[0], s[0]); s[1] = __builtin_fmaf(p, wv[1], s[1]); s[2] = __builtin_fmaf(p, wv[2], s[2]); s[3] = __builtin_fmaf(p, wv[3], s[3]);
     }
@@ -208,11 +221,19 @@ __global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* img, const 
 }
 
 // keypoint scores (ref :176-184): softmax over the 65 logits of a cell, drop the dustbin, depth-to-space: channel c of cell
-// (i, j) -> pixel (8i + c / 8, 8j + c % 8).  One wave per cell.
-__global__ __launch_bounds__(256) void sp_scores_kernel(const float* logits, float* scores, int B, int h, int w) {
+// (i, j) -> pixel (8i + c / 8, 8j + c % 8).  One wave per cell.  sizes (ragged batch, else null): a cell outside image b's (h_b >> 3) x (w_b >> 3) has no logits:
+// it writes 0, so that the score canvas is defined everywhere.
+__global__ __launch_bounds__(256) void sp_scores_kernel(const float* logits, float* scores, int B, int h, int w, const int* sizes) {
     const int lane = threadIdx.x & 63;
     const long long cell = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (cell >= (long long)B * h * w) return;
+    if (sizes) {     // (wave-uniform: one cell per wave)
+        const int j = (int)(cell % w), i = (int)((cell / w) % h), b = (int)(cell / ((long long)w * h));
+        if (i >= min(sizes[2 * b + 1] >> 3, h) || j >= min(sizes[2 * b] >> 3, w)) {
+            scores[((long long)b * h * 8 + i * 8 + (lane >> 3)) * (w * 8) + j * 8 + (lane & 7)] = 0.f;
+            return;
+        }
+    }
     const float* p = logits + cell * 65;
     const float v = p[lane], d = p[64];
     const float m = fmaxf(wave_max(v), d);
@@ -254,42 +275,49 @@ static hipError_t launch_sp_pack_weight(const float* src, float* dst, int Cout, 
     return launch_fold(src, dst, nullptr, Cout, Cin, k * k, PK_TAP_CO_CI, nullptr, nullptr, nullptr, s);
 }
 
+// H, W: this level's canvas; sizes (ragged batch, else null) / shift: the full-resolution (w, h) of every image and the level's halving
 static void conv(bool split, const float* in, float* out, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, int taps, int relu, int pool,
-                 int nchw, hipStream_t s) {
+                 int nchw, const int* sizes, int shift, hipStream_t s) {
     const ConvArgs a{in, w, bias, nullptr, nullptr, out, B, H, W, Cin, 0, Cout, taps, relu ? ACT_RELU : ACT_NONE, pool, nchw};
+    const RaggedConvArgs ra{a, sizes, shift};
     const dim3 grid((W + 31) / 32, (H + 7) / 8, B * ((Cout + 63) / 64));
-    if (!split) launch_conv(a, s);     // (every layer of the stack has cout >= 64: the 64-channel tile)
-    else if (taps == 9) hipLaunchKernelGGL(sp_conv3x3_split_kernel, grid, dim3(256), 0, s, a);      // (every 3 x 3 layer of the stack has cin % 32 == 0 and cout % 64 == 0)
-    else hipLaunchKernelGGL(sp_conv1x1_split_kernel, grid, dim3(256), 0, s, a);
+    if (!split) { if (sizes) launch_conv(ra, s); else launch_conv(a, s); }     // (every layer of the stack has cout >= 64: the 64-channel tile)
+    else if (taps == 9) {              // (every 3 x 3 layer of the stack has cin % 32 == 0 and cout % 64 == 0)
+        if (sizes) hipLaunchKernelGGL(sp_conv3x3_split_kernel<RaggedConvArgs>, grid, dim3(256), 0, s, ra);
+        else hipLaunchKernelGGL(sp_conv3x3_split_kernel<ConvArgs>, grid, dim3(256), 0, s, a);
+    } else if (sizes) hipLaunchKernelGGL(sp_conv1x1_split_kernel<RaggedConvArgs>, grid, dim3(256), 0, s, ra);
+    else hipLaunchKernelGGL(sp_conv1x1_split_kernel<ConvArgs>, grid, dim3(256), 0, s, a);
 }
 
 // params: packed weight / bias pointers in layer order conv1a, conv1b, conv2a, conv2b, conv3a, conv3b, conv4a, conv4b, convPa, convPb,
 // convDa, convDb (24 device pointers).  ws: two ping-pong buffers of B*H*W*64 floats each.
 // split != 0: every MFMA convolution on split-f16 operands (weights packed by launch_sp_pack_weight_split; conv1a — K = 9, VALU — stays fp32 with its fp32 packing)
-static hipError_t launch_sp_encode(const float* image, int B, int H, int W, const float* const* P, float* ws, float* scores, float* desc_map, int split_flag,
-                                   hipStream_t s) {
+// sizes: null, or the ragged batch's [B][2] (w, h) — H, W are then the canvas; level k of image b is its (h_b >> k) x (w_b >> k) corner of the level's canvas
+static hipError_t launch_sp_encode(const float* image, int B, int H, int W, const int* sizes, const float* const* P, float* ws, float* scores, float* desc_map,
+                                   int split_flag, hipStream_t s) {
     const bool split = split_flag != 0;
     const long long half = (long long)B * H * W * 64;
     float* A = ws; float* Bf = ws + half;
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
     const long long px = (long long)B * H * W * 16;
-    hipLaunchKernelGGL(sp_conv1a_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, image, P[0], P[1], A, B, H, W);
-    conv(split, A, Bf, P[2], P[3], B, H, W, 64, 64, 9, 1, 1, 0, s);           // conv1b + pool  -> [H2][W2][64]
-    conv(split, Bf, A, P[4], P[5], B, H2, W2, 64, 64, 9, 1, 0, 0, s);         // conv2a
-    conv(split, A, Bf, P[6], P[7], B, H2, W2, 64, 64, 9, 1, 1, 0, s);         // conv2b + pool  -> [H4][W4][64]
-    conv(split, Bf, A, P[8], P[9], B, H4, W4, 64, 128, 9, 1, 0, 0, s);        // conv3a
-    conv(split, A, Bf, P[10], P[11], B, H4, W4, 128, 128, 9, 1, 1, 0, s);     // conv3b + pool  -> [H8][W8][128]
-    conv(split, Bf, A, P[12], P[13], B, H8, W8, 128, 128, 9, 1, 0, 0, s);     // conv4a
-    conv(split, A, Bf, P[14], P[15], B, H8, W8, 128, 128, 9, 1, 0, 0, s);     // conv4b         -> x in Bf
+    if (sizes) hipLaunchKernelGGL(sp_conv1a_kernel<true>, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, image, P[0], P[1], A, B, H, W, sizes);
+    else hipLaunchKernelGGL(sp_conv1a_kernel<false>, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, image, P[0], P[1], A, B, H, W, sizes);
+    conv(split, A, Bf, P[2], P[3], B, H, W, 64, 64, 9, 1, 1, 0, sizes, 0, s);           // conv1b + pool  -> [H2][W2][64]
+    conv(split, Bf, A, P[4], P[5], B, H2, W2, 64, 64, 9, 1, 0, 0, sizes, 1, s);         // conv2a
+    conv(split, A, Bf, P[6], P[7], B, H2, W2, 64, 64, 9, 1, 1, 0, sizes, 1, s);         // conv2b + pool  -> [H4][W4][64]
+    conv(split, Bf, A, P[8], P[9], B, H4, W4, 64, 128, 9, 1, 0, 0, sizes, 2, s);        // conv3a
+    conv(split, A, Bf, P[10], P[11], B, H4, W4, 128, 128, 9, 1, 1, 0, sizes, 2, s);     // conv3b + pool  -> [H8][W8][128]
+    conv(split, Bf, A, P[12], P[13], B, H8, W8, 128, 128, 9, 1, 0, 0, sizes, 3, s);     // conv4a
+    conv(split, A, Bf, P[14], P[15], B, H8, W8, 128, 128, 9, 1, 0, 0, sizes, 3, s);     // conv4b         -> x in Bf
     float* x = Bf;
     float* t1 = A;                                                     // [H8][W8][256]
     float* t2 = A + (long long)B * H8 * W8 * 256;                      // [H8][W8][65]
-    conv(split, x, t1, P[16], P[17], B, H8, W8, 128, 256, 9, 1, 0, 0, s);     // convPa
-    conv(split, t1, t2, P[18], P[19], B, H8, W8, 256, 65, 1, 0, 0, 0, s);     // convPb (logits)
+    conv(split, x, t1, P[16], P[17], B, H8, W8, 128, 256, 9, 1, 0, 0, sizes, 3, s);     // convPa
+    conv(split, t1, t2, P[18], P[19], B, H8, W8, 256, 65, 1, 0, 0, 0, sizes, 3, s);     // convPb (logits)
     const long long cells = (long long)B * H8 * W8;
-    hipLaunchKernelGGL(sp_scores_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, t2, scores, B, H8, W8);
-    conv(split, x, t1, P[20], P[21], B, H8, W8, 128, 256, 9, 1, 0, 0, s);     // convDa
-    conv(split, t1, desc_map, P[22], P[23], B, H8, W8, 256, 256, 1, 0, 0, 1, s);   // convDb -> NCHW raw descriptor map
+    hipLaunchKernelGGL(sp_scores_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, t2, scores, B, H8, W8, sizes);
+    conv(split, x, t1, P[20], P[21], B, H8, W8, 128, 256, 9, 1, 0, 0, sizes, 3, s);     // convDa
+    conv(split, t1, desc_map, P[22], P[23], B, H8, W8, 256, 256, 1, 0, 0, 1, sizes, 3, s);   // convDb -> NCHW raw descriptor map
     return hipGetLastError();
 }
 
@@ -316,7 +344,7 @@ int lg_sp_encode(const float* image, int32_t batch, int32_t h, int32_t w, const 
     if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
     if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
     for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 0, static_cast<hipStream_t>(hip_stream)));
+    HIPCHK(launch_sp_encode(image, batch, h, w, nullptr, params, static_cast<float*>(workspace), scores, desc_map, 0, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
 }
 
@@ -334,7 +362,19 @@ int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, 
     if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
     if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
     for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, params, static_cast<float*>(workspace), scores, desc_map, 1, static_cast<hipStream_t>(hip_stream)));
+    HIPCHK(launch_sp_encode(image, batch, h, w, nullptr, params, static_cast<float*>(workspace), scores, desc_map, 1, static_cast<hipStream_t>(hip_stream)));
+    return LG_OK;
+}
+
+int lg_sp_encode_ragged(const float* image, int32_t batch, int32_t hc, int32_t wc, const int32_t* sizes, const float* const* params, void* workspace,
+                        int64_t workspace_bytes, float* scores, float* desc_map, int32_t split, void* hip_stream) {
+    if (batch < 1 || hc < 8 || wc < 8) return set_error(LG_ERR_INVALID, "canvas height / width must be at least 8");
+    // as lg_sp_encode_split: 32-bit element offsets inside one image, whose strides are the canvas's
+    if (split && (int64_t)hc * wc * 64 >= (int64_t)1 << 31) return set_error(LG_ERR_INVALID, "split-f16 conv stack: the canvas hc * wc must stay below 2^25 pixels (use conv_precision = fp32 for larger ones)");
+    if (!image || !sizes || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
+    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, hc, wc)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes of the canvas)");
+    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
+    HIPCHK(launch_sp_encode(image, batch, hc, wc, sizes, params, static_cast<float*>(workspace), scores, desc_map, split ? 1 : 0, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
 }
 

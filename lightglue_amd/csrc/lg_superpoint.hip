@@ -26,7 +26,14 @@ struct SpArgs {
     float* out;                // [B][N][256]
     int B, h, w, N, s, normalize_dense;
     int out_f16;               // != 0: `out` holds binary16 rows (lg_sp_sample_descriptors_half): the fp32 result rounded once, to nearest even, on store
+    const int* sizes;          // ragged batch (else null): [B][2] image (w, h); h, w above are then the CANVAS map (strides), the map of image b its top-left (h_b / s) x (w_b / s) corner
 };
+
+// rows / columns of image b's descriptor map: the grid normalisation and every bound (clamped into the canvas; h x w when the batch is uniform)
+__device__ __forceinline__ void sp_map_extent(const SpArgs& a, int b, int& h, int& w) {
+    h = a.h; w = a.w;
+    if (a.sizes) { h = min(max(a.sizes[2 * b + 1] / a.s, 1), a.h); w = min(max(a.sizes[2 * b] / a.s, 1), a.w); }
+}
 
 constexpr int SPC = 256;   // descriptor_dim of SuperPoint (ref superpoint.py:107)
 constexpr int SPT = 32;    // locations per workgroup tile (32 x 257 floats of LDS)
@@ -36,10 +43,14 @@ __global__ __launch_bounds__(256) void sp_dense_kernel(SpArgs a) {
     __shared__ float part[8][SPT];
     const int b = blockIdx.y, loc0 = blockIdx.x * SPT, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hw = a.h * a.w, l = lane & 31, half = lane >> 5, loc = loc0 + l;
+    int hi, wi;
+    sp_map_extent(a, b, hi, wi);
+    auto live = [&](int p) { return p < hw && (!a.sizes || (p / a.w < hi && p % a.w < wi)); };     // the canvas outside an image is neither read nor written
+    const bool in = live(loc);
     const float* src = a.desc_map + (long long)b * SPC * hw;
     float ss = 0.f;
     for (int c = wave * 2 + half; c < SPC; c += 8) {     // half-wave reads 32 consecutive locations (128 B) of one channel
-        const float v = loc < hw ? src[(long long)c * hw + loc] : 0.f;
+        const float v = in ? src[(long long)c * hw + loc] : 0.f;
         tile[l][c] = v;
         ss += v * v;
     }
@@ -48,6 +59,7 @@ __global__ __launch_bounds__(256) void sp_dense_kernel(SpArgs a) {
     float* dst = a.nhwc + ((long long)b * hw + loc0) * SPC;
     for (int r = wave; r < SPT; r += 4) {                // wave writes one location = 1 KB contiguous
         if (loc0 + r >= hw) break;
+        if (!live(loc0 + r)) continue;
         float inv = 1.f;
         if (a.normalize_dense) {                         // F.normalize: x / max(||x||_2, 1e-12)
             float q = 0.f;
@@ -73,11 +85,13 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(SpArgs a) {
     if (i >= n) { store(f32x4{0.f, 0.f, 0.f, 0.f}); return; }   // padding row of a ragged batch
     const float* kp = a.keypoints + ((long long)b * a.N + i) * 2;
     const float s = (float)a.s;
+    int hi, wi;
+    sp_map_extent(a, b, hi, wi);
     // ref :83-90: (k - s/2 + 0.5) / (w*s - s/2 - 0.5) in [0,1], *2-1, then align_corners=True un-normalisation
     // ((g + 1) / 2 * (w - 1)), evaluated in the reference's order
-    const float gx = (kp[0] - s / 2.f + 0.5f) / ((float)a.w * s - s / 2.f - 0.5f) * 2.f - 1.f;
-    const float gy = (kp[1] - s / 2.f + 0.5f) / ((float)a.h * s - s / 2.f - 0.5f) * 2.f - 1.f;
-    const float ix = (gx + 1.f) / 2.f * (float)(a.w - 1), iy = (gy + 1.f) / 2.f * (float)(a.h - 1);
+    const float gx = (kp[0] - s / 2.f + 0.5f) / ((float)wi * s - s / 2.f - 0.5f) * 2.f - 1.f;
+    const float gy = (kp[1] - s / 2.f + 0.5f) / ((float)hi * s - s / 2.f - 0.5f) * 2.f - 1.f;
+    const float ix = (gx + 1.f) / 2.f * (float)(wi - 1), iy = (gy + 1.f) / 2.f * (float)(hi - 1);
     const float fx = floorf(ix), fy = floorf(iy);
     const int x0 = (int)fx, y0 = (int)fy;
     const float tx = ix - fx, ty = iy - fy;
@@ -87,7 +101,7 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(SpArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int x = x0 + (k & 1), y = y0 + (k >> 1);
-        if (x >= 0 && x < a.w && y >= 0 && y < a.h) {    // padding_mode="zeros"
+        if (x >= 0 && x < wi && y >= 0 && y < hi) {      // padding_mode="zeros"
             const f32x4 v = *reinterpret_cast<const f32x4*>(map + ((long long)y * a.w + x) * SPC);
 #pragma unroll
             for (int c = 0; c < 4; ++c) acc[c] += v[c] * wgt[k];
@@ -158,23 +172,33 @@ extern "C" {
 // lg_sp_sample_descriptors / lg_sp_sample_descriptors_half: one path, the element type of `out` decided at the last kernel's store
 static int sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
                                  const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, void* out, bool out_f16,
-                                 void* hip_stream) {
+                                 const int32_t* sizes, void* hip_stream) {
     if (channels != 256) return set_error(LG_ERR_INVALID, "descriptor map must have 256 channels");
     if (batch < 1 || h < 1 || w < 1 || n < 0 || cell < 1) return set_error(LG_ERR_INVALID, "bad descriptor map / keypoint sizes");
     if (!desc_map || !workspace || (n && (!keypoints || !out))) return set_error(LG_ERR_INVALID, "null pointer");
-    SpArgs a{desc_map, workspace, keypoints, num, static_cast<float*>(out), batch, h, w, n, cell, normalize_dense ? 1 : 0, out_f16 ? 1 : 0};
+    SpArgs a{desc_map, workspace, keypoints, num, static_cast<float*>(out), batch, h, w, n, cell, normalize_dense ? 1 : 0, out_f16 ? 1 : 0, sizes};
     HIPCHK(launch_sp_sample(a, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
 }
 int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
                              const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out,
                              void* hip_stream) {
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, hip_stream);
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, nullptr, hip_stream);
 }
 int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
                                  const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, uint16_t* out,
                                  void* hip_stream) {
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, hip_stream);
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, nullptr, hip_stream);
+}
+int lg_sp_sample_descriptors_ragged(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, const float* keypoints,
+                                    const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out, void* hip_stream) {
+    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, sizes, hip_stream);
+}
+int lg_sp_sample_descriptors_ragged_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, const float* keypoints,
+                                         const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream) {
+    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
+    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, sizes, hip_stream);
 }
 
 int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t max_candidates) {
@@ -182,9 +206,10 @@ int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_
     return (int64_t)detect_layout(batch, h, w, max_candidates, max_candidates, false).total;
 }
 
-int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32_t nms_radius, int32_t remove_borders,
-                 float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
-                 int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
+// lg_sp_detect / lg_sp_detect_ragged: one path; sizes (null: every map fills h x w) are the score maps' (w, h) inside the h x w canvas
+static int sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
+                     float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
+                     int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
     if (batch < 1 || h < 1 || w < 1 || h >= 32768 || w >= 32768) return set_error(LG_ERR_INVALID, "bad score map size");
     if (nms_radius < 0 || nms_radius > 4) return set_error(LG_ERR_INVALID, "nms_radius must be in [0, 4]");
     if (max_keypoints > SP_TOPK_MAX) return set_error(LG_ERR_INVALID, "max_keypoints above 4096");
@@ -198,9 +223,26 @@ int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32
     d.S = scores; d.B = batch; d.H = h; d.W = w; d.radius = nms_radius;
     d.border = remove_borders; d.image_size = nullptr; d.border_value = -1.f; d.threshold = detection_threshold;
     d.max_candidates = max_candidates; d.K = max_keypoints; d.sort_always = 0; d.sel_cap = max_candidates;
+    d.sizes = sizes;
     a.capacity = capacity; a.keypoints = keypoints; a.kp_scores = kp_scores; a.counts = counts; a.totals = totals;
     HIPCHK(launch_sp_detect(a, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
+}
+
+int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32_t nms_radius, int32_t remove_borders,
+                 float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
+                 int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
+    return sp_detect(scores, batch, h, w, nullptr, nms_radius, remove_borders, detection_threshold, max_keypoints, capacity, max_candidates, workspace, workspace_bytes,
+                     keypoints, kp_scores, counts, totals, hip_stream);
+}
+
+int lg_sp_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
+                        float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
+                        int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
+    if (h < 8 || w < 8) return set_error(LG_ERR_INVALID, "score canvas height / width must be at least 8");
+    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
+    return sp_detect(scores, batch, h, w, sizes, nms_radius, remove_borders, detection_threshold, max_keypoints, capacity, max_candidates, workspace, workspace_bytes,
+                     keypoints, kp_scores, counts, totals, hip_stream);
 }
 
 }  // extern "C"

@@ -5,12 +5,15 @@ released `superpoint_v1.pth` loads with `load_state_dict` unchanged, and the sam
 (`:147-232`).  Everything runs in `lightglue_amd/csrc/`: the conv stack as exact-fp32 MFMA implicit GEMMs
 (`lg_sp_encoder.hip`, `lg_sp_encode`), keypoint extraction (`lg_sp_detect`: NMS, borders, threshold, top-k) and the
 descriptor head (`lg_sp_sample_descriptors`).  No CPU fallback.  `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`,
-`lg_preprocess.hip`) and maps the keypoints back like the reference's `Extractor.extract`; image FILE I/O (cv2) stays out of scope."""
+`lg_preprocess.hip`) and maps the keypoints back like the reference's `Extractor.extract`; image FILE I/O (cv2) stays out of scope.
+
+Images of DIFFERENT sizes run in one ragged batch: a canvas with image b in its top-left corner plus `valid_size` (`forward`, `encode`; the `*_ragged` entry points),
+every image's result bit-identical to the B = 1 call on its crop; `extract_batch` builds the feature store of a mixed photo set that way (`plan_image_batches`)."""
 from __future__ import annotations
 
 import ctypes as C
 from types import SimpleNamespace
-from typing import Optional
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -18,7 +21,43 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
-from .superpoint_head import check_descriptor_dtype, descriptor_head, detect_keypoints
+from .superpoint_head import _detect, _run as _descriptor_run, check_descriptor_dtype, check_sizes, sizes_on_device
+
+def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8, max_workspace_bytes: Optional[int] = None,
+                       order: str = "size") -> List[Tuple[List[int], Tuple[int, int]]]:
+    """Group images of sizes `sizes_hw[i] = (h_i, w_i)` into ragged batches for `SuperPoint.extract_batch`: a list of `(indices, (Hc, Wc))`
+    that covers every index exactly once, with at most `batch_size` indices per group and the group's canvas = the elementwise maximum of
+    its sizes.  Pure host arithmetic and deterministic.  `order="size"` (default) walks the images sorted by (h, w) descending, ties by index,
+    so that equal and similar sizes share a canvas and little of it is padding; `order="input"` keeps the given order.  A group is closed when
+    it is full or when the next image would push the conv stack's workspace, `lg_sp_encode_workspace_bytes(n, Hc, Wc)`, above
+    `max_workspace_bytes`; a single image that alone exceeds the cap raises ValueError."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    if order not in ("size", "input"):
+        raise ValueError("order must be 'size' or 'input'")
+    sizes = [(int(h), int(w)) for h, w in sizes_hw]
+    for i, (h, w) in enumerate(sizes):
+        if h < 8 or w < 8:
+            raise ValueError(f"image {i} is {h} x {w}: SuperPoint needs at least 8 x 8")
+    nbytes = _cabi.load().lg_sp_encode_workspace_bytes if max_workspace_bytes is not None else None
+    todo = sorted(range(len(sizes)), key=lambda i: (-sizes[i][0], -sizes[i][1], i)) if order == "size" else list(range(len(sizes)))
+    groups: List[Tuple[List[int], Tuple[int, int]]] = []
+    cur: List[int] = []
+    hc = wc = 0
+    for i in todo:
+        h, w = sizes[i]
+        if nbytes is not None and nbytes(1, h, w) > max_workspace_bytes:
+            raise ValueError(f"image {i} ({h} x {w}) alone needs {nbytes(1, h, w)} bytes of conv workspace, above max_workspace_bytes = {max_workspace_bytes}")
+        nh, nw = max(hc, h), max(wc, w)
+        if cur and (len(cur) == batch_size or (nbytes is not None and nbytes(len(cur) + 1, nh, nw) > max_workspace_bytes)):
+            groups.append((cur, (hc, wc)))
+            cur, nh, nw = [], h, w
+        cur.append(i)
+        hc, wc = nh, nw
+    if cur:
+        groups.append((cur, (hc, wc)))
+    return groups
+
 
 _LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
 
@@ -81,10 +120,19 @@ class SuperPoint(nn.Module):
 
     # ------------------------------------------------------------------ conv stack
     @torch.no_grad()
-    def encode(self, image: torch.Tensor):
+    def encode(self, image: torch.Tensor, valid_size=None):
         """image [B, 1, H, W] (or [B, 3, H, W]: converted like kornia's rgb_to_grayscale, ref :155-156) ->
         (scores [B, H // 8 * 8, W // 8 * 8], dense raw descriptors [B, 256, H // 8, W // 8]) — ref :159-184 and :213-214.  Any
-        H, W >= 8: the three 2 x 2 max-pools floor like the reference's nn.MaxPool2d, so the score map is cropped to whole 8 x 8 cells."""
+        H, W >= 8: the three 2 x 2 max-pools floor like the reference's nn.MaxPool2d, so the score map is cropped to whole 8 x 8 cells.
+
+        `valid_size` (ragged batch): `[B, 2]` `(w, h)`, integers with 8 <= size <= canvas — `image` is then a canvas and image b its top-left
+        h_b x w_b corner.  Nothing outside an image is read (the padding may hold anything); inside `(h_b // 8 * 8, w_b // 8 * 8)` the scores and inside
+        `(h_b // 8, w_b // 8)` the descriptors are bit-identical to the call on the crop; scores outside are 0, descriptors outside unspecified."""
+        sizes = None if valid_size is None else check_sizes(valid_size, image.shape[0], image.shape[-2:], 8, "valid_size")
+        return self._encode(image, sizes)
+
+    def _encode(self, image: torch.Tensor, sizes):
+        """encode with `sizes` = None, validated host rows (check_sizes) or the int32 device array made from them"""
         if image.device.type != "cuda":
             raise RuntimeError("lightglue_amd.SuperPoint runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
                                f"Got an image on {image.device}.")
@@ -103,10 +151,17 @@ class SuperPoint(nn.Module):
         work = torch.empty((nbytes,), device=device, dtype=torch.uint8)
         scores = torch.empty((bsz, h // 8 * 8, w // 8 * 8), device=device, dtype=torch.float32)
         dense = torch.empty((bsz, 256, h // 8, w // 8), device=device, dtype=torch.float32)
+        if sizes is not None and not torch.is_tensor(sizes):
+            sizes = sizes_on_device(sizes, device)
+        split = self.conf.conv_precision == "f16x3"
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            encode = lib.lg_sp_encode_split if self.conf.conv_precision == "f16x3" else lib.lg_sp_encode
-            _cabi.check(encode(image.data_ptr(), bsz, h, w, arr, work.data_ptr(), nbytes, scores.data_ptr(), dense.data_ptr(), C.c_void_p(stream)))
+            if sizes is None:
+                encode = lib.lg_sp_encode_split if split else lib.lg_sp_encode
+                _cabi.check(encode(image.data_ptr(), bsz, h, w, arr, work.data_ptr(), nbytes, scores.data_ptr(), dense.data_ptr(), C.c_void_p(stream)))
+            else:
+                _cabi.check(lib.lg_sp_encode_ragged(image.data_ptr(), bsz, h, w, sizes.data_ptr(), arr, work.data_ptr(), nbytes, scores.data_ptr(),
+                                                    dense.data_ptr(), int(split), C.c_void_p(stream)))
         return scores, dense
 
     # ------------------------------------------------------------------ the reference's forward
@@ -114,18 +169,29 @@ class SuperPoint(nn.Module):
     def forward(self, data: dict) -> dict:
         """ref :147-232.  Returns keypoints [B, N, 2] (x, y), keypoint_scores [B, N], descriptors [B, N, 256] (conf.descriptor_dtype) and — extension for
         ragged batches — num_keypoints [B] (rows beyond an image's count are padding; with max_num_keypoints and enough
-        detections every image has exactly that many, as the reference's torch.stack requires)."""
+        detections every image has exactly that many, as the reference's torch.stack requires).
+
+        Optional `data["valid_size"]` (`[B, 2]` `(w, h)`, integers; validated on the host, ValueError names the offending image): a ragged batch of images
+        of DIFFERENT sizes, image b in the top-left h_b x w_b corner of the canvas `data["image"]`.  Rows < num_keypoints[b] are then bit-identical to the
+        B = 1 call on that crop, keypoints in the image's own frame; absent, the path is exactly the uniform one."""
         for key in self.required_data_keys:
             assert key in data, f"Missing key {key} in data"
         c = self.conf
-        scores, dense = self.encode(data["image"])
-        kpts, kscores, counts = detect_keypoints(scores, c.nms_radius, c.remove_borders, c.detection_threshold, c.max_num_keypoints)
+        image = data["image"]
+        img_sizes = score_sizes = None
+        if data.get("valid_size") is not None:
+            rows = check_sizes(data["valid_size"], image.shape[0], image.shape[-2:], 8, "valid_size")
+            if image.device.type == "cuda":      # (a CPU image raises in _encode)
+                both = sizes_on_device(rows + [[w // 8 * 8, h // 8 * 8] for w, h in rows], image.device)      # one upload: the images, then their score maps
+                img_sizes, score_sizes = both[: len(rows)], both[len(rows):]
+        scores, dense = self._encode(image, img_sizes)
+        kpts, kscores, counts = _detect(scores, c.nms_radius, c.remove_borders, c.detection_threshold, c.max_num_keypoints, None, score_sizes)
         nmax = int(counts.max().item()) if counts.numel() else 0
         kpts, kscores = kpts[:, :nmax].contiguous(), kscores[:, :nmax].contiguous()
         if bool((counts < nmax).any()):   # ragged batch: rows beyond an image's count are padding — zero them (descriptor_head does the same)
             live = torch.arange(nmax, device=counts.device)[None, :] < counts[:, None]
             kpts = kpts * live[..., None]; kscores = kscores * live
-        desc = descriptor_head(kpts, dense, 8, counts, dtype=c.descriptor_dtype)
+        desc = _descriptor_run(kpts, dense, 8, True, counts, c.descriptor_dtype, img_sizes)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}   # counts: consumed by LightGlue.forward
 
     preprocess_conf = {"resize": None}   # NOT the reference's 1024 (superpoint.py:115-117): see extract()
@@ -147,3 +213,67 @@ class SuperPoint(nn.Module):
             return extracted_to_image_frame(feats, (h, w), scales)
         feats["image_size"] = torch.tensor([[w, h]], dtype=torch.float32, device=img.device)
         return feats
+
+    @torch.no_grad()
+    def extract_batch(self, images: Sequence[torch.Tensor], batch_size: int = 8, order: str = "size", **conf) -> dict:
+        """`extract` for a set of images of DIFFERENT sizes at batched speed: the feature store `collate_features([self.extract(i, **conf) for i in images])`
+        would give, key for key and bit for bit — keypoints [K, N, 2] in each ORIGINAL image's pixel frame, keypoint_scores, descriptors
+        (conf.descriptor_dtype), num_keypoints [K], image_size [K, 2] = original (w, h); N = the largest count, padding rows zero — ready for
+        `LightGlue.match_pairs`.  `images`: [C, H_i, W_i] / [1, C, H_i, W_i] tensors, everything `extract` accepts.  Each is preprocessed with
+        `{**preprocess_conf, **conf}`, the results are grouped by `plan_image_batches` (at most `batch_size` per group), each group is written into the
+        top-left corners of one canvas and extracted in ONE ragged `forward` (`valid_size`).  `order`: the planner's — "size" puts like sizes together
+        (little padding), "input" batches the images as they come."""
+        images = list(images)
+        if not images:
+            raise ValueError("extract_batch needs at least one image")
+        prep = ImagePreprocessor(**{**self.preprocess_conf, **conf})
+        ready, scales, resized, original = [], [], [], []
+        for i, img in enumerate(images):
+            if img.dim() == 3:
+                img = img[None]
+            if img.dim() != 4 or img.shape[0] != 1:
+                raise ValueError(f"image {i} must be [C, H, W] or [1, C, H, W], got {tuple(img.shape)}")
+            if img.device.type != "cuda":
+                raise RuntimeError("lightglue_amd.SuperPoint runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
+                                   f"Got image {i} on {img.device}.")
+            h, w = img.shape[-2:]
+            out, scale = prep(img)
+            if out.shape[1] == 3:      # as encode does, per image: the canvas has one channel
+                out = 0.299 * out[:, 0:1] + 0.587 * out[:, 1:2] + 0.114 * out[:, 2:3]
+            if out.shape[1] != 1:
+                raise ValueError(f"image {i} must have 1 or 3 channels, got {out.shape[1]}")
+            ready.append(out.to(torch.float32)); scales.append(scale); original.append((h, w))
+            resized.append(tuple(out.shape[-2:]) != (h, w))      # extract maps keypoints back only then
+        device = ready[0].device
+        groups = plan_image_batches([tuple(t.shape[-2:]) for t in ready], batch_size, order=order)
+        return self._extract_groups(ready, scales, resized, original, groups, device)
+
+    def _extract_groups(self, ready, scales, resized, original, groups, device) -> dict:
+        """one ragged forward per group of preprocessed [1, 1, h, w] images; the collated store in the images' own order"""
+        parts = []
+        for idx, (hc, wc) in groups:
+            canvas = torch.zeros((len(idx), 1, hc, wc), device=device, dtype=torch.float32)
+            for r, i in enumerate(idx):
+                h, w = ready[i].shape[-2:]
+                canvas[r, :, :h, :w].copy_(ready[i][0])
+            feats = self.forward({"image": canvas, "valid_size": [[ready[i].shape[-1], ready[i].shape[-2]] for i in idx]})
+            kp, counts = feats["keypoints"], feats["num_keypoints"]
+            if any(resized[i] for i in idx):      # back to the original frame, (k + 0.5) / scale - 0.5 (extracted_to_image_frame), for the images that were resized
+                sc = torch.stack([scales[i] for i in idx]).to(kp.dtype)[:, None, :]
+                moved = (kp + 0.5) / sc - 0.5
+                kp = torch.where(torch.tensor([resized[i] for i in idx], device=device)[:, None, None], moved, kp)
+                kp = torch.where((torch.arange(kp.shape[1], device=device)[None, :] < counts[:, None])[..., None], kp, torch.zeros_like(kp))      # padding rows stay zero
+            parts.append((idx, kp, feats["keypoint_scores"], feats["descriptors"], counts))
+        k, nmax = len(ready), max(p[1].shape[1] for p in parts)
+        order = torch.tensor([i for p in parts for i in p[0]], device=device)
+        def gather(j, tail):
+            buf = parts[0][j].new_zeros((k, nmax) + tail)
+            for p in parts:
+                buf[torch.tensor(p[0], device=device), : p[j].shape[1]] = p[j]
+            return buf
+        out = {"keypoints": gather(1, (2,)), "descriptors": gather(3, (256,)), "keypoint_scores": gather(2, ())}
+        out["image_size"] = torch.tensor([[w, h] for h, w in original], dtype=torch.float32).to(device)
+        counts = torch.empty((k,), dtype=torch.int32, device=device)
+        counts[order] = torch.cat([p[4] for p in parts])
+        out["num_keypoints"] = counts
+        return out

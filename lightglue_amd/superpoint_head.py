@@ -20,8 +20,39 @@ def check_descriptor_dtype(dtype) -> torch.dtype:
     return dtype
 
 
+def check_sizes(sizes, batch: int, canvas_hw, minimum: int = 8, what: str = "valid_size") -> list:
+    """Host-side validation of the per-image extents of a ragged batch: `sizes` is `[batch, 2]` `(w, h)` — a tensor, an array or nested
+    sequences — integer-valued, with `minimum <= h <= canvas_hw[0]` and `minimum <= w <= canvas_hw[1]`.  Returns them as a list of
+    `[w, h]` Python ints; raises ValueError naming the first offending image.  (The kernels clamp what they are given into the canvas;
+    this is the check proper, made where the sizes are host integers.  A device tensor is copied to the host for it.)"""
+    t = torch.as_tensor(sizes).detach().cpu()
+    if t.dim() != 2 or tuple(t.shape) != (batch, 2):
+        raise ValueError(f"{what} must have shape [{batch}, 2] = (w, h) per image, got {tuple(t.shape)}")
+    if t.dtype == torch.bool or t.is_complex():
+        raise ValueError(f"{what} must hold integers, got {t.dtype}")
+    if t.is_floating_point():
+        bad = ((t != t.round()) | ~torch.isfinite(t)).any(dim=1).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise ValueError(f"{what}[{i}] = {t[i].tolist()} is not integer-valued")
+    rows = [[int(v) for v in row] for row in t.tolist()]
+    hc, wc = int(canvas_hw[0]), int(canvas_hw[1])
+    for i, (w, h) in enumerate(rows):
+        if w < minimum or h < minimum:
+            raise ValueError(f"{what}[{i}] = (w {w}, h {h}) is below the minimum of {minimum}")
+        if w > wc or h > hc:
+            raise ValueError(f"{what}[{i}] = (w {w}, h {h}) does not fit the canvas (w {wc}, h {hc})")
+    return rows
+
+
+def sizes_on_device(rows: list, device) -> torch.Tensor:
+    """int32 `[B, 2]` device array of validated `(w, h)` rows: the `sizes` argument of the `*_ragged` entry points"""
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 2).to(device)
+
+
 def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: bool,
-         num_keypoints: Optional[torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
+         num_keypoints: Optional[torch.Tensor], dtype: torch.dtype = torch.float32, sizes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sizes`: None, or the VALIDATED int32 device array `[B, 2]` of the images' `(w, h)` (`sizes_on_device(check_sizes(...))`): `dense` is then a canvas"""
     check_descriptor_dtype(dtype)
     if dense.device.type != "cuda":
         raise RuntimeError("lightglue_amd.superpoint_head runs on MI355X (ROCm device type 'cuda') only; there is no "
@@ -42,10 +73,16 @@ def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: 
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
         lib = _cabi.load()
-        sample = lib.lg_sp_sample_descriptors_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors
-        _cabi.check(sample(
-            ptr(dense), b, c, h, w, ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
-            C.c_void_p(stream)))
+        if sizes is None:
+            sample = lib.lg_sp_sample_descriptors_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors
+            _cabi.check(sample(
+                ptr(dense), b, c, h, w, ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
+                C.c_void_p(stream)))
+        else:
+            sample = lib.lg_sp_sample_descriptors_ragged_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors_ragged
+            _cabi.check(sample(
+                ptr(dense), b, c, h, w, sizes.data_ptr(), ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
+                C.c_void_p(stream)))
     return out
 
 
@@ -58,22 +95,39 @@ def sample_descriptors(keypoints: torch.Tensor, descriptors: torch.Tensor, s: in
 
 
 def descriptor_head(keypoints: torch.Tensor, dense_descriptors: torch.Tensor, s: int = 8,
-                    num_keypoints: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                    num_keypoints: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.float32, sizes=None) -> torch.Tensor:
     """Descriptor tail of SuperPoint.forward (superpoint.py:216-228) for a whole (ragged) batch: dense L2
     normalisation over channels, sampling at the keypoints, final normalisation, `[B, N, 256]` layout.
-    `dense_descriptors` is the raw `convDb` output `[B, 256, H/8, W/8]`; rows >= num_keypoints[b] come back zero.  `dtype` as for `sample_descriptors`."""
-    return _run(keypoints, dense_descriptors, s, True, num_keypoints, dtype)
+    `dense_descriptors` is the raw `convDb` output `[B, 256, H/8, W/8]`; rows >= num_keypoints[b] come back zero.  `dtype` as for `sample_descriptors`.
+    `sizes` (ragged batch): `[B, 2]` `(w, h)` of the IMAGES; `dense_descriptors` is then the canvas `SuperPoint.encode(image, valid_size)` returns and the map
+    of image b its top-left `(h_b // s, w_b // s)` corner, which alone is read: rows < num_keypoints[b] are bit-identical to the call on that crop."""
+    if sizes is not None:
+        h, w = dense_descriptors.shape[-2:]
+        sizes = sizes_on_device(check_sizes(sizes, dense_descriptors.shape[0], (h * s + s - 1, w * s + s - 1), s, "sizes"), dense_descriptors.device)
+    return _run(keypoints, dense_descriptors, s, True, num_keypoints, dtype, sizes)
 
 
 def detect_keypoints(scores: torch.Tensor, nms_radius: int = 4, remove_borders: int = 4, detection_threshold: float = 0.0005,
-                     max_num_keypoints: Optional[int] = None, capacity: Optional[int] = None):
+                     max_num_keypoints: Optional[int] = None, capacity: Optional[int] = None, sizes=None):
     """Keypoint extraction of SuperPoint.forward (superpoint.py:186-218) on the dense score map `scores [B, H, W]`
     (after softmax / depth-to-space, :176-184): simple_nms, border removal, threshold, optional top-k.
 
     Returns `(keypoints [B, C, 2] float (x, y), keypoint_scores [B, C], num_keypoints [B] int32)` — a ragged batch in
     the form `LightGlue.forward` / `descriptor_head` take (`num_keypoints`); rows >= num_keypoints[b] are undefined.
     C = `capacity` (default: max_num_keypoints, or 1/8 of the pixels when it is None).  Without top-k, raises if an
-    image has more detections than `capacity` rows (the internal candidate buffer always holds every pixel)."""
+    image has more detections than `capacity` rows (the internal candidate buffer always holds every pixel).
+
+    `sizes` (ragged batch): `[B, 2]` `(w, h)` of the SCORE maps; `scores` is then a canvas whose top-left `h_b x w_b` corner is the map of image b.
+    Whatever lies outside is never read — it is max_pool2d's -inf padding, and the far borders are the map's — so the result is exactly that of
+    the call on each crop, keypoints in the crop's own frame."""
+    if sizes is not None and scores.device.type == "cuda":
+        sizes = sizes_on_device(check_sizes(sizes, scores.shape[0], scores.shape[-2:], 1, "sizes"), scores.device)
+    return _detect(scores, nms_radius, remove_borders, detection_threshold, max_num_keypoints, capacity, sizes)
+
+
+def _detect(scores: torch.Tensor, nms_radius: int, remove_borders: int, detection_threshold: float, max_num_keypoints: Optional[int],
+            capacity: Optional[int], sizes: Optional[torch.Tensor]):
+    """detect_keypoints with `sizes` already validated and on the device (int32 `[B, 2]`), or None"""
     if scores.device.type != "cuda":
         raise RuntimeError("lightglue_amd.superpoint_head runs on MI355X (ROCm device type 'cuda') only; there is no "
                            f"CPU fallback. Got scores on {scores.device}.")
@@ -94,9 +148,12 @@ def detect_keypoints(scores: torch.Tensor, nms_radius: int = 4, remove_borders: 
     totals = torch.empty((b,), device=device, dtype=torch.int32)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        _cabi.check(lib.lg_sp_detect(scores.data_ptr(), b, h, w, int(nms_radius), int(remove_borders), float(detection_threshold), k, cap,
-                                     maxc, work.data_ptr(), nbytes, kpts.data_ptr(), kscores.data_ptr(), counts.data_ptr(),
-                                     totals.data_ptr(), C.c_void_p(stream)))
+        tail = (int(nms_radius), int(remove_borders), float(detection_threshold), k, cap, maxc, work.data_ptr(), nbytes, kpts.data_ptr(), kscores.data_ptr(),
+                counts.data_ptr(), totals.data_ptr(), C.c_void_p(stream))
+        if sizes is None:
+            _cabi.check(lib.lg_sp_detect(scores.data_ptr(), b, h, w, *tail))
+        else:
+            _cabi.check(lib.lg_sp_detect_ragged(scores.data_ptr(), b, h, w, sizes.data_ptr(), *tail))
     if k == 0:
         worst = int(totals.max().item())
         if worst > cap:
