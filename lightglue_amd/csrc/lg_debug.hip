@@ -89,7 +89,7 @@ int lg_engine_profile_read(lg_engine* e, double* ms, int64_t* count, int32_t n) 
     return LG_OK;
 }
 
-int lg_engine_debug_stop_after(lg_engine* e, int32_t step) { if (!e) return set_error(LG_ERR_INVALID, "null engine"); e->debug_stop = step; return LG_OK; }
+int lg_engine_debug_stop_after(lg_engine* e, int32_t step) { if (!e) return set_error(LG_ERR_INVALID, "null engine"); e->opt.debug_stop = step; return LG_OK; }
 
 /* What the matrix pipe SUSTAINS on this box: a dense v_mfma_f32_16x16x32_bf16 spin on every SIMD for ~25 ms (long enough for
  * the power management to settle).  tflops = achieved dense bf16 rate (the nominal 2.5 PFLOP/s assumes 2.4 GHz; under this load

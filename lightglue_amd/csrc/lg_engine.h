@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lightglue_amd.h"
+#include "lg_forward_plan.h"
 #include "lg_kernels.h"
 
 #define TRY(x) do { int _rc = (x); if (_rc != LG_OK) return _rc; } while (0)
@@ -64,13 +65,9 @@ struct lg_engine {
     float* Wr = nullptr;
     size_t tail_cat_layer_bytes = 0, tail_2_layer_bytes = 0;
     char* w_final_p = nullptr; size_t final_layer_bytes = 0;   // fragment-packed final projection weights (lg_proj.hip)
-    bool attn_dma = true;   // option "attn_dma": LDS-DMA attention kernel (16-bit operands, 32 rows per wave)
-    int attn_rows = 32;   // query rows per attention wave (32 | 64), option "attn_rows" / env LG_ATTN_ROWS
-    int fused_tail = 1, fused_next = 1, fused_prep = 1;   // fused_prep: the per-keypoint preparation inside the first projection launch (input_dim == 256)
-    int tail_timing = 0; long long* TAILDBG = nullptr; long long* TAILDBG2 = nullptr;
+    lg::ForwardOptions opt;   // lg_engine_set_option, lg_engine_debug_stop_after (lg_forward_plan.h)
+    long long* TAILDBG = nullptr; long long* TAILDBG2 = nullptr;   // shader-clock stamps of the kernel opt.tail_timing names
     int* CFLAGS = nullptr; int compact_epoch = 0; bool cflags_clean = false;   // compaction chunk flags [2B][cap / 128] + 1 error word (lg_adaptive.hip)
-    int tail_row_tiles = 0;   // option "tail_row_tiles": 16-row tiles per fused-tail workgroup; 0 = by grid fill (4 | 2 | 1)
-    bool attn_auto_rows = true;   // small grids: 16 query rows per attention wave (twice the workgroups); off once "attn_rows" is set
     // ---- workspace
     void* ws = nullptr; size_t ws_bytes = 0;
     int capB = 0, cap0 = 0, cap1 = 0;      // reserved
@@ -81,14 +78,8 @@ struct lg_engine {
     void *Q, *K, *VT;
     int *IND, *DST, *LEN, *LEN_ORIG, *LEN_OLD, *ACTIVE, *FINAL_LAYER, *ARG0, *ARG1;
     int* RANGEF = nullptr;   // [B] range-guard flags (LG_FLAG_CHECK_FINITE), zeroed by init_state_kernel
-    // gather path of the adaptive width (round 6, option "adapt_gather", default on): a second set of residual / rotary buffers — the SelfBlock projection behind
-    // a pruning step reads rows from one set and writes the compacted rows to the other (lg_proj.hip proj_rows_kernel<GatherRows>) —, and which set each pair's rows are in
+    // gather path of the adaptive width (option "adapt_gather"): the second set of residual / rotary buffers, and which set each pair's rows are in
     float *X2 = nullptr, *COS2 = nullptr, *SIN2 = nullptr; int* XSEL = nullptr;
-    bool adapt_gather = true;
-    // split-f16 precision: the final projection stores f16 hi / lo planes and the similarity matrix is sim_planes_kernel (lg_sim.hip); 0 = fp32 rows + the generic sim_kernel (bit-identical)
-    bool sim_planes = true;
-    int sim_chunk = 0;      // image-1 rows per sim_planes workgroup, 0 = by grid fill (option "sim_chunk": tests / A-B; bit-identical)
-    int debug_stop = -1;
     // ---- per-kernel-class HIP-event timing (bench.py roofline leg)
     bool profiling = false, prof_open = false;
     int prof_only = -1;                // kernel class to time alone, -1 = every class

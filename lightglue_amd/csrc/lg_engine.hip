@@ -123,17 +123,17 @@ int lg_engine_reserve(lg_engine* e, int32_t max_batch, int32_t max_n0, int32_t m
 
 int lg_engine_set_option(lg_engine* e, const char* key, int32_t value) {
     if (!e || !key) return set_error(LG_ERR_INVALID, "null argument");
-    if (std::strcmp(key, "fused_tail") == 0) { e->fused_tail = value != 0; return LG_OK; }
-    if (std::strcmp(key, "fused_next") == 0) { e->fused_next = value != 0; return LG_OK; }
-    if (std::strcmp(key, "fused_prep") == 0) { e->fused_prep = value != 0; return LG_OK; }
-    if (std::strcmp(key, "attn_dma") == 0) { e->attn_dma = value != 0; return LG_OK; }
-    if (std::strcmp(key, "adapt_gather") == 0) { e->adapt_gather = value != 0; return LG_OK; }
-    if (std::strcmp(key, "sim_planes") == 0) { e->sim_planes = value != 0; return LG_OK; }
-    if (std::strcmp(key, "sim_chunk") == 0) { if (value < 0 || value % 64) return set_error(LG_ERR_INVALID, "sim_chunk: 0 or a multiple of 64"); e->sim_chunk = value; return LG_OK; }
-    if (std::strcmp(key, "attn_rows") == 0) { if (value != 16 && value != 32 && value != 64) return set_error(LG_ERR_INVALID, "attn_rows must be 16, 32 or 64"); e->attn_rows = value; e->attn_auto_rows = false; return LG_OK; }
-    if (std::strcmp(key, "tail_row_tiles") == 0) { if (value != 0 && value != 1 && value != 2 && value != 4) return set_error(LG_ERR_INVALID, "tail_row_tiles must be 0 (automatic), 1, 2 or 4"); e->tail_row_tiles = value; return LG_OK; }
+    if (std::strcmp(key, "fused_tail") == 0) { e->opt.fused_tail = value != 0; return LG_OK; }
+    if (std::strcmp(key, "fused_next") == 0) { e->opt.fused_next = value != 0; return LG_OK; }
+    if (std::strcmp(key, "fused_prep") == 0) { e->opt.fused_prep = value != 0; return LG_OK; }
+    if (std::strcmp(key, "attn_dma") == 0) { e->opt.attn_dma = value != 0; return LG_OK; }
+    if (std::strcmp(key, "adapt_gather") == 0) { e->opt.adapt_gather = value != 0; return LG_OK; }
+    if (std::strcmp(key, "sim_planes") == 0) { e->opt.sim_planes = value != 0; return LG_OK; }
+    if (std::strcmp(key, "sim_chunk") == 0) { if (value < 0 || value % 64) return set_error(LG_ERR_INVALID, "sim_chunk: 0 or a multiple of 64"); e->opt.sim_chunk = value; return LG_OK; }
+    if (std::strcmp(key, "attn_rows") == 0) { if (value != 16 && value != 32 && value != 64) return set_error(LG_ERR_INVALID, "attn_rows must be 16, 32 or 64"); e->opt.attn_rows = value; e->opt.attn_auto_rows = false; return LG_OK; }
+    if (std::strcmp(key, "tail_row_tiles") == 0) { if (value != 0 && value != 1 && value != 2 && value != 4) return set_error(LG_ERR_INVALID, "tail_row_tiles must be 0 (automatic), 1, 2 or 4"); e->opt.tail_row_tiles = value; return LG_OK; }
     if (std::strcmp(key, "profile_only") == 0) { e->prof_only = value; return LG_OK; }   // kernel class index, -1 = all classes
-    if (std::strcmp(key, "tail_timing") == 0) { e->tail_timing = value; return LG_OK; }   // 1: tail kernel, 2: self projection, 3: self attention (LG_ATTN_TIMING builds), 4: assign sweeps, 5 / 6: layer 0's CrossBlock / SelfBlock tail WITH its fused next projection (stamps of the projection in TAILDBG2)
+    if (std::strcmp(key, "tail_timing") == 0) { e->opt.tail_timing = value; return LG_OK; }   // which kernel leaves shader-clock stamps: ForwardOptions::tail_timing
     return set_error(LG_ERR_INVALID, std::string("unknown option '") + key + "'");
 }
 
@@ -151,12 +151,9 @@ int tail_row_tiles_for(int R) {
     return best;
 }
 
-bool pruning_on(const lg_engine* e, const lg_forward_io* io) { return e->cfg.width_confidence > 0 && !(io->flags & LG_FLAG_NO_PRUNING); }
-// LG_FLAG_INDEXED: the index fields sit behind the round-5 extension, so they are read only when both flags are set (check_forward_io refuses one without the other)
-bool indexed(const lg_forward_io* io) { return (io->flags & LG_FLAG_EXT) && (io->flags & LG_FLAG_INDEXED); }
 // bit `side` set: desc0 / desc1 hold binary16 rows (LG_FLAG_DESC0_F16 / _DESC1_F16; check_forward_io refuses them without LG_FLAG_EXT)
 int desc_f16_sides(const lg_forward_io* io) { return ((io->flags & LG_FLAG_DESC0_F16) ? 1 : 0) | ((io->flags & LG_FLAG_DESC1_F16) ? 2 : 0); }
-PairIndex pair_index(const lg_forward_io* io) { return indexed(io) ? PairIndex{io->index0, io->index1, io->images0, io->images1} : PairIndex{}; }
+PairIndex pair_index(const lg_forward_io* io) { return indexed(io->flags) ? PairIndex{io->index0, io->index1, io->images0, io->images1} : PairIndex{}; }
 
 int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if (!e || !io) return set_error(LG_ERR_INVALID, "null argument");
@@ -175,7 +172,7 @@ int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if ((n0 && (!io->matches0 || !io->scores0)) || (n1 && (!io->matches1 || !io->scores1))) return set_error(LG_ERR_INVALID, "null output pointer");
     if (n0 && n1 && (!io->matches || !io->match_scores)) return set_error(LG_ERR_INVALID, "null match-list pointer");
     if (n0 && n1 && (!io->kpts0 || !io->kpts1 || !io->desc0 || !io->desc1)) return set_error(LG_ERR_INVALID, "null input pointer");
-    const bool do_prune = pruning_on(e, io);
+    const bool do_prune = pruning_on(e->cfg, io->flags);
     if (do_prune && ((n0 && !io->prune0) || (n1 && !io->prune1))) return set_error(LG_ERR_INVALID, "prune0/prune1 required when width_confidence > 0");
     if (e->cfg.add_scale_ori && (!io->scales0 || !io->oris0 || !io->scales1 || !io->oris1)) return set_error(LG_ERR_INVALID, "scales/oris required");
     const bool ext = (io->flags & LG_FLAG_EXT) != 0;            // round-5 extension fields present
@@ -201,7 +198,7 @@ hipError_t write_outputs(const lg_engine* e, const lg_forward_io* io, const int*
     if (io->flags & LG_FLAG_EXT) {
         o.m0_64 = (long long*)io->matches0_i64; o.m1_64 = (long long*)io->matches1_i64; o.matches_64 = (long long*)io->matches_i64; o.stop_64 = (long long*)io->stop_i64;
         o.prune0_64 = (long long*)io->prune0_i64; o.prune1_64 = (long long*)io->prune1_i64; o.prune0_f = io->prune0_f32; o.prune1_f = io->prune1_f32;
-        o.wire = io->wire; o.wire_stride = io->wire_stride; o.wire_prune = pruning_on(e, io) ? 1 : 0; o.status = io->status; o.range_flag = range_flag; o.device_err = device_err;
+        o.wire = io->wire; o.wire_stride = io->wire_stride; o.wire_prune = pruning_on(e->cfg, io->flags) ? 1 : 0; o.status = io->status; o.range_flag = range_flag; o.device_err = device_err;
         o.px = pair_index(io);
     }
     return launch_write_outputs(o, s);
@@ -215,258 +212,290 @@ int forward_empty(const lg_engine* e, const lg_forward_io* io, hipStream_t s) {
     HIPCHK(hipMemsetAsync(io->n_matches, 0, sizeof(int) * (size_t)B, s));
     InitStateArgs is{};   // the prune counters alone
     is.B = B; is.n0 = n0; is.n1 = n1; is.L = e->cfg.n_layers; is.px = pair_index(io);
-    if (pruning_on(e, io)) { is.prune0 = n0 ? io->prune0 : nullptr; is.prune1 = n1 ? io->prune1 : nullptr; }
+    if (pruning_on(e->cfg, io->flags)) { is.prune0 = n0 ? io->prune0 : nullptr; is.prune1 = n1 ? io->prune1 : nullptr; }
     HIPCHK(launch_init_state(is, s));
     HIPCHK(write_outputs(e, io, nullptr, 1, nullptr, nullptr, s));   // stop = 1 for every pair (+ the extension outputs of an empty result)
     return LG_OK;
 }
+
+// ---- one forward: lg_engine_forward plans it (plan_forward, lg_forward_plan.h) and runs the plan in three stages — forward_prepare, forward_layers,
+// forward_assign.  The stages read the plan and decide nothing; what they share is the ForwardCtx.
+
+struct ForwardCtx {
+    hipStream_t s;
+    RowSpace rs_all, rs_act;   // every pair / the pairs still active
+    int R;                     // rows of the carved workspace: B * (cap0 + cap1)
+    int* range_flag;           // LG_FLAG_CHECK_FINITE: RANGEF, else nullptr
+    int* device_err;           // error word + compaction ticket behind the chunk flags (lg_adaptive.hip)
+    PrepArgs prep;             // the per-keypoint preparation: its own launch (forward_prepare), or inside the first projection launch (forward_layers)
+};
+
+#define PROFILED(cls, launch) do { TRY(prof_begin(e, cls, c.s)); HIPCHK(launch); TRY(prof_end(e, c.s)); } while (0)   // one launch inside its profile bracket
+
+ForwardCtx forward_ctx(const lg_engine* e, const lg_forward_io* io, const ForwardPlan& plan, hipStream_t s) {
+    const int B = io->batch, c0 = e->cur_cap0, c1 = e->cur_cap1;
+    ForwardCtx c{};
+    c.s = s; c.rs_all = RowSpace{B, c0, c1, e->LEN, nullptr}; c.rs_act = RowSpace{B, c0, c1, e->LEN, e->ACTIVE}; c.R = B * (c0 + c1);
+    c.range_flag = plan.check_finite ? e->RANGEF : nullptr;
+    c.device_err = e->CFLAGS + (size_t)2 * B * compact_chunks(c0, c1);
+    PrepArgs& p = c.prep;
+    p.rs = c.rs_all; p.n0 = io->n0; p.n1 = io->n1; p.px = pair_index(io); p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
+    p.scales0 = io->scales0; p.oris0 = io->oris0; p.scales1 = io->scales1; p.oris1 = io->oris1;
+    p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
+    p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim; p.desc_f16 = desc_f16_sides(io);
+    p.X = e->X; p.Xin = e->XIN; p.cosb = e->COS; p.sinb = e->SIN; p.ind = e->IND; p.bbox = e->BBOX;
+    return c;
+}
+
+// a set of residual / rotary buffers (BlockPlan::buf_set): 0 = X / COS / SIN, 1 = X2 / COS2 / SIN2
+struct BufSet { float *X, *cosb, *sinb; };
+BufSet buf_set(const lg_engine* e, int set) { return set ? BufSet{e->X2, e->COS2, e->SIN2} : BufSet{e->X, e->COS, e->SIN}; }
+
+// per-op GEMM out[R][Nout] = [A | A2] W^T + bias on the weights `w_elems` elements into the layer-major matrix W
+GemmArgs gemm_args(const lg_engine* e, const ForwardCtx& c, const RowSpace& rs, const float* A, int lda, const float* A2, int lda2, int K1, int K,
+                   const PackedW& W, size_t w_elems, const float* bias, int Nout, float* out) {
+    const int prec = e->cfg.precision;
+    GemmArgs g{};
+    g.rs = rs; g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = K1; g.K = K; g.bias = bias; g.Nout = Nout; g.out = out; g.ldo = Nout; g.out_scale = 1.f; g.R = c.R;
+    g.W = static_cast<char*>(W.hi) + w_elems * elem_size(prec); g.Wlo = W.lo ? static_cast<char*>(W.lo) + w_elems * elem_size(prec) : nullptr;
+    return g;
+}
+
+// q/k/v projection of block `blk` of `layer` on the rows of buffer set `set` (lg_proj.hip / fused into lg_tail.hip)
+ProjArgs proj_args(const lg_engine* e, const ForwardPlan& plan, const ForwardCtx& c, int layer, int blk, int set) {
+    const BufSet x = buf_set(e, set);
+    ProjArgs pj{};
+    pj.rs = c.rs_act; pj.X = x.X; pj.R = c.R; pj.q = e->Q; pj.k = e->K; pj.vt = e->VT; pj.plane = plan.split_qkv ? (long long)c.R * 256 : 0;
+    const BlockWeights& bw = e->blocks[blk];
+    pj.W = bw.qkv_p + (size_t)layer * bw.qkv_layer_bytes; pj.bias = bw.b_qkv + (size_t)layer * bw.Nout;
+    pj.Nout = bw.Nout; pj.n_qk_groups = bw.n_qk_groups;
+    if (blk == 0) { pj.cosb = x.cosb; pj.sinb = x.sinb; }   // rotary on q, k of the SelfBlock only
+    pj.dbg = nullptr; pj.range_flag = c.range_flag;
+    return pj;
+}
+
+// final projection (ref :289-291: / d**0.25), lg_proj.hip / fused into the last tail: of the active pairs at the last layer, or — per_pair — of every
+// pair with the weights of the layer it stopped at
+FinalArgs final_args(const lg_engine* e, const ForwardPlan& plan, const ForwardCtx& c, bool per_pair) {
+    const int layer = e->cfg.n_layers - 1;
+    FinalArgs f{};
+    f.rs = per_pair ? c.rs_all : c.rs_act; f.X = per_pair ? e->X : buf_set(e, plan.block(layer, 1).buf_set).X; f.R = c.R; f.out = e->MD; f.scale = 0.25f;
+    f.planes = plan.sim_planes ? 1 : 0;
+    if (per_pair) { f.X2 = e->X2; f.xsel = e->XSEL; }    // XSEL stays 0 unless a gather projection ran
+    f.W = e->w_final_p + (per_pair ? 0 : (size_t)layer * e->final_layer_bytes); f.bias = e->b_final + (per_pair ? 0 : (size_t)layer * 256);
+    f.layer_of_pair = per_pair ? e->FINAL_LAYER : nullptr; f.w_layer_bytes = (long long)e->final_layer_bytes;
+    return f;
+}
+
+// init_state, prep (or its bounding-box part when the first projection does the rest), input_proj (ref :521-522): debug step 0
+int forward_prepare(lg_engine* e, const lg_forward_io* io, const ForwardPlan& plan, const ForwardCtx& c, bool& stopped) {
+    const InitStateArgs is{io->batch, io->n0, io->n1, plan.n_layers, io->num0, io->num1, e->LEN, e->LEN_ORIG, e->LEN_OLD, e->ACTIVE, e->FINAL_LAYER,
+                           plan.do_prune ? io->prune0 : nullptr, plan.do_prune ? io->prune1 : nullptr, e->RANGEF, c.device_err, e->XSEL, pair_index(io)};
+    HIPCHK(launch_init_state(is, c.s));
+    TRY(prof_begin(e, PC_PREP, c.s));
+    if (plan.fuse_prep) HIPCHK(launch_prep_bbox(c.prep, c.s)); else HIPCHK(launch_prep(c.prep, c.s));
+    const int in = e->cfg.input_dim;
+    if (in != 256) {
+        GemmArgs g = gemm_args(e, c, c.rs_all, e->XIN, in, nullptr, 0, in, in, e->w_in, 0, e->b_in, 256, e->X);
+        HIPCHK(launch_gemm(e->cfg.precision, EPI_STORE, g, c.s));
+    }
+    TRY(prof_end(e, c.s));
+    stopped = plan.stops_at(0);
+    return LG_OK;
+}
+
+// the q/k/v of a block that the previous tail has not produced: one launch in the block's profile class
+int launch_block_proj(lg_engine* e, const ForwardPlan& plan, const ForwardCtx& c, int layer, int blk, const BlockPlan& b) {
+    const int prec = e->cfg.precision, ap = e->attn_prec;
+    ProjArgs pj = proj_args(e, plan, c, layer, blk, b.proj_by == ProjBy::OwnGather ? b.buf_set ^ 1 : b.buf_set);
+    pj.dbg = (e->opt.tail_timing == 2 && blk == 0) ? e->TAILDBG : nullptr;
+    TRY(prof_begin(e, blk == 0 ? PC_GEMM_QKV_SELF : PC_GEMM_QKV_CROSS, c.s));
+    if (b.proj_by == ProjBy::OwnFirst) {
+        pj.rs = c.rs_all;                                 // rs_all: what prep covers (pairs with an empty image too)
+        if (launch_proj_first(prec, ap, pj, c.prep, c.s) != hipSuccess) {
+            //  e.g. the 80 KB of dynamic LDS refused: the separate preparation kernel + the standard projection instead — bit-identical
+            (void)hipGetLastError();
+            HIPCHK(launch_prep(c.prep, c.s));
+            pj.rs = c.rs_act;
+            HIPCHK(launch_proj(prec, ap, pj, c.s));
+        }
+    }
+    else if (b.proj_by == ProjBy::OwnGather) {
+        // the rows of every pair that prunes move to the other buffer set on their way into the projection; pairs that do not prune at this
+        // layer are copied as they are (identity map): one buffer set is current for the whole batch
+        const BufSet from = buf_set(e, b.buf_set ^ 1), to = buf_set(e, b.buf_set);
+        GatherArgs ga{};
+        ga.Xold = from.X; ga.cos_old = from.cosb; ga.sin_old = from.sinb; ga.Xnew = to.X; ga.cos_new = to.cosb; ga.sin_new = to.sinb;
+        ga.src = e->DST; ga.len_old = e->LEN_OLD;
+        HIPCHK(launch_proj_gather(prec, ap, pj, ga, c.s));
+    }
+    else HIPCHK(launch_proj(prec, ap, pj, c.s));
+    TRY(prof_end(e, c.s));
+    return LG_OK;
+}
+
+// out_proj + ffn.0 + LayerNorm + GELU + ffn.3 + residual of a block in one kernel (lg_tail.hip), with what the plan appends to it
+int launch_block_tail(lg_engine* e, const ForwardPlan& plan, const ForwardCtx& c, int i, int blk, const BlockPlan& b) {
+    const BlockWeights& bw = e->blocks[blk];
+    const int D = 256, timing = e->opt.tail_timing;
+    TailArgs ta{};
+    ta.rs = c.rs_act; ta.X = buf_set(e, b.buf_set).X; ta.CTX = e->CTX; ta.range_flag = c.range_flag;
+    ta.Wcat = bw.tail_cat + (size_t)i * e->tail_cat_layer_bytes; ta.bcat = bw.b_cat + (size_t)i * 512;
+    ta.gamma = bw.ln_g + (size_t)i * 512; ta.beta = bw.ln_b + (size_t)i * 512;
+    ta.W2 = bw.tail_2 + (size_t)i * e->tail_2_layer_bytes; ta.b2 = bw.b_f2 + (size_t)i * D;
+    // the 256 -> 1 heads of a CrossBlock tail (BlockPlan): token confidence in head 0 when wanted, matchability in the first free head
+    if (b.want_tok) { ta.head_w0 = e->w_tok + (size_t)i * D; ta.head_b0 = e->b_tok + i; ta.head_out0 = e->CONF; }
+    if (b.prune_here || b.want_ls) {
+        float* sig = b.prune_here ? e->MSCORE : nullptr; float* ls = b.want_ls ? e->LS : nullptr;
+        float* lsneg = b.want_lsneg ? e->LSNEG : nullptr;
+        if (b.want_tok) { ta.head_w1 = e->w_match + (size_t)i * D; ta.head_b1 = e->b_match + i; ta.head_out1 = sig; ta.head_ls1 = ls; ta.head_lsneg1 = lsneg; }
+        else { ta.head_w0 = e->w_match + (size_t)i * D; ta.head_b0 = e->b_match + i; ta.head_out0 = sig; ta.head_ls0 = ls; ta.head_lsneg0 = lsneg; }
+    }
+    ta.dbg = (timing == 1 || (i == 0 && ((timing == 5 && blk == 1) || (timing == 6 && blk == 0)))) ? e->TAILDBG : nullptr;
+    ta.row_tiles = e->opt.tail_row_tiles ? e->opt.tail_row_tiles : tail_row_tiles_for(c.R);
+    if (b.tail_next == TailNext::NextProj) {
+        ta.next = proj_args(e, plan, c, i + blk, blk ^ 1, b.buf_set);   // this layer's CrossBlock, or the next layer's SelfBlock
+        if (ta.dbg && timing >= 5) ta.next.dbg = e->TAILDBG2;
+    } else if (b.tail_next == TailNext::FinalProj) ta.fin = final_args(e, plan, c, false);
+    PROFILED(PC_TAIL, launch_tail(e->cfg.precision, e->attn_prec, ta, c.s));
+    return LG_OK;
+}
+
+// the adaptive step behind layer `i` (ref :544-566, lg_adaptive.hip): early stop and / or point pruning, in place or leaving the row move to the next projection
+int launch_adaptive_step(lg_engine* e, const lg_forward_io* io, const ForwardPlan& plan, const ForwardCtx& c, int i, AdaptMode mode) {
+    const int B = io->batch, c0 = e->cur_cap0, c1 = e->cur_cap1, D = 256;
+    const bool do_stop = plan.do_stop, prune_now = prunes(mode);
+    if (!plan.fused_tail) {   // per-op path: the 256 -> 1 heads as their own pass (the fused CrossBlock tail computes them in its epilogue)
+        RowDotArgs rd{};
+        rd.rs = c.rs_act; rd.X = e->X;
+        if (do_stop) { rd.w0 = e->w_tok + (size_t)i * D; rd.b0 = e->b_tok + i; rd.out0 = e->CONF; rd.act0 = 1; }
+        if (do_stop && prune_now) { rd.w1 = e->w_match + (size_t)i * D; rd.b1 = e->b_match + i; rd.out1 = e->MSCORE; rd.act1 = 1; }
+        else if (prune_now) { rd.w0 = e->w_match + (size_t)i * D; rd.b0 = e->b_match + i; rd.out0 = e->MSCORE; rd.act0 = 1; }
+        PROFILED(PC_ROWDOT, launch_rowdot(rd, c.s));
+    }
+    AdaptArgs ad{};
+    ad.rs = c.rs_act; ad.len = e->LEN; ad.active = e->ACTIVE; ad.len_old = e->LEN_OLD; ad.final_layer = e->FINAL_LAYER;
+    ad.ind = e->IND; ad.dst = e->DST; ad.prune0 = io->prune0; ad.prune1 = io->prune1; ad.n0 = io->n0; ad.n1 = io->n1; ad.len_orig = e->LEN_ORIG;
+    ad.conf = e->CONF; ad.mscore = e->MSCORE; ad.X = e->X; ad.cosb = e->COS; ad.sinb = e->SIN;
+    if (mode == AdaptMode::PruneGather) { ad.gather = 1; ad.src = e->DST; ad.xsel = e->XSEL; ad.xnext = plan.block(i + 1, 0).buf_set; }
+    ad.layer = i;
+    // ref :631-634 threshold (float32 buffer), :656 and :640 compare in float32
+    ad.conf_thr = (float)std::fmin(std::fmax(0.8 + 0.1 * std::exp(-4.0 * i / plan.n_layers), 0.0), 1.0);
+    ad.depth_conf = (float)e->cfg.depth_confidence;
+    ad.width_conf = (float)(1.0 - e->cfg.width_confidence);
+    ad.pruning_min_kpts = e->cfg.pruning_min_kpts;
+    ad.do_stop = do_stop; ad.do_prune = prune_now;
+    ad.compact_chunks = compact_chunks(c0, c1); ad.compact_flags = e->CFLAGS; ad.compact_err = c.device_err; ad.compact_ticket = c.device_err + 1;
+    if (prune_now && !e->cflags_clean) {   // fresh carve: whatever the arena held there must not look like an epoch
+        HIPCHK(hipMemsetAsync(e->CFLAGS, 0, cflags_bytes(B, c0, c1), c.s));
+        e->cflags_clean = true;
+    }
+    ad.compact_epoch = ++e->compact_epoch;
+    PROFILED(PC_ADAPTIVE, launch_adapt(ad, c.s));
+    return LG_OK;
+}
+
+// the transformer (ref :541-566): per layer a SelfBlock and a CrossBlock — projection, attention, tail — and the adaptive step behind every layer but the last
+int forward_layers(lg_engine* e, const lg_forward_io* io, const ForwardPlan& plan, const ForwardCtx& c, bool& stopped) {
+    const int prec = e->cfg.precision, D = 256;
+    stopped = true;   // until the last block is through
+    for (int i = 0; i < plan.n_layers; ++i) {
+        for (int blk = 0; blk < 2; ++blk) {
+            const BlockPlan b = plan.block(i, blk);
+            const BlockWeights& bw = e->blocks[blk];
+            int step = b.first_step;
+            if (b.proj_by != ProjBy::PrevTail) TRY(launch_block_proj(e, plan, c, i, blk, b));
+            if (plan.stops_at(step++)) return LG_OK;
+            {
+                AttnArgs at{};
+                at.rs = c.rs_act; at.q = e->Q; at.k = e->K; at.vt = e->VT; at.plane = plan.split_qkv ? (long long)c.R * 256 : 0; at.ctx = e->CTX; at.R = c.R; at.cross = blk;
+                at.dbg = (e->opt.tail_timing == 3 && blk == 0) ? e->TAILDBG : nullptr;
+                at.rows_per_wave = (e->opt.attn_auto_rows && c.R / 128 * 4 < 256) ? 16 : e->opt.attn_rows; at.dma = e->opt.attn_dma ? 1 : 0;   // fewer 128-row workgroups than CUs: 64-row ones
+                PROFILED(blk == 0 ? PC_ATTN_SELF : PC_ATTN_CROSS, launch_attention(e->attn_prec, at, c.s));
+            }
+            if (plan.stops_at(step++)) return LG_OK;
+            if (plan.fused_tail) {
+                TRY(launch_block_tail(e, plan, c, i, blk, b));
+                if (plan.stops_at(step + 3)) return LG_OK;   // the fused tail completes the block's last four steps at once
+                continue;
+            }
+            {
+                GemmArgs g = gemm_args(e, c, c.rs_act, e->CTX, D, nullptr, 0, D, D, bw.out, (size_t)i * D * D, bw.b_out + (size_t)i * D, D, e->MSG);
+                PROFILED(PC_GEMM_OUT, launch_gemm(prec, EPI_STORE, g, c.s));
+            }
+            if (plan.stops_at(step++)) return LG_OK;
+            {
+                GemmArgs g = gemm_args(e, c, c.rs_act, e->X, D, e->MSG, D, D, 512, bw.f1, (size_t)i * 512 * 512, bw.b_f1 + (size_t)i * 512, 512, e->H1);
+                PROFILED(PC_GEMM_FFN1, launch_gemm(prec, EPI_STORE, g, c.s));
+            }
+            if (plan.stops_at(step++)) return LG_OK;
+            {
+                LnGeluArgs ln{c.rs_act, e->H1, e->G, bw.ln_g + (size_t)i * 512, bw.ln_b + (size_t)i * 512, c.R};
+                PROFILED(PC_LN_GELU, launch_ln_gelu(ln, c.s));
+            }
+            if (plan.stops_at(step++)) return LG_OK;
+            {
+                GemmArgs g = gemm_args(e, c, c.rs_act, e->G, 512, nullptr, 0, 512, 512, bw.f2, (size_t)i * D * 512, bw.b_f2 + (size_t)i * D, D, e->X);
+                PROFILED(PC_GEMM_FFN2, launch_gemm(prec, EPI_RESID, g, c.s));
+            }
+            if (plan.stops_at(step++)) return LG_OK;
+        }
+        const AdaptMode mode = plan.after_layer(i);
+        if (mode != AdaptMode::None) TRY(launch_adaptive_step(e, io, plan, c, i, mode));
+    }
+    stopped = false;
+    return LG_OK;
+}
+
+// log assignment with the weights of the layer each pair stopped at (ref :591): matchability terms, final projection, similarity, assignment, outputs
+int forward_assign(lg_engine* e, const lg_forward_io* io, const ForwardPlan& plan, const ForwardCtx& c) {
+    const int prec = e->cfg.precision, n0 = io->n0, n1 = io->n1, D = 256;
+    if (!plan.fused_tail) {   // per-op path: matchability terms as their own pass (the fused CrossBlock tails emit them from their heads)
+        RowDotArgs rd{};
+        rd.rs = c.rs_all; rd.X = e->X; rd.w0 = e->w_match; rd.b0 = e->b_match; rd.out0 = e->LS; rd.act0 = 2;
+        rd.layer_of_pair = e->FINAL_LAYER; rd.w_layer_stride = D; rd.ignore_active = 1;
+        if (plan.wants_log_assignment) { rd.w1 = e->w_match; rd.b1 = e->b_match; rd.out1 = e->LSNEG; rd.act1 = 3; }  // dustbin terms
+        PROFILED(PC_ROWDOT, launch_rowdot(rd, c.s));
+    }
+    if (!plan.final_proj_in_last_tail()) PROFILED(PC_GEMM_FINAL, launch_final_proj(prec, final_args(e, plan, c, true), c.s));
+    TRY(prof_begin(e, PC_SIM, c.s));
+    if (plan.sim_planes) {
+        SimPlanesArgs sp{c.rs_all, reinterpret_cast<const f16_t*>(e->MD), (long long)c.R * 256, D, e->SIM, e->opt.sim_chunk};
+        HIPCHK(launch_sim_planes(sp, c.s));
+    } else {
+        SimArgs sm{c.rs_all, e->MD, D, D, e->SIM};
+        HIPCHK(launch_sim(prec, sm, c.s));
+    }
+    TRY(prof_end(e, c.s));
+    AssignArgs as{};
+    as.rs = c.rs_all; as.sim = e->SIM; as.ls = e->LS; as.lse_r = e->LSE_R; as.lse_c = e->LSE_C; as.max0 = e->MAX0; as.arg0 = e->ARG0;
+    as.max1 = e->MAX1; as.arg1 = e->ARG1; as.cpm = e->CPM; as.cps = e->CPS; as.cbv = e->CBV; as.cbi = e->CBI; as.ind = e->IND; as.n0 = n0; as.n1 = n1; as.filter_threshold = (float)e->cfg.filter_threshold;
+    as.m0 = io->matches0; as.m1 = io->matches1; as.s0 = io->scores0; as.s1 = io->scores1;
+    as.matches = io->matches; as.mscores = io->match_scores; as.n_matches = io->n_matches; as.max_matches = n0 < n1 ? n0 : n1;
+    as.log_assignment = io->log_assignment; as.lsneg = e->LSNEG;
+    as.dbg = e->opt.tail_timing == 4 ? e->TAILDBG : nullptr;
+    as.all_rows_live = plan.all_rows_live ? 1 : 0;
+    PROFILED(PC_ASSIGN, launch_assign(as, c.s));
+    HIPCHK(write_outputs(e, io, e->FINAL_LAYER, 0, c.range_flag, c.device_err, c.s));
+    return LG_OK;
+}
+#undef PROFILED
 }  // namespace
 
 int lg_engine_forward(lg_engine* e, const lg_forward_io* io, void* hip_stream) {
     TRY(check_forward_io(e, io));
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int B = io->batch, n0 = io->n0, n1 = io->n1, L = e->cfg.n_layers, D = 256;
-    if (n0 == 0 || n1 == 0) return forward_empty(e, io, s);
-    const bool do_stop = e->cfg.depth_confidence > 0, do_prune = pruning_on(e, io);
-    const bool check_finite = (io->flags & LG_FLAG_EXT) && (io->flags & LG_FLAG_CHECK_FINITE);
-    const int max_matches = n0 < n1 ? n0 : n1;
-
-    TRY(ensure_workspace(e, B, n0, n1));
-    const int c0 = e->cur_cap0, c1 = e->cur_cap1, R = B * (c0 + c1);
-    RowSpace rs_all{B, c0, c1, e->LEN, nullptr};
-    RowSpace rs_act{B, c0, c1, e->LEN, e->ACTIVE};
-    const int prec = e->cfg.precision, ap = e->attn_prec;
-    int step = 0;
-#define STEP_DONE() do { if (e->debug_stop >= 0 && step >= e->debug_stop) return LG_OK; ++step; } while (0)
-#define PROFILED(cls, launch) do { TRY(prof_begin(e, cls, s)); HIPCHK(launch); TRY(prof_end(e, s)); } while (0)   // one launch inside its profile bracket
-
-    int* const device_err = e->CFLAGS + (size_t)2 * B * compact_chunks(c0, c1);   // error word + compaction ticket behind the chunk flags (lg_adaptive.hip)
-    const InitStateArgs is{B, n0, n1, L, io->num0, io->num1, e->LEN, e->LEN_ORIG, e->LEN_OLD, e->ACTIVE, e->FINAL_LAYER,
-                           do_prune ? io->prune0 : nullptr, do_prune ? io->prune1 : nullptr, e->RANGEF, device_err, e->XSEL, pair_index(io)};
-    HIPCHK(launch_init_state(is, s));
-    int* const range_flag = check_finite ? e->RANGEF : nullptr;
-    // prep (+ descriptor copy) as its own launch, or — input_dim == 256, no debug stop — inside the first projection launch (lg_proj.hip proj_rows_kernel<FirstRows>)
-    const bool fuse_prep = e->fused_prep && e->cfg.input_dim == D && e->debug_stop < 0 && e->tail_timing != 2;
-    PrepArgs p{};
-    p.rs = rs_all; p.n0 = n0; p.n1 = n1; p.px = pair_index(io); p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
-    p.scales0 = io->scales0; p.oris0 = io->oris0; p.scales1 = io->scales1; p.oris1 = io->oris1;
-    p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
-    p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim; p.desc_f16 = desc_f16_sides(io);
-    p.X = e->X; p.Xin = e->XIN; p.cosb = e->COS; p.sinb = e->SIN; p.ind = e->IND; p.bbox = e->BBOX;
-    TRY(prof_begin(e, PC_PREP, s));
-    if (fuse_prep) HIPCHK(launch_prep_bbox(p, s)); else HIPCHK(launch_prep(p, s));
-    // per-op GEMM out[R][Nout] = [A | A2] W^T + bias on the weights `w_elems` elements into the layer-major matrix W
-    auto gemm = [&](const RowSpace& rs, const float* A, int lda, const float* A2, int lda2, int K1, int K, const PackedW& W, size_t w_elems, const float* bias, int Nout, float* out) {
-        GemmArgs g{};
-        g.rs = rs; g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = K1; g.K = K; g.bias = bias; g.Nout = Nout; g.out = out; g.ldo = Nout; g.out_scale = 1.f; g.R = R;
-        g.W = static_cast<char*>(W.hi) + w_elems * elem_size(prec); g.Wlo = W.lo ? static_cast<char*>(W.lo) + w_elems * elem_size(prec) : nullptr;
-        return g;
-    };
-    if (e->cfg.input_dim != D) {  // ref :521-522
-        GemmArgs g = gemm(rs_all, e->XIN, e->cfg.input_dim, nullptr, 0, e->cfg.input_dim, e->cfg.input_dim, e->w_in, 0, e->b_in, D, e->X);
-        HIPCHK(launch_gemm(prec, EPI_STORE, g, s));
-    }
-    TRY(prof_end(e, s));
-    STEP_DONE();
-    const long long qkv_plane = ap == PREC_F16X3 ? (long long)R * 256 : 0;   // split attention: hi plane, then lo plane, of q / k / v^T
-
-    // current set of residual / rotary buffers: set 0 = X / COS / SIN, set 1 = X2 / COS2 / SIN2; flipped by every gather projection (adaptive width)
-    int xcur = 0;
-    float* Xs[2] = {e->X, e->X2}; float* Cs[2] = {e->COS, e->COS2}; float* Ss[2] = {e->SIN, e->SIN2};
-    bool gather_pending = false;   // the decide step of the previous layer ran in gather mode: the next SelfBlock projection moves the rows
-    auto make_proj = [&](int layer, int blk) {   // q/k/v projection of block `blk` of `layer` (lg_proj.hip / fused into lg_tail.hip)
-        ProjArgs pj{};
-        pj.rs = rs_act; pj.X = Xs[xcur]; pj.R = R; pj.q = e->Q; pj.k = e->K; pj.vt = e->VT; pj.plane = qkv_plane;
-        const BlockWeights& bw = e->blocks[blk];
-        pj.W = bw.qkv_p + (size_t)layer * bw.qkv_layer_bytes; pj.bias = bw.b_qkv + (size_t)layer * bw.Nout;
-        pj.Nout = bw.Nout; pj.n_qk_groups = bw.n_qk_groups;
-        if (blk == 0) { pj.cosb = Cs[xcur]; pj.sinb = Ss[xcur]; }   // rotary on q, k of the SelfBlock only
-        pj.dbg = nullptr; pj.range_flag = range_flag;
-        return pj;
-    };
-    // fused_next: a tail kernel also runs the NEXT block's projection on the x tile it has just produced.  Across a
-    // layer boundary that is only valid when nothing re-orders rows in between (no early stop / pruning step).
-    const bool fuse_next = e->fused_next && e->fused_tail && (e->tail_timing == 0 || e->tail_timing == 5 || e->tail_timing == 6) &&
-                           e->debug_stop < 0 && launch_tail_supports_next(prec, ap);
-    const bool prune_possible = do_prune && (n0 > e->cfg.pruning_min_kpts || n1 > e->cfg.pruning_min_kpts);
-    // gather path: the product configuration only (the per-op / debug-stop paths keep the in-place compaction kernel, which the tests compare it with)
-    const bool use_gather = e->adapt_gather && e->fused_tail && e->debug_stop < 0 && e->tail_timing == 0;
-    bool proj_done = false, final_done = false;
-    auto make_final = [&](const RowSpace& rs, int layer, bool per_pair) {   // final projection (ref :289-291: / d**0.25), lg_proj.hip / fused into the last tail
-        FinalArgs f{};
-        f.rs = rs; f.X = per_pair ? e->X : Xs[xcur]; f.R = R; f.out = e->MD; f.scale = 0.25f;
-        f.planes = (prec == PREC_F16X3 && e->sim_planes) ? 1 : 0;
-        if (per_pair) { f.X2 = e->X2; f.xsel = e->XSEL; }    // XSEL stays 0 unless a gather projection ran
-        f.W = e->w_final_p + (per_pair ? 0 : (size_t)layer * e->final_layer_bytes); f.bias = e->b_final + (per_pair ? 0 : (size_t)layer * D);
-        f.layer_of_pair = per_pair ? e->FINAL_LAYER : nullptr; f.w_layer_bytes = (long long)e->final_layer_bytes;
-        return f;
-    };
-    for (int i = 0; i < L; ++i) {
-        for (int blk = 0; blk < 2; ++blk) {  // 0 = SelfBlock (ref :159-172), 1 = CrossBlock (ref :201-230)
-            const BlockWeights& bw = e->blocks[blk];
-            if (!proj_done) {   // otherwise the previous block's tail kernel has already produced q/k/v (fused_next)
-                ProjArgs pj = make_proj(i, blk);
-                pj.dbg = (e->tail_timing == 2 && blk == 0) ? e->TAILDBG : nullptr;
-                TRY(prof_begin(e, blk == 0 ? PC_GEMM_QKV_SELF : PC_GEMM_QKV_CROSS, s));
-                if (fuse_prep && i == 0 && blk == 0) {
-                    pj.rs = rs_all;                                 // rs_all: what prep covers (pairs with an empty image too)
-                    if (launch_proj_first(prec, ap, pj, p, s) != hipSuccess) {
-                        //  e.g. the 80 KB of dynamic LDS refused: the separate preparation kernel + the standard projection instead — bit-identical
-                        (void)hipGetLastError();
-                        HIPCHK(launch_prep(p, s));
-                        pj.rs = rs_act;
-                        HIPCHK(launch_proj(prec, ap, pj, s));
-                    }
-                }
-                else if (gather_pending && blk == 0) {
-                    // the rows of every pair that prunes move to the other buffer set on their way into the projection; pairs that do not prune at this
-                    // layer are copied as they are (identity map): one buffer set is current for the whole batch
-                    GatherArgs ga{};
-                    ga.Xold = Xs[xcur]; ga.cos_old = Cs[xcur]; ga.sin_old = Ss[xcur]; ga.Xnew = Xs[xcur ^ 1]; ga.cos_new = Cs[xcur ^ 1]; ga.sin_new = Ss[xcur ^ 1];
-                    ga.src = e->DST; ga.len_old = e->LEN_OLD;
-                    HIPCHK(launch_proj_gather(prec, ap, pj, ga, s));
-                    xcur ^= 1; gather_pending = false;
-                }
-                else HIPCHK(launch_proj(prec, ap, pj, s));
-                TRY(prof_end(e, s));
-            }
-            proj_done = false;
-            STEP_DONE();
-            {
-                AttnArgs at{};
-                at.rs = rs_act; at.q = e->Q; at.k = e->K; at.vt = e->VT; at.plane = qkv_plane; at.ctx = e->CTX; at.R = R; at.cross = blk;
-                at.dbg = (e->tail_timing == 3 && blk == 0) ? e->TAILDBG : nullptr;
-                at.rows_per_wave = (e->attn_auto_rows && R / 128 * 4 < 256) ? 16 : e->attn_rows; at.dma = e->attn_dma ? 1 : 0;   // fewer 128-row workgroups than CUs: 64-row ones
-                PROFILED(blk == 0 ? PC_ATTN_SELF : PC_ATTN_CROSS, launch_attention(ap, at, s));
-            }
-            STEP_DONE();
-            if (e->fused_tail) {   // out_proj + ffn.0 + LayerNorm + GELU + ffn.3 + residual in one kernel (lg_tail.hip)
-                TailArgs ta{};
-                ta.rs = rs_act; ta.X = Xs[xcur]; ta.CTX = e->CTX; ta.range_flag = range_flag;
-                ta.Wcat = bw.tail_cat + (size_t)i * e->tail_cat_layer_bytes; ta.bcat = bw.b_cat + (size_t)i * 512;
-                ta.gamma = bw.ln_g + (size_t)i * 512; ta.beta = bw.ln_b + (size_t)i * 512;
-                ta.W2 = bw.tail_2 + (size_t)i * e->tail_2_layer_bytes; ta.b2 = bw.b_f2 + (size_t)i * D;
-                if (blk == 1) {   // 256 -> 1 heads on the rows this CrossBlock tail produces
-                    // token confidence of layer i (ref :548) for the stop decision; matchability of layer i (ref :298-299): its sigmoid for
-                    // the pruning mask (ref :553) and its log-sigmoids as the assignment's matchability terms (ref :268-276) wherever a pair
-                    // may END at this layer — the last one, or any one with early stopping
-                    const bool last = i + 1 == L;
-                    const bool prune_here = !last && do_prune && prune_possible;
-                    const bool want_tok = !last && do_stop, want_ls = last || do_stop;
-                    if (want_tok) { ta.head_w0 = e->w_tok + (size_t)i * D; ta.head_b0 = e->b_tok + i; ta.head_out0 = e->CONF; }
-                    if (prune_here || want_ls) {
-                        float* sig = prune_here ? e->MSCORE : nullptr; float* ls = want_ls ? e->LS : nullptr;
-                        float* lsneg = (want_ls && io->log_assignment) ? e->LSNEG : nullptr;
-                        if (want_tok) { ta.head_w1 = e->w_match + (size_t)i * D; ta.head_b1 = e->b_match + i; ta.head_out1 = sig; ta.head_ls1 = ls; ta.head_lsneg1 = lsneg; }
-                        else { ta.head_w0 = e->w_match + (size_t)i * D; ta.head_b0 = e->b_match + i; ta.head_out0 = sig; ta.head_ls0 = ls; ta.head_lsneg0 = lsneg; }
-                    }
-                }
-                ta.dbg = (e->tail_timing == 1 || (i == 0 && ((e->tail_timing == 5 && blk == 1) || (e->tail_timing == 6 && blk == 0)))) ? e->TAILDBG : nullptr;
-                ta.row_tiles = e->tail_row_tiles ? e->tail_row_tiles : tail_row_tiles_for(R);
-                // Across a layer boundary the fusion is valid whenever no row can MOVE in between: early stop alone only
-                // deactivates a pair (its speculative projection is never read), pruning re-orders rows — but it cannot
-                // happen while every segment is at or below the pruning threshold (ref :551 / :559; lengths only shrink).
-                if (fuse_next && (blk == 0 || (i + 1 < L && !prune_possible))) {
-                    ta.next = make_proj(i + blk, blk ^ 1);   // this layer's CrossBlock, or the next layer's SelfBlock
-                    if (ta.dbg && e->tail_timing >= 5) ta.next.dbg = e->TAILDBG2;
-                    proj_done = true;
-                } else if (fuse_next && blk == 1 && i + 1 == L && !do_stop) {
-                    // fixed depth: every live pair ends here, so the LAST tail also runs the final projection of the log assignment on its x tile
-                    ta.fin = make_final(rs_act, L - 1, false);
-                    final_done = true;
-                }
-                PROFILED(PC_TAIL, launch_tail(prec, ap, ta, s));
-                STEP_DONE(); STEP_DONE(); STEP_DONE(); STEP_DONE();
-                continue;
-            }
-            {
-                GemmArgs g = gemm(rs_act, e->CTX, D, nullptr, 0, D, D, bw.out, (size_t)i * D * D, bw.b_out + (size_t)i * D, D, e->MSG);
-                PROFILED(PC_GEMM_OUT, launch_gemm(prec, EPI_STORE, g, s));
-            }
-            STEP_DONE();
-            {
-                GemmArgs g = gemm(rs_act, e->X, D, e->MSG, D, D, 512, bw.f1, (size_t)i * 512 * 512, bw.b_f1 + (size_t)i * 512, 512, e->H1);
-                PROFILED(PC_GEMM_FFN1, launch_gemm(prec, EPI_STORE, g, s));
-            }
-            STEP_DONE();
-            {
-                LnGeluArgs ln{rs_act, e->H1, e->G, bw.ln_g + (size_t)i * 512, bw.ln_b + (size_t)i * 512, R};
-                PROFILED(PC_LN_GELU, launch_ln_gelu(ln, s));
-            }
-            STEP_DONE();
-            {
-                GemmArgs g = gemm(rs_act, e->G, 512, nullptr, 0, 512, 512, bw.f2, (size_t)i * D * 512, bw.b_f2 + (size_t)i * D, D, e->X);
-                PROFILED(PC_GEMM_FFN2, launch_gemm(prec, EPI_RESID, g, s));
-            }
-            STEP_DONE();
-        }
-        if (i == L - 1) break;  // ref :544-545
-        const bool prune_now = do_prune && prune_possible;   // below the threshold the pruning branch is never taken (ref :551 / :559)
-        if (do_stop || prune_now) {
-            if (!e->fused_tail) {   // per-op path: the 256 -> 1 heads as their own pass (the fused CrossBlock tail computes them in its epilogue)
-                RowDotArgs rd{};
-                rd.rs = rs_act; rd.X = e->X;
-                if (do_stop) { rd.w0 = e->w_tok + (size_t)i * D; rd.b0 = e->b_tok + i; rd.out0 = e->CONF; rd.act0 = 1; }
-                if (do_stop && prune_now) { rd.w1 = e->w_match + (size_t)i * D; rd.b1 = e->b_match + i; rd.out1 = e->MSCORE; rd.act1 = 1; }
-                else if (prune_now) { rd.w0 = e->w_match + (size_t)i * D; rd.b0 = e->b_match + i; rd.out0 = e->MSCORE; rd.act0 = 1; }
-                PROFILED(PC_ROWDOT, launch_rowdot(rd, s));
-            }
-            AdaptArgs ad{};
-            ad.rs = rs_act; ad.len = e->LEN; ad.active = e->ACTIVE; ad.len_old = e->LEN_OLD; ad.final_layer = e->FINAL_LAYER;
-            ad.ind = e->IND; ad.dst = e->DST; ad.prune0 = io->prune0; ad.prune1 = io->prune1; ad.n0 = n0; ad.n1 = n1; ad.len_orig = e->LEN_ORIG;
-            ad.conf = e->CONF; ad.mscore = e->MSCORE; ad.X = e->X; ad.cosb = e->COS; ad.sinb = e->SIN;
-            if (use_gather && prune_now) { ad.gather = 1; ad.src = e->DST; ad.xsel = e->XSEL; ad.xnext = xcur ^ 1; gather_pending = true; }
-            ad.layer = i;
-            // ref :631-634 threshold (float32 buffer), :656 and :640 compare in float32
-            ad.conf_thr = (float)std::fmin(std::fmax(0.8 + 0.1 * std::exp(-4.0 * i / L), 0.0), 1.0);
-            ad.depth_conf = (float)e->cfg.depth_confidence;
-            ad.width_conf = (float)(1.0 - e->cfg.width_confidence);
-            ad.pruning_min_kpts = e->cfg.pruning_min_kpts;
-            ad.do_stop = do_stop; ad.do_prune = prune_now;
-            ad.compact_chunks = compact_chunks(c0, c1); ad.compact_flags = e->CFLAGS; ad.compact_err = device_err; ad.compact_ticket = device_err + 1;
-            if (prune_now && !e->cflags_clean) {   // fresh carve: whatever the arena held there must not look like an epoch
-                HIPCHK(hipMemsetAsync(e->CFLAGS, 0, cflags_bytes(B, c0, c1), s));
-                e->cflags_clean = true;
-            }
-            ad.compact_epoch = ++e->compact_epoch;
-            PROFILED(PC_ADAPTIVE, launch_adapt(ad, s));
-        }
-    }
-    // ---- log assignment with the weights of the layer each pair stopped at (ref :591)
-    {
-        if (!e->fused_tail) {   // per-op path: matchability terms as their own pass (the fused CrossBlock tails emit them from their heads)
-            RowDotArgs rd{};
-            rd.rs = rs_all; rd.X = e->X; rd.w0 = e->w_match; rd.b0 = e->b_match; rd.out0 = e->LS; rd.act0 = 2;
-            rd.layer_of_pair = e->FINAL_LAYER; rd.w_layer_stride = D; rd.ignore_active = 1;
-            if (io->log_assignment) { rd.w1 = e->w_match; rd.b1 = e->b_match; rd.out1 = e->LSNEG; rd.act1 = 3; }  // dustbin terms
-            PROFILED(PC_ROWDOT, launch_rowdot(rd, s));
-        }
-        if (!final_done) {
-            PROFILED(PC_GEMM_FINAL, launch_final_proj(prec, make_final(rs_all, 0, true), s));
-        }
-        TRY(prof_begin(e, PC_SIM, s));
-        if (prec == PREC_F16X3 && e->sim_planes) {
-            SimPlanesArgs sp{rs_all, reinterpret_cast<const f16_t*>(e->MD), (long long)R * 256, D, e->SIM, e->sim_chunk};
-            HIPCHK(launch_sim_planes(sp, s));
-        } else {
-            SimArgs sm{rs_all, e->MD, D, D, e->SIM};
-            HIPCHK(launch_sim(prec, sm, s));
-        }
-        TRY(prof_end(e, s));
-        AssignArgs as{};
-        as.rs = rs_all; as.sim = e->SIM; as.ls = e->LS; as.lse_r = e->LSE_R; as.lse_c = e->LSE_C; as.max0 = e->MAX0; as.arg0 = e->ARG0;
-        as.max1 = e->MAX1; as.arg1 = e->ARG1; as.cpm = e->CPM; as.cps = e->CPS; as.cbv = e->CBV; as.cbi = e->CBI; as.ind = e->IND; as.n0 = n0; as.n1 = n1; as.filter_threshold = (float)e->cfg.filter_threshold;
-        as.m0 = io->matches0; as.m1 = io->matches1; as.s0 = io->scores0; as.s1 = io->scores1;
-        as.matches = io->matches; as.mscores = io->match_scores; as.n_matches = io->n_matches; as.max_matches = max_matches;
-        as.log_assignment = io->log_assignment; as.lsneg = e->LSNEG;
-        as.dbg = e->tail_timing == 4 ? e->TAILDBG : nullptr;
-        as.all_rows_live = (!do_prune && !io->num0 && !io->num1 && !indexed(io)) ? 1 : 0;   // indexed: a pair whose index is out of range has no live row
-        PROFILED(PC_ASSIGN, launch_assign(as, s));
-        HIPCHK(write_outputs(e, io, e->FINAL_LAYER, 0, range_flag, device_err, s));
-    }
-#undef PROFILED
-#undef STEP_DONE
-    return LG_OK;
+    if (io->n0 == 0 || io->n1 == 0) return forward_empty(e, io, s);
+    TRY(ensure_workspace(e, io->batch, io->n0, io->n1));
+    const ForwardPlan plan = plan_forward(e->cfg, e->attn_prec, e->opt, io->n0, io->n1, io->flags, io->num0 || io->num1, io->log_assignment != nullptr,
+                                          launch_tail_supports_next(e->cfg.precision, e->attn_prec));
+    const ForwardCtx c = forward_ctx(e, io, plan, s);
+    bool stopped = false;   // lg_engine_debug_stop_after: the step asked for is done
+    TRY(forward_prepare(e, io, plan, c, stopped));
+    if (stopped) return LG_OK;
+    TRY(forward_layers(e, io, plan, c, stopped));
+    if (stopped) return LG_OK;
+    return forward_assign(e, io, plan, c);
 }
 
 }  // extern "C"
