@@ -1,0 +1,235 @@
+"""The mechanics of one matcher call, written once for `LightGlue.forward` and `LightGlue.match_pairs` (lightglue.py keeps the class: conf, weights, engine
+handle, the launch path and the public methods): what the engine reads of one side (`normalise_side`), how a pair list is cut into engine calls
+(`plan_pair_chunks`), the output set of a call (`Outputs`) and its assembly into the reference's dict (`ragged_outputs`, `DeferredMatches`).  Plain tensor and
+pointer arithmetic: nothing here launches a kernel of the engine's.
+"""
+from __future__ import annotations
+
+import functools
+
+import torch
+
+from . import _cabi
+
+
+def require_gpu(device, what: str = "keypoints") -> None:
+    """THE device check of the matcher (forward, match_pairs, InflightMatcher): a missing GPU is an error, never another path."""
+    if device.type != "cuda":
+        raise RuntimeError(f"lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. Got {what} on {device}.")
+
+
+def raise_on_status(status) -> None:
+    """Per-pair status codes (lg_forward_io.status, in the order of the call's pair list) -> LightGlueAmdError naming the pairs."""
+    bad = [(i, int(c)) for i, c in enumerate(status) if int(c) != _cabi.LG_OK]
+    if bad:
+        what = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
+                _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
+                _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched"}
+        raise _cabi.LightGlueAmdError("; ".join(f"pair {i}: {what.get(c, c)}" for i, c in bad[:8]))
+
+
+def ragged_outputs(host, mlist, mscores, stop):
+    """The part of the output assembly (ref :593-629) that needs the host, for `Outputs.finish` and `parallel.Pending.wait`: host = [[stop per pair],
+    [matches per pair], [status per pair]] -> (matches List[[S_i, 2]], scores List[[S_i]], stop: an int for one pair, else the tensor `stop`); raises on a status."""
+    raise_on_status(host[2])
+    counts = host[1]
+    matches = [row[:c] for row, c in zip(mlist.unbind(0), counts)]
+    scores = [row[:c] for row, c in zip(mscores.unbind(0), counts)]
+    return matches, scores, int(host[0][0]) if len(counts) == 1 else stop
+
+
+class DeferredMatches:
+    """Handle of a forward whose outputs are on their way (LightGlue.forward_deferred)."""
+
+    def __init__(self, done, host_sizes, assemble, buffers=()):
+        self._done, self._host, self._assemble, self._out = done, host_sizes, assemble, None
+        self.buffers = buffers     # the allocations every output tensor is a view of (InflightMatcher hands THEM to the consumer's stream: 3 - 4 record_stream calls, not one per output)
+
+    def result(self) -> dict:
+        if self._out is None:
+            self._done.synchronize()
+            self._out = self._assemble(self._host.tolist())
+            self._assemble = None
+        return self._out
+
+
+def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS, max_sim_elems: int = _cabi.LG_MAX_SIM_ELEMS) -> list:
+    """Cut a list of P pairs of n0 x n1 keypoints into the FEWEST contiguous chunks [(start, stop), ...] that each fit one engine call
+    (include/lightglue_amd.h: pairs * (cap0 + cap1) <= max_rows and pairs * cap0 * cap1 <= max_sim_elems, cap = n rounded up to 128).  Chunk sizes differ
+    by at most one, larger chunks first: the first chunk is the largest call, so the engine's workspace grows at most once.  Pure host arithmetic."""
+    P, n0, n1 = int(P), int(n0), int(n1)
+    if n0 > _cabi.LG_MAX_KEYPOINTS or n1 > _cabi.LG_MAX_KEYPOINTS:    # what lg_engine_forward answers (AssertionError through _cabi.check): no chunking helps
+        raise AssertionError("more than LG_MAX_KEYPOINTS (8192) keypoints in one image")
+    if P <= 0:
+        return []
+    c0, c1 = (n0 + 127) // 128 * 128, (n1 + 127) // 128 * 128
+    per_call = P
+    if c0 + c1:
+        per_call = min(per_call, int(max_rows) // (c0 + c1))
+    if c0 * c1:
+        per_call = min(per_call, int(max_sim_elems) // (c0 * c1))
+    if per_call < 1:
+        raise ValueError(f"one pair of {n0} x {n1} keypoints needs {c0 + c1} rows and {c0 * c1} similarity entries: "
+                         f"more than max_rows = {max_rows} / max_sim_elems = {max_sim_elems} allow")
+    chunks = -(-P // per_call)
+    size, larger = divmod(P, chunks)
+    out, start = [], 0
+    for i in range(chunks):
+        stop = start + size + (1 if i < larger else 0)
+        out.append((start, stop))
+        start = stop
+    return out
+
+
+# ---------------------------------------------------------------------- one side of a call
+def _engine_descriptors(t: torch.Tensor, device) -> tuple:
+    """Descriptors as the engine reads them -> (tensor, stored as float16).  A float16 tensor is read IN PLACE (the side's LG_FLAG_DESC*_F16: the engine widens
+    every value exactly where the descriptors enter it, so the forward is bit-identical to one on `t.float()`) — untouched when it is on the device, contiguous
+    and 16-byte aligned, otherwise through one float16 copy; every other dtype becomes contiguous fp32, as before."""
+    if t.dtype is torch.float16:
+        if t.device != device or not t.is_contiguous():
+            t = t.detach().to(device=device).contiguous()
+        if t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
+            t = t.clone()
+        return t, True
+    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+        return t, False
+    return t.detach().to(device=device, dtype=torch.float32).contiguous(), False
+
+
+class Side:
+    """K images of N keypoint rows as the engine reads them: contiguous fp32 / int32 tensors on the device (descriptors fp32 or float16), absent pieces None."""
+    __slots__ = ("K", "N", "kpts", "desc", "desc_f16", "size", "scales", "oris", "num")
+
+
+def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, what: str = "feats") -> Side:
+    """{keypoints [K, N, 2], descriptors [K, N, input_dim], image_size [K, 2] | [1, 2] | [2] (optional; broadcast as the reference does, ref :35-42),
+    scales / oris [K, N] iff add_scale_ori, num_keypoints [K] (optional; clamped into [0, N])} -> Side.  `forward` calls it for image0 / image1 (K = B) and
+    `match_pairs` for its feature stores, once per call.  Only data pointers are handed on, so every shape is checked here (AssertionError naming the key) and
+    tensors that already qualify pass through untouched: no copy, no kernel."""
+    def f32(t):
+        if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+            return t
+        return t.detach().to(device=device, dtype=torch.float32).contiguous()
+    kpts, desc = feats["keypoints"], feats["descriptors"]
+    assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
+    s = Side()
+    K, N = s.K, s.N = kpts.shape[0], kpts.shape[1]
+    assert tuple(desc.shape) == (K, N, input_dim), f"{what}: descriptors must have shape [{K}, {N}, {input_dim}], got {tuple(desc.shape)}"
+    s.kpts = f32(kpts)
+    s.desc, s.desc_f16 = _engine_descriptors(desc, device)
+    s.size = s.scales = s.oris = s.num = None
+    size = feats.get("image_size")
+    if size is not None:
+        if not isinstance(size, torch.Tensor):
+            size = torch.tensor(size, dtype=torch.float32)
+        size = f32(size).reshape(-1, 2)
+        assert size.shape[0] in (1, K), f"{what}: image_size must have shape [2], [1, 2] or [{K}, 2]"
+        s.size = size if size.shape[0] == K else size.expand(K, 2).contiguous()
+    if add_scale_ori:
+        s.scales, s.oris = f32(feats["scales"]), f32(feats["oris"])
+        assert tuple(s.scales.shape) == (K, N) and tuple(s.oris.shape) == (K, N), f"{what}: scales / oris must have shape [{K}, {N}]"
+    num = feats.get("num_keypoints")
+    if num is not None:
+        num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
+        assert num.shape == (K,), f"{what}: num_keypoints must have shape [{K}]"
+        s.num = num.clamp(0, N)
+    return s
+
+
+# ---------------------------------------------------------------------- the outputs of a call
+@functools.lru_cache(maxsize=256)
+def carve_plan(b: int, m: int, n: int, pruning: bool) -> tuple:
+    """(sizes, offsets) x (int32, fp32, int64): the pieces of the three output allocations of `b` pairs of m x n keypoints, every piece at a 4-element
+    (16-byte) offset.  A pure function of the shape, cached: the host path of a B = 1 forward is ~0.3 ms, and this was a tenth of it."""
+    def carve(sizes):
+        off = [0]
+        for x in sizes:
+            off.append(off[-1] + ((x + 3) & ~3))
+        return tuple(off)
+    kmax = min(m, n)
+    isz = (b * m, b * n, b * kmax * 2, b * m if pruning else 0, b * n if pruning else 0, 3 * b)
+    fsz = (b * m, b * n, b * kmax, 0 if pruning else b * m, 0 if pruning else b * n)
+    lsz = (b * m, b * n, b * kmax * 2, b, b * m if pruning else 0, b * n if pruning else 0)
+    return isz, carve(isz), fsz, carve(fsz), lsz, carve(lsz)
+
+
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+class Outputs:
+    """The outputs of `b` pairs: ONE int32, ONE int64 and ONE fp32 allocation, carved into the tensors of the C ABI (`carve_plan`).  The engine's last kernel
+    writes the reference's dtypes itself (int64 indices / stop / prune counters, float prune0/1 without pruning, ref :616-629; round-5 extension of
+    lg_forward_io): no framework kernel runs between or behind the engine's launches.  Every piece is contiguous with the pair as its leading dimension, so
+    the outputs of pairs [start, stop) are the same pieces at a pointer offset (`io`).  `raw_mode`: no int64 allocation (LightGlue.forward_raw)."""
+
+    def __init__(self, b, m, n, device, pruning, raw_mode=False, log_assignment=False):
+        self.b, self.m, self.n, self.pruning, self.raw_mode = b, m, n, pruning, raw_mode
+        kmax = min(m, n)
+        isz, ioff, fsz, foff, lsz, loff = carve_plan(b, m, n, pruning)
+
+        def piece(buf, off, sz, k, *shape):
+            return buf[off[k]: off[k] + sz[k]].view(shape)
+        ibuf = self.ibuf = torch.empty((ioff[-1],), device=device, dtype=torch.int32)
+        self.m0, self.m1, self.mlist = piece(ibuf, ioff, isz, 0, b, m), piece(ibuf, ioff, isz, 1, b, n), piece(ibuf, ioff, isz, 2, b, kmax, 2)
+        self.prune0_i32 = piece(ibuf, ioff, isz, 3, b, m) if pruning else None
+        self.prune1_i32 = piece(ibuf, ioff, isz, 4, b, n) if pruning else None
+        self.stop_nm = piece(ibuf, ioff, isz, 5, 3, b)              # [0] = stop, [1] = n_matches, [2] = status (LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE / LG_ERR_INDEX)
+        fbuf = self.fbuf = torch.empty((foff[-1],), device=device, dtype=torch.float32)
+        self.ms0, self.ms1 = piece(fbuf, foff, fsz, 0, b, m), piece(fbuf, foff, fsz, 1, b, n)
+        self.mscore_list = piece(fbuf, foff, fsz, 2, b, kmax)
+        self.m0_64 = self.m1_64 = self.mlist64 = self.stop64 = self.prune0 = self.prune1 = self.lbuf = None
+        if not raw_mode:
+            lbuf = self.lbuf = torch.empty((loff[-1],), device=device, dtype=torch.int64)
+            self.m0_64, self.m1_64 = piece(lbuf, loff, lsz, 0, b, m), piece(lbuf, loff, lsz, 1, b, n)
+            self.mlist64, self.stop64 = piece(lbuf, loff, lsz, 2, b, kmax, 2), piece(lbuf, loff, lsz, 3, b)
+            if pruning:
+                self.prune0, self.prune1 = piece(lbuf, loff, lsz, 4, b, m), piece(lbuf, loff, lsz, 5, b, n)
+            else:   # ref :616-617 (padding rows of a ragged batch: 0)
+                self.prune0, self.prune1 = piece(fbuf, foff, fsz, 3, b, m), piece(fbuf, foff, fsz, 4, b, n)
+        self.log_assignment = None
+        if log_assignment and m > 0 and n > 0:
+            self.log_assignment = torch.empty((b, m + 1, n + 1), device=device, dtype=torch.float32)
+
+    def io(self, start, count, flags, s0: Side, s1: Side, wire=None, index=None):
+        """lg_forward_io of one engine call that writes pairs [start, start + count).  The sides are passed whole; `index`: the int32 [2, P] tensor
+        index0 | index1 of an LG_FLAG_INDEXED call, offset like the outputs."""
+        def at(t):     # the piece's rows from pair `start` on ([pairs, ...] contiguous)
+            return None if t is None or t.numel() == 0 else t.data_ptr() + start * t.stride(0) * t.element_size()
+        row = lambda k: self.stop_nm.data_ptr() + (k * self.b + start) * 4
+        i64 = not self.raw_mode
+        counters, fill = (i64 and self.pruning), (i64 and not self.pruning)     # prune0 / prune1 hold int64 counters or the reference's float fill
+        io = _cabi.LgForwardIO(
+            count, self.m, self.n, flags,
+            _ptr(s0.kpts), _ptr(s1.kpts), _ptr(s0.desc), _ptr(s1.desc), _ptr(s0.size), _ptr(s1.size), _ptr(s0.scales), _ptr(s0.oris), _ptr(s1.scales), _ptr(s1.oris),
+            at(self.m0), at(self.m1), at(self.ms0), at(self.ms1), row(0), at(self.prune0_i32), at(self.prune1_i32),
+            at(self.mlist), at(self.mscore_list), row(1), _ptr(s0.num), _ptr(s1.num), at(self.log_assignment),
+            at(self.m0_64), at(self.m1_64), at(self.mlist64), at(self.stop64),
+            at(self.prune0) if counters else None, at(self.prune1) if counters else None, at(self.prune0) if fill else None, at(self.prune1) if fill else None,
+            _ptr(wire), 0 if wire is None else wire.stride(0), row(2))
+        if index is not None:
+            io.index0, io.index1 = index[0].data_ptr() + 4 * start, index[1].data_ptr() + 4 * start
+            io.images0, io.images1 = s0.K, s1.K
+        return io
+
+    def raw(self) -> dict:
+        """What forward_raw returns.  "pruning": the wire row's prune block holds int counters (else the float fill's bits)."""
+        return {"matches0": self.m0, "matches1": self.m1, "matching_scores0": self.ms0, "matching_scores1": self.ms1, "stop": self.stop_nm[0],
+                "status": self.stop_nm[2], "pruning": self.pruning}
+
+    def _assemble(self, host):
+        matches, scores, stop = ragged_outputs(host, self.mlist64, self.mscore_list, self.stop64)
+        extra_out = {} if self.log_assignment is None else {"log_assignment": self.log_assignment}
+        return {**extra_out, "matches0": self.m0_64, "matches1": self.m1_64, "matching_scores0": self.ms0, "matching_scores1": self.ms1,
+                "stop": stop, "matches": matches, "scores": scores, "prune0": self.prune0, "prune1": self.prune1}
+
+    def finish(self, stream, defer):
+        """Output assembly (ref :593-629) behind the last engine call: the engine has written every fixed-shape tensor; only the ragged lists need the host."""
+        if defer:   # the sizes travel to pinned host memory behind an event; nothing waits here
+            hbuf = torch.empty((3, self.b), dtype=torch.int32, pin_memory=True)
+            hbuf.copy_(self.stop_nm, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+            return DeferredMatches(done, hbuf, self._assemble, tuple(t for t in (self.ibuf, self.fbuf, self.lbuf, self.log_assignment) if t is not None))
+        return self._assemble(self.stop_nm.tolist())  # THE host sync of the call: the ragged lists need their sizes (and B = 1 its `stop`)

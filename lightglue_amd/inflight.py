@@ -23,7 +23,8 @@ from typing import List
 
 import torch
 
-from .lightglue import DeferredMatches, LightGlue
+from ._call import DeferredMatches, require_gpu
+from .lightglue import LightGlue
 
 
 def _tensors(obj):
@@ -59,8 +60,7 @@ class InflightMatcher:
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback")
+        require_gpu(self.device, "an InflightMatcher")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.model = model

@@ -34,7 +34,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _cabi
+from . import _cabi, _call
+from ._call import DeferredMatches, _engine_descriptors, plan_pair_chunks  # noqa: F401  (importable from this module as before)
 
 
 class _Holder(nn.Module):
@@ -64,64 +65,6 @@ def _cross_block(d: int) -> nn.Module:  # ref :176-192
     m.to_out = nn.Linear(d, d)
     m.ffn = _ffn(d)
     return m
-
-
-class DeferredMatches:
-    """Handle of a forward whose outputs are on their way (LightGlue.forward_deferred)."""
-
-    def __init__(self, done, host_sizes, assemble, buffers=()):
-        self._done, self._host, self._assemble, self._out = done, host_sizes, assemble, None
-        self.buffers = buffers     # the allocations every output tensor is a view of (InflightMatcher hands THEM to the consumer's stream: 3 - 4 record_stream calls, not one per output)
-
-    def result(self) -> dict:
-        if self._out is None:
-            self._done.synchronize()
-            self._out = self._assemble(self._host.tolist())
-            self._assemble = None
-        return self._out
-
-
-def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS, max_sim_elems: int = _cabi.LG_MAX_SIM_ELEMS) -> list:
-    """Cut a list of P pairs of n0 x n1 keypoints into the FEWEST contiguous chunks [(start, stop), ...] that each fit one engine call
-    (include/lightglue_amd.h: pairs * (cap0 + cap1) <= max_rows and pairs * cap0 * cap1 <= max_sim_elems, cap = n rounded up to 128).  Chunk sizes differ
-    by at most one, larger chunks first: the first chunk is the largest call, so the engine's workspace grows at most once.  Pure host arithmetic."""
-    P, n0, n1 = int(P), int(n0), int(n1)
-    if n0 > _cabi.LG_MAX_KEYPOINTS or n1 > _cabi.LG_MAX_KEYPOINTS:    # what lg_engine_forward answers (AssertionError through _cabi.check): no chunking helps
-        raise AssertionError("more than LG_MAX_KEYPOINTS (8192) keypoints in one image")
-    if P <= 0:
-        return []
-    c0, c1 = (n0 + 127) // 128 * 128, (n1 + 127) // 128 * 128
-    per_call = P
-    if c0 + c1:
-        per_call = min(per_call, int(max_rows) // (c0 + c1))
-    if c0 * c1:
-        per_call = min(per_call, int(max_sim_elems) // (c0 * c1))
-    if per_call < 1:
-        raise ValueError(f"one pair of {n0} x {n1} keypoints needs {c0 + c1} rows and {c0 * c1} similarity entries: "
-                         f"more than max_rows = {max_rows} / max_sim_elems = {max_sim_elems} allow")
-    chunks = -(-P // per_call)
-    size, larger = divmod(P, chunks)
-    out, start = [], 0
-    for i in range(chunks):
-        stop = start + size + (1 if i < larger else 0)
-        out.append((start, stop))
-        start = stop
-    return out
-
-
-def _engine_descriptors(t: torch.Tensor, device) -> tuple:
-    """Descriptors as the engine reads them -> (tensor, stored as float16).  A float16 tensor is read IN PLACE (LG_FLAG_DESC0_F16 / _DESC1_F16: the engine widens
-    every value exactly where the descriptors enter it, so the forward is bit-identical to one on `t.float()`) — untouched when it is on the device, contiguous
-    and 16-byte aligned, otherwise through one float16 copy; every other dtype becomes contiguous fp32, as before."""
-    if t.dtype is torch.float16:
-        if t.device != device or not t.is_contiguous():
-            t = t.detach().to(device=device).contiguous()
-        if t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
-            t = t.clone()
-        return t, True
-    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-        return t, False
-    return t.detach().to(device=device, dtype=torch.float32).contiguous(), False
 
 
 class LightGlue(nn.Module):
@@ -230,6 +173,7 @@ class LightGlue(nn.Module):
         self._engine = None  # (handle, device_index, config signature)
         self._weights_sig = None
         self._plist = None
+        self._debug_step = -1   # debug_stop_after: >= 0 while the engine's pipeline stops early
         self.requires_grad_(False)
 
     # ------------------------------------------------------------------ weights
@@ -369,7 +313,7 @@ class LightGlue(nn.Module):
 
     def __getstate__(self):                              # copy.deepcopy / pickle / torch.save(model): the engine handle
         st = dict(self.__dict__)                         # is process-local; the copy creates its own lazily
-        st["_engine"] = None; st["_plist"] = None; st["_weights_sig"] = None
+        st["_engine"] = None; st["_plist"] = None; st["_weights_sig"] = None; st["_debug_step"] = -1
         return st
 
     def reserve(self, batch: int, n0: int, n1: int, device=None):
@@ -387,54 +331,55 @@ class LightGlue(nn.Module):
         do_compile = bool(self.static_lengths) and max(m, n) <= max(self.static_lengths)
         return self.conf.width_confidence > 0 and not do_compile
 
-    def _carve_plan(self, b, m, n, kmax, pruning):
-        """Sizes and 4-element-aligned offsets of the pieces of the three output allocations (int32 / fp32 / int64), cached per shape."""
-        key = (b, m, n, pruning)
-        cache = self.__dict__.setdefault("_plans", {})
-        plan = cache.get(key)
-        if plan is None:
-            def carve(sizes):
-                off = [0]
-                for x in sizes:
-                    off.append(off[-1] + ((x + 3) & ~3))
-                return off
-            isz = [b * m, b * n, b * kmax * 2, b * m if pruning else 0, b * n if pruning else 0, 3 * b]
-            fsz = [b * m, b * n, b * kmax, 0 if pruning else b * m, 0 if pruning else b * n]
-            lsz = [b * m, b * n, b * kmax * 2, b, b * m if pruning else 0, b * n if pruning else 0]
-            if len(cache) > 256:
-                cache.clear()
-            plan = cache[key] = (isz, carve(isz), fsz, carve(fsz), lsz, carve(lsz))
-        return plan
+    def _sides(self, feats0: dict, feats1: dict, names=("feats0", "feats1")):
+        """(device, side 0, side 1) of a call as the engine reads them, converted at most once per call; a non-GPU device is refused first."""
+        device = feats0["keypoints"].device
+        _call.require_gpu(device)
+        conf = self.conf
+        s0 = _call.normalise_side(feats0, device, conf.input_dim, conf.add_scale_ori, names[0])
+        s1 = s0 if feats1 is feats0 else _call.normalise_side(feats1, device, conf.input_dim, conf.add_scale_ori, names[1])
+        return device, s0, s1
 
-    def forward_raw(self, data: dict, wire: Optional[torch.Tensor] = None) -> dict:
-        """The forward without output widening, ragged lists or the host synchronisation: int32 `matches0/1` [B, M|N], fp32
-        `matching_scores0/1`, int32 `stop` and `status` [B] — views of the engine's own output buffers, valid on the current stream.
-        `wire`: optional int32 [pairs >= B][>= 3M + 3N + 2] buffer; the engine's last kernel then also packs one row per pair,
-        [matches0 | score0 bits | matches1 | score1 bits | stop | status | prune0 | prune1] — the send buffer of `PairShardedMatcher`
-        (`lg_unpack_wire` rebuilds the output dict's tensors on the receiving side)."""
-        return self.forward(data, _raw=True if wire is None else wire)
+    def _batch(self, data: dict, raw_mode: bool = False):
+        """`forward(data)` is `match_pairs` over two stores of B images with the identity pair list, which needs no index: (device, sides, outputs of B pairs)."""
+        for key in self.required_data_keys:
+            assert key in data, f"Missing key {key} in data"
+        device, s0, s1 = self._sides(data["image0"], data["image1"], self.required_data_keys)
+        assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+        return device, s0, s1, self._outputs(s0.K, s0, s1, device, raw_mode)
 
-    @staticmethod
-    def _raise_on_status(status) -> None:
-        bad = [(i, int(c)) for i, c in enumerate(status) if int(c) != _cabi.LG_OK]
-        if bad:
-            what = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
-                    _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
-                    _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched"}
-            raise _cabi.LightGlueAmdError("; ".join(f"pair {i}: {what.get(c, c)}" for i, c in bad[:8]))
+    def _outputs(self, pairs: int, s0, s1, device, raw_mode: bool = False):
+        return _call.Outputs(pairs, s0.N, s1.N, device, self.will_prune(s0.N, s1.N), raw_mode, self.return_log_assignment)
 
-    def forward_deferred(self, data: dict) -> "DeferredMatches":
-        """The forward enqueued WITHOUT its host synchronisation: `.result()` of the returned handle waits for this forward
-        only (an event), then builds the same dict as `forward`.  A caller that issues forward i + 1 before it asks for the
-        result of forward i keeps the GPU busy while Python assembles the ragged lists (bench.py does; the reference's
-        synchronous `forward` cannot)."""
-        return self.forward(data, _defer=True)
+    def _launch(self, device, s0, s1, o, chunks, index=None, wire=None, defer=False):
+        """THE call path: pairs [start, stop) of every chunk in one engine call each on the current stream, all writing their slice of the outputs `o`; then the
+        raw dict (`o.raw_mode`), a `DeferredMatches` (`defer`) or the dict behind the ONE host synchronisation of the call.  `index`: int32 [2, P] image indices
+        into the sides (LG_FLAG_INDEXED), None for pair p = (image p, image p).  The range guard is armed and consumed once per call and covers every chunk."""
+        debug = self._debug_step >= 0
+        assert not debug or len(chunks) <= 1, "debug taps (debug_stop_after) read the workspace of ONE engine call: match_pairs supports them for a single chunk only"
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            if chunks:
+                handle = self._get_engine(device)
+                self._sync_weights(handle, device)
+                guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
+                self._guard_pending = False
+                flags = (_cabi.LG_FLAG_EXT | (0 if index is None else _cabi.LG_FLAG_INDEXED) | (0 if o.pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
+                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0) | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0))
+                lib, stream_ptr = _cabi.load(), C.c_void_p(stream.cuda_stream)
+                for start, stop in chunks:
+                    io = o.io(start, stop - start, flags, s0, s1, wire, index)
+                    _cabi.check(lib.lg_engine_forward(handle, C.byref(io), stream_ptr))
+            if debug:   # test tap: the pipeline stopped early, outputs are not written
+                torch.cuda.synchronize(device)
+                return None
+            return o.raw() if o.raw_mode else o.finish(stream, defer)
 
     @torch.no_grad()
-    def forward(self, data: dict, _raw: bool = False, _defer: bool = False) -> dict:
+    def forward(self, data: dict) -> dict:
         """Match keypoints and descriptors between two images (same dict contract as ref :456-481).
 
-        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D] (float16 descriptors are read in place, per side: see _engine_descriptors),
+        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D] (float16 descriptors are read in place, per side: see _call._engine_descriptors),
                                        image_size [B,2] (optional),
                                        scales/oris [B,N] iff add_scale_ori,
                                        num_keypoints [B] int (optional, extension: ragged batch — pair b uses only
@@ -443,80 +388,33 @@ class LightGlue(nn.Module):
         Output (dict): matches0 [B,M] int64, matching_scores0 [B,M], matches1 [B,N], matching_scores1 [B,N],
                        matches List[[S_i,2]], scores List[[S_i]], stop, prune0 [B,M], prune1 [B,N]
         """
-        for key in self.required_data_keys:
-            assert key in data, f"Missing key {key} in data"
-        d0, d1 = data["image0"], data["image1"]
-        kpts0, kpts1 = d0["keypoints"], d1["keypoints"]
-        device = kpts0.device
-        if device.type != "cuda":
-            raise RuntimeError("lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
-                               f"Got keypoints on {device}.")
-        b, m, _ = kpts0.shape
-        b, n, _ = kpts1.shape
-        conf = self.conf
-        def f32(t):   # only the data pointer is handed on: tensors that already qualify pass through untouched
-            if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-                return t
-            return t.detach().to(device=device, dtype=torch.float32).contiguous()
+        device, s0, s1, o = self._batch(data)
+        return self._launch(device, s0, s1, o, [(0, o.b)])
 
-        k0, k1 = f32(kpts0), f32(kpts1)
-        (desc0, half0), (desc1, half1) = _engine_descriptors(d0["descriptors"], device), _engine_descriptors(d1["descriptors"], device)
-        assert desc0.shape[-1] == conf.input_dim
-        assert desc1.shape[-1] == conf.input_dim
-        size0, size1 = d0.get("image_size"), d1.get("image_size")
+    @torch.no_grad()
+    def forward_deferred(self, data: dict) -> "DeferredMatches":
+        """The forward enqueued WITHOUT its host synchronisation: `.result()` of the returned handle waits for this forward
+        only (an event), then builds the same dict as `forward`.  A caller that issues forward i + 1 before it asks for the
+        result of forward i keeps the GPU busy while Python assembles the ragged lists (bench.py does; the reference's
+        synchronous `forward` cannot)."""
+        device, s0, s1, o = self._batch(data)
+        return self._launch(device, s0, s1, o, [(0, o.b)], defer=True)
 
-        def as_size(s):
-            if s is None:
-                return None
-            if not isinstance(s, torch.Tensor):
-                s = torch.tensor(s, dtype=torch.float32)
-            s = f32(s).reshape(-1, 2)
-            assert s.shape[0] in (1, b), f"image_size must have shape [2], [1, 2] or [{b}, 2]"
-            return s if s.shape[0] == b else s.expand(b, 2).contiguous()   # the reference broadcasts (ref :35-42)
-
-        size0, size1 = as_size(size0), as_size(size1)
-        extra = [None] * 4
-        if conf.add_scale_ori:
-            extra = [f32(d0["scales"]), f32(d0["oris"]), f32(d1["scales"]), f32(d1["oris"])]
-
-        def as_count(c, nmax):
-            if c is None:
-                return None
-            c = torch.as_tensor(c).detach().to(device=device, dtype=torch.int32).contiguous()
-            assert c.shape == (b,), f"num_keypoints must have shape [{b}]"
-            return c.clamp(0, nmax)
-
-        num0, num1 = as_count(d0.get("num_keypoints"), m), as_count(d1.get("num_keypoints"), n)
-        ragged = num0 is not None or num1 is not None
-
-        do_early_stop = conf.depth_confidence > 0
-        do_point_pruning = self.will_prune(m, n)
-
-        o = self._alloc_outputs(b, m, n, device, do_point_pruning, _raw is not False)
-        wire = _raw if torch.is_tensor(_raw) else None          # PairShardedMatcher: [pairs >= b][>= 3m + 3n + 2] int32 rows the engine packs itself
-        handle = self._get_engine(device)
-        self._sync_weights(handle, device)
-        guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
-        self._guard_pending = False
+    @torch.no_grad()
+    def forward_raw(self, data: dict, wire: Optional[torch.Tensor] = None) -> dict:
+        """The forward without output widening, ragged lists or the host synchronisation: int32 `matches0/1` [B, M|N], fp32
+        `matching_scores0/1`, int32 `stop` and `status` [B] — views of the engine's own output buffers, valid on the current stream.
+        `wire`: optional int32 [pairs >= B][>= 3M + 3N + 2] buffer; the engine's last kernel then also packs one row per pair,
+        [matches0 | score0 bits | matches1 | score1 bits | stop | status | prune0 | prune1] — the send buffer of `PairShardedMatcher`
+        (`lg_unpack_wire` rebuilds the output dict's tensors on the receiving side)."""
+        device, s0, s1, o = self._batch(data, raw_mode=True)
         if wire is not None:   # the engine's last kernel writes b rows of 3m + 3n + 2 int32 into it: a short or mistyped buffer would be an out-of-bounds device write (ADVICE r05)
-            if not (wire.dtype is torch.int32 and wire.device == device and wire.dim() == 2 and wire.shape[0] >= b
-                    and wire.shape[1] >= _cabi.wire_width(m, n) and (wire.shape[1] == 1 or wire.stride(1) == 1)):
-                raise ValueError(f"wire must be an int32 [>= {b}, >= {_cabi.wire_width(m, n)}] tensor on {device} with unit column stride, got "
+            width = _cabi.wire_width(o.m, o.n)
+            if not (wire.dtype is torch.int32 and wire.device == device and wire.dim() == 2 and wire.shape[0] >= o.b
+                    and wire.shape[1] >= width and (wire.shape[1] == 1 or wire.stride(1) == 1)):
+                raise ValueError(f"wire must be an int32 [>= {o.b}, >= {width}] tensor on {device} with unit column stride, got "
                                  f"{wire.dtype} {tuple(wire.shape)} stride {tuple(wire.stride())} on {wire.device}")
-        flags = (_cabi.LG_FLAG_EXT | (0 if do_point_pruning or conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING) | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
-                 | (_cabi.LG_FLAG_DESC0_F16 if half0 else 0) | (_cabi.LG_FLAG_DESC1_F16 if half1 else 0))
-        io = self._forward_io(o, 0, b, flags, (k0, k1, desc0, desc1, size0, size1, *extra, num0, num1), wire)
-        with torch.cuda.device(device):
-            cur_stream = torch.cuda.current_stream(device)
-            _cabi.check(_cabi.load().lg_engine_forward(handle, C.byref(io), C.c_void_p(cur_stream.cuda_stream)))
-
-        if getattr(self, "_debug_step", -1) >= 0:  # test tap: the pipeline stopped early, outputs are not written
-            torch.cuda.synchronize(device)
-            return None
-        if o.raw_mode:
-            return {"matches0": o.m0, "matches1": o.m1, "matching_scores0": o.ms0, "matching_scores1": o.ms1, "stop": o.stop_nm[0], "status": o.stop_nm[2],
-                    "pruning": do_point_pruning}   # "pruning": the wire row's prune block holds int counters (else the float fill's bits)
-        return self._finish(o, cur_stream, _defer)
+        return self._launch(device, s0, s1, o, [(0, o.b)], wire=wire)
 
     # ------------------------------------------------------------------ pair lists over feature stores
     def _call_limits(self):
@@ -528,37 +426,6 @@ class LightGlue(nn.Module):
                 raise ValueError(f"{name} must lie in [1, {top}] (the envelope of one engine call, include/lightglue_amd.h), got {v}")
             limits.append(v)
         return limits
-
-    def _store(self, feats: dict, device) -> SimpleNamespace:
-        """A feature store as the engine reads it: contiguous fp32 / int32 tensors on `device`, descriptors fp32 or float16 (`desc_f16`; tensors that already
-        qualify pass through untouched)."""
-        conf = self.conf
-        def f32(t):
-            if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-                return t
-            return t.detach().to(device=device, dtype=torch.float32).contiguous()
-        kpts, desc = feats["keypoints"], feats["descriptors"]
-        assert kpts.dim() == 3 and kpts.shape[-1] == 2, "a feature store holds keypoints [K, N, 2]"
-        K, N = kpts.shape[:2]
-        assert tuple(desc.shape) == (K, N, conf.input_dim), f"a feature store holds descriptors [K, N, {conf.input_dim}]"
-        desc, desc_f16 = _engine_descriptors(desc, device)
-        st = SimpleNamespace(K=K, N=N, kpts=f32(kpts), desc=desc, desc_f16=desc_f16, size=None, scales=None, oris=None, num=None)
-        size = feats.get("image_size")
-        if size is not None:
-            if not isinstance(size, torch.Tensor):
-                size = torch.tensor(size, dtype=torch.float32)
-            size = f32(size).reshape(-1, 2)
-            assert size.shape[0] in (1, K), f"image_size must have shape [2], [1, 2] or [{K}, 2]"
-            st.size = size if size.shape[0] == K else size.expand(K, 2).contiguous()
-        if conf.add_scale_ori:
-            st.scales, st.oris = f32(feats["scales"]), f32(feats["oris"])
-            assert tuple(st.scales.shape) == (K, N) and tuple(st.oris.shape) == (K, N), "scales / oris must have shape [K, N]"
-        num = feats.get("num_keypoints")
-        if num is not None:
-            num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
-            assert num.shape == (K,), f"num_keypoints must have shape [{K}]"
-            st.num = num.clamp(0, N)
-        return st
 
     @torch.no_grad()
     def match_pairs(self, feats0: dict, pairs, feats1: Optional[dict] = None, *, deferred: bool = False, validate: bool = True):
@@ -598,130 +465,11 @@ class LightGlue(nn.Module):
             if lo < 0 or hi0 >= K0 or hi1 >= K1:
                 bad = ((host < 0) | (host >= torch.tensor([K0, K1]))).any(1).nonzero().flatten().tolist()
                 raise ValueError(f"pairs {bad[:8]} index outside the feature stores of {K0} and {K1} images")
-        device = feats0["keypoints"].device
-        if device.type != "cuda":
-            raise RuntimeError("lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
-                               f"Got keypoints on {device}.")
-        s0 = self._store(feats0, device)              # converted at most once per call, never per chunk
-        s1 = s0 if same else self._store(feats1, device)
-        m, n = s0.N, s1.N
-        chunks = plan_pair_chunks(P, m, n, max_rows, max_sim)
-        self.last_pair_chunks = chunks
-        pruning = self.will_prune(m, n)
-        o = self._alloc_outputs(P, m, n, device, pruning, False)
-        debug = getattr(self, "_debug_step", -1) >= 0
-        assert not debug or len(chunks) == 1, "debug taps (debug_stop_after) read the workspace of ONE engine call: match_pairs supports them for a single chunk only"
-        with torch.cuda.device(device):
-            cur_stream = torch.cuda.current_stream(device)
-            if P:
-                index = pt.to(device=device, dtype=torch.int32).t().contiguous()     # [2, P]: index0 | index1, a chunk is an offset into both
-                handle = self._get_engine(device)
-                self._sync_weights(handle, device)
-                guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
-                self._guard_pending = False
-                flags = (_cabi.LG_FLAG_EXT | _cabi.LG_FLAG_INDEXED | (0 if pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
-                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0)
-                         | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0))
-                inputs = (s0.kpts, s1.kpts, s0.desc, s1.desc, s0.size, s1.size, s0.scales, s0.oris, s1.scales, s1.oris, s0.num, s1.num)
-                lib, stream_ptr = _cabi.load(), C.c_void_p(cur_stream.cuda_stream)
-                for start, stop in chunks:
-                    io = self._forward_io(o, start, stop - start, flags, inputs, None, (index[0], index[1], s0.K, s1.K))
-                    _cabi.check(lib.lg_engine_forward(handle, C.byref(io), stream_ptr))
-            if debug:   # test tap: the pipeline stopped early, outputs are not written
-                torch.cuda.synchronize(device)
-                return None
-            return self._finish(o, cur_stream, deferred)
-
-    # ------------------------------------------------------------------ outputs (shared by forward and match_pairs)
-    def _alloc_outputs(self, b, m, n, device, pruning, raw_mode):
-        """The outputs of `b` pairs: ONE int32, ONE int64 and ONE fp32 allocation, carved into the tensors of the C ABI (16-byte aligned pieces).  The engine's
-        last kernel writes the reference's dtypes itself (int64 indices / stop / prune counters, float prune0/1 without pruning, ref :616-629; round-5 extension
-        of lg_forward_io): no framework kernel runs between or behind the engine's launches.  Every piece is contiguous with the pair as its leading
-        dimension, so the outputs of pairs [start, stop) are the same pieces at a pointer offset (`_forward_io`)."""
-        kmax = min(m, n)
-        isz, ioff, fsz, foff, lsz, loff = self._carve_plan(b, m, n, kmax, pruning)      # offsets of the pieces (cached per shape: the host path of a B = 1 forward is ~0.3 ms, and this was a tenth of it)
-        o = SimpleNamespace(b=b, m=m, n=n, pruning=pruning, raw_mode=raw_mode)
-        ibuf = o.ibuf = torch.empty((ioff[-1],), device=device, dtype=torch.int32)
-
-        def ipiece(buf, off, sz, k, *shape):
-            return buf[off[k]: off[k] + sz[k]].view(shape)
-        o.m0, o.m1, o.mlist = ipiece(ibuf, ioff, isz, 0, b, m), ipiece(ibuf, ioff, isz, 1, b, n), ipiece(ibuf, ioff, isz, 2, b, kmax, 2)
-        o.prune0_i32 = ipiece(ibuf, ioff, isz, 3, b, m) if pruning else None
-        o.prune1_i32 = ipiece(ibuf, ioff, isz, 4, b, n) if pruning else None
-        o.stop_nm = ipiece(ibuf, ioff, isz, 5, 3, b)              # [0] = stop, [1] = n_matches, [2] = status (LG_OK / LG_ERR_RANGE / LG_ERR_DEVICE / LG_ERR_INDEX)
-        fbuf = o.fbuf = torch.empty((foff[-1],), device=device, dtype=torch.float32)
-        o.ms0, o.ms1 = ipiece(fbuf, foff, fsz, 0, b, m), ipiece(fbuf, foff, fsz, 1, b, n)
-        o.mscore_list = ipiece(fbuf, foff, fsz, 2, b, kmax)
-        o.m0_64 = o.m1_64 = o.mlist64 = o.stop64 = o.prune0 = o.prune1 = o.lbuf = None
-        if not raw_mode:
-            lbuf = o.lbuf = torch.empty((loff[-1],), device=device, dtype=torch.int64)
-            o.m0_64, o.m1_64 = ipiece(lbuf, loff, lsz, 0, b, m), ipiece(lbuf, loff, lsz, 1, b, n)
-            o.mlist64, o.stop64 = ipiece(lbuf, loff, lsz, 2, b, kmax, 2), ipiece(lbuf, loff, lsz, 3, b)
-            if pruning:
-                o.prune0, o.prune1 = ipiece(lbuf, loff, lsz, 4, b, m), ipiece(lbuf, loff, lsz, 5, b, n)
-            else:   # ref :616-617 (padding rows of a ragged batch: 0)
-                o.prune0, o.prune1 = ipiece(fbuf, foff, fsz, 3, b, m), ipiece(fbuf, foff, fsz, 4, b, n)
-        o.log_assignment = None
-        if self.return_log_assignment and m > 0 and n > 0:
-            o.log_assignment = torch.empty((b, m + 1, n + 1), device=device, dtype=torch.float32)
-        return o
-
-    @staticmethod
-    def _forward_io(o, start, count, flags, inputs, wire=None, index=None):
-        """lg_forward_io of one engine call that writes pairs [start, start + count) of the outputs `o`.  `inputs`: kpts0, kpts1, desc0, desc1, size0, size1,
-        scales0, oris0, scales1, oris1, num0, num1 (tensors or None), passed whole; `index`: (index0, index1, images0, images1) of an LG_FLAG_INDEXED call,
-        the two int32 [P] tensors offset like the outputs."""
-        whole = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-        def at(t):     # the piece's rows from pair `start` on ([pairs, ...] contiguous)
-            return None if t is None or t.numel() == 0 else t.data_ptr() + start * t.stride(0) * t.element_size()
-        row = lambda k: o.stop_nm.data_ptr() + (k * o.b + start) * 4
-        k0, k1, desc0, desc1, size0, size1, sc0, or0, sc1, or1, num0, num1 = inputs
-        with_i64, prune = not o.raw_mode, o.pruning
-        io = _cabi.LgForwardIO(
-            count, o.m, o.n, flags,
-            whole(k0), whole(k1), whole(desc0), whole(desc1), whole(size0), whole(size1), whole(sc0), whole(or0), whole(sc1), whole(or1),
-            at(o.m0), at(o.m1), at(o.ms0), at(o.ms1), row(0), at(o.prune0_i32), at(o.prune1_i32),
-            at(o.mlist), at(o.mscore_list), row(1), whole(num0), whole(num1), at(o.log_assignment),
-            at(o.m0_64), at(o.m1_64), at(o.mlist64), at(o.stop64),
-            at(o.prune0) if (prune and with_i64) else None, at(o.prune1) if (prune and with_i64) else None,
-            None if (prune or not with_i64) else at(o.prune0), None if (prune or not with_i64) else at(o.prune1),
-            whole(wire), 0 if wire is None else wire.stride(0), row(2))
-        if index is not None:
-            io.index0, io.index1 = index[0].data_ptr() + 4 * start, index[1].data_ptr() + 4 * start
-            io.images0, io.images1 = index[2], index[3]
-        return io
-
-    def _finish(self, o, stream, defer):
-        """Output assembly (ref :593-629) behind the last engine call: the engine has written every fixed-shape tensor; only the ragged lists need the host."""
-        b = o.b
-
-        def assemble(host):   # host = [[stop per pair], [matches per pair], [status per pair]]
-            self._raise_on_status(host[2])
-            counts = host[1]
-            matches = [row[:c] for row, c in zip(o.mlist64.unbind(0), counts)]
-            mscores = [row[:c] for row, c in zip(o.mscore_list.unbind(0), counts)]
-            stop_out = int(host[0][0]) if b == 1 else o.stop64
-            extra_out = {} if o.log_assignment is None else {"log_assignment": o.log_assignment}
-            return {
-                **extra_out,
-                "matches0": o.m0_64,
-                "matches1": o.m1_64,
-                "matching_scores0": o.ms0,
-                "matching_scores1": o.ms1,
-                "stop": stop_out,
-                "matches": matches,
-                "scores": mscores,
-                "prune0": o.prune0,
-                "prune1": o.prune1,
-            }
-
-        if defer:   # the sizes travel to pinned host memory behind an event; nothing waits here
-            hbuf = torch.empty((3, b), dtype=torch.int32, pin_memory=True)
-            hbuf.copy_(o.stop_nm, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(stream)
-            return DeferredMatches(done, hbuf, assemble, tuple(t for t in (o.ibuf, o.fbuf, o.lbuf, o.log_assignment) if t is not None))
-        return assemble(o.stop_nm.tolist())  # THE host sync of the call: the ragged lists need their sizes (and B = 1 its `stop`)
+        device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
+        self.last_pair_chunks = chunks = plan_pair_chunks(P, s0.N, s1.N, max_rows, max_sim)
+        o = self._outputs(P, s0, s1, device)
+        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None     # [2, P]: index0 | index1, a chunk is an offset into both
+        return self._launch(device, s0, s1, o, chunks, index, defer=deferred)
 
     def set_option(self, key: str, value: int, device="cuda"):
         """Engine options (include/lightglue_amd.h lg_engine_set_option), e.g. ("fused_tail", 0)."""

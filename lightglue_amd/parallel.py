@@ -25,6 +25,9 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from ._cabi import wire_width  # noqa: F401  (LG_WIRE_WIDTH: int32 elements of one wire row; importable from here as before)
+from ._call import ragged_outputs
+
 
 def shard_range(batch: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous block of pairs owned by ``rank``: sizes differ by at most one."""
@@ -146,7 +149,9 @@ class PairShardedMatcher:
         will_prune = getattr(self.matcher, "will_prune", None)
         with_prune = bool(will_prune(m, n)) if will_prune is not None else bool(getattr(self.matcher, "wire_prunes", False))
         if nloc > 0 and raw is not None and dev.type == "cuda":
-            assert bool(raw(local, wire=buf)["pruning"]) == with_prune
+            pruned = bool(raw(local, wire=buf)["pruning"])
+            if pruned != with_prune:   # the receiving side would read the prune block as the wrong type
+                raise RuntimeError(f"the matcher's forward_raw pruned = {pruned}, its will_prune / wire_prunes said {with_prune}")
         elif nloc > 0:   # any other matcher with the dict contract (the CPU tests' stand-in): pack here
             out = self.matcher(local)
             _pack_rows(buf[:nloc], out, m, n)
@@ -205,11 +210,6 @@ class PairShardedMatcher:
             matches.append(torch.stack([i0, result["matches0"][k][valid]], -1))
             scores.append(result["matching_scores0"][k][valid])
         return matches, scores
-
-
-def wire_width(m: int, n: int) -> int:
-    """int32 elements of one wire row (LG_WIRE_WIDTH, include/lightglue_amd.h)"""
-    return 3 * m + 3 * n + 2
 
 
 def _pack_rows(rows: torch.Tensor, out: dict, m: int, n: int) -> None:
@@ -306,13 +306,8 @@ class Pending:
             self.done.synchronize()
             torch.cuda.current_stream(outs["matches0"].device).wait_event(self.done)
         host = self.info.tolist()       # THE host synchronisation of the step (a no-op on the side-stream path: `info` is pinned host memory there)
-        from .lightglue import LightGlue
-        LightGlue._raise_on_status(host[2])
-        counts = host[1]
-        mlist, mscores = outs.pop("_mlist"), outs.pop("_mscores")
-        outs["matches"] = [row[:c] for row, c in zip(mlist.unbind(0), counts)]
-        outs["scores"] = [row[:c] for row, c in zip(mscores.unbind(0), counts)]
-        if self.pairs == 1:
-            outs["stop"] = int(host[0][0])
+        matches, scores, outs["stop"] = ragged_outputs(host, outs["_mlist"], outs["_mscores"], outs["stop"])     # raises on a status, as LightGlue.forward
+        del outs["_mlist"], outs["_mscores"]
+        outs["matches"], outs["scores"] = matches, scores
         self._result = outs
         return outs

@@ -10,6 +10,7 @@ import torch
 import gpu_util
 from conftest import require_gpu
 from lightglue_amd import _cabi
+from lightglue_amd._call import normalise_side
 from lightglue_amd import synthetic as synth
 from test_gpu_match_pairs import ADAPTIVE, COUNTS, FIXED, PAIRS, _assert_same_dict, _stacked, _store
 
@@ -120,9 +121,9 @@ def test_store_is_read_in_place():
     require_gpu()
     model = _model()
     h, w = _halves(_store(3, COUNTS, 200))
-    st = model._store(h, h["descriptors"].device)
+    st = normalise_side(h, h["descriptors"].device, 256, False)
     assert st.desc.dtype is torch.float16 and st.desc.data_ptr() == h["descriptors"].data_ptr() and st.desc_f16
-    st = model._store(w, w["descriptors"].device)
+    st = normalise_side(w, w["descriptors"].device, 256, False)
     assert st.desc.dtype is torch.float32 and st.desc.data_ptr() == w["descriptors"].data_ptr() and not st.desc_f16
 
 
@@ -176,14 +177,14 @@ def test_views():
     pairs = [(0, 0), (0, 1), (2, 3), (3, 0), (1, 1)]
     vh, vw = {k: v[1:] for k, v in h.items()}, {k: v[1:] for k, v in w.items()}
     assert vh["descriptors"].is_contiguous() and vh["descriptors"].data_ptr() == h["descriptors"].data_ptr() + 200 * 256 * 2
-    assert model._store(vh, vh["keypoints"].device).desc.data_ptr() == vh["descriptors"].data_ptr()
+    assert normalise_side(vh, vh["keypoints"].device, 256, False).desc.data_ptr() == vh["descriptors"].data_ptr()
     want = model.match_pairs(vw, pairs)
     got = model.match_pairs(vh, pairs)
     _assert_same_dict(got, want, "view [1:]")
     assert (got["matches0"][0] > -1).any()
     nc = vh["descriptors"].transpose(1, 2).contiguous().transpose(1, 2)
     assert not nc.is_contiguous() and torch.equal(nc[0, :131], vh["descriptors"][0, :131])
-    st = model._store({**vh, "descriptors": nc}, nc.device)
+    st = normalise_side({**vh, "descriptors": nc}, nc.device, 256, False)
     assert st.desc.dtype is torch.float16 and st.desc.is_contiguous() and st.desc_f16
     _assert_same_dict(model.match_pairs({**vh, "descriptors": nc}, pairs), want, "non-contiguous")
     data = {"image0": {**_stacked(vh, [0, 2]), "descriptors": nc[[0, 2]].transpose(1, 2).contiguous().transpose(1, 2)}, "image1": _stacked(vh, [1, 3])}

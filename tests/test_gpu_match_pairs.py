@@ -6,7 +6,7 @@ import torch
 
 import gpu_util
 from conftest import require_gpu
-from lightglue_amd import _cabi
+from lightglue_amd import _cabi, _call
 from lightglue_amd import synthetic as synth
 
 pytestmark = pytest.mark.gpu
@@ -196,7 +196,7 @@ def test_device_index_guard():
     with pytest.raises(_cabi.LightGlueAmdError, match="LG_ERR_INDEX"):                # their neighbours are untouched
         handle.result()
     ibuf, fbuf, lbuf = handle.buffers[:3]
-    _, ioff, _, _, _, loff = model._carve_plan(5, 200, 200, 200, False)     # where the pieces of the three output allocations start
+    _, ioff, _, _, _, loff = _call.carve_plan(5, 200, 200, False)     # where the pieces of the three output allocations start
     m0, stop = lbuf[:5 * 200].view(5, 200), lbuf[loff[3]:loff[3] + 5]
     assert torch.equal(m0[0], good["matches0"][0]) and torch.equal(m0[3], good["matches0"][1])
     assert stop.tolist() == [int(good["stop"][0]), 1, 1, int(good["stop"][1]), 1]
@@ -218,3 +218,32 @@ def test_extractor_output_goes_straight_into_match_pairs():
     keys = ("keypoints", "descriptors", "num_keypoints")
     want = model({"image0": {k: feats[k][[0, 2, 0]] for k in keys}, "image1": {k: feats[k][[1, 3, 2]] for k in keys}})
     _assert_same_dict(got, want)
+
+
+@pytest.mark.parametrize("adaptive", [False, True])
+@pytest.mark.parametrize("dim,scale_ori", [(256, False), (128, True)])
+def test_every_route_of_the_one_call_path_returns_the_same_bits(dim, scale_ori, adaptive):
+    """forward, forward_deferred, forward_raw and match_pairs with the identity pair list are ONE call path: the same dict, bit for bit, on inputs that every
+    route has to normalise — image_size of side 0 a Python list (broadcast), float16 descriptors on side 1 only, non-contiguous keypoints on side 0."""
+    require_gpu()
+    model = _model(dim, scale_ori, adaptive)
+    feats0, feats1 = _store(3, COUNTS, 200, dim, scale_ori), _store(4, [136, 70, 0, 136, 5], 136, dim, scale_ori)
+    feats0["image_size"] = [1024, 768]
+    feats1["descriptors"] = feats1["descriptors"].half()
+    feats0["keypoints"] = feats0["keypoints"].transpose(1, 2).contiguous().transpose(1, 2)
+    assert not feats0["keypoints"].is_contiguous() and feats0["keypoints"].shape == (5, 200, 2)
+    data = {"image0": feats0, "image1": feats1}
+    want = model(data)
+    what = (dim, scale_ori, adaptive)
+    _assert_same_dict(model.forward_deferred(data).result(), want, (*what, "deferred"))
+    _assert_same_dict(model.match_pairs(feats0, [(i, i) for i in range(5)], feats1), want, (*what, "match_pairs"))
+    assert model.last_pair_chunks == [(0, 5)]
+    raw = model.forward_raw(data)
+    assert raw["pruning"] is adaptive and (raw["status"] == _cabi.LG_OK).all() and raw["status"].shape == (5,)
+    for key in ("matches0", "matches1", "stop"):
+        assert raw[key].dtype == torch.int32 and want[key].dtype == torch.int64 and raw[key].shape == want[key].shape and torch.equal(raw[key].long(), want[key]), (what, key)
+    for key in ("matching_scores0", "matching_scores1"):
+        assert raw[key].dtype == torch.float32 and torch.equal(raw[key], want[key]), (what, key)
+    assert want["matches0"].shape == (5, 200) and want["matches1"].shape == (5, 136)
+    assert int(want["stop"][4]) == 1 and (want["matches1"][4] == -1).all()            # an empty image on side 0: stop 1, no match
+    assert (want["matches0"] > -1).any() and sum(len(x) for x in want["matches"]) > 0     # not all -1: the equalities above compare something
