@@ -361,6 +361,34 @@ int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, 
 int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
                            const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream);
 
+/* ---- ALIKED on a ragged batch: images of different sizes in ONE call ----
+ * Each function is its uniform twin plus `sizes`: int32 [batch][2] (w_b, h_b) on the device, and h, w are the CANVAS.  The kernels clamp every size into
+ * [1, canvas], so a bad size cannot address outside a buffer; validation proper (8 <= size <= canvas) is the caller's, who has the sizes as host integers.
+ * Geometry:
+ *   * image b is the top-left h_b x w_b corner of image[b] ([batch][channels][h][w]); nothing outside it is read (the canvas padding may hold anything).
+ *   * each image keeps its OWN InputPadder(divis_by = 32) geometry: Hp_b, Wp_b (h_b, w_b rounded up to 32), pt_b = (Hp_b - h_b) / 2, pl_b = (Wp_b - w_b) / 2,
+ *     centred, replicated from the image's own border pixels.
+ *   * the padded frame Hp_b x Wp_b of image b is the top-left corner of a padded canvas Hpc x Wpc = the padded size of (h, w); the padding is monotone, so
+ *     Hp_b <= Hpc.  lg_aliked_levels_bytes(batch, h, w) / lg_aliked_workspace_bytes(batch, h, w, n_pos) and the level layout are those of the canvas: level
+ *     s = 0, 1, 3, 5 is [batch][Hpc >> s][Wpc >> s][32] and image b's part of it the top-left (Hp_b >> s) x (Wp_b >> s).
+ *   * addresses and strides come from the canvas, every bound from the image: on no level is anything outside an image's padded frame read (workspace and
+ *     level rows there are never written either).  The one exception: scores [batch][h][w] is written 0 outside each image, so it is defined everywhere.
+ * Inside the image every output is bit-identical to the uniform call with batch = 1 on the crop.
+ * lg_aliked_detect_ragged: the far borders, the soft-argmax window's zero padding, the (w - 1, h - 1) factors and the mean are image b's; keypoints are in its own
+ *   frame.  The fallback "no pixel passes scores_th -> the image's mean score" is decided PER IMAGE (the uniform call keeps the reference's whole-batch rule):
+ *   a ragged batch is a set of independent images, each equal to its own batch of one.  image_size: as for lg_aliked_detect (NULL: the sizes).
+ * lg_aliked_describe_ragged(_half): `levels` as lg_aliked_encode_ragged wrote them for the same batch, h, w, sizes. */
+int lg_aliked_encode_ragged(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
+                            void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream);
+int lg_aliked_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius,
+                            float scores_th, int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
+                            float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream);
+int lg_aliked_describe_ragged(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm,
+                              const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
+int lg_aliked_describe_ragged_half(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
+                                   const float* kp_norm, const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors,
+                                   void* hip_stream);
+
 /* ---- ImagePreprocessor (lightglue/utils.py:12-38): the resize in front of the extractors, one fused kernel (lg_preprocess.hip) ----
  * What the reference computes through kornia.geometry.transform.resize (always bilinear: `interpolation` is not forwarded):
  *   target size   `resize` = one edge length s + side, with ar = w / h in double: VERT (s, int(s ar)); HORZ (int(s / ar), s); LONG / SHORT:

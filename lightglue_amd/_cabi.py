@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "lg_preprocess_plan", "lg_preprocess_resize",
     "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
     "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
+    "lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half",
 )
 
 
@@ -174,6 +175,13 @@ def load() -> C.CDLL:
     lib.lg_aliked_describe_workspace_bytes.restype = C.c_int64
     lib.lg_aliked_describe.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.lg_aliked_describe_half.argtypes = lib.lg_aliked_describe.argtypes
+    # the ragged forms: `sizes` (int32 [B][2] (w, h), device) follows the canvas size
+    lib.lg_aliked_encode_ragged.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]
+    lib.lg_aliked_detect_ragged.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_float] + [C.c_int32] * 3
+                                            + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
+    lib.lg_aliked_describe_ragged.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+                                              + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+    lib.lg_aliked_describe_ragged_half.argtypes = lib.lg_aliked_describe_ragged.argtypes
     lib.lg_preprocess_plan.argtypes = [C.c_int32] * 7 + [C.POINTER(LgResizePlan)]
     lib.lg_preprocess_resize.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_int64] * 4 + [C.POINTER(LgResizePlan), C.c_void_p, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

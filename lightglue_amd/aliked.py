@@ -5,12 +5,16 @@ Same module tree / parameter names as the reference class (`lightglue/aliked.py:
 `load_state_dict(strict=True)`, and the same `forward({"image"[, "image_size"]})` contract (`:740-760`).  Everything runs in
 `lightglue_amd/csrc/lg_aliked.hip` behind the `lg_aliked_*` C entry points: the encoder, aggregation and score head
 (`lg_aliked_encode`), DKD (`lg_aliked_detect`) and SDDH (`lg_aliked_describe`), all exact fp32.  No CPU fallback.  As for
-SuperPoint, `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`) and maps the keypoints back."""
+SuperPoint, `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`) and maps the keypoints back.
+
+Images of DIFFERENT sizes run in one ragged batch: a canvas with image b in its top-left corner plus `valid_size` (`forward`, `encode`, `detect`, `describe`; the
+`lg_aliked_*_ragged` entry points).  Each image keeps its own padding to a multiple of 32, and its result is bit-identical to the B = 1 call on its crop;
+`extract_batch` builds the feature store of a mixed photo set that way (`superpoint.plan_image_batches`)."""
 from __future__ import annotations
 
 import ctypes as C
 from types import SimpleNamespace
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 from torch import nn
@@ -18,7 +22,8 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
-from .superpoint_head import check_descriptor_dtype
+from .superpoint import extract_groups, plan_image_batches
+from .superpoint_head import check_descriptor_dtype, check_sizes, sizes_on_device
 
 
 class DeformableConv2d(nn.Module):
@@ -159,9 +164,24 @@ class ALIKED(nn.Module):
 
     # ------------------------------------------------------------------ encoder + score head
     @torch.no_grad()
-    def encode(self, image: torch.Tensor):
+    def encode(self, image: torch.Tensor, valid_size=None):
         """image [B, 1|3, H, W] -> (scores [B, H, W], level maps): ref extract_dense_map (:696-738) without the dense feature map, which
-        lg_aliked_describe recomputes per keypoint from the four 32-channel level maps."""
+        lg_aliked_describe recomputes per keypoint from the four 32-channel level maps.
+
+        `valid_size` (ragged batch): `[B, 2]` `(w, h)`, integers with 8 <= size <= canvas — `image` is then a canvas and image b its top-left h_b x w_b corner,
+        padded to a multiple of 32 on its own (centred, replicated from ITS border).  Nothing outside an image is read (the padding may hold anything).  Inside
+        h_b x w_b the scores, and inside the image's padded level extents `(Hp_b >> s, Wp_b >> s)` the `level_maps(levels, (B, H, W))` of the canvas, are
+        bit-identical to the call on the crop; scores outside are 0, level maps outside unspecified."""
+        sizes = None if valid_size is None else check_sizes(valid_size, image.shape[0], image.shape[-2:], 8, "valid_size")
+        return self._encode(image, sizes)
+
+    @staticmethod
+    def _sizes(sizes, device):
+        """None, validated host rows (check_sizes) or the int32 device array made from them -> that device array (or None)"""
+        return sizes if sizes is None or torch.is_tensor(sizes) else sizes_on_device(sizes, device)
+
+    def _encode(self, image: torch.Tensor, sizes):
+        """encode with `sizes` = None, validated host rows (check_sizes) or the int32 device array made from them"""
         self._check_image(image)
         device = image.device
         image = image.detach().to(dtype=torch.float32).contiguous()
@@ -175,10 +195,15 @@ class ALIKED(nn.Module):
         levels = torch.empty((nlev,), device=device, dtype=torch.uint8)
         work = torch.empty((nws,), device=device, dtype=torch.uint8)
         scores = torch.empty((bsz, h, w), device=device, dtype=torch.float32)
+        sizes = self._sizes(sizes, device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            _cabi.check(lib.lg_aliked_encode(image.data_ptr(), bsz, ch, h, w, self.n_pos, packed.data_ptr(), levels.data_ptr(), work.data_ptr(), nws,
-                                             scores.data_ptr(), C.c_void_p(stream)))
+            if sizes is None:
+                _cabi.check(lib.lg_aliked_encode(image.data_ptr(), bsz, ch, h, w, self.n_pos, packed.data_ptr(), levels.data_ptr(), work.data_ptr(), nws,
+                                                 scores.data_ptr(), C.c_void_p(stream)))
+            else:
+                _cabi.check(lib.lg_aliked_encode_ragged(image.data_ptr(), bsz, ch, h, w, sizes.data_ptr(), self.n_pos, packed.data_ptr(), levels.data_ptr(),
+                                                        work.data_ptr(), nws, scores.data_ptr(), C.c_void_p(stream)))
         return scores, levels
 
     @staticmethod
@@ -200,8 +225,18 @@ class ALIKED(nn.Module):
         return [levels[o:o + 4 * d[0] * d[1] * d[2] * d[3]].view(torch.float32).view(d) for o, d in zip(offsets, dims)]
 
     @torch.no_grad()
-    def detect(self, scores: torch.Tensor, image_size: Optional[torch.Tensor] = None):
-        """DKD (ref :94-262) on a score map [B, H, W] -> keypoints [B, cap, 2] (pixels), scores [B, cap], normalised keypoints [B, cap, 2], counts [B]."""
+    def detect(self, scores: torch.Tensor, image_size: Optional[torch.Tensor] = None, valid_size=None):
+        """DKD (ref :94-262) on a score map [B, H, W] -> keypoints [B, cap, 2] (pixels), scores [B, cap], normalised keypoints [B, cap, 2], counts [B].
+
+        `valid_size` (ragged batch, `[B, 2]` `(w, h)`; not together with `image_size`): `scores` is a canvas, the score map of image b its top-left corner and
+        whatever lies outside it is ignored.  Each image is detected as its own batch of one — keypoints in its own frame, the mean-threshold fallback decided
+        per image — bit-identical to the call on the crop."""
+        if valid_size is not None and image_size is not None:
+            raise ValueError("valid_size and image_size cannot be given together: a ragged batch takes every border from valid_size")
+        sizes = None if valid_size is None else check_sizes(valid_size, scores.shape[0], scores.shape[-2:], 8, "valid_size")
+        return self._detect(scores, image_size, sizes)
+
+    def _detect(self, scores: torch.Tensor, image_size, sizes):
         bsz, h, w = scores.shape
         device = scores.device
         top_k, th, n_limit = self._dkd()
@@ -217,16 +252,26 @@ class ALIKED(nn.Module):
         if image_size is not None:
             image_size = image_size.to(device=device, dtype=torch.float32).reshape(bsz, 2).contiguous()
             size_ptr = image_size.data_ptr()
+        sizes = self._sizes(sizes, device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            _cabi.check(lib.lg_aliked_detect(scores.data_ptr(), bsz, h, w, size_ptr, int(self.conf.nms_radius), th, top_k, n_limit, cap,
-                                             work.data_ptr(), nws, kpts.data_ptr(), kscores.data_ptr(), knorm.data_ptr(), counts.data_ptr(), C.c_void_p(stream)))
+            tail = (size_ptr, int(self.conf.nms_radius), th, top_k, n_limit, cap, work.data_ptr(), nws, kpts.data_ptr(), kscores.data_ptr(), knorm.data_ptr(),
+                    counts.data_ptr(), C.c_void_p(stream))
+            if sizes is None:
+                _cabi.check(lib.lg_aliked_detect(scores.data_ptr(), bsz, h, w, *tail))
+            else:
+                _cabi.check(lib.lg_aliked_detect_ragged(scores.data_ptr(), bsz, h, w, sizes.data_ptr(), *tail))
         return kpts, kscores, knorm, counts
 
     @torch.no_grad()
-    def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor, dtype: Optional[torch.dtype] = None):
+    def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor, dtype: Optional[torch.dtype] = None, valid_size=None):
         """SDDH (ref :479-609): descriptors [B, N, 128] of the normalised keypoints knorm [B, N, 2]; rows >= counts[b] are zero.  `dtype`: torch.float32, or
-        torch.float16 = the same values rounded once on store (`lg_aliked_describe_half`); None = conf.descriptor_dtype."""
+        torch.float16 = the same values rounded once on store (`lg_aliked_describe_half`); None = conf.descriptor_dtype.  `valid_size` (ragged batch): `shape` is
+        the canvas and `levels` what `encode(canvas, valid_size)` returned; knorm is normalised in each image's own frame."""
+        sizes = None if valid_size is None else check_sizes(valid_size, shape[0], shape[1:], 8, "valid_size")
+        return self._describe(levels, shape, knorm, counts, dtype, sizes)
+
+    def _describe(self, levels, shape, knorm, counts, dtype, sizes):
         dtype = check_descriptor_dtype(self.conf.descriptor_dtype if dtype is None else dtype)
         bsz, h, w = shape
         n = knorm.shape[1]
@@ -239,28 +284,44 @@ class ALIKED(nn.Module):
         knorm = knorm.contiguous()
         nws = max(lib.lg_aliked_describe_workspace_bytes(bsz * n, self.n_pos), 1)
         work = torch.empty((nws,), device=device, dtype=torch.uint8)
+        sizes = self._sizes(sizes, device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            describe = lib.lg_aliked_describe_half if dtype is torch.float16 else lib.lg_aliked_describe
-            _cabi.check(describe(levels.data_ptr(), bsz, h, w, self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n,
-                                 work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream)))
+            tail = (self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n, work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream))
+            if sizes is None:
+                describe = lib.lg_aliked_describe_half if dtype is torch.float16 else lib.lg_aliked_describe
+                _cabi.check(describe(levels.data_ptr(), bsz, h, w, *tail))
+            else:
+                describe = lib.lg_aliked_describe_ragged_half if dtype is torch.float16 else lib.lg_aliked_describe_ragged
+                _cabi.check(describe(levels.data_ptr(), bsz, h, w, sizes.data_ptr(), *tail))
         return out
 
     # ------------------------------------------------------------------ the reference's forward
     @torch.no_grad()
     def forward(self, data: dict) -> dict:
         """ref :740-760.  Returns keypoints [B, N, 2] (pixel frame), keypoint_scores [B, N], descriptors [B, N, 128] and — extension for ragged
-        batches — num_keypoints [B]; rows beyond an image's count are zero (the reference's torch.stack only handles equal counts)."""
+        batches — num_keypoints [B]; rows beyond an image's count are zero (the reference's torch.stack only handles equal counts).
+
+        Optional `data["valid_size"]` (`[B, 2]` `(w, h)`, integers; validated on the host, ValueError names the offending image; not together with
+        `image_size`): a ragged batch of images of DIFFERENT sizes, image b in the top-left h_b x w_b corner of the canvas `data["image"]`.  Rows
+        < num_keypoints[b] are then bit-identical to the B = 1 call on that crop, keypoints in the image's own frame; absent, the path is exactly the uniform one."""
         for key in self.required_data_keys:
             assert key in data, f"Missing key {key} in data"
         image = data["image"]
+        sizes = None
+        if data.get("valid_size") is not None:
+            if data.get("image_size") is not None:
+                raise ValueError("valid_size and image_size cannot be given together: a ragged batch takes every border from valid_size")
+            sizes = check_sizes(data["valid_size"], image.shape[0], image.shape[-2:], 8, "valid_size")
         self._check_image(image)
         bsz, _, h, w = image.shape
-        scores, levels = self.encode(image)
-        kpts, kscores, knorm, counts = self.detect(scores, data.get("image_size"))
+        if sizes is not None:
+            sizes = sizes_on_device(sizes, image.device)      # one upload for the three stages
+        scores, levels = self._encode(image, sizes)
+        kpts, kscores, knorm, counts = self._detect(scores, data.get("image_size"), sizes)
         nmax = int(counts.cpu().max()) if counts.numel() else 0   # (a copy, not a reduction kernel)
         kpts, kscores, knorm = kpts[:, :nmax].contiguous(), kscores[:, :nmax].contiguous(), knorm[:, :nmax].contiguous()
-        desc = self.describe(levels, (bsz, h, w), knorm, counts)
+        desc = self._describe(levels, (bsz, h, w), knorm, counts, None, sizes)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}
 
     preprocess_conf = {"resize": None}   # NOT the reference's 1024 (aliked.py:631-633): see extract()
@@ -282,3 +343,35 @@ class ALIKED(nn.Module):
             return extracted_to_image_frame(feats, (h, w), scales)
         feats["image_size"] = torch.tensor([[w, h]], dtype=torch.float32, device=img.device)
         return feats
+
+    @torch.no_grad()
+    def extract_batch(self, images: Sequence[torch.Tensor], batch_size: int = 8, order: str = "size", **conf) -> dict:
+        """`extract` for a set of images of DIFFERENT sizes at batched speed: the feature store `collate_features([self.extract(i, **conf) for i in images])`
+        would give, key for key and bit for bit — keypoints [K, N, 2] in each ORIGINAL image's pixel frame, keypoint_scores, descriptors
+        (conf.descriptor_dtype), num_keypoints [K], image_size [K, 2] = original (w, h); N = the largest count, padding rows zero — ready for
+        `LightGlue.match_pairs`.  The contract of `SuperPoint.extract_batch`: each image ([C, H_i, W_i] / [1, C, H_i, W_i], float32 or uint8, C = 1 | 3) is
+        preprocessed with `{**preprocess_conf, **conf}`, the results are grouped by `plan_image_batches` (at most `batch_size` per group), each group is
+        written into the top-left corners of one zeroed canvas and extracted in ONE ragged `forward` (`valid_size`).  A group that mixes 1- and 3-channel
+        images runs on a 3-channel canvas: the first convolution broadcasts one channel to three itself, so the copy changes nothing."""
+        images = list(images)
+        if not images:
+            raise ValueError("extract_batch needs at least one image")
+        prep = ImagePreprocessor(**{**self.preprocess_conf, **conf})
+        ready, scales, resized, original = [], [], [], []
+        for i, img in enumerate(images):
+            if img.dim() == 3:
+                img = img[None]
+            if img.dim() != 4 or img.shape[0] != 1:
+                raise ValueError(f"image {i} must be [C, H, W] or [1, C, H, W], got {tuple(img.shape)}")
+            if img.device.type != "cuda":
+                raise RuntimeError("lightglue_amd.ALIKED runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
+                                   f"Got image {i} on {img.device}.")
+            if img.shape[1] not in (1, 3):
+                raise ValueError(f"image {i} must have 1 or 3 channels, got {img.shape[1]}")
+            h, w = img.shape[-2:]
+            out, scale = prep(img)
+            ready.append(out.to(torch.float32)); scales.append(scale); original.append((h, w))
+            resized.append(tuple(out.shape[-2:]) != (h, w))      # extract maps keypoints back only then
+        device = ready[0].device
+        groups = plan_image_batches([tuple(t.shape[-2:]) for t in ready], batch_size, order=order)
+        return extract_groups(self.forward, ready, scales, resized, original, groups, device)

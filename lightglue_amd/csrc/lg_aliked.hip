@@ -33,27 +33,68 @@ void conv(const float* in, const float* w, const float* bias, float* out, int B,
           const float* in2 = nullptr, const float* w2 = nullptr, int Cin2 = 0) {
     launch_conv(ConvArgs{in, w, bias, in2, w2, out, B, H, W, Cin, Cin2, Cout, taps, act_selu ? ACT_SELU : ACT_NONE, 0, 0}, s);
 }
+// the same on a ragged batch: H, W are the canvas of the level, `padded` the images' padded sizes [B][2] (Wp_b, Hp_b) at full resolution, `shift` the level's
+void conv(const int* padded, int shift, const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout, int taps,
+          int act_selu, hipStream_t s, const float* in2 = nullptr, const float* w2 = nullptr, int Cin2 = 0) {
+    RaggedConvArgs a{};
+    static_cast<ConvArgs&>(a) = ConvArgs{in, w, bias, in2, w2, out, B, H, W, Cin, Cin2, Cout, taps, act_selu ? ACT_SELU : ACT_NONE, 0, 0};
+    a.sizes = padded; a.size_shift = shift;
+    launch_conv(a, s);
+}
 
 // a [rows][K] x [Cout][K] GEMM as a 1 x 1 convolution over a 32-pixel-wide "image" (rows % 32 == 0)
 void gemm(const float* in, const float* w, const float* bias, float* out, int rows, int K, int Cout, int act, hipStream_t s) {
     conv(in, w, bias, out, 1, rows / 32, 32, K, Cout, 1, act, s);
 }
 
+// ==================================================================================================== ragged geometry
+// A ragged batch (lg_aliked_*_ragged): the arrays are a CANVAS, image b its top-left h_b x w_b corner with its OWN InputPadder geometry, its padded frame in the
+// top-left corner of the padded canvas.  Every kernel below is a template over Uniform / Ragged, passed as its LAST argument: addresses and strides come from
+// the canvas (the size arguments the uniform kernel always had), every bound from the image's Frame.  The Uniform instance reads the same arguments for both and
+// keeps the kernel arguments it had (an empty struct follows them).
+struct Uniform {};
+struct Ragged { const int* sizes; int Hc, Wc, shift; };      // [B][2] (w, h), clamped into the canvas Hc x Wc; shift: the pyramid level of this launch
+template <class R> inline constexpr bool ragged = false;
+template <> inline constexpr bool ragged<Ragged> = true;
+
+struct Frame { int h, w, Hp, Wp, pt, pl; };                  // image size, padded size, top / left padding (InputPadder(divis_by = 32): centred)
+__host__ __device__ __forceinline__ Frame frame_of(int h, int w) {
+    const int ph = ((h / 32 + 1) * 32 - h) % 32, pw = ((w / 32 + 1) * 32 - w) % 32;
+    return Frame{h, w, h + ph, w + pw, ph / 2, pw / 2};
+}
+__device__ __forceinline__ Frame frame_of(const Ragged& r, int b) {
+    return frame_of(min(max(r.sizes[2 * b + 1], 1), r.Hc), min(max(r.sizes[2 * b], 1), r.Wc));
+}
+// the padded sizes (Wp_b, Hp_b) RaggedConvArgs takes: multiples of 32, so every level's shift is exact.  thread = image
+__global__ void ak_padded_sizes_kernel(Ragged r, int B, int* padded) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const Frame f = frame_of(r, b);
+    padded[2 * b] = f.Wp; padded[2 * b + 1] = f.Hp;
+}
+
 // ==================================================================================================== encoder helpers (VALU)
 // block1.conv1: image [B][C][H][W] (C = 1 or 3) -> padded [B][Hp][Wp][16], BN folded, SELU.  w: [9 taps][3 cin][16 cout].
-// thread = (padded pixel, 4 output channels)
+// thread = (padded pixel, 4 output channels).  Ragged: H, W, Hp, Wp are the canvas and its padded canvas; the replicate clamp is against the image, the conv's
+// zero padding at the image's padded frame, and nothing is stored outside that frame.
+template <class R>
 __global__ __launch_bounds__(256) void ak_conv_first_kernel(const float* img, int C, int H, int W, int Hp, int Wp, int pt, int pl, const float* w,
-                                                            const float* bias, float* out, int B) {
+                                                            const float* bias, float* out, int B, R rg) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * Hp * Wp * 4;
     if (idx >= total) return;
     const int c4 = (int)(idx & 3);
     const long long pix = idx >> 2;
     const int xp = (int)(pix % Wp), yp = (int)((pix / Wp) % Hp), b = (int)(pix / ((long long)Wp * Hp));
+    Frame fr{H, W, Hp, Wp, pt, pl};
+    if constexpr (ragged<R>) {
+        fr = frame_of(rg, b);
+        if (yp >= fr.Hp || xp >= fr.Wp) return;
+    }
     f32x4 s = *reinterpret_cast<const f32x4*>(bias + c4 * 4);
     for (int t = 0; t < 9; ++t) {
         const int yy = yp + t / 3 - 1, xx = xp + t % 3 - 1;
-        if (yy < 0 || yy >= Hp || xx < 0 || xx >= Wp) continue;                  // the conv's own zero padding of the padded image
-        const int sy = min(max(yy - pt, 0), H - 1), sx = min(max(xx - pl, 0), W - 1);   // replicate padding (InputPadder)
+        if (yy < 0 || yy >= fr.Hp || xx < 0 || xx >= fr.Wp) continue;            // the conv's own zero padding of the padded image
+        const int sy = min(max(yy - fr.pt, 0), fr.h - 1), sx = min(max(xx - fr.pl, 0), fr.w - 1);   // replicate padding (InputPadder)
 #pragma unroll
         for (int ci = 0; ci < 3; ++ci) {
             const float p = img[(((long long)b * C + (C == 1 ? 0 : ci)) * H + sy) * W + sx];
@@ -67,14 +108,20 @@ __global__ __launch_bounds__(256) void ak_conv_first_kernel(const float* img, in
     *reinterpret_cast<f32x4*>(out + pix * 16 + c4 * 4) = s;
 }
 
-// f x f average pooling (nn.AvgPool2d, stride f), NHWC, C % 4 == 0.  thread = (output pixel, 4 channels)
-__global__ __launch_bounds__(256) void ak_pool_kernel(const float* in, float* out, int B, int H, int W, int C, int f) {
+// f x f average pooling (nn.AvgPool2d, stride f), NHWC, C % 4 == 0.  thread = (output pixel, 4 channels).  Ragged: H, W are the canvas of the input level
+// (rg.shift); output pixels outside the image's pooled level are neither computed nor stored
+template <class R>
+__global__ __launch_bounds__(256) void ak_pool_kernel(const float* in, float* out, int B, int H, int W, int C, int f, R rg) {
     const int Ho = H / f, Wo = W / f, C4 = C >> 2;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * Ho * Wo * C4;
     if (idx >= total) return;
     const int c4 = (int)(idx % C4);
     const long long pix = idx / C4;
     const int xo = (int)(pix % Wo), yo = (int)((pix / Wo) % Ho), b = (int)(pix / ((long long)Wo * Ho));
+    if constexpr (ragged<R>) {
+        const Frame fr = frame_of(rg, b);
+        if (yo >= (fr.Hp >> rg.shift) / f || xo >= (fr.Wp >> rg.shift) / f) return;
+    }
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     for (int i = 0; i < f; ++i)
         for (int j = 0; j < f; ++j) s += *reinterpret_cast<const f32x4*>(in + (((long long)b * H + yo * f + i) * W + xo * f + j) * C + c4 * 4);
@@ -84,7 +131,10 @@ __global__ __launch_bounds__(256) void ak_pool_kernel(const float* in, float* ou
 
 // torchvision deform_conv2d sampling (3 x 3, pad 1, stride 1, one offset group, no mask): in [B][h][w][cin], off [B][h][w][18]
 // (tap k = 3i + j: dy = channel 2k, dx = channel 2k + 1, clamped to +-max_off) -> cols [B][h][w][9][cin].  thread = (pixel, tap, 4 channels)
-__global__ __launch_bounds__(256) void ak_deform_gather_kernel(const float* in, const float* off, float* cols, int B, int h, int w, int cin, float max_off) {
+// Ragged: h, w are the canvas of the level (rg.shift) and give the strides; the sample bounds and max_off = max(h_b', w_b') / 4 are the image's level extent
+// (the canvas maximum would clamp the offsets differently), and a pixel outside it returns before any load.
+template <class R>
+__global__ __launch_bounds__(256) void ak_deform_gather_kernel(const float* in, const float* off, float* cols, int B, int h, int w, int cin, float max_off, R rg) {
     const int C4 = cin >> 2;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)B * h * w * 9 * C4;
     if (idx >= total) return;
@@ -93,19 +143,26 @@ __global__ __launch_bounds__(256) void ak_deform_gather_kernel(const float* in, 
     const int k = (int)(rest % 9);
     const long long pix = rest / 9;
     const int x = (int)(pix % w), y = (int)((pix / w) % h), b = (int)(pix / ((long long)w * h));
+    int hb = h, wb = w;      // the image's level extent: every bound
+    if constexpr (ragged<R>) {
+        const Frame fr = frame_of(rg, b);
+        hb = fr.Hp >> rg.shift; wb = fr.Wp >> rg.shift;
+        if (y >= hb || x >= wb) return;
+        max_off = (float)max(hb, wb) / 4.f;
+    }
     const float dy = fminf(fmaxf(off[pix * 18 + 2 * k], -max_off), max_off), dx = fminf(fmaxf(off[pix * 18 + 2 * k + 1], -max_off), max_off);
     const float py = (float)(y - 1 + k / 3) + dy, px = (float)(x - 1 + k % 3) + dx;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!(py <= -1.f || py >= (float)h || px <= -1.f || px >= (float)w)) {
+    if (!(py <= -1.f || py >= (float)hb || px <= -1.f || px >= (float)wb)) {
         const int hl = (int)floorf(py), wl = (int)floorf(px), hh = hl + 1, wh = wl + 1;
         const float lh = py - (float)hl, lw = px - (float)wl, uh = 1.f - lh, uw = 1.f - lw;
         const float* base = in + (long long)b * h * w * cin + c4 * 4;
         auto at = [&](int yy, int xx) { return *reinterpret_cast<const f32x4*>(base + ((long long)yy * w + xx) * cin); };
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const f32x4 v1 = (hl >= 0 && wl >= 0) ? at(hl, wl) : z;
-        const f32x4 v2 = (hl >= 0 && wh <= w - 1) ? at(hl, wh) : z;
-        const f32x4 v3 = (hh <= h - 1 && wl >= 0) ? at(hh, wl) : z;
-        const f32x4 v4 = (hh <= h - 1 && wh <= w - 1) ? at(hh, wh) : z;
+        const f32x4 v2 = (hl >= 0 && wh <= wb - 1) ? at(hl, wh) : z;
+        const f32x4 v3 = (hh <= hb - 1 && wl >= 0) ? at(hh, wl) : z;
+        const f32x4 v4 = (hh <= hb - 1 && wh <= wb - 1) ? at(hh, wh) : z;
         const float w1 = uh * uw, w2 = uh * lw, w3 = lh * uw, w4 = lh * lw;
         v = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
     }
@@ -127,23 +184,39 @@ __device__ __forceinline__ Up up_coord(int dst, int in, int out) {
 struct AkLevels { const float* x[4]; int B, Hp, Wp; };
 __device__ __forceinline__ int lvl_shift(int l) { return l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); }
 
-// score_head.0 (128 -> 8, no bias) + SELU on x1234 built per padded pixel.  w0: [8][128].  out [B][Hp][Wp][8].  thread = padded pixel
-__global__ __launch_bounds__(256) void ak_score_head0_kernel(AkLevels L, const float* w0, float* out) {
+// x1 .. x4 at padded pixel (yp, xp) of image b: level l's map has (L.Hp >> sh) x (L.Wp >> sh) pixels in memory (the canvas), the image's own part of it is
+// (fr.Hp >> sh) x (fr.Wp >> sh), and the align_corners=True scales of up_coord depend on the image's level and full extents.  Uniform: fr.Hp == L.Hp, fr.Wp == L.Wp
+struct LevelTaps { const float* p00; const float* p01; const float* p10; const float* p11; Up uy, ux; };
+__device__ __forceinline__ LevelTaps level_taps(const AkLevels& L, const Frame& fr, int l, int b, int yp, int xp) {
+    const int sh = lvl_shift(l), hc = L.Hp >> sh, wc = L.Wp >> sh;
+    const Up uy = up_coord(yp, fr.Hp >> sh, fr.Hp), ux = up_coord(xp, fr.Wp >> sh, fr.Wp);
+    const float* m = L.x[l] + (long long)b * hc * wc * 32;
+    return LevelTaps{m + ((long long)uy.i0 * wc + ux.i0) * 32, m + ((long long)uy.i0 * wc + ux.i1) * 32, m + ((long long)uy.i1 * wc + ux.i0) * 32,
+                     m + ((long long)uy.i1 * wc + ux.i1) * 32, uy, ux};
+}
+
+// score_head.0 (128 -> 8, no bias) + SELU on x1234 built per padded pixel.  w0: [8][128].  out [B][Hp][Wp][8].  thread = padded pixel (Ragged: of the padded
+// canvas; pixels outside the image's padded frame return)
+template <class R>
+__global__ __launch_bounds__(256) void ak_score_head0_kernel(AkLevels L, const float* w0, float* out, R rg) {
     __shared__ float sw[8 * 128];
     for (int i = threadIdx.x; i < 8 * 128; i += 256) sw[i] = w0[i];
     __syncthreads();
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pix >= (long long)L.B * L.Hp * L.Wp) return;
     const int xp = (int)(pix % L.Wp), yp = (int)((pix / L.Wp) % L.Hp), b = (int)(pix / ((long long)L.Wp * L.Hp));
+    Frame fr{0, 0, L.Hp, L.Wp, 0, 0};
+    if constexpr (ragged<R>) {
+        fr = frame_of(rg, b);
+        if (yp >= fr.Hp || xp >= fr.Wp) return;
+    }
     float acc[8];
 #pragma unroll
     for (int o = 0; o < 8; ++o) acc[o] = 0.f;
     for (int l = 0; l < 4; ++l) {
-        const int sh = lvl_shift(l), h = L.Hp >> sh, w = L.Wp >> sh;
-        const Up uy = up_coord(yp, h, L.Hp), ux = up_coord(xp, w, L.Wp);
-        const float* m = L.x[l] + (long long)b * h * w * 32;
-        const float* p00 = m + ((long long)uy.i0 * w + ux.i0) * 32; const float* p01 = m + ((long long)uy.i0 * w + ux.i1) * 32;
-        const float* p10 = m + ((long long)uy.i1 * w + ux.i0) * 32; const float* p11 = m + ((long long)uy.i1 * w + ux.i1) * 32;
+        const LevelTaps T = level_taps(L, fr, l, b, yp, xp);
+        const Up uy = T.uy, ux = T.ux;
+        const float* p00 = T.p00; const float* p01 = T.p01; const float* p10 = T.p10; const float* p11 = T.p11;
         for (int c4 = 0; c4 < 8; ++c4) {
             f32x4 v;
             if (l == 0) v = *reinterpret_cast<const f32x4*>(p00 + c4 * 4);
@@ -166,20 +239,30 @@ __global__ __launch_bounds__(256) void ak_score_head0_kernel(AkLevels L, const f
 }
 
 // score_head.2 / .4 / .6: 3 x 3, zero pad, no bias, raw weights [COUT][CIN][3][3].  Not FINAL: SELU, [B][Hp][Wp][COUT].  FINAL (COUT = 1): sigmoid
-// and the unpad crop, scores [B][H][W].  thread = output pixel
-template <int CIN, int COUT, bool FINAL>
-__global__ __launch_bounds__(256) void ak_small_conv_kernel(const float* in, const float* w, float* out, int B, int Hp, int Wp, int H, int W, int pt, int pl) {
+// and the unpad crop, scores [B][H][W].  thread = output pixel.  Ragged: Hp, Wp, H, W are the canvases (strides); the zero padding is at the image's padded
+// extent, nothing is stored outside its frame, and FINAL crops with the image's pt, pl and writes 0 for the score pixels outside h_b x w_b (the score canvas is
+// defined everywhere)
+template <int CIN, int COUT, bool FINAL, class R>
+__global__ __launch_bounds__(256) void ak_small_conv_kernel(const float* in, const float* w, float* out, int B, int Hp, int Wp, int H, int W, int pt, int pl, R rg) {
     const int OH = FINAL ? H : Hp, OW = FINAL ? W : Wp;
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pix >= (long long)B * OH * OW) return;
     const int xo = (int)(pix % OW), yo = (int)((pix / OW) % OH), b = (int)(pix / ((long long)OW * OH));
-    const int yp = FINAL ? yo + pt : yo, xp = FINAL ? xo + pl : xo;
+    Frame fr{H, W, Hp, Wp, pt, pl};
+    if constexpr (ragged<R>) {
+        fr = frame_of(rg, b);
+        if (FINAL ? (yo >= fr.h || xo >= fr.w) : (yo >= fr.Hp || xo >= fr.Wp)) {
+            if constexpr (FINAL) out[pix] = 0.f;
+            return;
+        }
+    }
+    const int yp = FINAL ? yo + fr.pt : yo, xp = FINAL ? xo + fr.pl : xo;
     float acc[COUT];
 #pragma unroll
     for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
     for (int t = 0; t < 9; ++t) {
         const int yy = yp + t / 3 - 1, xx = xp + t % 3 - 1;
-        if (yy < 0 || yy >= Hp || xx < 0 || xx >= Wp) continue;
+        if (yy < 0 || yy >= fr.Hp || xx < 0 || xx >= fr.Wp) continue;
         const float* p = in + (((long long)b * Hp + yy) * Wp + xx) * CIN;
 #pragma unroll
         for (int ci = 0; ci < CIN; ++ci) {
@@ -199,12 +282,16 @@ __global__ __launch_bounds__(256) void ak_small_conv_kernel(const float* in, con
 // ==================================================================================================== DKD
 // the threshold of each image (aliked.py:183-193): top-k mode: > 0 (the positive NMS maxima are the candidates); threshold mode: scores_th,
 // unless no pixel of the WHOLE batch passes it (or scores_th <= 0): the image's mean score.  Row counts of a.threshold = scores_th.  grid (B), 256 threads
+// Ragged (a.sizes): a set of independent images, so "no pixel passes" is asked of image b ALONE (each equals its own batch of one), and the mean is over its
+// h_b x w_b pixels: rowsum holds exact zeros below the image, at the thread positions the crop's shorter loop never visits, so the float64 sum is the crop's.
 __global__ __launch_bounds__(256) void ak_decide_kernel(DetectArgs a, int topk, const double* rowsum, float* th) {
     const int b = blockIdx.x;
     __shared__ int sh[4];
     __shared__ double shd[256];
+    const DetectExtent e = detect_extent(a, b);
     int any = 0;
-    for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.row_counts[i];
+    if (a.sizes) { for (int i = threadIdx.x; i < a.H; i += 256) any += a.row_counts[b * a.H + i]; }
+    else { for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.row_counts[i]; }
     any = block_sum_int(any, sh);
     double s = 0.0;
     for (int y = threadIdx.x; y < a.H; y += 256) s += rowsum[b * a.H + y];
@@ -212,7 +299,7 @@ __global__ __launch_bounds__(256) void ak_decide_kernel(DetectArgs a, int topk, 
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) shd[threadIdx.x] += shd[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) {
-        const float mean = (float)(shd[0] / ((double)a.H * a.W));
+        const float mean = (float)(shd[0] / ((double)e.h * e.w));
         th[b] = topk > 0 ? 0.f : ((a.threshold > 0.f && any > 0) ? a.threshold : mean);
     }
 }
@@ -220,7 +307,8 @@ __global__ __launch_bounds__(256) void ak_decide_kernel(DetectArgs a, int topk, 
 struct AkKeypoints { float* kpts; float* kscores; float* knorm; int* counts; };   // [B][cap][2], [B][cap], [B][cap][2], [B]; cap = a.sel_cap
 
 // per output slot: rank (selected_rank when sorted), soft-argmax refinement and the bilinear score (aliked.py:212-247).  Rows >= the image's
-// count are zero-filled.  grid (cap / 256, B)
+// count are zero-filled.  grid (cap / 256, B).  Ragged (a.sizes): the raster index stays y W + x of the canvas; the window's zero padding, the (w - 1, h - 1)
+// factors and the bilinear taps are the image's
 __global__ __launch_bounds__(256) void ak_refine_kernel(DetectArgs a, AkKeypoints k) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     const int n = selected_count(a, b);
@@ -236,7 +324,8 @@ __global__ __launch_bounds__(256) void ak_refine_kernel(DetectArgs a, AkKeypoint
     const int p = a.cand_idx[(long long)b * a.max_candidates + a.sel[ob + j]];
     const int y = p / a.W, x = p - y * a.W, r = a.radius;
     const float* S = a.S + (long long)b * a.H * a.W;
-    auto sv = [&](int yy, int xx) { return (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? S[(long long)yy * a.W + xx] : 0.f; };   // unfold: zero padding
+    const DetectExtent e = detect_extent(a, b);
+    auto sv = [&](int yy, int xx) { return (yy >= 0 && yy < e.h && xx >= 0 && xx < e.w) ? S[(long long)yy * a.W + xx] : 0.f; };   // unfold: zero padding
     float mx = -INFINITY;
     for (int dy = -r; dy <= r; ++dy)
         for (int dx = -r; dx <= r; ++dx) mx = fmaxf(mx, sv(y + dy, x + dx));
@@ -247,7 +336,7 @@ __global__ __launch_bounds__(256) void ak_refine_kernel(DetectArgs a, AkKeypoint
             se += e; sx = __builtin_fmaf(e, (float)dx, sx); sy = __builtin_fmaf(e, (float)dy, sy);
         }
     const float rx = __fdiv_rn(sx, se), ry = __fdiv_rn(sy, se);
-    const float wm1 = (float)(a.W - 1), hm1 = (float)(a.H - 1);
+    const float wm1 = (float)(e.w - 1), hm1 = (float)(e.h - 1);
     // (xy_nms + residual) / wh * 2 - 1, each step rounded like the reference's tensor ops (no contraction)
     const float kx = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)x, rx), wm1), 2.f), 1.f);
     const float ky = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)y, ry), hm1), 2.f), 1.f);
@@ -266,16 +355,17 @@ __global__ __launch_bounds__(256) void ak_refine_kernel(DetectArgs a, AkKeypoint
 }
 
 // ==================================================================================================== SDDH
-// one lane = 2 channels of x1234 at padded pixel (yp, xp): lanes 0-15 x1, 16-31 x2 (upsampled), 32-47 x3, 48-63 x4; L2-normalised over the wave
-__device__ __forceinline__ f32x2 x1234_norm(const AkLevels& L, int b, int yp, int xp, int lane) {
-    const int l = lane >> 4, c = (lane & 15) * 2, sh = lvl_shift(l), h = L.Hp >> sh, w = L.Wp >> sh;
-    const float* m = L.x[l] + (long long)b * h * w * 32 + c;
+// one lane = 2 channels of x1234 at padded pixel (yp, xp) of image b's frame `fr`: lanes 0-15 x1, 16-31 x2 (upsampled), 32-47 x3, 48-63 x4; L2-normalised
+// over the wave
+__device__ __forceinline__ f32x2 x1234_norm(const AkLevels& L, const Frame& fr, int b, int yp, int xp, int lane) {
+    const int l = lane >> 4, c = (lane & 15) * 2;
+    const LevelTaps T = level_taps(L, fr, l, b, yp, xp);
     f32x2 v;
-    if (l == 0) v = *reinterpret_cast<const f32x2*>(m + ((long long)yp * w + xp) * 32);
+    if (l == 0) v = *reinterpret_cast<const f32x2*>(T.p00 + c);
     else {
-        const Up uy = up_coord(yp, h, L.Hp), ux = up_coord(xp, w, L.Wp);
-        const f32x2 a00 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i0 * w + ux.i0) * 32), a01 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i0 * w + ux.i1) * 32);
-        const f32x2 a10 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i1 * w + ux.i0) * 32), a11 = *reinterpret_cast<const f32x2*>(m + ((long long)uy.i1 * w + ux.i1) * 32);
+        const Up uy = T.uy, ux = T.ux;
+        const f32x2 a00 = *reinterpret_cast<const f32x2*>(T.p00 + c), a01 = *reinterpret_cast<const f32x2*>(T.p01 + c);
+        const f32x2 a10 = *reinterpret_cast<const f32x2*>(T.p10 + c), a11 = *reinterpret_cast<const f32x2*>(T.p11 + c);
         v = uy.l0 * (ux.l0 * a00 + ux.l1 * a01) + uy.l1 * (ux.l0 * a10 + ux.l1 * a11);
     }
     const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1]));
@@ -291,37 +381,49 @@ struct AkDescribe {
     const int* counts; float* out;
     int out_f16;                           // != 0: `out` holds binary16 rows (lg_aliked_describe_half): the fp32 result rounded once, to nearest even, on store
 };
+// Ragged: H, W and L.Hp, L.Wp are the canvases (the level maps' strides), pt / pl unused; image b's frame gives the grid denormalisation, the pad offset into
+// the level maps, the upsampling coordinates and every tap bound.  A struct of its own for the ragged instances, as RaggedConvArgs is (lg_extract.h)
+struct AkDescribeRagged : AkDescribe { Ragged rg; };
+template <> inline constexpr bool ragged<AkDescribeRagged> = true;
+template <class D> __device__ __forceinline__ Frame frame_of_row(const D& d, int b) {
+    if constexpr (ragged<D>) return frame_of(d.rg, b);
+    else return Frame{d.H, d.W, d.L.Hp, d.L.Wp, d.pt, d.pl};
+}
 
-__device__ __forceinline__ void kp_pixel(const AkDescribe& d, int row, float& kw, float& kh) {   // (kpts / 2 + 0.5) * wh  (aliked.py:542)
+__device__ __forceinline__ void kp_pixel(const AkDescribe& d, const Frame& fr, int row, float& kw, float& kh) {   // (kpts / 2 + 0.5) * wh  (aliked.py:542)
     const float* k = d.knorm + 2LL * row;
-    kw = __fmul_rn(__fadd_rn(__fdiv_rn(k[0], 2.f), 0.5f), (float)(d.W - 1));
-    kh = __fmul_rn(__fadd_rn(__fdiv_rn(k[1], 2.f), 0.5f), (float)(d.H - 1));
+    kw = __fmul_rn(__fadd_rn(__fdiv_rn(k[0], 2.f), 0.5f), (float)(fr.w - 1));
+    kh = __fmul_rn(__fadd_rn(__fdiv_rn(k[1], 2.f), 0.5f), (float)(fr.h - 1));
 }
 
 // get_patches (aliked.py:48-64) of the normalised x1234 map: patch [row][tap = 3 dy + dx][128].  grid (rows), 4 waves: wave w takes taps w, w + 4, w + 8
-__global__ __launch_bounds__(256) void ak_patch_kernel(AkDescribe d) {
+template <class D>
+__global__ __launch_bounds__(256) void ak_patch_kernel(D d) {
     const int row = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, b = row / d.N;
+    const Frame fr = frame_of_row(d, b);
     float kw, kh;
-    kp_pixel(d, row, kw, kh);
+    kp_pixel(d, fr, row, kw, kh);
     const long long lw = (long long)kw, lh = (long long)kh;                      // .long()
     int cx = (int)(long long)((float)lw - 1.5f + 1.f), cy = (int)(long long)((float)lh - 1.5f + 1.f);
-    cx = min(max(cx, 0), d.W - 1 - 3); cy = min(max(cy, 0), d.H - 1 - 3);
+    cx = min(max(cx, 0), fr.w - 1 - 3); cy = min(max(cy, 0), fr.h - 1 - 3);
     for (int t = wv; t < 9; t += 4) {
-        const f32x2 v = x1234_norm(d.L, b, cy + t / 3 + d.pt, cx + t % 3 + d.pl, lane);
+        const f32x2 v = x1234_norm(d.L, fr, b, cy + t / 3 + fr.pt, cx + t % 3 + fr.pl, lane);
         *reinterpret_cast<f32x2*>(d.patch + ((long long)row * 9 + t) * 128 + lane * 2) = v;
     }
 }
 
 // offset_conv.2 (1 x 1, bias) on the SELU'd first conv, clamp, sample positions in map pixels (grid_sample's un-normalisation).  thread = keypoint row
-__global__ __launch_bounds__(256) void ak_offsets_kernel(AkDescribe d, int rows) {
+template <class D>
+__global__ __launch_bounds__(256) void ak_offsets_kernel(D d, int rows) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     const int C2 = 2 * d.np;
     const float* o1 = d.off1 + (long long)row * C2;
-    const float mo = (float)max(d.H, d.W) / 4.f;
+    const Frame fr = frame_of_row(d, row / d.N);
+    const float mo = (float)max(fr.h, fr.w) / 4.f;
     float kw, kh;
-    kp_pixel(d, row, kw, kh);
-    const float wm1 = (float)(d.W - 1), hm1 = (float)(d.H - 1);
+    kp_pixel(d, fr, row, kw, kh);
+    const float wm1 = (float)(fr.w - 1), hm1 = (float)(fr.h - 1);
     for (int p = 0; p < d.np; ++p) {
         float ox = d.b_off2[p], oy = d.b_off2[d.np + p];
         for (int i = 0; i < C2; ++i) {
@@ -337,10 +439,12 @@ __global__ __launch_bounds__(256) void ak_offsets_kernel(AkDescribe d, int rows)
 }
 
 // bilinear sample (align_corners=True, zeros outside the unpadded map) of the normalised x1234 at every position: feat [row * np + p][128].  wave = one sample
-__global__ __launch_bounds__(256) void ak_sample_kernel(AkDescribe d, int samples) {
+template <class D>
+__global__ __launch_bounds__(256) void ak_sample_kernel(D d, int samples) {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= samples) return;
     const int b = (s / d.np) / d.N;
+    const Frame fr = frame_of_row(d, b);
     const float ix = d.spos[2LL * s], iy = d.spos[2LL * s + 1];
     const float fx = floorf(ix), fy = floorf(iy);
     const int x0 = (int)fx, y0 = (int)fy;
@@ -350,8 +454,8 @@ __global__ __launch_bounds__(256) void ak_sample_kernel(AkDescribe d, int sample
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int x = x0 + (k & 1), y = y0 + (k >> 1);
-        if (x >= 0 && x < d.W && y >= 0 && y < d.H) {      // wave-uniform
-            const f32x2 v = x1234_norm(d.L, b, y + d.pt, x + d.pl, lane);
+        if (x >= 0 && x < fr.w && y >= 0 && y < fr.h) {      // wave-uniform
+            const f32x2 v = x1234_norm(d.L, fr, b, y + fr.pt, x + fr.pl, lane);
             acc += wgt[k] * v;
         }
     }
@@ -419,7 +523,7 @@ LevelLayout level_layout(int B, int h, int w) {
     return L;
 }
 
-struct EncodeLayout { long long full_a, full_b, p2, q2, r2, p3, off, cols, t3, r3, p4, t4, r4; long long total; };
+struct EncodeLayout { long long full_a, full_b, p2, q2, r2, p3, off, cols, t3, r3, p4, t4, r4, padded; long long total; };
 EncodeLayout encode_layout(int B, int h, int w) {
     const Dims D = dims_of(h, w);
     const long long f = (long long)B * D.Hp * D.Wp, f2 = f / 4, f8 = f / 64, f32 = f / 1024;
@@ -428,6 +532,7 @@ EncodeLayout encode_layout(int B, int h, int w) {
     E.p2 = bp.take(f2 * 16 * 4); E.q2 = bp.take(f2 * 32 * 4); E.r2 = bp.take(f2 * 32 * 4);
     E.p3 = bp.take(f8 * 32 * 4); E.off = bp.take(f8 * 18 * 4); E.cols = bp.take(f8 * 9 * 64 * 4); E.t3 = bp.take(f8 * 64 * 4); E.r3 = bp.take(f8 * 64 * 4);
     E.p4 = bp.take(f32 * 64 * 4); E.t4 = bp.take(f32 * 128 * 4); E.r4 = bp.take(f32 * 128 * 4);
+    E.padded = bp.take((long long)B * 2 * 4);                         // ragged: the padded sizes (Wp_b, Hp_b) of RaggedConvArgs
     E.total = bp.used;
     return E;
 }
@@ -515,12 +620,17 @@ int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n
     return encode_layout(batch, h, w).total;
 }
 
-int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
-                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+}  // extern "C"
+
+// lg_aliked_encode / lg_aliked_encode_ragged: one sequence of launches; with `sizes` every launch is the Ragged instance and h, w are the canvas
+template <class R>
+static int aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
+                         void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+    constexpr bool RG = ragged<R>;
     if (int rc = check_model(n_pos)) return rc;
     if (int rc = check_size(batch, h, w)) return rc;
     if (channels != 1 && channels != 3) return set_error(LG_ERR_INVALID, "ALIKED: images of 1 or 3 channels");
-    if (!image || !packed || !levels || !workspace || !scores) return set_error(LG_ERR_INVALID, "null pointer");
+    if (!image || !packed || !levels || !workspace || !scores || (RG && !sizes)) return set_error(LG_ERR_INVALID, "null pointer");
     if (workspace_bytes < encode_layout(batch, h, w).total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_workspace_bytes)");
     const PackLayout P = pack_layout(n_pos);
     const EncodeLayout E = encode_layout(batch, h, w);
@@ -535,43 +645,59 @@ int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_
     for (int l = 0; l < 4; ++l) x[l] = reinterpret_cast<float*>(lv + LL.x[l]);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const long long f = (long long)B * Hp * Wp;
+    // the geometry argument of every launch at pyramid shift `sh`, and the convolution on that level
+    int* padded = reinterpret_cast<int*>(ws + E.padded);
+    auto G = [&](int sh) { if constexpr (RG) return Ragged{sizes, h, w, sh}; else return Uniform{}; };
+    if constexpr (RG) hipLaunchKernelGGL(ak_padded_sizes_kernel, dim3(blocks(B)), dim3(256), 0, s, G(0), B, padded);
+    auto conv = [&](int sh, auto... args) { if constexpr (RG) lg::conv(padded, sh, args...); else lg::conv(args...); };
     // ---- block1 (ConvBlock) at full resolution
-    hipLaunchKernelGGL(ak_conv_first_kernel, dim3(blocks(f * 4)), dim3(256), 0, s, image, channels, h, w, Hp, Wp, D.pt, D.pl, p + P.b1c1_w, p + P.b1c1_b, W_(E.full_a), B);
-    conv(W_(E.full_a), p + P.b1c2_w, p + P.b1c2_b, W_(E.full_b), B, Hp, Wp, 16, 16, 9, 1, s);
-    conv(W_(E.full_b), p + P.cv[0], nullptr, x[0], B, Hp, Wp, 16, 32, 1, 1, s);                  // conv1 + SELU -> x1
+    hipLaunchKernelGGL(ak_conv_first_kernel<R>, dim3(blocks(f * 4)), dim3(256), 0, s, image, channels, h, w, Hp, Wp, D.pt, D.pl, p + P.b1c1_w, p + P.b1c1_b, W_(E.full_a), B, G(0));
+    conv(0, W_(E.full_a), p + P.b1c2_w, p + P.b1c2_b, W_(E.full_b), B, Hp, Wp, 16, 16, 9, 1, s);
+    conv(0, W_(E.full_b), p + P.cv[0], nullptr, x[0], B, Hp, Wp, 16, 32, 1, 1, s);                  // conv1 + SELU -> x1
     // ---- block2 (ResBlock) at 1/2
-    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 4 * 4)), dim3(256), 0, s, W_(E.full_b), W_(E.p2), B, Hp, Wp, 16, 2);
-    conv(W_(E.p2), p + P.b2c1_w, p + P.b2c1_b, W_(E.q2), B, H2, W2, 16, 32, 9, 1, s);
-    conv(W_(E.q2), p + P.b2c2_w, p + P.b2c2_b, W_(E.r2), B, H2, W2, 32, 32, 9, 1, s, W_(E.p2), p + P.b2ds_w, 16);
-    conv(W_(E.r2), p + P.cv[1], nullptr, x[1], B, H2, W2, 32, 32, 1, 1, s);                      // conv2 -> x2
+    hipLaunchKernelGGL(ak_pool_kernel<R>, dim3(blocks(f / 4 * 4)), dim3(256), 0, s, W_(E.full_b), W_(E.p2), B, Hp, Wp, 16, 2, G(0));
+    conv(1, W_(E.p2), p + P.b2c1_w, p + P.b2c1_b, W_(E.q2), B, H2, W2, 16, 32, 9, 1, s);
+    conv(1, W_(E.q2), p + P.b2c2_w, p + P.b2c2_b, W_(E.r2), B, H2, W2, 32, 32, 9, 1, s, W_(E.p2), p + P.b2ds_w, 16);
+    conv(1, W_(E.r2), p + P.cv[1], nullptr, x[1], B, H2, W2, 32, 32, 1, 1, s);                      // conv2 -> x2
     // ---- blocks 3 and 4 (deformable ResBlocks) at 1/8 and 1/32
-    auto dcn_block = [&](const PackLayout::Dcn& Dc, const float* in, float* t, float* out, int hh, int ww, int ci, int co) {
-        const float mo = (float)max(hh, ww) / 4.f;
+    auto dcn_block = [&](const PackLayout::Dcn& Dc, const float* in, float* t, float* out, int hh, int ww, int sh, int ci, int co) {
+        const float mo = (float)max(hh, ww) / 4.f;      // (ragged: the kernel takes it from the image's level extent)
         const long long px = (long long)B * hh * ww;
-        conv(in, p + Dc.off1_w, p + Dc.off1_b, W_(E.off), B, hh, ww, ci, 18, 9, 0, s);
-        hipLaunchKernelGGL(ak_deform_gather_kernel, dim3(blocks(px * 9 * (ci / 4))), dim3(256), 0, s, in, W_(E.off), W_(E.cols), B, hh, ww, ci, mo);
-        conv(W_(E.cols), p + Dc.reg1_w, p + Dc.reg1_b, t, B, hh, ww, 9 * ci, co, 1, 1, s);
-        conv(t, p + Dc.off2_w, p + Dc.off2_b, W_(E.off), B, hh, ww, co, 18, 9, 0, s);
-        hipLaunchKernelGGL(ak_deform_gather_kernel, dim3(blocks(px * 9 * (co / 4))), dim3(256), 0, s, t, W_(E.off), W_(E.cols), B, hh, ww, co, mo);
-        conv(W_(E.cols), p + Dc.reg2_w, p + Dc.reg2_b, out, B, hh, ww, 9 * co, co, 1, 1, s, in, p + Dc.ds_w, ci);
+        conv(sh, in, p + Dc.off1_w, p + Dc.off1_b, W_(E.off), B, hh, ww, ci, 18, 9, 0, s);
+        hipLaunchKernelGGL(ak_deform_gather_kernel<R>, dim3(blocks(px * 9 * (ci / 4))), dim3(256), 0, s, in, W_(E.off), W_(E.cols), B, hh, ww, ci, mo, G(sh));
+        conv(sh, W_(E.cols), p + Dc.reg1_w, p + Dc.reg1_b, t, B, hh, ww, 9 * ci, co, 1, 1, s);
+        conv(sh, t, p + Dc.off2_w, p + Dc.off2_b, W_(E.off), B, hh, ww, co, 18, 9, 0, s);
+        hipLaunchKernelGGL(ak_deform_gather_kernel<R>, dim3(blocks(px * 9 * (co / 4))), dim3(256), 0, s, t, W_(E.off), W_(E.cols), B, hh, ww, co, mo, G(sh));
+        conv(sh, W_(E.cols), p + Dc.reg2_w, p + Dc.reg2_b, out, B, hh, ww, 9 * co, co, 1, 1, s, in, p + Dc.ds_w, ci);
     };
-    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 64 * 8)), dim3(256), 0, s, W_(E.r2), W_(E.p3), B, H2, W2, 32, 4);
-    dcn_block(P.b3, W_(E.p3), W_(E.t3), W_(E.r3), H8, W8, 32, 64);
-    conv(W_(E.r3), p + P.cv[2], nullptr, x[2], B, H8, W8, 64, 32, 1, 1, s);                      // conv3 -> x3
-    hipLaunchKernelGGL(ak_pool_kernel, dim3(blocks(f / 1024 * 16)), dim3(256), 0, s, W_(E.r3), W_(E.p4), B, H8, W8, 64, 4);
-    dcn_block(P.b4, W_(E.p4), W_(E.t4), W_(E.r4), H32, W32, 64, 128);
-    conv(W_(E.r4), p + P.cv[3], nullptr, x[3], B, H32, W32, 128, 32, 1, 1, s);                  // conv4 -> x4
+    hipLaunchKernelGGL(ak_pool_kernel<R>, dim3(blocks(f / 64 * 8)), dim3(256), 0, s, W_(E.r2), W_(E.p3), B, H2, W2, 32, 4, G(1));
+    dcn_block(P.b3, W_(E.p3), W_(E.t3), W_(E.r3), H8, W8, 3, 32, 64);
+    conv(3, W_(E.r3), p + P.cv[2], nullptr, x[2], B, H8, W8, 64, 32, 1, 1, s);                      // conv3 -> x3
+    hipLaunchKernelGGL(ak_pool_kernel<R>, dim3(blocks(f / 1024 * 16)), dim3(256), 0, s, W_(E.r3), W_(E.p4), B, H8, W8, 64, 4, G(3));
+    dcn_block(P.b4, W_(E.p4), W_(E.t4), W_(E.r4), H32, W32, 5, 64, 128);
+    conv(5, W_(E.r4), p + P.cv[3], nullptr, x[3], B, H32, W32, 128, 32, 1, 1, s);                  // conv4 -> x4
     // ---- score head on x1234 (never materialised) -> scores [B][h][w]
     AkLevels L{{x[0], x[1], x[2], x[3]}, B, Hp, Wp};
     float* s8 = W_(E.full_a);                  // [f][8]
     float* s4a = W_(E.full_b);                 // [f][4]
     float* s4b = W_(E.full_a) + f * 8;         // [f][4]
-    hipLaunchKernelGGL(ak_score_head0_kernel, dim3(blocks(f)), dim3(256), 0, s, L, p + P.sh0, s8);
-    hipLaunchKernelGGL((ak_small_conv_kernel<8, 4, false>), dim3(blocks(f)), dim3(256), 0, s, s8, p + P.sh2, s4a, B, Hp, Wp, h, w, D.pt, D.pl);
-    hipLaunchKernelGGL((ak_small_conv_kernel<4, 4, false>), dim3(blocks(f)), dim3(256), 0, s, s4a, p + P.sh4, s4b, B, Hp, Wp, h, w, D.pt, D.pl);
-    hipLaunchKernelGGL((ak_small_conv_kernel<4, 1, true>), dim3(blocks((long long)B * h * w)), dim3(256), 0, s, s4b, p + P.sh6, scores, B, Hp, Wp, h, w, D.pt, D.pl);
+    hipLaunchKernelGGL(ak_score_head0_kernel<R>, dim3(blocks(f)), dim3(256), 0, s, L, p + P.sh0, s8, G(0));
+    hipLaunchKernelGGL((ak_small_conv_kernel<8, 4, false, R>), dim3(blocks(f)), dim3(256), 0, s, s8, p + P.sh2, s4a, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
+    hipLaunchKernelGGL((ak_small_conv_kernel<4, 4, false, R>), dim3(blocks(f)), dim3(256), 0, s, s4a, p + P.sh4, s4b, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
+    hipLaunchKernelGGL((ak_small_conv_kernel<4, 1, true, R>), dim3(blocks((long long)B * h * w)), dim3(256), 0, s, s4b, p + P.sh6, scores, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
+}
+
+extern "C" {
+
+int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
+                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+    return aliked_encode<Uniform>(image, batch, channels, h, w, nullptr, n_pos, packed, levels, workspace, workspace_bytes, scores, hip_stream);
+}
+int lg_aliked_encode_ragged(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
+                            void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+    return aliked_encode<Ragged>(image, batch, channels, h, w, sizes, n_pos, packed, levels, workspace, workspace_bytes, scores, hip_stream);
 }
 
 int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity) {
@@ -579,9 +705,10 @@ int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, in
     return detect_layout(batch, h, w, h * w, capacity, true).total;
 }
 
-int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th, int32_t top_k,
-                     int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, float* kp_norm,
-                     int32_t* counts, void* hip_stream) {
+// lg_aliked_detect / lg_aliked_detect_ragged: one path; `sizes` (DetectArgs::sizes) makes every bound the image's
+static int aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius, float scores_th,
+                         int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores,
+                         float* kp_norm, int32_t* counts, void* hip_stream) {
     if (int rc = check_size(batch, h, w)) return rc;
     if (nms_radius < 1 || nms_radius > 8) return set_error(LG_ERR_INVALID, "ALIKED: nms_radius must be in [1, 8]");
     if (n_limit > 20000 || top_k > 20000) return set_error(LG_ERR_INVALID, "ALIKED: n_limit / top_k above 20000 (ALIKED.n_limit_max)");
@@ -593,7 +720,7 @@ int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, c
     if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_detect_workspace_bytes)");
     DetectArgs a{};
     detect_bind(a, DL, workspace);
-    a.S = scores; a.B = batch; a.H = h; a.W = w; a.radius = nms_radius;
+    a.S = scores; a.B = batch; a.H = h; a.W = w; a.radius = nms_radius; a.sizes = sizes;
     a.border = nms_radius; a.image_size = image_size; a.border_value = 0.f; a.threshold = scores_th;
     a.max_candidates = h * w; a.K = K; a.sort_always = top_k > 0; a.sel_cap = capacity;
     double* rowsum = reinterpret_cast<double*>(static_cast<char*>(workspace) + DL.rowsum);
@@ -609,20 +736,36 @@ int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, c
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
 }
+int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th, int32_t top_k,
+                     int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, float* kp_norm,
+                     int32_t* counts, void* hip_stream) {
+    return aliked_detect(scores, batch, h, w, nullptr, image_size, nms_radius, scores_th, top_k, n_limit, capacity, workspace, workspace_bytes, keypoints, kp_scores,
+                         kp_norm, counts, hip_stream);
+}
+int lg_aliked_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius,
+                            float scores_th, int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
+                            float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream) {
+    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
+    return aliked_detect(scores, batch, h, w, sizes, image_size, nms_radius, scores_th, top_k, n_limit, capacity, workspace, workspace_bytes, keypoints, kp_scores,
+                         kp_norm, counts, hip_stream);
+}
 
 int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos) {
     if (check_model(n_pos) != LG_OK || rows < 1) return 0;
     return describe_layout(rows, n_pos).total;
 }
 
-// lg_aliked_describe / lg_aliked_describe_half: one path, the element type of `descriptors` decided at the last kernel's store
-static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
+}  // extern "C"
+
+// lg_aliked_describe / lg_aliked_describe_half and their ragged forms: one path, the element type of `descriptors` decided at the last kernel's store
+template <class DA>
+static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
                            int32_t n, void* workspace, int64_t workspace_bytes, void* descriptors, bool out_f16, void* hip_stream) {
     if (int rc = check_model(n_pos)) return rc;
     if (int rc = check_size(batch, h, w)) return rc;
     if (n < 1) return LG_OK;
     if (n > 20000) return set_error(LG_ERR_INVALID, "ALIKED: more than 20000 keypoints per image");
-    if (!levels || !packed || !kp_norm || !counts || !workspace || !descriptors) return set_error(LG_ERR_INVALID, "null pointer");
+    if (!levels || !packed || !kp_norm || !counts || !workspace || !descriptors || (ragged<DA> && !sizes)) return set_error(LG_ERR_INVALID, "null pointer");
     const int rows = batch * n;
     const DescribeLayout DL = describe_layout(rows, n_pos);
     if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_describe_workspace_bytes)");
@@ -632,7 +775,8 @@ static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t
     const float* p = static_cast<const float*>(packed);
     const char* lv = static_cast<const char*>(levels);
     char* ws = static_cast<char*>(workspace);
-    AkDescribe d{};
+    DA d{};
+    if constexpr (ragged<DA>) d.rg = Ragged{sizes, h, w, 0};
     for (int l = 0; l < 4; ++l) d.L.x[l] = reinterpret_cast<const float*>(lv + LL.x[l]);
     d.L.B = batch; d.L.Hp = D.Hp; d.L.Wp = D.Wp;
     d.H = h; d.W = w; d.pt = D.pt; d.pl = D.pl; d.N = n; d.np = n_pos; d.knorm = kp_norm;
@@ -641,25 +785,37 @@ static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t
     d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = counts; d.out = static_cast<float*>(descriptors); d.out_f16 = out_f16 ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int rp = DL.rows_pad;
-    hipLaunchKernelGGL(ak_patch_kernel, dim3(rows), dim3(256), 0, s, d);
+    hipLaunchKernelGGL(ak_patch_kernel<DA>, dim3(rows), dim3(256), 0, s, d);
     if (rp > rows) (void)hipMemsetAsync(d.patch + (long long)rows * 9 * 128, 0, (size_t)(rp - rows) * 9 * 128 * 4, s);   // GEMM pad rows: keep them finite
     gemm(d.patch, p + P.so0_w, p + P.so0_b, d.off1, rp, 9 * 128, 2 * n_pos, 1, s);            // offset_conv.0 + SELU
-    hipLaunchKernelGGL(ak_offsets_kernel, dim3(blocks(rows)), dim3(256), 0, s, d, rows);
-    hipLaunchKernelGGL(ak_sample_kernel, dim3(blocks((long long)rows * n_pos, 4)), dim3(256), 0, s, d, rows * n_pos);
+    hipLaunchKernelGGL(ak_offsets_kernel<DA>, dim3(blocks(rows)), dim3(256), 0, s, d, rows);
+    hipLaunchKernelGGL(ak_sample_kernel<DA>, dim3(blocks((long long)rows * n_pos, 4)), dim3(256), 0, s, d, rows * n_pos);
     if (rp > rows) (void)hipMemsetAsync(d.feat + (long long)rows * n_pos * 128, 0, (size_t)(rp - rows) * n_pos * 128 * 4, s);
     gemm(d.feat, p + P.sf, nullptr, d.sf, rp * n_pos, 128, 128, 1, s);                        // sf_conv + SELU
     gemm(d.sf, p + P.agg, nullptr, d.draw, rp, n_pos * 128, 128, 0, s);                      // einsum("ncp,pcd->nd")
-    hipLaunchKernelGGL(ak_desc_norm_kernel, dim3(blocks(rows, 4)), dim3(256), 0, s, d, rows);
+    hipLaunchKernelGGL(ak_desc_norm_kernel, dim3(blocks(rows, 4)), dim3(256), 0, s, static_cast<const AkDescribe&>(d), rows);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
 }
+
+extern "C" {
+
 int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
                        int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
-    return aliked_describe(levels, batch, h, w, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
+    return aliked_describe<AkDescribe>(levels, batch, h, w, nullptr, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
 }
 int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
                            int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream) {
-    return aliked_describe(levels, batch, h, w, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
+    return aliked_describe<AkDescribe>(levels, batch, h, w, nullptr, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
+}
+int lg_aliked_describe_ragged(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm,
+                              const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
+    return aliked_describe<AkDescribeRagged>(levels, batch, h, w, sizes, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
+}
+int lg_aliked_describe_ragged_half(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
+                                   const float* kp_norm, const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors,
+                                   void* hip_stream) {
+    return aliked_describe<AkDescribeRagged>(levels, batch, h, w, sizes, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
 }
 
 }  // extern "C"

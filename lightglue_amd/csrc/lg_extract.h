@@ -145,7 +145,7 @@ DetectLayout detect_layout(int B, int H, int W, int max_candidates, int sel_cap,
 void detect_bind(DetectArgs& a, const DetectLayout& L, void* ws);   // the workspace pointers of `a`
 
 void launch_nms(const DetectArgs& a, hipStream_t s);                                         // S -> nms (mask_a, mask_b as scratch)
-void launch_row_count(const DetectArgs& a, const float* th, double* rowsum, hipStream_t s);  // rowsum (optional): [B][H] row sums of S
+void launch_row_count(const DetectArgs& a, const float* th, double* rowsum, hipStream_t s);  // rowsum (optional): [B][H] row sums of S over the image's own columns, 0 below the image
 void launch_compact(const DetectArgs& a, const float* th, hipStream_t s);
 void launch_select(const DetectArgs& a, hipStream_t s);
 

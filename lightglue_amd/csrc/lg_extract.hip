@@ -226,15 +226,18 @@ __device__ __forceinline__ float detect_value(const DetectArgs& a, const DetectE
 }
 
 // per image row: the pixels above the threshold (th[b] when th is set, else a.threshold) and, when rowsum is set, the row sum of S.  grid (H, B)
+// The sum is over the image's own columns and rows: a pixel outside its extent adds an exact 0 at the thread and tree position it has, so the float64
+// sum of a ragged row is bit for bit the one of the crop (a shorter strided loop and the same tree), and a row below the image sums to 0.
 __global__ __launch_bounds__(256) void row_count_kernel(DetectArgs a, const float* th, double* rowsum) {
     const int y = blockIdx.x, b = blockIdx.y;
     const long long row = ((long long)b * a.H + y) * a.W;
     const float t = th ? th[b] : a.threshold;
     const DetectExtent e = detect_extent(a, b);
+    const int wsum = y < e.h ? e.w : 0;
     int cnt = 0; double sum = 0.0;
     for (int x = threadIdx.x; x < a.W; x += 256) {
         cnt += detect_value(a, e, b, y, x) > t;
-        if (rowsum) sum += (double)a.S[row + x];
+        if (rowsum && x < wsum) sum += (double)a.S[row + x];
     }
     __shared__ int sh[4];
     cnt = block_sum_int(cnt, sh);

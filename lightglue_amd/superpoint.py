@@ -24,13 +24,14 @@ from .preprocess import ImagePreprocessor
 from .superpoint_head import _detect, _run as _descriptor_run, check_descriptor_dtype, check_sizes, sizes_on_device
 
 def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8, max_workspace_bytes: Optional[int] = None,
-                       order: str = "size") -> List[Tuple[List[int], Tuple[int, int]]]:
+                       order: str = "size", workspace_bytes=None) -> List[Tuple[List[int], Tuple[int, int]]]:
     """Group images of sizes `sizes_hw[i] = (h_i, w_i)` into ragged batches for `SuperPoint.extract_batch`: a list of `(indices, (Hc, Wc))`
     that covers every index exactly once, with at most `batch_size` indices per group and the group's canvas = the elementwise maximum of
     its sizes.  Pure host arithmetic and deterministic.  `order="size"` (default) walks the images sorted by (h, w) descending, ties by index,
     so that equal and similar sizes share a canvas and little of it is padding; `order="input"` keeps the given order.  A group is closed when
     it is full or when the next image would push the conv stack's workspace, `lg_sp_encode_workspace_bytes(n, Hc, Wc)`, above
-    `max_workspace_bytes`; a single image that alone exceeds the cap raises ValueError."""
+    `max_workspace_bytes`; a single image that alone exceeds the cap raises ValueError.  `workspace_bytes`: the byte function `(n, Hc, Wc) -> int` the cap
+    is measured with, for another extractor (`ALIKED.extract_batch` passes its own encoder's); None = SuperPoint's, as above."""
     if batch_size < 1:
         raise ValueError("batch_size must be at least 1")
     if order not in ("size", "input"):
@@ -38,8 +39,8 @@ def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8,
     sizes = [(int(h), int(w)) for h, w in sizes_hw]
     for i, (h, w) in enumerate(sizes):
         if h < 8 or w < 8:
-            raise ValueError(f"image {i} is {h} x {w}: SuperPoint needs at least 8 x 8")
-    nbytes = _cabi.load().lg_sp_encode_workspace_bytes if max_workspace_bytes is not None else None
+            raise ValueError(f"image {i} is {h} x {w}: the extractors need at least 8 x 8")
+    nbytes = (workspace_bytes or _cabi.load().lg_sp_encode_workspace_bytes) if max_workspace_bytes is not None else None
     todo = sorted(range(len(sizes)), key=lambda i: (-sizes[i][0], -sizes[i][1], i)) if order == "size" else list(range(len(sizes)))
     groups: List[Tuple[List[int], Tuple[int, int]]] = []
     cur: List[int] = []
@@ -57,6 +58,38 @@ def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8,
     if cur:
         groups.append((cur, (hc, wc)))
     return groups
+
+
+def extract_groups(forward, ready, scales, resized, original, groups, device) -> dict:
+    """`extract_batch` of both extractors after preprocessing: one ragged `forward` per group of preprocessed [1, C, h, w] images (a group's canvas has the
+    most channels of its images; a 1-channel image fills them all), the collated store in the images' own order"""
+    parts = []
+    for idx, (hc, wc) in groups:
+        canvas = torch.zeros((len(idx), max(ready[i].shape[1] for i in idx), hc, wc), device=device, dtype=torch.float32)
+        for r, i in enumerate(idx):
+            h, w = ready[i].shape[-2:]
+            canvas[r, :, :h, :w].copy_(ready[i][0])
+        feats = forward({"image": canvas, "valid_size": [[ready[i].shape[-1], ready[i].shape[-2]] for i in idx]})
+        kp, counts = feats["keypoints"], feats["num_keypoints"]
+        if any(resized[i] for i in idx):      # back to the original frame, (k + 0.5) / scale - 0.5 (extracted_to_image_frame), for the images that were resized
+            sc = torch.stack([scales[i] for i in idx]).to(kp.dtype)[:, None, :]
+            moved = (kp + 0.5) / sc - 0.5
+            kp = torch.where(torch.tensor([resized[i] for i in idx], device=device)[:, None, None], moved, kp)
+            kp = torch.where((torch.arange(kp.shape[1], device=device)[None, :] < counts[:, None])[..., None], kp, torch.zeros_like(kp))      # padding rows stay zero
+        parts.append((idx, kp, feats["keypoint_scores"], feats["descriptors"], counts))
+    k, nmax = len(ready), max(p[1].shape[1] for p in parts)
+    order = torch.tensor([i for p in parts for i in p[0]], device=device)
+    def gather(j, tail):
+        buf = parts[0][j].new_zeros((k, nmax) + tail)
+        for p in parts:
+            buf[torch.tensor(p[0], device=device), : p[j].shape[1]] = p[j]
+        return buf
+    out = {"keypoints": gather(1, (2,)), "descriptors": gather(3, (parts[0][3].shape[-1],)), "keypoint_scores": gather(2, ())}
+    out["image_size"] = torch.tensor([[w, h] for h, w in original], dtype=torch.float32).to(device)
+    counts = torch.empty((k,), dtype=torch.int32, device=device)
+    counts[order] = torch.cat([p[4] for p in parts])
+    out["num_keypoints"] = counts
+    return out
 
 
 _LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
@@ -249,31 +282,4 @@ class SuperPoint(nn.Module):
         return self._extract_groups(ready, scales, resized, original, groups, device)
 
     def _extract_groups(self, ready, scales, resized, original, groups, device) -> dict:
-        """one ragged forward per group of preprocessed [1, 1, h, w] images; the collated store in the images' own order"""
-        parts = []
-        for idx, (hc, wc) in groups:
-            canvas = torch.zeros((len(idx), 1, hc, wc), device=device, dtype=torch.float32)
-            for r, i in enumerate(idx):
-                h, w = ready[i].shape[-2:]
-                canvas[r, :, :h, :w].copy_(ready[i][0])
-            feats = self.forward({"image": canvas, "valid_size": [[ready[i].shape[-1], ready[i].shape[-2]] for i in idx]})
-            kp, counts = feats["keypoints"], feats["num_keypoints"]
-            if any(resized[i] for i in idx):      # back to the original frame, (k + 0.5) / scale - 0.5 (extracted_to_image_frame), for the images that were resized
-                sc = torch.stack([scales[i] for i in idx]).to(kp.dtype)[:, None, :]
-                moved = (kp + 0.5) / sc - 0.5
-                kp = torch.where(torch.tensor([resized[i] for i in idx], device=device)[:, None, None], moved, kp)
-                kp = torch.where((torch.arange(kp.shape[1], device=device)[None, :] < counts[:, None])[..., None], kp, torch.zeros_like(kp))      # padding rows stay zero
-            parts.append((idx, kp, feats["keypoint_scores"], feats["descriptors"], counts))
-        k, nmax = len(ready), max(p[1].shape[1] for p in parts)
-        order = torch.tensor([i for p in parts for i in p[0]], device=device)
-        def gather(j, tail):
-            buf = parts[0][j].new_zeros((k, nmax) + tail)
-            for p in parts:
-                buf[torch.tensor(p[0], device=device), : p[j].shape[1]] = p[j]
-            return buf
-        out = {"keypoints": gather(1, (2,)), "descriptors": gather(3, (256,)), "keypoint_scores": gather(2, ())}
-        out["image_size"] = torch.tensor([[w, h] for h, w in original], dtype=torch.float32).to(device)
-        counts = torch.empty((k,), dtype=torch.int32, device=device)
-        counts[order] = torch.cat([p[4] for p in parts])
-        out["num_keypoints"] = counts
-        return out
+        return extract_groups(self.forward, ready, scales, resized, original, groups, device)
