@@ -425,6 +425,32 @@ int lg_preprocess_plan(int32_t h, int32_t w, int32_t resize_h, int32_t resize_w,
 int lg_preprocess_resize(const void* src, int32_t dtype, int32_t batch, int32_t channels, int32_t h, int32_t w, int64_t stride_b,
                          int64_t stride_c, int64_t stride_y, int64_t stride_x, const lg_resize_plan* plan, float* dst, void* hip_stream);
 
+/* ---- The ragged form: a set of images of DIFFERENT sizes, dtypes and plans into one canvas, ONE launch ----
+ * Image b (source b under plan b) is written into the top-left h_out_b x w_out_b corner of plane b of `canvas` [batch][c_out][hc][wc], float32 contiguous;
+ * nothing outside that corner is written.  Source channels -> canvas channels: equal counts as they are; 1 -> 3 writes the one result to all three planes;
+ * 3 -> 1 is the gray value r * 0.299f + g * 0.587f + b * 0.114f of the three resized channels (three rounded products added in that order, fp32, nothing
+ * contracted: what a float32 tensor expression `0.299 * r + 0.587 * g + 0.114 * b` gives).  A plan with `identity` set copies / converts the source values as
+ * they are.  Every other pixel equals what the uniform call gives for that image and plan, bit for bit.
+ * Split like plan / resize above:
+ *   lg_preprocess_ragged_table_bytes: size of the table for `batch` images (0 outside [1, LG_PREPROCESS_RAGGED_MAX_BATCH]).
+ *   lg_preprocess_ragged_plan: host-only arithmetic, no HIP call.  Fills `table_host` (caller-owned, `table_bytes` >= the size above) with one record per image
+ *     and returns the launch geometry: *total_tiles (the grid: every image's output tiles back to back) and *lds_bytes (the largest image's tile).  Optional
+ *     outputs, each [batch] or NULL: tile_prefix (tiles of the images before b: exclusive) and image_lds (LDS bytes of image b's tile shape).
+ *   lg_preprocess_resize_ragged: `table_dev` is the caller's DEVICE copy of the same bytes (uploaded by the caller, on `hip_stream` or ordered before it);
+ *     `table_host` is read for the geometry only.  zero_fill != 0: the whole canvas is cleared first (hipMemsetAsync on the stream).  Asynchronous, no allocation.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): per image exactly that of lg_preprocess_resize; 1 <= batch <=
+ *   LG_PREPROCESS_RAGGED_MAX_BATCH; c_out 1 or 3; every target fits (hc, wc); hc * wc < 2^31; total tiles < 2^31; the table buffer large enough; no null pointer. */
+#define LG_PREPROCESS_RAGGED_MAX_BATCH 256
+typedef struct lg_image_source {
+    const void* data;            /* device pointer to the image's first element                            */
+    int32_t dtype, channels, h, w;
+    int64_t stride_b, stride_c, stride_y, stride_x;   /* element strides as in the uniform call; stride_b is validated and otherwise unused (one image) */
+} lg_image_source;
+int64_t lg_preprocess_ragged_table_bytes(int32_t batch);
+int lg_preprocess_ragged_plan(const lg_image_source* sources, const lg_resize_plan* plans, int32_t batch, int32_t c_out, int32_t hc, int32_t wc,
+                              void* table_host, int64_t table_bytes, int64_t* total_tiles, int64_t* lds_bytes, int32_t* tile_prefix, int32_t* image_lds);
+int lg_preprocess_resize_ragged(const void* table_host, const void* table_dev, int32_t batch, float* canvas, int32_t zero_fill, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

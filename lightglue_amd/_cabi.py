@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "lg_aliked_packed_bytes", "lg_aliked_pack_weights", "lg_aliked_levels_bytes", "lg_aliked_workspace_bytes", "lg_aliked_encode",
     "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
     "lg_preprocess_plan", "lg_preprocess_resize",
+    "lg_preprocess_ragged_table_bytes", "lg_preprocess_ragged_plan", "lg_preprocess_resize_ragged",
     "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
     "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
     "lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half",
@@ -84,6 +85,7 @@ class LgUnpackIO(C.Structure):
 LG_PREPROCESS_MAX_TAPS, LG_PREPROCESS_MAX_SIDE, LG_RESIZE_EDGE = 33, 2 ** 23, -1
 LG_SIDE = {"long": 0, "short": 1, "vert": 2, "horz": 3}
 LG_DTYPE_F32, LG_DTYPE_U8 = 0, 1
+LG_PREPROCESS_RAGGED_MAX_BATCH = 256
 
 
 class LgResizePlan(C.Structure):
@@ -92,6 +94,14 @@ class LgResizePlan(C.Structure):
         ("h_in", C.c_int32), ("w_in", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
         ("ks_y", C.c_int32), ("ks_x", C.c_int32), ("align_corners", C.c_int32), ("identity", C.c_int32),
         ("sigma_y", C.c_double), ("sigma_x", C.c_double), ("scale_x", C.c_double), ("scale_y", C.c_double),
+    ]
+
+
+class LgImageSource(C.Structure):
+    """lg_image_source (include/lightglue_amd.h): one image of a ragged preprocess call"""
+    _fields_ = [
+        ("data", C.c_void_p), ("dtype", C.c_int32), ("channels", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64),
     ]
 
 
@@ -184,6 +194,11 @@ def load() -> C.CDLL:
     lib.lg_aliked_describe_ragged_half.argtypes = lib.lg_aliked_describe_ragged.argtypes
     lib.lg_preprocess_plan.argtypes = [C.c_int32] * 7 + [C.POINTER(LgResizePlan)]
     lib.lg_preprocess_resize.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_int64] * 4 + [C.POINTER(LgResizePlan), C.c_void_p, C.c_void_p]
+    lib.lg_preprocess_ragged_table_bytes.argtypes = [C.c_int32]
+    lib.lg_preprocess_ragged_table_bytes.restype = C.c_int64
+    lib.lg_preprocess_ragged_plan.argtypes = ([C.POINTER(LgImageSource), C.POINTER(LgResizePlan)] + [C.c_int32] * 4 + [C.c_void_p, C.c_int64]
+                                              + [C.POINTER(C.c_int64)] * 2 + [C.POINTER(C.c_int32)] * 2)
+    lib.lg_preprocess_resize_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

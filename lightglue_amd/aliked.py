@@ -22,7 +22,7 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
-from .superpoint import extract_groups, plan_image_batches
+from .superpoint import check_image_set, extract_groups
 from .superpoint_head import check_descriptor_dtype, check_sizes, sizes_on_device
 
 
@@ -350,28 +350,10 @@ class ALIKED(nn.Module):
         would give, key for key and bit for bit — keypoints [K, N, 2] in each ORIGINAL image's pixel frame, keypoint_scores, descriptors
         (conf.descriptor_dtype), num_keypoints [K], image_size [K, 2] = original (w, h); N = the largest count, padding rows zero — ready for
         `LightGlue.match_pairs`.  The contract of `SuperPoint.extract_batch`: each image ([C, H_i, W_i] / [1, C, H_i, W_i], float32 or uint8, C = 1 | 3) is
-        preprocessed with `{**preprocess_conf, **conf}`, the results are grouped by `plan_image_batches` (at most `batch_size` per group), each group is
-        written into the top-left corners of one zeroed canvas and extracted in ONE ragged `forward` (`valid_size`).  A group that mixes 1- and 3-channel
-        images runs on a 3-channel canvas: the first convolution broadcasts one channel to three itself, so the copy changes nothing."""
-        images = list(images)
-        if not images:
-            raise ValueError("extract_batch needs at least one image")
+        preprocessed with `{**preprocess_conf, **conf}`: the target sizes are planned on the host and grouped by `plan_image_batches` (at most `batch_size` per
+        group), each group is resized / converted into the top-left corners of one zeroed canvas by ONE kernel (`ImagePreprocessor.to_canvas`) and extracted in
+        ONE ragged `forward` (`valid_size`).  A group that mixes 1- and 3-channel images runs on a 3-channel canvas, the one channel written to all three
+        planes: the first convolution broadcasts one channel to three itself, so this changes nothing."""
+        images = check_image_set(images, "ALIKED")
         prep = ImagePreprocessor(**{**self.preprocess_conf, **conf})
-        ready, scales, resized, original = [], [], [], []
-        for i, img in enumerate(images):
-            if img.dim() == 3:
-                img = img[None]
-            if img.dim() != 4 or img.shape[0] != 1:
-                raise ValueError(f"image {i} must be [C, H, W] or [1, C, H, W], got {tuple(img.shape)}")
-            if img.device.type != "cuda":
-                raise RuntimeError("lightglue_amd.ALIKED runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
-                                   f"Got image {i} on {img.device}.")
-            if img.shape[1] not in (1, 3):
-                raise ValueError(f"image {i} must have 1 or 3 channels, got {img.shape[1]}")
-            h, w = img.shape[-2:]
-            out, scale = prep(img)
-            ready.append(out.to(torch.float32)); scales.append(scale); original.append((h, w))
-            resized.append(tuple(out.shape[-2:]) != (h, w))      # extract maps keypoints back only then
-        device = ready[0].device
-        groups = plan_image_batches([tuple(t.shape[-2:]) for t in ready], batch_size, order=order)
-        return extract_groups(self.forward, ready, scales, resized, original, groups, device)
+        return extract_groups(self.forward, prep, images, batch_size, order, None)

@@ -60,24 +60,48 @@ def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8,
     return groups
 
 
-def extract_groups(forward, ready, scales, resized, original, groups, device) -> dict:
-    """`extract_batch` of both extractors after preprocessing: one ragged `forward` per group of preprocessed [1, C, h, w] images (a group's canvas has the
-    most channels of its images; a 1-channel image fills them all), the collated store in the images' own order"""
+def check_image_set(images: Sequence[torch.Tensor], who: str) -> List[torch.Tensor]:
+    """The images of an `extract_batch` call as [1, C, H, W] tensors, or the first refusal: an empty set, dimensions, device, channels, dtype (in that order)"""
+    images = list(images)
+    if not images:
+        raise ValueError("extract_batch needs at least one image")
+    out = []
+    for i, img in enumerate(images):
+        if img.dim() == 3:
+            img = img[None]
+        if img.dim() != 4 or img.shape[0] != 1:
+            raise ValueError(f"image {i} must be [C, H, W] or [1, C, H, W], got {tuple(img.shape)}")
+        if img.device.type != "cuda":
+            raise RuntimeError(f"lightglue_amd.{who} runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
+                               f"Got image {i} on {img.device}.")
+        if img.shape[1] not in (1, 3):
+            raise ValueError(f"image {i} must have 1 or 3 channels, got {img.shape[1]}")
+        if img.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"image {i} must be float32 or uint8, got {img.dtype}")
+        out.append(img)
+    return out
+
+
+def extract_groups(forward, prep: ImagePreprocessor, images, batch_size: int, order: str, channels: Optional[int]) -> dict:
+    """`extract_batch` of both extractors after validation: the images' plans under `prep` (host), `plan_image_batches` on the planned target sizes, then per
+    group ONE `prep.to_canvas` (one kernel: every image resized / converted into its corner of the zeroed canvas; `channels` as `to_canvas` takes it) and ONE
+    ragged `forward`; the collated store in the images' own order"""
+    device = images[0].device
+    plans = prep.plan_images([tuple(t.shape[-2:]) for t in images])
+    groups = plan_image_batches([(p.h_out, p.w_out) for p in plans], batch_size, order=order)
     parts = []
     for idx, (hc, wc) in groups:
-        canvas = torch.zeros((len(idx), max(ready[i].shape[1] for i in idx), hc, wc), device=device, dtype=torch.float32)
-        for r, i in enumerate(idx):
-            h, w = ready[i].shape[-2:]
-            canvas[r, :, :h, :w].copy_(ready[i][0])
-        feats = forward({"image": canvas, "valid_size": [[ready[i].shape[-1], ready[i].shape[-2]] for i in idx]})
+        canvas, valid, scales = prep.to_canvas([images[i] for i in idx], channels=channels, canvas_size=(hc, wc))
+        feats = forward({"image": canvas, "valid_size": valid})
         kp, counts = feats["keypoints"], feats["num_keypoints"]
-        if any(resized[i] for i in idx):      # back to the original frame, (k + 0.5) / scale - 0.5 (extracted_to_image_frame), for the images that were resized
-            sc = torch.stack([scales[i] for i in idx]).to(kp.dtype)[:, None, :]
+        resized = [not plans[i].identity for i in idx]      # extract maps keypoints back only then
+        if any(resized):      # back to the original frame, (k + 0.5) / scale - 0.5 (extracted_to_image_frame), for the images that were resized
+            sc = scales.to(kp.dtype)[:, None, :]
             moved = (kp + 0.5) / sc - 0.5
-            kp = torch.where(torch.tensor([resized[i] for i in idx], device=device)[:, None, None], moved, kp)
+            kp = torch.where(torch.tensor(resized, device=device)[:, None, None], moved, kp)
             kp = torch.where((torch.arange(kp.shape[1], device=device)[None, :] < counts[:, None])[..., None], kp, torch.zeros_like(kp))      # padding rows stay zero
         parts.append((idx, kp, feats["keypoint_scores"], feats["descriptors"], counts))
-    k, nmax = len(ready), max(p[1].shape[1] for p in parts)
+    k, nmax = len(images), max(p[1].shape[1] for p in parts)
     order = torch.tensor([i for p in parts for i in p[0]], device=device)
     def gather(j, tail):
         buf = parts[0][j].new_zeros((k, nmax) + tail)
@@ -85,7 +109,7 @@ def extract_groups(forward, ready, scales, resized, original, groups, device) ->
             buf[torch.tensor(p[0], device=device), : p[j].shape[1]] = p[j]
         return buf
     out = {"keypoints": gather(1, (2,)), "descriptors": gather(3, (parts[0][3].shape[-1],)), "keypoint_scores": gather(2, ())}
-    out["image_size"] = torch.tensor([[w, h] for h, w in original], dtype=torch.float32).to(device)
+    out["image_size"] = torch.tensor([[p.w_in, p.h_in] for p in plans], dtype=torch.float32).to(device)
     counts = torch.empty((k,), dtype=torch.int32, device=device)
     counts[order] = torch.cat([p[4] for p in parts])
     out["num_keypoints"] = counts
@@ -223,7 +247,8 @@ class SuperPoint(nn.Module):
         kpts, kscores = kpts[:, :nmax].contiguous(), kscores[:, :nmax].contiguous()
         if bool((counts < nmax).any()):   # ragged batch: rows beyond an image's count are padding — zero them (descriptor_head does the same)
             live = torch.arange(nmax, device=counts.device)[None, :] < counts[:, None]
-            kpts = kpts * live[..., None]; kscores = kscores * live
+            # (a select, not a product: the rows past a count are unwritten memory, and NaN * 0 is NaN)
+            kpts = torch.where(live[..., None], kpts, 0.0); kscores = torch.where(live, kscores, 0.0)
         desc = _descriptor_run(kpts, dense, 8, True, counts, c.descriptor_dtype, img_sizes)
         return {"keypoints": kpts, "keypoint_scores": kscores, "descriptors": desc, "num_keypoints": counts}   # counts: consumed by LightGlue.forward
 
@@ -253,33 +278,9 @@ class SuperPoint(nn.Module):
         would give, key for key and bit for bit — keypoints [K, N, 2] in each ORIGINAL image's pixel frame, keypoint_scores, descriptors
         (conf.descriptor_dtype), num_keypoints [K], image_size [K, 2] = original (w, h); N = the largest count, padding rows zero — ready for
         `LightGlue.match_pairs`.  `images`: [C, H_i, W_i] / [1, C, H_i, W_i] tensors, everything `extract` accepts.  Each is preprocessed with
-        `{**preprocess_conf, **conf}`, the results are grouped by `plan_image_batches` (at most `batch_size` per group), each group is written into the
-        top-left corners of one canvas and extracted in ONE ragged `forward` (`valid_size`).  `order`: the planner's — "size" puts like sizes together
+        `{**preprocess_conf, **conf}`: the target sizes are planned on the host and grouped by `plan_image_batches` (at most `batch_size` per group), each group is
+        resized / converted into the top-left corners of one canvas by ONE kernel (`ImagePreprocessor.to_canvas`) and extracted in ONE ragged `forward` (`valid_size`).  `order`: the planner's — "size" puts like sizes together
         (little padding), "input" batches the images as they come."""
-        images = list(images)
-        if not images:
-            raise ValueError("extract_batch needs at least one image")
+        images = check_image_set(images, "SuperPoint")
         prep = ImagePreprocessor(**{**self.preprocess_conf, **conf})
-        ready, scales, resized, original = [], [], [], []
-        for i, img in enumerate(images):
-            if img.dim() == 3:
-                img = img[None]
-            if img.dim() != 4 or img.shape[0] != 1:
-                raise ValueError(f"image {i} must be [C, H, W] or [1, C, H, W], got {tuple(img.shape)}")
-            if img.device.type != "cuda":
-                raise RuntimeError("lightglue_amd.SuperPoint runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. "
-                                   f"Got image {i} on {img.device}.")
-            h, w = img.shape[-2:]
-            out, scale = prep(img)
-            if out.shape[1] == 3:      # as encode does, per image: the canvas has one channel
-                out = 0.299 * out[:, 0:1] + 0.587 * out[:, 1:2] + 0.114 * out[:, 2:3]
-            if out.shape[1] != 1:
-                raise ValueError(f"image {i} must have 1 or 3 channels, got {out.shape[1]}")
-            ready.append(out.to(torch.float32)); scales.append(scale); original.append((h, w))
-            resized.append(tuple(out.shape[-2:]) != (h, w))      # extract maps keypoints back only then
-        device = ready[0].device
-        groups = plan_image_batches([tuple(t.shape[-2:]) for t in ready], batch_size, order=order)
-        return self._extract_groups(ready, scales, resized, original, groups, device)
-
-    def _extract_groups(self, ready, scales, resized, original, groups, device) -> dict:
-        return extract_groups(self.forward, ready, scales, resized, original, groups, device)
+        return extract_groups(self.forward, prep, images, batch_size, order, 1)      # 3-channel images turn gray in the kernel, as encode does per image
