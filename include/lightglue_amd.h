@@ -97,11 +97,28 @@ typedef struct lg_engine lg_engine;
 #define LG_FLAG_DESC0_F16 16u
 #define LG_FLAG_DESC1_F16 32u
 
+/* SIFT feature stores as COLMAP / pycolmap / OpenCV write them: uint8 descriptors, and the RootSIFT transform the SIFT LightGlue weights expect.  Per side, like
+ * the binary16 flags, and composing with everything they compose with (LG_FLAG_INDEXED, ragged num0 / num1, LG_FLAG_CHECK_FINITE, every precision; a pair list may
+ * join a uint8 store with an fp32 or binary16 one).
+ *   LG_FLAG_DESC0_U8 / _DESC1_U8: desc0 / desc1 point to uint8 rows [B or images][n][input_dim], read in place and widened exactly (0 .. 255 -> fp32): the forward
+ *     is bit-identical to one on the same values converted to fp32 by the caller.
+ *   LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: after widening from its storage type (fp32, binary16 or uint8) every row is replaced by its RootSIFT before anything else reads
+ *     it — r = x / max(sum |x|, 1e-6); r = sqrt(max(r, 1e-6)); r / max(|r|_2, 1e-6), in fp32 (the reference's sift_to_rootsift, sift.py:53-56) — bit-identical to
+ *     a forward on the fp32 rows lg_rootsift() writes.
+ * LG_ERR_INVALID with a message, before the GPU is touched: any of the four without LG_FLAG_EXT; _U8 and _F16 on one side; a uint8 pointer that is not 16-byte
+ * aligned; input_dim % 4 != 0; RootSIFT with input_dim > 256.  With input_dim == 256 such a call prepares the keypoints in a launch of its own instead of inside the
+ * first projection (same bits).  Quantising descriptors to uint8 is the CALLER's storage format, outside the 1e-3 score bar like binary16. */
+#define LG_FLAG_DESC0_U8 64u
+#define LG_FLAG_DESC1_U8 128u
+#define LG_FLAG_ROOTSIFT0 256u
+#define LG_FLAG_ROOTSIFT1 512u
+#define LG_SIFT_STORE_FLAGS (LG_FLAG_DESC0_U8 | LG_FLAG_DESC1_U8 | LG_FLAG_ROOTSIFT0 | LG_FLAG_ROOTSIFT1)
+
 typedef struct lg_forward_io {
     int32_t batch, n0, n1;
     uint32_t flags;                        /* LG_FLAG_*                                           */
     const float *kpts0, *kpts1;            /* [B][n][2] pixel (x, y)                              */
-    const float *desc0, *desc1;            /* [B][n][input_dim]; binary16 rows behind the same pointer with LG_FLAG_DESC0_F16 / _DESC1_F16 */
+    const float *desc0, *desc1;            /* [B][n][input_dim]; binary16 / uint8 rows behind the same pointer with LG_FLAG_DESC0_F16 / _DESC1_F16 / LG_FLAG_DESC0_U8 / _DESC1_U8 */
     const float *size0, *size1;            /* [B][2] (w, h) or NULL -> bounding-box normalisation */
     const float *scales0, *oris0, *scales1, *oris1; /* [B][n] iff add_scale_ori, else NULL        */
     int32_t *matches0, *matches1;          /* [B][n0], [B][n1]; -1 = unmatched                    */
@@ -450,6 +467,30 @@ int64_t lg_preprocess_ragged_table_bytes(int32_t batch);
 int lg_preprocess_ragged_plan(const lg_image_source* sources, const lg_resize_plan* plans, int32_t batch, int32_t c_out, int32_t hc, int32_t wc,
                               void* table_host, int64_t table_bytes, int64_t* total_tiles, int64_t* lds_bytes, int32_t* tile_prefix, int32_t* image_lds);
 int lg_preprocess_resize_ragged(const void* table_host, const void* table_dev, int32_t batch, float* canvas, int32_t zero_fill, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SIFT helpers (the reference's sift.py:17-56; the detector itself is out of scope).
+ *
+ * lg_rootsift: dst[r] = RootSIFT of src[r] for `rows` rows of `dim` values — the transform of LG_FLAG_ROOTSIFT0 / _ROOTSIFT1, from the same device code.
+ *   src_kind 0: float32, 1: binary16, 2: uint8 rows (contiguous, widened exactly); dst float32, or binary16 with dst_f16 != 0 (the fp32 result rounded once, to
+ *   nearest even).  dim a multiple of 4 in [4, 256]; src / dst aligned to the 16 / 8 / 4 bytes of four elements.  One launch on `hip_stream`, no workspace;
+ *   rows == 0 is a no-op.
+ *
+ * lg_sift_filter: the reference's filter_dog_point for `images` images of up to `n` detections each, on the device.
+ *   points [images][n][2] (x, y), scales / angles / scores [images][n] float32 (scores NULL: the scales decide), num [images] detections per image (NULL: n),
+ *   sizes [images][2] int32 (h, w) on the device, clamped into (max_h, max_w).  With s = scores or scales and pixel p_i = (round_half_even(y_i - 0.5),
+ *   round_half_even(x_i - 0.5)):  1. keep i iff s_i == max(0, max s at p_i);  2. of those, iff |angle_i| == min |angle| at p_i;  3. nms_radius > 0: iff the
+ *   value kept at p_i equals the maximum over the (2 r + 1)^2 window clipped to the image.  All comparisons exact; the maxima go through integer atomics on the
+ *   bit patterns, so the result does not depend on any order.  A detection whose pixel lies outside its image is dropped (the reference wraps or raises).  NaN
+ *   inputs are outside the contract.
+ *   Outputs: keep [images][n] int64 — the kept indices in ascending order (np.where's), then -1 — and counts [images] int32.
+ *   workspace: lg_sift_filter_workspace_bytes(images, n, max_h, max_w) bytes (two max_h x max_w rasters per image and n flags; 0 for arguments outside the
+ *   envelope), 256-byte aligned.  Envelope: images in [1, 65535], n in [0, 2^24], max_h x max_w in [1, 2^31 - 1] pixels, nms_radius in [0, 64]. */
+int lg_rootsift(const void* src, int32_t src_kind, int64_t rows, int32_t dim, void* dst, int32_t dst_f16, void* hip_stream);
+int64_t lg_sift_filter_workspace_bytes(int32_t images, int32_t n, int32_t max_h, int32_t max_w);
+int lg_sift_filter(const float* points, const float* scales, const float* angles, const float* scores, const int32_t* num, const int32_t* sizes, int32_t images,
+                   int32_t n, int32_t max_h, int32_t max_w, int32_t nms_radius, void* workspace, int64_t workspace_bytes, int64_t* keep, int32_t* counts,
+                   void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,9 @@ LG_PREC = {"fp32": 0, "bf16": 1, "fp16": 2, "f16x3": 4}   # include/lightglue_am
 LG_OK, LG_ERR_INVALID, LG_ERR_HIP, LG_ERR_STATE, LG_ERR_RANGE, LG_ERR_DEVICE, LG_ERR_INDEX = 0, 1, 2, 3, 4, 5, 6
 LG_FLAG_NO_PRUNING, LG_FLAG_EXT, LG_FLAG_CHECK_FINITE, LG_FLAG_INDEXED = 1, 2, 4, 8
 LG_FLAG_DESC0_F16, LG_FLAG_DESC1_F16 = 16, 32   # desc0 / desc1 are binary16 rows, read in place
+LG_FLAG_DESC0_U8, LG_FLAG_DESC1_U8 = 64, 128    # desc0 / desc1 are uint8 rows (SIFT as COLMAP / OpenCV store it), read in place
+LG_FLAG_ROOTSIFT0, LG_FLAG_ROOTSIFT1 = 256, 512   # RootSIFT of every row of desc0 / desc1 where the descriptors enter the engine
+LG_DESC_KIND = {"float32": 0, "float16": 1, "uint8": 2}   # lg_rootsift src_kind
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
 # every symbol include/lightglue_amd.h declares (tests check the library exports all of them)
@@ -35,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
     "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
     "lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half",
+    "lg_rootsift", "lg_sift_filter_workspace_bytes", "lg_sift_filter",
 )
 
 
@@ -199,6 +203,10 @@ def load() -> C.CDLL:
     lib.lg_preprocess_ragged_plan.argtypes = ([C.POINTER(LgImageSource), C.POINTER(LgResizePlan)] + [C.c_int32] * 4 + [C.c_void_p, C.c_int64]
                                               + [C.POINTER(C.c_int64)] * 2 + [C.POINTER(C.c_int32)] * 2)
     lib.lg_preprocess_resize_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.lg_rootsift.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.lg_sift_filter_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.lg_sift_filter_workspace_bytes.restype = C.c_int64
+    lib.lg_sift_filter.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

@@ -85,26 +85,40 @@ def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS
 def _engine_descriptors(t: torch.Tensor, device) -> tuple:
     """Descriptors as the engine reads them -> (tensor, stored as float16).  A float16 tensor is read IN PLACE (the side's LG_FLAG_DESC*_F16: the engine widens
     every value exactly where the descriptors enter it, so the forward is bit-identical to one on `t.float()`) — untouched when it is on the device, contiguous
-    and 16-byte aligned, otherwise through one float16 copy; every other dtype becomes contiguous fp32, as before."""
-    if t.dtype is torch.float16:
+    and 16-byte aligned, otherwise through one float16 copy; a uint8 tensor (SIFT as COLMAP / OpenCV store it) likewise, through at most one uint8 copy
+    (the side's LG_FLAG_DESC*_U8; the returned tensor's dtype tells the two apart); every other dtype becomes contiguous fp32, as before."""
+    if t.dtype is torch.float16 or t.dtype is torch.uint8:
         if t.device != device or not t.is_contiguous():
             t = t.detach().to(device=device).contiguous()
         if t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
             t = t.clone()
-        return t, True
+        return t, t.dtype is torch.float16
     if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
         return t, False
     return t.detach().to(device=device, dtype=torch.float32).contiguous(), False
 
 
 class Side:
-    """K images of N keypoint rows as the engine reads them: contiguous fp32 / int32 tensors on the device (descriptors fp32 or float16), absent pieces None."""
-    __slots__ = ("K", "N", "kpts", "desc", "desc_f16", "size", "scales", "oris", "num")
+    """K images of N keypoint rows as the engine reads them: contiguous fp32 / int32 tensors on the device (descriptors fp32, float16 or uint8), absent pieces
+    None.  `rootsift`: the engine replaces every descriptor row by its RootSIFT where it enters (the store's "descriptor_transform")."""
+    __slots__ = ("K", "N", "kpts", "desc", "desc_f16", "desc_u8", "rootsift", "size", "scales", "oris", "num")
+
+
+DESCRIPTOR_TRANSFORMS = (None, "rootsift")
+
+
+def descriptor_transform(feats: dict, what: str = "feats"):
+    """The optional non-tensor key `descriptor_transform` of a feature dict: None or "rootsift"."""
+    tr = feats.get("descriptor_transform")
+    if tr not in DESCRIPTOR_TRANSFORMS:
+        raise ValueError(f"{what}: descriptor_transform must be None or 'rootsift', got {tr!r}")
+    return tr
 
 
 def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, what: str = "feats") -> Side:
     """{keypoints [K, N, 2], descriptors [K, N, input_dim], image_size [K, 2] | [1, 2] | [2] (optional; broadcast as the reference does, ref :35-42),
-    scales / oris [K, N] iff add_scale_ori, num_keypoints [K] (optional; clamped into [0, N])} -> Side.  `forward` calls it for image0 / image1 (K = B) and
+    scales / oris [K, N] iff add_scale_ori, num_keypoints [K] (optional; clamped into [0, N]), descriptor_transform None | "rootsift" (optional, not a
+    tensor; anything else is a ValueError)} -> Side.  `forward` calls it for image0 / image1 (K = B) and
     `match_pairs` for its feature stores, once per call.  Only data pointers are handed on, so every shape is checked here (AssertionError naming the key) and
     tensors that already qualify pass through untouched: no copy, no kernel."""
     def f32(t):
@@ -118,6 +132,8 @@ def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, wha
     assert tuple(desc.shape) == (K, N, input_dim), f"{what}: descriptors must have shape [{K}, {N}, {input_dim}], got {tuple(desc.shape)}"
     s.kpts = f32(kpts)
     s.desc, s.desc_f16 = _engine_descriptors(desc, device)
+    s.desc_u8 = s.desc.dtype is torch.uint8
+    s.rootsift = descriptor_transform(feats, what) == "rootsift"
     s.size = s.scales = s.oris = s.num = None
     size = feats.get("image_size")
     if size is not None:

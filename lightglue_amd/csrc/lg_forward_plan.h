@@ -10,7 +10,7 @@ namespace lg {
 
 // What lg_engine_set_option and lg_engine_debug_stop_after write (lg_engine::opt)
 struct ForwardOptions {
-    int fused_tail = 1, fused_next = 1, fused_prep = 1;   // fused_prep: the per-keypoint preparation inside the first projection launch (input_dim == 256)
+    int fused_tail = 1, fused_next = 1, fused_prep = 1;   // fused_prep: the per-keypoint preparation inside the first projection launch (input_dim == 256, no SIFT-store flag)
     // gather path of the adaptive width (round 6, default on): the SelfBlock projection behind a pruning step reads rows from one set of residual / rotary
     // buffers and writes the compacted rows to the other (lg_proj.hip proj_rows_kernel<GatherRows>)
     bool adapt_gather = true;
@@ -122,7 +122,9 @@ inline ForwardPlan plan_forward(const lg_config& cfg, int attn_prec, const Forwa
     p.do_stop = cfg.depth_confidence > 0; p.do_prune = pruning_on(cfg, io_flags);
     p.prune_possible = p.do_prune && (n0 > cfg.pruning_min_kpts || n1 > cfg.pruning_min_kpts);
     p.check_finite = (io_flags & LG_FLAG_EXT) && (io_flags & LG_FLAG_CHECK_FINITE);
-    p.fuse_prep = opt.fused_prep && cfg.input_dim == 256 && opt.debug_stop < 0 && opt.tail_timing != 2;
+    // SIFT stores (uint8 rows, RootSIFT on entry) are read by prep_kernel alone: such a call takes the two-launch form, which is bit-identical
+    const bool sift_store = (io_flags & LG_FLAG_EXT) && (io_flags & LG_SIFT_STORE_FLAGS);
+    p.fuse_prep = opt.fused_prep && cfg.input_dim == 256 && opt.debug_stop < 0 && opt.tail_timing != 2 && !sift_store;
     p.fuse_next = opt.fused_next && opt.fused_tail && (opt.tail_timing == 0 || opt.tail_timing == 5 || opt.tail_timing == 6) &&
                   opt.debug_stop < 0 && tail_supports_next;
     p.use_gather = opt.adapt_gather && opt.fused_tail && opt.debug_stop < 0 && opt.tail_timing == 0;

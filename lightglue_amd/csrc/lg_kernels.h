@@ -161,6 +161,10 @@ struct PrepArgs {
     const float* size0; const float* size1;      // [B][2] (w,h) or nullptr -> bbox
     const float* scales0; const float* oris0; const float* scales1; const float* oris1;  // [B][n] or nullptr
     const float* Wr; int pos_dim;  // [32][pos_dim], pos_dim = 2 or 4
+    // SIFT stores, read by prep_kernel only (the plan runs it whenever one is set).  Two bytes in the padding behind pos_dim: the layout of every other field, and so
+    // the argument block of the fused first projection (lg_proj.hip), is what it was.  Bit `side` set —
+    unsigned char desc_u8;         // LG_FLAG_DESC0_U8 / _DESC1_U8: uint8 rows behind the descriptor pointer, widened exactly (0 .. 255) on load
+    unsigned char rootsift;        // LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: every widened row is replaced by its RootSIFT (lg_sift.h) before it is stored
     const float* desc0; const float* desc1; int input_dim;  // [B][n][input_dim]
     int desc_f16;                  // bit `side` set (LG_FLAG_DESC0_F16 / _DESC1_F16): that side's descriptors are IEEE binary16 rows behind the same pointer, widened exactly on load
     float* X;                      // [R][256]  (written only when input_dim == 256; else see Xin)
@@ -169,6 +173,8 @@ struct PrepArgs {
     int* ind;                      // [R] original index of each live row
     float* bbox;                   // [2B][4] scratch (minx,miny,maxx,maxy) when size is absent
 };
+// the fused first projection takes PrepArgs as a kernel argument: a new field goes into padding or behind `bbox`, never in front of what lg_proj.hip reads
+static_assert(sizeof(PrepArgs) == 216 && offsetof(PrepArgs, desc0) == 144 && offsetof(PrepArgs, X) == 168, "PrepArgs: the layout lg_proj.hip was measured with");
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s);
 hipError_t launch_prep_bbox(const PrepArgs& a, hipStream_t s);   // only the bounding boxes (image_size absent); no-op otherwise
 // The FIRST SelfBlock projection of a forward with the per-keypoint preparation fused in (input_dim == 256): the workgroup builds the rotary rows of its

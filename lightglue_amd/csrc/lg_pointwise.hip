@@ -3,6 +3,7 @@
 // and the 256->1 heads (token confidence ref :89-94, matchability ref :298-299).
 // One wave (64 lanes) per keypoint row; 16-byte loads per lane.
 #include "lg_kernels.h"
+#include "lg_sift.h"
 
 namespace lg {
 
@@ -31,6 +32,9 @@ __global__ __launch_bounds__(256) void bbox_kernel(PrepArgs a) {
 }
 
 // ------------------------------------------------------------------ prep: one wave per input keypoint
+// SIFT: the instantiation for calls with a SIFT-store flag (uint8 rows, RootSIFT on entry; launch_prep picks it).  prep_kernel<false> compiles to the code the
+// kernel had before those flags existed.
+template <bool SIFT>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int seg = blockIdx.y, image = seg & 1, pair = seg >> 1;
@@ -62,7 +66,18 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     // descriptors -> residual stream (ref :502-503, :521-522 identity case) or input-projection staging
     const float* d0 = image ? a.desc1 : a.desc0;
     float* dst = (a.input_dim == 256) ? a.X + grow * 256 : a.Xin + grow * a.input_dim;
-    if ((a.desc_f16 >> image) & 1) {                  // binary16 rows: 8-byte loads of 4 halves, widened exactly
+    if (SIFT && (((a.desc_u8 | a.rootsift) >> image) & 1)) {    // this side is a SIFT store (uniform per workgroup): uint8 rows and / or RootSIFT on entry
+        const int kind = ((a.desc_u8 >> image) & 1) ? DESC_U8 : ((a.desc_f16 >> image) & 1) ? DESC_F16 : DESC_F32;
+        const long long at = (src * n + r) * a.input_dim;
+        if ((a.rootsift >> image) & 1) {              // the whole row in the wave's registers (input_dim <= 256: check_forward_io)
+            const bool own = lane * 4 < a.input_dim;
+            const f32x4 x = own ? load_desc4(d0, kind, at + lane * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 y = rootsift_row(x, lane, a.input_dim);
+            if (own) *reinterpret_cast<f32x4*>(dst + lane * 4) = y;
+        } else {
+            for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = load_desc4(d0, kind, at + c);
+        }
+    } else if ((a.desc_f16 >> image) & 1) {           // binary16 rows: 8-byte loads of 4 halves, widened exactly
         const f16_t* d = reinterpret_cast<const f16_t*>(d0) + (src * n + r) * a.input_dim;
         for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = widen4_f16(*reinterpret_cast<const f16x4*>(d + c));
     } else {
@@ -80,7 +95,8 @@ hipError_t launch_prep(const PrepArgs& a, hipStream_t s) {
     const int nseg = 2 * a.rs.B;
     if (!a.size0 || !a.size1) hipLaunchKernelGGL(bbox_kernel, dim3(nseg), dim3(256), 0, s, a);
     const int nmax = a.n0 > a.n1 ? a.n0 : a.n1;
-    if (nmax > 0) hipLaunchKernelGGL(prep_kernel, dim3((nmax + 3) / 4, nseg), dim3(256), 0, s, a);
+    if (nmax > 0 && (a.desc_u8 | a.rootsift)) hipLaunchKernelGGL(prep_kernel<true>, dim3((nmax + 3) / 4, nseg), dim3(256), 0, s, a);
+    else if (nmax > 0) hipLaunchKernelGGL(prep_kernel<false>, dim3((nmax + 3) / 4, nseg), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -10,6 +10,8 @@ from typing import Any, Callable, Dict
 
 import torch
 
+from ._call import descriptor_transform
+
 
 def _apply_to_tensors(obj: Any, fn: Callable[[torch.Tensor], torch.Tensor]) -> Any:
     """Rebuild nested dict / list / tuple containers with `fn` applied to every tensor leaf."""
@@ -122,7 +124,8 @@ def collate_features(feats: list) -> Dict[str, Any]:
     batch dimension of 1: `keypoints [N_i,2]`, `descriptors [N_i,D]`, optional `scales`/`oris`/`keypoint_scores
     [N_i]` and `image_size [2]`.  Per-keypoint tensors are zero-padded to max N_i and `num_keypoints [B]` carries
     the true counts; the engine never reads the padding (the reference instead pads with ones and masks every
-    attention call, `lightglue.py:46-55, 512-520`, and only inside `compile()`d B=1 calls)."""
+    attention call, `lightglue.py:46-55, 512-520`, and only inside `compile()`d B=1 calls).  Descriptors stay float16 / uint8
+    when every item stores them so, else fp32; `descriptor_transform` (None | "rootsift") is carried when all items agree."""
     items = []
     for f in feats:
         kp = f["keypoints"]
@@ -135,8 +138,8 @@ def collate_features(feats: list) -> Dict[str, Any]:
             continue
         first = items[0][key]
         dtype = first.dtype
-        if key == "descriptors" and dtype is torch.float16 and not all(f[key].dtype is torch.float16 for f in items):
-            dtype = torch.float32   # float16 only when EVERY item stores float16: a float16 first item must not round the fp32 ones behind it
+        if key == "descriptors" and dtype in (torch.float16, torch.uint8) and not all(f[key].dtype is dtype for f in items):
+            dtype = torch.float32   # float16 / uint8 only when EVERY item stores it: a float16 first item must not round the fp32 ones behind it
         buf = first.new_zeros((len(items), nmax) + tuple(first.shape[1:]), dtype=dtype)
         for b, f in enumerate(items):
             buf[b, : counts[b]] = f[key]
@@ -144,6 +147,11 @@ def collate_features(feats: list) -> Dict[str, Any]:
     if all("image_size" in f for f in items):
         out["image_size"] = torch.stack([torch.as_tensor(f["image_size"], dtype=torch.float32).reshape(2) for f in items]).to(out["keypoints"].device)
     out["num_keypoints"] = torch.tensor(counts, dtype=torch.int32, device=out["keypoints"].device)
+    transforms = {descriptor_transform(f, f"feats[{b}]") for b, f in enumerate(items)}
+    if len(transforms) > 1:
+        raise ValueError(f"descriptor_transform differs between the items ({sorted(map(str, transforms))}): one store has one transform")
+    if transforms and transforms != {None}:
+        out["descriptor_transform"] = transforms.pop()
     return out
 
 

@@ -365,7 +365,9 @@ class LightGlue(nn.Module):
                 guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
                 self._guard_pending = False
                 flags = (_cabi.LG_FLAG_EXT | (0 if index is None else _cabi.LG_FLAG_INDEXED) | (0 if o.pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
-                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0) | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0))
+                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0) | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0)
+                         | (_cabi.LG_FLAG_DESC0_U8 if s0.desc_u8 else 0) | (_cabi.LG_FLAG_DESC1_U8 if s1.desc_u8 else 0)
+                         | (_cabi.LG_FLAG_ROOTSIFT0 if s0.rootsift else 0) | (_cabi.LG_FLAG_ROOTSIFT1 if s1.rootsift else 0))
                 lib, stream_ptr = _cabi.load(), C.c_void_p(stream.cuda_stream)
                 for start, stop in chunks:
                     io = o.io(start, stop - start, flags, s0, s1, wire, index)
@@ -379,7 +381,8 @@ class LightGlue(nn.Module):
     def forward(self, data: dict) -> dict:
         """Match keypoints and descriptors between two images (same dict contract as ref :456-481).
 
-        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D] (float16 descriptors are read in place, per side: see _call._engine_descriptors),
+        Input (dict):  image0/image1: {keypoints [B,N,2], descriptors [B,N,D] (float16 / uint8 descriptors are read in place, per side: see _call._engine_descriptors),
+                                       descriptor_transform None | "rootsift" (optional, not a tensor: RootSIFT of every row as the engine reads it, per side),
                                        image_size [B,2] (optional),
                                        scales/oris [B,N] iff add_scale_ori,
                                        num_keypoints [B] int (optional, extension: ragged batch — pair b uses only

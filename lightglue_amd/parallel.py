@@ -57,8 +57,8 @@ def balanced_shards(costs: Sequence[float], world: int) -> List[List[int]]:
 
 
 def _take(data: dict, idx) -> dict:
-    """Rows `idx` (slice or index tensor) of every per-pair tensor of the nested input dict."""
-    pick = lambda t: t[idx] if isinstance(idx, slice) else t.index_select(0, idx.to(t.device))
+    """Rows `idx` (slice or index tensor) of every per-pair tensor of the nested input dict; a non-tensor entry (`descriptor_transform`) travels as it is."""
+    pick = lambda t: t if not torch.is_tensor(t) else (t[idx] if isinstance(idx, slice) else t.index_select(0, idx.to(t.device)))
     return {k: ({kk: pick(vv) for kk, vv in v.items()} if isinstance(v, dict) else v) for k, v in data.items()}
 
 

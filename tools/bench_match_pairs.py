@@ -10,7 +10,15 @@ and all but one host synchronisation) and, unless --no-uncapped, with the engine
 --store-dtype f16 keeps the store's descriptors as float16 (read in place, LG_FLAG_DESC0_F16 / _DESC1_F16; the stacked route then gathers float16 rows); the last
 lines report the store's bytes and the peak device memory of one match_pairs call above what was allocated before it.
 
-usage: bench_match_pairs.py [--images 32] [--kpts 1024] [--batch 32] [--runs 3] [--no-uncapped] [--store-dtype f32|f16]"""
+--features sift is a workload of its own: a SIFT store as COLMAP / OpenCV write it (128-d uint8 descriptors, scales, oris), matched by
+LightGlue(input_dim = 128, add_scale_ori) over the exhaustive pair list in two ways — (a) the route a caller had before uint8 stores: RootSIFT as the reference's
+torch expression on `store.float()`, then match_pairs on the fp32 result; (b) --store-dtype u8 --descriptor-transform rootsift: match_pairs on the uint8 store
+itself, transformed where the engine reads it.  Reported: ms per list (the transform of (a) included: it is paid per list unless a second, 4 x larger store is
+kept), bytes of the resident store, and the framework kernels in front of the engine's first launch.  The two routes differ in summation order inside RootSIFT
+(1e-7-class descriptor differences), so their outputs are compared by count, not bit for bit.
+
+usage: bench_match_pairs.py [--images 32] [--kpts 1024] [--batch 32] [--runs 3] [--no-uncapped] [--store-dtype f32|f16|u8] [--features superpoint|sift]
+                            [--descriptor-transform none|rootsift]"""
 import argparse
 import itertools
 import json
@@ -51,6 +59,69 @@ def stacked_route(model, store, pairs_dev, batch):
     return outs
 
 
+def make_sift_store(K, N, seed=0, dim=128):
+    """K views of one scene in the stored SIFT format: uint8 descriptors (sparse: most bins small, a few large), scales, oris."""
+    g = torch.Generator().manual_seed(seed)
+    base_k = torch.rand(N, 2, generator=g) * torch.tensor([1024.0, 768.0])
+    base_d = (torch.randn(N, dim, generator=g).abs() ** 3 * 12.0).clamp(0, 255)
+    kpts, desc = torch.empty(K, N, 2), torch.empty(K, N, dim, dtype=torch.uint8)
+    for i in range(K):
+        perm = torch.randperm(N, generator=g)
+        kpts[i] = base_k[perm] + 2.0 * torch.randn(N, 2, generator=g)
+        desc[i] = (base_d[perm] + 2.0 * torch.randn(N, dim, generator=g)).clamp(0, 255).to(torch.uint8)
+    size = torch.tensor([[1024.0, 768.0]]).expand(K, 2).contiguous()
+    scales, oris = 1.0 + 4.0 * torch.rand(K, N, generator=g), (torch.rand(K, N, generator=g) * 2 - 1) * 3.14159
+    return {"keypoints": kpts.cuda(), "descriptors": desc.cuda(), "image_size": size.cuda(), "scales": scales.cuda(), "oris": oris.cuda()}
+
+
+def torch_rootsift(x, eps=1e-6):
+    """RootSIFT in framework kernels, what a caller ran before the engine could: L1-normalise, clip, sqrt, L2-normalise."""
+    l1 = x.abs().sum(dim=-1, keepdim=True).clamp_min(eps)
+    root = (x / l1).clamp_min(eps).sqrt()
+    return root / root.norm(dim=-1, keepdim=True).clamp_min(eps)
+
+
+def kernels_in_front(call):
+    """(framework kernels launched before the engine's first one, engine kernels) of one call, as the profiler sees them."""
+    from torch.profiler import ProfilerActivity, profile
+    call(); torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+        call(); torch.cuda.synchronize()
+    ev = sorted((e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "Memcpy" not in e.name and "Memset" not in e.name),
+                key=lambda e: e.time_range.start)
+    names = [e.name for e in ev]
+    first = next((i for i, n in enumerate(names) if "lg::" in n), len(names))
+    return names[:first], sum("lg::" in n for n in names)
+
+
+def sift_main(a):
+    K, N = a.images, a.kpts
+    model = gpu_util.make_model(synth.make_state_dict(0, input_dim=128, add_scale_ori=True, recipe="A"), "f16x3", input_dim=128, add_scale_ori=True,
+                                depth_confidence=-1, width_confidence=-1)
+    store = make_sift_store(K, N)
+    pairs_dev = torch.tensor(list(itertools.combinations(range(K), 2)), device="cuda")
+    P = int(pairs_dev.shape[0])
+    nbytes = lambda st: sum(v.numel() * v.element_size() for v in st.values() if torch.is_tensor(v))
+    res = {"features": "sift", "images": K, "kpts": N, "pairs": P, "runs": a.runs, "device": torch.cuda.get_device_name(0)}
+    route_a = lambda: model.match_pairs({**store, "descriptors": torch_rootsift(store["descriptors"].float())}, pairs_dev, validate=False)
+    tagged = {**store, "descriptor_transform": "rootsift"}
+    route_b = lambda: model.match_pairs(tagged, pairs_dev, validate=False)
+    rows = []
+    for name, route, st in (("(a) torch RootSIFT on store.float(), then match_pairs", route_a, {**store, "descriptors": store["descriptors"].float()}),
+                            ("(b) uint8 store, descriptor_transform = rootsift", route_b, store)):
+        t, out = timed(route, a.runs)
+        front, ours = kernels_in_front(route)
+        rows.append((name, t))
+        res[name[:3]] = {"ms": {"median": statistics.median(t), "min": min(t), "max": max(t)}, "resident_store_bytes": nbytes(st),
+                         "framework_kernels_in_front": len(front), "engine_kernels": ours, "matches_per_pair": sum(len(x) for x in out["matches"]) / P,
+                         "chunks": len(model.last_pair_chunks)}
+        print(f"  {name:<60s} median {statistics.median(t):8.2f} ms  (min {min(t):8.2f}, max {max(t):8.2f})  store {nbytes(st) / 2 ** 20:7.1f} MiB  "
+              f"framework kernels in front of the engine {len(front)}  matches per pair {res[name[:3]]['matches_per_pair']:.0f}", flush=True)
+        del out
+    print(json.dumps(res))
+    return 0
+
+
 def timed(fn, runs):
     fn(); torch.cuda.synchronize()                      # warm-up: workspace growth, caches
     times = []
@@ -68,8 +139,16 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="pairs per forward of the stacked route (and per engine call of the capped match_pairs run)")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-uncapped", action="store_true", help="skip the match_pairs run with the engine's own per-call limits (its workspace is about 14 KB per keypoint row of a call)")
-    ap.add_argument("--store-dtype", default="f32", choices=["f32", "f16"], help="element type of the store's descriptors")
+    ap.add_argument("--store-dtype", default="f32", choices=["f32", "f16", "u8"], help="element type of the store's descriptors (u8: with --features sift)")
+    ap.add_argument("--features", default="superpoint", choices=["superpoint", "sift"], help="sift: 128-d uint8 descriptors with scales / oris, routes (a) and (b) of the docstring")
+    ap.add_argument("--descriptor-transform", default="none", choices=["none", "rootsift"], help="rootsift: the store carries descriptor_transform = 'rootsift' (with --features sift)")
     a = ap.parse_args()
+    if a.features == "sift":
+        if a.store_dtype != "u8" or a.descriptor_transform != "rootsift":
+            ap.error("--features sift measures the stored format: pass --store-dtype u8 --descriptor-transform rootsift")
+        return sift_main(a)
+    if a.store_dtype == "u8" or a.descriptor_transform != "none":
+        ap.error("--store-dtype u8 / --descriptor-transform rootsift belong to --features sift")
     K, N, B = a.images, a.kpts, a.batch
     model = gpu_util.make_model(synth.make_state_dict(0, recipe="A"), "f16x3", depth_confidence=-1, width_confidence=-1)
     store = make_store(K, N, dtype=torch.float16 if a.store_dtype == "f16" else torch.float32)
