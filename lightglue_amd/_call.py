@@ -82,26 +82,29 @@ def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS
 
 
 # ---------------------------------------------------------------------- one side of a call
-def _engine_descriptors(t: torch.Tensor, device) -> tuple:
-    """Descriptors as the engine reads them -> (tensor, stored as float16).  A float16 tensor is read IN PLACE (the side's LG_FLAG_DESC*_F16: the engine widens
-    every value exactly where the descriptors enter it, so the forward is bit-identical to one on `t.float()`) — untouched when it is on the device, contiguous
-    and 16-byte aligned, otherwise through one float16 copy; a uint8 tensor (SIFT as COLMAP / OpenCV store it) likewise, through at most one uint8 copy
-    (the side's LG_FLAG_DESC*_U8; the returned tensor's dtype tells the two apart); every other dtype becomes contiguous fp32, as before."""
-    if t.dtype is torch.float16 or t.dtype is torch.uint8:
-        if t.device != device or not t.is_contiguous():
-            t = t.detach().to(device=device).contiguous()
-        if t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
-            t = t.clone()
-        return t, t.dtype is torch.float16
-    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-        return t, False
-    return t.detach().to(device=device, dtype=torch.float32).contiguous(), False
+def _engine_descriptors(t: torch.Tensor, device, keep=(torch.float16, torch.uint8)) -> torch.Tensor:
+    """Descriptors as the engine reads them; the returned tensor's dtype is the side's storage format.  float16 and uint8 (SIFT as COLMAP / OpenCV store it)
+    tensors are read IN PLACE (the side's LG_FLAG_DESC*_F16 / _U8: the engine widens every value exactly where the descriptors enter it, so the forward is
+    bit-identical to one on `t.float()`) — untouched when on the device, contiguous and 16-byte aligned, otherwise through one copy in the same dtype; every
+    dtype outside `keep` becomes contiguous fp32 (keep = (): what every other input of a side goes through)."""
+    dtype = t.dtype if t.dtype in keep else torch.float32
+    if t.dtype is not dtype or t.device != device or not t.is_contiguous():
+        t = t.detach().to(device=device, dtype=dtype).contiguous()
+    if dtype is not torch.float32 and t.data_ptr() % 16:      # a view at an odd element offset (whole rows are multiples of 128 bytes)
+        t = t.clone()
+    return t
 
 
 class Side:
     """K images of N keypoint rows as the engine reads them: contiguous fp32 / int32 tensors on the device (descriptors fp32, float16 or uint8), absent pieces
     None.  `rootsift`: the engine replaces every descriptor row by its RootSIFT where it enters (the store's "descriptor_transform")."""
-    __slots__ = ("K", "N", "kpts", "desc", "desc_f16", "desc_u8", "rootsift", "size", "scales", "oris", "num")
+    __slots__ = ("K", "N", "kpts", "desc", "rootsift", "size", "scales", "oris", "num")
+    desc_f16 = property(lambda self: self.desc.dtype is torch.float16)
+    desc_u8 = property(lambda self: self.desc.dtype is torch.uint8)
+
+    def flags(self, side: int) -> int:
+        """The LG_FLAG_DESC*_F16 / _DESC*_U8 / LG_FLAG_ROOTSIFT* bits of this side as side 0 or 1 of a call (side 1's flag is side 0's << 1)."""
+        return (_cabi.LG_FLAG_DESC0_F16 * self.desc_f16 | _cabi.LG_FLAG_DESC0_U8 * self.desc_u8 | _cabi.LG_FLAG_ROOTSIFT0 * self.rootsift) << side
 
 
 DESCRIPTOR_TRANSFORMS = (None, "rootsift")
@@ -121,18 +124,14 @@ def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, wha
     tensor; anything else is a ValueError)} -> Side.  `forward` calls it for image0 / image1 (K = B) and
     `match_pairs` for its feature stores, once per call.  Only data pointers are handed on, so every shape is checked here (AssertionError naming the key) and
     tensors that already qualify pass through untouched: no copy, no kernel."""
-    def f32(t):
-        if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-            return t
-        return t.detach().to(device=device, dtype=torch.float32).contiguous()
+    f32 = lambda t: _engine_descriptors(t, device, keep=())
     kpts, desc = feats["keypoints"], feats["descriptors"]
     assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
     s = Side()
     K, N = s.K, s.N = kpts.shape[0], kpts.shape[1]
     assert tuple(desc.shape) == (K, N, input_dim), f"{what}: descriptors must have shape [{K}, {N}, {input_dim}], got {tuple(desc.shape)}"
     s.kpts = f32(kpts)
-    s.desc, s.desc_f16 = _engine_descriptors(desc, device)
-    s.desc_u8 = s.desc.dtype is torch.uint8
+    s.desc = _engine_descriptors(desc, device)
     s.rootsift = descriptor_transform(feats, what) == "rootsift"
     s.size = s.scales = s.oris = s.num = None
     size = feats.get("image_size")

@@ -151,33 +151,20 @@ int tail_row_tiles_for(int R) {
     return best;
 }
 
-// bit `side` set: desc0 / desc1 hold binary16 rows (LG_FLAG_DESC0_F16 / _DESC1_F16; check_forward_io refuses them without LG_FLAG_EXT)
-int desc_f16_sides(const lg_forward_io* io) { return ((io->flags & LG_FLAG_DESC0_F16) ? 1 : 0) | ((io->flags & LG_FLAG_DESC1_F16) ? 2 : 0); }
-// the same for uint8 rows (LG_FLAG_DESC0_U8 / _DESC1_U8) and for RootSIFT where the descriptors enter (LG_FLAG_ROOTSIFT0 / _ROOTSIFT1)
-int desc_u8_sides(const lg_forward_io* io) { return ((io->flags & LG_FLAG_DESC0_U8) ? 1 : 0) | ((io->flags & LG_FLAG_DESC1_U8) ? 2 : 0); }
-int rootsift_sides(const lg_forward_io* io) { return ((io->flags & LG_FLAG_ROOTSIFT0) ? 1 : 0) | ((io->flags & LG_FLAG_ROOTSIFT1) ? 2 : 0); }
 PairIndex pair_index(const lg_forward_io* io) { return indexed(io->flags) ? PairIndex{io->index0, io->index1, io->images0, io->images1} : PairIndex{}; }
 
 int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     if (!e || !io) return set_error(LG_ERR_INVALID, "null argument");
-    if (io->flags & (LG_FLAG_DESC0_F16 | LG_FLAG_DESC1_F16)) {   // pure argument checks, ahead of the engine's state: refused on any engine
-        if (!(io->flags & LG_FLAG_EXT)) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16 need LG_FLAG_EXT");
-        // the kernels read a binary16 row in 16-byte pieces: rows are input_dim * 2 bytes (a multiple of 128), so the base decides
-        if (((io->flags & LG_FLAG_DESC0_F16) && (reinterpret_cast<uintptr_t>(io->desc0) & 15)) ||
-            ((io->flags & LG_FLAG_DESC1_F16) && (reinterpret_cast<uintptr_t>(io->desc1) & 15)))
-            return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16: the descriptor pointer must be 16-byte aligned");
-    }
-    if (io->flags & LG_SIFT_STORE_FLAGS) {                       // SIFT stores: the same kind of check, ahead of the engine's state too
-        if (!(io->flags & LG_FLAG_EXT)) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_U8 / _DESC1_U8 / LG_FLAG_ROOTSIFT0 / _ROOTSIFT1 need LG_FLAG_EXT");
-        if (((io->flags & LG_FLAG_DESC0_U8) && (io->flags & LG_FLAG_DESC0_F16)) || ((io->flags & LG_FLAG_DESC1_U8) && (io->flags & LG_FLAG_DESC1_F16)))
-            return set_error(LG_ERR_INVALID, "LG_FLAG_DESC*_U8 and LG_FLAG_DESC*_F16 are both set on one side: a store has one format");
-        // a uint8 row is read in 4-byte pieces and is input_dim bytes long; the base is held to the 16 bytes of the other formats
-        if (((io->flags & LG_FLAG_DESC0_U8) && (reinterpret_cast<uintptr_t>(io->desc0) & 15)) ||
-            ((io->flags & LG_FLAG_DESC1_U8) && (reinterpret_cast<uintptr_t>(io->desc1) & 15)))
-            return set_error(LG_ERR_INVALID, "LG_FLAG_DESC0_U8 / LG_FLAG_DESC1_U8: the descriptor pointer must be 16-byte aligned");
-        if (e->cfg.input_dim % 4) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC*_U8 / LG_FLAG_ROOTSIFT*: input_dim must be a multiple of 4");
-        if ((io->flags & (LG_FLAG_ROOTSIFT0 | LG_FLAG_ROOTSIFT1)) && e->cfg.input_dim > 256)
-            return set_error(LG_ERR_INVALID, "LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: input_dim must be at most 256 (one wave holds the row)");
+    for (int side = 0; side < 2; ++side) {   // each side's storage format (side_format): pure argument checks, ahead of the engine's state: refused on any engine
+        const SideFormat f = side_format(io->flags, side);
+        if (!f.valid) return set_error(LG_ERR_INVALID, (io->flags & LG_FLAG_EXT) ? "LG_FLAG_DESC*_U8 and LG_FLAG_DESC*_F16 are both set on one side: a store has one format"
+                                                                                 : "LG_FLAG_DESC*_F16 / LG_FLAG_DESC*_U8 / LG_FLAG_ROOTSIFT* need LG_FLAG_EXT");
+        // binary16 rows are read in 16-byte pieces and are input_dim * 2 bytes long (a multiple of 128), so the base decides; uint8 rows are read in 4-byte
+        // pieces and held to the same 16 bytes
+        if (f.kind != DESC_F32 && (reinterpret_cast<uintptr_t>(side ? io->desc1 : io->desc0) & 15))
+            return set_error(LG_ERR_INVALID, "LG_FLAG_DESC*_F16 / LG_FLAG_DESC*_U8: the descriptor pointer must be 16-byte aligned");
+        if ((f.kind == DESC_U8 || f.rootsift) && e->cfg.input_dim % 4) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC*_U8 / LG_FLAG_ROOTSIFT*: input_dim must be a multiple of 4");
+        if (f.rootsift && e->cfg.input_dim > 256) return set_error(LG_ERR_INVALID, "LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: input_dim must be at most 256 (one wave holds the row)");
     }
     if (!e->weights_ready) return set_error(LG_ERR_STATE, "weights not finalised");
     const int B = io->batch, n0 = io->n0, n1 = io->n1;
@@ -254,11 +241,11 @@ ForwardCtx forward_ctx(const lg_engine* e, const lg_forward_io* io, const Forwar
     c.range_flag = plan.check_finite ? e->RANGEF : nullptr;
     c.device_err = e->CFLAGS + (size_t)2 * B * compact_chunks(c0, c1);
     PrepArgs& p = c.prep;
-    p.rs = c.rs_all; p.n0 = io->n0; p.n1 = io->n1; p.px = pair_index(io); p.kpts0 = io->kpts0; p.kpts1 = io->kpts1; p.size0 = io->size0; p.size1 = io->size1;
-    p.scales0 = io->scales0; p.oris0 = io->oris0; p.scales1 = io->scales1; p.oris1 = io->oris1;
-    p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0);
-    p.desc0 = io->desc0; p.desc1 = io->desc1; p.input_dim = e->cfg.input_dim; p.desc_f16 = desc_f16_sides(io);
-    p.desc_u8 = (unsigned char)desc_u8_sides(io); p.rootsift = (unsigned char)rootsift_sides(io);
+    p.rs = c.rs_all; p.px = pair_index(io);
+    p.side[0] = PrepSide{io->kpts0, io->size0, io->scales0, io->oris0, io->desc0, io->n0};
+    p.side[1] = PrepSide{io->kpts1, io->size1, io->scales1, io->oris1, io->desc1, io->n1};
+    for (int side = 0; side < 2; ++side) { const SideFormat f = side_format(io->flags, side); p.side[side].kind = f.kind; p.side[side].rootsift = f.rootsift; }
+    p.Wr = e->Wr; p.pos_dim = 2 + 2 * (e->cfg.add_scale_ori ? 1 : 0); p.input_dim = e->cfg.input_dim;
     p.X = e->X; p.Xin = e->XIN; p.cosb = e->COS; p.sinb = e->SIN; p.ind = e->IND; p.bbox = e->BBOX;
     return c;
 }

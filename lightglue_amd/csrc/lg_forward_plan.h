@@ -31,6 +31,21 @@ inline bool pruning_on(const lg_config& cfg, uint32_t io_flags) { return cfg.wid
 // LG_FLAG_INDEXED: the index fields sit behind the round-5 extension, so they are read only when both flags are set (check_forward_io refuses one without the other)
 inline bool indexed(uint32_t io_flags) { return (io_flags & LG_FLAG_EXT) && (io_flags & LG_FLAG_INDEXED); }
 
+// ---- the storage format of one side's descriptors, decoded once from the call's flags (check_forward_io validates it, forward_ctx hands it to the kernels as PrepSide)
+enum : int { DESC_F32 = 0, DESC_F16 = 1, DESC_U8 = 2 };   // how a descriptor row is stored (lg_rootsift's src_kind); lg_side.h loads each
+struct SideFormat {
+    int kind;         // DESC_*: LG_FLAG_DESC{side}_U8 / _F16, else fp32
+    bool rootsift;    // LG_FLAG_ROOTSIFT{side}: every widened row is replaced by its RootSIFT where it enters
+    bool valid;       // false: a storage flag of the side without LG_FLAG_EXT, or _U8 and _F16 together (a store has one format)
+};
+// The flags of side 0 / 1 lie one bit apart.  They sit behind the round-5 extension: without LG_FLAG_EXT every one of them is off.
+static_assert(LG_FLAG_DESC1_F16 == LG_FLAG_DESC0_F16 << 1 && LG_FLAG_DESC1_U8 == LG_FLAG_DESC0_U8 << 1 && LG_FLAG_ROOTSIFT1 == LG_FLAG_ROOTSIFT0 << 1, "side 1's flag = side 0's << 1");
+inline SideFormat side_format(uint32_t io_flags, int side) {
+    const bool f16 = io_flags & (LG_FLAG_DESC0_F16 << side), u8 = io_flags & (LG_FLAG_DESC0_U8 << side), root = io_flags & (LG_FLAG_ROOTSIFT0 << side);
+    if (!(io_flags & LG_FLAG_EXT)) return {DESC_F32, false, !(f16 || u8 || root)};
+    return {u8 ? DESC_U8 : f16 ? DESC_F16 : DESC_F32, root, !(u8 && f16)};
+}
+
 enum class ProjBy {     // how a block's q/k/v come about
     PrevTail,           // the previous block's tail kernel has already produced them (fused_next)
     Own,                // the block's own projection launch (lg_proj.hip)

@@ -153,28 +153,28 @@ struct AttnArgs {
 hipError_t launch_attention(int attn_prec, const AttnArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- pointwise (lg_pointwise.hip)
+// one side (image 0 / image 1) of a call as the preparation reads it; every array is per pair, or per IMAGE of a store when the call is indexed
+struct PrepSide {
+    const float* kpts;             // [B][n][2] pixels
+    const float* size;             // [B][2] (w,h) or nullptr -> bbox
+    const float* scales; const float* oris;   // [B][n] or nullptr
+    const void* desc;              // [B][n][input_dim] rows stored as `kind`, widened exactly on load (lg_side.h load_desc4)
+    int n;                         // dense input row count per image (input tensors are [B][n][..])
+    int kind;                      // DESC_F32 / DESC_F16 / DESC_U8 (lg_forward_plan.h side_format)
+    int rootsift;                  // != 0: every widened row is replaced by its RootSIFT (lg_side.h rootsift_row) before it is stored; prep_kernel only
+};
 struct PrepArgs {
     RowSpace rs;
-    int n0, n1;                    // dense input row counts per image (input tensors are [B][n][..])
-    PairIndex px;                  // indexed inputs: every input array below is per IMAGE of a store and pair b reads image source_image(px, b, side)
-    const float* kpts0; const float* kpts1;      // [B][n][2] pixels
-    const float* size0; const float* size1;      // [B][2] (w,h) or nullptr -> bbox
-    const float* scales0; const float* oris0; const float* scales1; const float* oris1;  // [B][n] or nullptr
+    PairIndex px;                  // indexed inputs: pair b reads image source_image(px, b, side) of side[side]'s arrays
+    PrepSide side[2];
     const float* Wr; int pos_dim;  // [32][pos_dim], pos_dim = 2 or 4
-    // SIFT stores, read by prep_kernel only (the plan runs it whenever one is set).  Two bytes in the padding behind pos_dim: the layout of every other field, and so
-    // the argument block of the fused first projection (lg_proj.hip), is what it was.  Bit `side` set —
-    unsigned char desc_u8;         // LG_FLAG_DESC0_U8 / _DESC1_U8: uint8 rows behind the descriptor pointer, widened exactly (0 .. 255) on load
-    unsigned char rootsift;        // LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: every widened row is replaced by its RootSIFT (lg_sift.h) before it is stored
-    const float* desc0; const float* desc1; int input_dim;  // [B][n][input_dim]
-    int desc_f16;                  // bit `side` set (LG_FLAG_DESC0_F16 / _DESC1_F16): that side's descriptors are IEEE binary16 rows behind the same pointer, widened exactly on load
+    int input_dim;
     float* X;                      // [R][256]  (written only when input_dim == 256; else see Xin)
     float* Xin;                    // [R][input_dim] staging for the input projection GEMM
     float* cosb; float* sinb;      // [R][32]
     int* ind;                      // [R] original index of each live row
     float* bbox;                   // [2B][4] scratch (minx,miny,maxx,maxy) when size is absent
 };
-// the fused first projection takes PrepArgs as a kernel argument: a new field goes into padding or behind `bbox`, never in front of what lg_proj.hip reads
-static_assert(sizeof(PrepArgs) == 216 && offsetof(PrepArgs, desc0) == 144 && offsetof(PrepArgs, X) == 168, "PrepArgs: the layout lg_proj.hip was measured with");
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s);
 hipError_t launch_prep_bbox(const PrepArgs& a, hipStream_t s);   // only the bounding boxes (image_size absent); no-op otherwise
 // The FIRST SelfBlock projection of a forward with the per-keypoint preparation fused in (input_dim == 256): the workgroup builds the rotary rows of its

@@ -2,8 +2,7 @@
 // encoding (ref lightglue.py:32-43, :76-81), LayerNorm(512)+GELU of the FFN (ref :152-157),
 // and the 256->1 heads (token confidence ref :89-94, matchability ref :298-299).
 // One wave (64 lanes) per keypoint row; 16-byte loads per lane.
-#include "lg_kernels.h"
-#include "lg_sift.h"
+#include "lg_side.h"
 
 namespace lg {
 
@@ -11,9 +10,9 @@ namespace lg {
 // ref :35-36: size = 1 + max - min over the keypoints of the image
 __global__ __launch_bounds__(256) void bbox_kernel(PrepArgs a) {
     const int seg = blockIdx.x, image = seg & 1, pair = seg >> 1;
-    const int n = image ? a.n1 : a.n0;
+    const PrepSide& sd = a.side[image];
     const int live = a.rs.len[seg];   // ragged batch: only the pair's own keypoints define its bounding box (0 for a pair whose index is out of range)
-    const float* kp = (image ? a.kpts1 : a.kpts0) + (long long)source_image(a.px, pair, image) * n * 2;
+    const float* kp = sd.kpts + (long long)source_image(a.px, pair, image) * sd.n * 2;
     float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
     for (int i = threadIdx.x; i < live; i += 256) {
         const float x = kp[2 * i], y = kp[2 * i + 1];
@@ -32,71 +31,46 @@ __global__ __launch_bounds__(256) void bbox_kernel(PrepArgs a) {
 }
 
 // ------------------------------------------------------------------ prep: one wave per input keypoint
-// SIFT: the instantiation for calls with a SIFT-store flag (uint8 rows, RootSIFT on entry; launch_prep picks it).  prep_kernel<false> compiles to the code the
-// kernel had before those flags existed.
-template <bool SIFT>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int seg = blockIdx.y, image = seg & 1, pair = seg >> 1;
-    const int n = image ? a.n1 : a.n0;
+    const PrepSide& sd = a.side[image];               // uniform per workgroup, and so are its format and transform
     const int r = blockIdx.x * 4 + wave;
     if (r >= a.rs.len[seg]) return;   // len <= n: rows past a pair's own count are padding (never read)
     const long long grow = seg_row_base(a.rs, seg) + r;
     const long long src = source_image(a.px, pair, image);   // the image whose rows this segment reads: the pair itself unless the inputs are indexed
-    const float* kp = (image ? a.kpts1 : a.kpts0) + (src * n + r) * 2;
-    const float* szp = image ? a.size1 : a.size0;
-    float sx, sy;
-    if (szp) { sx = szp[src * 2]; sy = szp[src * 2 + 1]; }
-    else { const float* bb = a.bbox + seg * 4; sx = 1.f + bb[2] - bb[0]; sy = 1.f + bb[3] - bb[1]; }
-    const float scale = fmaxf(sx, sy) / 2.f;          // ref :41
+    const long long in_row = src * sd.n + r;
     float kn[4];
-    kn[0] = (kp[0] - sx / 2.f) / scale;               // ref :40, :42
-    kn[1] = (kp[1] - sy / 2.f) / scale;
-    if (a.pos_dim == 4) {                             // ref :495-501
-        kn[2] = (image ? a.scales1 : a.scales0)[src * n + r];
-        kn[3] = (image ? a.oris1 : a.oris0)[src * n + r];
-    }
-    if (lane < 32) {                                  // ref :78-79 (32 frequencies, shared by all heads)
-        float p = 0.f;
-        for (int c = 0; c < a.pos_dim; ++c) p += kn[c] * a.Wr[lane * a.pos_dim + c];
+    normalised_keypoint(a, sd, seg, src, in_row, kn);
+    if (lane < 32) {                                  // 32 frequencies
+        const float p = fourier_phase(a, kn, lane);
         a.cosb[grow * 32 + lane] = cosf(p);
         a.sinb[grow * 32 + lane] = sinf(p);
     }
     if (lane == 0) a.ind[grow] = r;
     // descriptors -> residual stream (ref :502-503, :521-522 identity case) or input-projection staging
-    const float* d0 = image ? a.desc1 : a.desc0;
     float* dst = (a.input_dim == 256) ? a.X + grow * 256 : a.Xin + grow * a.input_dim;
-    if (SIFT && (((a.desc_u8 | a.rootsift) >> image) & 1)) {    // this side is a SIFT store (uniform per workgroup): uint8 rows and / or RootSIFT on entry
-        const int kind = ((a.desc_u8 >> image) & 1) ? DESC_U8 : ((a.desc_f16 >> image) & 1) ? DESC_F16 : DESC_F32;
-        const long long at = (src * n + r) * a.input_dim;
-        if ((a.rootsift >> image) & 1) {              // the whole row in the wave's registers (input_dim <= 256: check_forward_io)
-            const bool own = lane * 4 < a.input_dim;
-            const f32x4 x = own ? load_desc4(d0, kind, at + lane * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const f32x4 y = rootsift_row(x, lane, a.input_dim);
-            if (own) *reinterpret_cast<f32x4*>(dst + lane * 4) = y;
-        } else {
-            for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = load_desc4(d0, kind, at + c);
-        }
-    } else if ((a.desc_f16 >> image) & 1) {           // binary16 rows: 8-byte loads of 4 halves, widened exactly
-        const f16_t* d = reinterpret_cast<const f16_t*>(d0) + (src * n + r) * a.input_dim;
-        for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = widen4_f16(*reinterpret_cast<const f16x4*>(d + c));
+    const long long at = in_row * a.input_dim;
+    if (sd.rootsift) {                                // the whole row in the wave's registers (input_dim <= 256: check_forward_io)
+        const bool own = lane * 4 < a.input_dim;
+        const f32x4 x = own ? load_desc4(sd.desc, sd.kind, at + lane * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 y = rootsift_row(x, lane, a.input_dim);
+        if (own) *reinterpret_cast<f32x4*>(dst + lane * 4) = y;
     } else {
-        const float* d = d0 + (src * n + r) * a.input_dim;
-        for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(d + c);
+        for (int c = lane * 4; c < a.input_dim; c += 256) *reinterpret_cast<f32x4*>(dst + c) = load_desc4(sd.desc, sd.kind, at + c);
     }
 }
 
 hipError_t launch_prep_bbox(const PrepArgs& a, hipStream_t s) {
-    if (!a.size0 || !a.size1) hipLaunchKernelGGL(bbox_kernel, dim3(2 * a.rs.B), dim3(256), 0, s, a);
+    if (!a.side[0].size || !a.side[1].size) hipLaunchKernelGGL(bbox_kernel, dim3(2 * a.rs.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s) {
     if (a.input_dim % 4) return hipErrorInvalidValue;
-    const int nseg = 2 * a.rs.B;
-    if (!a.size0 || !a.size1) hipLaunchKernelGGL(bbox_kernel, dim3(nseg), dim3(256), 0, s, a);
-    const int nmax = a.n0 > a.n1 ? a.n0 : a.n1;
-    if (nmax > 0 && (a.desc_u8 | a.rootsift)) hipLaunchKernelGGL(prep_kernel<true>, dim3((nmax + 3) / 4, nseg), dim3(256), 0, s, a);
-    else if (nmax > 0) hipLaunchKernelGGL(prep_kernel<false>, dim3((nmax + 3) / 4, nseg), dim3(256), 0, s, a);
+    const hipError_t e = launch_prep_bbox(a, s);
+    if (e != hipSuccess) return e;
+    const int nmax = a.side[0].n > a.side[1].n ? a.side[0].n : a.side[1].n;
+    if (nmax > 0) hipLaunchKernelGGL(prep_kernel, dim3((nmax + 3) / 4, 2 * a.rs.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 // two passes of NTP n-tiles per wave (keeps accumulators + weight ring under the register budget); the outputs
 // leave straight from the accumulators (lg_proj_body.h: transposed MFMA form for q/k, plain form for v^T).
 #include "lg_proj_body.h"
+#include "lg_side.h"
 
 namespace lg {
 
@@ -99,42 +100,29 @@ __global__ __launch_bounds__(PTHREADS) void proj_kernel(ProjArgs a) {
 // of both go; the kernel stages them, stores them and projects.
 struct RowDest { float* X; float* cosb; float* sinb; };   // [R][256], [R][32], [R][32]
 
-// The first SelfBlock projection with the per-keypoint preparation fused in (lg_kernels.h launch_proj_first): rows come from the forward's inputs.  Same
-// arithmetic, in the same order, as prep_kernel (lg_pointwise.hip: ref lightglue.py:32-43, :76-81) and proj_kernel, so the outputs are bit-identical to
-// the two-launch form.
+// The first SelfBlock projection with the per-keypoint preparation fused in (lg_kernels.h launch_proj_first): rows come from the forward's inputs, through
+// the device functions prep_kernel calls (lg_side.h) and into proj_kernel's arithmetic, so the outputs are bit-identical to the two-launch form.
 struct FirstRows {
     typedef PrepArgs Args;
     const PrepArgs& pa;
-    int seg, image; long long simg, in_row;
-    __device__ __forceinline__ FirstRows(const PrepArgs& pa_, const TileLoc& t, int rc) : pa(pa_), seg(t.seg), image(t.seg & 1) {
-        simg = source_image(pa.px, t.pair, image);          // the image whose rows this tile reads: the pair itself unless the inputs are indexed
-        in_row = simg * (image ? pa.n1 : pa.n0) + rc;
+    const PrepSide& sd;                                     // the tile's side: uniform per workgroup
+    int seg; long long simg, in_row;
+    __device__ __forceinline__ FirstRows(const PrepArgs& pa_, const TileLoc& t, int rc) : pa(pa_), sd(pa_.side[t.seg & 1]), seg(t.seg) {
+        simg = source_image(pa.px, t.pair, seg & 1);        // the image whose rows this tile reads: the pair itself unless the inputs are indexed
+        in_row = simg * sd.n + rc;
     }
-    // descriptor rows (the x tile), fp32 or binary16 per side: uniform per workgroup
+    // descriptor rows (the x tile), fp32 or binary16 (a SIFT store never comes here: ForwardPlan::fuse_prep)
     template <int PREC> __device__ __forceinline__ void load_x(TileRegs<PREC>& h, int col) const {
-        const float* d = image ? pa.desc1 : pa.desc0;
-        if ((pa.desc_f16 >> image) & 1) h.load_f16(reinterpret_cast<const f16_t*>(d) + in_row * 256 + col);
-        else h.load(d + in_row * 256 + col);
+        if (sd.kind == DESC_F16) h.load_f16(static_cast<const f16_t*>(sd.desc) + in_row * 256 + col);
+        else h.load(static_cast<const float*>(sd.desc) + in_row * 256 + col);
     }
-    // rotary rows: thread -> keypoint srow, frequencies 4 sslot .. 4 sslot + 3 (prep_kernel's expressions)
+    // rotary rows: thread -> keypoint srow, frequencies 4 sslot .. 4 sslot + 3
     __device__ __forceinline__ void rotary(int sslot, f32x4& c4, f32x4& s4) const {
-        const float* kp = (image ? pa.kpts1 : pa.kpts0) + in_row * 2;
-        const float* szp = image ? pa.size1 : pa.size0;
-        float sx, sy;
-        if (szp) { sx = szp[simg * 2]; sy = szp[simg * 2 + 1]; }
-        else { const float* bb = pa.bbox + seg * 4; sx = 1.f + bb[2] - bb[0]; sy = 1.f + bb[3] - bb[1]; }
-        const float scale = fmaxf(sx, sy) / 2.f;
         float kn[4];
-        kn[0] = (kp[0] - sx / 2.f) / scale;
-        kn[1] = (kp[1] - sy / 2.f) / scale;
-        if (pa.pos_dim == 4) {
-            kn[2] = (image ? pa.scales1 : pa.scales0)[in_row];
-            kn[3] = (image ? pa.oris1 : pa.oris0)[in_row];
-        }
+        normalised_keypoint(pa, sd, seg, simg, in_row, kn);
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
-            float p = 0.f;
-            for (int c = 0; c < pa.pos_dim; ++c) p += kn[c] * pa.Wr[(sslot * 4 + f) * pa.pos_dim + c];
+            const float p = fourier_phase(pa, kn, sslot * 4 + f);
             c4[f] = cosf(p); s4[f] = sinf(p);
         }
     }

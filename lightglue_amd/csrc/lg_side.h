@@ -1,13 +1,33 @@
-// lightglue_amd — SIFT feature stores: descriptor rows in their storage format (fp32, binary16, uint8) and the RootSIFT transform (ref sift.py:53-56),
-// written once for prep_kernel (lg_pointwise.hip: LG_FLAG_DESC*_U8 / LG_FLAG_ROOTSIFT*) and the stand-alone rootsift_kernel (lg_sift.hip: lg_rootsift).
+// lightglue_amd — how one side of a call enters the engine, written once for every kernel that reads a forward's inputs: the normalised keypoint and its Fourier
+// phase (ref lightglue.py:32-43, :76-81; prep_kernel in lg_pointwise.hip and the fused first projection, FirstRows in lg_proj.hip), descriptor rows in their
+// storage format (fp32, binary16, uint8: the kinds are lg_forward_plan.h's DESC_*, host-visible) and the RootSIFT transform (ref sift.py:53-56; prep_kernel
+// and the stand-alone rootsift_kernel, lg_sift.hip).
 #pragma once
-#include "lg_common.h"
+#include "lg_forward_plan.h"
+#include "lg_kernels.h"
 
 namespace lg {
 
-typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
+// ---- the keypoint of input row `in_row` (= simg * sd.n + r, simg the image the segment reads) normalised by the image size or, without one, by the bounding
+// box of the segment's keypoints (ref :32-43); with pos_dim == 4 its scale and orientation behind it (ref :495-501).  kn[2], kn[3] stay unset otherwise.
+__device__ __forceinline__ void normalised_keypoint(const PrepArgs& a, const PrepSide& sd, int seg, long long simg, long long in_row, float (&kn)[4]) {
+    const float* kp = sd.kpts + in_row * 2;
+    float sx, sy;
+    if (sd.size) { sx = sd.size[simg * 2]; sy = sd.size[simg * 2 + 1]; }
+    else { const float* bb = a.bbox + seg * 4; sx = 1.f + bb[2] - bb[0]; sy = 1.f + bb[3] - bb[1]; }
+    const float scale = fmaxf(sx, sy) / 2.f;          // ref :41
+    kn[0] = (kp[0] - sx / 2.f) / scale;               // ref :40, :42
+    kn[1] = (kp[1] - sy / 2.f) / scale;
+    if (a.pos_dim == 4) { kn[2] = sd.scales[in_row]; kn[3] = sd.oris[in_row]; }
+}
+// the phase of frequency f (0 .. 31, shared by all heads; ref :78-79): the caller stores its cosf and sinf
+__device__ __forceinline__ float fourier_phase(const PrepArgs& a, const float (&kn)[4], int f) {
+    float p = 0.f;
+    for (int c = 0; c < a.pos_dim; ++c) p += kn[c] * a.Wr[f * a.pos_dim + c];
+    return p;
+}
 
-enum : int { DESC_F32 = 0, DESC_F16 = 1, DESC_U8 = 2 };   // storage format of a descriptor row (lg_rootsift's src_kind)
+typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
 
 // ---- uint8 -> fp32 of descriptors that are STORED as bytes (LG_FLAG_DESC0_U8 / _DESC1_U8; COLMAP / OpenCV SIFT): v_cvt_f32_ubyte0..3, exact (0 .. 255)
 __device__ __forceinline__ f32x4 widen4_u8(const u8x4& b) { return __builtin_convertvector(b, f32x4); }

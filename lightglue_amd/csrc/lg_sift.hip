@@ -3,8 +3,7 @@
 // kept indices in ascending order.  The SIFT detector itself is out of scope.
 #include <string>
 
-#include "lg_kernels.h"
-#include "lg_sift.h"
+#include "lg_side.h"
 #include "../../include/lightglue_amd.h"
 
 namespace lg {

@@ -365,9 +365,7 @@ class LightGlue(nn.Module):
                 guard = self.check_finite is True or (self.check_finite == "first" and self._guard_pending)
                 self._guard_pending = False
                 flags = (_cabi.LG_FLAG_EXT | (0 if index is None else _cabi.LG_FLAG_INDEXED) | (0 if o.pruning or self.conf.width_confidence <= 0 else _cabi.LG_FLAG_NO_PRUNING)
-                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0) | (_cabi.LG_FLAG_DESC0_F16 if s0.desc_f16 else 0) | (_cabi.LG_FLAG_DESC1_F16 if s1.desc_f16 else 0)
-                         | (_cabi.LG_FLAG_DESC0_U8 if s0.desc_u8 else 0) | (_cabi.LG_FLAG_DESC1_U8 if s1.desc_u8 else 0)
-                         | (_cabi.LG_FLAG_ROOTSIFT0 if s0.rootsift else 0) | (_cabi.LG_FLAG_ROOTSIFT1 if s1.rootsift else 0))
+                         | (_cabi.LG_FLAG_CHECK_FINITE if guard else 0) | s0.flags(0) | s1.flags(1))
                 lib, stream_ptr = _cabi.load(), C.c_void_p(stream.cuda_stream)
                 for start, stop in chunks:
                     io = o.io(start, stop - start, flags, s0, s1, wire, index)

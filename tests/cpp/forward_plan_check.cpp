@@ -144,6 +144,33 @@ int main() {
         const ForwardPlan plan = plan_forward(cfg, ap, o, 100, 100, 0, false, false, true);
         if (plan.sim_planes != (prec == LG_PREC_F16X3 && planes) || plan.split_qkv != (ap == LG_PREC_F16X3)) { std::printf("FAILED: sim_planes / split_qkv at precision %d / %d\n", prec, ap); return 1; }
     }
+    // ---- the storage format of a side (side_format), at all 64 combinations of the six storage flags, with and without LG_FLAG_EXT.  The rule, restated from
+    // include/lightglue_amd.h: a side's rows are uint8 with its _U8 flag, binary16 with its _F16 flag, fp32 with neither; both at once is no format;
+    // RootSIFT applies to any of them; and without LG_FLAG_EXT none of the flags may be set (nothing is on, and a set flag is a refusal).
+    const uint32_t f16[2] = {LG_FLAG_DESC0_F16, LG_FLAG_DESC1_F16}, u8[2] = {LG_FLAG_DESC0_U8, LG_FLAG_DESC1_U8}, root[2] = {LG_FLAG_ROOTSIFT0, LG_FLAG_ROOTSIFT1};
+    for (int combo = 0; combo < 64; ++combo) for (int ext = 0; ext < 2; ++ext) for (int other = 0; other < 2; ++other) {
+        uint32_t fl = (ext ? LG_FLAG_EXT : 0u) | (other ? LG_FLAG_INDEXED | LG_FLAG_NO_PRUNING | LG_FLAG_CHECK_FINITE : 0u);
+        bool any_sift = false;
+        for (int side = 0; side < 2; ++side) {
+            if (combo >> (3 * side) & 1) fl |= f16[side];
+            if (combo >> (3 * side + 1) & 1) { fl |= u8[side]; any_sift = true; }
+            if (combo >> (3 * side + 2) & 1) { fl |= root[side]; any_sift = true; }
+        }
+        for (int side = 0; side < 2; ++side) {
+            const bool h = (fl & f16[side]) != 0, b = (fl & u8[side]) != 0, r = (fl & root[side]) != 0;
+            const SideFormat f = side_format(fl, side);
+            const int kind = !ext ? DESC_F32 : b ? DESC_U8 : h ? DESC_F16 : DESC_F32;
+            const bool valid = ext ? !(h && b) : !(h || b || r);
+            if (f.valid != valid || (valid && (f.kind != kind || f.rootsift != (ext && r))) || (!ext && (f.kind != DESC_F32 || f.rootsift))) {
+                std::printf("FAILED: side_format(flags %u, side %d) = {kind %d, rootsift %d, valid %d}\n", fl, side, f.kind, f.rootsift, f.valid); return 1;
+            }
+        }
+        // a SIFT store is read by the preparation kernel alone: the fused preparation is off exactly when one of its flags is set (with LG_FLAG_EXT)
+        lg_config cfg{}; cfg.input_dim = 256; cfg.n_layers = 9; cfg.precision = LG_PREC_F16X3; cfg.pruning_min_kpts = kMinKpts;
+        const ForwardPlan plan = plan_forward(cfg, LG_PREC_F16X3, ForwardOptions{}, 100, 100, fl, false, false, true);
+        if (plan.fuse_prep != !(ext && any_sift)) { std::printf("FAILED: fuse_prep %d at flags %u\n", plan.fuse_prep, fl); return 1; }
+        ++g_points;
+    }
     std::printf("ok %lld\n", g_points);
     return 0;
 }

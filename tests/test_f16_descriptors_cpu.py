@@ -88,20 +88,20 @@ def test_engine_descriptors_dtype_rule_on_the_host():
     from lightglue_amd.lightglue import _engine_descriptors
     cpu = torch.device("cpu")
     h = torch.arange(24, dtype=torch.float16).reshape(1, 3, 8)
-    t, is_half = _engine_descriptors(h, cpu)
-    assert is_half and t.data_ptr() == h.data_ptr()
+    t = _engine_descriptors(h, cpu)
+    assert t.dtype is torch.float16 and t.data_ptr() == h.data_ptr()
     nc = h.transpose(1, 2).contiguous().transpose(1, 2)
-    t, is_half = _engine_descriptors(nc, cpu)
-    assert is_half and t.dtype is torch.float16 and t.is_contiguous() and torch.equal(t, h)
+    t = _engine_descriptors(nc, cpu)
+    assert t.dtype is torch.float16 and t.is_contiguous() and torch.equal(t, h)
     odd = torch.zeros(1 + 24, dtype=torch.float16)[1:].view(1, 3, 8)      # 2 bytes off a 16-byte boundary: copied, still float16
-    t, is_half = _engine_descriptors(odd, cpu)
-    assert is_half and t.data_ptr() % 16 == 0 and t.dtype is torch.float16
+    t = _engine_descriptors(odd, cpu)
+    assert t.data_ptr() % 16 == 0 and t.dtype is torch.float16
     for dtype in (torch.float64, torch.bfloat16):
-        t, is_half = _engine_descriptors(h.to(dtype), cpu)
-        assert not is_half and t.dtype is torch.float32
+        t = _engine_descriptors(h.to(dtype), cpu)
+        assert t.dtype is torch.float32
     f = h.float()
-    t, is_half = _engine_descriptors(f, cpu)
-    assert not is_half and t.data_ptr() == f.data_ptr()
+    t = _engine_descriptors(f, cpu)
+    assert t.dtype is torch.float32 and t.data_ptr() == f.data_ptr()
 
 
 RECORD = json.loads((ROOT / "tests" / "golden" / "f16_descriptor_drift.json").read_text())

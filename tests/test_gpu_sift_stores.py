@@ -145,6 +145,29 @@ def test_rootsift_on_entry_at_256_and_adaptive():
         _has_matches(got)
 
 
+@pytest.mark.parametrize("dim", [128, 256])
+def test_one_preparation_launch_serves_any_two_formats_and_transforms(dim):
+    """The preparation kernel picks storage format and transform per side inside one launch: every pair of storage kinds (fp32, float16, uint8) on the two
+    sides, with descriptor_transform = "rootsift" on image0 only, on image1 only and on both, == the call on fp32 tensors converted (exact: the values are
+    0 .. 255) and transformed beforehand.  n0 = 70 / n1 = 130 cross a 64-row tile, and pair 1 has an empty image0."""
+    require_gpu()
+    model = _model(dim)
+    a, b = _u8_store(5, [70, 0], 70, dim), _u8_store(5, [130, 97], 130, dim)
+    kinds = (torch.float32, torch.float16, torch.uint8)
+    matched = []
+    for root0, root1 in ((True, False), (False, True), (True, True)):
+        pre = lambda s, root: _with(s, descriptors=sift_to_rootsift(s["descriptors"]) if root else s["descriptors"].float())
+        want = model({"image0": pre(a, root0), "image1": pre(b, root1)})
+        matched.append((want["matches0"] > -1).sum(1).tolist())
+        assert matched[-1][1] == 0, "the pair with an empty image has no match"
+        side = lambda s, kind, root: _with(s, descriptors=s["descriptors"].to(kind), **({"descriptor_transform": "rootsift"} if root else {}))
+        for k0 in kinds:
+            for k1 in kinds:
+                _assert_same_dict(model({"image0": side(a, k0, root0), "image1": side(b, k1, root1)}), want, (dim, root0, root1, k0, k1))
+    print(f"dim {dim}: matches per pair with RootSIFT on image0 / image1 / both {matched}")
+    assert matched[2][0] > 0, "with both sides transformed pair 0 must produce matches: the equality compares something"
+
+
 def test_match_pairs_over_an_indexed_uint8_rootsift_store():
     """K = 3, P = 4 with a repeated image and a self pair == forward on the stacked, pre-transformed fp32 tensors; deferred and raw calls carry the key too."""
     require_gpu()
