@@ -492,6 +492,57 @@ int lg_sift_filter(const float* points, const float* scales, const float* angles
                    int32_t n, int32_t max_h, int32_t max_w, int32_t nms_radius, void* workspace, int64_t workspace_bytes, int64_t* keep, int32_t* counts,
                    void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Nearest-neighbour matcher: mutual nearest neighbour with Lowe's ratio test and a distance threshold, over the same feature stores, pair lists and storage
+ * formats as lg_engine_forward — without weights, so without an engine: the two functions below are stateless.  The reference has no such matcher; this is the
+ * definition.
+ *   rows      a_i (i < num0 of the pair's image 0, else n0) and b_j of image 1, widened exactly from fp32 / binary16 / uint8, RootSIFT first where the side's
+ *             LG_FLAG_ROOTSIFT* is set, then L2-normalised in fp32: x / max(|x|_2, 1e-12)
+ *   sim[i][j] the dot product of the two normalised rows on fp32 operands with fp32 accumulation, k ascending (v_mfma_f32_16x16x4_f32: an fmaf chain).  The
+ *             matrix is never written to memory, and nothing of a call is bounded by LG_MAX_SIM_ELEMS
+ *   row i     j1 = the column of the largest sim[i][.], the lowest index among equal values; s1 its value, s2 the largest over j != j1; d = max(2 (1 - s), 0).
+ *             kept iff (ratio off, or fewer than two columns, or d1 <= ratio^2 d2) and (distance off or d1 <= distance^2): raw0[i] = j1 if kept, else -1.
+ *             Columns likewise with the roles swapped (raw1): the same fp32 sim in both directions.
+ *   matches   LG_FLAG_NN_MUTUAL: matches0[i] = raw0[i] if raw0[i] = j >= 0 and raw1[j] == i, else -1 (matches1 likewise); without the flag matches = raw.
+ *             scores0[i] = (s1 + 1) / 2 where matches0[i] > -1, else 0.  The list holds the rows (i, matches0[i]) in ascending i and their scores.
+ *   Rows at or beyond num0 / num1 come back as -1 / 0 and are never read (they may hold anything); an empty side gives all -1.  NaN / inf inside live rows is
+ *   outside the contract (no fault, nothing written out of bounds).
+ * Pairs: with LG_FLAG_INDEXED exactly as in lg_forward_io: desc / num are per image of a store and pair p reads images index0[p], index1[p] (an index outside its store:
+ *   status LG_ERR_INDEX, the pair is not matched); without it pair p reads image p of either side (images0 / images1 are not read).  Any number of pairs runs in
+ *   one call.  The per-side bits LG_FLAG_DESC*_F16, LG_FLAG_DESC*_U8, LG_FLAG_ROOTSIFT* mean what they mean to the engine (LG_FLAG_EXT is not needed).
+ * Workspace: lg_nn_workspace_bytes(images0, images1, n0, n1, dim, flags) bytes, 256-byte aligned — the normalised fp32 rows of both stores (each row of an image
+ *   the pair list touches is prepared once per call) plus one byte per image: it does not depend on the number of pairs.  -1 for arguments outside the envelope.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): dim a multiple of 16 in [16, 256]; n0, n1 in [0, LG_MAX_KEYPOINTS]; a store of at most
+ *   2^31 - 1 rows; descriptor pointers 16-byte aligned; ratio_threshold <= 1; no unknown flag; no null pointer among the required ones.
+ * A workgroup of the matching kernel owns LG_NN_ROWS_PER_WORKGROUP rows of one side and streams the other side through LDS LG_NN_TILE rows at a time. */
+#define LG_FLAG_NN_MUTUAL 1024u
+#define LG_NN_ROWS_PER_WORKGROUP 128
+#define LG_NN_TILE 64
+typedef struct lg_nn_io {
+    int32_t pairs, n0, n1, dim;
+    uint32_t flags;                        /* LG_FLAG_INDEXED | LG_FLAG_DESC*_F16 | LG_FLAG_DESC*_U8 | LG_FLAG_ROOTSIFT* | LG_FLAG_NN_MUTUAL */
+    float ratio_threshold;                 /* in (0, 1]; <= 0: no ratio test                                           */
+    float distance_threshold;              /* > 0; <= 0: no distance test                                             */
+    const void *desc0, *desc1;             /* [pairs or images][n][dim] in the side's storage format                  */
+    const int32_t *num0, *num1;            /* [pairs or images] live rows, or NULL = n                                */
+    const int32_t *index0, *index1;        /* [pairs], LG_FLAG_INDEXED                                                */
+    int32_t images0, images1;              /* LG_FLAG_INDEXED: images in either store, >= 1                           */
+    void *workspace; int64_t workspace_bytes;
+    int32_t *raw0, *raw1;                  /* [pairs][n0], [pairs][n1]: the one-directional result; rows >= num are not written */
+    int64_t *matches0, *matches1;          /* [pairs][n0], [pairs][n1]                                                */
+    float *scores0, *scores1;              /* [pairs][n0], [pairs][n1]                                                */
+    int64_t *matches; float *match_scores; /* [pairs][list_rows][2], [pairs][list_rows]; rows >= n_matches[p] are not written */
+    int32_t list_rows;                     /* >= min(n0, n1) with LG_FLAG_NN_MUTUAL, else >= n0                       */
+    int32_t *n_matches;                    /* [pairs]                                                                 */
+    int32_t *status;                       /* [pairs] LG_OK / LG_ERR_INDEX                                            */
+    /* optional (NULL = not written): the fields of the matcher's output dict that are constant here, so that no other kernel has to fill them */
+    int32_t *stop; int64_t *stop_i64;      /* [pairs] zeros                                                           */
+    float *prune0, *prune1;                /* [pairs][n0], [pairs][n1] zeros                                          */
+} lg_nn_io;
+int64_t lg_nn_workspace_bytes(int64_t images0, int64_t images1, int32_t n0, int32_t n1, int32_t dim, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_nn_match(const lg_nn_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

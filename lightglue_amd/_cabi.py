@@ -21,6 +21,8 @@ LG_FLAG_DESC0_F16, LG_FLAG_DESC1_F16 = 16, 32   # desc0 / desc1 are binary16 row
 LG_FLAG_DESC0_U8, LG_FLAG_DESC1_U8 = 64, 128    # desc0 / desc1 are uint8 rows (SIFT as COLMAP / OpenCV store it), read in place
 LG_FLAG_ROOTSIFT0, LG_FLAG_ROOTSIFT1 = 256, 512   # RootSIFT of every row of desc0 / desc1 where the descriptors enter the engine
 LG_DESC_KIND = {"float32": 0, "float16": 1, "uint8": 2}   # lg_rootsift src_kind
+LG_FLAG_NN_MUTUAL = 1024                          # lg_nn_match: keep a match only if both directions agree
+LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
 # every symbol include/lightglue_amd.h declares (tests check the library exports all of them)
@@ -39,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
     "lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half",
     "lg_rootsift", "lg_sift_filter_workspace_bytes", "lg_sift_filter",
+    "lg_nn_workspace_bytes", "lg_nn_match",
 )
 
 
@@ -82,6 +85,19 @@ class LgUnpackIO(C.Structure):
         ("prune0_i64", _fp), ("prune1_i64", _fp), ("prune0_f32", _fp), ("prune1_f32", _fp),
         ("matches", _fp), ("match_scores", _fp),
         ("info", _fp),
+    ]
+
+
+class LgNnIO(C.Structure):
+    """lg_nn_io (include/lightglue_amd.h): one call of the nearest-neighbour matcher"""
+    _fields_ = [
+        ("pairs", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32), ("dim", C.c_int32), ("flags", C.c_uint32),
+        ("ratio_threshold", C.c_float), ("distance_threshold", C.c_float),
+        ("desc0", _fp), ("desc1", _fp), ("num0", _fp), ("num1", _fp), ("index0", _fp), ("index1", _fp), ("images0", C.c_int32), ("images1", C.c_int32),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("raw0", _fp), ("raw1", _fp), ("matches0", _fp), ("matches1", _fp), ("scores0", _fp), ("scores1", _fp),
+        ("matches", _fp), ("match_scores", _fp), ("list_rows", C.c_int32), ("n_matches", _fp), ("status", _fp),
+        ("stop", _fp), ("stop_i64", _fp), ("prune0", _fp), ("prune1", _fp),
     ]
 
 
@@ -207,6 +223,9 @@ def load() -> C.CDLL:
     lib.lg_sift_filter_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lg_sift_filter_workspace_bytes.restype = C.c_int64
     lib.lg_sift_filter.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lg_nn_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    lib.lg_nn_workspace_bytes.restype = C.c_int64
+    lib.lg_nn_match.argtypes = [C.POINTER(LgNnIO), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

@@ -81,6 +81,26 @@ def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS
     return out
 
 
+def pair_list(pairs, K0: int, K1: int, validate: bool = True) -> torch.Tensor:
+    """THE pair list of a `match_pairs` call (LightGlue's and NearestNeighborMatcher's): `pairs` (sequence, CPU or device tensor) -> an integer tensor [P, 2].
+    validate: shape, dtype and range are checked on the host (a device tensor is copied there once) and a ValueError names the offending positions."""
+    as_given = torch.is_tensor(pairs)
+    pt = pairs if as_given else torch.as_tensor(pairs)
+    if not as_given and pt.numel() == 0:
+        pt = pt.reshape(0, 2).to(torch.int64)
+    if pt.dim() != 2 or pt.shape[1] != 2:
+        raise ValueError(f"pairs must have shape [P, 2], got {tuple(pt.shape)}")
+    if pt.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"pairs must hold integers, got {pt.dtype}")
+    if validate and pt.shape[0]:
+        host = pt.cpu()
+        lo, hi0, hi1 = int(host.min()), int(host[:, 0].max()), int(host[:, 1].max())
+        if lo < 0 or hi0 >= K0 or hi1 >= K1:
+            bad = ((host < 0) | (host >= torch.tensor([K0, K1]))).any(1).nonzero().flatten().tolist()
+            raise ValueError(f"pairs {bad[:8]} index outside the feature stores of {K0} and {K1} images")
+    return pt
+
+
 # ---------------------------------------------------------------------- one side of a call
 def _engine_descriptors(t: torch.Tensor, device, keep=(torch.float16, torch.uint8)) -> torch.Tensor:
     """Descriptors as the engine reads them; the returned tensor's dtype is the side's storage format.  float16 and uint8 (SIFT as COLMAP / OpenCV store it)

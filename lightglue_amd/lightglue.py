@@ -450,22 +450,8 @@ class LightGlue(nn.Module):
         same = feats1 is None or feats1 is feats0
         K0 = int(feats0["keypoints"].shape[0])
         K1 = K0 if same else int(feats1["keypoints"].shape[0])
-        # ---- the pair list: [P, 2] integers
-        as_given = torch.is_tensor(pairs)
-        pt = pairs if as_given else torch.as_tensor(pairs)
-        if not as_given and pt.numel() == 0:
-            pt = pt.reshape(0, 2).to(torch.int64)
-        if pt.dim() != 2 or pt.shape[1] != 2:
-            raise ValueError(f"pairs must have shape [P, 2], got {tuple(pt.shape)}")
-        if pt.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-            raise ValueError(f"pairs must hold integers, got {pt.dtype}")
+        pt = _call.pair_list(pairs, K0, K1, validate)
         P = int(pt.shape[0])
-        if validate and P:
-            host = pt.cpu()
-            lo, hi0, hi1 = int(host.min()), int(host[:, 0].max()), int(host[:, 1].max())
-            if lo < 0 or hi0 >= K0 or hi1 >= K1:
-                bad = ((host < 0) | (host >= torch.tensor([K0, K1]))).any(1).nonzero().flatten().tolist()
-                raise ValueError(f"pairs {bad[:8]} index outside the feature stores of {K0} and {K1} images")
         device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
         self.last_pair_chunks = chunks = plan_pair_chunks(P, s0.N, s1.N, max_rows, max_sim)
         o = self._outputs(P, s0, s1, device)
