@@ -256,22 +256,46 @@ int lg_engine_profile_enable(lg_engine* e, int32_t on);
 /* Accumulated milliseconds and launch-site counts per class since the last read (resets). */
 int lg_engine_profile_read(lg_engine* e, double* ms, int64_t* count, int32_t n_classes);
 
+/* ------------------------------------------------------------------------------------------------
+ * The extractor stages (SuperPoint: encode, detect, sample descriptors; ALIKED: encode, detect, describe): ONE entry point per stage,
+ *   int lg_<stage>(const lg_<stage>_io* io, void* hip_stream)
+ * in the form of lg_forward_io / lg_nn_io: the arguments are named fields of one struct and the variants of a stage are bits of `flags`, shared by the six:
+ *   LG_EXTRACT_RAGGED    images of DIFFERENT sizes in one call: `sizes` is read — a device array int32 [batch][2] = (w_b, h_b) — the arrays of the call are
+ *                        CANVASES and image b their top-left corner.  Which (w, h) a stage's `sizes` holds is said at its struct.  Rule of every kernel: addresses
+ *                        and strides come from the canvas, every bound (zero padding, stores, pooling, NMS padding, borders, grid normalisation) from the image,
+ *                        so nothing outside an image is read — the canvas padding may hold anything, NaN included — and for every image the outputs are
+ *                        BIT-IDENTICAL to the batch-1 call on its h_b x w_b crop.  The kernels clamp `sizes` into the canvas (a bad value cannot address outside a buffer);
+ *                        validating them (8 <= size <= canvas) is the caller's job, who has them as host integers.  Without the flag `sizes` is never read.
+ *   LG_EXTRACT_DESC_F16  lg_sp_sample_descriptors / lg_aliked_describe: the descriptor output is IEEE binary16 instead of fp32 — the last kernel rounds its fp32
+ *                        result once, to nearest even, on store: bit-identical to converting the fp32 output, zero padding rows included, at half the bytes written
+ *                        (and read by the matcher: LG_FLAG_DESC0_F16 / _DESC1_F16).
+ *   LG_EXTRACT_SPLIT     lg_sp_encode: the conv stack on split-f16 operands (see there).
+ * Refused with LG_ERR_INVALID and a message before the GPU is touched, by every stage alike: a null `io`; a flag bit the stage does not define (LG_EXTRACT_SPLIT
+ * on anything but lg_sp_encode, LG_EXTRACT_DESC_F16 on an encode or detect stage, any other bit); LG_EXTRACT_RAGGED with sizes == NULL ("null pointer").
+ * All data pointers are device pointers; kernels are enqueued on the caller's stream; no stage allocates or synchronises. */
+#define LG_EXTRACT_RAGGED   1u   /* `sizes` is read: the arrays are canvases, image b their top-left corner */
+#define LG_EXTRACT_DESC_F16 2u   /* the descriptor output is binary16, rounded once on the last kernel's store */
+#define LG_EXTRACT_SPLIT    4u   /* SuperPoint conv stack on split-f16 operands */
+
 /* ---- SuperPoint descriptor head: the producer of the matcher's descriptor tensors ----
  * Replaces, for descriptor_dim 256 and cell size s (8), the tail of SuperPoint.forward
  * (lightglue/superpoint.py:216-228): optional dense L2 normalisation of the descriptor map (:218),
  * sample_descriptors (:80-95: bilinear grid_sample with align_corners=True and zero padding + L2
- * normalisation) and the transpose to [B][N][256] (:228).  Stateless; all pointers are device pointers.
- *   desc_map   [B][256][h][w] fp32 (NCHW)         keypoints [B][N][2] fp32 pixel (x, y)
- *   num        [B] live keypoints per image or NULL; rows >= num[b] of `out` are zero-filled
- *   workspace  [B][h][w][256] fp32 scratch          out       [B][N][256] fp32 */
-int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w,
-                             const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
-                             int32_t normalize_dense, float* workspace, float* out, void* hip_stream);
-/* The same with `out` [B][N][256] as IEEE binary16: the last kernel rounds its fp32 result once, to nearest even, on store — bit-identical to converting the fp32
- * output, zero padding rows included, at half the bytes written (and read by the matcher: LG_FLAG_DESC0_F16 / _DESC1_F16). */
-int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w,
-                                 const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
-                                 int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream);
+ * normalisation) and the transpose to [B][N][256] (:228).  Stateless.
+ * LG_EXTRACT_RAGGED: `desc_map` is a descriptor canvas [batch][256][h][w] (as lg_sp_encode wrote it for the same batch) and `sizes` holds the IMAGES' (w_b, h_b):
+ * the map of image b is its top-left (h_b / cell, w_b / cell) corner, which alone is read; the grid normalisation and the zero padding of the sampling are that map's. */
+typedef struct lg_sp_sample_io {
+    int32_t batch, channels, h, w;         /* of desc_map; channels must be 256                                      */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED | LG_EXTRACT_DESC_F16                                 */
+    const float *desc_map;                 /* [B][256][h][w] fp32 (NCHW)                                              */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [B][2] (w, h) of the IMAGES                          */
+    const float *keypoints;                /* [B][N][2] fp32 pixel (x, y)                                             */
+    const int32_t *num;                    /* [B] live keypoints per image or NULL; rows >= num[b] of `out` are zero-filled */
+    int32_t n, cell, normalize_dense;      /* N; cell size s; != 0: the dense L2 normalisation                        */
+    float *workspace;                      /* [B][h][w][256] fp32 scratch                                             */
+    void *out;                             /* [B][N][256] fp32, or binary16 with LG_EXTRACT_DESC_F16                  */
+} lg_sp_sample_io;
+int lg_sp_sample_descriptors(const lg_sp_sample_io* io, void* hip_stream);
 
 /* ---- SuperPoint conv stack (replaces superpoint.py:127-141 layers and :159-184, :213-214 of forward) ----
  * lg_sp_pack_conv_weight: repack one nn.Conv2d weight [cout][cin][k][k] (device fp32) into the layout the kernels read,
@@ -282,20 +306,33 @@ int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t 
  *   desc_map [batch][256][h/8][w/8]   RAW convDb output (NCHW), the input of lg_sp_sample_descriptors(normalize_dense = 1)
  *   params: 24 device pointers = (packed weight, bias) of conv1a, conv1b, conv2a, conv2b, conv3a, conv3b, conv4a, conv4b,
  *           convPa, convPb, convDa, convDb; workspace: lg_sp_encode_workspace_bytes(batch, h, w) bytes.
- * Exact fp32 arithmetic (f32 MFMA): scores agree with an fp32 convolution to round-off. */
-int lg_sp_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t k, float* dst, void* hip_stream);
-int64_t lg_sp_encode_workspace_bytes(int32_t batch, int32_t h, int32_t w);
-int lg_sp_encode(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                 int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream);
-/* Opt-in split-f16 form of the same stack (SuperPoint(conv_precision="f16x3")): every MFMA convolution multiplies hi + lo f16 planes of its operands (22 bits) with three
+ * Exact fp32 arithmetic (f32 MFMA): scores agree with an fp32 convolution to round-off.
+ * LG_EXTRACT_SPLIT, the opt-in split-f16 form of the same stack (SuperPoint(conv_precision="f16x3")): every MFMA convolution multiplies hi + lo f16 planes of its operands (22 bits) with three
  * v_mfma_f32_16x16x32_f16 per product and fp32 accumulation — the dropped lo x lo term is 2^-24-class, i.e. below the summation-order noise of an fp32 convolution — at a
- * multiple of the f32 MFMA rate.  Values must lie inside the f16 range (|x| < 65504); conv1a (K = 9) stays fp32.
+ * multiple of the f32 MFMA rate.  Values must lie inside the f16 range (|x| < 65504); conv1a (K = 9) stays fp32.  For images — with LG_EXTRACT_RAGGED: a canvas — of
+ * h * w < 2^25 pixels (32-bit element offsets inside one image, whose strides are the canvas's; larger ones are refused); params[0..1] (conv1a) packed by
+ * lg_sp_pack_conv_weight, the weights of the other eleven layers by lg_sp_pack_conv_weight_split.
  * lg_sp_pack_conv_weight_split: [cout][cin][k][k] fp32 -> hi / lo f16 planes in the order the kernels read (k = 1: [2 planes][cout][cin]; k = 3: MFMA-fragment order
  *   [cout / 64][cin / 32][tap][4 n-tiles][2 planes][64 lanes][8], cout % 64 == 0); dst holds cout*cin*k*k*4 BYTES (as the fp32 form).  cin % 32 == 0.
- * lg_sp_encode_split: as lg_sp_encode, for images of h * w < 2^25 pixels (32-bit element offsets inside one image; larger ones are refused); params[0..1] (conv1a) packed by lg_sp_pack_conv_weight, the weights of the other eleven layers by lg_sp_pack_conv_weight_split. */
+ * LG_EXTRACT_RAGGED: the batch is a canvas [batch][1][h][w]; image b is its top-left h_b x w_b corner, 8 <= h_b <= h, 8 <= w_b <= w, and `sizes` holds the IMAGES'
+ * (w_b, h_b).  Nothing outside an image is read — the canvas padding may hold anything, NaN included; every bound (zero padding, stores, pooling) is the image's.
+ * Extents: pyramid level k (h_b >> k, w_b >> k) inside the canvas (h >> k, w >> k); score map ((h_b >> 3) << 3, (w_b >> 3) << 3); descriptor map (h_b >> 3, w_b >> 3).
+ * The workspace is lg_sp_encode_workspace_bytes(batch, h, w) of the canvas.  scores [batch][h/8*8][w/8*8]: 0 outside an image's score map; desc_map
+ * [batch][256][h/8][w/8]: unspecified outside an image's map (and never read by lg_sp_sample_descriptors under the same flag).
+ * Null pointers (a null layer parameter among them), batch < 1, an image or canvas below 8 x 8 and a workspace too small are refused before the GPU is touched. */
+int lg_sp_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t k, float* dst, void* hip_stream);
 int lg_sp_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t k, void* dst, void* hip_stream);
-int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                       int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream);
+int64_t lg_sp_encode_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+typedef struct lg_sp_encode_io {
+    int32_t batch, h, w;                   /* of `image` (LG_EXTRACT_RAGGED: the canvas)                              */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED | LG_EXTRACT_SPLIT                                    */
+    const float *image;                    /* [batch][1][h][w] fp32                                                   */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [batch][2] (w, h) of the IMAGES                      */
+    const float *const *params;            /* HOST array of the 24 device pointers                                    */
+    void *workspace; int64_t workspace_bytes;
+    float *scores, *desc_map;              /* [batch][h/8*8][w/8*8], [batch][256][h/8][w/8]                           */
+} lg_sp_encode_io;
+int lg_sp_encode(const lg_sp_encode_io* io, void* hip_stream);
 
 /* Keypoint extraction from SuperPoint's dense score map: replaces simple_nms (lightglue/superpoint.py:52-70), the
  * border removal, thresholding, per-image split (:186-204), top_k_keypoints (:73-77, :207-215) and the (y, x) -> (x, y)
@@ -305,40 +342,24 @@ int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, 
  *   order, otherwise (<= 4096) the max_keypoints best sorted by score when more were found (the reference's rule).
  *   keypoints [B][capacity][2] (x, y), kp_scores [B][capacity], counts [B] rows written per image;
  *   totals [B] or NULL: detections above the threshold before top-k / clipping (> max_candidates = overflow).
- *   workspace: lg_sp_detect_workspace_bytes(...) bytes of device scratch. */
+ *   workspace: lg_sp_detect_workspace_bytes(...) bytes of device scratch.
+ * LG_EXTRACT_RAGGED: `scores` is a score canvas [batch][h][w], h, w >= 8, and here `sizes` holds the (w, h) of the SCORE maps (after lg_sp_encode under the same
+ * flag: whole cells, (w_b >> 3) << 3).  Pixels outside a map are max_pool2d's -inf padding — not zeros, which would be maxima of their own and suppress real maxima
+ * next to the far border — and never pass the threshold; the far borders are the map's.  Keypoints are (x, y) in the image's own frame (the corner is the origin). */
 int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t max_candidates);
-int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32_t nms_radius, int32_t remove_borders,
-                 float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates,
-                 void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts,
-                 int32_t* totals, void* hip_stream);
-
-/* ---- SuperPoint on a ragged batch: images of different sizes in ONE call ----
- * The batch is a canvas [batch][1][hc][wc]; image b is its top-left h_b x w_b corner, 8 <= h_b <= hc, 8 <= w_b <= wc, and `sizes` is a device array
- * int32 [batch][2] = (w_b, h_b).  Rule of every kernel: addresses and strides come from the canvas, every bound (zero padding, stores, pooling, NMS padding,
- * borders, grid normalisation) from the image, so nothing outside an image is read — the canvas padding may hold anything, NaN included — and for every image the
- * outputs are BIT-IDENTICAL to the batch-1 call on its h_b x w_b crop.  Extents: pyramid level k (h_b >> k, w_b >> k) inside the canvas (hc >> k, wc >> k); score map
- * ((h_b >> 3) << 3, (w_b >> 3) << 3); descriptor map (h_b >> 3, w_b >> 3).  The kernels clamp `sizes` into the canvas (a bad value cannot address outside a
- * buffer); validating them is the caller's job, who has them as host integers.  Null pointers, batch < 1 and a canvas below 8 x 8 are refused before the GPU is touched.
- * lg_sp_encode_ragged: lg_sp_encode (split == 0) / lg_sp_encode_split (split != 0: the canvas hc * wc < 2^25 pixels) on the canvas; workspace
- *   lg_sp_encode_workspace_bytes(batch, hc, wc).  scores [batch][hc/8*8][wc/8*8]: 0 outside an image's score map; desc_map [batch][256][hc/8][wc/8]: unspecified outside
- *   an image's map (and never read by lg_sp_sample_descriptors_ragged).
- * lg_sp_detect_ragged: lg_sp_detect on a score canvas [batch][h][w]; here `sizes` holds the (w, h) of the SCORE maps (after lg_sp_encode_ragged: whole cells,
- *   (w_b >> 3) << 3).  Pixels outside a map are max_pool2d's -inf padding — not zeros, which would be maxima of their own and suppress real maxima next to the far
- *   border — and never pass the threshold; the far borders are the map's.  Keypoints are (x, y) in the image's own frame (the corner is the origin).
- * lg_sp_sample_descriptors_ragged(_half): lg_sp_sample_descriptors(_half) on a descriptor canvas [batch][256][h][w]; `sizes` holds the IMAGES' (w_b, h_b): the map
- *   of image b is (h_b / cell, w_b / cell). */
-int lg_sp_encode_ragged(const float* image, int32_t batch, int32_t hc, int32_t wc, const int32_t* sizes, const float* const* params, void* workspace,
-                        int64_t workspace_bytes, float* scores, float* desc_map, int32_t split, void* hip_stream);
-int lg_sp_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
-                        float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates,
-                        void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts,
-                        int32_t* totals, void* hip_stream);
-int lg_sp_sample_descriptors_ragged(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes,
-                                    const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
-                                    int32_t normalize_dense, float* workspace, float* out, void* hip_stream);
-int lg_sp_sample_descriptors_ragged_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes,
-                                         const float* keypoints, const int32_t* num, int32_t n, int32_t cell,
-                                         int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream);
+typedef struct lg_sp_detect_io {
+    int32_t batch, h, w;                   /* of `scores`                                                             */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED                                                       */
+    const float *scores;                   /* [B][h][w] fp32                                                          */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [B][2] (w, h) of the SCORE maps                      */
+    int32_t nms_radius, remove_borders;
+    float detection_threshold;
+    int32_t max_keypoints, capacity, max_candidates;
+    void *workspace; int64_t workspace_bytes;
+    float *keypoints, *kp_scores;          /* [B][capacity][2] (x, y), [B][capacity]                                  */
+    int32_t *counts, *totals;              /* [B]; totals may be NULL                                                 */
+} lg_sp_detect_io;
+int lg_sp_detect(const lg_sp_detect_io* io, void* hip_stream);
 
 /* ---- ALIKED extractor (aliked-n16 / n16rot / n32; lightglue/aliked.py:612-760) ----
  * Exact fp32 arithmetic throughout.  `n_pos` selects the model: 16 (aliked-n16, aliked-n16rot) or 32 (aliked-n32); anything else is
@@ -359,29 +380,10 @@ int lg_sp_sample_descriptors_ragged_half(const float* desc_map, int32_t batch, i
  *   image_size [batch][2] (w, h) or NULL.  keypoints [batch][capacity][2] pixel (x, y), kp_scores [batch][capacity], kp_norm [batch][capacity][2]
  *   (the (-1, 1) frame lg_aliked_describe reads), counts [batch]; rows >= counts[b] are zero.  workspace: lg_aliked_detect_workspace_bytes.
  * lg_aliked_describe: SDDH descriptors [batch][n][128] for kp_norm [batch][n][2] (rows >= counts[b] give zero rows); n <= 20000;
- *   workspace: lg_aliked_describe_workspace_bytes(batch * n, n_pos). */
-int64_t lg_aliked_packed_bytes(int32_t n_pos);
-int lg_aliked_pack_weights(int32_t n_pos, const float* const* tensors, int32_t n_tensors, void* packed, int64_t packed_bytes, void* hip_stream);
-int64_t lg_aliked_levels_bytes(int32_t batch, int32_t h, int32_t w);
-int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n_pos);
-int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
-                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream);
-int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity);
-int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th,
-                     int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
-                     float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream);
-int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos);
-int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
-                       const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
-/* lg_aliked_describe with `descriptors` [batch][n][128] as IEEE binary16: the fp32 result rounded once, to nearest even, by the last kernel's store (bit-identical
- * to converting the fp32 output; rows >= counts[b] are zero). */
-int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm,
-                           const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream);
-
-/* ---- ALIKED on a ragged batch: images of different sizes in ONE call ----
- * Each function is its uniform twin plus `sizes`: int32 [batch][2] (w_b, h_b) on the device, and h, w are the CANVAS.  The kernels clamp every size into
- * [1, canvas], so a bad size cannot address outside a buffer; validation proper (8 <= size <= canvas) is the caller's, who has the sizes as host integers.
- * Geometry:
+ *   workspace: lg_aliked_describe_workspace_bytes(batch * n, n_pos).
+ *
+ * LG_EXTRACT_RAGGED, for all three: `sizes` holds the IMAGES' (w_b, h_b) and h, w are the CANVAS.  The kernels clamp every size into [1, canvas], so a bad size
+ * cannot address outside a buffer; validation proper (8 <= size <= canvas) is the caller's, who has the sizes as host integers.  Geometry:
  *   * image b is the top-left h_b x w_b corner of image[b] ([batch][channels][h][w]); nothing outside it is read (the canvas padding may hold anything).
  *   * each image keeps its OWN InputPadder(divis_by = 32) geometry: Hp_b, Wp_b (h_b, w_b rounded up to 32), pt_b = (Hp_b - h_b) / 2, pl_b = (Wp_b - w_b) / 2,
  *     centred, replicated from the image's own border pixels.
@@ -391,20 +393,54 @@ int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_
  *   * addresses and strides come from the canvas, every bound from the image: on no level is anything outside an image's padded frame read (workspace and
  *     level rows there are never written either).  The one exception: scores [batch][h][w] is written 0 outside each image, so it is defined everywhere.
  * Inside the image every output is bit-identical to the uniform call with batch = 1 on the crop.
- * lg_aliked_detect_ragged: the far borders, the soft-argmax window's zero padding, the (w - 1, h - 1) factors and the mean are image b's; keypoints are in its own
- *   frame.  The fallback "no pixel passes scores_th -> the image's mean score" is decided PER IMAGE (the uniform call keeps the reference's whole-batch rule):
- *   a ragged batch is a set of independent images, each equal to its own batch of one.  image_size: as for lg_aliked_detect (NULL: the sizes).
- * lg_aliked_describe_ragged(_half): `levels` as lg_aliked_encode_ragged wrote them for the same batch, h, w, sizes. */
-int lg_aliked_encode_ragged(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
-                            void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream);
-int lg_aliked_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius,
-                            float scores_th, int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
-                            float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream);
-int lg_aliked_describe_ragged(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm,
-                              const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream);
-int lg_aliked_describe_ragged_half(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
-                                   const float* kp_norm, const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors,
-                                   void* hip_stream);
+ * lg_aliked_detect under the flag: the far borders, the soft-argmax window's zero padding, the (w - 1, h - 1) factors and the mean are image b's; keypoints are in
+ *   its own frame.  The fallback "no pixel passes scores_th -> the image's mean score" is decided PER IMAGE (the uniform call keeps the reference's whole-batch
+ *   rule): a ragged batch is a set of independent images, each equal to its own batch of one.  image_size: as without the flag (NULL: the sizes).
+ * lg_aliked_describe under the flag: `levels` as lg_aliked_encode wrote them under it for the same batch, h, w, sizes. */
+int64_t lg_aliked_packed_bytes(int32_t n_pos);
+int lg_aliked_pack_weights(int32_t n_pos, const float* const* tensors, int32_t n_tensors, void* packed, int64_t packed_bytes, void* hip_stream);
+int64_t lg_aliked_levels_bytes(int32_t batch, int32_t h, int32_t w);
+int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n_pos);
+typedef struct lg_aliked_encode_io {
+    int32_t batch, channels, h, w, n_pos;  /* of `image` (LG_EXTRACT_RAGGED: the canvas); the model                   */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED                                                       */
+    const float *image;                    /* [batch][channels = 1 | 3][h][w] fp32                                    */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [batch][2] (w, h) of the IMAGES                      */
+    const void *packed;                    /* lg_aliked_pack_weights' buffer                                          */
+    void *levels;                          /* lg_aliked_levels_bytes(batch, h, w) bytes                               */
+    void *workspace; int64_t workspace_bytes;
+    float *scores;                         /* [batch][h][w]                                                           */
+} lg_aliked_encode_io;
+int lg_aliked_encode(const lg_aliked_encode_io* io, void* hip_stream);
+int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity);
+typedef struct lg_aliked_detect_io {
+    int32_t batch, h, w;                   /* of `scores`                                                             */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED                                                       */
+    const float *scores;                   /* [batch][h][w]                                                           */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [batch][2] (w, h) of the IMAGES                      */
+    const float *image_size;               /* [batch][2] (w, h) or NULL                                               */
+    int32_t nms_radius;
+    float scores_th;
+    int32_t top_k, n_limit, capacity;
+    void *workspace; int64_t workspace_bytes;
+    float *keypoints, *kp_scores, *kp_norm;   /* [batch][capacity][2], [batch][capacity], [batch][capacity][2]        */
+    int32_t *counts;                       /* [batch]                                                                 */
+} lg_aliked_detect_io;
+int lg_aliked_detect(const lg_aliked_detect_io* io, void* hip_stream);
+int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos);
+typedef struct lg_aliked_describe_io {
+    int32_t batch, h, w, n_pos;            /* of the images `levels` was encoded from (LG_EXTRACT_RAGGED: the canvas); the model */
+    uint32_t flags;                        /* LG_EXTRACT_RAGGED | LG_EXTRACT_DESC_F16                                 */
+    const void *levels;                    /* as lg_aliked_encode wrote them                                          */
+    const int32_t *sizes;                  /* LG_EXTRACT_RAGGED: [batch][2] (w, h) of the IMAGES                      */
+    const void *packed;
+    const float *kp_norm;                  /* [batch][n][2]                                                           */
+    const int32_t *counts;                 /* [batch]                                                                 */
+    int32_t n;
+    void *workspace; int64_t workspace_bytes;
+    void *descriptors;                     /* [batch][n][128] fp32, or binary16 with LG_EXTRACT_DESC_F16 (rows >= counts[b] are zero) */
+} lg_aliked_describe_io;
+int lg_aliked_describe(const lg_aliked_describe_io* io, void* hip_stream);
 
 /* ---- ImagePreprocessor (lightglue/utils.py:12-38): the resize in front of the extractors, one fused kernel (lg_preprocess.hip) ----
  * What the reference computes through kornia.geometry.transform.resize (always bilinear: `interpolation` is not forwarded):

@@ -22,6 +22,7 @@ LG_FLAG_DESC0_U8, LG_FLAG_DESC1_U8 = 64, 128    # desc0 / desc1 are uint8 rows (
 LG_FLAG_ROOTSIFT0, LG_FLAG_ROOTSIFT1 = 256, 512   # RootSIFT of every row of desc0 / desc1 where the descriptors enter the engine
 LG_DESC_KIND = {"float32": 0, "float16": 1, "uint8": 2}   # lg_rootsift src_kind
 LG_FLAG_NN_MUTUAL = 1024                          # lg_nn_match: keep a match only if both directions agree
+LG_EXTRACT_RAGGED, LG_EXTRACT_DESC_F16, LG_EXTRACT_SPLIT = 1, 2, 4   # the extractor stages' io flags: `sizes` is read / binary16 descriptors / split-f16 SuperPoint conv stack
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
@@ -32,14 +33,11 @@ EXPORTED_SYMBOLS = (
     "lg_engine_debug_stop_after", "lg_engine_debug_read", "lg_engine_debug_caps",
     "lg_profile_num_classes", "lg_profile_class_name", "lg_engine_profile_enable", "lg_engine_profile_read",
     "lg_sp_sample_descriptors", "lg_sp_detect_workspace_bytes", "lg_sp_detect",
-    "lg_sp_pack_conv_weight", "lg_sp_encode_workspace_bytes", "lg_sp_encode", "lg_sp_pack_conv_weight_split", "lg_sp_encode_split", "lg_debug_mfma_sustained",
+    "lg_sp_pack_conv_weight", "lg_sp_encode_workspace_bytes", "lg_sp_encode", "lg_sp_pack_conv_weight_split", "lg_debug_mfma_sustained",
     "lg_aliked_packed_bytes", "lg_aliked_pack_weights", "lg_aliked_levels_bytes", "lg_aliked_workspace_bytes", "lg_aliked_encode",
     "lg_aliked_detect_workspace_bytes", "lg_aliked_detect", "lg_aliked_describe_workspace_bytes", "lg_aliked_describe",
     "lg_preprocess_plan", "lg_preprocess_resize",
     "lg_preprocess_ragged_table_bytes", "lg_preprocess_ragged_plan", "lg_preprocess_resize_ragged",
-    "lg_sp_sample_descriptors_half", "lg_aliked_describe_half",
-    "lg_sp_encode_ragged", "lg_sp_detect_ragged", "lg_sp_sample_descriptors_ragged", "lg_sp_sample_descriptors_ragged_half",
-    "lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half",
     "lg_rootsift", "lg_sift_filter_workspace_bytes", "lg_sift_filter",
     "lg_nn_workspace_bytes", "lg_nn_match",
 )
@@ -99,6 +97,71 @@ class LgNnIO(C.Structure):
         ("matches", _fp), ("match_scores", _fp), ("list_rows", C.c_int32), ("n_matches", _fp), ("status", _fp),
         ("stop", _fp), ("stop_i64", _fp), ("prune0", _fp), ("prune1", _fp),
     ]
+
+
+# The io structs of the six extractor stages (include/lightglue_amd.h): the variants of a stage are bits of `flags` (LG_EXTRACT_*), `sizes` is read only with
+# LG_EXTRACT_RAGGED.  tests/test_cabi_symbols.py checks field order AND element types against the header.
+_i32 = C.c_int32
+
+
+class LgSpSampleIO(C.Structure):
+    """lg_sp_sample_io: lg_sp_sample_descriptors"""
+    _fields_ = [
+        ("batch", _i32), ("channels", _i32), ("h", _i32), ("w", _i32), ("flags", C.c_uint32),
+        ("desc_map", _fp), ("sizes", _fp), ("keypoints", _fp), ("num", _fp),
+        ("n", _i32), ("cell", _i32), ("normalize_dense", _i32), ("workspace", _fp), ("out", _fp),
+    ]
+
+
+class LgSpEncodeIO(C.Structure):
+    """lg_sp_encode_io: lg_sp_encode; `params` is a host array of the 24 device pointers"""
+    _fields_ = [
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("flags", C.c_uint32),
+        ("image", _fp), ("sizes", _fp), ("params", C.POINTER(C.c_void_p)), ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("scores", _fp), ("desc_map", _fp),
+    ]
+
+
+class LgSpDetectIO(C.Structure):
+    """lg_sp_detect_io: lg_sp_detect"""
+    _fields_ = [
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("flags", C.c_uint32),
+        ("scores", _fp), ("sizes", _fp), ("nms_radius", _i32), ("remove_borders", _i32), ("detection_threshold", C.c_float),
+        ("max_keypoints", _i32), ("capacity", _i32), ("max_candidates", _i32), ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("keypoints", _fp), ("kp_scores", _fp), ("counts", _fp), ("totals", _fp),
+    ]
+
+
+class LgAlikedEncodeIO(C.Structure):
+    """lg_aliked_encode_io: lg_aliked_encode"""
+    _fields_ = [
+        ("batch", _i32), ("channels", _i32), ("h", _i32), ("w", _i32), ("n_pos", _i32), ("flags", C.c_uint32),
+        ("image", _fp), ("sizes", _fp), ("packed", _fp), ("levels", _fp), ("workspace", _fp), ("workspace_bytes", C.c_int64), ("scores", _fp),
+    ]
+
+
+class LgAlikedDetectIO(C.Structure):
+    """lg_aliked_detect_io: lg_aliked_detect"""
+    _fields_ = [
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("flags", C.c_uint32),
+        ("scores", _fp), ("sizes", _fp), ("image_size", _fp), ("nms_radius", _i32), ("scores_th", C.c_float),
+        ("top_k", _i32), ("n_limit", _i32), ("capacity", _i32), ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("keypoints", _fp), ("kp_scores", _fp), ("kp_norm", _fp), ("counts", _fp),
+    ]
+
+
+class LgAlikedDescribeIO(C.Structure):
+    """lg_aliked_describe_io: lg_aliked_describe"""
+    _fields_ = [
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("n_pos", _i32), ("flags", C.c_uint32),
+        ("levels", _fp), ("sizes", _fp), ("packed", _fp), ("kp_norm", _fp), ("counts", _fp),
+        ("n", _i32), ("workspace", _fp), ("workspace_bytes", C.c_int64), ("descriptors", _fp),
+    ]
+
+
+# entry point -> its io struct
+EXTRACT_STAGES = {"lg_sp_encode": LgSpEncodeIO, "lg_sp_detect": LgSpDetectIO, "lg_sp_sample_descriptors": LgSpSampleIO,
+                  "lg_aliked_encode": LgAlikedEncodeIO, "lg_aliked_detect": LgAlikedDetectIO, "lg_aliked_describe": LgAlikedDescribeIO}
 
 
 # lg_preprocess_plan / lg_preprocess_resize (include/lightglue_amd.h)
@@ -170,25 +233,12 @@ def load() -> C.CDLL:
     lib.lg_profile_class_name.argtypes = [C.c_int32]
     lib.lg_engine_profile_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.lg_engine_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
-    lib.lg_sp_sample_descriptors.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                             C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lg_sp_sample_descriptors_half.argtypes = lib.lg_sp_sample_descriptors.argtypes
     lib.lg_sp_detect_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lg_sp_detect_workspace_bytes.restype = C.c_int64
-    lib.lg_sp_detect.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_float] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
     lib.lg_sp_pack_conv_weight.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lg_sp_encode_workspace_bytes.argtypes = [C.c_int32] * 3
     lib.lg_sp_encode_workspace_bytes.restype = C.c_int64
-    lib.lg_sp_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lg_sp_pack_conv_weight_split.argtypes = lib.lg_sp_pack_conv_weight.argtypes
-    lib.lg_sp_encode_split.argtypes = lib.lg_sp_encode.argtypes
-    # the ragged forms: `sizes` (int32 [B][2] (w, h), device) follows the map / canvas size
-    lib.lg_sp_encode_ragged.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                         C.c_int32, C.c_void_p])
-    lib.lg_sp_detect_ragged.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_float] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
-    lib.lg_sp_sample_descriptors_ragged.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lg_sp_sample_descriptors_ragged_half.argtypes = lib.lg_sp_sample_descriptors_ragged.argtypes
     lib.lg_aliked_packed_bytes.argtypes = [C.c_int32]
     lib.lg_aliked_packed_bytes.restype = C.c_int64
     lib.lg_aliked_pack_weights.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
@@ -196,22 +246,10 @@ def load() -> C.CDLL:
     lib.lg_aliked_levels_bytes.restype = C.c_int64
     lib.lg_aliked_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lg_aliked_workspace_bytes.restype = C.c_int64
-    lib.lg_aliked_encode.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]
     lib.lg_aliked_detect_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lg_aliked_detect_workspace_bytes.restype = C.c_int64
-    lib.lg_aliked_detect.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_float] + [C.c_int32] * 3
-                                     + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
     lib.lg_aliked_describe_workspace_bytes.argtypes = [C.c_int32] * 2
     lib.lg_aliked_describe_workspace_bytes.restype = C.c_int64
-    lib.lg_aliked_describe.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.lg_aliked_describe_half.argtypes = lib.lg_aliked_describe.argtypes
-    # the ragged forms: `sizes` (int32 [B][2] (w, h), device) follows the canvas size
-    lib.lg_aliked_encode_ragged.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]
-    lib.lg_aliked_detect_ragged.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_float] + [C.c_int32] * 3
-                                            + [C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
-    lib.lg_aliked_describe_ragged.argtypes = ([C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
-                                              + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
-    lib.lg_aliked_describe_ragged_half.argtypes = lib.lg_aliked_describe_ragged.argtypes
     lib.lg_preprocess_plan.argtypes = [C.c_int32] * 7 + [C.POINTER(LgResizePlan)]
     lib.lg_preprocess_resize.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_int64] * 4 + [C.POINTER(LgResizePlan), C.c_void_p, C.c_void_p]
     lib.lg_preprocess_ragged_table_bytes.argtypes = [C.c_int32]
@@ -226,6 +264,8 @@ def load() -> C.CDLL:
     lib.lg_nn_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
     lib.lg_nn_workspace_bytes.restype = C.c_int64
     lib.lg_nn_match.argtypes = [C.POINTER(LgNnIO), C.c_void_p]
+    for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
+        getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     _lib = lib
     return lib

@@ -4,11 +4,11 @@ Same module tree / parameter names as the reference class (`lightglue/aliked.py:
 `nn.BatchNorm2d` only (no torchvision, no kornia), so a released `aliked-n16.pth` / `aliked-n32.pth` loads with
 `load_state_dict(strict=True)`, and the same `forward({"image"[, "image_size"]})` contract (`:740-760`).  Everything runs in
 `lightglue_amd/csrc/lg_aliked.hip` behind the `lg_aliked_*` C entry points: the encoder, aggregation and score head
-(`lg_aliked_encode`), DKD (`lg_aliked_detect`) and SDDH (`lg_aliked_describe`), all exact fp32.  No CPU fallback.  As for
+(`lg_aliked_encode`), DKD (`lg_aliked_detect`) and SDDH (`lg_aliked_describe`), all exact fp32; each takes one io struct of named fields whose `flags` carry its variants.  No CPU fallback.  As for
 SuperPoint, `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`) and maps the keypoints back.
 
 Images of DIFFERENT sizes run in one ragged batch: a canvas with image b in its top-left corner plus `valid_size` (`forward`, `encode`, `detect`, `describe`; the
-`lg_aliked_*_ragged` entry points).  Each image keeps its own padding to a multiple of 32, and its result is bit-identical to the B = 1 call on its crop;
+`LG_EXTRACT_RAGGED` flag of the three stages' io structs).  Each image keeps its own padding to a multiple of 32, and its result is bit-identical to the B = 1 call on its crop;
 `extract_batch` builds the feature store of a mixed photo set that way (`superpoint.plan_image_batches`)."""
 from __future__ import annotations
 
@@ -23,7 +23,7 @@ from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
 from .superpoint import check_image_set, extract_groups
-from .superpoint_head import check_descriptor_dtype, check_sizes, sizes_on_device
+from .superpoint_head import check_descriptor_dtype, check_sizes, device_sizes, sizes_on_device
 
 
 class DeformableConv2d(nn.Module):
@@ -175,11 +175,6 @@ class ALIKED(nn.Module):
         sizes = None if valid_size is None else check_sizes(valid_size, image.shape[0], image.shape[-2:], 8, "valid_size")
         return self._encode(image, sizes)
 
-    @staticmethod
-    def _sizes(sizes, device):
-        """None, validated host rows (check_sizes) or the int32 device array made from them -> that device array (or None)"""
-        return sizes if sizes is None or torch.is_tensor(sizes) else sizes_on_device(sizes, device)
-
     def _encode(self, image: torch.Tensor, sizes):
         """encode with `sizes` = None, validated host rows (check_sizes) or the int32 device array made from them"""
         self._check_image(image)
@@ -195,22 +190,19 @@ class ALIKED(nn.Module):
         levels = torch.empty((nlev,), device=device, dtype=torch.uint8)
         work = torch.empty((nws,), device=device, dtype=torch.uint8)
         scores = torch.empty((bsz, h, w), device=device, dtype=torch.float32)
-        sizes = self._sizes(sizes, device)
+        sizes = device_sizes(sizes, device)
+        io = _cabi.LgAlikedEncodeIO(batch=bsz, channels=ch, h=h, w=w, n_pos=self.n_pos, flags=_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0,
+                                    image=image.data_ptr(), sizes=None if sizes is None else sizes.data_ptr(), packed=packed.data_ptr(), levels=levels.data_ptr(),
+                                    workspace=work.data_ptr(), workspace_bytes=nws, scores=scores.data_ptr())
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            if sizes is None:
-                _cabi.check(lib.lg_aliked_encode(image.data_ptr(), bsz, ch, h, w, self.n_pos, packed.data_ptr(), levels.data_ptr(), work.data_ptr(), nws,
-                                                 scores.data_ptr(), C.c_void_p(stream)))
-            else:
-                _cabi.check(lib.lg_aliked_encode_ragged(image.data_ptr(), bsz, ch, h, w, sizes.data_ptr(), self.n_pos, packed.data_ptr(), levels.data_ptr(),
-                                                        work.data_ptr(), nws, scores.data_ptr(), C.c_void_p(stream)))
+            _cabi.check(lib.lg_aliked_encode(C.byref(io), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         return scores, levels
 
     @staticmethod
     def level_maps(levels: torch.Tensor, shape):
         """The four level maps x1 .. x4 inside the opaque `levels` buffer of `encode` / `describe` for images of `shape` = (B, H, W): float32
         views [B, Hp >> s, Wp >> s, 32] for s = 0, 1, 3, 5 (NHWC, after conv1 .. conv4 + SELU) that share its memory, so a caller can read
-        the encoder's levels or write its own.  Restates the layout of lg_aliked.hip: Hp, Wp from InputPadder(divis_by=32) (`dims_of`), each
+        the encoder's levels or write its own.  Restates the layout of lg_aliked.hip: Hp, Wp from InputPadder(divis_by=32) (`frame_of`), each
         level's size rounded up to 256 bytes (`level_layout`); the total is checked against lg_aliked_levels_bytes."""
         bsz, h, w = shape
         hp, wp = h + ((h // 32 + 1) * 32 - h) % 32, w + ((w // 32 + 1) * 32 - w) % 32
@@ -252,21 +244,19 @@ class ALIKED(nn.Module):
         if image_size is not None:
             image_size = image_size.to(device=device, dtype=torch.float32).reshape(bsz, 2).contiguous()
             size_ptr = image_size.data_ptr()
-        sizes = self._sizes(sizes, device)
+        sizes = device_sizes(sizes, device)
+        io = _cabi.LgAlikedDetectIO(batch=bsz, h=h, w=w, flags=_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0, scores=scores.data_ptr(),
+                                    sizes=None if sizes is None else sizes.data_ptr(), image_size=size_ptr, nms_radius=int(self.conf.nms_radius), scores_th=th,
+                                    top_k=top_k, n_limit=n_limit, capacity=cap, workspace=work.data_ptr(), workspace_bytes=nws, keypoints=kpts.data_ptr(),
+                                    kp_scores=kscores.data_ptr(), kp_norm=knorm.data_ptr(), counts=counts.data_ptr())
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            tail = (size_ptr, int(self.conf.nms_radius), th, top_k, n_limit, cap, work.data_ptr(), nws, kpts.data_ptr(), kscores.data_ptr(), knorm.data_ptr(),
-                    counts.data_ptr(), C.c_void_p(stream))
-            if sizes is None:
-                _cabi.check(lib.lg_aliked_detect(scores.data_ptr(), bsz, h, w, *tail))
-            else:
-                _cabi.check(lib.lg_aliked_detect_ragged(scores.data_ptr(), bsz, h, w, sizes.data_ptr(), *tail))
+            _cabi.check(lib.lg_aliked_detect(C.byref(io), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         return kpts, kscores, knorm, counts
 
     @torch.no_grad()
     def describe(self, levels: torch.Tensor, shape, knorm: torch.Tensor, counts: torch.Tensor, dtype: Optional[torch.dtype] = None, valid_size=None):
         """SDDH (ref :479-609): descriptors [B, N, 128] of the normalised keypoints knorm [B, N, 2]; rows >= counts[b] are zero.  `dtype`: torch.float32, or
-        torch.float16 = the same values rounded once on store (`lg_aliked_describe_half`); None = conf.descriptor_dtype.  `valid_size` (ragged batch): `shape` is
+        torch.float16 = the same values rounded once on store (`LG_EXTRACT_DESC_F16`); None = conf.descriptor_dtype.  `valid_size` (ragged batch): `shape` is
         the canvas and `levels` what `encode(canvas, valid_size)` returned; knorm is normalised in each image's own frame."""
         sizes = None if valid_size is None else check_sizes(valid_size, shape[0], shape[1:], 8, "valid_size")
         return self._describe(levels, shape, knorm, counts, dtype, sizes)
@@ -284,16 +274,13 @@ class ALIKED(nn.Module):
         knorm = knorm.contiguous()
         nws = max(lib.lg_aliked_describe_workspace_bytes(bsz * n, self.n_pos), 1)
         work = torch.empty((nws,), device=device, dtype=torch.uint8)
-        sizes = self._sizes(sizes, device)
+        sizes = device_sizes(sizes, device)
+        flags = (_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0) | (_cabi.LG_EXTRACT_DESC_F16 if dtype is torch.float16 else 0)
+        io = _cabi.LgAlikedDescribeIO(batch=bsz, h=h, w=w, n_pos=self.n_pos, flags=flags, levels=levels.data_ptr(), sizes=None if sizes is None else sizes.data_ptr(),
+                                      packed=packed.data_ptr(), kp_norm=knorm.data_ptr(), counts=counts.data_ptr(), n=n, workspace=work.data_ptr(),
+                                      workspace_bytes=nws, descriptors=out.data_ptr())
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            tail = (self.n_pos, packed.data_ptr(), knorm.data_ptr(), counts.data_ptr(), n, work.data_ptr(), nws, out.data_ptr(), C.c_void_p(stream))
-            if sizes is None:
-                describe = lib.lg_aliked_describe_half if dtype is torch.float16 else lib.lg_aliked_describe
-                _cabi.check(describe(levels.data_ptr(), bsz, h, w, *tail))
-            else:
-                describe = lib.lg_aliked_describe_ragged_half if dtype is torch.float16 else lib.lg_aliked_describe_ragged
-                _cabi.check(describe(levels.data_ptr(), bsz, h, w, sizes.data_ptr(), *tail))
+            _cabi.check(lib.lg_aliked_describe(C.byref(io), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         return out
 
     # ------------------------------------------------------------------ the reference's forward

@@ -48,7 +48,7 @@ void gemm(const float* in, const float* w, const float* bias, float* out, int ro
 }
 
 // ==================================================================================================== ragged geometry
-// A ragged batch (lg_aliked_*_ragged): the arrays are a CANVAS, image b its top-left h_b x w_b corner with its OWN InputPadder geometry, its padded frame in the
+// A ragged batch (LG_EXTRACT_RAGGED): the arrays are a CANVAS, image b its top-left h_b x w_b corner with its OWN InputPadder geometry, its padded frame in the
 // top-left corner of the padded canvas.  Every kernel below is a template over Uniform / Ragged, passed as its LAST argument: addresses and strides come from
 // the canvas (the size arguments the uniform kernel always had), every bound from the image's Frame.  The Uniform instance reads the same arguments for both and
 // keeps the kernel arguments it had (an empty struct follows them).
@@ -182,7 +182,7 @@ __device__ __forceinline__ Up up_coord(int dst, int in, int out) {
 
 // the four 32-channel level maps of x1234 (after conv1 .. conv4 + SELU); level l has (Hp >> sh[l]) x (Wp >> sh[l]) pixels, sh = 0, 1, 3, 5
 struct AkLevels { const float* x[4]; int B, Hp, Wp; };
-__device__ __forceinline__ int lvl_shift(int l) { return l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); }
+__host__ __device__ __forceinline__ int lvl_shift(int l) { return l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); }
 
 // x1 .. x4 at padded pixel (yp, xp) of image b: level l's map has (L.Hp >> sh) x (L.Wp >> sh) pixels in memory (the canvas), the image's own part of it is
 // (fr.Hp >> sh) x (fr.Wp >> sh), and the align_corners=True scales of up_coord depend on the image's level and full extents.  Uniform: fr.Hp == L.Hp, fr.Wp == L.Wp
@@ -379,7 +379,7 @@ struct AkDescribe {
     float* patch; float* off1; float* spos; float* feat; float* sf; float* draw;
     const float* w_off2; const float* b_off2;
     const int* counts; float* out;
-    int out_f16;                           // != 0: `out` holds binary16 rows (lg_aliked_describe_half): the fp32 result rounded once, to nearest even, on store
+    int out_f16;                           // != 0: `out` holds binary16 rows (LG_EXTRACT_DESC_F16): the fp32 result rounded once, to nearest even, on store
 };
 // Ragged: H, W and L.Hp, L.Wp are the canvases (the level maps' strides), pt / pl unused; image b's frame gives the grid denormalisation, the pad offset into
 // the level maps, the upsampling coordinates and every tap bound.  A struct of its own for the ragged instances, as RaggedConvArgs is (lg_extract.h)
@@ -507,25 +507,19 @@ PackLayout pack_layout(int np) {
     return P;
 }
 
-struct Dims { int Hp, Wp, pt, pl; };
-Dims dims_of(int h, int w) {
-    const int ph = ((h / 32 + 1) * 32 - h) % 32, pw = ((w / 32 + 1) * 32 - w) % 32;   // InputPadder(divis_by = 32)
-    return Dims{h + ph, w + pw, ph / 2, pw / 2};
-}
-
 // level maps x1 .. x4 (32 channels each), one buffer
 struct LevelLayout { long long x[4]; long long total; };
 LevelLayout level_layout(int B, int h, int w) {
-    const Dims D = dims_of(h, w);
+    const Frame D = frame_of(h, w);
     Bump bp; LevelLayout L{};
-    for (int l = 0; l < 4; ++l) { const int s = l == 0 ? 0 : (l == 1 ? 1 : (l == 2 ? 3 : 5)); L.x[l] = bp.take((long long)B * (D.Hp >> s) * (D.Wp >> s) * 32 * 4); }
+    for (int l = 0; l < 4; ++l) L.x[l] = bp.take((long long)B * (D.Hp >> lvl_shift(l)) * (D.Wp >> lvl_shift(l)) * 32 * 4);
     L.total = bp.used;
     return L;
 }
 
 struct EncodeLayout { long long full_a, full_b, p2, q2, r2, p3, off, cols, t3, r3, p4, t4, r4, padded; long long total; };
 EncodeLayout encode_layout(int B, int h, int w) {
-    const Dims D = dims_of(h, w);
+    const Frame D = frame_of(h, w);
     const long long f = (long long)B * D.Hp * D.Wp, f2 = f / 4, f8 = f / 64, f32 = f / 1024;
     Bump bp; EncodeLayout E{};
     E.full_a = bp.take(f * 16 * 4); E.full_b = bp.take(f * 16 * 4);   // block1 (later: score head 8 + 4 channels, and 4 channels)
@@ -559,7 +553,7 @@ int fold(const float* src, float* dst, float* bias_dst, int cout, int cin, int k
 int check_model(int np) { return (np == 16 || np == 32) ? LG_OK : set_error(LG_ERR_INVALID, "unknown ALIKED model: n_pos must be 16 (aliked-n16, -n16rot) or 32 (aliked-n32)"); }
 int check_size(int B, int h, int w) {
     if (B < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "ALIKED: batch >= 1 and images of at least 8 x 8 pixels");
-    const Dims D = dims_of(h, w);
+    const Frame D = frame_of(h, w);
     if ((long long)D.Hp * D.Wp >= kMaxPixels) return set_error(LG_ERR_INVALID, "ALIKED: the padded image must stay below 2^25 pixels (32-bit pixel indices)");
     return LG_OK;
 }
@@ -622,36 +616,35 @@ int64_t lg_aliked_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t n
 
 }  // extern "C"
 
-// lg_aliked_encode / lg_aliked_encode_ragged: one sequence of launches; with `sizes` every launch is the Ragged instance and h, w are the canvas
+// lg_aliked_encode: one sequence of launches; with LG_EXTRACT_RAGGED every launch is the Ragged instance and h, w are the canvas
 template <class R>
-static int aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
-                         void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
+static int aliked_encode(const lg_aliked_encode_io& io, hipStream_t s) {
     constexpr bool RG = ragged<R>;
-    if (int rc = check_model(n_pos)) return rc;
-    if (int rc = check_size(batch, h, w)) return rc;
-    if (channels != 1 && channels != 3) return set_error(LG_ERR_INVALID, "ALIKED: images of 1 or 3 channels");
-    if (!image || !packed || !levels || !workspace || !scores || (RG && !sizes)) return set_error(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < encode_layout(batch, h, w).total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_workspace_bytes)");
-    const PackLayout P = pack_layout(n_pos);
-    const EncodeLayout E = encode_layout(batch, h, w);
-    const LevelLayout LL = level_layout(batch, h, w);
-    const Dims D = dims_of(h, w);
-    const int B = batch, Hp = D.Hp, Wp = D.Wp, H2 = Hp / 2, W2 = Wp / 2, H8 = Hp / 8, W8 = Wp / 8, H32 = Hp / 32, W32 = Wp / 32;
-    const float* p = static_cast<const float*>(packed);
-    char* ws = static_cast<char*>(workspace);
-    char* lv = static_cast<char*>(levels);
+    const int B = io.batch, h = io.h, w = io.w;
+    if (int rc = check_model(io.n_pos)) return rc;
+    if (int rc = check_size(B, h, w)) return rc;
+    if (io.channels != 1 && io.channels != 3) return set_error(LG_ERR_INVALID, "ALIKED: images of 1 or 3 channels");
+    if (!io.image || !io.packed || !io.levels || !io.workspace || !io.scores) return set_error(LG_ERR_INVALID, "null pointer");
+    const EncodeLayout E = encode_layout(B, h, w);
+    if (io.workspace_bytes < E.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_workspace_bytes)");
+    const PackLayout P = pack_layout(io.n_pos);
+    const LevelLayout LL = level_layout(B, h, w);
+    const Frame D = frame_of(h, w);
+    const int Hp = D.Hp, Wp = D.Wp, H2 = Hp / 2, W2 = Wp / 2, H8 = Hp / 8, W8 = Wp / 8, H32 = Hp / 32, W32 = Wp / 32;
+    const float* p = static_cast<const float*>(io.packed);
+    char* ws = static_cast<char*>(io.workspace);
+    char* lv = static_cast<char*>(io.levels);
     auto W_ = [&](long long off) { return reinterpret_cast<float*>(ws + off); };
     float* x[4];
     for (int l = 0; l < 4; ++l) x[l] = reinterpret_cast<float*>(lv + LL.x[l]);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const long long f = (long long)B * Hp * Wp;
     // the geometry argument of every launch at pyramid shift `sh`, and the convolution on that level
     int* padded = reinterpret_cast<int*>(ws + E.padded);
-    auto G = [&](int sh) { if constexpr (RG) return Ragged{sizes, h, w, sh}; else return Uniform{}; };
+    auto G = [&](int sh) { if constexpr (RG) return Ragged{io.sizes, h, w, sh}; else return Uniform{}; };
     if constexpr (RG) hipLaunchKernelGGL(ak_padded_sizes_kernel, dim3(blocks(B)), dim3(256), 0, s, G(0), B, padded);
     auto conv = [&](int sh, auto... args) { if constexpr (RG) lg::conv(padded, sh, args...); else lg::conv(args...); };
     // ---- block1 (ConvBlock) at full resolution
-    hipLaunchKernelGGL(ak_conv_first_kernel<R>, dim3(blocks(f * 4)), dim3(256), 0, s, image, channels, h, w, Hp, Wp, D.pt, D.pl, p + P.b1c1_w, p + P.b1c1_b, W_(E.full_a), B, G(0));
+    hipLaunchKernelGGL(ak_conv_first_kernel<R>, dim3(blocks(f * 4)), dim3(256), 0, s, io.image, io.channels, h, w, Hp, Wp, D.pt, D.pl, p + P.b1c1_w, p + P.b1c1_b, W_(E.full_a), B, G(0));
     conv(0, W_(E.full_a), p + P.b1c2_w, p + P.b1c2_b, W_(E.full_b), B, Hp, Wp, 16, 16, 9, 1, s);
     conv(0, W_(E.full_b), p + P.cv[0], nullptr, x[0], B, Hp, Wp, 16, 32, 1, 1, s);                  // conv1 + SELU -> x1
     // ---- block2 (ResBlock) at 1/2
@@ -684,106 +677,38 @@ static int aliked_encode(const float* image, int32_t batch, int32_t channels, in
     hipLaunchKernelGGL(ak_score_head0_kernel<R>, dim3(blocks(f)), dim3(256), 0, s, L, p + P.sh0, s8, G(0));
     hipLaunchKernelGGL((ak_small_conv_kernel<8, 4, false, R>), dim3(blocks(f)), dim3(256), 0, s, s8, p + P.sh2, s4a, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
     hipLaunchKernelGGL((ak_small_conv_kernel<4, 4, false, R>), dim3(blocks(f)), dim3(256), 0, s, s4a, p + P.sh4, s4b, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
-    hipLaunchKernelGGL((ak_small_conv_kernel<4, 1, true, R>), dim3(blocks((long long)B * h * w)), dim3(256), 0, s, s4b, p + P.sh6, scores, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
+    hipLaunchKernelGGL((ak_small_conv_kernel<4, 1, true, R>), dim3(blocks((long long)B * h * w)), dim3(256), 0, s, s4b, p + P.sh6, io.scores, B, Hp, Wp, h, w, D.pt, D.pl, G(0));
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
 }
 
-extern "C" {
-
-int lg_aliked_encode(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t n_pos, const void* packed, void* levels,
-                     void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
-    return aliked_encode<Uniform>(image, batch, channels, h, w, nullptr, n_pos, packed, levels, workspace, workspace_bytes, scores, hip_stream);
-}
-int lg_aliked_encode_ragged(const float* image, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
-                            void* levels, void* workspace, int64_t workspace_bytes, float* scores, void* hip_stream) {
-    return aliked_encode<Ragged>(image, batch, channels, h, w, sizes, n_pos, packed, levels, workspace, workspace_bytes, scores, hip_stream);
-}
-
-int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity) {
-    if (check_size(batch, h, w) != LG_OK || capacity < 1) return 0;
-    return detect_layout(batch, h, w, h * w, capacity, true).total;
-}
-
-// lg_aliked_detect / lg_aliked_detect_ragged: one path; `sizes` (DetectArgs::sizes) makes every bound the image's
-static int aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius, float scores_th,
-                         int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores,
-                         float* kp_norm, int32_t* counts, void* hip_stream) {
-    if (int rc = check_size(batch, h, w)) return rc;
-    if (nms_radius < 1 || nms_radius > 8) return set_error(LG_ERR_INVALID, "ALIKED: nms_radius must be in [1, 8]");
-    if (n_limit > 20000 || top_k > 20000) return set_error(LG_ERR_INVALID, "ALIKED: n_limit / top_k above 20000 (ALIKED.n_limit_max)");
-    if (top_k <= 0 && n_limit < 1) return set_error(LG_ERR_INVALID, "ALIKED: threshold mode needs n_limit >= 1");
-    const int K = top_k > 0 ? top_k : n_limit;
-    if (capacity < K) return set_error(LG_ERR_INVALID, "ALIKED: capacity must be at least top_k / n_limit");
-    if (!scores || !workspace || !keypoints || !kp_scores || !kp_norm || !counts) return set_error(LG_ERR_INVALID, "null pointer");
-    const DetectLayout DL = detect_layout(batch, h, w, h * w, capacity, true);
-    if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_detect_workspace_bytes)");
-    DetectArgs a{};
-    detect_bind(a, DL, workspace);
-    a.S = scores; a.B = batch; a.H = h; a.W = w; a.radius = nms_radius; a.sizes = sizes;
-    a.border = nms_radius; a.image_size = image_size; a.border_value = 0.f; a.threshold = scores_th;
-    a.max_candidates = h * w; a.K = K; a.sort_always = top_k > 0; a.sel_cap = capacity;
-    double* rowsum = reinterpret_cast<double*>(static_cast<char*>(workspace) + DL.rowsum);
-    float* th = reinterpret_cast<float*>(static_cast<char*>(workspace) + DL.th);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    launch_nms(a, s);                               // simple_nms (aliked.py:69-91)
-    launch_row_count(a, nullptr, rowsum, s);        // against scores_th, and the row sums for the mean
-    hipLaunchKernelGGL(ak_decide_kernel, dim3(batch), dim3(256), 0, s, a, top_k, (const double*)rowsum, th);
-    launch_row_count(a, th, nullptr, s);
-    launch_compact(a, th, s);
-    launch_select(a, s);
-    hipLaunchKernelGGL(ak_refine_kernel, dim3(blocks(capacity), batch), dim3(256), 0, s, a, AkKeypoints{keypoints, kp_scores, kp_norm, counts});
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
-}
-int lg_aliked_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const float* image_size, int32_t nms_radius, float scores_th, int32_t top_k,
-                     int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints, float* kp_scores, float* kp_norm,
-                     int32_t* counts, void* hip_stream) {
-    return aliked_detect(scores, batch, h, w, nullptr, image_size, nms_radius, scores_th, top_k, n_limit, capacity, workspace, workspace_bytes, keypoints, kp_scores,
-                         kp_norm, counts, hip_stream);
-}
-int lg_aliked_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, const float* image_size, int32_t nms_radius,
-                            float scores_th, int32_t top_k, int32_t n_limit, int32_t capacity, void* workspace, int64_t workspace_bytes, float* keypoints,
-                            float* kp_scores, float* kp_norm, int32_t* counts, void* hip_stream) {
-    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
-    return aliked_detect(scores, batch, h, w, sizes, image_size, nms_radius, scores_th, top_k, n_limit, capacity, workspace, workspace_bytes, keypoints, kp_scores,
-                         kp_norm, counts, hip_stream);
-}
-
-int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos) {
-    if (check_model(n_pos) != LG_OK || rows < 1) return 0;
-    return describe_layout(rows, n_pos).total;
-}
-
-}  // extern "C"
-
-// lg_aliked_describe / lg_aliked_describe_half and their ragged forms: one path, the element type of `descriptors` decided at the last kernel's store
+// lg_aliked_describe: one path, the element type of `descriptors` decided at the last kernel's store (LG_EXTRACT_DESC_F16); DA = AkDescribeRagged with LG_EXTRACT_RAGGED
 template <class DA>
-static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
-                           int32_t n, void* workspace, int64_t workspace_bytes, void* descriptors, bool out_f16, void* hip_stream) {
+static int aliked_describe(const lg_aliked_describe_io& io, hipStream_t s) {
+    const int n = io.n, n_pos = io.n_pos;
     if (int rc = check_model(n_pos)) return rc;
-    if (int rc = check_size(batch, h, w)) return rc;
+    if (int rc = check_size(io.batch, io.h, io.w)) return rc;
     if (n < 1) return LG_OK;
     if (n > 20000) return set_error(LG_ERR_INVALID, "ALIKED: more than 20000 keypoints per image");
-    if (!levels || !packed || !kp_norm || !counts || !workspace || !descriptors || (ragged<DA> && !sizes)) return set_error(LG_ERR_INVALID, "null pointer");
-    const int rows = batch * n;
+    if (!io.levels || !io.packed || !io.kp_norm || !io.counts || !io.workspace || !io.descriptors) return set_error(LG_ERR_INVALID, "null pointer");
+    const int rows = io.batch * n;
     const DescribeLayout DL = describe_layout(rows, n_pos);
-    if (workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_describe_workspace_bytes)");
+    if (io.workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_describe_workspace_bytes)");
     const PackLayout P = pack_layout(n_pos);
-    const LevelLayout LL = level_layout(batch, h, w);
-    const Dims D = dims_of(h, w);
-    const float* p = static_cast<const float*>(packed);
-    const char* lv = static_cast<const char*>(levels);
-    char* ws = static_cast<char*>(workspace);
+    const LevelLayout LL = level_layout(io.batch, io.h, io.w);
+    const Frame D = frame_of(io.h, io.w);
+    const float* p = static_cast<const float*>(io.packed);
+    const char* lv = static_cast<const char*>(io.levels);
+    char* ws = static_cast<char*>(io.workspace);
     DA d{};
-    if constexpr (ragged<DA>) d.rg = Ragged{sizes, h, w, 0};
+    if constexpr (ragged<DA>) d.rg = Ragged{io.sizes, io.h, io.w, 0};
     for (int l = 0; l < 4; ++l) d.L.x[l] = reinterpret_cast<const float*>(lv + LL.x[l]);
-    d.L.B = batch; d.L.Hp = D.Hp; d.L.Wp = D.Wp;
-    d.H = h; d.W = w; d.pt = D.pt; d.pl = D.pl; d.N = n; d.np = n_pos; d.knorm = kp_norm;
+    d.L.B = io.batch; d.L.Hp = D.Hp; d.L.Wp = D.Wp;
+    d.H = io.h; d.W = io.w; d.pt = D.pt; d.pl = D.pl; d.N = n; d.np = n_pos; d.knorm = io.kp_norm;
     d.patch = reinterpret_cast<float*>(ws + DL.patch); d.off1 = reinterpret_cast<float*>(ws + DL.off1); d.spos = reinterpret_cast<float*>(ws + DL.spos);
     d.feat = reinterpret_cast<float*>(ws + DL.feat); d.sf = reinterpret_cast<float*>(ws + DL.sf); d.draw = reinterpret_cast<float*>(ws + DL.draw);
-    d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = counts; d.out = static_cast<float*>(descriptors); d.out_f16 = out_f16 ? 1 : 0;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    d.w_off2 = p + P.so2_w; d.b_off2 = p + P.so2_b; d.counts = io.counts; d.out = static_cast<float*>(io.descriptors);
+    d.out_f16 = (io.flags & LG_EXTRACT_DESC_F16) ? 1 : 0;
     const int rp = DL.rows_pad;
     hipLaunchKernelGGL(ak_patch_kernel<DA>, dim3(rows), dim3(256), 0, s, d);
     if (rp > rows) (void)hipMemsetAsync(d.patch + (long long)rows * 9 * 128, 0, (size_t)(rp - rows) * 9 * 128 * 4, s);   // GEMM pad rows: keep them finite
@@ -800,22 +725,58 @@ static int aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t
 
 extern "C" {
 
-int lg_aliked_describe(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
-                       int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
-    return aliked_describe<AkDescribe>(levels, batch, h, w, nullptr, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
+int lg_aliked_encode(const lg_aliked_encode_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED, "lg_aliked_encode")) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return !(io->flags & LG_EXTRACT_RAGGED) ? aliked_encode<Uniform>(*io, s) : aliked_encode<Ragged>(*io, s);
 }
-int lg_aliked_describe_half(const void* levels, int32_t batch, int32_t h, int32_t w, int32_t n_pos, const void* packed, const float* kp_norm, const int32_t* counts,
-                           int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors, void* hip_stream) {
-    return aliked_describe<AkDescribe>(levels, batch, h, w, nullptr, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
+
+int64_t lg_aliked_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t capacity) {
+    if (check_size(batch, h, w) != LG_OK || capacity < 1) return 0;
+    return detect_layout(batch, h, w, h * w, capacity, true).total;
 }
-int lg_aliked_describe_ragged(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed, const float* kp_norm,
-                              const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, float* descriptors, void* hip_stream) {
-    return aliked_describe<AkDescribeRagged>(levels, batch, h, w, sizes, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, false, hip_stream);
+
+// one path; with LG_EXTRACT_RAGGED `sizes` (DetectArgs::sizes) makes every bound the image's
+int lg_aliked_detect(const lg_aliked_detect_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED, "lg_aliked_detect")) return rc;
+    const lg_aliked_detect_io& i = *io;
+    if (int rc = check_size(i.batch, i.h, i.w)) return rc;
+    if (i.nms_radius < 1 || i.nms_radius > 8) return set_error(LG_ERR_INVALID, "ALIKED: nms_radius must be in [1, 8]");
+    if (i.n_limit > 20000 || i.top_k > 20000) return set_error(LG_ERR_INVALID, "ALIKED: n_limit / top_k above 20000 (ALIKED.n_limit_max)");
+    if (i.top_k <= 0 && i.n_limit < 1) return set_error(LG_ERR_INVALID, "ALIKED: threshold mode needs n_limit >= 1");
+    const int K = i.top_k > 0 ? i.top_k : i.n_limit;
+    if (i.capacity < K) return set_error(LG_ERR_INVALID, "ALIKED: capacity must be at least top_k / n_limit");
+    if (!i.scores || !i.workspace || !i.keypoints || !i.kp_scores || !i.kp_norm || !i.counts) return set_error(LG_ERR_INVALID, "null pointer");
+    const DetectLayout DL = detect_layout(i.batch, i.h, i.w, i.h * i.w, i.capacity, true);
+    if (i.workspace_bytes < DL.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_aliked_detect_workspace_bytes)");
+    DetectArgs a{};
+    detect_bind(a, DL, i.workspace);
+    a.S = i.scores; a.B = i.batch; a.H = i.h; a.W = i.w; a.radius = i.nms_radius; a.sizes = extract_sizes(i);
+    a.border = i.nms_radius; a.image_size = i.image_size; a.border_value = 0.f; a.threshold = i.scores_th;
+    a.max_candidates = i.h * i.w; a.K = K; a.sort_always = i.top_k > 0; a.sel_cap = i.capacity;
+    double* rowsum = reinterpret_cast<double*>(static_cast<char*>(i.workspace) + DL.rowsum);
+    float* th = reinterpret_cast<float*>(static_cast<char*>(i.workspace) + DL.th);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    launch_nms(a, s);                               // simple_nms (aliked.py:69-91)
+    launch_row_count(a, nullptr, rowsum, s);        // against scores_th, and the row sums for the mean
+    hipLaunchKernelGGL(ak_decide_kernel, dim3(i.batch), dim3(256), 0, s, a, i.top_k, (const double*)rowsum, th);
+    launch_row_count(a, th, nullptr, s);
+    launch_compact(a, th, s);
+    launch_select(a, s);
+    hipLaunchKernelGGL(ak_refine_kernel, dim3(blocks(i.capacity), i.batch), dim3(256), 0, s, a, AkKeypoints{i.keypoints, i.kp_scores, i.kp_norm, i.counts});
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LG_OK : set_error(LG_ERR_HIP, hipGetErrorString(e));
 }
-int lg_aliked_describe_ragged_half(const void* levels, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t n_pos, const void* packed,
-                                   const float* kp_norm, const int32_t* counts, int32_t n, void* workspace, int64_t workspace_bytes, uint16_t* descriptors,
-                                   void* hip_stream) {
-    return aliked_describe<AkDescribeRagged>(levels, batch, h, w, sizes, n_pos, packed, kp_norm, counts, n, workspace, workspace_bytes, descriptors, true, hip_stream);
+
+int64_t lg_aliked_describe_workspace_bytes(int32_t rows, int32_t n_pos) {
+    if (check_model(n_pos) != LG_OK || rows < 1) return 0;
+    return describe_layout(rows, n_pos).total;
+}
+
+int lg_aliked_describe(const lg_aliked_describe_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED | LG_EXTRACT_DESC_F16, "lg_aliked_describe")) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return !(io->flags & LG_EXTRACT_RAGGED) ? aliked_describe<AkDescribe>(*io, s) : aliked_describe<AkDescribeRagged>(*io, s);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // compaction and the top-K selection.
 #pragma once
 #include "lg_kernels.h"
+#include "../../include/lightglue_amd.h"
 
 namespace lg {
 
@@ -187,5 +188,17 @@ struct Bump {
     long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
 };
 inline unsigned blocks(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+// ---------------------------------------------------------------- the io struct of an extractor stage (include/lightglue_amd.h: lg_*_io)
+// The refusals all six stages share, made before a field other than `flags` and `sizes` is looked at: a null io, a flag bit outside `defined`, and
+// LG_EXTRACT_RAGGED without `sizes`.
+template <class IO> int check_extract_io(const IO* io, uint32_t defined, const char* stage) {
+    if (!io) return set_error(LG_ERR_INVALID, std::string(stage) + ": null io");
+    if (io->flags & ~defined) return set_error(LG_ERR_INVALID, std::string(stage) + ": a flag bit this stage does not define (LG_EXTRACT_*)");
+    if ((io->flags & LG_EXTRACT_RAGGED) && !io->sizes) return set_error(LG_ERR_INVALID, "null pointer");
+    return LG_OK;
+}
+// `sizes` is read only with the flag: null means a uniform batch everywhere below the entry points
+template <class IO> const int32_t* extract_sizes(const IO& io) { return (io.flags & LG_EXTRACT_RAGGED) ? io.sizes : nullptr; }
 
 }  // namespace lg

@@ -338,43 +338,25 @@ int64_t lg_sp_encode_workspace_bytes(int32_t batch, int32_t h, int32_t w) {
     return (int64_t)2 * batch * h * w * 64 * 4;
 }
 
-int lg_sp_encode(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                 int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
-    if (batch < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "image height / width must be at least 8");
-    if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
-    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, nullptr, params, static_cast<float*>(workspace), scores, desc_map, 0, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
 int lg_sp_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t k, void* dst, void* hip_stream) {
     if (!src || !dst || cout < 1 || cin < 32 || cin % 32 || (k != 1 && k != 3) || (k == 3 && cout % 64)) return set_error(LG_ERR_INVALID, "bad conv weight (split form: cin a multiple of 32; 3 x 3 layers: cout a multiple of 64)");
     HIPCHK(launch_sp_pack_weight_split(src, dst, cout, cin, k, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
 }
 
-int lg_sp_encode_split(const float* image, int32_t batch, int32_t h, int32_t w, const float* const* params, void* workspace,
-                       int64_t workspace_bytes, float* scores, float* desc_map, void* hip_stream) {
-    if (batch < 1 || h < 8 || w < 8) return set_error(LG_ERR_INVALID, "image height / width must be at least 8");
-    // sp_conv3x3_split_kernel addresses the pixels of ONE image with 32-bit element offsets (h w 64 channels at full resolution)
-    if ((int64_t)h * w * 64 >= (int64_t)1 << 31) return set_error(LG_ERR_INVALID, "split-f16 conv stack: h * w must stay below 2^25 pixels (use conv_precision = fp32 for larger images)");
-    if (!image || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, h, w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes)");
-    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, h, w, nullptr, params, static_cast<float*>(workspace), scores, desc_map, 1, static_cast<hipStream_t>(hip_stream)));
-    return LG_OK;
-}
-
-int lg_sp_encode_ragged(const float* image, int32_t batch, int32_t hc, int32_t wc, const int32_t* sizes, const float* const* params, void* workspace,
-                        int64_t workspace_bytes, float* scores, float* desc_map, int32_t split, void* hip_stream) {
-    if (batch < 1 || hc < 8 || wc < 8) return set_error(LG_ERR_INVALID, "canvas height / width must be at least 8");
-    // as lg_sp_encode_split: 32-bit element offsets inside one image, whose strides are the canvas's
-    if (split && (int64_t)hc * wc * 64 >= (int64_t)1 << 31) return set_error(LG_ERR_INVALID, "split-f16 conv stack: the canvas hc * wc must stay below 2^25 pixels (use conv_precision = fp32 for larger ones)");
-    if (!image || !sizes || !params || !workspace || !scores || !desc_map) return set_error(LG_ERR_INVALID, "null pointer");
-    if (workspace_bytes < lg_sp_encode_workspace_bytes(batch, hc, wc)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes of the canvas)");
-    for (int i = 0; i < 24; ++i) if (!params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
-    HIPCHK(launch_sp_encode(image, batch, hc, wc, sizes, params, static_cast<float*>(workspace), scores, desc_map, split ? 1 : 0, static_cast<hipStream_t>(hip_stream)));
+int lg_sp_encode(const lg_sp_encode_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED | LG_EXTRACT_SPLIT, "lg_sp_encode")) return rc;
+    const lg_sp_encode_io& a = *io;
+    const bool split = a.flags & LG_EXTRACT_SPLIT;
+    if (a.batch < 1 || a.h < 8 || a.w < 8) return set_error(LG_ERR_INVALID, "image (ragged batch: canvas) height / width must be at least 8");
+    // sp_conv3x3_split_kernel addresses the pixels of ONE image with 32-bit element offsets (h w 64 channels at full resolution; a ragged image's strides are the canvas's)
+    if (split && (int64_t)a.h * a.w * 64 >= (int64_t)1 << 31)
+        return set_error(LG_ERR_INVALID, "split-f16 conv stack: h * w (ragged batch: of the canvas) must stay below 2^25 pixels (use conv_precision = fp32 for larger images)");
+    if (!a.image || !a.params || !a.workspace || !a.scores || !a.desc_map) return set_error(LG_ERR_INVALID, "null pointer");
+    if (a.workspace_bytes < lg_sp_encode_workspace_bytes(a.batch, a.h, a.w)) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_encode_workspace_bytes; ragged batch: of the canvas)");
+    for (int i = 0; i < 24; ++i) if (!a.params[i]) return set_error(LG_ERR_INVALID, "null layer parameter");
+    HIPCHK(launch_sp_encode(a.image, a.batch, a.h, a.w, extract_sizes(a), a.params, static_cast<float*>(a.workspace), a.scores, a.desc_map, split ? 1 : 0,
+                            static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
 }
 

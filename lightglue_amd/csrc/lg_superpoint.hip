@@ -25,7 +25,7 @@ struct SpArgs {
     const int* num;            // [B] live keypoints per image or nullptr
     float* out;                // [B][N][256]
     int B, h, w, N, s, normalize_dense;
-    int out_f16;               // != 0: `out` holds binary16 rows (lg_sp_sample_descriptors_half): the fp32 result rounded once, to nearest even, on store
+    int out_f16;               // != 0: `out` holds binary16 rows (LG_EXTRACT_DESC_F16): the fp32 result rounded once, to nearest even, on store
     const int* sizes;          // ragged batch (else null): [B][2] image (w, h); h, w above are then the CANVAS map (strides), the map of image b its top-left (h_b / s) x (w_b / s) corner
 };
 
@@ -169,36 +169,17 @@ using namespace lg;
 
 extern "C" {
 
-// lg_sp_sample_descriptors / lg_sp_sample_descriptors_half: one path, the element type of `out` decided at the last kernel's store
-static int sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
-                                 const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, void* out, bool out_f16,
-                                 const int32_t* sizes, void* hip_stream) {
-    if (channels != 256) return set_error(LG_ERR_INVALID, "descriptor map must have 256 channels");
-    if (batch < 1 || h < 1 || w < 1 || n < 0 || cell < 1) return set_error(LG_ERR_INVALID, "bad descriptor map / keypoint sizes");
-    if (!desc_map || !workspace || (n && (!keypoints || !out))) return set_error(LG_ERR_INVALID, "null pointer");
-    SpArgs a{desc_map, workspace, keypoints, num, static_cast<float*>(out), batch, h, w, n, cell, normalize_dense ? 1 : 0, out_f16 ? 1 : 0, sizes};
+// LG_EXTRACT_DESC_F16: the element type of `out`, decided at the last kernel's store
+int lg_sp_sample_descriptors(const lg_sp_sample_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED | LG_EXTRACT_DESC_F16, "lg_sp_sample_descriptors")) return rc;
+    const lg_sp_sample_io& i = *io;
+    if (i.channels != 256) return set_error(LG_ERR_INVALID, "descriptor map must have 256 channels");
+    if (i.batch < 1 || i.h < 1 || i.w < 1 || i.n < 0 || i.cell < 1) return set_error(LG_ERR_INVALID, "bad descriptor map / keypoint sizes");
+    if (!i.desc_map || !i.workspace || (i.n && (!i.keypoints || !i.out))) return set_error(LG_ERR_INVALID, "null pointer");
+    SpArgs a{i.desc_map, i.workspace, i.keypoints, i.num, static_cast<float*>(i.out), i.batch, i.h, i.w, i.n, i.cell, i.normalize_dense ? 1 : 0,
+             (i.flags & LG_EXTRACT_DESC_F16) ? 1 : 0, extract_sizes(i)};
     HIPCHK(launch_sp_sample(a, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
-}
-int lg_sp_sample_descriptors(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
-                             const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out,
-                             void* hip_stream) {
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, nullptr, hip_stream);
-}
-int lg_sp_sample_descriptors_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const float* keypoints,
-                                 const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, uint16_t* out,
-                                 void* hip_stream) {
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, nullptr, hip_stream);
-}
-int lg_sp_sample_descriptors_ragged(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, const float* keypoints,
-                                    const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, float* out, void* hip_stream) {
-    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, false, sizes, hip_stream);
-}
-int lg_sp_sample_descriptors_ragged_half(const float* desc_map, int32_t batch, int32_t channels, int32_t h, int32_t w, const int32_t* sizes, const float* keypoints,
-                                         const int32_t* num, int32_t n, int32_t cell, int32_t normalize_dense, float* workspace, uint16_t* out, void* hip_stream) {
-    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
-    return sp_sample_descriptors(desc_map, batch, channels, h, w, keypoints, num, n, cell, normalize_dense, workspace, out, true, sizes, hip_stream);
 }
 
 int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t max_candidates) {
@@ -206,43 +187,28 @@ int64_t lg_sp_detect_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_
     return (int64_t)detect_layout(batch, h, w, max_candidates, max_candidates, false).total;
 }
 
-// lg_sp_detect / lg_sp_detect_ragged: one path; sizes (null: every map fills h x w) are the score maps' (w, h) inside the h x w canvas
-static int sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
-                     float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
-                     int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
-    if (batch < 1 || h < 1 || w < 1 || h >= 32768 || w >= 32768) return set_error(LG_ERR_INVALID, "bad score map size");
-    if (nms_radius < 0 || nms_radius > 4) return set_error(LG_ERR_INVALID, "nms_radius must be in [0, 4]");
-    if (max_keypoints > SP_TOPK_MAX) return set_error(LG_ERR_INVALID, "max_keypoints above 4096");
-    if (capacity < 1 || max_candidates < 1 || (max_keypoints > 0 && capacity < max_keypoints)) return set_error(LG_ERR_INVALID, "bad capacity / max_candidates");
-    if (!scores || !workspace || !keypoints || !kp_scores || !counts) return set_error(LG_ERR_INVALID, "null pointer");
-    const DetectLayout l = detect_layout(batch, h, w, max_candidates, max_candidates, false);
-    if (workspace_bytes < (int64_t)l.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_detect_workspace_bytes)");
+// LG_EXTRACT_RAGGED: sizes (else null: every map fills h x w) are the score maps' (w, h) inside the h x w canvas
+int lg_sp_detect(const lg_sp_detect_io* io, void* hip_stream) {
+    if (int rc = check_extract_io(io, LG_EXTRACT_RAGGED, "lg_sp_detect")) return rc;
+    const lg_sp_detect_io& i = *io;
+    if ((i.flags & LG_EXTRACT_RAGGED) && (i.h < 8 || i.w < 8)) return set_error(LG_ERR_INVALID, "score canvas height / width must be at least 8");
+    if (i.batch < 1 || i.h < 1 || i.w < 1 || i.h >= 32768 || i.w >= 32768) return set_error(LG_ERR_INVALID, "bad score map size");
+    if (i.nms_radius < 0 || i.nms_radius > 4) return set_error(LG_ERR_INVALID, "nms_radius must be in [0, 4]");
+    if (i.max_keypoints > SP_TOPK_MAX) return set_error(LG_ERR_INVALID, "max_keypoints above 4096");
+    if (i.capacity < 1 || i.max_candidates < 1 || (i.max_keypoints > 0 && i.capacity < i.max_keypoints)) return set_error(LG_ERR_INVALID, "bad capacity / max_candidates");
+    if (!i.scores || !i.workspace || !i.keypoints || !i.kp_scores || !i.counts) return set_error(LG_ERR_INVALID, "null pointer");
+    const DetectLayout l = detect_layout(i.batch, i.h, i.w, i.max_candidates, i.max_candidates, false);
+    if (i.workspace_bytes < (int64_t)l.total) return set_error(LG_ERR_INVALID, "workspace too small (lg_sp_detect_workspace_bytes)");
     SpDetectArgs a{};
     DetectArgs& d = a.d;
-    detect_bind(d, l, workspace);
-    d.S = scores; d.B = batch; d.H = h; d.W = w; d.radius = nms_radius;
-    d.border = remove_borders; d.image_size = nullptr; d.border_value = -1.f; d.threshold = detection_threshold;
-    d.max_candidates = max_candidates; d.K = max_keypoints; d.sort_always = 0; d.sel_cap = max_candidates;
-    d.sizes = sizes;
-    a.capacity = capacity; a.keypoints = keypoints; a.kp_scores = kp_scores; a.counts = counts; a.totals = totals;
+    detect_bind(d, l, i.workspace);
+    d.S = i.scores; d.B = i.batch; d.H = i.h; d.W = i.w; d.radius = i.nms_radius;
+    d.border = i.remove_borders; d.image_size = nullptr; d.border_value = -1.f; d.threshold = i.detection_threshold;
+    d.max_candidates = i.max_candidates; d.K = i.max_keypoints; d.sort_always = 0; d.sel_cap = i.max_candidates;
+    d.sizes = extract_sizes(i);
+    a.capacity = i.capacity; a.keypoints = i.keypoints; a.kp_scores = i.kp_scores; a.counts = i.counts; a.totals = i.totals;
     HIPCHK(launch_sp_detect(a, static_cast<hipStream_t>(hip_stream)));
     return LG_OK;
-}
-
-int lg_sp_detect(const float* scores, int32_t batch, int32_t h, int32_t w, int32_t nms_radius, int32_t remove_borders,
-                 float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
-                 int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
-    return sp_detect(scores, batch, h, w, nullptr, nms_radius, remove_borders, detection_threshold, max_keypoints, capacity, max_candidates, workspace, workspace_bytes,
-                     keypoints, kp_scores, counts, totals, hip_stream);
-}
-
-int lg_sp_detect_ragged(const float* scores, int32_t batch, int32_t h, int32_t w, const int32_t* sizes, int32_t nms_radius, int32_t remove_borders,
-                        float detection_threshold, int32_t max_keypoints, int32_t capacity, int32_t max_candidates, void* workspace,
-                        int64_t workspace_bytes, float* keypoints, float* kp_scores, int32_t* counts, int32_t* totals, void* hip_stream) {
-    if (h < 8 || w < 8) return set_error(LG_ERR_INVALID, "score canvas height / width must be at least 8");
-    if (!sizes) return set_error(LG_ERR_INVALID, "null pointer");
-    return sp_detect(scores, batch, h, w, sizes, nms_radius, remove_borders, detection_threshold, max_keypoints, capacity, max_candidates, workspace, workspace_bytes,
-                     keypoints, kp_scores, counts, totals, hip_stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@ released `superpoint_v1.pth` loads with `load_state_dict` unchanged, and the sam
 descriptor head (`lg_sp_sample_descriptors`).  No CPU fallback.  `extract(img, resize=...)` resizes on the device first (`preprocess.ImagePreprocessor`,
 `lg_preprocess.hip`) and maps the keypoints back like the reference's `Extractor.extract`; image FILE I/O (cv2) stays out of scope.
 
-Images of DIFFERENT sizes run in one ragged batch: a canvas with image b in its top-left corner plus `valid_size` (`forward`, `encode`; the `*_ragged` entry points),
+Images of DIFFERENT sizes run in one ragged batch: a canvas with image b in its top-left corner plus `valid_size` (`forward`, `encode`; the `LG_EXTRACT_RAGGED` flag of the three stages' io structs),
 every image's result bit-identical to the B = 1 call on its crop; `extract_batch` builds the feature store of a mixed photo set that way (`plan_image_batches`)."""
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from torch import nn
 from . import _cabi
 from .glue import extracted_to_image_frame
 from .preprocess import ImagePreprocessor
-from .superpoint_head import _detect, _run as _descriptor_run, check_descriptor_dtype, check_sizes, sizes_on_device
+from .superpoint_head import _detect, _run as _descriptor_run, check_descriptor_dtype, check_sizes, device_sizes, sizes_on_device
 
 def plan_image_batches(sizes_hw: Sequence[Tuple[int, int]], batch_size: int = 8, max_workspace_bytes: Optional[int] = None,
                        order: str = "size", workspace_bytes=None) -> List[Tuple[List[int], Tuple[int, int]]]:
@@ -208,17 +208,12 @@ class SuperPoint(nn.Module):
         work = torch.empty((nbytes,), device=device, dtype=torch.uint8)
         scores = torch.empty((bsz, h // 8 * 8, w // 8 * 8), device=device, dtype=torch.float32)
         dense = torch.empty((bsz, 256, h // 8, w // 8), device=device, dtype=torch.float32)
-        if sizes is not None and not torch.is_tensor(sizes):
-            sizes = sizes_on_device(sizes, device)
-        split = self.conf.conv_precision == "f16x3"
+        sizes = device_sizes(sizes, device)
+        flags = (_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0) | (_cabi.LG_EXTRACT_SPLIT if self.conf.conv_precision == "f16x3" else 0)
+        io = _cabi.LgSpEncodeIO(batch=bsz, h=h, w=w, flags=flags, image=image.data_ptr(), sizes=None if sizes is None else sizes.data_ptr(), params=arr,
+                                workspace=work.data_ptr(), workspace_bytes=nbytes, scores=scores.data_ptr(), desc_map=dense.data_ptr())
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            if sizes is None:
-                encode = lib.lg_sp_encode_split if split else lib.lg_sp_encode
-                _cabi.check(encode(image.data_ptr(), bsz, h, w, arr, work.data_ptr(), nbytes, scores.data_ptr(), dense.data_ptr(), C.c_void_p(stream)))
-            else:
-                _cabi.check(lib.lg_sp_encode_ragged(image.data_ptr(), bsz, h, w, sizes.data_ptr(), arr, work.data_ptr(), nbytes, scores.data_ptr(),
-                                                    dense.data_ptr(), int(split), C.c_void_p(stream)))
+            _cabi.check(lib.lg_sp_encode(C.byref(io), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         return scores, dense
 
     # ------------------------------------------------------------------ the reference's forward

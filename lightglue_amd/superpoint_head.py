@@ -1,7 +1,8 @@
 """SuperPoint descriptor head on the MI355X: the step between the SuperPoint conv stack and
 the matcher.  Mirrors the reference's `sample_descriptors` (lightglue/superpoint.py:80-95) and the descriptor tail
 of `SuperPoint.forward` (:216-228); both run in `lightglue_amd/csrc/lg_superpoint.hip` through
-`lg_sp_sample_descriptors` (include/lightglue_amd.h).  The conv stack, NMS and top-k selection stay out of scope.
+`lg_sp_sample_descriptors` and `lg_sp_detect` (include/lightglue_amd.h): one entry point each, taking an io struct whose `flags` say whether the batch is ragged
+(`LG_EXTRACT_RAGGED`: `sizes` is read) and whether the descriptors are stored as float16 (`LG_EXTRACT_DESC_F16`).  The conv stack stays out of scope.
 No CPU fallback: CPU tensors raise."""
 from __future__ import annotations
 
@@ -46,8 +47,13 @@ def check_sizes(sizes, batch: int, canvas_hw, minimum: int = 8, what: str = "val
 
 
 def sizes_on_device(rows: list, device) -> torch.Tensor:
-    """int32 `[B, 2]` device array of validated `(w, h)` rows: the `sizes` argument of the `*_ragged` entry points"""
+    """int32 `[B, 2]` device array of validated `(w, h)` rows: the `sizes` field of a stage's io under LG_EXTRACT_RAGGED"""
     return torch.tensor(rows, dtype=torch.int32).reshape(-1, 2).to(device)
+
+
+def device_sizes(sizes, device) -> Optional[torch.Tensor]:
+    """None, validated host rows (check_sizes) or the int32 device array made from them -> that device array (or None)"""
+    return sizes if sizes is None or torch.is_tensor(sizes) else sizes_on_device(sizes, device)
 
 
 def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: bool,
@@ -72,17 +78,10 @@ def _run(keypoints: torch.Tensor, dense: torch.Tensor, s: int, normalize_dense: 
     ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        lib = _cabi.load()
-        if sizes is None:
-            sample = lib.lg_sp_sample_descriptors_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors
-            _cabi.check(sample(
-                ptr(dense), b, c, h, w, ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
-                C.c_void_p(stream)))
-        else:
-            sample = lib.lg_sp_sample_descriptors_ragged_half if dtype is torch.float16 else lib.lg_sp_sample_descriptors_ragged
-            _cabi.check(sample(
-                ptr(dense), b, c, h, w, sizes.data_ptr(), ptr(keypoints), ptr(num), n, int(s), int(normalize_dense), ptr(work), ptr(out),
-                C.c_void_p(stream)))
+        flags = (_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0) | (_cabi.LG_EXTRACT_DESC_F16 if dtype is torch.float16 else 0)
+        io = _cabi.LgSpSampleIO(batch=b, channels=c, h=h, w=w, flags=flags, desc_map=ptr(dense), sizes=ptr(sizes), keypoints=ptr(keypoints), num=ptr(num),
+                                n=n, cell=int(s), normalize_dense=int(normalize_dense), workspace=ptr(work), out=ptr(out))
+        _cabi.check(_cabi.load().lg_sp_sample_descriptors(C.byref(io), C.c_void_p(stream)))
     return out
 
 
@@ -90,7 +89,7 @@ def sample_descriptors(keypoints: torch.Tensor, descriptors: torch.Tensor, s: in
     """Same contract as the reference function (superpoint.py:80-95): `keypoints [b, N, 2]` pixel (x, y),
     `descriptors [b, c, h, w]` -> L2-normalised bilinear samples `[b, c, N]` (a transposed view of the kernel's
     matcher-ready `[b, N, c]` output).  Unlike the reference, `keypoints` is not modified in place.  `dtype=torch.float16`: the fp32 result
-    rounded once on store (`lg_sp_sample_descriptors_half`), bit-identical to `.half()` of the fp32 output."""
+    rounded once on store (`LG_EXTRACT_DESC_F16`), bit-identical to `.half()` of the fp32 output."""
     return _run(keypoints, descriptors, s, False, None, dtype).transpose(1, 2)
 
 
@@ -148,12 +147,11 @@ def _detect(scores: torch.Tensor, nms_radius: int, remove_borders: int, detectio
     totals = torch.empty((b,), device=device, dtype=torch.int32)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        tail = (int(nms_radius), int(remove_borders), float(detection_threshold), k, cap, maxc, work.data_ptr(), nbytes, kpts.data_ptr(), kscores.data_ptr(),
-                counts.data_ptr(), totals.data_ptr(), C.c_void_p(stream))
-        if sizes is None:
-            _cabi.check(lib.lg_sp_detect(scores.data_ptr(), b, h, w, *tail))
-        else:
-            _cabi.check(lib.lg_sp_detect_ragged(scores.data_ptr(), b, h, w, sizes.data_ptr(), *tail))
+        io = _cabi.LgSpDetectIO(batch=b, h=h, w=w, flags=_cabi.LG_EXTRACT_RAGGED if sizes is not None else 0, scores=scores.data_ptr(),
+                                sizes=None if sizes is None else sizes.data_ptr(), nms_radius=int(nms_radius), remove_borders=int(remove_borders),
+                                detection_threshold=float(detection_threshold), max_keypoints=k, capacity=cap, max_candidates=maxc, workspace=work.data_ptr(),
+                                workspace_bytes=nbytes, keypoints=kpts.data_ptr(), kp_scores=kscores.data_ptr(), counts=counts.data_ptr(), totals=totals.data_ptr())
+        _cabi.check(lib.lg_sp_detect(C.byref(io), C.c_void_p(stream)))
     if k == 0:
         worst = int(totals.max().item())
         if worst > cap:

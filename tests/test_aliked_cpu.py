@@ -82,11 +82,11 @@ def test_cabi_refusals_without_gpu():
     assert lib.lg_aliked_packed_bytes(16) > 0 and lib.lg_aliked_packed_bytes(32) > lib.lg_aliked_packed_bytes(16)
     assert lib.lg_aliked_packed_bytes(8) == 0
     assert lib.lg_aliked_workspace_bytes(1, 8192, 4096, 16) == 0          # >= 2^25 padded pixels
-    rc = lib.lg_aliked_encode(None, 1, 3, 8192, 4096, 16, None, None, None, 0, None, None)
+    rc = lib.lg_aliked_encode(C.byref(_cabi.LgAlikedEncodeIO(batch=1, channels=3, h=8192, w=4096, n_pos=16)), None)
     assert rc == _cabi.LG_ERR_INVALID and b"2^25" in lib.lg_last_error()
-    rc = lib.lg_aliked_encode(None, 1, 3, 64, 64, 24, None, None, None, 0, None, None)
+    rc = lib.lg_aliked_encode(C.byref(_cabi.LgAlikedEncodeIO(batch=1, channels=3, h=64, w=64, n_pos=24)), None)
     assert rc == _cabi.LG_ERR_INVALID and b"unknown ALIKED model" in lib.lg_last_error()
-    rc = lib.lg_aliked_detect(None, 1, 64, 64, None, 2, C.c_float(0.2), -1, 20001, 20001, None, 0, None, None, None, None, None)
+    rc = lib.lg_aliked_detect(C.byref(_cabi.LgAlikedDetectIO(batch=1, h=64, w=64, nms_radius=2, scores_th=0.2, top_k=-1, n_limit=20001, capacity=20001)), None)
     assert rc == _cabi.LG_ERR_INVALID and b"20000" in lib.lg_last_error()
     rc = lib.lg_aliked_pack_weights(16, None, 68, None, 0, None)
     assert rc == _cabi.LG_ERR_INVALID

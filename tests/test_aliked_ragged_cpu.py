@@ -1,5 +1,6 @@
 """Ragged-batch ALIKED extraction, the parts that need no GPU: the host-side validation of `valid_size`, the batch planner with ALIKED's own byte
-function, the per-image padding geometry the `lg_aliked_*_ragged` entry points document, and the presence of their symbols."""
+function, the per-image padding geometry the header documents for `LG_EXTRACT_RAGGED`, and the stages' refusal of a ragged call without sizes."""
+import ctypes as C
 import re
 from pathlib import Path
 
@@ -8,9 +9,7 @@ import torch
 
 from lightglue_amd import ALIKED, _cabi, plan_image_batches
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = (ROOT / "include" / "lightglue_amd.h").read_text()
-RAGGED_SYMBOLS = ("lg_aliked_encode_ragged", "lg_aliked_detect_ragged", "lg_aliked_describe_ragged", "lg_aliked_describe_ragged_half")
+HEADER = (Path(__file__).resolve().parent.parent / "include" / "lightglue_amd.h").read_text()
 # (h, w) of the GPU test's canvas of four: centred pads 12 / 12; pads 15 + 16 and 0 + 1; no pad; one 32-pixel tile
 SIZES = [(40, 72), (33, 31), (64, 96), (8, 8)]
 
@@ -99,27 +98,39 @@ def test_per_image_padding_geometry():
         assert lib.lg_aliked_workspace_bytes(4, hc, wc, 16) == lib.lg_aliked_workspace_bytes(4, hp, wp, 16)
 
 
-def test_ragged_symbols_declared_and_bound():
+def test_ragged_is_a_flag_of_each_stage_declared_and_bound():
+    """A ragged call and its uniform twin cannot drift apart: they are ONE prototype and ONE struct per stage, the ragged form being `LG_EXTRACT_RAGGED` plus the
+    struct's `sizes`.  Each stage is declared once, exported, bound as (const io*, stream); its io declares `flags` and `const int32_t *sizes`; no `_ragged` /
+    `_half` symbol of a stage is left in the header, the binding or the library."""
     lib = _cabi.load()
-    for fn in RAGGED_SYMBOLS:
-        assert re.search(r"\bint %s\(" % fn, HEADER) and fn in _cabi.EXPORTED_SYMBOLS and getattr(lib, fn) is not None
-        assert not re.search(r"\d", fn)
-    # each is its uniform twin plus `const int32_t* sizes`
-    for fn in RAGGED_SYMBOLS:
-        twin = fn.replace("_ragged", "")
-        args = lambda name: re.search(r"\bint %s\(([^;]*)\);" % name, HEADER).group(1)      # noqa: E731
-        ragged, uniform = [a.strip() for a in args(fn).replace("\n", " ").split(",")], [a.strip() for a in args(twin).replace("\n", " ").split(",")]
-        assert "const int32_t* sizes" in ragged
-        ragged.remove("const int32_t* sizes")
-        assert ragged == uniform, (fn, ragged, uniform)
+    stages = {"lg_aliked_encode": ("lg_aliked_encode_io", _cabi.LgAlikedEncodeIO), "lg_aliked_detect": ("lg_aliked_detect_io", _cabi.LgAlikedDetectIO),
+              "lg_aliked_describe": ("lg_aliked_describe_io", _cabi.LgAlikedDescribeIO)}
+    for fn, (struct, mirror) in stages.items():
+        assert len(re.findall(r"\bint %s\(const %s\* io, void\* hip_stream\);" % (fn, struct), HEADER)) == 1, fn
+        assert len(re.findall(r"\bint %s\w*\(" % fn, HEADER)) == 1, fn                      # the stage has no second prototype under a longer name
+        assert fn in _cabi.EXPORTED_SYMBOLS and getattr(lib, fn).argtypes == [C.POINTER(mirror), C.c_void_p]
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), HEADER, re.S).group(1)
+        assert re.search(r"\buint32_t flags;", body) and re.search(r"\bconst int32_t \*sizes;", body), struct
+        fields = dict(mirror._fields_)
+        assert fields["flags"] is C.c_uint32 and fields["sizes"] is C.c_void_p
+        for suffix in ("_ragged", "_half", "_ragged_half"):
+            assert fn + suffix not in _cabi.EXPORTED_SYMBOLS and not hasattr(lib, fn + suffix), fn + suffix
+    assert re.search(r"#define LG_EXTRACT_RAGGED\s+1u", HEADER) and _cabi.LG_EXTRACT_RAGGED == 1
 
 
 def test_ragged_entry_points_refuse_null_sizes_before_the_device():
     lib = _cabi.load()
     one = 1      # any non-null value: refusals come before a pointer is used
-    rc = lib.lg_aliked_encode_ragged(one, 2, 3, 64, 96, None, 16, one, one, one, 1 << 40, one, None)
+    R = _cabi.LG_EXTRACT_RAGGED
+    io = _cabi.LgAlikedEncodeIO(batch=2, channels=3, h=64, w=96, n_pos=16, flags=R, image=one, sizes=None, packed=one, levels=one, workspace=one,
+                                workspace_bytes=1 << 40, scores=one)
+    rc = lib.lg_aliked_encode(C.byref(io), None)
     assert rc == _cabi.LG_ERR_INVALID and b"null pointer" in lib.lg_last_error()
-    rc = lib.lg_aliked_detect_ragged(one, 2, 64, 96, None, None, 2, 0.2, -1, 100, 100, one, 1 << 40, one, one, one, one, None)
+    io = _cabi.LgAlikedDetectIO(batch=2, h=64, w=96, flags=R, scores=one, sizes=None, image_size=None, nms_radius=2, scores_th=0.2, top_k=-1, n_limit=100,
+                                capacity=100, workspace=one, workspace_bytes=1 << 40, keypoints=one, kp_scores=one, kp_norm=one, counts=one)
+    rc = lib.lg_aliked_detect(C.byref(io), None)
     assert rc == _cabi.LG_ERR_INVALID and b"null pointer" in lib.lg_last_error()
-    rc = lib.lg_aliked_describe_ragged(one, 2, 64, 96, None, 16, one, one, one, 10, one, 1 << 40, one, None)
+    io = _cabi.LgAlikedDescribeIO(batch=2, h=64, w=96, n_pos=16, flags=R, levels=one, sizes=None, packed=one, kp_norm=one, counts=one, n=10, workspace=one,
+                                  workspace_bytes=1 << 40, descriptors=one)
+    rc = lib.lg_aliked_describe(C.byref(io), None)
     assert rc == _cabi.LG_ERR_INVALID and b"null pointer" in lib.lg_last_error()

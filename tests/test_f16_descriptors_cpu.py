@@ -20,10 +20,13 @@ def test_flags_and_entry_points_are_declared_bound_and_exported():
         assert int(re.search(r"#define %s (\d+)u" % name, HEADER).group(1)) == value == getattr(_cabi, name)
     flags = [_cabi.LG_FLAG_NO_PRUNING, _cabi.LG_FLAG_EXT, _cabi.LG_FLAG_CHECK_FINITE, _cabi.LG_FLAG_INDEXED, _cabi.LG_FLAG_DESC0_F16, _cabi.LG_FLAG_DESC1_F16]
     assert sorted(flags) == [1, 2, 4, 8, 16, 32]
+    # the extractors' binary16 output is a flag of the two descriptor stages' io (tests/test_cabi_symbols.py checks the structs and the flag values
+    # against the header, and that exactly these two stages accept the bit): the output fields are void*, the flag says which element type
+    assert int(re.search(r"#define LG_EXTRACT_DESC_F16\s+(\d+)u", HEADER).group(1)) == _cabi.LG_EXTRACT_DESC_F16
     lib = _cabi.load()
-    for fn in ("lg_sp_sample_descriptors_half", "lg_aliked_describe_half"):
-        assert re.search(r"\bint %s\(" % fn, HEADER) and fn in _cabi.EXPORTED_SYMBOLS and getattr(lib, fn) is not None
-    assert "uint16_t* out" in HEADER and "uint16_t* descriptors" in HEADER
+    for fn, mirror, field in (("lg_sp_sample_descriptors", _cabi.LgSpSampleIO, "out"), ("lg_aliked_describe", _cabi.LgAlikedDescribeIO, "descriptors")):
+        assert fn in _cabi.EXPORTED_SYMBOLS and getattr(lib, fn).argtypes == [ctypes.POINTER(mirror), ctypes.c_void_p]
+        assert dict(mirror._fields_)[field] is ctypes.c_void_p and re.search(r"void \*%s;" % field, HEADER)
 
 
 def test_float16_flags_are_refused_without_touching_a_gpu():

@@ -1,4 +1,4 @@
-"""GPU tests of float16 descriptors (include/lightglue_amd.h LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16, lg_sp_sample_descriptors_half, lg_aliked_describe_half).
+"""GPU tests of float16 descriptors (include/lightglue_amd.h LG_FLAG_DESC0_F16 / LG_FLAG_DESC1_F16, LG_EXTRACT_DESC_F16 of lg_sp_sample_descriptors / lg_aliked_describe).
 
 The engine reads a float16 descriptor tensor in place and widens every value exactly where the descriptors enter it, so every comparison here is bit for bit:
 outputs on `d16` against outputs on `d16.float()`, and an extractor's float16 descriptors against `.half()` of its fp32 ones.  Shapes, stores and pair lists are

@@ -1,5 +1,5 @@
 """Ragged-batch SuperPoint extraction, the parts that need no GPU: the batch planner of `extract_batch`, the host-side validation of
-`valid_size`, and the `*_ragged` entry points' refusals (null pointers, small canvases) before the device is touched."""
+`valid_size`, and the stage entry points' refusals under `LG_EXTRACT_RAGGED` (null pointers, small canvases) before the device is touched."""
 import ctypes
 
 import pytest
@@ -95,28 +95,44 @@ def test_extract_batch_refuses_empty_sets_and_cpu_tensors():
 
 def test_ragged_entry_points_refuse_bad_arguments_without_gpu():
     lib = _cabi.load()
-    fake = ctypes.c_void_p(16)
+    fake = 16
     arr = (ctypes.c_void_p * 24)(*[16] * 24)
     inv = _cabi.LG_ERR_INVALID
     big = 1 << 40
-    # lg_sp_encode_ragged: canvas below 8 x 8, batch < 1, null image / sizes / outputs, the split form's 2^25-pixel canvas
-    assert lib.lg_sp_encode_ragged(fake, 2, 7, 64, fake, arr, fake, big, fake, fake, 0, None) == inv and b"at least 8" in lib.lg_last_error()
-    assert lib.lg_sp_encode_ragged(fake, 2, 64, 7, fake, arr, fake, big, fake, fake, 1, None) == inv
-    assert lib.lg_sp_encode_ragged(fake, 0, 64, 64, fake, arr, fake, big, fake, fake, 0, None) == inv
-    assert lib.lg_sp_encode_ragged(fake, 2, 64, 64, None, arr, fake, big, fake, fake, 0, None) == inv and b"null pointer" in lib.lg_last_error()
-    assert lib.lg_sp_encode_ragged(None, 2, 64, 64, fake, arr, fake, big, fake, fake, 0, None) == inv and b"null pointer" in lib.lg_last_error()
-    assert lib.lg_sp_encode_ragged(fake, 2, 64, 64, fake, arr, fake, big, None, fake, 0, None) == inv
-    assert lib.lg_sp_encode_ragged(fake, 2, 64, 64, fake, arr, fake, 16, fake, fake, 0, None) == inv and b"workspace" in lib.lg_last_error()
-    assert lib.lg_sp_encode_ragged(fake, 1, 8192, 4096, fake, arr, fake, big, fake, fake, 1, None) == inv and b"2^25" in lib.lg_last_error()
-    # lg_sp_detect_ragged
-    tail = (4, 4, 0.0005, 0, 64, 4096, fake, big, fake, fake, fake, None, None)
-    assert lib.lg_sp_detect_ragged(fake, 1, 64, 64, None, *tail) == inv and b"null pointer" in lib.lg_last_error()
-    assert lib.lg_sp_detect_ragged(None, 1, 64, 64, fake, *tail) == inv and b"null pointer" in lib.lg_last_error()
-    assert lib.lg_sp_detect_ragged(fake, 1, 7, 64, fake, *tail) == inv and b"at least 8" in lib.lg_last_error()
-    assert lib.lg_sp_detect_ragged(fake, 0, 64, 64, fake, *tail) == inv
-    # lg_sp_sample_descriptors_ragged / _half
-    for fn in (lib.lg_sp_sample_descriptors_ragged, lib.lg_sp_sample_descriptors_ragged_half):
-        assert fn(fake, 1, 256, 8, 8, None, fake, None, 4, 8, 1, fake, fake, None) == inv and b"null pointer" in lib.lg_last_error()
-        assert fn(None, 1, 256, 8, 8, fake, fake, None, 4, 8, 1, fake, fake, None) == inv and b"null pointer" in lib.lg_last_error()
-        assert fn(fake, 0, 256, 8, 8, fake, fake, None, 4, 8, 1, fake, fake, None) == inv
-        assert fn(fake, 1, 256, 0, 8, fake, fake, None, 4, 8, 1, fake, fake, None) == inv
+    RAGGED, SPLIT, F16 = _cabi.LG_EXTRACT_RAGGED, _cabi.LG_EXTRACT_SPLIT, _cabi.LG_EXTRACT_DESC_F16
+
+    def encode(**kw):
+        io = _cabi.LgSpEncodeIO(**{**dict(batch=2, h=64, w=64, flags=RAGGED, image=fake, sizes=fake, params=arr, workspace=fake, workspace_bytes=big, scores=fake,
+                                          desc_map=fake), **kw})
+        return lib.lg_sp_encode(ctypes.byref(io), None)
+    # lg_sp_encode, LG_EXTRACT_RAGGED: canvas below 8 x 8, batch < 1, null image / sizes / outputs, the split form's 2^25-pixel canvas
+    assert encode(h=7) == inv and b"at least 8" in lib.lg_last_error()
+    assert encode(w=7, flags=RAGGED | SPLIT) == inv
+    assert encode(batch=0) == inv
+    assert encode(sizes=None) == inv and b"null pointer" in lib.lg_last_error()
+    assert encode(image=None) == inv and b"null pointer" in lib.lg_last_error()
+    assert encode(scores=None) == inv
+    assert encode(workspace_bytes=16) == inv and b"workspace" in lib.lg_last_error()
+    assert encode(batch=1, h=8192, w=4096, flags=RAGGED | SPLIT) == inv and b"2^25" in lib.lg_last_error()
+
+    def detect(**kw):
+        io = _cabi.LgSpDetectIO(**{**dict(batch=1, h=64, w=64, flags=RAGGED, scores=fake, sizes=fake, nms_radius=4, remove_borders=4, detection_threshold=0.0005,
+                                          max_keypoints=0, capacity=64, max_candidates=4096, workspace=fake, workspace_bytes=big, keypoints=fake, kp_scores=fake,
+                                          counts=fake, totals=None), **kw})
+        return lib.lg_sp_detect(ctypes.byref(io), None)
+    # lg_sp_detect, LG_EXTRACT_RAGGED
+    assert detect(sizes=None) == inv and b"null pointer" in lib.lg_last_error()
+    assert detect(scores=None) == inv and b"null pointer" in lib.lg_last_error()
+    assert detect(h=7) == inv and b"at least 8" in lib.lg_last_error()
+    assert detect(batch=0) == inv
+
+    # lg_sp_sample_descriptors, LG_EXTRACT_RAGGED with and without LG_EXTRACT_DESC_F16
+    for flags in (RAGGED, RAGGED | F16):
+        def sample(**kw):
+            io = _cabi.LgSpSampleIO(**{**dict(batch=1, channels=256, h=8, w=8, flags=flags, desc_map=fake, sizes=fake, keypoints=fake, num=None, n=4, cell=8,
+                                              normalize_dense=1, workspace=fake, out=fake), **kw})
+            return lib.lg_sp_sample_descriptors(ctypes.byref(io), None)
+        assert sample(sizes=None) == inv and b"null pointer" in lib.lg_last_error()
+        assert sample(desc_map=None) == inv and b"null pointer" in lib.lg_last_error()
+        assert sample(batch=0) == inv
+        assert sample(h=0) == inv
