@@ -579,6 +579,71 @@ int64_t lg_nn_workspace_bytes(int64_t images0, int64_t images1, int32_t n0, int3
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_nn_match(const lg_nn_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Two-view geometric verification of match lists: hypothesise-and-verify RANSAC with a FIXED hypothesis budget, one call for any number of pairs, reading what
+ * a matcher leaves on the device (keypoint stores, the pair index, matches0).  Stateless like the nearest-neighbour matcher.  The reference has no such step;
+ * this is the definition (tests/twoview_oracle.py restates it in numpy).
+ *   correspondences  row i of matches0[p] is a correspondence (kpts0[i], kpts1[m]), m = matches0[p][i], unless m < 0, i >= num0 of the pair's image 0, m >= n1 or
+ *             m >= num1 of its image 1: such an entry is unmatched and nothing is read through it.  The S_p correspondences are numbered 0 .. S_p - 1 in ascending i.
+ *   models    LG_TWOVIEW_HOMOGRAPHY: x1 ~ H x0, from 4 correspondences.  LG_TWOVIEW_FUNDAMENTAL: x1^T F x0 = 0, from 7, up to 3 real roots per sample (root
+ *             index 0 .. 2).  Both map image 0 to image 1 in the keypoints' own units; a model is 9 floats, row-major.
+ *   sampling  mix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16 (uint32 arithmetic).
+ *             hash(seed, hypothesis, slot) = mix(mix(seed + 0x9E3779B9 * (hypothesis + 1)) + 0x85EBCA6B * (slot + 1)).
+ *             Slot s = 0, 1, .. of hypothesis h draws d = hash(seed, h, s) mod (S_p - s) and skips past the earlier picks: for every earlier pick e in ascending
+ *             order, d += 1 if d >= e.  The picks are distinct.  The pair's position in the list is not part of the key.
+ *   solving   in Hartley-normalised coordinates, computed once per pair and side over all S_p correspondences: x' = (x - centroid) * sqrt(2) / mean distance
+ *             (scale 1 if that distance is 0).  H: the map through the projective basis of the first three picks, valid iff the four triple determinants of
+ *             either side all exceed 1e-3 in magnitude.  F: Gauss-Jordan elimination with row pivoting of the 7 x 9 system, columns F21 and F22 free, valid iff
+ *             every pivot exceeds 1e-4 in magnitude; the cubic det(N1 + z N2) = 0 in closed form, every root polished by two Newton steps and valid iff
+ *             |p'(z)| > 1e-2 (|3 z^2| + |2 A z| + |B|) on the monic cubic p = z^3 + A z^2 + B z + C (a nearly double root is lost to rounding).  The model is
+ *             denormalised and scaled to Frobenius norm 1; a model with a non-finite entry is invalid.  An invalid sample scores 0.
+ *   scoring   division-free, fp32, threshold t in keypoint units.  F: (x1^T F x0)^2 <= t^2 (|(F x0)_{1,2}|^2 + |(F^T x1)_{1,2}|^2) (squared Sampson distance).
+ *             H: with w = h3 . x0, (x1 w - h1 . x0)^2 + (y1 w - h2 . x0)^2 <= t^2 w^2 and w > 0 under the representative +H or -H that gives more inliers:
+ *             the sign of a homography matrix carries no meaning.  On a tie it is the representative in output form (below).  The score of a hypothesis is its
+ *             inlier count.
+ *   winner    most inliers, then the lowest hypothesis index, then the lowest root index (one integer maximum; independent of the launch geometry).
+ *   refit     LG_TWOVIEW_REFINE: once, by least squares over the winner's inliers in the pair's normalised coordinates (DLT for H with >= 4 inliers, 8-point
+ *             for F with >= 8): the 9 x 9 normal matrix in fp64 summed in a fixed order, its smallest eigenvector by cyclic Jacobi in fp64; F is forced to
+ *             rank 2 by F - (F v3) v3^T, v3 the smallest eigenvector of F^T F.  The refit model is kept iff its inlier count is not below the winner's.
+ *   outputs   models[p] in output form: Frobenius norm 1, the entry of largest magnitude positive (the first such entry among equals).  inliers0[p][i] = 1 iff row i is an inlier
+ *             correspondence; num_inliers[p] their number; matches0_out = matches0 on the inliers, -1 elsewhere; best_hypothesis[p] the winner's hypothesis
+ *             index.  An empty result (count 0, zero model, all-false mask, best_hypothesis -1, status LG_OK, nothing non-finite) comes back for S_p below the
+ *             sample size and for a pair whose every hypothesis is invalid or without inliers.
+ *   LG_TWOVIEW_GIVEN_MODELS skips sampling and solving: hypothesis h of pair p is models_in[p][h] as it stands (invalid iff non-finite or all zero).
+ * Pairs: LG_FLAG_INDEXED as in the nearest-neighbour matcher's io (an index outside its store: status LG_ERR_INDEX, an empty result, nothing read through it); without it pair p reads image p.
+ * Every pair's result is a function of its own correspondences, the configuration and the seed alone.
+ * Workspace: lg_twoview_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: the pair's correspondence list and a 32-byte record.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): null io; undefined flag bits; both or neither model bit; n0, n1 in [0, LG_MAX_KEYPOINTS];
+ *   num_hypotheses a multiple of 256 in [256, 65536]; threshold > 0; the workspace size and alignment; no null pointer among the required ones.
+ * A workgroup of the scoring kernel holds 256 hypotheses, one per lane, and streams the correspondences through LDS LG_TWOVIEW_TILE at a time. */
+#define LG_TWOVIEW_HOMOGRAPHY 2048u
+#define LG_TWOVIEW_FUNDAMENTAL 4096u
+#define LG_TWOVIEW_REFINE 8192u
+#define LG_TWOVIEW_GIVEN_MODELS 16384u
+#define LG_TWOVIEW_TILE 256
+typedef struct lg_twoview_io {
+    int32_t pairs, n0, n1, images0, images1;   /* images0 / images1: LG_FLAG_INDEXED only, >= 1                    */
+    uint32_t flags;                        /* LG_FLAG_INDEXED | one of LG_TWOVIEW_HOMOGRAPHY, _FUNDAMENTAL | LG_TWOVIEW_REFINE | LG_TWOVIEW_GIVEN_MODELS */
+    float threshold;                       /* t > 0, in keypoint units                                                */
+    int32_t num_hypotheses;                /* a multiple of 256 in [256, 65536]                                       */
+    uint32_t seed;
+    const float *kpts0, *kpts1;            /* [pairs or images][n][2], read in place                                  */
+    const int32_t *num0, *num1;            /* [pairs or images] live rows, or NULL = n                                */
+    const int32_t *index0, *index1;        /* [pairs], LG_FLAG_INDEXED                                                */
+    const int64_t *matches0;               /* [pairs][n0]: the matcher's output, read in place                        */
+    const float *models_in;                /* [pairs][num_hypotheses][9], LG_TWOVIEW_GIVEN_MODELS only                */
+    void *workspace; int64_t workspace_bytes;
+    float *models;                         /* [pairs][9]                                                              */
+    uint8_t *inliers0;                     /* [pairs][n0]                                                             */
+    int32_t *num_inliers;                  /* [pairs]                                                                 */
+    int64_t *matches0_out;                 /* [pairs][n0], may be NULL                                                */
+    int32_t *best_hypothesis;              /* [pairs], may be NULL                                                    */
+    int32_t *status;                       /* [pairs] LG_OK / LG_ERR_INDEX                                            */
+} lg_twoview_io;
+int64_t lg_twoview_workspace_bytes(int64_t pairs, int32_t n0, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_twoview_verify(const lg_twoview_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

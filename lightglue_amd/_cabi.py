@@ -23,6 +23,8 @@ LG_FLAG_ROOTSIFT0, LG_FLAG_ROOTSIFT1 = 256, 512   # RootSIFT of every row of des
 LG_DESC_KIND = {"float32": 0, "float16": 1, "uint8": 2}   # lg_rootsift src_kind
 LG_FLAG_NN_MUTUAL = 1024                          # lg_nn_match: keep a match only if both directions agree
 LG_EXTRACT_RAGGED, LG_EXTRACT_DESC_F16, LG_EXTRACT_SPLIT = 1, 2, 4   # the extractor stages' io flags: `sizes` is read / binary16 descriptors / split-f16 SuperPoint conv stack
+LG_TWOVIEW_HOMOGRAPHY, LG_TWOVIEW_FUNDAMENTAL, LG_TWOVIEW_REFINE, LG_TWOVIEW_GIVEN_MODELS = 2048, 4096, 8192, 16384   # lg_twoview_verify's io flags
+LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
 
@@ -40,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "lg_preprocess_ragged_table_bytes", "lg_preprocess_ragged_plan", "lg_preprocess_resize_ragged",
     "lg_rootsift", "lg_sift_filter_workspace_bytes", "lg_sift_filter",
     "lg_nn_workspace_bytes", "lg_nn_match",
+    "lg_twoview_workspace_bytes", "lg_twoview_verify",
 )
 
 
@@ -96,6 +99,17 @@ class LgNnIO(C.Structure):
         ("raw0", _fp), ("raw1", _fp), ("matches0", _fp), ("matches1", _fp), ("scores0", _fp), ("scores1", _fp),
         ("matches", _fp), ("match_scores", _fp), ("list_rows", C.c_int32), ("n_matches", _fp), ("status", _fp),
         ("stop", _fp), ("stop_i64", _fp), ("prune0", _fp), ("prune1", _fp),
+    ]
+
+
+class LgTwoViewIO(C.Structure):
+    """lg_twoview_io (include/lightglue_amd.h): one call of the two-view verifier"""
+    _fields_ = [
+        ("pairs", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32), ("images0", C.c_int32), ("images1", C.c_int32), ("flags", C.c_uint32),
+        ("threshold", C.c_float), ("num_hypotheses", C.c_int32), ("seed", C.c_uint32),
+        ("kpts0", _fp), ("kpts1", _fp), ("num0", _fp), ("num1", _fp), ("index0", _fp), ("index1", _fp), ("matches0", _fp), ("models_in", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("models", _fp), ("inliers0", _fp), ("num_inliers", _fp), ("matches0_out", _fp), ("best_hypothesis", _fp), ("status", _fp),
     ]
 
 
@@ -264,6 +278,9 @@ def load() -> C.CDLL:
     lib.lg_nn_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
     lib.lg_nn_workspace_bytes.restype = C.c_int64
     lib.lg_nn_match.argtypes = [C.POINTER(LgNnIO), C.c_void_p]
+    lib.lg_twoview_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
+    lib.lg_twoview_workspace_bytes.restype = C.c_int64
+    lib.lg_twoview_verify.argtypes = [C.POINTER(LgTwoViewIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

@@ -16,6 +16,6 @@ int set_error(int code, const std::string& msg) { g_err = msg; return code; }
 extern "C" {
 
 const char* lg_last_error(void) { return g_err.c_str(); }
-const char* lg_version(void) { return "lightglue_amd 0.5 (gfx950)"; }
+const char* lg_version(void) { return "lightglue_amd 0.6 (gfx950)"; }
 
 }  // extern "C"

@@ -1,0 +1,621 @@
+// lightglue_amd — two-view geometric verification of match lists: RANSAC with a fixed hypothesis budget for a homography or a fundamental matrix per pair
+// (lg_twoview_verify; the definition is in include/lightglue_amd.h).  Three launches per call:
+//   tv_compact     one workgroup per pair: matches0[p, :] -> the dense list of correspondences (x0, y0, x1, y1) in ascending order of the image-0 keypoint
+//                  (wave ballot + prefix: the order is fixed), its length S_p, the Hartley normalisation of either side, the pair's key reset to 0;
+//   tv_hypothesis  pairs x (H / 256) workgroups, one LANE per hypothesis: the lane draws its sample, solves it (up to 3 models of 9 floats in registers),
+//                  the pair's correspondences stream through LDS in tiles of TV_TILE (every lane reads the same address: a broadcast), the score is the integer
+//                  inlier count, and the best of the pair is one atomicMax on (count, ~hypothesis, ~root);
+//   tv_finalise    one workgroup per pair: the winner recomputed from its hypothesis number, the optional fp64 least-squares refit, mask, count, model.
+// The solvers are compiled without floating-point contraction and the scoring is written in explicit fmaf: a model and a decision are the same bits in
+// tv_hypothesis and tv_finalise, whatever the compiler would fuse in either.
+#include <string>
+
+#include "lg_kernels.h"
+#include "../../include/lightglue_amd.h"
+
+#pragma clang fp contract(off)
+
+namespace lg {
+
+constexpr int TV_THREADS = 256, TV_TILE = LG_TWOVIEW_TILE;
+constexpr int TV_H = 0, TV_F = 1;                        // model kinds
+constexpr float TV_EPS_H = 1e-3f, TV_EPS_F = 1e-4f, TV_EPS_CUBIC = 1e-8f, TV_EPS_ROOT = 1e-2f;
+static_assert(TV_TILE == TV_THREADS, "a tile is loaded by one float4 per thread");
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct TvHeader { int count; unsigned key; float cx0, cy0, s0, cx1, cy1, s1; };       // 32 bytes per pair
+static_assert(sizeof(TvHeader) == 32, "lg_twoview_workspace_bytes counts 32 bytes");
+
+struct TvArgs {
+    int pair0, n0, n1, images0, images1, kind, refine, given, hyps;
+    unsigned seed; float t2;
+    const float* kpts0; const float* kpts1; const int* num0; const int* num1; const int* index0; const int* index1;
+    const long long* matches0; const float* models_in;
+    TvHeader* head; f32x4* corr; int* rows;              // workspace: [pairs], [pairs][n0], [pairs][n0]
+    float* models; unsigned char* inliers0; int* num_inliers; long long* matches0_out; int* best; int* status;
+};
+
+__device__ __forceinline__ bool tv_images(const TvArgs& a, int pair, int& i0, int& i1) {
+    i0 = a.index0 ? a.index0[pair] : pair; i1 = a.index1 ? a.index1[pair] : pair;
+    return (unsigned)i0 < (unsigned)a.images0 && (unsigned)i1 < (unsigned)a.images1;
+}
+__device__ __forceinline__ int tv_live(const int* num, int image, int n) { return num ? min(max(num[image], 0), n) : n; }
+
+// block-wide sum of one double per thread in a fixed order: xor butterfly inside the wave (every lane the same total), then the four waves in ascending order
+__device__ __forceinline__ double tv_block_sum(double v, double* red4) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();                                     // the previous use of red4 has been read
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
+}
+
+// ------------------------------------------------------------------ compaction: one workgroup per pair
+__global__ __launch_bounds__(TV_THREADS) void tv_compact_kernel(TvArgs a) {
+    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int i0, i1;
+    const bool ok = tv_images(a, pair, i0, i1);
+    const int live0 = ok ? tv_live(a.num0, i0, a.n0) : 0, live1 = ok ? tv_live(a.num1, i1, a.n1) : 0;
+    const long long at = (long long)pair * a.n0;
+    f32x4* corr = a.corr + at; int* rows = a.rows + at;
+    __shared__ int wsum[4];
+    __shared__ double red4[4];
+    int base = 0;
+    for (int r0 = 0; r0 < live0; r0 += TV_THREADS) {     // rows at or beyond num0 are unmatched and never read
+        const int i = r0 + tid;
+        long long m = -1;
+        if (i < live0) m = a.matches0[at + i];
+        const bool take = m >= 0 && m < live1;           // live1 <= n1
+        const unsigned long long vote = __ballot(take);
+        __syncthreads();
+        if (lane == 0) wsum[wave] = __popcll(vote);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < 4; ++w) { before += w < wave ? wsum[w] : 0; total += wsum[w]; }
+        if (take) {
+            const int k = base + before + __popcll(vote & ((1ull << lane) - 1ull));
+            const float* p0 = a.kpts0 + ((long long)i0 * a.n0 + i) * 2;
+            const float* p1 = a.kpts1 + ((long long)i1 * a.n1 + m) * 2;
+            corr[k] = f32x4{p0[0], p0[1], p1[0], p1[1]};
+            rows[k] = i;
+        }
+        base += total;
+    }
+    const int S = base;
+    __syncthreads();                                     // the list is complete and visible to the workgroup
+    // Hartley normalisation of either side, sums in fp64 (per-thread strided partial sums, then tv_block_sum)
+    double sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
+    for (int k = tid; k < S; k += TV_THREADS) { const f32x4 c = corr[k]; sx0 += c[0]; sy0 += c[1]; sx1 += c[2]; sy1 += c[3]; }
+    const double inv = S ? 1.0 / S : 0.0;
+    const double cx0 = tv_block_sum(sx0, red4) * inv, cy0 = tv_block_sum(sy0, red4) * inv;
+    const double cx1 = tv_block_sum(sx1, red4) * inv, cy1 = tv_block_sum(sy1, red4) * inv;
+    double d0 = 0, d1 = 0;
+    for (int k = tid; k < S; k += TV_THREADS) {
+        const f32x4 c = corr[k];
+        const double ax = c[0] - cx0, ay = c[1] - cy0, bx = c[2] - cx1, by = c[3] - cy1;
+        d0 += sqrt(ax * ax + ay * ay); d1 += sqrt(bx * bx + by * by);
+    }
+    const double m0 = tv_block_sum(d0, red4) * inv, m1 = tv_block_sum(d1, red4) * inv;
+    if (tid == 0) {
+        TvHeader h;
+        h.count = S; h.key = 0u;
+        h.cx0 = (float)cx0; h.cy0 = (float)cy0; h.s0 = m0 > 0 ? (float)(1.4142135623730951 / m0) : 1.f;
+        h.cx1 = (float)cx1; h.cy1 = (float)cy1; h.s1 = m1 > 0 ? (float)(1.4142135623730951 / m1) : 1.f;
+        a.head[pair] = h;
+    }
+}
+
+// ------------------------------------------------------------------ sampling
+__device__ __forceinline__ unsigned tv_mix(unsigned x) { x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16; return x; }
+__device__ __forceinline__ unsigned tv_hash(unsigned seed, unsigned hyp, unsigned slot) {
+    return tv_mix(tv_mix(seed + 0x9E3779B9u * (hyp + 1u)) + 0x85EBCA6Bu * (slot + 1u));
+}
+// M distinct indices below S (S >= M): slot s draws from S - s and skips past the earlier picks, kept sorted in srt
+template <int M> __device__ __forceinline__ void tv_sample(unsigned seed, unsigned hyp, int S, int (&pick)[M]) {
+    int srt[M];
+#pragma unroll
+    for (int s = 0; s < M; ++s) {
+        int d = (int)(tv_hash(seed, hyp, (unsigned)s) % (unsigned)(S - s));
+#pragma unroll
+        for (int e = 0; e < M; ++e) if (e < s && d >= srt[e]) ++d;
+        pick[s] = d;
+        int v = d;
+#pragma unroll
+        for (int e = 0; e < M; ++e) if (e < s) { const int lo = min(srt[e], v), hi = max(srt[e], v); srt[e] = lo; v = hi; }
+        srt[s] = v;
+    }
+}
+
+// ------------------------------------------------------------------ models: 9 floats, row-major
+__device__ __forceinline__ bool tv_finite9(const float (&m)[9]) {
+    bool f = true;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f = f && isfinite(m[i]);
+    return f;
+}
+// output form: the entry of largest magnitude (the first one among equals) positive.  Every model is scored in this form, so that "+H" means one matrix
+__device__ __forceinline__ void tv_output_form(float (&m)[9]) {
+    float big = m[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) big = fabsf(m[i]) > fabsf(big) ? m[i] : big;
+    const float sgn = big < 0.f ? -1.f : 1.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m[i] = sgn * m[i];
+}
+// m / |m|_F in output form; false if the norm is 0 or anything is non-finite (m is then all zero)
+__device__ __forceinline__ bool tv_unit(float (&m)[9]) {
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) sq = sq + m[i] * m[i];
+    const float nrm = sqrtf(sq);
+    bool ok = nrm > 0.f && isfinite(nrm);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m[i] = m[i] / nrm;
+    ok = ok && tv_finite9(m);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m[i] = ok ? m[i] : 0.f;
+    tv_output_form(m);
+    return ok;
+}
+// G = M T0, T0 = [s0 0 -s0 cx0; 0 s0 -s0 cy0; 0 0 1]: the part of the denormalisation both models share
+template <class T> __device__ __forceinline__ void tv_right_t0(T (&m)[9], T s0, T cx0, T cy0) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const T a = m[3 * r] * s0, b = m[3 * r + 1] * s0;
+        m[3 * r + 2] = (m[3 * r + 2] - a * cx0) - b * cy0;
+        m[3 * r] = a; m[3 * r + 1] = b;
+    }
+}
+// H = T1^-1 Hn T0, F = T1^T Fn T0 (T of side 1 alike)
+template <int KIND, class T> __device__ __forceinline__ void tv_denormalise(T (&m)[9], T cx0, T cy0, T s0, T cx1, T cy1, T s1) {
+    tv_right_t0(m, s0, cx0, cy0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (KIND == TV_H) {
+            m[c] = m[c] / s1 + cx1 * m[6 + c];
+            m[3 + c] = m[3 + c] / s1 + cy1 * m[6 + c];
+        } else {
+            const T a = m[c] * s1, b = m[3 + c] * s1;
+            m[6 + c] = (m[6 + c] - a * cx1) - b * cy1;
+            m[c] = a; m[3 + c] = b;
+        }
+    }
+}
+
+// the projective basis of four points (x, y, 1): c[i] = the cross products of the first three, lam[i] = c[i] . p3, det = c[0] . p0; false below TV_EPS_H
+__device__ __forceinline__ bool tv_basis(const float (&x)[4], const float (&y)[4], float (&c)[3][3], float (&lam)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        c[i][0] = y[j] - y[k]; c[i][1] = x[k] - x[j]; c[i][2] = x[j] * y[k] - y[j] * x[k];
+        lam[i] = (c[i][0] * x[3] + c[i][1] * y[3]) + c[i][2];
+    }
+    const float det = (c[0][0] * x[0] + c[0][1] * y[0]) + c[0][2];
+    return fminf(fminf(fabsf(lam[0]), fabsf(lam[1])), fminf(fabsf(lam[2]), fabsf(det))) > TV_EPS_H;
+}
+// the homography of 4 normalised correspondences q[i] = (x0, y0, x1, y1); normalised model out (not yet of unit norm)
+__device__ __forceinline__ bool tv_solve_h(const f32x4 (&q)[4], float (&h)[9]) {
+    float xs[4], ys[4], xd[4], yd[4], cs[3][3], ls[3], cd[3][3], ld[3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { xs[i] = q[i][0]; ys[i] = q[i][1]; xd[i] = q[i][2]; yd[i] = q[i][3]; }
+    const bool ok0 = tv_basis(xs, ys, cs, ls), ok1 = tv_basis(xd, yd, cd, ld), ok = ok0 && ok1;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) h[e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        const float w = ld[i] * (ls[j] * ls[k]);         // column i of B = ld[i] (xd, yd, 1)_i, row i of A^-1 = cs[i] ls[j] ls[k]
+        const float b[3] = {w * xd[i], w * yd[i], w};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int col = 0; col < 3; ++col) h[3 * r + col] = h[3 * r + col] + b[r] * cs[i][col];
+    }
+    return ok;
+}
+
+__device__ __forceinline__ float tv_det3(const float* r0, const float* r1, const float* r2) {
+    return (r0[0] * (r1[1] * r2[2] - r1[2] * r2[1]) - r0[1] * (r1[0] * r2[2] - r1[2] * r2[0])) + r0[2] * (r1[0] * r2[1] - r1[1] * r2[0]);
+}
+// the null space of 7 normalised correspondences as N1 + z N2 (N1[7] = 1, N2[8] = 1) and the real roots z of det = 0; returns their number, 0 for an invalid sample;
+// well[k]: root k is well conditioned
+__device__ __forceinline__ int tv_solve_f(const f32x4 (&q)[7], float (&n1)[9], float (&n2)[9], float (&z)[3], bool (&well)[3]) {
+    float a[7][9];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const float x = q[i][0], y = q[i][1], u = q[i][2], v = q[i][3];
+        a[i][0] = u * x; a[i][1] = u * y; a[i][2] = u; a[i][3] = v * x; a[i][4] = v * y; a[i][5] = v; a[i][6] = x; a[i][7] = y; a[i][8] = 1.f;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+#pragma unroll
+        for (int i = k + 1; i < 7; ++i) {                // the largest |a[i][k]|, i >= k, ends in row k (the first one on a tie)
+            const bool sw = fabsf(a[i][k]) > fabsf(a[k][k]);
+#pragma unroll
+            for (int c = k; c < 9; ++c) { const float t = a[k][c]; a[k][c] = sw ? a[i][c] : t; a[i][c] = sw ? t : a[i][c]; }
+        }
+        ok = ok && fabsf(a[k][k]) > TV_EPS_F;
+        const float piv = a[k][k];
+#pragma unroll
+        for (int c = k; c < 9; ++c) a[k][c] = a[k][c] / piv;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            if (i == k) continue;
+            const float f = a[i][k];
+#pragma unroll
+            for (int c = k; c < 9; ++c) a[i][c] = a[i][c] - f * a[k][c];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) { n1[i] = -a[i][7]; n2[i] = -a[i][8]; }
+    n1[7] = 1.f; n1[8] = 0.f; n2[7] = 0.f; n2[8] = 1.f;
+    // det(N1 + z N2) = c0 + c1 z + c2 z^2 + c3 z^3 by multilinearity in the rows
+    const float c0 = tv_det3(n1, n1 + 3, n1 + 6), c3 = tv_det3(n2, n2 + 3, n2 + 6);
+    const float c1 = (tv_det3(n2, n1 + 3, n1 + 6) + tv_det3(n1, n2 + 3, n1 + 6)) + tv_det3(n1, n1 + 3, n2 + 6);
+    const float c2 = (tv_det3(n1, n2 + 3, n2 + 6) + tv_det3(n2, n1 + 3, n2 + 6)) + tv_det3(n2, n2 + 3, n1 + 6);
+    ok = ok && fabsf(c3) > TV_EPS_CUBIC;
+    const float A = c2 / c3, B = c1 / c3, C = c0 / c3;
+    const float Q = (A * A - 3.f * B) / 9.f, R = ((2.f * A * A * A - 9.f * A * B) + 27.f * C) / 54.f;
+    const float Q3 = Q * Q * Q, R2 = R * R;
+    int n;
+    if (R2 < Q3) {
+        const float th = acosf(fminf(fmaxf(R / sqrtf(Q3), -1.f), 1.f)), sq = -2.f * sqrtf(Q);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) z[k] = sq * cosf((th + 6.2831853071795865f * (float)k) / 3.f) - A / 3.f;
+        n = 3;
+    } else {
+        const float e = -copysignf(cbrtf(fabsf(R) + sqrtf(R2 - Q3)), R);
+        const float g = e != 0.f ? Q / e : 0.f;
+        z[0] = (e + g) - A / 3.f; z[1] = z[2] = 0.f;
+        n = 1;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {                 // Newton on the monic cubic
+            const float p = ((z[k] + A) * z[k] + B) * z[k] + C, dp = (3.f * z[k] + 2.f * A) * z[k] + B;
+            if (fabsf(dp) > 1e-20f) z[k] = z[k] - p / dp;
+        }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {                        // a (nearly) double root is lost to rounding: |p'(z)| against the size of its terms
+        const float dp = (3.f * z[k] + 2.f * A) * z[k] + B;
+        well[k] = fabsf(dp) > TV_EPS_ROOT * ((fabsf((3.f * z[k]) * z[k]) + fabsf((2.f * A) * z[k])) + fabsf(B));
+    }
+    return ok ? n : 0;
+}
+
+// the sample of hypothesis `hyp`, normalised
+template <int M> __device__ __forceinline__ void tv_gather(const TvHeader& h, const f32x4* corr, unsigned seed, unsigned hyp, f32x4 (&q)[M]) {
+    int pick[M];
+    tv_sample<M>(seed, hyp, h.count, pick);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        const f32x4 c = corr[pick[i]];
+        q[i] = f32x4{(c[0] - h.cx0) * h.s0, (c[1] - h.cy0) * h.s0, (c[2] - h.cx1) * h.s1, (c[3] - h.cy1) * h.s1};
+    }
+}
+// the models of hypothesis `hyp` of a pair, denormalised, unit norm: m[r] valid for r < the returned number (invalid ones in between are all zero, see valid[])
+template <int KIND> __device__ __forceinline__ int tv_models(const TvArgs& a, const TvHeader& h, const f32x4* corr, int pair, int hyp, float (&m)[3][9], bool (&valid)[3]) {
+    valid[0] = valid[1] = valid[2] = false;
+    if (a.given) {
+        const float* src = a.models_in + ((long long)pair * a.hyps + hyp) * 9;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { m[0][e] = src[e]; m[1][e] = m[2][e] = 0.f; any = any || src[e] != 0.f; }
+        valid[0] = any && tv_finite9(m[0]);
+        tv_output_form(m[0]);
+        return 1;
+    }
+    if (KIND == TV_H) {
+        f32x4 q[4];
+        tv_gather<4>(h, corr, a.seed, (unsigned)hyp, q);
+        const bool ok = tv_solve_h(q, m[0]);
+        tv_denormalise<TV_H, float>(m[0], h.cx0, h.cy0, h.s0, h.cx1, h.cy1, h.s1);
+        valid[0] = tv_unit(m[0]) && ok;
+        return 1;
+    } else {
+        f32x4 q[7];
+        float n1[9], n2[9], z[3];
+        bool well[3];
+        tv_gather<7>(h, corr, a.seed, (unsigned)hyp, q);
+        const int n = tv_solve_f(q, n1, n2, z, well);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) m[r][e] = n1[e] + z[r] * n2[e];
+            tv_denormalise<TV_F, float>(m[r], h.cx0, h.cy0, h.s0, h.cx1, h.cy1, h.s1);
+            valid[r] = tv_unit(m[r]) && well[r] && r < n;
+        }
+        return n > 0 ? n : 1;
+    }
+}
+
+// ------------------------------------------------------------------ the inlier test: 0 = outside, +1 = inside (H: with w > 0), -1 = inside with w < 0 (H only)
+template <int KIND> __device__ __forceinline__ int tv_test(const float (&m)[9], const f32x4& p, float t2) {
+    const float x = p[0], y = p[1], u = p[2], v = p[3];
+    const float l0 = fmaf(m[0], x, fmaf(m[1], y, m[2])), l1 = fmaf(m[3], x, fmaf(m[4], y, m[5])), l2 = fmaf(m[6], x, fmaf(m[7], y, m[8]));
+    if (KIND == TV_H) {
+        const float dx = fmaf(u, l2, -l0), dy = fmaf(v, l2, -l1);
+        const bool in = fmaf(dx, dx, dy * dy) <= t2 * (l2 * l2);
+        return in ? (l2 > 0.f ? 1 : l2 < 0.f ? -1 : 0) : 0;
+    } else {
+        const float r = fmaf(u, l0, fmaf(v, l1, l2));
+        const float g0 = fmaf(m[0], u, fmaf(m[3], v, m[6])), g1 = fmaf(m[1], u, fmaf(m[4], v, m[7]));
+        const float den = fmaf(l0, l0, fmaf(l1, l1, fmaf(g0, g0, g1 * g1)));
+        return r * r <= t2 * den ? 1 : 0;
+    }
+}
+
+// ------------------------------------------------------------------ hypotheses: one lane each
+template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_hypothesis_kernel(TvArgs a) {
+    __shared__ f32x4 tile[TV_TILE];
+    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x, hyp = blockIdx.y * TV_THREADS + tid;
+    const TvHeader h = a.head[pair];
+    const int S = h.count;
+    if (S < (a.given ? 1 : KIND == TV_H ? 4 : 7)) return;       // uniform per workgroup: the key stays 0
+    const f32x4* corr = a.corr + (long long)pair * a.n0;
+    float m[3][9]; bool valid[3];
+    tv_models<KIND>(a, h, corr, pair, hyp, m, valid);
+    int pos[3] = {0, 0, 0}, neg[3] = {0, 0, 0};
+    for (int t0 = 0; t0 < S; t0 += TV_TILE) {
+        if (t0) __syncthreads();
+        if (t0 + tid < S) tile[tid] = corr[t0 + tid];
+        __syncthreads();
+        const int cnt = min(TV_TILE, S - t0);
+        for (int j = 0; j < cnt; ++j) {
+            const f32x4 p = tile[j];                     // one address for the whole wave: a broadcast
+#pragma unroll
+            for (int r = 0; r < (KIND == TV_H ? 1 : 3); ++r) {
+                const int in = tv_test<KIND>(m[r], p, a.t2);
+                pos[r] += in > 0; neg[r] += in < 0;
+            }
+        }
+    }
+    unsigned key = 0u;
+#pragma unroll
+    for (int r = (KIND == TV_H ? 0 : 2); r >= 0; --r) {
+        const int count = valid[r] ? max(pos[r], neg[r]) : 0;
+        const unsigned k = count > 0 ? ((unsigned)count << 18) | ((0xFFFFu - (unsigned)hyp) << 2) | (3u - (unsigned)r) : 0u;
+        key = max(key, k);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, o, 64));
+    if ((tid & 63) == 0 && key) atomicMax(&a.head[pair].key, key);
+}
+
+// ------------------------------------------------------------------ finalise: one workgroup per pair
+// cyclic Jacobi on the symmetric n x n matrix A (row-major, destroyed), eigenvectors in the columns of V; returns the index of the smallest eigenvalue.  One lane.
+__device__ int tv_jacobi(double* A, double* V, int n) {
+    for (int i = 0; i < n * n; ++i) V[i] = (i / n == i % n) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        double off = 0, diag = 0;
+        for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { const double v = A[p * n + q]; if (p == q) diag += v * v; else off += v * v; }
+        if (off <= 1e-32 * diag) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[p * n + q];
+                if (apq == 0.0) continue;
+                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) { const double x = A[k * n + p], y = A[k * n + q]; A[k * n + p] = c * x - s * y; A[k * n + q] = s * x + c * y; }
+                for (int k = 0; k < n; ++k) { const double x = A[p * n + k], y = A[q * n + k]; A[p * n + k] = c * x - s * y; A[q * n + k] = s * x + c * y; }
+                for (int k = 0; k < n; ++k) { const double x = V[k * n + p], y = V[k * n + q]; V[k * n + p] = c * x - s * y; V[k * n + q] = s * x + c * y; }
+            }
+    }
+    int best = 0;
+    for (int i = 1; i < n; ++i) if (A[i * n + i] < A[best * n + best]) best = i;
+    return best;
+}
+
+struct TvCount { int count, sign; };
+// the inlier count of model m (in output form) over the pair's list, the same number in every thread (H: under the sign with more inliers, + on a tie)
+template <int KIND> __device__ __forceinline__ TvCount tv_count(const float (&m)[9], const f32x4* corr, int S, float t2, int* red8) {
+    int pos = 0, neg = 0;
+    for (int k = threadIdx.x; k < S; k += TV_THREADS) { const int in = tv_test<KIND>(m, corr[k], t2); pos += in > 0; neg += in < 0; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { pos += __shfl_xor(pos, o, 64); neg += __shfl_xor(neg, o, 64); }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red8[threadIdx.x >> 6] = pos; red8[4 + (threadIdx.x >> 6)] = neg; }
+    __syncthreads();
+    pos = red8[0] + red8[1] + red8[2] + red8[3]; neg = red8[4] + red8[5] + red8[6] + red8[7];
+    return pos >= neg ? TvCount{pos, 1} : TvCount{neg, -1};
+}
+
+template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_kernel(TvArgs a) {
+    __shared__ unsigned char mask[LG_MAX_KEYPOINTS];
+    __shared__ float model[2][9];
+    __shared__ int red8[8], flag;
+    __shared__ double red4[4], JA[81], JV[81], J3[9], V3[9];
+    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x;
+    int i0, i1;
+    const bool ok = tv_images(a, pair, i0, i1);
+    const TvHeader h = a.head[pair];
+    const int S = h.count;
+    const long long at = (long long)pair * a.n0;
+    const f32x4* corr = a.corr + at; const int* rows = a.rows + at;
+    const unsigned key = h.key;
+    const int hyp = 0xFFFF - (int)((key >> 2) & 0xFFFFu), root = 3 - (int)(key & 3u);
+    for (int i = tid; i < a.n0; i += TV_THREADS) mask[i] = 0;
+    float fin[9];
+    TvCount cur{0, 1};
+    if (key) {                                           // uniform per workgroup
+        if (tid == 0) {
+            float m[3][9]; bool valid[3];
+            tv_models<KIND>(a, h, corr, pair, hyp, m, valid);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) if (r == root) for (int e = 0; e < 9; ++e) model[0][e] = m[r][e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 9; ++e) fin[e] = model[0][e];
+        cur = tv_count<KIND>(fin, corr, S, a.t2, red8);
+        if (a.refine && cur.count >= (KIND == TV_H ? 4 : 8)) {
+            // the normal matrix of the inliers in the pair's normalised coordinates, upper triangle, fp64
+            double acc[45];
+#pragma unroll
+            for (int e = 0; e < 45; ++e) acc[e] = 0.0;
+            for (int k = tid; k < S; k += TV_THREADS) {
+                const f32x4 c = corr[k];
+                if (tv_test<KIND>(fin, c, a.t2) != cur.sign) continue;
+                const double x = ((double)c[0] - h.cx0) * h.s0, y = ((double)c[1] - h.cy0) * h.s0, u = ((double)c[2] - h.cx1) * h.s1, v = ((double)c[3] - h.cy1) * h.s1;
+                if (KIND == TV_H) {
+                    const double r1[9] = {-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u}, r2[9] = {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v};
+                    int e = 0;
+#pragma unroll
+                    for (int p = 0; p < 9; ++p)
+#pragma unroll
+                        for (int q = p; q < 9; ++q) { acc[e] += r1[p] * r1[q] + r2[p] * r2[q]; ++e; }
+                } else {
+                    const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+                    int e = 0;
+#pragma unroll
+                    for (int p = 0; p < 9; ++p)
+#pragma unroll
+                        for (int q = p; q < 9; ++q) { acc[e] += r1[p] * r1[q]; ++e; }
+                }
+            }
+            {
+                int e = 0;
+#pragma unroll
+                for (int p = 0; p < 9; ++p)
+#pragma unroll
+                    for (int q = p; q < 9; ++q) {
+                        const double s = tv_block_sum(acc[e], red4);
+                        if (tid == 0) { JA[p * 9 + q] = s; JA[q * 9 + p] = s; }
+                        ++e;
+                    }
+            }
+            if (tid == 0) {
+                const int col = tv_jacobi(JA, JV, 9);
+                double f[9];
+                for (int e = 0; e < 9; ++e) f[e] = JV[e * 9 + col];
+                if (KIND == TV_F) {                      // rank 2: F - (F v3) v3^T, v3 the smallest eigenvector of F^T F
+                    for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) J3[p * 3 + q] = f[p] * f[q] + f[3 + p] * f[3 + q] + f[6 + p] * f[6 + q];
+                    const int c3 = tv_jacobi(J3, V3, 3);
+                    const double v3[3] = {V3[c3], V3[3 + c3], V3[6 + c3]};
+                    for (int r = 0; r < 3; ++r) {
+                        const double fv = f[3 * r] * v3[0] + f[3 * r + 1] * v3[1] + f[3 * r + 2] * v3[2];
+                        for (int c = 0; c < 3; ++c) f[3 * r + c] -= fv * v3[c];
+                    }
+                }
+                tv_denormalise<KIND, double>(f, (double)h.cx0, (double)h.cy0, (double)h.s0, (double)h.cx1, (double)h.cy1, (double)h.s1);
+                double sq = 0;
+                for (int e = 0; e < 9; ++e) sq += f[e] * f[e];
+                const double nrm = sqrt(sq);
+                bool good = nrm > 0 && isfinite(nrm);
+                float ref[9];
+                for (int e = 0; e < 9; ++e) { ref[e] = good ? (float)(f[e] / nrm) : 0.f; good = good && isfinite(ref[e]); }
+                tv_output_form(ref);
+                for (int e = 0; e < 9; ++e) model[1][e] = ref[e];
+                flag = good ? 1 : 0;
+            }
+            __syncthreads();
+            if (flag) {                                  // uniform
+                float ref[9];
+#pragma unroll
+                for (int e = 0; e < 9; ++e) ref[e] = model[1][e];
+                const TvCount again = tv_count<KIND>(ref, corr, S, a.t2, red8);
+                if (again.count >= cur.count) {
+                    cur = again;
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) fin[e] = ref[e];
+                }
+            }
+        }
+    }
+    const bool empty = !key || cur.count == 0;
+    __syncthreads();                                     // mask[] is zeroed
+    if (!empty)
+        for (int k = tid; k < S; k += TV_THREADS) if (tv_test<KIND>(fin, corr[k], a.t2) == cur.sign) mask[rows[k]] = 1;
+    __syncthreads();
+    for (int i = tid; i < a.n0; i += TV_THREADS) {
+        const unsigned char in = mask[i];
+        a.inliers0[at + i] = in;
+        if (a.matches0_out) a.matches0_out[at + i] = in ? a.matches0[at + i] : -1;
+    }
+    if (tid == 0) {
+        for (int e = 0; e < 9; ++e) a.models[(long long)pair * 9 + e] = empty ? 0.f : fin[e];      // in output form since it was made
+        a.num_inliers[pair] = empty ? 0 : cur.count;
+        if (a.best) a.best[pair] = empty ? -1 : hyp;
+        a.status[pair] = ok ? LG_OK : LG_ERR_INDEX;
+    }
+}
+
+// ------------------------------------------------------------------ host side
+constexpr uint32_t TV_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_TWOVIEW_HOMOGRAPHY | LG_TWOVIEW_FUNDAMENTAL | LG_TWOVIEW_REFINE | LG_TWOVIEW_GIVEN_MODELS;
+constexpr int TV_PAIRS_PER_LAUNCH = 1 << 20;             // pairs are grid.x (as in lg_nn_match)
+
+struct TvLayout { long long head, corr, rows, total; };
+static const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& L) {
+    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
+    if (n0 < 0 || n0 > LG_MAX_KEYPOINTS) return "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]";
+    if (flags & ~TV_KNOWN_FLAGS) return "undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)";
+    if (!(flags & LG_TWOVIEW_HOMOGRAPHY) == !(flags & LG_TWOVIEW_FUNDAMENTAL)) return "exactly one of LG_TWOVIEW_HOMOGRAPHY and LG_TWOVIEW_FUNDAMENTAL must be set";
+    auto up = [](long long b) { return (b + 255) / 256 * 256; };
+    L.head = 0; L.corr = up(pairs * 32); L.rows = L.corr + up(pairs * n0 * 16); L.total = L.rows + up(pairs * n0 * 4);
+    return nullptr;
+}
+
+template <int KIND> static void tv_launch(const TvArgs& a, int count, hipStream_t s) {
+    hipLaunchKernelGGL(tv_compact_kernel, dim3(count), dim3(TV_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tv_hypothesis_kernel<KIND>, dim3(count, a.hyps / TV_THREADS), dim3(TV_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tv_finalise_kernel<KIND>, dim3(count), dim3(TV_THREADS), 0, s, a);
+}
+
+}  // namespace lg
+
+using namespace lg;
+
+extern "C" {
+
+int64_t lg_twoview_workspace_bytes(int64_t pairs, int32_t n0, uint32_t flags) {
+    TvLayout L;
+    return tv_layout(pairs, n0, flags, L) ? -1 : L.total;
+}
+
+int lg_twoview_verify(const lg_twoview_io* io, void* hip_stream) {
+    if (!io) return set_error(LG_ERR_INVALID, "lg_twoview_verify: null io");
+    TvLayout L;
+    if (const char* why = tv_layout(io->pairs, io->n0, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_twoview_verify: ") + why);
+    if (io->n1 < 0 || io->n1 > LG_MAX_KEYPOINTS) return set_error(LG_ERR_INVALID, "lg_twoview_verify: n0, n1 must lie in [0, LG_MAX_KEYPOINTS]");
+    if (io->num_hypotheses < 256 || io->num_hypotheses > 65536 || io->num_hypotheses % 256)
+        return set_error(LG_ERR_INVALID, "lg_twoview_verify: num_hypotheses must be a multiple of 256 in [256, 65536]");
+    if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return set_error(LG_ERR_INVALID, "lg_twoview_verify: threshold must be > 0 (and finite)");
+    const bool indexed = io->flags & LG_FLAG_INDEXED, given = io->flags & LG_TWOVIEW_GIVEN_MODELS;
+    const int P = io->pairs, n0 = io->n0, n1 = io->n1;
+    if (indexed && (!io->index0 || !io->index1 || io->images0 < 1 || io->images1 < 1))
+        return set_error(LG_ERR_INVALID, "lg_twoview_verify: LG_FLAG_INDEXED needs index0, index1 and images0, images1 >= 1");
+    if (!io->models || !io->num_inliers || !io->status || (n0 && (!io->inliers0 || !io->matches0)) || (n0 && n1 && (!io->kpts0 || !io->kpts1)) || (given && !io->models_in))
+        return set_error(LG_ERR_INVALID, "lg_twoview_verify: null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status");
+    if (!io->workspace) return set_error(LG_ERR_INVALID, "lg_twoview_verify: null workspace");
+    if (io->workspace_bytes < L.total)
+        return set_error(LG_ERR_INVALID, "lg_twoview_verify: the workspace holds " + std::to_string(io->workspace_bytes) + " bytes, lg_twoview_workspace_bytes = " + std::to_string(L.total));
+    if (reinterpret_cast<uintptr_t>(io->workspace) & 255) return set_error(LG_ERR_INVALID, "lg_twoview_verify: the workspace must be 256-byte aligned");
+    if (P == 0) return LG_OK;
+
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    char* ws = static_cast<char*>(io->workspace);
+    TvArgs a{};
+    a.n0 = n0; a.n1 = n1; a.images0 = indexed ? io->images0 : P; a.images1 = indexed ? io->images1 : P;
+    a.kind = (io->flags & LG_TWOVIEW_HOMOGRAPHY) ? TV_H : TV_F; a.refine = (io->flags & LG_TWOVIEW_REFINE) ? 1 : 0; a.given = given ? 1 : 0;
+    a.hyps = io->num_hypotheses; a.seed = io->seed; a.t2 = io->threshold * io->threshold;
+    a.kpts0 = io->kpts0; a.kpts1 = io->kpts1; a.num0 = io->num0; a.num1 = io->num1;
+    a.index0 = indexed ? io->index0 : nullptr; a.index1 = indexed ? io->index1 : nullptr;
+    a.matches0 = reinterpret_cast<const long long*>(io->matches0); a.models_in = io->models_in;
+    a.head = reinterpret_cast<TvHeader*>(ws + L.head); a.corr = reinterpret_cast<f32x4*>(ws + L.corr); a.rows = reinterpret_cast<int*>(ws + L.rows);
+    a.models = io->models; a.inliers0 = io->inliers0; a.num_inliers = io->num_inliers;
+    a.matches0_out = reinterpret_cast<long long*>(io->matches0_out); a.best = io->best_hypothesis; a.status = io->status;
+    for (int p0 = 0; p0 < P; p0 += TV_PAIRS_PER_LAUNCH) {
+        a.pair0 = p0;
+        const int count = P - p0 < TV_PAIRS_PER_LAUNCH ? P - p0 : TV_PAIRS_PER_LAUNCH;
+        if (a.kind == TV_H) tv_launch<TV_H>(a, count, s); else tv_launch<TV_F>(a, count, s);
+        HIPCHK(hipGetLastError());
+    }
+    return LG_OK;
+}
+
+}  // extern "C"

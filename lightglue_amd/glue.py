@@ -203,6 +203,15 @@ def match_pairs(matcher, feats, pairs, feats1=None) -> list:
     return out
 
 
+def verify_pairs(verifier, result, feats, pairs, feats1=None) -> dict:
+    """Geometric verification of what `matcher.match_pairs(feats, pairs, feats1)` returned (`result`: its dict or its `DeferredMatches`), by a
+    `TwoViewVerifier`: the same stores (or lists of per-image dicts, collated once) and the same pair list; only `keypoints` and `num_keypoints` are read.
+    Returns the verifier's dict: models [P, 3, 3], inliers0 [P, N0], num_inliers [P], matches0 (-1 off the inliers), matches, best_hypothesis."""
+    store0 = collate_features(feats) if isinstance(feats, (list, tuple)) else feats
+    store1 = None if feats1 is None or feats1 is feats else (collate_features(feats1) if isinstance(feats1, (list, tuple)) else feats1)
+    return verifier.verify_pairs(store0, pairs, result, store1)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output

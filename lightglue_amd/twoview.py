@@ -1,0 +1,144 @@
+"""Two-view geometric verification of match lists on the device: RANSAC with a fixed hypothesis budget for a homography or a fundamental matrix per pair, on the
+kernels of `csrc/lg_twoview.hip` behind `lg_twoview_verify` (include/lightglue_amd.h holds the definition).  It reads what a matcher leaves on the device — the
+keypoint stores, the pair list and `matches0` — in place, runs any number of pairs in ONE call with ONE host synchronisation, and every pair's result is a
+function of its own correspondences, the configuration and the seed alone: the same bits wherever the pair stands in a list."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import _cabi, _call
+
+MODELS = {"homography": _cabi.LG_TWOVIEW_HOMOGRAPHY, "fundamental": _cabi.LG_TWOVIEW_FUNDAMENTAL}
+
+
+class TwoViewVerifier(nn.Module):
+    """model: "homography" (x1 ~ H x0, 4-point samples) or "fundamental" (x1^T F x0 = 0, 7-point samples).  threshold: the inlier distance in keypoint units
+    (reprojection error for H, Sampson distance for F).  num_hypotheses: the fixed budget, a multiple of 256 in [256, 65536].  refine: one least-squares refit
+    on the winner's inliers, kept if the inlier count does not drop.  seed: the only source of randomness."""
+    required_data_keys = ("image0", "image1")
+
+    def __init__(self, model: str = "fundamental", threshold: float = 3.0, num_hypotheses: int = 1024, refine: bool = True, seed: int = 0):
+        super().__init__()
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
+        if not float(threshold) > 0.0:
+            raise ValueError(f"threshold must be > 0, got {threshold!r}")
+        if int(num_hypotheses) % 256 or not 256 <= int(num_hypotheses) <= 65536:
+            raise ValueError(f"num_hypotheses must be a multiple of 256 in [256, 65536], got {num_hypotheses!r}")
+        if not 0 <= int(seed) < 2 ** 32:
+            raise ValueError(f"seed must lie in [0, 2^32), got {seed!r}")
+        self.model, self.threshold, self.num_hypotheses, self.refine, self.seed = model, float(threshold), int(num_hypotheses), bool(refine), int(seed)
+
+    # ------------------------------------------------------------------ one side of a call
+    @staticmethod
+    def _side(feats: dict, device, what: str) -> _call.Side:
+        """{keypoints [K, N, 2], num_keypoints [K] (optional)} -> the `_call.Side` of it; nothing else is read."""
+        kpts = feats["keypoints"]
+        assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
+        s = _call.Side()
+        s.K, s.N = int(kpts.shape[0]), int(kpts.shape[1])
+        s.kpts = _call._engine_descriptors(kpts, device, keep=())
+        s.desc = s.size = s.scales = s.oris = s.num = None
+        s.rootsift = False
+        num = feats.get("num_keypoints")
+        if num is not None:
+            num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
+            assert num.shape == (s.K,), f"{what}: num_keypoints must have shape [{s.K}]"
+            s.num = num.clamp(0, s.N)
+        return s
+
+    def _sides(self, feats0: dict, feats1: dict, names=("feats0", "feats1")):
+        device = feats0["keypoints"].device
+        _call.require_gpu(device, "keypoints")
+        s0 = self._side(feats0, device, names[0])
+        s1 = s0 if feats1 is feats0 else self._side(feats1, device, names[1])
+        return device, s0, s1
+
+    # ------------------------------------------------------------------ the call path
+    def _launch(self, device, s0, s1, P: int, index, result, models=None) -> dict:
+        """P pairs in ONE lg_twoview_verify call on the current stream, then the dict behind the one host synchronisation of the call."""
+        if isinstance(result, _call.DeferredMatches):
+            result = result.result()
+        m0 = result["matches0"] if isinstance(result, dict) else result
+        assert torch.is_tensor(m0) and tuple(m0.shape) == (P, s0.N), f"matches0 must have shape [{P}, {s0.N}], got {tuple(m0.shape)}"
+        if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
+            m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+        H = self.num_hypotheses
+        flags = MODELS[self.model] | (_cabi.LG_TWOVIEW_REFINE if self.refine else 0) | (0 if index is None else _cabi.LG_FLAG_INDEXED)
+        if models is not None:
+            assert models.dim() == 4 and models.shape[0] == P and tuple(models.shape[2:]) == (3, 3), f"models must have shape [{P}, H, 3, 3], got {tuple(models.shape)}"
+            H = int(models.shape[1])
+            models = models.detach().to(device=device, dtype=torch.float32).contiguous()
+            flags |= _cabi.LG_TWOVIEW_GIVEN_MODELS
+        out_models = torch.empty((P, 3, 3), device=device, dtype=torch.float32)
+        inl = torch.empty((P, s0.N), device=device, dtype=torch.uint8)
+        verified = torch.empty((P, s0.N), device=device, dtype=torch.int64)
+        ints = torch.empty((3, P), device=device, dtype=torch.int32)          # [0] = num_inliers, [1] = best_hypothesis, [2] = status
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            if P:
+                lib = _cabi.load()
+                nbytes = lib.lg_twoview_workspace_bytes(P, s0.N, flags)       # -1: outside the envelope — lg_twoview_verify below says why
+                ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
+                p = _call._ptr
+                io = _cabi.LgTwoViewIO(
+                    pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
+                    kpts0=p(s0.kpts), kpts1=p(s1.kpts), num0=p(s0.num), num1=p(s1.num),
+                    index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
+                    matches0=p(m0), models_in=p(models), workspace=p(ws), workspace_bytes=max(nbytes, 0),
+                    models=p(out_models), inliers0=p(inl), num_inliers=ints[0].data_ptr(), matches0_out=p(verified),
+                    best_hypothesis=ints[1].data_ptr(), status=ints[2].data_ptr())
+                _cabi.check(lib.lg_twoview_verify(C.byref(io), C.c_void_p(stream.cuda_stream)))
+            host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
+        mask = inl.bool()
+        # the ragged lists without another synchronisation: a stable sort puts every pair's inlier rows first, in ascending order; their number is on the host
+        order = torch.sort((~mask).to(torch.uint8), dim=1, stable=True)[1]
+        listed = torch.stack([order, torch.gather(verified, 1, order)], -1)
+        matches = [listed[b, :c] for b, c in enumerate(host[0])]
+        out = {"models": out_models, "inliers0": mask, "num_inliers": ints[0].long(), "matches0": verified, "matches": matches, "best_hypothesis": ints[1].long()}
+        try:
+            _call.raise_on_status(host[2])
+        except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
+            err.outputs = out
+            raise
+        return out
+
+    @torch.no_grad()
+    def forward(self, data: dict, result) -> dict:
+        """{"image0": feats, "image1": feats}, feats = {keypoints [B, N, 2], num_keypoints [B] (optional)}, and the matcher's result for these B pairs (its dict,
+        a `DeferredMatches` or matches0 [B, N0] itself).  Returns models [B, 3, 3], inliers0 [B, N0] bool, num_inliers [B], matches0 [B, N0] (the verified
+        matches, -1 elsewhere), matches List[[S_i, 2]], best_hypothesis [B] (-1: no model)."""
+        for key in self.required_data_keys:
+            assert key in data, f"Missing key {key} in data"
+        device, s0, s1 = self._sides(data["image0"], data["image1"], self.required_data_keys)
+        assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+        return self._launch(device, s0, s1, s0.K, None, result)
+
+    def _pairs(self, feats0, pairs, feats1, validate):
+        same = feats1 is None or feats1 is feats0
+        K0 = int(feats0["keypoints"].shape[0])
+        K1 = K0 if same else int(feats1["keypoints"].shape[0])
+        pt = _call.pair_list(pairs, K0, K1, validate)
+        P = int(pt.shape[0])
+        device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
+        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None     # [2, P]: index0 | index1
+        return device, s0, s1, P, index
+
+    @torch.no_grad()
+    def verify_pairs(self, feats0: dict, pairs, result, feats1: Optional[dict] = None, *, validate: bool = True) -> dict:
+        """The pair list of `match_pairs` verified: pair p = (i, j) reads the keypoints of image i of the store `feats0` and image j of `feats1` (None: of
+        `feats0` too) in place through the index, and row p of `result`'s matches0.  Outputs allocated once for all P pairs, ONE host synchronisation, no
+        chunking.  `validate` as in `match_pairs`: without it an index outside its store gives LG_ERR_INDEX for that pair (raised after the call)."""
+        device, s0, s1, P, index = self._pairs(feats0, pairs, feats1, validate)
+        return self._launch(device, s0, s1, P, index, result)
+
+    @torch.no_grad()
+    def score_models(self, feats0: dict, pairs, result, models: torch.Tensor, feats1: Optional[dict] = None, *, validate: bool = True) -> dict:
+        """Verification against given geometry (LG_TWOVIEW_GIVEN_MODELS): no sampling, no solving — hypothesis h of pair p is models[p, h] ([P, H, 3, 3], H a
+        multiple of 256) as it stands, and the winner is the one with the most inliers, the lowest h on a tie."""
+        device, s0, s1, P, index = self._pairs(feats0, pairs, feats1, validate)
+        return self._launch(device, s0, s1, P, index, result, models=models)
