@@ -1,7 +1,8 @@
-"""The mechanics of one matcher call, written once for `LightGlue.forward` and `LightGlue.match_pairs` (lightglue.py keeps the class: conf, weights, engine
-handle, the launch path and the public methods): what the engine reads of one side (`normalise_side`), how a pair list is cut into engine calls
-(`plan_pair_chunks`), the output set of a call (`Outputs`) and its assembly into the reference's dict (`ragged_outputs`, `DeferredMatches`).  Plain tensor and
-pointer arithmetic: nothing here launches a kernel of the engine's.
+"""The mechanics of one call over feature stores, written once for `LightGlue`, `NearestNeighborMatcher` and `TwoViewVerifier` (each module keeps its class:
+configuration, the launch path and the public methods): what a caller reads of one side (`build_side`; `normalise_side` is the engine's reading), the opening
+of a call (`sides`, `batch_sides` for `forward`, `store_pairs` and `pair_list` for a pair list), how a pair list is cut into engine calls (`plan_pair_chunks`),
+the output set of a call (`Outputs`) and its assembly into the reference's dict (`ragged_outputs`, `DeferredMatches`).  Plain tensor and pointer arithmetic:
+nothing here launches a kernel of the library's.
 """
 from __future__ import annotations
 
@@ -138,30 +139,38 @@ def descriptor_transform(feats: dict, what: str = "feats"):
     return tr
 
 
-def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, what: str = "feats") -> Side:
-    """{keypoints [K, N, 2], descriptors [K, N, input_dim], image_size [K, 2] | [1, 2] | [2] (optional; broadcast as the reference does, ref :35-42),
-    scales / oris [K, N] iff add_scale_ori, num_keypoints [K] (optional; clamped into [0, N]), descriptor_transform None | "rootsift" (optional, not a
-    tensor; anything else is a ValueError)} -> Side.  `forward` calls it for image0 / image1 (K = B) and
-    `match_pairs` for its feature stores, once per call.  Only data pointers are handed on, so every shape is checked here (AssertionError naming the key) and
-    tensors that already qualify pass through untouched: no copy, no kernel."""
+def build_side(feats: dict, device, what: str = "feats", *, keypoints: bool = True, descriptors=None, image_size: bool = False, scale_ori: bool = False) -> Side:
+    """THE reader of one side of a call (LightGlue, NearestNeighborMatcher, TwoViewVerifier): a feature dict -> Side, holding what the caller reads and None
+    elsewhere.  keypoints: [K, N, 2].  descriptors: None = not read, "any" = [K, N, D] of any D, an int = exactly that D; with them the optional non-tensor key
+    descriptor_transform (None | "rootsift"; anything else is a ValueError).  image_size: the optional [K, 2] | [1, 2] | [2], broadcast as the reference does
+    (ref :35-42).  scale_ori: scales / oris [K, N].  num_keypoints [K] is optional everywhere and clamped into [0, N].  Only data pointers are handed on, so
+    every shape is checked here (AssertionError naming the key) and tensors that already qualify pass through untouched: no copy, no kernel."""
     f32 = lambda t: _engine_descriptors(t, device, keep=())
-    kpts, desc = feats["keypoints"], feats["descriptors"]
-    assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
     s = Side()
-    K, N = s.K, s.N = kpts.shape[0], kpts.shape[1]
-    assert tuple(desc.shape) == (K, N, input_dim), f"{what}: descriptors must have shape [{K}, {N}, {input_dim}], got {tuple(desc.shape)}"
-    s.kpts = f32(kpts)
-    s.desc = _engine_descriptors(desc, device)
-    s.rootsift = descriptor_transform(feats, what) == "rootsift"
-    s.size = s.scales = s.oris = s.num = None
-    size = feats.get("image_size")
+    s.kpts = s.desc = s.size = s.scales = s.oris = s.num = None
+    s.rootsift = False
+    kpts, desc = feats["keypoints"] if keypoints else None, None if descriptors is None else feats["descriptors"]
+    if keypoints:
+        assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
+        K, N = kpts.shape[0], kpts.shape[1]
+    if desc is not None:      # [K, N, D]: K and N the keypoints' where those are read, D the caller's unless any will do
+        assert desc.dim() == 3 and (not keypoints or (desc.shape[0], desc.shape[1]) == (K, N)) and descriptors in ("any", desc.shape[2]), \
+            f"{what}: descriptors must have shape [{K if keypoints else 'K'}, {N if keypoints else 'N'}, {'D' if descriptors == 'any' else descriptors}], got {tuple(desc.shape)}"
+        K, N = desc.shape[0], desc.shape[1]
+    s.K, s.N = K, N
+    if keypoints:
+        s.kpts = f32(kpts)
+    if desc is not None:
+        s.desc = _engine_descriptors(desc, device)
+        s.rootsift = descriptor_transform(feats, what) == "rootsift"
+    size = feats.get("image_size") if image_size else None
     if size is not None:
         if not isinstance(size, torch.Tensor):
             size = torch.tensor(size, dtype=torch.float32)
         size = f32(size).reshape(-1, 2)
         assert size.shape[0] in (1, K), f"{what}: image_size must have shape [2], [1, 2] or [{K}, 2]"
         s.size = size if size.shape[0] == K else size.expand(K, 2).contiguous()
-    if add_scale_ori:
+    if scale_ori:
         s.scales, s.oris = f32(feats["scales"]), f32(feats["oris"])
         assert tuple(s.scales.shape) == (K, N) and tuple(s.oris.shape) == (K, N), f"{what}: scales / oris must have shape [{K}, {N}]"
     num = feats.get("num_keypoints")
@@ -170,6 +179,44 @@ def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, wha
         assert num.shape == (K,), f"{what}: num_keypoints must have shape [{K}]"
         s.num = num.clamp(0, N)
     return s
+
+
+def normalise_side(feats: dict, device, input_dim: int, add_scale_ori: bool, what: str = "feats") -> Side:
+    """What the engine reads of one side: keypoints, descriptors [K, N, input_dim], image_size, scales / oris iff add_scale_ori (`build_side`)."""
+    return build_side(feats, device, what, descriptors=input_dim, image_size=True, scale_ori=add_scale_ori)
+
+
+def sides(feats0: dict, feats1: dict, names, build, key: str = "keypoints", check=None):
+    """(device, side 0, side 1) of a call, each converted at most once by build(feats, device, what); a non-GPU device (that of feats0[key]) is refused first,
+    side 1 IS side 0 over one store, check(s0, s1) is the caller's own test of the two together."""
+    device = feats0[key].device
+    require_gpu(device, key)
+    s0 = build(feats0, device, names[0])
+    s1 = s0 if feats1 is feats0 else build(feats1, device, names[1])
+    if check is not None:
+        check(s0, s1)
+    return device, s0, s1
+
+
+def batch_sides(data: dict, keys, build, key: str = "keypoints", check=None):
+    """The opening of every `forward(data)`: both of `keys` present, `sides` of data[keys[0]] / data[keys[1]], as many images on either side."""
+    for k in keys:
+        assert k in data, f"Missing key {k} in data"
+    device, s0, s1 = sides(data[keys[0]], data[keys[1]], keys, build, key, check)
+    assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+    return device, s0, s1
+
+
+def store_pairs(feats0: dict, pairs, feats1, validate: bool, key: str = "keypoints"):
+    """The opening of every call over a pair list (match_pairs, verify_pairs, score_models): (same, P, index).  same: both sides read the store feats0
+    (feats1 None or feats0 itself); the stores hold feats[key].shape[0] images; `pairs` goes through `pair_list` (malformed pairs raise before any device
+    check); index: the int32 [2, P] tensor index0 | index1 on the store's device (a chunk of the list is an offset into both), None for an empty list."""
+    same = feats1 is None or feats1 is feats0
+    K0 = int(feats0[key].shape[0])
+    K1 = K0 if same else int(feats1[key].shape[0])
+    pt = pair_list(pairs, K0, K1, validate)
+    P = int(pt.shape[0])
+    return same, P, pt.to(device=feats0[key].device, dtype=torch.int32).t().contiguous() if P else None
 
 
 # ---------------------------------------------------------------------- the outputs of a call

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void ak_decide_kernel(DetectArgs a, int topk, 
     int any = 0;
     if (a.sizes) { for (int i = threadIdx.x; i < a.H; i += 256) any += a.row_counts[b * a.H + i]; }
     else { for (int i = threadIdx.x; i < a.B * a.H; i += 256) any += a.row_counts[i]; }
-    any = block_sum_int(any, sh);
+    any = block_sum(any, sh);
     double s = 0.0;
     for (int y = threadIdx.x; y < a.H; y += 256) s += rowsum[b * a.H + y];
     shd[threadIdx.x] = s;

@@ -210,16 +210,52 @@ __device__ __forceinline__ int seg_row_base(const RowSpace& rs, int seg) {
     return (seg >> 1) * (rs.cap0 + rs.cap1) + (seg & 1) * rs.cap0;
 }
 
-// ---- source images of a pair (LG_FLAG_INDEXED): the inputs of the forward are per-IMAGE arrays (a feature store) and pair b reads image index0[b] /
-// index1[b] of them.  All zero = not indexed: pair b reads image b of either side.
+// ---- a pair list over feature stores (LG_FLAG_INDEXED), THE definition for the engine's forward, lg_nn_match and lg_twoview_verify: the inputs of a call are
+// per-IMAGE arrays (a feature store) and pair p reads image index0[p] / index1[p] of them.  A null index0 = not indexed: pair p reads image p of either side.
+// When the index of EITHER side lies outside its store, the pair is empty on both sides and ends with the status LG_ERR_INDEX: no kernel forms an input
+// address from it.  The lookup is uniform per workgroup wherever it is used: one or two scalar loads.
 struct PairIndex { const int* index0; const int* index1; int images0, images1; };
-// The image `pair` reads on side `image`, or -1 when the index of EITHER side lies outside its store: such a pair is empty (init_state_kernel gives both of
-// its segments length 0), so no kernel forms an input address from it.  Uniform per workgroup wherever it is used: one or two scalar loads.
+__device__ __forceinline__ bool inside_stores(const PairIndex& px, int s0, int s1) { return (unsigned)s0 < (unsigned)px.images0 && (unsigned)s1 < (unsigned)px.images1; }
+struct PairImages { int i0, i1; bool ok; };      // both images of a pair; not to be used unless ok
+__device__ __forceinline__ PairImages pair_images(const PairIndex& px, int pair) {
+    if (!px.index0) return {pair, pair, true};
+    const int s0 = px.index0[pair], s1 = px.index1[pair];
+    return {s0, s1, inside_stores(px, s0, s1)};
+}
+// One side of it, or -1.  (Its own three lines, not pair_images(...).ok ? ... : -1: through the struct hipcc keeps the flag in a register pair, and the engine's
+// preparation kernels, which read one side per workgroup, come out two to ten scalar instructions longer.)
 __device__ __forceinline__ int source_image(const PairIndex& px, int pair, int image) {
     if (!px.index0) return pair;
     const int s0 = px.index0[pair], s1 = px.index1[pair];
-    if ((unsigned)s0 >= (unsigned)px.images0 || (unsigned)s1 >= (unsigned)px.images1) return -1;
-    return image ? s1 : s0;
+    return !inside_stores(px, s0, s1) ? -1 : image ? s1 : s0;
+}
+// live keypoint rows of `image` of a store of n-row images: num[image] clamped into [0, n]; a null `num` means n
+__device__ __forceinline__ int live_rows(const int* num, int image, int n) { return num ? min(max(num[image], 0), n) : n; }
+
+// ---- 256-thread workgroups (4 waves); every thread calls.  One round of an ORDERED compaction: the slot of this thread's item = `base` + the takers among
+// the threads below it; `base` advances by the round's takers, so rounds over ascending items fill a list in ascending order.  wsum: __shared__ int[4].  Two
+// barriers: the first keeps a wave from overwriting wsum while another still reads the previous round's, the second publishes this round's.
+__device__ __forceinline__ int compact_slot(bool take, int& base, int* wsum) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long vote = __ballot(take);
+    __syncthreads();
+    if (lane == 0) wsum[wave] = __popcll(vote);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 4; ++w) { before += w < wave ? wsum[w] : 0; total += wsum[w]; }
+    const int slot = base + before + __popcll(vote & ((1ull << lane) - 1ull));
+    base += total;
+    return slot;
+}
+// The sum of one value per thread in a fixed order (lg_twoview.hip's fp64 sums are part of its bit-exact contract): xor butterfly inside the wave, then the
+// waves ascending, ((a + b) + c) + d.  sh4: __shared__ T[4]; the first barrier guards its previous use.
+template <class T> __device__ __forceinline__ T block_sum(T v, T* sh4) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
 }
 
 // Workgroup id runs on XCD id % 8 (round-robin dispatch; tools/tail_wall.py: 1024 of 1024).  For a kernel whose tiles share nothing (the

@@ -10,6 +10,7 @@
 
 #include "../../include/lightglue_amd.h"
 #include "lg_forward_plan.h"
+#include "lg_host_call.h"
 #include "lg_kernels.h"
 
 #define TRY(x) do { int _rc = (x); if (_rc != LG_OK) return _rc; } while (0)

@@ -166,6 +166,11 @@ int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
         if ((f.kind == DESC_U8 || f.rootsift) && e->cfg.input_dim % 4) return set_error(LG_ERR_INVALID, "LG_FLAG_DESC*_U8 / LG_FLAG_ROOTSIFT*: input_dim must be a multiple of 4");
         if (f.rootsift && e->cfg.input_dim > 256) return set_error(LG_ERR_INVALID, "LG_FLAG_ROOTSIFT0 / _ROOTSIFT1: input_dim must be at most 256 (one wave holds the row)");
     }
+    const bool ext = (io->flags & LG_FLAG_EXT) != 0;            // round-5 extension fields present
+    if (io->flags & LG_FLAG_INDEXED) {                          // the pair list: a pure argument check too
+        if (!ext || !io->status) return set_error(LG_ERR_INVALID, "lg_engine_forward: LG_FLAG_INDEXED needs LG_FLAG_EXT and a status array");
+        TRY(check_pair_list("lg_engine_forward", io->flags, io->index0, io->index1, io->images0, io->images1));
+    }
     if (!e->weights_ready) return set_error(LG_ERR_STATE, "weights not finalised");
     const int B = io->batch, n0 = io->n0, n1 = io->n1;
     if (B < 1 || n0 < 0 || n1 < 0) return set_error(LG_ERR_INVALID, "bad batch / keypoint counts");
@@ -177,13 +182,7 @@ int check_forward_io(const lg_engine* e, const lg_forward_io* io) {
     const bool do_prune = pruning_on(e->cfg, io->flags);
     if (do_prune && ((n0 && !io->prune0) || (n1 && !io->prune1))) return set_error(LG_ERR_INVALID, "prune0/prune1 required when width_confidence > 0");
     if (e->cfg.add_scale_ori && (!io->scales0 || !io->oris0 || !io->scales1 || !io->oris1)) return set_error(LG_ERR_INVALID, "scales/oris required");
-    const bool ext = (io->flags & LG_FLAG_EXT) != 0;            // round-5 extension fields present
     if ((io->flags & LG_FLAG_CHECK_FINITE) && (!ext || !io->status)) return set_error(LG_ERR_INVALID, "LG_FLAG_CHECK_FINITE needs LG_FLAG_EXT and a status array");
-    if (io->flags & LG_FLAG_INDEXED) {
-        if (!ext || !io->status) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED needs LG_FLAG_EXT and a status array");
-        if (!io->index0 || !io->index1) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED: null index0 / index1");
-        if (io->images0 < 1 || io->images1 < 1) return set_error(LG_ERR_INVALID, "LG_FLAG_INDEXED: images0 and images1 must be at least 1");
-    }
     if (ext && io->wire && io->wire_stride < LG_WIRE_WIDTH(n0, n1)) return set_error(LG_ERR_INVALID, "wire_stride < LG_WIRE_WIDTH(n0, n1) = 3 n0 + 3 n1 + 2");
     if (ext && do_prune && ((io->prune0_f32 || io->prune1_f32))) return set_error(LG_ERR_INVALID, "prune0_f32 / prune1_f32 are the outputs of a forward WITHOUT pruning");
     if (ext && !do_prune && ((io->prune0_i64 || io->prune1_i64))) return set_error(LG_ERR_INVALID, "prune0_i64 / prune1_i64 are the outputs of a forward WITH pruning");

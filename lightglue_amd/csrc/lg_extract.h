@@ -2,6 +2,7 @@
 // implemented once in lg_extract.hip: the exact-fp32 implicit-GEMM convolution, the weight repack, simple_nms, threshold + raster-order
 // compaction and the top-K selection.
 #pragma once
+#include "lg_host_call.h"     // Bump: workspace carving
 #include "lg_kernels.h"
 #include "../../include/lightglue_amd.h"
 
@@ -174,19 +175,6 @@ __device__ __forceinline__ int selected_rank(const unsigned* key, int n, int j) 
     return rank;
 }
 
-__device__ __forceinline__ int block_sum_int(int v, int* sh) {   // 256 threads
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// host: workspace carving, 256-byte aligned offsets
-struct Bump {
-    long long used = 0;
-    long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
-};
 inline unsigned blocks(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------- the io struct of an extractor stage (include/lightglue_amd.h: lg_*_io)

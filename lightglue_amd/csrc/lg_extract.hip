@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void row_count_kernel(DetectArgs a, const floa
         if (rowsum && x < wsum) sum += (double)a.S[row + x];
     }
     __shared__ int sh[4];
-    cnt = block_sum_int(cnt, sh);
+    cnt = block_sum(cnt, sh);
     if (threadIdx.x == 0) a.row_counts[b * a.H + y] = cnt;
     if (rowsum) {
         __shared__ double shd[256];
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void compact_kernel(DetectArgs a, const float*
     __shared__ int sh[4];
     int pre = 0;
     for (int yy = tid; yy < y; yy += 256) pre += a.row_counts[b * a.H + yy];
-    int running = block_sum_int(pre, sh);
+    int running = block_sum(pre, sh);
     const long long cb = (long long)b * a.max_candidates;
     for (int x0 = 0; x0 < a.W; x0 += 256) {
         const int x = x0 + tid;

@@ -1,0 +1,88 @@
+// lightglue_amd — the host side the entry points over a pair list or a caller's workspace share (lg_engine_forward, lg_nn_match, lg_twoview_verify,
+// lg_sift_filter): their refusals, the carving of a workspace, the stateless entry points' layouts, the cut of a pair list into launches.  Host-only C++17
+// like lg_forward_plan.h (no HIP header, no device type): tests/cpp/host_call_check.cpp walks it with any host compiler, and under its address sanitizer.
+#pragma once
+#include <cstdint>
+#include <string>
+
+#include "../../include/lightglue_amd.h"
+
+namespace lg {
+
+// the error every C entry point reports: sets the message lg_last_error() returns (lg_api.hip) and returns `code`
+int set_error(int code, const std::string& msg);
+
+// ---------------------------------------------------------------- refusals; every message starts with the entry point's name (`stage`)
+// THE LG_FLAG_INDEXED rule.  (The engine also asks for LG_FLAG_EXT and a status array, check_forward_io: its index fields sit behind the round-5 extension.)
+inline int check_pair_list(const char* stage, uint32_t flags, const void* index0, const void* index1, long long images0, long long images1) {
+    if ((flags & LG_FLAG_INDEXED) && (!index0 || !index1 || images0 < 1 || images1 < 1))
+        return set_error(LG_ERR_INVALID, std::string(stage) + ": LG_FLAG_INDEXED needs index0, index1 and images0, images1 >= 1");
+    return LG_OK;
+}
+// A caller's workspace of `need` bytes (what `size_function` returns): null — accepted for 0 bytes with null_if_empty, lg_nn_match over empty stores —, too small, not aligned
+inline int check_workspace(const char* stage, const char* size_function, const void* ptr, long long bytes, long long need, bool null_if_empty = false) {
+    if (!ptr && !(null_if_empty && need == 0)) return set_error(LG_ERR_INVALID, std::string(stage) + ": null workspace");
+    if (bytes < need)
+        return set_error(LG_ERR_INVALID, std::string(stage) + ": the workspace holds " + std::to_string(bytes) + " bytes, " + size_function + " = " + std::to_string(need));
+    if (reinterpret_cast<uintptr_t>(ptr) & 255) return set_error(LG_ERR_INVALID, std::string(stage) + ": the workspace must be 256-byte aligned");
+    return LG_OK;
+}
+// keypoint rows per image of a call: nullptr, or why they are refused
+inline const char* keypoint_counts_error(int n0, int n1 = 0) {
+    return n0 < 0 || n1 < 0 || n0 > LG_MAX_KEYPOINTS || n1 > LG_MAX_KEYPOINTS ? "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]" : nullptr;
+}
+
+// ---------------------------------------------------------------- workspace carving (every piece at a 256-byte aligned offset) and the three layouts
+struct Bump {
+    long long used = 0;
+    long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
+};
+// lg_nn_match: the normalised fp32 rows of either store, one "touched" byte per image of either store.  No pair count: the size depends on the stores alone.
+constexpr uint32_t NN_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_FLAG_DESC0_F16 | LG_FLAG_DESC1_F16 | LG_SIFT_STORE_FLAGS | LG_FLAG_NN_MUTUAL;
+struct NnLayout { long long rows0, rows1, ws0, ws1, touched0, touched1, total; };
+inline const char* nn_layout(long long images0, long long images1, int n0, int n1, int dim, uint32_t flags, NnLayout& L) {
+    if (dim < 16 || dim > 256 || dim % 16) return "dim must be a multiple of 16 in [16, 256]";
+    if (const char* why = keypoint_counts_error(n0, n1)) return why;
+    if (images0 < 0 || images1 < 0) return "negative image count";
+    if (flags & ~NN_KNOWN_FLAGS) return "unknown flag bits (the nearest-neighbour matcher reads LG_FLAG_INDEXED, the per-side descriptor flags and LG_FLAG_NN_MUTUAL)";
+    if (((flags & LG_FLAG_DESC0_F16) && (flags & LG_FLAG_DESC0_U8)) || ((flags & LG_FLAG_DESC1_F16) && (flags & LG_FLAG_DESC1_U8)))
+        return "a side is stored as binary16 or as uint8, not both";
+    L.rows0 = images0 * n0; L.rows1 = images1 * n1;
+    if (L.rows0 > 0x7FFFFFFFLL || L.rows1 > 0x7FFFFFFFLL) return "a store of more than 2^31 - 1 rows";
+    Bump bp;
+    L.ws0 = bp.take(L.rows0 * dim * 4); L.ws1 = bp.take(L.rows1 * dim * 4); L.touched0 = bp.take(images0); L.touched1 = bp.take(images1); L.total = bp.used;
+    return nullptr;
+}
+// lg_twoview_verify: one 32-byte record per pair, the correspondence list (16 bytes per row) and its image-0 rows (4 bytes per row) of every pair
+constexpr uint32_t TV_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_TWOVIEW_HOMOGRAPHY | LG_TWOVIEW_FUNDAMENTAL | LG_TWOVIEW_REFINE | LG_TWOVIEW_GIVEN_MODELS;
+struct TvLayout { long long head, corr, rows, total; };
+inline const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& L) {
+    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
+    if (const char* why = keypoint_counts_error(n0)) return why;
+    if (flags & ~TV_KNOWN_FLAGS) return "undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)";
+    if (!(flags & LG_TWOVIEW_HOMOGRAPHY) == !(flags & LG_TWOVIEW_FUNDAMENTAL)) return "exactly one of LG_TWOVIEW_HOMOGRAPHY and LG_TWOVIEW_FUNDAMENTAL must be set";
+    Bump bp;
+    L.head = bp.take(pairs * 32); L.corr = bp.take(pairs * n0 * 16); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
+    return nullptr;
+}
+// lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
+struct SiftFilterLayout { long long m1, m2, flags, total; };
+inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {
+    if (images < 1 || images > 65535 || n < 0 || n > (1 << 24) || max_h < 1 || max_w < 1 || (long long)max_h * max_w > 2147483647LL) return false;
+    const long long raster = (long long)images * max_h * max_w * 4;
+    if (raster > (1LL << 40)) return false;
+    Bump bp;
+    L.m1 = bp.take(raster); L.m2 = bp.take(raster); L.flags = bp.take((long long)images * n); L.total = bp.used;
+    return true;
+}
+
+// ---------------------------------------------------------------- pairs are grid.x: 2^20 x 512 threads stays below the 2^32 threads per grid axis HIP accepts,
+// and a longer list is cut into launches.  launch(first pair, count) -> LG_*
+constexpr int PAIRS_PER_LAUNCH = 1 << 20;
+template <class F> int for_pair_launches(int pairs, F launch) {
+    for (long long p0 = 0; p0 < pairs; p0 += PAIRS_PER_LAUNCH)       // (64-bit: the step past the last launch of a list near 2^31 pairs)
+        if (const int rc = launch((int)p0, pairs - p0 < PAIRS_PER_LAUNCH ? (int)(pairs - p0) : PAIRS_PER_LAUNCH)) return rc;
+    return LG_OK;
+}
+
+}  // namespace lg

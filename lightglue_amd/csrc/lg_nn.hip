@@ -6,8 +6,11 @@
 //                       through LDS in tiles of NN_TILE, and keeps (best, its index, second best) per row in registers.  Launched twice, sides swapped: both
 //                       passes multiply the same fp32 operands in the same k order, so sim[i][j] is the same fp32 number in both and nothing depends on an order;
 //   nn_outputs          mutual check, scores, the sorted match list and its length, the reference dtypes (int64 indices) — one workgroup per pair.
+// What a pair reads is lg_common.h's: PairIndex / pair_images (the swapped direction passes the pair list swapped), live_rows, and compact_slot for the match list.
+// The refusals, the workspace layout (NnLayout) and the cut of the pair list into launches are lg_host_call.h's.
 #include <string>
 
+#include "lg_host_call.h"
 #include "lg_side.h"
 #include "../../include/lightglue_amd.h"
 
@@ -17,14 +20,6 @@ constexpr int NN_WAVES = 8, NN_THREADS = NN_WAVES * 64;
 constexpr int NN_ROWS = LG_NN_ROWS_PER_WORKGROUP;      // 16 rows per wave
 constexpr int NN_TILE = LG_NN_TILE;                    // side-B rows per LDS tile: four 16-column MFMA tiles with independent accumulators
 static_assert(NN_ROWS == NN_WAVES * 16 && NN_TILE == 64, "the kernel below is written for 8 waves of 16 rows and 4 column tiles");
-
-// the images pair p reads on either side; false when an index lies outside its store (the pair is then not matched and nothing is read through it: LG_ERR_INDEX)
-struct NnPairs { const int* index0; const int* index1; int images0, images1; };
-__device__ __forceinline__ bool nn_images(const NnPairs& px, int pair, int& i0, int& i1) {
-    i0 = px.index0 ? px.index0[pair] : pair; i1 = px.index1 ? px.index1[pair] : pair;
-    return (unsigned)i0 < (unsigned)px.images0 && (unsigned)i1 < (unsigned)px.images1;
-}
-__device__ __forceinline__ int nn_count(const int* num, int image, int n) { return num ? min(max(num[image], 0), n) : n; }
 
 // ------------------------------------------------------------------ which images does the pair list read
 struct NnMarkArgs { const int* index; int pairs, images; unsigned char* touched; };
@@ -47,7 +42,7 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(NnPrepArgs a) {
     const long long k = r / a.n;
     const int i = (int)(r - k * a.n);
     if (a.touched && !a.touched[k]) return;
-    if (i >= nn_count(a.num, (int)k, a.n)) return; // rows beyond num_keypoints are never read: whatever they hold stays out of the workspace
+    if (i >= live_rows(a.num, (int)k, a.n)) return; // rows beyond num_keypoints are never read: whatever they hold stays out of the workspace
     const bool own = lane * 4 < a.dim;
     f32x4 x = own ? load_desc4(a.src, a.kind, r * a.dim + lane * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     if (a.rootsift) x = rootsift_row(x, lane, a.dim);
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(NnPrepArgs a) {
 struct NnArgs {
     const float* rowsA; const float* rowsB;      // normalised rows [imagesA][nA][dim], [imagesB][nB][dim] (nn_prep_kernel's layout)
     const int* numA; const int* numB;            // live rows per image or nullptr
-    NnPairs px;                                  // index0 / images0 belong to side A of THIS launch
+    PairIndex px;                                // index0 / images0 belong to side A of THIS launch (the second one passes the pair list swapped)
     int nA, nB, dim, pair0;
     float ratio2, dist2;                         // squared thresholds, <= 0: off
     int* raw; float* sim;                        // [pairs][nA]: nearest neighbour after the tests (-1: none / rejected) and its similarity
@@ -82,9 +77,9 @@ template <int CMAX>       // 16-value blocks of a row the A registers can hold: 
 __global__ __launch_bounds__(NN_THREADS) void nn_kernel(NnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nn_lds[];
     const int pair = a.pair0 + blockIdx.x, row0 = blockIdx.y * NN_ROWS;
-    int ia, ib;
-    if (!nn_images(a.px, pair, ia, ib)) return;                  // everything up to the tile loop is uniform per workgroup
-    const int na = nn_count(a.numA, ia, a.nA), nb = nn_count(a.numB, ib, a.nB);
+    const PairImages src = pair_images(a.px, pair);
+    if (!src.ok) return;                                         // everything up to the tile loop is uniform per workgroup
+    const int ia = src.i0, ib = src.i1, na = live_rows(a.numA, ia, a.nA), nb = live_rows(a.numB, ib, a.nB);
     if (row0 >= na) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, g = lane >> 4;
     const int nch = a.dim >> 4, slots = a.dim >> 2;              // 16-value blocks / 16-byte slots of a row
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(NnArgs a) {
 
 // ------------------------------------------------------------------ outputs: one workgroup per pair
 struct NnOutArgs {
-    NnPairs px; const int* num0; const int* num1;
+    PairIndex px; const int* num0; const int* num1;
     int n0, n1, pair0, mutual, list_rows;
     const int* raw0; const int* raw1;            // [pairs][n0], [pairs][n1] (nn_kernel)
     long long* m0; long long* m1; float* sc0; float* sc1;      // sc0 / sc1 arrive holding nn_kernel's similarities
@@ -182,10 +177,10 @@ __device__ __forceinline__ void nn_side_row(int i, int live, bool mutual, const 
     if (prune) prune[i] = 0.f;
 }
 __global__ __launch_bounds__(256) void nn_outputs_kernel(NnOutArgs a) {
-    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int i0, i1;
-    const bool ok = nn_images(a.px, pair, i0, i1);
-    int live0 = ok ? nn_count(a.num0, i0, a.n0) : 0, live1 = ok ? nn_count(a.num1, i1, a.n1) : 0;
+    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x;
+    const PairImages src = pair_images(a.px, pair);
+    const bool ok = src.ok;
+    int live0 = ok ? live_rows(a.num0, src.i0, a.n0) : 0, live1 = ok ? live_rows(a.num1, src.i1, a.n1) : 0;
     if (live0 == 0 || live1 == 0) live0 = live1 = 0;             // an empty side: nn_kernel's rows of this pair are not read
     const long long at0 = (long long)pair * a.n0, at1 = (long long)pair * a.n1;
     const int* raw0 = a.raw0 + at0; const int* raw1 = a.raw1 + at1;
@@ -203,15 +198,8 @@ __global__ __launch_bounds__(256) void nn_outputs_kernel(NnOutArgs a) {
         const int i = r0 + tid;
         int match = -1; float score = 0.f;
         if (i < a.n0) nn_side_row(i, live0, mutual, raw0, raw1, a.m0 + at0, a.sc0 + at0, a.prune0 ? a.prune0 + at0 : nullptr, match, score);
-        const unsigned long long vote = __ballot(match >= 0);
-        __syncthreads();                              // the previous round's wsum has been read
-        if (lane == 0) wsum[wave] = __popcll(vote);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 4; ++w) { before += w < wave ? wsum[w] : 0; total += wsum[w]; }
-        const int k = base + before + __popcll(vote & ((1ull << lane) - 1ull));
+        const int k = compact_slot(match >= 0, base, wsum);
         if (match >= 0 && k < a.list_rows) { mlist[2 * k] = i; mlist[2 * k + 1] = match; mscores[k] = score; }
-        base += total;
     }
     if (tid == 0) {
         a.n_matches[pair] = min(base, a.list_rows);
@@ -222,24 +210,6 @@ __global__ __launch_bounds__(256) void nn_outputs_kernel(NnOutArgs a) {
 }
 
 // ------------------------------------------------------------------ host side
-constexpr uint32_t NN_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_FLAG_DESC0_F16 | LG_FLAG_DESC1_F16 | LG_SIFT_STORE_FLAGS | LG_FLAG_NN_MUTUAL;
-constexpr int NN_PAIRS_PER_LAUNCH = 1 << 20;      // pairs are grid.x: 2^20 x 512 threads stays below the 2^32 threads per grid axis HIP accepts; longer lists are cut into launches
-
-struct NnLayout { long long rows0, rows1, ws0, ws1, touched0, touched1, total; };
-static const char* nn_layout(long long images0, long long images1, int n0, int n1, int dim, uint32_t flags, NnLayout& L) {
-    if (dim < 16 || dim > 256 || dim % 16) return "dim must be a multiple of 16 in [16, 256]";
-    if (n0 < 0 || n1 < 0 || n0 > LG_MAX_KEYPOINTS || n1 > LG_MAX_KEYPOINTS) return "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]";
-    if (images0 < 0 || images1 < 0) return "negative image count";
-    if (flags & ~NN_KNOWN_FLAGS) return "unknown flag bits (the nearest-neighbour matcher reads LG_FLAG_INDEXED, the per-side descriptor flags and LG_FLAG_NN_MUTUAL)";
-    if (((flags & LG_FLAG_DESC0_F16) && (flags & LG_FLAG_DESC0_U8)) || ((flags & LG_FLAG_DESC1_F16) && (flags & LG_FLAG_DESC1_U8)))
-        return "a side is stored as binary16 or as uint8, not both";
-    L.rows0 = images0 * n0; L.rows1 = images1 * n1;
-    if (L.rows0 > 0x7FFFFFFFLL || L.rows1 > 0x7FFFFFFFLL) return "a store of more than 2^31 - 1 rows";
-    auto up = [](long long b) { return (b + 255) / 256 * 256; };
-    L.ws0 = 0; L.ws1 = up(L.rows0 * dim * 4); L.touched0 = L.ws1 + up(L.rows1 * dim * 4); L.touched1 = L.touched0 + up(images0); L.total = L.touched1 + up(images1);
-    return nullptr;
-}
-
 template <int CMAX>
 static hipError_t nn_launch(const NnArgs& a, int pairs, hipStream_t s) {
     const dim3 grid(pairs, (a.nA + NN_ROWS - 1) / NN_ROWS);
@@ -270,8 +240,7 @@ int lg_nn_match(const lg_nn_io* io, void* hip_stream) {
     if (P == 0) return LG_OK;
     const int n0 = io->n0, n1 = io->n1, dim = io->dim;
     const bool mutual = io->flags & LG_FLAG_NN_MUTUAL;
-    if (indexed && (!io->index0 || !io->index1 || images0 < 1 || images1 < 1))
-        return set_error(LG_ERR_INVALID, "lg_nn_match: LG_FLAG_INDEXED needs index0, index1 and images0, images1 >= 1");
+    if (const int rc = check_pair_list("lg_nn_match", io->flags, io->index0, io->index1, images0, images1)) return rc;
     if ((L.rows0 && !io->desc0) || (L.rows1 && !io->desc1)) return set_error(LG_ERR_INVALID, "lg_nn_match: null descriptor pointer");
     if (!io->n_matches || !io->status || (n0 && (!io->raw0 || !io->matches0 || !io->scores0)) || (n1 && (!io->raw1 || !io->matches1 || !io->scores1)))
         return set_error(LG_ERR_INVALID, "lg_nn_match: null output pointer");
@@ -280,10 +249,7 @@ int lg_nn_match(const lg_nn_io* io, void* hip_stream) {
     if (io->list_rows && (!io->matches || !io->match_scores)) return set_error(LG_ERR_INVALID, "lg_nn_match: null match list pointer");
     if ((reinterpret_cast<uintptr_t>(io->desc0) & 15) || (reinterpret_cast<uintptr_t>(io->desc1) & 15))
         return set_error(LG_ERR_INVALID, "lg_nn_match: descriptor pointers must be 16-byte aligned");
-    if (L.total && !io->workspace) return set_error(LG_ERR_INVALID, "lg_nn_match: null workspace");
-    if (io->workspace_bytes < L.total)
-        return set_error(LG_ERR_INVALID, "lg_nn_match: the workspace holds " + std::to_string(io->workspace_bytes) + " bytes, lg_nn_workspace_bytes = " + std::to_string(L.total));
-    if (reinterpret_cast<uintptr_t>(io->workspace) & 255) return set_error(LG_ERR_INVALID, "lg_nn_match: the workspace must be 256-byte aligned");
+    if (const int rc = check_workspace("lg_nn_match", "lg_nn_workspace_bytes", io->workspace, io->workspace_bytes, L.total, true)) return rc;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(io->workspace);
@@ -310,9 +276,9 @@ int lg_nn_match(const lg_nn_io* io, void* hip_stream) {
 
     const float ratio2 = io->ratio_threshold > 0.f ? io->ratio_threshold * io->ratio_threshold : 0.f;
     const float dist2 = io->distance_threshold > 0.f ? io->distance_threshold * io->distance_threshold : 0.f;
-    const NnPairs px01{io->index0, io->index1, (int)images0, (int)images1}, px10{io->index1, io->index0, (int)images1, (int)images0};
-    for (int p0 = 0; p0 < P; p0 += NN_PAIRS_PER_LAUNCH) {
-        const int count = P - p0 < NN_PAIRS_PER_LAUNCH ? P - p0 : NN_PAIRS_PER_LAUNCH;
+    const PairIndex px01 = indexed ? PairIndex{io->index0, io->index1, (int)images0, (int)images1} : PairIndex{};
+    const PairIndex px10{px01.index1, px01.index0, px01.images1, px01.images0};
+    return for_pair_launches(P, [&](int p0, int count) -> int {
         const NnArgs dir[2] = {{rows0, rows1, io->num0, io->num1, px01, n0, n1, dim, p0, ratio2, dist2, io->raw0, io->scores0},
                                {rows1, rows0, io->num1, io->num0, px10, n1, n0, dim, p0, ratio2, dist2, io->raw1, io->scores1}};
         for (const NnArgs& a : dir) {
@@ -325,8 +291,8 @@ int lg_nn_match(const lg_nn_io* io, void* hip_stream) {
                           io->stop, reinterpret_cast<long long*>(io->stop_i64), io->prune0, io->prune1};
         hipLaunchKernelGGL(nn_outputs_kernel, dim3(count), dim3(256), 0, s, o);
         HIPCHK(hipGetLastError());
-    }
-    return LG_OK;
+        return LG_OK;
+    });
 }
 
 }  // extern "C"

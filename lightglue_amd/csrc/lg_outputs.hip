@@ -6,12 +6,10 @@
 namespace lg {
 namespace {
 
-// keypoints of image `pair` of a ragged batch: num[pair] clamped to [0, n]; num == nullptr: n
-__device__ __forceinline__ int count(const int* num, int pair, int n) { int v = num ? num[pair] : n; return v < 0 ? 0 : (v > n ? n : v); }
-// the same through the pair's source image (indexed inputs: num is per image); 0 on both sides for a pair whose index is out of range
+// keypoints of side `image` of a pair: the live rows of the image it reads (indexed inputs: num is per image); 0 on both sides for a pair whose index is out of range
 __device__ __forceinline__ int count(const int* num, const PairIndex& px, int pair, int image, int n) {
     const int src = source_image(px, pair, image);
-    return src < 0 ? 0 : count(num, src, n);
+    return src < 0 ? 0 : live_rows(num, src, n);
 }
 
 __global__ void init_state_kernel(InitStateArgs a) {

@@ -3,6 +3,7 @@
 // kept indices in ascending order.  The SIFT detector itself is out of scope.
 #include <string>
 
+#include "lg_host_call.h"
 #include "lg_side.h"
 #include "../../include/lightglue_amd.h"
 
@@ -44,8 +45,7 @@ struct SiftPoint { bool live; int h, w, y, x; float s, a; long long pix; };
 __device__ __forceinline__ SiftPoint sift_point(const SiftFilterArgs& a, int k, int i) {
     SiftPoint p{};
     p.h = min(max(a.sizes[2 * k], 0), a.max_h); p.w = min(max(a.sizes[2 * k + 1], 0), a.max_w);      // a bad size cannot address outside the rasters
-    const int cnt = a.num ? min(max(a.num[k], 0), a.n) : a.n;
-    if (i >= cnt) return p;
+    if (i >= live_rows(a.num, k, a.n)) return p;
     const long long at = (long long)k * a.n + i;
     const float fy = rintf(a.points[2 * at + 1] - 0.5f), fx = rintf(a.points[2 * at] - 0.5f);
     if (!(fy >= 0.f && fy < (float)p.h && fx >= 0.f && fx < (float)p.w)) return p;                   // (NaN fails every comparison)
@@ -97,6 +97,7 @@ __global__ __launch_bounds__(256) void sift_compact_kernel(SiftFilterArgs a) {
     for (int i0 = 0; i0 < a.n; i0 += 256) {
         const int i = i0 + threadIdx.x;
         const bool f = i < a.n && flags[i] != 0;
+        // compact_slot (lg_common.h) written out: through the helper hipcc allocates this kernel two more VGPRs (16 -> 18)
         const unsigned long long vote = __ballot(f);
         __syncthreads();                              // the previous round's wsum has been read
         if (lane == 0) wsum[wave] = __popcll(vote);
@@ -108,16 +109,6 @@ __global__ __launch_bounds__(256) void sift_compact_kernel(SiftFilterArgs a) {
     }
     for (int i = base + threadIdx.x; i < a.n; i += 256) keep[i] = -1;
     if (threadIdx.x == 0) a.counts[k] = base;
-}
-
-struct SiftFilterLayout { long long m1, m2, flags, total; };
-static bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {
-    if (images < 1 || images > 65535 || n < 0 || n > (1 << 24) || max_h < 1 || max_w < 1 || (long long)max_h * max_w > 2147483647LL) return false;
-    const long long raster = (long long)images * max_h * max_w * 4;
-    if (raster > (1LL << 40)) return false;
-    auto up = [](long long b) { return (b + 255) / 256 * 256; };
-    L.m1 = 0; L.m2 = up(raster); L.flags = 2 * up(raster); L.total = L.flags + up((long long)images * n);   // m1 | m2 contiguous: one clear
-    return true;
 }
 
 }  // namespace lg
@@ -153,10 +144,8 @@ int lg_sift_filter(const float* points, const float* scales, const float* angles
     if (!sift_filter_layout(images, n, max_h, max_w, L))
         return set_error(LG_ERR_INVALID, "lg_sift_filter: images in [1, 65535], n in [0, 2^24], max_h x max_w in [1, 2^31 - 1] pixels");
     if (nms_radius < 0 || nms_radius > 64) return set_error(LG_ERR_INVALID, "lg_sift_filter: nms_radius must lie in [0, 64]");
-    if (!sizes || !counts || !workspace || (n && (!points || !scales || !angles || !keep))) return set_error(LG_ERR_INVALID, "lg_sift_filter: null pointer");
-    if (workspace_bytes < L.total)
-        return set_error(LG_ERR_INVALID, "lg_sift_filter: the workspace holds " + std::to_string(workspace_bytes) + " bytes, lg_sift_filter_workspace_bytes = " + std::to_string(L.total));
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return set_error(LG_ERR_INVALID, "lg_sift_filter: the workspace must be 256-byte aligned");
+    if (!sizes || !counts || (n && (!points || !scales || !angles || !keep))) return set_error(LG_ERR_INVALID, "lg_sift_filter: null pointer");
+    if (const int rc = check_workspace("lg_sift_filter", "lg_sift_filter_workspace_bytes", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(workspace);
     const SiftFilterArgs a{points, scales, angles, scores, num, sizes, images, n, max_h, max_w, nms_radius,

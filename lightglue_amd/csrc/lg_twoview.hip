@@ -6,10 +6,13 @@
 //                  the pair's correspondences stream through LDS in tiles of TV_TILE (every lane reads the same address: a broadcast), the score is the integer
 //                  inlier count, and the best of the pair is one atomicMax on (count, ~hypothesis, ~root);
 //   tv_finalise    one workgroup per pair: the winner recomputed from its hypothesis number, the optional fp64 least-squares refit, mask, count, model.
+// What a pair reads is lg_common.h's (PairIndex / pair_images, live_rows), and so are the compaction round (compact_slot) and the fixed-order block sum of the fp64
+// reductions (block_sum); the refusals, the workspace layout (TvLayout) and the cut of the pair list into launches are lg_host_call.h's.
 // The solvers are compiled without floating-point contraction and the scoring is written in explicit fmaf: a model and a decision are the same bits in
 // tv_hypothesis and tv_finalise, whatever the compiler would fuse in either.
 #include <string>
 
+#include "lg_host_call.h"
 #include "lg_kernels.h"
 #include "../../include/lightglue_amd.h"
 
@@ -28,36 +31,20 @@ struct TvHeader { int count; unsigned key; float cx0, cy0, s0, cx1, cy1, s1; }; 
 static_assert(sizeof(TvHeader) == 32, "lg_twoview_workspace_bytes counts 32 bytes");
 
 struct TvArgs {
-    int pair0, n0, n1, images0, images1, kind, refine, given, hyps;
+    int pair0, n0, n1, kind, refine, given, hyps;
     unsigned seed; float t2;
-    const float* kpts0; const float* kpts1; const int* num0; const int* num1; const int* index0; const int* index1;
+    PairIndex px;                                        // the images pair p reads (lg_common.h)
+    const float* kpts0; const float* kpts1; const int* num0; const int* num1;
     const long long* matches0; const float* models_in;
     TvHeader* head; f32x4* corr; int* rows;              // workspace: [pairs], [pairs][n0], [pairs][n0]
     float* models; unsigned char* inliers0; int* num_inliers; long long* matches0_out; int* best; int* status;
 };
 
-__device__ __forceinline__ bool tv_images(const TvArgs& a, int pair, int& i0, int& i1) {
-    i0 = a.index0 ? a.index0[pair] : pair; i1 = a.index1 ? a.index1[pair] : pair;
-    return (unsigned)i0 < (unsigned)a.images0 && (unsigned)i1 < (unsigned)a.images1;
-}
-__device__ __forceinline__ int tv_live(const int* num, int image, int n) { return num ? min(max(num[image], 0), n) : n; }
-
-// block-wide sum of one double per thread in a fixed order: xor butterfly inside the wave (every lane the same total), then the four waves in ascending order
-__device__ __forceinline__ double tv_block_sum(double v, double* red4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                                     // the previous use of red4 has been read
-    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
-}
-
 // ------------------------------------------------------------------ compaction: one workgroup per pair
 __global__ __launch_bounds__(TV_THREADS) void tv_compact_kernel(TvArgs a) {
-    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int i0, i1;
-    const bool ok = tv_images(a, pair, i0, i1);
-    const int live0 = ok ? tv_live(a.num0, i0, a.n0) : 0, live1 = ok ? tv_live(a.num1, i1, a.n1) : 0;
+    const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x;
+    const PairImages src = pair_images(a.px, pair);
+    const int i0 = src.i0, i1 = src.i1, live0 = src.ok ? live_rows(a.num0, i0, a.n0) : 0, live1 = src.ok ? live_rows(a.num1, i1, a.n1) : 0;
     const long long at = (long long)pair * a.n0;
     f32x4* corr = a.corr + at; int* rows = a.rows + at;
     __shared__ int wsum[4];
@@ -68,36 +55,29 @@ __global__ __launch_bounds__(TV_THREADS) void tv_compact_kernel(TvArgs a) {
         long long m = -1;
         if (i < live0) m = a.matches0[at + i];
         const bool take = m >= 0 && m < live1;           // live1 <= n1
-        const unsigned long long vote = __ballot(take);
-        __syncthreads();
-        if (lane == 0) wsum[wave] = __popcll(vote);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 4; ++w) { before += w < wave ? wsum[w] : 0; total += wsum[w]; }
+        const int k = compact_slot(take, base, wsum);
         if (take) {
-            const int k = base + before + __popcll(vote & ((1ull << lane) - 1ull));
             const float* p0 = a.kpts0 + ((long long)i0 * a.n0 + i) * 2;
             const float* p1 = a.kpts1 + ((long long)i1 * a.n1 + m) * 2;
             corr[k] = f32x4{p0[0], p0[1], p1[0], p1[1]};
             rows[k] = i;
         }
-        base += total;
     }
     const int S = base;
     __syncthreads();                                     // the list is complete and visible to the workgroup
-    // Hartley normalisation of either side, sums in fp64 (per-thread strided partial sums, then tv_block_sum)
+    // Hartley normalisation of either side, sums in fp64 (per-thread strided partial sums, then block_sum)
     double sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
     for (int k = tid; k < S; k += TV_THREADS) { const f32x4 c = corr[k]; sx0 += c[0]; sy0 += c[1]; sx1 += c[2]; sy1 += c[3]; }
     const double inv = S ? 1.0 / S : 0.0;
-    const double cx0 = tv_block_sum(sx0, red4) * inv, cy0 = tv_block_sum(sy0, red4) * inv;
-    const double cx1 = tv_block_sum(sx1, red4) * inv, cy1 = tv_block_sum(sy1, red4) * inv;
+    const double cx0 = block_sum(sx0, red4) * inv, cy0 = block_sum(sy0, red4) * inv;
+    const double cx1 = block_sum(sx1, red4) * inv, cy1 = block_sum(sy1, red4) * inv;
     double d0 = 0, d1 = 0;
     for (int k = tid; k < S; k += TV_THREADS) {
         const f32x4 c = corr[k];
         const double ax = c[0] - cx0, ay = c[1] - cy0, bx = c[2] - cx1, by = c[3] - cy1;
         d0 += sqrt(ax * ax + ay * ay); d1 += sqrt(bx * bx + by * by);
     }
-    const double m0 = tv_block_sum(d0, red4) * inv, m1 = tv_block_sum(d1, red4) * inv;
+    const double m0 = block_sum(d0, red4) * inv, m1 = block_sum(d1, red4) * inv;
     if (tid == 0) {
         TvHeader h;
         h.count = S; h.key = 0u;
@@ -431,8 +411,7 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
     __shared__ int red8[8], flag;
     __shared__ double red4[4], JA[81], JV[81], J3[9], V3[9];
     const int pair = a.pair0 + blockIdx.x, tid = threadIdx.x;
-    int i0, i1;
-    const bool ok = tv_images(a, pair, i0, i1);
+    const bool ok = pair_images(a.px, pair).ok;
     const TvHeader h = a.head[pair];
     const int S = h.count;
     const long long at = (long long)pair * a.n0;
@@ -484,7 +463,7 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
                 for (int p = 0; p < 9; ++p)
 #pragma unroll
                     for (int q = p; q < 9; ++q) {
-                        const double s = tv_block_sum(acc[e], red4);
+                        const double s = block_sum(acc[e], red4);
                         if (tid == 0) { JA[p * 9 + q] = s; JA[q * 9 + p] = s; }
                         ++e;
                     }
@@ -546,20 +525,6 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
 }
 
 // ------------------------------------------------------------------ host side
-constexpr uint32_t TV_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_TWOVIEW_HOMOGRAPHY | LG_TWOVIEW_FUNDAMENTAL | LG_TWOVIEW_REFINE | LG_TWOVIEW_GIVEN_MODELS;
-constexpr int TV_PAIRS_PER_LAUNCH = 1 << 20;             // pairs are grid.x (as in lg_nn_match)
-
-struct TvLayout { long long head, corr, rows, total; };
-static const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& L) {
-    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
-    if (n0 < 0 || n0 > LG_MAX_KEYPOINTS) return "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]";
-    if (flags & ~TV_KNOWN_FLAGS) return "undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)";
-    if (!(flags & LG_TWOVIEW_HOMOGRAPHY) == !(flags & LG_TWOVIEW_FUNDAMENTAL)) return "exactly one of LG_TWOVIEW_HOMOGRAPHY and LG_TWOVIEW_FUNDAMENTAL must be set";
-    auto up = [](long long b) { return (b + 255) / 256 * 256; };
-    L.head = 0; L.corr = up(pairs * 32); L.rows = L.corr + up(pairs * n0 * 16); L.total = L.rows + up(pairs * n0 * 4);
-    return nullptr;
-}
-
 template <int KIND> static void tv_launch(const TvArgs& a, int count, hipStream_t s) {
     hipLaunchKernelGGL(tv_compact_kernel, dim3(count), dim3(TV_THREADS), 0, s, a);
     hipLaunchKernelGGL(tv_hypothesis_kernel<KIND>, dim3(count, a.hyps / TV_THREADS), dim3(TV_THREADS), 0, s, a);
@@ -581,41 +546,36 @@ int lg_twoview_verify(const lg_twoview_io* io, void* hip_stream) {
     if (!io) return set_error(LG_ERR_INVALID, "lg_twoview_verify: null io");
     TvLayout L;
     if (const char* why = tv_layout(io->pairs, io->n0, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_twoview_verify: ") + why);
-    if (io->n1 < 0 || io->n1 > LG_MAX_KEYPOINTS) return set_error(LG_ERR_INVALID, "lg_twoview_verify: n0, n1 must lie in [0, LG_MAX_KEYPOINTS]");
+    if (const char* why = keypoint_counts_error(0, io->n1)) return set_error(LG_ERR_INVALID, std::string("lg_twoview_verify: ") + why);
     if (io->num_hypotheses < 256 || io->num_hypotheses > 65536 || io->num_hypotheses % 256)
         return set_error(LG_ERR_INVALID, "lg_twoview_verify: num_hypotheses must be a multiple of 256 in [256, 65536]");
     if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return set_error(LG_ERR_INVALID, "lg_twoview_verify: threshold must be > 0 (and finite)");
     const bool indexed = io->flags & LG_FLAG_INDEXED, given = io->flags & LG_TWOVIEW_GIVEN_MODELS;
     const int P = io->pairs, n0 = io->n0, n1 = io->n1;
-    if (indexed && (!io->index0 || !io->index1 || io->images0 < 1 || io->images1 < 1))
-        return set_error(LG_ERR_INVALID, "lg_twoview_verify: LG_FLAG_INDEXED needs index0, index1 and images0, images1 >= 1");
+    if (const int rc = check_pair_list("lg_twoview_verify", io->flags, io->index0, io->index1, io->images0, io->images1)) return rc;
     if (!io->models || !io->num_inliers || !io->status || (n0 && (!io->inliers0 || !io->matches0)) || (n0 && n1 && (!io->kpts0 || !io->kpts1)) || (given && !io->models_in))
         return set_error(LG_ERR_INVALID, "lg_twoview_verify: null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status");
-    if (!io->workspace) return set_error(LG_ERR_INVALID, "lg_twoview_verify: null workspace");
-    if (io->workspace_bytes < L.total)
-        return set_error(LG_ERR_INVALID, "lg_twoview_verify: the workspace holds " + std::to_string(io->workspace_bytes) + " bytes, lg_twoview_workspace_bytes = " + std::to_string(L.total));
-    if (reinterpret_cast<uintptr_t>(io->workspace) & 255) return set_error(LG_ERR_INVALID, "lg_twoview_verify: the workspace must be 256-byte aligned");
+    if (const int rc = check_workspace("lg_twoview_verify", "lg_twoview_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
     if (P == 0) return LG_OK;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(io->workspace);
     TvArgs a{};
-    a.n0 = n0; a.n1 = n1; a.images0 = indexed ? io->images0 : P; a.images1 = indexed ? io->images1 : P;
+    a.n0 = n0; a.n1 = n1;
+    if (indexed) a.px = PairIndex{io->index0, io->index1, io->images0, io->images1};
     a.kind = (io->flags & LG_TWOVIEW_HOMOGRAPHY) ? TV_H : TV_F; a.refine = (io->flags & LG_TWOVIEW_REFINE) ? 1 : 0; a.given = given ? 1 : 0;
     a.hyps = io->num_hypotheses; a.seed = io->seed; a.t2 = io->threshold * io->threshold;
     a.kpts0 = io->kpts0; a.kpts1 = io->kpts1; a.num0 = io->num0; a.num1 = io->num1;
-    a.index0 = indexed ? io->index0 : nullptr; a.index1 = indexed ? io->index1 : nullptr;
     a.matches0 = reinterpret_cast<const long long*>(io->matches0); a.models_in = io->models_in;
     a.head = reinterpret_cast<TvHeader*>(ws + L.head); a.corr = reinterpret_cast<f32x4*>(ws + L.corr); a.rows = reinterpret_cast<int*>(ws + L.rows);
     a.models = io->models; a.inliers0 = io->inliers0; a.num_inliers = io->num_inliers;
     a.matches0_out = reinterpret_cast<long long*>(io->matches0_out); a.best = io->best_hypothesis; a.status = io->status;
-    for (int p0 = 0; p0 < P; p0 += TV_PAIRS_PER_LAUNCH) {
+    return for_pair_launches(P, [&](int p0, int count) -> int {
         a.pair0 = p0;
-        const int count = P - p0 < TV_PAIRS_PER_LAUNCH ? P - p0 : TV_PAIRS_PER_LAUNCH;
         if (a.kind == TV_H) tv_launch<TV_H>(a, count, s); else tv_launch<TV_F>(a, count, s);
         HIPCHK(hipGetLastError());
-    }
-    return LG_OK;
+        return LG_OK;
+    });
 }
 
 }  // extern "C"

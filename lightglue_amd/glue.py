@@ -155,6 +155,22 @@ def collate_features(feats: list) -> Dict[str, Any]:
     return out
 
 
+def _as_store(feats):
+    """a feature store as it is; a list of per-image dicts collated into one"""
+    return collate_features(feats) if isinstance(feats, (list, tuple)) else feats
+
+
+def _trimmed(res: dict, b: int, n0: int, n1: int, stop) -> dict:
+    """pair b of a batched result as an `rbd`-style dict, trimmed to the pair's own keypoint counts"""
+    return {
+        "matches0": res["matches0"][b, :n0], "matches1": res["matches1"][b, :n1],
+        "matching_scores0": res["matching_scores0"][b, :n0], "matching_scores1": res["matching_scores1"][b, :n1],
+        "matches": res["matches"][b], "scores": res["scores"][b],
+        "prune0": res["prune0"][b, :n0], "prune1": res["prune1"][b, :n1],
+        "stop": stop,
+    }
+
+
 def match_batch(matcher, feats0: list, feats1: list) -> list:
     """Match B independent image pairs with ragged keypoint counts in ONE forward; returns one `rbd`-style result
     dict per pair, trimmed to that pair's own keypoint counts (what B separate `matcher(...)` calls would give)."""
@@ -162,17 +178,8 @@ def match_batch(matcher, feats0: list, feats1: list) -> list:
     batch0, batch1 = collate_features(feats0), collate_features(feats1)
     res = matcher({"image0": batch0, "image1": batch1})
     n0, n1 = batch0["num_keypoints"].tolist(), batch1["num_keypoints"].tolist()
-    out = []
-    for b in range(len(feats0)):
-        stop = res["stop"]
-        out.append({
-            "matches0": res["matches0"][b, : n0[b]], "matches1": res["matches1"][b, : n1[b]],
-            "matching_scores0": res["matching_scores0"][b, : n0[b]], "matching_scores1": res["matching_scores1"][b, : n1[b]],
-            "matches": res["matches"][b], "scores": res["scores"][b],
-            "prune0": res["prune0"][b, : n0[b]], "prune1": res["prune1"][b, : n1[b]],
-            "stop": int(stop[b]) if torch.is_tensor(stop) else stop,
-        })
-    return out
+    stop = res["stop"]
+    return [_trimmed(res, b, n0[b], n1[b], int(stop[b]) if torch.is_tensor(stop) else stop) for b in range(len(feats0))]
 
 
 def match_pairs(matcher, feats, pairs, feats1=None) -> list:
@@ -180,8 +187,7 @@ def match_pairs(matcher, feats, pairs, feats1=None) -> list:
     a feature store (the output of an extractor on an image batch, or of `collate_features`) or a list of per-image dicts, which is collated ONCE — the
     matcher then reads every pair's rows in the store (`LightGlue.match_pairs`: nothing is stacked per pair, and the list may be longer than one engine
     call).  Returns one `rbd`-style result dict per pair, trimmed to that pair's own keypoint counts, as `match_batch` does."""
-    store0 = collate_features(feats) if isinstance(feats, (list, tuple)) else feats
-    store1 = None if feats1 is None or feats1 is feats else (collate_features(feats1) if isinstance(feats1, (list, tuple)) else feats1)
+    store0, store1 = _as_store(feats), None if feats1 is None or feats1 is feats else _as_store(feats1)
     res = matcher.match_pairs(store0, pairs, store1)
     def counts(store):
         num = store.get("num_keypoints")
@@ -190,25 +196,14 @@ def match_pairs(matcher, feats, pairs, feats1=None) -> list:
     c1 = c0 if store1 is None else counts(store1)
     stop = res["stop"]
     stops = stop.tolist() if torch.is_tensor(stop) else [stop]
-    out = []
-    for b, (i, j) in enumerate(torch.as_tensor(pairs).reshape(-1, 2).tolist()):
-        n0, n1 = c0[i], c1[j]
-        out.append({
-            "matches0": res["matches0"][b, :n0], "matches1": res["matches1"][b, :n1],
-            "matching_scores0": res["matching_scores0"][b, :n0], "matching_scores1": res["matching_scores1"][b, :n1],
-            "matches": res["matches"][b], "scores": res["scores"][b],
-            "prune0": res["prune0"][b, :n0], "prune1": res["prune1"][b, :n1],
-            "stop": int(stops[b]),
-        })
-    return out
+    return [_trimmed(res, b, c0[i], c1[j], int(stops[b])) for b, (i, j) in enumerate(torch.as_tensor(pairs).reshape(-1, 2).tolist())]
 
 
 def verify_pairs(verifier, result, feats, pairs, feats1=None) -> dict:
     """Geometric verification of what `matcher.match_pairs(feats, pairs, feats1)` returned (`result`: its dict or its `DeferredMatches`), by a
     `TwoViewVerifier`: the same stores (or lists of per-image dicts, collated once) and the same pair list; only `keypoints` and `num_keypoints` are read.
     Returns the verifier's dict: models [P, 3, 3], inliers0 [P, N0], num_inliers [P], matches0 (-1 off the inliers), matches, best_hypothesis."""
-    store0 = collate_features(feats) if isinstance(feats, (list, tuple)) else feats
-    store1 = None if feats1 is None or feats1 is feats else (collate_features(feats1) if isinstance(feats1, (list, tuple)) else feats1)
+    store0, store1 = _as_store(feats), None if feats1 is None or feats1 is feats else _as_store(feats1)
     return verifier.verify_pairs(store0, pairs, result, store1)
 
 

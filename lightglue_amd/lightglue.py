@@ -331,21 +331,12 @@ class LightGlue(nn.Module):
         do_compile = bool(self.static_lengths) and max(m, n) <= max(self.static_lengths)
         return self.conf.width_confidence > 0 and not do_compile
 
-    def _sides(self, feats0: dict, feats1: dict, names=("feats0", "feats1")):
-        """(device, side 0, side 1) of a call as the engine reads them, converted at most once per call; a non-GPU device is refused first."""
-        device = feats0["keypoints"].device
-        _call.require_gpu(device)
-        conf = self.conf
-        s0 = _call.normalise_side(feats0, device, conf.input_dim, conf.add_scale_ori, names[0])
-        s1 = s0 if feats1 is feats0 else _call.normalise_side(feats1, device, conf.input_dim, conf.add_scale_ori, names[1])
-        return device, s0, s1
+    def _read_side(self, feats: dict, device, what: str):
+        return _call.normalise_side(feats, device, self.conf.input_dim, self.conf.add_scale_ori, what)
 
     def _batch(self, data: dict, raw_mode: bool = False):
         """`forward(data)` is `match_pairs` over two stores of B images with the identity pair list, which needs no index: (device, sides, outputs of B pairs)."""
-        for key in self.required_data_keys:
-            assert key in data, f"Missing key {key} in data"
-        device, s0, s1 = self._sides(data["image0"], data["image1"], self.required_data_keys)
-        assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+        device, s0, s1 = _call.batch_sides(data, self.required_data_keys, self._read_side)
         return device, s0, s1, self._outputs(s0.K, s0, s1, device, raw_mode)
 
     def _outputs(self, pairs: int, s0, s1, device, raw_mode: bool = False):
@@ -447,15 +438,10 @@ class LightGlue(nn.Module):
         anything is launched.  validate=False uses a device tensor as given, without a host copy: the engine's own check of every index then is the
         safety net — a pair with an index outside its store is not matched and raises LG_ERR_INDEX."""
         max_rows, max_sim = self._call_limits()
-        same = feats1 is None or feats1 is feats0
-        K0 = int(feats0["keypoints"].shape[0])
-        K1 = K0 if same else int(feats1["keypoints"].shape[0])
-        pt = _call.pair_list(pairs, K0, K1, validate)
-        P = int(pt.shape[0])
-        device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
+        same, P, index = _call.store_pairs(feats0, pairs, feats1, validate)
+        device, s0, s1 = _call.sides(feats0, feats0 if same else feats1, ("feats0", "feats1"), self._read_side)
         self.last_pair_chunks = chunks = plan_pair_chunks(P, s0.N, s1.N, max_rows, max_sim)
         o = self._outputs(P, s0, s1, device)
-        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None     # [2, P]: index0 | index1, a chunk is an offset into both
         return self._launch(device, s0, s1, o, chunks, index, defer=deferred)
 
     def set_option(self, key: str, value: int, device="cuda"):

@@ -6,12 +6,21 @@ checkpoint covers (any dim that is a multiple of 16 up to 256) and the quickest 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _cabi, _call
+
+
+# one side of a call: descriptors [K, N, D] of any D, num_keypoints and descriptor_transform; nothing else is read.  Both sides: the same D
+_READ = dict(build=functools.partial(_call.build_side, keypoints=False, descriptors="any"), key="descriptors")
+
+
+def _same_dim(s0, s1):
+    assert s0.desc.shape[2] == s1.desc.shape[2], f"descriptor dims differ: {s0.desc.shape[2]} and {s1.desc.shape[2]}"
 
 
 class NearestNeighborMatcher(nn.Module):
@@ -28,32 +37,6 @@ class NearestNeighborMatcher(nn.Module):
         self.mutual = bool(mutual)
         self.ratio_threshold = None if ratio_threshold is None else float(ratio_threshold)
         self.distance_threshold = None if distance_threshold is None else float(distance_threshold)
-
-    # ------------------------------------------------------------------ one side of a call
-    @staticmethod
-    def _side(feats: dict, device, what: str) -> _call.Side:
-        """{descriptors [K, N, D], num_keypoints [K] (optional), descriptor_transform (optional)} -> the `_call.Side` of it; nothing else is read."""
-        desc = feats["descriptors"]
-        assert desc.dim() == 3, f"{what}: descriptors must have shape [K, N, D], got {tuple(desc.shape)}"
-        s = _call.Side()
-        s.K, s.N = int(desc.shape[0]), int(desc.shape[1])
-        s.desc = _call._engine_descriptors(desc, device)
-        s.rootsift = _call.descriptor_transform(feats, what) == "rootsift"
-        s.kpts = s.size = s.scales = s.oris = s.num = None
-        num = feats.get("num_keypoints")
-        if num is not None:
-            num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
-            assert num.shape == (s.K,), f"{what}: num_keypoints must have shape [{s.K}]"
-            s.num = num.clamp(0, s.N)
-        return s
-
-    def _sides(self, feats0: dict, feats1: dict, names=("feats0", "feats1")):
-        device = feats0["descriptors"].device
-        _call.require_gpu(device, "descriptors")
-        s0 = self._side(feats0, device, names[0])
-        s1 = s0 if feats1 is feats0 else self._side(feats1, device, names[1])
-        assert s0.desc.shape[2] == s1.desc.shape[2], f"descriptor dims differ: {s0.desc.shape[2]} and {s1.desc.shape[2]}"
-        return device, s0, s1
 
     # ------------------------------------------------------------------ the call path
     def _launch(self, device, s0, s1, P: int, index, defer: bool):
@@ -90,10 +73,7 @@ class NearestNeighborMatcher(nn.Module):
         """{"image0": feats, "image1": feats}, feats = {descriptors [B, N, D] (fp32, or float16 / uint8 read in place), num_keypoints [B] (optional),
         descriptor_transform None | "rootsift" (optional)}; `keypoints` may be absent.  Returns the dict of `LightGlue.forward`: matches0 [B, M] int64,
         matching_scores0 [B, M], matches1 / matching_scores1 [B, N], matches List[[S_i, 2]], scores List[[S_i]], stop (0), prune0 / prune1 (zeros)."""
-        for key in self.required_data_keys:
-            assert key in data, f"Missing key {key} in data"
-        device, s0, s1 = self._sides(data["image0"], data["image1"], self.required_data_keys)
-        assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+        device, s0, s1 = _call.batch_sides(data, self.required_data_keys, check=_same_dim, **_READ)
         return self._launch(device, s0, s1, s0.K, None, False)
 
     @torch.no_grad()
@@ -101,11 +81,6 @@ class NearestNeighborMatcher(nn.Module):
         """`LightGlue.match_pairs` for this matcher, same contract: pair p = (i, j) matches image i of the store `feats0` against image j of `feats1` (None: of
         `feats0` too), read in place through the index; outputs allocated once for all P pairs; ONE host synchronisation, none with `deferred=True`
         (a `DeferredMatches`); `validate` as there.  Bit-identical to `forward` on the stacked tensors {k: v[index]}.  No chunking: any P is one call."""
-        same = feats1 is None or feats1 is feats0
-        K0 = int(feats0["descriptors"].shape[0])
-        K1 = K0 if same else int(feats1["descriptors"].shape[0])
-        pt = _call.pair_list(pairs, K0, K1, validate)
-        P = int(pt.shape[0])
-        device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
-        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None     # [2, P]: index0 | index1
+        same, P, index = _call.store_pairs(feats0, pairs, feats1, validate, "descriptors")
+        device, s0, s1 = _call.sides(feats0, feats0 if same else feats1, ("feats0", "feats1"), check=_same_dim, **_READ)
         return self._launch(device, s0, s1, P, index, deferred)

@@ -33,31 +33,6 @@ class TwoViewVerifier(nn.Module):
             raise ValueError(f"seed must lie in [0, 2^32), got {seed!r}")
         self.model, self.threshold, self.num_hypotheses, self.refine, self.seed = model, float(threshold), int(num_hypotheses), bool(refine), int(seed)
 
-    # ------------------------------------------------------------------ one side of a call
-    @staticmethod
-    def _side(feats: dict, device, what: str) -> _call.Side:
-        """{keypoints [K, N, 2], num_keypoints [K] (optional)} -> the `_call.Side` of it; nothing else is read."""
-        kpts = feats["keypoints"]
-        assert kpts.dim() == 3 and kpts.shape[-1] == 2, f"{what}: keypoints must have shape [K, N, 2], got {tuple(kpts.shape)}"
-        s = _call.Side()
-        s.K, s.N = int(kpts.shape[0]), int(kpts.shape[1])
-        s.kpts = _call._engine_descriptors(kpts, device, keep=())
-        s.desc = s.size = s.scales = s.oris = s.num = None
-        s.rootsift = False
-        num = feats.get("num_keypoints")
-        if num is not None:
-            num = torch.as_tensor(num).detach().to(device=device, dtype=torch.int32).contiguous()
-            assert num.shape == (s.K,), f"{what}: num_keypoints must have shape [{s.K}]"
-            s.num = num.clamp(0, s.N)
-        return s
-
-    def _sides(self, feats0: dict, feats1: dict, names=("feats0", "feats1")):
-        device = feats0["keypoints"].device
-        _call.require_gpu(device, "keypoints")
-        s0 = self._side(feats0, device, names[0])
-        s1 = s0 if feats1 is feats0 else self._side(feats1, device, names[1])
-        return device, s0, s1
-
     # ------------------------------------------------------------------ the call path
     def _launch(self, device, s0, s1, P: int, index, result, models=None) -> dict:
         """P pairs in ONE lg_twoview_verify call on the current stream, then the dict behind the one host synchronisation of the call."""
@@ -112,33 +87,22 @@ class TwoViewVerifier(nn.Module):
         """{"image0": feats, "image1": feats}, feats = {keypoints [B, N, 2], num_keypoints [B] (optional)}, and the matcher's result for these B pairs (its dict,
         a `DeferredMatches` or matches0 [B, N0] itself).  Returns models [B, 3, 3], inliers0 [B, N0] bool, num_inliers [B], matches0 [B, N0] (the verified
         matches, -1 elsewhere), matches List[[S_i, 2]], best_hypothesis [B] (-1: no model)."""
-        for key in self.required_data_keys:
-            assert key in data, f"Missing key {key} in data"
-        device, s0, s1 = self._sides(data["image0"], data["image1"], self.required_data_keys)
-        assert s0.K == s1.K, f"image0 and image1 must hold the same number of images, got {s0.K} and {s1.K}"
+        device, s0, s1 = _call.batch_sides(data, self.required_data_keys, _call.build_side)        # keypoints [B, N, 2] and num_keypoints: nothing else is read
         return self._launch(device, s0, s1, s0.K, None, result)
-
-    def _pairs(self, feats0, pairs, feats1, validate):
-        same = feats1 is None or feats1 is feats0
-        K0 = int(feats0["keypoints"].shape[0])
-        K1 = K0 if same else int(feats1["keypoints"].shape[0])
-        pt = _call.pair_list(pairs, K0, K1, validate)
-        P = int(pt.shape[0])
-        device, s0, s1 = self._sides(feats0, feats0 if same else feats1)
-        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None     # [2, P]: index0 | index1
-        return device, s0, s1, P, index
 
     @torch.no_grad()
     def verify_pairs(self, feats0: dict, pairs, result, feats1: Optional[dict] = None, *, validate: bool = True) -> dict:
         """The pair list of `match_pairs` verified: pair p = (i, j) reads the keypoints of image i of the store `feats0` and image j of `feats1` (None: of
         `feats0` too) in place through the index, and row p of `result`'s matches0.  Outputs allocated once for all P pairs, ONE host synchronisation, no
         chunking.  `validate` as in `match_pairs`: without it an index outside its store gives LG_ERR_INDEX for that pair (raised after the call)."""
-        device, s0, s1, P, index = self._pairs(feats0, pairs, feats1, validate)
+        same, P, index = _call.store_pairs(feats0, pairs, feats1, validate)
+        device, s0, s1 = _call.sides(feats0, feats0 if same else feats1, ("feats0", "feats1"), _call.build_side)
         return self._launch(device, s0, s1, P, index, result)
 
     @torch.no_grad()
     def score_models(self, feats0: dict, pairs, result, models: torch.Tensor, feats1: Optional[dict] = None, *, validate: bool = True) -> dict:
         """Verification against given geometry (LG_TWOVIEW_GIVEN_MODELS): no sampling, no solving — hypothesis h of pair p is models[p, h] ([P, H, 3, 3], H a
         multiple of 256) as it stands, and the winner is the one with the most inliers, the lowest h on a tie."""
-        device, s0, s1, P, index = self._pairs(feats0, pairs, feats1, validate)
+        same, P, index = _call.store_pairs(feats0, pairs, feats1, validate)
+        device, s0, s1 = _call.sides(feats0, feats0 if same else feats1, ("feats0", "feats1"), _call.build_side)
         return self._launch(device, s0, s1, P, index, result, models=models)

@@ -6,7 +6,7 @@ from pathlib import Path
 import pytest
 import torch
 
-from lightglue_amd import LightGlue, _call
+from lightglue_amd import LightGlue, NearestNeighborMatcher, TwoViewVerifier, _call
 from lightglue_amd._call import carve_plan, normalise_side
 
 CPU = torch.device("cpu")
@@ -89,7 +89,8 @@ def past_the_device_check(monkeypatch):
     def launch(self, *a, **k):
         raise _Reached
     monkeypatch.setattr(_call, "require_gpu", lambda device, what="keypoints": None)
-    monkeypatch.setattr(LightGlue, "_launch", launch)
+    for cls in (LightGlue, NearestNeighborMatcher, TwoViewVerifier):
+        monkeypatch.setattr(cls, "_launch", launch)
 
 
 @pytest.mark.parametrize("dim,scale_ori,wrong,exc,key", MALFORMED)
@@ -104,6 +105,42 @@ def test_forward_and_match_pairs_refuse_the_same_side(past_the_device_check, dim
     feats[side] = _side(dim, scale_ori, **wrong)
     for call in (lambda: model({"image0": feats[0], "image1": feats[1]}), lambda: model.forward_raw({"image0": feats[0], "image1": feats[1]}),
                  lambda: model.forward_deferred({"image0": feats[0], "image1": feats[1]}), lambda: model.match_pairs(feats[0], [(0, 0)], feats[1], validate=False)):
+        with pytest.raises(exc, match=key):
+            call()
+
+
+OTHERS_MALFORMED = [                            # (class, what is wrong with something the class reads, the key the message names)
+    (NearestNeighborMatcher, dict(descriptors=torch.rand(K * N, 256)), "descriptors"),
+    (NearestNeighborMatcher, dict(num_keypoints=torch.tensor([1, 2])), "num_keypoints"),
+    (NearestNeighborMatcher, dict(num_keypoints=torch.tensor([[1, 2, 3]])), "num_keypoints"),
+    (NearestNeighborMatcher, dict(descriptor_transform="hellinger"), "descriptor_transform"),
+    (TwoViewVerifier, dict(keypoints=torch.rand(K, N, 3)), "keypoints"),
+    (TwoViewVerifier, dict(keypoints=torch.rand(N, 2)), "keypoints"),
+    (TwoViewVerifier, dict(num_keypoints=torch.tensor([1, 2])), "num_keypoints"),
+    (TwoViewVerifier, dict(num_keypoints=torch.tensor([[1, 2, 3]])), "num_keypoints"),
+]
+
+
+@pytest.mark.parametrize("cls,wrong,key", OTHERS_MALFORMED)
+@pytest.mark.parametrize("side", [0, 1])
+def test_nn_matcher_and_verifier_refuse_the_same_side(past_the_device_check, cls, wrong, key, side):
+    """every route of the weight-free matcher and of the verifier refuses a malformed side with the exception type LightGlue raises for it, naming the same key"""
+    with pytest.raises(Exception) as lightglue_says:
+        LightGlue(features=None)({"image0": _side(**wrong), "image1": _side()})
+    exc = type(lightglue_says.value)
+    assert exc is not _Reached and key in str(lightglue_says.value)
+    m, m0 = cls(), torch.full((K, N), -1)
+    if cls is NearestNeighborMatcher:
+        routes = lambda f: (lambda: m({"image0": f[0], "image1": f[1]}), lambda: m.match_pairs(f[0], [(0, 0)], f[1], validate=False))
+    else:
+        routes = lambda f: (lambda: m({"image0": f[0], "image1": f[1]}, m0), lambda: m.verify_pairs(f[0], [(0, 0)], m0[:1], f[1], validate=False),
+                            lambda: m.score_models(f[0], [(0, 0)], m0[:1], torch.zeros(1, 256, 3, 3), f[1], validate=False))
+    feats = [_side(), _side()]
+    for call in routes(feats):                                                          # every route takes the well-formed sides
+        with pytest.raises(_Reached):
+            call()
+    feats[side] = _side(**wrong)
+    for call in routes(feats):
         with pytest.raises(exc, match=key):
             call()
 

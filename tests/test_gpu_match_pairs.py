@@ -247,3 +247,61 @@ def test_every_route_of_the_one_call_path_returns_the_same_bits(dim, scale_ori, 
     assert want["matches0"].shape == (5, 200) and want["matches1"].shape == (5, 136)
     assert int(want["stop"][4]) == 1 and (want["matches1"][4] == -1).all()            # an empty image on side 0: stop 1, no match
     assert (want["matches0"] > -1).any() and sum(len(x) for x in want["matches"]) > 0     # not all -1: the equalities above compare something
+
+
+def test_three_consumers_read_one_pair_list_alike():
+    """The engine, the nearest-neighbour matcher and the verifier over ONE store (K = 4 images of 130 rows, dim 128: two row-workgroups of the NN kernel, and
+    70 live rows = one full LG_NN_TILE plus a remainder) and ONE device pair list with two indices outside the store: each of them reports LG_ERR_INDEX for
+    pairs 1 and 2 and for no other, leaves -1 / 0 / False in every row at or beyond num_keypoints, and gives the good pairs the bits of a call over them alone."""
+    require_gpu()
+    from lightglue_amd import NearestNeighborMatcher, TwoViewVerifier
+    K, n, num = 4, 130, [130, 70, 0, 1]
+    store = _store(23, num, n, dim=128)
+    listed = [(0, 1), (-1, 1), (1, 4), (2, 0), (3, 3), (1, 0)]
+    good_at = [0, 3, 4, 5]
+    pairs, good_pairs, P = torch.tensor(listed, device="cuda"), [listed[p] for p in good_at], len(listed)
+    want_status = [_cabi.LG_OK, _cabi.LG_ERR_INDEX, _cabi.LG_ERR_INDEX, _cabi.LG_OK, _cabi.LG_OK, _cabi.LG_OK]
+
+    def written(handle):       # what a matcher wrote for the call, read from its three output allocations (as the engine's test above does)
+        ibuf, fbuf, lbuf = handle.buffers[:3]
+        _, ioff, _, foff, _, loff = _call.carve_plan(P, n, n, False)
+        piece = lambda buf, off, k: buf[off[k]:off[k] + P * n].view(P, n)
+        return {"matches0": piece(lbuf, loff, 0), "matches1": piece(lbuf, loff, 1), "matching_scores0": piece(fbuf, foff, 0), "matching_scores1": piece(fbuf, foff, 1),
+                "status": ibuf[ioff[5] + 2 * P:ioff[5] + 3 * P].tolist()}
+
+    def check_rows(m, fill, side):       # rows at or beyond num of the image a good pair reads; every row of a bad pair
+        for p, ij in enumerate(listed):
+            live = num[ij[side]] if p in good_at else 0
+            assert (m[p, live:] == fill).all(), (p, side)
+
+    nn_m0 = None
+    for matcher in (_model(dim=128), NearestNeighborMatcher(mutual=True, ratio_threshold=0.95)):
+        good = matcher.match_pairs(store, good_pairs)
+        with pytest.raises(_cabi.LightGlueAmdError, match="LG_ERR_INDEX") as err:
+            matcher.match_pairs(store, pairs, validate=False)
+        msg = str(err.value)
+        assert "pair 1:" in msg and "pair 2:" in msg and all(f"pair {p}:" not in msg for p in good_at)
+        handle = matcher.match_pairs(store, pairs, validate=False, deferred=True)
+        with pytest.raises(_cabi.LightGlueAmdError, match="LG_ERR_INDEX"):
+            handle.result()
+        got = written(handle)
+        assert got["status"] == want_status, type(matcher).__name__
+        for key, fill, side in (("matches0", -1, 0), ("matches1", -1, 1), ("matching_scores0", 0, 0), ("matching_scores1", 0, 1)):
+            check_rows(got[key], fill, side)
+            assert torch.equal(got[key][good_at], good[key]), (type(matcher).__name__, key)
+        nn_m0, nn_good = got["matches0"], good
+    assert (nn_good["matches0"][0] > -1).sum() >= 8           # the verifier below has something to verify
+
+    verifier = TwoViewVerifier(model="homography", num_hypotheses=256)
+    good = verifier.verify_pairs(store, good_pairs, nn_good)
+    with pytest.raises(_cabi.LightGlueAmdError, match="LG_ERR_INDEX") as err:
+        verifier.verify_pairs(store, pairs, nn_m0, validate=False)
+    msg, got = str(err.value), err.value.outputs
+    named = [p for p in range(P) if f"pair {p}:" in msg]
+    assert [_cabi.LG_ERR_INDEX if p in named else _cabi.LG_OK for p in range(P)] == want_status and msg.count("LG_ERR_INDEX") == len(named)
+    check_rows(got["inliers0"], False, 0)
+    check_rows(got["matches0"], -1, 0)
+    for key in ("models", "inliers0", "num_inliers", "matches0", "best_hypothesis"):
+        assert torch.equal(got[key][good_at], good[key]), key
+    assert all(torch.equal(got["matches"][p], good["matches"][q]) for q, p in enumerate(good_at))
+    assert got["num_inliers"][[1, 2]].tolist() == [0, 0] and got["best_hypothesis"][[1, 2]].tolist() == [-1, -1] and len(got["matches"][1]) == len(got["matches"][2]) == 0
