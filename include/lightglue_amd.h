@@ -644,6 +644,85 @@ int64_t lg_twoview_workspace_bytes(int64_t pairs, int32_t n0, uint32_t flags);
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_twoview_verify(const lg_twoview_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Relative pose of calibrated pairs: 5-point essential-matrix RANSAC with a FIXED hypothesis budget, then the pose (R, t) of camera 1 against camera 0, one call
+ * for any number of pairs, reading the same things the two-view verifier reads plus one pinhole camera per image.  Stateless.  The reference has no such step;
+ * this is the definition (tests/relpose_oracle.py restates it in float64 numpy, with a solver of its own).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   correspondences, sampling, pairs, independence: exactly the two-view verifier's (above); a sample is 5 correspondences, slots 0 .. 4 of the hash.
+ *   cameras   cameras0[i] / cameras1[j] = (fx, fy, cx, cy), float32, of image i of store 0 / image j of store 1.  A pair whose fx or fy (either side) is not
+ *             finite or not > 0, or whose cx or cy is not finite, comes back empty with status LG_ERR_CAMERA (an index outside its store wins: LG_ERR_INDEX,
+ *             and no camera is read through it).
+ *   bearings  xh = (x - cx) / fx, yh = (y - cy) / fy, formed in float32 (one subtraction, one division, both correctly rounded) and widened to fp64.
+ *   model     x1h^T E x0h = 0, E = [t]x R, X1 = R X0 + t, |t| = 1.
+ *   solving   fp64 throughout.  Gauss-Jordan elimination with row pivoting of the 5 x 9 system (columns E12, E20, E21, E22 free; invalid if a pivot is not above
+ *             1e-9), the four null vectors orthonormalised by modified Gram-Schmidt in that order: E = x X + y Y + z Z + W.  The nine equations
+ *             2 E E^T E - tr(E E^T) E = 0 and det E = 0 as a 10 x 20 system in the monomials of (x, y, z), eliminated (row pivoting, invalid if a pivot is not
+ *             above 1e-12) down to a 3 x 3 matrix of polynomials in the hidden variable z acting on (x, y, 1) (Nister 2004); its determinant is a polynomial
+ *             of degree 10 whose real roots are bracketed between the roots of its derivative (recursively from the 9th derivative up, inside the Cauchy
+ *             bound of the polynomial), bisected 64 times and polished by 3 Newton steps that may not leave the bracket.  ROOT ORDER: ascending z, root index
+ *             0 .. 9.  (x, y) come from the cross product of the two rows of the 3 x 3 matrix at z whose cross product is longest.
+ *   candidate F = K1^-T E K0^-1 in fp64 (pixel units), rounded to float32, scaled to Frobenius norm 1 and put in output form exactly as the verifier's models;
+ *             a candidate with a non-finite entry or a zero norm is invalid and all zero, and so are the root slots past a sample's last root.
+ *   scoring   THE inlier test of LG_TWOVIEW_FUNDAMENTAL on that F (one piece of code for both entry points): squared Sampson distance, fp32, division-free,
+ *             threshold t in pixels.
+ *   winner    most inliers, then the lowest hypothesis, then the lowest root: one 64-bit integer maximum per pair,
+ *             count << 20 | (65535 - hypothesis) << 4 | (15 - root).  num_hypotheses is a multiple of 256 in [256, 65536].
+ *   refit     LG_RELPOSE_REFINE: once, if the winner has >= 8 inliers: linear least squares for E over them in Hartley-normalised bearings (centroid and
+ *             sqrt(2) / mean distance per side over ALL S_p bearings of the pair, fp64 sums in the fixed block order, the six numbers rounded to float32), the
+ *             9 x 9 normal matrix in fp64 summed in the fixed block order, its smallest eigenvector by cyclic Jacobi; denormalised; projected onto the essential
+ *             manifold E <- E (v1 v1^T + v2 v2^T) with v1, v2 the two largest eigenvectors of E^T E and both columns scaled to singular value 1; then
+ *             the candidate F as above.  Kept iff its inlier count is not below the winner's.
+ *   outputs   models[p]: the pixel-space F of the result (unit norm, output form); inliers0, num_inliers, matches0_out, best_hypothesis as the verifier's.
+ *             essentials[p]: K1^T F K0 computed in fp64 from the returned float32 F, scaled to Frobenius norm 1, rounded to float32, in output form.
+ *   pose      from essentials[p] as returned (float32 widened to fp64) scaled to Frobenius norm sqrt(2): t0 = the eigenvector of E E^T of smallest eigenvalue
+ *             (cyclic Jacobi), its entry of largest magnitude (the first among equals) positive, v3 = that of E^T E; R_a = -[t0]x E + s t0 v3^T,
+ *             R_b = +[t0]x E + s t0 v3^T, s = +1 or -1 so that the determinant is positive (with E = U diag(s1, s2, s3) V^T these are U W^T diag(s1, s2, 1) V^T
+ *             and U W diag(s1, s2, 1) V^T: the singular values of E do not enter the rotation), each followed by one orthonormalising step
+ *             R <- R (3 I - R^T R) / 2.  The four decompositions in the order
+ *             (R_a, +t0), (R_a, -t0), (R_b, +t0), (R_b, -t0).  An inlier with bearings b0 = (x0h, y0h, 1), b1 counts for (R, t) iff, with a = R b0, both
+ *             (a.b1)(b1.t) - (b1.b1)(a.t) > 0 and (a.a)(b1.t) - (a.b1)(a.t) > 0 (the two depths of the midpoint triangulation, up to their common positive
+ *             denominator), in fp64.  The decomposition with the highest count wins, the first in the order above on a tie: rotations[p] (row-major), translations[p]
+ *             (unit norm) and num_in_front[p] in float32 / int32.
+ *   empty     S_p < 5, no valid candidate with an inlier, LG_ERR_INDEX or LG_ERR_CAMERA: the verifier's empty form, and essentials, rotations, translations all zero,
+ *             num_in_front 0.
+ *   candidates (optional, may be NULL) [pairs][num_hypotheses][10][9]: the candidate F of every root of every hypothesis, all zero where there is none.
+ * Workspace: lg_relpose_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: the verifier's 32-byte record, a 48-byte record (key, cameras),
+ *   the correspondence list and its rows per pair, and 360 bytes per hypothesis and pair for the candidates.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): the verifier's, with the flag bits LG_FLAG_INDEXED | LG_RELPOSE_REFINE, and null cameras.
+ * Four launches: compaction (with the cameras), solve (one hypothesis per lane, 64 lanes per workgroup), score (one candidate per lane, LG_TWOVIEW_TILE
+ * correspondences per LDS tile), finalise (one workgroup per pair). */
+#define LG_ERR_CAMERA 7    /* per-pair status of the relative-pose estimator: a focal length that is not finite and > 0, or a non-finite principal point */
+#define LG_RELPOSE_REFINE 32768u
+#define LG_RELPOSE_ROOTS 10
+typedef struct lg_relpose_io {
+    int32_t pairs, n0, n1, images0, images1;   /* images0 / images1: LG_FLAG_INDEXED only, >= 1                    */
+    uint32_t flags;                        /* LG_FLAG_INDEXED | LG_RELPOSE_REFINE                                     */
+    float threshold;                       /* t > 0, in pixels                                                        */
+    int32_t num_hypotheses;                /* a multiple of 256 in [256, 65536]                                       */
+    uint32_t seed;
+    const float *kpts0, *kpts1;            /* [pairs or images][n][2], read in place                                  */
+    const int32_t *num0, *num1;            /* [pairs or images] live rows, or NULL = n                                */
+    const int32_t *index0, *index1;        /* [pairs], LG_FLAG_INDEXED                                                */
+    const int64_t *matches0;               /* [pairs][n0]: the matcher's output, read in place                        */
+    const float *cameras0, *cameras1;      /* [pairs or images0][4], [pairs or images1][4]: (fx, fy, cx, cy)          */
+    void *workspace; int64_t workspace_bytes;
+    float *rotations;                      /* [pairs][9]                                                              */
+    float *translations;                   /* [pairs][3]                                                              */
+    float *essentials;                     /* [pairs][9]                                                              */
+    float *models;                         /* [pairs][9]: the pixel-space F                                           */
+    float *candidates;                     /* [pairs][num_hypotheses][10][9], may be NULL                             */
+    uint8_t *inliers0;                     /* [pairs][n0]                                                             */
+    int32_t *num_inliers;                  /* [pairs]                                                                 */
+    int64_t *matches0_out;                 /* [pairs][n0], may be NULL                                                */
+    int32_t *best_hypothesis;              /* [pairs], may be NULL                                                    */
+    int32_t *num_in_front;                 /* [pairs]                                                                 */
+    int32_t *status;                       /* [pairs] LG_OK / LG_ERR_INDEX / LG_ERR_CAMERA                            */
+} lg_relpose_io;
+int64_t lg_relpose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypotheses, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_relpose_estimate(const lg_relpose_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

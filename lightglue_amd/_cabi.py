@@ -16,6 +16,7 @@ _LIB_PATH = Path(os.environ.get("LIGHTGLUE_AMD_LIB") or Path(__file__).resolve()
 
 LG_PREC = {"fp32": 0, "bf16": 1, "fp16": 2, "f16x3": 4}   # include/lightglue_amd.h LG_PREC_* (3 was split-bf16, removed in round 3)
 LG_OK, LG_ERR_INVALID, LG_ERR_HIP, LG_ERR_STATE, LG_ERR_RANGE, LG_ERR_DEVICE, LG_ERR_INDEX = 0, 1, 2, 3, 4, 5, 6
+LG_ERR_CAMERA = 7                                 # lg_relpose_estimate's per-pair status: a focal length that is not finite and > 0, or a non-finite principal point
 LG_FLAG_NO_PRUNING, LG_FLAG_EXT, LG_FLAG_CHECK_FINITE, LG_FLAG_INDEXED = 1, 2, 4, 8
 LG_FLAG_DESC0_F16, LG_FLAG_DESC1_F16 = 16, 32   # desc0 / desc1 are binary16 rows, read in place
 LG_FLAG_DESC0_U8, LG_FLAG_DESC1_U8 = 64, 128    # desc0 / desc1 are uint8 rows (SIFT as COLMAP / OpenCV store it), read in place
@@ -24,6 +25,7 @@ LG_DESC_KIND = {"float32": 0, "float16": 1, "uint8": 2}   # lg_rootsift src_kind
 LG_FLAG_NN_MUTUAL = 1024                          # lg_nn_match: keep a match only if both directions agree
 LG_EXTRACT_RAGGED, LG_EXTRACT_DESC_F16, LG_EXTRACT_SPLIT = 1, 2, 4   # the extractor stages' io flags: `sizes` is read / binary16 descriptors / split-f16 SuperPoint conv stack
 LG_TWOVIEW_HOMOGRAPHY, LG_TWOVIEW_FUNDAMENTAL, LG_TWOVIEW_REFINE, LG_TWOVIEW_GIVEN_MODELS = 2048, 4096, 8192, 16384   # lg_twoview_verify's io flags
+LG_RELPOSE_REFINE, LG_RELPOSE_ROOTS = 32768, 10   # lg_relpose_estimate: its refit flag, candidate models per hypothesis
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
@@ -43,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "lg_rootsift", "lg_sift_filter_workspace_bytes", "lg_sift_filter",
     "lg_nn_workspace_bytes", "lg_nn_match",
     "lg_twoview_workspace_bytes", "lg_twoview_verify",
+    "lg_relpose_workspace_bytes", "lg_relpose_estimate",
 )
 
 
@@ -110,6 +113,18 @@ class LgTwoViewIO(C.Structure):
         ("kpts0", _fp), ("kpts1", _fp), ("num0", _fp), ("num1", _fp), ("index0", _fp), ("index1", _fp), ("matches0", _fp), ("models_in", _fp),
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("models", _fp), ("inliers0", _fp), ("num_inliers", _fp), ("matches0_out", _fp), ("best_hypothesis", _fp), ("status", _fp),
+    ]
+
+
+class LgRelPoseIO(C.Structure):
+    """lg_relpose_io (include/lightglue_amd.h): one call of the relative-pose estimator"""
+    _fields_ = [
+        ("pairs", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32), ("images0", C.c_int32), ("images1", C.c_int32), ("flags", C.c_uint32),
+        ("threshold", C.c_float), ("num_hypotheses", C.c_int32), ("seed", C.c_uint32),
+        ("kpts0", _fp), ("kpts1", _fp), ("num0", _fp), ("num1", _fp), ("index0", _fp), ("index1", _fp), ("matches0", _fp), ("cameras0", _fp), ("cameras1", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("rotations", _fp), ("translations", _fp), ("essentials", _fp), ("models", _fp), ("candidates", _fp),
+        ("inliers0", _fp), ("num_inliers", _fp), ("matches0_out", _fp), ("best_hypothesis", _fp), ("num_in_front", _fp), ("status", _fp),
     ]
 
 
@@ -281,6 +296,9 @@ def load() -> C.CDLL:
     lib.lg_twoview_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
     lib.lg_twoview_workspace_bytes.restype = C.c_int64
     lib.lg_twoview_verify.argtypes = [C.POINTER(LgTwoViewIO), C.c_void_p]
+    lib.lg_relpose_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_uint32]
+    lib.lg_relpose_workspace_bytes.restype = C.c_int64
+    lib.lg_relpose_estimate.argtypes = [C.POINTER(LgRelPoseIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

@@ -25,7 +25,8 @@ def raise_on_status(status) -> None:
     if bad:
         what = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
                 _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
-                _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched"}
+                _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched",
+                _cabi.LG_ERR_CAMERA: "a camera whose focal length is not finite and > 0, or whose principal point is not finite (LG_ERR_CAMERA)"}
         raise _cabi.LightGlueAmdError("; ".join(f"pair {i}: {what.get(c, c)}" for i, c in bad[:8]))
 
 

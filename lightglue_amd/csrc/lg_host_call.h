@@ -65,6 +65,23 @@ inline const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& 
     L.head = bp.take(pairs * 32); L.corr = bp.take(pairs * n0 * 16); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
     return nullptr;
 }
+// lg_relpose_estimate: the verifier's record, list and rows per pair, a 48-byte record per pair (the 64-bit key, the two cameras) and the candidate models:
+// LG_RELPOSE_ROOTS x 9 floats per hypothesis and pair
+constexpr uint32_t RP_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_RELPOSE_REFINE;
+struct RpLayout { long long head, ext, corr, rows, cand, total; };
+inline const char* hypothesis_budget_error(long long num_hypotheses) {
+    return num_hypotheses < 256 || num_hypotheses > 65536 || num_hypotheses % 256 ? "num_hypotheses must be a multiple of 256 in [256, 65536]" : nullptr;
+}
+inline const char* rp_layout(long long pairs, int n0, long long num_hypotheses, uint32_t flags, RpLayout& L) {
+    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
+    if (const char* why = keypoint_counts_error(n0)) return why;
+    if (flags & ~RP_KNOWN_FLAGS) return "undefined flag bits (the pose estimator reads LG_FLAG_INDEXED and LG_RELPOSE_REFINE)";
+    if (const char* why = hypothesis_budget_error(num_hypotheses)) return why;
+    Bump bp;
+    L.head = bp.take(pairs * 32); L.ext = bp.take(pairs * 48); L.corr = bp.take(pairs * n0 * 16); L.rows = bp.take(pairs * n0 * 4);
+    L.cand = bp.take(pairs * num_hypotheses * LG_RELPOSE_ROOTS * 36); L.total = bp.used;
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

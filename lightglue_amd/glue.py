@@ -207,6 +207,15 @@ def verify_pairs(verifier, result, feats, pairs, feats1=None) -> dict:
     return verifier.verify_pairs(store0, pairs, result, store1)
 
 
+def estimate_poses(estimator, result, feats, pairs, cameras, feats1=None, cameras1=None) -> dict:
+    """Relative pose from what `matcher.match_pairs(feats, pairs, feats1)` returned (`result`: its dict or its `DeferredMatches`), by a
+    `RelativePoseEstimator`: the same stores (or lists of per-image dicts, collated once), the same pair list and one camera per image of either store
+    ([K, 4] (fx, fy, cx, cy) or [K, 3, 3]; cameras1 None: `cameras`).  Returns the estimator's dict: R [P, 3, 3], t [P, 3], E, models, inliers0, num_inliers,
+    num_in_front, matches0 (-1 off the inliers), matches, best_hypothesis."""
+    store0, store1 = _as_store(feats), None if feats1 is None or feats1 is feats else _as_store(feats1)
+    return estimator.estimate_pairs(store0, pairs, result, cameras, store1, cameras1)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output
