@@ -397,8 +397,9 @@ def matchability_logit(p, i: int, x):
     return (x @ w.T + b)[..., 0]
 
 
-def log_assignment(ctx: _Ctx, p, i: int, x0, x1):
-    """ref :287-296 + :265-277.  Returns scores [m+1, n+1] (dustbins included) and sim."""
+def log_assignment(ctx: _Ctx, p, i: int, x0, x1, tr=None):
+    """ref :287-296 + :265-277.  Returns scores [m+1, n+1] (dustbins included) and sim.  ``tr`` (dict) receives the projected descriptors
+    ``md0`` / ``md1``, ``sim`` and the matchability logits ``z0`` / ``z1`` (the inputs of the assignment stages, tests/assign_oracle.py)."""
     pre = f"log_assignment.{i}."
     d = x0.shape[-1]
     md0 = ctx.linear(x0, p[pre + "final_proj.weight"], p[pre + "final_proj.bias"], "final") / d**0.25
@@ -406,6 +407,8 @@ def log_assignment(ctx: _Ctx, p, i: int, x0, x1):
     sim = ctx.mm(md0, md1.T, "final")
     z0 = matchability_logit(p, i, x0)[:, None]
     z1 = matchability_logit(p, i, x1)[:, None]
+    if tr is not None:
+        tr["md0"], tr["md1"], tr["sim"], tr["z0"], tr["z1"] = md0, md1, sim, z0[:, 0], z1[:, 0]
     m, n = sim.shape
     certainties = _logsigmoid(z0) + _logsigmoid(z1).T
     scores0 = ctx.log_softmax(sim)
@@ -491,6 +494,10 @@ def forward_pair(params: Dict[str, np.ndarray], conf: SimpleNamespace,
         x0, x1 = cross_block(ctx, p, i, x0, x1, H, trace if full else None, f"l{i}_cross_")  # ref :253
         if trace is not None:
             trace[f"desc0_l{i}"], trace[f"desc1_l{i}"] = x0.copy(), x1.copy()
+        if full:   # the 256 -> 1 heads on this layer's output: matchability logit (every layer), token confidence (every layer but the last)
+            trace[f"l{i}_z0"], trace[f"l{i}_z1"] = matchability_logit(p, i, x0), matchability_logit(p, i, x1)
+            if i < L - 1:
+                trace[f"l{i}_tok0"], trace[f"l{i}_tok1"] = token_confidence(ctx, p, i, x0), token_confidence(ctx, p, i, x1)
         if i == L - 1:  # ref :544-545
             continue
         if do_early_stop:  # ref :547-550
@@ -529,7 +536,7 @@ def forward_pair(params: Dict[str, np.ndarray], conf: SimpleNamespace,
         out["prune0"], out["prune1"] = prune0, prune1
         return out
 
-    scores, _ = log_assignment(ctx, p, i, x0, x1)  # ref :591
+    scores, _ = log_assignment(ctx, p, i, x0, x1, trace)  # ref :591
     m0, m1, ms0, ms1 = filter_matches(scores, conf.filter_threshold)  # ref :592
     valid = m0 > -1  # ref :595-602
     mi0 = np.where(valid)[0]
