@@ -723,6 +723,106 @@ int64_t lg_relpose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypoth
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_relpose_estimate(const lg_relpose_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Absolute pose of a query camera against a known model: P3P RANSAC with a FIXED hypothesis budget over 2-D - 3-D matches, one call for any number of pairs,
+ * reading what a matcher leaves on the device plus one world point per database keypoint and one pinhole camera per query image.  Stateless.  The reference
+ * has no such step; this is the definition (tests/abspose_oracle.py restates it in float64 numpy, with a solver of its own).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   sides     side 0 is the query image: kpts0, num0, index0 and cameras0[i] = (fx, fy, cx, cy) of image i (the relative pose's camera rule).  Side 1 is a
+ *             database image whose keypoint ROWS carry world points: points3d1[j][m] = (X, Y, Z), float32; a row with a non-finite coordinate has no point.
+ *             The keypoints of side 1 are never read.
+ *   correspondences  row i of matches0[p] is a correspondence (kpts0[i], points3d1[m]), m = matches0[p][i], unless the verifier's rules make it unmatched
+ *             (m < 0, i >= num0, m >= n1, m >= num1) or the point has a non-finite coordinate; nothing is read through an unmatched entry beyond the point's
+ *             three floats.
+ *   problems  without LG_ABSPOSE_GROUPED problem g is pair g (groups is not read).  With it group_offsets [groups + 1] (ascending, 0 .. pairs) and group_pairs
+ *             [pairs] (a permutation of the pairs) define problem g: the pairs group_pairs[group_offsets[g] .. group_offsets[g + 1]) in that order.  The
+ *             problem's list is the concatenation of its pairs' lists, each in ascending i, numbered 0 .. S_g - 1.  Every pair reads keypoints through its own
+ *             index: grouping pairs of different queries is meaningless but memory safe (offsets are clamped into their range, an entry of group_pairs outside
+ *             [0, pairs) is passed over).  A pair with an index outside its store contributes nothing and gets status LG_ERR_INDEX; its problem goes on
+ *             without it.  The camera of a problem is that of image 0 of its first pair whose indices lie inside the stores; a problem whose camera fails the
+ *             camera rule is empty and each of its pairs (but those with LG_ERR_INDEX) gets LG_ERR_CAMERA.  The same world point reached through several
+ *             database images is kept as often as it comes.
+ *   centring  c = the centroid of the S_g points, sums in fp64 in the fixed block order, times 1 / S_g, rounded to float32; the list holds X' = X - c (one
+ *             float32 subtraction per coordinate).  Solving, scoring and refinement work on X' with t' = t + R c.
+ *   sampling  the verifier's hash and skip rule; a sample is 3 correspondences, slots 0 .. 2.  The problem's position in the call is not part of the key.
+ *   solving   fp64 throughout.  Bearings f_k = (xh, yh, 1) / |.| with xh = (x - cx) / fx, yh = (y - cy) / fy formed in float32 as in the relative pose, then
+ *             widened.  a = |P2 - P3|, b = |P1 - P3|, c = |P1 - P2| of the centred world points; cos A = f2.f3, cos B = f1.f3, cos G = f1.f2.  With depths s1,
+ *             s2 = u s1, s3 = v s1 along the bearings the law of cosines gives Grunert's quartic A4 v^4 + .. + A0 = 0; with k = (a^2 - c^2) / b^2 and
+ *             m = (a^2 + c^2) / b^2:
+ *               A4 = (k - 1)^2 - 4 (c^2 / b^2) cos^2 A
+ *               A3 = 4 [k (1 - k) cos B - (1 - m) cos A cos G + 2 (c^2 / b^2) cos^2 A cos B]
+ *               A2 = 2 [k^2 - 1 + 2 k^2 cos^2 B + 2 ((b^2 - c^2) / b^2) cos^2 A - 4 m cos A cos B cos G + 2 ((b^2 - a^2) / b^2) cos^2 G]
+ *               A1 = 4 [-k (1 + k) cos B + 2 (a^2 / b^2) cos^2 G cos B - (1 - m) cos A cos G]
+ *               A0 = (1 + k)^2 - 4 (a^2 / b^2) cos^2 G
+ *             u = [(k - 1) v^2 - 2 k cos B v + 1 + k] / (2 (cos G - v cos A)), s1^2 = c^2 / (1 + u^2 - 2 u cos G).  The real roots by the relative pose's
+ *             method at degree 4 (brackets between the roots of the derivative inside the Cauchy bound, 64 bisections, 3 Newton steps that may not leave the
+ *             bracket).  ROOT ORDER: ascending v, root index 0 .. 3 — the depth ratio of the third pick to the first, a geometric quantity.  A root is
+ *             invalid if b^2 = 0, the triangle's normal |(P2 - P1) x (P3 - P1)| <= 1e-12 b c, |A4| = 0 or a coefficient is not finite; if v <= 0,
+ *             |cos G - v cos A| <= 1e-12, u <= 0 or 1 + u^2 - 2 u cos G <= 0; or if the pose has a non-finite entry.
+ *   pose      of a root: camera points C_k = s_k f_k; the frame e1 = (P2 - P1) / |.|, e3 = e1 x (P3 - P1) normalised, e2 = e3 x e1 of the centred world
+ *             points and the same frame of the C_k; R = [e1 e2 e3]_cam [e1 e2 e3]_world^T, t' = mean(C) - R mean(P').  A candidate is (R | t'): 12 floats,
+ *             row-major 3 x 4, rounded to float32; an invalid slot is all zero.
+ *   scoring   fp32, division-free, explicit fmaf, one piece of code for every entry point: p = R X' + t', each row fmaf(r0, X', fmaf(r1, Y', fmaf(r2, Z', t')));
+ *             ex = fmaf(fx, px, (cx - x) pz), ey likewise; inlier iff pz > 0 and fmaf(ex, ex, ey ey) <= t^2 (pz pz): the squared reprojection error in
+ *             pixels against t^2.  The score of a candidate is its inlier count.
+ *   winner    the relative pose's: most inliers, then the lowest hypothesis, then the lowest root, one 64-bit integer maximum per problem.
+ *   refine    LG_ABSPOSE_REFINE: once, if the winner has >= 4 inliers: five Gauss-Newton steps in fp64 from the winner's float32 candidate on the sum of
+ *             squared pixel reprojection errors over the WINNER's inlier set (fixed through the steps).  Per inlier, p = R X' + t': residual
+ *             r = (fx px / pz + cx - x, fy py / pz + cy - y), Jacobian [[fx / pz, 0, -fx px / pz^2], [0, fy / pz, -fy py / pz^2]] [-[p]x | I] for the
+ *             camera-frame twist (w, d); an inlier with pz <= 0 at a step is passed over in that step.  J^T J (21 numbers) and J^T r (6) are summed in the
+ *             fixed block order, the 6 x 6 system (J^T J) (w, d) = -J^T r is solved by Gaussian elimination with row pivoting (abandoned, the winner stays,
+ *             if a pivot is not above 1e-12 times the largest diagonal entry); R <- Rodrigues(w) R, t' <- Rodrigues(w) t' + d.  The result, rounded to
+ *             float32, is kept iff its inlier count is not below the winner's.
+ *   outputs   rotations[g] = R and translations[g] = t' - R c formed in fp64 and rounded to float32 (X_cam = R X_world + t).  What comes back is consistent
+ *             with itself: num_inliers[g], inliers0, pair_num_inliers and matches0_out are those of the RETURNED pose, re-centred as LG_ABSPOSE_GIVEN_POSES
+ *             re-centres a pose, so scoring the returned pose again gives the same bits.  inliers0 / matches0_out / pair_num_inliers / status are per pair,
+ *             in the caller's pair order; best_hypothesis[g] is the winner's hypothesis.  The verifier's empty form (zeros, all-false masks, -1, LG_OK)
+ *             comes back for S_g < 3 (< 1 with LG_ABSPOSE_GIVEN_POSES) and for a problem without a valid candidate that has an inlier.
+ *   candidates (optional, may be NULL) [groups][num_hypotheses][4][12]: every root's candidate in the world frame (t as above), zero where there is none; not written
+ *             with LG_ABSPOSE_GIVEN_POSES.
+ *   LG_ABSPOSE_GIVEN_POSES skips sampling and solving: hypothesis h of problem g is poses_in[g][h], 12 floats (R | t) in the world frame, root index 0;
+ *             t' = t + R c in fp64, rounded to float32; invalid iff non-finite or all zero.
+ * Workspace: lg_abspose_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: a 64-byte record per pair and 28 bytes per row of matches0
+ *   (six floats and the row's place in its problem).  No candidate is stored: the finalising workgroup solves the winner's sample again.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): the verifier's, with the flag bits LG_FLAG_INDEXED | LG_ABSPOSE_REFINE | LG_ABSPOSE_GROUPED
+ *   | LG_ABSPOSE_GIVEN_POSES; null points3d1 or cameras0 (poses_in with LG_ABSPOSE_GIVEN_POSES); with LG_ABSPOSE_GROUPED null group arrays, groups outside
+ *   [1, pairs] or pairs x n0 above LG_MAX_ROWS.
+ * Three launches: compaction with centring (one workgroup per problem), solve + score fused (one hypothesis per lane: its <= 4 candidates stay in registers
+ * while the list streams through LDS LG_TWOVIEW_TILE correspondences at a time), finalise (one workgroup per problem). */
+#define LG_ABSPOSE_REFINE 65536u
+#define LG_ABSPOSE_GROUPED 131072u
+#define LG_ABSPOSE_GIVEN_POSES 262144u
+#define LG_ABSPOSE_ROOTS 4
+typedef struct lg_abspose_io {
+    int32_t pairs, n0, n1, images0, images1;   /* images0 / images1: LG_FLAG_INDEXED only, >= 1                    */
+    int32_t groups;                        /* LG_ABSPOSE_GROUPED only: problems, in [1, pairs]                        */
+    uint32_t flags;                        /* LG_FLAG_INDEXED | LG_ABSPOSE_REFINE | LG_ABSPOSE_GROUPED | LG_ABSPOSE_GIVEN_POSES */
+    float threshold;                       /* t > 0, in pixels                                                        */
+    int32_t num_hypotheses;                /* a multiple of 256 in [256, 65536]                                       */
+    uint32_t seed;
+    const float *kpts0;                    /* [pairs or images0][n0][2], read in place                                */
+    const float *points3d1;                /* [pairs or images1][n1][3]: the world point of every database keypoint row */
+    const int32_t *num0, *num1;            /* [pairs or images] live rows, or NULL = n                                */
+    const int32_t *index0, *index1;        /* [pairs], LG_FLAG_INDEXED                                                */
+    const int64_t *matches0;               /* [pairs][n0]: the matcher's output, read in place                        */
+    const float *cameras0;                 /* [pairs or images0][4]: (fx, fy, cx, cy)                                 */
+    const int32_t *group_offsets, *group_pairs;   /* [groups + 1], [pairs]: LG_ABSPOSE_GROUPED only                  */
+    const float *poses_in;                 /* [groups][num_hypotheses][12], LG_ABSPOSE_GIVEN_POSES only               */
+    void *workspace; int64_t workspace_bytes;
+    float *rotations;                      /* [groups][9]                                                             */
+    float *translations;                   /* [groups][3]                                                             */
+    int32_t *num_inliers;                  /* [groups]                                                                */
+    int32_t *best_hypothesis;              /* [groups], may be NULL                                                   */
+    float *candidates;                     /* [groups][num_hypotheses][4][12], may be NULL                            */
+    uint8_t *inliers0;                     /* [pairs][n0]                                                             */
+    int32_t *pair_num_inliers;             /* [pairs]                                                                 */
+    int64_t *matches0_out;                 /* [pairs][n0], may be NULL                                                */
+    int32_t *status;                       /* [pairs] LG_OK / LG_ERR_INDEX / LG_ERR_CAMERA                            */
+} lg_abspose_io;
+int64_t lg_abspose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypotheses, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_abspose_estimate(const lg_abspose_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ LG_FLAG_NN_MUTUAL = 1024                          # lg_nn_match: keep a match on
 LG_EXTRACT_RAGGED, LG_EXTRACT_DESC_F16, LG_EXTRACT_SPLIT = 1, 2, 4   # the extractor stages' io flags: `sizes` is read / binary16 descriptors / split-f16 SuperPoint conv stack
 LG_TWOVIEW_HOMOGRAPHY, LG_TWOVIEW_FUNDAMENTAL, LG_TWOVIEW_REFINE, LG_TWOVIEW_GIVEN_MODELS = 2048, 4096, 8192, 16384   # lg_twoview_verify's io flags
 LG_RELPOSE_REFINE, LG_RELPOSE_ROOTS = 32768, 10   # lg_relpose_estimate: its refit flag, candidate models per hypothesis
+LG_ABSPOSE_REFINE, LG_ABSPOSE_GROUPED, LG_ABSPOSE_GIVEN_POSES, LG_ABSPOSE_ROOTS = 65536, 131072, 262144, 4   # lg_abspose_estimate: its io flags, candidates per hypothesis
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
@@ -46,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "lg_nn_workspace_bytes", "lg_nn_match",
     "lg_twoview_workspace_bytes", "lg_twoview_verify",
     "lg_relpose_workspace_bytes", "lg_relpose_estimate",
+    "lg_abspose_workspace_bytes", "lg_abspose_estimate",
 )
 
 
@@ -125,6 +127,19 @@ class LgRelPoseIO(C.Structure):
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("rotations", _fp), ("translations", _fp), ("essentials", _fp), ("models", _fp), ("candidates", _fp),
         ("inliers0", _fp), ("num_inliers", _fp), ("matches0_out", _fp), ("best_hypothesis", _fp), ("num_in_front", _fp), ("status", _fp),
+    ]
+
+
+class LgAbsposeIO(C.Structure):
+    """lg_abspose_io (include/lightglue_amd.h): one call of the absolute-pose estimator"""
+    _fields_ = [
+        ("pairs", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32), ("images0", C.c_int32), ("images1", C.c_int32), ("groups", C.c_int32), ("flags", C.c_uint32),
+        ("threshold", C.c_float), ("num_hypotheses", C.c_int32), ("seed", C.c_uint32),
+        ("kpts0", _fp), ("points3d1", _fp), ("num0", _fp), ("num1", _fp), ("index0", _fp), ("index1", _fp), ("matches0", _fp), ("cameras0", _fp),
+        ("group_offsets", _fp), ("group_pairs", _fp), ("poses_in", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("rotations", _fp), ("translations", _fp), ("num_inliers", _fp), ("best_hypothesis", _fp), ("candidates", _fp),
+        ("inliers0", _fp), ("pair_num_inliers", _fp), ("matches0_out", _fp), ("status", _fp),
     ]
 
 
@@ -299,6 +314,9 @@ def load() -> C.CDLL:
     lib.lg_relpose_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_uint32]
     lib.lg_relpose_workspace_bytes.restype = C.c_int64
     lib.lg_relpose_estimate.argtypes = [C.POINTER(LgRelPoseIO), C.c_void_p]
+    lib.lg_abspose_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_uint32]
+    lib.lg_abspose_workspace_bytes.restype = C.c_int64
+    lib.lg_abspose_estimate.argtypes = [C.POINTER(LgAbsposeIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

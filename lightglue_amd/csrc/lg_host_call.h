@@ -82,6 +82,20 @@ inline const char* rp_layout(long long pairs, int n0, long long num_hypotheses, 
     L.cand = bp.take(pairs * num_hypotheses * LG_RELPOSE_ROOTS * 36); L.total = bp.used;
     return nullptr;
 }
+// lg_abspose_estimate: a 64-byte record per pair (a problem is at most every pair on its own) and, per row of matches0, the correspondence (x, y, X', Y' as one
+// float4, Z' as one float2) and the row's place in its problem
+constexpr uint32_t AP_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_ABSPOSE_REFINE | LG_ABSPOSE_GROUPED | LG_ABSPOSE_GIVEN_POSES;
+struct ApLayout { long long head, ca, cb, rows, total; };
+inline const char* ap_layout(long long pairs, int n0, long long num_hypotheses, uint32_t flags, ApLayout& L) {
+    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
+    if (const char* why = keypoint_counts_error(n0)) return why;
+    if (flags & ~AP_KNOWN_FLAGS) return "undefined flag bits (the absolute-pose estimator reads LG_FLAG_INDEXED and the LG_ABSPOSE_* bits)";
+    if (const char* why = hypothesis_budget_error(num_hypotheses)) return why;
+    if ((flags & LG_ABSPOSE_GROUPED) && pairs * n0 > LG_MAX_ROWS) return "with LG_ABSPOSE_GROUPED pairs x n0 must not exceed LG_MAX_ROWS";
+    Bump bp;
+    L.head = bp.take(pairs * 64); L.ca = bp.take(pairs * n0 * 16); L.cb = bp.take(pairs * n0 * 8); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

@@ -216,6 +216,16 @@ def estimate_poses(estimator, result, feats, pairs, cameras, feats1=None, camera
     return estimator.estimate_pairs(store0, pairs, result, cameras, store1, cameras1)
 
 
+def estimate_absolute_poses(estimator, result, feats, pairs, cameras, points3d, feats1=None, pool: bool = True) -> dict:
+    """Absolute pose of the query images from what `matcher.match_pairs(feats, pairs, feats1)` returned (`result`: its dict or its `DeferredMatches`), by an
+    `AbsolutePoseEstimator`: the same stores (or lists of per-image dicts, collated once), the same pair list (query, database), one camera per query image
+    ([K, 4] (fx, fy, cx, cy) or [K, 3, 3]) and the world point of every database keypoint row (points3d [K1, N1, 3], NaN where a row has none).  pool: all
+    pairs of one query form ONE 2-D - 3-D problem (how localisation runs PnP); without it one problem per pair.  Returns the estimator's dict: R [G, 3, 3],
+    t [G, 3], num_inliers, best_hypothesis, queries [G], group_of_pair [P], and per pair inliers0, pair_num_inliers, matches0 (-1 off the inliers), matches."""
+    store0, store1 = _as_store(feats), None if feats1 is None or feats1 is feats else _as_store(feats1)
+    return estimator.estimate_pairs(store0, pairs, result, cameras, points3d, store1, pool=pool)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output
