@@ -823,6 +823,82 @@ int64_t lg_abspose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypoth
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_abspose_estimate(const lg_abspose_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Tracks and multi-view triangulation with known poses: the connected components of the match graph of a pair list over ONE feature store, each triangulated
+ * from all its views, one call for any number of pairs, reading what a matcher leaves on the device plus one pinhole camera and one pose per image.  What
+ * comes back is points3d [images][n][3], the layout lg_abspose_estimate reads as points3d1, in the same convention X_cam = R X_world + t.  Stateless.  The
+ * reference has no such step; this is the definition (tests/triangulate_oracle.py restates it in float64 numpy, with a union-find of its own).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   nodes     node v = k n + i is row i of image k; it is live iff i < num[k] (num NULL: n; num[k] is clamped into [0, n]).
+ *   edges     row i of pair p = (a, b) = (index0[p], index1[p]) with m = matches0[p][i] is an edge (a n + i, b n + m) iff 0 <= a, b < images and a != b,
+ *             i < num[a], 0 <= m < n and m < num[b], and — unless LG_TRI_TRACKS_ONLY — both images pass the camera rule: the relative pose's rule on
+ *             cameras[k] = (fx, fy, cx, cy), and every one of the 12 entries of poses[k] = (R | t), row-major 3 x 4, finite.  A pair with an index outside the
+ *             store or with a == b contributes nothing and gets status LG_ERR_INDEX; a pair with a failing image contributes nothing and gets LG_ERR_CAMERA
+ *             (LG_ERR_INDEX wins when both apply).  Nothing is read through a rejected entry.  A pair listed twice or in both directions adds no new edge.
+ *   tracks    a track is a connected component of the edge graph with at least two nodes.  Its name is its lowest node; its observations are its nodes in
+ *             ascending node order (by image, then by row).  Tracks are a function of the edge SET alone: the order of the pair list is part of no result,
+ *             and every output is the same bits from run to run and under any permutation, duplication or reversal of the list.
+ *   node_state  0 not in a track; 1 triangulated; 2 conflict: the track holds two rows of one image; 3 too long: more than max_track_length observations;
+ *             4 degenerate: a pivot of the initial 3 x 3 system is not above 1e-12 times its largest diagonal entry, or a non-finite result; 5 an observation
+ *             with pz <= 0; 6 an observation's reprojection error above max_reproj_error; 7 no pair of observations with an angle of at least min_angle between
+ *             their rays.  The first failing test in the order 3, 2, 4, 5, 6, 7 names the state, and every node of a track carries the track's state.
+ *   geometry  fp64 throughout, no fused multiply-add.  The image's R, t and camera are the float32 inputs widened; c = -R^T t, each entry
+ *             -((R0j t0 + R1j t1) + R2j t2).  Per observation xh = (x - cx) / fx, yh = (y - cy) / fy are formed in float32 as in the relative pose, then
+ *             widened; w = R^T (xh, yh, 1) (entry j: (R0j xh + R1j yh) + R2j), ray d = w / sqrt((w0 w0 + w1 w1) + w2 w2): the norm of the rotated
+ *             vector, so that |d| = 1 also under a float32 R, which is orthonormal to 1e-7 only.
+ *             Start: [sum (I - d d^T)] X = sum (c - d (d . c)), sums in observation order, by Gaussian elimination with row pivoting: per column each lower
+ *             row in turn is exchanged with the pivot row if its entry is strictly larger in magnitude; the pivot must be above 1e-12 times the largest
+ *             diagonal entry of the matrix as summed; back substitution x2, x1, x0.
+ *   refine    LG_TRI_REFINE: five Gauss-Newton steps on the sum of squared pixel reprojection errors over all observations: p = R X + t (each row
+ *             ((r0 X0 + r1 X1) + r2 X2) + t), r = (fx px / pz + cx - x, fy py / pz + cy - y), J = [[fx / pz, 0, -fx px / pz^2], [0, fy / pz, -fy py / pz^2]] R;
+ *             an observation with pz <= 0 at a step is passed over in that step; (J^T J) s = -J^T r by the same elimination, X <- X + s.  A failed pivot or
+ *             a non-finite step abandons the refinement and the start stays.
+ *   accept    on the final X in fp64: the error of an observation is sqrt(rx rx + ry ry), compared with max_reproj_error widened; track_error is the sum of
+ *             the errors in observation order divided by their number.  The angle test is on the cosine, without acos: a pair (i, j) passes iff
+ *             (X - c_i) . (X - c_j) <= cos(min_angle) |X - c_i| |X - c_j|, cos(min_angle) = cos(min_angle pi / 180) formed once on the host in fp64; with
+ *             min_angle = 0 the test is skipped.  Outputs are rounded to float32 once.
+ *   outputs   track ids are dense in [0, T), in ascending order of the track's lowest node, over the tracks of state 1.  points3d[v] = the track's point at
+ *             every node of such a track, NaN elsewhere; track_id[v] its id, -1 elsewhere; node_state[v]; xyz, track_length, track_error [T] (capacity
+ *             images n / 2 entries); counts[0] = T, counts[1 + s] = the tracks of state s (counts[1] = 0); status [pairs].
+ *   LG_TRI_TRACKS_ONLY  no geometry: cameras, poses, max_reproj_error and min_angle are not read, every image passes, a track that is neither too long nor
+ *             conflicted has state 1 and an id, points3d, xyz and track_error may be NULL and are not written.
+ * Workspace: lg_triangulate_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: a 256-byte record, 160 bytes per image, seven int32 per node and
+ *   28 bytes per possible track (every second node); it does not depend on the number of pairs.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): null io; undefined flag bits; negative counts; n above LG_MAX_KEYPOINTS; images x n (or
+ *   images) above LG_MAX_ROWS; pairs x n >= 2^31; max_track_length outside [2, 1024]; without LG_TRI_TRACKS_ONLY max_reproj_error not > 0 and finite or
+ *   min_angle outside [0, 180); a null required pointer; a workspace that is too small or not 256-byte aligned.
+ * Eight launches, none of which waits on another workgroup: image records and parent[v] = v; union (one lane per row of matches0: a lock-free union-find that
+ *   hooks the higher root under the lower by compare-and-swap, parent[v] <= v at every instant); flatten and count; one scan over the roots; fill; sort and
+ *   triangulate (one lane per track); one scan over the tracks; scatter. */
+#define LG_TRI_REFINE 524288u
+#define LG_TRI_TRACKS_ONLY 1048576u
+#define LG_TRI_MAX_TRACK_LENGTH 1024
+typedef struct lg_triangulate_io {
+    int32_t pairs, n, images;
+    uint32_t flags;                        /* LG_TRI_REFINE | LG_TRI_TRACKS_ONLY                                      */
+    float max_reproj_error;                /* > 0, in pixels                                                          */
+    float min_angle;                       /* in [0, 180), degrees                                                    */
+    int32_t max_track_length;              /* in [2, LG_TRI_MAX_TRACK_LENGTH]                                         */
+    const float *kpts;                     /* [images][n][2], read in place                                           */
+    const int32_t *num;                    /* [images] live rows, or NULL = n                                         */
+    const int32_t *index0, *index1;        /* [pairs]: both index the one store                                       */
+    const int64_t *matches0;               /* [pairs][n]: the matcher's output, read in place                         */
+    const float *cameras;                  /* [images][4]: (fx, fy, cx, cy)                                           */
+    const float *poses;                    /* [images][12]: (R | t) row-major 3 x 4, X_cam = R X_world + t            */
+    void *workspace; int64_t workspace_bytes;
+    float *points3d;                       /* [images][n][3]                                                          */
+    int64_t *track_id;                     /* [images][n]                                                             */
+    uint8_t *node_state;                   /* [images][n]                                                             */
+    float *xyz;                            /* [images n / 2][3], the first T written                                  */
+    int32_t *track_length;                 /* [images n / 2]                                                          */
+    float *track_error;                    /* [images n / 2]                                                          */
+    int32_t *counts;                       /* [9]: T, then the tracks of state 0 .. 7                                 */
+    int32_t *status;                       /* [pairs] LG_OK / LG_ERR_INDEX / LG_ERR_CAMERA                            */
+} lg_triangulate_io;
+int64_t lg_triangulate_workspace_bytes(int64_t images, int32_t n, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_triangulate(const lg_triangulate_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

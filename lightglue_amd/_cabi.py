@@ -27,6 +27,7 @@ LG_EXTRACT_RAGGED, LG_EXTRACT_DESC_F16, LG_EXTRACT_SPLIT = 1, 2, 4   # the extra
 LG_TWOVIEW_HOMOGRAPHY, LG_TWOVIEW_FUNDAMENTAL, LG_TWOVIEW_REFINE, LG_TWOVIEW_GIVEN_MODELS = 2048, 4096, 8192, 16384   # lg_twoview_verify's io flags
 LG_RELPOSE_REFINE, LG_RELPOSE_ROOTS = 32768, 10   # lg_relpose_estimate: its refit flag, candidate models per hypothesis
 LG_ABSPOSE_REFINE, LG_ABSPOSE_GROUPED, LG_ABSPOSE_GIVEN_POSES, LG_ABSPOSE_ROOTS = 65536, 131072, 262144, 4   # lg_abspose_estimate: its io flags, candidates per hypothesis
+LG_TRI_REFINE, LG_TRI_TRACKS_ONLY, LG_TRI_MAX_TRACK_LENGTH = 524288, 1048576, 1024   # lg_triangulate: its io flags, the longest track it triangulates
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
@@ -48,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "lg_twoview_workspace_bytes", "lg_twoview_verify",
     "lg_relpose_workspace_bytes", "lg_relpose_estimate",
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
+    "lg_triangulate_workspace_bytes", "lg_triangulate",
 )
 
 
@@ -140,6 +142,17 @@ class LgAbsposeIO(C.Structure):
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("rotations", _fp), ("translations", _fp), ("num_inliers", _fp), ("best_hypothesis", _fp), ("candidates", _fp),
         ("inliers0", _fp), ("pair_num_inliers", _fp), ("matches0_out", _fp), ("status", _fp),
+    ]
+
+
+class LgTriangulateIO(C.Structure):
+    """lg_triangulate_io (include/lightglue_amd.h): one call of the triangulator"""
+    _fields_ = [
+        ("pairs", C.c_int32), ("n", C.c_int32), ("images", C.c_int32), ("flags", C.c_uint32),
+        ("max_reproj_error", C.c_float), ("min_angle", C.c_float), ("max_track_length", C.c_int32),
+        ("kpts", _fp), ("num", _fp), ("index0", _fp), ("index1", _fp), ("matches0", _fp), ("cameras", _fp), ("poses", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("points3d", _fp), ("track_id", _fp), ("node_state", _fp), ("xyz", _fp), ("track_length", _fp), ("track_error", _fp), ("counts", _fp), ("status", _fp),
     ]
 
 
@@ -317,6 +330,9 @@ def load() -> C.CDLL:
     lib.lg_abspose_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_uint32]
     lib.lg_abspose_workspace_bytes.restype = C.c_int64
     lib.lg_abspose_estimate.argtypes = [C.POINTER(LgAbsposeIO), C.c_void_p]
+    lib.lg_triangulate_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
+    lib.lg_triangulate_workspace_bytes.restype = C.c_int64
+    lib.lg_triangulate.argtypes = [C.POINTER(LgTriangulateIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

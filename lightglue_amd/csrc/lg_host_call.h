@@ -96,6 +96,22 @@ inline const char* ap_layout(long long pairs, int n0, long long num_hypotheses, 
     L.head = bp.take(pairs * 64); L.ca = bp.take(pairs * n0 * 16); L.cb = bp.take(pairs * n0 * 8); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
     return nullptr;
 }
+// lg_triangulate: a 256-byte record of the call, a 160-byte record per image, seven int32 per node (parent, root, count, list offset, component, fill cursor,
+// list entry) and, per possible track (at most every second node), its root, state, dense id and (X, Y, Z, error)
+constexpr uint32_t TRI_KNOWN_FLAGS = LG_TRI_REFINE | LG_TRI_TRACKS_ONLY;
+struct TriLayout { long long nodes, tracks, head, rec, parent, root, cnt, off, comp, cursor, list, croot, cstate, tid, cres, total; };
+inline const char* tri_layout(long long images, long long n, uint32_t flags, TriLayout& L) {
+    if (flags & ~TRI_KNOWN_FLAGS) return "undefined flag bits (the triangulator reads LG_TRI_REFINE and LG_TRI_TRACKS_ONLY)";
+    if (n < 0 || n > LG_MAX_KEYPOINTS) return "n must lie in [0, LG_MAX_KEYPOINTS]";
+    if (images < 0 || images > LG_MAX_ROWS || images * n > LG_MAX_ROWS) return "images and images x n must lie in [0, LG_MAX_ROWS]";
+    L.nodes = images * n; L.tracks = L.nodes / 2;
+    Bump bp;
+    L.head = bp.take(256); L.rec = bp.take(images * 160);
+    L.parent = bp.take(L.nodes * 4); L.root = bp.take(L.nodes * 4); L.cnt = bp.take(L.nodes * 4); L.off = bp.take(L.nodes * 4); L.comp = bp.take(L.nodes * 4);
+    L.cursor = bp.take(L.nodes * 4); L.list = bp.take(L.nodes * 4);
+    L.croot = bp.take(L.tracks * 4); L.cstate = bp.take(L.tracks * 4); L.tid = bp.take(L.tracks * 4); L.cres = bp.take(L.tracks * 16); L.total = bp.used;
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

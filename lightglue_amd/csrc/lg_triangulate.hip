@@ -1,0 +1,441 @@
+// lightglue_amd — tracks and multi-view triangulation with known poses (lg_triangulate; the definition is in include/lightglue_amd.h).  Eight launches per call:
+//   tri_init      one lane per node, pair and image: parent[v] = v, the counters cleared; the pair's status; the image's record in fp64 (R, t, c = -R^T t, camera, ok);
+//   tri_union     one lane per row of matches0: the edge's two nodes are united by a lock-free union-find (below);
+//   tri_flatten   one lane per node: root[v] = find(v) into an array of its own (parent is read-only here), the nodes of every root counted by integer atomicAdd;
+//   tri_scan      ONE workgroup: an exclusive scan over the roots with >= 2 nodes gives every component its index (ascending root = ascending lowest node) and
+//                 the offset of its list;
+//   tri_fill      one lane per node: the node takes a place in its component's list by atomicAdd on the component's cursor.  Arrival order is arbitrary;
+//   tri_tracks    one lane per component: a list no longer than max_track_length is put into ascending node order (insertion sort in place: what the atomics
+//                 left is gone), conflicts are two adjacent entries of one image, then the geometry in fp64: the lane streams the observations and the cached image
+//                 records and holds 6 + 3 accumulators and X in registers; every small matrix is indexed statically (no scratch: profiles/triangulate.md);
+//   tri_number    ONE workgroup: an exclusive scan over the components' "state 1" flags gives the dense track ids; xyz, track_length, track_error, counts;
+//   tri_scatter   one lane per node: points3d, track_id, node_state.
+// No kernel waits on another workgroup: the two scans are single workgroups, and the union loop retries only when its compare-and-swap lost to another lane's
+// progress.  Everything behind tri_fill reads sorted lists and fixed orders, so every output is the same bits whatever the atomics' interleaving was.
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "lg_host_call.h"
+#include "lg_kernels.h"
+#include "../../include/lightglue_amd.h"
+
+#pragma clang fp contract(off)
+
+namespace lg {
+
+constexpr int TRI_THREADS = 256, TRI_SCAN_THREADS = 1024, TRI_GN_STEPS = 5;
+constexpr double TRI_EPS = 1e-12;
+
+struct TriImage { double R[9], t[3], c[3], cam[4]; int ok, pad; };                  // 160 bytes per image
+static_assert(sizeof(TriImage) == 160, "lg_triangulate_workspace_bytes counts 160 bytes");
+struct TriHead { int components, entries; };
+
+struct TriArgs {
+    int pairs, n, images, nodes, max_len, refine, tracks_only, angle_test;
+    double max_err, cos_min;
+    const float* kpts; const int* num; const int* index0; const int* index1; const long long* matches0; const float* cameras; const float* poses;
+    TriHead* head; TriImage* rec; int* parent; int* root; int* cnt; int* off; int* comp; int* cursor; int* list;      // workspace, per node
+    int* croot; int* cstate; int* tid; float* cres;                                                                   // workspace, per component
+    float* points3d; long long* track_id; unsigned char* node_state; float* xyz; int* track_length; float* track_error; int* counts; int* status;
+};
+
+// the camera rule of one image: the relative pose's rule, and a finite pose
+__device__ __forceinline__ bool tri_image_ok(const TriArgs& a, int k) {
+    const float* c = a.cameras + (long long)k * 4;
+    bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f;
+    const float* p = a.poses + (long long)k * 12;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) ok = ok && isfinite(p[e]);
+    return ok;
+}
+
+// ------------------------------------------------------------------ 1. records, statuses, parent[v] = v
+__global__ __launch_bounds__(TRI_THREADS) void tri_init_kernel(TriArgs a) {
+    const long long g = (long long)blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (g == 0) *a.head = TriHead{0, 0};
+    if (g < a.nodes) { a.parent[g] = (int)g; a.cnt[g] = 0; a.cursor[g] = 0; }
+    if (g < a.images) {
+        const int k = (int)g;
+        TriImage im{};
+        im.ok = 1;
+        if (!a.tracks_only) {
+            im.ok = tri_image_ok(a, k) ? 1 : 0;
+            const float* p = a.poses + (long long)k * 12;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) im.R[3 * r + j] = (double)p[4 * r + j];
+                im.t[r] = (double)p[4 * r + 3];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) im.c[j] = -((im.R[j] * im.t[0] + im.R[3 + j] * im.t[1]) + im.R[6 + j] * im.t[2]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) im.cam[e] = (double)a.cameras[(long long)k * 4 + e];
+        }
+        a.rec[k] = im;
+    }
+    if (g < a.pairs) {
+        const int i0 = a.index0[g], i1 = a.index1[g];
+        int st = LG_OK;
+        if ((unsigned)i0 >= (unsigned)a.images || (unsigned)i1 >= (unsigned)a.images || i0 == i1) st = LG_ERR_INDEX;
+        else if (!a.tracks_only && !(tri_image_ok(a, i0) && tri_image_ok(a, i1))) st = LG_ERR_CAMERA;
+        a.status[g] = st;
+    }
+}
+
+// ------------------------------------------------------------------ 2. union
+__device__ __forceinline__ int tri_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// THE INVARIANT: parent[v] <= v at every instant (tri_init writes v; the only later writes are the compare-and-swap below, which puts lo < hi at hi, and the
+// atomicMin here, which only lowers).  So a find is a strictly descending walk over non-negative integers: it ends after at most x steps whatever other lanes
+// do meanwhile, and `p >= x` ends it even over memory that does not hold the invariant.  A node that has a parent below it never becomes a root again.
+template <bool HALVE> __device__ __forceinline__ int tri_find(int* parent, int x) {
+    for (;;) {
+        const int p = tri_load(parent + x);
+        if (p >= x || p < 0) return x;
+        if (HALVE) {                                       // path halving: the grandparent is an ancestor of x below p
+            const int gp = tri_load(parent + p);
+            if (gp >= 0 && gp < p) atomicMin(parent + x, gp);
+        }
+        x = p;
+    }
+}
+
+__global__ __launch_bounds__(TRI_THREADS) void tri_union_kernel(TriArgs a) {
+    const long long e = (long long)blockIdx.x * TRI_THREADS + threadIdx.x;
+    const int n = a.n;
+    if (e >= (long long)a.pairs * n) return;
+    const int pair = (int)(e / n), i = (int)(e % n);
+    const int i0 = a.index0[pair], i1 = a.index1[pair];
+    if ((unsigned)i0 >= (unsigned)a.images || (unsigned)i1 >= (unsigned)a.images || i0 == i1) return;
+    if (!(a.rec[i0].ok && a.rec[i1].ok)) return;
+    if (i >= live_rows(a.num, i0, n)) return;              // rows at or beyond num are unmatched and never read
+    const long long m = a.matches0[e];
+    if (m < 0 || m >= live_rows(a.num, i1, n)) return;     // live rows <= n
+    int u = i0 * n + i, v = i1 * n + (int)m;               // both < images n = nodes
+    // Lock-free: the higher root is hooked under the lower.  The loop comes round again only when the compare-and-swap found parent[hi] != hi, that is when
+    // ANOTHER lane's hook of hi succeeded in between; every success takes one root away for good and there are at most `nodes` roots, so the retries of all
+    // lanes together are bounded by the successes of all lanes together: no lane waits for another, none holds anything another needs.  A lane that lost goes
+    // on from what the compare-and-swap returned, hi's parent below hi, so max(u, v) falls in every round: at most hi rounds even if every load were stale.
+    for (;;) {
+        u = tri_find<true>(a.parent, u); v = tri_find<true>(a.parent, v);
+        if (u == v) break;
+        const int hi = max(u, v), lo = min(u, v);
+        const int old = atomicCAS(a.parent + hi, hi, lo);
+        if (old == hi) break;
+        if (old < 0 || old > hi) break;                    // not memory this call wrote: nothing to unite
+        u = old; v = lo;
+    }
+}
+
+// ------------------------------------------------------------------ 3. flatten and count
+__global__ __launch_bounds__(TRI_THREADS) void tri_flatten_kernel(TriArgs a) {
+    const int v = blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (v >= a.nodes) return;
+    const int r = tri_find<false>(a.parent, v);            // r <= v < nodes
+    a.root[v] = r;
+    atomicAdd(a.cnt + r, 1);
+}
+
+// ------------------------------------------------------------------ 4. / 7. the two scans: ONE workgroup, a contiguous share per thread, two passes
+// exclusive scan of (x, y) per thread over the workgroup; the totals come back in tx, ty.  Inside a wave by shuffles, across the 16 waves through
+// sh: __shared__ int[2 * TRI_SCAN_WAVES].  Integers: the order of the additions changes nothing.  Every thread calls
+constexpr int TRI_SCAN_WAVES = TRI_SCAN_THREADS / 64;
+__device__ __forceinline__ void tri_block_scan(int& x, int& y, int& tx, int& ty, int* sh) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int ix = x, iy = y;                                    // inclusive inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int ux = __shfl_up(ix, o, 64), uy = __shfl_up(iy, o, 64);
+        if (lane >= o) { ix += ux; iy += uy; }
+    }
+    __syncthreads();
+    if (lane == 63) { sh[2 * wave] = ix; sh[2 * wave + 1] = iy; }
+    __syncthreads();
+    int bx = 0, by = 0;
+    tx = 0; ty = 0;
+    for (int w = 0; w < TRI_SCAN_WAVES; ++w) {
+        const int vx = sh[2 * w], vy = sh[2 * w + 1];
+        if (w < wave) { bx += vx; by += vy; }
+        tx += vx; ty += vy;
+    }
+    x = bx + ix - x; y = by + iy - y;
+}
+
+__global__ __launch_bounds__(TRI_SCAN_THREADS) void tri_scan_kernel(TriArgs a) {
+    __shared__ int sh[2 * TRI_SCAN_WAVES];
+    const int share = (a.nodes + TRI_SCAN_THREADS - 1) / TRI_SCAN_THREADS;
+    const int beg = min((int)threadIdx.x * share, a.nodes), end = min(beg + share, a.nodes);
+    int comps = 0, entries = 0, tc, te;
+    for (int v = beg; v < end; ++v) if (a.root[v] == v && a.cnt[v] >= 2) { ++comps; entries += a.cnt[v]; }
+    tri_block_scan(comps, entries, tc, te, sh);
+    for (int v = beg; v < end; ++v)
+        if (a.root[v] == v && a.cnt[v] >= 2) {             // comps < nodes / 2 + 1 and entries + cnt[v] <= nodes: every node is counted once
+            a.comp[v] = comps; a.off[v] = entries; a.croot[comps] = v;
+            ++comps; entries += a.cnt[v];
+        }
+    if (threadIdx.x == 0) *a.head = TriHead{tc, te};
+}
+
+// ------------------------------------------------------------------ 5. fill
+__global__ __launch_bounds__(TRI_THREADS) void tri_fill_kernel(TriArgs a) {
+    const int v = blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (v >= a.nodes) return;
+    const int r = a.root[v], len = a.cnt[r];
+    if (len < 2) return;
+    const int at = atomicAdd(a.cursor + r, 1);
+    if (at < len) a.list[a.off[r] + at] = v;               // always: cnt[r] nodes have this root
+}
+
+// ------------------------------------------------------------------ 6. one lane per component
+// M x = b for a symmetric 3 x 3 M given by its upper triangle; false on a pivot that is not above TRI_EPS times M's largest diagonal entry.  Static indices only
+__device__ __forceinline__ bool tri_solve3(const double (&s)[6], const double (&b)[3], double (&x)[3]) {
+    double M[3][4] = {{s[0], s[1], s[2], b[0]}, {s[1], s[3], s[4], b[1]}, {s[2], s[4], s[5], b[2]}};
+    const double bar = TRI_EPS * fmax(fmax(s[0], s[3]), s[5]);
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 3; ++r) {
+            const bool swap = fabs(M[r][c]) > fabs(M[c][c]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const double lo = M[c][j], hi = M[r][j]; M[c][j] = swap ? hi : lo; M[r][j] = swap ? lo : hi; }
+        }
+        ok = ok && fabs(M[c][c]) > bar;
+#pragma unroll
+        for (int r = c + 1; r < 3; ++r) {
+            const double f = M[r][c] / M[c][c];
+#pragma unroll
+            for (int j = c + 1; j < 4; ++j) M[r][j] = M[r][j] - f * M[c][j];
+        }
+    }
+    x[2] = M[2][3] / M[2][2];
+    x[1] = (M[1][3] - M[1][2] * x[2]) / M[1][1];
+    x[0] = ((M[0][3] - M[0][1] * x[1]) - M[0][2] * x[2]) / M[0][0];
+    return ok && isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
+}
+
+struct TriProj { double px, py, pz; };
+__device__ __forceinline__ TriProj tri_project(const TriImage& im, const double (&X)[3]) {
+    return {((im.R[0] * X[0] + im.R[1] * X[1]) + im.R[2] * X[2]) + im.t[0], ((im.R[3] * X[0] + im.R[4] * X[1]) + im.R[5] * X[2]) + im.t[1],
+            ((im.R[6] * X[0] + im.R[7] * X[1]) + im.R[8] * X[2]) + im.t[2]};
+}
+
+// the state of one track (4 .. 7, or 1) and its point and mean error; lst: its observations in ascending node order
+__device__ __forceinline__ int tri_geometry(const TriArgs& a, const int* lst, int len, double (&X)[3], double& mean_err) {
+    const int n = a.n;
+    double S[6] = {0, 0, 0, 0, 0, 0}, B[3] = {0, 0, 0};
+    for (int j = 0; j < len; ++j) {
+        const int v = lst[j];
+        const TriImage& im = a.rec[v / n];
+        const float* kp = a.kpts + (long long)v * 2;
+        const double xh = (double)((kp[0] - (float)im.cam[2]) / (float)im.cam[0]), yh = (double)((kp[1] - (float)im.cam[3]) / (float)im.cam[1]);
+        double d[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) d[e] = (im.R[e] * xh + im.R[3 + e] * yh) + im.R[6 + e];
+        const double nrm = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);      // of the rotated vector: a float32 R is orthonormal to 1e-7 only
+#pragma unroll
+        for (int e = 0; e < 3; ++e) d[e] = d[e] / nrm;
+        const double dc = (d[0] * im.c[0] + d[1] * im.c[1]) + d[2] * im.c[2];
+        S[0] += 1.0 - d[0] * d[0]; S[1] += -(d[0] * d[1]); S[2] += -(d[0] * d[2]);
+        S[3] += 1.0 - d[1] * d[1]; S[4] += -(d[1] * d[2]); S[5] += 1.0 - d[2] * d[2];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) B[e] += im.c[e] - d[e] * dc;
+    }
+    if (!tri_solve3(S, B, X)) return 4;
+    if (a.refine) {
+        double Y[3] = {X[0], X[1], X[2]};
+        bool kept = true;
+        for (int step = 0; step < TRI_GN_STEPS && kept; ++step) {
+            double H[6] = {0, 0, 0, 0, 0, 0}, G[3] = {0, 0, 0};
+            for (int j = 0; j < len; ++j) {
+                const int v = lst[j];
+                const TriImage& im = a.rec[v / n];
+                const TriProj p = tri_project(im, Y);
+                if (!(p.pz > 0.0)) continue;
+                const float* kp = a.kpts + (long long)v * 2;
+                const double iz = 1.0 / p.pz, fx = im.cam[0], fy = im.cam[1];
+                const double rx = ((fx * p.px) * iz + im.cam[2]) - (double)kp[0], ry = ((fy * p.py) * iz + im.cam[3]) - (double)kp[1];
+                const double ax = fx * iz, az = -(((fx * p.px) * iz) * iz), by = fy * iz, bz = -(((fy * p.py) * iz) * iz);
+                double J0[3], J1[3];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) { J0[e] = ax * im.R[e] + az * im.R[6 + e]; J1[e] = by * im.R[3 + e] + bz * im.R[6 + e]; }
+                H[0] += J0[0] * J0[0] + J1[0] * J1[0]; H[1] += J0[0] * J0[1] + J1[0] * J1[1]; H[2] += J0[0] * J0[2] + J1[0] * J1[2];
+                H[3] += J0[1] * J0[1] + J1[1] * J1[1]; H[4] += J0[1] * J0[2] + J1[1] * J1[2]; H[5] += J0[2] * J0[2] + J1[2] * J1[2];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) G[e] += J0[e] * rx + J1[e] * ry;
+            }
+            const double ng[3] = {-G[0], -G[1], -G[2]};
+            double s[3];
+            kept = tri_solve3(H, ng, s);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) Y[e] = Y[e] + s[e];
+            kept = kept && isfinite(Y[0]) && isfinite(Y[1]) && isfinite(Y[2]);
+        }
+        if (kept) { X[0] = Y[0]; X[1] = Y[1]; X[2] = Y[2]; }
+    }
+    bool behind = false, far = false;
+    double sum = 0.0;
+    for (int j = 0; j < len; ++j) {
+        const int v = lst[j];
+        const TriImage& im = a.rec[v / n];
+        const TriProj p = tri_project(im, X);
+        if (!(p.pz > 0.0)) { behind = true; continue; }
+        const float* kp = a.kpts + (long long)v * 2;
+        const double iz = 1.0 / p.pz;
+        const double rx = ((im.cam[0] * p.px) * iz + im.cam[2]) - (double)kp[0], ry = ((im.cam[1] * p.py) * iz + im.cam[3]) - (double)kp[1];
+        const double err = sqrt(rx * rx + ry * ry);
+        far = far || !(err <= a.max_err);
+        sum += err;
+    }
+    if (behind) return 5;
+    if (far) return 6;
+    mean_err = sum / (double)len;
+    if (a.angle_test) {
+        bool wide = false;
+        for (int i = 0; i + 1 < len && !wide; ++i) {
+            const TriImage& ii = a.rec[lst[i] / n];
+            const double u[3] = {X[0] - ii.c[0], X[1] - ii.c[1], X[2] - ii.c[2]};
+            const double nu = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+            for (int j = i + 1; j < len && !wide; ++j) {
+                const TriImage& ij = a.rec[lst[j] / n];
+                const double w[3] = {X[0] - ij.c[0], X[1] - ij.c[1], X[2] - ij.c[2]};
+                const double nw = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+                wide = (u[0] * w[0] + u[1] * w[1]) + u[2] * w[2] <= (a.cos_min * nu) * nw;
+            }
+        }
+        if (!wide) return 7;
+    }
+    return 1;
+}
+
+__global__ __launch_bounds__(TRI_THREADS) void tri_tracks_kernel(TriArgs a) {
+    const int c = blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (c >= a.head->components) return;                   // components <= nodes / 2: the size of the per-component arrays
+    const int r = a.croot[c], len = a.cnt[r];
+    int* lst = a.list + a.off[r];                          // [off, off + len) lies inside list: the scan summed these very counts
+    int state = 1;
+    double X[3] = {0, 0, 0}, err = 0.0;
+    if (len > a.max_len) state = 3;
+    else {
+        for (int j = 1; j < len; ++j) {                    // ascending node order, whatever order the atomics left
+            const int key = lst[j];
+            int q = j - 1;
+            while (q >= 0 && lst[q] > key) { lst[q + 1] = lst[q]; --q; }
+            lst[q + 1] = key;
+        }
+        for (int j = 1; j < len; ++j) if (lst[j] / a.n == lst[j - 1] / a.n) state = 2;
+        if (state == 1 && !a.tracks_only) state = tri_geometry(a, lst, len, X, err);
+    }
+    a.cstate[c] = state;
+    float* res = a.cres + (long long)c * 4;
+    res[0] = (float)X[0]; res[1] = (float)X[1]; res[2] = (float)X[2]; res[3] = (float)err;
+}
+
+// ------------------------------------------------------------------ 7. dense ids of the tracks of state 1, the per-track outputs, the counts
+__global__ __launch_bounds__(TRI_SCAN_THREADS) void tri_number_kernel(TriArgs a) {
+    __shared__ int sh[2 * TRI_SCAN_WAVES];
+    __shared__ int per_state[8];
+    const int C = a.head->components;
+    if (threadIdx.x < 8) per_state[threadIdx.x] = 0;
+    const int share = (C + TRI_SCAN_THREADS - 1) / TRI_SCAN_THREADS;
+    const int beg = min((int)threadIdx.x * share, C), end = min(beg + share, C);
+    int good = 0, unused = 0, total, t2;
+    for (int c = beg; c < end; ++c) good += a.cstate[c] == 1;
+    tri_block_scan(good, unused, total, t2, sh);           // (its barriers also publish the cleared per_state)
+    for (int c = beg; c < end; ++c) {
+        const int st = a.cstate[c];
+        atomicAdd(per_state + (st & 7), 1);                // integer counts: the order of arrival changes nothing
+        if (st != 1) { a.tid[c] = -1; continue; }
+        a.tid[c] = good;                                   // good < total <= nodes / 2: the capacity of xyz, track_length, track_error
+        a.track_length[good] = a.cnt[a.croot[c]];
+        if (!a.tracks_only) {
+            const float* res = a.cres + (long long)c * 4;
+            a.xyz[(long long)good * 3] = res[0]; a.xyz[(long long)good * 3 + 1] = res[1]; a.xyz[(long long)good * 3 + 2] = res[2];
+            a.track_error[good] = res[3];
+        }
+        ++good;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.counts[0] = total;
+    if (threadIdx.x < 8) a.counts[1 + threadIdx.x] = per_state[threadIdx.x];
+}
+
+// ------------------------------------------------------------------ 8. scatter
+__global__ __launch_bounds__(TRI_THREADS) void tri_scatter_kernel(TriArgs a) {
+    const int v = blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (v >= a.nodes) return;
+    const int r = a.root[v];
+    int state = 0, id = -1;
+    float x = __builtin_nanf(""), y = x, z = x;
+    if (a.cnt[r] >= 2) {
+        const int c = a.comp[r];
+        state = a.cstate[c]; id = a.tid[c];
+        if (state == 1 && !a.tracks_only) { const float* res = a.cres + (long long)c * 4; x = res[0]; y = res[1]; z = res[2]; }
+    }
+    a.node_state[v] = (unsigned char)state;
+    a.track_id[v] = id;
+    if (a.points3d) { float* p = a.points3d + (long long)v * 3; p[0] = x; p[1] = y; p[2] = z; }
+}
+
+}  // namespace lg
+
+using namespace lg;
+
+extern "C" {
+
+int64_t lg_triangulate_workspace_bytes(int64_t images, int32_t n, uint32_t flags) {
+    TriLayout L;
+    return tri_layout(images, n, flags, L) ? -1 : L.total;
+}
+
+int lg_triangulate(const lg_triangulate_io* io, void* hip_stream) {
+    if (!io) return set_error(LG_ERR_INVALID, "lg_triangulate: null io");
+    TriLayout L;
+    if (const char* why = tri_layout(io->images, io->n, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_triangulate: ") + why);
+    const bool tracks_only = io->flags & LG_TRI_TRACKS_ONLY;
+    const long long P = io->pairs, n = io->n;
+    if (P < 0 || P * n >= (1LL << 31)) return set_error(LG_ERR_INVALID, "lg_triangulate: the pair count must not be negative and pairs x n must stay below 2^31");
+    if (io->max_track_length < 2 || io->max_track_length > LG_TRI_MAX_TRACK_LENGTH)
+        return set_error(LG_ERR_INVALID, "lg_triangulate: max_track_length must lie in [2, LG_TRI_MAX_TRACK_LENGTH]");
+    if (!tracks_only && (!(io->max_reproj_error > 0.f) || !(io->max_reproj_error <= 3.0e18f)))
+        return set_error(LG_ERR_INVALID, "lg_triangulate: max_reproj_error must be > 0 (and finite)");
+    if (!tracks_only && (!(io->min_angle >= 0.f) || !(io->min_angle < 180.f))) return set_error(LG_ERR_INVALID, "lg_triangulate: min_angle must lie in [0, 180)");
+    if (!io->counts || (P && (!io->index0 || !io->index1 || !io->status)) || (P && n && !io->matches0) || (L.nodes && (!io->track_id || !io->node_state || !io->track_length)) ||
+        (!tracks_only && ((io->images && (!io->cameras || !io->poses)) || (L.nodes && (!io->kpts || !io->points3d || !io->xyz || !io->track_error)))))
+        return set_error(LG_ERR_INVALID, "lg_triangulate: null pointer among kpts, index0, index1, matches0, cameras, poses, points3d, track_id, node_state, xyz, "
+                                         "track_length, track_error, counts, status");
+    if (const int rc = check_workspace("lg_triangulate", "lg_triangulate_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    char* ws = static_cast<char*>(io->workspace);
+    TriArgs a{};
+    a.pairs = (int)P; a.n = (int)n; a.images = io->images; a.nodes = (int)L.nodes; a.max_len = io->max_track_length;
+    a.refine = (io->flags & LG_TRI_REFINE) ? 1 : 0; a.tracks_only = tracks_only ? 1 : 0;
+    a.angle_test = !tracks_only && io->min_angle > 0.f; a.max_err = (double)io->max_reproj_error;
+    a.cos_min = std::cos((double)io->min_angle * 3.141592653589793 / 180.0);
+    a.kpts = io->kpts; a.num = io->num; a.index0 = io->index0; a.index1 = io->index1; a.matches0 = reinterpret_cast<const long long*>(io->matches0);
+    a.cameras = io->cameras; a.poses = io->poses;
+    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
+    a.head = reinterpret_cast<TriHead*>(ws + L.head); a.rec = reinterpret_cast<TriImage*>(ws + L.rec);
+    a.parent = ints(L.parent); a.root = ints(L.root); a.cnt = ints(L.cnt); a.off = ints(L.off); a.comp = ints(L.comp); a.cursor = ints(L.cursor); a.list = ints(L.list);
+    a.croot = ints(L.croot); a.cstate = ints(L.cstate); a.tid = ints(L.tid); a.cres = reinterpret_cast<float*>(ws + L.cres);
+    a.points3d = tracks_only ? nullptr : io->points3d; a.track_id = reinterpret_cast<long long*>(io->track_id); a.node_state = io->node_state;
+    a.xyz = io->xyz; a.track_length = io->track_length; a.track_error = io->track_error; a.counts = io->counts; a.status = io->status;
+
+    auto blocks = [](long long items) { return dim3((unsigned)((items + TRI_THREADS - 1) / TRI_THREADS)); };
+    const long long first = std::max<long long>(std::max<long long>(L.nodes, P), std::max<long long>(io->images, 1));
+    hipLaunchKernelGGL(tri_init_kernel, blocks(first), dim3(TRI_THREADS), 0, s, a);
+    if (P * n) hipLaunchKernelGGL(tri_union_kernel, blocks(P * n), dim3(TRI_THREADS), 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(tri_flatten_kernel, blocks(L.nodes), dim3(TRI_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(tri_fill_kernel, blocks(L.nodes), dim3(TRI_THREADS), 0, s, a);
+    if (L.tracks) hipLaunchKernelGGL(tri_tracks_kernel, blocks(L.tracks), dim3(TRI_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tri_number_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(tri_scatter_kernel, blocks(L.nodes), dim3(TRI_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return LG_OK;
+}
+
+}  // extern "C"

@@ -226,6 +226,14 @@ def estimate_absolute_poses(estimator, result, feats, pairs, cameras, points3d, 
     return estimator.estimate_pairs(store0, pairs, result, cameras, points3d, store1, pool=pool)
 
 
+def triangulate_tracks(triangulator, result, feats, pairs, cameras, poses) -> dict:
+    """Tracks and their world points from what `matcher.match_pairs(feats, pairs)` or a verifier over the same list returned (`result`: a dict, a
+    `DeferredMatches` or matches0 itself), by a `Triangulator`: the same store (or a list of per-image dicts, collated once), the same pair list — both
+    columns index the one store —, one camera ([K, 4] (fx, fy, cx, cy) or [K, 3, 3]) and one known pose ([K, 3, 4] (R | t) or (R, t)) per image.  Returns the
+    triangulator's dict; its points3d [K, N, 3] is what `estimate_absolute_poses` takes as points3d."""
+    return triangulator.triangulate(_as_store(feats), pairs, result, cameras, poses)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output

@@ -1,0 +1,120 @@
+"""Tracks and multi-view triangulation with known poses on the device, on the kernels of `csrc/lg_triangulate.hip` behind `lg_triangulate`
+(include/lightglue_amd.h holds the definition).  It reads what a matcher or a verifier leaves on the device — ONE keypoint store, the pair list over it and
+`matches0` — in place, plus one pinhole camera (fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image.  Tracks are the connected components of
+the match graph; each is triangulated from all its views.  `points3d [K, N, 3]` (NaN where a row has no point) is what `AbsolutePoseEstimator` takes as
+points3d1.  Any number of pairs in ONE call with ONE host synchronisation; every output is a function of the edge set alone, not of the list's order."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import _cabi, _call
+from .relpose import as_cameras
+
+STATES = ("none", "triangulated", "conflict", "too_long", "degenerate", "behind", "reprojection", "angle")    # node_state 0 .. 7
+
+
+def as_poses(poses, K: int, device) -> torch.Tensor:
+    """[K, 3, 4] float32 (R | t) on `device` from a [K, 3, 4] tensor or a tuple (R [K, 3, 3], t [K, 3])"""
+    if isinstance(poses, (tuple, list)) and len(poses) == 2:
+        R, t = torch.as_tensor(poses[0]), torch.as_tensor(poses[1])
+        if tuple(R.shape) != (K, 3, 3) or tuple(t.shape) != (K, 3):
+            raise ValueError(f"poses (R, t) must have shapes [{K}, 3, 3] and [{K}, 3], got {tuple(R.shape)} and {tuple(t.shape)}")
+        poses = torch.cat([R.to(device=device, dtype=torch.float32), t.to(device=device, dtype=torch.float32)[:, :, None]], 2)
+    poses = torch.as_tensor(poses)
+    if tuple(poses.shape) != (K, 3, 4):
+        raise ValueError(f"poses must have shape [{K}, 3, 4] (R | t) or be a tuple (R [{K}, 3, 3], t [{K}, 3]), got {tuple(poses.shape)}")
+    return poses.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+class Triangulator(nn.Module):
+    """max_reproj_error: the largest reprojection error, in pixels, an observation of an accepted track may have.  min_angle: the smallest angle, in degrees,
+    the widest pair of rays of an accepted track must have.  max_track_length: a longer track is reported too long, in [2, 1024].  refine: five Gauss-Newton
+    steps on the reprojection error from the linear start."""
+
+    def __init__(self, max_reproj_error: float = 4.0, min_angle: float = 1.5, max_track_length: int = 128, refine: bool = True):
+        super().__init__()
+        if not 0.0 < float(max_reproj_error) < float("inf"):
+            raise ValueError(f"max_reproj_error must be > 0, got {max_reproj_error!r}")
+        if not 0.0 <= float(min_angle) < 180.0:
+            raise ValueError(f"min_angle must lie in [0, 180), got {min_angle!r}")
+        if int(max_track_length) != max_track_length or not 2 <= int(max_track_length) <= _cabi.LG_TRI_MAX_TRACK_LENGTH:
+            raise ValueError(f"max_track_length must be an integer in [2, {_cabi.LG_TRI_MAX_TRACK_LENGTH}], got {max_track_length!r}")
+        self.max_reproj_error, self.min_angle, self.max_track_length, self.refine = float(max_reproj_error), float(min_angle), int(max_track_length), bool(refine)
+
+    # ------------------------------------------------------------------ the call path
+    def _launch(self, feats: dict, pairs, result, cameras, poses, validate: bool, tracks_only: bool) -> dict:
+        """ONE lg_triangulate call on the current stream, then the dict behind the one host synchronisation of the call"""
+        device = feats["keypoints"].device
+        _call.require_gpu(device, "keypoints")
+        s = _call.build_side(feats, device, "feats")
+        K, N = int(s.K), int(s.N)
+        pt = _call.pair_list(pairs, K, K, validate)
+        P = int(pt.shape[0])
+        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None
+        if isinstance(result, _call.DeferredMatches):
+            result = result.result()
+        m0 = result["matches0"] if isinstance(result, dict) else result
+        assert torch.is_tensor(m0) and tuple(m0.shape) == (P, N), f"matches0 must have shape [{P}, {N}], got {tuple(m0.shape)}"
+        if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
+            m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+        cam = pose = None
+        if not tracks_only:
+            cam, pose = as_cameras(cameras, K, device, "cameras"), as_poses(poses, K, device)
+        flags = (_cabi.LG_TRI_REFINE if self.refine else 0) | (_cabi.LG_TRI_TRACKS_ONLY if tracks_only else 0)
+        cap = K * N // 2                                                   # a track has at least two nodes
+        pts = None if tracks_only else torch.empty((K, N, 3), device=device, dtype=torch.float32)
+        track_id = torch.empty((K, N), device=device, dtype=torch.int64)
+        state = torch.empty((K, N), device=device, dtype=torch.uint8)
+        per_track = torch.empty((max(cap, 1), 5), device=device, dtype=torch.float32)      # xyz [cap, 3] | track_error [cap] | track_length [cap] (int32 bits)
+        ints = torch.zeros((9 + P,), device=device, dtype=torch.int32)          # T | tracks per state [8] | status [P]
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            lib = _cabi.load()
+            nbytes = lib.lg_triangulate_workspace_bytes(K, N, flags)          # -1: outside the envelope — lg_triangulate below says why
+            ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
+            p = _call._ptr
+            base = per_track.data_ptr()
+            io = _cabi.LgTriangulateIO(
+                pairs=P, n=N, images=K, flags=flags, max_reproj_error=self.max_reproj_error, min_angle=self.min_angle, max_track_length=self.max_track_length,
+                kpts=p(s.kpts), num=p(s.num), index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
+                matches0=p(m0), cameras=p(cam), poses=p(pose), workspace=p(ws), workspace_bytes=max(nbytes, 0),
+                points3d=p(pts), track_id=p(track_id), node_state=p(state),
+                xyz=base, track_error=base + 12 * cap, track_length=base + 16 * cap,
+                counts=ints.data_ptr(), status=None if not P else ints.data_ptr() + 36)
+            _cabi.check(lib.lg_triangulate(C.byref(io), C.c_void_p(stream.cuda_stream)))
+            host = ints.tolist()              # THE host sync of the call: the per-track outputs need their number
+        T = host[0]
+        flat = per_track.view(-1)
+        out = {"track_id": track_id, "node_state": state, "num_tracks": T, "track_length": flat[4 * cap:4 * cap + T].view(torch.int32).long(),
+               "state_counts": dict(zip(STATES, host[1:9])), "status": ints[9:]}
+        if not tracks_only:
+            out.update(points3d=pts, xyz=flat[:3 * T].view(T, 3), track_error=flat[3 * cap:3 * cap + T])
+        try:
+            _call.raise_on_status(host[9:])
+        except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
+            err.outputs = out
+            raise
+        return out
+
+    @torch.no_grad()
+    def triangulate(self, feats: dict, pairs, result, cameras, poses, *, validate: bool = True) -> dict:
+        """feats = {keypoints [K, N, 2], num_keypoints [K] (optional)}: ONE store, indexed by both columns of `pairs` [P, 2] (host or device); `result`: either
+        matcher's dict, a `DeferredMatches`, the dict of `TwoViewVerifier` / `RelativePoseEstimator` (its verified matches0) or matches0 [P, N] itself — only
+        matches0 is read; cameras [K, 4] (fx, fy, cx, cy) or [K, 3, 3]; poses [K, 3, 4] (R | t) or (R [K, 3, 3], t [K, 3]), X_cam = R X_world + t.  Returns
+        points3d [K, N, 3] float32 (the track's point at every row of a triangulated track, NaN elsewhere: what `AbsolutePoseEstimator` takes as points3d1),
+        track_id [K, N] int64 (dense in [0, T) in ascending order of the track's lowest node, -1 elsewhere), node_state [K, N] uint8 (`STATES`), num_tracks = T,
+        xyz [T, 3], track_length [T], track_error [T] (mean reprojection error in pixels), state_counts (tracks per state), status [P].  ONE host
+        synchronisation.  `validate` as in `match_pairs`; a pair (a, a), an index outside the store or an image whose camera or pose fails the camera rule
+        raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else."""
+        return self._launch(feats, pairs, result, cameras, poses, validate, False)
+
+    forward = triangulate
+
+    @torch.no_grad()
+    def build_tracks(self, feats: dict, pairs, result, *, validate: bool = True) -> dict:
+        """Tracks only (LG_TRI_TRACKS_ONLY): no cameras, no poses, no geometry.  node_state holds 0 .. 3 (1: a clean track), track_id numbers every clean
+        track; returns track_id, node_state, num_tracks, track_length, state_counts, status."""
+        return self._launch(feats, pairs, result, None, None, validate, True)
