@@ -443,6 +443,25 @@ def filter_matches(scores: np.ndarray, th: float):
 
 
 # --------------------------------------------------------------------------- forward
+def layer_trace(ctx: _Ctx, p, i: int, x0, x1, cos0, sin0, cos1, sin1, heads: int, n_layers: int, trace: Optional[dict] = None, full: bool = True):
+    """ref :251-253: layer ``i`` (SelfBlock on either image, then the CrossBlock) on the rows given — the body of ``forward_pair``'s loop, which
+    calls it, so a layer run on its own (from any state: pruned rows and their rotary tables) leaves the same trace keys.  ``trace`` receives
+    ``desc{0,1}_l{i}``; with ``full`` also every intermediate of both blocks and the 256 -> 1 heads on the layer's output.  Returns (x0, x1)."""
+    tr = trace if (trace is not None and full) else None
+    x0 = self_block(ctx, p, i, x0, cos0, sin0, heads, tr, f"l{i}_self0_")  # ref :251
+    x1 = self_block(ctx, p, i, x1, cos1, sin1, heads, tr, f"l{i}_self1_")  # ref :252
+    if tr is not None:
+        tr[f"l{i}_xs0"], tr[f"l{i}_xs1"] = x0.copy(), x1.copy()
+    x0, x1 = cross_block(ctx, p, i, x0, x1, heads, tr, f"l{i}_cross_")  # ref :253
+    if trace is not None:
+        trace[f"desc0_l{i}"], trace[f"desc1_l{i}"] = x0.copy(), x1.copy()
+    if tr is not None:   # the 256 -> 1 heads on this layer's output: matchability logit (every layer), token confidence (every layer but the last)
+        tr[f"l{i}_z0"], tr[f"l{i}_z1"] = matchability_logit(p, i, x0), matchability_logit(p, i, x1)
+        if i < n_layers - 1:
+            tr[f"l{i}_tok0"], tr[f"l{i}_tok1"] = token_confidence(ctx, p, i, x0), token_confidence(ctx, p, i, x1)
+    return x0, x1
+
+
 def forward_pair(params: Dict[str, np.ndarray], conf: SimpleNamespace,
                  kpts0, kpts1, desc0, desc1, size0=None, size1=None,
                  scales0=None, oris0=None, scales1=None, oris1=None,
@@ -487,19 +506,13 @@ def forward_pair(params: Dict[str, np.ndarray], conf: SimpleNamespace,
         if x0.shape[0] == 0 or x1.shape[0] == 0:  # ref :539-540
             break
         full = trace is not None and i in trace.get("_full_layers", ())
-        x0 = self_block(ctx, p, i, x0, cos0, sin0, H, trace if full else None, f"l{i}_self0_")  # ref :251
-        x1 = self_block(ctx, p, i, x1, cos1, sin1, H, trace if full else None, f"l{i}_self1_")  # ref :252
-        if full:
-            trace[f"l{i}_xs0"], trace[f"l{i}_xs1"] = x0.copy(), x1.copy()
-        x0, x1 = cross_block(ctx, p, i, x0, x1, H, trace if full else None, f"l{i}_cross_")  # ref :253
-        if trace is not None:
-            trace[f"desc0_l{i}"], trace[f"desc1_l{i}"] = x0.copy(), x1.copy()
-        if full:   # the 256 -> 1 heads on this layer's output: matchability logit (every layer), token confidence (every layer but the last)
-            trace[f"l{i}_z0"], trace[f"l{i}_z1"] = matchability_logit(p, i, x0), matchability_logit(p, i, x1)
-            if i < L - 1:
-                trace[f"l{i}_tok0"], trace[f"l{i}_tok1"] = token_confidence(ctx, p, i, x0), token_confidence(ctx, p, i, x1)
+        x0, x1 = layer_trace(ctx, p, i, x0, x1, cos0, sin0, cos1, sin1, H, L, trace, full)  # ref :251-253
         if i == L - 1:  # ref :544-545
             continue
+        if trace is not None:   # what the adaptive step behind this layer sees (tests/adaptive_oracle.py): it changes no result
+            trace[f"l{i}_mscore0"], trace[f"l{i}_mscore1"] = _sigmoid(matchability_logit(p, i, x0)), _sigmoid(matchability_logit(p, i, x1))
+            if do_early_stop:
+                trace[f"l{i}_conf0"], trace[f"l{i}_conf1"] = token_confidence(ctx, p, i, x0), token_confidence(ctx, p, i, x1)
         if do_early_stop:  # ref :547-550
             token0, token1 = token_confidence(ctx, p, i, x0), token_confidence(ctx, p, i, x1)
             conf_all = np.concatenate([token0, token1], -1)
@@ -523,6 +536,8 @@ def forward_pair(params: Dict[str, np.ndarray], conf: SimpleNamespace,
             keep1 = np.where(keep)[0]
             ind1, x1, cos1, sin1 = ind1[keep1], x1[keep1], cos1[keep1], sin1[keep1]
             prune1[ind1] += 1
+        if trace is not None and do_point_pruning:   # the index sets behind this layer's step
+            trace[f"l{i}_ind0"], trace[f"l{i}_ind1"] = ind0.copy(), ind1.copy()
 
     if x0.shape[0] == 0 or x1.shape[0] == 0:  # ref :568-588
         out = {

@@ -40,15 +40,31 @@ def read_attn_buf(model, name):
 
 
 class Rows:
-    """global row index of (pair, image, r) for the engine's row space"""
+    """global row index of (pair, image, r) for the engine's row space.  `lens` ([B][2], optional): the live rows of every segment of a ragged or
+    pruned row space (the engine's LEN); without it every segment is n0 / n1 rows long."""
 
-    def __init__(self, B, n0, n1, cap0, cap1):
+    def __init__(self, B, n0, n1, cap0, cap1, lens=None):
         self.B, self.n0, self.n1, self.c0, self.c1 = B, n0, n1, cap0, cap1
         self.R = B * (cap0 + cap1)
+        self.lens = None if lens is None else np.asarray(lens, np.int64).reshape(B, 2)
+
+    def base(self, pair, image):
+        return pair * (self.c0 + self.c1) + image * self.c0
+
+    def cap(self, image):
+        return self.c1 if image else self.c0
+
+    def len(self, pair, image):
+        return int(self.lens[pair, image]) if self.lens is not None else (self.n1 if image else self.n0)
 
     def sl(self, pair, image):
-        base = pair * (self.c0 + self.c1) + image * self.c0
-        return slice(base, base + (self.n1 if image else self.n0))
+        base = self.base(pair, image)
+        return slice(base, base + self.len(pair, image))
+
+    def seg(self, pair, image):
+        """the whole capacity of the segment, dead rows included"""
+        base = self.base(pair, image)
+        return slice(base, base + self.cap(image))
 
 
 def err(a, b):
@@ -74,34 +90,47 @@ def oracle_traces(sd, data, conf_kw, layer=0):
     return traces
 
 
-def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False, options=None, traces=None):
+def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False, options=None, traces=None, model=None, tdata=None, lens=None, before_run=None, raw=None):
     """Run the pipeline up to every step of `layer` and compare the step's output buffer with the
     oracle.  Returns {stage name: (max abs err, err / rms)}.  `options`: engine options applied with
-    set_option after the model is made; `traces`: oracle_traces(...) of the same inputs, when the caller shares them."""
+    set_option after the model is made; `traces`: oracle_traces(...) of the same inputs, when the caller shares them.
+    A layer behind an adaptive step: `traces` are the oracle's of THAT layer on the rows the device holds in front of it and `lens` [B][2] the
+    live rows of every segment there (the engine's LEN); `model` / `tdata`: the caller's model (made as make_model makes it) and torch batch
+    (ragged counts, poisoned padding), so that the state the traces were made from is the state compared.  `before_run()` is called in front of
+    every forward; `raw` (dict) receives the live rows of every stage's buffer as the device holds them, for bit comparisons between two runs."""
     B, n0 = data["image0"]["keypoints"].shape[:2]
     n1 = data["image1"]["keypoints"].shape[1]
     if traces is None:
         traces = oracle_traces(sd, data, conf_kw, layer)
-    model = make_model(sd, precision, **conf_kw)
+    if model is None:
+        model = make_model(sd, precision, **conf_kw)
     model.set_option("fused_tail", int(fused))   # unfused: every intermediate buffer of the chain exists
     for key, value in (options or {}).items():
         model.set_option(key, value)
-    tdata = to_torch(data)
+    if tdata is None:
+        tdata = to_torch(data)
     res = {}
     L = layer
     base = 1 + 12 * L
 
     def run_to(step):
+        if before_run is not None:
+            before_run()
         model.debug_stop_after(step)
         model(tdata)
         c0, c1 = model.debug_caps()
-        return Rows(B, n0, n1, c0, c1)
+        return Rows(B, n0, n1, c0, c1, lens)
+
+    def keep_raw(name, got):
+        if raw is not None:
+            raw.setdefault(name, []).append(np.array(got))
 
     def cmp_rows(name, buf, width, key_fn):
         worst = (0.0, 0.0)
         for b in range(B):
             for im in (0, 1):
                 got = buf.reshape(rows.R, width)[rows.sl(b, im)]
+                keep_raw(name, got)
                 e = err(got, key_fn(traces[b], im))
                 worst = max(worst, e)
         res[name] = worst
@@ -115,6 +144,7 @@ def stage_errors(sd, data, precision, conf_kw, layer=0, fused=False, options=Non
                     got = buf.reshape(4, 64, rows.R)[:, :, rows.sl(b, im)].transpose(0, 2, 1)
                 else:
                     got = buf.reshape(4, rows.R, 64)[:, rows.sl(b, im), :]
+                keep_raw(name, got)
                 worst = max(worst, err(got, ref))
         res[name] = worst
 
