@@ -899,6 +899,104 @@ int64_t lg_triangulate_workspace_bytes(int64_t images, int32_t n, uint32_t flags
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_triangulate(const lg_triangulate_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bundle adjustment: joint refinement of the free poses and of all track points by Levenberg-Marquardt on the sum of squared pixel reprojection errors, over
+ * what the triangulator returns (track_id, xyz) plus one camera and one pose per image; intrinsics are fixed.  Schur complement onto the poses, dense Cholesky
+ * of the reduced camera system, fp64 throughout, no fused multiply-add, one call and one host synchronisation for the whole problem.  Stateless.  The reference
+ * has no such step; this is the definition (tests/bundle_oracle.py restates it in float64 numpy, with a solver of its own).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   nodes     as in the triangulator: node v = k n + i, live iff i < num[k] (num NULL: n; clamped into [0, n]).
+ *   candidates  node (k, i) with j = track_id[k][i] is a candidate observation of track j iff i < num[k]; 0 <= j < tracks; image k passes the camera rule (the
+ *             triangulator's: the relative pose's rule on cameras[k], the 12 entries of poses[k] finite); the three entries of xyz[j] are finite; and at the
+ *             INPUT state pz > 0 (pz as in "residual" below, from the widened float32 inputs).
+ *   observations  a track with at least 2 and at most LG_BA_MAX_TRACK_LENGTH candidates is ADJUSTED and its candidates are the active observations; the set is
+ *             fixed for the whole call.  Its observations are ordered by ascending node (by image, then by row).  Two rows of one image in one track are two
+ *             observations.  Every other track is not adjusted: its point comes back as the bits that went in.
+ *   node_state  0 not labelled (a dead row, or track_id outside [0, tracks)); 1 active observation; 2 bad image; 3 non-finite point; 4 behind at the start
+ *             (pz <= 0); 5 a candidate of a track left with fewer than 2 candidates; 6 a candidate of a track with more than LG_BA_MAX_TRACK_LENGTH.  The first
+ *             failing test in the order 0, 2, 3, 4, then 5 / 6 names the state.
+ *   status    [images]: LG_ERR_CAMERA for an image that fails the camera rule, else LG_OK.  Such an image takes its observations out (state 2), its pose comes
+ *             back as the bits that went in, and everything else is what the same call without its labels gives, bit for bit.
+ *   state     poses are carried in fp64 through the call, starting from the float32 inputs widened; the input R is NOT re-orthonormalised, and what comes
+ *             back is Rodrigues products of it.  Points likewise.  Outputs are rounded to float32 once.
+ *   residual  of observation (k, i) of track j, the triangulator's: p = R X + t (each row ((r0 X0 + r1 X1) + r2 X2) + t), iz = 1 / pz,
+ *             r = ((fx px) iz + cx - x, (fy py) iz + cy - y), x, y the float32 keypoint widened.  cost = sum of rx rx + ry ry.
+ *   Jacobians  Jp = [[ax, 0, az], [0, by, bz]], ax = fx iz, az = -(((fx px) iz) iz), by = fy iz, bz = -(((fy py) iz) iz).  Point: B = Jp R (2 x 3, the
+ *             triangulator's J).  Pose: A = Jp [-[p]x | I] (2 x 6) for the camera-frame twist (w, d), the absolute pose's parametrisation:
+ *             A0 = (az py, ax pz - az px, -(ax py), ax, 0, az), A1 = (bz py - by pz, -(bz px), by px, 0, by, bz).
+ *             Update: R <- Rodrigues(w) R, t <- Rodrigues(w) t + d, Rodrigues(w) = I + sin(th) [k]x + (1 - cos(th)) [k]x^2, th = |w|, k = w / th (I for th = 0).
+ *   gauge     an image is FREE iff it passes the camera rule, constant_pose[k] = 0 and it has at least one active observation.  Every other image keeps its
+ *             observations (they enter the points' blocks and the cost) but its 6 columns drop out: identity diagonal block, zero coupling, zero right-hand
+ *             side, and its pose comes back as the bits that went in.  Nothing here fixes the gauge if no image is constant: the caller must hold at least one
+ *             (the Python layer refuses otherwise); two constant images fix scale, with one the damping holds it.
+ *   normal equations  per free image a: U_a = sum A^T A (6 x 6), g_a = sum A^T r, over its active rows in ascending row order.  Per adjusted track j:
+ *             V_j = sum B^T B (3 x 3), g_j = sum B^T r, over its observations in order.  Per observation of a free image W = A^T B (6 x 3),
+ *             W[r][m] = A0[r] B0[m] + A1[r] B1[m]; W is formed again wherever it is needed, not stored.
+ *   damping   Marquardt's: every diagonal entry d of U and V becomes d + lambda clamp(d, 1e-6, 1e32).
+ *   points    Vi_j = the inverse of the damped V'_j, column c = the solution of V'_j x = e_c by the triangulator's 3 x 3 elimination and pivot rule (Vi is not
+ *             symmetrised); y_j = Vi_j g_j, row r: (Vi[r][0] g0 + Vi[r][1] g1) + Vi[r][2] g2.
+ *   reduced system  S of size 6 images x 6 images, lower block triangle.  For free a, free b <= a: E_ab = sum over the active rows i of image a in ascending row
+ *             order, and for each over the observations (b, i') of the same track in order, of Y W_(b,i')^T with Y = W_(a,i) Vi_j
+ *             (Y[r][m] = (W[r][0] Vi[0][m] + W[r][1] Vi[1][m]) + W[r][2] Vi[2][m]; entry (r, c): (Y[r][0] Wb[c][0] + Y[r][1] Wb[c][1]) + Y[r][2] Wb[c][2]);
+ *             S_ab = -E_ab, S_aa = U'_a - E_aa.  Right-hand side of image a: (sum over its active rows in row order of W y_j) - g_a.  Only the lower triangle
+ *             of S is read.
+ *   Cholesky  S = L L^T, blocked by LG_BA_CHOLESKY_BLOCK = 48 columns, the right-hand side carried as row 6 images of S (so L z = rhs comes out with the factor):
+ *             entry (i, j) = S_ij minus the sum of L_ik L_jk over ALL earlier panels' k in ascending order, then the panel's own columns in ascending order.
+ *             A pivot that is not > 0 (or not finite) fails the trial; the factorisation goes on with 1 in its place.  L^T s = z backwards gives the pose
+ *             steps; per panel the rows below are summed in 5 interleaved partial sums (row i goes to partial (i - first row below) mod 5) added in order 0 .. 4.
+ *   point step  X_j <- X_j - (y_j + Vi_j sum over the track's observations of free images, in order, of W^T s_a), W^T s summed over r ascending.
+ *   trial     the cost at the trial state: per image the sum over its active rows in ascending row order, the images added in ascending order.  The trial is
+ *             REJECTED if an active observation has pz <= 0, a trial pose, point or cost is not finite, a 3 x 3 pivot failed or a Cholesky pivot failed.
+ *             Otherwise: converged = |cost - cost_new| <= function_tolerance cost; accepted iff cost_new < cost.  Accepted: the trial becomes the state,
+ *             lambda <- max(lambda / 10, 1e-12); else lambda <- min(10 lambda, 1e12).  lambda starts at initial_damping.
+ *   stopping  num_iterations is a fixed budget: every launch of every iteration is enqueued unconditionally; cost, lambda, the accept / reject decision and
+ *             `converged` live in a device record the kernels read, and once converged the remaining launches return at once.  No host round trip.
+ *   outputs   poses [images][12] and xyz [tracks][3] rounded to float32 once (bits unchanged for an image that is not free / a track that is not adjusted);
+ *             points3d [images][n][3] = the adjusted point at every active observation's row, NaN elsewhere (what lg_abspose_estimate reads as points3d1);
+ *             node_state; observation_error [images][n] = sqrt(rx rx + ry ry) at the final state, NaN where not active; status [images];
+ *             summary [8] fp64: initial cost, final cost, iterations run, steps accepted, converged, active observations, final lambda, 0.
+ *   Determinism: no floating-point atomics; every sum is a fixed function of position, so every output is the same bits from run to run and under any
+ *             relabelling of the tracks (a permutation of the rows of xyz with track_id renamed accordingly).
+ * Workspace: lg_bundle_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: a 256-byte record; per image 312 bytes (a 64-byte record, the
+ *   pose twice, the step, the cost); S with its right-hand side row, (6 images + 1) x 6 images fp64 (18.9 MB at 256 images); 8 bytes per node (the track list:
+ *   node and image); 156 bytes per track (count, offset, cursor, the point twice, Vi, y).  W is recomputed, not stored (it would be 144 bytes per observation).
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): null io; any flag bit (none is defined); n above LG_MAX_KEYPOINTS; images outside
+ *   [1, LG_BA_MAX_IMAGES]; images x n above LG_MAX_ROWS; tracks outside [0, images x n / 2]; num_iterations outside [1, LG_BA_MAX_ITERATIONS]; initial_damping or
+ *   function_tolerance not finite and > 0; a null required pointer; a workspace that is too small or not 256-byte aligned.
+ * Launches, none of which waits on another workgroup: records; candidates (count); one scan over the tracks; fill; sort (one lane per track); the cost of the
+ *   input; then per iteration: points (one lane per track: V, g, Vi, y), reduce (one workgroup per image and 6 column blocks: U, g, the block row of S, rhs),
+ *   two launches per Cholesky panel (ONE workgroup factors the diagonal block, then one workgroup per 48-row tile solves its rows below it), back substitution and trial poses (ONE workgroup), trial points (one lane
+ *   per track), trial cost (one workgroup per image), decide (one lane); last the scatter. */
+#define LG_BA_MAX_IMAGES 256
+#define LG_BA_MAX_ITERATIONS 100
+#define LG_BA_MAX_TRACK_LENGTH 1024
+#define LG_BA_CHOLESKY_BLOCK 48
+typedef struct lg_bundle_io {
+    int32_t n, images, tracks;
+    uint32_t flags;                        /* none defined: must be 0                                                 */
+    int32_t num_iterations;                /* in [1, LG_BA_MAX_ITERATIONS]                                            */
+    double initial_damping;                /* > 0                                                                     */
+    double function_tolerance;             /* > 0                                                                     */
+    const float *kpts;                     /* [images][n][2], read in place                                           */
+    const int32_t *num;                    /* [images] live rows, or NULL = n                                         */
+    const int64_t *track_id;               /* [images][n]: the triangulator's output                                  */
+    const float *xyz;                      /* [tracks][3]                                                             */
+    const float *cameras;                  /* [images][4]: (fx, fy, cx, cy)                                           */
+    const float *poses;                    /* [images][12]: (R | t) row-major 3 x 4, X_cam = R X_world + t            */
+    const uint8_t *constant_pose;          /* [images]: non-zero = the pose is held fixed                             */
+    void *workspace; int64_t workspace_bytes;
+    float *poses_out;                      /* [images][12]                                                            */
+    float *xyz_out;                        /* [tracks][3]                                                             */
+    float *points3d;                       /* [images][n][3]                                                          */
+    uint8_t *node_state;                   /* [images][n]                                                             */
+    float *observation_error;              /* [images][n]                                                             */
+    double *summary;                       /* [8]                                                                     */
+    int32_t *status;                       /* [images] LG_OK / LG_ERR_CAMERA                                          */
+} lg_bundle_io;
+int64_t lg_bundle_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_bundle_adjust(const lg_bundle_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,122 @@
+"""Bundle adjustment of poses and points on the device, on the kernels of `csrc/lg_bundle.hip` behind `lg_bundle_adjust` (include/lightglue_amd.h holds the
+definition).  It reads what `Triangulator` returns — `track_id [K, N]` and `xyz [T, 3]` over ONE keypoint store — in place, plus one pinhole camera
+(fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image, and refines all free poses and all track points jointly: Levenberg-Marquardt on the
+sum of squared pixel reprojection errors, Schur complement, dense Cholesky, fp64.  Intrinsics are fixed.  ONE call with ONE host synchronisation; `points3d
+[K, N, 3]` (NaN where a row is no active observation) is what `AbsolutePoseEstimator` takes as points3d1."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _cabi, _call
+from .relpose import as_cameras
+from .triangulate import as_poses
+
+STATES = ("none", "active", "bad_image", "non_finite_point", "behind", "short_track", "too_long")    # node_state 0 .. 6
+
+
+def as_tracks(tracks, K: int, N: int, device):
+    """(track_id [K, N] int64, xyz [T, 3] float32) on `device` from `Triangulator`'s dict or a tuple (track_id, xyz)"""
+    if isinstance(tracks, dict):
+        tracks = (tracks["track_id"], tracks["xyz"])
+    if not isinstance(tracks, (tuple, list)) or len(tracks) != 2:
+        raise ValueError("tracks must be the Triangulator's dict or a tuple (track_id [K, N], xyz [T, 3])")
+    tid, xyz = torch.as_tensor(tracks[0]), torch.as_tensor(tracks[1])
+    if tuple(tid.shape) != (K, N):
+        raise ValueError(f"track_id must have shape [{K}, {N}], got {tuple(tid.shape)}")
+    if tid.dtype.is_floating_point or tid.dtype is torch.bool:
+        raise ValueError(f"track_id must hold integers, got {tid.dtype}")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"xyz must have shape [T, 3], got {tuple(xyz.shape)}")
+    if xyz.shape[0] > K * N // 2:
+        raise ValueError(f"xyz holds {xyz.shape[0]} tracks: more than K N / 2 = {K * N // 2} (a track has at least two observations)")
+    return tid.detach().to(device=device, dtype=torch.int64).contiguous(), xyz.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def as_constant(constant_pose, K: int) -> torch.Tensor:
+    """[K] bool on the host from a [K] mask or a sequence of image indices; at least one image must be constant"""
+    c = torch.as_tensor(constant_pose).detach().cpu()
+    if c.numel() == 0 and c.dtype is not torch.bool:       # an empty index list (torch reads [] as float)
+        c = c.reshape(0).long()
+    if c.dtype is not torch.bool:
+        if c.dtype.is_floating_point or c.dim() != 1:
+            raise ValueError("constant_pose must be a [K] bool mask or a sequence of image indices")
+        if c.numel() and (int(c.min()) < 0 or int(c.max()) >= K):
+            raise ValueError(f"constant_pose names an image outside [0, {K})")
+        mask = torch.zeros(K, dtype=torch.bool)
+        mask[c.long()] = True
+        c = mask
+    if tuple(c.shape) != (K,):
+        raise ValueError(f"constant_pose must have shape [{K}], got {tuple(c.shape)}")
+    if not bool(c.any()):
+        raise ValueError("constant_pose holds no image: nothing fixes the gauge (hold at least one pose; two fix scale as well)")
+    return c
+
+
+class BundleAdjuster(nn.Module):
+    """num_iterations: the fixed budget of Levenberg-Marquardt iterations, in [1, 100].  initial_damping: lambda of the first iteration.  function_tolerance:
+    the call converges after a trial with |cost - cost_new| <= function_tolerance cost.  At least one image must be held constant; two constant images fix the
+    scale of the reconstruction, with one the damping holds it (it may drift slowly)."""
+
+    def __init__(self, num_iterations: int = 10, initial_damping: float = 1e-4, function_tolerance: float = 1e-6):
+        super().__init__()
+        if int(num_iterations) != num_iterations or not 1 <= int(num_iterations) <= _cabi.LG_BA_MAX_ITERATIONS:
+            raise ValueError(f"num_iterations must be an integer in [1, {_cabi.LG_BA_MAX_ITERATIONS}], got {num_iterations!r}")
+        if not 0.0 < float(initial_damping) < float("inf"):
+            raise ValueError(f"initial_damping must be > 0, got {initial_damping!r}")
+        if not 0.0 < float(function_tolerance) < float("inf"):
+            raise ValueError(f"function_tolerance must be > 0, got {function_tolerance!r}")
+        self.num_iterations, self.initial_damping, self.function_tolerance = int(num_iterations), float(initial_damping), float(function_tolerance)
+
+    @torch.no_grad()
+    def adjust(self, feats: dict, tracks, cameras, poses, constant_pose) -> dict:
+        """feats = {keypoints [K, N, 2], num_keypoints [K] (optional)}: the store the tracks were built over; `tracks`: `Triangulator`'s dict or
+        (track_id [K, N], xyz [T, 3]); cameras [K, 4] (fx, fy, cx, cy) or [K, 3, 3]; poses [K, 3, 4] (R | t) or (R [K, 3, 3], t [K, 3]); constant_pose: a [K]
+        bool mask or the indices of the images whose pose is held fixed (at least one: ValueError otherwise; two fix scale).  Returns poses [K, 3, 4], xyz
+        [T, 3], points3d [K, N, 3] (NaN where a row is no active observation), node_state [K, N] uint8 (`STATES`), observation_error [K, N] (pixels, NaN where
+        not active), initial_cost, final_cost, num_iterations (run), num_accepted, converged, num_observations, status [K].  ONE host synchronisation.  An
+        image whose camera or pose fails the camera rule raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else."""
+        device = feats["keypoints"].device
+        s = _call.build_side(feats, device, "feats")
+        K, N = int(s.K), int(s.N)
+        const = as_constant(constant_pose, K)
+        tid, xyz = as_tracks(tracks, K, N, device)
+        cam, pose = as_cameras(cameras, K, device, "cameras"), as_poses(poses, K, device)
+        _call.require_gpu(device, "keypoints")          # behind every shape check: those need no device
+        T = int(xyz.shape[0])
+        const = const.to(device=device, dtype=torch.uint8)
+        poses_out = torch.empty((K, 3, 4), device=device, dtype=torch.float32)
+        xyz_out = torch.empty((T, 3), device=device, dtype=torch.float32)
+        pts = torch.empty((K, N, 3), device=device, dtype=torch.float32)
+        state = torch.empty((K, N), device=device, dtype=torch.uint8)
+        err = torch.empty((K, N), device=device, dtype=torch.float32)
+        small = torch.zeros((16 + K,), device=device, dtype=torch.int32)          # summary [8] fp64 | status [K]
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            lib = _cabi.load()
+            nbytes = lib.lg_bundle_workspace_bytes(K, N, T, 0)                    # -1: outside the envelope — lg_bundle_adjust below says why
+            ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
+            p = _call._ptr
+            io = _cabi.LgBundleIO(
+                n=N, images=K, tracks=T, flags=0, num_iterations=self.num_iterations, initial_damping=self.initial_damping,
+                function_tolerance=self.function_tolerance, kpts=p(s.kpts), num=p(s.num), track_id=p(tid), xyz=p(xyz), cameras=p(cam), poses=p(pose),
+                constant_pose=p(const), workspace=p(ws), workspace_bytes=max(nbytes, 0), poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
+                node_state=p(state), observation_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 64)
+            _cabi.check(lib.lg_bundle_adjust(C.byref(io), C.c_void_p(stream.cuda_stream)))
+            host = small.cpu().numpy()                # THE host sync of the call
+        summary, status = host[:16].view(np.float64), host[16:]
+        out = {"poses": poses_out, "xyz": xyz_out, "points3d": pts, "node_state": state, "observation_error": err,
+               "initial_cost": float(summary[0]), "final_cost": float(summary[1]), "num_iterations": int(summary[2]), "num_accepted": int(summary[3]),
+               "converged": bool(summary[4]), "num_observations": int(summary[5]), "status": small[16:]}
+        bad = [k for k, c in enumerate(status.tolist()) if c != _cabi.LG_OK]
+        if bad:          # every other image is complete: the error carries the call's outputs
+            error = _cabi.LightGlueAmdError("; ".join(f"image {k}: a camera whose focal length is not finite and > 0, whose principal point is not finite, or a "
+                                                      f"non-finite pose (LG_ERR_CAMERA): its observations were left out" for k in bad[:8]))
+            error.outputs = out
+            raise error
+        return out
+
+    forward = adjust

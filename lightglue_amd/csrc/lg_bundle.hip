@@ -1,0 +1,725 @@
+// lightglue_amd — bundle adjustment of poses and points (lg_bundle_adjust; the definition is in include/lightglue_amd.h).  Launches per call:
+//   ba_init       one lane per image and track: the image's record, its pose widened, its status; the track's counters cleared, its point widened;
+//   ba_count      one lane per node: its state (0, 2, 3, 4) or "candidate", the candidates of every track counted by integer atomicAdd;
+//   ba_scan       ONE workgroup: an exclusive scan over the tracks gives every adjusted track the offset of its list;
+//   ba_fill       one lane per node: states 5 / 6, or a place in the track's list by atomicAdd on its cursor (arrival order is arbitrary), the image's count;
+//   ba_sort       one lane per track: the list put into ascending node order (what the atomics left is gone), the image of every entry;
+//   ba_cost + ba_decide   the cost of the input;
+//   per iteration: ba_points, ba_reduce, ba_cholesky_diag + ba_cholesky_rows once per panel, ba_backsolve, ba_trial_points, ba_cost, ba_decide;
+//   ba_scatter    one lane per node, track and image: the outputs.
+// No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
+// other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
+// No floating-point atomics: every sum runs in the fixed order the header names.  Small matrices are indexed statically (no scratch: profiles/bundle_adjust.md).
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "lg_host_call.h"
+#include "lg_kernels.h"
+#include "lg_solve3.h"
+#include "../../include/lightglue_amd.h"
+
+#pragma clang fp contract(off)
+
+namespace lg {
+
+constexpr int BA_THREADS = 256, BA_SCAN_THREADS = 1024, BA_SCAN_WAVES = BA_SCAN_THREADS / 64;
+constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK, BA_KT = 32;      // Cholesky: columns per panel = rows per tile, columns of earlier panels per LDS chunk
+constexpr int BA_TILE = 32, BA_BCHUNK = 6;                   // reduce: rows of image a per LDS tile, column blocks b per workgroup (6 x 36 = 216 threads)
+constexpr int BA_PARTS = 5;                                  // back substitution: interleaved partial sums over the rows below a panel
+
+struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, pad0, pad1; };
+static_assert(sizeof(BaHead) <= 256, "the record of the call is 256 bytes");
+struct BaImage { double cam[4]; int ok, constant, nact, pad; double pad2[2]; };
+static_assert(sizeof(BaImage) == 64, "lg_bundle_workspace_bytes counts 64 bytes");
+
+struct BaArgs {
+    int n, images, nodes, tracks, dim;
+    double lambda0, ftol;
+    const float* kpts; const int* num; const long long* track_id; const float* xyz; const float* cameras; const float* poses; const unsigned char* constant;
+    BaHead* head; BaImage* rec; double* pose; double* delta; double* icost; double* S;         // pose [2][images][12], S [dim + 1][dim]
+    int* list; int* limg; int* tcnt; int* toff; int* tcur; double* X; double* Vinv; double* y;  // X [2][tracks][3]
+    float* poses_out; float* xyz_out; float* points3d; unsigned char* node_state; float* obs_err; double* summary; int* status;
+};
+
+__device__ __forceinline__ bool ba_adjusted(const BaArgs& a, int j) { const int c = a.tcnt[j]; return c >= 2 && c <= LG_BA_MAX_TRACK_LENGTH; }
+__device__ __forceinline__ bool ba_free(const BaArgs& a, int k) { const BaImage& im = a.rec[k]; return im.ok && !im.constant && im.nact > 0; }
+__device__ __forceinline__ const double* ba_pose(const BaArgs& a, int which, int k) { return a.pose + ((long long)which * a.images + k) * 12; }
+__device__ __forceinline__ const double* ba_point(const BaArgs& a, int which, int j) { return a.X + ((long long)which * a.tracks + j) * 3; }
+
+// p = R X + t of pose P [12] (R | t row-major 3 x 4)
+__device__ __forceinline__ void ba_project(const double* P, const double* X, double (&p)[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) p[r] = ((P[4 * r] * X[0] + P[4 * r + 1] * X[1]) + P[4 * r + 2] * X[2]) + P[4 * r + 3];
+}
+// the two rows of the pose Jacobian A (2 x 6) and of the point Jacobian B (2 x 3) at p
+__device__ __forceinline__ void ba_jacobians(const double* P, const double* cam, const double (&p)[3], double (&A0)[6], double (&A1)[6], double (&B0)[3], double (&B1)[3]) {
+    const double iz = 1.0 / p[2], fx = cam[0], fy = cam[1];
+    const double ax = fx * iz, az = -(((fx * p[0]) * iz) * iz), by = fy * iz, bz = -(((fy * p[1]) * iz) * iz);
+    A0[0] = az * p[1]; A0[1] = ax * p[2] - az * p[0]; A0[2] = -(ax * p[1]); A0[3] = ax; A0[4] = 0.0; A0[5] = az;
+    A1[0] = bz * p[1] - by * p[2]; A1[1] = -(bz * p[0]); A1[2] = by * p[0]; A1[3] = 0.0; A1[4] = by; A1[5] = bz;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { B0[e] = ax * P[e] + az * P[8 + e]; B1[e] = by * P[4 + e] + bz * P[8 + e]; }
+}
+__device__ __forceinline__ void ba_residual(const double* cam, const double (&p)[3], const float* kp, double& rx, double& ry) {
+    const double iz = 1.0 / p[2];
+    rx = ((cam[0] * p[0]) * iz + cam[2]) - (double)kp[0]; ry = ((cam[1] * p[1]) * iz + cam[3]) - (double)kp[1];
+}
+__device__ __forceinline__ double ba_damped(double d, double lambda) { return d + lambda * fmin(fmax(d, 1e-6), 1e32); }
+
+// ------------------------------------------------------------------ records
+__global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
+    const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
+    if (g == 0) { BaHead h{}; h.lambda = a.lambda0; *a.head = h; }
+    if (g < a.images) {
+        const int k = (int)g;
+        const float* c = a.cameras + (long long)k * 4;
+        const float* p = a.poses + (long long)k * 12;
+        bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) ok = ok && isfinite(p[e]);
+        BaImage im{};
+        im.ok = ok ? 1 : 0; im.constant = a.constant[k] ? 1 : 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) im.cam[e] = (double)c[e];
+        a.rec[k] = im;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            const double v = ok ? (double)p[e] : 0.0;
+            a.pose[(long long)k * 12 + e] = v; a.pose[((long long)a.images + k) * 12 + e] = v;
+        }
+#pragma unroll
+        for (int e = 0; e < 6; ++e) a.delta[(long long)k * 6 + e] = 0.0;
+        a.icost[k] = 0.0;
+        a.status[k] = ok ? LG_OK : LG_ERR_CAMERA;
+    }
+    if (g < a.tracks) {
+        a.tcnt[g] = 0; a.tcur[g] = 0; a.toff[g] = 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { const double v = (double)a.xyz[g * 3 + e]; a.X[g * 3 + e] = v; a.X[((long long)a.tracks + g) * 3 + e] = v; }
+    }
+}
+
+// ------------------------------------------------------------------ candidates
+__global__ __launch_bounds__(BA_THREADS) void ba_count_kernel(BaArgs a) {
+    const int v = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (v >= a.nodes) return;
+    const int k = v / a.n, i = v - k * a.n;
+    int state = 0;
+    const long long j = a.track_id[v];
+    if (i < live_rows(a.num, k, a.n) && j >= 0 && j < a.tracks) {
+        const double* X = ba_point(a, 0, (int)j);
+        if (!a.rec[k].ok) state = 2;
+        else if (!(isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]))) state = 3;
+        else {
+            double p[3];
+            ba_project(ba_pose(a, 0, k), X, p);
+            state = p[2] > 0.0 ? 1 : 4;
+        }
+        if (state == 1) atomicAdd(a.tcnt + j, 1);
+    }
+    a.node_state[v] = (unsigned char)state;
+}
+
+// ONE workgroup: the exclusive scan of the adjusted tracks' counts (integers: the order of the additions changes nothing)
+__global__ __launch_bounds__(BA_SCAN_THREADS) void ba_scan_kernel(BaArgs a) {
+    __shared__ int sh[BA_SCAN_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int share = (a.tracks + BA_SCAN_THREADS - 1) / BA_SCAN_THREADS;
+    const int beg = min((int)threadIdx.x * share, a.tracks), end = min(beg + share, a.tracks);
+    int mine = 0;
+    for (int j = beg; j < end; ++j) if (ba_adjusted(a, j)) mine += a.tcnt[j];
+    int inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+    if (lane == 63) sh[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += sh[w];
+    int at = base + inc - mine;                            // the sum of all counts is at most nodes: every node is counted once
+    for (int j = beg; j < end; ++j) if (ba_adjusted(a, j)) { a.toff[j] = at; at += a.tcnt[j]; }
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_fill_kernel(BaArgs a) {
+    const int v = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (v >= a.nodes) return;
+    if (a.node_state[v] != 1) return;
+    const int j = (int)a.track_id[v], cnt = a.tcnt[j];     // a candidate: 0 <= j < tracks
+    if (cnt < 2) { a.node_state[v] = 5; return; }
+    if (cnt > LG_BA_MAX_TRACK_LENGTH) { a.node_state[v] = 6; return; }
+    const int at = atomicAdd(a.tcur + j, 1);
+    if (at < cnt) a.list[a.toff[j] + at] = v;              // always: cnt candidates carry this track; toff + cnt <= nodes
+    atomicAdd(&a.rec[v / a.n].nact, 1);
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_sort_kernel(BaArgs a) {
+    const int j = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (j >= a.tracks || !ba_adjusted(a, j)) return;
+    const int len = a.tcnt[j];
+    int* lst = a.list + a.toff[j];
+    for (int q = 1; q < len; ++q) {                        // ascending node order, whatever order the atomics left; len <= 1024
+        const int key = lst[q];
+        int r = q - 1;
+        while (r >= 0 && lst[r] > key) { lst[r + 1] = lst[r]; --r; }
+        lst[r + 1] = key;
+    }
+    int* img = a.limg + a.toff[j];
+    for (int q = 0; q < len; ++q) img[q] = lst[q] / a.n;
+}
+
+// ------------------------------------------------------------------ the cost of a state: one workgroup per image, rows in ascending order
+// trial = 0: the accepted state (the input); 1: the trial.  A row with pz <= 0 or a non-finite term fails the trial
+__global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgs a, int trial) {
+    __shared__ double term[BA_THREADS];
+    if (trial && a.head->converged) return;
+    const int k = blockIdx.x, which = a.head->sel ^ trial;
+    const double* P = ba_pose(a, which, k);
+    const double* cam = a.rec[k].cam;
+    double sum = 0.0;
+    int bad = 0;
+    for (int i0 = 0; i0 < a.n; i0 += BA_THREADS) {
+        const int i = i0 + threadIdx.x;
+        double c = 0.0;
+        if (i < a.n && a.node_state[(long long)k * a.n + i] == 1) {
+            const long long v = (long long)k * a.n + i;
+            double p[3], rx, ry;
+            ba_project(P, ba_point(a, which, (int)a.track_id[v]), p);
+            ba_residual(cam, p, a.kpts + v * 2, rx, ry);
+            c = rx * rx + ry * ry;
+            if (!(p[2] > 0.0) || !isfinite(c)) { bad = 1; c = 0.0; }
+        }
+        __syncthreads();
+        term[threadIdx.x] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = min(BA_THREADS, a.n - i0);
+            for (int q = 0; q < m; ++q) sum += term[q];
+        }
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        a.icost[k] = sum;
+        if (bad) atomicOr(&a.head->fail, 1);
+    }
+}
+
+// one lane: the images' costs in ascending order, the decision, lambda, the counters
+__global__ void ba_decide_kernel(BaArgs a, int initial) {
+    if (blockIdx.x || threadIdx.x) return;
+    BaHead& h = *a.head;
+    if (!initial && h.converged) return;
+    double sum = 0.0;
+    for (int k = 0; k < a.images; ++k) sum += a.icost[k];
+    if (initial) {
+        int nobs = 0;
+        for (int k = 0; k < a.images; ++k) nobs += a.rec[k].nact;
+        h.cost = sum; h.initial_cost = sum; h.nobs = nobs; h.fail = 0;
+        return;
+    }
+    h.cost_new = sum;
+    h.iters += 1;
+    const bool ok = !h.fail && isfinite(sum);
+    const bool conv = ok && fabs(h.cost - sum) <= a.ftol * h.cost, accept = ok && sum < h.cost;
+    if (accept) { h.cost = sum; h.sel ^= 1; h.accepted += 1; h.lambda = fmax(h.lambda / 10.0, 1e-12); }
+    else h.lambda = fmin(10.0 * h.lambda, 1e12);
+    if (conv) h.converged = 1;
+    h.fail = 0;
+}
+
+// ------------------------------------------------------------------ per iteration 1: one lane per track: V, g, the damped inverse, y
+__global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
+    if (a.head->converged) return;
+    const int j = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (j >= a.tracks || !ba_adjusted(a, j)) return;
+    const int s = a.head->sel, len = a.tcnt[j], off = a.toff[j];
+    const double lambda = a.head->lambda;
+    const double* Xp = ba_point(a, s, j);
+    const double X[3] = {Xp[0], Xp[1], Xp[2]};
+    double V[6] = {0, 0, 0, 0, 0, 0}, G[3] = {0, 0, 0};
+    for (int q = 0; q < len; ++q) {
+        const int v = a.list[off + q], k = a.limg[off + q];
+        const double* P = ba_pose(a, s, k);
+        const double* cam = a.rec[k].cam;
+        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+        ba_project(P, X, p);
+        ba_jacobians(P, cam, p, A0, A1, B0, B1);
+        ba_residual(cam, p, a.kpts + (long long)v * 2, rx, ry);
+        V[0] += B0[0] * B0[0] + B1[0] * B1[0]; V[1] += B0[0] * B0[1] + B1[0] * B1[1]; V[2] += B0[0] * B0[2] + B1[0] * B1[2];
+        V[3] += B0[1] * B0[1] + B1[1] * B1[1]; V[4] += B0[1] * B0[2] + B1[1] * B1[2]; V[5] += B0[2] * B0[2] + B1[2] * B1[2];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) G[e] += B0[e] * rx + B1[e] * ry;
+    }
+    V[0] = ba_damped(V[0], lambda); V[3] = ba_damped(V[3], lambda); V[5] = ba_damped(V[5], lambda);
+    double Vi[3][3];
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0};
+        double x[3];
+        ok = tri_solve3(V, e, x) && ok;
+        Vi[0][c] = x[0]; Vi[1][c] = x[1]; Vi[2][c] = x[2];
+    }
+    double* vo = a.Vinv + (long long)j * 9;
+    double* yo = a.y + (long long)j * 3;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vo[3 * r + c] = ok ? Vi[r][c] : 0.0;
+        yo[r] = ok ? (Vi[r][0] * G[0] + Vi[r][1] * G[1]) + Vi[r][2] * G[2] : 0.0;
+    }
+    if (!ok) atomicOr(&a.head->fail, 1);
+}
+
+// ------------------------------------------------------------------ per iteration 2: the block row of image a, BA_BCHUNK column blocks per workgroup
+// grid (images, ceil(images / BA_BCHUNK)).  Threads 0 .. 215: entry (r, c) of block (a, b); in the workgroup that holds the diagonal block, threads 216 .. 248:
+// the 21 entries of U_a's upper triangle, g_a (6), the sum of W y (6).  BA_TILE rows of image a at a time go through LDS in four steps: the first BA_TILE
+// threads stage a row each (Y, A, r, W y, X, the row's track list); all threads count the list's entries per column block (integer LDS atomics: a count has no
+// order); one thread per (row, column block) with an entry forms W_b once; then every entry thread adds its rows in ascending order
+__global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
+    __shared__ double sY[BA_TILE][18], sA[BA_TILE][12], sWy[BA_TILE][6], sX[BA_TILE][3], sR[BA_TILE][2], sW[BA_TILE][BA_BCHUNK][18], sU[33];
+    __shared__ int sOff[BA_TILE], sLen[BA_TILE], sCnt[BA_TILE][BA_BCHUNK];
+    if (a.head->converged) return;
+    const int ia = blockIdx.x, b0 = blockIdx.y * BA_BCHUNK, t = threadIdx.x, dim = a.dim;
+    if (b0 > ia) return;
+    const bool diag = ia / BA_BCHUNK == (int)blockIdx.y, free_a = ba_free(a, ia);
+    const int bl = t / 36, rc = t - bl * 36, r = rc / 6, c = rc - r * 6, ib = b0 + bl;
+    const bool entry = t < 36 * BA_BCHUNK && ib <= ia;      // ib <= ia < images
+    const int e = t - 36 * BA_BCHUNK;                       // 0 .. 32 in the diagonal workgroup: U (21), g (6), W y (6)
+    const bool extra = diag && e >= 0 && e < 33;
+    double* out = a.S + ((long long)(6 * ia + r) * dim + 6 * ib + c);
+    if (!free_a) {                                          // the image's columns drop out: identity, zero coupling, zero right-hand side
+        if (entry) *out = (ib == ia && r == c) ? 1.0 : 0.0;
+        if (extra && e >= 27) a.S[(long long)dim * dim + 6 * ia + (e - 27)] = 0.0;
+        return;
+    }
+    const int s = a.head->sel;
+    const double lambda = a.head->lambda;
+    const bool free_b = entry && ba_free(a, ib);
+    // the thread's (row, column block) item of a tile, and the pose of that block's image
+    const int iq = t / BA_BCHUNK, ibl = t - iq * BA_BCHUNK, item_b = b0 + ibl;
+    const bool item = t < BA_TILE * BA_BCHUNK, item_free = item && item_b <= ia && ba_free(a, item_b);
+    double Pb[12], fb[2] = {0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 12; ++q) Pb[q] = item_free ? ba_pose(a, s, item_b)[q] : 0.0;
+    if (item_free) { fb[0] = a.rec[item_b].cam[0]; fb[1] = a.rec[item_b].cam[1]; }
+    const int cq = t >> 3, part = t & 7;                    // counting: 8 threads per row of the tile
+    static_assert(BA_THREADS == 8 * BA_TILE && BA_TILE * BA_BCHUNK <= BA_THREADS, "8 counting threads and BA_BCHUNK items per tile row");
+    // U's upper triangle in row-major order: entry e -> (ur, uc)
+    int ur = 0, uc = 0;
+    if (extra && e < 21) { int left = e; while (left >= 6 - ur) { left -= 6 - ur; ++ur; } uc = ur + left; }
+    const double* Pa = ba_pose(a, s, ia);
+    const double* cama = a.rec[ia].cam;
+    double acc = 0.0;
+    for (int i0 = 0; i0 < a.n; i0 += BA_TILE) {
+        __syncthreads();                                    // the previous tile has been read
+        if (t < BA_TILE) {
+            const int i = i0 + t;
+            const long long v = (long long)ia * a.n + i;
+            int len = 0;
+            if (i < a.n && a.node_state[v] == 1) {
+                const int j = (int)a.track_id[v];
+                len = a.tcnt[j]; sOff[t] = a.toff[j];
+                const double* Xp = ba_point(a, s, j);
+                const double* Vi = a.Vinv + (long long)j * 9;
+                const double* y = a.y + (long long)j * 3;
+                double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+                ba_project(Pa, Xp, p);
+                ba_jacobians(Pa, cama, p, A0, A1, B0, B1);
+                ba_residual(cama, p, a.kpts + v * 2, rx, ry);
+                sX[t][0] = Xp[0]; sX[t][1] = Xp[1]; sX[t][2] = Xp[2];
+                sR[t][0] = rx; sR[t][1] = ry;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    sA[t][q] = A0[q]; sA[t][6 + q] = A1[q];
+                    const double w0 = A0[q] * B0[0] + A1[q] * B1[0], w1 = A0[q] * B0[1] + A1[q] * B1[1], w2 = A0[q] * B0[2] + A1[q] * B1[2];
+#pragma unroll
+                    for (int m = 0; m < 3; ++m) sY[t][3 * q + m] = (w0 * Vi[m] + w1 * Vi[3 + m]) + w2 * Vi[6 + m];
+                    sWy[t][q] = (w0 * y[0] + w1 * y[1]) + w2 * y[2];
+                }
+            }
+            sLen[t] = len;
+        }
+        if (item) sCnt[iq][ibl] = 0;
+        __syncthreads();
+        {
+            const int len = sLen[cq], off = sOff[cq];
+            for (int l = part; l < len; l += 8) {
+                const int d = a.limg[off + l] - b0;
+                if (d >= 0 && d < BA_BCHUNK && b0 + d <= ia) atomicAdd(&sCnt[cq][d], 1);
+            }
+        }
+        __syncthreads();
+        if (item_free && sCnt[iq][ibl] > 0) {               // W of (image item_b, the row's track): it does not depend on the observation's row in b
+            double p[3], A0[6], A1[6], B0[3], B1[3];
+            ba_project(Pb, sX[iq], p);
+            ba_jacobians(Pb, fb, p, A0, A1, B0, B1);
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+                for (int m = 0; m < 3; ++m) sW[iq][ibl][3 * q + m] = A0[q] * B0[m] + A1[q] * B1[m];
+        }
+        __syncthreads();
+        const int rows = min(BA_TILE, a.n - i0);
+        if (free_b) {
+            for (int q = 0; q < rows; ++q) {
+                const int times = sCnt[q][bl];              // the observations of the row's track in image b, in order: the same W each
+                if (!times) continue;
+                const double term = (sY[q][3 * r] * sW[q][bl][3 * c] + sY[q][3 * r + 1] * sW[q][bl][3 * c + 1]) + sY[q][3 * r + 2] * sW[q][bl][3 * c + 2];
+                for (int m = 0; m < times; ++m) acc += term;
+            }
+        } else if (extra) {
+            for (int q = 0; q < rows; ++q) {
+                if (!sLen[q]) continue;
+                if (e < 21) acc += sA[q][ur] * sA[q][uc] + sA[q][6 + ur] * sA[q][6 + uc];
+                else if (e < 27) acc += sA[q][e - 21] * sR[q][0] + sA[q][6 + e - 21] * sR[q][1];
+                else acc += sWy[q][e - 27];
+            }
+        }
+    }
+    if (extra) sU[e] = acc;
+    __syncthreads();
+    if (entry) {
+        double val = free_b ? -acc : 0.0;
+        if (ib == ia) {                                     // the diagonal block: U' - E (this workgroup is the diagonal one, sU is its own)
+            const int lo = min(r, c), hi = max(r, c);
+            double u = sU[lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
+            if (r == c) u = ba_damped(u, lambda);
+            val = u - acc;
+        }
+        *out = val;
+    }
+    if (extra && e >= 27) a.S[(long long)dim * dim + 6 * ia + (e - 27)] = acc - sU[e - 6];      // (sum of W y) - g
+}
+
+// ------------------------------------------------------------------ per iteration 3: panel p of the left-looking blocked Cholesky, the right-hand side as row dim
+// Two launches per panel, so that no workgroup reads what another workgroup of its launch writes.  Thread (tr, tc) of the 16 x 16 grid holds entries
+// (tr + 16 ii, tc + 16 jj), ii, jj < 3, of a BA_NB x BA_NB block.
+// 3a. ONE workgroup: the panel's diagonal block D = S_pp - L_p L_p^T over all earlier columns, factored in LDS and written over S_pp
+__global__ __launch_bounds__(BA_THREADS) void ba_cholesky_diag_kernel(BaArgs a, int panel) {
+    __shared__ double Bs[BA_NB][BA_KT + 1], Dm[BA_NB][BA_NB + 1];
+    if (a.head->converged) return;
+    const int dim = a.dim, t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0);            // the panel's columns [C0, C0 + nb)
+    double* S = a.S;
+    double acc[3][3];
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) acc[ii][jj] = 0.0;
+    for (int k0 = 0; k0 < C0; k0 += BA_KT) {                            // C0 is a multiple of BA_NB; the last chunk may be short
+        const int kt = min(BA_KT, C0 - k0);
+        __syncthreads();
+        for (int q = t; q < BA_NB * BA_KT; q += BA_THREADS) {
+            const int row = q / BA_KT, kk = q - row * BA_KT;
+            Bs[row][kk] = (row < nb && kk < kt) ? S[(long long)(C0 + row) * dim + k0 + kk] : 0.0;
+        }
+        __syncthreads();
+        for (int kk = 0; kk < kt; ++kk) {
+            double bv[3], dv[3];
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii) { dv[ii] = Bs[tr + 16 * ii][kk]; bv[ii] = Bs[tc + 16 * ii][kk]; }
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+                for (int jj = 0; jj < 3; ++jj) acc[ii][jj] += dv[ii] * bv[jj];
+        }
+    }
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) {
+            const int row = tr + 16 * ii, col = tc + 16 * jj;
+            Dm[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] - acc[ii][jj] : 0.0;
+        }
+    __syncthreads();
+    // right-looking inside the block: column kk scaled, then the columns to its right updated
+    for (int kk = 0; kk < nb; ++kk) {
+        double d = Dm[kk][kk];
+        const bool good = d > 0.0 && isfinite(d);
+        if (!good) d = 1.0;
+        const double l = sqrt(d);
+        __syncthreads();
+        if (t == 0) { Dm[kk][kk] = l; if (!good) atomicOr(&a.head->fail, 1); }
+        if (t > kk && t < nb) Dm[t][kk] = Dm[t][kk] / l;
+        __syncthreads();
+        for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
+            const int row = q / BA_NB, col = q - row * BA_NB;
+            if (col > kk && col <= row && row < nb) Dm[row][col] = Dm[row][col] - Dm[row][kk] * Dm[col][kk];
+        }
+        __syncthreads();
+    }
+    for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
+        const int row = q / BA_NB, col = q - row * BA_NB;
+        if (row < nb && col <= row) S[(long long)(C0 + row) * dim + C0 + col] = Dm[row][col];
+    }
+}
+
+// 3b. one workgroup per BA_NB-row tile that has rows below the diagonal block: G = S_ip - L_i L_p^T, then L_i = G L_pp^-T.  It reads the panel's rows (earlier
+// columns and L_pp: finished by earlier launches) and its own rows; it writes its own rows' panel columns, which no other workgroup of the launch reads
+__global__ __launch_bounds__(BA_THREADS) void ba_cholesky_rows_kernel(BaArgs a, int panel) {
+    __shared__ double As[BA_NB][BA_KT + 1], Bs[BA_NB][BA_KT + 1], Lp[BA_NB][BA_NB + 1], Gm[BA_NB][BA_NB + 1];
+    if (a.head->converged) return;
+    const int dim = a.dim, t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0);            // the panel's columns [C0, C0 + nb)
+    const int tile = panel + blockIdx.x, R0 = tile * BA_NB, nr = min(BA_NB, dim + 1 - R0);      // this workgroup's rows [R0, R0 + nr), nr >= 1
+    if (R0 + nr <= C0 + nb) return;                                     // the diagonal tile without the right-hand side's row: nothing below the block
+    double* S = a.S;
+    double acc[3][3];
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) acc[ii][jj] = 0.0;
+    for (int k0 = 0; k0 < C0; k0 += BA_KT) {
+        const int kt = min(BA_KT, C0 - k0);
+        __syncthreads();
+        for (int q = t; q < BA_NB * BA_KT; q += BA_THREADS) {
+            const int row = q / BA_KT, kk = q - row * BA_KT;
+            As[row][kk] = (row < nr && R0 + row >= C0 + nb && kk < kt) ? S[(long long)(R0 + row) * dim + k0 + kk] : 0.0;
+            Bs[row][kk] = (row < nb && kk < kt) ? S[(long long)(C0 + row) * dim + k0 + kk] : 0.0;
+        }
+        __syncthreads();
+        for (int kk = 0; kk < kt; ++kk) {
+            double av[3], bv[3];
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii) { av[ii] = As[tr + 16 * ii][kk]; bv[ii] = Bs[tc + 16 * ii][kk]; }
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+                for (int jj = 0; jj < 3; ++jj) acc[ii][jj] += av[ii] * bv[jj];
+        }
+    }
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) {
+            const int row = tr + 16 * ii, col = tc + 16 * jj;
+            Gm[row][col] = (row < nr && col < nb && R0 + row >= C0 + nb) ? S[(long long)(R0 + row) * dim + C0 + col] - acc[ii][jj] : 0.0;
+            Lp[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] : 0.0;
+        }
+    __syncthreads();
+    // one lane per row, columns in ascending order
+    if (t < nr && R0 + t >= C0 + nb) {
+        for (int col = 0; col < nb; ++col) {
+            double v = Gm[t][col];
+            for (int kk = 0; kk < col; ++kk) v = v - Gm[t][kk] * Lp[col][kk];
+            v = v / Lp[col][col];
+            Gm[t][col] = v;
+            S[(long long)(R0 + t) * dim + C0 + col] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ per iteration 4: ONE workgroup: L^T s = z backwards, the trial poses
+__global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
+    __shared__ double sd[6 * LG_BA_MAX_IMAGES], part[BA_PARTS][BA_NB], Lp[BA_NB][BA_NB + 1];
+    if (a.head->converged) return;
+    const int dim = a.dim, t = threadIdx.x;
+    const double* S = a.S;
+    const double* z = S + (long long)dim * dim;
+    const int panels = (dim + BA_NB - 1) / BA_NB;
+    for (int panel = panels - 1; panel >= 0; --panel) {
+        const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0), below = C0 + nb;
+        if (t < BA_PARTS * BA_NB) {
+            const int col = t % BA_NB, part_id = t / BA_NB;
+            double sum = 0.0;
+            if (col < nb) for (int i = below + part_id; i < dim; i += BA_PARTS) sum += S[(long long)i * dim + C0 + col] * sd[i];
+            part[part_id][col] = sum;
+        }
+        for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
+            const int row = q / BA_NB, col = q - row * BA_NB;
+            Lp[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] : 0.0;
+        }
+        __syncthreads();
+        if (t == 0)
+            for (int col = nb - 1; col >= 0; --col) {
+                double v = z[C0 + col] - ((((part[0][col] + part[1][col]) + part[2][col]) + part[3][col]) + part[4][col]);
+                for (int i = col + 1; i < nb; ++i) v = v - Lp[i][col] * sd[C0 + i];
+                sd[C0 + col] = v / Lp[col][col];
+            }
+        __syncthreads();
+    }
+    const int s = a.head->sel;
+    int bad = 0;
+    for (int k = t; k < a.images; k += BA_THREADS) {
+        const double* P = ba_pose(a, s, k);
+        double* out = a.pose + ((long long)(s ^ 1) * a.images + k) * 12;
+        if (!ba_free(a, k)) {
+            for (int q = 0; q < 12; ++q) out[q] = P[q];
+            for (int q = 0; q < 6; ++q) a.delta[k * 6 + q] = 0.0;
+            continue;
+        }
+        double x[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) { x[q] = sd[6 * k + q]; a.delta[k * 6 + q] = x[q]; }
+        // Rodrigues(w) = I + sin(th) [k]x + (1 - cos(th)) [k]x^2, k = w / th
+        const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+        double Q[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        if (th > 0.0) {
+            const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th, sn = sin(th), c1 = 1.0 - cos(th);
+            const double Kx[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const double kk = (Kx[3 * i] * Kx[j] + Kx[3 * i + 1] * Kx[3 + j]) + Kx[3 * i + 2] * Kx[6 + j];
+                    Q[3 * i + j] = (Q[3 * i + j] + sn * Kx[3 * i + j]) + c1 * kk;
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double v = (Q[3 * i] * P[j] + Q[3 * i + 1] * P[4 + j]) + Q[3 * i + 2] * P[8 + j];
+                if (j == 3) v = v + x[3 + i];
+                if (!isfinite(v)) bad = 1;
+                out[4 * i + j] = v;
+            }
+    }
+    if (bad) atomicOr(&a.head->fail, 1);
+}
+
+// ------------------------------------------------------------------ per iteration 5: one lane per track: the point's step and its trial
+__global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
+    if (a.head->converged) return;
+    const int j = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (j >= a.tracks || !ba_adjusted(a, j)) return;
+    const int s = a.head->sel, len = a.tcnt[j], off = a.toff[j];
+    const double* Xp = ba_point(a, s, j);
+    const double X[3] = {Xp[0], Xp[1], Xp[2]};
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int q = 0; q < len; ++q) {
+        const int k = a.limg[off + q];
+        if (!ba_free(a, k)) continue;
+        const double* P = ba_pose(a, s, k);
+        const double* d = a.delta + (long long)k * 6;
+        double p[3], A0[6], A1[6], B0[3], B1[3];
+        ba_project(P, X, p);
+        ba_jacobians(P, a.rec[k].cam, p, A0, A1, B0, B1);
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            double w = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) w += (A0[r] * B0[m] + A1[r] * B1[m]) * d[r];
+            acc[m] += w;
+        }
+    }
+    const double* Vi = a.Vinv + (long long)j * 9;
+    const double* y = a.y + (long long)j * 3;
+    double* out = a.X + ((long long)(s ^ 1) * a.tracks + j) * 3;
+    bool fin = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double v = X[r] - (y[r] + ((Vi[3 * r] * acc[0] + Vi[3 * r + 1] * acc[1]) + Vi[3 * r + 2] * acc[2]));
+        fin = fin && isfinite(v);
+        out[r] = v;
+    }
+    if (!fin) atomicOr(&a.head->fail, 1);
+}
+
+// ------------------------------------------------------------------ the outputs
+__global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgs a) {
+    const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
+    const BaHead h = *a.head;
+    const int s = h.sel;
+    if (g == 0) {
+        a.summary[0] = h.initial_cost; a.summary[1] = h.cost; a.summary[2] = (double)h.iters; a.summary[3] = (double)h.accepted;
+        a.summary[4] = (double)h.converged; a.summary[5] = (double)h.nobs; a.summary[6] = h.lambda; a.summary[7] = 0.0;
+    }
+    if (g < a.nodes) {
+        const int k = (int)(g / a.n);
+        float x = __builtin_nanf(""), y = x, z = x, err = x;
+        if (a.node_state[g] == 1) {
+            const double* X = ba_point(a, s, (int)a.track_id[g]);
+            double p[3], rx, ry;
+            ba_project(ba_pose(a, s, k), X, p);
+            ba_residual(a.rec[k].cam, p, a.kpts + g * 2, rx, ry);
+            x = (float)X[0]; y = (float)X[1]; z = (float)X[2]; err = (float)sqrt(rx * rx + ry * ry);
+        }
+        float* o = a.points3d + g * 3;
+        o[0] = x; o[1] = y; o[2] = z;
+        a.obs_err[g] = err;
+    }
+    if (g < a.tracks) {
+        const bool adj = ba_adjusted(a, (int)g);
+        const double* X = ba_point(a, s, (int)g);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) a.xyz_out[g * 3 + e] = adj ? (float)X[e] : a.xyz[g * 3 + e];
+    }
+    if (g < a.images) {
+        const bool fr = ba_free(a, (int)g);
+        const double* P = ba_pose(a, s, (int)g);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) a.poses_out[g * 12 + e] = fr ? (float)P[e] : a.poses[g * 12 + e];
+    }
+}
+
+}  // namespace lg
+
+using namespace lg;
+
+extern "C" {
+
+int64_t lg_bundle_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags) {
+    BaLayout L;
+    return ba_layout(images, n, tracks, flags, L) ? -1 : L.total;
+}
+
+int lg_bundle_adjust(const lg_bundle_io* io, void* hip_stream) {
+    if (!io) return set_error(LG_ERR_INVALID, "lg_bundle_adjust: null io");
+    BaLayout L;
+    if (const char* why = ba_layout(io->images, io->n, io->tracks, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_bundle_adjust: ") + why);
+    if (io->num_iterations < 1 || io->num_iterations > LG_BA_MAX_ITERATIONS)
+        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: num_iterations must lie in [1, LG_BA_MAX_ITERATIONS]");
+    if (!(io->initial_damping > 0.0) || !std::isfinite(io->initial_damping) || !(io->function_tolerance > 0.0) || !std::isfinite(io->function_tolerance))
+        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: initial_damping and function_tolerance must be > 0 (and finite)");
+    if (!io->cameras || !io->poses || !io->constant_pose || !io->poses_out || !io->summary || !io->status || (io->tracks && (!io->xyz || !io->xyz_out)) ||
+        (L.nodes && (!io->kpts || !io->track_id || !io->points3d || !io->node_state || !io->observation_error)))
+        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: null pointer among kpts, track_id, xyz, cameras, poses, constant_pose, poses_out, xyz_out, points3d, "
+                                         "node_state, observation_error, summary, status");
+    if (const int rc = check_workspace("lg_bundle_adjust", "lg_bundle_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    char* ws = static_cast<char*>(io->workspace);
+    BaArgs a{};
+    a.n = io->n; a.images = io->images; a.nodes = (int)L.nodes; a.tracks = io->tracks; a.dim = (int)L.dim;
+    a.lambda0 = io->initial_damping; a.ftol = io->function_tolerance;
+    a.kpts = io->kpts; a.num = io->num; a.track_id = reinterpret_cast<const long long*>(io->track_id); a.xyz = io->xyz; a.cameras = io->cameras; a.poses = io->poses;
+    a.constant = io->constant_pose;
+    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
+    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
+    a.head = reinterpret_cast<BaHead*>(ws + L.head); a.rec = reinterpret_cast<BaImage*>(ws + L.rec);
+    a.pose = f64(L.pose); a.delta = f64(L.delta); a.icost = f64(L.icost); a.S = f64(L.S);
+    a.list = ints(L.list); a.limg = ints(L.limg); a.tcnt = ints(L.tcnt); a.toff = ints(L.toff); a.tcur = ints(L.tcur);
+    a.X = f64(L.X); a.Vinv = f64(L.Vinv); a.y = f64(L.y);
+    a.poses_out = io->poses_out; a.xyz_out = io->xyz_out; a.points3d = io->points3d; a.node_state = io->node_state; a.obs_err = io->observation_error;
+    a.summary = io->summary; a.status = io->status;
+
+    auto blocks = [](long long items) { return dim3((unsigned)((items + BA_THREADS - 1) / BA_THREADS)); };
+    const dim3 th(BA_THREADS);
+    const int K = io->images, T = io->tracks;
+    const int panels = ((int)L.dim + BA_NB - 1) / BA_NB, tiles = ((int)L.dim + 1 + BA_NB - 1) / BA_NB;
+    hipLaunchKernelGGL(ba_init_kernel, blocks(std::max<long long>(K, T)), th, 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(ba_count_kernel, blocks(L.nodes), th, 0, s, a);
+    if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
+    if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
+    hipLaunchKernelGGL(ba_cost_kernel, dim3(K), th, 0, s, a, 0);
+    hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 1);
+    for (int it = 0; it < io->num_iterations; ++it) {
+        if (T) hipLaunchKernelGGL(ba_points_kernel, blocks(T), th, 0, s, a);
+        hipLaunchKernelGGL(ba_reduce_kernel, dim3(K, (K + BA_BCHUNK - 1) / BA_BCHUNK), th, 0, s, a);
+        for (int p = 0; p < panels; ++p) {
+            hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, a, p);
+            hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, a, p);
+        }
+        hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
+        if (T) hipLaunchKernelGGL(ba_trial_points_kernel, blocks(T), th, 0, s, a);
+        hipLaunchKernelGGL(ba_cost_kernel, dim3(K), th, 0, s, a, 1);
+        hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 0);
+    }
+    hipLaunchKernelGGL(ba_scatter_kernel, blocks(std::max<long long>(std::max<long long>(L.nodes, T), K)), th, 0, s, a);
+    HIPCHK(hipGetLastError());
+    return LG_OK;
+}
+
+}  // extern "C"

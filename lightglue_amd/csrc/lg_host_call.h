@@ -112,6 +112,27 @@ inline const char* tri_layout(long long images, long long n, uint32_t flags, Tri
     L.croot = bp.take(L.tracks * 4); L.cstate = bp.take(L.tracks * 4); L.tid = bp.take(L.tracks * 4); L.cres = bp.take(L.tracks * 16); L.total = bp.used;
     return nullptr;
 }
+// lg_bundle_adjust: a 256-byte record of the call; per image a 64-byte record, the pose twice in fp64 (the state and the trial: 192 bytes), its step (48) and
+// its cost (8); the reduced camera system with its right-hand side as one more row ((6 images + 1) x 6 images fp64); per node its track-list entry and that
+// entry's image (8 bytes); per track three int32 (count, offset, cursor) and fifteen + three fp64 (the point twice, the inverse of its damped 3 x 3 block, that
+// inverse times its gradient: 156 bytes in all).  W is not stored: it is formed again from the pose and the point where it is needed
+constexpr uint32_t BA_KNOWN_FLAGS = 0u;
+struct BaLayout { long long nodes, dim, head, rec, pose, delta, icost, S, list, limg, tcnt, toff, tcur, X, Vinv, y, total; };
+inline const char* ba_layout(long long images, long long n, long long tracks, uint32_t flags, BaLayout& L) {
+    if (flags & ~BA_KNOWN_FLAGS) return "undefined flag bits (the bundle adjuster defines none)";
+    if (n < 0 || n > LG_MAX_KEYPOINTS) return "n must lie in [0, LG_MAX_KEYPOINTS]";
+    if (images < 1 || images > LG_BA_MAX_IMAGES) return "images must lie in [1, LG_BA_MAX_IMAGES]";
+    if (images * n > LG_MAX_ROWS) return "images x n must lie in [0, LG_MAX_ROWS]";
+    if (tracks < 0 || tracks > images * n / 2) return "tracks must lie in [0, images x n / 2]";
+    L.nodes = images * n; L.dim = 6 * images;
+    Bump bp;
+    L.head = bp.take(256); L.rec = bp.take(images * 64); L.pose = bp.take(images * 192); L.delta = bp.take(images * 48); L.icost = bp.take(images * 8);
+    L.S = bp.take((L.dim + 1) * L.dim * 8);
+    L.list = bp.take(L.nodes * 4); L.limg = bp.take(L.nodes * 4);
+    L.tcnt = bp.take(tracks * 4); L.toff = bp.take(tracks * 4); L.tcur = bp.take(tracks * 4);
+    L.X = bp.take(tracks * 48); L.Vinv = bp.take(tracks * 72); L.y = bp.take(tracks * 24); L.total = bp.used;
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

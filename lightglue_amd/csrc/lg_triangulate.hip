@@ -18,6 +18,7 @@
 
 #include "lg_host_call.h"
 #include "lg_kernels.h"
+#include "lg_solve3.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -25,7 +26,6 @@
 namespace lg {
 
 constexpr int TRI_THREADS = 256, TRI_SCAN_THREADS = 1024, TRI_GN_STEPS = 5;
-constexpr double TRI_EPS = 1e-12;
 
 struct TriImage { double R[9], t[3], c[3], cam[4]; int ok, pad; };                  // 160 bytes per image
 static_assert(sizeof(TriImage) == 160, "lg_triangulate_workspace_bytes counts 160 bytes");
@@ -188,34 +188,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_fill_kernel(TriArgs a) {
     if (at < len) a.list[a.off[r] + at] = v;               // always: cnt[r] nodes have this root
 }
 
-// ------------------------------------------------------------------ 6. one lane per component
-// M x = b for a symmetric 3 x 3 M given by its upper triangle; false on a pivot that is not above TRI_EPS times M's largest diagonal entry.  Static indices only
-__device__ __forceinline__ bool tri_solve3(const double (&s)[6], const double (&b)[3], double (&x)[3]) {
-    double M[3][4] = {{s[0], s[1], s[2], b[0]}, {s[1], s[3], s[4], b[1]}, {s[2], s[4], s[5], b[2]}};
-    const double bar = TRI_EPS * fmax(fmax(s[0], s[3]), s[5]);
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int r = c + 1; r < 3; ++r) {
-            const bool swap = fabs(M[r][c]) > fabs(M[c][c]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const double lo = M[c][j], hi = M[r][j]; M[c][j] = swap ? hi : lo; M[r][j] = swap ? lo : hi; }
-        }
-        ok = ok && fabs(M[c][c]) > bar;
-#pragma unroll
-        for (int r = c + 1; r < 3; ++r) {
-            const double f = M[r][c] / M[c][c];
-#pragma unroll
-            for (int j = c + 1; j < 4; ++j) M[r][j] = M[r][j] - f * M[c][j];
-        }
-    }
-    x[2] = M[2][3] / M[2][2];
-    x[1] = (M[1][3] - M[1][2] * x[2]) / M[1][1];
-    x[0] = ((M[0][3] - M[0][1] * x[1]) - M[0][2] * x[2]) / M[0][0];
-    return ok && isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
-}
-
+// ------------------------------------------------------------------ 6. one lane per component (the 3 x 3 elimination: lg_solve3.h)
 struct TriProj { double px, py, pz; };
 __device__ __forceinline__ TriProj tri_project(const TriImage& im, const double (&X)[3]) {
     return {((im.R[0] * X[0] + im.R[1] * X[1]) + im.R[2] * X[2]) + im.t[0], ((im.R[3] * X[0] + im.R[4] * X[1]) + im.R[5] * X[2]) + im.t[1],

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""`BundleAdjuster.adjust` (lg_bundle_adjust: records, track lists, then per iteration points / reduce / Cholesky panels / back substitution / trial points /
+trial cost / decide, and the scatter; one call, one host synchronisation) on the tracks `Triangulator` builds, next to that `triangulate` call and next to the
+float64 numpy definition on the host.
+
+Workload: tools/bench_triangulate.py's (K = 16 views x N = 2 048 keypoints of one point cloud, 120 exhaustive pairs matched by `NearestNeighborMatcher` and
+verified by `TwoViewVerifier`, triangulated under the poses the store was projected with).  The adjuster then gets the poses of images 2 .. K - 1 moved by about
+0.002 rad and 0.01 units (images 0 and 1 are held constant) and the triangulated points as they are.  Per iteration budget: the wall-clock ms of the call
+(synchronised before and after, one warm-up, the configurations visited in turn `--runs` times: median and range), the iterations run, the costs.  The host
+route is tests/bundle_oracle.py (float64, one thread) with `--host-iterations` iterations, timed once.  One JSON line.
+`--only-adjust`: one call and nothing else — the run to put under a kernel trace for the per-launch times.
+
+usage: bench_bundle_adjust.py [--images 16] [--kpts 2048] [--runs 5] [--host-iterations 2] [--only-adjust]"""
+import argparse
+import itertools
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests")); sys.path.insert(0, str(ROOT / "tools"))
+import bundle_oracle as B
+from abspose_oracle import rodrigues
+from bench_triangulate import CAMERA, replay
+from bench_verify_pairs import make_store, stats, timed
+from lightglue_amd import BundleAdjuster, NearestNeighborMatcher, Triangulator, TwoViewVerifier
+
+
+def moved_poses(poses, rot=0.002, shift=0.01, seed=1):
+    rng = np.random.default_rng(seed)
+    out = poses.astype(np.float64)
+    for k in range(2, len(out)):
+        Q = rodrigues(rot * rng.standard_normal(3) / np.sqrt(3))
+        R, c = out[k][:, :3], -out[k][:, :3].T @ out[k][:, 3]
+        c = c + shift * rng.standard_normal(3) / np.sqrt(3)
+        out[k] = np.concatenate([Q @ R, (-(Q @ R) @ c)[:, None]], 1)
+    return out.astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=16)
+    ap.add_argument("--kpts", type=int, default=2048)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--host-iterations", type=int, default=2, help="iterations of the numpy definition on the host (0: skip)")
+    ap.add_argument("--only-adjust", action="store_true", help="one call and nothing else: the run to put under a kernel trace")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_bundle_adjust.py measures on an MI355X; there is nothing to measure without one")
+    K = args.images
+    store = make_store(K, args.kpts)
+    poses_host, truth = replay(K, args.kpts)
+    pairs_dev = torch.tensor(list(itertools.combinations(range(K), 2)), device="cuda")
+    cameras = torch.tensor([CAMERA] * K, device="cuda")
+    raw = NearestNeighborMatcher(ratio_threshold=0.8).match_pairs(store, pairs_dev, validate=False)
+    verified = TwoViewVerifier(model="fundamental", threshold=3.0, num_hypotheses=1024, refine=True).verify_pairs(store, pairs_dev, raw, validate=False)
+    tri = Triangulator()
+    true_poses = torch.from_numpy(poses_host).cuda()
+    triangulate = lambda: tri.triangulate(store, pairs_dev, verified, cameras, true_poses, validate=False)
+    tracks = triangulate()
+    start = torch.from_numpy(moved_poses(poses_host)).cuda()
+    constant = [0, 1]
+    budgets = (1, 10)
+    runs = {n: (lambda n=n: BundleAdjuster(num_iterations=n).adjust(store, tracks, cameras, start, constant)) for n in budgets}
+    outs = {n: fn() for n, fn in runs.items()}                                   # warm-up of every timed shape
+    if args.only_adjust:
+        ms, out = timed(runs[10])
+        print(json.dumps({"num_iterations": out["num_iterations"], "ms": round(ms, 3)}), flush=True)
+        return
+    ms, tri_ms = {n: [] for n in runs}, []
+    for _ in range(args.runs):
+        tri_ms.append(timed(triangulate)[0])
+        for n in runs:                                                           # in turn, not back to back
+            ms[n].append(timed(runs[n])[0])
+    res = {"images": K, "kpts": args.kpts, "pairs": int(pairs_dev.shape[0]), "device": torch.cuda.get_device_name(0), "runs": args.runs,
+           "tracks": tracks["num_tracks"], "triangulate": stats(tri_ms), "adjust": []}
+    for n in runs:
+        o = outs[n]
+        d = (o["points3d"].double().cpu() - torch.from_numpy(truth)).norm(dim=-1)
+        d0 = (tracks["points3d"].double().cpu() - torch.from_numpy(truth)).norm(dim=-1)
+        res["adjust"].append({"budget": n, **stats(ms[n]), "iterations_run": o["num_iterations"], "accepted": o["num_accepted"], "converged": o["converged"],
+                              "observations": o["num_observations"], "initial_cost": round(o["initial_cost"], 3), "final_cost": round(o["final_cost"], 3),
+                              "median_distance_to_cloud_before": round(float(d0[torch.isfinite(d0)].median()), 5),
+                              "median_distance_to_cloud_after": round(float(d[torch.isfinite(d)].median()), 5)})
+    ten, one = res["adjust"][1], res["adjust"][0]
+    if ten["iterations_run"] > 1:
+        res["ms_per_iteration"] = round((ten["ms_median"] - one["ms_median"]) / (ten["iterations_run"] - 1), 3)
+    if args.host_iterations:
+        inp = dict(kpts=store["keypoints"].cpu().numpy(), num=None, track_id=tracks["track_id"].cpu().numpy(), xyz=tracks["xyz"].cpu().numpy(),
+                   cams=np.asarray([CAMERA] * K, np.float32), poses=start.cpu().numpy(), constant=np.arange(K) < 2)
+        t = time.perf_counter()
+        host = B.adjust(inp, num_iterations=args.host_iterations)
+        host_ms = (time.perf_counter() - t) * 1e3
+        dev = BundleAdjuster(num_iterations=args.host_iterations).adjust(store, tracks, cameras, start, constant)
+        res["host"] = {"threads": 1, "iterations": host["num_iterations"], "ms": round(host_ms, 1), "final_cost": round(host["final_cost"], 3),
+                       "device_final_cost_same_budget": round(dev["final_cost"], 3), "near_decisions": host["near"],
+                       "same_states_as_device": bool((torch.from_numpy(host["node_state"]) == dev["node_state"].cpu()).all())}
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
