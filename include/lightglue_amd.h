@@ -997,6 +997,89 @@ int64_t lg_bundle_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uin
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_bundle_adjust(const lg_bundle_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Global poses: one pose per image from the relative poses of a pair list (what lg_relpose_estimate returns), by rotation averaging over the view graph and
+ * position averaging along the pairs' translation directions, both robust to wrong pairs; the per-image poses are what lg_triangulate and lg_bundle_adjust
+ * take.  fp64 throughout, no fused multiply-add, dense Cholesky, one call and one host synchronisation.  Stateless.  The reference has no such step; this is
+ * the definition (tests/posegraph_oracle.py restates it in float64 numpy).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   inputs    pair p = (a, b) = pair_index[p]; rotations[p] = R_ab (row-major 3 x 3) and translations[p] = t_ab with X_b = R_ab X_a + t_ab, t_ab a direction
+ *             (any length > 0); weights[p]; num_inliers[p] if given.  All float32, widened; R_ab is NOT re-orthonormalised.  Angles of the io are degrees.
+ *   pair_state  0 used; 1 a or b outside [0, images) or a = b; 2 no model: an entry of R_ab not finite, an entry of R_ab^T R_ab further than 1e-3 from the
+ *             identity, det R_ab <= 0, t_ab not finite or |t_ab|^2 not > 0, the weight not finite and > 0, or num_inliers[p] < min_inliers; 3 outside the
+ *             origin's component; 4 rotation outlier; 5 touches an image without a position.  The first failing test in this order names the state; a pair
+ *             takes part in a step iff none of the tests before that step failed (4 and 5 still enter the rotations, 5 not the positions).
+ *   image_state  0 posed; 1 rotation only (in the origin's component, no position); 2 not connected to the origin.
+ *   adjacency  every pair that passes 1 and 2 is listed under both of its images; an image's list is in ascending (neighbour image, pair index) order and every
+ *             sum below over an image's pairs runs in that order.  A pair listed twice, in either direction, is two entries.
+ *   tree      level-synchronous breadth-first search from `origin` (level 0, rotation I): an image without a level takes as parent the neighbour ON THE CURRENT
+ *             LEVEL over its heaviest pair, the first such entry of its list on ties; R_i = R_ab R_a if it is the pair's b, R_ab^T R_b if it is its a.  The
+ *             images reached are the origin's component.
+ *   log       of M: v = (M21 - M12, M02 - M20, M10 - M01), tr = (M00 + M11) + M22, theta = atan2(|v| / 2, (tr - 1) / 2), omega = (theta / |v|) v; if
+ *             |v| < 1e-6: omega = v / 2, or 0 if tr < 0.  exp is the bundle adjuster's Rodrigues.
+ *   rotation averaging  num_iterations steps of reweighted Gauss-Newton.  Iteration it: per pair omega = log(R_b^T (R_ab R_a)), theta = |omega|,
+ *             w' = w / (1 + (theta / s)^2), s = rotation_scale max(1, 2^(n - 5 - it)).  System: images x images, row i: diagonal = sum of w' over i's list,
+ *             entry (i, j) = -(sum of w' over the entries with neighbour j), right-hand sides (three columns) = sum of +w' omega where i is the pair's b,
+ *             -w' omega where it is its a.  The origin and every image outside the component: identity row and column, zero right-hand side.  Solved by the
+ *             Cholesky below; R_i <- R_i exp(delta_i).  The stage ends after the update of an iteration with s = rotation_scale, every delta finite and
+ *             max |delta| < 1e-10.  Then rotation_error[p] = |omega| in degrees at the final rotations (NaN for states 1 .. 3); above max_rotation_error: 4.
+ *   direction  d_p = -R_b^T (t_ab / |t_ab|): from the centre of a to the centre of b, with the solved R_b.
+ *   baseline  the neighbour of `origin` over its heaviest pair of state 0 (to `baseline` if that is >= 0), the first such entry on ties; c_origin = 0,
+ *             c_baseline = d_p of that pair, or -d_p if the origin is its b.  No such pair: no positions (as after a failed pivot below; 0 iterations).
+ *   positions  which images get one: start with the component; repeat until nothing changes (all images at once per round): drop every image other than the
+ *             origin and the baseline that has state-0 pairs to fewer than two different images still there.  A state-0 pair with a dropped image: 5.
+ *   position averaging  num_iterations steps of reweighted least squares on the sum of w rho |(I - d d^T)(c_b - c_a)|^2 over the state-0 pairs.  Iteration 0:
+ *             rho = 1.  Later, with e = c_b - c_a of the previous iterate: rho = (1 / max(|e|^2, 1e-12)) / (1 + (phi / s)^2), phi = atan2(|e - (d . e) d|, d . e),
+ *             s = direction_scale max(1, 2^(n - 6 - it)).  System: 3 images x 3 images of 3 x 3 blocks M = (w rho)(I - d d^T): diagonal block = sum of M over
+ *             the image's list, block (i, j) = -(sum over the entries with neighbour j); the origin, the baseline and every image without a position:
+ *             identity rows and columns; the baseline's centre moves to the right-hand side (sum of M c_baseline over the entries with that neighbour).
+ *             The stage ends after an iteration with s = direction_scale, every step finite and max |c_new - c_old| < 1e-12.
+ *   Cholesky  the bundle adjuster's (48 columns per panel, right-hand sides as extra rows, the same order of every sum, the same substitution), except for
+ *             the pivot rule: a pivot fails unless it is finite and > 1e-10 x the diagonal entry it started from (a system that is singular in exact
+ *             arithmetic leaves rounding noise of either sign there: a sign test alone would decide by chance).  It goes on with 1 in its place.  A failed
+ *             pivot of ANY position iteration clears positions_ok: every image of the component is "rotation only".  (The rotation system of a connected
+ *             component with finite weights is positive definite; a failed pivot there is not reported.)
+ *   outputs   poses [images][12] (R | t) rounded to float32 once, t_i = -(R_i c_i) (each row (r0 c0 + r1 c1) + r2 c2): R NaN for state 2, t NaN for states
+ *             1 and 2; direction_error[p] = phi in degrees at the final centres for state 0 with positions_ok, else NaN;
+ *             summary [8] fp64: origin, baseline (-1: none), images posed, rotation iterations run, position iterations run, positions_ok, 0, 0.
+ *   Determinism: no floating-point atomics; every sum is a fixed function of the lists' order, so every output is the same bits from run to run, and under a
+ *             permutation of a pair list in which no image pair appears twice (then an image's list order does not depend on the pair indices).
+ * Workspace: lg_posegraph_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: a 256-byte record; 116 bytes per image; 52 bytes per
+ *   pair; the position system with its right-hand side row, (3 images + 1) x 3 images fp64 (4.7 MB at 256 images), every piece rounded up to 256 bytes.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): null io; any flag bit (none is defined); images outside [2, LG_BA_MAX_IMAGES]; pairs
+ *   outside [1, 2^20]; num_iterations outside [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]; origin outside [0, images); baseline neither -1 nor an image other
+ *   than origin; a scale or max_rotation_error not finite and > 0; a null required pointer (num_inliers may be NULL); a workspace too small or not aligned.
+ * Launches, none of which waits on another workgroup: clear, classify, scan, fill, sort (one lane per image), tree (ONE workgroup); per rotation iteration
+ *   assemble (one workgroup per image row), two per Cholesky panel, update (ONE workgroup); select (ONE workgroup); per position iteration the same four kinds
+ *   over 3 images columns; output.  8 + n (4 + 2 ceil(images / 48) + 2 ceil(3 images / 48)) in all; after a stage has ended its launches return at once. */
+#define LG_PG_MIN_ITERATIONS 6
+typedef struct lg_posegraph_io {
+    int32_t images, pairs;
+    uint32_t flags;                        /* none defined: must be 0                                                 */
+    int32_t num_iterations;                /* of EACH stage, in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]          */
+    int32_t origin;                        /* the image whose pose is the identity                                    */
+    int32_t baseline;                      /* the image at distance 1 from it, or -1: chosen on the device            */
+    int32_t min_inliers;                   /* read only with num_inliers                                              */
+    double rotation_scale;                 /* degrees, > 0                                                            */
+    double max_rotation_error;             /* degrees, > 0                                                            */
+    double direction_scale;                /* degrees, > 0                                                            */
+    const int64_t *pair_index;             /* [pairs][2]: (a, b)                                                      */
+    const float *rotations;                /* [pairs][9]                                                              */
+    const float *translations;             /* [pairs][3]                                                              */
+    const float *weights;                  /* [pairs]                                                                 */
+    const int32_t *num_inliers;            /* [pairs], or NULL                                                        */
+    void *workspace; int64_t workspace_bytes;
+    float *poses;                          /* [images][12]                                                            */
+    uint8_t *image_state;                  /* [images]                                                                */
+    uint8_t *pair_state;                   /* [pairs]                                                                 */
+    float *rotation_error;                 /* [pairs] degrees                                                         */
+    float *direction_error;                /* [pairs] degrees                                                         */
+    double *summary;                       /* [8]                                                                     */
+} lg_posegraph_io;
+int64_t lg_posegraph_workspace_bytes(int64_t images, int64_t pairs, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_posegraph_solve(const lg_posegraph_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

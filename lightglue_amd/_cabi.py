@@ -29,6 +29,7 @@ LG_RELPOSE_REFINE, LG_RELPOSE_ROOTS = 32768, 10   # lg_relpose_estimate: its ref
 LG_ABSPOSE_REFINE, LG_ABSPOSE_GROUPED, LG_ABSPOSE_GIVEN_POSES, LG_ABSPOSE_ROOTS = 65536, 131072, 262144, 4   # lg_abspose_estimate: its io flags, candidates per hypothesis
 LG_TRI_REFINE, LG_TRI_TRACKS_ONLY, LG_TRI_MAX_TRACK_LENGTH = 524288, 1048576, 1024   # lg_triangulate: its io flags, the longest track it triangulates
 LG_BA_MAX_IMAGES, LG_BA_MAX_ITERATIONS, LG_BA_MAX_TRACK_LENGTH, LG_BA_CHOLESKY_BLOCK = 256, 100, 1024, 48   # lg_bundle_adjust: its envelope, the columns per Cholesky panel (it defines no flag bit)
+LG_PG_MIN_ITERATIONS, LG_PG_MAX_PAIRS = 6, 2 ** 20   # lg_posegraph_solve: its envelope next to LG_BA_MAX_IMAGES and LG_BA_MAX_ITERATIONS (it defines no flag bit)
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
 LG_MAX_KEYPOINTS, LG_MAX_ROWS, LG_MAX_SIM_ELEMS = 8192, 2 ** 21, 2 ** 31 - 1   # the envelope of one lg_engine_forward call
@@ -52,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
     "lg_triangulate_workspace_bytes", "lg_triangulate",
     "lg_bundle_workspace_bytes", "lg_bundle_adjust",
+    "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
 )
 
 
@@ -166,6 +168,17 @@ class LgBundleIO(C.Structure):
         ("kpts", _fp), ("num", _fp), ("track_id", _fp), ("xyz", _fp), ("cameras", _fp), ("poses", _fp), ("constant_pose", _fp),
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("poses_out", _fp), ("xyz_out", _fp), ("points3d", _fp), ("node_state", _fp), ("observation_error", _fp), ("summary", _fp), ("status", _fp),
+    ]
+
+
+class LgPosegraphIO(C.Structure):
+    """lg_posegraph_io (include/lightglue_amd.h): one call of the global pose estimator"""
+    _fields_ = [
+        ("images", C.c_int32), ("pairs", C.c_int32), ("flags", C.c_uint32), ("num_iterations", C.c_int32), ("origin", C.c_int32), ("baseline", C.c_int32),
+        ("min_inliers", C.c_int32), ("rotation_scale", C.c_double), ("max_rotation_error", C.c_double), ("direction_scale", C.c_double),
+        ("pair_index", _fp), ("rotations", _fp), ("translations", _fp), ("weights", _fp), ("num_inliers", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("poses", _fp), ("image_state", _fp), ("pair_state", _fp), ("rotation_error", _fp), ("direction_error", _fp), ("summary", _fp),
     ]
 
 
@@ -349,6 +362,9 @@ def load() -> C.CDLL:
     lib.lg_bundle_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_bundle_workspace_bytes.restype = C.c_int64
     lib.lg_bundle_adjust.argtypes = [C.POINTER(LgBundleIO), C.c_void_p]
+    lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
+    lib.lg_posegraph_workspace_bytes.restype = C.c_int64
+    lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

@@ -5,7 +5,8 @@
 //   ba_fill       one lane per node: states 5 / 6, or a place in the track's list by atomicAdd on its cursor (arrival order is arbitrary), the image's count;
 //   ba_sort       one lane per track: the list put into ascending node order (what the atomics left is gone), the image of every entry;
 //   ba_cost + ba_decide   the cost of the input;
-//   per iteration: ba_points, ba_reduce, ba_cholesky_diag + ba_cholesky_rows once per panel, ba_backsolve, ba_trial_points, ba_cost, ba_decide;
+//   per iteration: ba_points, ba_reduce, ba_cholesky_diag + ba_cholesky_rows once per panel (bodies in lg_cholesky.h), ba_backsolve, ba_trial_points, ba_cost,
+//   ba_decide;
 //   ba_scatter    one lane per node, track and image: the outputs.
 // No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
 // other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
@@ -14,6 +15,7 @@
 #include <cmath>
 #include <string>
 
+#include "lg_cholesky.h"
 #include "lg_host_call.h"
 #include "lg_kernels.h"
 #include "lg_solve3.h"
@@ -24,9 +26,9 @@
 namespace lg {
 
 constexpr int BA_THREADS = 256, BA_SCAN_THREADS = 1024, BA_SCAN_WAVES = BA_SCAN_THREADS / 64;
-constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK, BA_KT = 32;      // Cholesky: columns per panel = rows per tile, columns of earlier panels per LDS chunk
+constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK;                  // Cholesky (lg_cholesky.h): columns per panel = rows per tile
+static_assert(BA_NB == CH_NB && BA_THREADS == CH_THREADS, "lg_cholesky.h is written for 48-column panels and 256 threads");
 constexpr int BA_TILE = 32, BA_BCHUNK = 6;                   // reduce: rows of image a per LDS tile, column blocks b per workgroup (6 x 36 = 216 threads)
-constexpr int BA_PARTS = 5;                                  // back substitution: interleaved partial sums over the rows below a panel
 
 struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, pad0, pad1; };
 static_assert(sizeof(BaHead) <= 256, "the record of the call is 256 bytes");
@@ -396,148 +398,26 @@ __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
 // (tr + 16 ii, tc + 16 jj), ii, jj < 3, of a BA_NB x BA_NB block.
 // 3a. ONE workgroup: the panel's diagonal block D = S_pp - L_p L_p^T over all earlier columns, factored in LDS and written over S_pp
 __global__ __launch_bounds__(BA_THREADS) void ba_cholesky_diag_kernel(BaArgs a, int panel) {
-    __shared__ double Bs[BA_NB][BA_KT + 1], Dm[BA_NB][BA_NB + 1];
+    __shared__ CholeskyDiagLds m;
     if (a.head->converged) return;
-    const int dim = a.dim, t = threadIdx.x, tr = t >> 4, tc = t & 15;
-    const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0);            // the panel's columns [C0, C0 + nb)
-    double* S = a.S;
-    double acc[3][3];
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) acc[ii][jj] = 0.0;
-    for (int k0 = 0; k0 < C0; k0 += BA_KT) {                            // C0 is a multiple of BA_NB; the last chunk may be short
-        const int kt = min(BA_KT, C0 - k0);
-        __syncthreads();
-        for (int q = t; q < BA_NB * BA_KT; q += BA_THREADS) {
-            const int row = q / BA_KT, kk = q - row * BA_KT;
-            Bs[row][kk] = (row < nb && kk < kt) ? S[(long long)(C0 + row) * dim + k0 + kk] : 0.0;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < kt; ++kk) {
-            double bv[3], dv[3];
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii) { dv[ii] = Bs[tr + 16 * ii][kk]; bv[ii] = Bs[tc + 16 * ii][kk]; }
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-                for (int jj = 0; jj < 3; ++jj) acc[ii][jj] += dv[ii] * bv[jj];
-        }
-    }
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) {
-            const int row = tr + 16 * ii, col = tc + 16 * jj;
-            Dm[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] - acc[ii][jj] : 0.0;
-        }
-    __syncthreads();
-    // right-looking inside the block: column kk scaled, then the columns to its right updated
-    for (int kk = 0; kk < nb; ++kk) {
-        double d = Dm[kk][kk];
-        const bool good = d > 0.0 && isfinite(d);
-        if (!good) d = 1.0;
-        const double l = sqrt(d);
-        __syncthreads();
-        if (t == 0) { Dm[kk][kk] = l; if (!good) atomicOr(&a.head->fail, 1); }
-        if (t > kk && t < nb) Dm[t][kk] = Dm[t][kk] / l;
-        __syncthreads();
-        for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
-            const int row = q / BA_NB, col = q - row * BA_NB;
-            if (col > kk && col <= row && row < nb) Dm[row][col] = Dm[row][col] - Dm[row][kk] * Dm[col][kk];
-        }
-        __syncthreads();
-    }
-    for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
-        const int row = q / BA_NB, col = q - row * BA_NB;
-        if (row < nb && col <= row) S[(long long)(C0 + row) * dim + C0 + col] = Dm[row][col];
-    }
+    cholesky_diag(a.S, a.dim, panel, 0.0, &a.head->fail, m);            // floor 0: a pivot fails unless it is > 0 (and finite)
 }
 
 // 3b. one workgroup per BA_NB-row tile that has rows below the diagonal block: G = S_ip - L_i L_p^T, then L_i = G L_pp^-T.  It reads the panel's rows (earlier
 // columns and L_pp: finished by earlier launches) and its own rows; it writes its own rows' panel columns, which no other workgroup of the launch reads
 __global__ __launch_bounds__(BA_THREADS) void ba_cholesky_rows_kernel(BaArgs a, int panel) {
-    __shared__ double As[BA_NB][BA_KT + 1], Bs[BA_NB][BA_KT + 1], Lp[BA_NB][BA_NB + 1], Gm[BA_NB][BA_NB + 1];
+    __shared__ CholeskyRowsLds m;
     if (a.head->converged) return;
-    const int dim = a.dim, t = threadIdx.x, tr = t >> 4, tc = t & 15;
-    const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0);            // the panel's columns [C0, C0 + nb)
-    const int tile = panel + blockIdx.x, R0 = tile * BA_NB, nr = min(BA_NB, dim + 1 - R0);      // this workgroup's rows [R0, R0 + nr), nr >= 1
-    if (R0 + nr <= C0 + nb) return;                                     // the diagonal tile without the right-hand side's row: nothing below the block
-    double* S = a.S;
-    double acc[3][3];
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) acc[ii][jj] = 0.0;
-    for (int k0 = 0; k0 < C0; k0 += BA_KT) {
-        const int kt = min(BA_KT, C0 - k0);
-        __syncthreads();
-        for (int q = t; q < BA_NB * BA_KT; q += BA_THREADS) {
-            const int row = q / BA_KT, kk = q - row * BA_KT;
-            As[row][kk] = (row < nr && R0 + row >= C0 + nb && kk < kt) ? S[(long long)(R0 + row) * dim + k0 + kk] : 0.0;
-            Bs[row][kk] = (row < nb && kk < kt) ? S[(long long)(C0 + row) * dim + k0 + kk] : 0.0;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < kt; ++kk) {
-            double av[3], bv[3];
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii) { av[ii] = As[tr + 16 * ii][kk]; bv[ii] = Bs[tc + 16 * ii][kk]; }
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-                for (int jj = 0; jj < 3; ++jj) acc[ii][jj] += av[ii] * bv[jj];
-        }
-    }
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) {
-            const int row = tr + 16 * ii, col = tc + 16 * jj;
-            Gm[row][col] = (row < nr && col < nb && R0 + row >= C0 + nb) ? S[(long long)(R0 + row) * dim + C0 + col] - acc[ii][jj] : 0.0;
-            Lp[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] : 0.0;
-        }
-    __syncthreads();
-    // one lane per row, columns in ascending order
-    if (t < nr && R0 + t >= C0 + nb) {
-        for (int col = 0; col < nb; ++col) {
-            double v = Gm[t][col];
-            for (int kk = 0; kk < col; ++kk) v = v - Gm[t][kk] * Lp[col][kk];
-            v = v / Lp[col][col];
-            Gm[t][col] = v;
-            S[(long long)(R0 + t) * dim + C0 + col] = v;
-        }
-    }
+    cholesky_rows(a.S, a.dim, 1, panel, panel + blockIdx.x, m);
 }
 
 // ------------------------------------------------------------------ per iteration 4: ONE workgroup: L^T s = z backwards, the trial poses
 __global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
-    __shared__ double sd[6 * LG_BA_MAX_IMAGES], part[BA_PARTS][BA_NB], Lp[BA_NB][BA_NB + 1];
+    __shared__ double sd[6 * LG_BA_MAX_IMAGES];
+    __shared__ CholeskySolveLds m;
     if (a.head->converged) return;
-    const int dim = a.dim, t = threadIdx.x;
-    const double* S = a.S;
-    const double* z = S + (long long)dim * dim;
-    const int panels = (dim + BA_NB - 1) / BA_NB;
-    for (int panel = panels - 1; panel >= 0; --panel) {
-        const int C0 = panel * BA_NB, nb = min(BA_NB, dim - C0), below = C0 + nb;
-        if (t < BA_PARTS * BA_NB) {
-            const int col = t % BA_NB, part_id = t / BA_NB;
-            double sum = 0.0;
-            if (col < nb) for (int i = below + part_id; i < dim; i += BA_PARTS) sum += S[(long long)i * dim + C0 + col] * sd[i];
-            part[part_id][col] = sum;
-        }
-        for (int q = t; q < BA_NB * BA_NB; q += BA_THREADS) {
-            const int row = q / BA_NB, col = q - row * BA_NB;
-            Lp[row][col] = (row < nb && col <= row) ? S[(long long)(C0 + row) * dim + C0 + col] : 0.0;
-        }
-        __syncthreads();
-        if (t == 0)
-            for (int col = nb - 1; col >= 0; --col) {
-                double v = z[C0 + col] - ((((part[0][col] + part[1][col]) + part[2][col]) + part[3][col]) + part[4][col]);
-                for (int i = col + 1; i < nb; ++i) v = v - Lp[i][col] * sd[C0 + i];
-                sd[C0 + col] = v / Lp[col][col];
-            }
-        __syncthreads();
-    }
+    const int t = threadIdx.x;
+    cholesky_backsolve(a.S, a.dim, 1, sd, m);
     const int s = a.head->sel;
     int bad = 0;
     for (int k = t; k < a.images; k += BA_THREADS) {

@@ -133,6 +133,33 @@ inline const char* ba_layout(long long images, long long n, long long tracks, ui
     L.X = bp.take(tracks * 48); L.Vinv = bp.take(tracks * 72); L.y = bp.take(tracks * 24); L.total = bp.used;
     return nullptr;
 }
+// lg_posegraph_solve: a 256-byte record of the call; per image its rotation and centre in fp64 (96 bytes) and five int32 (level, present, list count, list
+// offset, fill cursor; the offsets hold one more entry); per pair its state (4), its rotation error (8), its direction (24) and its two adjacency entries
+// (16); the larger of the two systems with its right-hand side row: (3 images + 1) x 3 images fp64 (the rotation system, (images + 3) x images, fits in it)
+constexpr uint32_t PG_KNOWN_FLAGS = 0u;
+constexpr long long PG_MAX_PAIRS = 1LL << 20;
+struct PgLayout { long long head, rot, cen, level, present, acount, aoff, acur, pstate, perr, dir, adj, S, total; };
+inline const char* pg_layout(long long images, long long pairs, uint32_t flags, PgLayout& L) {
+    if (flags & ~PG_KNOWN_FLAGS) return "undefined flag bits (the pose-graph solver defines none)";
+    if (images < 2 || images > LG_BA_MAX_IMAGES) return "images must lie in [2, LG_BA_MAX_IMAGES]";
+    if (pairs < 1 || pairs > PG_MAX_PAIRS) return "pairs must lie in [1, 2^20]";
+    Bump bp;
+    L.head = bp.take(256); L.rot = bp.take(images * 72); L.cen = bp.take(images * 24);
+    L.level = bp.take(images * 4); L.present = bp.take(images * 4); L.acount = bp.take(images * 4); L.aoff = bp.take((images + 1) * 4); L.acur = bp.take(images * 4);
+    L.pstate = bp.take(pairs * 4); L.perr = bp.take(pairs * 8); L.dir = bp.take(pairs * 24); L.adj = bp.take(pairs * 16);
+    L.S = bp.take((3 * images + 1) * 3 * images * 8); L.total = bp.used;
+    return nullptr;
+}
+inline const char* pg_settings_error(long long images, long long num_iterations, long long origin, long long baseline, double rotation_scale,
+                                     double max_rotation_error, double direction_scale) {
+    if (num_iterations < LG_PG_MIN_ITERATIONS || num_iterations > LG_BA_MAX_ITERATIONS) return "num_iterations must lie in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]";
+    if (origin < 0 || origin >= images) return "origin must name an image";
+    if (baseline < -1 || baseline >= images || baseline == origin) return "baseline must be -1 or name an image other than origin";
+    auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
+    if (!positive(rotation_scale) || !positive(max_rotation_error) || !positive(direction_scale))
+        return "rotation_scale, max_rotation_error and direction_scale must be > 0 (and finite)";
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

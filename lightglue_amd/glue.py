@@ -242,6 +242,13 @@ def bundle_adjust(adjuster, tracks, feats, cameras, poses, constant_pose) -> dic
     return adjuster.adjust(_as_store(feats), tracks, cameras, poses, constant_pose)
 
 
+def estimate_global_poses(estimator, relative, pairs, num_images, **kw) -> dict:
+    """One pose per image from what `estimate_poses` returned over the same pair list (`relative`: its dict, or (R, t)), by a `GlobalPoseEstimator`: rotation
+    and position averaging over the view graph of `num_images` images; **kw: origin, baseline, weights.  Returns the estimator's dict; its poses [K, 3, 4] are
+    what `triangulate_tracks` and `bundle_adjust` take, its origin and baseline the two images to hold constant there (the same gauge and scale)."""
+    return estimator.estimate(pairs, relative, num_images, **kw)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output
