@@ -900,6 +900,53 @@ int64_t lg_triangulate_workspace_bytes(int64_t images, int32_t n, uint32_t flags
 int lg_triangulate(const lg_triangulate_io* io, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The robust mode of the triangulator: per component a consensus over its views, and up to max_tracks tracks out of one component.  One wrong match no
+ * longer rejects its track (the observation is left out as an outlier), and two tracks that a wrong match merged come apart again.  lg_triangulate itself is
+ * unchanged in every bit and refusal; this is a second entry point over the same io struct.  tests/triangulate_robust_oracle.py restates it in float64 numpy.
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   unchanged nodes, edges, statuses, components, their names, the ascending node order of a component's list and the too-long rule (state 3) are those of
+ *             lg_triangulate; all geometry is fp64 without fused multiply-add, and "start", "refine" and "accept" above are used as they stand.
+ *   rounds    a component with at most max_track_length nodes is processed in up to max_tracks rounds.  A round runs on the list `rest` of L nodes in
+ *             ascending order; round 0 runs on all the component's nodes.
+ *   hypotheses  the index pairs (i, j), i < j, of `rest` in lexicographic order are numbered 0 .. Q - 1, Q = L (L - 1) / 2.  With Q <= num_hypotheses
+ *             hypothesis h is pair h, h in [0, Q); otherwise hypothesis h in [0, num_hypotheses) is pair floor(h Q / num_hypotheses), in 64-bit integers.  No
+ *             seed and no hash: the hypotheses are a function of the component alone.  A hypothesis whose two nodes lie in one image is skipped.  Its point is
+ *             the start over exactly its two observations, in that order; a failed pivot or a non-finite point skips the hypothesis.
+ *   score     an integer: the number of images that own at least one node of `rest` with pz > 0 and error sqrt(rx rx + ry ry) <= max_reproj_error at the
+ *             hypothesis' point.  The winner has the highest score; among equal scores the lowest h.
+ *   consensus under the winner's point every image contributes its passing node of smallest error; the comparison is a strict < in ascending node order, so
+ *             a tie keeps the lowest node.  The consensus list is these nodes in ascending order.
+ *   failures  no valid hypothesis: the round fails with state 4; a best score below 2: state 6.
+ *   fit       start, refine (with LG_TRI_REFINE) and accept run on the consensus list exactly as lg_triangulate runs them on a whole track; the round's state
+ *             is their result.  State 1: the consensus nodes are a track with that point, track_length the consensus size and track_error the mean error;
+ *             `rest` becomes the nodes outside the consensus and the next round runs if at least 2 nodes and a round are left.  There is no re-admission of
+ *             observations after the fit.  A failed round ends the component.
+ *   node_state  a consensus node of a successful round: 1, with that track's id and point.  Round 0 failed: every node of the component carries round 0's
+ *             state, as in lg_triangulate.  Otherwise every node left over has state 8, outlier: track_id -1, points3d NaN.  State 2 does not occur.
+ *   outputs   track ids are dense in ascending (component name, round).  counts[0] = T, counts[2] = T, counts[1 + s] for s != 1 = the components whose round
+ *             0 failed with state s (too long included).  outlier_counts[0] = the nodes of state 8, outlier_counts[1] = the components with more than one
+ *             track.  Every output is a function of the edge set alone, the same bits from run to run and under permutation, duplication or reversal of
+ *             the pair list.  When the round-0 consensus is the whole component, its point, error and state are bit for bit those of lg_triangulate.
+ * Workspace: lg_triangulate_robust_workspace_bytes bytes (-1 outside the envelope): that of lg_triangulate plus two int32 per node and 28 bytes per possible
+ *   track and round.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): that of lg_triangulate, and LG_TRI_TRACKS_ONLY or any other bit than LG_TRI_REFINE in
+ *   base.flags; num_hypotheses outside [1, LG_TRI_MAX_HYPOTHESES]; max_tracks outside [1, LG_TRI_MAX_TRACKS]; a null outlier_counts.
+ * Eight launches: the first five of lg_triangulate as they are; then ONE WAVE per component: the list in ascending order by rank, the observations staged in
+ *   that wave's LDS slice (12 bytes per node), lanes stride over the hypotheses, an integer wave maximum of score << 16 | (0xFFFF - h) names the winner, one
+ *   lane selects the consensus and fits it; one scan over the (component, round) slots; scatter.  No floating-point atomics, and no wave waits on another. */
+#define LG_TRI_MAX_HYPOTHESES 4096
+#define LG_TRI_MAX_TRACKS 4
+typedef struct lg_triangulate_robust_io {
+    lg_triangulate_io base;                /* flags: LG_TRI_REFINE only; workspace: lg_triangulate_robust_workspace_bytes */
+    int32_t num_hypotheses;                /* in [1, LG_TRI_MAX_HYPOTHESES], per round                                */
+    int32_t max_tracks;                    /* in [1, LG_TRI_MAX_TRACKS]: the rounds of one component                  */
+    int32_t *outlier_counts;               /* [2]: nodes of state 8, components with more than one track              */
+} lg_triangulate_robust_io;
+int64_t lg_triangulate_robust_workspace_bytes(int64_t images, int32_t n, int32_t max_tracks);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_triangulate_robust(const lg_triangulate_robust_io* io, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bundle adjustment: joint refinement of the free poses and of all track points by Levenberg-Marquardt on the sum of squared pixel reprojection errors, over
  * what the triangulator returns (track_id, xyz) plus one camera and one pose per image; intrinsics are fixed.  Schur complement onto the poses, dense Cholesky
  * of the reduced camera system, fp64 throughout, no fused multiply-add, one call and one host synchronisation for the whole problem.  Stateless.  The reference

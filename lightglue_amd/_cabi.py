@@ -28,6 +28,7 @@ LG_TWOVIEW_HOMOGRAPHY, LG_TWOVIEW_FUNDAMENTAL, LG_TWOVIEW_REFINE, LG_TWOVIEW_GIV
 LG_RELPOSE_REFINE, LG_RELPOSE_ROOTS = 32768, 10   # lg_relpose_estimate: its refit flag, candidate models per hypothesis
 LG_ABSPOSE_REFINE, LG_ABSPOSE_GROUPED, LG_ABSPOSE_GIVEN_POSES, LG_ABSPOSE_ROOTS = 65536, 131072, 262144, 4   # lg_abspose_estimate: its io flags, candidates per hypothesis
 LG_TRI_REFINE, LG_TRI_TRACKS_ONLY, LG_TRI_MAX_TRACK_LENGTH = 524288, 1048576, 1024   # lg_triangulate: its io flags, the longest track it triangulates
+LG_TRI_MAX_HYPOTHESES, LG_TRI_MAX_TRACKS = 4096, 4   # lg_triangulate_robust: hypotheses per round, rounds (tracks) per component
 LG_BA_MAX_IMAGES, LG_BA_MAX_ITERATIONS, LG_BA_MAX_TRACK_LENGTH, LG_BA_CHOLESKY_BLOCK = 256, 100, 1024, 48   # lg_bundle_adjust: its envelope, the columns per Cholesky panel (it defines no flag bit)
 LG_PG_MIN_ITERATIONS, LG_PG_MAX_PAIRS = 6, 2 ** 20   # lg_posegraph_solve: its envelope next to LG_BA_MAX_IMAGES and LG_BA_MAX_ITERATIONS (it defines no flag bit)
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
@@ -51,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "lg_twoview_workspace_bytes", "lg_twoview_verify",
     "lg_relpose_workspace_bytes", "lg_relpose_estimate",
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
-    "lg_triangulate_workspace_bytes", "lg_triangulate",
+    "lg_triangulate_workspace_bytes", "lg_triangulate", "lg_triangulate_robust_workspace_bytes", "lg_triangulate_robust",
     "lg_bundle_workspace_bytes", "lg_bundle_adjust",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
 )
@@ -158,6 +159,11 @@ class LgTriangulateIO(C.Structure):
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("points3d", _fp), ("track_id", _fp), ("node_state", _fp), ("xyz", _fp), ("track_length", _fp), ("track_error", _fp), ("counts", _fp), ("status", _fp),
     ]
+
+
+class LgTriangulateRobustIO(C.Structure):
+    """lg_triangulate_robust_io (include/lightglue_amd.h): one call of the triangulator's robust mode"""
+    _fields_ = [("base", LgTriangulateIO), ("num_hypotheses", C.c_int32), ("max_tracks", C.c_int32), ("outlier_counts", _fp)]
 
 
 class LgBundleIO(C.Structure):
@@ -359,6 +365,9 @@ def load() -> C.CDLL:
     lib.lg_triangulate_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
     lib.lg_triangulate_workspace_bytes.restype = C.c_int64
     lib.lg_triangulate.argtypes = [C.POINTER(LgTriangulateIO), C.c_void_p]
+    lib.lg_triangulate_robust_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.lg_triangulate_robust_workspace_bytes.restype = C.c_int64
+    lib.lg_triangulate_robust.argtypes = [C.POINTER(LgTriangulateRobustIO), C.c_void_p]
     lib.lg_bundle_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_bundle_workspace_bytes.restype = C.c_int64
     lib.lg_bundle_adjust.argtypes = [C.POINTER(LgBundleIO), C.c_void_p]

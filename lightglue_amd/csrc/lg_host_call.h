@@ -112,6 +112,20 @@ inline const char* tri_layout(long long images, long long n, uint32_t flags, Tri
     L.croot = bp.take(L.tracks * 4); L.cstate = bp.take(L.tracks * 4); L.tid = bp.take(L.tracks * 4); L.cres = bp.take(L.tracks * 16); L.total = bp.used;
     return nullptr;
 }
+// lg_triangulate_robust: lg_triangulate's layout, then two more int32 per node (the consensus list of the running round, the round that took the node) and,
+// per slot (possible component x max_tracks), its state, dense id, consensus size and (X, Y, Z, error)
+struct TriRobustLayout { TriLayout base; long long cons, nround, sstate, stid, slen, sres, total; };
+inline const char* tri_robust_layout(long long images, long long n, uint32_t flags, long long max_tracks, TriRobustLayout& L) {
+    if (flags & ~LG_TRI_REFINE) return "undefined flag bits (the robust triangulator reads LG_TRI_REFINE)";
+    if (const char* why = tri_layout(images, n, flags, L.base)) return why;
+    if (max_tracks < 1 || max_tracks > LG_TRI_MAX_TRACKS) return "max_tracks must lie in [1, LG_TRI_MAX_TRACKS]";
+    const long long nodes = L.base.nodes, slots = L.base.tracks * max_tracks;
+    Bump bp;
+    bp.used = L.base.total;
+    L.cons = bp.take(nodes * 4); L.nround = bp.take(nodes * 4);
+    L.sstate = bp.take(slots * 4); L.stid = bp.take(slots * 4); L.slen = bp.take(slots * 4); L.sres = bp.take(slots * 16); L.total = bp.used;
+    return nullptr;
+}
 // lg_bundle_adjust: a 256-byte record of the call; per image a 64-byte record, the pose twice in fp64 (the state and the trial: 192 bytes), its step (48) and
 // its cost (8); the reduced camera system with its right-hand side as one more row ((6 images + 1) x 6 images fp64); per node its track-list entry and that
 // entry's image (8 bytes); per track three int32 (count, offset, cursor) and fifteen + three fp64 (the point twice, the inverse of its damped 3 x 3 block, that

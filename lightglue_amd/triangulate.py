@@ -2,7 +2,9 @@
 (include/lightglue_amd.h holds the definition).  It reads what a matcher or a verifier leaves on the device — ONE keypoint store, the pair list over it and
 `matches0` — in place, plus one pinhole camera (fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image.  Tracks are the connected components of
 the match graph; each is triangulated from all its views.  `points3d [K, N, 3]` (NaN where a row has no point) is what `AbsolutePoseEstimator` takes as
-points3d1.  Any number of pairs in ONE call with ONE host synchronisation; every output is a function of the edge set alone, not of the list's order."""
+points3d1.  Any number of pairs in ONE call with ONE host synchronisation; every output is a function of the edge set alone, not of the list's order.
+`robust=True` (`lg_triangulate_robust`): a consensus over every component's views and up to `max_tracks` tracks out of one component, so that a wrong match
+costs an outlier node and not the track."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +16,7 @@ from . import _cabi, _call
 from .relpose import as_cameras
 
 STATES = ("none", "triangulated", "conflict", "too_long", "degenerate", "behind", "reprojection", "angle")    # node_state 0 .. 7
+ROBUST_STATES = STATES + ("outlier",)                    # node_state 0 .. 8 of the robust mode: 8 is a node its component's tracks left over (2 does not occur)
 
 
 def as_poses(poses, K: int, device) -> torch.Tensor:
@@ -32,10 +35,18 @@ def as_poses(poses, K: int, device) -> torch.Tensor:
 class Triangulator(nn.Module):
     """max_reproj_error: the largest reprojection error, in pixels, an observation of an accepted track may have.  min_angle: the smallest angle, in degrees,
     the widest pair of rays of an accepted track must have.  max_track_length: a longer track is reported too long, in [2, 1024].  refine: five Gauss-Newton
-    steps on the reprojection error from the linear start."""
+    steps on the reprojection error from the linear start.  robust: per component a consensus over its views from `num_hypotheses` two-view hypotheses per
+    round, and up to `max_tracks` tracks (rounds) out of one component (lg_triangulate_robust): a wrong match leaves an outlier node (state 8) behind, not a
+    rejected track, and two tracks it merged come apart again.  A failed round 0 still rejects the component, and a node is not re-admitted after the fit."""
 
-    def __init__(self, max_reproj_error: float = 4.0, min_angle: float = 1.5, max_track_length: int = 128, refine: bool = True):
+    def __init__(self, max_reproj_error: float = 4.0, min_angle: float = 1.5, max_track_length: int = 128, refine: bool = True, robust: bool = False,
+                 num_hypotheses: int = 64, max_tracks: int = 2):
         super().__init__()
+        if int(num_hypotheses) != num_hypotheses or not 1 <= int(num_hypotheses) <= _cabi.LG_TRI_MAX_HYPOTHESES:
+            raise ValueError(f"num_hypotheses must be an integer in [1, {_cabi.LG_TRI_MAX_HYPOTHESES}], got {num_hypotheses!r}")
+        if int(max_tracks) != max_tracks or not 1 <= int(max_tracks) <= _cabi.LG_TRI_MAX_TRACKS:
+            raise ValueError(f"max_tracks must be an integer in [1, {_cabi.LG_TRI_MAX_TRACKS}], got {max_tracks!r}")
+        self.robust, self.num_hypotheses, self.max_tracks = bool(robust), int(num_hypotheses), int(max_tracks)
         if not 0.0 < float(max_reproj_error) < float("inf"):
             raise ValueError(f"max_reproj_error must be > 0, got {max_reproj_error!r}")
         if not 0.0 <= float(min_angle) < 180.0:
@@ -46,7 +57,7 @@ class Triangulator(nn.Module):
 
     # ------------------------------------------------------------------ the call path
     def _launch(self, feats: dict, pairs, result, cameras, poses, validate: bool, tracks_only: bool) -> dict:
-        """ONE lg_triangulate call on the current stream, then the dict behind the one host synchronisation of the call"""
+        """ONE lg_triangulate (robust: lg_triangulate_robust) call on the current stream, then the dict behind the one host synchronisation of the call"""
         device = feats["keypoints"].device
         _call.require_gpu(device, "keypoints")
         s = _call.build_side(feats, device, "feats")
@@ -69,11 +80,14 @@ class Triangulator(nn.Module):
         track_id = torch.empty((K, N), device=device, dtype=torch.int64)
         state = torch.empty((K, N), device=device, dtype=torch.uint8)
         per_track = torch.empty((max(cap, 1), 5), device=device, dtype=torch.float32)      # xyz [cap, 3] | track_error [cap] | track_length [cap] (int32 bits)
-        ints = torch.zeros((9 + P,), device=device, dtype=torch.int32)          # T | tracks per state [8] | status [P]
+        robust = self.robust                                                    # (never with tracks_only: build_tracks refuses)
+        extra = 2 if robust else 0                                              # robust: | outlier nodes | components with more than one track, at the end
+        ints = torch.zeros((9 + P + extra,), device=device, dtype=torch.int32)  # T | tracks per state [8] | status [P]
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
             lib = _cabi.load()
-            nbytes = lib.lg_triangulate_workspace_bytes(K, N, flags)          # -1: outside the envelope — lg_triangulate below says why
+            # -1: outside the envelope — the call below says why
+            nbytes = lib.lg_triangulate_robust_workspace_bytes(K, N, self.max_tracks) if robust else lib.lg_triangulate_workspace_bytes(K, N, flags)
             ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
             p = _call._ptr
             base = per_track.data_ptr()
@@ -84,16 +98,22 @@ class Triangulator(nn.Module):
                 points3d=p(pts), track_id=p(track_id), node_state=p(state),
                 xyz=base, track_error=base + 12 * cap, track_length=base + 16 * cap,
                 counts=ints.data_ptr(), status=None if not P else ints.data_ptr() + 36)
-            _cabi.check(lib.lg_triangulate(C.byref(io), C.c_void_p(stream.cuda_stream)))
+            if robust:
+                rio = _cabi.LgTriangulateRobustIO(base=io, num_hypotheses=self.num_hypotheses, max_tracks=self.max_tracks, outlier_counts=ints.data_ptr() + 4 * (9 + P))
+                _cabi.check(lib.lg_triangulate_robust(C.byref(rio), C.c_void_p(stream.cuda_stream)))
+            else:
+                _cabi.check(lib.lg_triangulate(C.byref(io), C.c_void_p(stream.cuda_stream)))
             host = ints.tolist()              # THE host sync of the call: the per-track outputs need their number
         T = host[0]
         flat = per_track.view(-1)
         out = {"track_id": track_id, "node_state": state, "num_tracks": T, "track_length": flat[4 * cap:4 * cap + T].view(torch.int32).long(),
-               "state_counts": dict(zip(STATES, host[1:9])), "status": ints[9:]}
+               "state_counts": dict(zip(STATES, host[1:9])), "status": ints[9:9 + P]}
+        if robust:
+            out.update(num_outliers=host[9 + P], num_split=host[10 + P])
         if not tracks_only:
             out.update(points3d=pts, xyz=flat[:3 * T].view(T, 3), track_error=flat[3 * cap:3 * cap + T])
         try:
-            _call.raise_on_status(host[9:])
+            _call.raise_on_status(host[9:9 + P])
         except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
             err.outputs = out
             raise
@@ -108,7 +128,9 @@ class Triangulator(nn.Module):
         track_id [K, N] int64 (dense in [0, T) in ascending order of the track's lowest node, -1 elsewhere), node_state [K, N] uint8 (`STATES`), num_tracks = T,
         xyz [T, 3], track_length [T], track_error [T] (mean reprojection error in pixels), state_counts (tracks per state), status [P].  ONE host
         synchronisation.  `validate` as in `match_pairs`; a pair (a, a), an index outside the store or an image whose camera or pose fails the camera rule
-        raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else."""
+        raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else.  With `robust` also num_outliers (the nodes of
+        state 8, `ROBUST_STATES`) and num_split (the components that gave more than one track); state_counts then counts the tracks under "triangulated" and,
+        under every other state, the components whose first round failed with it."""
         return self._launch(feats, pairs, result, cameras, poses, validate, False)
 
     forward = triangulate
@@ -116,5 +138,7 @@ class Triangulator(nn.Module):
     @torch.no_grad()
     def build_tracks(self, feats: dict, pairs, result, *, validate: bool = True) -> dict:
         """Tracks only (LG_TRI_TRACKS_ONLY): no cameras, no poses, no geometry.  node_state holds 0 .. 3 (1: a clean track), track_id numbers every clean
-        track; returns track_id, node_state, num_tracks, track_length, state_counts, status."""
+        track; returns track_id, node_state, num_tracks, track_length, state_counts, status.  There are no tracks without geometry in the robust mode."""
+        if self.robust:
+            raise ValueError("build_tracks has no robust mode: the consensus over a component's views needs cameras and poses (use triangulate)")
         return self._launch(feats, pairs, result, None, None, validate, True)

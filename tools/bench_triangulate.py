@@ -10,8 +10,13 @@ verified matches) x refine on / off, and for build_tracks: the wall-clock ms of 
 visited in turn `--runs` times: median and range), the tracks per state, and the distance of the triangulated points to the cloud's.  The host route is
 tests/triangulate_oracle.py (float64, one thread) after one device-to-host copy of `matches0`, timed once on the verified matches with refine on.  One JSON line.
 `--only-triangulate`: one call per configuration and nothing else — the run to put under a kernel trace for the per-launch times.
+`--robust` adds the robust mode (lg_triangulate_robust: `--num-hypotheses` per round, `--max-tracks` rounds per component, refine on) on either source, next to
+the plain calls of the same job, with its outliers and split components.  `--contaminate F` replaces the fraction F of every source's matches by wrong rows
+(a seeded choice of the matched rows, each sent to a uniformly drawn row of the other image) before anything is triangulated: what a mode keeps of a list
+with wrong matches in it.  The host route is skipped on a contaminated list.
 
-usage: bench_triangulate.py [--images 16] [--kpts 2048] [--runs 5] [--no-host] [--only-triangulate]"""
+usage: bench_triangulate.py [--images 16] [--kpts 2048] [--runs 5] [--no-host] [--only-triangulate] [--robust] [--num-hypotheses 64] [--max-tracks 2]
+                            [--contaminate 0]"""
 import argparse
 import itertools
 import json
@@ -53,6 +58,7 @@ def replay(K, N, dim=256, seed=0):
 def summary(out, truth):
     """what a call found: tracks per state, lengths, errors, and the distance of the points to the cloud's at each track's rows"""
     res = {"num_tracks": out["num_tracks"], "state_counts": out["state_counts"]}
+    res.update({k: out[k] for k in ("num_outliers", "num_split") if k in out})
     if out["num_tracks"]:
         res["mean_track_length"] = round(float(out["track_length"].float().mean()), 2)
     if "xyz" in out and out["num_tracks"]:
@@ -64,6 +70,16 @@ def summary(out, truth):
     return res
 
 
+def contaminate(m0, fraction, seed=0):
+    """matches0 [P, N] with the fraction `fraction` of its matches replaced by uniformly drawn rows (a seeded choice, made on the host)"""
+    m0 = m0.cpu().numpy().copy()
+    rng = np.random.default_rng(seed)
+    at = np.flatnonzero(m0.reshape(-1) >= 0)
+    pick = rng.choice(at, int(round(fraction * len(at))), replace=False)
+    m0.reshape(-1)[pick] = rng.integers(0, m0.shape[1], len(pick))
+    return torch.from_numpy(m0).cuda(), len(pick)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=16)
@@ -71,6 +87,10 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--only-triangulate", action="store_true", help="one call per configuration and nothing else: the run to put under a kernel trace")
+    ap.add_argument("--robust", action="store_true", help="also the robust mode on either source")
+    ap.add_argument("--num-hypotheses", type=int, default=64)
+    ap.add_argument("--max-tracks", type=int, default=2)
+    ap.add_argument("--contaminate", type=float, default=0.0, help="the fraction of every source's matches replaced by wrong rows")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_triangulate.py measures on an MI355X; there is nothing to measure without one")
@@ -86,10 +106,18 @@ def main():
     raw = match()
     verify = lambda: verifier.verify_pairs(store, pairs_dev, raw, validate=False)
     sources = {"raw": raw, "verified": verify()}
+    replaced = {}
+    if args.contaminate > 0:
+        for name in sources:
+            m0, replaced[name] = contaminate(sources[name]["matches0"], args.contaminate)
+            sources[name] = {"matches0": m0}
     configs = [(s, r) for s in sources for r in (False, True)]
     tris = {r: Triangulator(refine=r) for r in (False, True)}
     runs = {(s, r): (lambda s=s, r=r: tris[r].triangulate(store, pairs_dev, sources[s], cameras, poses, validate=False)) for s, r in configs}
     runs.update({(s, "tracks"): (lambda s=s: tris[True].build_tracks(store, pairs_dev, sources[s], validate=False)) for s in sources})
+    if args.robust:
+        robust = Triangulator(robust=True, num_hypotheses=args.num_hypotheses, max_tracks=args.max_tracks)
+        runs.update({(s, "robust"): (lambda s=s: robust.triangulate(store, pairs_dev, sources[s], cameras, poses, validate=False)) for s in sources})
     outs = {c: fn() for c, fn in runs.items()}                                  # warm-up of every timed shape
     if args.only_triangulate:
         for c, fn in runs.items():
@@ -102,11 +130,14 @@ def main():
         for c in runs:                                                          # in turn, not back to back
             ms[c].append(timed(runs[c])[0])
     res = {"images": args.images, "kpts": args.kpts, "pairs": len(pairs), "device": torch.cuda.get_device_name(0), "runs": args.runs,
+           **({"contaminate": args.contaminate, "matches_replaced": replaced} if replaced else {}),
+           **({"num_hypotheses": args.num_hypotheses, "max_tracks": args.max_tracks} if args.robust else {}),
            "matched_per_pair": {s: round(float((r["matches0"] > -1).sum()) / len(pairs), 1) for s, r in sources.items()},
            "nn_match_pairs": stats(match_ms), "verify_pairs": stats(verify_ms), "triangulate": []}
     for c in runs:
-        res["triangulate"].append({"source": c[0], "mode": "build_tracks" if c[1] == "tracks" else "refine" if c[1] else "start", **stats(ms[c]), **summary(outs[c], truth)})
-    if not args.no_host:
+        mode = "build_tracks" if c[1] == "tracks" else "robust" if c[1] == "robust" else "refine" if c[1] else "start"
+        res["triangulate"].append({"source": c[0], "mode": mode, **stats(ms[c]), **summary(outs[c], truth)})
+    if not args.no_host and not replaced:
         t = time.perf_counter()
         inp = dict(kpts=store["keypoints"].cpu().numpy(), num=None, pairs=np.asarray(pairs), matches0=sources["verified"]["matches0"].cpu().numpy(),
                    cams=np.asarray([CAMERA] * args.images, np.float32), poses=poses_host)
