@@ -55,6 +55,49 @@ class DeferredMatches:
         return self._out
 
 
+# ---------------------------------------------------------------------- the geometry estimators over a match list (TwoViewVerifier, RelativePoseEstimator,
+# AbsolutePoseEstimator; the Triangulator reads matches0 the same way)
+def ransac_settings(threshold, num_hypotheses, seed) -> tuple:
+    """THE constructor check of the three hypothesise-and-verify estimators: (threshold, num_hypotheses, seed) as (float, int, int), or the ValueError."""
+    if not float(threshold) > 0.0:
+        raise ValueError(f"threshold must be > 0, got {threshold!r}")
+    if int(num_hypotheses) % 256 or not 256 <= int(num_hypotheses) <= 65536:
+        raise ValueError(f"num_hypotheses must be a multiple of 256 in [256, 65536], got {num_hypotheses!r}")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"seed must lie in [0, 2^32), got {seed!r}")
+    return float(threshold), int(num_hypotheses), int(seed)
+
+
+def as_matches0(result, P: int, N: int, device) -> torch.Tensor:
+    """matches0 [P, N] as the C ABI reads it — int64, contiguous, on `device` — from a matcher's result: its dict, a `DeferredMatches` or the tensor itself.
+    A tensor that already qualifies passes through untouched."""
+    if isinstance(result, DeferredMatches):
+        result = result.result()
+    m0 = result["matches0"] if isinstance(result, dict) else result
+    assert torch.is_tensor(m0) and tuple(m0.shape) == (P, N), f"matches0 must have shape [{P}, {N}], got {tuple(m0.shape)}"
+    if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
+        m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+    return m0
+
+
+def ragged_matches(mask: torch.Tensor, verified: torch.Tensor, counts) -> list:
+    """The ragged `matches` lists List[[S_i, 2]] without a synchronisation of their own: a stable sort puts every pair's inlier rows (mask [P, N] bool) first,
+    in ascending order, beside their matches (verified [P, N]); their numbers `counts` are on the host already."""
+    order = torch.sort((~mask).to(torch.uint8), dim=1, stable=True)[1]
+    listed = torch.stack([order, torch.gather(verified, 1, order)], -1)
+    return [listed[b, :c] for b, c in enumerate(counts)]
+
+
+def raise_with_outputs(status, out: dict) -> dict:
+    """`out`, or `raise_on_status`'s error carrying it as `.outputs`: the pairs with status LG_OK are complete."""
+    try:
+        raise_on_status(status)
+    except _cabi.LightGlueAmdError as err:
+        err.outputs = out
+        raise
+    return out
+
+
 def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS, max_sim_elems: int = _cabi.LG_MAX_SIM_ELEMS) -> list:
     """Cut a list of P pairs of n0 x n1 keypoints into the FEWEST contiguous chunks [(start, stop), ...] that each fit one engine call
     (include/lightglue_amd.h: pairs * (cap0 + cap1) <= max_rows and pairs * cap0 * cap1 <= max_sim_elems, cap = n rounded up to 128).  Chunk sizes differ

@@ -58,24 +58,14 @@ class AbsolutePoseEstimator(nn.Module):
 
     def __init__(self, threshold: float = 3.0, num_hypotheses: int = 1024, refine: bool = True, seed: int = 0):
         super().__init__()
-        if not float(threshold) > 0.0:
-            raise ValueError(f"threshold must be > 0, got {threshold!r}")
-        if int(num_hypotheses) % 256 or not 256 <= int(num_hypotheses) <= 65536:
-            raise ValueError(f"num_hypotheses must be a multiple of 256 in [256, 65536], got {num_hypotheses!r}")
-        if not 0 <= int(seed) < 2 ** 32:
-            raise ValueError(f"seed must lie in [0, 2^32), got {seed!r}")
-        self.threshold, self.num_hypotheses, self.refine, self.seed = float(threshold), int(num_hypotheses), bool(refine), int(seed)
+        self.threshold, self.num_hypotheses, self.seed = _call.ransac_settings(threshold, num_hypotheses, seed)
+        self.refine = bool(refine)
 
     # ------------------------------------------------------------------ the call path
     def _launch(self, device, s0, s1, pts, P: int, index, image0, result, cameras0, pool: bool, poses=None, return_candidates: bool = False) -> dict:
         """P pairs in ONE lg_abspose_estimate call on the current stream, then the dict behind the one host synchronisation of the call.  image0 [P]: the
         image-0 index of every pair (host or device), read on the host only to pool."""
-        if isinstance(result, _call.DeferredMatches):
-            result = result.result()
-        m0 = result["matches0"] if isinstance(result, dict) else result
-        assert torch.is_tensor(m0) and tuple(m0.shape) == (P, s0.N), f"matches0 must have shape [{P}, {s0.N}], got {tuple(m0.shape)}"
-        if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
-            m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+        m0 = _call.as_matches0(result, P, s0.N, device)
         cam0 = as_cameras(cameras0, s0.K, device, "cameras0")
         H = self.num_hypotheses
         flags = (_cabi.LG_ABSPOSE_REFINE if self.refine else 0) | (0 if index is None else _cabi.LG_FLAG_INDEXED)
@@ -116,20 +106,12 @@ class AbsolutePoseEstimator(nn.Module):
                 _cabi.check(lib.lg_abspose_estimate(C.byref(io), C.c_void_p(stream.cuda_stream)))
             host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
         mask = inl.bool()
-        # the ragged lists without another synchronisation: a stable sort puts every pair's inlier rows first, in ascending order; their number is on the host
-        order = torch.sort((~mask).to(torch.uint8), dim=1, stable=True)[1]
-        listed = torch.stack([order, torch.gather(verified, 1, order)], -1)
-        matches = [listed[b, :c] for b, c in enumerate(host[2 * G:2 * G + P])]
+        matches = _call.ragged_matches(mask, verified, host[2 * G:2 * G + P])
         out = {"R": R, "t": t, "num_inliers": ints[:G].long(), "best_hypothesis": ints[G:2 * G].long(), "queries": queries, "group_of_pair": group_of_pair,
                "inliers0": mask, "pair_num_inliers": ints[2 * G:2 * G + P].long(), "matches0": verified, "matches": matches}
         if return_candidates:
             out["candidates"] = cand
-        try:
-            _call.raise_on_status(host[2 * G + P:])
-        except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
-            err.outputs = out
-            raise
-        return out
+        return _call.raise_with_outputs(host[2 * G + P:], out)
 
     @torch.no_grad()
     def forward(self, data: dict, result, cameras0, points3d1) -> dict:

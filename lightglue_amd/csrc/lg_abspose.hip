@@ -8,13 +8,13 @@
 //                compiler's figures);
 //   ap_finalise  one workgroup per problem: the winner solved again by one lane (nothing is stored per hypothesis), the optional five Gauss-Newton steps in
 //                fp64, the keep-or-drop count, t' -> t, and the per-pair masks, counts and matches scattered through the rows' places.
-// The sampler, the tile geometry and block_sum / compact_slot are the verifier's (lg_twoview_common.h, lg_common.h); the degree-4 root finder restates
-// lg_relpose.hip's method with every array indexed statically.  The refusals and the workspace layout (ApLayout) are lg_host_call.h's.
-#include <string>
-
+// The sampler, the tile geometry, bearing, horner<N>, the winner's key (PoseKey, publish_winner) and
+// the two-row accumulate_upper2<6> / reduce_upper<6> of the Gauss-Newton system are lg_ransac_common.h's; block_sum, compact_slot and the camera rule are
+// lg_common.h's.  The refusals (check_estimator_call) and the workspace layout (ApLayout) are lg_host_call.h's.  What is the estimator's own is here: the 3-D
+// list with its centroid, Grunert's solver and its unrolled degree-4 root finder, the reprojection test and its tile loop, the Gauss-Newton update and the scatter of a problem's mask to its pairs.
 #include "lg_host_call.h"
 #include "lg_kernels.h"
-#include "lg_twoview_common.h"
+#include "lg_ransac_common.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -52,7 +52,6 @@ __device__ __forceinline__ int ap_pair(const ApArgs& a, int place) {
     const int p = a.group_pairs[place];
     return (unsigned)p < (unsigned)a.pairs ? p : -1;
 }
-__device__ __forceinline__ bool ap_camera_ok(const float* c) { return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f; }
 
 // ------------------------------------------------------------------ compaction: one workgroup per problem
 __global__ __launch_bounds__(TV_THREADS) void ap_compact_kernel(ApArgs a) {
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(TV_THREADS) void ap_compact_kernel(ApArgs a) {
         if (cam_image >= 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) h.cam[e] = a.cameras0[(long long)cam_image * 4 + e];
-            h.bad = ap_camera_ok(h.cam) ? 0 : 1;
+            h.bad = camera_ok(h.cam) ? 0 : 1;
         }
         if (h.bad) h.count = 0;                          // an empty problem to every later launch
         a.head[g] = h;
@@ -116,14 +115,9 @@ __global__ __launch_bounds__(TV_THREADS) void ap_compact_kernel(ApArgs a) {
 }
 
 // ------------------------------------------------------------------ the P3P solver, fp64, one lane, every array indexed statically
-template <int N> __device__ __forceinline__ double ap_horner(const double (&c)[N + 1], double z) {
-    double v = c[N];
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) v = v * z + c[i];
-    return v;
-}
-// the real roots of p (degree N, p[N] != 0) in ascending order: lg_relpose.hip's rp_real_roots (the roots of the k-th derivative lie one in each interval
-// between those of the (k + 1)-th; every derivative padded with zeros to degree N, which changes no bit), unrolled so that no index is a run-time value
+// the real roots of p (degree N, p[N] != 0) in ascending order, the rest of root[] zero: lg_relpose.hip's rp_real_roots (the roots of the k-th derivative lie one in each
+// interval between those of the (k + 1)-th; 64 bisections and 3 guarded Newton steps per sign change; every derivative padded with zeros to degree N, which changes no
+// bit), unrolled so that no index is a run-time value and nothing goes to scratch
 template <int N> __device__ __forceinline__ int ap_real_roots(const double (&p)[N + 1], double (&root)[N]) {
 #pragma unroll
     for (int i = 0; i < N; ++i) root[i] = 0.0;
@@ -151,22 +145,22 @@ template <int N> __device__ __forceinline__ int ap_real_roots(const double (&p)[
         for (int i = 0; i < N; ++i) { dc[i] = c[i + 1] * (double)(i + 1); nxt[i] = 0.0; }
         dc[N] = 0.0;
         int n = 0;
-        double lo = -bound, flo = ap_horner<N>(c, lo);
+        double lo = -bound, flo = horner<N>(c, lo);
 #pragma unroll
         for (int s = 0; s < N - k; ++s) {                // the derivative above has at most N - k - 1 roots: at most N - k intervals
             if (s <= nprev) {
-                const double hi = s < nprev ? root[s] : bound, fhi = ap_horner<N>(c, hi);
+                const double hi = s < nprev ? root[s] : bound, fhi = horner<N>(c, hi);
                 if ((flo < 0.0 && fhi > 0.0) || (flo > 0.0 && fhi < 0.0)) {
                     double x0 = lo, x1 = hi;
 #pragma unroll 1
                     for (int it = 0; it < 64; ++it) {
-                        const double m = 0.5 * (x0 + x1), fm = ap_horner<N>(c, m);
+                        const double m = 0.5 * (x0 + x1), fm = horner<N>(c, m);
                         if ((fm < 0.0) == (flo < 0.0)) x0 = m; else x1 = m;
                     }
                     double z = 0.5 * (x0 + x1);
 #pragma unroll 1
                     for (int it = 0; it < 3; ++it) {
-                        const double zn = z - ap_horner<N>(c, z) / ap_horner<N>(dc, z);
+                        const double zn = z - horner<N>(c, z) / horner<N>(dc, z);
                         if (zn >= x0 && zn <= x1) z = zn;
                     }
 #pragma unroll
@@ -183,7 +177,6 @@ template <int N> __device__ __forceinline__ int ap_real_roots(const double (&p)[
     return nprev;
 }
 
-__device__ __forceinline__ float ap_bearing(float x, float c, float f) { return (x - c) / f; }
 __device__ __forceinline__ void ap_cross(const double (&u)[3], const double (&v)[3], double (&w)[3]) {
     w[0] = u[1] * v[2] - u[2] * v[1]; w[1] = u[2] * v[0] - u[0] * v[2]; w[2] = u[0] * v[1] - u[1] * v[0];
 }
@@ -208,7 +201,7 @@ __device__ __forceinline__ void ap_p3p(const float (&q)[3][5], const float (&cam
     double f[3][3], P[3][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const double bx = (double)ap_bearing(q[k][0], cam[2], cam[0]), by = (double)ap_bearing(q[k][1], cam[3], cam[1]);
+        const double bx = (double)bearing(q[k][0], cam[2], cam[0]), by = (double)bearing(q[k][1], cam[3], cam[1]);
         const double n = sqrt((bx * bx + by * by) + 1.0);
         f[k][0] = bx / n; f[k][1] = by / n; f[k][2] = 1.0 / n;
 #pragma unroll
@@ -362,16 +355,10 @@ template <bool GIVEN> __global__ __launch_bounds__(TV_THREADS) void ap_score_ker
     unsigned long long key = 0ull;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const unsigned long long kr = cnt[r] > 0 ? ((unsigned long long)cnt[r] << 20) | ((unsigned long long)(0xFFFFu - (unsigned)hyp) << 4) | (unsigned long long)(15u - (unsigned)r) : 0ull;
+        const unsigned long long kr = PoseKey::make(cnt[r], hyp, r);
         key = kr > key ? kr : key;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned hi = (unsigned)__shfl_xor((int)(key >> 32), o, 64), lo = (unsigned)__shfl_xor((int)(key & 0xFFFFFFFFull), o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        key = other > key ? other : key;
-    }
-    if ((tid & 63) == 0 && key) atomicMax(&a.head[g].key, key);
+    publish_winner(key, &a.head[g].key);
 }
 
 // ------------------------------------------------------------------ finalise: one workgroup per problem
@@ -443,7 +430,7 @@ template <bool GIVEN> __global__ __launch_bounds__(TV_THREADS) void ap_finalise_
     const long long at = (long long)sp.beg * n0;
     const f32x4* ca = a.ca + at; const f32x2* cb = a.cb + at; const int* rows = a.rows + at;
     const unsigned long long key = h.key;
-    const int hyp = 0xFFFF - (int)((key >> 4) & 0xFFFFull), root = 15 - (int)(key & 15ull);
+    const int hyp = PoseKey::hyp_of(key), root = PoseKey::root_of(key);
     // every pair of the problem: its status, an all-false mask, no match, no inlier
     for (int place = sp.beg; place < sp.end; ++place) {
         const int pair = ap_pair(a, place);
@@ -485,9 +472,11 @@ template <bool GIVEN> __global__ __launch_bounds__(TV_THREADS) void ap_finalise_
                 double P[12];
 #pragma unroll
                 for (int e = 0; e < 12; ++e) P[e] = pose[e];
-                double acc[27];
+                double acc[21], rhs[6];                 // the upper triangle of J^T J, and J^T r
 #pragma unroll
-                for (int e = 0; e < 27; ++e) acc[e] = 0.0;
+                for (int e = 0; e < 21; ++e) acc[e] = 0.0;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) rhs[e] = 0.0;
                 for (int k = tid; k < S; k += TV_THREADS) {
                     const f32x4 c = ca[k];
                     const float Zf = cb[k][0];
@@ -499,29 +488,15 @@ template <bool GIVEN> __global__ __launch_bounds__(TV_THREADS) void ap_finalise_
                     const double r0 = (fx * px * iz + cx) - (double)c[0], r1 = (fy * py * iz + cy) - (double)c[1];
                     const double J0[6] = {jb * py, ja * pz - jb * px, -(ja * py), ja, 0.0, jb};
                     const double J1[6] = {jd * py - jc * pz, -(jd * px), jc * px, 0.0, jc, jd};
-                    int e = 0;
+                    accumulate_upper2<6>(acc, J0, J1);
 #pragma unroll
-                    for (int p = 0; p < 6; ++p)
-#pragma unroll
-                        for (int q = p; q < 6; ++q) { acc[e] += J0[p] * J0[q] + J1[p] * J1[q]; ++e; }
-#pragma unroll
-                    for (int p = 0; p < 6; ++p) acc[21 + p] += J0[p] * r0 + J1[p] * r1;
+                    for (int p = 0; p < 6; ++p) rhs[p] += J0[p] * r0 + J1[p] * r1;
                 }
-                {
-                    int e = 0;
+                reduce_upper<6>(acc, A, 7, red4);
 #pragma unroll
-                    for (int p = 0; p < 6; ++p)
-#pragma unroll
-                        for (int q = p; q < 6; ++q) {
-                            const double s = block_sum(acc[e], red4);
-                            if (tid == 0) { A[p * 7 + q] = s; A[q * 7 + p] = s; }
-                            ++e;
-                        }
-#pragma unroll
-                    for (int p = 0; p < 6; ++p) {
-                        const double s = block_sum(acc[21 + p], red4);
-                        if (tid == 0) A[p * 7 + 6] = -s;
-                    }
+                for (int p = 0; p < 6; ++p) {
+                    const double s = block_sum(rhs[p], red4);
+                    if (tid == 0) A[p * 7 + 6] = -s;
                 }
                 if (tid == 0) flag = ap_gn_update(A, pose) ? 1 : 0;
                 __syncthreads();
@@ -586,23 +561,10 @@ int64_t lg_abspose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypoth
 }
 
 int lg_abspose_estimate(const lg_abspose_io* io, void* hip_stream) {
-    if (!io) return set_error(LG_ERR_INVALID, "lg_abspose_estimate: null io");
     ApLayout L;
-    if (const char* why = ap_layout(io->pairs, io->n0, io->num_hypotheses, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_abspose_estimate: ") + why);
-    if (const char* why = keypoint_counts_error(0, io->n1)) return set_error(LG_ERR_INVALID, std::string("lg_abspose_estimate: ") + why);
-    if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return set_error(LG_ERR_INVALID, "lg_abspose_estimate: threshold must be > 0 (and finite)");
+    if (const int rc = check_estimator_call("lg_abspose_estimate", "lg_abspose_workspace_bytes", io, L)) return rc;
     const bool indexed = io->flags & LG_FLAG_INDEXED, grouped = io->flags & LG_ABSPOSE_GROUPED, given = io->flags & LG_ABSPOSE_GIVEN_POSES;
     const int P = io->pairs, n0 = io->n0, n1 = io->n1;
-    if (const int rc = check_pair_list("lg_abspose_estimate", io->flags, io->index0, io->index1, io->images0, io->images1)) return rc;
-    if (!io->cameras0 || !io->rotations || !io->translations || !io->num_inliers || !io->pair_num_inliers || !io->status || (given && !io->poses_in) ||
-        (n0 && (!io->inliers0 || !io->matches0 || !io->kpts0)) || (n0 && n1 && !io->points3d1))
-        return set_error(LG_ERR_INVALID, "lg_abspose_estimate: null pointer among kpts0, points3d1, matches0, cameras0, poses_in (LG_ABSPOSE_GIVEN_POSES), rotations, "
-                                         "translations, num_inliers, inliers0, pair_num_inliers, status");
-    if (grouped && (!io->group_offsets || !io->group_pairs))
-        return set_error(LG_ERR_INVALID, "lg_abspose_estimate: null pointer: LG_ABSPOSE_GROUPED needs group_offsets and group_pairs");
-    if (grouped && P > 0 && (io->groups < 1 || io->groups > P))
-        return set_error(LG_ERR_INVALID, "lg_abspose_estimate: with LG_ABSPOSE_GROUPED groups must lie in [1, pairs]");
-    if (const int rc = check_workspace("lg_abspose_estimate", "lg_abspose_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
     if (P == 0) return LG_OK;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);

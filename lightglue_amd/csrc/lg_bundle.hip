@@ -77,7 +77,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
         const int k = (int)g;
         const float* c = a.cameras + (long long)k * 4;
         const float* p = a.poses + (long long)k * 12;
-        bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f;
+        bool ok = camera_ok(c);
 #pragma unroll
         for (int e = 0; e < 12; ++e) ok = ok && isfinite(p[e]);
         BaImage im{};

@@ -231,6 +231,8 @@ __device__ __forceinline__ int source_image(const PairIndex& px, int pair, int i
 }
 // live keypoint rows of `image` of a store of n-row images: num[image] clamped into [0, n]; a null `num` means n
 __device__ __forceinline__ int live_rows(const int* num, int image, int n) { return num ? min(max(num[image], 0), n) : n; }
+// THE camera rule of the geometry entry points (LG_ERR_CAMERA): a pinhole camera c = (fx, fy, cx, cy) with every entry finite and both focal lengths > 0
+__device__ __forceinline__ bool camera_ok(const float* c) { return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f; }
 
 // ---- 256-thread workgroups (4 waves); every thread calls.  One round of an ORDERED compaction: the slot of this thread's item = `base` + the takers among
 // the threads below it; `base` advances by the round's takers, so rounds over ascending items fill a list in ascending order.  wsum: __shared__ int[4].  Two

@@ -1,5 +1,6 @@
 // lightglue_amd — the host side the entry points over a pair list or a caller's workspace share (lg_engine_forward, lg_nn_match, lg_twoview_verify,
-// lg_sift_filter): their refusals, the carving of a workspace, the stateless entry points' layouts, the cut of a pair list into launches.  Host-only C++17
+// lg_relpose_estimate, lg_abspose_estimate, lg_sift_filter): their refusals, the carving of a workspace, the stateless entry points' layouts, the cut of a pair
+// list into launches, and the whole opening of a call of the three hypothesise-and-verify estimators (check_estimator_call).  Host-only C++17
 // like lg_forward_plan.h (no HIP header, no device type): tests/cpp/host_call_check.cpp walks it with any host compiler, and under its address sanitizer.
 #pragma once
 #include <cstdint>
@@ -53,13 +54,20 @@ inline const char* nn_layout(long long images0, long long images1, int n0, int n
     L.ws0 = bp.take(L.rows0 * dim * 4); L.ws1 = bp.take(L.rows1 * dim * 4); L.touched0 = bp.take(images0); L.touched1 = bp.take(images1); L.total = bp.used;
     return nullptr;
 }
+// the three hypothesise-and-verify estimators: the budget, and what their layouts refuse first (the pair count, n0, flag bits outside `known`)
+inline const char* hypothesis_budget_error(long long num_hypotheses) {
+    return num_hypotheses < 256 || num_hypotheses > 65536 || num_hypotheses % 256 ? "num_hypotheses must be a multiple of 256 in [256, 65536]" : nullptr;
+}
+inline const char* pair_rows_error(long long pairs, int n0, uint32_t flags, uint32_t known, const char* undefined_bits) {
+    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
+    if (const char* why = keypoint_counts_error(n0)) return why;
+    return flags & ~known ? undefined_bits : nullptr;
+}
 // lg_twoview_verify: one 32-byte record per pair, the correspondence list (16 bytes per row) and its image-0 rows (4 bytes per row) of every pair
 constexpr uint32_t TV_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_TWOVIEW_HOMOGRAPHY | LG_TWOVIEW_FUNDAMENTAL | LG_TWOVIEW_REFINE | LG_TWOVIEW_GIVEN_MODELS;
 struct TvLayout { long long head, corr, rows, total; };
 inline const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& L) {
-    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
-    if (const char* why = keypoint_counts_error(n0)) return why;
-    if (flags & ~TV_KNOWN_FLAGS) return "undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)";
+    if (const char* why = pair_rows_error(pairs, n0, flags, TV_KNOWN_FLAGS, "undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)")) return why;
     if (!(flags & LG_TWOVIEW_HOMOGRAPHY) == !(flags & LG_TWOVIEW_FUNDAMENTAL)) return "exactly one of LG_TWOVIEW_HOMOGRAPHY and LG_TWOVIEW_FUNDAMENTAL must be set";
     Bump bp;
     L.head = bp.take(pairs * 32); L.corr = bp.take(pairs * n0 * 16); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
@@ -69,13 +77,8 @@ inline const char* tv_layout(long long pairs, int n0, uint32_t flags, TvLayout& 
 // LG_RELPOSE_ROOTS x 9 floats per hypothesis and pair
 constexpr uint32_t RP_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_RELPOSE_REFINE;
 struct RpLayout { long long head, ext, corr, rows, cand, total; };
-inline const char* hypothesis_budget_error(long long num_hypotheses) {
-    return num_hypotheses < 256 || num_hypotheses > 65536 || num_hypotheses % 256 ? "num_hypotheses must be a multiple of 256 in [256, 65536]" : nullptr;
-}
 inline const char* rp_layout(long long pairs, int n0, long long num_hypotheses, uint32_t flags, RpLayout& L) {
-    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
-    if (const char* why = keypoint_counts_error(n0)) return why;
-    if (flags & ~RP_KNOWN_FLAGS) return "undefined flag bits (the pose estimator reads LG_FLAG_INDEXED and LG_RELPOSE_REFINE)";
+    if (const char* why = pair_rows_error(pairs, n0, flags, RP_KNOWN_FLAGS, "undefined flag bits (the pose estimator reads LG_FLAG_INDEXED and LG_RELPOSE_REFINE)")) return why;
     if (const char* why = hypothesis_budget_error(num_hypotheses)) return why;
     Bump bp;
     L.head = bp.take(pairs * 32); L.ext = bp.take(pairs * 48); L.corr = bp.take(pairs * n0 * 16); L.rows = bp.take(pairs * n0 * 4);
@@ -87,15 +90,57 @@ inline const char* rp_layout(long long pairs, int n0, long long num_hypotheses, 
 constexpr uint32_t AP_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_ABSPOSE_REFINE | LG_ABSPOSE_GROUPED | LG_ABSPOSE_GIVEN_POSES;
 struct ApLayout { long long head, ca, cb, rows, total; };
 inline const char* ap_layout(long long pairs, int n0, long long num_hypotheses, uint32_t flags, ApLayout& L) {
-    if (pairs < 0 || pairs > 0x7FFFFFFFLL) return "the pair count must lie in [0, 2^31 - 1]";
-    if (const char* why = keypoint_counts_error(n0)) return why;
-    if (flags & ~AP_KNOWN_FLAGS) return "undefined flag bits (the absolute-pose estimator reads LG_FLAG_INDEXED and the LG_ABSPOSE_* bits)";
+    if (const char* why = pair_rows_error(pairs, n0, flags, AP_KNOWN_FLAGS, "undefined flag bits (the absolute-pose estimator reads LG_FLAG_INDEXED and the LG_ABSPOSE_* bits)"))
+        return why;
     if (const char* why = hypothesis_budget_error(num_hypotheses)) return why;
     if ((flags & LG_ABSPOSE_GROUPED) && pairs * n0 > LG_MAX_ROWS) return "with LG_ABSPOSE_GROUPED pairs x n0 must not exceed LG_MAX_ROWS";
     Bump bp;
     L.head = bp.take(pairs * 64); L.ca = bp.take(pairs * n0 * 16); L.cb = bp.take(pairs * n0 * 8); L.rows = bp.take(pairs * n0 * 4); L.total = bp.used;
     return nullptr;
 }
+// ---------------------------------------------------------------- the opening of a call of lg_twoview_verify / lg_relpose_estimate / lg_abspose_estimate.  What differs
+// per entry point is its layout and the pointers it needs, one overload each; the refusals and their order are written once
+inline const char* io_layout(const lg_twoview_io& io, TvLayout& L) { return tv_layout(io.pairs, io.n0, io.flags, L); }
+inline const char* io_layout(const lg_relpose_io& io, RpLayout& L) { return rp_layout(io.pairs, io.n0, io.num_hypotheses, io.flags, L); }
+inline const char* io_layout(const lg_abspose_io& io, ApLayout& L) { return ap_layout(io.pairs, io.n0, io.num_hypotheses, io.flags, L); }
+inline const char* io_pointers_error(const lg_twoview_io& io) {
+    const int n0 = io.n0, n1 = io.n1;
+    if (!io.models || !io.num_inliers || !io.status || (n0 && (!io.inliers0 || !io.matches0)) || (n0 && n1 && (!io.kpts0 || !io.kpts1)) ||
+        ((io.flags & LG_TWOVIEW_GIVEN_MODELS) && !io.models_in))
+        return "null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status";
+    return nullptr;
+}
+inline const char* io_pointers_error(const lg_relpose_io& io) {
+    const int n0 = io.n0, n1 = io.n1;
+    if (!io.cameras0 || !io.cameras1 || !io.rotations || !io.translations || !io.essentials || !io.models || !io.num_inliers || !io.num_in_front || !io.status ||
+        (n0 && (!io.inliers0 || !io.matches0)) || (n0 && n1 && (!io.kpts0 || !io.kpts1)))
+        return "null pointer among kpts0, kpts1, matches0, cameras0, cameras1, rotations, translations, essentials, models, inliers0, num_inliers, num_in_front, status";
+    return nullptr;
+}
+inline const char* io_pointers_error(const lg_abspose_io& io) {
+    const int n0 = io.n0, n1 = io.n1;
+    const bool grouped = io.flags & LG_ABSPOSE_GROUPED;
+    if (!io.cameras0 || !io.rotations || !io.translations || !io.num_inliers || !io.pair_num_inliers || !io.status || ((io.flags & LG_ABSPOSE_GIVEN_POSES) && !io.poses_in) ||
+        (n0 && (!io.inliers0 || !io.matches0 || !io.kpts0)) || (n0 && n1 && !io.points3d1))
+        return "null pointer among kpts0, points3d1, matches0, cameras0, poses_in (LG_ABSPOSE_GIVEN_POSES), rotations, translations, num_inliers, inliers0, pair_num_inliers, status";
+    if (grouped && (!io.group_offsets || !io.group_pairs)) return "null pointer: LG_ABSPOSE_GROUPED needs group_offsets and group_pairs";
+    if (grouped && io.pairs > 0 && (io.groups < 1 || io.groups > io.pairs)) return "with LG_ABSPOSE_GROUPED groups must lie in [1, pairs]";
+    return nullptr;
+}
+// LG_OK and the layout in L, or the first refusal in this order: null io, the layout's, n1, the hypothesis budget, the threshold, the pair list, the entry
+// point's pointers, the workspace (`size_function` names what sizes it)
+template <class IO, class Layout> int check_estimator_call(const char* stage, const char* size_function, const IO* io, Layout& L) {
+    const auto refuse = [stage](const char* why) { return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why); };
+    if (!io) return refuse("null io");
+    if (const char* why = io_layout(*io, L)) return refuse(why);
+    if (const char* why = keypoint_counts_error(0, io->n1)) return refuse(why);
+    if (const char* why = hypothesis_budget_error(io->num_hypotheses)) return refuse(why);       // two-view only: the pose layouts have refused it already
+    if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return refuse("threshold must be > 0 (and finite)");
+    if (const int rc = check_pair_list(stage, io->flags, io->index0, io->index1, io->images0, io->images1)) return rc;
+    if (const char* why = io_pointers_error(*io)) return refuse(why);
+    return check_workspace(stage, size_function, io->workspace, io->workspace_bytes, L.total);
+}
+
 // lg_triangulate: a 256-byte record of the call, a 160-byte record per image, seven int32 per node (parent, root, count, list offset, component, fill cursor,
 // list entry) and, per possible track (at most every second node), its root, state, dense id and (X, Y, Z, error)
 constexpr uint32_t TRI_KNOWN_FLAGS = LG_TRI_REFINE | LG_TRI_TRACKS_ONLY;

@@ -9,12 +9,13 @@
 //   rp_finalise  one workgroup per pair: the winner re-read from the workspace, the optional fp64 refit on the essential manifold, mask, count, F, E, and the
 //                pose among the four decompositions by the cheirality count over the inliers.
 // The per-lane arrays of the solver (the 10 x 20 system alone is 1600 bytes) are indexed at run time and live in scratch memory: profiles/relative_pose.md
-// has the compiler's figures.  Everything shared with the verifier is lg_twoview_common.h's; the refusals and the workspace layout (RpLayout) are lg_host_call.h's.
-#include <string>
-
+// has the compiler's figures.  Everything shared with the verifier and the absolute pose is lg_ransac_common.h's: the compaction, the sampler, bearings, horner<N> (the
+// degree-10 root finder over it is this file's), det3 / ata3, the tile scoring loop, the winner's key (PoseKey, publish_winner), the Hartley normalisation (here over bearings), the F refit up to its
+// null vector, the keep-if-not-worse recount and the mask; the camera rule is lg_common.h's.  The refusals (check_estimator_call) and the workspace layout (RpLayout)
+// are lg_host_call.h's.  What is the estimator's own is here: the 5-point solver, the projection onto the essential manifold, the decomposition and the cheirality count.
 #include "lg_host_call.h"
 #include "lg_kernels.h"
-#include "lg_twoview_common.h"
+#include "lg_ransac_common.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -38,8 +39,6 @@ struct RpArgs {
 };
 
 // ------------------------------------------------------------------ compaction: one workgroup per pair
-__device__ __forceinline__ bool rp_camera_ok(const float* c) { return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f; }
-
 __global__ __launch_bounds__(TV_THREADS) void rp_compact_kernel(RpArgs a) {
     const int pair = a.pair0 + blockIdx.x;
     const long long at = (long long)pair * a.src.n0;
@@ -52,7 +51,7 @@ __global__ __launch_bounds__(TV_THREADS) void rp_compact_kernel(RpArgs a) {
         if (src.ok) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { x.cam0[e] = a.cameras0[(long long)src.i0 * 4 + e]; x.cam1[e] = a.cameras1[(long long)src.i1 * 4 + e]; }
-            x.bad = rp_camera_ok(x.cam0) && rp_camera_ok(x.cam1) ? 0 : 1;
+            x.bad = camera_ok(x.cam0) && camera_ok(x.cam1) ? 0 : 1;
         }
         if (x.bad) h.count = 0;                          // an empty pair to every later launch
         a.head[pair] = h;
@@ -89,18 +88,9 @@ __device__ void rp_minor(const double (&N)[4][9], int ea, int eb, int ec, int ed
     for (int e = 0; e < 10; ++e) q[e] = 0.0;
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) q[RP_QI[i][j]] += N[i][ea] * N[j][eb] - N[i][ec] * N[j][ed];
 }
-__device__ __forceinline__ double rp_horner(const double* c, int d, double z) {
-    double v = c[d];
-    for (int i = d - 1; i >= 0; --i) v = v * z + c[i];
-    return v;
-}
-__device__ __forceinline__ double rp_horner10(const double (&c)[11], double z) {
-    double v = c[10];
-#pragma unroll
-    for (int i = 9; i >= 0; --i) v = v * z + c[i];
-    return v;
-}
-// the real roots of p (degree 10, p[10] != 0) in ascending order: the roots of the k-th derivative lie one in each interval between those of the (k + 1)-th
+// the real roots of p (degree 10, p[10] != 0) in ascending order: the roots of the k-th derivative lie one in each interval between those of the (k + 1)-th.  Rolled over
+// the derivative order, prev[] / root[] indexed at run time (the solver's arrays live in scratch anyway); lg_abspose.hip's ap_real_roots<N> is the same method fully
+// unrolled, which P3P needs to stay out of scratch and which costs this kernel time at degree 10 (profiles/ab_ransac_steps.md): two root finders over one horner<N>
 __device__ int rp_real_roots(const double (&p)[11], double (&root)[10]) {
     if (!(fabs(p[10]) > 0.0)) return 0;
     double bound = 0.0;
@@ -126,18 +116,18 @@ __device__ int rp_real_roots(const double (&p)[11], double (&root)[10]) {
         for (int i = 0; i < 10; ++i) dc[i] = c[i + 1] * (double)(i + 1);
         dc[10] = 0.0;
         n = 0;
-        double lo = -bound, flo = rp_horner10(c, lo);
+        double lo = -bound, flo = horner<10>(c, lo);
         for (int s = 0; s <= nprev; ++s) {
-            const double hi = s < nprev ? prev[s] : bound, fhi = rp_horner10(c, hi);
+            const double hi = s < nprev ? prev[s] : bound, fhi = horner<10>(c, hi);
             if ((flo < 0.0 && fhi > 0.0) || (flo > 0.0 && fhi < 0.0)) {
                 double a = lo, b = hi;
                 for (int it = 0; it < 64; ++it) {
-                    const double m = 0.5 * (a + b), fm = rp_horner10(c, m);
+                    const double m = 0.5 * (a + b), fm = horner<10>(c, m);
                     if ((fm < 0.0) == (flo < 0.0)) a = m; else b = m;
                 }
                 double z = 0.5 * (a + b);
                 for (int it = 0; it < 3; ++it) {
-                    const double zn = z - rp_horner10(c, z) / rp_horner10(dc, z);
+                    const double zn = z - horner<10>(c, z) / horner<10>(dc, z);
                     if (zn >= a && zn <= b) z = zn;
                 }
                 root[n++] = z;
@@ -228,7 +218,7 @@ __device__ int rp_five_point(const double (&q)[5][4], double (&N)[4][9], double 
     for (int k = 0; k < n; ++k) {
         const double z = root[k];
         double v[3][3];
-        for (int r = 0; r < 3; ++r) { v[r][0] = rp_horner(bx[r], 3, z); v[r][1] = rp_horner(by[r], 3, z); v[r][2] = rp_horner(b1[r], 4, z); }
+        for (int r = 0; r < 3; ++r) { v[r][0] = horner<3>(bx[r], z); v[r][1] = horner<3>(by[r], z); v[r][2] = horner<4>(b1[r], z); }
         double best[3] = {0.0, 0.0, 0.0}, len = -1.0;
         for (int r = 0; r < 3; ++r) {                    // the row pairs (0, 1), (0, 2), (1, 2)
             const int i = r == 2 ? 1 : 0, j = r == 0 ? 1 : 2;
@@ -255,7 +245,6 @@ __device__ bool rp_candidate(const double (&E)[9], const float* cam0, const floa
     }
     return tv_unit(m);
 }
-__device__ __forceinline__ float rp_bearing(float x, float c, float f) { return (x - c) / f; }
 
 __global__ __launch_bounds__(RP_SOLVE_THREADS) void rp_solve_kernel(RpArgs a) {
     const int pair = a.pair0 + blockIdx.x, hyp = blockIdx.y * RP_SOLVE_THREADS + threadIdx.x;
@@ -270,9 +259,8 @@ __global__ __launch_bounds__(RP_SOLVE_THREADS) void rp_solve_kernel(RpArgs a) {
         tv_sample<5>(a.seed, (unsigned)hyp, h.count, pick);
         double q[5][4];
         for (int i = 0; i < 5; ++i) {
-            const f32x4 c = corr[pick[i]];
-            q[i][0] = rp_bearing(c[0], x.cam0[2], x.cam0[0]); q[i][1] = rp_bearing(c[1], x.cam0[3], x.cam0[1]);
-            q[i][2] = rp_bearing(c[2], x.cam1[2], x.cam1[0]); q[i][3] = rp_bearing(c[3], x.cam1[3], x.cam1[1]);
+            const f32x4 b = bearings(corr[pick[i]], x.cam0, x.cam1);
+            for (int e = 0; e < 4; ++e) q[i][e] = b[e];
         }
         n = rp_five_point(q, N, sol);
     }
@@ -303,20 +291,13 @@ __global__ __launch_bounds__(TV_THREADS) void rp_score_kernel(RpArgs a) {
     int pos[1] = {0}, neg[1] = {0};
     tv_score_tiles<TV_F, 1>(m, corr, S, a.t2, tile, pos, neg);
     const int count = valid ? pos[0] : 0;
-    unsigned long long key = count > 0 ? ((unsigned long long)count << 20) | ((unsigned long long)(0xFFFFu - (unsigned)hyp) << 4) | (unsigned long long)(15u - (unsigned)root) : 0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned hi = (unsigned)__shfl_xor((int)(key >> 32), o, 64), lo = (unsigned)__shfl_xor((int)(key & 0xFFFFFFFFull), o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        key = other > key ? other : key;
-    }
-    if ((tid & 63) == 0 && key) atomicMax(&a.ext[pair].key, key);
+    publish_winner(PoseKey::make(count, hyp, root), &a.ext[pair].key);
 }
 
 // ------------------------------------------------------------------ finalise: one workgroup per pair
 // E <- E (v1 v1^T + v2 v2^T) with both singular values 1 (v1, v2 the two largest eigenvectors of E^T E).  One lane; J3, V3: 9 doubles each
 __device__ bool rp_project_essential(double (&E)[9], double* J3, double* V3) {
-    for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) J3[p * 3 + q] = (E[p] * E[q] + E[3 + p] * E[3 + q]) + E[6 + p] * E[6 + q];
+    ata3(E, J3);
     const int c3 = tv_jacobi(J3, V3, 3);
     double out[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool ok = true;
@@ -352,7 +333,7 @@ __device__ void rp_decompose(const float (&e32)[9], double (&Ra)[9], double (&Rb
     for (int i = 1; i < 3; ++i) big = fabs(t0[i]) > fabs(big) ? t0[i] : big;
     const double nrm = sqrt((t0[0] * t0[0] + t0[1] * t0[1]) + t0[2] * t0[2]) * (big < 0.0 ? -1.0 : 1.0);
     for (int i = 0; i < 3; ++i) t0[i] = t0[i] / nrm;
-    for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) J3[p * 3 + q] = (e[p] * e[q] + e[3 + p] * e[3 + q]) + e[6 + p] * e[6 + q];
+    ata3(e, J3);
     const int d3 = tv_jacobi(J3, V3, 3);
     const double v3[3] = {V3[d3], V3[3 + d3], V3[6 + d3]};
     // with E = U diag(s1, s2, s3) V^T: -+[t0]x E + s t0 v3^T = U (W^T or W) diag(s1, s2, 1) V^T for the sign s that makes the determinant positive
@@ -361,8 +342,7 @@ __device__ void rp_decompose(const float (&e32)[9], double (&Ra)[9], double (&Rb
         Ra[c] = t0[0] * v3[c] - te0; Ra[3 + c] = t0[1] * v3[c] - te1; Ra[6 + c] = t0[2] * v3[c] - te2;
         Rb[c] = t0[0] * v3[c] + te0; Rb[3 + c] = t0[1] * v3[c] + te1; Rb[6 + c] = t0[2] * v3[c] + te2;
     }
-    const double da = (Ra[0] * (Ra[4] * Ra[8] - Ra[5] * Ra[7]) - Ra[1] * (Ra[3] * Ra[8] - Ra[5] * Ra[6])) + Ra[2] * (Ra[3] * Ra[7] - Ra[4] * Ra[6]);
-    const double db = (Rb[0] * (Rb[4] * Rb[8] - Rb[5] * Rb[7]) - Rb[1] * (Rb[3] * Rb[8] - Rb[5] * Rb[6])) + Rb[2] * (Rb[3] * Rb[7] - Rb[4] * Rb[6]);
+    const double da = det3<double>(Ra, Ra + 3, Ra + 6), db = det3<double>(Rb, Rb + 3, Rb + 6);
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) {
             if (da < 0.0) Ra[3 * r + c] = Ra[3 * r + c] - 2.0 * (t0[r] * v3[c]);
@@ -385,8 +365,9 @@ __global__ __launch_bounds__(TV_THREADS) void rp_finalise_kernel(RpArgs a) {
     const long long at = (long long)pair * n0;
     const f32x4* corr = a.corr + at; const int* rows = a.rows + at;
     const unsigned long long key = x.key;
-    const int hyp = 0xFFFF - (int)((key >> 4) & 0xFFFFull), root = 15 - (int)(key & 15ull);
+    const int hyp = PoseKey::hyp_of(key), root = PoseKey::root_of(key);
     for (int i = tid; i < n0; i += TV_THREADS) mask[i] = 0;
+    const auto to_bearings = [&x](const f32x4& c) { return bearings(c, x.cam0, x.cam1); };
     float fin[9];
 #pragma unroll
     for (int e = 0; e < 9; ++e) fin[e] = 0.f;
@@ -397,59 +378,11 @@ __global__ __launch_bounds__(TV_THREADS) void rp_finalise_kernel(RpArgs a) {
         for (int e = 0; e < 9; ++e) fin[e] = src[e];
         cur = tv_count<TV_F>(fin, corr, S, a.t2, red8);
         if (a.refine && cur.count >= 8) {
-            // Hartley normalisation of the bearings of either side over the whole list, sums in fp64
-            double sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
-            for (int k = tid; k < S; k += TV_THREADS) {
-                const f32x4 c = corr[k];
-                sx0 += rp_bearing(c[0], x.cam0[2], x.cam0[0]); sy0 += rp_bearing(c[1], x.cam0[3], x.cam0[1]);
-                sx1 += rp_bearing(c[2], x.cam1[2], x.cam1[0]); sy1 += rp_bearing(c[3], x.cam1[3], x.cam1[1]);
-            }
-            const double inv = 1.0 / S;
-            const double mx0 = block_sum(sx0, red4) * inv, my0 = block_sum(sy0, red4) * inv;
-            const double mx1 = block_sum(sx1, red4) * inv, my1 = block_sum(sy1, red4) * inv;
-            double d0 = 0, d1 = 0;
-            for (int k = tid; k < S; k += TV_THREADS) {
-                const f32x4 c = corr[k];
-                const double ax = rp_bearing(c[0], x.cam0[2], x.cam0[0]) - mx0, ay = rp_bearing(c[1], x.cam0[3], x.cam0[1]) - my0;
-                const double bx = rp_bearing(c[2], x.cam1[2], x.cam1[0]) - mx1, by = rp_bearing(c[3], x.cam1[3], x.cam1[1]) - my1;
-                d0 += sqrt(ax * ax + ay * ay); d1 += sqrt(bx * bx + by * by);
-            }
-            const double m0 = block_sum(d0, red4) * inv, m1 = block_sum(d1, red4) * inv;
-            const float hcx0 = (float)mx0, hcy0 = (float)my0, hs0 = m0 > 0 ? (float)(1.4142135623730951 / m0) : 1.f;
-            const float hcx1 = (float)mx1, hcy1 = (float)my1, hs1 = m1 > 0 ? (float)(1.4142135623730951 / m1) : 1.f;
-            // the normal matrix of the inliers in those coordinates, upper triangle, fp64
-            double acc[45];
-#pragma unroll
-            for (int e = 0; e < 45; ++e) acc[e] = 0.0;
-            for (int k = tid; k < S; k += TV_THREADS) {
-                const f32x4 c = corr[k];
-                if (tv_test<TV_F>(fin, c, a.t2) != cur.sign) continue;
-                const double bx0 = rp_bearing(c[0], x.cam0[2], x.cam0[0]), by0 = rp_bearing(c[1], x.cam0[3], x.cam0[1]);
-                const double bx1 = rp_bearing(c[2], x.cam1[2], x.cam1[0]), by1 = rp_bearing(c[3], x.cam1[3], x.cam1[1]);
-                const double px = (bx0 - hcx0) * hs0, py = (by0 - hcy0) * hs0, u = (bx1 - hcx1) * hs1, v = (by1 - hcy1) * hs1;
-                const double r1[9] = {u * px, u * py, u, v * px, v * py, v, px, py, 1.0};
-                int e = 0;
-#pragma unroll
-                for (int p = 0; p < 9; ++p)
-#pragma unroll
-                    for (int q = p; q < 9; ++q) { acc[e] += r1[p] * r1[q]; ++e; }
-            }
-            {
-                int e = 0;
-#pragma unroll
-                for (int p = 0; p < 9; ++p)
-#pragma unroll
-                    for (int q = p; q < 9; ++q) {
-                        const double s = block_sum(acc[e], red4);
-                        if (tid == 0) { JA[p * 9 + q] = s; JA[q * 9 + p] = s; }
-                        ++e;
-                    }
-            }
+            const Hartley hn = hartley(corr, S, to_bearings, red4);          // of the bearings of either side over the whole list
+            double f[9];
+            tv_null_vector<TV_F>(fin, cur.sign, corr, S, a.t2, hn, to_bearings, JA, JV, red4, f);
             if (tid == 0) {
-                const int col = tv_jacobi(JA, JV, 9);
-                double f[9];
-                for (int e = 0; e < 9; ++e) f[e] = JV[e * 9 + col];
-                tv_denormalise<TV_F, double>(f, (double)hcx0, (double)hcy0, (double)hs0, (double)hcx1, (double)hcy1, (double)hs1);
+                tv_denormalise<TV_F, double>(f, hn);
                 bool good = rp_project_essential(f, J3, V3);
                 float ref[9];
                 good = rp_candidate(f, x.cam0, x.cam1, ref) && good;
@@ -457,23 +390,12 @@ __global__ __launch_bounds__(TV_THREADS) void rp_finalise_kernel(RpArgs a) {
                 flag = good ? 1 : 0;
             }
             __syncthreads();
-            if (flag) {                                  // uniform
-                float ref[9];
-#pragma unroll
-                for (int e = 0; e < 9; ++e) ref[e] = model[e];
-                const TvCount again = tv_count<TV_F>(ref, corr, S, a.t2, red8);
-                if (again.count >= cur.count) {
-                    cur = again;
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) fin[e] = ref[e];
-                }
-            }
+            if (flag) tv_keep_if_not_worse<TV_F>(model, corr, S, a.t2, red8, cur, fin);        // uniform
         }
     }
     const bool empty = !key || cur.count == 0;
     __syncthreads();                                     // mask[] is zeroed
-    if (!empty)
-        for (int k = tid; k < S; k += TV_THREADS) if (tv_test<TV_F>(fin, corr[k], a.t2) == cur.sign) mask[rows[k]] = 1;
+    tv_mark_inliers<TV_F>(empty, fin, cur.sign, corr, rows, S, a.t2, mask);
     // E = K1^T F K0 of the returned F, unit norm, float32, output form; the two rotations and t0 of it
     if (tid == 0) {
         float e32[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -503,19 +425,15 @@ __global__ __launch_bounds__(TV_THREADS) void rp_finalise_kernel(RpArgs a) {
         flag = good ? 1 : 0;
     }
     __syncthreads();                                     // mask[], ess[], pose[], flag
-    for (int i = tid; i < n0; i += TV_THREADS) {
-        const unsigned char in = mask[i];
-        a.inliers0[at + i] = in;
-        if (a.matches0_out) a.matches0_out[at + i] = in ? a.src.matches0[at + i] : -1;
-    }
+    tv_write_rows(n0, mask, a.src.matches0 + at, a.inliers0 + at, a.matches0_out ? a.matches0_out + at : nullptr);
     const bool posed = flag != 0;                        // uniform
     int front[4] = {0, 0, 0, 0};
     if (posed) {
         for (int k = tid; k < S; k += TV_THREADS) {
             const f32x4 c = corr[k];
             if (tv_test<TV_F>(fin, c, a.t2) != cur.sign) continue;
-            const double b0[3] = {(double)rp_bearing(c[0], x.cam0[2], x.cam0[0]), (double)rp_bearing(c[1], x.cam0[3], x.cam0[1]), 1.0};
-            const double b1[3] = {(double)rp_bearing(c[2], x.cam1[2], x.cam1[0]), (double)rp_bearing(c[3], x.cam1[3], x.cam1[1]), 1.0};
+            const f32x4 b = to_bearings(c);
+            const double b0[3] = {(double)b[0], (double)b[1], 1.0}, b1[3] = {(double)b[2], (double)b[3], 1.0};
             const double bb = (b1[0] * b1[0] + b1[1] * b1[1]) + b1[2] * b1[2];
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
@@ -573,19 +491,10 @@ int64_t lg_relpose_workspace_bytes(int64_t pairs, int32_t n0, int32_t num_hypoth
 }
 
 int lg_relpose_estimate(const lg_relpose_io* io, void* hip_stream) {
-    if (!io) return set_error(LG_ERR_INVALID, "lg_relpose_estimate: null io");
     RpLayout L;
-    if (const char* why = rp_layout(io->pairs, io->n0, io->num_hypotheses, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_relpose_estimate: ") + why);
-    if (const char* why = keypoint_counts_error(0, io->n1)) return set_error(LG_ERR_INVALID, std::string("lg_relpose_estimate: ") + why);
-    if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return set_error(LG_ERR_INVALID, "lg_relpose_estimate: threshold must be > 0 (and finite)");
+    if (const int rc = check_estimator_call("lg_relpose_estimate", "lg_relpose_workspace_bytes", io, L)) return rc;
     const bool indexed = io->flags & LG_FLAG_INDEXED;
     const int P = io->pairs, n0 = io->n0, n1 = io->n1;
-    if (const int rc = check_pair_list("lg_relpose_estimate", io->flags, io->index0, io->index1, io->images0, io->images1)) return rc;
-    if (!io->cameras0 || !io->cameras1 || !io->rotations || !io->translations || !io->essentials || !io->models || !io->num_inliers || !io->num_in_front || !io->status ||
-        (n0 && (!io->inliers0 || !io->matches0)) || (n0 && n1 && (!io->kpts0 || !io->kpts1)))
-        return set_error(LG_ERR_INVALID, "lg_relpose_estimate: null pointer among kpts0, kpts1, matches0, cameras0, cameras1, rotations, translations, essentials, models, "
-                                         "inliers0, num_inliers, num_in_front, status");
-    if (const int rc = check_workspace("lg_relpose_estimate", "lg_relpose_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
     if (P == 0) return LG_OK;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);

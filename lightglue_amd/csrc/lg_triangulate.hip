@@ -44,10 +44,9 @@ struct TriArgs {
     float* points3d; long long* track_id; unsigned char* node_state; float* xyz; int* track_length; float* track_error; int* counts; int* status;
 };
 
-// the camera rule of one image: the relative pose's rule, and a finite pose
+// the camera rule of one image: camera_ok (lg_common.h: the rule of every geometry entry point), and a finite pose
 __device__ __forceinline__ bool tri_image_ok(const TriArgs& a, int k) {
-    const float* c = a.cameras + (long long)k * 4;
-    bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]) && c[0] > 0.f && c[1] > 0.f;
+    bool ok = camera_ok(a.cameras + (long long)k * 4);
     const float* p = a.poses + (long long)k * 12;
 #pragma unroll
     for (int e = 0; e < 12; ++e) ok = ok && isfinite(p[e]);

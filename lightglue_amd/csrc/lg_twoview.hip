@@ -7,15 +7,15 @@
 //                  inlier count, and the best of the pair is one atomicMax on (count, ~hypothesis, ~root);
 //   tv_finalise    one workgroup per pair: the winner recomputed from its hypothesis number, the optional fp64 least-squares refit, mask, count, model.
 // What a pair reads is lg_common.h's (PairIndex / pair_images, live_rows), and so are the compaction round (compact_slot) and the fixed-order block sum of the fp64
-// reductions (block_sum); the refusals, the workspace layout (TvLayout) and the cut of the pair list into launches are lg_host_call.h's.  The compaction, the
-// sampling hash, the model helpers, the inlier test, the tile scoring loop, the count and the Jacobi are lg_twoview_common.h's: lg_relpose.hip runs the same code.
+// reductions (block_sum); the refusals (check_estimator_call), the workspace layout (TvLayout) and the cut of the pair list into launches are lg_host_call.h's.
+// The compaction with its Hartley normalisation, the sampling hash, the model helpers, the inlier test, the tile scoring loop, the winner's key (TvKey,
+// publish_winner), the refit up to its null vector (tv_null_vector), the keep-if-not-worse recount, the count and the mask steps are lg_ransac_common.h's: lg_relpose.hip
+// runs the same code.  What is the verifier's own is here: the two minimal solvers, the rank-2 step of the F refit and the order of the launches.
 // The solvers are compiled without floating-point contraction and the scoring is written in explicit fmaf: a model and a decision are the same bits in
 // tv_hypothesis and tv_finalise, whatever the compiler would fuse in either.
-#include <string>
-
 #include "lg_host_call.h"
 #include "lg_kernels.h"
-#include "lg_twoview_common.h"
+#include "lg_ransac_common.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -75,9 +75,6 @@ __device__ __forceinline__ bool tv_solve_h(const f32x4 (&q)[4], float (&h)[9]) {
     return ok;
 }
 
-__device__ __forceinline__ float tv_det3(const float* r0, const float* r1, const float* r2) {
-    return (r0[0] * (r1[1] * r2[2] - r1[2] * r2[1]) - r0[1] * (r1[0] * r2[2] - r1[2] * r2[0])) + r0[2] * (r1[0] * r2[1] - r1[1] * r2[0]);
-}
 // the null space of 7 normalised correspondences as N1 + z N2 (N1[7] = 1, N2[8] = 1) and the real roots z of det = 0; returns their number, 0 for an invalid sample;
 // well[k]: root k is well conditioned
 __device__ __forceinline__ int tv_solve_f(const f32x4 (&q)[7], float (&n1)[9], float (&n2)[9], float (&z)[3], bool (&well)[3]) {
@@ -112,9 +109,9 @@ __device__ __forceinline__ int tv_solve_f(const f32x4 (&q)[7], float (&n1)[9], f
     for (int i = 0; i < 7; ++i) { n1[i] = -a[i][7]; n2[i] = -a[i][8]; }
     n1[7] = 1.f; n1[8] = 0.f; n2[7] = 0.f; n2[8] = 1.f;
     // det(N1 + z N2) = c0 + c1 z + c2 z^2 + c3 z^3 by multilinearity in the rows
-    const float c0 = tv_det3(n1, n1 + 3, n1 + 6), c3 = tv_det3(n2, n2 + 3, n2 + 6);
-    const float c1 = (tv_det3(n2, n1 + 3, n1 + 6) + tv_det3(n1, n2 + 3, n1 + 6)) + tv_det3(n1, n1 + 3, n2 + 6);
-    const float c2 = (tv_det3(n1, n2 + 3, n2 + 6) + tv_det3(n2, n1 + 3, n2 + 6)) + tv_det3(n2, n2 + 3, n1 + 6);
+    const float c0 = det3(n1, n1 + 3, n1 + 6), c3 = det3(n2, n2 + 3, n2 + 6);
+    const float c1 = (det3(n2, n1 + 3, n1 + 6) + det3(n1, n2 + 3, n1 + 6)) + det3(n1, n1 + 3, n2 + 6);
+    const float c2 = (det3(n1, n2 + 3, n2 + 6) + det3(n2, n1 + 3, n2 + 6)) + det3(n2, n2 + 3, n1 + 6);
     ok = ok && fabsf(c3) > TV_EPS_CUBIC;
     const float A = c2 / c3, B = c1 / c3, C = c0 / c3;
     const float Q = (A * A - 3.f * B) / 9.f, R = ((2.f * A * A * A - 9.f * A * B) + 27.f * C) / 54.f;
@@ -153,7 +150,7 @@ template <int M> __device__ __forceinline__ void tv_gather(const TvHeader& h, co
 #pragma unroll
     for (int i = 0; i < M; ++i) {
         const f32x4 c = corr[pick[i]];
-        q[i] = f32x4{(c[0] - h.cx0) * h.s0, (c[1] - h.cy0) * h.s0, (c[2] - h.cx1) * h.s1, (c[3] - h.cy1) * h.s1};
+        q[i] = f32x4{(c[0] - h.n.cx0) * h.n.s0, (c[1] - h.n.cy0) * h.n.s0, (c[2] - h.n.cx1) * h.n.s1, (c[3] - h.n.cy1) * h.n.s1};
     }
 }
 // the models of hypothesis `hyp` of a pair, denormalised, unit norm: m[r] valid for r < the returned number (invalid ones in between are all zero, see valid[])
@@ -172,7 +169,7 @@ template <int KIND> __device__ __forceinline__ int tv_models(const TvArgs& a, co
         f32x4 q[4];
         tv_gather<4>(h, corr, a.seed, (unsigned)hyp, q);
         const bool ok = tv_solve_h(q, m[0]);
-        tv_denormalise<TV_H, float>(m[0], h.cx0, h.cy0, h.s0, h.cx1, h.cy1, h.s1);
+        tv_denormalise<TV_H, float>(m[0], h.n);
         valid[0] = tv_unit(m[0]) && ok;
         return 1;
     } else {
@@ -185,7 +182,7 @@ template <int KIND> __device__ __forceinline__ int tv_models(const TvArgs& a, co
         for (int r = 0; r < 3; ++r) {
 #pragma unroll
             for (int e = 0; e < 9; ++e) m[r][e] = n1[e] + z[r] * n2[e];
-            tv_denormalise<TV_F, float>(m[r], h.cx0, h.cy0, h.s0, h.cx1, h.cy1, h.s1);
+            tv_denormalise<TV_F, float>(m[r], h.n);
             valid[r] = tv_unit(m[r]) && well[r] && r < n;
         }
         return n > 0 ? n : 1;
@@ -208,12 +205,9 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_hypothesis_
 #pragma unroll
     for (int r = (KIND == TV_H ? 0 : 2); r >= 0; --r) {
         const int count = valid[r] ? max(pos[r], neg[r]) : 0;
-        const unsigned k = count > 0 ? ((unsigned)count << 18) | ((0xFFFFu - (unsigned)hyp) << 2) | (3u - (unsigned)r) : 0u;
-        key = max(key, k);
+        key = max(key, TvKey::make(count, hyp, r));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, o, 64));
-    if ((tid & 63) == 0 && key) atomicMax(&a.head[pair].key, key);
+    publish_winner(key, &a.head[pair].key);
 }
 
 // ------------------------------------------------------------------ finalise: one workgroup per pair
@@ -229,7 +223,7 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
     const long long at = (long long)pair * n0;
     const f32x4* corr = a.corr + at; const int* rows = a.rows + at;
     const unsigned key = h.key;
-    const int hyp = 0xFFFF - (int)((key >> 2) & 0xFFFFu), root = 3 - (int)(key & 3u);
+    const int hyp = TvKey::hyp_of(key), root = TvKey::root_of(key);
     for (int i = tid; i < n0; i += TV_THREADS) mask[i] = 0;
     float fin[9];
     TvCount cur{0, 1};
@@ -245,47 +239,11 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
         for (int e = 0; e < 9; ++e) fin[e] = model[0][e];
         cur = tv_count<KIND>(fin, corr, S, a.t2, red8);
         if (a.refine && cur.count >= (KIND == TV_H ? 4 : 8)) {
-            // the normal matrix of the inliers in the pair's normalised coordinates, upper triangle, fp64
-            double acc[45];
-#pragma unroll
-            for (int e = 0; e < 45; ++e) acc[e] = 0.0;
-            for (int k = tid; k < S; k += TV_THREADS) {
-                const f32x4 c = corr[k];
-                if (tv_test<KIND>(fin, c, a.t2) != cur.sign) continue;
-                const double x = ((double)c[0] - h.cx0) * h.s0, y = ((double)c[1] - h.cy0) * h.s0, u = ((double)c[2] - h.cx1) * h.s1, v = ((double)c[3] - h.cy1) * h.s1;
-                if (KIND == TV_H) {
-                    const double r1[9] = {-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u}, r2[9] = {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v};
-                    int e = 0;
-#pragma unroll
-                    for (int p = 0; p < 9; ++p)
-#pragma unroll
-                        for (int q = p; q < 9; ++q) { acc[e] += r1[p] * r1[q] + r2[p] * r2[q]; ++e; }
-                } else {
-                    const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
-                    int e = 0;
-#pragma unroll
-                    for (int p = 0; p < 9; ++p)
-#pragma unroll
-                        for (int q = p; q < 9; ++q) { acc[e] += r1[p] * r1[q]; ++e; }
-                }
-            }
-            {
-                int e = 0;
-#pragma unroll
-                for (int p = 0; p < 9; ++p)
-#pragma unroll
-                    for (int q = p; q < 9; ++q) {
-                        const double s = block_sum(acc[e], red4);
-                        if (tid == 0) { JA[p * 9 + q] = s; JA[q * 9 + p] = s; }
-                        ++e;
-                    }
-            }
+            double f[9];
+            tv_null_vector<KIND>(fin, cur.sign, corr, S, a.t2, h.n, [](const f32x4& c) { return c; }, JA, JV, red4, f);
             if (tid == 0) {
-                const int col = tv_jacobi(JA, JV, 9);
-                double f[9];
-                for (int e = 0; e < 9; ++e) f[e] = JV[e * 9 + col];
                 if (KIND == TV_F) {                      // rank 2: F - (F v3) v3^T, v3 the smallest eigenvector of F^T F
-                    for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) J3[p * 3 + q] = f[p] * f[q] + f[3 + p] * f[3 + q] + f[6 + p] * f[6 + q];
+                    ata3(f, J3);
                     const int c3 = tv_jacobi(J3, V3, 3);
                     const double v3[3] = {V3[c3], V3[3 + c3], V3[6 + c3]};
                     for (int r = 0; r < 3; ++r) {
@@ -293,7 +251,7 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
                         for (int c = 0; c < 3; ++c) f[3 * r + c] -= fv * v3[c];
                     }
                 }
-                tv_denormalise<KIND, double>(f, (double)h.cx0, (double)h.cy0, (double)h.s0, (double)h.cx1, (double)h.cy1, (double)h.s1);
+                tv_denormalise<KIND, double>(f, h.n);
                 double sq = 0;
                 for (int e = 0; e < 9; ++e) sq += f[e] * f[e];
                 const double nrm = sqrt(sq);
@@ -305,29 +263,14 @@ template <int KIND> __global__ __launch_bounds__(TV_THREADS) void tv_finalise_ke
                 flag = good ? 1 : 0;
             }
             __syncthreads();
-            if (flag) {                                  // uniform
-                float ref[9];
-#pragma unroll
-                for (int e = 0; e < 9; ++e) ref[e] = model[1][e];
-                const TvCount again = tv_count<KIND>(ref, corr, S, a.t2, red8);
-                if (again.count >= cur.count) {
-                    cur = again;
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) fin[e] = ref[e];
-                }
-            }
+            if (flag) tv_keep_if_not_worse<KIND>(model[1], corr, S, a.t2, red8, cur, fin);       // uniform
         }
     }
     const bool empty = !key || cur.count == 0;
     __syncthreads();                                     // mask[] is zeroed
-    if (!empty)
-        for (int k = tid; k < S; k += TV_THREADS) if (tv_test<KIND>(fin, corr[k], a.t2) == cur.sign) mask[rows[k]] = 1;
+    tv_mark_inliers<KIND>(empty, fin, cur.sign, corr, rows, S, a.t2, mask);
     __syncthreads();
-    for (int i = tid; i < n0; i += TV_THREADS) {
-        const unsigned char in = mask[i];
-        a.inliers0[at + i] = in;
-        if (a.matches0_out) a.matches0_out[at + i] = in ? a.src.matches0[at + i] : -1;
-    }
+    tv_write_rows(n0, mask, a.src.matches0 + at, a.inliers0 + at, a.matches0_out ? a.matches0_out + at : nullptr);
     if (tid == 0) {
         for (int e = 0; e < 9; ++e) a.models[(long long)pair * 9 + e] = empty ? 0.f : fin[e];      // in output form since it was made
         a.num_inliers[pair] = empty ? 0 : cur.count;
@@ -355,19 +298,10 @@ int64_t lg_twoview_workspace_bytes(int64_t pairs, int32_t n0, uint32_t flags) {
 }
 
 int lg_twoview_verify(const lg_twoview_io* io, void* hip_stream) {
-    if (!io) return set_error(LG_ERR_INVALID, "lg_twoview_verify: null io");
     TvLayout L;
-    if (const char* why = tv_layout(io->pairs, io->n0, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_twoview_verify: ") + why);
-    if (const char* why = keypoint_counts_error(0, io->n1)) return set_error(LG_ERR_INVALID, std::string("lg_twoview_verify: ") + why);
-    if (io->num_hypotheses < 256 || io->num_hypotheses > 65536 || io->num_hypotheses % 256)
-        return set_error(LG_ERR_INVALID, "lg_twoview_verify: num_hypotheses must be a multiple of 256 in [256, 65536]");
-    if (!(io->threshold > 0.f) || !(io->threshold <= 3.0e18f)) return set_error(LG_ERR_INVALID, "lg_twoview_verify: threshold must be > 0 (and finite)");
+    if (const int rc = check_estimator_call("lg_twoview_verify", "lg_twoview_workspace_bytes", io, L)) return rc;
     const bool indexed = io->flags & LG_FLAG_INDEXED, given = io->flags & LG_TWOVIEW_GIVEN_MODELS;
     const int P = io->pairs, n0 = io->n0, n1 = io->n1;
-    if (const int rc = check_pair_list("lg_twoview_verify", io->flags, io->index0, io->index1, io->images0, io->images1)) return rc;
-    if (!io->models || !io->num_inliers || !io->status || (n0 && (!io->inliers0 || !io->matches0)) || (n0 && n1 && (!io->kpts0 || !io->kpts1)) || (given && !io->models_in))
-        return set_error(LG_ERR_INVALID, "lg_twoview_verify: null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status");
-    if (const int rc = check_workspace("lg_twoview_verify", "lg_twoview_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
     if (P == 0) return LG_OK;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);

@@ -36,23 +36,13 @@ class RelativePoseEstimator(nn.Module):
 
     def __init__(self, threshold: float = 3.0, num_hypotheses: int = 1024, refine: bool = True, seed: int = 0):
         super().__init__()
-        if not float(threshold) > 0.0:
-            raise ValueError(f"threshold must be > 0, got {threshold!r}")
-        if int(num_hypotheses) % 256 or not 256 <= int(num_hypotheses) <= 65536:
-            raise ValueError(f"num_hypotheses must be a multiple of 256 in [256, 65536], got {num_hypotheses!r}")
-        if not 0 <= int(seed) < 2 ** 32:
-            raise ValueError(f"seed must lie in [0, 2^32), got {seed!r}")
-        self.threshold, self.num_hypotheses, self.refine, self.seed = float(threshold), int(num_hypotheses), bool(refine), int(seed)
+        self.threshold, self.num_hypotheses, self.seed = _call.ransac_settings(threshold, num_hypotheses, seed)
+        self.refine = bool(refine)
 
     # ------------------------------------------------------------------ the call path
     def _launch(self, device, s0, s1, P: int, index, result, cameras0, cameras1, return_candidates: bool = False) -> dict:
         """P pairs in ONE lg_relpose_estimate call on the current stream, then the dict behind the one host synchronisation of the call."""
-        if isinstance(result, _call.DeferredMatches):
-            result = result.result()
-        m0 = result["matches0"] if isinstance(result, dict) else result
-        assert torch.is_tensor(m0) and tuple(m0.shape) == (P, s0.N), f"matches0 must have shape [{P}, {s0.N}], got {tuple(m0.shape)}"
-        if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
-            m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+        m0 = _call.as_matches0(result, P, s0.N, device)
         cam0 = as_cameras(cameras0, s0.K, device, "cameras0")
         cam1 = cam0 if cameras1 is None and s1.K == s0.K else as_cameras(cameras0 if cameras1 is None else cameras1, s1.K, device, "cameras1")
         H = self.num_hypotheses
@@ -81,20 +71,12 @@ class RelativePoseEstimator(nn.Module):
                 _cabi.check(lib.lg_relpose_estimate(C.byref(io), C.c_void_p(stream.cuda_stream)))
             host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
         mask = inl.bool()
-        # the ragged lists without another synchronisation: a stable sort puts every pair's inlier rows first, in ascending order; their number is on the host
-        order = torch.sort((~mask).to(torch.uint8), dim=1, stable=True)[1]
-        listed = torch.stack([order, torch.gather(verified, 1, order)], -1)
-        matches = [listed[b, :c] for b, c in enumerate(host[0])]
+        matches = _call.ragged_matches(mask, verified, host[0])
         out = {"R": R, "t": t, "E": E, "models": F, "inliers0": mask, "num_inliers": ints[0].long(), "num_in_front": ints[3].long(), "matches0": verified,
                "matches": matches, "best_hypothesis": ints[1].long()}
         if return_candidates:
             out["candidates"] = cand
-        try:
-            _call.raise_on_status(host[2])
-        except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
-            err.outputs = out
-            raise
-        return out
+        return _call.raise_with_outputs(host[2], out)
 
     @torch.no_grad()
     def forward(self, data: dict, result, cameras0, cameras1) -> dict:

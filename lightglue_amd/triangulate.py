@@ -65,12 +65,7 @@ class Triangulator(nn.Module):
         pt = _call.pair_list(pairs, K, K, validate)
         P = int(pt.shape[0])
         index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None
-        if isinstance(result, _call.DeferredMatches):
-            result = result.result()
-        m0 = result["matches0"] if isinstance(result, dict) else result
-        assert torch.is_tensor(m0) and tuple(m0.shape) == (P, N), f"matches0 must have shape [{P}, {N}], got {tuple(m0.shape)}"
-        if m0.dtype is not torch.int64 or m0.device != device or not m0.is_contiguous():
-            m0 = m0.detach().to(device=device, dtype=torch.int64).contiguous()
+        m0 = _call.as_matches0(result, P, N, device)
         cam = pose = None
         if not tracks_only:
             cam, pose = as_cameras(cameras, K, device, "cameras"), as_poses(poses, K, device)
@@ -112,12 +107,7 @@ class Triangulator(nn.Module):
             out.update(num_outliers=host[9 + P], num_split=host[10 + P])
         if not tracks_only:
             out.update(points3d=pts, xyz=flat[:3 * T].view(T, 3), track_error=flat[3 * cap:3 * cap + T])
-        try:
-            _call.raise_on_status(host[9:9 + P])
-        except _cabi.LightGlueAmdError as err:       # the pairs with status LG_OK are complete: the error carries the call's outputs
-            err.outputs = out
-            raise
-        return out
+        return _call.raise_with_outputs(host[9:9 + P], out)
 
     @torch.no_grad()
     def triangulate(self, feats: dict, pairs, result, cameras, poses, *, validate: bool = True) -> dict:

@@ -1,7 +1,8 @@
 // Checks the host side the stateless entry points share (lightglue_amd/csrc/lg_host_call.h) without a GPU: every rule below is restated from
 // include/lightglue_amd.h, then asserted over a grid — the LG_FLAG_INDEXED refusal, the workspace refusals, the keypoint-count envelope, the three workspace
 // layouts (piece by piece: every piece at a 256-byte aligned offset behind the one before it, and the byte totals the entry points have always returned) and
-// the cut of a pair list into launches.  Stand-alone: built and run by tests/test_host_call_cpu.py; for a sanitizer run add -fsanitize=address,undefined.
+// the cut of a pair list into launches — and the opening of a call of the three estimators (check_estimator_call): every refusal in its order, with the exact
+// message, per entry point.  Stand-alone: built and run by tests/test_host_call_cpu.py; for a sanitizer run add -fsanitize=address,undefined.
 // Exit status 0 and "ok <checks>" on success, the first violated rule otherwise.
 #include <cstdio>
 #include <cstdlib>
@@ -142,9 +143,133 @@ void launch_rules() {
     CHECK(for_pair_launches(3 * PAIRS_PER_LAUNCH, [&](int, int) -> int { return ++calls == 2 ? LG_ERR_HIP : LG_OK; }) == LG_ERR_HIP && calls == 2, "a failed launch ends the list");
 }
 
+// The opening of a call of the three estimators (check_estimator_call): the refusals in their order, code and exact message (the texts are those the three
+// entry points have always set).  A call that violates refusal i AND every later one must be answered with refusal i, a valid call with LG_OK and the layout.
+char g_store[64];                                        // something non-null for every pointer field; never read
+void* const P = g_store;
+template <class T> T* ptr() { return reinterpret_cast<T*>(P); }
+
+template <class IO> void common_fields(IO& io, uint32_t flags) {
+    io.pairs = 3; io.n0 = 40; io.n1 = 50; io.images0 = 2; io.images1 = 2; io.flags = flags | LG_FLAG_INDEXED; io.threshold = 2.f; io.num_hypotheses = 512;
+    io.index0 = ptr<const int32_t>(); io.index1 = ptr<const int32_t>(); io.workspace = at(1 << 20);
+}
+// break(io, i): violate refusal i (1 = the layout's ... 7 = the workspace; 0, null io, is the caller's)
+template <class IO> void break_common(IO& io, int i) {
+    if (i == 1) io.pairs = -1;
+    if (i == 2) io.n1 = LG_MAX_KEYPOINTS + 1;
+    if (i == 3) io.num_hypotheses = 300;
+    if (i == 4) io.threshold = 0.f;
+    if (i == 5) io.images1 = 0;
+    if (i == 7) io.workspace = nullptr;
+}
+lg_twoview_io valid_twoview() {
+    lg_twoview_io io{};
+    common_fields(io, LG_TWOVIEW_FUNDAMENTAL | LG_TWOVIEW_REFINE);
+    io.kpts0 = io.kpts1 = ptr<const float>(); io.matches0 = ptr<const int64_t>(); io.models = ptr<float>(); io.inliers0 = ptr<uint8_t>();
+    io.num_inliers = ptr<int32_t>(); io.status = ptr<int32_t>();
+    return io;
+}
+lg_relpose_io valid_relpose() {
+    lg_relpose_io io{};
+    common_fields(io, LG_RELPOSE_REFINE);
+    io.kpts0 = io.kpts1 = io.cameras0 = io.cameras1 = ptr<const float>(); io.matches0 = ptr<const int64_t>();
+    io.rotations = io.translations = io.essentials = io.models = ptr<float>(); io.inliers0 = ptr<uint8_t>();
+    io.num_inliers = io.num_in_front = io.status = ptr<int32_t>();
+    return io;
+}
+lg_abspose_io valid_abspose() {
+    lg_abspose_io io{};
+    common_fields(io, LG_ABSPOSE_REFINE);
+    io.kpts0 = io.points3d1 = io.cameras0 = ptr<const float>(); io.matches0 = ptr<const int64_t>();
+    io.rotations = io.translations = ptr<float>(); io.inliers0 = ptr<uint8_t>(); io.num_inliers = io.pair_num_inliers = io.status = ptr<int32_t>();
+    return io;
+}
+
+// budget_first: the pose estimators' layouts depend on the budget and refuse it themselves, before n1; the verifier refuses it behind n1
+template <class IO, class Layout, class Break6>
+void walk_estimator(const char* stage, const char* size_function, IO (*valid)(), long long total, bool budget_first, const char* pointers, Break6 break6) {
+    const std::string s = std::string(stage) + ": ";
+    const std::string expect[8] = {
+        s + "null io", s + "the pair count must lie in [0, 2^31 - 1]", s + "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]", s + "num_hypotheses must be a multiple of 256 in [256, 65536]",
+        s + "threshold must be > 0 (and finite)", s + "LG_FLAG_INDEXED needs index0, index1 and images0, images1 >= 1", s + pointers, s + "null workspace"};
+    Layout L;
+    IO io = valid();
+    io.workspace_bytes = total;
+    g_msg.clear();
+    CHECK(check_estimator_call(stage, size_function, &io, L) == LG_OK && g_msg.empty() && L.total == total, "%s: a valid call, total %lld", stage, L.total);
+    CHECK(check_estimator_call(stage, size_function, static_cast<const IO*>(nullptr), L) == LG_ERR_INVALID && g_msg == expect[0], "%s: null io", stage);
+    const int order[7] = {1, budget_first ? 3 : 2, budget_first ? 2 : 3, 4, 5, 6, 7};
+    for (int first = 0; first < 7; ++first) {
+        io = valid();
+        io.workspace_bytes = total;
+        for (int k = first; k < 7; ++k) { break_common(io, order[k]); if (order[k] == 6) break6(io); }
+        g_msg.clear();
+        const std::string& want = expect[order[first]];
+        CHECK(check_estimator_call(stage, size_function, &io, L) == LG_ERR_INVALID && g_msg == want, "%s: refusal %d, expected \"%s\"", stage, order[first], want.c_str());
+    }
+    // the workspace's other two refusals
+    io = valid();
+    io.workspace_bytes = total - 1;
+    CHECK(check_estimator_call(stage, size_function, &io, L) == LG_ERR_INVALID &&
+          g_msg == s + "the workspace holds " + std::to_string(total - 1) + " bytes, " + size_function + " = " + std::to_string(total), "%s: small workspace", stage);
+    io.workspace_bytes = total; io.workspace = at((1 << 20) + 64);
+    CHECK(check_estimator_call(stage, size_function, &io, L) == LG_ERR_INVALID && g_msg == s + "the workspace must be 256-byte aligned", "%s: skewed workspace", stage);
+    // the threshold's other side, and the layout's further refusals come before n1
+    io = valid(); io.workspace_bytes = total; io.threshold = 4.0e18f;
+    CHECK(check_estimator_call(stage, size_function, &io, L) == LG_ERR_INVALID && g_msg == expect[4], "%s: a threshold beyond 3e18", stage);
+    io = valid(); io.workspace_bytes = total; io.n0 = -1; io.n1 = -1;
+    CHECK(check_estimator_call(stage, size_function, &io, L) == LG_ERR_INVALID && g_msg == expect[2], "%s: n0", stage);
+}
+
+void estimator_call_rules() {
+    const long long rows = 3 * 40;
+    walk_estimator<lg_twoview_io, TvLayout>("lg_twoview_verify", "lg_twoview_workspace_bytes", valid_twoview, up(3 * 32) + up(rows * 16) + up(rows * 4), false,
+        "null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status", [](lg_twoview_io& io) { io.status = nullptr; });
+    walk_estimator<lg_relpose_io, RpLayout>("lg_relpose_estimate", "lg_relpose_workspace_bytes", valid_relpose,
+        up(3 * 32) + up(3 * 48) + up(rows * 16) + up(rows * 4) + up(3LL * 512 * LG_RELPOSE_ROOTS * 36), true,
+        "null pointer among kpts0, kpts1, matches0, cameras0, cameras1, rotations, translations, essentials, models, inliers0, num_inliers, num_in_front, status",
+        [](lg_relpose_io& io) { io.cameras1 = nullptr; });
+    walk_estimator<lg_abspose_io, ApLayout>("lg_abspose_estimate", "lg_abspose_workspace_bytes", valid_abspose, up(3 * 64) + up(rows * 16) + up(rows * 8) + up(rows * 4), true,
+        "null pointer among kpts0, points3d1, matches0, cameras0, poses_in (LG_ABSPOSE_GIVEN_POSES), rotations, translations, num_inliers, inliers0, pair_num_inliers, status",
+        [](lg_abspose_io& io) { io.points3d1 = nullptr; });
+    // the refusals one entry point has alone, each at its place
+    TvLayout T; RpLayout R; ApLayout A;
+    lg_twoview_io tv = valid_twoview();
+    tv.workspace_bytes = 1 << 20; tv.flags |= LG_TWOVIEW_HOMOGRAPHY; tv.n1 = -1;
+    CHECK(check_estimator_call("lg_twoview_verify", "f", &tv, T) && g_msg == "lg_twoview_verify: exactly one of LG_TWOVIEW_HOMOGRAPHY and LG_TWOVIEW_FUNDAMENTAL must be set", "tv kinds");
+    tv = valid_twoview(); tv.workspace_bytes = 1 << 20; tv.flags |= 1u << 30;
+    CHECK(check_estimator_call("lg_twoview_verify", "f", &tv, T) && g_msg == "lg_twoview_verify: undefined flag bits (the verifier reads LG_FLAG_INDEXED and the LG_TWOVIEW_* bits)", "tv bits");
+    tv = valid_twoview(); tv.workspace_bytes = 1 << 20; tv.flags |= LG_TWOVIEW_GIVEN_MODELS;
+    CHECK(check_estimator_call("lg_twoview_verify", "f", &tv, T) && g_msg == "lg_twoview_verify: null pointer among kpts0, kpts1, matches0, models_in, models, inliers0, num_inliers, status", "tv models_in");
+    tv = valid_twoview(); tv.workspace_bytes = 1 << 20; tv.n1 = -1; tv.num_hypotheses = 0;          // the verifier's budget is refused behind n1 ...
+    CHECK(check_estimator_call("lg_twoview_verify", "f", &tv, T) && g_msg == "lg_twoview_verify: n0, n1 must lie in [0, LG_MAX_KEYPOINTS]", "tv: n1 before the budget");
+    lg_relpose_io rp = valid_relpose();
+    rp.workspace_bytes = 1 << 30; rp.n1 = -1; rp.num_hypotheses = 0;                                 // ... the pose estimators' with the layout, before it
+    CHECK(check_estimator_call("lg_relpose_estimate", "f", &rp, R) && g_msg == "lg_relpose_estimate: num_hypotheses must be a multiple of 256 in [256, 65536]", "rp: the budget before n1");
+    rp = valid_relpose(); rp.workspace_bytes = 1 << 30; rp.flags |= LG_TWOVIEW_HOMOGRAPHY;
+    CHECK(check_estimator_call("lg_relpose_estimate", "f", &rp, R) && g_msg == "lg_relpose_estimate: undefined flag bits (the pose estimator reads LG_FLAG_INDEXED and LG_RELPOSE_REFINE)", "rp bits");
+    lg_abspose_io ap = valid_abspose();
+    ap.workspace_bytes = 1 << 20; ap.n1 = -1; ap.num_hypotheses = 65536 + 256;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: num_hypotheses must be a multiple of 256 in [256, 65536]", "ap: the budget before n1");
+    ap = valid_abspose(); ap.workspace_bytes = 1 << 20; ap.flags |= 1u << 30;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: undefined flag bits (the absolute-pose estimator reads LG_FLAG_INDEXED and the LG_ABSPOSE_* bits)", "ap bits");
+    ap = valid_abspose(); ap.workspace_bytes = 1 << 20; ap.flags |= LG_ABSPOSE_GROUPED; ap.pairs = LG_MAX_ROWS / 40 + 1;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: with LG_ABSPOSE_GROUPED pairs x n0 must not exceed LG_MAX_ROWS", "ap grouped rows");
+    ap = valid_abspose(); ap.workspace_bytes = 1 << 20; ap.flags |= LG_ABSPOSE_GIVEN_POSES | LG_ABSPOSE_GROUPED;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: null pointer among kpts0, points3d1, matches0, cameras0, poses_in (LG_ABSPOSE_GIVEN_POSES), "
+          "rotations, translations, num_inliers, inliers0, pair_num_inliers, status", "ap poses_in");
+    ap.poses_in = ptr<const float>();
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: null pointer: LG_ABSPOSE_GROUPED needs group_offsets and group_pairs", "ap groups");
+    ap.group_offsets = ap.group_pairs = ptr<const int32_t>(); ap.groups = 4; ap.workspace = nullptr;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: with LG_ABSPOSE_GROUPED groups must lie in [1, pairs]", "ap group count");
+    ap.groups = 3;
+    CHECK(check_estimator_call("lg_abspose_estimate", "f", &ap, A) && g_msg == "lg_abspose_estimate: null workspace", "ap: the workspace last");
+}
+
 }  // namespace
 
 int main() {
+    estimator_call_rules();
     pair_list_rules();
     workspace_rules();
     keypoint_rules();

@@ -363,6 +363,59 @@ def test_empty_results_and_statuses():
         est.estimate_pairs({"keypoints": feats0["keypoints"].cpu()}, pairs[:1], m0[:1].cpu(), cameras, points.cpu(), feats1)
 
 
+EDGE_N0 = 300                               # not a multiple of 256
+EDGE_SIZES = (2, 3, 4, 257)                 # below the sample, the sample, the refinement threshold, one past the 256-row tile
+
+
+@pytest.mark.parametrize("S", EDGE_SIZES)
+def test_list_lengths_at_the_thresholds(S):
+    """the S = 1000 scene cut to its first EDGE_N0 image-0 rows and thinned to the first S correspondences among them: as one pair, and pooled from two pairs
+    (the first 200 rows of the list at most, then the rest: at S = 257 the list passes 256 only as their concatenation) — the same list, so the same bits"""
+    c = A.case(1000)
+    rows = c["rows"][c["rows"] < EDGE_N0][:S]
+    assert len(rows) == S
+    m0 = np.full(EDGE_N0, -1, np.int64)
+    m0[rows] = c["matches0"][rows]
+    corr, planted, cam = c["corr"][:S], c["planted"][:S], c["cam"]
+    first = min(200, S // 2)
+    halves = np.stack([np.where(np.isin(np.arange(EDGE_N0), rows[:first]), m0, -1), np.where(np.isin(np.arange(EDGE_N0), rows[first:]), m0, -1)])
+    feats0, cams, points = {"keypoints": cuda(c["kpts0"][None, :EDGE_N0])}, torch.tensor([A.CAM]), cuda(c["points"][None])
+    views_of = {}
+    for refine in (False, True):
+        est = AbsolutePoseEstimator(threshold=A.T, num_hypotheses=256, refine=refine, seed=A.SEED)
+        one = est.estimate_pairs(feats0, [(0, 0)], cuda(m0[None]), cams, points)       # status LG_OK: nothing was raised
+        pool = est.estimate_pairs(feats0, [(0, 0), (0, 0)], cuda(halves), cams, points, pool=True)
+        assert pool["R"].shape == (1, 3, 3) and pool["pair_num_inliers"].tolist() == [int(pool["inliers0"][0].sum()), int(pool["inliers0"][1].sum())]
+        for k in PROBLEM_KEYS:
+            assert torch.equal(pool[k], one[k]), (S, refine, k)
+        assert torch.equal(pool["inliers0"].any(0), one["inliers0"][0]) and not bool(pool["inliers0"].all(0).any()), (S, refine)
+        assert torch.equal(pool["matches0"].max(0)[0], one["matches0"][0]), (S, refine)
+        inl, got0 = one["inliers0"][0].cpu().numpy(), one["matches0"][0].cpu().numpy()
+        ok = (got0 == np.where(inl, m0, -1)).all() and inl.sum() == inl[rows].sum() == int(one["pair_num_inliers"][0])
+        ok = ok and (one["matches"][0].cpu().numpy() == np.stack([np.nonzero(inl)[0], got0[inl]], -1)).all()
+        views_of[refine] = dict({k: one[k][0].cpu().numpy() for k in PROBLEM_KEYS}, mask=inl[rows], consistent=bool(ok))
+    plain, refined = views_of[False], views_of[True]
+    if S < A.SAMPLE:
+        check_empty(plain, S)
+        check_empty(refined, S)
+        return
+    allin = A.all_inlier_of(planted, S, 256)
+    shrunk = A.verify(corr, cam, A.T * (1 - MARGIN), 256, A.SEED, False)
+    bound = int(shrunk["counts"][allin].max()) if allin.any() else 0
+    for refine, got in ((False, plain), (True, refined)):
+        what = (S, refine)
+        if got["num_inliers"] == 0:
+            check_empty(got, what)
+            continue
+        d = check_consistent(got, corr, cam, what)
+        print(what, "count", int(got["num_inliers"]), "bound", bound, "within the margin %.4f (at most %.2f)" % ((abs(d - A.T) <= MARGIN * A.T).mean(), MAX_EXCLUDED))
+        assert got["num_inliers"] >= bound, (what, got["num_inliers"], bound)
+    assert refined["num_inliers"] >= plain["num_inliers"] and refined["best_hypothesis"] == plain["best_hypothesis"], S
+    if plain["num_inliers"] < A.REFINE_MIN:                             # no refinement below 4 inliers: at S = 3 never
+        assert (world_pose(refined) == world_pose(plain)).all() and (refined["mask"] == plain["mask"]).all(), S
+    assert S >= A.REFINE_MIN or plain["num_inliers"] < A.REFINE_MIN
+
+
 def test_pooled_statuses_and_a_problem_that_goes_on_without_a_pair():
     pr = A.pooled()
     out, message = run_pool(256, True)

@@ -252,6 +252,50 @@ def test_empty_results_and_statuses():
         est.estimate_pairs({"keypoints": feats0["keypoints"].cpu()}, pairs[:1], m0[:1].cpu(), cameras0, {"keypoints": feats1["keypoints"].cpu()}, cameras1)
 
 
+EDGE_N0 = 300                               # not a multiple of 256
+EDGE_SIZES = (4, 5, 7, 8, 257)              # below the sample, the sample, below and at the refit threshold, one past the 256-row tile
+
+
+@pytest.mark.parametrize("S", EDGE_SIZES)
+def test_list_lengths_at_the_thresholds(S):
+    """the S = 1000 scene (K0 != K1) cut to its first EDGE_N0 image-0 rows and thinned to the first S correspondences among them"""
+    c = P.case(1000, "other")
+    rows = c["rows"][c["rows"] < EDGE_N0][:S]
+    assert len(rows) == S
+    m0 = np.full(EDGE_N0, -1, np.int64)
+    m0[rows] = c["matches0"][rows]
+    c = dict(c, matches0=m0, rows=rows, corr=c["corr"][:S], planted=c["planted"][:S])
+    data = {"image0": {"keypoints": cuda(c["kpts0"][None, :EDGE_N0])}, "image1": {"keypoints": cuda(c["kpts1"][None])}}
+    cams = torch.tensor([P.CAM0]), torch.tensor([P.CAMS1["other"]])
+    outs = {refine: RelativePoseEstimator(threshold=P.T, num_hypotheses=256, refine=refine, seed=P.SEED)(data, cuda(m0[None]), *cams) for refine in (False, True)}
+    plain, refined = host(outs[False], 0), host(outs[True], 0)          # status LG_OK: nothing was raised
+    if S < P.SAMPLE:
+        check_empty(plain, S)
+        check_empty(refined, S)
+        return
+    allin = c["planted"][P.sample(P.SEED, 256, S, P.SAMPLE)].all(1)
+    shrunk = P.verify(c["corr"], c["cam0"], c["cam1"], P.T * (1 - MARGIN), 256, P.SEED, False)
+    bound = int(shrunk["counts"][allin].max()) if allin.any() else 0
+    for refine, got in ((False, plain), (True, refined)):
+        what = (S, refine)
+        if got["num_inliers"] == 0:
+            check_empty(got, what)
+            continue
+        d = check_consistent(got, c, what)
+        print(what, "count", int(got["num_inliers"]), "bound", bound, "within the margin %.4f (at most %.2f)" % ((abs(d - P.T) <= MARGIN * P.T).mean(), MAX_EXCLUDED))
+        assert got["num_inliers"] >= bound, (what, got["num_inliers"], bound)
+        assert (outs[refine]["matches"][0].cpu().numpy() == np.stack([np.nonzero(got["inliers0"])[0], got["matches0"][got["inliers0"]]], -1)).all(), what
+        # the scoring is the verifier's, at these lengths too
+        models = outs[refine]["models"][:, None].expand(-1, 256, -1, -1).contiguous()
+        ref = TwoViewVerifier(model="fundamental", threshold=P.T, num_hypotheses=256, refine=False).score_models(data["image0"], [(0, 0)], cuda(m0[None]), models, data["image1"])
+        for k in ("inliers0", "num_inliers", "matches0", "models"):
+            assert torch.equal(ref[k], outs[refine][k]), (what, k)
+    assert refined["num_inliers"] >= plain["num_inliers"] and refined["best_hypothesis"] == plain["best_hypothesis"], S
+    if plain["num_inliers"] < P.REFIT_MIN:                              # no refit below 8 inliers: at S = 5 and 7 never
+        same(outs[True], outs[False], (S, "no refit"))
+    assert S >= P.REFIT_MIN or plain["num_inliers"] < P.REFIT_MIN
+
+
 def test_num_keypoints_is_honoured():
     c = P.case(65, "same")
     num0, num1 = 1000, 1040

@@ -240,6 +240,62 @@ def test_an_index_outside_the_store_empties_that_pair_only(kind):
         v.verify_pairs({"keypoints": torch.from_numpy(kpts)}, pairs[:1], torch.from_numpy(m0[:1]))
 
 
+# ---------------------------------------------------------------------- 4b. list lengths around the sample size, the refit threshold and the 256-row tile
+EDGE_N0 = 300                               # not a multiple of 256
+EDGE_SIZES = {"homography": (3, 4, 255, 256, 257), "fundamental": (6, 7, 8, 257)}
+
+
+# the window of image-0 rows a case is cut from: the first of 0, 100, 200, ... on which the float64 definition's own models (refined or not) keep at most 2 % of
+# the correspondences within the margin — the rule behind twoview_oracle.SCENE_SEED, decided by the definition alone; the test asserts it before it reads the GPU.
+# The finding behind the one entry: homography, S = 255 cut from rows 0 - 299 leaves 7 of the 255 correspondences (0.0275) within the margin of the returned model, on
+# the library before the shared steps exactly as on this one, and the float64 definition's own unrefined model has the same 0.0275 there (it does not recover the
+# plane: count 51 against 80 refined); rows 200 - 499 give 0.0078 / 0.0.  The kernels are not at fault at rows 0 - 299 and nothing was changed in them for it
+EDGE_START = {("homography", 255): 200}
+
+
+def thinned(c, S, n0=EDGE_N0, start=0):
+    """the S = 1000 scene cut to the n0 image-0 rows from `start` on and thinned to the first S correspondences among them (the oracle's order is ascending in the row)"""
+    first = int(np.searchsorted(c["rows"], start))
+    rows = c["rows"][first:first + S]
+    assert len(rows) == S and rows[-1] < start + n0
+    m0 = np.full(n0, -1, np.int64)
+    m0[rows - start] = c["matches0"][rows]
+    return dict(kpts0=c["kpts0"][start:start + n0], kpts1=c["kpts1"], matches0=m0, rows=rows - start, corr=c["corr"][first:first + S], planted=c["planted"][first:first + S])
+
+
+@pytest.mark.parametrize("kind, S", [(kind, S) for kind in KINDS for S in EDGE_SIZES[kind]])
+def test_list_lengths_at_the_thresholds(kind, S):
+    c = thinned(O.case(kind, 1000), S, start=EDGE_START.get((kind, S), 0))
+    if S >= O.SAMPLE[kind]:
+        for refine in (False, True):                                    # the input is one the definition itself can be compared on
+            r64 = O.verify(kind, c["corr"], O.T, 256, O.SEED, refine)
+            if r64["count"]:
+                assert (abs(O.distances(kind, np.asarray(r64["model"], np.float64).reshape(9), c["corr"]) - O.T) <= MARGIN * O.T).mean() <= MAX_EXCLUDED, (kind, S, refine)
+    data = {"image0": {"keypoints": cuda(c["kpts0"][None])}, "image1": {"keypoints": cuda(c["kpts1"][None])}}
+    outs = {refine: TwoViewVerifier(model=kind, threshold=O.T, num_hypotheses=256, refine=refine, seed=O.SEED)(data, cuda(c["matches0"][None])) for refine in (False, True)}
+    plain, refined = host(outs[False], 0), host(outs[True], 0)          # status LG_OK: nothing was raised
+    if S < O.SAMPLE[kind]:
+        check_empty(plain, (kind, S))
+        check_empty(refined, (kind, S))
+        return
+    allin = c["planted"][O.sample(O.SEED, 256, S, O.SAMPLE[kind])].all(1)
+    shrunk = O.verify(kind, c["corr"], O.T * (1 - MARGIN), 256, O.SEED, False)
+    bound = int(shrunk["counts"][allin].max()) if allin.any() else 0
+    for refine, got in ((False, plain), (True, refined)):
+        what = (kind, S, refine)
+        if got["num_inliers"] == 0:
+            check_empty(got, what)
+        else:
+            d = check_consistent(kind, got, c, what)
+            print(what, "count", int(got["num_inliers"]), "bound", bound, "within the margin %.4f (at most %.2f)" % ((abs(d - O.T) <= MARGIN * O.T).mean(), MAX_EXCLUDED))
+        assert got["num_inliers"] >= bound, (what, got["num_inliers"], bound)
+        assert (outs[refine]["matches"][0].cpu().numpy() == np.stack([np.nonzero(got["inliers0"])[0], got["matches0"][got["inliers0"]]], -1)).all(), what
+    assert refined["num_inliers"] >= plain["num_inliers"] and refined["best_hypothesis"] == plain["best_hypothesis"], (kind, S)
+    if plain["num_inliers"] < O.REFIT_MIN[kind]:                        # no refit below 4 (H) / 8 (F) inliers: at S = 7 never
+        same(outs[True], outs[False], (kind, S, "no refit"))
+    assert S != 7 or plain["num_inliers"] < O.REFIT_MIN[kind]
+
+
 # ---------------------------------------------------------------------- 5. behind the nearest-neighbour matcher
 @pytest.mark.parametrize("kind", KINDS)
 def test_verify_pairs_behind_the_nn_matcher(kind):
