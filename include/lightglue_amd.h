@@ -1045,6 +1045,61 @@ int64_t lg_bundle_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uin
 int lg_bundle_adjust(const lg_bundle_io* io, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The robust mode of the bundle adjuster: a robust loss on the pixel errors (iteratively reweighted least squares) and, in the same call, up to
+ * LG_BA_MAX_FILTER_ROUNDS rounds of "drop the observations above max_reproj_error and adjust again".  lg_bundle_adjust itself is unchanged in every bit and
+ * refusal; this is a second entry point whose io holds lg_bundle_io as `base`.  tests/bundle_robust_oracle.py restates it in float64 numpy.  Everything not
+ * named here is lg_bundle_adjust's definition, word for word.
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   loss      for an observation with residual (rx, ry), s = rx rx + ry ry, c = loss_scale (pixels), c2 = c c:
+ *             LG_BA_LOSS_SQUARED  rho = s, w = 1;
+ *             LG_BA_LOSS_HUBER    rho = s if s <= c2, else (2 c) sqrt(s) - c2;  w = 1 if s <= c2, else c / sqrt(s);
+ *             LG_BA_LOSS_CAUCHY   rho = c2 log1p(s / c2);  w = 1 / (1 + s / c2).
+ *             cost = sum of rho(s), in the orders of lg_bundle_adjust (per image in ascending row order, the images in ascending order).
+ *   weights   first order (iteratively reweighted least squares, no second-order correction): at the accepted state sw = sqrt(w); the two rows of A, the two
+ *             rows of B and (rx, ry) are each multiplied by sw ONCE, right after they are formed; every later formula (U, V, g, W, Y, E, the right-hand sides,
+ *             the point step) reads the scaled quantities and is otherwise unchanged.  W of an observation therefore carries that observation's weight.  With
+ *             LG_BA_LOSS_SQUARED no multiplication is made.  Both robust losses are concave in s, so the weighted quadratic majorises the cost; the accept /
+ *             reject / convergence rules are those of lg_bundle_adjust on the sum of rho.  A pz <= 0 or a non-finite s fails a trial as before (its term is 0).
+ *   stages    a call runs filter_rounds + 1 stages of num_iterations iterations each.  After every stage but the last, the FILTER: an active observation
+ *             whose error at the accepted state exceeds e = max_reproj_error (tested as s > e e, s unweighted) takes node_state 7, filtered.  Then the
+ *             tracks' lists and counts and the images' active counts are rebuilt from the nodes still in state 1, in ascending node order: a track left
+ *             with fewer than 2 observations stops being adjusted and its remaining observations take state 5; an image left without an active
+ *             observation stops being free.  A track or image that stops moving returns its LAST ACCEPTED state, not the bits that went in (a track that
+ *             was never adjusted and an image that was never free return their input bits, as in lg_bundle_adjust).  There is no re-admission.
+ *             If the filter removed at least one observation: cost is computed again over the new set, lambda returns to initial_damping and `converged`
+ *             is cleared.  If it removed none the record is left alone and the next stage goes on where the last one stopped (a converged call stays
+ *             converged): a call whose filters remove nothing is, bit for bit, the call with filter_rounds = 0 and num_iterations x (filter_rounds + 1).
+ *   stopping  as in lg_bundle_adjust: every launch of every stage is enqueued unconditionally, the decisions live in the device record, one host
+ *             synchronisation (the caller's).
+ *   outputs   those of lg_bundle_adjust; points3d and observation_error (always the UNWEIGHTED pixel error) are set at the rows active at the end, NaN elsewhere.
+ *             summary [12] fp64: 0 the initial cost over the first stage's set under the loss; 1 the final cost over the final set; 2 iterations run and
+ *             3 steps accepted, summed over the stages; 4 `converged` of the last stage; 5 active observations at the end; 6 final lambda; 7 zero; 8 filtered
+ *             observations; 9 stages in which a filter removed something; 10, 11 zero.
+ *   Determinism: as lg_bundle_adjust.  The filter is a per-node test and adds no order; the rebuilt lists are sorted again.  With LG_BA_LOSS_SQUARED and
+ *             filter_rounds = 0 every output is that of lg_bundle_adjust bit for bit, and so is LG_BA_LOSS_HUBER while no s exceeds c2 (all weights are 1).
+ * Workspace: lg_bundle_robust_workspace_bytes bytes (-1 outside the envelope): that of lg_bundle_adjust plus one int32 per track.
+ * Envelope (LG_ERR_INVALID with a message that names the field, before the GPU is touched): that of lg_bundle_adjust (any bit in base.flags included), and
+ *   loss outside 0 .. 2; loss_scale not finite or not > 0 when the loss is not squared; filter_rounds outside [0, LG_BA_MAX_FILTER_ROUNDS]; max_reproj_error
+ *   not finite or not > 0 when filter_rounds > 0.
+ * Launches, none of which waits on another workgroup: those of lg_bundle_adjust per stage, with the loss compiled into points, reduce, trial points and cost;
+ *   between two stages the filter (one lane per node, an integer count of what it removed; the same launch clears the tracks' and images' counters), count
+ *   (candidate = state 1), scan, fill, sort, the cost of the accepted state and one lane that starts the record again if something was removed. */
+#define LG_BA_LOSS_SQUARED 0
+#define LG_BA_LOSS_HUBER 1
+#define LG_BA_LOSS_CAUCHY 2
+#define LG_BA_MAX_FILTER_ROUNDS 4
+typedef struct lg_bundle_robust_io {
+    lg_bundle_io base;                     /* flags: must be 0; workspace: lg_bundle_robust_workspace_bytes; summary: [12] */
+    int32_t loss;                          /* LG_BA_LOSS_*                                                            */
+    int32_t filter_rounds;                 /* in [0, LG_BA_MAX_FILTER_ROUNDS]                                         */
+    double loss_scale;                     /* c in pixels, > 0 (not read with LG_BA_LOSS_SQUARED)                     */
+    double max_reproj_error;               /* e in pixels, > 0 (not read with filter_rounds = 0)                      */
+} lg_bundle_robust_io;
+int64_t lg_bundle_robust_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_bundle_adjust_robust(const lg_bundle_robust_io* io, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Global poses: one pose per image from the relative poses of a pair list (what lg_relpose_estimate returns), by rotation averaging over the view graph and
  * position averaging along the pairs' translation directions, both robust to wrong pairs; the per-image poses are what lg_triangulate and lg_bundle_adjust
  * take.  fp64 throughout, no fused multiply-add, dense Cholesky, one call and one host synchronisation.  Stateless.  The reference has no such step; this is

@@ -30,6 +30,8 @@ LG_ABSPOSE_REFINE, LG_ABSPOSE_GROUPED, LG_ABSPOSE_GIVEN_POSES, LG_ABSPOSE_ROOTS 
 LG_TRI_REFINE, LG_TRI_TRACKS_ONLY, LG_TRI_MAX_TRACK_LENGTH = 524288, 1048576, 1024   # lg_triangulate: its io flags, the longest track it triangulates
 LG_TRI_MAX_HYPOTHESES, LG_TRI_MAX_TRACKS = 4096, 4   # lg_triangulate_robust: hypotheses per round, rounds (tracks) per component
 LG_BA_MAX_IMAGES, LG_BA_MAX_ITERATIONS, LG_BA_MAX_TRACK_LENGTH, LG_BA_CHOLESKY_BLOCK = 256, 100, 1024, 48   # lg_bundle_adjust: its envelope, the columns per Cholesky panel (it defines no flag bit)
+LG_BA_LOSS = {"squared": 0, "huber": 1, "cauchy": 2}   # lg_bundle_adjust_robust: LG_BA_LOSS_*
+LG_BA_MAX_FILTER_ROUNDS = 4                         # lg_bundle_adjust_robust: filters (stages - 1) of one call
 LG_PG_MIN_ITERATIONS, LG_PG_MAX_PAIRS = 6, 2 ** 20   # lg_posegraph_solve: its envelope next to LG_BA_MAX_IMAGES and LG_BA_MAX_ITERATIONS (it defines no flag bit)
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
@@ -53,7 +55,7 @@ EXPORTED_SYMBOLS = (
     "lg_relpose_workspace_bytes", "lg_relpose_estimate",
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
     "lg_triangulate_workspace_bytes", "lg_triangulate", "lg_triangulate_robust_workspace_bytes", "lg_triangulate_robust",
-    "lg_bundle_workspace_bytes", "lg_bundle_adjust",
+    "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
 )
 
@@ -175,6 +177,11 @@ class LgBundleIO(C.Structure):
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("poses_out", _fp), ("xyz_out", _fp), ("points3d", _fp), ("node_state", _fp), ("observation_error", _fp), ("summary", _fp), ("status", _fp),
     ]
+
+
+class LgBundleRobustIO(C.Structure):
+    """lg_bundle_robust_io (include/lightglue_amd.h): one call of the bundle adjuster's robust mode"""
+    _fields_ = [("base", LgBundleIO), ("loss", C.c_int32), ("filter_rounds", C.c_int32), ("loss_scale", C.c_double), ("max_reproj_error", C.c_double)]
 
 
 class LgPosegraphIO(C.Structure):
@@ -371,6 +378,9 @@ def load() -> C.CDLL:
     lib.lg_bundle_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_bundle_workspace_bytes.restype = C.c_int64
     lib.lg_bundle_adjust.argtypes = [C.POINTER(LgBundleIO), C.c_void_p]
+    lib.lg_bundle_robust_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
+    lib.lg_bundle_robust_workspace_bytes.restype = C.c_int64
+    lib.lg_bundle_adjust_robust.argtypes = [C.POINTER(LgBundleRobustIO), C.c_void_p]
     lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
     lib.lg_posegraph_workspace_bytes.restype = C.c_int64
     lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]

@@ -1,5 +1,5 @@
-"""Bundle adjustment of poses and points on the device, on the kernels of `csrc/lg_bundle.hip` behind `lg_bundle_adjust` (include/lightglue_amd.h holds the
-definition).  It reads what `Triangulator` returns — `track_id [K, N]` and `xyz [T, 3]` over ONE keypoint store — in place, plus one pinhole camera
+"""Bundle adjustment of poses and points on the device, on the kernels of `csrc/lg_bundle.hip` behind `lg_bundle_adjust` and, with a robust loss or filter
+rounds, `lg_bundle_adjust_robust` (include/lightglue_amd.h holds both definitions).  It reads what `Triangulator` returns — `track_id [K, N]` and `xyz [T, 3]` over ONE keypoint store — in place, plus one pinhole camera
 (fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image, and refines all free poses and all track points jointly: Levenberg-Marquardt on the
 sum of squared pixel reprojection errors, Schur complement, dense Cholesky, fp64.  Intrinsics are fixed.  ONE call with ONE host synchronisation; `points3d
 [K, N, 3]` (NaN where a row is no active observation) is what `AbsolutePoseEstimator` takes as points3d1."""
@@ -15,7 +15,7 @@ from . import _cabi, _call
 from .relpose import as_cameras
 from .triangulate import as_poses
 
-STATES = ("none", "active", "bad_image", "non_finite_point", "behind", "short_track", "too_long")    # node_state 0 .. 6
+STATES = ("none", "active", "bad_image", "non_finite_point", "behind", "short_track", "too_long", "filtered")    # node_state 0 .. 7 (7: the robust mode's filter)
 
 
 def as_tracks(tracks, K: int, N: int, device):
@@ -59,10 +59,26 @@ def as_constant(constant_pose, K: int) -> torch.Tensor:
 class BundleAdjuster(nn.Module):
     """num_iterations: the fixed budget of Levenberg-Marquardt iterations, in [1, 100].  initial_damping: lambda of the first iteration.  function_tolerance:
     the call converges after a trial with |cost - cost_new| <= function_tolerance cost.  At least one image must be held constant; two constant images fix the
-    scale of the reconstruction, with one the damping holds it (it may drift slowly)."""
+    scale of the reconstruction, with one the damping holds it (it may drift slowly).
+    loss: "squared", "huber" or "cauchy" on the pixel error, with loss_scale (c, pixels) where the loss bends; filter_rounds in [0, 4]: after each of that
+    many stages of num_iterations the observations above max_reproj_error (pixels) are dropped (node_state 7) and the rest is adjusted again.  The defaults
+    (squared, no filter) call `lg_bundle_adjust` as before; anything else calls `lg_bundle_adjust_robust`."""
 
-    def __init__(self, num_iterations: int = 10, initial_damping: float = 1e-4, function_tolerance: float = 1e-6):
+    def __init__(self, num_iterations: int = 10, initial_damping: float = 1e-4, function_tolerance: float = 1e-6, loss: str = "squared", loss_scale: float = 2.0,
+                 filter_rounds: int = 0, max_reproj_error: float = 4.0):
         super().__init__()
+        # the defaults are not examined further (what the C side does not read is not refused), and the robust settings are ONE attribute: an nn.Module
+        # pays for every attribute it sets, and this constructor sits inside callers' loops
+        if not (loss == "squared" and type(filter_rounds) is int and filter_rounds == 0):
+            if loss not in _cabi.LG_BA_LOSS:
+                raise ValueError(f"loss must be one of {sorted(_cabi.LG_BA_LOSS)}, got {loss!r}")
+            if isinstance(filter_rounds, bool) or int(filter_rounds) != filter_rounds or not 0 <= int(filter_rounds) <= _cabi.LG_BA_MAX_FILTER_ROUNDS:
+                raise ValueError(f"filter_rounds must be an integer in [0, {_cabi.LG_BA_MAX_FILTER_ROUNDS}], got {filter_rounds!r}")
+            if loss != "squared" and not 0.0 < float(loss_scale) < float("inf"):
+                raise ValueError(f"loss_scale must be > 0 with a robust loss, got {loss_scale!r}")
+            if int(filter_rounds) > 0 and not 0.0 < float(max_reproj_error) < float("inf"):
+                raise ValueError(f"max_reproj_error must be > 0 with filter_rounds > 0, got {max_reproj_error!r}")
+        self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0)
         if int(num_iterations) != num_iterations or not 1 <= int(num_iterations) <= _cabi.LG_BA_MAX_ITERATIONS:
             raise ValueError(f"num_iterations must be an integer in [1, {_cabi.LG_BA_MAX_ITERATIONS}], got {num_iterations!r}")
         if not 0.0 < float(initial_damping) < float("inf"):
@@ -71,13 +87,29 @@ class BundleAdjuster(nn.Module):
             raise ValueError(f"function_tolerance must be > 0, got {function_tolerance!r}")
         self.num_iterations, self.initial_damping, self.function_tolerance = int(num_iterations), float(initial_damping), float(function_tolerance)
 
+    loss = property(lambda self: self.robust[0])
+    loss_scale = property(lambda self: self.robust[1])
+    filter_rounds = property(lambda self: self.robust[2])
+    max_reproj_error = property(lambda self: self.robust[3])
+
+    @property
+    def robust_entry(self) -> bool:
+        """the C entry point adjust() takes: lg_bundle_adjust_robust also accepts the plain settings and then returns lg_bundle_adjust's bytes (the tests
+        set this to compare the two on one call)"""
+        return self.robust[4]
+
+    @robust_entry.setter
+    def robust_entry(self, value):
+        self.robust = self.robust[:4] + (bool(value),)
+
     @torch.no_grad()
     def adjust(self, feats: dict, tracks, cameras, poses, constant_pose) -> dict:
         """feats = {keypoints [K, N, 2], num_keypoints [K] (optional)}: the store the tracks were built over; `tracks`: `Triangulator`'s dict or
         (track_id [K, N], xyz [T, 3]); cameras [K, 4] (fx, fy, cx, cy) or [K, 3, 3]; poses [K, 3, 4] (R | t) or (R [K, 3, 3], t [K, 3]); constant_pose: a [K]
         bool mask or the indices of the images whose pose is held fixed (at least one: ValueError otherwise; two fix scale).  Returns poses [K, 3, 4], xyz
         [T, 3], points3d [K, N, 3] (NaN where a row is no active observation), node_state [K, N] uint8 (`STATES`), observation_error [K, N] (pixels, NaN where
-        not active), initial_cost, final_cost, num_iterations (run), num_accepted, converged, num_observations, status [K].  ONE host synchronisation.  An
+        not active), initial_cost, final_cost, num_iterations (run), num_accepted, converged, num_observations, num_filtered, num_filter_stages (both 0 without
+        a filter), status [K].  ONE host synchronisation.  An
         image whose camera or pose fails the camera rule raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else."""
         device = feats["keypoints"].device
         s = _call.build_side(feats, device, "feats")
@@ -93,24 +125,31 @@ class BundleAdjuster(nn.Module):
         pts = torch.empty((K, N, 3), device=device, dtype=torch.float32)
         state = torch.empty((K, N), device=device, dtype=torch.uint8)
         err = torch.empty((K, N), device=device, dtype=torch.float32)
-        small = torch.zeros((16 + K,), device=device, dtype=torch.int32)          # summary [8] fp64 | status [K]
+        loss, loss_scale, filter_rounds, max_reproj_error, robust = self.robust
+        small = torch.zeros((24 + K,), device=device, dtype=torch.int32)          # summary [12] fp64 (lg_bundle_adjust writes 8) | status [K]
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
             lib = _cabi.load()
-            nbytes = lib.lg_bundle_workspace_bytes(K, N, T, 0)                    # -1: outside the envelope — lg_bundle_adjust below says why
+            size = lib.lg_bundle_robust_workspace_bytes if robust else lib.lg_bundle_workspace_bytes
+            nbytes = size(K, N, T, 0)                                             # -1: outside the envelope — the call below says why
             ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
             p = _call._ptr
             io = _cabi.LgBundleIO(
                 n=N, images=K, tracks=T, flags=0, num_iterations=self.num_iterations, initial_damping=self.initial_damping,
                 function_tolerance=self.function_tolerance, kpts=p(s.kpts), num=p(s.num), track_id=p(tid), xyz=p(xyz), cameras=p(cam), poses=p(pose),
                 constant_pose=p(const), workspace=p(ws), workspace_bytes=max(nbytes, 0), poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
-                node_state=p(state), observation_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 64)
-            _cabi.check(lib.lg_bundle_adjust(C.byref(io), C.c_void_p(stream.cuda_stream)))
+                node_state=p(state), observation_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 96)
+            if robust:
+                rio = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
+                _cabi.check(lib.lg_bundle_adjust_robust(C.byref(rio), C.c_void_p(stream.cuda_stream)))
+            else:
+                _cabi.check(lib.lg_bundle_adjust(C.byref(io), C.c_void_p(stream.cuda_stream)))
             host = small.cpu().numpy()                # THE host sync of the call
-        summary, status = host[:16].view(np.float64), host[16:]
+        summary, status = host[:24].view(np.float64), host[24:]
         out = {"poses": poses_out, "xyz": xyz_out, "points3d": pts, "node_state": state, "observation_error": err,
                "initial_cost": float(summary[0]), "final_cost": float(summary[1]), "num_iterations": int(summary[2]), "num_accepted": int(summary[3]),
-               "converged": bool(summary[4]), "num_observations": int(summary[5]), "status": small[16:]}
+               "converged": bool(summary[4]), "num_observations": int(summary[5]), "num_filtered": int(summary[8]), "num_filter_stages": int(summary[9]),
+               "status": small[24:]}
         bad = [k for k, c in enumerate(status.tolist()) if c != _cabi.LG_OK]
         if bad:          # every other image is complete: the error carries the call's outputs
             error = _cabi.LightGlueAmdError("; ".join(f"image {k}: a camera whose focal length is not finite and > 0, whose principal point is not finite, or a "

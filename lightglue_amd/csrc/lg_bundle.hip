@@ -8,6 +8,9 @@
 //   per iteration: ba_points, ba_reduce, ba_cholesky_diag + ba_cholesky_rows once per panel (bodies in lg_cholesky.h), ba_backsolve, ba_trial_points, ba_cost,
 //   ba_decide;
 //   ba_scatter    one lane per node, track and image: the outputs.
+// lg_bundle_adjust_robust runs the same list per stage with the loss compiled in (ba_linearise<LOSS> is the one weighted linearisation: points, reduce, trial
+// points; ba_rho<LOSS> in the cost; the squared instantiation is lg_bundle_adjust's code) and between two stages ba_filter, ba_count<true>, ba_scan, ba_fill,
+// ba_sort, ba_cost and ba_restage.  Registers and scratch of every instantiation: profiles/bundle_adjust_robust.md.
 // No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
 // other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
 // No floating-point atomics: every sum runs in the fixed order the header names.  Small matrices are indexed statically (no scratch: profiles/bundle_adjust.md).
@@ -30,9 +33,9 @@ constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK;                  // Cholesky (lg_cho
 static_assert(BA_NB == CH_NB && BA_THREADS == CH_THREADS, "lg_cholesky.h is written for 48-column panels and 256 threads");
 constexpr int BA_TILE = 32, BA_BCHUNK = 6;                   // reduce: rows of image a per LDS tile, column blocks b per workgroup (6 x 36 = 216 threads)
 
-struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, pad0, pad1; };
+struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, removed, filtered, fstages, pad; };   // removed: by the running filter
 static_assert(sizeof(BaHead) <= 256, "the record of the call is 256 bytes");
-struct BaImage { double cam[4]; int ok, constant, nact, pad; double pad2[2]; };
+struct BaImage { double cam[4]; int ok, constant, nact, moved; double pad2[2]; };           // moved: free in an earlier stage (lg_bundle_adjust_robust)
 static_assert(sizeof(BaImage) == 64, "lg_bundle_workspace_bytes counts 64 bytes");
 
 struct BaArgs {
@@ -42,6 +45,9 @@ struct BaArgs {
     BaHead* head; BaImage* rec; double* pose; double* delta; double* icost; double* S;         // pose [2][images][12], S [dim + 1][dim]
     int* list; int* limg; int* tcnt; int* toff; int* tcur; double* X; double* Vinv; double* y;  // X [2][tracks][3]
     float* poses_out; float* xyz_out; float* points3d; unsigned char* node_state; float* obs_err; double* summary; int* status;
+    // lg_bundle_adjust_robust, behind everything lg_bundle_adjust's kernels read (their argument offsets stay what they were): the loss scale c, c c, the
+    // filter's bar e e, and per track "it moved in an earlier stage" (null without a filter)
+    double lc, lc2, fe2; int* tmov;
 };
 
 __device__ __forceinline__ bool ba_adjusted(const BaArgs& a, int j) { const int c = a.tcnt[j]; return c >= 2 && c <= LG_BA_MAX_TRACK_LENGTH; }
@@ -68,6 +74,33 @@ __device__ __forceinline__ void ba_residual(const double* cam, const double (&p)
     rx = ((cam[0] * p[0]) * iz + cam[2]) - (double)kp[0]; ry = ((cam[1] * p[1]) * iz + cam[3]) - (double)kp[1];
 }
 __device__ __forceinline__ double ba_damped(double d, double lambda) { return d + lambda * fmin(fmax(d, 1e-6), 1e32); }
+
+// ------------------------------------------------------------------ the loss (lg_bundle_adjust_robust): rho and the weight w of s = rx rx + ry ry
+template <int LOSS> __device__ __forceinline__ double ba_rho(const BaArgs& a, double s) {
+    if constexpr (LOSS == LG_BA_LOSS_HUBER) return s <= a.lc2 ? s : (2.0 * a.lc) * sqrt(s) - a.lc2;
+    else if constexpr (LOSS == LG_BA_LOSS_CAUCHY) return a.lc2 * log1p(s / a.lc2);
+    else return s;
+}
+template <int LOSS> __device__ __forceinline__ double ba_weight(const BaArgs& a, double s) {
+    if constexpr (LOSS == LG_BA_LOSS_HUBER) return s <= a.lc2 ? 1.0 : a.lc / sqrt(s);
+    else if constexpr (LOSS == LG_BA_LOSS_CAUCHY) return 1.0 / (1.0 + s / a.lc2);
+    else return 1.0;
+}
+// THE weighted linearisation of one observation at p: A, B and r, each multiplied by sqrt(w) once; with the squared loss no multiplication is made
+template <int LOSS>
+__device__ __forceinline__ void ba_linearise(const BaArgs& a, const double* P, const double* cam, const double (&p)[3], const float* kp, double (&A0)[6], double (&A1)[6],
+                                             double (&B0)[3], double (&B1)[3], double& rx, double& ry) {
+    ba_jacobians(P, cam, p, A0, A1, B0, B1);
+    ba_residual(cam, p, kp, rx, ry);
+    if constexpr (LOSS != LG_BA_LOSS_SQUARED) {
+        const double sw = sqrt(ba_weight<LOSS>(a, rx * rx + ry * ry));
+#pragma unroll
+        for (int e = 0; e < 6; ++e) { A0[e] = sw * A0[e]; A1[e] = sw * A1[e]; }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { B0[e] = sw * B0[e]; B1[e] = sw * B1[e]; }
+        rx = sw * rx; ry = sw * ry;
+    }
+}
 
 // ------------------------------------------------------------------ records
 __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
@@ -103,9 +136,14 @@ __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
 }
 
 // ------------------------------------------------------------------ candidates
-__global__ __launch_bounds__(BA_THREADS) void ba_count_kernel(BaArgs a) {
+// AGAIN (after a filter): a candidate is a node still in state 1, and no state is written
+template <bool AGAIN> __global__ __launch_bounds__(BA_THREADS) void ba_count_kernel(BaArgs a) {
     const int v = blockIdx.x * BA_THREADS + threadIdx.x;
     if (v >= a.nodes) return;
+    if constexpr (AGAIN) {
+        if (a.node_state[v] == 1) atomicAdd(a.tcnt + a.track_id[v], 1);
+        return;
+    }
     const int k = v / a.n, i = v - k * a.n;
     int state = 0;
     const long long j = a.track_id[v];
@@ -169,9 +207,50 @@ __global__ __launch_bounds__(BA_THREADS) void ba_sort_kernel(BaArgs a) {
     for (int q = 0; q < len; ++q) img[q] = lst[q] / a.n;
 }
 
+// ------------------------------------------------------------------ between two stages (lg_bundle_adjust_robust): the filter, then count<true>, scan, fill, sort, cost
+// One lane per node: an active observation whose error at the accepted state exceeds the bar becomes state 7, counted by an integer atomicAdd.  The same
+// launch, one lane per track and image: what moved so far is remembered (a track or image that stops moving returns its last accepted state), the trial point
+// takes the accepted one (nothing writes a track's trial once it is not adjusted, and a later accepted step flips sel), and the counters the rebuild fills are
+// cleared.  The node lanes read neither tcnt nor nact, so the order of the lanes does not matter
+__global__ __launch_bounds__(BA_THREADS) void ba_filter_kernel(BaArgs a, int first) {
+    const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
+    const int s = a.head->sel;
+    if (g < a.nodes && a.node_state[g] == 1) {
+        const int k = (int)(g / a.n);
+        double p[3], rx, ry;
+        ba_project(ba_pose(a, s, k), ba_point(a, s, (int)a.track_id[g]), p);
+        ba_residual(a.rec[k].cam, p, a.kpts + g * 2, rx, ry);
+        if (rx * rx + ry * ry > a.fe2) { a.node_state[g] = 7; atomicAdd(&a.head->removed, 1); }
+    }
+    if (g < a.tracks) {
+        a.tmov[g] = ((first ? 0 : a.tmov[g]) || ba_adjusted(a, (int)g)) ? 1 : 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) a.X[((long long)(s ^ 1) * a.tracks + g) * 3 + e] = a.X[((long long)s * a.tracks + g) * 3 + e];
+        a.tcnt[g] = 0; a.tcur[g] = 0; a.toff[g] = 0;
+    }
+    if (g < a.images) {
+        if (ba_free(a, (int)g)) a.rec[g].moved = 1;
+        a.rec[g].nact = 0;
+    }
+}
+
+// one lane: if the filter removed something, the cost of the new set (the images' costs in ascending order), lambda and `converged` start again
+__global__ void ba_restage_kernel(BaArgs a) {
+    if (blockIdx.x || threadIdx.x) return;
+    BaHead& h = *a.head;
+    if (h.removed > 0) {
+        double sum = 0.0;
+        int nobs = 0;
+        for (int k = 0; k < a.images; ++k) { sum += a.icost[k]; nobs += a.rec[k].nact; }
+        h.cost = sum; h.nobs = nobs; h.lambda = a.lambda0; h.converged = 0;
+        h.filtered += h.removed; h.fstages += 1;
+    }
+    h.removed = 0; h.fail = 0;
+}
+
 // ------------------------------------------------------------------ the cost of a state: one workgroup per image, rows in ascending order
 // trial = 0: the accepted state (the input); 1: the trial.  A row with pz <= 0 or a non-finite term fails the trial
-__global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgs a, int trial) {
+template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgs a, int trial) {
     __shared__ double term[BA_THREADS];
     if (trial && a.head->converged) return;
     const int k = blockIdx.x, which = a.head->sel ^ trial;
@@ -189,6 +268,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgs a, int trial
             ba_residual(cam, p, a.kpts + v * 2, rx, ry);
             c = rx * rx + ry * ry;
             if (!(p[2] > 0.0) || !isfinite(c)) { bad = 1; c = 0.0; }
+            if constexpr (LOSS != LG_BA_LOSS_SQUARED) c = ba_rho<LOSS>(a, c);      // rho(0) = 0
         }
         __syncthreads();
         term[threadIdx.x] = c;
@@ -229,7 +309,7 @@ __global__ void ba_decide_kernel(BaArgs a, int initial) {
 }
 
 // ------------------------------------------------------------------ per iteration 1: one lane per track: V, g, the damped inverse, y
-__global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
+template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
     if (j >= a.tracks || !ba_adjusted(a, j)) return;
@@ -244,8 +324,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
         const double* cam = a.rec[k].cam;
         double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
         ba_project(P, X, p);
-        ba_jacobians(P, cam, p, A0, A1, B0, B1);
-        ba_residual(cam, p, a.kpts + (long long)v * 2, rx, ry);
+        ba_linearise<LOSS>(a, P, cam, p, a.kpts + (long long)v * 2, A0, A1, B0, B1, rx, ry);
         V[0] += B0[0] * B0[0] + B1[0] * B1[0]; V[1] += B0[0] * B0[1] + B1[0] * B1[1]; V[2] += B0[0] * B0[2] + B1[0] * B1[2];
         V[3] += B0[1] * B0[1] + B1[1] * B1[1]; V[4] += B0[1] * B0[2] + B1[1] * B1[2]; V[5] += B0[2] * B0[2] + B1[2] * B1[2];
 #pragma unroll
@@ -276,10 +355,13 @@ __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
 // grid (images, ceil(images / BA_BCHUNK)).  Threads 0 .. 215: entry (r, c) of block (a, b); in the workgroup that holds the diagonal block, threads 216 .. 248:
 // the 21 entries of U_a's upper triangle, g_a (6), the sum of W y (6).  BA_TILE rows of image a at a time go through LDS in four steps: the first BA_TILE
 // threads stage a row each (Y, A, r, W y, X, the row's track list); all threads count the list's entries per column block (integer LDS atomics: a count has no
-// order); one thread per (row, column block) with an entry forms W_b once; then every entry thread adds its rows in ascending order
-__global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
+// order); one thread per (row, column block) with an entry forms W_b once; then every entry thread adds its rows in ascending order.
+// With a robust loss W_b carries the weight of ITS observation: the counting also finds the track's first entry in image b (an integer minimum), whose W goes
+// to LDS; where a track has more than one observation in image b (rare) the entry threads form every W themselves, in the list's order
+template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
+    constexpr bool ROBUST = LOSS != LG_BA_LOSS_SQUARED;
     __shared__ double sY[BA_TILE][18], sA[BA_TILE][12], sWy[BA_TILE][6], sX[BA_TILE][3], sR[BA_TILE][2], sW[BA_TILE][BA_BCHUNK][18], sU[33];
-    __shared__ int sOff[BA_TILE], sLen[BA_TILE], sCnt[BA_TILE][BA_BCHUNK];
+    __shared__ int sOff[BA_TILE], sLen[BA_TILE], sCnt[BA_TILE][BA_BCHUNK], sFirst[ROBUST ? BA_TILE : 1][BA_BCHUNK];
     if (a.head->converged) return;
     const int ia = blockIdx.x, b0 = blockIdx.y * BA_BCHUNK, t = threadIdx.x, dim = a.dim;
     if (b0 > ia) return;
@@ -300,10 +382,11 @@ __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
     // the thread's (row, column block) item of a tile, and the pose of that block's image
     const int iq = t / BA_BCHUNK, ibl = t - iq * BA_BCHUNK, item_b = b0 + ibl;
     const bool item = t < BA_TILE * BA_BCHUNK, item_free = item && item_b <= ia && ba_free(a, item_b);
-    double Pb[12], fb[2] = {0.0, 0.0};
+    double Pb[12], fb[ROBUST ? 4 : 2] = {0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 12; ++q) Pb[q] = item_free ? ba_pose(a, s, item_b)[q] : 0.0;
     if (item_free) { fb[0] = a.rec[item_b].cam[0]; fb[1] = a.rec[item_b].cam[1]; }
+    if constexpr (ROBUST) if (item_free) { fb[2] = a.rec[item_b].cam[2]; fb[3] = a.rec[item_b].cam[3]; }
     const int cq = t >> 3, part = t & 7;                    // counting: 8 threads per row of the tile
     static_assert(BA_THREADS == 8 * BA_TILE && BA_TILE * BA_BCHUNK <= BA_THREADS, "8 counting threads and BA_BCHUNK items per tile row");
     // U's upper triangle in row-major order: entry e -> (ur, uc)
@@ -326,8 +409,10 @@ __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
                 const double* y = a.y + (long long)j * 3;
                 double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
                 ba_project(Pa, Xp, p);
-                ba_jacobians(Pa, cama, p, A0, A1, B0, B1);
-                ba_residual(cama, p, a.kpts + v * 2, rx, ry);
+                // squared: ba_linearise<0>'s two calls written out; through the wrapper the compiler allocates this kernel's registers differently from
+                // lg_bundle_adjust's build before the robust mode (measured: 0.9 % on a call, profiles/bundle_adjust_robust.md): like this the instruction stream is that one
+                if constexpr (ROBUST) ba_linearise<LOSS>(a, Pa, cama, p, a.kpts + v * 2, A0, A1, B0, B1, rx, ry);
+                else { ba_jacobians(Pa, cama, p, A0, A1, B0, B1); ba_residual(cama, p, a.kpts + v * 2, rx, ry); }
                 sX[t][0] = Xp[0]; sX[t][1] = Xp[1]; sX[t][2] = Xp[2];
                 sR[t][0] = rx; sR[t][1] = ry;
 #pragma unroll
@@ -342,19 +427,26 @@ __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
             sLen[t] = len;
         }
         if (item) sCnt[iq][ibl] = 0;
+        if constexpr (ROBUST) if (item) sFirst[iq][ibl] = 0x7FFFFFFF;
         __syncthreads();
         {
             const int len = sLen[cq], off = sOff[cq];
             for (int l = part; l < len; l += 8) {
                 const int d = a.limg[off + l] - b0;
-                if (d >= 0 && d < BA_BCHUNK && b0 + d <= ia) atomicAdd(&sCnt[cq][d], 1);
+                if (d >= 0 && d < BA_BCHUNK && b0 + d <= ia) {
+                    atomicAdd(&sCnt[cq][d], 1);
+                    if constexpr (ROBUST) atomicMin(&sFirst[cq][d], l);
+                }
             }
         }
         __syncthreads();
         if (item_free && sCnt[iq][ibl] > 0) {               // W of (image item_b, the row's track): it does not depend on the observation's row in b
             double p[3], A0[6], A1[6], B0[3], B1[3];
             ba_project(Pb, sX[iq], p);
-            ba_jacobians(Pb, fb, p, A0, A1, B0, B1);
+            if constexpr (ROBUST) {                             // the weight of the track's first observation in image item_b (sCnt > 0: sFirst < sLen)
+                double rx, ry;
+                ba_linearise<LOSS>(a, Pb, fb, p, a.kpts + (long long)a.list[sOff[iq] + sFirst[iq][ibl]] * 2, A0, A1, B0, B1, rx, ry);
+            } else ba_jacobians(Pb, fb, p, A0, A1, B0, B1);
 #pragma unroll
             for (int q = 0; q < 6; ++q)
 #pragma unroll
@@ -366,6 +458,20 @@ __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
             for (int q = 0; q < rows; ++q) {
                 const int times = sCnt[q][bl];              // the observations of the row's track in image b, in order: the same W each
                 if (!times) continue;
+                if constexpr (ROBUST) if (times > 1) {          // every observation of the row's track in image ib has a weight of its own
+                    const double* Pi = ba_pose(a, s, ib);
+                    const double* cami = a.rec[ib].cam;
+                    for (int l = 0; l < sLen[q]; ++l) {
+                        if (a.limg[sOff[q] + l] != ib) continue;
+                        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry, a0 = 0.0, a1 = 0.0;
+                        ba_project(Pi, sX[q], p);
+                        ba_linearise<LOSS>(a, Pi, cami, p, a.kpts + (long long)a.list[sOff[q] + l] * 2, A0, A1, B0, B1, rx, ry);
+#pragma unroll
+                        for (int cc = 0; cc < 6; ++cc) if (cc == c) { a0 = A0[cc]; a1 = A1[cc]; }
+                        acc += (sY[q][3 * r] * (a0 * B0[0] + a1 * B1[0]) + sY[q][3 * r + 1] * (a0 * B0[1] + a1 * B1[1])) + sY[q][3 * r + 2] * (a0 * B0[2] + a1 * B1[2]);
+                    }
+                    continue;
+                }
                 const double term = (sY[q][3 * r] * sW[q][bl][3 * c] + sY[q][3 * r + 1] * sW[q][bl][3 * c + 1]) + sY[q][3 * r + 2] * sW[q][bl][3 * c + 2];
                 for (int m = 0; m < times; ++m) acc += term;
             }
@@ -459,7 +565,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
 }
 
 // ------------------------------------------------------------------ per iteration 5: one lane per track: the point's step and its trial
-__global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
+template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
     if (j >= a.tracks || !ba_adjusted(a, j)) return;
@@ -472,9 +578,9 @@ __global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
         if (!ba_free(a, k)) continue;
         const double* P = ba_pose(a, s, k);
         const double* d = a.delta + (long long)k * 6;
-        double p[3], A0[6], A1[6], B0[3], B1[3];
+        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;       // the squared loss reads neither the residual nor the keypoint
         ba_project(P, X, p);
-        ba_jacobians(P, a.rec[k].cam, p, A0, A1, B0, B1);
+        ba_linearise<LOSS>(a, P, a.rec[k].cam, p, a.kpts + (long long)a.list[off + q] * 2, A0, A1, B0, B1, rx, ry);
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             double w = 0.0;
@@ -497,13 +603,15 @@ __global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
 }
 
 // ------------------------------------------------------------------ the outputs
-__global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgs a) {
+// ROBUST (lg_bundle_adjust_robust): summary [12], and a track or image that moved in an earlier stage returns its last accepted state
+template <bool ROBUST> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgs a) {
     const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
     const BaHead h = *a.head;
     const int s = h.sel;
     if (g == 0) {
         a.summary[0] = h.initial_cost; a.summary[1] = h.cost; a.summary[2] = (double)h.iters; a.summary[3] = (double)h.accepted;
         a.summary[4] = (double)h.converged; a.summary[5] = (double)h.nobs; a.summary[6] = h.lambda; a.summary[7] = 0.0;
+        if constexpr (ROBUST) { a.summary[8] = (double)h.filtered; a.summary[9] = (double)h.fstages; a.summary[10] = 0.0; a.summary[11] = 0.0; }
     }
     if (g < a.nodes) {
         const int k = (int)(g / a.n);
@@ -520,17 +628,80 @@ __global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgs a) {
         a.obs_err[g] = err;
     }
     if (g < a.tracks) {
-        const bool adj = ba_adjusted(a, (int)g);
+        bool adj = ba_adjusted(a, (int)g);
+        if constexpr (ROBUST) adj = adj || (a.tmov && a.tmov[g]);
         const double* X = ba_point(a, s, (int)g);
 #pragma unroll
         for (int e = 0; e < 3; ++e) a.xyz_out[g * 3 + e] = adj ? (float)X[e] : a.xyz[g * 3 + e];
     }
     if (g < a.images) {
-        const bool fr = ba_free(a, (int)g);
+        bool fr = ba_free(a, (int)g);
+        if constexpr (ROBUST) fr = fr || a.rec[g].moved;
         const double* P = ba_pose(a, s, (int)g);
 #pragma unroll
         for (int e = 0; e < 12; ++e) a.poses_out[g * 12 + e] = fr ? (float)P[e] : a.poses[g * 12 + e];
     }
+}
+
+// ------------------------------------------------------------------ the launch list of both entry points: `rounds` filters, rounds + 1 stages of `iterations`
+template <int LOSS, bool ROBUST> static int ba_enqueue(const BaArgs& a, const BaLayout& L, int iterations, int rounds, hipStream_t s) {
+    auto blocks = [](long long items) { return dim3((unsigned)((items + BA_THREADS - 1) / BA_THREADS)); };
+    const dim3 th(BA_THREADS);
+    const int K = a.images, T = a.tracks;
+    const int panels = ((int)L.dim + BA_NB - 1) / BA_NB, tiles = ((int)L.dim + 1 + BA_NB - 1) / BA_NB;
+    const long long all = std::max<long long>(std::max<long long>(L.nodes, T), K);
+    hipLaunchKernelGGL(ba_init_kernel, blocks(std::max<long long>(K, T)), th, 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<false>, blocks(L.nodes), th, 0, s, a);
+    if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
+    if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
+    hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 0);
+    hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 1);
+    for (int stage = 0; stage <= rounds; ++stage) {
+        if (stage) {                                            // the filter and the rebuild of the lists from the nodes still in state 1
+            hipLaunchKernelGGL(ba_filter_kernel, blocks(all), th, 0, s, a, stage == 1 ? 1 : 0);
+            if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<true>, blocks(L.nodes), th, 0, s, a);
+            if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
+            if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
+            if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
+            hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 0);
+            hipLaunchKernelGGL(ba_restage_kernel, dim3(1), dim3(64), 0, s, a);
+        }
+        for (int it = 0; it < iterations; ++it) {
+            if (T) hipLaunchKernelGGL(ba_points_kernel<LOSS>, blocks(T), th, 0, s, a);
+            hipLaunchKernelGGL(ba_reduce_kernel<LOSS>, dim3(K, (K + BA_BCHUNK - 1) / BA_BCHUNK), th, 0, s, a);
+            for (int p = 0; p < panels; ++p) {
+                hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, a, p);
+                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, a, p);
+            }
+            hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
+            if (T) hipLaunchKernelGGL(ba_trial_points_kernel<LOSS>, blocks(T), th, 0, s, a);
+            hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 1);
+            hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 0);
+        }
+    }
+    hipLaunchKernelGGL(ba_scatter_kernel<ROBUST>, blocks(all), th, 0, s, a);
+    HIPCHK(hipGetLastError());
+    return LG_OK;
+}
+
+// the kernels' view of a checked call: the caller's arrays and the workspace carved by L
+static BaArgs ba_args(const lg_bundle_io& io, const BaLayout& L) {
+    char* ws = static_cast<char*>(io.workspace);
+    BaArgs a{};
+    a.n = io.n; a.images = io.images; a.nodes = (int)L.nodes; a.tracks = io.tracks; a.dim = (int)L.dim;
+    a.lambda0 = io.initial_damping; a.ftol = io.function_tolerance;
+    a.kpts = io.kpts; a.num = io.num; a.track_id = reinterpret_cast<const long long*>(io.track_id); a.xyz = io.xyz; a.cameras = io.cameras; a.poses = io.poses;
+    a.constant = io.constant_pose;
+    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
+    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
+    a.head = reinterpret_cast<BaHead*>(ws + L.head); a.rec = reinterpret_cast<BaImage*>(ws + L.rec);
+    a.pose = f64(L.pose); a.delta = f64(L.delta); a.icost = f64(L.icost); a.S = f64(L.S);
+    a.list = ints(L.list); a.limg = ints(L.limg); a.tcnt = ints(L.tcnt); a.toff = ints(L.toff); a.tcur = ints(L.tcur);
+    a.X = f64(L.X); a.Vinv = f64(L.Vinv); a.y = f64(L.y);
+    a.poses_out = io.poses_out; a.xyz_out = io.xyz_out; a.points3d = io.points3d; a.node_state = io.node_state; a.obs_err = io.observation_error;
+    a.summary = io.summary; a.status = io.status;
+    return a;
 }
 
 }  // namespace lg
@@ -548,58 +719,32 @@ int lg_bundle_adjust(const lg_bundle_io* io, void* hip_stream) {
     if (!io) return set_error(LG_ERR_INVALID, "lg_bundle_adjust: null io");
     BaLayout L;
     if (const char* why = ba_layout(io->images, io->n, io->tracks, io->flags, L)) return set_error(LG_ERR_INVALID, std::string("lg_bundle_adjust: ") + why);
-    if (io->num_iterations < 1 || io->num_iterations > LG_BA_MAX_ITERATIONS)
-        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: num_iterations must lie in [1, LG_BA_MAX_ITERATIONS]");
-    if (!(io->initial_damping > 0.0) || !std::isfinite(io->initial_damping) || !(io->function_tolerance > 0.0) || !std::isfinite(io->function_tolerance))
-        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: initial_damping and function_tolerance must be > 0 (and finite)");
-    if (!io->cameras || !io->poses || !io->constant_pose || !io->poses_out || !io->summary || !io->status || (io->tracks && (!io->xyz || !io->xyz_out)) ||
-        (L.nodes && (!io->kpts || !io->track_id || !io->points3d || !io->node_state || !io->observation_error)))
-        return set_error(LG_ERR_INVALID, "lg_bundle_adjust: null pointer among kpts, track_id, xyz, cameras, poses, constant_pose, poses_out, xyz_out, points3d, "
-                                         "node_state, observation_error, summary, status");
-    if (const int rc = check_workspace("lg_bundle_adjust", "lg_bundle_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
+    if (const int rc = ba_check_settings("lg_bundle_adjust", "lg_bundle_workspace_bytes", *io, L.nodes, L.total)) return rc;
+    return ba_enqueue<LG_BA_LOSS_SQUARED, false>(ba_args(*io, L), L, io->num_iterations, 0, static_cast<hipStream_t>(hip_stream));
+}
 
+int64_t lg_bundle_robust_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags) {
+    BaRobustLayout L;
+    return ba_robust_layout(images, n, tracks, flags, L) ? -1 : L.total;
+}
+
+int lg_bundle_adjust_robust(const lg_bundle_robust_io* io, void* hip_stream) {
+    static const char* const stage = "lg_bundle_adjust_robust";
+    if (!io) return set_error(LG_ERR_INVALID, std::string(stage) + ": null io");
+    BaRobustLayout L;
+    if (const char* why = ba_robust_layout(io->base.images, io->base.n, io->base.tracks, io->base.flags, L)) return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why);
+    if (const char* why = ba_robust_settings_error(io->loss, io->loss_scale, io->filter_rounds, io->max_reproj_error))
+        return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why);
+    if (const int rc = ba_check_settings(stage, "lg_bundle_robust_workspace_bytes", io->base, L.base.nodes, L.total)) return rc;
+    BaArgs a = ba_args(io->base, L.base);
+    a.lc = io->loss_scale; a.lc2 = io->loss_scale * io->loss_scale; a.fe2 = io->max_reproj_error * io->max_reproj_error;
+    a.tmov = io->filter_rounds > 0 ? reinterpret_cast<int*>(static_cast<char*>(io->base.workspace) + L.tmov) : nullptr;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    char* ws = static_cast<char*>(io->workspace);
-    BaArgs a{};
-    a.n = io->n; a.images = io->images; a.nodes = (int)L.nodes; a.tracks = io->tracks; a.dim = (int)L.dim;
-    a.lambda0 = io->initial_damping; a.ftol = io->function_tolerance;
-    a.kpts = io->kpts; a.num = io->num; a.track_id = reinterpret_cast<const long long*>(io->track_id); a.xyz = io->xyz; a.cameras = io->cameras; a.poses = io->poses;
-    a.constant = io->constant_pose;
-    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
-    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
-    a.head = reinterpret_cast<BaHead*>(ws + L.head); a.rec = reinterpret_cast<BaImage*>(ws + L.rec);
-    a.pose = f64(L.pose); a.delta = f64(L.delta); a.icost = f64(L.icost); a.S = f64(L.S);
-    a.list = ints(L.list); a.limg = ints(L.limg); a.tcnt = ints(L.tcnt); a.toff = ints(L.toff); a.tcur = ints(L.tcur);
-    a.X = f64(L.X); a.Vinv = f64(L.Vinv); a.y = f64(L.y);
-    a.poses_out = io->poses_out; a.xyz_out = io->xyz_out; a.points3d = io->points3d; a.node_state = io->node_state; a.obs_err = io->observation_error;
-    a.summary = io->summary; a.status = io->status;
-
-    auto blocks = [](long long items) { return dim3((unsigned)((items + BA_THREADS - 1) / BA_THREADS)); };
-    const dim3 th(BA_THREADS);
-    const int K = io->images, T = io->tracks;
-    const int panels = ((int)L.dim + BA_NB - 1) / BA_NB, tiles = ((int)L.dim + 1 + BA_NB - 1) / BA_NB;
-    hipLaunchKernelGGL(ba_init_kernel, blocks(std::max<long long>(K, T)), th, 0, s, a);
-    if (L.nodes) hipLaunchKernelGGL(ba_count_kernel, blocks(L.nodes), th, 0, s, a);
-    if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
-    if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
-    if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
-    hipLaunchKernelGGL(ba_cost_kernel, dim3(K), th, 0, s, a, 0);
-    hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 1);
-    for (int it = 0; it < io->num_iterations; ++it) {
-        if (T) hipLaunchKernelGGL(ba_points_kernel, blocks(T), th, 0, s, a);
-        hipLaunchKernelGGL(ba_reduce_kernel, dim3(K, (K + BA_BCHUNK - 1) / BA_BCHUNK), th, 0, s, a);
-        for (int p = 0; p < panels; ++p) {
-            hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, a, p);
-            hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, a, p);
-        }
-        hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
-        if (T) hipLaunchKernelGGL(ba_trial_points_kernel, blocks(T), th, 0, s, a);
-        hipLaunchKernelGGL(ba_cost_kernel, dim3(K), th, 0, s, a, 1);
-        hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 0);
+    switch (io->loss) {
+        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
+        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
+        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
     }
-    hipLaunchKernelGGL(ba_scatter_kernel, blocks(std::max<long long>(std::max<long long>(L.nodes, T), K)), th, 0, s, a);
-    HIPCHK(hipGetLastError());
-    return LG_OK;
 }
 
 }  // extern "C"

@@ -192,6 +192,35 @@ inline const char* ba_layout(long long images, long long n, long long tracks, ui
     L.X = bp.take(tracks * 48); L.Vinv = bp.take(tracks * 72); L.y = bp.take(tracks * 24); L.total = bp.used;
     return nullptr;
 }
+// what lg_bundle_adjust and lg_bundle_adjust_robust refuse once the layout stands, in this order: the budget, damping and tolerance, a null pointer, the
+// workspace of `need` bytes (`size_function` names what sizes it)
+inline int ba_check_settings(const char* stage, const char* size_function, const lg_bundle_io& io, long long nodes, long long need) {
+    const auto refuse = [stage](const char* why) { return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why); };
+    const auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
+    if (io.num_iterations < 1 || io.num_iterations > LG_BA_MAX_ITERATIONS) return refuse("num_iterations must lie in [1, LG_BA_MAX_ITERATIONS]");
+    if (!positive(io.initial_damping) || !positive(io.function_tolerance)) return refuse("initial_damping and function_tolerance must be > 0 (and finite)");
+    if (!io.cameras || !io.poses || !io.constant_pose || !io.poses_out || !io.summary || !io.status || (io.tracks && (!io.xyz || !io.xyz_out)) ||
+        (nodes && (!io.kpts || !io.track_id || !io.points3d || !io.node_state || !io.observation_error)))
+        return refuse("null pointer among kpts, track_id, xyz, cameras, poses, constant_pose, poses_out, xyz_out, points3d, node_state, observation_error, summary, status");
+    return check_workspace(stage, size_function, io.workspace, io.workspace_bytes, need);
+}
+// lg_bundle_adjust_robust: lg_bundle_adjust's layout, then one int32 per track (it moved in an earlier stage)
+struct BaRobustLayout { BaLayout base; long long tmov, total; };
+inline const char* ba_robust_layout(long long images, long long n, long long tracks, uint32_t flags, BaRobustLayout& L) {
+    if (const char* why = ba_layout(images, n, tracks, flags, L.base)) return why;
+    Bump bp;
+    bp.used = L.base.total;
+    L.tmov = bp.take(tracks * 4); L.total = bp.used;
+    return nullptr;
+}
+inline const char* ba_robust_settings_error(long long loss, double loss_scale, long long filter_rounds, double max_reproj_error) {
+    const auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
+    if (loss < LG_BA_LOSS_SQUARED || loss > LG_BA_LOSS_CAUCHY) return "loss must be LG_BA_LOSS_SQUARED, LG_BA_LOSS_HUBER or LG_BA_LOSS_CAUCHY";
+    if (loss != LG_BA_LOSS_SQUARED && !positive(loss_scale)) return "loss_scale must be > 0 (and finite) with a robust loss";
+    if (filter_rounds < 0 || filter_rounds > LG_BA_MAX_FILTER_ROUNDS) return "filter_rounds must lie in [0, LG_BA_MAX_FILTER_ROUNDS]";
+    if (filter_rounds > 0 && !positive(max_reproj_error)) return "max_reproj_error must be > 0 (and finite) with filter_rounds > 0";
+    return nullptr;
+}
 // lg_posegraph_solve: a 256-byte record of the call; per image its rotation and centre in fp64 (96 bytes) and five int32 (level, present, list count, list
 // offset, fill cursor; the offsets hold one more entry); per pair its state (4), its rotation error (8), its direction (24) and its two adjacency entries
 // (16); the larger of the two systems with its right-hand side row: (3 images + 1) x 3 images fp64 (the rotation system, (images + 3) x images, fits in it)

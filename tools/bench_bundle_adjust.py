@@ -9,8 +9,13 @@ verified by `TwoViewVerifier`, triangulated under the poses the store was projec
 (synchronised before and after, one warm-up, the configurations visited in turn `--runs` times: median and range), the iterations run, the costs.  The host
 route is tests/bundle_oracle.py (float64, one thread) with `--host-iterations` iterations, timed once.  One JSON line.
 `--only-adjust`: one call and nothing else — the run to put under a kernel trace for the per-launch times.
+`--loss`, `--loss-scale`, `--filter-rounds`, `--max-reproj-error`: the adjuster's robust mode (lg_bundle_adjust_robust; the host route is then
+tests/bundle_robust_oracle.py).  `--contaminate F`: after the triangulation, the keypoints of a fraction F of the observations — of tracks with at least
+3 observations, at most one per track — are moved by 20 .. 80 pixels in a random direction; the result line then also counts how many of them end above
+4 pixels or filtered, how many clean observations do, and the tracks still adjusted at the end.
 
-usage: bench_bundle_adjust.py [--images 16] [--kpts 2048] [--runs 5] [--host-iterations 2] [--only-adjust]"""
+usage: bench_bundle_adjust.py [--images 16] [--kpts 2048] [--runs 5] [--host-iterations 2] [--only-adjust] [--loss squared|huber|cauchy] [--loss-scale 2]
+                              [--filter-rounds 0] [--max-reproj-error 4] [--contaminate 0]"""
 import argparse
 import itertools
 import json
@@ -24,6 +29,7 @@ import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests")); sys.path.insert(0, str(ROOT / "tools"))
 import bundle_oracle as B
+import bundle_robust_oracle as R
 from abspose_oracle import rodrigues
 from bench_triangulate import CAMERA, replay
 from bench_verify_pairs import make_store, stats, timed
@@ -41,6 +47,27 @@ def moved_poses(poses, rot=0.002, shift=0.01, seed=1):
     return out.astype(np.float32)
 
 
+def contaminate(store, tracks, fraction, seed=5):
+    """-> (a store with moved keypoints, the moved nodes as a [K, N] bool mask on the device)"""
+    tid = tracks["track_id"].cpu().numpy()
+    kpts = store["keypoints"].cpu().numpy().copy()
+    rng = np.random.default_rng(seed)
+    length = np.bincount(tid[tid >= 0], minlength=int(tid.max()) + 2)
+    nodes = np.argwhere((tid >= 0) & (length[np.maximum(tid, 0)] >= 3))
+    want, taken, mask = int(round(fraction * (tid >= 0).sum())), set(), np.zeros(tid.shape, bool)
+    for at in rng.permutation(len(nodes)):
+        if len(taken) >= want:
+            break
+        k, i = nodes[at]
+        if int(tid[k, i]) in taken:
+            continue
+        taken.add(int(tid[k, i]))
+        angle, dist = rng.uniform(0.0, 2.0 * np.pi), rng.uniform(20.0, 80.0)
+        kpts[k, i] += (dist * np.array([np.cos(angle), np.sin(angle)])).astype(np.float32)
+        mask[k, i] = True
+    return dict(store, keypoints=torch.from_numpy(kpts).to(store["keypoints"].device)), torch.from_numpy(mask).cuda()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=16)
@@ -48,7 +75,13 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--host-iterations", type=int, default=2, help="iterations of the numpy definition on the host (0: skip)")
     ap.add_argument("--only-adjust", action="store_true", help="one call and nothing else: the run to put under a kernel trace")
+    ap.add_argument("--loss", default="squared", choices=("squared", "huber", "cauchy"))
+    ap.add_argument("--loss-scale", type=float, default=2.0)
+    ap.add_argument("--filter-rounds", type=int, default=0)
+    ap.add_argument("--max-reproj-error", type=float, default=4.0)
+    ap.add_argument("--contaminate", type=float, default=0.0, help="fraction of the observations moved by 20 .. 80 pixels after the triangulation")
     args = ap.parse_args()
+    conf = dict(loss=args.loss, loss_scale=args.loss_scale, filter_rounds=args.filter_rounds, max_reproj_error=args.max_reproj_error)
     if not torch.cuda.is_available():
         raise SystemExit("bench_bundle_adjust.py measures on an MI355X; there is nothing to measure without one")
     K = args.images
@@ -63,9 +96,13 @@ def main():
     triangulate = lambda: tri.triangulate(store, pairs_dev, verified, cameras, true_poses, validate=False)
     tracks = triangulate()
     start = torch.from_numpy(moved_poses(poses_host)).cuda()
+    clean_store, planted = store, None
+    if args.contaminate > 0:
+        store, planted = contaminate(store, tracks, args.contaminate)
+    triangulate = lambda: tri.triangulate(clean_store, pairs_dev, verified, cameras, true_poses, validate=False)
     constant = [0, 1]
     budgets = (1, 10)
-    runs = {n: (lambda n=n: BundleAdjuster(num_iterations=n).adjust(store, tracks, cameras, start, constant)) for n in budgets}
+    runs = {n: (lambda n=n: BundleAdjuster(num_iterations=n, **conf).adjust(store, tracks, cameras, start, constant)) for n in budgets}
     outs = {n: fn() for n, fn in runs.items()}                                   # warm-up of every timed shape
     if args.only_adjust:
         ms, out = timed(runs[10])
@@ -77,7 +114,8 @@ def main():
         for n in runs:                                                           # in turn, not back to back
             ms[n].append(timed(runs[n])[0])
     res = {"images": K, "kpts": args.kpts, "pairs": int(pairs_dev.shape[0]), "device": torch.cuda.get_device_name(0), "runs": args.runs,
-           "tracks": tracks["num_tracks"], "triangulate": stats(tri_ms), "adjust": []}
+           "tracks": tracks["num_tracks"], "triangulate": stats(tri_ms), **conf, "contaminate": args.contaminate,
+           "planted": 0 if planted is None else int(planted.sum()), "adjust": []}
     for n in runs:
         o = outs[n]
         d = (o["points3d"].double().cpu() - torch.from_numpy(truth)).norm(dim=-1)
@@ -86,16 +124,25 @@ def main():
                               "observations": o["num_observations"], "initial_cost": round(o["initial_cost"], 3), "final_cost": round(o["final_cost"], 3),
                               "median_distance_to_cloud_before": round(float(d0[torch.isfinite(d0)].median()), 5),
                               "median_distance_to_cloud_after": round(float(d[torch.isfinite(d)].median()), 5)})
+        active = o["node_state"] == 1
+        kept = torch.bincount(tracks["track_id"][active], minlength=1)
+        above = torch.nan_to_num(o["observation_error"]) > 4.0
+        res["adjust"][-1].update({"filtered": o["num_filtered"], "filter_stages": o["num_filter_stages"], "tracks_adjusted_at_the_end": int((kept >= 2).sum()),
+                                  "clean_above_4px": int((above & ~planted).sum()) if planted is not None else int(above.sum()),
+                                  "clean_filtered": int(((o["node_state"] == 7) & ~planted).sum()) if planted is not None else o["num_filtered"]})
+        if planted is not None:
+            res["adjust"][-1].update({"planted_above_4px": int((above & planted).sum()), "planted_filtered": int(((o["node_state"] == 7) & planted).sum())})
     ten, one = res["adjust"][1], res["adjust"][0]
-    if ten["iterations_run"] > 1:
-        res["ms_per_iteration"] = round((ten["ms_median"] - one["ms_median"]) / (ten["iterations_run"] - 1), 3)
+    if ten["iterations_run"] > one["iterations_run"]:          # with filter rounds both figures hold the rebuilds between the stages
+        res["ms_per_iteration"] = round((ten["ms_median"] - one["ms_median"]) / (ten["iterations_run"] - one["iterations_run"]), 3)
     if args.host_iterations:
         inp = dict(kpts=store["keypoints"].cpu().numpy(), num=None, track_id=tracks["track_id"].cpu().numpy(), xyz=tracks["xyz"].cpu().numpy(),
                    cams=np.asarray([CAMERA] * K, np.float32), poses=start.cpu().numpy(), constant=np.arange(K) < 2)
         t = time.perf_counter()
-        host = B.adjust(inp, num_iterations=args.host_iterations)
+        robust = args.loss != "squared" or args.filter_rounds > 0
+        host = R.adjust(inp, num_iterations=args.host_iterations, **conf) if robust else B.adjust(inp, num_iterations=args.host_iterations)
         host_ms = (time.perf_counter() - t) * 1e3
-        dev = BundleAdjuster(num_iterations=args.host_iterations).adjust(store, tracks, cameras, start, constant)
+        dev = BundleAdjuster(num_iterations=args.host_iterations, **conf).adjust(store, tracks, cameras, start, constant)
         res["host"] = {"threads": 1, "iterations": host["num_iterations"], "ms": round(host_ms, 1), "final_cost": round(host["final_cost"], 3),
                        "device_final_cost_same_budget": round(dev["final_cost"], 3), "near_decisions": host["near"],
                        "same_states_as_device": bool((torch.from_numpy(host["node_state"]) == dev["node_state"].cpu()).all())}
