@@ -1,10 +1,13 @@
-"""TEST INFRASTRUCTURE ONLY — numpy restatement of the reference's ALIKED stages DKD and SDDH.
+"""TEST INFRASTRUCTURE ONLY — numpy restatement of the reference's ALIKED stages: the encoder, DKD and SDDH.
 
 Only tests/ may import this file; the product path (lightglue_amd/aliked.py -> lg_aliked.hip, lg_extract.hip) never does.
 Follows lightglue/aliked.py by line number: simple_nms (:68-91, the same function as superpoint.py:52-70, so `superpoint_oracle.simple_nms`
 is reused), DKD.forward (:127-261), get_patches (:48-65), SDDH.forward (:534-609), the dense map of extract_dense_map (:728-738) and the pixel
-keypoints of ALIKED.forward (:757).  torch ops are restated from their documented semantics: `nn.Upsample(mode="bilinear",
-align_corners=True)`, `F.grid_sample(mode="bilinear", padding_mode="zeros", align_corners=True)`, `F.normalize(p=2, eps=1e-12)`, `nn.SELU`.
+keypoints of ALIKED.forward (:757), and the encoder of extract_dense_map (:709-740) with its blocks (InputPadder :264-288, DeformableConv2d
+:328-349, ConvBlock :412-415, ResBlock :460-476) in `encoder`, BatchNorm applied as written (never folded).  torch ops are restated from
+their documented semantics: `nn.Upsample(mode="bilinear", align_corners=True)`, `F.grid_sample(mode="bilinear", padding_mode="zeros",
+align_corners=True)`, `F.normalize(p=2, eps=1e-12)`, `nn.SELU`, `nn.BatchNorm2d` (eval), `nn.AvgPool2d`, `F.pad(mode="replicate")`,
+`torchvision.ops.deform_conv2d`.
 Everything discrete (NMS, thresholds, selection, `.long()` truncations, patch corners) is computed on the fp32 values in the reference's
 operation order; everything continuous is float64.  Parity with the reference's own modules is pinned by tests/golden/aliked_stages/*.npz
 (tools/make_golden_aliked.py --stages) in tests/test_aliked_oracle_cpu.py."""
@@ -196,6 +199,125 @@ def sddh(levels, shape, knorm, weights: dict, n_pos: int) -> list:
     return out
 
 
+# --------------------------------------------------------------------------- encoder (extract_dense_map, ref :709-740)
+BN_EPS = 1e-5                                                                            # nn.BatchNorm2d's default
+
+
+def replicate_pad(x: np.ndarray, div: int = 32) -> np.ndarray:
+    """InputPadder(div).pad (ref :267-281) of x [B, H, W, C]: replicate padding, centred, the odd pixel on the far side"""
+    h, w = x.shape[1:3]
+    hp, wp, pt, pl = padded_dims(h, w, div)
+    return np.pad(x, ((0, 0), (pt, hp - h - pt), (pl, wp - w - pl), (0, 0)), mode="edge")
+
+
+def conv2d(x: np.ndarray, weight: np.ndarray, bias=None) -> np.ndarray:
+    """nn.Conv2d(k x k, stride 1, zero padding k // 2) of x [B, H, W, Cin] with weight [Cout, Cin, k, k] -> [B, H, W, Cout], float64"""
+    weight = np.asarray(weight, np.float64)
+    k = weight.shape[2]
+    r = k // 2
+    b, h, w, _ = x.shape
+    xp = np.pad(np.asarray(x, np.float64), ((0, 0), (r, r), (r, r), (0, 0)))
+    out = np.zeros((b, h, w, weight.shape[0]))
+    for i in range(k):
+        for j in range(k):
+            out += xp[:, i:i + h, j:j + w] @ weight[:, :, i, j].T
+    return out if bias is None else out + np.asarray(bias, np.float64)
+
+
+def batch_norm(x: np.ndarray, weights: dict, name: str, eps: float = BN_EPS) -> np.ndarray:
+    """nn.BatchNorm2d in eval mode, as written (not folded into the convolution): (x - running_mean) / sqrt(running_var + eps) * weight + bias"""
+    g = lambda n: np.asarray(weights[f"{name}.{n}"], np.float64)   # noqa: E731
+    return (x - g("running_mean")) / np.sqrt(g("running_var") + eps) * g("weight") + g("bias")
+
+
+def avg_pool(x: np.ndarray, f: int) -> np.ndarray:
+    """nn.AvgPool2d(f, stride f) of x [B, H, W, C], H and W multiples of f"""
+    b, h, w, c = x.shape
+    return x.reshape(b, h // f, f, w // f, f, c).mean(axis=(2, 4))
+
+
+def deform_positions(offsets: np.ndarray):
+    """sample positions of a 3 x 3, padding 1, stride 1 deformable convolution: offsets [B, h, w, 18], tap k = 3 i + j with (dy, dx) in channels
+    (2k, 2k + 1) -> (py, px) [B, h, w, 9] = the tap's own pixel (y - 1 + i, x - 1 + j) plus its offset"""
+    b, h, w, _ = offsets.shape
+    ys, xs = np.arange(h, dtype=np.float64)[None, :, None, None], np.arange(w, dtype=np.float64)[None, None, :, None]
+    ki, kj = np.divmod(np.arange(9), 3)
+    return ys - 1 + ki + offsets[..., 0::2], xs - 1 + kj + offsets[..., 1::2]
+
+
+def sample_classes(py: np.ndarray, px: np.ndarray, h: int, w: int):
+    """where deformable samples fall on an h x w map -> boolean (inside, partly, outside): `outside` gives a zero sample (torchvision: py <= -1, py >= h,
+    px <= -1 or px >= w), `inside` has its whole bilinear cell on the map (0 <= py <= h - 1, 0 <= px <= w - 1), `partly` is the rest: a cell that straddles
+    the border, some corners dropped"""
+    outside = (py <= -1) | (py >= h) | (px <= -1) | (px >= w)
+    inside = (py >= 0) & (py <= h - 1) & (px >= 0) & (px <= w - 1)
+    return inside, ~inside & ~outside, outside
+
+
+def deform_conv2d(x: np.ndarray, offsets: np.ndarray, weight: np.ndarray) -> np.ndarray:
+    """torchvision.ops.deform_conv2d (3 x 3, padding 1, stride 1, one offset group, no mask, no bias) from its documented rules: x [B, h, w, Cin],
+    offsets [B, h, w, 18] (already clamped), weight [Cout, Cin, 3, 3] -> [B, h, w, Cout].  A sample outside (-1, h) x (-1, w) is zero; otherwise it is
+    the bilinear mix of the four pixels around it, each of which counts as zero on its own when it lies off the map."""
+    b, h, w, cin = x.shape
+    weight = np.asarray(weight, np.float64)
+    py, px = deform_positions(offsets)
+    _, _, outside = sample_classes(py, px, h, w)
+    out = np.zeros((b, h, w, weight.shape[0]))
+    for i in range(b):
+        cols = bilinear_zeros(x[i], px[i].ravel(), py[i].ravel()).reshape(h, w, 9, cin)   # the per-corner rule
+        cols[outside[i]] = 0                                                             # the whole-sample rule (implied by the corners; stated)
+        out[i] = np.einsum("hwkc,ock->hwo", cols, weight.reshape(weight.shape[0], cin, 9))
+    return out
+
+
+def encoder(image: np.ndarray, weights: dict, trace: dict = None, eps: float = BN_EPS):
+    """ref extract_dense_map (:709-740) behind forward's gray broadcast (:744-745): image [B, 1|3, H, W], `weights` the state dict under the
+    reference's names -> (levels, scores): x1 .. x4 after conv1 .. conv4 + SELU as [B, Hp >> s, Wp >> s, 32] for s = 0, 1, 3, 5 over the whole padded
+    extent (the layout of ALIKED.level_maps), and the unpadded score map [B, H, W]; all float64.  Independent of n_pos.  `trace`, when given, receives
+    "offsets": the clamped offsets [B, h, w, 18] of block3.conv1, block3.conv2, block4.conv1, block4.conv2, in that order.  `eps` is BatchNorm's."""
+    g = lambda n: np.asarray(weights[n], np.float64)   # noqa: E731
+    x = np.asarray(image, np.float64)
+    _, c, h, w = x.shape
+    assert c in (1, 3)
+    if c == 1:
+        x = np.concatenate([x, x, x], axis=1)                                            # ref :744-745
+    hp, wp, pt, pl = padded_dims(h, w)
+    x = replicate_pad(x.transpose(0, 2, 3, 1))                                           # ref :712-713, NHWC from here on
+    offsets = []
+
+    def conv(name, t):
+        if f"{name}.weight" in weights:
+            return conv2d(t, g(f"{name}.weight"))
+        lh, lw = t.shape[1:3]
+        max_offset = max(lh, lw) / 4.0                                                   # ref :329-330
+        off = conv2d(t, g(f"{name}.offset_conv.weight"), g(f"{name}.offset_conv.bias"))   # ref :332
+        off = np.clip(off, -max_offset, max_offset)                                      # ref :340
+        offsets.append(off)
+        return deform_conv2d(t, off, g(f"{name}.regular_conv.weight"))                   # ref :341-348
+
+    def res_block(name, t):                                                              # ref :460-476
+        out = selu(batch_norm(conv(f"{name}.conv1", t), weights, f"{name}.bn1", eps))
+        out = batch_norm(conv(f"{name}.conv2", out), weights, f"{name}.bn2", eps)
+        return selu(out + conv2d(t, g(f"{name}.downsample.weight"), g(f"{name}.downsample.bias")))
+
+    x1 = selu(batch_norm(conv("block1.conv1", x), weights, "block1.bn1", eps))           # ref :413
+    x1 = selu(batch_norm(conv("block1.conv2", x1), weights, "block1.bn2", eps))          # ref :414
+    x2 = res_block("block2", avg_pool(x1, 2))                                            # ref :717-718
+    x3 = res_block("block3", avg_pool(x2, 4))                                            # ref :719-720
+    x4 = res_block("block4", avg_pool(x3, 4))                                            # ref :721-722
+    levels = [selu(conv2d(t, g(f"conv{i + 1}.weight"))) for i, t in enumerate((x1, x2, x3, x4))]   # ref :724-727
+    x1234 = np.stack([np.concatenate([upsample_align(l[b], hp, wp) for l in levels], axis=-1) for b in range(x.shape[0])])   # ref :728-731
+    s = x1234
+    for i in (0, 2, 4):                                                                  # ref :733 (:671-679)
+        s = selu(conv2d(s, g(f"score_head.{i}.weight")))
+    s = conv2d(s, g("score_head.6.weight"))[..., 0]
+    scores = 1.0 / (1.0 + np.exp(-s))
+    if trace is not None:
+        trace["offsets"] = offsets
+    return levels, scores[:, pt:pt + h, pl:pl + w]                                       # ref :738
+
+
 # T_ref: the largest deviation of the REFERENCE's fp32 results from this float64 oracle over all stage fixtures, per quantity (measured and
 # asserted in tests/test_aliked_oracle_cpu.py, which states where each figure comes from).  The GPU stage tests allow the kernels 4 x T_ref.
-T_REF = {"knorm": 1.7e-7, "keypoints": 4.6e-5, "keypoint_scores": 3.6e-5, "descriptors": 1.1e-6}
+T_REF = {"knorm": 1.7e-7, "keypoints": 4.6e-5, "keypoint_scores": 3.6e-5, "descriptors": 1.1e-6,
+         "x1": 1.6e-6, "x2": 2.2e-6, "x3": 3.2e-6, "x4": 1.6e-6, "encoder_scores": 7.2e-6}

@@ -16,7 +16,9 @@ The fixtures store the unpadded score map and the outputs; weights and images ar
 `--stages` writes tests/golden/aliked_stages/*.npz instead: the reference's own DKD and SDDH modules on the seeded crafted inputs of the
 "stage inputs" section below (score maps, level maps, keypoints; plain functions that never touch the reference either).  Those fixtures hold
 the reference's outputs and the case parameters only; they pin oracle/aliked_oracle.py (tests/test_aliked_oracle_cpu.py), which the GPU stage
-tests then compare the kernels with.
+tests then compare the kernels with.  The encoder fixtures (`ENC_STAGES`) come from the reference's whole ALIKED module on seeded images
+(`noise_image` / `aliked_image`) and seeded weights (`scaled_encoder_offsets`, `small_variance`): forward hooks on conv1 .. conv4 record the
+gated level maps x1 .. x4, stored with the unpadded score map.
     python tools/make_golden_aliked.py [NAME ...] # whole-model fixtures (all, or the named cases)
     python tools/make_golden_aliked.py --stages   # stage fixtures
 """
@@ -180,8 +182,62 @@ def scaled_offset_weights(sd: dict, gain: float) -> dict:
     return out
 
 
+def noise_image(seed: int, b: int, h: int, w: int, c: int = 3) -> torch.Tensor:
+    """[b, c, h, w] fp32, independent uniform(0, 1) pixels: every pixel differs from its neighbours, so the replicate-padding seam and the phase of
+    the pooling windows show in the first level (on the smooth `aliked_image` they barely do)"""
+    rng = np.random.Generator(np.random.PCG64(900 + seed))
+    return torch.from_numpy(rng.uniform(0.0, 1.0, (b, c, h, w)).astype(np.float32))
+
+
+ENCODER_OFFSET_CONVS = tuple(f"block{b}.conv{c}.offset_conv" for b in (3, 4) for c in (1, 2))
+
+
+def scaled_encoder_offsets(sd: dict, gain: float) -> dict:
+    """`sd` with the four offset convs of the deformable blocks (weight and bias) times `gain`: the encoder's counterpart of `scaled_offset_weights`.  The
+    offsets grow until most hit the +-max(h, w) / 4 clamp of DeformableConv2d and many samples fall partly or wholly off the map"""
+    out = dict(sd)
+    for n in ENCODER_OFFSET_CONVS:
+        for k in (f"{n}.weight", f"{n}.bias"):
+            out[k] = sd[k] * gain
+    return out
+
+
+def small_variance(sd: dict, seed: int) -> dict:
+    """`sd` with every BatchNorm `running_var` redrawn log-uniform in [1e-6, 1e-3] and the matching weight multiplied by sqrt(var + 1e-5), so the
+    activations keep their scale while BatchNorm's epsilon (1e-5) decides the result: 1 / sqrt(var + eps) moves by 0.5 % .. 70 % without it"""
+    rng = np.random.Generator(np.random.PCG64(950 + seed))
+    out = dict(sd)
+    for name in sd:
+        if name.endswith("running_var"):
+            var = torch.from_numpy(np.exp(rng.uniform(math.log(1e-6), math.log(1e-3), tuple(sd[name].shape))).astype(np.float32))
+            out[name] = var
+            out[name[:-len("running_var")] + "weight"] = sd[name[:-len("running_var")] + "weight"] * torch.sqrt(var + 1e-5)
+    return out
+
+
 STAGES = ROOT / "tests" / "golden" / "aliked_stages"
 OFFSET_GAIN = 40.0
+# The encoder on whole images (aliked-n16; the encoder does not depend on n_pos).  name -> (weight seed, image generator, image seed, B, C, H, W,
+# offset gain, small_variance seed or None, whether x1 and x2 are stored: on the two large cases x1 alone is above the size limit of a committed file)
+ENC_STAGES = {
+    "enc_8x8_b1_rgb_noise_g1": (30, "noise_image", 1, 1, 3, 8, 8, 1.0, None, True),
+    "enc_8x8_b1_rgb_noise_g4_smallvar": (42, "noise_image", 2, 1, 3, 8, 8, 4.0, 1, True),
+    "enc_24x17_b2_rgb_noise_g4": (38, "noise_image", 3, 2, 3, 24, 17, 4.0, None, True),
+    "enc_31x33_b1_gray_noise_g1": (33, "noise_image", 4, 1, 1, 31, 33, 1.0, None, True),
+    "enc_40x56_b1_rgb_image_g4": (58, "aliked_image", 5, 1, 3, 40, 56, 4.0, None, True),
+    "enc_40x300_b1_rgb_noise_g4": (35, "noise_image", 6, 1, 3, 40, 300, 4.0, None, False),
+    "enc_72x90_b1_rgb_noise_g1": (36, "noise_image", 7, 1, 3, 72, 90, 1.0, None, False),
+}
+
+
+def encoder_inputs(name: str, gain: float = None):
+    """(state dict, image [B, C, H, W]) of an ENC_STAGES case; `gain` replaces the table's offset gain"""
+    wseed, gen, iseed, b, c, h, w, g, sv, _ = ENC_STAGES[name]
+    sd = aliked_state_dict(wseed, "aliked-n16")
+    if sv is not None:
+        sd = small_variance(sd, sv)
+    sd = scaled_encoder_offsets(sd, g if gain is None else gain)
+    return sd, {"noise_image": noise_image, "aliked_image": aliked_image}[gen](iseed, b, h, w, c)
 # DKD on crafted score maps.  name -> (map generator, its arguments, radius, top_k, scores_th, n_limit, image_size or None).  Only cases the
 # reference defines: image_size absent or equal to the map, and in top-k mode at least top_k positive maxima.
 DKD_STAGES = {
@@ -256,6 +312,28 @@ def make_stages(mod):
         meta = {"model": model, "wseed": wseed, "gain": gain, "lseed": lseed, "b": b, "h": h, "w": w, "n": n, "kseed": kseed}
         np.savez_compressed(STAGES / f"{name}.npz", meta=json.dumps(meta), descriptors=np.stack([d.numpy() for d in desc]))
         print(f"{name}: {clamped:.0%} of the offsets at the clamp")
+    for name, (wseed, gen, iseed, b, c, h, w, gain, sv, store_x12) in ENC_STAGES.items():
+        sd, image = encoder_inputs(name)
+        mod.torch.hub.load_state_dict_from_url = lambda url, map_location=None, _sd=sd: _sd
+        net = mod.ALIKED(model_name="aliked-n16").eval()
+        taps = {}   # conv1 .. conv4: (the output tensor itself, which the in-place SELU of extract_dense_map then gates; a copy taken before that)
+        hooks = [getattr(net, f"conv{i}").register_forward_hook(lambda m, a, out, _i=i: taps.__setitem__(_i, (out, out.detach().clone()))) for i in range(1, 5)]
+        with torch.no_grad():
+            _, score_map = net.extract_dense_map(image if c == 3 else mod.grayscale_to_rgb(image))
+        for hk in hooks:
+            hk.remove()
+        levels = {}
+        for i in range(1, 5):
+            gated, raw = taps[i]
+            assert torch.equal(gated, F.selu(raw)) and not torch.equal(gated, raw), "the hooked tensor must hold the gated level map"
+            levels[f"x{i}"] = gated.permute(0, 2, 3, 1).contiguous().numpy()              # [B, Hp >> s, Wp >> s, 32]: the layout of ALIKED.level_maps
+        if not store_x12:
+            del levels["x1"], levels["x2"]
+        meta = {"wseed": wseed, "gen": gen, "iseed": iseed, "b": b, "c": c, "h": h, "w": w, "gain": gain, "small_variance": sv}
+        np.savez_compressed(STAGES / f"{name}.npz", meta=json.dumps(meta), scores=score_map[:, 0].numpy(), **levels)
+        size = (STAGES / f"{name}.npz").stat().st_size
+        assert size < 952 * 1024, f"{name}: {size} bytes"
+        print(f"{name}: levels {sorted(levels)} {size} bytes, score range [{float(score_map.min()):.3f}, {float(score_map.max()):.3f}]")
 
 
 # ---------------------------------------------------------------------------------------------------- deform_conv2d restatement
