@@ -1182,6 +1182,100 @@ int64_t lg_posegraph_workspace_bytes(int64_t images, int64_t pairs, uint32_t fla
 /* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
 int lg_posegraph_solve(const lg_posegraph_io* io, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Global positioning: the camera centres of the free images and the points of all tracks, solved jointly from the viewing rays of every observation, with
+ * the rotations kept as they come in (from lg_posegraph_solve, say) and at least two images held to fix origin, orientation and scale.  It replaces the
+ * positions that averaging the pairs' translation directions gives: a track ties many rays to one point, a pair carries one direction.  The points come with
+ * it, so lg_bundle_adjust can start from (track_id_out, xyz) directly.  fp64 throughout, no fused multiply-add, dense Cholesky, one call and one host
+ * synchronisation.  Stateless.  The reference has no such step; this is the definition (tests/positioning_oracle.py restates it in float64 numpy).
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   nodes     as in the triangulator: node v = k n + i, live iff i < num[k] (num NULL: n; clamped into [0, n]).
+ *   images    image k PASSES iff cameras[k] passes the camera rule and the 9 entries of its rotation (poses[k], columns 0 .. 2) are finite; a HELD image
+ *             (constant_pose[k] != 0) also needs its 3 translation entries finite.  The translation of an image that is not held is not read.  status[k] is
+ *             LG_ERR_CAMERA for an image that does not pass, else LG_OK.  A held image's centre is c = -(R^T t), each entry -((R0e t0 + R1e t1) + R2e t2).
+ *   gauge     at least two held images must pass and their centres must not all be equal; otherwise nothing is solved (summary[5] = 0: the Python layer
+ *             raises).  They fix origin, orientation and scale.
+ *   ray       of node (k, i): u = ((x - cx) / fx, (y - cy) / fy, 1) from the float32 inputs widened, w = R_k^T u, entry e: (R0e ux + R1e uy) + R2e, and
+ *             v = w / |w|, |w| = sqrt((w0 w0 + w1 w1) + w2 w2): the length is taken of the ROTATED vector, as the triangulator does, because a float32 R is
+ *             orthonormal to 1e-7 only and I - v v^T must be a projection (parallel rays must fail the 3 x 3 pivot).  R is NOT re-orthonormalised.
+ *   candidates  node (k, i) with j = track_id[k][i] is a candidate observation of track j iff i < num[k], 0 <= j < tracks and image k passes.  Two rows of one
+ *             image in one track are two observations.  A track with more than LG_BA_MAX_TRACK_LENGTH candidates is left out.  A track's observations are
+ *             ordered by ascending node.
+ *   who takes part  start from all candidates of the tracks with 2 .. LG_BA_MAX_TRACK_LENGTH of them and all images that pass; repeat until nothing changes:
+ *             a track leaves if it has observations in fewer than two DIFFERENT images still there; an image that is not held leaves if it has observations
+ *             in fewer than two different tracks still there.  (Removal is monotone: what is left does not depend on the order of the removals.)  Then the
+ *             images and tracks that no chain of shared observations joins to a held image leave as "not connected".  An image that takes part and is not
+ *             held is FREE.
+ *   cost      the sum of rho |(I - v v^T)(X_j - c_k)|^2 over the observations taking part, solved by num_iterations steps of reweighted LINEAR least squares
+ *             in all free centres and all points at once.  Iteration 0: rho = 1 (no initial centres or points are needed).  Later, with e = X_j - c_k of the
+ *             previous iterate: rho = (1 / max(|e|^2, 1e-12)) / (1 + (phi / s)^2), phi = atan2(|e - (v . e) v|, v . e), s = angle_scale max(1, 2^(n - 6 - it))
+ *             (the position stage's schedule and depth weight in lg_posegraph_solve, for the same reason: the cost must not shrink the scene).
+ *   system    M = rho (I - v v^T) per observation, entries rho (1 - v0 v0), rho (0 - v0 v1), ...  Per track: V_j = sum of M, g_j = sum over its observations in
+ *             HELD images of M c_k (rows (m0 c0 + m1 c1) + m2 c2), in list order; Vi_j column c = the solution of V_j x = e_c by the triangulator's 3 x 3
+ *             elimination and pivot rule.  A failed pivot takes the track out for the rest of the call (node_state 6).  Reduced system over the free centres,
+ *             3 images x 3 images of 3 x 3 blocks, lower block triangle: for free a and free b <= a, E_ab = sum over the rows i of image a in ascending order
+ *             whose observation takes part, and for each over the observations (b, i') of the same track in list order, of Y M_(b,i') with Y = M_(a,i) Vi_j
+ *             (Y[r][m] = (M[r][0] Vi[0][m] + M[r][1] Vi[1][m]) + M[r][2] Vi[2][m]; entry (r, c): (Y[r][0] Mb[0][c] + Y[r][1] Mb[1][c]) + Y[r][2] Mb[2][c]);
+ *             S_ab = -E_ab, S_aa = U_a - E_aa with U_a = sum of M over the same rows; right-hand side of a = sum over the same rows of Y g_j.  These three
+ *             sums over the rows of image a run in GROUPS of G consecutive rows, G = half the smallest power of two >= max(images, 2): a group's terms are
+ *             added in ascending row order starting from zero, and the groups' sums are added to the total in ascending order (with few images a
+ *             workgroup shares the rows out over its lanes; the order stays a function of position alone).  Every other image: identity rows and columns,
+ *             zero right-hand side.
+ *   Cholesky  lg_posegraph_solve's: the bundle adjuster's blocked factorisation with one right-hand-side row and the pivot floor 1e-10 x the diagonal entry.
+ *             A failed pivot of ANY iteration clears positions_ok: no free image gets a centre (image_state 5) and no point is returned (node_state 9).
+ *   points    X_j = Vi_j (g_j + sum over its observations in free images, in list order, of M c_k) with the NEW centres and this iteration's M.
+ *   stopping  num_iterations is a fixed budget, every launch is enqueued unconditionally; the stage ends after an iteration with s = angle_scale, every
+ *             step finite and max |c_new - c_old| < 1e-12 (that iteration's points are still formed); later launches return at once.
+ *   final state  per observation taking part: angle_error = phi in degrees at the final centres and points; it is an OUTLIER (node_state 7) iff not
+ *             (v . e > 0 and phi <= max_angle_error).  No solve follows.  A track left with inlier observations in fewer than two different images has no
+ *             point (those nodes: 8).
+ *   node_state  0 not labelled; 1 inlier observation; 2 bad image; 3 a candidate of a track with more than LG_BA_MAX_TRACK_LENGTH; 4 peeled (its track has
+ *             fewer than 2 candidates, or its track or image left in the peeling); 5 not connected; 6 its track's 3 x 3 pivot failed; 7 outlier; 8 inlier of a
+ *             track without a point; 9 no solution (a Cholesky pivot failed).
+ *   image_state  0 posed (free, with a centre); 1 held; 2 too few tracks (peeled); 3 not connected; 4 bad image; 5 no solution.
+ *   outputs   poses_out [images][12]: R the input's bits; t = -(R c) rounded to float32 once for a posed image, the input's bits for a held one, NaN for states
+ *             2, 3, 5; all twelve NaN for a bad image.  xyz [tracks][3] rounded once, NaN for a track without a point.  points3d [images][n][3] the point and
+ *             track_id_out [images][n] the input label at every inlier observation, NaN / -1 elsewhere (labels are not renumbered).  angle_error [images][n],
+ *             NaN where not evaluated.  summary [8] fp64: images with a pose (held or posed), tracks with a point, outlier observations, iterations run,
+ *             positions_ok, gauge ok, tracks whose 3 x 3 pivot failed, 0.
+ *   Determinism: no floating-point atomics; every sum is a fixed function of position (a track's list in ascending node order, an image's rows ascending,
+ *             images ascending), so every output is the same bits from run to run and under any relabelling of the tracks.  An image that does not pass
+ *             takes its observations out and leaves everything else bit for bit.
+ * Workspace: lg_positioning_workspace_bytes bytes (below; -1 outside the envelope), 256-byte aligned: a 256-byte record; 180 bytes per image; the system with
+ *   its right-hand side row, (3 images + 1) x 3 images fp64 (4.7 MB at 256 images); 40 bytes per node (list entry, its image, ray, rho); 140 bytes per track.
+ * Envelope (LG_ERR_INVALID with a message before the GPU is touched): null io; any flag bit (none is defined); n above LG_MAX_KEYPOINTS; images outside
+ *   [2, LG_BA_MAX_IMAGES]; images x n above LG_MAX_ROWS; tracks outside [0, images x n / 2]; num_iterations outside [LG_PG_MIN_ITERATIONS,
+ *   LG_BA_MAX_ITERATIONS]; angle_scale or max_angle_error not finite and > 0; a null required pointer; a workspace too small or not 256-byte aligned.
+ * Launches, none of which waits on another workgroup: records; candidates and rays (count); one scan over the tracks; fill; sort (one lane per track); who
+ *   takes part (ONE workgroup); per iteration points (one lane per track), reduce (one workgroup per image: its block row), two per Cholesky panel, centres
+ *   (ONE workgroup), point update (one lane per track); classify (one lane per track); output.  8 + n (4 + 2 ceil(3 images / 48)) in all. */
+typedef struct lg_positioning_io {
+    int32_t n, images, tracks;
+    uint32_t flags;                        /* none defined: must be 0                                                 */
+    int32_t num_iterations;                /* in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]                         */
+    double angle_scale;                    /* degrees, > 0                                                            */
+    double max_angle_error;                /* degrees, > 0                                                            */
+    const float *kpts;                     /* [images][n][2], read in place                                           */
+    const int32_t *num;                    /* [images] live rows, or NULL = n                                         */
+    const int64_t *track_id;               /* [images][n]: the triangulator's labels                                  */
+    const float *cameras;                  /* [images][4]: (fx, fy, cx, cy)                                           */
+    const float *poses;                    /* [images][12]: (R | t) row-major 3 x 4; t is read for held images only   */
+    const uint8_t *constant_pose;          /* [images]: non-zero = the image is held                                  */
+    void *workspace; int64_t workspace_bytes;
+    float *poses_out;                      /* [images][12]                                                            */
+    float *xyz;                            /* [tracks][3]                                                             */
+    float *points3d;                       /* [images][n][3]                                                          */
+    int64_t *track_id_out;                 /* [images][n]                                                             */
+    uint8_t *node_state;                   /* [images][n]                                                             */
+    uint8_t *image_state;                  /* [images]                                                                */
+    float *angle_error;                    /* [images][n] degrees                                                     */
+    double *summary;                       /* [8]                                                                     */
+    int32_t *status;                       /* [images] LG_OK / LG_ERR_CAMERA                                          */
+} lg_positioning_io;
+int64_t lg_positioning_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_positioning_solve(const lg_positioning_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

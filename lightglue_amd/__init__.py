@@ -14,14 +14,15 @@ from .abspose import AbsolutePoseEstimator  # noqa: F401
 from .triangulate import Triangulator  # noqa: F401
 from .bundle import BundleAdjuster  # noqa: F401
 from .posegraph import GlobalPoseEstimator  # noqa: F401
+from .positioning import GlobalPositioner  # noqa: F401
 from .superpoint import SuperPoint, plan_image_batches  # noqa: F401
 from .aliked import ALIKED  # noqa: F401
 from .preprocess import ImagePreprocessor, numpy_image_to_torch  # noqa: F401
 from .parallel import PairShardedMatcher, shard_range  # noqa: F401
 from .inflight import InflightMatcher  # noqa: F401
 from .sift import filter_dog_point, sift_features, sift_to_rootsift  # noqa: F401
-from .glue import batch_to_device, cm_prune, collate_features, extracted_to_image_frame, match_batch, match_pair, match_pairs, prefetch_to_device, rbd, verify_pairs, estimate_poses, estimate_absolute_poses, triangulate_tracks, bundle_adjust, estimate_global_poses  # noqa: F401
+from .glue import batch_to_device, cm_prune, collate_features, extracted_to_image_frame, match_batch, match_pair, match_pairs, prefetch_to_device, rbd, verify_pairs, estimate_poses, estimate_absolute_poses, triangulate_tracks, bundle_adjust, estimate_global_poses, position_from_tracks  # noqa: F401
 
-__all__ = ["LightGlue", "NearestNeighborMatcher", "TwoViewVerifier", "verify_pairs", "RelativePoseEstimator", "estimate_poses", "AbsolutePoseEstimator", "estimate_absolute_poses", "Triangulator", "triangulate_tracks", "BundleAdjuster", "bundle_adjust", "GlobalPoseEstimator", "estimate_global_poses", "SuperPoint", "ALIKED", "ImagePreprocessor", "numpy_image_to_torch", "PairShardedMatcher", "InflightMatcher", "shard_range", "match_pair", "match_batch", "match_pairs", "collate_features", "extracted_to_image_frame", "rbd", "cm_prune",
+__all__ = ["LightGlue", "NearestNeighborMatcher", "TwoViewVerifier", "verify_pairs", "RelativePoseEstimator", "estimate_poses", "AbsolutePoseEstimator", "estimate_absolute_poses", "Triangulator", "triangulate_tracks", "BundleAdjuster", "bundle_adjust", "GlobalPoseEstimator", "estimate_global_poses", "GlobalPositioner", "position_from_tracks", "SuperPoint", "ALIKED", "ImagePreprocessor", "numpy_image_to_torch", "PairShardedMatcher", "InflightMatcher", "shard_range", "match_pair", "match_batch", "match_pairs", "collate_features", "extracted_to_image_frame", "rbd", "cm_prune",
            "batch_to_device", "prefetch_to_device", "plan_image_batches", "sift_to_rootsift", "filter_dog_point", "sift_features"]
 __version__ = "0.2.0"

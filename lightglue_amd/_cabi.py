@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "lg_triangulate_workspace_bytes", "lg_triangulate", "lg_triangulate_robust_workspace_bytes", "lg_triangulate_robust",
     "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
+    "lg_positioning_workspace_bytes", "lg_positioning_solve",
 )
 
 
@@ -192,6 +193,18 @@ class LgPosegraphIO(C.Structure):
         ("pair_index", _fp), ("rotations", _fp), ("translations", _fp), ("weights", _fp), ("num_inliers", _fp),
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("poses", _fp), ("image_state", _fp), ("pair_state", _fp), ("rotation_error", _fp), ("direction_error", _fp), ("summary", _fp),
+    ]
+
+
+class LgPositioningIO(C.Structure):
+    """lg_positioning_io (include/lightglue_amd.h): one call of the global positioner"""
+    _fields_ = [
+        ("n", C.c_int32), ("images", C.c_int32), ("tracks", C.c_int32), ("flags", C.c_uint32), ("num_iterations", C.c_int32),
+        ("angle_scale", C.c_double), ("max_angle_error", C.c_double),
+        ("kpts", _fp), ("num", _fp), ("track_id", _fp), ("cameras", _fp), ("poses", _fp), ("constant_pose", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64),
+        ("poses_out", _fp), ("xyz", _fp), ("points3d", _fp), ("track_id_out", _fp), ("node_state", _fp), ("image_state", _fp), ("angle_error", _fp),
+        ("summary", _fp), ("status", _fp),
     ]
 
 
@@ -384,6 +397,9 @@ def load() -> C.CDLL:
     lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
     lib.lg_posegraph_workspace_bytes.restype = C.c_int64
     lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]
+    lib.lg_positioning_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
+    lib.lg_positioning_workspace_bytes.restype = C.c_int64
+    lib.lg_positioning_solve.argtypes = [C.POINTER(LgPositioningIO), C.c_void_p]
     for fn, io in EXTRACT_STAGES.items():      # the six extractor stages: lg_<stage>(const lg_<stage>_io*, hipStream_t)
         getattr(lib, fn).argtypes = [C.POINTER(io), C.c_void_p]
     lib.lg_debug_mfma_sustained.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]

@@ -248,6 +248,32 @@ inline const char* pg_settings_error(long long images, long long num_iterations,
         return "rotation_scale, max_rotation_error and direction_scale must be > 0 (and finite)";
     return nullptr;
 }
+// lg_positioning_solve: a 256-byte record of the call; per image a 128-byte record (camera, rotation, held centre), its flags (4) and its centre twice in fp64
+// (48); the position system with its right-hand side row, (3 images + 1) x 3 images fp64; per node its track-list entry and that entry's image (8), its ray
+// (24) and its weight (8); per track five int32 (count, offset, cursor, state, reached) and fifteen fp64 (the point, Vi, g: 120 bytes)
+constexpr uint32_t POS_KNOWN_FLAGS = 0u;
+struct PosLayout { long long nodes, head, rec, iflag, cen, S, list, limg, ray, rho, tcnt, toff, tcur, tin, treach, X, Vinv, g, total; };
+inline const char* pos_layout(long long images, long long n, long long tracks, uint32_t flags, PosLayout& L) {
+    if (flags & ~POS_KNOWN_FLAGS) return "undefined flag bits (the positioner defines none)";
+    if (n < 0 || n > LG_MAX_KEYPOINTS) return "n must lie in [0, LG_MAX_KEYPOINTS]";
+    if (images < 2 || images > LG_BA_MAX_IMAGES) return "images must lie in [2, LG_BA_MAX_IMAGES]";
+    if (images * n > LG_MAX_ROWS) return "images x n must lie in [0, LG_MAX_ROWS]";
+    if (tracks < 0 || tracks > images * n / 2) return "tracks must lie in [0, images x n / 2]";
+    L.nodes = images * n;
+    Bump bp;
+    L.head = bp.take(256); L.rec = bp.take(images * 128); L.iflag = bp.take(images * 4); L.cen = bp.take(images * 48);
+    L.S = bp.take((3 * images + 1) * 3 * images * 8);
+    L.list = bp.take(L.nodes * 4); L.limg = bp.take(L.nodes * 4); L.ray = bp.take(L.nodes * 24); L.rho = bp.take(L.nodes * 8);
+    L.tcnt = bp.take(tracks * 4); L.toff = bp.take(tracks * 4); L.tcur = bp.take(tracks * 4); L.tin = bp.take(tracks * 4); L.treach = bp.take(tracks * 4);
+    L.X = bp.take(tracks * 24); L.Vinv = bp.take(tracks * 72); L.g = bp.take(tracks * 24); L.total = bp.used;
+    return nullptr;
+}
+inline const char* pos_settings_error(long long num_iterations, double angle_scale, double max_angle_error) {
+    if (num_iterations < LG_PG_MIN_ITERATIONS || num_iterations > LG_BA_MAX_ITERATIONS) return "num_iterations must lie in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]";
+    auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
+    if (!positive(angle_scale) || !positive(max_angle_error)) return "angle_scale and max_angle_error must be > 0 (and finite)";
+    return nullptr;
+}
 // lg_sift_filter: two int32 rasters per image (m1 | m2 contiguous: one clear) and one flag per detection
 struct SiftFilterLayout { long long m1, m2, flags, total; };
 inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilterLayout& L) {

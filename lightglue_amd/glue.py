@@ -249,6 +249,14 @@ def estimate_global_poses(estimator, relative, pairs, num_images, **kw) -> dict:
     return estimator.estimate(pairs, relative, num_images, **kw)
 
 
+def position_from_tracks(positioner, tracks, feats, cameras, poses, constant_pose=None) -> dict:
+    """Camera centres and track points from the tracks of `Triangulator.build_tracks` (`tracks`: its dict, or (track_id, T)) and the rotations of
+    `estimate_global_poses` (`poses`: its dict — origin and baseline are then held —, [K, 3, 4] or (R, t)), by a `GlobalPositioner`: the same store (or a list
+    of per-image dicts, collated once) and cameras; constant_pose: a [K] bool mask or image indices, at least two.  Returns the positioner's dict: its poses are
+    what `triangulate_tracks` takes, (track_id, xyz) what `bundle_adjust` takes as `tracks`, points3d what `estimate_absolute_poses` takes."""
+    return positioner.solve(_as_store(feats), tracks, cameras, poses, constant_pose)
+
+
 def cm_prune(prune):
     """RGBA colour per keypoint from the matcher's ``prune0`` / ``prune1`` output (the layer at which a point was
     dropped; points alive to the end carry the maximum) — the consumer the reference ships for that output
