@@ -1100,6 +1100,61 @@ int64_t lg_bundle_robust_workspace_bytes(int64_t images, int32_t n, int64_t trac
 int lg_bundle_adjust_robust(const lg_bundle_robust_io* io, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The bundle adjuster with one focal length per image refined next to the poses and the points.  lg_bundle_adjust and lg_bundle_adjust_robust are unchanged
+ * in every bit, message and refusal (their kernels' instruction streams are compared in profiles/bundle_adjust_focal.md); this is a third entry point whose
+ * io holds lg_bundle_robust_io as `base`.  tests/bundle_focal_oracle.py restates it in float64 numpy.  Everything not named here is lg_bundle_adjust_robust's
+ * definition (and through it lg_bundle_adjust's), word for word: candidates, observations, node states, status, the loss and its weights, the stages and the
+ * filter, the point blocks, the damping, the accept / reject / convergence rules, the stopping.
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   unknowns  image k carries SEVEN: the pose's twist (w, d) as before (columns 0 .. 5) and d_k (column 6), the logarithm of a common scale of fx and fy.
+ *             Update: fx <- fx exp(d_k), fy <- fy exp(d_k) (exp of the fp64 library), so the aspect ratio and the sign of the focal lengths stay; cx and cy
+ *             are never touched.  The camera state is carried in fp64 through the call like the poses, starting from the float32 inputs widened, it lives
+ *             twice (the accepted state and the trial) and every residual, Jacobian, cost and filter test reads the state it belongs to.
+ *   Jacobian  column 6 of A at camera-frame point p: (ax px, by py) with ax = fx iz, by = fy iz of lg_bundle_adjust, fx and fy of the ACCEPTED state: the
+ *             derivative of ((fx exp(d) px) iz, (fy exp(d) py) iz) at d = 0.  Under a robust loss both entries are multiplied by sw with the rest of the row.
+ *   free columns  pose and camera are held independently.  Columns 0 .. 5 of image k are free iff the image is FREE in lg_bundle_adjust's sense (camera rule,
+ *             constant_pose[k] = 0, at least one active observation); column 6 is free iff the image passes the camera rule, constant_camera[k] = 0
+ *             (constant_camera NULL: no camera is held) and it has at least one active observation.  A held column is lg_bundle_adjust's dropped column:
+ *             identity diagonal, zero coupling to every other column (those of its own image included), zero right-hand side, step 0.  An image with a held
+ *             pose and a free camera returns its pose as the bits that went in and its focal lengths refined; with a free pose and a held camera the
+ *             reverse; an image that fails the camera rule or has no active observation keeps both.  Nothing here fixes the gauge of the poses: the
+ *             caller holds at least one, as before.  After a filter an image may lose its last observation: both its pose and its camera then stop moving
+ *             and return their last accepted state (lg_bundle_adjust_robust's rule for poses).
+ *   layout    the reduced system S has 7 images columns, INTERLEAVED per image: column 7 k + c is unknown c of image k, so block (a, b) is 7 x 7 and the
+ *             right-hand side is row 7 images of S.  U_a = sum A^T A (7 x 7), g_a = sum A^T r, W = A^T B (7 x 3), Y = W Vi, E_ab, S_ab = -E_ab,
+ *             S_aa = U'_a - E_aa and the right-hand side (sum of W y_j) - g_a are lg_bundle_adjust's formulas with r, c running to 6, over the same rows and
+ *             observations in the same orders; every diagonal entry of U, column 6's included, is damped by Marquardt's rule; then the held columns
+ *             are overwritten as above.  Cholesky, its panels of LG_BA_CHOLESKY_BLOCK columns, the failed-pivot rule and the back substitution with its five
+ *             interleaved partial sums are lg_bundle_adjust's on dim = 7 images (with 7 images the 49 columns cross the first panel by one).
+ *   point step  as lg_bundle_adjust with W^T s summed over r = 0 .. 6 ascending, over the track's observations of images with at least one free column
+ *             (a held column's step is 0).
+ *   trial     as lg_bundle_adjust_robust; additionally a trial is REJECTED if a free camera's trial fx or fy is not finite or not > 0.
+ *   outputs   those of lg_bundle_adjust_robust, and cameras_out [images][4]: fx and fy of the accepted state rounded to float32 once for a camera that was
+ *             free in any stage, the input's bits for every other camera; cx and cy always the input's bits.  An image with LG_ERR_CAMERA returns its input
+ *             row.  summary [12]: as lg_bundle_adjust_robust, and 10 = the number of cameras that were free in any stage.
+ *   Determinism: as lg_bundle_adjust (no floating-point atomics, every sum a fixed function of position, the same bits from run to run and under a relabelling
+ *             of the tracks).  With every camera held the result is lg_bundle_adjust_robust's within rounding (the same sums at other positions of a wider
+ *             matrix: other panels, other partial sums); bit equality is not promised.
+ * Workspace: lg_bundle_focal_workspace_bytes bytes (-1 outside the envelope), 256-byte aligned: that of lg_bundle_adjust_robust with 56 bytes of step per
+ *   image instead of 48 and S with its right-hand side row as (7 images + 1) x 7 images fp64 (25.7 MB at 256 images instead of 18.9), plus the camera state
+ *   twice (64 bytes per image).
+ * Envelope (LG_ERR_INVALID with a message that names the field, before the GPU is touched), in this order: null io; the layout (any bit in
+ *   base.base.flags, n, images, images x n, tracks: lg_bundle_adjust's bounds); the robust settings (loss, loss_scale, filter_rounds, max_reproj_error:
+ *   lg_bundle_adjust_robust's rules); a null cameras_out; then lg_bundle_adjust's list (num_iterations, initial_damping and function_tolerance, a null
+ *   required pointer, the workspace).  A null constant_camera is not refused.
+ * Launches, none of which waits on another workgroup: those of lg_bundle_adjust_robust, each in the instantiation that reads the camera state; the reduce
+ *   runs one workgroup per image and 4 column blocks (4 x 49 entry threads, and in the diagonal workgroup 28 + 7 + 7 threads for U, g and the sum of W y);
+ *   the back substitution (ONE workgroup) also writes the trial cameras; the scatter also writes cameras_out. */
+typedef struct lg_bundle_focal_io {
+    lg_bundle_robust_io base;              /* base.base.workspace: lg_bundle_focal_workspace_bytes; summary: [12]     */
+    const uint8_t *constant_camera;        /* [images]: non-zero = the camera is held fixed; NULL = none is held      */
+    float *cameras_out;                    /* [images][4]                                                             */
+} lg_bundle_focal_io;
+int64_t lg_bundle_focal_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_bundle_adjust_focal(const lg_bundle_focal_io* io, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Global poses: one pose per image from the relative poses of a pair list (what lg_relpose_estimate returns), by rotation averaging over the view graph and
  * position averaging along the pairs' translation directions, both robust to wrong pairs; the per-image poses are what lg_triangulate and lg_bundle_adjust
  * take.  fp64 throughout, no fused multiply-add, dense Cholesky, one call and one host synchronisation.  Stateless.  The reference has no such step; this is

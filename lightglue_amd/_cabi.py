@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = (
     "lg_relpose_workspace_bytes", "lg_relpose_estimate",
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
     "lg_triangulate_workspace_bytes", "lg_triangulate", "lg_triangulate_robust_workspace_bytes", "lg_triangulate_robust",
-    "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust",
+    "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust", "lg_bundle_focal_workspace_bytes", "lg_bundle_adjust_focal",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
     "lg_positioning_workspace_bytes", "lg_positioning_solve",
 )
@@ -183,6 +183,11 @@ class LgBundleIO(C.Structure):
 class LgBundleRobustIO(C.Structure):
     """lg_bundle_robust_io (include/lightglue_amd.h): one call of the bundle adjuster's robust mode"""
     _fields_ = [("base", LgBundleIO), ("loss", C.c_int32), ("filter_rounds", C.c_int32), ("loss_scale", C.c_double), ("max_reproj_error", C.c_double)]
+
+
+class LgBundleFocalIO(C.Structure):
+    """lg_bundle_focal_io (include/lightglue_amd.h): one call of the bundle adjuster with per-image focal lengths refined"""
+    _fields_ = [("base", LgBundleRobustIO), ("constant_camera", _fp), ("cameras_out", _fp)]
 
 
 class LgPosegraphIO(C.Structure):
@@ -394,6 +399,9 @@ def load() -> C.CDLL:
     lib.lg_bundle_robust_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_bundle_robust_workspace_bytes.restype = C.c_int64
     lib.lg_bundle_adjust_robust.argtypes = [C.POINTER(LgBundleRobustIO), C.c_void_p]
+    lib.lg_bundle_focal_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
+    lib.lg_bundle_focal_workspace_bytes.restype = C.c_int64
+    lib.lg_bundle_adjust_focal.argtypes = [C.POINTER(LgBundleFocalIO), C.c_void_p]
     lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
     lib.lg_posegraph_workspace_bytes.restype = C.c_int64
     lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]

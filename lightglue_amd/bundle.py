@@ -1,7 +1,9 @@
-"""Bundle adjustment of poses and points on the device, on the kernels of `csrc/lg_bundle.hip` behind `lg_bundle_adjust` and, with a robust loss or filter
-rounds, `lg_bundle_adjust_robust` (include/lightglue_amd.h holds both definitions).  It reads what `Triangulator` returns — `track_id [K, N]` and `xyz [T, 3]` over ONE keypoint store — in place, plus one pinhole camera
+"""Bundle adjustment of poses, points and (opt-in) per-image focal lengths on the device, on the kernels of `csrc/lg_bundle.hip` behind `lg_bundle_adjust`,
+with a robust loss or filter rounds `lg_bundle_adjust_robust`, and with `refine_focal=True` `lg_bundle_adjust_focal` (include/lightglue_amd.h holds the three definitions).  It reads what `Triangulator` returns — `track_id [K, N]` and `xyz [T, 3]` over ONE keypoint store — in place, plus one pinhole camera
 (fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image, and refines all free poses and all track points jointly: Levenberg-Marquardt on the
-sum of squared pixel reprojection errors, Schur complement, dense Cholesky, fp64.  Intrinsics are fixed.  ONE call with ONE host synchronisation; `points3d
+sum of squared pixel reprojection errors, Schur complement, dense Cholesky, fp64.  Intrinsics are fixed unless `refine_focal=True`: then every image carries
+one more unknown, the logarithm of a common scale of fx and fy (cx, cy stay), held or free per image by `constant_camera` independently of its pose, and the
+dict holds `cameras [K, 4]`, which every other estimator takes as it is.  Principal point, distortion, shared intrinsics and a prior stay out.  ONE call with ONE host synchronisation; `points3d
 [K, N, 3]` (NaN where a row is no active observation) is what `AbsolutePoseEstimator` takes as points3d1."""
 from __future__ import annotations
 
@@ -36,22 +38,22 @@ def as_tracks(tracks, K: int, N: int, device):
     return tid.detach().to(device=device, dtype=torch.int64).contiguous(), xyz.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-def as_constant(constant_pose, K: int) -> torch.Tensor:
-    """[K] bool on the host from a [K] mask or a sequence of image indices; at least one image must be constant"""
+def as_constant(constant_pose, K: int, name: str = "constant_pose") -> torch.Tensor:
+    """[K] bool on the host from a [K] mask or a sequence of image indices; at least one pose must be constant (no camera need be: name = "constant_camera")"""
     c = torch.as_tensor(constant_pose).detach().cpu()
     if c.numel() == 0 and c.dtype is not torch.bool:       # an empty index list (torch reads [] as float)
         c = c.reshape(0).long()
     if c.dtype is not torch.bool:
         if c.dtype.is_floating_point or c.dim() != 1:
-            raise ValueError("constant_pose must be a [K] bool mask or a sequence of image indices")
+            raise ValueError(f"{name} must be a [K] bool mask or a sequence of image indices")
         if c.numel() and (int(c.min()) < 0 or int(c.max()) >= K):
-            raise ValueError(f"constant_pose names an image outside [0, {K})")
+            raise ValueError(f"{name} names an image outside [0, {K})")
         mask = torch.zeros(K, dtype=torch.bool)
         mask[c.long()] = True
         c = mask
     if tuple(c.shape) != (K,):
-        raise ValueError(f"constant_pose must have shape [{K}], got {tuple(c.shape)}")
-    if not bool(c.any()):
+        raise ValueError(f"{name} must have shape [{K}], got {tuple(c.shape)}")
+    if name == "constant_pose" and not bool(c.any()):
         raise ValueError("constant_pose holds no image: nothing fixes the gauge (hold at least one pose; two fix scale as well)")
     return c
 
@@ -62,11 +64,16 @@ class BundleAdjuster(nn.Module):
     scale of the reconstruction, with one the damping holds it (it may drift slowly).
     loss: "squared", "huber" or "cauchy" on the pixel error, with loss_scale (c, pixels) where the loss bends; filter_rounds in [0, 4]: after each of that
     many stages of num_iterations the observations above max_reproj_error (pixels) are dropped (node_state 7) and the rest is adjusted again.  The defaults
-    (squared, no filter) call `lg_bundle_adjust` as before; anything else calls `lg_bundle_adjust_robust`."""
+    (squared, no filter) call `lg_bundle_adjust` as before; anything else calls `lg_bundle_adjust_robust`.
+    refine_focal: every image carries one more unknown d, a step sets fx <- fx exp(d), fy <- fy exp(d) (the aspect ratio and the sign stay, cx and cy are not
+    touched); `adjust` then takes `constant_camera` and returns `cameras` and `num_free_cameras`, on `lg_bundle_adjust_focal`, with every loss and filter
+    setting meaning what it means without it.  False (the default) changes nothing."""
 
     def __init__(self, num_iterations: int = 10, initial_damping: float = 1e-4, function_tolerance: float = 1e-6, loss: str = "squared", loss_scale: float = 2.0,
-                 filter_rounds: int = 0, max_reproj_error: float = 4.0):
+                 filter_rounds: int = 0, max_reproj_error: float = 4.0, refine_focal: bool = False):
         super().__init__()
+        if not isinstance(refine_focal, (bool, np.bool_)):
+            raise ValueError(f"refine_focal must be a bool, got {refine_focal!r}")
         # the defaults are not examined further (what the C side does not read is not refused), and the robust settings are ONE attribute: an nn.Module
         # pays for every attribute it sets, and this constructor sits inside callers' loops
         if not (loss == "squared" and type(filter_rounds) is int and filter_rounds == 0):
@@ -78,7 +85,7 @@ class BundleAdjuster(nn.Module):
                 raise ValueError(f"loss_scale must be > 0 with a robust loss, got {loss_scale!r}")
             if int(filter_rounds) > 0 and not 0.0 < float(max_reproj_error) < float("inf"):
                 raise ValueError(f"max_reproj_error must be > 0 with filter_rounds > 0, got {max_reproj_error!r}")
-        self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0)
+        self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0, bool(refine_focal))
         if int(num_iterations) != num_iterations or not 1 <= int(num_iterations) <= _cabi.LG_BA_MAX_ITERATIONS:
             raise ValueError(f"num_iterations must be an integer in [1, {_cabi.LG_BA_MAX_ITERATIONS}], got {num_iterations!r}")
         if not 0.0 < float(initial_damping) < float("inf"):
@@ -91,6 +98,7 @@ class BundleAdjuster(nn.Module):
     loss_scale = property(lambda self: self.robust[1])
     filter_rounds = property(lambda self: self.robust[2])
     max_reproj_error = property(lambda self: self.robust[3])
+    refine_focal = property(lambda self: self.robust[5])
 
     @property
     def robust_entry(self) -> bool:
@@ -100,21 +108,28 @@ class BundleAdjuster(nn.Module):
 
     @robust_entry.setter
     def robust_entry(self, value):
-        self.robust = self.robust[:4] + (bool(value),)
+        self.robust = self.robust[:4] + (bool(value),) + self.robust[5:]
 
     @torch.no_grad()
-    def adjust(self, feats: dict, tracks, cameras, poses, constant_pose) -> dict:
+    def adjust(self, feats: dict, tracks, cameras, poses, constant_pose, constant_camera=None) -> dict:
         """feats = {keypoints [K, N, 2], num_keypoints [K] (optional)}: the store the tracks were built over; `tracks`: `Triangulator`'s dict or
         (track_id [K, N], xyz [T, 3]); cameras [K, 4] (fx, fy, cx, cy) or [K, 3, 3]; poses [K, 3, 4] (R | t) or (R [K, 3, 3], t [K, 3]); constant_pose: a [K]
         bool mask or the indices of the images whose pose is held fixed (at least one: ValueError otherwise; two fix scale).  Returns poses [K, 3, 4], xyz
         [T, 3], points3d [K, N, 3] (NaN where a row is no active observation), node_state [K, N] uint8 (`STATES`), observation_error [K, N] (pixels, NaN where
         not active), initial_cost, final_cost, num_iterations (run), num_accepted, converged, num_observations, num_filtered, num_filter_stages (both 0 without
-        a filter), status [K].  ONE host synchronisation.  An
+        a filter), status [K].  With refine_focal: constant_camera (None: no camera is held; else a [K] bool mask or image indices, parsed like
+        constant_pose) names the images whose focal length is held, independently of the poses, and the dict also holds cameras [K, 4] float32 (fx, fy
+        refined where the camera was free; cx, cy and every camera that never moved are the input's bits: what `Triangulator`, `AbsolutePoseEstimator` and
+        `RelativePoseEstimator` take as cameras) and num_free_cameras.  Without refine_focal constant_camera must be None.  ONE host synchronisation.  An
         image whose camera or pose fails the camera rule raises LightGlueAmdError after the call, with `err.outputs` holding the outputs of everything else."""
         device = feats["keypoints"].device
         s = _call.build_side(feats, device, "feats")
         K, N = int(s.K), int(s.N)
         const = as_constant(constant_pose, K)
+        loss, loss_scale, filter_rounds, max_reproj_error, robust, focal = self.robust
+        if constant_camera is not None and not focal:
+            raise ValueError("constant_camera needs refine_focal=True: without it every camera is held")
+        const_cam = as_constant(constant_camera, K, "constant_camera") if constant_camera is not None else None
         tid, xyz = as_tracks(tracks, K, N, device)
         cam, pose = as_cameras(cameras, K, device, "cameras"), as_poses(poses, K, device)
         _call.require_gpu(device, "keypoints")          # behind every shape check: those need no device
@@ -125,12 +140,11 @@ class BundleAdjuster(nn.Module):
         pts = torch.empty((K, N, 3), device=device, dtype=torch.float32)
         state = torch.empty((K, N), device=device, dtype=torch.uint8)
         err = torch.empty((K, N), device=device, dtype=torch.float32)
-        loss, loss_scale, filter_rounds, max_reproj_error, robust = self.robust
         small = torch.zeros((24 + K,), device=device, dtype=torch.int32)          # summary [12] fp64 (lg_bundle_adjust writes 8) | status [K]
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
             lib = _cabi.load()
-            size = lib.lg_bundle_robust_workspace_bytes if robust else lib.lg_bundle_workspace_bytes
+            size = lib.lg_bundle_focal_workspace_bytes if focal else lib.lg_bundle_robust_workspace_bytes if robust else lib.lg_bundle_workspace_bytes
             nbytes = size(K, N, T, 0)                                             # -1: outside the envelope — the call below says why
             ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
             p = _call._ptr
@@ -139,7 +153,13 @@ class BundleAdjuster(nn.Module):
                 function_tolerance=self.function_tolerance, kpts=p(s.kpts), num=p(s.num), track_id=p(tid), xyz=p(xyz), cameras=p(cam), poses=p(pose),
                 constant_pose=p(const), workspace=p(ws), workspace_bytes=max(nbytes, 0), poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
                 node_state=p(state), observation_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 96)
-            if robust:
+            if focal:
+                cameras_out = torch.empty((K, 4), device=device, dtype=torch.float32)
+                held = const_cam.to(device=device, dtype=torch.uint8) if const_cam is not None else None
+                rio = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
+                fio = _cabi.LgBundleFocalIO(base=rio, constant_camera=p(held) if held is not None else None, cameras_out=p(cameras_out))
+                _cabi.check(lib.lg_bundle_adjust_focal(C.byref(fio), C.c_void_p(stream.cuda_stream)))
+            elif robust:
                 rio = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
                 _cabi.check(lib.lg_bundle_adjust_robust(C.byref(rio), C.c_void_p(stream.cuda_stream)))
             else:
@@ -150,6 +170,8 @@ class BundleAdjuster(nn.Module):
                "initial_cost": float(summary[0]), "final_cost": float(summary[1]), "num_iterations": int(summary[2]), "num_accepted": int(summary[3]),
                "converged": bool(summary[4]), "num_observations": int(summary[5]), "num_filtered": int(summary[8]), "num_filter_stages": int(summary[9]),
                "status": small[24:]}
+        if focal:
+            out["cameras"], out["num_free_cameras"] = cameras_out, int(summary[10])
         bad = [k for k, c in enumerate(status.tolist()) if c != _cabi.LG_OK]
         if bad:          # every other image is complete: the error carries the call's outputs
             error = _cabi.LightGlueAmdError("; ".join(f"image {k}: a camera whose focal length is not finite and > 0, whose principal point is not finite, or a "

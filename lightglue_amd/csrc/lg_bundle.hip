@@ -11,13 +11,21 @@
 // lg_bundle_adjust_robust runs the same list per stage with the loss compiled in (ba_linearise<LOSS> is the one weighted linearisation: points, reduce, trial
 // points; ba_rho<LOSS> in the cost; the squared instantiation is lg_bundle_adjust's code) and between two stages ba_filter, ba_count<true>, ba_scan, ba_fill,
 // ba_sort, ba_cost and ba_restage.  Registers and scratch of every instantiation: profiles/bundle_adjust_robust.md.
+// lg_bundle_adjust_focal runs that list with FOCAL compiled in: seven unknowns per image (column 6: the log of a common scale of fx and fy), interleaved per
+// image in S; the camera state lives twice like the poses (ba_cam<FOCAL> names the buffer; without FOCAL it is the image's record, which never moves);
+// ba_jacobians / ba_linearise fill a seventh column when they are given arrays of 7; the reduce runs 4 column blocks of 49 entries and 28 + 7 + 7 extras and
+// overwrites held columns (identity, zero coupling, zero right-hand side); its back substitution is ba_backsolve_focal_kernel in lg_bundle_focal.hip.  The
+// FOCAL kernels take BaFocalArgs, so the other two entry points' kernels keep their argument block and their instruction streams
+// (profiles/bundle_adjust_focal.md, which also lists registers and scratch of the new instantiations).
 // No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
 // other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
 // No floating-point atomics: every sum runs in the fixed order the header names.  Small matrices are indexed statically (no scratch: profiles/bundle_adjust.md).
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 
+#include "lg_bundle_args.h"
 #include "lg_cholesky.h"
 #include "lg_host_call.h"
 #include "lg_kernels.h"
@@ -28,44 +36,20 @@
 
 namespace lg {
 
-constexpr int BA_THREADS = 256, BA_SCAN_THREADS = 1024, BA_SCAN_WAVES = BA_SCAN_THREADS / 64;
-constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK;                  // Cholesky (lg_cholesky.h): columns per panel = rows per tile
-static_assert(BA_NB == CH_NB && BA_THREADS == CH_THREADS, "lg_cholesky.h is written for 48-column panels and 256 threads");
-constexpr int BA_TILE = 32, BA_BCHUNK = 6;                   // reduce: rows of image a per LDS tile, column blocks b per workgroup (6 x 36 = 216 threads)
-
-struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, removed, filtered, fstages, pad; };   // removed: by the running filter
-static_assert(sizeof(BaHead) <= 256, "the record of the call is 256 bytes");
-struct BaImage { double cam[4]; int ok, constant, nact, moved; double pad2[2]; };           // moved: free in an earlier stage (lg_bundle_adjust_robust)
-static_assert(sizeof(BaImage) == 64, "lg_bundle_workspace_bytes counts 64 bytes");
-
-struct BaArgs {
-    int n, images, nodes, tracks, dim;
-    double lambda0, ftol;
-    const float* kpts; const int* num; const long long* track_id; const float* xyz; const float* cameras; const float* poses; const unsigned char* constant;
-    BaHead* head; BaImage* rec; double* pose; double* delta; double* icost; double* S;         // pose [2][images][12], S [dim + 1][dim]
-    int* list; int* limg; int* tcnt; int* toff; int* tcur; double* X; double* Vinv; double* y;  // X [2][tracks][3]
-    float* poses_out; float* xyz_out; float* points3d; unsigned char* node_state; float* obs_err; double* summary; int* status;
-    // lg_bundle_adjust_robust, behind everything lg_bundle_adjust's kernels read (their argument offsets stay what they were): the loss scale c, c c, the
-    // filter's bar e e, and per track "it moved in an earlier stage" (null without a filter)
-    double lc, lc2, fe2; int* tmov;
-};
-
-__device__ __forceinline__ bool ba_adjusted(const BaArgs& a, int j) { const int c = a.tcnt[j]; return c >= 2 && c <= LG_BA_MAX_TRACK_LENGTH; }
-__device__ __forceinline__ bool ba_free(const BaArgs& a, int k) { const BaImage& im = a.rec[k]; return im.ok && !im.constant && im.nact > 0; }
-__device__ __forceinline__ const double* ba_pose(const BaArgs& a, int which, int k) { return a.pose + ((long long)which * a.images + k) * 12; }
-__device__ __forceinline__ const double* ba_point(const BaArgs& a, int which, int j) { return a.X + ((long long)which * a.tracks + j) * 3; }
-
 // p = R X + t of pose P [12] (R | t row-major 3 x 4)
 __device__ __forceinline__ void ba_project(const double* P, const double* X, double (&p)[3]) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) p[r] = ((P[4 * r] * X[0] + P[4 * r + 1] * X[1]) + P[4 * r + 2] * X[2]) + P[4 * r + 3];
 }
-// the two rows of the pose Jacobian A (2 x 6) and of the point Jacobian B (2 x 3) at p
-__device__ __forceinline__ void ba_jacobians(const double* P, const double* cam, const double (&p)[3], double (&A0)[6], double (&A1)[6], double (&B0)[3], double (&B1)[3]) {
+// the two rows of the pose Jacobian A (2 x 6) and of the point Jacobian B (2 x 3) at p; NA = 7 (lg_bundle_adjust_focal): column 6 is the log focal scale's
+template <int NA>
+__device__ __forceinline__ void ba_jacobians(const double* P, const double* cam, const double (&p)[3], double (&A0)[NA], double (&A1)[NA], double (&B0)[3], double (&B1)[3]) {
+    static_assert(NA == 6 || NA == 7, "six pose columns, or those and the focal column");
     const double iz = 1.0 / p[2], fx = cam[0], fy = cam[1];
     const double ax = fx * iz, az = -(((fx * p[0]) * iz) * iz), by = fy * iz, bz = -(((fy * p[1]) * iz) * iz);
     A0[0] = az * p[1]; A0[1] = ax * p[2] - az * p[0]; A0[2] = -(ax * p[1]); A0[3] = ax; A0[4] = 0.0; A0[5] = az;
     A1[0] = bz * p[1] - by * p[2]; A1[1] = -(bz * p[0]); A1[2] = by * p[0]; A1[3] = 0.0; A1[4] = by; A1[5] = bz;
+    if constexpr (NA == 7) { A0[6] = ax * p[0]; A1[6] = by * p[1]; }
 #pragma unroll
     for (int e = 0; e < 3; ++e) { B0[e] = ax * P[e] + az * P[8 + e]; B1[e] = by * P[4 + e] + bz * P[8 + e]; }
 }
@@ -87,15 +71,15 @@ template <int LOSS> __device__ __forceinline__ double ba_weight(const BaArgs& a,
     else return 1.0;
 }
 // THE weighted linearisation of one observation at p: A, B and r, each multiplied by sqrt(w) once; with the squared loss no multiplication is made
-template <int LOSS>
-__device__ __forceinline__ void ba_linearise(const BaArgs& a, const double* P, const double* cam, const double (&p)[3], const float* kp, double (&A0)[6], double (&A1)[6],
+template <int LOSS, int NA>
+__device__ __forceinline__ void ba_linearise(const BaArgs& a, const double* P, const double* cam, const double (&p)[3], const float* kp, double (&A0)[NA], double (&A1)[NA],
                                              double (&B0)[3], double (&B1)[3], double& rx, double& ry) {
     ba_jacobians(P, cam, p, A0, A1, B0, B1);
     ba_residual(cam, p, kp, rx, ry);
     if constexpr (LOSS != LG_BA_LOSS_SQUARED) {
         const double sw = sqrt(ba_weight<LOSS>(a, rx * rx + ry * ry));
 #pragma unroll
-        for (int e = 0; e < 6; ++e) { A0[e] = sw * A0[e]; A1[e] = sw * A1[e]; }
+        for (int e = 0; e < NA; ++e) { A0[e] = sw * A0[e]; A1[e] = sw * A1[e]; }
 #pragma unroll
         for (int e = 0; e < 3; ++e) { B0[e] = sw * B0[e]; B1[e] = sw * B1[e]; }
         rx = sw * rx; ry = sw * ry;
@@ -103,7 +87,8 @@ __device__ __forceinline__ void ba_linearise(const BaArgs& a, const double* P, c
 }
 
 // ------------------------------------------------------------------ records
-__global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
+template <bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgsOf<FOCAL> a) {
+    constexpr int D = BA_COLS<FOCAL>;
     const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
     if (g == 0) { BaHead h{}; h.lambda = a.lambda0; *a.head = h; }
     if (g < a.images) {
@@ -117,6 +102,11 @@ __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
         im.ok = ok ? 1 : 0; im.constant = a.constant[k] ? 1 : 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) im.cam[e] = (double)c[e];
+        if constexpr (FOCAL) {
+            im.cconstant = (a.cconstant && a.cconstant[k]) ? 1 : 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a.cam[(long long)k * 4 + e] = (double)c[e]; a.cam[((long long)a.images + k) * 4 + e] = (double)c[e]; }
+        }
         a.rec[k] = im;
 #pragma unroll
         for (int e = 0; e < 12; ++e) {
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
             a.pose[(long long)k * 12 + e] = v; a.pose[((long long)a.images + k) * 12 + e] = v;
         }
 #pragma unroll
-        for (int e = 0; e < 6; ++e) a.delta[(long long)k * 6 + e] = 0.0;
+        for (int e = 0; e < D; ++e) a.delta[(long long)k * D + e] = 0.0;
         a.icost[k] = 0.0;
         a.status[k] = ok ? LG_OK : LG_ERR_CAMERA;
     }
@@ -212,14 +202,14 @@ __global__ __launch_bounds__(BA_THREADS) void ba_sort_kernel(BaArgs a) {
 // launch, one lane per track and image: what moved so far is remembered (a track or image that stops moving returns its last accepted state), the trial point
 // takes the accepted one (nothing writes a track's trial once it is not adjusted, and a later accepted step flips sel), and the counters the rebuild fills are
 // cleared.  The node lanes read neither tcnt nor nact, so the order of the lanes does not matter
-__global__ __launch_bounds__(BA_THREADS) void ba_filter_kernel(BaArgs a, int first) {
+template <bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_filter_kernel(BaArgsOf<FOCAL> a, int first) {
     const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
     const int s = a.head->sel;
     if (g < a.nodes && a.node_state[g] == 1) {
         const int k = (int)(g / a.n);
         double p[3], rx, ry;
         ba_project(ba_pose(a, s, k), ba_point(a, s, (int)a.track_id[g]), p);
-        ba_residual(a.rec[k].cam, p, a.kpts + g * 2, rx, ry);
+        ba_residual(ba_cam<FOCAL>(a, s, k), p, a.kpts + g * 2, rx, ry);
         if (rx * rx + ry * ry > a.fe2) { a.node_state[g] = 7; atomicAdd(&a.head->removed, 1); }
     }
     if (g < a.tracks) {
@@ -230,6 +220,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_filter_kernel(BaArgs a, int fir
     }
     if (g < a.images) {
         if (ba_free(a, (int)g)) a.rec[g].moved = 1;
+        if constexpr (FOCAL) if (ba_cam_free(a, (int)g)) a.rec[g].cmoved = 1;
         a.rec[g].nact = 0;
     }
 }
@@ -250,12 +241,12 @@ __global__ void ba_restage_kernel(BaArgs a) {
 
 // ------------------------------------------------------------------ the cost of a state: one workgroup per image, rows in ascending order
 // trial = 0: the accepted state (the input); 1: the trial.  A row with pz <= 0 or a non-finite term fails the trial
-template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgs a, int trial) {
+template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_cost_kernel(BaArgsOf<FOCAL> a, int trial) {
     __shared__ double term[BA_THREADS];
     if (trial && a.head->converged) return;
     const int k = blockIdx.x, which = a.head->sel ^ trial;
     const double* P = ba_pose(a, which, k);
-    const double* cam = a.rec[k].cam;
+    const double* cam = ba_cam<FOCAL>(a, which, k);
     double sum = 0.0;
     int bad = 0;
     for (int i0 = 0; i0 < a.n; i0 += BA_THREADS) {
@@ -309,7 +300,7 @@ __global__ void ba_decide_kernel(BaArgs a, int initial) {
 }
 
 // ------------------------------------------------------------------ per iteration 1: one lane per track: V, g, the damped inverse, y
-template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgs a) {
+template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgsOf<FOCAL> a) {
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
     if (j >= a.tracks || !ba_adjusted(a, j)) return;
@@ -321,7 +312,7 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_points_kern
     for (int q = 0; q < len; ++q) {
         const int v = a.list[off + q], k = a.limg[off + q];
         const double* P = ba_pose(a, s, k);
-        const double* cam = a.rec[k].cam;
+        const double* cam = ba_cam<FOCAL>(a, s, k);
         double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
         ba_project(P, X, p);
         ba_linearise<LOSS>(a, P, cam, p, a.kpts + (long long)v * 2, A0, A1, B0, B1, rx, ry);
@@ -358,42 +349,44 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_points_kern
 // order); one thread per (row, column block) with an entry forms W_b once; then every entry thread adds its rows in ascending order.
 // With a robust loss W_b carries the weight of ITS observation: the counting also finds the track's first entry in image b (an integer minimum), whose W goes
 // to LDS; where a track has more than one observation in image b (rare) the entry threads form every W themselves, in the list's order
-template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgs a) {
+template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kernel(BaArgsOf<FOCAL> a) {
     constexpr bool ROBUST = LOSS != LG_BA_LOSS_SQUARED;
-    __shared__ double sY[BA_TILE][18], sA[BA_TILE][12], sWy[BA_TILE][6], sX[BA_TILE][3], sR[BA_TILE][2], sW[BA_TILE][BA_BCHUNK][18], sU[33];
-    __shared__ int sOff[BA_TILE], sLen[BA_TILE], sCnt[BA_TILE][BA_BCHUNK], sFirst[ROBUST ? BA_TILE : 1][BA_BCHUNK];
+    constexpr int D = BA_COLS<FOCAL>, DD = D * D, BCH = BA_CHUNK<FOCAL>, NU = D * (D + 1) / 2, NX = NU + 2 * D;     // columns per image, entries per block, column blocks, U's triangle, extras
+    static_assert(DD * BCH + NX <= BA_THREADS, "entry threads and extras");
+    __shared__ double sY[BA_TILE][3 * D], sA[BA_TILE][2 * D], sWy[BA_TILE][D], sX[BA_TILE][3], sR[BA_TILE][2], sW[BA_TILE][BCH][3 * D], sU[NX];
+    __shared__ int sOff[BA_TILE], sLen[BA_TILE], sCnt[BA_TILE][BCH], sFirst[ROBUST ? BA_TILE : 1][BCH];
     if (a.head->converged) return;
-    const int ia = blockIdx.x, b0 = blockIdx.y * BA_BCHUNK, t = threadIdx.x, dim = a.dim;
+    const int ia = blockIdx.x, b0 = blockIdx.y * BCH, t = threadIdx.x, dim = a.dim;
     if (b0 > ia) return;
-    const bool diag = ia / BA_BCHUNK == (int)blockIdx.y, free_a = ba_free(a, ia);
-    const int bl = t / 36, rc = t - bl * 36, r = rc / 6, c = rc - r * 6, ib = b0 + bl;
-    const bool entry = t < 36 * BA_BCHUNK && ib <= ia;      // ib <= ia < images
-    const int e = t - 36 * BA_BCHUNK;                       // 0 .. 32 in the diagonal workgroup: U (21), g (6), W y (6)
-    const bool extra = diag && e >= 0 && e < 33;
-    double* out = a.S + ((long long)(6 * ia + r) * dim + 6 * ib + c);
+    const bool diag = ia / BCH == (int)blockIdx.y, free_a = ba_any_free<FOCAL>(a, ia);
+    const int bl = t / DD, rc = t - bl * DD, r = rc / D, c = rc - r * D, ib = b0 + bl;
+    const bool entry = t < DD * BCH && ib <= ia;      // ib <= ia < images
+    const int e = t - DD * BCH;                             // 0 .. NX - 1 in the diagonal workgroup: U (21 | 28), g (D), W y (D)
+    const bool extra = diag && e >= 0 && e < NX;
+    double* out = a.S + ((long long)(D * ia + r) * dim + D * ib + c);
     if (!free_a) {                                          // the image's columns drop out: identity, zero coupling, zero right-hand side
         if (entry) *out = (ib == ia && r == c) ? 1.0 : 0.0;
-        if (extra && e >= 27) a.S[(long long)dim * dim + 6 * ia + (e - 27)] = 0.0;
+        if (extra && e >= NU + D) a.S[(long long)dim * dim + D * ia + (e - (NU + D))] = 0.0;
         return;
     }
     const int s = a.head->sel;
     const double lambda = a.head->lambda;
-    const bool free_b = entry && ba_free(a, ib);
+    const bool free_b = entry && ba_any_free<FOCAL>(a, ib);
     // the thread's (row, column block) item of a tile, and the pose of that block's image
-    const int iq = t / BA_BCHUNK, ibl = t - iq * BA_BCHUNK, item_b = b0 + ibl;
-    const bool item = t < BA_TILE * BA_BCHUNK, item_free = item && item_b <= ia && ba_free(a, item_b);
+    const int iq = t / BCH, ibl = t - iq * BCH, item_b = b0 + ibl;
+    const bool item = t < BA_TILE * BCH, item_free = item && item_b <= ia && ba_any_free<FOCAL>(a, item_b);
     double Pb[12], fb[ROBUST ? 4 : 2] = {0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 12; ++q) Pb[q] = item_free ? ba_pose(a, s, item_b)[q] : 0.0;
-    if (item_free) { fb[0] = a.rec[item_b].cam[0]; fb[1] = a.rec[item_b].cam[1]; }
-    if constexpr (ROBUST) if (item_free) { fb[2] = a.rec[item_b].cam[2]; fb[3] = a.rec[item_b].cam[3]; }
+    if (item_free) { fb[0] = ba_cam<FOCAL>(a, s, item_b)[0]; fb[1] = ba_cam<FOCAL>(a, s, item_b)[1]; }
+    if constexpr (ROBUST) if (item_free) { fb[2] = ba_cam<FOCAL>(a, s, item_b)[2]; fb[3] = ba_cam<FOCAL>(a, s, item_b)[3]; }
     const int cq = t >> 3, part = t & 7;                    // counting: 8 threads per row of the tile
-    static_assert(BA_THREADS == 8 * BA_TILE && BA_TILE * BA_BCHUNK <= BA_THREADS, "8 counting threads and BA_BCHUNK items per tile row");
+    static_assert(BA_THREADS == 8 * BA_TILE && BA_TILE * BCH <= BA_THREADS, "8 counting threads and BCH items per tile row");
     // U's upper triangle in row-major order: entry e -> (ur, uc)
     int ur = 0, uc = 0;
-    if (extra && e < 21) { int left = e; while (left >= 6 - ur) { left -= 6 - ur; ++ur; } uc = ur + left; }
+    if (extra && e < NU) { int left = e; while (left >= D - ur) { left -= D - ur; ++ur; } uc = ur + left; }
     const double* Pa = ba_pose(a, s, ia);
-    const double* cama = a.rec[ia].cam;
+    const double* cama = ba_cam<FOCAL>(a, s, ia);
     double acc = 0.0;
     for (int i0 = 0; i0 < a.n; i0 += BA_TILE) {
         __syncthreads();                                    // the previous tile has been read
@@ -407,7 +400,7 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
                 const double* Xp = ba_point(a, s, j);
                 const double* Vi = a.Vinv + (long long)j * 9;
                 const double* y = a.y + (long long)j * 3;
-                double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+                double p[3], A0[D], A1[D], B0[3], B1[3], rx, ry;
                 ba_project(Pa, Xp, p);
                 // squared: ba_linearise<0>'s two calls written out; through the wrapper the compiler allocates this kernel's registers differently from
                 // lg_bundle_adjust's build before the robust mode (measured: 0.9 % on a call, profiles/bundle_adjust_robust.md): like this the instruction stream is that one
@@ -416,8 +409,8 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
                 sX[t][0] = Xp[0]; sX[t][1] = Xp[1]; sX[t][2] = Xp[2];
                 sR[t][0] = rx; sR[t][1] = ry;
 #pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    sA[t][q] = A0[q]; sA[t][6 + q] = A1[q];
+                for (int q = 0; q < D; ++q) {
+                    sA[t][q] = A0[q]; sA[t][D + q] = A1[q];
                     const double w0 = A0[q] * B0[0] + A1[q] * B1[0], w1 = A0[q] * B0[1] + A1[q] * B1[1], w2 = A0[q] * B0[2] + A1[q] * B1[2];
 #pragma unroll
                     for (int m = 0; m < 3; ++m) sY[t][3 * q + m] = (w0 * Vi[m] + w1 * Vi[3 + m]) + w2 * Vi[6 + m];
@@ -433,7 +426,7 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
             const int len = sLen[cq], off = sOff[cq];
             for (int l = part; l < len; l += 8) {
                 const int d = a.limg[off + l] - b0;
-                if (d >= 0 && d < BA_BCHUNK && b0 + d <= ia) {
+                if (d >= 0 && d < BCH && b0 + d <= ia) {
                     atomicAdd(&sCnt[cq][d], 1);
                     if constexpr (ROBUST) atomicMin(&sFirst[cq][d], l);
                 }
@@ -441,14 +434,14 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
         }
         __syncthreads();
         if (item_free && sCnt[iq][ibl] > 0) {               // W of (image item_b, the row's track): it does not depend on the observation's row in b
-            double p[3], A0[6], A1[6], B0[3], B1[3];
+            double p[3], A0[D], A1[D], B0[3], B1[3];
             ba_project(Pb, sX[iq], p);
             if constexpr (ROBUST) {                             // the weight of the track's first observation in image item_b (sCnt > 0: sFirst < sLen)
                 double rx, ry;
                 ba_linearise<LOSS>(a, Pb, fb, p, a.kpts + (long long)a.list[sOff[iq] + sFirst[iq][ibl]] * 2, A0, A1, B0, B1, rx, ry);
             } else ba_jacobians(Pb, fb, p, A0, A1, B0, B1);
 #pragma unroll
-            for (int q = 0; q < 6; ++q)
+            for (int q = 0; q < D; ++q)
 #pragma unroll
                 for (int m = 0; m < 3; ++m) sW[iq][ibl][3 * q + m] = A0[q] * B0[m] + A1[q] * B1[m];
         }
@@ -460,14 +453,14 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
                 if (!times) continue;
                 if constexpr (ROBUST) if (times > 1) {          // every observation of the row's track in image ib has a weight of its own
                     const double* Pi = ba_pose(a, s, ib);
-                    const double* cami = a.rec[ib].cam;
+                    const double* cami = ba_cam<FOCAL>(a, s, ib);
                     for (int l = 0; l < sLen[q]; ++l) {
                         if (a.limg[sOff[q] + l] != ib) continue;
-                        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry, a0 = 0.0, a1 = 0.0;
+                        double p[3], A0[D], A1[D], B0[3], B1[3], rx, ry, a0 = 0.0, a1 = 0.0;
                         ba_project(Pi, sX[q], p);
                         ba_linearise<LOSS>(a, Pi, cami, p, a.kpts + (long long)a.list[sOff[q] + l] * 2, A0, A1, B0, B1, rx, ry);
 #pragma unroll
-                        for (int cc = 0; cc < 6; ++cc) if (cc == c) { a0 = A0[cc]; a1 = A1[cc]; }
+                        for (int cc = 0; cc < D; ++cc) if (cc == c) { a0 = A0[cc]; a1 = A1[cc]; }
                         acc += (sY[q][3 * r] * (a0 * B0[0] + a1 * B1[0]) + sY[q][3 * r + 1] * (a0 * B0[1] + a1 * B1[1])) + sY[q][3 * r + 2] * (a0 * B0[2] + a1 * B1[2]);
                     }
                     continue;
@@ -478,9 +471,9 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
         } else if (extra) {
             for (int q = 0; q < rows; ++q) {
                 if (!sLen[q]) continue;
-                if (e < 21) acc += sA[q][ur] * sA[q][uc] + sA[q][6 + ur] * sA[q][6 + uc];
-                else if (e < 27) acc += sA[q][e - 21] * sR[q][0] + sA[q][6 + e - 21] * sR[q][1];
-                else acc += sWy[q][e - 27];
+                if (e < NU) acc += sA[q][ur] * sA[q][uc] + sA[q][D + ur] * sA[q][D + uc];
+                else if (e < NU + D) acc += sA[q][e - NU] * sR[q][0] + sA[q][D + e - NU] * sR[q][1];
+                else acc += sWy[q][e - (NU + D)];
             }
         }
     }
@@ -490,13 +483,19 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_reduce_kern
         double val = free_b ? -acc : 0.0;
         if (ib == ia) {                                     // the diagonal block: U' - E (this workgroup is the diagonal one, sU is its own)
             const int lo = min(r, c), hi = max(r, c);
-            double u = sU[lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
+            double u = sU[lo * D - lo * (lo - 1) / 2 + (hi - lo)];
             if (r == c) u = ba_damped(u, lambda);
             val = u - acc;
         }
+        if constexpr (FOCAL)                                // a held column of either image: identity, zero coupling
+            if (!((r < 6 ? ba_free(a, ia) : ba_cam_free(a, ia)) && (c < 6 ? ba_free(a, ib) : ba_cam_free(a, ib)))) val = (ib == ia && r == c) ? 1.0 : 0.0;
         *out = val;
     }
-    if (extra && e >= 27) a.S[(long long)dim * dim + 6 * ia + (e - 27)] = acc - sU[e - 6];      // (sum of W y) - g
+    if (extra && e >= NU + D) {                             // (sum of W y) - g
+        double rhs = acc - sU[e - D];
+        if constexpr (FOCAL) if (!(e - (NU + D) < 6 ? ba_free(a, ia) : ba_cam_free(a, ia))) rhs = 0.0;
+        a.S[(long long)dim * dim + D * ia + (e - (NU + D))] = rhs;
+    }
 }
 
 // ------------------------------------------------------------------ per iteration 3: panel p of the left-looking blocked Cholesky, the right-hand side as row dim
@@ -565,7 +564,8 @@ __global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
 }
 
 // ------------------------------------------------------------------ per iteration 5: one lane per track: the point's step and its trial
-template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgs a) {
+template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_trial_points_kernel(BaArgsOf<FOCAL> a) {
+    constexpr int D = BA_COLS<FOCAL>;              // a held column's step is 0 (ba_backsolve)
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
     if (j >= a.tracks || !ba_adjusted(a, j)) return;
@@ -575,17 +575,17 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_trial_point
     double acc[3] = {0.0, 0.0, 0.0};
     for (int q = 0; q < len; ++q) {
         const int k = a.limg[off + q];
-        if (!ba_free(a, k)) continue;
+        if (!ba_any_free<FOCAL>(a, k)) continue;
         const double* P = ba_pose(a, s, k);
-        const double* d = a.delta + (long long)k * 6;
-        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;       // the squared loss reads neither the residual nor the keypoint
+        const double* d = a.delta + (long long)k * D;
+        double p[3], A0[D], A1[D], B0[3], B1[3], rx, ry;       // the squared loss reads neither the residual nor the keypoint
         ba_project(P, X, p);
-        ba_linearise<LOSS>(a, P, a.rec[k].cam, p, a.kpts + (long long)a.list[off + q] * 2, A0, A1, B0, B1, rx, ry);
+        ba_linearise<LOSS>(a, P, ba_cam<FOCAL>(a, s, k), p, a.kpts + (long long)a.list[off + q] * 2, A0, A1, B0, B1, rx, ry);
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             double w = 0.0;
 #pragma unroll
-            for (int r = 0; r < 6; ++r) w += (A0[r] * B0[m] + A1[r] * B1[m]) * d[r];
+            for (int r = 0; r < D; ++r) w += (A0[r] * B0[m] + A1[r] * B1[m]) * d[r];
             acc[m] += w;
         }
     }
@@ -604,7 +604,8 @@ template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_trial_point
 
 // ------------------------------------------------------------------ the outputs
 // ROBUST (lg_bundle_adjust_robust): summary [12], and a track or image that moved in an earlier stage returns its last accepted state
-template <bool ROBUST> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgs a) {
+// FOCAL (lg_bundle_adjust_focal): cameras_out, and summary [10] = the cameras that were free in any stage
+template <bool ROBUST, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_kernel(BaArgsOf<FOCAL> a) {
     const long long g = (long long)blockIdx.x * BA_THREADS + threadIdx.x;
     const BaHead h = *a.head;
     const int s = h.sel;
@@ -612,6 +613,11 @@ template <bool ROBUST> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_
         a.summary[0] = h.initial_cost; a.summary[1] = h.cost; a.summary[2] = (double)h.iters; a.summary[3] = (double)h.accepted;
         a.summary[4] = (double)h.converged; a.summary[5] = (double)h.nobs; a.summary[6] = h.lambda; a.summary[7] = 0.0;
         if constexpr (ROBUST) { a.summary[8] = (double)h.filtered; a.summary[9] = (double)h.fstages; a.summary[10] = 0.0; a.summary[11] = 0.0; }
+        if constexpr (FOCAL) {
+            int moved = 0;
+            for (int k = 0; k < a.images; ++k) moved += (ba_cam_free(a, k) || a.rec[k].cmoved) ? 1 : 0;
+            a.summary[10] = (double)moved;
+        }
     }
     if (g < a.nodes) {
         const int k = (int)(g / a.n);
@@ -620,7 +626,7 @@ template <bool ROBUST> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_
             const double* X = ba_point(a, s, (int)a.track_id[g]);
             double p[3], rx, ry;
             ba_project(ba_pose(a, s, k), X, p);
-            ba_residual(a.rec[k].cam, p, a.kpts + g * 2, rx, ry);
+            ba_residual(ba_cam<FOCAL>(a, s, k), p, a.kpts + g * 2, rx, ry);
             x = (float)X[0]; y = (float)X[1]; z = (float)X[2]; err = (float)sqrt(rx * rx + ry * ry);
         }
         float* o = a.points3d + g * 3;
@@ -640,47 +646,55 @@ template <bool ROBUST> __global__ __launch_bounds__(BA_THREADS) void ba_scatter_
         const double* P = ba_pose(a, s, (int)g);
 #pragma unroll
         for (int e = 0; e < 12; ++e) a.poses_out[g * 12 + e] = fr ? (float)P[e] : a.poses[g * 12 + e];
+        if constexpr (FOCAL) {                              // fx, fy of a camera that moved; cx, cy and every other row are the input's bits
+            const bool cf = ba_cam_free(a, (int)g) || a.rec[g].cmoved;
+            const double* c = ba_cam<true>(a, s, (int)g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a.cameras_out[g * 4 + e] = (cf && e < 2) ? (float)c[e] : a.cameras[g * 4 + e];
+        }
     }
 }
 
 // ------------------------------------------------------------------ the launch list of both entry points: `rounds` filters, rounds + 1 stages of `iterations`
-template <int LOSS, bool ROBUST> static int ba_enqueue(const BaArgs& a, const BaLayout& L, int iterations, int rounds, hipStream_t s) {
+template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const BaArgsOf<FOCAL>& a, const BaLayout& L, int iterations, int rounds, hipStream_t s) {
     auto blocks = [](long long items) { return dim3((unsigned)((items + BA_THREADS - 1) / BA_THREADS)); };
     const dim3 th(BA_THREADS);
+    const BaArgs& b = a;                                        // what the kernels that know no focal column take
     const int K = a.images, T = a.tracks;
     const int panels = ((int)L.dim + BA_NB - 1) / BA_NB, tiles = ((int)L.dim + 1 + BA_NB - 1) / BA_NB;
     const long long all = std::max<long long>(std::max<long long>(L.nodes, T), K);
-    hipLaunchKernelGGL(ba_init_kernel, blocks(std::max<long long>(K, T)), th, 0, s, a);
-    if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<false>, blocks(L.nodes), th, 0, s, a);
-    if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
-    if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
-    if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
-    hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 0);
-    hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 1);
+    hipLaunchKernelGGL(ba_init_kernel<FOCAL>, blocks(std::max<long long>(K, T)), th, 0, s, a);
+    if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<false>, blocks(L.nodes), th, 0, s, b);
+    if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, b);
+    if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, b);
+    if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, b);
+    hipLaunchKernelGGL((ba_cost_kernel<LOSS, FOCAL>), dim3(K), th, 0, s, a, 0);
+    hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, b, 1);
     for (int stage = 0; stage <= rounds; ++stage) {
         if (stage) {                                            // the filter and the rebuild of the lists from the nodes still in state 1
-            hipLaunchKernelGGL(ba_filter_kernel, blocks(all), th, 0, s, a, stage == 1 ? 1 : 0);
-            if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<true>, blocks(L.nodes), th, 0, s, a);
-            if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, a);
-            if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, a);
-            if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, a);
-            hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 0);
-            hipLaunchKernelGGL(ba_restage_kernel, dim3(1), dim3(64), 0, s, a);
+            hipLaunchKernelGGL(ba_filter_kernel<FOCAL>, blocks(all), th, 0, s, a, stage == 1 ? 1 : 0);
+            if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<true>, blocks(L.nodes), th, 0, s, b);
+            if (T) hipLaunchKernelGGL(ba_scan_kernel, dim3(1), dim3(BA_SCAN_THREADS), 0, s, b);
+            if (L.nodes) hipLaunchKernelGGL(ba_fill_kernel, blocks(L.nodes), th, 0, s, b);
+            if (T) hipLaunchKernelGGL(ba_sort_kernel, blocks(T), th, 0, s, b);
+            hipLaunchKernelGGL((ba_cost_kernel<LOSS, FOCAL>), dim3(K), th, 0, s, a, 0);
+            hipLaunchKernelGGL(ba_restage_kernel, dim3(1), dim3(64), 0, s, b);
         }
         for (int it = 0; it < iterations; ++it) {
-            if (T) hipLaunchKernelGGL(ba_points_kernel<LOSS>, blocks(T), th, 0, s, a);
-            hipLaunchKernelGGL(ba_reduce_kernel<LOSS>, dim3(K, (K + BA_BCHUNK - 1) / BA_BCHUNK), th, 0, s, a);
+            if (T) hipLaunchKernelGGL((ba_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
+            hipLaunchKernelGGL((ba_reduce_kernel<LOSS, FOCAL>), dim3(K, (K + BA_CHUNK<FOCAL> - 1) / BA_CHUNK<FOCAL>), th, 0, s, a);
             for (int p = 0; p < panels; ++p) {
-                hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, a, p);
-                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, a, p);
+                hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, b, p);
+                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, b, p);
             }
-            hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
-            if (T) hipLaunchKernelGGL(ba_trial_points_kernel<LOSS>, blocks(T), th, 0, s, a);
-            hipLaunchKernelGGL(ba_cost_kernel<LOSS>, dim3(K), th, 0, s, a, 1);
-            hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, a, 0);
+            if constexpr (FOCAL) ba_launch_backsolve_focal(a, s);
+            else hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
+            if (T) hipLaunchKernelGGL((ba_trial_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
+            hipLaunchKernelGGL((ba_cost_kernel<LOSS, FOCAL>), dim3(K), th, 0, s, a, 1);
+            hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, b, 0);
         }
     }
-    hipLaunchKernelGGL(ba_scatter_kernel<ROBUST>, blocks(all), th, 0, s, a);
+    hipLaunchKernelGGL((ba_scatter_kernel<ROBUST, FOCAL>), blocks(all), th, 0, s, a);
     HIPCHK(hipGetLastError());
     return LG_OK;
 }
@@ -744,6 +758,30 @@ int lg_bundle_adjust_robust(const lg_bundle_robust_io* io, void* hip_stream) {
         case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
         case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
         default: return ba_enqueue<LG_BA_LOSS_SQUARED, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
+    }
+}
+
+int64_t lg_bundle_focal_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags) {
+    BaFocalLayout L;
+    return ba_focal_layout(images, n, tracks, flags, L) ? -1 : L.total;
+}
+
+int lg_bundle_adjust_focal(const lg_bundle_focal_io* io, void* hip_stream) {
+    static const char* const stage = "lg_bundle_adjust_focal";
+    if (!io) return set_error(LG_ERR_INVALID, std::string(stage) + ": null io");
+    const lg_bundle_robust_io& r = io->base;
+    BaFocalLayout L;
+    if (const char* why = ba_focal_layout(r.base.images, r.base.n, r.base.tracks, r.base.flags, L)) return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why);
+    if (const int rc = ba_focal_check_settings(stage, *io, L)) return rc;
+    char* ws = static_cast<char*>(r.base.workspace);
+    BaFocalArgs a{ba_args(r.base, L.base.base), io->constant_camera, reinterpret_cast<double*>(ws + L.cam), io->cameras_out};
+    a.lc = r.loss_scale; a.lc2 = r.loss_scale * r.loss_scale; a.fe2 = r.max_reproj_error * r.max_reproj_error;
+    a.tmov = r.filter_rounds > 0 ? reinterpret_cast<int*>(ws + L.base.tmov) : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    switch (r.loss) {
+        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
+        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
+        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
     }
 }
 

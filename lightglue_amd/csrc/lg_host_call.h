@@ -177,15 +177,15 @@ inline const char* tri_robust_layout(long long images, long long n, uint32_t fla
 // inverse times its gradient: 156 bytes in all).  W is not stored: it is formed again from the pose and the point where it is needed
 constexpr uint32_t BA_KNOWN_FLAGS = 0u;
 struct BaLayout { long long nodes, dim, head, rec, pose, delta, icost, S, list, limg, tcnt, toff, tcur, X, Vinv, y, total; };
-inline const char* ba_layout(long long images, long long n, long long tracks, uint32_t flags, BaLayout& L) {
+inline const char* ba_layout(long long images, long long n, long long tracks, uint32_t flags, BaLayout& L, long long cols = 6) {   // cols: unknowns per image
     if (flags & ~BA_KNOWN_FLAGS) return "undefined flag bits (the bundle adjuster defines none)";
     if (n < 0 || n > LG_MAX_KEYPOINTS) return "n must lie in [0, LG_MAX_KEYPOINTS]";
     if (images < 1 || images > LG_BA_MAX_IMAGES) return "images must lie in [1, LG_BA_MAX_IMAGES]";
     if (images * n > LG_MAX_ROWS) return "images x n must lie in [0, LG_MAX_ROWS]";
     if (tracks < 0 || tracks > images * n / 2) return "tracks must lie in [0, images x n / 2]";
-    L.nodes = images * n; L.dim = 6 * images;
+    L.nodes = images * n; L.dim = cols * images;
     Bump bp;
-    L.head = bp.take(256); L.rec = bp.take(images * 64); L.pose = bp.take(images * 192); L.delta = bp.take(images * 48); L.icost = bp.take(images * 8);
+    L.head = bp.take(256); L.rec = bp.take(images * 64); L.pose = bp.take(images * 192); L.delta = bp.take(images * cols * 8); L.icost = bp.take(images * 8);
     L.S = bp.take((L.dim + 1) * L.dim * 8);
     L.list = bp.take(L.nodes * 4); L.limg = bp.take(L.nodes * 4);
     L.tcnt = bp.take(tracks * 4); L.toff = bp.take(tracks * 4); L.tcur = bp.take(tracks * 4);
@@ -206,8 +206,8 @@ inline int ba_check_settings(const char* stage, const char* size_function, const
 }
 // lg_bundle_adjust_robust: lg_bundle_adjust's layout, then one int32 per track (it moved in an earlier stage)
 struct BaRobustLayout { BaLayout base; long long tmov, total; };
-inline const char* ba_robust_layout(long long images, long long n, long long tracks, uint32_t flags, BaRobustLayout& L) {
-    if (const char* why = ba_layout(images, n, tracks, flags, L.base)) return why;
+inline const char* ba_robust_layout(long long images, long long n, long long tracks, uint32_t flags, BaRobustLayout& L, long long cols = 6) {
+    if (const char* why = ba_layout(images, n, tracks, flags, L.base, cols)) return why;
     Bump bp;
     bp.used = L.base.total;
     L.tmov = bp.take(tracks * 4); L.total = bp.used;
@@ -220,6 +220,24 @@ inline const char* ba_robust_settings_error(long long loss, double loss_scale, l
     if (filter_rounds < 0 || filter_rounds > LG_BA_MAX_FILTER_ROUNDS) return "filter_rounds must lie in [0, LG_BA_MAX_FILTER_ROUNDS]";
     if (filter_rounds > 0 && !positive(max_reproj_error)) return "max_reproj_error must be > 0 (and finite) with filter_rounds > 0";
     return nullptr;
+}
+// lg_bundle_adjust_focal: lg_bundle_adjust_robust's layout with 7 unknowns per image (the step is 56 bytes, S is (7 images + 1) x 7 images), then the camera
+// state twice in fp64 (64 bytes per image)
+struct BaFocalLayout { BaRobustLayout base; long long cam, total; };
+inline const char* ba_focal_layout(long long images, long long n, long long tracks, uint32_t flags, BaFocalLayout& L) {
+    if (const char* why = ba_robust_layout(images, n, tracks, flags, L.base, 7)) return why;
+    Bump bp;
+    bp.used = L.base.total;
+    L.cam = bp.take(images * 64); L.total = bp.used;
+    return nullptr;
+}
+// what lg_bundle_adjust_focal refuses once the layout stands, in this order: the robust settings, cameras_out, lg_bundle_adjust's list (ba_check_settings)
+inline int ba_focal_check_settings(const char* stage, const lg_bundle_focal_io& io, const BaFocalLayout& L) {
+    const auto refuse = [stage](const char* why) { return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why); };
+    const lg_bundle_robust_io& r = io.base;
+    if (const char* why = ba_robust_settings_error(r.loss, r.loss_scale, r.filter_rounds, r.max_reproj_error)) return refuse(why);
+    if (!io.cameras_out) return refuse("null pointer cameras_out");
+    return ba_check_settings(stage, "lg_bundle_focal_workspace_bytes", r.base, L.base.base.nodes, L.total);
 }
 // lg_posegraph_solve: a 256-byte record of the call; per image its rotation and centre in fp64 (96 bytes) and five int32 (level, present, list count, list
 // offset, fill cursor; the offsets hold one more entry); per pair its state (4), its rotation error (8), its direction (24) and its two adjacency entries

@@ -234,12 +234,13 @@ def triangulate_tracks(triangulator, result, feats, pairs, cameras, poses) -> di
     return triangulator.triangulate(_as_store(feats), pairs, result, cameras, poses)
 
 
-def bundle_adjust(adjuster, tracks, feats, cameras, poses, constant_pose) -> dict:
+def bundle_adjust(adjuster, tracks, feats, cameras, poses, constant_pose, constant_camera=None) -> dict:
     """Joint refinement of the free poses and of all track points from what `triangulate_tracks` returned (`tracks`: its dict, or (track_id, xyz)), by a
     `BundleAdjuster`: the same store (or a list of per-image dicts, collated once), the same cameras and poses, and the images whose pose is held fixed
-    (constant_pose: a [K] bool mask or image indices; at least one, two fix scale).  Returns the adjuster's dict; its points3d [K, N, 3] is what
+    (constant_pose: a [K] bool mask or image indices; at least one, two fix scale) and, with an adjuster built with refine_focal=True, the images whose focal
+    length is held (constant_camera: None, a mask or indices).  Returns the adjuster's dict; its points3d [K, N, 3] is what
     `estimate_absolute_poses` takes as points3d."""
-    return adjuster.adjust(_as_store(feats), tracks, cameras, poses, constant_pose)
+    return adjuster.adjust(_as_store(feats), tracks, cameras, poses, constant_pose, constant_camera)
 
 
 def estimate_global_poses(estimator, relative, pairs, num_images, **kw) -> dict:

@@ -14,8 +14,12 @@ tests/bundle_robust_oracle.py).  `--contaminate F`: after the triangulation, the
 3 observations, at most one per track — are moved by 20 .. 80 pixels in a random direction; the result line then also counts how many of them end above
 4 pixels or filtered, how many clean observations do, and the tracks still adjusted at the end.
 
+`--refine-focal`: the focal lengths are unknowns too (lg_bundle_adjust_focal; the host route is then tests/bundle_focal_oracle.py).  `--focal-error F`: the
+adjuster's cameras get fx and fy multiplied by 1 + F in the even images and 1 - F in the odd ones (the tracks are still those triangulated under the true
+cameras); the result line then holds the relative focal error per budget before and after (median and worst over the images).
+
 usage: bench_bundle_adjust.py [--images 16] [--kpts 2048] [--runs 5] [--host-iterations 2] [--only-adjust] [--loss squared|huber|cauchy] [--loss-scale 2]
-                              [--filter-rounds 0] [--max-reproj-error 4] [--contaminate 0]"""
+                              [--filter-rounds 0] [--max-reproj-error 4] [--contaminate 0] [--refine-focal] [--focal-error 0]"""
 import argparse
 import itertools
 import json
@@ -28,6 +32,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests")); sys.path.insert(0, str(ROOT / "tools"))
+import bundle_focal_oracle as F
 import bundle_oracle as B
 import bundle_robust_oracle as R
 from abspose_oracle import rodrigues
@@ -80,8 +85,12 @@ def main():
     ap.add_argument("--filter-rounds", type=int, default=0)
     ap.add_argument("--max-reproj-error", type=float, default=4.0)
     ap.add_argument("--contaminate", type=float, default=0.0, help="fraction of the observations moved by 20 .. 80 pixels after the triangulation")
+    ap.add_argument("--refine-focal", action="store_true", help="refine one focal length per image with the poses and points (lg_bundle_adjust_focal)")
+    ap.add_argument("--focal-error", type=float, default=0.0, help="relative error of the focal lengths given to the adjuster, the sign alternating by image")
     args = ap.parse_args()
     conf = dict(loss=args.loss, loss_scale=args.loss_scale, filter_rounds=args.filter_rounds, max_reproj_error=args.max_reproj_error)
+    if args.refine_focal:
+        conf["refine_focal"] = True
     if not torch.cuda.is_available():
         raise SystemExit("bench_bundle_adjust.py measures on an MI355X; there is nothing to measure without one")
     K = args.images
@@ -99,8 +108,12 @@ def main():
     clean_store, planted = store, None
     if args.contaminate > 0:
         store, planted = contaminate(store, tracks, args.contaminate)
-    triangulate = lambda: tri.triangulate(clean_store, pairs_dev, verified, cameras, true_poses, validate=False)
     constant = [0, 1]
+    true_cameras = cameras
+    if args.focal_error:                                                         # the triangulation above and below keeps the true cameras
+        factor = torch.tensor([1.0 + args.focal_error if k % 2 == 0 else 1.0 - args.focal_error for k in range(K)], device="cuda")
+        cameras = torch.cat([true_cameras[:, :2] * factor[:, None], true_cameras[:, 2:]], 1).float()
+    triangulate = lambda: tri.triangulate(clean_store, pairs_dev, verified, true_cameras, true_poses, validate=False)
     budgets = (1, 10)
     runs = {n: (lambda n=n: BundleAdjuster(num_iterations=n, **conf).adjust(store, tracks, cameras, start, constant)) for n in budgets}
     outs = {n: fn() for n, fn in runs.items()}                                   # warm-up of every timed shape
@@ -115,7 +128,8 @@ def main():
             ms[n].append(timed(runs[n])[0])
     res = {"images": K, "kpts": args.kpts, "pairs": int(pairs_dev.shape[0]), "device": torch.cuda.get_device_name(0), "runs": args.runs,
            "tracks": tracks["num_tracks"], "triangulate": stats(tri_ms), **conf, "contaminate": args.contaminate,
-           "planted": 0 if planted is None else int(planted.sum()), "adjust": []}
+           "planted": 0 if planted is None else int(planted.sum()), "refine_focal": args.refine_focal, "focal_error": args.focal_error, "adjust": []}
+    focal_error = lambda c: (c[:, 0].double() / true_cameras[:, 0].double() - 1.0).abs().cpu()
     for n in runs:
         o = outs[n]
         d = (o["points3d"].double().cpu() - torch.from_numpy(truth)).norm(dim=-1)
@@ -130,6 +144,11 @@ def main():
         res["adjust"][-1].update({"filtered": o["num_filtered"], "filter_stages": o["num_filter_stages"], "tracks_adjusted_at_the_end": int((kept >= 2).sum()),
                                   "clean_above_4px": int((above & ~planted).sum()) if planted is not None else int(above.sum()),
                                   "clean_filtered": int(((o["node_state"] == 7) & ~planted).sum()) if planted is not None else o["num_filtered"]})
+        if args.refine_focal:
+            before, after = focal_error(cameras), focal_error(o["cameras"])
+            res["adjust"][-1].update({"free_cameras": o["num_free_cameras"], "focal_error_before_median": round(float(before.median()), 6),
+                                      "focal_error_before_max": round(float(before.max()), 6), "focal_error_after_median": round(float(after.median()), 6),
+                                      "focal_error_after_max": round(float(after.max()), 6)})
         if planted is not None:
             res["adjust"][-1].update({"planted_above_4px": int((above & planted).sum()), "planted_filtered": int(((o["node_state"] == 7) & planted).sum())})
     ten, one = res["adjust"][1], res["adjust"][0]
@@ -137,10 +156,11 @@ def main():
         res["ms_per_iteration"] = round((ten["ms_median"] - one["ms_median"]) / (ten["iterations_run"] - one["iterations_run"]), 3)
     if args.host_iterations:
         inp = dict(kpts=store["keypoints"].cpu().numpy(), num=None, track_id=tracks["track_id"].cpu().numpy(), xyz=tracks["xyz"].cpu().numpy(),
-                   cams=np.asarray([CAMERA] * K, np.float32), poses=start.cpu().numpy(), constant=np.arange(K) < 2)
+                   cams=cameras.cpu().numpy(), poses=start.cpu().numpy(), constant=np.arange(K) < 2)
         t = time.perf_counter()
         robust = args.loss != "squared" or args.filter_rounds > 0
-        host = R.adjust(inp, num_iterations=args.host_iterations, **conf) if robust else B.adjust(inp, num_iterations=args.host_iterations)
+        host_conf = {k: v for k, v in conf.items() if k != "refine_focal"}
+        host = (F if args.refine_focal else R).adjust(inp, num_iterations=args.host_iterations, **host_conf) if robust or args.refine_focal else B.adjust(inp, num_iterations=args.host_iterations)
         host_ms = (time.perf_counter() - t) * 1e3
         dev = BundleAdjuster(num_iterations=args.host_iterations, **conf).adjust(store, tracks, cameras, start, constant)
         res["host"] = {"threads": 1, "iterations": host["num_iterations"], "ms": round(host_ms, 1), "final_cost": round(host["final_cost"], 3),
