@@ -20,22 +20,28 @@ from .triangulate import as_poses
 STATES = ("none", "active", "bad_image", "non_finite_point", "behind", "short_track", "too_long", "filtered")    # node_state 0 .. 7 (7: the robust mode's filter)
 
 
+def as_track_id(track_id, K: int, N: int, device) -> torch.Tensor:
+    """track_id [K, N] int64 on `device`: THE check of the labels `BundleAdjuster` and `GlobalPositioner` read"""
+    tid = torch.as_tensor(track_id)
+    if tuple(tid.shape) != (K, N):
+        raise ValueError(f"track_id must have shape [{K}, {N}], got {tuple(tid.shape)}")
+    if tid.dtype.is_floating_point or tid.dtype is torch.bool:
+        raise ValueError(f"track_id must hold integers, got {tid.dtype}")
+    return tid.detach().to(device=device, dtype=torch.int64).contiguous()
+
+
 def as_tracks(tracks, K: int, N: int, device):
     """(track_id [K, N] int64, xyz [T, 3] float32) on `device` from `Triangulator`'s dict or a tuple (track_id, xyz)"""
     if isinstance(tracks, dict):
         tracks = (tracks["track_id"], tracks["xyz"])
     if not isinstance(tracks, (tuple, list)) or len(tracks) != 2:
         raise ValueError("tracks must be the Triangulator's dict or a tuple (track_id [K, N], xyz [T, 3])")
-    tid, xyz = torch.as_tensor(tracks[0]), torch.as_tensor(tracks[1])
-    if tuple(tid.shape) != (K, N):
-        raise ValueError(f"track_id must have shape [{K}, {N}], got {tuple(tid.shape)}")
-    if tid.dtype.is_floating_point or tid.dtype is torch.bool:
-        raise ValueError(f"track_id must hold integers, got {tid.dtype}")
+    tid, xyz = as_track_id(tracks[0], K, N, device), torch.as_tensor(tracks[1])
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError(f"xyz must have shape [T, 3], got {tuple(xyz.shape)}")
     if xyz.shape[0] > K * N // 2:
         raise ValueError(f"xyz holds {xyz.shape[0]} tracks: more than K N / 2 = {K * N // 2} (a track has at least two observations)")
-    return tid.detach().to(device=device, dtype=torch.int64).contiguous(), xyz.detach().to(device=device, dtype=torch.float32).contiguous()
+    return tid, xyz.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 def as_constant(constant_pose, K: int, name: str = "constant_pose") -> torch.Tensor:

@@ -14,9 +14,10 @@
 // lg_bundle_adjust_focal runs that list with FOCAL compiled in: seven unknowns per image (column 6: the log of a common scale of fx and fy), interleaved per
 // image in S; the camera state lives twice like the poses (ba_cam<FOCAL> names the buffer; without FOCAL it is the image's record, which never moves);
 // ba_jacobians / ba_linearise fill a seventh column when they are given arrays of 7; the reduce runs 4 column blocks of 49 entries and 28 + 7 + 7 extras and
-// overwrites held columns (identity, zero coupling, zero right-hand side); its back substitution is ba_backsolve_focal_kernel in lg_bundle_focal.hip.  The
-// FOCAL kernels take BaFocalArgs, so the other two entry points' kernels keep their argument block and their instruction streams
-// (profiles/bundle_adjust_focal.md, which also lists registers and scratch of the new instantiations).
+// overwrites held columns (identity, zero coupling, zero right-hand side); ba_backsolve<true> also writes the trial cameras.  The FOCAL kernels take
+// BaFocalArgs, so the other two entry points' kernels keep their argument block (profiles/bundle_adjust_focal.md lists registers and scratch of the FOCAL
+// instantiations; profiles/ab_track_solver_steps.md those of the one back substitution).
+// The track lists (scan / fill / sort, "adjusted" = track_listed) and exp of a rotation vector are lg_solver_steps.h's, shared with lg_positioning.hip.
 // No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
 // other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
 // No floating-point atomics: every sum runs in the fixed order the header names.  Small matrices are indexed statically (no scratch: profiles/bundle_adjust.md).
@@ -25,16 +26,63 @@
 #include <string>
 #include <type_traits>
 
-#include "lg_bundle_args.h"
 #include "lg_cholesky.h"
 #include "lg_host_call.h"
 #include "lg_kernels.h"
 #include "lg_solve3.h"
+#include "lg_solver_steps.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
 
 namespace lg {
+
+// ------------------------------------------------------------------ the sizes, the device records, the kernels' argument blocks, the accessors of the state
+constexpr int BA_THREADS = 256, BA_SCAN_THREADS = 1024, BA_SCAN_WAVES = BA_SCAN_THREADS / 64;
+constexpr int BA_NB = LG_BA_CHOLESKY_BLOCK;                  // Cholesky (lg_cholesky.h): columns per panel = rows per tile
+static_assert(BA_NB == CH_NB && BA_THREADS == CH_THREADS, "lg_cholesky.h is written for 48-column panels and 256 threads");
+constexpr int BA_TILE = 32, BA_BCHUNK = 6;                   // reduce: rows of image a per LDS tile, column blocks b per workgroup (6 x 36 = 216 threads)
+constexpr int BA_FOCAL_BCHUNK = 4;                           // lg_bundle_adjust_focal: 7 columns per image, 4 x 49 = 196 entry threads and 28 + 7 + 7 extras
+template <bool FOCAL> constexpr int BA_COLS = FOCAL ? 7 : 6;
+template <bool FOCAL> constexpr int BA_CHUNK = FOCAL ? BA_FOCAL_BCHUNK : BA_BCHUNK;
+
+struct BaHead { double cost, cost_new, lambda, initial_cost; int sel, converged, iters, accepted, fail, nobs, removed, filtered, fstages, pad; };   // removed: by the running filter
+static_assert(sizeof(BaHead) <= 256, "the record of the call is 256 bytes");
+struct BaImage { double cam[4]; int ok, constant, nact, moved, cconstant, cmoved; double pad2; };   // moved: free in an earlier stage (lg_bundle_adjust_robust);
+                                                                                            // cconstant, cmoved: the same of the camera (lg_bundle_adjust_focal)
+static_assert(sizeof(BaImage) == 64, "lg_bundle_workspace_bytes counts 64 bytes");
+
+struct BaArgs {
+    int n, images, nodes, tracks, dim;
+    double lambda0, ftol;
+    const float* kpts; const int* num; const long long* track_id; const float* xyz; const float* cameras; const float* poses; const unsigned char* constant;
+    BaHead* head; BaImage* rec; double* pose; double* delta; double* icost; double* S;         // pose [2][images][12], S [dim + 1][dim]
+    int* list; int* limg; int* tcnt; int* toff; int* tcur; double* X; double* Vinv; double* y;  // X [2][tracks][3]
+    float* poses_out; float* xyz_out; float* points3d; unsigned char* node_state; float* obs_err; double* summary; int* status;
+    // lg_bundle_adjust_robust, behind everything lg_bundle_adjust's kernels read (their argument offsets stay what they were): the loss scale c, c c, the
+    // filter's bar e e, and per track "it moved in an earlier stage" (null without a filter)
+    double lc, lc2, fe2; int* tmov;
+};
+// lg_bundle_adjust_focal: the held cameras (null: none), the camera state (fx, fy, cx, cy) [2][images][4] (head->sel names the accepted one, like the poses),
+// cameras_out.  With it delta is [images][7] and S [7 images + 1][7 images].  A type of its own, so that the kernels of the other two entry points keep
+// their argument block to the byte (profiles/bundle_adjust_focal.md compares their instruction streams)
+struct BaFocalArgs : BaArgs { const unsigned char* cconstant; double* cam; float* cameras_out; };
+template <bool FOCAL> using BaArgsOf = std::conditional_t<FOCAL, BaFocalArgs, BaArgs>;
+
+__device__ __forceinline__ bool ba_free(const BaArgs& a, int k) { const BaImage& im = a.rec[k]; return im.ok && !im.constant && im.nact > 0; }
+__device__ __forceinline__ bool ba_cam_free(const BaArgs& a, int k) { const BaImage& im = a.rec[k]; return im.ok && !im.cconstant && im.nact > 0; }
+// an image with at least one free column
+template <bool FOCAL> __device__ __forceinline__ bool ba_any_free(const BaArgs& a, int k) {
+    if constexpr (FOCAL) return ba_free(a, k) || ba_cam_free(a, k);
+    else return ba_free(a, k);
+}
+// the camera of image k: with FOCAL buffer `which` of the state, else the record's (it never moves)
+template <bool FOCAL> __device__ __forceinline__ const double* ba_cam(const BaArgsOf<FOCAL>& a, int which, int k) {
+    if constexpr (FOCAL) return a.cam + ((long long)which * a.images + k) * 4;
+    else return a.rec[k].cam;
+}
+__device__ __forceinline__ const double* ba_pose(const BaArgs& a, int which, int k) { return a.pose + ((long long)which * a.images + k) * 12; }
+__device__ __forceinline__ const double* ba_point(const BaArgs& a, int which, int j) { return a.X + ((long long)which * a.tracks + j) * 3; }
 
 // p = R X + t of pose P [12] (R | t row-major 3 x 4)
 __device__ __forceinline__ void ba_project(const double* P, const double* X, double (&p)[3]) {
@@ -151,51 +199,16 @@ template <bool AGAIN> __global__ __launch_bounds__(BA_THREADS) void ba_count_ker
     a.node_state[v] = (unsigned char)state;
 }
 
-// ONE workgroup: the exclusive scan of the adjusted tracks' counts (integers: the order of the additions changes nothing)
+// the lists of the adjusted tracks (lg_solver_steps.h): ONE workgroup scans; one lane per node fills (states 5 / 6, the image's count); one lane per track sorts
 __global__ __launch_bounds__(BA_SCAN_THREADS) void ba_scan_kernel(BaArgs a) {
     __shared__ int sh[BA_SCAN_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int share = (a.tracks + BA_SCAN_THREADS - 1) / BA_SCAN_THREADS;
-    const int beg = min((int)threadIdx.x * share, a.tracks), end = min(beg + share, a.tracks);
-    int mine = 0;
-    for (int j = beg; j < end; ++j) if (ba_adjusted(a, j)) mine += a.tcnt[j];
-    int inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += sh[w];
-    int at = base + inc - mine;                            // the sum of all counts is at most nodes: every node is counted once
-    for (int j = beg; j < end; ++j) if (ba_adjusted(a, j)) { a.toff[j] = at; at += a.tcnt[j]; }
+    track_scan<BA_SCAN_THREADS>(a, sh);
 }
-
 __global__ __launch_bounds__(BA_THREADS) void ba_fill_kernel(BaArgs a) {
     const int v = blockIdx.x * BA_THREADS + threadIdx.x;
-    if (v >= a.nodes) return;
-    if (a.node_state[v] != 1) return;
-    const int j = (int)a.track_id[v], cnt = a.tcnt[j];     // a candidate: 0 <= j < tracks
-    if (cnt < 2) { a.node_state[v] = 5; return; }
-    if (cnt > LG_BA_MAX_TRACK_LENGTH) { a.node_state[v] = 6; return; }
-    const int at = atomicAdd(a.tcur + j, 1);
-    if (at < cnt) a.list[a.toff[j] + at] = v;              // always: cnt candidates carry this track; toff + cnt <= nodes
-    atomicAdd(&a.rec[v / a.n].nact, 1);
+    if (track_fill<5, 6>(a, v)) atomicAdd(&a.rec[v / a.n].nact, 1);
 }
-
-__global__ __launch_bounds__(BA_THREADS) void ba_sort_kernel(BaArgs a) {
-    const int j = blockIdx.x * BA_THREADS + threadIdx.x;
-    if (j >= a.tracks || !ba_adjusted(a, j)) return;
-    const int len = a.tcnt[j];
-    int* lst = a.list + a.toff[j];
-    for (int q = 1; q < len; ++q) {                        // ascending node order, whatever order the atomics left; len <= 1024
-        const int key = lst[q];
-        int r = q - 1;
-        while (r >= 0 && lst[r] > key) { lst[r + 1] = lst[r]; --r; }
-        lst[r + 1] = key;
-    }
-    int* img = a.limg + a.toff[j];
-    for (int q = 0; q < len; ++q) img[q] = lst[q] / a.n;
-}
+__global__ __launch_bounds__(BA_THREADS) void ba_sort_kernel(BaArgs a) { track_sort(a, blockIdx.x * BA_THREADS + threadIdx.x); }
 
 // ------------------------------------------------------------------ between two stages (lg_bundle_adjust_robust): the filter, then count<true>, scan, fill, sort, cost
 // One lane per node: an active observation whose error at the accepted state exceeds the bar becomes state 7, counted by an integer atomicAdd.  The same
@@ -213,7 +226,7 @@ template <bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_filter_ke
         if (rx * rx + ry * ry > a.fe2) { a.node_state[g] = 7; atomicAdd(&a.head->removed, 1); }
     }
     if (g < a.tracks) {
-        a.tmov[g] = ((first ? 0 : a.tmov[g]) || ba_adjusted(a, (int)g)) ? 1 : 0;
+        a.tmov[g] = ((first ? 0 : a.tmov[g]) || track_listed(a, (int)g)) ? 1 : 0;
 #pragma unroll
         for (int e = 0; e < 3; ++e) a.X[((long long)(s ^ 1) * a.tracks + g) * 3 + e] = a.X[((long long)s * a.tracks + g) * 3 + e];
         a.tcnt[g] = 0; a.tcur[g] = 0; a.toff[g] = 0;
@@ -303,7 +316,7 @@ __global__ void ba_decide_kernel(BaArgs a, int initial) {
 template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_points_kernel(BaArgsOf<FOCAL> a) {
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
-    if (j >= a.tracks || !ba_adjusted(a, j)) return;
+    if (j >= a.tracks || !track_listed(a, j)) return;
     const int s = a.head->sel, len = a.tcnt[j], off = a.toff[j];
     const double lambda = a.head->lambda;
     const double* Xp = ba_point(a, s, j);
@@ -323,14 +336,7 @@ template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba
     }
     V[0] = ba_damped(V[0], lambda); V[3] = ba_damped(V[3], lambda); V[5] = ba_damped(V[5], lambda);
     double Vi[3][3];
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0};
-        double x[3];
-        ok = tri_solve3(V, e, x) && ok;
-        Vi[0][c] = x[0]; Vi[1][c] = x[1]; Vi[2][c] = x[2];
-    }
+    const bool ok = tri_inverse3(V, Vi);
     double* vo = a.Vinv + (long long)j * 9;
     double* yo = a.y + (long long)j * 3;
 #pragma unroll
@@ -517,8 +523,11 @@ __global__ __launch_bounds__(BA_THREADS) void ba_cholesky_rows_kernel(BaArgs a, 
 }
 
 // ------------------------------------------------------------------ per iteration 4: ONE workgroup: L^T s = z backwards, the trial poses
-__global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
-    __shared__ double sd[6 * LG_BA_MAX_IMAGES];
+// FOCAL: 7 entries per image, and the trial cameras, f <- f exp(d) for fx and fy of a free camera (a trial focal length that is not finite or not > 0 fails
+// the step); a held column's step is 0
+template <bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgsOf<FOCAL> a) {
+    constexpr int D = BA_COLS<FOCAL>;
+    __shared__ double sd[D * LG_BA_MAX_IMAGES];
     __shared__ CholeskySolveLds m;
     if (a.head->converged) return;
     const int t = threadIdx.x;
@@ -528,28 +537,28 @@ __global__ __launch_bounds__(BA_THREADS) void ba_backsolve_kernel(BaArgs a) {
     for (int k = t; k < a.images; k += BA_THREADS) {
         const double* P = ba_pose(a, s, k);
         double* out = a.pose + ((long long)(s ^ 1) * a.images + k) * 12;
+        if constexpr (FOCAL) {
+            const bool cf = ba_cam_free(a, k);
+            const double d = cf ? sd[D * k + 6] : 0.0, scale = exp(d);
+            const double* c0 = ba_cam<true>(a, s, k);
+            double* c1 = a.cam + ((long long)(s ^ 1) * a.images + k) * 4;
+            a.delta[k * D + 6] = d;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const double v = cf ? c0[q] * scale : c0[q];
+                if (cf && !(isfinite(v) && v > 0.0)) bad = 1;
+                c1[q] = v; c1[2 + q] = c0[2 + q];
+            }
+        }
         if (!ba_free(a, k)) {
             for (int q = 0; q < 12; ++q) out[q] = P[q];
-            for (int q = 0; q < 6; ++q) a.delta[k * 6 + q] = 0.0;
+            for (int q = 0; q < 6; ++q) a.delta[k * D + q] = 0.0;
             continue;
         }
-        double x[6];
+        double x[6], Q[9];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) { x[q] = sd[6 * k + q]; a.delta[k * 6 + q] = x[q]; }
-        // Rodrigues(w) = I + sin(th) [k]x + (1 - cos(th)) [k]x^2, k = w / th
-        const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-        double Q[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-        if (th > 0.0) {
-            const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th, sn = sin(th), c1 = 1.0 - cos(th);
-            const double Kx[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const double kk = (Kx[3 * i] * Kx[j] + Kx[3 * i + 1] * Kx[3 + j]) + Kx[3 * i + 2] * Kx[6 + j];
-                    Q[3 * i + j] = (Q[3 * i + j] + sn * Kx[3 * i + j]) + c1 * kk;
-                }
-        }
+        for (int q = 0; q < 6; ++q) { x[q] = sd[D * k + q]; a.delta[k * D + q] = x[q]; }
+        so3_exp(x, Q);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -568,7 +577,7 @@ template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba
     constexpr int D = BA_COLS<FOCAL>;              // a held column's step is 0 (ba_backsolve)
     if (a.head->converged) return;
     const int j = blockIdx.x * BA_THREADS + threadIdx.x;
-    if (j >= a.tracks || !ba_adjusted(a, j)) return;
+    if (j >= a.tracks || !track_listed(a, j)) return;
     const int s = a.head->sel, len = a.tcnt[j], off = a.toff[j];
     const double* Xp = ba_point(a, s, j);
     const double X[3] = {Xp[0], Xp[1], Xp[2]};
@@ -634,7 +643,7 @@ template <bool ROBUST, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void
         a.obs_err[g] = err;
     }
     if (g < a.tracks) {
-        bool adj = ba_adjusted(a, (int)g);
+        bool adj = track_listed(a, (int)g);
         if constexpr (ROBUST) adj = adj || (a.tmov && a.tmov[g]);
         const double* X = ba_point(a, s, (int)g);
 #pragma unroll
@@ -661,7 +670,6 @@ template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const
     const dim3 th(BA_THREADS);
     const BaArgs& b = a;                                        // what the kernels that know no focal column take
     const int K = a.images, T = a.tracks;
-    const int panels = ((int)L.dim + BA_NB - 1) / BA_NB, tiles = ((int)L.dim + 1 + BA_NB - 1) / BA_NB;
     const long long all = std::max<long long>(std::max<long long>(L.nodes, T), K);
     hipLaunchKernelGGL(ba_init_kernel<FOCAL>, blocks(std::max<long long>(K, T)), th, 0, s, a);
     if (L.nodes) hipLaunchKernelGGL(ba_count_kernel<false>, blocks(L.nodes), th, 0, s, b);
@@ -683,12 +691,11 @@ template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const
         for (int it = 0; it < iterations; ++it) {
             if (T) hipLaunchKernelGGL((ba_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
             hipLaunchKernelGGL((ba_reduce_kernel<LOSS, FOCAL>), dim3(K, (K + BA_CHUNK<FOCAL> - 1) / BA_CHUNK<FOCAL>), th, 0, s, a);
-            for (int p = 0; p < panels; ++p) {
+            for_cholesky_panels((int)L.dim, 1, [&](int p, int tiles_below) {
                 hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, b, p);
-                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles - p), th, 0, s, b, p);
-            }
-            if constexpr (FOCAL) ba_launch_backsolve_focal(a, s);
-            else hipLaunchKernelGGL(ba_backsolve_kernel, dim3(1), th, 0, s, a);
+                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles_below), th, 0, s, b, p);
+            });
+            hipLaunchKernelGGL(ba_backsolve_kernel<FOCAL>, dim3(1), th, 0, s, a);
             if (T) hipLaunchKernelGGL((ba_trial_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
             hipLaunchKernelGGL((ba_cost_kernel<LOSS, FOCAL>), dim3(K), th, 0, s, a, 1);
             hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, b, 0);
@@ -701,21 +708,31 @@ template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const
 
 // the kernels' view of a checked call: the caller's arrays and the workspace carved by L
 static BaArgs ba_args(const lg_bundle_io& io, const BaLayout& L) {
-    char* ws = static_cast<char*>(io.workspace);
+    const Carved ws(io.workspace);
     BaArgs a{};
     a.n = io.n; a.images = io.images; a.nodes = (int)L.nodes; a.tracks = io.tracks; a.dim = (int)L.dim;
     a.lambda0 = io.initial_damping; a.ftol = io.function_tolerance;
     a.kpts = io.kpts; a.num = io.num; a.track_id = reinterpret_cast<const long long*>(io.track_id); a.xyz = io.xyz; a.cameras = io.cameras; a.poses = io.poses;
     a.constant = io.constant_pose;
-    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
-    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
-    a.head = reinterpret_cast<BaHead*>(ws + L.head); a.rec = reinterpret_cast<BaImage*>(ws + L.rec);
-    a.pose = f64(L.pose); a.delta = f64(L.delta); a.icost = f64(L.icost); a.S = f64(L.S);
-    a.list = ints(L.list); a.limg = ints(L.limg); a.tcnt = ints(L.tcnt); a.toff = ints(L.toff); a.tcur = ints(L.tcur);
-    a.X = f64(L.X); a.Vinv = f64(L.Vinv); a.y = f64(L.y);
+    a.head = ws.as<BaHead>(L.head); a.rec = ws.as<BaImage>(L.rec);
+    a.pose = ws.f64(L.pose); a.delta = ws.f64(L.delta); a.icost = ws.f64(L.icost); a.S = ws.f64(L.S);
+    a.list = ws.ints(L.list); a.limg = ws.ints(L.limg); a.tcnt = ws.ints(L.tcnt); a.toff = ws.ints(L.toff); a.tcur = ws.ints(L.tcur);
+    a.X = ws.f64(L.X); a.Vinv = ws.f64(L.Vinv); a.y = ws.f64(L.y);
     a.poses_out = io.poses_out; a.xyz_out = io.xyz_out; a.points3d = io.points3d; a.node_state = io.node_state; a.obs_err = io.observation_error;
     a.summary = io.summary; a.status = io.status;
     return a;
+}
+
+// lg_bundle_adjust_robust and lg_bundle_adjust_focal: the robust settings behind a checked call's arguments, and the launch list with r's loss compiled in
+template <bool FOCAL> static int ba_enqueue_robust(BaArgsOf<FOCAL> a, const BaRobustLayout& L, const lg_bundle_robust_io& r, void* hip_stream) {
+    a.lc = r.loss_scale; a.lc2 = r.loss_scale * r.loss_scale; a.fe2 = r.max_reproj_error * r.max_reproj_error;
+    a.tmov = r.filter_rounds > 0 ? Carved(r.base.workspace).ints(L.tmov) : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    switch (r.loss) {
+        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
+        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
+        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
+    }
 }
 
 }  // namespace lg
@@ -750,15 +767,7 @@ int lg_bundle_adjust_robust(const lg_bundle_robust_io* io, void* hip_stream) {
     if (const char* why = ba_robust_settings_error(io->loss, io->loss_scale, io->filter_rounds, io->max_reproj_error))
         return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why);
     if (const int rc = ba_check_settings(stage, "lg_bundle_robust_workspace_bytes", io->base, L.base.nodes, L.total)) return rc;
-    BaArgs a = ba_args(io->base, L.base);
-    a.lc = io->loss_scale; a.lc2 = io->loss_scale * io->loss_scale; a.fe2 = io->max_reproj_error * io->max_reproj_error;
-    a.tmov = io->filter_rounds > 0 ? reinterpret_cast<int*>(static_cast<char*>(io->base.workspace) + L.tmov) : nullptr;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    switch (io->loss) {
-        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
-        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
-        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true>(a, L.base, io->base.num_iterations, io->filter_rounds, s);
-    }
+    return ba_enqueue_robust<false>(ba_args(io->base, L.base), L, *io, hip_stream);
 }
 
 int64_t lg_bundle_focal_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags) {
@@ -773,16 +782,8 @@ int lg_bundle_adjust_focal(const lg_bundle_focal_io* io, void* hip_stream) {
     BaFocalLayout L;
     if (const char* why = ba_focal_layout(r.base.images, r.base.n, r.base.tracks, r.base.flags, L)) return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why);
     if (const int rc = ba_focal_check_settings(stage, *io, L)) return rc;
-    char* ws = static_cast<char*>(r.base.workspace);
-    BaFocalArgs a{ba_args(r.base, L.base.base), io->constant_camera, reinterpret_cast<double*>(ws + L.cam), io->cameras_out};
-    a.lc = r.loss_scale; a.lc2 = r.loss_scale * r.loss_scale; a.fe2 = r.max_reproj_error * r.max_reproj_error;
-    a.tmov = r.filter_rounds > 0 ? reinterpret_cast<int*>(ws + L.base.tmov) : nullptr;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    switch (r.loss) {
-        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
-        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
-        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
-    }
+    const BaFocalArgs a{ba_args(r.base, L.base.base), io->constant_camera, Carved(r.base.workspace).f64(L.cam), io->cameras_out};
+    return ba_enqueue_robust<true>(a, L.base, r, hip_stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // lightglue_amd — the host side the entry points over a pair list or a caller's workspace share (lg_engine_forward, lg_nn_match, lg_twoview_verify,
-// lg_relpose_estimate, lg_abspose_estimate, lg_sift_filter): their refusals, the carving of a workspace, the stateless entry points' layouts, the cut of a pair
-// list into launches, and the whole opening of a call of the three hypothesise-and-verify estimators (check_estimator_call).  Host-only C++17
+// lg_relpose_estimate, lg_abspose_estimate, lg_sift_filter) and the solvers (lg_bundle_adjust*, lg_posegraph_solve, lg_positioning_solve): their refusals, the
+// carving of a workspace, the stateless entry points' layouts, the cut of a pair list into launches, the panel loop of the Cholesky, and the whole opening of
+// a call of the three hypothesise-and-verify estimators (check_estimator_call).  Host-only C++17
 // like lg_forward_plan.h (no HIP header, no device type): tests/cpp/host_call_check.cpp walks it with any host compiler, and under its address sanitizer.
 #pragma once
 #include <cstdint>
@@ -28,6 +29,8 @@ inline int check_workspace(const char* stage, const char* size_function, const v
     if (reinterpret_cast<uintptr_t>(ptr) & 255) return set_error(LG_ERR_INVALID, std::string(stage) + ": the workspace must be 256-byte aligned");
     return LG_OK;
 }
+// THE "> 0 (and finite)" test of every fp64 setting
+inline bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
 // keypoint rows per image of a call: nullptr, or why they are refused
 inline const char* keypoint_counts_error(int n0, int n1 = 0) {
     return n0 < 0 || n1 < 0 || n0 > LG_MAX_KEYPOINTS || n1 > LG_MAX_KEYPOINTS ? "n0, n1 must lie in [0, LG_MAX_KEYPOINTS]" : nullptr;
@@ -37,6 +40,14 @@ inline const char* keypoint_counts_error(int n0, int n1 = 0) {
 struct Bump {
     long long used = 0;
     long long take(long long bytes) { const long long o = used; used += (bytes + 255) / 256 * 256; return o; }
+};
+// typed pointers into a workspace at a layout's offsets
+struct Carved {
+    char* base;
+    explicit Carved(void* workspace) : base(static_cast<char*>(workspace)) {}
+    template <class T> T* as(long long at) const { return reinterpret_cast<T*>(base + at); }
+    int* ints(long long at) const { return as<int>(at); }
+    double* f64(long long at) const { return as<double>(at); }
 };
 // lg_nn_match: the normalised fp32 rows of either store, one "touched" byte per image of either store.  No pair count: the size depends on the stores alone.
 constexpr uint32_t NN_KNOWN_FLAGS = LG_FLAG_INDEXED | LG_FLAG_DESC0_F16 | LG_FLAG_DESC1_F16 | LG_SIFT_STORE_FLAGS | LG_FLAG_NN_MUTUAL;
@@ -196,7 +207,6 @@ inline const char* ba_layout(long long images, long long n, long long tracks, ui
 // workspace of `need` bytes (`size_function` names what sizes it)
 inline int ba_check_settings(const char* stage, const char* size_function, const lg_bundle_io& io, long long nodes, long long need) {
     const auto refuse = [stage](const char* why) { return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why); };
-    const auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     if (io.num_iterations < 1 || io.num_iterations > LG_BA_MAX_ITERATIONS) return refuse("num_iterations must lie in [1, LG_BA_MAX_ITERATIONS]");
     if (!positive(io.initial_damping) || !positive(io.function_tolerance)) return refuse("initial_damping and function_tolerance must be > 0 (and finite)");
     if (!io.cameras || !io.poses || !io.constant_pose || !io.poses_out || !io.summary || !io.status || (io.tracks && (!io.xyz || !io.xyz_out)) ||
@@ -214,7 +224,6 @@ inline const char* ba_robust_layout(long long images, long long n, long long tra
     return nullptr;
 }
 inline const char* ba_robust_settings_error(long long loss, double loss_scale, long long filter_rounds, double max_reproj_error) {
-    const auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     if (loss < LG_BA_LOSS_SQUARED || loss > LG_BA_LOSS_CAUCHY) return "loss must be LG_BA_LOSS_SQUARED, LG_BA_LOSS_HUBER or LG_BA_LOSS_CAUCHY";
     if (loss != LG_BA_LOSS_SQUARED && !positive(loss_scale)) return "loss_scale must be > 0 (and finite) with a robust loss";
     if (filter_rounds < 0 || filter_rounds > LG_BA_MAX_FILTER_ROUNDS) return "filter_rounds must lie in [0, LG_BA_MAX_FILTER_ROUNDS]";
@@ -261,7 +270,6 @@ inline const char* pg_settings_error(long long images, long long num_iterations,
     if (num_iterations < LG_PG_MIN_ITERATIONS || num_iterations > LG_BA_MAX_ITERATIONS) return "num_iterations must lie in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]";
     if (origin < 0 || origin >= images) return "origin must name an image";
     if (baseline < -1 || baseline >= images || baseline == origin) return "baseline must be -1 or name an image other than origin";
-    auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     if (!positive(rotation_scale) || !positive(max_rotation_error) || !positive(direction_scale))
         return "rotation_scale, max_rotation_error and direction_scale must be > 0 (and finite)";
     return nullptr;
@@ -288,7 +296,6 @@ inline const char* pos_layout(long long images, long long n, long long tracks, u
 }
 inline const char* pos_settings_error(long long num_iterations, double angle_scale, double max_angle_error) {
     if (num_iterations < LG_PG_MIN_ITERATIONS || num_iterations > LG_BA_MAX_ITERATIONS) return "num_iterations must lie in [LG_PG_MIN_ITERATIONS, LG_BA_MAX_ITERATIONS]";
-    auto positive = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
     if (!positive(angle_scale) || !positive(max_angle_error)) return "angle_scale and max_angle_error must be > 0 (and finite)";
     return nullptr;
 }
@@ -301,6 +308,15 @@ inline bool sift_filter_layout(int images, int n, int max_h, int max_w, SiftFilt
     Bump bp;
     L.m1 = bp.take(raster); L.m2 = bp.take(raster); L.flags = bp.take((long long)images * n); L.total = bp.used;
     return true;
+}
+
+// ---------------------------------------------------------------- the launches of the blocked Cholesky (lg_cholesky.h) of a dim x dim system with nrhs
+// right-hand sides as further rows: visit(panel, tiles_below) per panel of LG_BA_CHOLESKY_BLOCK columns, in order; tiles_below: the row tiles from the
+// panel's own down to the last (the rows launch's grid)
+template <class F> void for_cholesky_panels(int dim, int nrhs, F visit) {
+    constexpr int NB = LG_BA_CHOLESKY_BLOCK;
+    const int panels = (dim + NB - 1) / NB, tiles = (dim + nrhs + NB - 1) / NB;
+    for (int p = 0; p < panels; ++p) visit(p, tiles - p);
 }
 
 // ---------------------------------------------------------------- pairs are grid.x: 2^20 x 512 threads stays below the 2^32 threads per grid axis HIP accepts,

@@ -11,7 +11,8 @@
 //   pg_output     one lane per image and pair.
 // That is 8 + n (4 + 2 ceil(K / 48) + 2 ceil(3 K / 48)) launches for n iterations over K images: 104 at K = 16, n = 12; 584 at K = 256.  No kernel waits on
 // another workgroup; every kernel of a stage returns at once when the stage's `done` is set in the record (uniform over the grid: only the update kernels
-// write it).  No floating-point atomics: every sum runs over the image's sorted list.  Small matrices are indexed statically.
+// write it).  No floating-point atomics: every sum runs over the image's sorted list.  Small matrices are indexed statically.  exp of a rotation vector and the
+// position stage's ray steps (ray_block, ray_apply, ray_angle, ray_weight) are lg_solver_steps.h's, shared with lg_bundle.hip and lg_positioning.hip.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -19,6 +20,7 @@
 #include "lg_cholesky.h"
 #include "lg_host_call.h"
 #include "lg_kernels.h"
+#include "lg_solver_steps.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -79,12 +81,6 @@ __device__ __forceinline__ void pair_omega(const PgArgs& a, int p, int ia, int i
     mul33(Rab, a.rot + (long long)ia * 9, T);
     mulT33(a.rot + (long long)ib * 9, T, M);
     so3_log(M, om);
-}
-// atan2(|e - (d . e) d|, d . e)
-__device__ __forceinline__ double angle_to(const double* d, const double (&e)[3]) {
-    const double de = (d[0] * e[0] + d[1] * e[1]) + d[2] * e[2];
-    const double r[3] = {e[0] - de * d[0], e[1] - de * d[1], e[2] - de * d[2]};
-    return atan2(sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]), de);
 }
 
 // ------------------------------------------------------------------ records, states 1 and 2, the adjacency
@@ -289,21 +285,9 @@ __global__ __launch_bounds__(PG_THREADS) void pg_rot_update_kernel(PgArgs a, int
         if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) bad = 1;
         mx = fmax(fmax(fabs(x[0]), fabs(x[1])), fabs(x[2]));
         if (a.level[i] >= 0 && i != a.origin) {
-            const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-            double Q[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-            if (th > 0.0) {
-                const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th, sn = sin(th), c1 = 1.0 - cos(th);
-                const double Kx[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const double kk = (Kx[3 * r] * Kx[c] + Kx[3 * r + 1] * Kx[3 + c]) + Kx[3 * r + 2] * Kx[6 + c];
-                        Q[3 * r + c] = (Q[3 * r + c] + sn * Kx[3 * r + c]) + c1 * kk;
-                    }
-            }
             double* Ri = a.rot + (long long)i * 9;
-            double out[9];
+            double Q[9], out[9];
+            so3_exp(x, Q);
             mul33(Ri, Q, out);
 #pragma unroll
             for (int e = 0; e < 9; ++e) Ri[e] = out[e];
@@ -431,13 +415,10 @@ __global__ __launch_bounds__(PG_THREADS) void pg_pos_assemble_kernel(PgArgs a, i
                 double rho = 1.0;
                 if (it > 0) {
                     const double e[3] = {a.cen[3 * ib] - a.cen[3 * ia], a.cen[3 * ib + 1] - a.cen[3 * ia + 1], a.cen[3 * ib + 2] - a.cen[3 * ia + 2]};
-                    const double ee = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2], q = angle_to(d, e) / tau_it;
-                    rho = 1.0 / fmax(ee, 1e-12) / (1.0 + q * q);
+                    rho = ray_weight(d, e, tau_it);
                 }
-                const double c = (double)a.w[p] * rho;
                 j = key_nbr(key);
-                sM[t][0] = c * (1.0 - d[0] * d[0]); sM[t][1] = c * (0.0 - d[0] * d[1]); sM[t][2] = c * (0.0 - d[0] * d[2]);
-                sM[t][3] = c * (1.0 - d[1] * d[1]); sM[t][4] = c * (0.0 - d[1] * d[2]); sM[t][5] = c * (1.0 - d[2] * d[2]);
+                ray_block(d, (double)a.w[p] * rho, sM[t]);
             }
         }
         sJ[t] = j;
@@ -447,13 +428,13 @@ __global__ __launch_bounds__(PG_THREADS) void pg_pos_assemble_kernel(PgArgs a, i
             for (int q = 0; q < m; ++q) {
                 const int jq = sJ[q];
                 if (jq < 0) continue;
-                const double* M = sM[q];
+                const double (&M)[6] = sM[q];
 #pragma unroll
                 for (int s = 0; s < 6; ++s) diag[s] += M[s];
                 if (jq == base) {                           // the baseline's known centre moves to the right-hand side
-                    rhs[0] += (M[0] * cb[0] + M[1] * cb[1]) + M[2] * cb[2];
-                    rhs[1] += (M[1] * cb[0] + M[3] * cb[1]) + M[4] * cb[2];
-                    rhs[2] += (M[2] * cb[0] + M[4] * cb[1]) + M[5] * cb[2];
+                    double y[3];
+                    ray_apply(M, cb, y);
+                    rhs[0] += y[0]; rhs[1] += y[1]; rhs[2] += y[2];
                 } else if (jq < i && jq != a.origin) {      // a free image (state 0: it is present), the lower block triangle
                     if (jq != runj) {
                         if (runj >= 0) flush(runj, run);
@@ -524,7 +505,7 @@ __global__ __launch_bounds__(PG_THREADS) void pg_output_kernel(PgArgs a) {
         for (int r = 0; r < 3; ++r) {
 #pragma unroll
             for (int e = 0; e < 3; ++e) o[4 * r + e] = in ? (float)R[3 * r + e] : nanf_;
-            o[4 * r + 3] = posed ? (float)(-((R[3 * r] * c[0] + R[3 * r + 1] * c[1]) + R[3 * r + 2] * c[2])) : nanf_;
+            o[4 * r + 3] = posed ? (float)minus_Rc(R, c, r) : nanf_;
         }
         a.image_state[g] = (unsigned char)(posed ? 0 : in ? 1 : 2);
     }
@@ -534,7 +515,7 @@ __global__ __launch_bounds__(PG_THREADS) void pg_output_kernel(PgArgs a) {
         if (st == 0 && positions) {
             const int ia = (int)a.pairs[2 * (long long)g], ib = (int)a.pairs[2 * (long long)g + 1];
             const double e[3] = {a.cen[3 * ib] - a.cen[3 * ia], a.cen[3 * ib + 1] - a.cen[3 * ia + 1], a.cen[3 * ib + 2] - a.cen[3 * ia + 2]};
-            de = (float)(angle_to(a.dir + 3 * (long long)g, e) * PG_DEG);
+            de = (float)(ray_angle(a.dir + 3 * (long long)g, e) * PG_DEG);
         }
         a.pair_state[g] = (unsigned char)st;
         a.rot_err[g] = (float)a.perr[g];
@@ -567,17 +548,15 @@ int lg_posegraph_solve(const lg_posegraph_io* io, void* hip_stream) {
     if (const int rc = check_workspace("lg_posegraph_solve", "lg_posegraph_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    char* ws = static_cast<char*>(io->workspace);
+    const Carved ws(io->workspace);
     const double rad = 3.14159265358979323846 / 180.0;
     PgArgs a{};
     a.K = io->images; a.P = io->pairs; a.n = io->num_iterations; a.origin = io->origin; a.baseline_in = io->baseline; a.min_inliers = io->min_inliers;
     a.sigma = io->rotation_scale * rad; a.tau = io->direction_scale * rad; a.max_rot = io->max_rotation_error;
     a.pairs = reinterpret_cast<const long long*>(io->pair_index); a.R = io->rotations; a.t = io->translations; a.w = io->weights; a.inl = io->num_inliers;
-    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
-    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
-    a.head = reinterpret_cast<PgHead*>(ws + L.head); a.rot = f64(L.rot); a.cen = f64(L.cen);
-    a.level = ints(L.level); a.present = ints(L.present); a.acount = ints(L.acount); a.aoff = ints(L.aoff); a.acur = ints(L.acur);
-    a.pstate = ints(L.pstate); a.perr = f64(L.perr); a.dir = f64(L.dir); a.adj = reinterpret_cast<unsigned long long*>(ws + L.adj); a.S = f64(L.S);
+    a.head = ws.as<PgHead>(L.head); a.rot = ws.f64(L.rot); a.cen = ws.f64(L.cen);
+    a.level = ws.ints(L.level); a.present = ws.ints(L.present); a.acount = ws.ints(L.acount); a.aoff = ws.ints(L.aoff); a.acur = ws.ints(L.acur);
+    a.pstate = ws.ints(L.pstate); a.perr = ws.f64(L.perr); a.dir = ws.f64(L.dir); a.adj = ws.as<unsigned long long>(L.adj); a.S = ws.f64(L.S);
     a.poses = io->poses; a.image_state = io->image_state; a.pair_state = io->pair_state; a.rot_err = io->rotation_error; a.dir_err = io->direction_error;
     a.summary = io->summary;
 
@@ -585,11 +564,10 @@ int lg_posegraph_solve(const lg_posegraph_io* io, void* hip_stream) {
     const dim3 th(PG_THREADS);
     const int K = io->images, P = io->pairs, n = io->num_iterations;
     auto factor = [&](int stage, int dim, int nrhs) {
-        const int panels = (dim + CH_NB - 1) / CH_NB, tiles = (dim + nrhs + CH_NB - 1) / CH_NB;
-        for (int p = 0; p < panels; ++p) {
+        for_cholesky_panels(dim, nrhs, [&](int p, int tiles_below) {
             hipLaunchKernelGGL(pg_chol_diag_kernel, dim3(1), th, 0, s, a, stage, dim, p);
-            hipLaunchKernelGGL(pg_chol_rows_kernel, dim3(tiles - p), th, 0, s, a, stage, dim, nrhs, p);
-        }
+            hipLaunchKernelGGL(pg_chol_rows_kernel, dim3(tiles_below), th, 0, s, a, stage, dim, nrhs, p);
+        });
     };
     hipLaunchKernelGGL(pg_clear_kernel, blocks(K), th, 0, s, a);
     hipLaunchKernelGGL(pg_classify_kernel, blocks(P), th, 0, s, a);

@@ -13,8 +13,8 @@
 //   pos_output    one lane per image: pose and state; lane 0 the summary.
 // That is 8 + n (4 + 2 ceil(3 K / 48)) launches for n iterations over K images.  No kernel waits on another workgroup; every kernel of an iteration returns
 // at once when the record says the stage has ended (uniform over the grid: only pos_take_part and pos_centres write it).  No floating-point atomics: every sum
-// runs in the fixed order the header names.  The track lists follow lg_bundle.hip (count / scan / fill / sort), kept as a local copy: that file's compiled
-// code stays what it was.  Small matrices are indexed statically (no scratch: profiles/global_positioning.md).
+// runs in the fixed order the header names.  The track lists (scan / fill / sort, track_listed) and the ray steps (ray_block, ray_apply, ray_angle, ray_weight)
+// are lg_solver_steps.h's, shared with lg_bundle.hip and lg_posegraph.hip.  Small matrices are indexed statically (no scratch: profiles/global_positioning.md).
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -23,6 +23,7 @@
 #include "lg_host_call.h"
 #include "lg_kernels.h"
 #include "lg_solve3.h"
+#include "lg_solver_steps.h"
 #include "../../include/lightglue_amd.h"
 
 #pragma clang fp contract(off)
@@ -54,27 +55,9 @@ struct PosArgs {
     double* summary; int* status;
 };
 
-__device__ __forceinline__ bool pos_listed(const PosArgs& a, int j) { const int c = a.tcnt[j]; return c >= 2 && c <= LG_BA_MAX_TRACK_LENGTH; }
 __device__ __forceinline__ bool pos_stopped(const PosArgs& a, int it) { const PosHead& h = *a.head; return h.off || (h.last >= 0 && it > h.last); }
 __device__ __forceinline__ bool pos_free(int flag) { return (flag & POS_IN) && !(flag & POS_HELD); }
 __device__ __forceinline__ const double* pos_centre(const PosArgs& a, int which, int k) { return a.cen + ((long long)which * a.images + k) * 3; }
-// M = rho (I - v v^T) as its upper triangle (xx, xy, xz, yy, yz, zz)
-__device__ __forceinline__ void pos_block(const double* v, double rho, double (&M)[6]) {
-    M[0] = rho * (1.0 - v[0] * v[0]); M[1] = rho * (0.0 - v[0] * v[1]); M[2] = rho * (0.0 - v[0] * v[2]);
-    M[3] = rho * (1.0 - v[1] * v[1]); M[4] = rho * (0.0 - v[1] * v[2]); M[5] = rho * (1.0 - v[2] * v[2]);
-}
-// M x, each row (m0 x0 + m1 x1) + m2 x2
-__device__ __forceinline__ void pos_apply(const double (&M)[6], const double* x, double (&y)[3]) {
-    y[0] = (M[0] * x[0] + M[1] * x[1]) + M[2] * x[2];
-    y[1] = (M[1] * x[0] + M[3] * x[1]) + M[4] * x[2];
-    y[2] = (M[2] * x[0] + M[4] * x[1]) + M[5] * x[2];
-}
-// v . e and phi = atan2(|e - (v . e) v|, v . e)
-__device__ __forceinline__ double pos_angle(const double* v, const double (&e)[3], double& ve) {
-    ve = (v[0] * e[0] + v[1] * e[1]) + v[2] * e[2];
-    const double r[3] = {e[0] - ve * v[0], e[1] - ve * v[1], e[2] - ve * v[2]};
-    return atan2(sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]), ve);
-}
 
 // ------------------------------------------------------------------ records
 __global__ __launch_bounds__(POS_THREADS) void pos_init_kernel(PosArgs a) {
@@ -145,50 +128,13 @@ __global__ __launch_bounds__(POS_THREADS) void pos_count_kernel(PosArgs a) {
     a.node_state[v] = (unsigned char)state;
 }
 
-// ONE workgroup: the exclusive scan of the listed tracks' counts (integers: the order of the additions changes nothing)
+// the lists of the listed tracks (lg_solver_steps.h): ONE workgroup scans; one lane per node fills (states 4 / 3); one lane per track sorts
 __global__ __launch_bounds__(POS_SCAN_THREADS) void pos_scan_kernel(PosArgs a) {
     __shared__ int sh[POS_SCAN_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int share = (a.tracks + POS_SCAN_THREADS - 1) / POS_SCAN_THREADS;
-    const int beg = min((int)threadIdx.x * share, a.tracks), end = min(beg + share, a.tracks);
-    int mine = 0;
-    for (int j = beg; j < end; ++j) if (pos_listed(a, j)) mine += a.tcnt[j];
-    int inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += sh[w];
-    int at = base + inc - mine;                            // the sum of all counts is at most nodes: every node is counted once
-    for (int j = beg; j < end; ++j) if (pos_listed(a, j)) { a.toff[j] = at; at += a.tcnt[j]; }
+    track_scan<POS_SCAN_THREADS>(a, sh);
 }
-
-__global__ __launch_bounds__(POS_THREADS) void pos_fill_kernel(PosArgs a) {
-    const int v = blockIdx.x * POS_THREADS + threadIdx.x;
-    if (v >= a.nodes) return;
-    if (a.node_state[v] != 1) return;
-    const int j = (int)a.track_id[v], cnt = a.tcnt[j];     // a candidate: 0 <= j < tracks
-    if (cnt < 2) { a.node_state[v] = 4; return; }
-    if (cnt > LG_BA_MAX_TRACK_LENGTH) { a.node_state[v] = 3; return; }
-    const int at = atomicAdd(a.tcur + j, 1);
-    if (at < cnt) a.list[a.toff[j] + at] = v;              // always: cnt candidates carry this track; toff + cnt <= nodes
-}
-
-__global__ __launch_bounds__(POS_THREADS) void pos_sort_kernel(PosArgs a) {
-    const int j = blockIdx.x * POS_THREADS + threadIdx.x;
-    if (j >= a.tracks || !pos_listed(a, j)) return;
-    const int len = a.tcnt[j];
-    int* lst = a.list + a.toff[j];
-    for (int q = 1; q < len; ++q) {                        // ascending node order, whatever order the atomics left; len <= 1024
-        const int key = lst[q];
-        int r = q - 1;
-        while (r >= 0 && lst[r] > key) { lst[r + 1] = lst[r]; --r; }
-        lst[r + 1] = key;
-    }
-    int* img = a.limg + a.toff[j];
-    for (int q = 0; q < len; ++q) img[q] = lst[q] / a.n;
-}
+__global__ __launch_bounds__(POS_THREADS) void pos_fill_kernel(PosArgs a) { track_fill<4, 3>(a, blockIdx.x * POS_THREADS + threadIdx.x); }
+__global__ __launch_bounds__(POS_THREADS) void pos_sort_kernel(PosArgs a) { track_sort(a, blockIdx.x * POS_THREADS + threadIdx.x); }
 
 // ------------------------------------------------------------------ who takes part: ONE workgroup, lane i = image i, tracks and nodes strided
 // The gauge: at least two held images that pass the rules, not all at one centre; otherwise nothing is solved.  Peeling: removal is monotone, so the set left
@@ -214,7 +160,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_take_part_kernel(PosArgs a) {
         return;
     }
     in[i] = (flag & POS_OK) ? 1 : 0;
-    for (int j = i; j < a.tracks; j += POS_THREADS) a.tin[j] = pos_listed(a, j) ? TRK_IN : TRK_OUT;
+    for (int j = i; j < a.tracks; j += POS_THREADS) a.tin[j] = track_listed(a, j) ? TRK_IN : TRK_OUT;
     __syncthreads();
     for (;;) {
         int changed = 0;
@@ -285,31 +231,22 @@ __global__ __launch_bounds__(POS_THREADS) void pos_points_kernel(PosArgs a, int 
         double rho = 1.0;
         if (it > 0) {
             const double e[3] = {X[0] - c[0], X[1] - c[1], X[2] - c[2]};
-            double ve;
-            const double ee = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2], r = pos_angle(ray, e, ve) / s_it;
-            rho = 1.0 / fmax(ee, 1e-12) / (1.0 + r * r);
+            rho = ray_weight(ray, e, s_it);
         }
         a.rho[v] = rho;
         double M[6];
-        pos_block(ray, rho, M);
+        ray_block(ray, rho, M);
 #pragma unroll
         for (int e = 0; e < 6; ++e) V[e] += M[e];
         if (flag & POS_HELD) {
             double y[3];
-            pos_apply(M, c, y);
+            ray_apply(M, c, y);
 #pragma unroll
             for (int e = 0; e < 3; ++e) G[e] += y[e];
         }
     }
     double Vi[3][3];
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0};
-        double x[3];
-        ok = tri_solve3(V, e, x) && ok;
-        Vi[0][c] = x[0]; Vi[1][c] = x[1]; Vi[2][c] = x[2];
-    }
+    const bool ok = tri_inverse3(V, Vi);
     double* vo = a.Vinv + (long long)j * 9;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -361,7 +298,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_reduce_kernel(PosArgs a, int 
                 if (a.tin[j] == TRK_IN) {
                     len = a.tcnt[j]; off = a.toff[j];
                     double M[6];
-                    pos_block(a.ray + v * 3, a.rho[v], M);
+                    ray_block(a.ray + v * 3, a.rho[v], M);
                     const double* Vi = a.Vinv + (long long)j * 9;
                     const double* g = a.g + (long long)j * 3;
                     const double Mf[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
@@ -391,7 +328,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_reduce_kernel(PosArgs a, int 
                     if (k < b) continue;
                     const int v = l < POS_STAGE ? sNode[q][l] : a.list[off + l];
                     double M[6];
-                    pos_block(a.ray + (long long)v * 3, a.rho[v], M);
+                    ray_block(a.ray + (long long)v * 3, a.rho[v], M);
                     const double Mf[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
 #pragma unroll
                     for (int r = 0; r < 3; ++r)
@@ -496,8 +433,8 @@ __global__ __launch_bounds__(POS_THREADS) void pos_update_kernel(PosArgs a, int 
         const int v = a.list[off + q], k = a.limg[off + q];
         if (!pos_free(a.iflag[k])) continue;
         double M[6], y[3];
-        pos_block(a.ray + (long long)v * 3, a.rho[v], M);
-        pos_apply(M, pos_centre(a, now, k), y);
+        ray_block(a.ray + (long long)v * 3, a.rho[v], M);
+        ray_apply(M, pos_centre(a, now, k), y);
 #pragma unroll
         for (int e = 0; e < 3; ++e) acc[e] += y[e];
     }
@@ -513,7 +450,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_classify_kernel(PosArgs a) {
     const float nanf_ = __builtin_nanf("");
     float* xo = a.xyz + (long long)j * 3;
     xo[0] = nanf_; xo[1] = nanf_; xo[2] = nanf_;
-    if (!pos_listed(a, j)) return;                          // its nodes carry 3 or 4 already
+    if (!track_listed(a, j)) return;                          // its nodes carry 3 or 4 already
     const PosHead h = *a.head;
     const int len = a.tcnt[j], off = a.toff[j], tin = a.tin[j];
     if (tin != TRK_IN || h.pos_bad) {
@@ -531,7 +468,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_classify_kernel(PosArgs a) {
         const double* c = pos_centre(a, h.csel, k);
         const double e[3] = {X[0] - c[0], X[1] - c[1], X[2] - c[2]};
         double ve;
-        const double phi = pos_angle(a.ray + (long long)v * 3, e, ve) * POS_DEG;
+        const double phi = ray_angle(a.ray + (long long)v * 3, e, ve) * POS_DEG;
         const bool inlier = ve > 0.0 && phi <= a.max_angle;
         a.angle_error[v] = (float)phi;
         a.node_state[v] = inlier ? 1 : 7;
@@ -575,7 +512,7 @@ __global__ __launch_bounds__(POS_THREADS) void pos_output_kernel(PosArgs a) {
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) o[4 * r + e] = ok ? p[4 * r + e] : nanf_;
-        o[4 * r + 3] = !ok ? nanf_ : held ? p[4 * r + 3] : posed ? (float)(-((R[3 * r] * c[0] + R[3 * r + 1] * c[1]) + R[3 * r + 2] * c[2])) : nanf_;
+        o[4 * r + 3] = !ok ? nanf_ : held ? p[4 * r + 3] : posed ? (float)minus_Rc(R, c, r) : nanf_;
     }
     a.image_state[k] = (unsigned char)(!ok ? 4 : held ? 1 : posed ? 0 : in ? 5 : (f & POS_LOST) ? 3 : 2);
 }
@@ -605,25 +542,22 @@ int lg_positioning_solve(const lg_positioning_io* io, void* hip_stream) {
     if (const int rc = check_workspace(stage, "lg_positioning_workspace_bytes", io->workspace, io->workspace_bytes, L.total)) return rc;
 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    char* ws = static_cast<char*>(io->workspace);
+    const Carved ws(io->workspace);
     PosArgs a{};
     a.n = io->n; a.images = io->images; a.nodes = (int)L.nodes; a.tracks = io->tracks; a.iterations = io->num_iterations;
     a.scale = io->angle_scale * (3.14159265358979323846 / 180.0); a.max_angle = io->max_angle_error;
     a.kpts = io->kpts; a.num = io->num; a.track_id = reinterpret_cast<const long long*>(io->track_id); a.cameras = io->cameras; a.poses = io->poses;
     a.constant = io->constant_pose;
-    auto ints = [&](long long at) { return reinterpret_cast<int*>(ws + at); };
-    auto f64 = [&](long long at) { return reinterpret_cast<double*>(ws + at); };
-    a.head = reinterpret_cast<PosHead*>(ws + L.head); a.rec = reinterpret_cast<PosImage*>(ws + L.rec); a.iflag = ints(L.iflag); a.cen = f64(L.cen); a.S = f64(L.S);
-    a.list = ints(L.list); a.limg = ints(L.limg); a.ray = f64(L.ray); a.rho = f64(L.rho);
-    a.tcnt = ints(L.tcnt); a.toff = ints(L.toff); a.tcur = ints(L.tcur); a.tin = ints(L.tin); a.treach = ints(L.treach);
-    a.X = f64(L.X); a.Vinv = f64(L.Vinv); a.g = f64(L.g);
+    a.head = ws.as<PosHead>(L.head); a.rec = ws.as<PosImage>(L.rec); a.iflag = ws.ints(L.iflag); a.cen = ws.f64(L.cen); a.S = ws.f64(L.S);
+    a.list = ws.ints(L.list); a.limg = ws.ints(L.limg); a.ray = ws.f64(L.ray); a.rho = ws.f64(L.rho);
+    a.tcnt = ws.ints(L.tcnt); a.toff = ws.ints(L.toff); a.tcur = ws.ints(L.tcur); a.tin = ws.ints(L.tin); a.treach = ws.ints(L.treach);
+    a.X = ws.f64(L.X); a.Vinv = ws.f64(L.Vinv); a.g = ws.f64(L.g);
     a.poses_out = io->poses_out; a.xyz = io->xyz; a.points3d = io->points3d; a.track_id_out = reinterpret_cast<long long*>(io->track_id_out);
     a.node_state = io->node_state; a.image_state = io->image_state; a.angle_error = io->angle_error; a.summary = io->summary; a.status = io->status;
 
     auto blocks = [](long long items) { return dim3((unsigned)((items + POS_THREADS - 1) / POS_THREADS)); };
     const dim3 th(POS_THREADS);
-    const int K = io->images, T = io->tracks, n = io->num_iterations, dim = 3 * K;
-    const int panels = (dim + CH_NB - 1) / CH_NB, tiles = (dim + 1 + CH_NB - 1) / CH_NB;
+    const int K = io->images, T = io->tracks, n = io->num_iterations;
     hipLaunchKernelGGL(pos_init_kernel, blocks(std::max<long long>(K, T)), th, 0, s, a);
     if (L.nodes) hipLaunchKernelGGL(pos_count_kernel, blocks(L.nodes), th, 0, s, a);
     if (T) hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(POS_SCAN_THREADS), 0, s, a);
@@ -634,10 +568,10 @@ int lg_positioning_solve(const lg_positioning_io* io, void* hip_stream) {
         const int halvings = std::max(0, n - 6 - it);
         if (T) hipLaunchKernelGGL(pos_points_kernel, blocks(T), th, 0, s, a, it, a.scale * std::ldexp(1.0, halvings));
         hipLaunchKernelGGL(pos_reduce_kernel, dim3(K), th, 0, s, a, it);
-        for (int p = 0; p < panels; ++p) {
+        for_cholesky_panels(3 * K, 1, [&](int p, int tiles_below) {
             hipLaunchKernelGGL(pos_chol_diag_kernel, dim3(1), th, 0, s, a, it, p);
-            hipLaunchKernelGGL(pos_chol_rows_kernel, dim3(tiles - p), th, 0, s, a, it, p);
-        }
+            hipLaunchKernelGGL(pos_chol_rows_kernel, dim3(tiles_below), th, 0, s, a, it, p);
+        });
         hipLaunchKernelGGL(pos_centres_kernel, dim3(1), th, 0, s, a, it, halvings == 0 ? 1 : 0);
         if (T) hipLaunchKernelGGL(pos_update_kernel, blocks(T), th, 0, s, a, it);
     }

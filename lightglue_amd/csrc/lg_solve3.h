@@ -1,5 +1,5 @@
-// lightglue_amd — THE 3 x 3 elimination of the triangulator and the bundle adjuster (include/lightglue_amd.h, lg_triangulate: "Start"): device code, static
-// indices only (no scratch).
+// lightglue_amd — THE 3 x 3 elimination of the triangulator, the bundle adjuster and the positioner (include/lightglue_amd.h, lg_triangulate: "Start"), and
+// the inverse by columns the two points kernels take from it: device code, static indices only (no scratch).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,19 @@ __device__ __forceinline__ bool tri_solve3(const double (&s)[6], const double (&
     x[1] = (M[1][3] - M[1][2] * x[2]) / M[1][1];
     x[0] = ((M[0][3] - M[0][1] * x[1]) - M[0][2] * x[2]) / M[0][0];
     return ok && isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
+}
+
+// Mi = M^-1 of the same M, column by column through tri_solve3; false if any column's elimination fails (every column is still written)
+__device__ __forceinline__ bool tri_inverse3(const double (&s)[6], double (&Mi)[3][3]) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0};
+        double x[3];
+        ok = tri_solve3(s, e, x) && ok;
+        Mi[0][c] = x[0]; Mi[1][c] = x[1]; Mi[2][c] = x[2];
+    }
+    return ok;
 }
 
 }  // namespace lg

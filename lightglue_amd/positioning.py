@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import _cabi, _call
-from .bundle import as_constant
+from .bundle import as_constant, as_track_id
 from .relpose import as_cameras
 from .triangulate import as_poses
 
@@ -32,14 +32,10 @@ def as_labels(tracks, K: int, N: int, device):
         tracks = (tracks["track_id"], tracks["num_tracks"])
     if not isinstance(tracks, (tuple, list)) or len(tracks) != 2:
         raise ValueError("tracks must be the Triangulator's dict or a tuple (track_id [K, N], T)")
-    tid, T = torch.as_tensor(tracks[0]), tracks[1]
-    if tuple(tid.shape) != (K, N):
-        raise ValueError(f"track_id must have shape [{K}, {N}], got {tuple(tid.shape)}")
-    if tid.dtype.is_floating_point or tid.dtype is torch.bool:
-        raise ValueError(f"track_id must hold integers, got {tid.dtype}")
+    tid, T = as_track_id(tracks[0], K, N, device), tracks[1]
     if isinstance(T, bool) or torch.is_tensor(T) or int(T) != T or not 0 <= int(T) <= K * N // 2:
         raise ValueError(f"the number of tracks must be an integer in [0, K N / 2 = {K * N // 2}] (a track has at least two observations), got {T!r}")
-    return tid.detach().to(device=device, dtype=torch.int64).contiguous(), int(T)
+    return tid, int(T)
 
 
 class GlobalPositioner(nn.Module):

@@ -1,9 +1,11 @@
 // Checks the host side the stateless entry points share (lightglue_amd/csrc/lg_host_call.h) without a GPU: every rule below is restated from
 // include/lightglue_amd.h, then asserted over a grid — the LG_FLAG_INDEXED refusal, the workspace refusals, the keypoint-count envelope, the three workspace
 // layouts (piece by piece: every piece at a 256-byte aligned offset behind the one before it, and the byte totals the entry points have always returned) and
-// the cut of a pair list into launches — and the opening of a call of the three estimators (check_estimator_call): every refusal in its order, with the exact
+// the cut of a pair list into launches, the solvers' byte totals and envelope refusals, the "> 0 and finite" test, the carving of typed pointers and the
+// panel loop of the Cholesky — and the opening of a call of the three estimators (check_estimator_call): every refusal in its order, with the exact
 // message, per entry point.  Stand-alone: built and run by tests/test_host_call_cpu.py; for a sanitizer run add -fsanitize=address,undefined.
 // Exit status 0 and "ok <checks>" on success, the first violated rule otherwise.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -127,6 +129,64 @@ void layout_rules() {
     CHECK(sift_filter_layout(2, 64, 48, 64, S) && S.total == 49408, "sift total %lld", S.total);
     CHECK(!sift_filter_layout(0, 1, 1, 1, S) && !sift_filter_layout(65536, 1, 1, 1, S) && !sift_filter_layout(1, -1, 1, 1, S) && !sift_filter_layout(1, (1 << 24) + 1, 1, 1, S), "sift counts");
     CHECK(!sift_filter_layout(1, 1, 0, 1, S) && !sift_filter_layout(1, 1, 65536, 65536, S) && !sift_filter_layout(65535, 1, 46340, 46340, S), "sift rasters");
+}
+
+// The solvers' layouts (lg_bundle_adjust, _robust, _focal, lg_posegraph_solve, lg_positioning_solve): the byte totals the entry points returned before the
+// solver steps were written once (computed from that commit's header), at (images, n, tracks) = (6, 96, 50) and (256, 16, 900), pairs = 15 and 900; and the
+// envelope's refusals
+void solver_layout_rules() {
+    struct { long long images, n, tracks, pairs, ba, robust, focal, pg, pos; } sizes[] = {
+        {6, 96, 50, 15, 26624, 26880, 31232, 6400, 35328}, {256, 16, 900, 900, 19141120, 19144960, 25981184, 4802560, 5062656}};
+    BaLayout B; BaRobustLayout R; BaFocalLayout F; PgLayout G; PosLayout Q;
+    for (const auto& c : sizes) {
+        CHECK(ba_layout(c.images, c.n, c.tracks, 0, B) == nullptr && B.total == c.ba, "ba total %lld", B.total);
+        CHECK(ba_robust_layout(c.images, c.n, c.tracks, 0, R) == nullptr && R.total == c.robust && R.tmov == c.ba, "robust total %lld", R.total);
+        CHECK(ba_focal_layout(c.images, c.n, c.tracks, 0, F) == nullptr && F.total == c.focal, "focal total %lld", F.total);
+        CHECK(pg_layout(c.images, c.pairs, 0, G) == nullptr && G.total == c.pg, "pg total %lld", G.total);
+        CHECK(pos_layout(c.images, c.n, c.tracks, 0, Q) == nullptr && Q.total == c.pos, "pos total %lld", Q.total);
+    }
+    const auto says_why = [](const char* why, const char* word) { return why && std::strstr(why, word); };
+    // images = 0, images = 257, tracks > images x n / 2, an undefined flag bit
+    CHECK(says_why(ba_layout(0, 96, 50, 0, B), "images must lie in [1, LG_BA_MAX_IMAGES]") && says_why(ba_layout(257, 16, 900, 0, B), "images must lie in [1, LG_BA_MAX_IMAGES]"), "ba images");
+    CHECK(says_why(ba_layout(6, 96, 289, 0, B), "tracks must lie in") && !ba_layout(6, 96, 288, 0, B) && says_why(ba_layout(6, 96, 50, 1u, B), "undefined flag bits"), "ba tracks, flags");
+    CHECK(says_why(ba_robust_layout(0, 96, 50, 0, R), "images must lie in") && says_why(ba_robust_layout(257, 16, 900, 0, R), "images must lie in") &&
+          says_why(ba_robust_layout(6, 96, 289, 0, R), "tracks must lie in") && says_why(ba_robust_layout(6, 96, 50, 1u << 31, R), "undefined flag bits"), "robust envelope");
+    CHECK(says_why(ba_focal_layout(0, 96, 50, 0, F), "images must lie in") && says_why(ba_focal_layout(257, 16, 900, 0, F), "images must lie in") &&
+          says_why(ba_focal_layout(6, 96, 289, 0, F), "tracks must lie in") && says_why(ba_focal_layout(6, 96, 50, 2u, F), "undefined flag bits"), "focal envelope");
+    CHECK(says_why(pos_layout(0, 96, 50, 0, Q), "images must lie in [2, LG_BA_MAX_IMAGES]") && says_why(pos_layout(257, 16, 900, 0, Q), "images must lie in [2, LG_BA_MAX_IMAGES]") &&
+          says_why(pos_layout(6, 96, 289, 0, Q), "tracks must lie in") && !pos_layout(6, 96, 288, 0, Q) && says_why(pos_layout(6, 96, 50, 1u, Q), "undefined flag bits"), "pos envelope");
+    CHECK(says_why(pg_layout(0, 15, 0, G), "images must lie in [2, LG_BA_MAX_IMAGES]") && says_why(pg_layout(257, 900, 0, G), "images must lie in [2, LG_BA_MAX_IMAGES]") &&
+          says_why(pg_layout(6, 15, 1u, G), "undefined flag bits"), "pg envelope");
+    // the "> 0 (and finite)" test of the settings
+    CHECK(positive(1e-300) && positive(1.7976931348623157e308) && !positive(0.0) && !positive(-1.0) && !positive(HUGE_VAL) && !positive(std::nan("")), "positive");
+    CHECK(!pos_settings_error(12, 1.0, 2.0) && pos_settings_error(12, 0.0, 2.0) && pg_settings_error(6, 12, 0, -1, 1.0, HUGE_VAL, 1.0) &&
+          ba_robust_settings_error(LG_BA_LOSS_HUBER, std::nan(""), 0, 4.0) && !ba_robust_settings_error(LG_BA_LOSS_SQUARED, 0.0, 0, 0.0), "settings");
+    // typed pointers at a layout's offsets
+    alignas(8) char ws[64];
+    const Carved w(ws);
+    CHECK((char*)w.ints(8) == ws + 8 && (char*)w.f64(16) == ws + 16 && (char*)w.as<long long>(24) == ws + 24, "carving");
+}
+
+// The panel loop of the blocked Cholesky: per panel of 48 columns, the panel and the row tiles from its own down to the last (with the right-hand sides' rows)
+void cholesky_panel_rules() {
+    struct { int dim, nrhs, panels, first; } cases[] = {{48, 1, 1, 2}, {49, 1, 2, 2}, {768, 3, 16, 17}, {1, 1, 1, 1}, {47, 1, 1, 1}, {96, 1, 2, 3}, {1792, 1, 38, 38}};
+    for (const auto& c : cases) {
+        int next = 0;
+        for_cholesky_panels(c.dim, c.nrhs, [&](int panel, int tiles_below) {
+            CHECK(panel == next && tiles_below == c.first - panel && tiles_below >= 1, "dim %d nrhs %d: panel %d with %d tiles", c.dim, c.nrhs, panel, tiles_below);
+            ++next;
+        });
+        CHECK(next == c.panels, "dim %d: %d panels", c.dim, next);
+    }
+    std::vector<int> seen;
+    for_cholesky_panels(49, 1, [&](int p, int below) { seen.push_back(p); seen.push_back(below); });
+    CHECK(seen == std::vector<int>({0, 2, 1, 1}), "dim 49: (0, 2), (1, 1)");
+    seen.clear();
+    for_cholesky_panels(48, 1, [&](int p, int below) { seen.push_back(p); seen.push_back(below); });
+    CHECK(seen == std::vector<int>({0, 2}), "dim 48: (0, 2)");
+    seen.clear();
+    for_cholesky_panels(768, 3, [&](int p, int below) { seen.push_back(p); seen.push_back(below); });
+    CHECK(seen.size() == 32 && seen[0] == 0 && seen[1] == 17 && seen[30] == 15 && seen[31] == 2, "dim 768, 3 right-hand sides: (0, 17) ... (15, 2)");
 }
 
 void launch_rules() {
@@ -274,6 +334,8 @@ int main() {
     workspace_rules();
     keypoint_rules();
     layout_rules();
+    solver_layout_rules();
+    cholesky_panel_rules();
     launch_rules();
     std::printf("ok %lld\n", g_checks);
     return 0;

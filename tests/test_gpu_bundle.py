@@ -144,6 +144,23 @@ def test_too_long_track_and_shared_labels():
     assert ((got["node_state"] == B.ACTIVE) == (alone["node_state"] == B.ACTIVE)).all()
 
 
+# ---------------------------------------------------------------------- 3c. more tracks than the scan's workgroup has threads
+def test_more_tracks_than_scan_threads():
+    """1030 two-view tracks over 6 x 400 nodes: each of the scan's 1024 threads owns ceil(1030 / 1024) = 2 consecutive tracks (the last 509 own none), and
+    tracks 500 and 1027 lose one observation each, so two unlisted tracks sit between listed ones and their offsets must not move.  Two iterations."""
+    sc = B.scene(6, 400, 1030, 201, hi=2)
+    tid, left = sc["track_id"].copy(), []
+    for j in (500, 1027):
+        (k, i), other = sorted(sc["planted"]["rows"][j].items())
+        tid[k, i] = -1
+        left.append(other)
+    inp = dict(B.oracle_input(sc), track_id=tid)
+    want = B.adjust(inp, num_iterations=2)
+    assert len(inp["xyz"]) == 1030 > 1024 and all(want["node_state"][k, i] == B.SHORT for k, i in left)          # on the definition, before the GPU is read
+    assert want["num_observations"] == 2056 and (want["node_state"] == B.SHORT).sum() == 2 and want["num_accepted"] == 2
+    check(run(inp, num_iterations=2), want, inp, "1030 tracks")
+
+
 # ---------------------------------------------------------------------- 4. invariance
 def test_outputs_are_the_same_bits(main):
     inp = B.GPU_SCENES["main"]()

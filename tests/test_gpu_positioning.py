@@ -118,6 +118,23 @@ def test_the_envelope_256_images():
     check(run(inp, num_iterations=6), want, inp, "K = 256", 6)
 
 
+def test_more_tracks_than_scan_threads():
+    """1030 two-view tracks over 6 x 400 nodes (400 rows per image: 352 would run the planting out of rows): each of the scan's 1024 threads owns
+    ceil(1030 / 1024) = 2 consecutive tracks (the last 509 own none), and tracks 500 and 1027 lose one observation each, so two unlisted tracks sit between
+    listed ones and their offsets must not move"""
+    sc = P.scene(6, 400, 1030, seed=3, lo=2, hi=2)
+    tid, left = sc["track_id"].copy(), []
+    for j in (500, 1027):
+        (k, i), other = sorted(sc["planted"]["rows"][j].items())
+        tid[k, i] = -1
+        left.append(other)
+    inp = dict(P.oracle_input(sc), track_id=tid)
+    want = P.solve(inp, num_iterations=6)
+    assert inp["T"] == 1030 > 1024 and all(want["node_state"][k, i] == P.PEELED for k, i in left)                # on the definition, before the GPU is read
+    assert want["num_posed"] == 6 and want["num_points"] == 1028 and (want["node_state"] == P.PEELED).sum() == 2 and want["positions_ok"]
+    check(run(inp, num_iterations=6), want, inp, "1030 tracks", 6)
+
+
 # ---------------------------------------------------------------------- 2. every edge
 def extras_scene():
     """scene(8, 32, 48) with ragged num_keypoints (dead rows that carry labels), four tracks with a second row in one of their images (0.3 px beside the first)

@@ -93,7 +93,8 @@ def test_null_workspace_is_refused():
 
 def test_refusals_and_layouts_hold_on_the_whole_grid(tmp_path):
     """the header is host-only C++17: the stand-alone program is built as plain C++ with the host compiler (no device pass) and walks the refusal table, the
-    three workspace layouts piece by piece and the cut of a pair list into launches.  (For a sanitizer run of the header, build the same program with
+    three workspace layouts piece by piece, the solvers' byte totals and envelopes, the Cholesky's panel loop and the cut of a pair list into launches.
+    (For a sanitizer run of the header, build the same program with
     -fsanitize=address,undefined.)"""
     cxx = shutil.which("hipcc") or shutil.which("c++")
     assert cxx, "needs a C++17 host compiler (hipcc or c++)"
