@@ -1,13 +1,18 @@
-"""The mechanics of one call over feature stores, written once for `LightGlue`, `NearestNeighborMatcher` and `TwoViewVerifier` (each module keeps its class:
-configuration, the launch path and the public methods): what a caller reads of one side (`build_side`; `normalise_side` is the engine's reading), the opening
-of a call (`sides`, `batch_sides` for `forward`, `store_pairs` and `pair_list` for a pair list), how a pair list is cut into engine calls (`plan_pair_chunks`),
-the output set of a call (`Outputs`) and its assembly into the reference's dict (`ragged_outputs`, `DeferredMatches`).  Plain tensor and pointer arithmetic:
-nothing here launches a kernel of the library's.
+"""The mechanics of one call over feature stores, written once for `LightGlue`, `NearestNeighborMatcher` and the seven geometry classes (each module keeps its
+class: configuration, the io struct of its entry point and the public methods): what a caller reads of one side (`build_side`; `normalise_side` is the engine's
+reading), the opening of a call (`sides`, `batch_sides` for `forward`, `store_pairs`, `pair_list` and `device_index` for a pair list), how a pair list is cut into
+engine calls (`plan_pair_chunks`), the output set of a call (`Outputs`) and its assembly into the reference's dict (`ragged_outputs`, `DeferredMatches`); for
+the nearest-neighbour matcher and the geometry classes also the setting checks (`ransac_settings`, `int_in`, `positive`), THE device call (`device_call`:
+device, stream, library, workspace, entry point), the index pointers (`index_ptrs`), the summary | status buffer (`summary_status`) and the per-item status
+error (`raise_on_status`, `raise_with_outputs`).  `_readers.py` holds the readers of cameras, poses and tracks.  Plain tensor and pointer arithmetic:
+`device_call` is the only place that enters the library, through the entry point it is given.
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 
+import numpy as np
 import torch
 
 from . import _cabi
@@ -19,15 +24,18 @@ def require_gpu(device, what: str = "keypoints") -> None:
         raise RuntimeError(f"lightglue_amd runs on MI355X (ROCm device type 'cuda') only; there is no CPU fallback. Got {what} on {device}.")
 
 
-def raise_on_status(status) -> None:
-    """Per-pair status codes (lg_forward_io.status, in the order of the call's pair list) -> LightGlueAmdError naming the pairs."""
+PAIR_STATUS = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
+               _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
+               _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched",
+               _cabi.LG_ERR_CAMERA: "a camera whose focal length is not finite and > 0, or whose principal point is not finite (LG_ERR_CAMERA)"}
+
+
+def raise_on_status(status, noun: str = "pair", what: dict = PAIR_STATUS) -> None:
+    """Per-item status codes (lg_forward_io.status, in the order of the call's pair list; the solvers' status per image) -> LightGlueAmdError naming the
+    items as `noun` with the texts of the table `what`."""
     bad = [(i, int(c)) for i, c in enumerate(status) if int(c) != _cabi.LG_OK]
     if bad:
-        what = {_cabi.LG_ERR_RANGE: "values outside the f16 operand range (|x| >= 65504, inf or NaN; LG_ERR_RANGE)",
-                _cabi.LG_ERR_DEVICE: "an internal device-side wait expired (LG_ERR_DEVICE)",
-                _cabi.LG_ERR_INDEX: "an image index outside its feature store (LG_ERR_INDEX): the pair was not matched",
-                _cabi.LG_ERR_CAMERA: "a camera whose focal length is not finite and > 0, or whose principal point is not finite (LG_ERR_CAMERA)"}
-        raise _cabi.LightGlueAmdError("; ".join(f"pair {i}: {what.get(c, c)}" for i, c in bad[:8]))
+        raise _cabi.LightGlueAmdError("; ".join(f"{noun} {i}: {what.get(c, c)}" for i, c in bad[:8]))
 
 
 def ragged_outputs(host, mlist, mscores, stop):
@@ -68,6 +76,21 @@ def ransac_settings(threshold, num_hypotheses, seed) -> tuple:
     return float(threshold), int(num_hypotheses), int(seed)
 
 
+def int_in(name: str, value, lo: int, hi: int, refuse_bool: bool = False, what: str = None) -> int:
+    """THE check of an integer setting in [lo, hi]: int(value), or the ValueError `{name} {what}, got ...` (what: "must be an integer in [lo, hi]" unless given).
+    1.0 passes, "3" does not; True passes as 1 unless refuse_bool."""
+    if (refuse_bool and isinstance(value, bool)) or int(value) != value or not lo <= int(value) <= hi:
+        raise ValueError(f"{name} {what or f'must be an integer in [{lo}, {hi}]'}, got {value!r}")
+    return int(value)
+
+
+def positive(name: str, value, suffix: str = "") -> float:
+    """THE check of a setting that is finite and > 0: float(value), or the ValueError `{name} must be > 0{suffix}, got ...`."""
+    if not 0.0 < float(value) < float("inf"):
+        raise ValueError(f"{name} must be > 0{suffix}, got {value!r}")
+    return float(value)
+
+
 def as_matches0(result, P: int, N: int, device) -> torch.Tensor:
     """matches0 [P, N] as the C ABI reads it — int64, contiguous, on `device` — from a matcher's result: its dict, a `DeferredMatches` or the tensor itself.
     A tensor that already qualifies passes through untouched."""
@@ -88,14 +111,46 @@ def ragged_matches(mask: torch.Tensor, verified: torch.Tensor, counts) -> list:
     return [listed[b, :c] for b, c in enumerate(counts)]
 
 
-def raise_with_outputs(status, out: dict) -> dict:
-    """`out`, or `raise_on_status`'s error carrying it as `.outputs`: the pairs with status LG_OK are complete."""
+def raise_with_outputs(status, out: dict, noun: str = "pair", what: dict = PAIR_STATUS) -> dict:
+    """`out`, or `raise_on_status`'s error carrying it as `.outputs`: the items with status LG_OK are complete."""
     try:
-        raise_on_status(status)
+        raise_on_status(status, noun, what)
     except _cabi.LightGlueAmdError as err:
         err.outputs = out
         raise
     return out
+
+
+def index_ptrs(index) -> tuple:
+    """(index0, index1) of an io struct: the addresses of the two rows of the int32 [2, P] index (`store_pairs`), (None, None) without one."""
+    return (None, None) if index is None else (index[0].data_ptr(), index[1].data_ptr())
+
+
+def summary_status(n: int, K: int, device) -> tuple:
+    """The solvers' "n doubles of summary | K int32 of status" in ONE zeroed allocation: (the status [K] on `device`, the summary's address, the status's
+    address, read); read() is THE host sync of the call and gives (summary [n] float64, status [K] int32) as numpy views of one host copy."""
+    small = torch.zeros((2 * n + K,), device=device, dtype=torch.int32)
+
+    def read():
+        host = small.cpu().numpy()
+        return host[:2 * n].view(np.float64), host[2 * n:]
+    return small[2 * n:], small.data_ptr(), small.data_ptr() + 8 * n, read
+
+
+def device_call(device, entry: str, sizer: str, size_args: tuple, make_io, skip: bool = False, floor: int = 256):
+    """THE device call of the nearest-neighbour matcher and the geometry classes: on `device` and its current stream, the workspace of
+    lib.<sizer>(*size_args) bytes (at least `floor`: 256 everywhere but for the matcher, whose scratch is the stores' rows), io = make_io(workspace address,
+    workspace bytes), lib.<entry>(io, stream) through `_cabi.check`.  A size of -1 (outside the envelope) reaches the entry point with 0 bytes: its message
+    is the error the caller sees.  skip: nothing is called (the matcher and the three estimators over an empty pair list).  Returns the stream."""
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        if not skip:
+            lib = _cabi.load()
+            nbytes = getattr(lib, sizer)(*size_args)
+            ws = torch.empty((max(nbytes, floor),), device=device, dtype=torch.uint8)
+            io = make_io(_ptr(ws), max(nbytes, 0))
+            _cabi.check(getattr(lib, entry)(C.byref(io), C.c_void_p(stream.cuda_stream)))
+    return stream
 
 
 def plan_pair_chunks(P: int, n0: int, n1: int, max_rows: int = _cabi.LG_MAX_ROWS, max_sim_elems: int = _cabi.LG_MAX_SIM_ELEMS) -> list:
@@ -259,8 +314,12 @@ def store_pairs(feats0: dict, pairs, feats1, validate: bool, key: str = "keypoin
     K0 = int(feats0[key].shape[0])
     K1 = K0 if same else int(feats1[key].shape[0])
     pt = pair_list(pairs, K0, K1, validate)
-    P = int(pt.shape[0])
-    return same, P, pt.to(device=feats0[key].device, dtype=torch.int32).t().contiguous() if P else None
+    return same, int(pt.shape[0]), device_index(pt, feats0[key].device)
+
+
+def device_index(pt: torch.Tensor, device):
+    """A pair list [P, 2] as the int32 [2, P] tensor index0 | index1 on `device`, None for an empty list."""
+    return pt.to(device=device, dtype=torch.int32).t().contiguous() if pt.shape[0] else None
 
 
 # ---------------------------------------------------------------------- the outputs of a call

@@ -6,14 +6,13 @@ of pairs in ONE call with ONE host synchronisation, and every problem's result i
 the seed alone."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _cabi, _call
-from .relpose import as_cameras
+from ._readers import as_cameras
 
 
 class _Store1:
@@ -86,25 +85,16 @@ class AbsolutePoseEstimator(nn.Module):
         ints = torch.empty((2 * G + 2 * P,), device=device, dtype=torch.int32)   # num_inliers [G] | best_hypothesis [G] | pair_num_inliers [P] | status [P]
         R, t = torch.empty((G, 3, 3), device=device, dtype=torch.float32), torch.empty((G, 3), device=device, dtype=torch.float32)
         cand = torch.empty((G, H, _cabi.LG_ABSPOSE_ROOTS, 3, 4), device=device, dtype=torch.float32) if return_candidates else None
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            if P:
-                lib = _cabi.load()
-                nbytes = lib.lg_abspose_workspace_bytes(P, s0.N, H, flags)    # -1: outside the envelope — lg_abspose_estimate below says why
-                ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-                p = _call._ptr
-                at = lambda k: ints.data_ptr() + 4 * k
-                io = _cabi.LgAbsposeIO(
-                    pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, groups=G, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
-                    kpts0=p(s0.kpts), points3d1=p(pts), num0=p(s0.num), num1=p(s1.num),
-                    index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
-                    matches0=p(m0), cameras0=p(cam0),
-                    group_offsets=None if groups is None else groups.data_ptr(), group_pairs=None if groups is None else groups.data_ptr() + 4 * (G + 1),
-                    poses_in=p(poses), workspace=p(ws), workspace_bytes=max(nbytes, 0),
-                    rotations=p(R), translations=p(t), num_inliers=at(0), best_hypothesis=at(G), candidates=p(cand),
-                    inliers0=p(inl), pair_num_inliers=at(2 * G), matches0_out=p(verified), status=at(2 * G + P))
-                _cabi.check(lib.lg_abspose_estimate(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
+        p, (index0, index1), at = _call._ptr, _call.index_ptrs(index), lambda k: ints.data_ptr() + 4 * k
+        io = lambda ws, nbytes: _cabi.LgAbsposeIO(
+            pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, groups=G, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
+            kpts0=p(s0.kpts), points3d1=p(pts), num0=p(s0.num), num1=p(s1.num), index0=index0, index1=index1, matches0=p(m0), cameras0=p(cam0),
+            group_offsets=None if groups is None else groups.data_ptr(), group_pairs=None if groups is None else groups.data_ptr() + 4 * (G + 1),
+            poses_in=p(poses), workspace=ws, workspace_bytes=nbytes,
+            rotations=p(R), translations=p(t), num_inliers=at(0), best_hypothesis=at(G), candidates=p(cand),
+            inliers0=p(inl), pair_num_inliers=at(2 * G), matches0_out=p(verified), status=at(2 * G + P))
+        _call.device_call(device, "lg_abspose_estimate", "lg_abspose_workspace_bytes", (P, s0.N, H, flags), io, skip=not P)
+        host = ints.tolist()                  # THE host sync of the call: the ragged lists need their sizes
         mask = inl.bool()
         matches = _call.ragged_matches(mask, verified, host[2 * G:2 * G + P])
         out = {"R": R, "t": t, "num_inliers": ints[:G].long(), "best_hypothesis": ints[G:2 * G].long(), "queries": queries, "group_of_pair": group_of_pair,
@@ -135,9 +125,7 @@ class AbsolutePoseEstimator(nn.Module):
         s0 = _call.build_side(feats0, device, "feats0")
         pts, s1 = _database_side(points3d1, feats1, device, feats0)
         pt = _call.pair_list(pairs, s0.K, s1.K, validate)
-        P = int(pt.shape[0])
-        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None
-        return device, s0, s1, pts, P, index, pt[:, 0]
+        return device, s0, s1, pts, int(pt.shape[0]), _call.device_index(pt, device), pt[:, 0]
 
     @torch.no_grad()
     def estimate_pairs(self, feats0: dict, pairs, result, cameras0, points3d1, feats1: Optional[dict] = None, *, pool: bool = False, validate: bool = True,

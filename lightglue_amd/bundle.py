@@ -7,61 +7,16 @@ dict holds `cameras [K, 4]`, which every other estimator takes as it is.  Princi
 [K, N, 3]` (NaN where a row is no active observation) is what `AbsolutePoseEstimator` takes as points3d1."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 from torch import nn
 
 from . import _cabi, _call
-from .relpose import as_cameras
-from .triangulate import as_poses
+from ._readers import as_cameras, as_constant, as_poses, as_tracks
 
 STATES = ("none", "active", "bad_image", "non_finite_point", "behind", "short_track", "too_long", "filtered")    # node_state 0 .. 7 (7: the robust mode's filter)
-
-
-def as_track_id(track_id, K: int, N: int, device) -> torch.Tensor:
-    """track_id [K, N] int64 on `device`: THE check of the labels `BundleAdjuster` and `GlobalPositioner` read"""
-    tid = torch.as_tensor(track_id)
-    if tuple(tid.shape) != (K, N):
-        raise ValueError(f"track_id must have shape [{K}, {N}], got {tuple(tid.shape)}")
-    if tid.dtype.is_floating_point or tid.dtype is torch.bool:
-        raise ValueError(f"track_id must hold integers, got {tid.dtype}")
-    return tid.detach().to(device=device, dtype=torch.int64).contiguous()
-
-
-def as_tracks(tracks, K: int, N: int, device):
-    """(track_id [K, N] int64, xyz [T, 3] float32) on `device` from `Triangulator`'s dict or a tuple (track_id, xyz)"""
-    if isinstance(tracks, dict):
-        tracks = (tracks["track_id"], tracks["xyz"])
-    if not isinstance(tracks, (tuple, list)) or len(tracks) != 2:
-        raise ValueError("tracks must be the Triangulator's dict or a tuple (track_id [K, N], xyz [T, 3])")
-    tid, xyz = as_track_id(tracks[0], K, N, device), torch.as_tensor(tracks[1])
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError(f"xyz must have shape [T, 3], got {tuple(xyz.shape)}")
-    if xyz.shape[0] > K * N // 2:
-        raise ValueError(f"xyz holds {xyz.shape[0]} tracks: more than K N / 2 = {K * N // 2} (a track has at least two observations)")
-    return tid, xyz.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-def as_constant(constant_pose, K: int, name: str = "constant_pose") -> torch.Tensor:
-    """[K] bool on the host from a [K] mask or a sequence of image indices; at least one pose must be constant (no camera need be: name = "constant_camera")"""
-    c = torch.as_tensor(constant_pose).detach().cpu()
-    if c.numel() == 0 and c.dtype is not torch.bool:       # an empty index list (torch reads [] as float)
-        c = c.reshape(0).long()
-    if c.dtype is not torch.bool:
-        if c.dtype.is_floating_point or c.dim() != 1:
-            raise ValueError(f"{name} must be a [K] bool mask or a sequence of image indices")
-        if c.numel() and (int(c.min()) < 0 or int(c.max()) >= K):
-            raise ValueError(f"{name} names an image outside [0, {K})")
-        mask = torch.zeros(K, dtype=torch.bool)
-        mask[c.long()] = True
-        c = mask
-    if tuple(c.shape) != (K,):
-        raise ValueError(f"{name} must have shape [{K}], got {tuple(c.shape)}")
-    if name == "constant_pose" and not bool(c.any()):
-        raise ValueError("constant_pose holds no image: nothing fixes the gauge (hold at least one pose; two fix scale as well)")
-    return c
+IMAGE_STATUS = {_cabi.LG_ERR_CAMERA: "a camera whose focal length is not finite and > 0, whose principal point is not finite, or a non-finite pose (LG_ERR_CAMERA): "
+                                     "its observations were left out"}     # status [K] of an adjust call (the only code lg_bundle.hip writes there beside LG_OK)
 
 
 class BundleAdjuster(nn.Module):
@@ -85,20 +40,14 @@ class BundleAdjuster(nn.Module):
         if not (loss == "squared" and type(filter_rounds) is int and filter_rounds == 0):
             if loss not in _cabi.LG_BA_LOSS:
                 raise ValueError(f"loss must be one of {sorted(_cabi.LG_BA_LOSS)}, got {loss!r}")
-            if isinstance(filter_rounds, bool) or int(filter_rounds) != filter_rounds or not 0 <= int(filter_rounds) <= _cabi.LG_BA_MAX_FILTER_ROUNDS:
-                raise ValueError(f"filter_rounds must be an integer in [0, {_cabi.LG_BA_MAX_FILTER_ROUNDS}], got {filter_rounds!r}")
-            if loss != "squared" and not 0.0 < float(loss_scale) < float("inf"):
-                raise ValueError(f"loss_scale must be > 0 with a robust loss, got {loss_scale!r}")
-            if int(filter_rounds) > 0 and not 0.0 < float(max_reproj_error) < float("inf"):
-                raise ValueError(f"max_reproj_error must be > 0 with filter_rounds > 0, got {max_reproj_error!r}")
+            rounds = _call.int_in("filter_rounds", filter_rounds, 0, _cabi.LG_BA_MAX_FILTER_ROUNDS, refuse_bool=True)
+            if loss != "squared":
+                _call.positive("loss_scale", loss_scale, " with a robust loss")
+            if rounds > 0:
+                _call.positive("max_reproj_error", max_reproj_error, " with filter_rounds > 0")
         self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0, bool(refine_focal))
-        if int(num_iterations) != num_iterations or not 1 <= int(num_iterations) <= _cabi.LG_BA_MAX_ITERATIONS:
-            raise ValueError(f"num_iterations must be an integer in [1, {_cabi.LG_BA_MAX_ITERATIONS}], got {num_iterations!r}")
-        if not 0.0 < float(initial_damping) < float("inf"):
-            raise ValueError(f"initial_damping must be > 0, got {initial_damping!r}")
-        if not 0.0 < float(function_tolerance) < float("inf"):
-            raise ValueError(f"function_tolerance must be > 0, got {function_tolerance!r}")
-        self.num_iterations, self.initial_damping, self.function_tolerance = int(num_iterations), float(initial_damping), float(function_tolerance)
+        self.num_iterations = _call.int_in("num_iterations", num_iterations, 1, _cabi.LG_BA_MAX_ITERATIONS)        # takes True as 1, as it always has
+        self.initial_damping, self.function_tolerance = _call.positive("initial_damping", initial_damping), _call.positive("function_tolerance", function_tolerance)
 
     loss = property(lambda self: self.robust[0])
     loss_scale = property(lambda self: self.robust[1])
@@ -146,44 +95,30 @@ class BundleAdjuster(nn.Module):
         pts = torch.empty((K, N, 3), device=device, dtype=torch.float32)
         state = torch.empty((K, N), device=device, dtype=torch.uint8)
         err = torch.empty((K, N), device=device, dtype=torch.float32)
-        small = torch.zeros((24 + K,), device=device, dtype=torch.int32)          # summary [12] fp64 (lg_bundle_adjust writes 8) | status [K]
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            lib = _cabi.load()
-            size = lib.lg_bundle_focal_workspace_bytes if focal else lib.lg_bundle_robust_workspace_bytes if robust else lib.lg_bundle_workspace_bytes
-            nbytes = size(K, N, T, 0)                                             # -1: outside the envelope — the call below says why
-            ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-            p = _call._ptr
+        status, summary_ptr, status_ptr, read = _call.summary_status(12, K, device)       # lg_bundle_adjust writes 8 of the 12 doubles
+        cameras_out = torch.empty((K, 4), device=device, dtype=torch.float32) if focal else None
+        held = const_cam.to(device=device, dtype=torch.uint8) if const_cam is not None else None
+        p = _call._ptr
+
+        def make_io(ws, nbytes):      # the plain struct, wrapped once for the robust entry point and once more for the focal one
             io = _cabi.LgBundleIO(
                 n=N, images=K, tracks=T, flags=0, num_iterations=self.num_iterations, initial_damping=self.initial_damping,
                 function_tolerance=self.function_tolerance, kpts=p(s.kpts), num=p(s.num), track_id=p(tid), xyz=p(xyz), cameras=p(cam), poses=p(pose),
-                constant_pose=p(const), workspace=p(ws), workspace_bytes=max(nbytes, 0), poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
-                node_state=p(state), observation_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 96)
-            if focal:
-                cameras_out = torch.empty((K, 4), device=device, dtype=torch.float32)
-                held = const_cam.to(device=device, dtype=torch.uint8) if const_cam is not None else None
-                rio = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
-                fio = _cabi.LgBundleFocalIO(base=rio, constant_camera=p(held) if held is not None else None, cameras_out=p(cameras_out))
-                _cabi.check(lib.lg_bundle_adjust_focal(C.byref(fio), C.c_void_p(stream.cuda_stream)))
-            elif robust:
-                rio = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
-                _cabi.check(lib.lg_bundle_adjust_robust(C.byref(rio), C.c_void_p(stream.cuda_stream)))
-            else:
-                _cabi.check(lib.lg_bundle_adjust(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = small.cpu().numpy()                # THE host sync of the call
-        summary, status = host[:24].view(np.float64), host[24:]
+                constant_pose=p(const), workspace=ws, workspace_bytes=nbytes, poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
+                node_state=p(state), observation_error=p(err), summary=summary_ptr, status=status_ptr)
+            if robust or focal:
+                io = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
+            return _cabi.LgBundleFocalIO(base=io, constant_camera=p(held) if held is not None else None, cameras_out=p(cameras_out)) if focal else io
+        entry = (("lg_bundle_adjust_focal", "lg_bundle_focal_workspace_bytes") if focal else ("lg_bundle_adjust_robust", "lg_bundle_robust_workspace_bytes") if robust
+                 else ("lg_bundle_adjust", "lg_bundle_workspace_bytes"))
+        _call.device_call(device, *entry, (K, N, T, 0), make_io)
+        summary, host_status = read()             # THE host sync of the call
         out = {"poses": poses_out, "xyz": xyz_out, "points3d": pts, "node_state": state, "observation_error": err,
                "initial_cost": float(summary[0]), "final_cost": float(summary[1]), "num_iterations": int(summary[2]), "num_accepted": int(summary[3]),
                "converged": bool(summary[4]), "num_observations": int(summary[5]), "num_filtered": int(summary[8]), "num_filter_stages": int(summary[9]),
-               "status": small[24:]}
+               "status": status}
         if focal:
             out["cameras"], out["num_free_cameras"] = cameras_out, int(summary[10])
-        bad = [k for k, c in enumerate(status.tolist()) if c != _cabi.LG_OK]
-        if bad:          # every other image is complete: the error carries the call's outputs
-            error = _cabi.LightGlueAmdError("; ".join(f"image {k}: a camera whose focal length is not finite and > 0, whose principal point is not finite, or a "
-                                                      f"non-finite pose (LG_ERR_CAMERA): its observations were left out" for k in bad[:8]))
-            error.outputs = out
-            raise error
-        return out
+        return _call.raise_with_outputs(host_status.tolist(), out, "image", IMAGE_STATUS)      # every other image is complete: the error carries the call's outputs
 
     forward = adjust

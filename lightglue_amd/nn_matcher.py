@@ -5,7 +5,6 @@ checkpoint covers (any dim that is a multiple of 16 up to 256) and the quickest 
 `glue.match_pairs` take it unchanged.  The similarity matrix is never materialised: the only scratch of a call is the normalised copy of the stores' rows."""
 from __future__ import annotations
 
-import ctypes as C
 import functools
 from typing import Optional
 
@@ -46,26 +45,19 @@ class NearestNeighborMatcher(nn.Module):
         if not self.mutual and s0.N > s1.N:          # without the mutual check every row of image 0 may match: the list needs n0 rows, not min(n0, n1)
             o.mlist64 = torch.empty((P, s0.N, 2), device=device, dtype=torch.int64)
             o.mscore_list = torch.empty((P, s0.N), device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            if P:
-                lib = _cabi.load()
-                dim = int(s0.desc.shape[2])
-                flags = ((0 if index is None else _cabi.LG_FLAG_INDEXED) | (_cabi.LG_FLAG_NN_MUTUAL if self.mutual else 0) | s0.flags(0) | s1.flags(1))
-                nbytes = lib.lg_nn_workspace_bytes(s0.K, s1.K, s0.N, s1.N, dim, flags)      # -1: outside the envelope — lg_nn_match below says why
-                ws = torch.empty((max(nbytes, 0),), device=device, dtype=torch.uint8)       # the normalised rows of the stores: independent of P
-                p = _call._ptr
-                io = _cabi.LgNnIO(
-                    pairs=P, n0=s0.N, n1=s1.N, dim=dim, flags=flags,
-                    ratio_threshold=self.ratio_threshold or 0.0, distance_threshold=self.distance_threshold or 0.0,
-                    desc0=p(s0.desc), desc1=p(s1.desc), num0=p(s0.num), num1=p(s1.num),
-                    index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(), images0=s0.K, images1=s1.K,
-                    workspace=p(ws), workspace_bytes=max(nbytes, 0),
-                    raw0=p(o.m0), raw1=p(o.m1), matches0=p(o.m0_64), matches1=p(o.m1_64), scores0=p(o.ms0), scores1=p(o.ms1),
-                    matches=p(o.mlist64), match_scores=p(o.mscore_list), list_rows=int(o.mscore_list.shape[1]),
-                    n_matches=o.stop_nm[1].data_ptr(), status=o.stop_nm[2].data_ptr(), stop=o.stop_nm[0].data_ptr(), stop_i64=p(o.stop64),
-                    prune0=p(o.prune0), prune1=p(o.prune1))
-                _cabi.check(lib.lg_nn_match(C.byref(io), C.c_void_p(stream.cuda_stream)))
+        dim, p, (index0, index1) = int(s0.desc.shape[2]), _call._ptr, _call.index_ptrs(index)
+        flags = ((0 if index is None else _cabi.LG_FLAG_INDEXED) | (_cabi.LG_FLAG_NN_MUTUAL if self.mutual else 0) | s0.flags(0) | s1.flags(1))
+        io = lambda ws, nbytes: _cabi.LgNnIO(
+            pairs=P, n0=s0.N, n1=s1.N, dim=dim, flags=flags,
+            ratio_threshold=self.ratio_threshold or 0.0, distance_threshold=self.distance_threshold or 0.0,
+            desc0=p(s0.desc), desc1=p(s1.desc), num0=p(s0.num), num1=p(s1.num), index0=index0, index1=index1, images0=s0.K, images1=s1.K,
+            workspace=ws, workspace_bytes=nbytes,
+            raw0=p(o.m0), raw1=p(o.m1), matches0=p(o.m0_64), matches1=p(o.m1_64), scores0=p(o.ms0), scores1=p(o.ms1),
+            matches=p(o.mlist64), match_scores=p(o.mscore_list), list_rows=int(o.mscore_list.shape[1]),
+            n_matches=o.stop_nm[1].data_ptr(), status=o.stop_nm[2].data_ptr(), stop=o.stop_nm[0].data_ptr(), stop_i64=p(o.stop64),
+            prune0=p(o.prune0), prune1=p(o.prune1))
+        with torch.cuda.device(device):       # the scratch is the normalised rows of the stores, independent of P: no floor under its size
+            stream = _call.device_call(device, "lg_nn_match", "lg_nn_workspace_bytes", (s0.K, s1.K, s0.N, s1.N, dim, flags), io, skip=not P, floor=0)
             return o.finish(stream, defer)
 
     @torch.no_grad()

@@ -6,36 +6,16 @@ reweighted linear least squares, Schur complement onto the centres, dense Choles
 ONE call with ONE host synchronisation."""
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
 import torch
 from torch import nn
 
 from . import _cabi, _call
-from .bundle import as_constant, as_track_id
-from .relpose import as_cameras
-from .triangulate import as_poses
+from ._readers import as_cameras, as_constant, as_labels, as_poses
 
 # node_state 0 .. 9, image_state 0 .. 5
 STATES = ("none", "inlier", "bad_image", "too_long", "peeled", "not_connected", "degenerate", "outlier", "no_point", "no_solution")
 IMAGE_STATES = ("posed", "held", "too_few_tracks", "not_connected", "bad_image", "no_solution")
 NO_GAUGE = "constant_pose must hold at least two images with finite poses and distinct centres: they fix origin, orientation and scale"
-
-
-def as_labels(tracks, K: int, N: int, device):
-    """(track_id [K, N] int64 on `device`, T) from the dict of `Triangulator.build_tracks` / `triangulate` (track_id, num_tracks) or a tuple (track_id, T)"""
-    if isinstance(tracks, dict):
-        for k in ("track_id", "num_tracks"):
-            if k not in tracks:
-                raise ValueError(f"tracks is a dict without {k!r}: pass the Triangulator's dict or a tuple (track_id [K, N], T)")
-        tracks = (tracks["track_id"], tracks["num_tracks"])
-    if not isinstance(tracks, (tuple, list)) or len(tracks) != 2:
-        raise ValueError("tracks must be the Triangulator's dict or a tuple (track_id [K, N], T)")
-    tid, T = as_track_id(tracks[0], K, N, device), tracks[1]
-    if isinstance(T, bool) or torch.is_tensor(T) or int(T) != T or not 0 <= int(T) <= K * N // 2:
-        raise ValueError(f"the number of tracks must be an integer in [0, K N / 2 = {K * N // 2}] (a track has at least two observations), got {T!r}")
-    return tid, int(T)
 
 
 class GlobalPositioner(nn.Module):
@@ -45,13 +25,8 @@ class GlobalPositioner(nn.Module):
 
     def __init__(self, num_iterations: int = 12, angle_scale: float = 1.0, max_angle_error: float = 2.0):
         super().__init__()
-        lo, hi = _cabi.LG_PG_MIN_ITERATIONS, _cabi.LG_BA_MAX_ITERATIONS
-        if isinstance(num_iterations, bool) or int(num_iterations) != num_iterations or not lo <= int(num_iterations) <= hi:
-            raise ValueError(f"num_iterations must be an integer in [{lo}, {hi}], got {num_iterations!r}")
-        for name, v in (("angle_scale", angle_scale), ("max_angle_error", max_angle_error)):
-            if not 0.0 < float(v) < float("inf"):
-                raise ValueError(f"{name} must be > 0 degrees, got {v!r}")
-        self.num_iterations, self.angle_scale, self.max_angle_error = int(num_iterations), float(angle_scale), float(max_angle_error)
+        self.num_iterations = _call.int_in("num_iterations", num_iterations, _cabi.LG_PG_MIN_ITERATIONS, _cabi.LG_BA_MAX_ITERATIONS, refuse_bool=True)
+        self.angle_scale, self.max_angle_error = _call.positive("angle_scale", angle_scale, " degrees"), _call.positive("max_angle_error", max_angle_error, " degrees")
 
     @torch.no_grad()
     def solve(self, feats: dict, tracks, cameras, poses, constant_pose=None) -> dict:
@@ -102,25 +77,19 @@ class GlobalPositioner(nn.Module):
         state = torch.empty((K, N), device=device, dtype=torch.uint8)
         image_state = torch.empty((K,), device=device, dtype=torch.uint8)
         err = torch.empty((K, N), device=device, dtype=torch.float32)
-        small = torch.zeros((16 + K,), device=device, dtype=torch.int32)          # summary [8] fp64 | status [K]
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            lib = _cabi.load()
-            nbytes = lib.lg_positioning_workspace_bytes(K, N, T, 0)                # -1: outside the envelope — the call below says why
-            ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-            p = _call._ptr
-            io = _cabi.LgPositioningIO(
-                n=N, images=K, tracks=T, flags=0, num_iterations=self.num_iterations, angle_scale=self.angle_scale, max_angle_error=self.max_angle_error,
-                kpts=p(s.kpts), num=p(s.num), track_id=p(tid), cameras=p(cam), poses=p(pose), constant_pose=p(const), workspace=p(ws),
-                workspace_bytes=max(nbytes, 0), poses_out=p(poses_out), xyz=p(xyz), points3d=p(pts), track_id_out=p(tid_out), node_state=p(state),
-                image_state=p(image_state), angle_error=p(err), summary=small.data_ptr(), status=small.data_ptr() + 64)
-            _cabi.check(lib.lg_positioning_solve(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = small.cpu().numpy()                # THE host sync of the call
-        summary = host[:16].view(np.float64)
+        status, summary_ptr, status_ptr, read = _call.summary_status(8, K, device)
+        p = _call._ptr
+        io = lambda ws, nbytes: _cabi.LgPositioningIO(
+            n=N, images=K, tracks=T, flags=0, num_iterations=self.num_iterations, angle_scale=self.angle_scale, max_angle_error=self.max_angle_error,
+            kpts=p(s.kpts), num=p(s.num), track_id=p(tid), cameras=p(cam), poses=p(pose), constant_pose=p(const), workspace=ws,
+            workspace_bytes=nbytes, poses_out=p(poses_out), xyz=p(xyz), points3d=p(pts), track_id_out=p(tid_out), node_state=p(state),
+            image_state=p(image_state), angle_error=p(err), summary=summary_ptr, status=status_ptr)
+        _call.device_call(device, "lg_positioning_solve", "lg_positioning_workspace_bytes", (K, N, T, 0), io)
+        summary = read()[0]                           # THE host sync of the call
         if not summary[5]:
             raise ValueError(NO_GAUGE)
         return {"poses": poses_out, "xyz": xyz, "points3d": pts, "track_id": tid_out, "node_state": state, "image_state": image_state, "angle_error": err,
-                "status": small[16:], "num_posed": int(summary[0]), "num_points": int(summary[1]), "num_outliers": int(summary[2]),
+                "status": status, "num_posed": int(summary[0]), "num_points": int(summary[1]), "num_outliers": int(summary[2]),
                 "iterations": int(summary[3]), "positions_ok": bool(summary[4]), "num_degenerate": int(summary[6])}
 
     forward = solve

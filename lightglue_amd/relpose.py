@@ -4,28 +4,13 @@ stores, the pair list and `matches0` — in place, plus one pinhole camera (fx, 
 synchronisation, and every pair's result is a function of its own correspondences, its two cameras, the configuration and the seed alone."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _cabi, _call
-
-
-def as_cameras(cameras, K: int, device, what: str = "cameras") -> torch.Tensor:
-    """[K, 4] float32 (fx, fy, cx, cy) on `device` from a [K, 4] tensor or from [K, 3, 3] calibration matrices (zero skew, last row (0, 0, 1): checked on
-    the host, so matrices that live on the device cost a copy of their own; the [K, 4] form is read as it stands)"""
-    cam = torch.as_tensor(cameras)
-    if cam.dim() == 3 and tuple(cam.shape[1:]) == (3, 3):
-        flat = cam.detach().to(torch.float64).reshape(-1, 9)
-        zero, one = flat[:, [1, 3, 6, 7]], flat[:, 8]
-        if bool((zero != 0).any()) or bool((one != 1).any()):
-            raise ValueError(f"{what}: calibration matrices must have zero skew and a last row of (0, 0, 1)")
-        cam = flat[:, [0, 4, 2, 5]]
-    if cam.dim() != 2 or tuple(cam.shape) != (K, 4):
-        raise ValueError(f"{what} must have shape [{K}, 4] (fx, fy, cx, cy) or [{K}, 3, 3], got {tuple(cam.shape)}")
-    return cam.detach().to(device=device, dtype=torch.float32).contiguous()
+from ._readers import as_cameras
 
 
 class RelativePoseEstimator(nn.Module):
@@ -53,23 +38,16 @@ class RelativePoseEstimator(nn.Module):
         R, t = torch.empty((P, 3, 3), device=device, dtype=torch.float32), torch.empty((P, 3), device=device, dtype=torch.float32)
         E, F = torch.empty((P, 3, 3), device=device, dtype=torch.float32), torch.empty((P, 3, 3), device=device, dtype=torch.float32)
         cand = torch.empty((P, H, _cabi.LG_RELPOSE_ROOTS, 3, 3), device=device, dtype=torch.float32) if return_candidates else None
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            if P:
-                lib = _cabi.load()
-                nbytes = lib.lg_relpose_workspace_bytes(P, s0.N, H, flags)    # -1: outside the envelope — lg_relpose_estimate below says why
-                ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-                p = _call._ptr
-                io = _cabi.LgRelPoseIO(
-                    pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
-                    kpts0=p(s0.kpts), kpts1=p(s1.kpts), num0=p(s0.num), num1=p(s1.num),
-                    index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
-                    matches0=p(m0), cameras0=p(cam0), cameras1=p(cam1), workspace=p(ws), workspace_bytes=max(nbytes, 0),
-                    rotations=p(R), translations=p(t), essentials=p(E), models=p(F), candidates=p(cand),
-                    inliers0=p(inl), num_inliers=ints[0].data_ptr(), matches0_out=p(verified),
-                    best_hypothesis=ints[1].data_ptr(), num_in_front=ints[3].data_ptr(), status=ints[2].data_ptr())
-                _cabi.check(lib.lg_relpose_estimate(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
+        p, (index0, index1) = _call._ptr, _call.index_ptrs(index)
+        io = lambda ws, nbytes: _cabi.LgRelPoseIO(
+            pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
+            kpts0=p(s0.kpts), kpts1=p(s1.kpts), num0=p(s0.num), num1=p(s1.num), index0=index0, index1=index1,
+            matches0=p(m0), cameras0=p(cam0), cameras1=p(cam1), workspace=ws, workspace_bytes=nbytes,
+            rotations=p(R), translations=p(t), essentials=p(E), models=p(F), candidates=p(cand),
+            inliers0=p(inl), num_inliers=ints[0].data_ptr(), matches0_out=p(verified),
+            best_hypothesis=ints[1].data_ptr(), num_in_front=ints[3].data_ptr(), status=ints[2].data_ptr())
+        _call.device_call(device, "lg_relpose_estimate", "lg_relpose_workspace_bytes", (P, s0.N, H, flags), io, skip=not P)
+        host = ints.tolist()                  # THE host sync of the call: the ragged lists need their sizes
         mask = inl.bool()
         matches = _call.ragged_matches(mask, verified, host[0])
         out = {"R": R, "t": t, "E": E, "models": F, "inliers0": mask, "num_inliers": ints[0].long(), "num_in_front": ints[3].long(), "matches0": verified,

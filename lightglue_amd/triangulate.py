@@ -7,29 +7,14 @@ points3d1.  Any number of pairs in ONE call with ONE host synchronisation; every
 costs an outlier node and not the track."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _cabi, _call
-from .relpose import as_cameras
+from ._readers import as_cameras, as_poses
 
 STATES = ("none", "triangulated", "conflict", "too_long", "degenerate", "behind", "reprojection", "angle")    # node_state 0 .. 7
 ROBUST_STATES = STATES + ("outlier",)                    # node_state 0 .. 8 of the robust mode: 8 is a node its component's tracks left over (2 does not occur)
-
-
-def as_poses(poses, K: int, device) -> torch.Tensor:
-    """[K, 3, 4] float32 (R | t) on `device` from a [K, 3, 4] tensor or a tuple (R [K, 3, 3], t [K, 3])"""
-    if isinstance(poses, (tuple, list)) and len(poses) == 2:
-        R, t = torch.as_tensor(poses[0]), torch.as_tensor(poses[1])
-        if tuple(R.shape) != (K, 3, 3) or tuple(t.shape) != (K, 3):
-            raise ValueError(f"poses (R, t) must have shapes [{K}, 3, 3] and [{K}, 3], got {tuple(R.shape)} and {tuple(t.shape)}")
-        poses = torch.cat([R.to(device=device, dtype=torch.float32), t.to(device=device, dtype=torch.float32)[:, :, None]], 2)
-    poses = torch.as_tensor(poses)
-    if tuple(poses.shape) != (K, 3, 4):
-        raise ValueError(f"poses must have shape [{K}, 3, 4] (R | t) or be a tuple (R [{K}, 3, 3], t [{K}, 3]), got {tuple(poses.shape)}")
-    return poses.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 class Triangulator(nn.Module):
@@ -42,18 +27,13 @@ class Triangulator(nn.Module):
     def __init__(self, max_reproj_error: float = 4.0, min_angle: float = 1.5, max_track_length: int = 128, refine: bool = True, robust: bool = False,
                  num_hypotheses: int = 64, max_tracks: int = 2):
         super().__init__()
-        if int(num_hypotheses) != num_hypotheses or not 1 <= int(num_hypotheses) <= _cabi.LG_TRI_MAX_HYPOTHESES:
-            raise ValueError(f"num_hypotheses must be an integer in [1, {_cabi.LG_TRI_MAX_HYPOTHESES}], got {num_hypotheses!r}")
-        if int(max_tracks) != max_tracks or not 1 <= int(max_tracks) <= _cabi.LG_TRI_MAX_TRACKS:
-            raise ValueError(f"max_tracks must be an integer in [1, {_cabi.LG_TRI_MAX_TRACKS}], got {max_tracks!r}")
-        self.robust, self.num_hypotheses, self.max_tracks = bool(robust), int(num_hypotheses), int(max_tracks)
-        if not 0.0 < float(max_reproj_error) < float("inf"):
-            raise ValueError(f"max_reproj_error must be > 0, got {max_reproj_error!r}")
+        self.num_hypotheses = _call.int_in("num_hypotheses", num_hypotheses, 1, _cabi.LG_TRI_MAX_HYPOTHESES)       # these integers take True as 1
+        self.max_tracks, self.robust = _call.int_in("max_tracks", max_tracks, 1, _cabi.LG_TRI_MAX_TRACKS), bool(robust)
+        self.max_reproj_error = _call.positive("max_reproj_error", max_reproj_error)
         if not 0.0 <= float(min_angle) < 180.0:
             raise ValueError(f"min_angle must lie in [0, 180), got {min_angle!r}")
-        if int(max_track_length) != max_track_length or not 2 <= int(max_track_length) <= _cabi.LG_TRI_MAX_TRACK_LENGTH:
-            raise ValueError(f"max_track_length must be an integer in [2, {_cabi.LG_TRI_MAX_TRACK_LENGTH}], got {max_track_length!r}")
-        self.max_reproj_error, self.min_angle, self.max_track_length, self.refine = float(max_reproj_error), float(min_angle), int(max_track_length), bool(refine)
+        self.max_track_length = _call.int_in("max_track_length", max_track_length, 2, _cabi.LG_TRI_MAX_TRACK_LENGTH)
+        self.min_angle, self.refine = float(min_angle), bool(refine)
 
     # ------------------------------------------------------------------ the call path
     def _launch(self, feats: dict, pairs, result, cameras, poses, validate: bool, tracks_only: bool) -> dict:
@@ -63,8 +43,7 @@ class Triangulator(nn.Module):
         s = _call.build_side(feats, device, "feats")
         K, N = int(s.K), int(s.N)
         pt = _call.pair_list(pairs, K, K, validate)
-        P = int(pt.shape[0])
-        index = pt.to(device=device, dtype=torch.int32).t().contiguous() if P else None
+        P, index = int(pt.shape[0]), _call.device_index(pt, device)
         m0 = _call.as_matches0(result, P, N, device)
         cam = pose = None
         if not tracks_only:
@@ -78,27 +57,20 @@ class Triangulator(nn.Module):
         robust = self.robust                                                    # (never with tracks_only: build_tracks refuses)
         extra = 2 if robust else 0                                              # robust: | outlier nodes | components with more than one track, at the end
         ints = torch.zeros((9 + P + extra,), device=device, dtype=torch.int32)  # T | tracks per state [8] | status [P]
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            lib = _cabi.load()
-            # -1: outside the envelope — the call below says why
-            nbytes = lib.lg_triangulate_robust_workspace_bytes(K, N, self.max_tracks) if robust else lib.lg_triangulate_workspace_bytes(K, N, flags)
-            ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-            p = _call._ptr
-            base = per_track.data_ptr()
+        p, (index0, index1), base = _call._ptr, _call.index_ptrs(index), per_track.data_ptr()
+
+        def make_io(ws, nbytes):
             io = _cabi.LgTriangulateIO(
                 pairs=P, n=N, images=K, flags=flags, max_reproj_error=self.max_reproj_error, min_angle=self.min_angle, max_track_length=self.max_track_length,
-                kpts=p(s.kpts), num=p(s.num), index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
-                matches0=p(m0), cameras=p(cam), poses=p(pose), workspace=p(ws), workspace_bytes=max(nbytes, 0),
-                points3d=p(pts), track_id=p(track_id), node_state=p(state),
-                xyz=base, track_error=base + 12 * cap, track_length=base + 16 * cap,
+                kpts=p(s.kpts), num=p(s.num), index0=index0, index1=index1, matches0=p(m0), cameras=p(cam), poses=p(pose), workspace=ws, workspace_bytes=nbytes,
+                points3d=p(pts), track_id=p(track_id), node_state=p(state), xyz=base, track_error=base + 12 * cap, track_length=base + 16 * cap,
                 counts=ints.data_ptr(), status=None if not P else ints.data_ptr() + 36)
             if robust:
-                rio = _cabi.LgTriangulateRobustIO(base=io, num_hypotheses=self.num_hypotheses, max_tracks=self.max_tracks, outlier_counts=ints.data_ptr() + 4 * (9 + P))
-                _cabi.check(lib.lg_triangulate_robust(C.byref(rio), C.c_void_p(stream.cuda_stream)))
-            else:
-                _cabi.check(lib.lg_triangulate(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = ints.tolist()              # THE host sync of the call: the per-track outputs need their number
+                io = _cabi.LgTriangulateRobustIO(base=io, num_hypotheses=self.num_hypotheses, max_tracks=self.max_tracks, outlier_counts=ints.data_ptr() + 4 * (9 + P))
+            return io
+        entry = ("lg_triangulate_robust", "lg_triangulate_robust_workspace_bytes", (K, N, self.max_tracks)) if robust else ("lg_triangulate", "lg_triangulate_workspace_bytes", (K, N, flags))
+        _call.device_call(device, *entry, make_io)
+        host = ints.tolist()                  # THE host sync of the call: the per-track outputs need their number
         T = host[0]
         flat = per_track.view(-1)
         out = {"track_id": track_id, "node_state": state, "num_tracks": T, "track_length": flat[4 * cap:4 * cap + T].view(torch.int32).long(),

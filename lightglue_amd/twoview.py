@@ -4,7 +4,6 @@ keypoint stores, the pair list and `matches0` — in place, runs any number of p
 function of its own correspondences, the configuration and the seed alone: the same bits wherever the pair stands in a list."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -43,22 +42,15 @@ class TwoViewVerifier(nn.Module):
         inl = torch.empty((P, s0.N), device=device, dtype=torch.uint8)
         verified = torch.empty((P, s0.N), device=device, dtype=torch.int64)
         ints = torch.empty((3, P), device=device, dtype=torch.int32)          # [0] = num_inliers, [1] = best_hypothesis, [2] = status
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            if P:
-                lib = _cabi.load()
-                nbytes = lib.lg_twoview_workspace_bytes(P, s0.N, flags)       # -1: outside the envelope — lg_twoview_verify below says why
-                ws = torch.empty((max(nbytes, 256),), device=device, dtype=torch.uint8)
-                p = _call._ptr
-                io = _cabi.LgTwoViewIO(
-                    pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
-                    kpts0=p(s0.kpts), kpts1=p(s1.kpts), num0=p(s0.num), num1=p(s1.num),
-                    index0=None if index is None else index[0].data_ptr(), index1=None if index is None else index[1].data_ptr(),
-                    matches0=p(m0), models_in=p(models), workspace=p(ws), workspace_bytes=max(nbytes, 0),
-                    models=p(out_models), inliers0=p(inl), num_inliers=ints[0].data_ptr(), matches0_out=p(verified),
-                    best_hypothesis=ints[1].data_ptr(), status=ints[2].data_ptr())
-                _cabi.check(lib.lg_twoview_verify(C.byref(io), C.c_void_p(stream.cuda_stream)))
-            host = ints.tolist()              # THE host sync of the call: the ragged lists need their sizes
+        p, (index0, index1) = _call._ptr, _call.index_ptrs(index)
+        io = lambda ws, nbytes: _cabi.LgTwoViewIO(
+            pairs=P, n0=s0.N, n1=s1.N, images0=s0.K, images1=s1.K, flags=flags, threshold=self.threshold, num_hypotheses=H, seed=self.seed,
+            kpts0=p(s0.kpts), kpts1=p(s1.kpts), num0=p(s0.num), num1=p(s1.num), index0=index0, index1=index1,
+            matches0=p(m0), models_in=p(models), workspace=ws, workspace_bytes=nbytes,
+            models=p(out_models), inliers0=p(inl), num_inliers=ints[0].data_ptr(), matches0_out=p(verified),
+            best_hypothesis=ints[1].data_ptr(), status=ints[2].data_ptr())
+        _call.device_call(device, "lg_twoview_verify", "lg_twoview_workspace_bytes", (P, s0.N, flags), io, skip=not P)
+        host = ints.tolist()                  # THE host sync of the call: the ragged lists need their sizes
         mask = inl.bool()
         matches = _call.ragged_matches(mask, verified, host[0])
         out = {"models": out_models, "inliers0": mask, "num_inliers": ints[0].long(), "matches0": verified, "matches": matches, "best_hypothesis": ints[1].long()}

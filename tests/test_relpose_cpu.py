@@ -14,7 +14,7 @@ import relpose_oracle as P
 import twoview_oracle as TV
 import test_gpu_relpose as G
 from lightglue_amd import RelativePoseEstimator, TwoViewVerifier, _cabi
-from lightglue_amd.relpose import as_cameras
+from lightglue_amd._readers import as_cameras
 from test_twoview_cpu import typed_fields_of
 
 HEADER = (Path(__file__).resolve().parent.parent / "include" / "lightglue_amd.h").read_text()

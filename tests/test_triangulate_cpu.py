@@ -13,7 +13,8 @@ import torch
 import triangulate_oracle as O
 import test_gpu_triangulate as G
 from lightglue_amd import Triangulator, _cabi
-from lightglue_amd.triangulate import STATES, as_poses
+from lightglue_amd._readers import as_poses
+from lightglue_amd.triangulate import STATES
 from test_twoview_cpu import typed_fields_of
 
 HEADER = (Path(__file__).resolve().parent.parent / "include" / "lightglue_amd.h").read_text()
