@@ -1155,6 +1155,70 @@ int64_t lg_bundle_focal_workspace_bytes(int64_t images, int32_t n, int64_t track
 int lg_bundle_adjust_focal(const lg_bundle_focal_io* io, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The bundle adjuster with an iterative solver for the reduced camera system: preconditioned conjugate gradients with the block-Jacobi preconditioner
+ * (Ceres: ITERATIVE_SCHUR with SCHUR_JACOBI), matrix-free (S is never formed), fp64, for up to LG_BA_PCG_MAX_IMAGES images.  lg_bundle_adjust,
+ * lg_bundle_adjust_robust and lg_bundle_adjust_focal are unchanged in every bit, message and refusal; this is a fourth entry point whose io holds
+ * lg_bundle_robust_io as `base`.  tests/bundle_pcg_oracle.py restates it in float64 numpy.  Everything outside the linear solve is lg_bundle_adjust_robust's
+ * definition (and through it lg_bundle_adjust's), word for word: candidates, node states, status, the loss and its weights, damping, the 3 x 3 point blocks
+ * (V', Vi, y), the point step, the trial, accept / reject / convergence, the stages, the filter and the outputs.  Seven unknowns per image are not offered.
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ * Per Levenberg-Marquardt iteration, after the points (V', Vi, y per adjusted track):
+ *   setup     per free image a, over its active rows in ascending row order: U_a and g_a (lg_bundle_adjust's; the upper triangle of U is summed and mirrored),
+ *             U'_a = U_a with Marquardt's damping on its diagonal, the right-hand side b_a = (sum of W y_j) - g_a, and the lower triangle (c <= r) of
+ *             E_aa = the sum over the rows i, and for each over the observations (a, i') of the same track in the track's order, of Y W_(a,i')^T with
+ *             Y = W_(a,i) Vi_j (lg_bundle_adjust's formulas and orders; two rows of one image in one track are two observations, each W with its own weight).
+ *             S_aa = U'_a - E_aa (lower triangle).  S_aa = L L^T by rows: for entry (i, j), j <= i, the products L_ik L_jk, k < j ascending, are subtracted
+ *             from S_ij one at a time; L_ii is the square root of what is left, L_ij that over L_jj.  A pivot that is not > 0 (or not finite) fails the
+ *             trial and the factorisation goes on with 1 in its place (the dense path's rule).
+ *             M_a = S_aa^-1, column c: L w = e_c forwards, w_i = (e_i less L_ik w_k, k < i ascending, one at a time) / L_ii, then L^T m = w backwards,
+ *             m_i = (w_i less L_ki m_k, k = i + 1 .. 5 ascending, one at a time) / L_ii; M[r][c] = m_r (M is not symmetrised).
+ *             An image that is not free has no unknowns: its entries of every vector below are 0 and are never read as anything else.
+ *   products  M v of image a: entry r is the sum of M[r][c] v_c over c ascending (the first product starts the sum); U' v likewise.
+ *   operator  q = S p: per adjusted track j, u_j = Vi_j w with w = the sum over the track's observations of free images, in the track's order, of W^T p_k
+ *             (entry m: the sum over r ascending of W[r][m] p_k[r], started at 0 — lg_bundle_adjust's point step with p in place of the step);
+ *             u_j[r] = (Vi[r][0] w0 + Vi[r][1] w1) + Vi[r][2] w2.  Per free image a: q_a = U'_a p_a - (the sum over its active rows in ascending row order
+ *             of W_(a,i) u_j, entry r: (W[r][0] u0 + W[r][1] u1) + W[r][2] u2).  W is formed again from the pose and the point, as everywhere.
+ *   dot       a.b = per image d_k = the sum of a_k[e] b_k[e] over e ascending (the first product starts the sum; 0 for an image that is not free); partial m,
+ *             m < 256, = the sum of d_k over the images k = m, m + 256, m + 512, .. ascending, started at 0; then for h = 128, 64, .. 1: partial m +=
+ *             partial m + h for every m < h; the result is partial 0.
+ *   PCG       x = 0, r = b, z = M r, p = z, rz0 = rz = r.z.  If rz0 is 0 the solve ends at once with x = 0; if it is not finite or < 0 the trial fails.
+ *             Step i = 1, 2, ..: q = S p; pq = p.q; a pq that is not > 0 or not finite fails the trial.  alpha = rz / pq; x += alpha p; r -= alpha q
+ *             (each entry x + alpha p, r - alpha q); z = M r; rz' = r.z; an rz' that is not finite or < 0 (a non-finite vector entry shows here) fails
+ *             the trial.  The solve ends on the tolerance iff sqrt(rz') <= cg_tolerance sqrt(rz0), else on the budget iff i = max_cg_iterations; otherwise
+ *             beta = rz' / rz, p = z + beta p, rz = rz'.  A trial that failed in the points, the setup or the solve is rejected by lg_bundle_adjust's rule.
+ *             The pose step is x; trial poses, trial points, cost and the decision are lg_bundle_adjust's.
+ *   stopping  the budget is fixed like num_iterations: every launch of every solver iteration of every Levenberg-Marquardt iteration is enqueued
+ *             unconditionally; "this solve is done" is a field of the device record that only the single-workgroup step kernel writes, and once it is
+ *             set, or `converged` or the trial's failure is, the solve's remaining launches return at once.
+ *   outputs   those of lg_bundle_adjust_robust, summary [12] with 7 = the solver iterations run over the whole call and 11 = the Levenberg-Marquardt
+ *             iterations whose solve ended on the budget.
+ *   Determinism: as lg_bundle_adjust: no floating-point atomics, every sum a fixed function of position, the same bits from run to run and under a
+ *             relabelling of the tracks.
+ * Workspace: lg_bundle_pcg_workspace_bytes bytes (-1 outside the envelope), 256-byte aligned, every piece rounded up to 256 bytes: that of
+ *   lg_bundle_adjust_robust without S, plus a 256-byte record, 784 bytes per image (r, z, p, q: 4 x 48; U' and M: 2 x 288; the image's partials of p.q and
+ *   r.z: 2 x 8; x is lg_bundle_adjust's step) and 24 bytes per track (u).
+ * Envelope (LG_ERR_INVALID with a message that names the field, before the GPU is touched), in this order: null io; lg_bundle_adjust's layout bounds with
+ *   images in [1, LG_BA_PCG_MAX_IMAGES] (images x n <= LG_MAX_ROWS still binds); the robust settings; pad not 0; max_cg_iterations outside
+ *   [1, LG_BA_PCG_MAX_CG_ITERATIONS]; cg_tolerance not in (0, 1) (NaN included); num_iterations x (filter_rounds + 1) x max_cg_iterations above
+ *   LG_BA_PCG_MAX_SOLVER_ITERATIONS (the call enqueues that many solver iterations); then lg_bundle_adjust's list.
+ * Launches, none of which waits on another workgroup: those of lg_bundle_adjust_robust with reduce, the Cholesky panels and the back substitution replaced by
+ *   setup (one workgroup per image) and, max_cg_iterations times, tracks (one lane per track: u), images (one workgroup per image: q and its partial of
+ *   p.q) and step (ONE workgroup: the dots, alpha, beta, x, r, z, p, the record, and the trial poses when the solve ends); last one lane writes summary
+ *   7 and 11. */
+#define LG_BA_PCG_MAX_IMAGES 4096
+#define LG_BA_PCG_MAX_CG_ITERATIONS 1000
+#define LG_BA_PCG_MAX_SOLVER_ITERATIONS 20000
+typedef struct lg_bundle_pcg_io {
+    lg_bundle_robust_io base;              /* base.base.workspace: lg_bundle_pcg_workspace_bytes; summary: [12]       */
+    int32_t max_cg_iterations;             /* in [1, LG_BA_PCG_MAX_CG_ITERATIONS]                                     */
+    int32_t pad;                           /* must be 0                                                               */
+    double cg_tolerance;                   /* in (0, 1)                                                               */
+} lg_bundle_pcg_io;
+int64_t lg_bundle_pcg_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_bundle_adjust_pcg(const lg_bundle_pcg_io* io, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Global poses: one pose per image from the relative poses of a pair list (what lg_relpose_estimate returns), by rotation averaging over the view graph and
  * position averaging along the pairs' translation directions, both robust to wrong pairs; the per-image poses are what lg_triangulate and lg_bundle_adjust
  * take.  fp64 throughout, no fused multiply-add, dense Cholesky, one call and one host synchronisation.  Stateless.  The reference has no such step; this is

@@ -32,6 +32,7 @@ LG_TRI_MAX_HYPOTHESES, LG_TRI_MAX_TRACKS = 4096, 4   # lg_triangulate_robust: hy
 LG_BA_MAX_IMAGES, LG_BA_MAX_ITERATIONS, LG_BA_MAX_TRACK_LENGTH, LG_BA_CHOLESKY_BLOCK = 256, 100, 1024, 48   # lg_bundle_adjust: its envelope, the columns per Cholesky panel (it defines no flag bit)
 LG_BA_LOSS = {"squared": 0, "huber": 1, "cauchy": 2}   # lg_bundle_adjust_robust: LG_BA_LOSS_*
 LG_BA_MAX_FILTER_ROUNDS = 4                         # lg_bundle_adjust_robust: filters (stages - 1) of one call
+LG_BA_PCG_MAX_IMAGES, LG_BA_PCG_MAX_CG_ITERATIONS, LG_BA_PCG_MAX_SOLVER_ITERATIONS = 4096, 1000, 20000   # lg_bundle_adjust_pcg: its envelope (solver iterations: enqueued per call)
 LG_PG_MIN_ITERATIONS, LG_PG_MAX_PAIRS = 6, 2 ** 20   # lg_posegraph_solve: its envelope next to LG_BA_MAX_IMAGES and LG_BA_MAX_ITERATIONS (it defines no flag bit)
 LG_TWOVIEW_TILE = 256                             # lg_twoview_verify: correspondences per LDS tile of the scoring kernel (= hypotheses per workgroup)
 LG_NN_ROWS_PER_WORKGROUP, LG_NN_TILE = 128, 64    # lg_nn_match's kernel shape: rows of one side a workgroup owns, rows of the other side per LDS tile
@@ -56,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "lg_abspose_workspace_bytes", "lg_abspose_estimate",
     "lg_triangulate_workspace_bytes", "lg_triangulate", "lg_triangulate_robust_workspace_bytes", "lg_triangulate_robust",
     "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust", "lg_bundle_focal_workspace_bytes", "lg_bundle_adjust_focal",
+    "lg_bundle_pcg_workspace_bytes", "lg_bundle_adjust_pcg",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
     "lg_positioning_workspace_bytes", "lg_positioning_solve",
 )
@@ -188,6 +190,11 @@ class LgBundleRobustIO(C.Structure):
 class LgBundleFocalIO(C.Structure):
     """lg_bundle_focal_io (include/lightglue_amd.h): one call of the bundle adjuster with per-image focal lengths refined"""
     _fields_ = [("base", LgBundleRobustIO), ("constant_camera", _fp), ("cameras_out", _fp)]
+
+
+class LgBundlePcgIO(C.Structure):
+    """lg_bundle_pcg_io (include/lightglue_amd.h): one call of the bundle adjuster with the iterative solver"""
+    _fields_ = [("base", LgBundleRobustIO), ("max_cg_iterations", C.c_int32), ("pad", C.c_int32), ("cg_tolerance", C.c_double)]
 
 
 class LgPosegraphIO(C.Structure):
@@ -402,6 +409,9 @@ def load() -> C.CDLL:
     lib.lg_bundle_focal_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_bundle_focal_workspace_bytes.restype = C.c_int64
     lib.lg_bundle_adjust_focal.argtypes = [C.POINTER(LgBundleFocalIO), C.c_void_p]
+    lib.lg_bundle_pcg_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
+    lib.lg_bundle_pcg_workspace_bytes.restype = C.c_int64
+    lib.lg_bundle_adjust_pcg.argtypes = [C.POINTER(LgBundlePcgIO), C.c_void_p]
     lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
     lib.lg_posegraph_workspace_bytes.restype = C.c_int64
     lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]

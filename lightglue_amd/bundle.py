@@ -3,7 +3,9 @@ with a robust loss or filter rounds `lg_bundle_adjust_robust`, and with `refine_
 (fx, fy, cx, cy) and one pose (R | t), X_cam = R X_world + t, per image, and refines all free poses and all track points jointly: Levenberg-Marquardt on the
 sum of squared pixel reprojection errors, Schur complement, dense Cholesky, fp64.  Intrinsics are fixed unless `refine_focal=True`: then every image carries
 one more unknown, the logarithm of a common scale of fx and fy (cx, cy stay), held or free per image by `constant_camera` independently of its pose, and the
-dict holds `cameras [K, 4]`, which every other estimator takes as it is.  Principal point, distortion, shared intrinsics and a prior stay out.  ONE call with ONE host synchronisation; `points3d
+dict holds `cameras [K, 4]`, which every other estimator takes as it is.  Principal point, distortion, shared intrinsics and a prior stay out.
+`solver="pcg"` replaces the dense Cholesky by matrix-free preconditioned conjugate gradients on the reduced camera system (`lg_bundle_adjust_pcg`, block-Jacobi
+preconditioner, fp64) and lifts the bound of 256 images to 4096.  ONE call with ONE host synchronisation; `points3d
 [K, N, 3]` (NaN where a row is no active observation) is what `AbsolutePoseEstimator` takes as points3d1."""
 from __future__ import annotations
 
@@ -28,10 +30,17 @@ class BundleAdjuster(nn.Module):
     (squared, no filter) call `lg_bundle_adjust` as before; anything else calls `lg_bundle_adjust_robust`.
     refine_focal: every image carries one more unknown d, a step sets fx <- fx exp(d), fy <- fy exp(d) (the aspect ratio and the sign stay, cx and cy are not
     touched); `adjust` then takes `constant_camera` and returns `cameras` and `num_free_cameras`, on `lg_bundle_adjust_focal`, with every loss and filter
-    setting meaning what it means without it.  False (the default) changes nothing."""
+    setting meaning what it means without it.  False (the default) changes nothing.
+    solver: "cholesky" (the default: the dense factorisation, at most 256 images, nothing changes) or "pcg": every Levenberg-Marquardt step is solved by at
+    most max_cg_iterations (in [1, 1000]) iterations of preconditioned conjugate gradients, stopped once the preconditioned residual norm sqrt(r.z) has
+    fallen to cg_tolerance (in (0, 1)) times its start; up to 4096 images, with every loss and filter setting (`lg_bundle_adjust_pcg`), not with
+    refine_focal.  num_iterations x (filter_rounds + 1) x max_cg_iterations may not exceed 20000: the call enqueues that many solver iterations.  The dict
+    then counts them in `cg_iterations`, and in `cg_unconverged` the Levenberg-Marquardt iterations whose solve ended on the budget.  With "cholesky"
+    max_cg_iterations and cg_tolerance are not read and therefore not examined, like the robust settings under the defaults."""
 
     def __init__(self, num_iterations: int = 10, initial_damping: float = 1e-4, function_tolerance: float = 1e-6, loss: str = "squared", loss_scale: float = 2.0,
-                 filter_rounds: int = 0, max_reproj_error: float = 4.0, refine_focal: bool = False):
+                 filter_rounds: int = 0, max_reproj_error: float = 4.0, refine_focal: bool = False, solver: str = "cholesky", max_cg_iterations: int = 100,
+                 cg_tolerance: float = 1e-6):
         super().__init__()
         if not isinstance(refine_focal, (bool, np.bool_)):
             raise ValueError(f"refine_focal must be a bool, got {refine_focal!r}")
@@ -45,8 +54,20 @@ class BundleAdjuster(nn.Module):
                 _call.positive("loss_scale", loss_scale, " with a robust loss")
             if rounds > 0:
                 _call.positive("max_reproj_error", max_reproj_error, " with filter_rounds > 0")
-        self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0, bool(refine_focal))
+        pcg = None                                          # or (max_cg_iterations, cg_tolerance): the last entry of the one attribute
+        if solver != "cholesky":
+            if solver != "pcg":
+                raise ValueError(f"solver must be 'cholesky' or 'pcg', got {solver!r}")
+            if refine_focal:
+                raise ValueError("solver='pcg' does not refine focal lengths: refine_focal needs solver='cholesky'")
+            if not isinstance(cg_tolerance, (int, float, np.floating)) or not 0.0 < float(cg_tolerance) < 1.0:
+                raise ValueError(f"cg_tolerance must be a number in (0, 1), got {cg_tolerance!r}")
+            pcg = (_call.int_in("max_cg_iterations", max_cg_iterations, 1, _cabi.LG_BA_PCG_MAX_CG_ITERATIONS, refuse_bool=True), float(cg_tolerance))
+        self.robust = (loss, float(loss_scale), int(filter_rounds), float(max_reproj_error), loss != "squared" or filter_rounds > 0, bool(refine_focal), pcg)
         self.num_iterations = _call.int_in("num_iterations", num_iterations, 1, _cabi.LG_BA_MAX_ITERATIONS)        # takes True as 1, as it always has
+        if pcg and self.num_iterations * (int(filter_rounds) + 1) * pcg[0] > _cabi.LG_BA_PCG_MAX_SOLVER_ITERATIONS:
+            raise ValueError(f"num_iterations x (filter_rounds + 1) x max_cg_iterations must not exceed {_cabi.LG_BA_PCG_MAX_SOLVER_ITERATIONS} (the call enqueues "
+                             f"that many solver iterations), got {self.num_iterations} x {int(filter_rounds) + 1} x {pcg[0]}")
         self.initial_damping, self.function_tolerance = _call.positive("initial_damping", initial_damping), _call.positive("function_tolerance", function_tolerance)
 
     loss = property(lambda self: self.robust[0])
@@ -54,6 +75,9 @@ class BundleAdjuster(nn.Module):
     filter_rounds = property(lambda self: self.robust[2])
     max_reproj_error = property(lambda self: self.robust[3])
     refine_focal = property(lambda self: self.robust[5])
+    solver = property(lambda self: "pcg" if self.robust[6] else "cholesky")
+    max_cg_iterations = property(lambda self: self.robust[6][0] if self.robust[6] else None)
+    cg_tolerance = property(lambda self: self.robust[6][1] if self.robust[6] else None)
 
     @property
     def robust_entry(self) -> bool:
@@ -72,7 +96,7 @@ class BundleAdjuster(nn.Module):
         bool mask or the indices of the images whose pose is held fixed (at least one: ValueError otherwise; two fix scale).  Returns poses [K, 3, 4], xyz
         [T, 3], points3d [K, N, 3] (NaN where a row is no active observation), node_state [K, N] uint8 (`STATES`), observation_error [K, N] (pixels, NaN where
         not active), initial_cost, final_cost, num_iterations (run), num_accepted, converged, num_observations, num_filtered, num_filter_stages (both 0 without
-        a filter), status [K].  With refine_focal: constant_camera (None: no camera is held; else a [K] bool mask or image indices, parsed like
+        a filter), status [K]; with solver="pcg" also cg_iterations and cg_unconverged.  With refine_focal: constant_camera (None: no camera is held; else a [K] bool mask or image indices, parsed like
         constant_pose) names the images whose focal length is held, independently of the poses, and the dict also holds cameras [K, 4] float32 (fx, fy
         refined where the camera was free; cx, cy and every camera that never moved are the input's bits: what `Triangulator`, `AbsolutePoseEstimator` and
         `RelativePoseEstimator` take as cameras) and num_free_cameras.  Without refine_focal constant_camera must be None.  ONE host synchronisation.  An
@@ -81,7 +105,7 @@ class BundleAdjuster(nn.Module):
         s = _call.build_side(feats, device, "feats")
         K, N = int(s.K), int(s.N)
         const = as_constant(constant_pose, K)
-        loss, loss_scale, filter_rounds, max_reproj_error, robust, focal = self.robust
+        loss, loss_scale, filter_rounds, max_reproj_error, robust, focal, pcg = self.robust
         if constant_camera is not None and not focal:
             raise ValueError("constant_camera needs refine_focal=True: without it every camera is held")
         const_cam = as_constant(constant_camera, K, "constant_camera") if constant_camera is not None else None
@@ -106,17 +130,21 @@ class BundleAdjuster(nn.Module):
                 function_tolerance=self.function_tolerance, kpts=p(s.kpts), num=p(s.num), track_id=p(tid), xyz=p(xyz), cameras=p(cam), poses=p(pose),
                 constant_pose=p(const), workspace=ws, workspace_bytes=nbytes, poses_out=p(poses_out), xyz_out=p(xyz_out), points3d=p(pts),
                 node_state=p(state), observation_error=p(err), summary=summary_ptr, status=status_ptr)
-            if robust or focal:
+            if robust or focal or pcg:
                 io = _cabi.LgBundleRobustIO(base=io, loss=_cabi.LG_BA_LOSS[loss], filter_rounds=filter_rounds, loss_scale=loss_scale, max_reproj_error=max_reproj_error)
+            if pcg:
+                return _cabi.LgBundlePcgIO(base=io, max_cg_iterations=pcg[0], pad=0, cg_tolerance=pcg[1])
             return _cabi.LgBundleFocalIO(base=io, constant_camera=p(held) if held is not None else None, cameras_out=p(cameras_out)) if focal else io
-        entry = (("lg_bundle_adjust_focal", "lg_bundle_focal_workspace_bytes") if focal else ("lg_bundle_adjust_robust", "lg_bundle_robust_workspace_bytes") if robust
-                 else ("lg_bundle_adjust", "lg_bundle_workspace_bytes"))
+        entry = (("lg_bundle_adjust_pcg", "lg_bundle_pcg_workspace_bytes") if pcg else ("lg_bundle_adjust_focal", "lg_bundle_focal_workspace_bytes") if focal
+                 else ("lg_bundle_adjust_robust", "lg_bundle_robust_workspace_bytes") if robust else ("lg_bundle_adjust", "lg_bundle_workspace_bytes"))
         _call.device_call(device, *entry, (K, N, T, 0), make_io)
         summary, host_status = read()             # THE host sync of the call
         out = {"poses": poses_out, "xyz": xyz_out, "points3d": pts, "node_state": state, "observation_error": err,
                "initial_cost": float(summary[0]), "final_cost": float(summary[1]), "num_iterations": int(summary[2]), "num_accepted": int(summary[3]),
                "converged": bool(summary[4]), "num_observations": int(summary[5]), "num_filtered": int(summary[8]), "num_filter_stages": int(summary[9]),
                "status": status}
+        if pcg:
+            out["cg_iterations"], out["cg_unconverged"] = int(summary[7]), int(summary[11])
         if focal:
             out["cameras"], out["num_free_cameras"] = cameras_out, int(summary[10])
         return _call.raise_with_outputs(host_status.tolist(), out, "image", IMAGE_STATUS)      # every other image is complete: the error carries the call's outputs

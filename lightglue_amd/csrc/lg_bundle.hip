@@ -17,6 +17,10 @@
 // overwrites held columns (identity, zero coupling, zero right-hand side); ba_backsolve<true> also writes the trial cameras.  The FOCAL kernels take
 // BaFocalArgs, so the other two entry points' kernels keep their argument block (profiles/bundle_adjust_focal.md lists registers and scratch of the FOCAL
 // instantiations; profiles/ab_track_solver_steps.md those of the one back substitution).
+// lg_bundle_adjust_pcg runs lg_bundle_adjust_robust's list with the solve swapped: ba_pcg_setup (one workgroup per image: U', b, M = S_aa^-1, the start of the
+// solve) and, max_cg_iterations times, ba_pcg_tracks (one lane per track: u), ba_pcg_images (one workgroup per image: q = S p, its p.q) and ba_pcg_step (ONE
+// workgroup: the dots, alpha, beta, x, r, z, p, the solver's record, the trial poses when the solve ends); S is never formed and its workspace has none
+// (profiles/bundle_adjust_pcg.md lists registers and scratch).
 // The track lists (scan / fill / sort, "adjusted" = track_listed) and exp of a rotation vector are lg_solver_steps.h's, shared with lg_positioning.hip.
 // No kernel waits on another workgroup.  The state lives twice (pose and point buffers 0 / 1): head->sel names the accepted one, a trial is written into the
 // other and accepting it flips sel.  Every kernel of an iteration returns at once when head->converged is set (uniform over the grid: only ba_decide writes it).
@@ -611,6 +615,376 @@ template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba
     if (!fin) atomicOr(&a.head->fail, 1);
 }
 
+// ------------------------------------------------------------------ lg_bundle_adjust_pcg: the reduced camera system solved by preconditioned conjugate gradients
+// S is never formed: per solver iteration q = S p is one pass over the tracks (u = Vi sum of W^T p) and one over the images (q = U' p - sum of W u), and ONE
+// workgroup does the two dot products, alpha, beta and the vector updates.  Every launch of the whole budget is enqueued; the step kernel alone writes
+// BaPcgHead (the call's first setup launch clears it), and once `done` names the running Levenberg-Marquardt iteration (or the trial has failed, or the call converged) the rest return at once.
+// The bodies of the trial pose and of the track's sum of W^T p stand here a second time, next to ba_backsolve_kernel's and ba_trial_points_kernel's: called
+// from those kernels as shared device functions they changed the kernels' instruction streams, which this file keeps (profiles/bundle_adjust_pcg.md)
+constexpr int PCG_THREADS = 64, PCG_STEP_THREADS = 1024, PCG_PARTIALS = 256;        // setup and images: one wave per image, a tile is 64 rows
+constexpr int PCG_NT = 21, PCG_SUMS = 2 * PCG_NT + 12;                               // E_aa's lower triangle, U's upper triangle, g, the sum of W y
+
+struct BaPcgHead { double rz, rz0; int done, cg_total, unconverged, pad; };          // done: 1 + the Levenberg-Marquardt iteration (counted over the call) whose solve ended
+static_assert(sizeof(BaPcgHead) <= 256, "the record of the solver is 256 bytes");
+struct BaPcgArgs : BaArgs {
+    BaPcgHead* ph; double* r; double* z; double* p; double* q; double* U; double* M; double* pq; double* rz; double* u;      // x is `delta`; U, M [images][36]; u [tracks][3]
+    double tol; int budget;
+};
+
+// entry r of (6 x 6 row-major) m times v: the products over c ascending, the first starts the sum
+__device__ __forceinline__ double pcg_row(const double* m, int r, const double (&v)[6]) {
+    double s = m[6 * r] * v[0];
+#pragma unroll
+    for (int c = 1; c < 6; ++c) s += m[6 * r + c] * v[c];
+    return s;
+}
+__device__ __forceinline__ double pcg_dot6(const double (&x)[6], const double (&y)[6]) {
+    double s = x[0] * y[0];
+#pragma unroll
+    for (int e = 1; e < 6; ++e) s += x[e] * y[e];
+    return s;
+}
+
+// one workgroup (one wave) per image: U', b, M = S_aa^-1 and the start of the solve (x = 0, r = b, z = M b, p = z, the image's r.z).  A tile of 64 rows at a
+// time: lane t linearises row t (A, r, W, Y = W Vi, W y, how often the row's track is seen in this image) into LDS, then lane e < 54 adds its entry over the
+// tile's active rows in ascending order.  E_aa as in ba_reduce_kernel: the row's own W once per observation of its track in the image with the squared
+// loss; with a robust loss every such observation's own W, formed by the entry lanes (rare)
+template <int LOSS> __global__ __launch_bounds__(PCG_THREADS) void ba_pcg_setup_kernel(BaPcgArgs a, int lm) {
+    constexpr bool ROBUST = LOSS != LG_BA_LOSS_SQUARED;
+    __shared__ double sA[PCG_THREADS][12], sR[PCG_THREADS][2], sWy[PCG_THREADS][6], sY[PCG_THREADS][18], sW[PCG_THREADS][18], sX[PCG_THREADS][3], sS[PCG_SUMS], sL[PCG_NT], sM[36], sV[12];
+    __shared__ int sCnt[PCG_THREADS], sOff[PCG_THREADS], sLen[PCG_THREADS];
+    const int ia = blockIdx.x, t = threadIdx.x;
+    if (lm == 0 && ia == 0 && t == 0) *a.ph = BaPcgHead{};   // the call's first solver launch clears the record (no launch of this one reads it)
+    if (a.head->converged) return;
+    const long long at = (long long)ia * 6;
+    if (!ba_free(a, ia)) {                                  // no unknowns: every entry is 0
+        if (t < 6) { a.delta[at + t] = 0.0; a.r[at + t] = 0.0; a.z[at + t] = 0.0; a.p[at + t] = 0.0; a.q[at + t] = 0.0; }
+        if (t == 0) { a.pq[ia] = 0.0; a.rz[ia] = 0.0; }
+        return;
+    }
+    const int s = a.head->sel;
+    const double lambda = a.head->lambda;
+    const double* Pa = ba_pose(a, s, ia);
+    const double* cama = a.rec[ia].cam;
+    // lane e: 0 .. 20 entry (er, ec), ec <= er, of E_aa (row-major lower triangle); 21 .. 41 entry (er, ec), er <= ec, of U (row-major upper triangle);
+    // 42 .. 47 g; 48 .. 53 the sum of W y
+    int er = 0, ec = 0;
+    if (t < PCG_NT) { int left = t; while (left > er) { left -= er + 1; ++er; } ec = left; }
+    else if (t < 2 * PCG_NT) { int left = t - PCG_NT; while (left >= 6 - er) { left -= 6 - er; ++er; } ec = er + left; }
+    double acc = 0.0;
+    for (int i0 = 0; i0 < a.n; i0 += PCG_THREADS) {
+        __syncthreads();                                    // the previous tile has been read
+        const int i = i0 + t;
+        const long long v = (long long)ia * a.n + i;
+        int cnt = 0;
+        if (i < a.n && a.node_state[v] == 1) {
+            const int j = (int)a.track_id[v], len = a.tcnt[j], off = a.toff[j];
+            const double* Xp = ba_point(a, s, j);
+            const double* Vi = a.Vinv + (long long)j * 9;
+            const double* y = a.y + (long long)j * 3;
+            double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+            ba_project(Pa, Xp, p);
+            ba_linearise<LOSS>(a, Pa, cama, p, a.kpts + v * 2, A0, A1, B0, B1, rx, ry);
+            sX[t][0] = Xp[0]; sX[t][1] = Xp[1]; sX[t][2] = Xp[2];
+            sR[t][0] = rx; sR[t][1] = ry;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                sA[t][q] = A0[q]; sA[t][6 + q] = A1[q];
+                const double w0 = A0[q] * B0[0] + A1[q] * B1[0], w1 = A0[q] * B0[1] + A1[q] * B1[1], w2 = A0[q] * B0[2] + A1[q] * B1[2];
+                sW[t][3 * q] = w0; sW[t][3 * q + 1] = w1; sW[t][3 * q + 2] = w2;
+#pragma unroll
+                for (int m = 0; m < 3; ++m) sY[t][3 * q + m] = (w0 * Vi[m] + w1 * Vi[3 + m]) + w2 * Vi[6 + m];
+                sWy[t][q] = (w0 * y[0] + w1 * y[1]) + w2 * y[2];
+            }
+            for (int l = 0; l < len; ++l) cnt += a.limg[off + l] == ia ? 1 : 0;     // >= 1: the row itself
+            sOff[t] = off; sLen[t] = len;
+        }
+        sCnt[t] = cnt;
+        __syncthreads();
+        if (t >= PCG_SUMS) continue;
+        const int rows = min(PCG_THREADS, a.n - i0);
+        for (int q = 0; q < rows; ++q) {
+            const int times = sCnt[q];
+            if (!times) continue;
+            if (t < PCG_NT) {
+                if constexpr (ROBUST) if (times > 1) {      // every observation of the row's track in this image has a weight of its own
+                    for (int l = 0; l < sLen[q]; ++l) {
+                        if (a.limg[sOff[q] + l] != ia) continue;
+                        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry, a0 = 0.0, a1 = 0.0;
+                        ba_project(Pa, sX[q], p);
+                        ba_linearise<LOSS>(a, Pa, cama, p, a.kpts + (long long)a.list[sOff[q] + l] * 2, A0, A1, B0, B1, rx, ry);
+#pragma unroll
+                        for (int cc = 0; cc < 6; ++cc) if (cc == ec) { a0 = A0[cc]; a1 = A1[cc]; }
+                        acc += (sY[q][3 * er] * (a0 * B0[0] + a1 * B1[0]) + sY[q][3 * er + 1] * (a0 * B0[1] + a1 * B1[1])) + sY[q][3 * er + 2] * (a0 * B0[2] + a1 * B1[2]);
+                    }
+                    continue;
+                }
+                const double term = (sY[q][3 * er] * sW[q][3 * ec] + sY[q][3 * er + 1] * sW[q][3 * ec + 1]) + sY[q][3 * er + 2] * sW[q][3 * ec + 2];
+                for (int m = 0; m < times; ++m) acc += term;
+            } else if (t < 2 * PCG_NT) acc += sA[q][er] * sA[q][ec] + sA[q][6 + er] * sA[q][6 + ec];
+            else if (t < 2 * PCG_NT + 6) acc += sA[q][t - 2 * PCG_NT] * sR[q][0] + sA[q][6 + t - 2 * PCG_NT] * sR[q][1];
+            else acc += sWy[q][t - (2 * PCG_NT + 6)];
+        }
+    }
+    if (t < PCG_SUMS) sS[t] = acc;
+    __syncthreads();
+    // U' (mirrored, its diagonal damped) and b = (sum of W y) - g
+    if (t < 36) {
+        const int r = t / 6, c = t - 6 * r, lo = min(r, c), hi = max(r, c);
+        double u = sS[PCG_NT + lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
+        if (r == c) u = ba_damped(u, lambda);
+        a.U[(long long)ia * 36 + t] = u;
+    }
+    if (t < 6) sV[t] = sS[2 * PCG_NT + 6 + t] - sS[2 * PCG_NT + t];
+    // lane 0: S_aa = U' - E_aa = L L^T by rows, in registers; a pivot that is not > 0 (or not finite) fails the trial and 1 takes its place
+    if (t == 0) {
+        double L[PCG_NT];
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                double u = sS[PCG_NT + j * 6 - j * (j - 1) / 2 + (i - j)];
+                if (i == j) u = ba_damped(u, lambda);
+                double d = u - sS[i * (i + 1) / 2 + j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) d = d - L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+                if (i == j) {
+                    if (!(isfinite(d) && d > 0.0)) { bad = true; d = 1.0; }
+                    L[i * (i + 1) / 2 + j] = sqrt(d);
+                } else L[i * (i + 1) / 2 + j] = d / L[j * (j + 1) / 2 + j];
+            }
+#pragma unroll
+        for (int e = 0; e < PCG_NT; ++e) sL[e] = L[e];
+        if (bad) atomicOr(&a.head->fail, 1);
+    }
+    __syncthreads();
+    // lane c < 6: column c of M = S_aa^-1: L w = e_c forwards, L^T m = w backwards
+    if (t < 6) {
+        double w[6], m[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double d = i == t ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < i; ++k) d = d - sL[i * (i + 1) / 2 + k] * w[k];
+            w[i] = d / sL[i * (i + 1) / 2 + i];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+            double d = w[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) d = d - sL[k * (k + 1) / 2 + i] * m[k];
+            m[i] = d / sL[i * (i + 1) / 2 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { a.M[(long long)ia * 36 + 6 * i + t] = m[i]; sM[6 * i + t] = m[i]; }
+    }
+    __syncthreads();
+    if (t < 6) {
+        double b[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) b[e] = sV[e];
+        const double zr = pcg_row(sM, t, b);
+        a.delta[at + t] = 0.0; a.r[at + t] = b[t]; a.z[at + t] = zr; a.p[at + t] = zr; a.q[at + t] = 0.0;
+        sV[6 + t] = zr;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double b[6], z[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) { b[e] = sV[e]; z[e] = sV[6 + e]; }
+        a.rz[ia] = pcg_dot6(b, z); a.pq[ia] = 0.0;
+    }
+}
+
+// the solve of Levenberg-Marquardt iteration `lm` (counted over the call) is over, or not to be run
+__device__ __forceinline__ bool pcg_idle(const BaPcgArgs& a, int lm) { return a.head->converged || a.head->fail || a.ph->done == lm + 1; }
+
+// one lane per listed track: u = Vi sum of W^T p (ba_trial_points_kernel's sum with p in place of the step)
+template <int LOSS> __global__ __launch_bounds__(BA_THREADS) void ba_pcg_tracks_kernel(BaPcgArgs a, int lm) {
+    if (pcg_idle(a, lm)) return;
+    const int j = blockIdx.x * BA_THREADS + threadIdx.x;
+    if (j >= a.tracks || !track_listed(a, j)) return;
+    const int s = a.head->sel, len = a.tcnt[j], off = a.toff[j];
+    const double* Xp = ba_point(a, s, j);
+    const double X[3] = {Xp[0], Xp[1], Xp[2]};
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int q = 0; q < len; ++q) {
+        const int k = a.limg[off + q];
+        if (!ba_free(a, k)) continue;
+        const double* P = ba_pose(a, s, k);
+        const double* d = a.p + (long long)k * 6;
+        double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+        ba_project(P, X, p);
+        ba_linearise<LOSS>(a, P, a.rec[k].cam, p, a.kpts + (long long)a.list[off + q] * 2, A0, A1, B0, B1, rx, ry);
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            double w = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) w += (A0[r] * B0[m] + A1[r] * B1[m]) * d[r];
+            acc[m] += w;
+        }
+    }
+    const double* Vi = a.Vinv + (long long)j * 9;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) a.u[(long long)j * 3 + r] = (Vi[3 * r] * acc[0] + Vi[3 * r + 1] * acc[1]) + Vi[3 * r + 2] * acc[2];
+}
+
+// one workgroup (one wave) per image: q = U' p - sum of W u over its active rows in ascending row order, and the image's p.q.  Lane t forms W u of row t of a
+// tile; lanes 0 .. 5 add their entry over the tile's active rows (the wave's ballot names them) in ascending order
+template <int LOSS> __global__ __launch_bounds__(PCG_THREADS) void ba_pcg_images_kernel(BaPcgArgs a, int lm) {
+    __shared__ double sT[PCG_THREADS][7], sQ[6];
+    if (pcg_idle(a, lm)) return;                            // uniform over the grid: no launch between the step kernels writes any of the three
+    const int ia = blockIdx.x, t = threadIdx.x;
+    if (!ba_free(a, ia)) return;                            // q and the partial stay 0 (ba_pcg_setup_kernel)
+    const int s = a.head->sel;
+    const double* Pa = ba_pose(a, s, ia);
+    const double* cama = a.rec[ia].cam;
+    double acc = 0.0;
+    for (int i0 = 0; i0 < a.n; i0 += PCG_THREADS) {
+        __syncthreads();                                    // the previous tile has been read
+        const int i = i0 + t;
+        const long long v = (long long)ia * a.n + i;
+        const bool active = i < a.n && a.node_state[v] == 1;
+        if (active) {
+            const int j = (int)a.track_id[v];
+            const double* u = a.u + (long long)j * 3;
+            double p[3], A0[6], A1[6], B0[3], B1[3], rx, ry;
+            ba_project(Pa, ba_point(a, s, j), p);
+            ba_linearise<LOSS>(a, Pa, cama, p, a.kpts + v * 2, A0, A1, B0, B1, rx, ry);
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+                sT[t][r] = ((A0[r] * B0[0] + A1[r] * B1[0]) * u[0] + (A0[r] * B0[1] + A1[r] * B1[1]) * u[1]) + (A0[r] * B0[2] + A1[r] * B1[2]) * u[2];
+        }
+        unsigned long long mask = __ballot(active);
+        __syncthreads();
+        if (t < 6)
+            while (mask) { const int q = __ffsll((long long)mask) - 1; mask &= mask - 1; acc += sT[q][t]; }
+    }
+    if (t < 6) {
+        double p[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) p[e] = a.p[(long long)ia * 6 + e];
+        const double qv = pcg_row(a.U + (long long)ia * 36, t, p) - acc;
+        a.q[(long long)ia * 6 + t] = qv;
+        sQ[t] = qv;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double p[6], q[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) { p[e] = a.p[(long long)ia * 6 + e]; q[e] = sQ[e]; }
+        a.pq[ia] = pcg_dot6(p, q);
+    }
+}
+
+// the images' partials d [images] added in THE fixed order: partial m < 256 = d[m] + d[m + 256] + .. ascending from 0, then a halving tree over the partials.
+// All PCG_STEP_THREADS threads call it; d may have been written by this workgroup before the call
+__device__ __forceinline__ double pcg_sum_images(const double* d, int images, double* part) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    if (t < PCG_PARTIALS) {
+        double s = 0.0;
+        for (int k = t; k < images; k += PCG_PARTIALS) s += d[k];
+        part[t] = s;
+    }
+    __syncthreads();
+    for (int h = PCG_PARTIALS / 2; h >= 1; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+// ONE workgroup, solver iteration `it` of Levenberg-Marquardt iteration `lm`: p.q, alpha, x, r, z = M r, r.z, the stopping test, beta, p; the record; when the
+// solve ends the trial poses (ba_backsolve_kernel's).  Strided loops over the images, no per-image LDS array
+__global__ __launch_bounds__(PCG_STEP_THREADS) void ba_pcg_step_kernel(BaPcgArgs a, int lm, int it) {
+    __shared__ double part[PCG_PARTIALS];
+    const int t = threadIdx.x;
+    BaPcgHead& h = *a.ph;
+    if (pcg_idle(a, lm)) return;
+    const int s = a.head->sel;
+    double rz = h.rz, rz0 = h.rz0;                          // (read by all before lane 0 writes them again, behind the barriers of pcg_sum_images)
+    bool end = false, bad = false;
+    if (it == 0) {
+        rz = rz0 = pcg_sum_images(a.rz, a.images, part);
+        if (t == 0) { h.rz = rz; h.rz0 = rz0; }
+        if (!(isfinite(rz) && rz >= 0.0)) bad = true;
+        else if (rz == 0.0) end = true;                     // b = 0 (no free image among them): x = 0
+    }
+    double rz_new = rz;
+    if (!bad && !end) {
+        const double pq = pcg_sum_images(a.pq, a.images, part);
+        if (!(isfinite(pq) && pq > 0.0)) bad = true;
+        else {
+            const double alpha = rz / pq;
+            for (int k = t; k < a.images; k += PCG_STEP_THREADS) {
+                if (!ba_free(a, k)) continue;
+                const long long at = (long long)k * 6;
+                double r[6], z[6];
+#pragma unroll
+                for (int e = 0; e < 6; ++e) {
+                    a.delta[at + e] = a.delta[at + e] + alpha * a.p[at + e];
+                    r[e] = a.r[at + e] - alpha * a.q[at + e];
+                    a.r[at + e] = r[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 6; ++e) { z[e] = pcg_row(a.M + (long long)k * 36, e, r); a.z[at + e] = z[e]; }
+                a.rz[k] = pcg_dot6(r, z);
+            }
+            rz_new = pcg_sum_images(a.rz, a.images, part);
+            if (t == 0) h.cg_total += 1;
+            if (!(isfinite(rz_new) && rz_new >= 0.0)) bad = true;
+            else {
+                const bool reached = sqrt(rz_new) <= a.tol * sqrt(rz0);
+                end = reached || it == a.budget - 1;
+                if (end && !reached && t == 0) h.unconverged += 1;
+            }
+        }
+    }
+    if (bad) { if (t == 0) atomicOr(&a.head->fail, 1); return; }
+    if (!end) {
+        const double beta = rz_new / rz;
+        for (int k = t; k < a.images; k += PCG_STEP_THREADS) {
+            if (!ba_free(a, k)) continue;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) a.p[(long long)k * 6 + e] = a.z[(long long)k * 6 + e] + beta * a.p[(long long)k * 6 + e];
+        }
+        if (t == 0) h.rz = rz_new;
+        return;
+    }
+    if (t == 0) h.done = lm + 1;
+    int fail = 0;
+    for (int k = t; k < a.images; k += PCG_STEP_THREADS) {
+        const double* P = ba_pose(a, s, k);
+        double* out = a.pose + ((long long)(s ^ 1) * a.images + k) * 12;
+        if (!ba_free(a, k)) {
+            for (int q = 0; q < 12; ++q) out[q] = P[q];
+            continue;
+        }
+        double x[6], Q[9];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) x[q] = a.delta[(long long)k * 6 + q];
+        so3_exp(x, Q);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double v = (Q[3 * i] * P[j] + Q[3 * i + 1] * P[4 + j]) + Q[3 * i + 2] * P[8 + j];
+                if (j == 3) v = v + x[3 + i];
+                if (!isfinite(v)) fail = 1;
+                out[4 * i + j] = v;
+            }
+    }
+    if (fail) atomicOr(&a.head->fail, 1);
+}
+
+// one lane, behind the scatter: the two counters of the solver
+__global__ void ba_pcg_summary_kernel(BaPcgArgs a) {
+    if (blockIdx.x || threadIdx.x) return;
+    a.summary[7] = (double)a.ph->cg_total; a.summary[11] = (double)a.ph->unconverged;
+}
+
 // ------------------------------------------------------------------ the outputs
 // ROBUST (lg_bundle_adjust_robust): summary [12], and a track or image that moved in an earlier stage returns its last accepted state
 // FOCAL (lg_bundle_adjust_focal): cameras_out, and summary [10] = the cameras that were free in any stage
@@ -665,7 +1039,10 @@ template <bool ROBUST, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void
 }
 
 // ------------------------------------------------------------------ the launch list of both entry points: `rounds` filters, rounds + 1 stages of `iterations`
-template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const BaArgsOf<FOCAL>& a, const BaLayout& L, int iterations, int rounds, hipStream_t s) {
+// PCG (lg_bundle_adjust_pcg): the solve is setup and `budget` times tracks, images, step instead of reduce, the Cholesky panels and the back substitution
+template <int LOSS, bool ROBUST, bool FOCAL = false, bool PCG = false>
+static int ba_enqueue(const std::conditional_t<PCG, BaPcgArgs, BaArgsOf<FOCAL>>& a, const BaLayout& L, int iterations, int rounds, hipStream_t s) {
+    static_assert(!(PCG && FOCAL), "the iterative solver knows six unknowns per image");
     auto blocks = [](long long items) { return dim3((unsigned)((items + BA_THREADS - 1) / BA_THREADS)); };
     const dim3 th(BA_THREADS);
     const BaArgs& b = a;                                        // what the kernels that know no focal column take
@@ -690,18 +1067,29 @@ template <int LOSS, bool ROBUST, bool FOCAL = false> static int ba_enqueue(const
         }
         for (int it = 0; it < iterations; ++it) {
             if (T) hipLaunchKernelGGL((ba_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
-            hipLaunchKernelGGL((ba_reduce_kernel<LOSS, FOCAL>), dim3(K, (K + BA_CHUNK<FOCAL> - 1) / BA_CHUNK<FOCAL>), th, 0, s, a);
-            for_cholesky_panels((int)L.dim, 1, [&](int p, int tiles_below) {
-                hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, b, p);
-                hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles_below), th, 0, s, b, p);
-            });
-            hipLaunchKernelGGL(ba_backsolve_kernel<FOCAL>, dim3(1), th, 0, s, a);
+            if constexpr (PCG) {
+                const int lm = stage * iterations + it;
+                hipLaunchKernelGGL(ba_pcg_setup_kernel<LOSS>, dim3(K), dim3(PCG_THREADS), 0, s, a, lm);
+                for (int cg = 0; cg < a.budget; ++cg) {
+                    if (T) hipLaunchKernelGGL(ba_pcg_tracks_kernel<LOSS>, blocks(T), th, 0, s, a, lm);
+                    hipLaunchKernelGGL(ba_pcg_images_kernel<LOSS>, dim3(K), dim3(PCG_THREADS), 0, s, a, lm);
+                    hipLaunchKernelGGL(ba_pcg_step_kernel, dim3(1), dim3(PCG_STEP_THREADS), 0, s, a, lm, cg);
+                }
+            } else {
+                hipLaunchKernelGGL((ba_reduce_kernel<LOSS, FOCAL>), dim3(K, (K + BA_CHUNK<FOCAL> - 1) / BA_CHUNK<FOCAL>), th, 0, s, a);
+                for_cholesky_panels((int)L.dim, 1, [&](int p, int tiles_below) {
+                    hipLaunchKernelGGL(ba_cholesky_diag_kernel, dim3(1), th, 0, s, b, p);
+                    hipLaunchKernelGGL(ba_cholesky_rows_kernel, dim3(tiles_below), th, 0, s, b, p);
+                });
+                hipLaunchKernelGGL(ba_backsolve_kernel<FOCAL>, dim3(1), th, 0, s, a);
+            }
             if (T) hipLaunchKernelGGL((ba_trial_points_kernel<LOSS, FOCAL>), blocks(T), th, 0, s, a);
             hipLaunchKernelGGL((ba_cost_kernel<LOSS, FOCAL>), dim3(K), th, 0, s, a, 1);
             hipLaunchKernelGGL(ba_decide_kernel, dim3(1), dim3(64), 0, s, b, 0);
         }
     }
     hipLaunchKernelGGL((ba_scatter_kernel<ROBUST, FOCAL>), blocks(all), th, 0, s, a);
+    if constexpr (PCG) hipLaunchKernelGGL(ba_pcg_summary_kernel, dim3(1), dim3(64), 0, s, a);
     HIPCHK(hipGetLastError());
     return LG_OK;
 }
@@ -732,6 +1120,25 @@ template <bool FOCAL> static int ba_enqueue_robust(BaArgsOf<FOCAL> a, const BaRo
         case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
         case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
         default: return ba_enqueue<LG_BA_LOSS_SQUARED, true, FOCAL>(a, L.base, r.base.num_iterations, r.filter_rounds, s);
+    }
+}
+
+// lg_bundle_adjust_pcg: the robust settings and the solver's arrays behind a checked call's arguments, and the launch list with the loss compiled in
+static int ba_enqueue_pcg(const lg_bundle_pcg_io& io, const BaPcgLayout& L, void* hip_stream) {
+    const lg_bundle_robust_io& r = io.base;
+    const Carved ws(r.base.workspace);
+    BaPcgArgs a{};
+    static_cast<BaArgs&>(a) = ba_args(r.base, L.base.base);
+    a.lc = r.loss_scale; a.lc2 = r.loss_scale * r.loss_scale; a.fe2 = r.max_reproj_error * r.max_reproj_error;
+    a.tmov = r.filter_rounds > 0 ? ws.ints(L.base.tmov) : nullptr;
+    a.ph = ws.as<BaPcgHead>(L.head); a.r = ws.f64(L.r); a.z = ws.f64(L.z); a.p = ws.f64(L.p); a.q = ws.f64(L.q); a.U = ws.f64(L.U); a.M = ws.f64(L.M);
+    a.pq = ws.f64(L.pq); a.rz = ws.f64(L.rz); a.u = ws.f64(L.u);
+    a.tol = io.cg_tolerance; a.budget = io.max_cg_iterations;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    switch (r.loss) {
+        case LG_BA_LOSS_HUBER: return ba_enqueue<LG_BA_LOSS_HUBER, true, false, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
+        case LG_BA_LOSS_CAUCHY: return ba_enqueue<LG_BA_LOSS_CAUCHY, true, false, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
+        default: return ba_enqueue<LG_BA_LOSS_SQUARED, true, false, true>(a, L.base.base, r.base.num_iterations, r.filter_rounds, s);
     }
 }
 
@@ -784,6 +1191,24 @@ int lg_bundle_adjust_focal(const lg_bundle_focal_io* io, void* hip_stream) {
     if (const int rc = ba_focal_check_settings(stage, *io, L)) return rc;
     const BaFocalArgs a{ba_args(r.base, L.base.base), io->constant_camera, Carved(r.base.workspace).f64(L.cam), io->cameras_out};
     return ba_enqueue_robust<true>(a, L.base, r, hip_stream);
+}
+
+int64_t lg_bundle_pcg_workspace_bytes(int64_t images, int32_t n, int64_t tracks, uint32_t flags) {
+    BaPcgLayout L;
+    return ba_pcg_layout(images, n, tracks, flags, L) ? -1 : L.total;
+}
+
+int lg_bundle_adjust_pcg(const lg_bundle_pcg_io* io, void* hip_stream) {
+    static const char* const stage = "lg_bundle_adjust_pcg";
+    const auto refuse = [](const char* why) { return set_error(LG_ERR_INVALID, std::string(stage) + ": " + why); };
+    if (!io) return refuse("null io");
+    const lg_bundle_robust_io& r = io->base;
+    BaPcgLayout L;
+    if (const char* why = ba_pcg_layout(r.base.images, r.base.n, r.base.tracks, r.base.flags, L)) return refuse(why);
+    if (const char* why = ba_robust_settings_error(r.loss, r.loss_scale, r.filter_rounds, r.max_reproj_error)) return refuse(why);
+    if (const char* why = ba_pcg_settings_error(r.base.num_iterations, r.filter_rounds, io->max_cg_iterations, io->pad, io->cg_tolerance)) return refuse(why);
+    if (const int rc = ba_check_settings(stage, "lg_bundle_pcg_workspace_bytes", r.base, L.base.base.nodes, L.total)) return rc;
+    return ba_enqueue_pcg(*io, L, hip_stream);
 }
 
 }  // extern "C"

@@ -188,16 +188,18 @@ inline const char* tri_robust_layout(long long images, long long n, uint32_t fla
 // inverse times its gradient: 156 bytes in all).  W is not stored: it is formed again from the pose and the point where it is needed
 constexpr uint32_t BA_KNOWN_FLAGS = 0u;
 struct BaLayout { long long nodes, dim, head, rec, pose, delta, icost, S, list, limg, tcnt, toff, tcur, X, Vinv, y, total; };
-inline const char* ba_layout(long long images, long long n, long long tracks, uint32_t flags, BaLayout& L, long long cols = 6) {   // cols: unknowns per image
+// dense = false (lg_bundle_adjust_pcg): no S, and the image bound is LG_BA_PCG_MAX_IMAGES
+inline const char* ba_layout(long long images, long long n, long long tracks, uint32_t flags, BaLayout& L, long long cols = 6, bool dense = true) {   // cols: unknowns per image
     if (flags & ~BA_KNOWN_FLAGS) return "undefined flag bits (the bundle adjuster defines none)";
     if (n < 0 || n > LG_MAX_KEYPOINTS) return "n must lie in [0, LG_MAX_KEYPOINTS]";
-    if (images < 1 || images > LG_BA_MAX_IMAGES) return "images must lie in [1, LG_BA_MAX_IMAGES]";
+    if (dense && (images < 1 || images > LG_BA_MAX_IMAGES)) return "images must lie in [1, LG_BA_MAX_IMAGES]";
+    if (!dense && (images < 1 || images > LG_BA_PCG_MAX_IMAGES)) return "images must lie in [1, LG_BA_PCG_MAX_IMAGES]";
     if (images * n > LG_MAX_ROWS) return "images x n must lie in [0, LG_MAX_ROWS]";
     if (tracks < 0 || tracks > images * n / 2) return "tracks must lie in [0, images x n / 2]";
     L.nodes = images * n; L.dim = cols * images;
     Bump bp;
     L.head = bp.take(256); L.rec = bp.take(images * 64); L.pose = bp.take(images * 192); L.delta = bp.take(images * cols * 8); L.icost = bp.take(images * 8);
-    L.S = bp.take((L.dim + 1) * L.dim * 8);
+    L.S = bp.take(dense ? (L.dim + 1) * L.dim * 8 : 0);
     L.list = bp.take(L.nodes * 4); L.limg = bp.take(L.nodes * 4);
     L.tcnt = bp.take(tracks * 4); L.toff = bp.take(tracks * 4); L.tcur = bp.take(tracks * 4);
     L.X = bp.take(tracks * 48); L.Vinv = bp.take(tracks * 72); L.y = bp.take(tracks * 24); L.total = bp.used;
@@ -216,8 +218,8 @@ inline int ba_check_settings(const char* stage, const char* size_function, const
 }
 // lg_bundle_adjust_robust: lg_bundle_adjust's layout, then one int32 per track (it moved in an earlier stage)
 struct BaRobustLayout { BaLayout base; long long tmov, total; };
-inline const char* ba_robust_layout(long long images, long long n, long long tracks, uint32_t flags, BaRobustLayout& L, long long cols = 6) {
-    if (const char* why = ba_layout(images, n, tracks, flags, L.base, cols)) return why;
+inline const char* ba_robust_layout(long long images, long long n, long long tracks, uint32_t flags, BaRobustLayout& L, long long cols = 6, bool dense = true) {
+    if (const char* why = ba_layout(images, n, tracks, flags, L.base, cols, dense)) return why;
     Bump bp;
     bp.used = L.base.total;
     L.tmov = bp.take(tracks * 4); L.total = bp.used;
@@ -228,6 +230,26 @@ inline const char* ba_robust_settings_error(long long loss, double loss_scale, l
     if (loss != LG_BA_LOSS_SQUARED && !positive(loss_scale)) return "loss_scale must be > 0 (and finite) with a robust loss";
     if (filter_rounds < 0 || filter_rounds > LG_BA_MAX_FILTER_ROUNDS) return "filter_rounds must lie in [0, LG_BA_MAX_FILTER_ROUNDS]";
     if (filter_rounds > 0 && !positive(max_reproj_error)) return "max_reproj_error must be > 0 (and finite) with filter_rounds > 0";
+    return nullptr;
+}
+// lg_bundle_adjust_pcg: lg_bundle_adjust_robust's layout without S, then a 256-byte record of the solver; per image r, z, p, q (4 x 48 bytes), U' and M
+// (2 x 288) and its partials of p.q and r.z (2 x 8): 784 bytes; per track u (24 bytes).  x is the step (`delta`) of lg_bundle_adjust's layout
+struct BaPcgLayout { BaRobustLayout base; long long head, r, z, p, q, U, M, pq, rz, u, total; };
+inline const char* ba_pcg_layout(long long images, long long n, long long tracks, uint32_t flags, BaPcgLayout& L) {
+    if (const char* why = ba_robust_layout(images, n, tracks, flags, L.base, 6, false)) return why;
+    Bump bp;
+    bp.used = L.base.total;
+    L.head = bp.take(256); L.r = bp.take(images * 48); L.z = bp.take(images * 48); L.p = bp.take(images * 48); L.q = bp.take(images * 48);
+    L.U = bp.take(images * 288); L.M = bp.take(images * 288); L.pq = bp.take(images * 8); L.rz = bp.take(images * 8); L.u = bp.take(tracks * 24); L.total = bp.used;
+    return nullptr;
+}
+// the solver's own settings; the product counts the solver iterations the call enqueues
+inline const char* ba_pcg_settings_error(long long num_iterations, long long filter_rounds, long long max_cg_iterations, long long pad, double cg_tolerance) {
+    if (pad != 0) return "pad must be 0";
+    if (max_cg_iterations < 1 || max_cg_iterations > LG_BA_PCG_MAX_CG_ITERATIONS) return "max_cg_iterations must lie in [1, LG_BA_PCG_MAX_CG_ITERATIONS]";
+    if (!(cg_tolerance > 0.0 && cg_tolerance < 1.0)) return "cg_tolerance must lie in (0, 1)";
+    if (num_iterations >= 1 && filter_rounds >= 0 && num_iterations * (filter_rounds + 1) * max_cg_iterations > LG_BA_PCG_MAX_SOLVER_ITERATIONS)
+        return "num_iterations x (filter_rounds + 1) x max_cg_iterations must not exceed LG_BA_PCG_MAX_SOLVER_ITERATIONS";
     return nullptr;
 }
 // lg_bundle_adjust_focal: lg_bundle_adjust_robust's layout with 7 unknowns per image (the step is 56 bytes, S is (7 images + 1) x 7 images), then the camera

@@ -18,7 +18,11 @@ tests/bundle_robust_oracle.py).  `--contaminate F`: after the triangulation, the
 adjuster's cameras get fx and fy multiplied by 1 + F in the even images and 1 - F in the odd ones (the tracks are still those triangulated under the true
 cameras); the result line then holds the relative focal error per budget before and after (median and worst over the images).
 
-usage: bench_bundle_adjust.py [--images 16] [--kpts 2048] [--runs 5] [--host-iterations 2] [--only-adjust] [--loss squared|huber|cauchy] [--loss-scale 2]
+`--solver pcg [--max-cg-iterations 100 --cg-tolerance 1e-6]`: the iterative solver (lg_bundle_adjust_pcg; the host route is then tests/bundle_pcg_oracle.py);
+the result line then holds the solver iterations and the iterations that ended on the budget.  Beyond 256 images this tool's exhaustive pair list stops being
+a workload: tools/bench_bundle_pcg_scale.py times the solver on planted scenes there.
+
+usage: bench_bundle_adjust.py [--solver cholesky|pcg] [--max-cg-iterations 100] [--cg-tolerance 1e-6] [--images 16] [--kpts | --keypoints 2048] [--runs 5] [--host-iterations 2] [--only-adjust] [--loss squared|huber|cauchy] [--loss-scale 2]
                               [--filter-rounds 0] [--max-reproj-error 4] [--contaminate 0] [--refine-focal] [--focal-error 0]"""
 import argparse
 import itertools
@@ -34,6 +38,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests")); sys.path.insert(0, str(ROOT / "tools"))
 import bundle_focal_oracle as F
 import bundle_oracle as B
+import bundle_pcg_oracle as P
 import bundle_robust_oracle as R
 from abspose_oracle import rodrigues
 from bench_triangulate import CAMERA, replay
@@ -76,7 +81,10 @@ def contaminate(store, tracks, fraction, seed=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=16)
-    ap.add_argument("--kpts", type=int, default=2048)
+    ap.add_argument("--kpts", "--keypoints", type=int, default=2048)
+    ap.add_argument("--solver", default="cholesky", choices=("cholesky", "pcg"), help="pcg: lg_bundle_adjust_pcg, up to 4096 images")
+    ap.add_argument("--max-cg-iterations", type=int, default=100)
+    ap.add_argument("--cg-tolerance", type=float, default=1e-6)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--host-iterations", type=int, default=2, help="iterations of the numpy definition on the host (0: skip)")
     ap.add_argument("--only-adjust", action="store_true", help="one call and nothing else: the run to put under a kernel trace")
@@ -91,6 +99,8 @@ def main():
     conf = dict(loss=args.loss, loss_scale=args.loss_scale, filter_rounds=args.filter_rounds, max_reproj_error=args.max_reproj_error)
     if args.refine_focal:
         conf["refine_focal"] = True
+    if args.solver == "pcg":
+        conf.update(solver="pcg", max_cg_iterations=args.max_cg_iterations, cg_tolerance=args.cg_tolerance)
     if not torch.cuda.is_available():
         raise SystemExit("bench_bundle_adjust.py measures on an MI355X; there is nothing to measure without one")
     K = args.images
@@ -119,7 +129,8 @@ def main():
     outs = {n: fn() for n, fn in runs.items()}                                   # warm-up of every timed shape
     if args.only_adjust:
         ms, out = timed(runs[10])
-        print(json.dumps({"num_iterations": out["num_iterations"], "ms": round(ms, 3)}), flush=True)
+        print(json.dumps({"num_iterations": out["num_iterations"], "ms": round(ms, 3), **({"cg_iterations": out["cg_iterations"]} if "cg_iterations" in out else {})}),
+              flush=True)
         return
     ms, tri_ms = {n: [] for n in runs}, []
     for _ in range(args.runs):
@@ -128,7 +139,7 @@ def main():
             ms[n].append(timed(runs[n])[0])
     res = {"images": K, "kpts": args.kpts, "pairs": int(pairs_dev.shape[0]), "device": torch.cuda.get_device_name(0), "runs": args.runs,
            "tracks": tracks["num_tracks"], "triangulate": stats(tri_ms), **conf, "contaminate": args.contaminate,
-           "planted": 0 if planted is None else int(planted.sum()), "refine_focal": args.refine_focal, "focal_error": args.focal_error, "adjust": []}
+           "planted": 0 if planted is None else int(planted.sum()), "refine_focal": args.refine_focal, "focal_error": args.focal_error, "solver": args.solver, "adjust": []}
     focal_error = lambda c: (c[:, 0].double() / true_cameras[:, 0].double() - 1.0).abs().cpu()
     for n in runs:
         o = outs[n]
@@ -144,6 +155,8 @@ def main():
         res["adjust"][-1].update({"filtered": o["num_filtered"], "filter_stages": o["num_filter_stages"], "tracks_adjusted_at_the_end": int((kept >= 2).sum()),
                                   "clean_above_4px": int((above & ~planted).sum()) if planted is not None else int(above.sum()),
                                   "clean_filtered": int(((o["node_state"] == 7) & ~planted).sum()) if planted is not None else o["num_filtered"]})
+        if args.solver == "pcg":
+            res["adjust"][-1].update({"cg_iterations": o["cg_iterations"], "cg_unconverged": o["cg_unconverged"]})
         if args.refine_focal:
             before, after = focal_error(cameras), focal_error(o["cameras"])
             res["adjust"][-1].update({"free_cameras": o["num_free_cameras"], "focal_error_before_median": round(float(before.median()), 6),
@@ -159,8 +172,9 @@ def main():
                    cams=cameras.cpu().numpy(), poses=start.cpu().numpy(), constant=np.arange(K) < 2)
         t = time.perf_counter()
         robust = args.loss != "squared" or args.filter_rounds > 0
-        host_conf = {k: v for k, v in conf.items() if k != "refine_focal"}
-        host = (F if args.refine_focal else R).adjust(inp, num_iterations=args.host_iterations, **host_conf) if robust or args.refine_focal else B.adjust(inp, num_iterations=args.host_iterations)
+        host_conf = {k: v for k, v in conf.items() if k not in ("refine_focal", "solver")}
+        host = ((P if args.solver == "pcg" else F if args.refine_focal else R).adjust(inp, num_iterations=args.host_iterations, **host_conf)
+                if robust or args.refine_focal or args.solver == "pcg" else B.adjust(inp, num_iterations=args.host_iterations))
         host_ms = (time.perf_counter() - t) * 1e3
         dev = BundleAdjuster(num_iterations=args.host_iterations, **conf).adjust(store, tracks, cameras, start, constant)
         res["host"] = {"threads": 1, "iterations": host["num_iterations"], "ms": round(host_ms, 1), "final_cost": round(host["final_cost"], 3),
