@@ -1302,6 +1302,77 @@ int64_t lg_posegraph_workspace_bytes(int64_t images, int64_t pairs, uint32_t fla
 int lg_posegraph_solve(const lg_posegraph_io* io, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Global poses with an iterative solver for both stages: preconditioned conjugate gradients with the (block-)Jacobi preconditioner, matrix-free (neither
+ * system is formed: both are operators over the images' adjacency lists), fp64, for up to LG_BA_PCG_MAX_IMAGES images.  lg_posegraph_solve is unchanged in
+ * every bit, message and refusal; this is a second entry point whose io holds lg_posegraph_io as `base`.  tests/posegraph_pcg_oracle.py restates it in
+ * float64 numpy.  Everything outside the two linear solves is lg_posegraph_solve's definition, word for word: pair and image states, the adjacency and its
+ * order, the tree, log / exp, the weights and their schedules, the baseline, the peeling, the direction, the stage-convergence tests (1e-10 / 1e-12) and the
+ * outputs.
+ * History: added to ABI 0.6 without a version bump; the addition is backward compatible (no existing struct, flag, refusal or formula changed).
+ *   list sum  THE order of every sum over an image's list below: the entries that take part keep their positions e = 0, 1, .. in the sorted list (an entry
+ *             that does not take part adds nothing); partial l, l < 64, = the sum of the terms at positions l, l + 64, l + 128, .. ascending, started at 0;
+ *             then for h = 32, 16, .. 1: partial l += partial l + h for every l < h; the result is partial 0.  A vector or block is summed entry by entry.
+ *   free      rotation stage: an image of the origin's component other than the origin.  Position stage: an image that gets a position other than the
+ *             origin and the baseline.  An image that is not free has no unknowns: its entries of r, z, p, q, x are 0 and are never read as anything else.
+ *   rotation stage, iteration it.  Per pair of state 0: omega and w' of lg_posegraph_solve, and the vector w' omega (each entry w' x omega_r).  Per free
+ *             image i: D_i = the list sum of w'; b_i = the list sum of +(w' omega) where i is the pair's b, -(w' omega) where it is its a.  The unknown
+ *             is the 3-vector delta_i per free image; operator q_i = D_i p_i - (the list sum of w'_p p_j over the entries (j, p)), each entry of q_i
+ *             D_i p_i[r] less the sum; preconditioner z_i = (1 / D_i) r_i (the reciprocal is formed once).  x0 = 0, r = b.  R_i <- R_i exp(x_i).
+ *   position stage, iteration it.  Per pair of state 0: M = (w rho)(I - d d^T) as six entries (lg_posegraph_solve's rho, schedule and block).  Per free
+ *             image i: D_i = the list sum of M; b_i = the list sum of M c_baseline over the entries whose neighbour is the baseline; t_i = the list sum of
+ *             M c_j over all other entries, c_j the current centre (0 for the origin).  M v: each row (m0 v0 + m1 v1) + m2 v2.  Operator q_i = D_i p_i
+ *             - (the list sum of M p_j).  Preconditioner z_i = Di_i r_i (rows as above) with Di_i = D_i^-1 column by column by the 3 x 3 elimination of
+ *             lg_triangulate (partial pivoting; a pivot must exceed 1e-12 x the block's largest diagonal entry).  A block that fails it, in ANY position
+ *             iteration, clears positions_ok like the dense path's failed pivot, and the position stage ends there (the centres keep their last values;
+ *             the iteration is counted).  Collinear cameras give blocks of rank 2 up to rounding and are caught here.
+ *             Warm start: the system is solved for the centres themselves, so x0 = the current centres (0 at iteration 0) and
+ *             r_i = b_i - (D_i c_i - t_i).  Started from 0 at cg_tolerance 1e-6 the poses sit up to 5e-6 from the dense definition, warm-started 2e-11.
+ *   dot       a.b = per image d_k = (a0 b0 + a1 b1) + a2 b2 (0 for an image that is not free), then lg_bundle_adjust_pcg's fold of the images' d_k
+ *             (256 partials, a halving tree).
+ *   PCG       lg_bundle_adjust_pcg's recurrence and stopping rule: z = M r, p = z, rz0 = rz = r.z with r the (warm-started) residual.  rz0 = 0 ends the
+ *             solve at once with x = x0.  Step i = 1, 2, ..: q = A p; pq = p.q; alpha = rz / pq; x += alpha p; r -= alpha q; z = M r; rz' = r.z.  The
+ *             solve ends on the tolerance iff sqrt(rz') <= cg_tolerance sqrt(rz0), else on the budget iff i = the stage's budget; otherwise
+ *             beta = rz' / rz, p = z + beta p, rz = rz'.  A pq that is not finite and > 0, or an rz0 / rz' that is not finite and >= 0, is a failed
+ *             recurrence: in the rotation stage the solve ends with the step taken so far (which is applied), in the position stage it clears
+ *             positions_ok and ends the stage like a failed block.  Either is counted in summary 6.
+ *   update    when a solve ends: the rotations or centres of the free images take x, and the stage's iteration counter, largest step and convergence are
+ *             lg_posegraph_solve's.
+ *   stopping  both budgets are fixed like num_iterations: every launch of every solver iteration of every iteration of both stages is enqueued
+ *             unconditionally; "this solve is done" is a field of the device record that only the single-workgroup step kernel writes, and once it is
+ *             set, or the stage has ended, the remaining launches return at once.
+ *   outputs   those of lg_posegraph_solve; summary [12]: the eight values of lg_posegraph_solve with 6 = failed recurrences, then 8 = rotation solver
+ *             iterations run over the call, 9 = position solver iterations run, 10 = rotation solves that ended on the budget, 11 = position solves that
+ *             ended on the budget.
+ *   Documented difference: positions_ok = 0 is reported only for a missing baseline, a failed 3 x 3 block and a failed recurrence.  A view graph whose
+ *             position system the dense path calls singular by its pivot floor is NOT recognised: an iterative solve has no pivot to test.  On 1 100 images
+ *             with 3 300 pairs (3 per image) the dense definition fails a pivot and returns positions_ok = 0; this solver converges (up to 918 solver
+ *             iterations in one solve) to centres 4.35 x the scene's extent off.  With 8 pairs per image (1 100 / 8 800, 600 / 4 800) both definitions
+ *             pose every image and agree (centre error 0.25 - 0.29 % of the extent).  The caller's signals are direction_error and summary 10 / 11.
+ *   Determinism: as lg_posegraph_solve: no floating-point atomics, every sum a fixed function of the lists' order and the image index.
+ * Workspace: lg_posegraph_pcg_workspace_bytes bytes (-1 outside the envelope), 256-byte aligned, every piece rounded up to 256 bytes: that of
+ *   lg_posegraph_solve without the dense system, plus a 256-byte record, 48 bytes per pair (w' and w' omega, or M) and 256 bytes per image (r, z, p, q, x:
+ *   5 x 24; D: 48; D^-1: 72; the image's partials of p.q and r.z: 2 x 8): 512 + 372 images + 4 + 100 pairs before the rounding.
+ * Envelope (LG_ERR_INVALID with a message that names the field, before the GPU is touched), in this order: null io; any flag bit; images outside
+ *   [2, LG_BA_PCG_MAX_IMAGES]; pairs outside [1, 2^20]; lg_posegraph_solve's settings (num_iterations, origin, baseline, the scales); rotation_cg_iterations
+ *   outside [1, LG_BA_PCG_MAX_CG_ITERATIONS]; position_cg_iterations likewise; cg_tolerance not in (0, 1) (NaN included); num_iterations x
+ *   (rotation_cg_iterations + position_cg_iterations) above LG_BA_PCG_MAX_SOLVER_ITERATIONS (the call enqueues that many solver iterations); a null required
+ *   pointer; the workspace.
+ * Launches, none of which waits on another workgroup: clear, classify, scan, fill, sort and output are lg_posegraph_solve's; tree and select are ONE workgroup
+ *   of 1 024 threads with the images strided over the lanes (the same decisions); per iteration of a stage pairs (one lane per pair), setup (one wave per
+ *   image: D, D^-1, b, the warm-started r, z, p, its partial of r.z) and, budget times, operator (one wave per image: q and its partial of p.q) and step (ONE
+ *   workgroup: the dots, alpha, beta, x, r, z, p, the record, and the stage's update when the solve ends); last one lane writes summary 6 and 8 .. 11.
+ *   9 + 2 n (2 + rotation_cg_iterations + position_cg_iterations) in all. */
+typedef struct lg_posegraph_pcg_io {
+    lg_posegraph_io base;                  /* base.workspace: lg_posegraph_pcg_workspace_bytes; base.summary: [12]    */
+    int32_t rotation_cg_iterations;        /* per rotation iteration, in [1, LG_BA_PCG_MAX_CG_ITERATIONS]             */
+    int32_t position_cg_iterations;        /* per position iteration, in [1, LG_BA_PCG_MAX_CG_ITERATIONS]             */
+    double cg_tolerance;                   /* in (0, 1)                                                               */
+} lg_posegraph_pcg_io;
+int64_t lg_posegraph_pcg_workspace_bytes(int64_t images, int64_t pairs, uint32_t flags);
+/* Enqueue the whole call on `hip_stream`: asynchronous, no allocation, no host synchronisation. */
+int lg_posegraph_solve_pcg(const lg_posegraph_pcg_io* io, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Global positioning: the camera centres of the free images and the points of all tracks, solved jointly from the viewing rays of every observation, with
  * the rotations kept as they come in (from lg_posegraph_solve, say) and at least two images held to fix origin, orientation and scale.  It replaces the
  * positions that averaging the pairs' translation directions gives: a track ties many rays to one point, a pair carries one direction.  The points come with

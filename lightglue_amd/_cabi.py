@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "lg_bundle_workspace_bytes", "lg_bundle_adjust", "lg_bundle_robust_workspace_bytes", "lg_bundle_adjust_robust", "lg_bundle_focal_workspace_bytes", "lg_bundle_adjust_focal",
     "lg_bundle_pcg_workspace_bytes", "lg_bundle_adjust_pcg",
     "lg_posegraph_workspace_bytes", "lg_posegraph_solve",
+    "lg_posegraph_pcg_workspace_bytes", "lg_posegraph_solve_pcg",
     "lg_positioning_workspace_bytes", "lg_positioning_solve",
 )
 
@@ -206,6 +207,11 @@ class LgPosegraphIO(C.Structure):
         ("workspace", _fp), ("workspace_bytes", C.c_int64),
         ("poses", _fp), ("image_state", _fp), ("pair_state", _fp), ("rotation_error", _fp), ("direction_error", _fp), ("summary", _fp),
     ]
+
+
+class LgPosegraphPcgIO(C.Structure):
+    """lg_posegraph_pcg_io (include/lightglue_amd.h): one call of the global pose estimator with the iterative solver"""
+    _fields_ = [("base", LgPosegraphIO), ("rotation_cg_iterations", C.c_int32), ("position_cg_iterations", C.c_int32), ("cg_tolerance", C.c_double)]
 
 
 class LgPositioningIO(C.Structure):
@@ -415,6 +421,9 @@ def load() -> C.CDLL:
     lib.lg_posegraph_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
     lib.lg_posegraph_workspace_bytes.restype = C.c_int64
     lib.lg_posegraph_solve.argtypes = [C.POINTER(LgPosegraphIO), C.c_void_p]
+    lib.lg_posegraph_pcg_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32]
+    lib.lg_posegraph_pcg_workspace_bytes.restype = C.c_int64
+    lib.lg_posegraph_solve_pcg.argtypes = [C.POINTER(LgPosegraphPcgIO), C.c_void_p]
     lib.lg_positioning_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_uint32]
     lib.lg_positioning_workspace_bytes.restype = C.c_int64
     lib.lg_positioning_solve.argtypes = [C.POINTER(LgPositioningIO), C.c_void_p]

@@ -621,7 +621,7 @@ template <int LOSS, bool FOCAL> __global__ __launch_bounds__(BA_THREADS) void ba
 // BaPcgHead (the call's first setup launch clears it), and once `done` names the running Levenberg-Marquardt iteration (or the trial has failed, or the call converged) the rest return at once.
 // The bodies of the trial pose and of the track's sum of W^T p stand here a second time, next to ba_backsolve_kernel's and ba_trial_points_kernel's: called
 // from those kernels as shared device functions they changed the kernels' instruction streams, which this file keeps (profiles/bundle_adjust_pcg.md)
-constexpr int PCG_THREADS = 64, PCG_STEP_THREADS = 1024, PCG_PARTIALS = 256;        // setup and images: one wave per image, a tile is 64 rows
+constexpr int PCG_THREADS = 64, PCG_STEP_THREADS = 1024, PCG_PARTIALS = IMAGE_SUM_PARTIALS;      // setup and images: one wave per image, a tile is 64 rows; the dots: image_sum (lg_solver_steps.h)
 constexpr int PCG_NT = 21, PCG_SUMS = 2 * PCG_NT + 12;                               // E_aa's lower triangle, U's upper triangle, g, the sum of W y
 
 struct BaPcgHead { double rz, rz0; int done, cg_total, unconverged, pad; };          // done: 1 + the Levenberg-Marquardt iteration (counted over the call) whose solve ended
@@ -878,24 +878,6 @@ template <int LOSS> __global__ __launch_bounds__(PCG_THREADS) void ba_pcg_images
     }
 }
 
-// the images' partials d [images] added in THE fixed order: partial m < 256 = d[m] + d[m + 256] + .. ascending from 0, then a halving tree over the partials.
-// All PCG_STEP_THREADS threads call it; d may have been written by this workgroup before the call
-__device__ __forceinline__ double pcg_sum_images(const double* d, int images, double* part) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    if (t < PCG_PARTIALS) {
-        double s = 0.0;
-        for (int k = t; k < images; k += PCG_PARTIALS) s += d[k];
-        part[t] = s;
-    }
-    __syncthreads();
-    for (int h = PCG_PARTIALS / 2; h >= 1; h >>= 1) {
-        if (t < h) part[t] += part[t + h];
-        __syncthreads();
-    }
-    return part[0];
-}
-
 // ONE workgroup, solver iteration `it` of Levenberg-Marquardt iteration `lm`: p.q, alpha, x, r, z = M r, r.z, the stopping test, beta, p; the record; when the
 // solve ends the trial poses (ba_backsolve_kernel's).  Strided loops over the images, no per-image LDS array
 __global__ __launch_bounds__(PCG_STEP_THREADS) void ba_pcg_step_kernel(BaPcgArgs a, int lm, int it) {
@@ -904,17 +886,17 @@ __global__ __launch_bounds__(PCG_STEP_THREADS) void ba_pcg_step_kernel(BaPcgArgs
     BaPcgHead& h = *a.ph;
     if (pcg_idle(a, lm)) return;
     const int s = a.head->sel;
-    double rz = h.rz, rz0 = h.rz0;                          // (read by all before lane 0 writes them again, behind the barriers of pcg_sum_images)
+    double rz = h.rz, rz0 = h.rz0;                          // (read by all before lane 0 writes them again, behind the barriers of image_sum)
     bool end = false, bad = false;
     if (it == 0) {
-        rz = rz0 = pcg_sum_images(a.rz, a.images, part);
+        rz = rz0 = image_sum(a.rz, a.images, part);
         if (t == 0) { h.rz = rz; h.rz0 = rz0; }
         if (!(isfinite(rz) && rz >= 0.0)) bad = true;
         else if (rz == 0.0) end = true;                     // b = 0 (no free image among them): x = 0
     }
     double rz_new = rz;
     if (!bad && !end) {
-        const double pq = pcg_sum_images(a.pq, a.images, part);
+        const double pq = image_sum(a.pq, a.images, part);
         if (!(isfinite(pq) && pq > 0.0)) bad = true;
         else {
             const double alpha = rz / pq;
@@ -932,7 +914,7 @@ __global__ __launch_bounds__(PCG_STEP_THREADS) void ba_pcg_step_kernel(BaPcgArgs
                 for (int e = 0; e < 6; ++e) { z[e] = pcg_row(a.M + (long long)k * 36, e, r); a.z[at + e] = z[e]; }
                 a.rz[k] = pcg_dot6(r, z);
             }
-            rz_new = pcg_sum_images(a.rz, a.images, part);
+            rz_new = image_sum(a.rz, a.images, part);
             if (t == 0) h.cg_total += 1;
             if (!(isfinite(rz_new) && rz_new >= 0.0)) bad = true;
             else {

@@ -296,6 +296,36 @@ inline const char* pg_settings_error(long long images, long long num_iterations,
         return "rotation_scale, max_rotation_error and direction_scale must be > 0 (and finite)";
     return nullptr;
 }
+// lg_posegraph_solve_pcg: lg_posegraph_solve's layout without S and with the image bound LG_BA_PCG_MAX_IMAGES, then a 256-byte record of the solver; per
+// pair six fp64 (w' and w' omega, or the six entries of M: 48 bytes); per image r, z, p, q, x (5 x 24 bytes), D (48), D^-1 (72) and its partials of p.q
+// and r.z (2 x 8): 256 bytes.  Bytes: 512 + 116 images + 4 + 100 pairs + 256 images, every piece rounded up to 256 bytes
+struct PgPcgLayout { PgLayout base; long long head, pm, r, z, p, q, x, D, Di, pq, rz, total; };
+inline const char* pg_pcg_layout(long long images, long long pairs, uint32_t flags, PgPcgLayout& L) {
+    if (flags & ~PG_KNOWN_FLAGS) return "undefined flag bits (the pose-graph solver defines none)";
+    if (images < 2 || images > LG_BA_PCG_MAX_IMAGES) return "images must lie in [2, LG_BA_PCG_MAX_IMAGES]";
+    if (pairs < 1 || pairs > PG_MAX_PAIRS) return "pairs must lie in [1, 2^20]";
+    PgLayout& B = L.base;
+    Bump bp;
+    B.head = bp.take(256); B.rot = bp.take(images * 72); B.cen = bp.take(images * 24);
+    B.level = bp.take(images * 4); B.present = bp.take(images * 4); B.acount = bp.take(images * 4); B.aoff = bp.take((images + 1) * 4); B.acur = bp.take(images * 4);
+    B.pstate = bp.take(pairs * 4); B.perr = bp.take(pairs * 8); B.dir = bp.take(pairs * 24); B.adj = bp.take(pairs * 16);
+    B.S = bp.used; B.total = bp.used;                       // no S
+    L.head = bp.take(256); L.pm = bp.take(pairs * 48);
+    L.r = bp.take(images * 24); L.z = bp.take(images * 24); L.p = bp.take(images * 24); L.q = bp.take(images * 24); L.x = bp.take(images * 24);
+    L.D = bp.take(images * 48); L.Di = bp.take(images * 72); L.pq = bp.take(images * 8); L.rz = bp.take(images * 8); L.total = bp.used;
+    return nullptr;
+}
+// the solver's own settings, refused in this order; the product counts the solver iterations the call enqueues
+inline const char* pg_pcg_settings_error(long long num_iterations, long long rotation_cg_iterations, long long position_cg_iterations, double cg_tolerance) {
+    if (rotation_cg_iterations < 1 || rotation_cg_iterations > LG_BA_PCG_MAX_CG_ITERATIONS)
+        return "rotation_cg_iterations must lie in [1, LG_BA_PCG_MAX_CG_ITERATIONS]";
+    if (position_cg_iterations < 1 || position_cg_iterations > LG_BA_PCG_MAX_CG_ITERATIONS)
+        return "position_cg_iterations must lie in [1, LG_BA_PCG_MAX_CG_ITERATIONS]";
+    if (!(cg_tolerance > 0.0 && cg_tolerance < 1.0)) return "cg_tolerance must lie in (0, 1)";
+    if (num_iterations * (rotation_cg_iterations + position_cg_iterations) > LG_BA_PCG_MAX_SOLVER_ITERATIONS)
+        return "num_iterations x (rotation_cg_iterations + position_cg_iterations) must not exceed LG_BA_PCG_MAX_SOLVER_ITERATIONS";
+    return nullptr;
+}
 // lg_positioning_solve: a 256-byte record of the call; per image a 128-byte record (camera, rotation, held centre), its flags (4) and its centre twice in fp64
 // (48); the position system with its right-hand side row, (3 images + 1) x 3 images fp64; per node its track-list entry and that entry's image (8), its ray
 // (24) and its weight (8); per track five int32 (count, offset, cursor, state, reached) and fifteen fp64 (the point, Vi, g: 120 bytes)

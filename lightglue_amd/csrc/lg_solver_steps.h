@@ -1,5 +1,6 @@
 // lightglue_amd — THE steps the track and pose-graph solvers share (lg_bundle.hip, lg_positioning.hip, lg_posegraph.hip), each written once: the track lists
-// (listed / scan / fill / sort), exp of a rotation vector, and the ray block rho (I - v v^T) with its product, angle and reweighting.  Device bodies in the
+// (listed / scan / fill / sort), exp of a rotation vector, the ray block rho (I - v v^T) with its product, angle and reweighting, and the image dot of the
+// two iterative solvers (image_sum).  Device bodies in the
 // pattern of lg_cholesky.h: the callers' kernels are thin wrappers that keep their names, launch shapes and argument blocks.  The track steps are templates on
 // the argument block A, which names tracks, nodes, n, track_id, node_state, list, limg, tcnt, toff, tcur (BaArgs and PosArgs do).  Static indices only.
 #pragma once
@@ -106,6 +107,26 @@ __device__ __forceinline__ double ray_angle(const double* v, const double (&e)[3
 __device__ __forceinline__ double ray_weight(const double* v, const double (&e)[3], double s) {
     const double ee = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2], q = ray_angle(v, e) / s;
     return 1.0 / fmax(ee, 1e-12) / (1.0 + q * q);
+}
+
+// ------------------------------------------------------------------ the image dot of the iterative solvers (lg_bundle_adjust_pcg, lg_posegraph_solve_pcg)
+// the images' partials d [images] added in THE fixed order: partial m < 256 = d[m] + d[m + 256] + .. ascending from 0, then a halving tree over the partials.
+// Every thread of the (single) workgroup calls it, part holds IMAGE_SUM_PARTIALS doubles; d may have been written by this workgroup before the call
+constexpr int IMAGE_SUM_PARTIALS = 256;
+__device__ __forceinline__ double image_sum(const double* d, int images, double* part) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    if (t < IMAGE_SUM_PARTIALS) {
+        double s = 0.0;
+        for (int k = t; k < images; k += IMAGE_SUM_PARTIALS) s += d[k];
+        part[t] = s;
+    }
+    __syncthreads();
+    for (int h = IMAGE_SUM_PARTIALS / 2; h >= 1; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    return part[0];
 }
 
 }  // namespace lg
